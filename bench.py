@@ -17,7 +17,9 @@ are fetched before it is given its next batch.  Frames are independent, so with 
 GPUs every rank processes its own frames (weak scaling, no collective on the data
 path); the timed region is bracketed by a barrier + device sync and the MAX over
 ranks is taken.  `detail.resident_fps` is the same loop without the per-step
-upload (points resident in HBM).
+upload (points resident in HBM).  `--dump-outputs DIR` writes the detections of
+the last timed step as DIR/<name>.npy; the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 
 The JSON line also carries
   roofline      the dominant kernel (largest share of GPU time with ONE batch in
@@ -242,6 +244,18 @@ class Feeder:
 
 
 SETTLE_STEPS = 40   # untimed set-up before the W warm-up steps: graph capture for both input buffers, clocks, caches
+
+
+def dump_outputs(out_dir, dets, n):
+    """What the timed path hands its caller for one batch (Engine.detections: the kept detections of every frame,
+    zeros behind them, and the count per frame) as <out_dir>/<field>.npy, float32 / float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "n_dets.npy"), n.astype(np.float32))
+    for name in dets.dtype.names:
+        if name == "reserved":
+            continue
+        a = dets[name]
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
 
 
 def timed_run(feeder, steps, warmup, barrier, settle=0):
@@ -533,6 +547,9 @@ def main():
                     help="frames per GPU of the --only train leg (default: the reference's training batch, 2)")
     ap.add_argument("--only", choices=["cfgk", "train"], default=None,
                     help="run ONE secondary leg by itself and print its dict (profiling runs: one regime per trace)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the detections of the last timed step as DIR/<name>.npy "
+                         "(seeded inputs: the same arguments give the same batch, for comparing two builds)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -624,6 +641,9 @@ def main():
 
     feeder = Feeder(engines, stagings)
     elapsed = timed_run(feeder, args.steps, args.warmup, barrier, settle=SETTLE_STEPS)
+    if args.dump_outputs and rank == 0:
+        # the last step's engine holds its results until its next pass: fetched again here, outside the timed region
+        dump_outputs(args.dump_outputs, *engines[(feeder.i - 1) % len(engines)].detections())
     elapsed = pp.frame_shard.max_over_ranks(elapsed, dist, comm_dev)
     counts = pp.frame_shard.gather_counts(B * args.steps, dist, comm_dev)
     ms_per_step = elapsed / args.steps * 1e3
