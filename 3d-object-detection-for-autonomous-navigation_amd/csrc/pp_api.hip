@@ -64,6 +64,10 @@ struct pp_engine {
     int cache_budget_mb = 256;            // run_backbone's frame sub-ranges (pp_set_cache_budget; 0 = off)
     bool vox_ahead = false;               // the resident batch was voxelised at upload time (pp_detect_async skips it)
     bool prevox_issued = false;           // a voxeliser launch is (or was) queued on the copy stream: a main-stream one waits for ev_up
+    // ... and the other direction: a voxeliser launch is (or was) queued on the main stream (the zero-copy, synchronous and
+    // device feeds, PP_PREVOX=0, profiling, the stage call, training), so the next copy-stream one waits for ev_vox_main
+    bool main_vox_pending = false;
+    hipEvent_t ev_vox_main = nullptr;     // recorded on the main stream (outside any capture) by that wait
     int results_buf = 0;                  // set the last pp_detect_async read (pp_fetch_intermediates)
     hipStream_t copy_stream = nullptr;   // the device's shared upload stream (not owned by the handle)
     hipEvent_t ev_up = nullptr;           // recorded on the copy stream behind an asynchronous upload
@@ -439,12 +443,13 @@ int run_voxelize(pp_engine* e, int batch, int max_n, hipStream_t vs = nullptr) {
         // the voxeliser's scratch (cells, keys, indices) exists once: a launch here must not overtake one that
         // pp_upload_points_async queued on the copy stream
         if (e->prevox_issued) { HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_up, 0)); e->prevox_issued = false; }
+        e->main_vox_pending = true;
     }
     const bool lds_first = voxel_first_in_lds(max_n, e->ncell, e->cfg.max_voxels);
     int* d_first = lds_first ? nullptr : e->d_first;
     if (!lds_first) {
-        ProfScope ps(e, "memset_first", true);
-        HIPCHK(e, hipMemsetAsync(e->d_first, 0x7f, (size_t)batch * e->ncell * sizeof(int), vs));
+        ProfScope ps(e, "k_fill_first");   // (0x7f7f7f7f: the bytes the memset of rounds 1-4 wrote)
+        launch_fill_first(e->d_first, 0x7f7f7f7f, (long long)batch * e->ncell, vs);
     }
     {
         ProfScope ps(e, "k_cell_first");   // also clears the cell map
@@ -562,12 +567,26 @@ int run_backbone(pp_engine* e, int batch) {
         size_t j = i;
         int sub = batch;
         if (sub_on && e->layers[i].kind == LAYER_SEP) {
-            double per_frame = 0.0;          // bytes of the largest (input + output) map pair of the run, per frame
+            // The two activation buffers ping-pong, so layers i+1, i+3, ... write the buffer that holds the run's input:
+            // walked sub-range by sub-range, L(i+1) of frames [f0, f0 + nb) writes [f0, f0 + nb) * its output bytes per
+            // frame while L(i) has yet to read frames f0 + nb.. of that buffer at its input bytes per frame.  A layer that
+            // writes more per frame than the run's first layer reads (a stride-1 block that widens the channels, or stride 2
+            // with cout > 4 cin) ends the run before it.  (The other buffer holds nothing that a later sub-range reads: each
+            // of its readers reads what the layer before wrote for the same frames; the layers after the first share one
+            // output shape, so the run's last output is not overwritten either.)
+            const LayerDesc& l0 = e->layers[i];
+            // (floats per frame of the run's input: its producer, a separable layer, writes rows of ld_out = cout = cin)
+            const size_t in0 = (size_t)l0.in_h * l0.in_w * l0.cin;
             while (j < e->layers.size() && e->layers[j].kind == LAYER_SEP) {
                 const LayerDesc& l = e->layers[j];
-                const double in_b = (j == 0 && l.d_occ != nullptr) ? 0.0 : 4.0 * l.in_h * l.in_w * l.cin;   // (the sparse canvas is not read as a map)
-                per_frame = std::max(per_frame, in_b + 4.0 * l.out_h * l.out_w * l.cout);
+                if (j > i && l.out == l0.in && (size_t)l.out_h * l.out_w * l.ld_out > in0) break;
                 ++j;
+            }
+            double per_frame = 0.0;          // bytes of the largest (input + output) map pair of the run, per frame
+            for (size_t k = i; k < j; ++k) {
+                const LayerDesc& l = e->layers[k];
+                const double in_b = (k == 0 && l.d_occ != nullptr) ? 0.0 : 4.0 * l.in_h * l.in_w * l.cin;   // (the sparse canvas is not read as a map)
+                per_frame = std::max(per_frame, in_b + 4.0 * l.out_h * l.out_w * l.cout);
             }
             const double budget = (double)sub_mb * 1048576.0;
             while (sub > 1 && per_frame * sub > budget && sub % 2 == 0) sub /= 2;
@@ -907,6 +926,7 @@ int pp_create(const pp_config* cfg, int device, pp_handle* out) {
                 e->d_feed[i] = (const PpFeed*)dp;
             }
             if (st2 == PP_OK && hipEventCreateWithFlags(&e->ev_up, hipEventDisableTiming) != hipSuccess) st2 = PP_ERR_HIP;
+            if (st2 == PP_OK && hipEventCreateWithFlags(&e->ev_vox_main, hipEventDisableTiming) != hipSuccess) st2 = PP_ERR_HIP;
             if (st2 == PP_OK && hipEventCreateWithFlags(&e->ev_tgt, hipEventDisableTiming) != hipSuccess) st2 = PP_ERR_HIP;
             for (int i = 0; i < 2 && st2 == PP_OK; ++i)
                 if (hipEventCreateWithFlags(&e->ev_read[i], hipEventDisableTiming) != hipSuccess) st2 = PP_ERR_HIP;
@@ -972,6 +992,7 @@ int pp_destroy(pp_handle e) {
     if (e->ev_in) (void)hipEventDestroy(e->ev_in);
     for (PpFeed* f : e->h_feed) if (f) (void)hipHostFree(f);
     if (e->ev_up) (void)hipEventDestroy(e->ev_up);
+    if (e->ev_vox_main) (void)hipEventDestroy(e->ev_vox_main);
     if (e->ev_tgt) (void)hipEventDestroy(e->ev_tgt);
     if (e->h_train_losses) (void)hipHostFree(e->h_train_losses);
     for (hipEvent_t ev : e->ev_read) if (ev) (void)hipEventDestroy(ev);
@@ -1243,6 +1264,14 @@ int pp_upload_points_async(pp_handle e, const float* points_pinned, const int32_
     static int prevox = -1;
     if (prevox < 0) { const char* s_ = getenv("PP_PREVOX"); prevox = (s_ && s_[0] == '0') ? 0 : 1; }
     if (prevox && e->prof <= 0 && e->train == nullptr) {
+        // The voxeliser's scratch (cells, keys, sorted indices) exists once per handle: a voxeliser queued on the main
+        // stream -- the pass in flight, if it was fed by zero-copy / pp_upload_points / pp_upload_points_device -- must
+        // be through before this one overwrites it.  Only after such a pass: copy feed after copy feed adds no wait.
+        if (e->main_vox_pending) {
+            HIPCHK(e, hipEventRecord(e->ev_vox_main, e->stream));
+            HIPCHK(e, hipStreamWaitEvent(e->copy_stream, e->ev_vox_main, 0));
+            e->main_vox_pending = false;
+        }
         if ((st = run_voxelize(e, batch, e->cur_max_n, e->copy_stream))) return st;
         e->vox_ahead = true;
         e->prevox_issued = true;
@@ -1383,6 +1412,10 @@ int pp_detect_async(pp_handle e) {
         e->up_pending = false;
         e->prevox_issued = false;
     }
+    // (a graph replay voxelises without passing run_voxelize.  A second pass over the same upload -- Engine.detect's
+    // float32 retry -- either voxelises here again, flagged the same way, or, vox_ahead, reads only the products of
+    // set in_buf, which no later copy-stream voxeliser writes before ev_read[in_buf])
+    if (!e->vox_ahead) e->main_vox_pending = true;
     // ~35 launches per batch replay as ONE graph launch: every kernel argument is a device pointer or a
     // per-(batch, max points) constant, so the captured graph is reusable until either changes (profiling
     // needs the per-launch events and uses plain launches)
@@ -1966,6 +1999,11 @@ int train_buffers(pp_engine* e) {
     // depthwise backward falls back to the shared scratch, train.hip)
     cx.gemm_part_floats = std::min<long>(std::max<long>(16l << 20, (long)B * (4l << 20)), 192l << 20);
     A1(dalloc(e, &cx.gemm_part, (size_t)cx.gemm_part_floats));
+    // PP_TRAIN_ARENA_FLOATS=n: the step uses at most n floats of it (tests: the arena-exhausted branches of train.hip).
+    // Where partial rows live and how many K slices a product gets change; what is computed does not.
+    static long arena_cap = -1;
+    if (arena_cap < 0) { const char* s_ = getenv("PP_TRAIN_ARENA_FLOATS"); arena_cap = s_ ? std::max(0l, atol(s_)) : 0; }
+    if (arena_cap > 0) cx.gemm_part_floats = std::min(cx.gemm_part_floats, arena_cap);
     if (st == PP_OK) st = ensure_loss_buffers(e);
     if (st == PP_OK) t->buffers = true;
     return st;
@@ -2045,6 +2083,7 @@ int pp_train_step_async(pp_handle e, const float* params_dev, float* grads_dev, 
         e->prevox_issued = false;
     }
     prof_reset(e);
+    e->main_vox_pending = true;    // the step voxelises on the main stream (inside its graph, too)
     // labels and regression targets travel on the copy stream (behind the points, if their upload is still queued
     // there) while voxeliser and forward pass run: the loss kernel is the first reader, the second half of the step
     // waits for ev_tgt.  (The previous step has been synchronised before it returned: nobody still reads the buffers.)

@@ -140,6 +140,8 @@ bool voxel_first_in_lds(int max_n, int ncell, int max_voxels);   // pass first =
 void launch_voxel_frame(const int* offsets, const int* cell, const int* first, int* cellmap, unsigned* keyA,
                         unsigned* idxA, unsigned* keyB, unsigned* idxB, int* pillar_start, int* pillar_cell,
                         int* npillars, int* nvalid, int batch, int max_n, int ncell, int max_voxels, hipStream_t s);
+// first[i] = v for i < n (k_voxel_frame's global-memory path: every cell "no point yet" before k_cell_first)
+void launch_fill_first(int* first, int v, long long n, hipStream_t s);
 // pts_sorted[n0 + j] = pts[n0 + sorted_idx[n0 + j]], j < nvalid[frame]: the pillar-sorted copy the PFN streams
 void launch_sort_points(const float* pts, const int* offsets, const unsigned* sorted_idx, const int* nvalid, int batch,
                         int max_n, int F, float* pts_sorted, hipStream_t s);

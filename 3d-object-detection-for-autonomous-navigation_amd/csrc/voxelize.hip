@@ -629,6 +629,21 @@ void launch_voxel_frame(const int* offsets, const int* cell, const int* first, i
 #undef VOX_LAUNCH
 }
 
+// first[i] = v, i < n: the global-memory voxeliser's "no point yet" clear (frames over 16 384 points), as a kernel rather
+// than a memset, so that a captured pass is a chain of kernel nodes only.  With the memset node, replays of the zero-copy
+// pass on the HIP runtime torch 2.10 bundles (7.0) found stale first-point indices from the third launch on: half the
+// pillars, then out-of-range stores and an illegal-address fault; the system 7.2 runtime and plain launches did not.
+__global__ __launch_bounds__(256) void k_fill_first(int* __restrict__ first, int v, long long n) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        first[i] = v;
+}
+
+void launch_fill_first(int* first, int v, long long n, hipStream_t s) {
+    if (n <= 0) return;
+    const long long blocks = std::min<long long>((n + 255) / 256, 8192);
+    PP_LAUNCH("k_fill_first", k_fill_first, dim3((unsigned)blocks), dim3(256), 0, s, first, v, n);
+}
+
 void launch_sort_points(const float* pts, const int* offsets, const unsigned* sorted_idx, const int* nvalid, int batch,
                         int max_n, int F, float* pts_sorted, hipStream_t s) {
     if (batch <= 0 || max_n <= 0) return;

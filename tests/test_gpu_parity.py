@@ -551,9 +551,9 @@ def test_bench_one_rank_under_launcher_with_rccl(hip_lib):
     assert "error" not in tr and tr["ms_per_step"] > 0 and np.isfinite(tr["last_loss"]), tr
 
 
-def _random_config(rng, B):
+def _random_config(rng, B, s23=(2, 2)):
     """A small reference-schema config drawn at random: grid, first stride, z cells, channel widths, layer counts,
-    point features, pillar capacity."""
+    point features, pillar capacity.  s23: the strides of blocks 2 and 3 (the upsample strides follow)."""
     import copy
     cfg = copy.deepcopy(pp_mod().config.pedestrian_d435i_config(B))
     s1 = int(rng.choice([1, 2]))
@@ -573,8 +573,8 @@ def _random_config(rng, B):
                                 max_number_of_points_per_voxel=int(rng.choice([5, 12, 50])),
                                 max_number_of_voxels=int(rng.choice([150, 2000])))
     s["voxel_feature_extractor"]["num_filters"] = C
-    s["rpn"].update(layer_nums=[int(rng.integers(1, 3)) for _ in range(3)], layer_strides=[s1, 2, 2],
-                    num_filters=filters, upsample_strides=[1, 2, 4], num_upsample_filters=[up] * 3)
+    s["rpn"].update(layer_nums=[int(rng.integers(1, 3)) for _ in range(3)], layer_strides=[s1, s23[0], s23[1]],
+                    num_filters=filters, upsample_strides=[1, s23[0], s23[0] * s23[1]], num_upsample_filters=[up] * 3)
     s["target_assigner"]["anchor_generators"]["anchor_generator_stride"].update(
         strides=[v * s1, v * s1, 0.0], offsets=[x0 + v * s1, y0, -1.465])
     return cfg
@@ -586,14 +586,15 @@ def pp_mod():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("seed", [101, 102, 103, 104, 105, 106, 107, 108, 109, 110])
-def test_random_small_configs_end_to_end(seed):
+@pytest.mark.parametrize("seed,s23", [pytest.param(s, (2, 2), id=str(s)) for s in range(101, 111)] +
+                         [pytest.param(s, s23, id=f"{s}-strides{s23[0]}{s23[1]}") for s, s23 in ((111, (1, 2)), (112, (2, 1)), (113, (1, 1)))])
+def test_random_small_configs_end_to_end(seed, s23):
     """Configurations the shipped YAML does not use (first stride 2, one z cell, 4 point features, narrow layers,
-    small pillar caps that trigger the max_voxels break): whole path against the oracle."""
+    small pillar caps that trigger the max_voxels break, stride-1 blocks 2 / 3): whole path against the oracle."""
     pp = pp_mod()
     rng = np.random.default_rng(seed)
     B = 2
-    cfg = _random_config(rng, B)
+    cfg = _random_config(rng, B, s23)
     eng = pp.Engine(cfg, max_batch=B, max_points_per_frame=8192)
     d = eng.d
     w = pp.weights.init_weights(d, seed=seed)

@@ -399,3 +399,64 @@ def test_decisions_tap_surface(pp, hip_lib):
           f"({ {k: v for k, v in differ.items() if v} }); smallest margin {min(v for k, v in marg.items() if not k.startswith('#')):.1e}")
     assert sum(differ.values()) <= 5          # (a handful of elements within round-off of a kink, typically none)
     tr.close()
+
+
+def _profiled_step_kernels(pp, name):
+    """names of the launches of one profiled training step of a small-grid variant, in launch order"""
+    B = 2
+    cfg = _variant(pp, name, B)
+    rng = np.random.default_rng(4)
+    frames = [rng.uniform([0, -0.64, -3], [1.6, 0.64, 3], (n, 3)).astype(np.float32) for n in (900, 400)]
+    d, labels, reg = _problem(pp, cfg, frames, 11)
+    tr = pp.Trainer(cfg, pp.weights.init_weights(d, seed=21), max_batch=B, max_points_per_frame=4096)
+    tr.engine.set_profiling(True)
+    tr.forward_backward(frames, labels, reg)
+    names = [n for n, _ in tr.engine.kernel_times()]
+    tr.close()
+    return names
+
+
+_ARENA_CHILD = """
+import json, sys
+sys.path.insert(0, "tests")
+import pp_amd as pp
+import test_gpu_train as t
+for name in ("tiny", "wide", "deep"):
+    t.test_gradients_match_autograd_small_grids(pp, None, name)
+t.test_gradients_shipped_config_batch2(pp, None)
+print("KERNELS " + json.dumps(t._profiled_step_kernels(pp, "wide")))
+"""
+
+
+def test_gradients_with_the_training_arena_exhausted(pp, hip_lib):
+    """PP_TRAIN_ARENA_FLOATS caps the split-K / deferred-reduction arena (read once per process: a child process).
+    With 4 096 floats neither depthwise backward finds room: k_tr_dw_bwd and k_tr_dw_bwd_w leave their partial rows in
+    the shared scratch, reduced by the launch right behind them (and k_tr_dw_bwd's two BatchNorm sum rows are read from
+    there by the layer before's backward), and the products keep fewer K slices (fewer deferred-reduction launches).
+    The gradients are held to the bars of the uncapped tests: three small-grid variants against torch autograd and
+    the shipped configuration against the float64 graph."""
+    import json
+    env = dict(os.environ)
+    env["PP_TRAIN_ARENA_FLOATS"] = "4096"
+    r = subprocess.run([sys.executable, "-c", _ARENA_CHILD], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    capped = json.loads(next(l for l in r.stdout.splitlines() if l.startswith("KERNELS "))[len("KERNELS "):])
+    full = _profiled_step_kernels(pp, "wide")            # this process: the whole arena
+    def reduces_after(names, k):
+        """per launch of k: how many k_tr_reduce launches follow it directly"""
+        out = []
+        for i, n in enumerate(names):
+            if n == k:
+                j = i + 1
+                while j < len(names) and names[j] == "k_tr_reduce":
+                    j += 1
+                out.append(j - i - 1)
+        return out
+    for k in ("k_tr_dw_bwd", "k_tr_dw_bwd_w"):
+        r_full, r_cap = reduces_after(full, k), reduces_after(capped, k)
+        assert r_full, (k, "the variant must run this kernel")
+        # arena exhausted: one reduce more behind every launch (its kernel-gradient rows, added at once; with room they
+        # wait for the deferred-reduction launch -- k_tr_dw_bwd's next reduce is the layer before's BatchNorm sums)
+        assert r_cap == [v + 1 for v in r_full], (k, r_full, r_cap)
+    multi_full, multi_cap = full.count("k_tr_reduce_multi"), capped.count("k_tr_reduce_multi")
+    assert multi_cap < multi_full, (multi_cap, multi_full)

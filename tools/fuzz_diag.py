@@ -19,7 +19,7 @@ def main():
     seed = int(sys.argv[1])
     rng = np.random.default_rng(seed)
     B = int(rng.choice([1, 2, 3, 5, 8, 17, 32]))
-    cfg = fz.random_config(pp, rng, B)
+    cfg = fz.random_config(pp, rng, B, fz.block_strides(seed) if "--fixed-strides" not in sys.argv else (2, 2))
     eng = pp.Engine(cfg, max_batch=B, max_points_per_frame=8192)
     d = eng.d
     w = pp.weights.init_weights(d, seed=seed)

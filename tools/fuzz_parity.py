@@ -2,7 +2,7 @@
 
     python tools/fuzz_parity.py [--seconds 300] [--seed0 1000] [--out gpurun_out/fuzz.log]
 
-Per case: a random reference-schema configuration (grid, first stride, z cells, point features, channel widths, layer
+Per case: a random reference-schema configuration (grid, block strides, z cells, point features, channel widths, layer
 counts, class count, direction head, distance feature, pillar caps, NMS sizes and thresholds), a random batch size from
 both sides of the engine's kernel selection (a handful of frames: the split-K small-map kernels; dozens: the
 persistent ones), random clouds (empty frames, points outside the range, crowded pillars).  The HIP path through the
@@ -30,7 +30,14 @@ TOL = 1e-4
 LARGE = False       # --large: KITTI-sized, mostly empty grids (the sparse first layer, the pillar-centric PFN, frame sub-ranges)
 
 
-def random_config(pp, rng, B):
+def block_strides(seed):
+    """The strides of blocks 2 and 3 for a case of the soak, each 1 or 2: drawn from a generator of their own, so that
+    a seed's other draws (and the cases the tests pin with both strides 2) stay what they were."""
+    rng = np.random.default_rng([int(seed), 23])
+    return int(rng.choice([1, 2])), int(rng.choice([1, 2]))
+
+
+def random_config(pp, rng, B, s23=(2, 2)):
     cfg = copy.deepcopy(pp.config.pedestrian_d435i_config(B))
     s1 = int(rng.choice([1, 2]))
     nx, ny = 4 * s1 * int(rng.integers(3, 14)), 4 * s1 * int(rng.integers(2, 12))
@@ -57,8 +64,8 @@ def random_config(pp, rng, B):
                                 max_number_of_voxels=int(rng.choice([150, 2000, 12000])))
     s["voxel_feature_extractor"]["num_filters"] = C
     s["voxel_feature_extractor"]["with_distance"] = bool(rng.integers(0, 3) == 0)
-    s["rpn"].update(layer_nums=[int(rng.integers(1, 4)) for _ in range(3)], layer_strides=[s1, 2, 2],
-                    num_filters=filters, upsample_strides=[1, 2, 4], num_upsample_filters=[up] * 3)
+    s["rpn"].update(layer_nums=[int(rng.integers(1, 4)) for _ in range(3)], layer_strides=[s1, s23[0], s23[1]],
+                    num_filters=filters, upsample_strides=[1, s23[0], s23[0] * s23[1]], num_upsample_filters=[up] * 3)
     s["target_assigner"]["anchor_generators"]["anchor_generator_stride"].update(
         strides=[v * s1, v * s1, 0.0], offsets=[x0 + v * s1, y0, -1.465])
     s["nms_pre_max_size"] = int(rng.choice([50, 300, 1000]))
@@ -85,10 +92,11 @@ def random_frames(rng, d, B):
     return frames
 
 
-def one_case(pp, util_ref, seed):
+def one_case(pp, util_ref, seed, wide_strides=False):
+    """wide_strides: blocks 2 and 3 draw their strides from {1, 2} (block_strides), else both are 2"""
     rng = np.random.default_rng(seed)
     B = int(rng.choice([1, 2, 3, 5, 8, 17, 32])) if not LARGE else int(rng.choice([1, 2, 4, 9]))
-    cfg = random_config(pp, rng, B)
+    cfg = random_config(pp, rng, B, block_strides(seed) if wide_strides else (2, 2))
     eng = pp.Engine(cfg, max_batch=B, max_points_per_frame=8192 if not LARGE else 20480)
     try:
         d = eng.d
@@ -160,7 +168,7 @@ def one_case(pp, util_ref, seed):
                 assert float(np.max(sc[lo_:hi_ + 1]) - np.min(sc[lo_:hi_ + 1])) <= tie, \
                     f"frame {b}: box {i} moved to {j} across scores {sc[lo_:hi_ + 1]}"
             ties += 1
-        return f"B={B} grid={d.grid[0]}x{d.grid[1]}x{d.grid[2]} C={d.pfn_filters} f={d.num_filters} L={d.layer_nums} " \
+        return f"B={B} grid={d.grid[0]}x{d.grid[1]}x{d.grid[2]} C={d.pfn_filters} f={d.num_filters} s={d.layer_strides} L={d.layer_nums} " \
                f"cls={d.num_class} dir={int(d.use_direction_classifier)} dets={ndet} maxerr={worst:.2e}" + (f" tie-order-frames={ties}" if ties else "")
     finally:
         eng.close()
@@ -174,6 +182,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--seeds", default=None, help="comma-separated seeds to run instead of the timed sweep")
     ap.add_argument("--large", action="store_true", help="KITTI-sized grids (160..496 cells a side), up to 20 000 points, batches 1..9")
+    ap.add_argument("--fixed-strides", action="store_true", help="blocks 2 and 3 at stride 2 only (the cases of earlier soaks)")
     a = ap.parse_args()
     global LARGE
     LARGE = a.large
@@ -194,7 +203,7 @@ def main():
         if todo is not None:
             seed = todo[n]
         try:
-            say(f"seed {seed}: ok  {one_case(pp, util_ref, seed)}")
+            say(f"seed {seed}: ok  {one_case(pp, util_ref, seed, wide_strides=not a.fixed_strides)}")
         except AssertionError as ex:
             bad.append(seed)
             say(f"seed {seed}: MISMATCH " + " ".join(str(ex).split())[:900])
