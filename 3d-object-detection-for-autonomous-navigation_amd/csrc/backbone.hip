@@ -134,7 +134,8 @@ struct GemmArgs {
     const float4* tr_coef;   // [cin] (sc, sh, ., .): the input map is the PRE-BatchNorm map of the layer before and the
                              // activation relu(z * sc + sh) is evaluated on the way in; NULL: the input is a tensor
     float* tr_D;             // depthwise output [M][cin], kept for the weight-gradient product (or NULL)
-    float* tr_stat;          // BatchNorm statistics partials [gridDim.x][2][n_total]: column sums / sums of squares
+    float* tr_stat;          // BatchNorm statistics partials [gridDim.x][2][n_total]: column sums / squared deviations about
+                             // the workgroup's own column means, then [gridDim.x] row counts
                              // of the output rows each workgroup produced
 };
 
@@ -789,8 +790,8 @@ __device__ __forceinline__ void fast_divmod(int n, int d, float inv_d, int& q, i
 // the pre-BatchNorm map of the layer before, activated on the way in with that layer's batch-statistics coefficients
 // (two more "tap" vectors per channel group: sc, sh; the padding comes from a NaN header -- v_max_f32(NaN, 0) = 0 -- so
 // no window element is ever masked or selected); the depthwise output is also stored (the weight-gradient product's
-// operand); the epilogue writes the raw product (this layer's pre-BatchNorm map) and the column sums / sums of squares
-// of each wave's 32 rows for the batch statistics.  PREC 1 only.
+// operand); the epilogue writes the raw product (this layer's pre-BatchNorm map) and the centred column statistics
+// of each wave's 32 rows for the batch statistics (k_tr_bn_finalize).  PREC 1 only.
 template <int NT, int S, int WPS, int PREC, int OCC = 0, int TR = 0>
 __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
     static_assert(TR == 0 || (PREC == 1 && OCC == 0), "training forward: split-precision, dense input");
@@ -810,7 +811,7 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
     constexpr int NB4 = (PREC == 0) ? (NT * G + 255) / 256 : (NT * 2 * PP_NPIECE + 255) / 256;   // 16-byte weight items per thread per chunk
     constexpr int NTILES = NT / 32;
     constexpr int KQ = KCH / 8;
-    // (TR: + the workgroup's running column sums / sums of squares, one [2][NT] row per wave)
+    // (TR: + the workgroup's running column sums / squared deviations, one [2][NT] row per wave)
     __shared__ __attribute__((aligned(16))) float smem[8 * SAW + 2 * SB + (PW ? 0 : NTAP * 256) + (TR ? 8 * NT : 0)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (a.dbg & 128) return;   // tuning aid: launch + dispatch cost only
@@ -840,8 +841,9 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
     const int first = tbase + gl;
     const int n0 = blockIdx.y * NT;
     if (first >= tend) {                               // uniform for the workgroup
-        if (TR && a.tr_stat != nullptr && tid < 2 * NT)   // its (all-zero) row of the statistics partials
+        if (TR && a.tr_stat != nullptr && tid < 2 * NT)   // its (empty) row of the statistics partials: no rows
             a.tr_stat[((size_t)blockIdx.x * 2 + tid / NT) * a.n_total + n0 + tid % NT] = 0.f;
+        if (TR && a.tr_stat != nullptr && tid == 0 && blockIdx.y == 0) a.tr_stat[(size_t)gridDim.x * 2 * a.n_total + blockIdx.x] = 0.f;
         return;
     }
     const int ntl = (tend - first + GL - 1) / GL;      // tiles of this workgroup
@@ -975,6 +977,7 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
     int ld_tile = first, ld_kc = 0;      // next position whose loads get issued
     int st_kc = 0;                       // chunk index of the next position to stage
     int mm_tile = first, mm_kc = 0;      // position the MFMAs work on
+    [[maybe_unused]] float st_n = 0.f;   // TR: rows merged into this wave's running statistics so far (wave-uniform)
     U_TILE_OFFSETS(ld_tile)
     U_LOAD_CHUNK(0)
     ld_kc = 1;                           // nchunks >= 2 (cin >= 32, checked by the launcher)
@@ -1104,17 +1107,28 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
 #define U_EPILOGUE()                                                                                     \
     {                                                                                                    \
         const int pw = mm_tile * 128 + wave * 32;                                                        \
-        if (TR) {   /* column sums of this lane's 16 rows (rows >= M are exact zeros), kept over the workgroup's tiles */ \
+        [[maybe_unused]] const int nw = min(max(a.M - pw, 0), 32);   /* the wave's valid rows of the tile */ \
+        if (TR && nw > 0) {   /* centred column statistics of the wave's 32 rows (sum, then the squared deviations \
+                                 from their mean over the valid rows), merged into the wave's running ones */   \
             _Pragma("unroll") for (int n = 0; n < NTILES; ++n) {                                         \
-                float s1 = 0.f, s2 = 0.f;                                                                \
-                _Pragma("unroll") for (int r = 0; r < 16; ++r) { const float z = acc[n][r]; s1 += z; s2 = fmaf(z, z, s2); }  \
+                float s1 = 0.f;                                                                          \
+                _Pragma("unroll") for (int r = 0; r < 16; ++r) s1 += acc[n][r];                          \
                 s1 += __shfl_xor(s1, 32);                                                                \
-                s2 += __shfl_xor(s2, 32);                                                                \
+                const float mean_ = s1 / (float)nw;                                                      \
+                float q = 0.f;                                                                           \
+                _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                         \
+                    const float dz = acc[n][r] - mean_;                                                  \
+                    if (pw + (r & 3) + 8 * (r >> 2) + 4 * h < a.M) q = fmaf(dz, dz, q);                  \
+                }                                                                                        \
+                q += __shfl_xor(q, 32);                                                                  \
                 if (h == 0) {   /* wave-private LDS row: no synchronisation (a wave's LDS operations execute in order) */ \
-                    sST[(wave * 2 + 0) * NT + n * 32 + r32] += s1;                                       \
-                    sST[(wave * 2 + 1) * NT + n * 32 + r32] += s2;                                       \
+                    float n_ = st_n, s_ = sST[(wave * 2 + 0) * NT + n * 32 + r32], m_ = sST[(wave * 2 + 1) * NT + n * 32 + r32];  \
+                    bn_chan_merge(n_, s_, m_, (float)nw, s1, q);                                         \
+                    sST[(wave * 2 + 0) * NT + n * 32 + r32] = s_;                                        \
+                    sST[(wave * 2 + 1) * NT + n * 32 + r32] = m_;                                        \
                 }                                                                                        \
             }                                                                                            \
+            st_n += (float)nw;                                                                           \
         }                                                                                                \
         if (!(dbg & 4) && pw < a.M) {                                                                    \
             const int qi = lane & 3, qj = r32 >> 2;                                                      \
@@ -1195,15 +1209,21 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
     U_MFMA(1)
     ++mm_kc;
     U_EPILOGUE()
-    if (TR && a.tr_stat != nullptr) {   // one statistics row per workgroup: [gridDim.x][2][n_total]; the four waves' sums added in a fixed order
-        __syncthreads();                               // every wave's sums are in its row
+    if (TR && a.tr_stat != nullptr) {   // one statistics row per workgroup: [gridDim.x][2][n_total]; the four waves' merged in a fixed order
+        __syncthreads();                               // every wave's statistics are in its row
         const float* red = sST;                        // [4 waves][2][NT]
-        if (tid < 2 * NT) {
-            const int which = tid / NT, col = tid % NT;
-            const float v = ((red[(0 * 2 + which) * NT + col] + red[(1 * 2 + which) * NT + col]) +
-                             red[(2 * 2 + which) * NT + col]) + red[(3 * 2 + which) * NT + col];
-            a.tr_stat[((size_t)blockIdx.x * 2 + which) * a.n_total + n0 + col] = v;
+        float wn[4] = {0.f, 0.f, 0.f, 0.f};            // the waves' row counts over the workgroup's tiles
+        for (int t = first; t < tend; t += GL)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) wn[w] += (float)min(max(a.M - (t * 128 + w * 32), 0), 32);
+        if (tid < NT) {
+            float n_ = 0.f, s_ = 0.f, m_ = 0.f;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) bn_chan_merge(n_, s_, m_, wn[w], red[(w * 2) * NT + tid], red[(w * 2 + 1) * NT + tid]);
+            a.tr_stat[((size_t)blockIdx.x * 2 + 0) * a.n_total + n0 + tid] = s_;
+            a.tr_stat[((size_t)blockIdx.x * 2 + 1) * a.n_total + n0 + tid] = m_;
         }
+        if (tid == 0 && blockIdx.y == 0) a.tr_stat[(size_t)gridDim.x * 2 * a.n_total + blockIdx.x] = ((wn[0] + wn[1]) + wn[2]) + wn[3];
     }
 #undef U_MFMA
 #undef U_STAGE

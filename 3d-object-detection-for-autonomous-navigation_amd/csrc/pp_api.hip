@@ -1980,11 +1980,12 @@ int train_buffers(pp_engine* e) {
     A1(dalloc(e, &cx.dhead_w, (size_t)s.CC * PP_HEAD_COLS)); A1(dalloc(e, &cx.dhead_b, (size_t)2 * PP_HEAD_COLS));
     A1(dalloc(e, &cx.dZ, max_z)); A1(dalloc(e, &cx.dD, max_d));
     A1(dalloc(e, &cx.part, train_part_floats(s)));
-    {   // one [2][N] row per 64-row tile of the largest forward product (per 32 rows for the fused separable launches)
+    {   // one [2][N] row (+ its row count) per 64-row tile of the largest forward product (per 32 rows for the fused
+        // separable launches)
         size_t need = 1;
         for (const LayerDesc& l : s.layers) {
-            if (l.kind == LAYER_SEP) need = std::max(need, (B * l.out_h * l.out_w + 127) / 128 * 4 * 2 * (size_t)l.cout);
-            else if (l.kind == LAYER_DECONV) need = std::max(need, ((B * l.in_h * l.in_w + 63) / 64 + 8) * 2 * (size_t)l.k * l.k * l.cout);
+            if (l.kind == LAYER_SEP) need = std::max(need, (B * l.out_h * l.out_w + 127) / 128 * 4 * (2 * (size_t)l.cout + 1));
+            else if (l.kind == LAYER_DECONV) need = std::max(need, ((B * l.in_h * l.in_w + 63) / 64 + 8) * (2 * (size_t)l.k * l.k * l.cout + 1));
         }
         A1(dalloc(e, &cx.stat_part, need));
         cx.stat_part_floats = (long)need;

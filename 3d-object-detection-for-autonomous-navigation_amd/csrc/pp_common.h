@@ -73,6 +73,20 @@ __device__ __forceinline__ int wave_inclusive_scan(int v) {
 // silently wrong boxes.  The backbone's ReLUs keep a NaN, so it reaches the head maps, where the post-process sees it
 // (bit PP_NDETS_NONFINITE of a frame's detection count -> PP_ERR_NUMERIC).
 __device__ __forceinline__ float relu_keep_nan(float x) { return (x < 0.f) ? 0.f : x; }
+// BatchNorm statistics partials are centred: (n, s, m2) = (rows, sum, sum of squared deviations about the rows' own
+// mean).  Chan et al.'s pairwise merge: (n, s, m2) += (nb, sb, m2b); an empty side (count 0) changes nothing.  The
+// deviation of the two means is what a sum of squares about zero would lose to cancellation (|mean| / std large).
+__device__ __forceinline__ void bn_chan_merge(float& n, float& s, float& m2, float nb, float sb, float m2b) {
+    if (nb <= 0.f) return;
+    if (n > 0.f) {
+        const float d = sb / nb - s / n;
+        m2 = (m2 + m2b) + d * d * (n * nb / (n + nb));
+    } else {
+        m2 = m2b;
+    }
+    n += nb;
+    s += sb;
+}
 __device__ __forceinline__ bool pp_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 #define PP_NDETS_NONFINITE (1 << 30)
 

@@ -321,30 +321,47 @@ __device__ __forceinline__ void t2_gemm_tile(const TGemm2& a2, int bx, int by, i
         }
     }
     // D[row][col]: col = lane & 31 (n), row = (reg & 3) + 8 * (reg >> 2) + 4 * h (m)
-    if (a2.stat_part != nullptr) {      // column sums of this workgroup's rows (rows >= M are zero rows of A)
+    if (a2.stat_part != nullptr) {      // centred column statistics of this workgroup's rows (rows >= M are zero rows of A)
+        // partial row by: [2][N] = (sum, sum of squared deviations about the tile's own column mean), then the row
+        // counts of all row tiles after them ([tiles] floats).  Two passes over the accumulators (registers): the
+        // sums, then the deviations from their mean -- over the valid rows only.
         __syncthreads();
-        float* red = reinterpret_cast<float*>(sA);         // [2 row-waves][2][BN]
+        float* red = reinterpret_cast<float*>(sA);         // [2 row-waves][BN] sums, then [2 row-waves][BN] deviations
+        const int nrows = min(BM, g.M - m0);
 #pragma unroll
         for (int j = 0; j < WN; ++j) {
-            float s1 = 0.f, s2 = 0.f;
+            float s1 = 0.f;
 #pragma unroll
             for (int i = 0; i < WM; ++i)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) { const float z = acc[i][j][r]; s1 += z; s2 = fmaf(z, z, s2); }
+                for (int r = 0; r < 16; ++r) s1 += acc[i][j][r];
             s1 += __shfl_xor(s1, 32);
-            s2 += __shfl_xor(s2, 32);
-            if (h == 0) {
-                const int col = wn * 32 * WN + j * 32 + r32;
-                red[(wm * 2 + 0) * BN + col] = s1;
-                red[(wm * 2 + 1) * BN + col] = s2;
-            }
+            if (h == 0) red[wm * BN + wn * 32 * WN + j * 32 + r32] = s1;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < WN; ++j) {
+            const int col = wn * 32 * WN + j * 32 + r32;
+            const float mean = (red[col] + red[BN + col]) / (float)nrows;
+            float q = 0.f;
+#pragma unroll
+            for (int i = 0; i < WM; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = m0 + wm * 32 * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const float dz = acc[i][j][r] - mean;
+                    if (m < g.M) q = fmaf(dz, dz, q);
+                }
+            q += __shfl_xor(q, 32);
+            if (h == 0) red[(2 + wm) * BN + col] = q;
         }
         __syncthreads();
         for (int e = tid; e < 2 * BN; e += 256) {
             const int which = e / BN, col = e % BN;
             if (n0 + col < g.N)
-                a2.stat_part[((size_t)by * 2 + which) * g.N + n0 + col] = red[which * BN + col] + red[(2 + which) * BN + col];
+                a2.stat_part[((size_t)by * 2 + which) * g.N + n0 + col] = red[(2 * which) * BN + col] + red[(2 * which + 1) * BN + col];
         }
+        if (bx == 0 && tid == 0) a2.stat_part[(size_t)((g.M + BM - 1) / BM) * 2 * g.N + by] = (float)nrows;
     }
 #pragma unroll
     for (int j = 0; j < WN; ++j) {
@@ -1093,11 +1110,48 @@ __global__ __launch_bounds__(256) void k_tr_colstats(const float* __restrict__ Z
     }
 }
 
-// BatchNorm statistics from the per-workgroup partial sums part[p][0/1][c] (16 lanes per channel add the partial
-// rows in a fixed order -- the reduction and the finalisation in one launch): stats[c] = (mean, 1/sqrt(var + eps))
-// with the biased batch variance; moving statistics updated in place as Keras does
+// centred BatchNorm statistics partials of Z[rows][C] (k_tr_bn_finalize's input when no product left them):
+// part[blk][0][c] = sum z, part[blk][1][c] = sum (z - blk mean)^2 over the workgroup's rows; part[nblk][2][C] + blk =
+// their count.  Two passes over the rows (the second from cache): the sums, then the deviations from their mean.
+__global__ __launch_bounds__(256) void k_tr_colstats_c(const float* __restrict__ Z, long rows, int C, float* __restrict__ part) {
+    __shared__ float s1[256], s2[256];
+    const int tid = threadIdx.x;
+    const int lanes_per_row = (C >= 256) ? 256 : C;      // C in {32, 64, 128, 256}
+    const int rsub = tid / lanes_per_row, nsub = 256 / lanes_per_row, lc = tid % lanes_per_row;
+    const long step = (long)gridDim.x * nsub;
+    for (int cb = 0; cb < C; cb += 256) {
+        const int c = cb + lc;
+        float a = 0.f, cnt = 0.f;
+        for (long r = (long)blockIdx.x * nsub + rsub; r < rows; r += step) { a += Z[(size_t)r * C + c]; cnt += 1.f; }
+        s1[tid] = a; s2[tid] = cnt;
+        __syncthreads();
+        float sum = s1[lc], n = s2[lc];
+        for (int k = 1; k < nsub; ++k) { sum += s1[lc + k * lanes_per_row]; n += s2[lc + k * lanes_per_row]; }
+        const float mean = (n > 0.f) ? sum / n : 0.f;
+        float q = 0.f;
+        for (long r = (long)blockIdx.x * nsub + rsub; r < rows; r += step) { const float dz = Z[(size_t)r * C + c] - mean; q = fmaf(dz, dz, q); }
+        __syncthreads();                                  // every thread has read the sums
+        s1[tid] = q;
+        __syncthreads();
+        if (rsub == 0) {
+            for (int k = 1; k < nsub; ++k) q += s1[tid + k * lanes_per_row];
+            part[((size_t)blockIdx.x * 2 + 0) * C + c] = sum;
+            part[((size_t)blockIdx.x * 2 + 1) * C + c] = q;
+            if (cb == 0 && c == 0) part[(size_t)gridDim.x * 2 * C + blockIdx.x] = n;
+        }
+        __syncthreads();
+    }
+}
+
+// BatchNorm statistics from centred per-workgroup partials part[p][0/1][c] = (sum, sum of squared deviations about
+// the partial's own mean) with the partials' row counts part[nparts][2][C * ntaps] + p (16 lanes per channel walk the
+// partial rows in a fixed order -- the reduction and the finalisation in one launch): stats[c] = (mean, 1/sqrt(var +
+// eps)) with the biased batch variance; moving statistics updated in place as Keras does
 // (ntaps > 1: the partial rows are [2][ntaps * C] -- a transposed convolution's GEMM columns, tap-major -- and a
 // channel's statistics run over all its taps)
+// The merge is Chan's in float64: n var = sum m2_p + sum n_p (mean_p - mean)^2, the second sum accumulated as
+// sum s_p^2 / n_p - n mean^2 -- the same quantity, whose float64 cancellation costs ~1e-16 (|mean| / std)^2; a
+// single-pass float32 sum z^2 / n - mean^2 costs ~6e-8 (|mean| / std)^2, all of the variance from |mean| / std ~ 4e3.
 // LPC lanes share a channel (16: a handful of partial rows; 64 / 256: the many row tiles of a large batch)
 template <int LPC>
 __global__ __launch_bounds__(256) void k_tr_bn_finalize(const float* __restrict__ part, int nparts, int C, float n_rows_arg,
@@ -1108,15 +1162,16 @@ __global__ __launch_bounds__(256) void k_tr_bn_finalize(const float* __restrict_
                                                         const float* __restrict__ beta, float4* __restrict__ coef) {
     const int l = threadIdx.x & (LPC - 1);
     const int c = blockIdx.x * (256 / LPC) + threadIdx.x / LPC;
-    float s1 = 0.f, s2 = 0.f;
+    double s1 = 0.0, s2 = 0.0;      // sum s_p, sum (m2_p + s_p^2 / n_p)
     if (c < C) {
         // lane l adds the (partial row, tap) pairs l, l + LPC, ... in that order, EIGHT pairs' loads in flight at a time:
         // written as "load, add, load, add" the loop waited a full memory round trip per pair (the disassembly had a
         // vmcnt(0) per iteration) and this launch -- 20 per step -- took 5.6 us at B=2 / 9 us at B=32 for ~2 us of work
         const size_t N = (size_t)C * ntaps;
+        const float* cnt = part + (size_t)nparts * 2 * N;
         const int total = nparts * ntaps;
         for (int i0 = l; i0 < total; i0 += LPC * 8) {
-            float a[8], q[8];
+            float a[8], q[8], n[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int i = i0 + k * LPC;
@@ -1127,16 +1182,22 @@ __global__ __launch_bounds__(256) void k_tr_bn_finalize(const float* __restrict_
                 const float* src = part + ((size_t)pr * 2) * N + (size_t)t * C + c;
                 a[k] = src[0];
                 q[k] = src[N];
-                if (!ok) { a[k] = 0.f; q[k] = 0.f; }
+                n[k] = cnt[pr];
+                if (!ok) n[k] = 0.f;
             }
 #pragma unroll
-            for (int k = 0; k < 8; ++k) { s1 += a[k]; s2 += q[k]; }
+            for (int k = 0; k < 8; ++k)
+                if (n[k] > 0.f) {
+                    const double ak = (double)a[k];
+                    s1 += ak;
+                    s2 += (double)q[k] + ak * ak / (double)n[k];
+                }
         }
     }
 #pragma unroll
     for (int off = (LPC > 64 ? 64 : LPC) / 2; off >= 1; off >>= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
     if (LPC > 64) {                                       // a whole workgroup per channel: the four wave sums in order
-        __shared__ float sw[2][4];
+        __shared__ double sw[2][4];
         if ((threadIdx.x & 63) == 0) { sw[0][threadIdx.x >> 6] = s1; sw[1][threadIdx.x >> 6] = s2; }
         __syncthreads();
         s1 = ((sw[0][0] + sw[0][1]) + sw[0][2]) + sw[0][3];
@@ -1144,8 +1205,9 @@ __global__ __launch_bounds__(256) void k_tr_bn_finalize(const float* __restrict_
     }
     if (c >= C || l != 0) return;
     const float n_rows = fmaxf((n_rows_dev != nullptr) ? *n_rows_dev : n_rows_arg, 1.f);   // PFN: P * T, known on the device only
-    const float mean = s1 / n_rows;
-    float var = s2 / n_rows - mean * mean;
+    const double mean64 = s1 / (double)n_rows;
+    const float mean = (float)mean64;
+    float var = (float)((s2 - s1 * mean64) / (double)n_rows);
     var = fmaxf(var, 0.f);
     const float inv = 1.0f / sqrtf(var + TR_EPS);
     stats[2 * c] = mean;
@@ -1671,10 +1733,14 @@ __device__ __forceinline__ void pfn_y(const PfnFold<CPL>& o, const PfnPt& t, con
         }                                                                                                \
     }
 
-// part[blk][0/1][c] = sums of y, y^2 over this workgroup's rows
+// centred BatchNorm partials of y over this workgroup's rows -- its pillars' T rows each, padded rows (y = 0) included:
+// part[blk][0][c] = sum y, part[blk][1][c] = sum (y - blk mean)^2, part[nblk][2][C] + blk = the rows.  Welford's update
+// per point (the row count is wave-uniform), each pillar's padded rows merged as one group of zeros, then the four
+// waves merged in order (bn_chan_merge).
 template <int CPL>
 __global__ __launch_bounds__(256) void k_tr_pfn_lin(PfnT p, float* __restrict__ part) {
     __shared__ float sp[4][2][64 * CPL];
+    __shared__ float sn[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int C = p.C;
     PfnFold<CPL> fw;
@@ -1683,9 +1749,9 @@ __global__ __launch_bounds__(256) void k_tr_pfn_lin(PfnT p, float* __restrict__ 
         pfn_load_weights<CPL>(p, lane, w);
         pfn_fold<CPL>(w, fw);
     }
-    float s1[CPL], s2[CPL];
+    float mu[CPL], m2[CPL], cnt = 0.f;
 #pragma unroll
-    for (int q = 0; q < CPL; ++q) s1[q] = s2[q] = 0.f;
+    for (int q = 0; q < CPL; ++q) mu[q] = m2[q] = 0.f;
     const int total = p.pprefix[p.batch];
     int bcur = 0;
     for (int gp = (int)blockIdx.x * 4 + wave; gp < total; gp += (int)gridDim.x * 4) {
@@ -1698,17 +1764,30 @@ __global__ __launch_bounds__(256) void k_tr_pfn_lin(PfnT p, float* __restrict__ 
             (void)j;
             float y[CPL];
             pfn_y<CPL>(fw, pt, K, y);
+            cnt += 1.f;
+            const float rc = 1.f / cnt;
 _Pragma("unroll")
-            for (int q = 0; q < CPL; ++q) { s1[q] += y[q]; s2[q] = fmaf(y[q], y[q], s2[q]); }
+            for (int q = 0; q < CPL; ++q) { const float dy = y[q] - mu[q]; mu[q] = fmaf(dy, rc, mu[q]); m2[q] = fmaf(dy, y[q] - mu[q], m2[q]); }
         })
+        const float npad = (float)(p.T - h.n);
+        if (npad > 0.f) {           // the pillar's padded rows: npad zeros
+            const float tot = cnt + npad, f = cnt * npad / tot;
+_Pragma("unroll")
+            for (int q = 0; q < CPL; ++q) { m2[q] = fmaf(mu[q] * mu[q], f, m2[q]); mu[q] *= cnt / tot; }
+            cnt = tot;
+        }
     }
 #pragma unroll
-    for (int q = 0; q < CPL; ++q) { sp[wave][0][lane * CPL + q] = s1[q]; sp[wave][1][lane * CPL + q] = s2[q]; }
+    for (int q = 0; q < CPL; ++q) { sp[wave][0][lane * CPL + q] = mu[q] * cnt; sp[wave][1][lane * CPL + q] = m2[q]; }
+    if (lane == 0) sn[wave] = cnt;
     __syncthreads();
-    for (int e = threadIdx.x; e < 2 * C; e += 256) {
-        const int which = e / C, c = e - which * C;
-        part[((size_t)blockIdx.x * 2 + which) * C + c] = ((sp[0][which][c] + sp[1][which][c]) + sp[2][which][c]) + sp[3][which][c];
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float n = 0.f, s = 0.f, q = 0.f;
+        for (int w = 0; w < 4; ++w) bn_chan_merge(n, s, q, sn[w], sp[w][0][c], sp[w][1][c]);
+        part[((size_t)blockIdx.x * 2 + 0) * C + c] = s;
+        part[((size_t)blockIdx.x * 2 + 1) * C + c] = q;
     }
+    if (threadIdx.x == 0) part[(size_t)gridDim.x * 2 * C + blockIdx.x] = ((sn[0] + sn[1]) + sn[2]) + sn[3];
 }
 
 // feat[pillar][c] = max over the T rows of relu(bn(y)) (padded rows: bn(0)); arg[pillar][c] = winning row, -1 = a padded
@@ -2085,13 +2164,13 @@ static void bn_finalize(const TrainCtx& cx, const float* part, int nparts, int C
         if (const char* e = getenv("PP_TRAIN_FIN_THR")) { long a = 0, b = 0; if (sscanf(e, "%ld,%ld", &a, &b) == 2 && a > 0 && b > 0) { thr256 = a; thr64 = b; } }
     }
     if ((long)nparts * ntaps >= thr256)
-        PP_LAUNCH("k_tr_bn_finalize", (k_tr_bn_finalize<256>), dim3(C), dim3(256), 0, cx.stream, part, nparts, C, n_rows,
+        PP_LAUNCH("k_tr_bn_finalize:256", (k_tr_bn_finalize<256>), dim3(C), dim3(256), 0, cx.stream, part, nparts, C, n_rows,
                   n_rows_dev, momentum, unbiased, stats, mmean, mvar, ntaps, gamma, beta, coef);
     else if ((long)nparts * ntaps >= thr64)
-        PP_LAUNCH("k_tr_bn_finalize", (k_tr_bn_finalize<64>), dim3((C + 3) / 4), dim3(256), 0, cx.stream, part, nparts, C, n_rows,
+        PP_LAUNCH("k_tr_bn_finalize:64", (k_tr_bn_finalize<64>), dim3((C + 3) / 4), dim3(256), 0, cx.stream, part, nparts, C, n_rows,
                   n_rows_dev, momentum, unbiased, stats, mmean, mvar, ntaps, gamma, beta, coef);
     else
-        PP_LAUNCH("k_tr_bn_finalize", (k_tr_bn_finalize<16>), dim3((C + 15) / 16), dim3(256), 0, cx.stream, part, nparts, C, n_rows,
+        PP_LAUNCH("k_tr_bn_finalize:16", (k_tr_bn_finalize<16>), dim3((C + 15) / 16), dim3(256), 0, cx.stream, part, nparts, C, n_rows,
                   n_rows_dev, momentum, unbiased, stats, mmean, mvar, ntaps, gamma, beta, coef);
 }
 
@@ -2111,14 +2190,15 @@ void col_reduce(const TrainCtx& cx, int C, float* sums, float* dup0 = nullptr, f
 // BatchNorm (training) statistics of Z[rows][C] -> stats + coefficient table, moving stats updated; with A != NULL the
 // activation relu(bn(Z)) is written too (mapped rows) -- only where somebody reads it as a tensor (the block-final
 // layers and the transposed convolutions); the in-block consumers evaluate it from Z and the table
-// stat_tiles > 0: the product that wrote Z left per-row-tile column sums in cx.stat_part ([stat_tiles][2][C * ntaps])
+// stat_tiles > 0: the product that wrote Z left centred per-row-tile partials in cx.stat_part ([stat_tiles][2][C * ntaps],
+// then the tiles' row counts)
 void bn_relu_forward(const TrainCtx& cx, const float* Z, long rows, int C, const float* gamma, const float* beta,
                      float* stats, float4* coef, float* mmean, float* mvar, float momentum, float* A, int ld, int co_off,
                      RowMap rm, int stat_tiles = 0, int ntaps = 1) {
     if (stat_tiles > 0) {
         bn_finalize(cx, cx.stat_part, stat_tiles, C, (float)rows, nullptr, momentum, 1, stats, mmean, mvar, ntaps, gamma, beta, coef);
     } else {
-        PP_LAUNCH("k_tr_colstats", k_tr_colstats, dim3(TR_NPART), dim3(256), 0, cx.stream, Z, rows, C, cx.part);
+        PP_LAUNCH("k_tr_colstats:bn", k_tr_colstats_c, dim3(TR_NPART), dim3(256), 0, cx.stream, Z, rows, C, cx.part);
         bn_finalize(cx, cx.part, TR_NPART, C, (float)rows, nullptr, momentum, 1, stats, mmean, mvar, 1, gamma, beta, coef);
     }
     if (A != nullptr)
@@ -2280,7 +2360,7 @@ int train_step(const TrainCtx& cx, const TrainShape& s, const std::vector<TrainE
             const std::string pre = "rpn/block" + std::to_string(bi + 1) + "/" + std::to_string(li);
             const long rows = (long)B * l.out_h * l.out_w;
             int stat_rows = 0;
-            if (fused && rows >= fused_min && ((rows + 127) / 128 + 8) * 2 * l.cout <= cx.stat_part_floats) {
+            if (fused && rows >= fused_min && ((rows + 127) / 128 + 8) * (2 * l.cout + 1) <= cx.stat_part_floats) {
                 SepTrainArgs t;
                 t.in = cur; t.coef = cur_coef; t.dw = L.p(pre + "/depthwise_kernel"); t.wt16 = cx.pw16 + tb.pw16_off;
                 t.Z = tb.Z; t.D = tb.D; t.stat = cx.stat_part;
@@ -2332,7 +2412,7 @@ int train_step(const TrainCtx& cx, const TrainShape& s, const std::vector<TrainE
             // 10 240 rows x 2 048 columns = 1 280 tiles of 128 x 128)
             const long wg_tiles = ((m + 127) / 128) * (long)(N / ((N % 128 == 0) ? 128 : ((N % 64 == 0) ? 64 : 32)));
             if (fused && (m >= fused_min || (fused_min > 0 && wg_tiles >= 512)) &&
-                ((m + 127) / 128 + 8) * 2 * (long)N <= cx.stat_part_floats) {
+                ((m + 127) / 128 + 8) * (2 * (long)N + 1) <= cx.stat_part_floats) {
                 static thread_local std::string tags[64];
                 std::string& tag = tags[i % 64];
                 tag = "k_sep_u_tr:deconv" + std::to_string(bi + 1);

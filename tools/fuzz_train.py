@@ -72,14 +72,27 @@ def one_case(pp, util_ref, train_ref, fuzz_parity, seed, check_decisions=False):
         # forward probe per BatchNorm layer: the batch mean / variance the step folded into the moving statistics
         after = tr.weights()
         fwd_worst = ("", 0.0)
+        rows, h, wd = {}, d.ny, d.nx                     # BatchNorm rows of the RPN layers (Keras' Bessel factor)
+        for kind, name, sh in pp.weights.layer_table(d):
+            if kind == "sep":
+                if sh["stride"] == 2:
+                    h, wd = (h + 1) // 2, (wd + 1) // 2
+                rows[name + "/bn"] = B * h * wd
+            elif kind == "deconv":
+                rows[name + "/bn"] = B * h * wd * sh["k"] * sh["k"]
         for pre, (mean, var) in stats.items():
             mom = 0.01 if pre == "pfn/bn" else 0.99
             got_mean = (after[pre + "/moving_mean"] - w[pre + "/moving_mean"] * mom) / (1 - mom)
             em = float(np.max(np.abs(got_mean - mean))) / max(float(np.max(np.abs(mean))), 1e-6)
+            # ... and the batch variance (centred partials merged in float64: DESIGN 7.1, BatchNorm statistics)
+            got_var = (after[pre + "/moving_variance"] - w[pre + "/moving_variance"] * mom) / (1 - mom)
+            if pre != "pfn/bn":
+                got_var = got_var * (rows[pre] - 1.0) / rows[pre]
+            ev = float(np.max(np.abs(got_var - var) / np.maximum(np.abs(var), 1e-6)))
             if VERBOSE:
-                print(f"    fwd {pre:36s} batch-mean rel err {em:.2e}", flush=True)
-            if em > fwd_worst[1]:
-                fwd_worst = (pre, em)
+                print(f"    fwd {pre:36s} batch-mean rel err {em:.2e}  batch-var rel err {ev:.2e}", flush=True)
+            if max(em, ev) > fwd_worst[1]:
+                fwd_worst = (pre, max(em, ev))
         got = tr.gradients()
         worst = ("", 0.0)
         for name, g in grads.items():
