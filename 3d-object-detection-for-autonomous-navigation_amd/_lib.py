@@ -18,7 +18,7 @@ _INCLUDE = os.path.join(os.path.dirname(_PKG), "include", "pp_hip.h")
 SO_PATH = os.path.join(_PKG, os.environ.get("PP_HIP_LIB", "libpp_hip.so"))
 _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
 SOURCES = ["pp_api.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
-           "rotate_iou.hip", "loss.hip", "optim.hip", "train.hip"]
+           "rotate_iou.hip", "loss.hip", "optim.hip", "train.hip", "targets.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
@@ -34,6 +34,7 @@ EXPORTS = [
     "pp_rotate_iou_eval", "pp_d3_box_overlap", "pp_head_loss", "pp_adamw_step_device",
     "pp_train_layout", "pp_train_layout_entry", "pp_train_step", "pp_train_step_async", "pp_train_step_wait",
     "pp_train_graph_stats", "pp_stream", "pp_train_fetch_decisions",
+    "pp_assign_targets", "pp_train_step_gt_async", "pp_train_step_gt",
 ]
 
 
@@ -78,6 +79,14 @@ class PPLossConfig(ctypes.Structure):
         ("norm_by_num_positives", ctypes.c_int32),
         ("encode_rad_error_by_sin", ctypes.c_int32),
         ("use_direction_classifier", ctypes.c_int32),
+    ]
+
+
+class PPTargetConfig(ctypes.Structure):
+    _fields_ = [
+        ("matched_threshold", ctypes.c_float),
+        ("unmatched_threshold", ctypes.c_float),
+        ("reserved", ctypes.c_int32 * 2),
     ]
 
 
@@ -246,6 +255,11 @@ def lib():
     L.pp_stream.argtypes = [vp, ctypes.POINTER(vp)]
     L.pp_train_graph_stats.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.pp_train_fetch_decisions.argtypes = [vp, i32, vp, i64, ctypes.POINTER(i64)]
+    L.pp_assign_targets.argtypes = [vp, f32p, vp, vp, i32, vp, ctypes.POINTER(PPTargetConfig), vp, f32p, vp, f32p]
+    L.pp_train_step_gt_async.argtypes = [vp, vp, vp, vp, f32p, vp, vp, i32, ctypes.POINTER(PPLossConfig),
+                                         ctypes.POINTER(PPTargetConfig)]
+    L.pp_train_step_gt.argtypes = [vp, vp, vp, vp, f32p, vp, vp, i32, ctypes.POINTER(PPLossConfig),
+                                   ctypes.POINTER(PPTargetConfig), f32p]
     L.pp_adamw_step_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, i64, ctypes.c_float, ctypes.c_float,
                                        ctypes.c_float, ctypes.c_float, ctypes.c_float]
     for name in EXPORTS:

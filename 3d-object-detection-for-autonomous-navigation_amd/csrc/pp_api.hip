@@ -3,7 +3,9 @@
 // kernels live in voxelize.hip / pfn.hip / anchor_mask.hip / backbone.hip /
 // postprocess.hip.  Everything runs on one HIP stream owned by the handle.
 #include <math.h>
+#include <cmath>
 #include <algorithm>
+#include <functional>
 #include <mutex>
 #include <stdarg.h>
 #include <stdio.h>
@@ -109,6 +111,15 @@ struct pp_engine {
     uint8_t* d_mask = nullptr;
     float* d_anchors = nullptr;
     int* d_cells = nullptr;
+    float4* d_anchor_near = nullptr;   // [A] nearest standing / lying box of every anchor (target assignment)
+    // target assignment from boxes (pp_assign_targets / pp_train_step_gt*), sized for max_batch x PP_MAX_GT_PER_FRAME
+    float* d_gt_boxes = nullptr;
+    int* d_gt_cls = nullptr;
+    int* d_gt_cnt = nullptr;
+    unsigned* d_gt_top = nullptr;      // per box: its best overlap (float bits), reset before every assignment
+    uint8_t* d_tmask = nullptr;        // [B][A] the assignment's anchor mask (d_mask stays the inference pass's)
+    int* d_tgt_index = nullptr;        // [B][A] optional outputs of pp_assign_targets, allocated on first use
+    float* d_tgt_overlap = nullptr;
     float* d_calib = nullptr;
     pp_detection* d_dets = nullptr;
     int* d_ndets = nullptr;
@@ -909,6 +920,12 @@ int pp_create(const pp_config* cfg, int device, pp_handle* out) {
             A1(dalloc(q, &e->d_mask, (size_t)e->B * e->A));
             A1(dalloc(q, &e->d_anchors, (size_t)e->A * 7));
             A1(dalloc(q, &e->d_cells, (size_t)e->A * 4));
+            A1(dalloc(q, &e->d_anchor_near, (size_t)e->A));
+            A1(dalloc(q, &e->d_gt_boxes, (size_t)e->B * PP_MAX_GT_PER_FRAME * 7));
+            A1(dalloc(q, &e->d_gt_cls, (size_t)e->B * PP_MAX_GT_PER_FRAME));
+            A1(dalloc(q, &e->d_gt_cnt, (size_t)e->B));
+            A1(dalloc(q, &e->d_gt_top, (size_t)e->B * PP_MAX_GT_PER_FRAME));
+            A1(dalloc(q, &e->d_tmask, (size_t)e->B * e->A));
             A1(dalloc(q, &e->d_calib, (size_t)e->B * 16));
             A1(dalloc(q, &e->d_dets, (size_t)e->B * cfg->nms_post_max_size));
             A1(dalloc(q, &e->d_ndets, (size_t)e->B));
@@ -1155,6 +1172,9 @@ int pp_set_anchors(pp_handle e, const float* anchors, const int32_t* cells, int6
     (void)hipSetDevice(e->device);
     HIPCHK(e, hipMemcpy(e->d_anchors, anchors, (size_t)num_anchors * 7 * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(e->d_cells, cells, (size_t)num_anchors * 4 * sizeof(int), hipMemcpyHostToDevice));
+    launch_anchor_near(e->d_anchors, num_anchors, e->d_anchor_near, e->stream);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipStreamSynchronize(e->stream));
     e->anchors_ready = true;
     return PP_OK;
 }
@@ -2010,6 +2030,75 @@ int train_buffers(pp_engine* e) {
     return st;
 }
 
+// ---- training targets from ground-truth boxes (targets.hip) ----
+
+// The boxes of `batch` frames as pp_assign_targets / pp_train_step_gt* take them; *total = boxes over all frames.
+int check_gt(pp_engine* e, const char* who, const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts,
+             int batch, const pp_target_config* tc, int64_t* total) {
+    if (!gt_counts || !tc) return fail(e, PP_ERR_ARG, "%s: null argument", who);
+    if (batch < 1 || batch > e->B) return fail(e, PP_ERR_ARG, "%s: batch %d outside [1, max_batch=%d]", who, batch, e->B);
+    if (!std::isfinite(tc->matched_threshold) || !std::isfinite(tc->unmatched_threshold))
+        return fail(e, PP_ERR_ARG, "%s: thresholds must be finite", who);
+    int64_t n = 0;
+    for (int b = 0; b < batch; ++b) {
+        if (gt_counts[b] < 0 || gt_counts[b] > PP_MAX_GT_PER_FRAME)
+            return fail(e, PP_ERR_ARG, "%s: frame %d has %d boxes (0..%d)", who, b, gt_counts[b], PP_MAX_GT_PER_FRAME);
+        n += gt_counts[b];
+    }
+    if (n > 0 && !gt_boxes) return fail(e, PP_ERR_ARG, "%s: gt_boxes is NULL", who);
+    for (int64_t i = 0; i < n; ++i) {
+        const float* q = gt_boxes + i * 7;
+        for (int k = 0; k < 7; ++k)
+            if (!std::isfinite(q[k])) return fail(e, PP_ERR_ARG, "%s: box %lld is not finite", who, (long long)i);
+        if (!(q[3] > 0.f && q[4] > 0.f && q[5] > 0.f))
+            return fail(e, PP_ERR_ARG, "%s: box %lld has a size <= 0 (w l h = %g %g %g)", who, (long long)i, q[3], q[4], q[5]);
+        if (gt_classes && (gt_classes[i] < 1 || gt_classes[i] > e->cfg.num_class))
+            return fail(e, PP_ERR_ARG, "%s: box %lld has class %d (1..%d)", who, (long long)i, gt_classes[i], e->cfg.num_class);
+    }
+    *total = n;
+    return PP_OK;
+}
+
+// Queues the assignment for `batch` frames on the handle's stream: the boxes go up on `up` (the copy stream: the main
+// stream then waits for ev_tgt; or the main stream itself), the anchor mask of the resident frames is built from the
+// current cell map when `resident_mask` (else d_tmask holds the caller's), the per-box maxima are reset, then the two
+// passes write d_loss_labels / d_loss_regt (and the optional per-anchor outputs).
+int enqueue_targets(pp_engine* e, int batch, const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts,
+                    int64_t total, bool resident_mask, const pp_target_config* tc, bool extra, hipStream_t up) {
+    if (total > 0) HIPCHK(e, hipMemcpyAsync(e->d_gt_boxes, gt_boxes, (size_t)total * 7 * sizeof(float), hipMemcpyHostToDevice, up));
+    if (total > 0 && gt_classes)
+        HIPCHK(e, hipMemcpyAsync(e->d_gt_cls, gt_classes, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice, up));
+    HIPCHK(e, hipMemcpyAsync(e->d_gt_cnt, gt_counts, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, up));
+    if (up != e->stream) {
+        HIPCHK(e, hipEventRecord(e->ev_tgt, up));
+        HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_tgt, 0));
+    }
+    ProfScope ps(e, nullptr);      // each launch under its own name
+    const uint8_t* mask = e->d_tmask;
+    if (resident_mask) {
+        // the integral-image kernels on this pass's cell map (the bitmap variant would trust occbits_live, which
+        // describes the last inference PFN launch); anchor_area_threshold < 0 keeps every anchor (area >= 0)
+        if (e->cfg.anchor_area_threshold >= 0.f)
+            launch_anchor_mask(e->d_cellmap, batch, e->nz, e->ny, e->nx, e->d_cells, e->A, e->cfg.anchor_area_threshold,
+                               e->d_integ, e->d_tmask, e->stream);
+        else
+            mask = nullptr;
+    }
+    {
+        ProfScope pm(e, "memset:tgt_top", true);
+        HIPCHK(e, hipMemsetAsync(e->d_gt_top, 0, (size_t)batch * PP_MAX_GT_PER_FRAME * sizeof(unsigned), e->stream));
+    }
+    TargetParams p;
+    p.batch = batch; p.A = e->A; p.anchor_near = e->d_anchor_near; p.anchors = e->d_anchors; p.mask = mask;
+    p.gt = e->d_gt_boxes; p.gt_cls = gt_classes ? e->d_gt_cls : nullptr; p.gt_cnt = e->d_gt_cnt; p.top = e->d_gt_top;
+    p.matched = tc->matched_threshold; p.unmatched = tc->unmatched_threshold;
+    p.labels = e->d_loss_labels; p.reg_targets = e->d_loss_regt;
+    p.gt_index = extra ? e->d_tgt_index : nullptr; p.overlap = extra ? e->d_tgt_overlap : nullptr;
+    launch_targets(p, e->stream);
+    HIPCHK(e, hipGetLastError());
+    return PP_OK;
+}
+
 }  // namespace
 
 int pp_head_loss(pp_handle e, const int32_t* labels, const float* reg_targets, int32_t batch,
@@ -2063,10 +2152,15 @@ int pp_train_layout_entry(pp_handle e, int32_t i, const char** name, int64_t* of
     return PP_OK;
 }
 
-int pp_train_step_async(pp_handle e, const float* params_dev, float* grads_dev, float* state_dev, const int32_t* labels,
-                        const float* reg_targets, int32_t batch, const pp_loss_config* lc) {
-    if (!e) return PP_ERR_ARG;
-    if (!params_dev || !grads_dev || !state_dev || !labels || !reg_targets || !lc)
+}  // extern "C"
+
+namespace {
+
+// pp_train_step_async and pp_train_step_gt_async: `targets` fills d_loss_labels / d_loss_regt between the two halves of
+// the step (plain stream work between the two graph replays, or between the two eager halves)
+int train_step_launch(pp_engine* e, const float* params_dev, float* grads_dev, float* state_dev, int32_t batch,
+                      const pp_loss_config* lc, const std::function<int()>& targets) {
+    if (!params_dev || !grads_dev || !state_dev || !lc)
         return fail(e, PP_ERR_ARG, "pp_train_step: null argument");
     if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_train_step_async: the step before has not been waited for");
     if (!e->anchors_ready) return fail(e, PP_ERR_STATE, "pp_train_step: anchors not set");
@@ -2085,18 +2179,6 @@ int pp_train_step_async(pp_handle e, const float* params_dev, float* grads_dev, 
     }
     prof_reset(e);
     e->main_vox_pending = true;    // the step voxelises on the main stream (inside its graph, too)
-    // labels and regression targets travel on the copy stream (behind the points, if their upload is still queued
-    // there) while voxeliser and forward pass run: the loss kernel is the first reader, the second half of the step
-    // waits for ev_tgt.  (The previous step has been synchronised before it returned: nobody still reads the buffers.)
-    // Issued AFTER the first half has been launched: a pageable source makes hipMemcpyAsync block the host, and the
-    // GPU should be busy with the forward pass by then.
-    auto upload_targets = [&]() -> int {
-        HIPCHK(e, hipMemcpyAsync(e->d_loss_labels, labels, (size_t)batch * e->A * sizeof(int32_t), hipMemcpyHostToDevice, e->copy_stream));
-        HIPCHK(e, hipMemcpyAsync(e->d_loss_regt, reg_targets, (size_t)batch * e->A * 7 * sizeof(float), hipMemcpyHostToDevice, e->copy_stream));
-        HIPCHK(e, hipEventRecord(e->ev_tgt, e->copy_stream));
-        HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_tgt, 0));
-        return PP_OK;
-    };
     pp_engine::TrainState* t = e->train;
     TrainCtx& cx = t->cx;
     cx.stream = e->stream;
@@ -2159,7 +2241,7 @@ int pp_train_step_async(pp_handle e, const float* params_dev, float* grads_dev, 
         }
         if (tg.exec != nullptr && tg.exec_bwd != nullptr) {
             HIPCHK(e, hipGraphLaunch(tg.exec, e->stream));
-            if ((st = upload_targets())) return st;
+            if ((st = targets())) return st;
             HIPCHK(e, hipGraphLaunch(tg.exec_bwd, e->stream));
             ++t->n_replays;
             launched = true;
@@ -2169,7 +2251,7 @@ int pp_train_step_async(pp_handle e, const float* params_dev, float* grads_dev, 
     if (!launched) {
         ProfScope ps(e, nullptr);
         st = enqueue(e->cur_max_n, 1);
-        if (st == PP_OK) st = upload_targets();
+        if (st == PP_OK) st = targets();
         if (st == PP_OK) st = enqueue(e->cur_max_n, 2);
     }
     if (st) return fail(e, st, "pp_train_step: configuration not supported by the training kernels");
@@ -2186,6 +2268,96 @@ int pp_train_step_async(pp_handle e, const float* params_dev, float* grads_dev, 
     e->cls_plane_live = false;
     e->train_pending = true;
     t->last_batch = batch;
+    return PP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pp_train_step_async(pp_handle e, const float* params_dev, float* grads_dev, float* state_dev, const int32_t* labels,
+                        const float* reg_targets, int32_t batch, const pp_loss_config* lc) {
+    if (!e) return PP_ERR_ARG;
+    if (!labels || !reg_targets) return fail(e, PP_ERR_ARG, "pp_train_step: null argument");
+    // labels and regression targets travel on the copy stream (behind the points, if their upload is still queued
+    // there) while voxeliser and forward pass run: the loss kernel is the first reader, the second half of the step
+    // waits for ev_tgt.  (The previous step has been synchronised before it returned: nobody still reads the buffers.)
+    // Issued AFTER the first half has been launched: a pageable source makes hipMemcpyAsync block the host, and the
+    // GPU should be busy with the forward pass by then.
+    auto upload_targets = [&]() -> int {
+        HIPCHK(e, hipMemcpyAsync(e->d_loss_labels, labels, (size_t)batch * e->A * sizeof(int32_t), hipMemcpyHostToDevice, e->copy_stream));
+        HIPCHK(e, hipMemcpyAsync(e->d_loss_regt, reg_targets, (size_t)batch * e->A * 7 * sizeof(float), hipMemcpyHostToDevice, e->copy_stream));
+        HIPCHK(e, hipEventRecord(e->ev_tgt, e->copy_stream));
+        HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_tgt, 0));
+        return PP_OK;
+    };
+    return train_step_launch(e, params_dev, grads_dev, state_dev, batch, lc, upload_targets);
+}
+
+int pp_train_step_gt_async(pp_handle e, const float* params_dev, float* grads_dev, float* state_dev, const float* gt_boxes,
+                           const int32_t* gt_classes, const int32_t* gt_counts, int32_t batch, const pp_loss_config* lc,
+                           const pp_target_config* tc) {
+    if (!e) return PP_ERR_ARG;
+    int64_t total = 0;
+    int st = check_gt(e, "pp_train_step_gt", gt_boxes, gt_classes, gt_counts, batch, tc, &total);
+    if (st) return st;
+    // the boxes follow the labels' route (copy stream, behind the first half); the anchor mask and the two assignment
+    // passes are plain launches between the halves: the backward graph reads the fixed d_loss_labels / d_loss_regt
+    auto assign = [&]() -> int {
+        return enqueue_targets(e, batch, gt_boxes, gt_classes, gt_counts, total, true, tc, false, e->copy_stream);
+    };
+    return train_step_launch(e, params_dev, grads_dev, state_dev, batch, lc, assign);
+}
+
+int pp_train_step_gt(pp_handle e, const float* params_dev, float* grads_dev, float* state_dev, const float* gt_boxes,
+                     const int32_t* gt_classes, const int32_t* gt_counts, int32_t batch, const pp_loss_config* lc,
+                     const pp_target_config* tc, float* losses) {
+    if (!e) return PP_ERR_ARG;
+    if (!losses) return fail(e, PP_ERR_ARG, "pp_train_step_gt: null argument");
+    int st = pp_train_step_gt_async(e, params_dev, grads_dev, state_dev, gt_boxes, gt_classes, gt_counts, batch, lc, tc);
+    if (st) return st;
+    return pp_train_step_wait(e, losses);
+}
+
+int pp_assign_targets(pp_handle e, const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts,
+                      int32_t batch, const uint8_t* anchors_mask, const pp_target_config* tc, int32_t* labels,
+                      float* reg_targets, int32_t* gt_index, float* overlap) {
+    if (!e) return PP_ERR_ARG;
+    if (!labels || !reg_targets) return fail(e, PP_ERR_ARG, "pp_assign_targets: null argument");
+    if (!e->anchors_ready) return fail(e, PP_ERR_STATE, "pp_assign_targets: anchors not set");
+    int64_t total = 0;
+    int st = check_gt(e, "pp_assign_targets", gt_boxes, gt_classes, gt_counts, batch, tc, &total);
+    if (st) return st;
+    if (!anchors_mask && e->cur_batch != batch)
+        return fail(e, PP_ERR_STATE, "pp_assign_targets: %d frames are resident, batch is %d (upload the frames or pass "
+                    "anchors_mask)", e->cur_batch, batch);
+    (void)hipSetDevice(e->device);
+    if ((st = ensure_loss_buffers(e))) return st;
+    const bool extra = gt_index || overlap;
+    if (extra && !e->d_tgt_index) {
+        if ((st = dalloc(e, &e->d_tgt_index, (size_t)e->B * e->A))) return st;
+        if ((st = dalloc(e, &e->d_tgt_overlap, (size_t)e->B * e->A))) return st;
+    }
+    if (anchors_mask) {
+        HIPCHK(e, hipMemcpyAsync(e->d_tmask, anchors_mask, (size_t)batch * e->A, hipMemcpyHostToDevice, e->stream));
+    } else {
+        // the resident frames' cell map: voxelised at upload time (wait for it) or here
+        if (e->up_pending || e->prevox_issued) {
+            HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_up, 0));
+            e->up_pending = false;
+            e->prevox_issued = false;
+        }
+        if (!e->vox_ahead && (st = run_voxelize(e, batch, e->cur_max_n))) return st;
+    }
+    prof_reset(e);
+    if ((st = enqueue_targets(e, batch, gt_boxes, gt_classes, gt_counts, total, anchors_mask == nullptr, tc, extra, e->stream)))
+        return st;
+    const size_t n = (size_t)batch * e->A;
+    HIPCHK(e, hipMemcpyAsync(labels, e->d_loss_labels, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(reg_targets, e->d_loss_regt, n * 7 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (gt_index) HIPCHK(e, hipMemcpyAsync(gt_index, e->d_tgt_index, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (overlap) HIPCHK(e, hipMemcpyAsync(overlap, e->d_tgt_overlap, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
     return PP_OK;
 }
 

@@ -304,3 +304,24 @@ void launch_riou_corners(const float* boxes, int64_t n, float* corners, hipStrea
 void launch_riou_pairs(const float* bc, int64_t N, const float* qc, int64_t K, int criterion, float* out, hipStream_t s);
 void launch_d3_finish(const double* boxes, int64_t N, const double* qboxes, int64_t K, int criterion,
                       const float* rinc, double* out, hipStream_t s);
+
+// targets.hip: training targets from ground-truth boxes on the device (create_target_np, load_data.py:331-532)
+struct TargetParams {
+    int batch;
+    int64_t A;                 // anchors per frame
+    const float4* anchor_near; // [A] nearest standing / lying box of every anchor (xmin, ymin, xmax, ymax)
+    const float* anchors;      // [A][7]
+    const uint8_t* mask;       // [batch][A] anchors kept per frame, or NULL: every anchor
+    const float* gt;           // [sum counts][7] x y z w l h r, the frames' boxes back to back
+    const int* gt_cls;         // [sum counts] classes 1..num_class, or NULL: all 1
+    const int* gt_cnt;         // [batch] boxes per frame (<= PP_MAX_GT_PER_FRAME)
+    unsigned* top;             // [batch][PP_MAX_GT_PER_FRAME] per box: its best overlap over the kept anchors (float bits,
+                               // zeroed before the first pass)
+    float matched, unmatched;  // thresholds (float32 compares)
+    int* labels;               // [batch][A] out
+    float* reg_targets;        // [batch][A][7] out
+    int* gt_index;             // [batch][A] out or NULL: best box per kept anchor, -1 otherwise
+    float* overlap;            // [batch][A] out or NULL: its overlap, -1 for a masked-out anchor
+};
+void launch_anchor_near(const float* anchors, int64_t A, float4* near, hipStream_t s);
+void launch_targets(const TargetParams& p, hipStream_t s);   // pass 1 (per-box maxima) + pass 2 (labels, targets)

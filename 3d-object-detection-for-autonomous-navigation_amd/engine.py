@@ -513,6 +513,77 @@ class Engine:
                     "pp_train_step_async")
         self._train_targets = (labels, reg_targets)      # the copy engine reads them while the forward pass runs
 
+    # ---- training targets from ground-truth boxes (f3, data half) ----
+    def target_config(self):
+        """The assignment's thresholds as the C-ABI struct (target_assigner.gpu_target_config: raises ValueError for a
+        configuration with positive-fraction sampling)."""
+        from .target_assigner import gpu_target_config
+        hi, lo = gpu_target_config(self.d)
+        tc = _lib.PPTargetConfig()
+        tc.matched_threshold, tc.unmatched_threshold = hi, lo
+        return tc
+
+    @staticmethod
+    def pack_gt(gt_boxes, gt_classes=None):
+        """Per-frame [G_b, 7] boxes (and [G_b] classes, or None: all 1) -> (boxes [sum G, 7] float32, classes [sum G]
+        int32 or None, counts [B] int32), the layout pp_assign_targets / pp_train_step_gt* take."""
+        boxes = [np.asarray(g, dtype=np.float32).reshape(-1, 7) for g in gt_boxes]
+        counts = np.array([len(g) for g in boxes], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(boxes, axis=0) if boxes else np.zeros((0, 7), np.float32))
+        cls = None
+        if gt_classes is not None:
+            if len(gt_classes) != len(boxes):
+                raise ValueError(f"gt_classes: {len(gt_classes)} frames, gt_boxes: {len(boxes)}")
+            parts = [np.asarray(c, dtype=np.int32).reshape(-1) for c in gt_classes]
+            for b, (c, g) in enumerate(zip(parts, boxes)):
+                if len(c) != len(g):
+                    raise ValueError(f"frame {b}: {len(g)} boxes but {len(c)} classes")
+            cls = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0,), np.int32))
+        return flat, cls, counts
+
+    def assign_targets(self, gt_boxes, gt_classes=None, anchors_mask=None):
+        """The training targets of len(gt_boxes) frames on the GPU (pp_assign_targets): target_assigner.assign as the
+        reference's loader calls it (load_data.py:3086-3101), one dict per frame with create_target_np's keys and dtypes.
+        gt_boxes: per frame [G_b, 7] x y z w l h r; gt_classes: per frame [G_b] (1..num_class) or None (all 1);
+        anchors_mask: [B, A] (bool / uint8), or None = the masks of the frames uploaded to this engine."""
+        boxes, cls, counts = self.pack_gt(gt_boxes, gt_classes)
+        B, A = len(counts), self.d.num_anchors
+        tc = self.target_config()
+        mask = None
+        if anchors_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(anchors_mask).reshape(B, A) != 0, dtype=np.uint8)
+        labels = np.empty((B, A), np.int32)
+        reg = np.empty((B, A, 7), np.float32)
+        gi = np.empty((B, A), np.int32)
+        ov = np.empty((B, A), np.float32)
+        self._check(self._lib.pp_assign_targets(self._h, _ptr(boxes), _ptr(cls), _ptr(counts), B, _ptr(mask),
+                                                ctypes.byref(tc), _ptr(labels), _ptr(reg), _ptr(gi), _ptr(ov)),
+                    "pp_assign_targets")
+        out = []
+        for b in range(B):
+            pos = np.where(labels[b] > 0)[0]
+            w = np.zeros((A,), np.float32)
+            w[pos] = 1.0
+            matched = counts[b] > 0 and bool((ov[b] >= 0).any())      # overlap -1: a masked-out anchor
+            out.append({"labels": labels[b], "bbox_targets": reg[b], "bbox_outside_weights": w,
+                        "assigned_anchors_overlap": ov[b][pos] if matched else None,
+                        "positive_gt_id": gi[b][pos].astype(np.int32), "assigned_anchors_inds": pos.astype(np.int64)})
+        return out
+
+    def train_step_gt_async(self, params_ptr, grads_ptr, state_ptr, boxes, classes, counts):
+        """train_step_async with the targets assigned on the GPU from the boxes (pp_train_step_gt_async); boxes / classes
+        / counts as pack_gt returns them (page-locked arrays: Trainer.stage_gt).  They are held here until
+        train_step_wait()."""
+        boxes = _f32(boxes).reshape(-1, 7)
+        counts = _i32(counts).reshape(-1)
+        classes = None if classes is None else _i32(classes).reshape(-1)
+        lc, tc = self.loss_config(), self.target_config()
+        self._check(self._lib.pp_train_step_gt_async(self._h, ctypes.c_void_p(int(params_ptr)),
+                                                     ctypes.c_void_p(int(grads_ptr)), ctypes.c_void_p(int(state_ptr)),
+                                                     _ptr(boxes), _ptr(classes), _ptr(counts), len(counts),
+                                                     ctypes.byref(lc), ctypes.byref(tc)), "pp_train_step_gt_async")
+        self._train_targets = (boxes, classes, counts)   # the copy engine reads them while the forward pass runs
+
     def train_step_wait(self):
         """Wait for the step train_step_async() launched; returns the reference's loss scalars."""
         losses = np.zeros(8, np.float32)

@@ -9,6 +9,9 @@ Host numpy, as in the reference (it runs in the tf.data thread, load_data.py:308
 The matching is the FAIR-detectron rule: every ground-truth box takes the anchors that tie for its best
 overlap, every anchor at or above `matched_threshold` takes its best box, anchors below
 `unmatched_threshold` are background, the rest are ignored (-1).
+
+The same assignment runs on the GPU (csrc/targets.hip: Engine.assign_targets, Trainer.step(gt_boxes=...)) for
+configurations without positive-fraction sampling; `gpu_target_config` reads its thresholds.
 """
 import numpy as np
 import numpy.random as npr
@@ -179,3 +182,19 @@ def assign(anchors, gt_boxes, anchors_mask, gt_classes, matched_thresholds, unma
                             matched_threshold=matched_thresholds, unmatched_threshold=unmatched_thresholds,
                             positive_fraction=frac, rpn_batch_size=config_target_assigner["rpn_batch_size"],
                             norm_by_num_examples=False, box_code_size=7)
+
+
+def gpu_target_config(config):
+    """(matched_threshold, unmatched_threshold) of the GPU assignment (pp_target_config) from a reference-schema config
+    dict or a config.Derived.  Raises ValueError when target_assigner.sample_positive_fraction is a number: that
+    subsampling draws from numpy's global generator, which the GPU cannot reproduce -- such a configuration stays on the
+    host path (`assign`)."""
+    cfg = getattr(config, "config", config)
+    ta = cfg["model"]["second"]["target_assigner"]
+    frac = ta.get("sample_positive_fraction")
+    if frac is not None and frac != "None":
+        raise ValueError(f"target_assigner.sample_positive_fraction = {frac!r}: the positive-fraction subsampling draws from "
+                         "numpy's global generator, which the GPU cannot reproduce; assign these targets on the host "
+                         "(target_assigner.assign) and pass labels / reg_targets")
+    ag = ta["anchor_generators"]["anchor_generator_stride"]
+    return float(ag["matched_threshold"]), float(ag["unmatched_threshold"])

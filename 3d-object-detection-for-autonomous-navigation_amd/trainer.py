@@ -2,6 +2,7 @@
 
     trainer = Trainer(config, weights, max_batch=2)            # one per GPU / rank
     out = trainer.step(frames, labels, reg_targets, dist)      # forward + loss + backward, all-reduce, AdamW
+    out = trainer.step(frames, gt_boxes=boxes, dist=dist)      # ... with the targets assigned on the GPU from the boxes
     trainer.weights()                                          # Keras-layout dict (Engine.load_weights, save_npz)
 
 What runs where: the frames are uploaded and voxelised by the engine, `pp_train_step` (csrc/train.hip) runs the
@@ -9,7 +10,9 @@ training-mode forward pass, the loss and the backward pass and leaves the gradie
 flat float32 buffer; that buffer is averaged over the ranks with ONE all-reduce (`torch.distributed`, backend
 "nccl" = RCCL over xGMI; BatchNorm statistics stay per replica, as in the single-GPU reference) and consumed by the
 AdamW kernel (csrc/optim.hip).  torch owns the flat device buffers and the communicator; no torch operator touches
-the numbers.  Labels / regression targets come from `target_assigner` (the reference's training dataloader).
+the numbers.  Labels / regression targets come either from `target_assigner` on the host (the reference's training
+dataloader) or, given the ground-truth boxes (`gt_boxes=`), from the same assignment on the GPU between the forward and
+the backward half of the step (csrc/targets.hip).
 """
 import numpy as np
 
@@ -20,13 +23,16 @@ from .engine import Engine
 class TrainBatch:
     """Page-locked staging of one training batch (Trainer.stage)."""
 
+    labels = reg_targets = None          # stage(): the dense targets
+    gt = None                            # stage_gt(): (boxes, classes or None, counts) as Engine.pack_gt lays them out
+
     def close(self):
-        for k in ("points", "_lab", "_reg"):
+        for k in ("points", "_lab", "_reg", "_gtb", "_gtc", "_gtn"):
             o = getattr(self, k, None)
             if o is not None:
                 o.close()
                 setattr(self, k, None)
-        self.labels = self.reg_targets = None
+        self.labels = self.reg_targets = self.gt = None
 
 
 class Trainer:
@@ -150,29 +156,67 @@ class Trainer:
         st.reg_targets[...] = np.asarray(reg_targets, dtype=np.float32).reshape(B, d.num_anchors, 7)
         return st
 
-    def _launch(self, frames, labels, reg_targets, prefetch):
-        """Enqueue the step (and the upload of the next batch beside it); the caller waits with engine.train_step_wait()."""
+    def stage_gt(self, frames, gt_boxes, gt_classes=None):
+        """stage() with ground-truth boxes instead of dense targets: the points as an engine Staging, the boxes (per frame
+        [G_b, 7]), their classes (per frame [G_b], or None: all 1) and the per-frame counts packed into page-locked
+        arrays (`.gt`).  The step assigns the targets on the GPU (csrc/targets.hip)."""
+        boxes, cls, counts = self.engine.pack_gt(gt_boxes, gt_classes)
+        if len(counts) != len(frames):
+            raise ValueError(f"{len(frames)} frames but boxes for {len(counts)}")
+        st = TrainBatch()
+        st.points = self.engine.staging(frames)
+        st._gtb = self.engine.pinned(boxes.shape, np.float32)
+        st._gtb.array[...] = boxes
+        st._gtn = self.engine.pinned(counts.shape, np.int32)
+        st._gtn.array[...] = counts
+        if cls is not None:
+            st._gtc = self.engine.pinned(cls.shape, np.int32)
+            st._gtc.array[...] = cls
+        st.gt = (st._gtb.array, st._gtc.array if cls is not None else None, st._gtn.array)
+        return st
+
+    def _enqueue_step(self, labels, reg_targets, gt):
+        ptrs = (self.params.data_ptr(), self.grads.data_ptr(), self.state.data_ptr())
+        if gt is not None:
+            self.engine.train_step_gt_async(*ptrs, *gt)
+        else:
+            self.engine.train_step_async(*ptrs, labels, reg_targets)
+
+    def _launch(self, frames, labels, reg_targets, prefetch, gt_boxes=None, gt_classes=None):
+        """Enqueue the step (and the upload of the next batch beside it); the caller waits with engine.train_step_wait().
+        Targets: a TrainBatch's own (stage / stage_gt), else labels / reg_targets, else gt_boxes (+ gt_classes)."""
         if isinstance(frames, TrainBatch):
             tb = frames
+            if gt_boxes is not None or gt_classes is not None:
+                raise ValueError("a TrainBatch carries its own targets")
             if self._prefetched is not tb:
                 self.engine.upload_async(tb.points)
             self._prefetched = None
-            self.engine.train_step_async(self.params.data_ptr(), self.grads.data_ptr(), self.state.data_ptr(), tb.labels,
-                                         tb.reg_targets)
+            self._enqueue_step(tb.labels, tb.reg_targets, tb.gt)
             if isinstance(prefetch, TrainBatch):
                 self.engine.upload_async(prefetch.points)
                 self._prefetched = prefetch
             return
+        gt = None
+        if gt_boxes is not None:
+            if labels is not None or reg_targets is not None:
+                raise ValueError("pass either labels / reg_targets or gt_boxes, not both")
+            gt = self.engine.pack_gt(gt_boxes, gt_classes)
+            if len(gt[2]) != len(frames):
+                raise ValueError(f"{len(frames)} frames but boxes for {len(gt[2])}")
+        elif gt_classes is not None:
+            raise ValueError("gt_classes needs gt_boxes")
         self._prefetched = None
         self.engine.upload(frames)
-        self.engine.train_step_async(self.params.data_ptr(), self.grads.data_ptr(), self.state.data_ptr(), labels, reg_targets)
+        self._enqueue_step(labels, reg_targets, gt)
 
-    def forward_backward(self, frames, labels=None, reg_targets=None, prefetch=None):
-        """frames: a list of clouds with labels / reg_targets, or one TrainBatch from stage().
+    def forward_backward(self, frames, labels=None, reg_targets=None, prefetch=None, gt_boxes=None, gt_classes=None):
+        """frames: a list of clouds with labels / reg_targets (or gt_boxes / gt_classes: the targets are then assigned
+        on the GPU), or one TrainBatch from stage() / stage_gt().
         prefetch: the TrainBatch of the NEXT step -- its points go to the GPU (the handle's other input buffer, the copy
         stream) while this step's kernels run, the loader's hand-over of train.py:228-304; pass that same batch as
         `frames` of the next call."""
-        self._launch(frames, labels, reg_targets, prefetch)
+        self._launch(frames, labels, reg_targets, prefetch, gt_boxes, gt_classes)
         return self.engine.train_step_wait()
 
     def _engine_stream(self):
@@ -206,10 +250,10 @@ class Trainer:
         self._enqueue_update(dist)
         self._engine_stream().synchronize()
 
-    def step(self, frames, labels=None, reg_targets=None, dist=None, prefetch=None):
+    def step(self, frames, labels=None, reg_targets=None, dist=None, prefetch=None, gt_boxes=None, gt_classes=None):
         """One optimizer step: forward + loss + backward, gradient exchange, AdamW -- enqueued back to back on the engine's
-        stream, ONE host wait at the end."""
-        self._launch(frames, labels, reg_targets, prefetch)
+        stream, ONE host wait at the end.  Targets as forward_backward takes them."""
+        self._launch(frames, labels, reg_targets, prefetch, gt_boxes, gt_classes)
         try:
             self._enqueue_update(dist)
         except BaseException:

@@ -13,7 +13,8 @@ numpy arrays or anything with `.numpy()` (the reference passes TF tensors).
 Training mode (model/voxelnet.py:922-1049 + train.py:265-304), `VoxelNet(config, writer, training=True)`:
     ret = net(voxels, num_points, coors, batch_anchors, labels, reg_targets)   # the reference's loss dict (scalars)
     net.apply_gradients(dist=None)        # optimizer.apply_gradients: one all-reduce over the ranks + AdamW
-or, from raw clouds, `net.train_step(frames, labels, reg_targets, dist)`.  The forward pass, the loss and the
+or, from raw clouds, `net.train_step(frames, labels, reg_targets, dist)` -- or `net.train_step(frames, gt_boxes=boxes)`,
+which assigns the targets on the GPU (the loader's target_assigner.assign, csrc/targets.hip).  The forward pass, the loss and the
 gradients of a call come from one `pp_train_step` (csrc/train.hip); the padded voxel tensor is unpadded on the
 host into the pillar-ordered point list it was built from (the voxeliser then reproduces the same pillars).
 """
@@ -85,12 +86,19 @@ class VoxelNet:
                           if len(rows) else np.zeros((0, voxels.shape[2]), np.float32))
         return frames
 
-    def train_step(self, frames, labels, reg_targets, dist=None, apply=True):
+    def train_step(self, frames, labels=None, reg_targets=None, dist=None, apply=True, gt_boxes=None, gt_classes=None):
         """Forward (training mode) + loss + backward on raw clouds; apply=True also runs the optimizer step.
-        Returns the reference's loss scalars (model/voxelnet.py:1032-1043)."""
+        Targets: exactly one of labels + reg_targets (dense, per anchor) or gt_boxes (per frame [G_b, 7], with
+        gt_classes per frame or None: all 1; assigned on the GPU).  Returns the reference's loss scalars
+        (model/voxelnet.py:1032-1043)."""
         if self.trainer is None:
             raise RuntimeError("VoxelNet(training=True): load_weights() with the initial values first")
-        out = self.trainer.forward_backward(frames, labels, reg_targets)
+        dense = labels is not None or reg_targets is not None
+        if dense == (gt_boxes is not None):
+            raise ValueError("train_step needs exactly one of labels + reg_targets or gt_boxes")
+        if dense and (labels is None or reg_targets is None):
+            raise ValueError("train_step: labels and reg_targets go together")
+        out = self.trainer.forward_backward(frames, labels, reg_targets, gt_boxes=gt_boxes, gt_classes=gt_classes)
         if apply:
             self.apply_gradients(dist)
         return out

@@ -27,7 +27,9 @@
 extern "C" {
 #endif
 
-/* 3: PP_ERR_NUMERIC, pp_set_gemm_precision / pp_get_gemm_precision, pp_set_cache_budget.  4: pp_train_fetch_decisions. */
+/* 3: PP_ERR_NUMERIC, pp_set_gemm_precision / pp_get_gemm_precision, pp_set_cache_budget.  4: pp_train_fetch_decisions;
+ * later additions within 4 (nothing before them changed): pp_target_config, pp_assign_targets, pp_train_step_gt_async,
+ * pp_train_step_gt. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -339,6 +341,44 @@ int pp_train_step(pp_handle h, const float* params_dev, float* grads_dev, float*
 int pp_train_step_async(pp_handle h, const float* params_dev, float* grads_dev, float* state_dev, const int32_t* labels,
                         const float* reg_targets, int32_t batch, const pp_loss_config* cfg);
 int pp_train_step_wait(pp_handle h, float* losses);
+
+/* ---- training targets from ground-truth boxes (SURVEY section 8f, row f3 -- data half) -------------- */
+
+/* Replaces the loader's target_assigner.assign -> create_target_np (load_data.py:3086-3101, :267-293, :331-532) with
+ * anchors pruned by the frame's anchors_mask, no positive-fraction sampling (target_assigner.sample_positive_fraction
+ * draws from numpy's global generator: that configuration stays on the host), norm_by_num_examples=False, box code
+ * size 7.  Bit-exact with the float32 numpy code (the log columns of the regression targets: within 1 ulp). */
+#define PP_MAX_GT_PER_FRAME 256
+
+/* Mirrors model.second.target_assigner.anchor_generators.anchor_generator_stride's thresholds (compared in float32). */
+typedef struct pp_target_config {
+    float matched_threshold;     /* anchor_generator_stride.matched_threshold (0.5) */
+    float unmatched_threshold;   /* ...unmatched_threshold (0.35) */
+    int32_t reserved[2];         /* 0 */
+} pp_target_config;
+
+/* Targets for `batch` frames.  gt_boxes: [sum(gt_counts), 7] x y z w l h r, the frames' boxes back to back; gt_classes:
+ * [sum(gt_counts)] (1..num_class) or NULL (all 1); gt_counts [batch], each 0..PP_MAX_GT_PER_FRAME.  anchors_mask:
+ * [batch, A] uint8, or NULL = the masks of the frames resident in the handle (voxelised on the GPU; `batch` must be the
+ * number of frames uploaded, else PP_ERR_STATE).  Outputs, [batch, A] each: labels (>0 class, 0 background, -1
+ * ignored or masked out), reg_targets [batch, A, 7] (0 where label <= 0); optional (NULL = not wanted): gt_index = the
+ * box of the anchor's best overlap (first maximum; index within the frame; -1 for a masked-out anchor or a frame
+ * without boxes) and overlap = that overlap (-1 for a masked-out anchor).  PP_ERR_ARG for a non-finite box, a size
+ * w / l / h <= 0, a class outside 1..num_class, a negative count or one above PP_MAX_GT_PER_FRAME.  Host pointers;
+ * synchronous.  The handle's fused-path results are left alone. */
+int pp_assign_targets(pp_handle h, const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts,
+                      int32_t batch, const uint8_t* anchors_mask, const pp_target_config* tc, int32_t* labels,
+                      float* reg_targets, int32_t* gt_index, float* overlap);
+/* pp_train_step_async / pp_train_step with the targets assigned on the GPU from the boxes (arguments as
+ * pp_assign_targets; the anchor masks of the resident frames): the boxes go up on the copy stream behind the first half
+ * of the step, the assignment runs between the halves.  gt_boxes / gt_classes / gt_counts must stay unchanged until
+ * pp_train_step_wait returns, which serves both entry points. */
+int pp_train_step_gt_async(pp_handle h, const float* params_dev, float* grads_dev, float* state_dev, const float* gt_boxes,
+                           const int32_t* gt_classes, const int32_t* gt_counts, int32_t batch, const pp_loss_config* lc,
+                           const pp_target_config* tc);
+int pp_train_step_gt(pp_handle h, const float* params_dev, float* grads_dev, float* state_dev, const float* gt_boxes,
+                     const int32_t* gt_classes, const int32_t* gt_counts, int32_t batch, const pp_loss_config* lc,
+                     const pp_target_config* tc, float* losses);
 
 /* The handle's HIP stream (hipStream_t as void*).  A caller that enqueues its own device work behind a pp_train_step_async
  * -- the gradient all-reduce and pp_adamw_step_device of the optimizer step (train.py:301) -- does it on this stream and
