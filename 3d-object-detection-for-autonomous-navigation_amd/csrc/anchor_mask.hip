@@ -10,8 +10,6 @@
 // from the voxeliser's cell -> pillar map.  Counts are kept in int32 (the
 // reference's float32 counts are exact integers).  HBM/L2-bound integer work:
 // 4*nz bytes read + 4 bytes written per cell, 16 B + 4 gathers + 1 B per anchor.
-#include <stdlib.h>
-
 #include "pp_common.h"
 #include "anchor_mask_dev.h"
 
@@ -117,12 +115,9 @@ void launch_anchor_mask_bits(const unsigned long long* occbits, int batch, int n
 void launch_anchor_mask(const int* cellmap, int batch, int nz, int ny, int nx, const int* cells, int64_t A,
                         float threshold, int* integ, uint8_t* mask, hipStream_t s) {
     if (batch <= 0) return;
-    static int fused = -1;      // PP_ANCHOR_MASK_FUSED=0: the three-kernel path everywhere (A/B measurements)
-    if (fused < 0) { const char* e = getenv("PP_ANCHOR_MASK_FUSED"); fused = (e && e[0] == '0') ? 0 : 1; }
-    // one workgroup per frame whenever the grid fits the LDS image; larger grids keep the three chip-wide kernels
-    static int maxb = -1;       // PP_ANCHOR_MASK_FUSED_MAXB: largest batch of the one-workgroup-per-frame kernel
-    if (maxb < 0) { const char* e = getenv("PP_ANCHOR_MASK_FUSED_MAXB"); maxb = e ? atoi(e) : (1 << 30); }   // (8 until round 3: at B=64 one launch of 64 workgroups instead of three chip-wide ones is 0-1 % more frames/s)
-    if (fused && ny * (nx | 1) <= AM_MAX_CELLS && batch <= maxb) {
+    // one workgroup per frame whenever the grid fits the LDS image, at any batch size (at B=64 one launch of 64
+    // workgroups instead of three chip-wide ones is 0-1 % more frames/s); larger grids keep the three chip-wide kernels
+    if (ny * (nx | 1) <= AM_MAX_CELLS) {
         PP_LAUNCH("k_anchor_mask_frame", k_anchor_mask_frame, dim3(batch), dim3(1024), 0, s, cellmap, nz, ny, nx, cells, A,
                   threshold, mask);
         return;

@@ -82,16 +82,13 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
 
 int g_num_cus = 256;   // set by pp_create from the device properties (persistent launches)
 
-// GEMM arithmetic: split-precision bf16 MFMA (default) or the float32 MFMA.  PP_GEMM_PREC=f32 selects the
-// latter; pp_bench_layer's ablation bits 2048 / 4096 force bf16x3 / f32.
-static bool split_precision(int ablate) {
+// GEMM arithmetic: split-precision bf16 MFMA (default) or the float32 MFMA.  PP_GEMM_PREC=f32 selects the latter.
+static bool split_precision() {
     static int dflt = -1;
     if (dflt < 0) {
         const char* e = getenv("PP_GEMM_PREC");
         dflt = (e && e[0] == 'f') ? 0 : 1;
     }
-    if (ablate & 2048) return true;
-    if (ablate & 4096) return false;
     return dflt == 1;
 }
 #define KC 32
@@ -113,8 +110,6 @@ struct GemmArgs {
     int M;                // GEMM rows (pixels) < 2^31 (checked by the launcher)
     int tile_lo;          // k_sep_u: first 128-pixel tile of this launch (a launch over the frames [f0, f1) of a batch walks
                           // the tiles [f0 * hw / 128, ceil(f1 * hw / 128)) of the whole batch's pixel space, M = f1 * hw)
-    int dbg;              // tuning aid: ablation bits (pp_bench_layer), 0 in production
-    long long* stamps;    // tuning aid (dbg & 64): [block<64][role 2][iter 40][4] shader-clock stamps
     int in_h, in_w, cin;
     int px_h, px_w;       // pixel space of M (sep: output map; deconv/head: input map)
     int stride;
@@ -145,7 +140,6 @@ template <int NTILES>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[NTILES], int p0, int n0, int wave,
                                               int lane, const int* s_opix) {
     const int h = lane >> 5, col_l = lane & 31;
-    if (a.dbg & 4) return;
     if (a.epi == 0) {
 #pragma unroll
         for (int n = 0; n < NTILES; ++n) {
@@ -373,7 +367,6 @@ __global__ __launch_bounds__(PXB * 4, (MODE == 0 && S == 2) ? 3 : 4) void k_gemm
     const int n0 = blockIdx.y * NT;
     const int cin = a.cin;
     const int nchunks = cin / KCH;
-    const int dbg = a.dbg;
 
     if (tid < PXB) {   // output pixel index per tile row (deconv: pixel of tap (0,0))
         const int pix = min(p0 + tid, a.M - 1);
@@ -420,11 +413,11 @@ __global__ __launch_bounds__(PXB * 4, (MODE == 0 && S == 2) ? 3 : 4) void k_gemm
             for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
                 for (int dx = 0; dx < WW; ++dx)
-                    if (pvalid && yi + dy >= 0 && yi + dy < a.in_h && xi + dx >= 0 && xi + dx < a.in_w && !(dbg & 8))
+                    if (pvalid && yi + dy >= 0 && yi + dy < a.in_h && xi + dx >= 0 && xi + dx < a.in_w)
                         okmask |= 1u << (dy * WW + dx);
         } else {
             cbase = (unsigned)(pc * cin) * 4u + PP_ZPAD_FLOATS * 4u;
-            if (pvalid && !(dbg & 8)) okmask = 1u;
+            if (pvalid) okmask = 1u;
         }
         const int rs4 = a.in_w * cin * 4, cin4 = cin * 4;   // row / pixel stride in bytes (uniform)
         // per-thread byte offsets of the NLD window elements (incl. this lane's channel group), fixed for
@@ -476,21 +469,7 @@ __global__ __launch_bounds__(PXB * 4, (MODE == 0 && S == 2) ? 3 : 4) void k_gemm
             WS_LOAD_CHUNK(0)
         }
         __syncthreads();   // (A) depthwise taps / s_opix visible; chunk-0 loads are already in flight
-#ifdef PP_KERNEL_STAMPS   // diagnostic build (tools/layer_bench.py --ablate 64): in-kernel phase stamps
-        const bool stamp = (dbg & 64) && a.stamps != nullptr && blockIdx.x < 64 && blockIdx.y == 0 && pt == 0;
-        long long* st = a.stamps ? a.stamps + ((size_t)blockIdx.x * 2 + 1) * 40 * 4 : nullptr;
-#else
-        constexpr bool stamp = false;
-        long long* st = nullptr;
-#endif
         for (int s = -1; s < nchunks; ++s) {
-            if (stamp && s + 1 < 40) st[(s + 1) * 4 + 0] = clock64();
-#ifdef PP_KERNEL_STAMPS
-            if ((dbg & 64) && a.stamps != nullptr && blockIdx.x < 64 && blockIdx.y == 0 && wave == NCW) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // isolate the load wait
-                if (stamp && s + 1 < 40) st[(s + 1) * 4 + 1] = clock64();
-            }
-#endif
             if (s + 1 < nchunks) {
                 // ---- stage chunk s+1 (registers -> LDS buffer (s+1)&1) ----
                 const int kc = s + 1, buf = kc & 1;
@@ -500,28 +479,26 @@ __global__ __launch_bounds__(PXB * 4, (MODE == 0 && S == 2) ? 3 : 4) void k_gemm
                     float4 o[PXT];
 #pragma unroll
                     for (int j = 0; j < PXT; ++j) o[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (!(dbg & 2)) {
-                        // all 9 tap vectors of this chunk first (one LDS latency, overlapping the tail of the
-                        // global-load wait), then the FMAs
-                        float4 wv[9];
+                    // all 9 tap vectors of this chunk first (one LDS latency, overlapping the tail of the
+                    // global-load wait), then the FMAs
+                    float4 wv[9];
 #pragma unroll
-                        for (int t = 0; t < 9; ++t) wv[t] = *reinterpret_cast<const float4*>(sDW + t * cin + ch);
-                        __builtin_amdgcn_sched_barrier(0);
+                    for (int t = 0; t < 9; ++t) wv[t] = *reinterpret_cast<const float4*>(sDW + t * cin + ch);
+                    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                        for (int dy = 0; dy < 3; ++dy)
+                    for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                            for (int dx = 0; dx < 3; ++dx) {
-                                const float4 w4 = wv[dy * 3 + dx];
+                        for (int dx = 0; dx < 3; ++dx) {
+                            const float4 w4 = wv[dy * 3 + dx];
 #pragma unroll
-                                for (int j = 0; j < PXT; ++j) {
-                                    const float4 v = rin[dy * WW + j * S + dx];
-                                    o[j].x = fmaf(v.x, w4.x, o[j].x);
-                                    o[j].y = fmaf(v.y, w4.y, o[j].y);
-                                    o[j].z = fmaf(v.z, w4.z, o[j].z);
-                                    o[j].w = fmaf(v.w, w4.w, o[j].w);
-                                }
+                            for (int j = 0; j < PXT; ++j) {
+                                const float4 v = rin[dy * WW + j * S + dx];
+                                o[j].x = fmaf(v.x, w4.x, o[j].x);
+                                o[j].y = fmaf(v.y, w4.y, o[j].y);
+                                o[j].z = fmaf(v.z, w4.z, o[j].z);
+                                o[j].w = fmaf(v.w, w4.w, o[j].w);
                             }
-                    }
+                        }
 #pragma unroll
                     for (int j = 0; j < PXT; ++j) *reinterpret_cast<float4*>(dst + j * LSTR) = o[j];
                 } else {
@@ -535,12 +512,10 @@ __global__ __launch_bounds__(PXB * 4, (MODE == 0 && S == 2) ? 3 : 4) void k_gemm
                 }
                 WS_STORE_B(0, rb0) WS_STORE_B(1, rb1) WS_STORE_B(2, rb2) WS_STORE_B(3, rb3)
                 WS_STORE_B(4, rb4) WS_STORE_B(5, rb5) WS_STORE_B(6, rb6) WS_STORE_B(7, rb7)
-                if (stamp && s + 1 < 40) st[(s + 1) * 4 + 2] = clock64();
                 // ---- issue the loads of chunk s+2 ----
                 if (s + 2 < nchunks) WS_LOAD_CHUNK(s + 2)
             }
             __syncthreads();
-            if (stamp && s + 1 < 40) st[(s + 1) * 4 + 3] = clock64();
         }
         return;
 #undef WS_LOAD_CHUNK
@@ -556,59 +531,48 @@ __global__ __launch_bounds__(PXB * 4, (MODE == 0 && S == 2) ? 3 : 4) void k_gemm
         for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
     const int h = lane >> 5, r32 = lane & 31;
     __syncthreads();   // (A)
-#ifdef PP_KERNEL_STAMPS
-    const bool stamp = (dbg & 64) && a.stamps != nullptr && blockIdx.x < 64 && blockIdx.y == 0 && tid == 0;
-    long long* st = a.stamps ? a.stamps + ((size_t)blockIdx.x * 2 + 0) * 40 * 4 : nullptr;
-#else
-    constexpr bool stamp = false;
-    long long* st = nullptr;
-#endif
-    if (stamp) st[0] = clock64();
     __syncthreads();   // chunk 0 staged
-    if (stamp) st[3] = clock64();
     for (int k = 0; k < nchunks; ++k) {
-        if (stamp && k + 1 < 40) st[(k + 1) * 4 + 0] = clock64();
         const float* cA = sA + (k & 1) * SA + (wave * 32 + r32) * LSTR + h * (KCH / 2);
         const float* cB = sB + (k & 1) * SB + r32 * LSTR + h * (KCH / 2);
         float4 a4[KQ];
 #pragma unroll
         for (int q = 0; q < KQ; ++q) a4[q] = *reinterpret_cast<const float4*>(cA + q * 4);
-        if (!(dbg & 1)) {
-            if constexpr (NTILES * KQ <= 8) {
-                // all B fragments of the chunk first (one LDS latency), then the MFMAs back to back
-                float4 bq[NTILES][KQ];
+        // scheduling boundary: without it every B fragment of the chunk is read ahead of the MFMAs
+        // (k_gemm_ws<128, 1, 1, 128>: 95 -> 112 VGPRs)
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (NTILES * KQ <= 8) {
+            // all B fragments of the chunk first (one LDS latency), then the MFMAs back to back
+            float4 bq[NTILES][KQ];
 #pragma unroll
-                for (int n = 0; n < NTILES; ++n)
+            for (int n = 0; n < NTILES; ++n)
 #pragma unroll
-                    for (int q = 0; q < KQ; ++q) bq[n][q] = *reinterpret_cast<const float4*>(cB + n * 32 * LSTR + q * 4);
+                for (int q = 0; q < KQ; ++q) bq[n][q] = *reinterpret_cast<const float4*>(cB + n * 32 * LSTR + q * 4);
 #pragma unroll
-                for (int n = 0; n < NTILES; ++n)
+            for (int n = 0; n < NTILES; ++n)
 #pragma unroll
-                    for (int q = 0; q < KQ; ++q) {
-                        acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].x, bq[n][q].x, acc[n], 0, 0, 0);
-                        acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].y, bq[n][q].y, acc[n], 0, 0, 0);
-                        acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].z, bq[n][q].z, acc[n], 0, 0, 0);
-                        acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].w, bq[n][q].w, acc[n], 0, 0, 0);
-                    }
-            } else {
+                for (int q = 0; q < KQ; ++q) {
+                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].x, bq[n][q].x, acc[n], 0, 0, 0);
+                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].y, bq[n][q].y, acc[n], 0, 0, 0);
+                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].z, bq[n][q].z, acc[n], 0, 0, 0);
+                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].w, bq[n][q].w, acc[n], 0, 0, 0);
+                }
+        } else {
 #pragma unroll
-                for (int n = 0; n < NTILES; ++n) {
-                    float4 b4[KQ];
+            for (int n = 0; n < NTILES; ++n) {
+                float4 b4[KQ];
 #pragma unroll
-                    for (int q = 0; q < KQ; ++q) b4[q] = *reinterpret_cast<const float4*>(cB + n * 32 * LSTR + q * 4);
+                for (int q = 0; q < KQ; ++q) b4[q] = *reinterpret_cast<const float4*>(cB + n * 32 * LSTR + q * 4);
 #pragma unroll
-                    for (int q = 0; q < KQ; ++q) {
-                        acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].x, b4[q].x, acc[n], 0, 0, 0);
-                        acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].y, b4[q].y, acc[n], 0, 0, 0);
-                        acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].z, b4[q].z, acc[n], 0, 0, 0);
-                        acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].w, b4[q].w, acc[n], 0, 0, 0);
-                    }
+                for (int q = 0; q < KQ; ++q) {
+                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].x, b4[q].x, acc[n], 0, 0, 0);
+                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].y, b4[q].y, acc[n], 0, 0, 0);
+                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].z, b4[q].z, acc[n], 0, 0, 0);
+                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[q].w, b4[q].w, acc[n], 0, 0, 0);
                 }
             }
         }
-        if (stamp && k + 1 < 40) { asm volatile("" :: "v"(acc[0][0])); st[(k + 1) * 4 + 2] = clock64(); }
         __syncthreads();
-        if (stamp && k + 1 < 40) st[(k + 1) * 4 + 3] = clock64();
     }
     if (a.epi == 2) {
         gemm_epilogue<NTILES>(a, acc, p0, n0, wave, lane, s_opix);
@@ -616,7 +580,6 @@ __global__ __launch_bounds__(PXB * 4, (MODE == 0 && S == 2) ? 3 : 4) void k_gemm
     }
     // ---- coalesced epilogue: bias + ReLU -> this wave's LDS rows -> 16-byte stores of whole channel
     // rows (the final barrier of the K loop guarantees nobody still reads the arena) ----
-    if (dbg & 4) return;
     float* so = smem + wave * 32 * OSTR;
     int cbase = n0, delta = 0;
     if (a.epi == 1) {
@@ -688,7 +651,6 @@ __global__ __launch_bounds__(PXB * 4, (MODE == 0 && S == 2) ? 3 : 4) void k_gemm
             }
         }
     }
-    if (stamp) st[39 * 4 + 1] = clock64();
 }
 
 
@@ -814,19 +776,6 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
     // (TR: + the workgroup's running column sums / squared deviations, one [2][NT] row per wave)
     __shared__ __attribute__((aligned(16))) float smem[8 * SAW + 2 * SB + (PW ? 0 : NTAP * 256) + (TR ? 8 * NT : 0)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (a.dbg & 128) return;   // tuning aid: launch + dispatch cost only
-#ifdef PP_KERNEL_STAMPS   // diagnostic build: wall-clock phase stamps of every workgroup (wave 0)
-    long long* ust = ((a.dbg & 64) && a.stamps && tid == 0 && blockIdx.y == 0 && blockIdx.x < 4096)
-                         ? a.stamps + (size_t)blockIdx.x * 8 : nullptr;
-    if (ust) {
-        ust[0] = wall_clock64();
-        ust[5] = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_ID
-        ust[6] = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // XCC_ID
-    }
-#define U_STAMP(i) { if (ust) ust[i] = wall_clock64(); }
-#else
-#define U_STAMP(i) {}
-#endif
     float* const sAw = smem + wave * 2 * SAW;
     float* const sB = smem + 8 * SAW;
     float* const sDW = smem + 8 * SAW + 2 * SB;
@@ -849,11 +798,6 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
     const int ntl = (tend - first + GL - 1) / GL;      // tiles of this workgroup
     const int cin = a.cin;
     const int nchunks = cin / KCH;
-#ifdef PP_KERNEL_STAMPS
-    const int dbg = a.dbg;                             // phase ablation bits (diagnostic build only)
-#else
-    constexpr int dbg = 0;                             // production: no ablation branches inside the K loop
-#endif
     const int total = ntl * nchunks;                   // K-chunks in this workgroup's stream (>= 2: cin >= 32)
 
     // ---- staging role: lane (q, c4) owns output pixels pw + 2q, +1 and channels 4*c4..+3 of a chunk ----
@@ -893,7 +837,7 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
         bool rowok_[3], colok_[WW];                                                                      \
         unsigned rowoff_[3], coloff_[WW];                                                                \
         _Pragma("unroll") for (int dy_ = 0; dy_ < 3; ++dy_) {                                            \
-            rowok_[dy_] = pvalid_ & ((unsigned)(yi_ + dy_) < (unsigned)a.in_h) & !(dbg & 8);             \
+            rowok_[dy_] = pvalid_ & ((unsigned)(yi_ + dy_) < (unsigned)a.in_h);                          \
             rowoff_[dy_] = cbase_ + (unsigned)((dy_ - 1) * rs4);                                         \
         }                                                                                                \
         _Pragma("unroll") for (int dx_ = 0; dx_ < WW; ++dx_) {                                           \
@@ -957,12 +901,7 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
 #define U_LOAD_ACT(KCIDX, RIN)                                                                           \
     {                                                                                                    \
         const unsigned so_ = (unsigned)(KCIDX) * (KCH * 4);                                              \
-        _Pragma("unroll") for (int e = 0; e < NLD; ++e) {                                                \
-            /* diagnostic build, bit 256: the two outer window columns are not loaded (half the window   \
-               traffic of a stride-1 layer; wrong results, timing only) */                               \
-            if ((dbg & 256) && (e % WW == 0 || e % WW == WW - 1)) RIN[e] = make_float4(0.f, 0.f, 0.f, 0.f); \
-            else RIN[e] = buf_load16(rs_in, aoff[e], so_);                                               \
-        }                                                                                                \
+        _Pragma("unroll") for (int e = 0; e < NLD; ++e) RIN[e] = buf_load16(rs_in, aoff[e], so_);        \
     }
 #define U_LOAD_WT(KCIDX)                                                                                 \
     {                                                                                                    \
@@ -1010,12 +949,11 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
 #pragma unroll
     for (int n = 0; n < NTILES; ++n) bias_r[n] = (TR && a.bias == nullptr) ? 0.f : a.bias[n0 + n * 32 + r32];
     __syncthreads();   // depthwise taps visible
-    U_STAMP(1)
 
     // ---- the parts of one stream position ----
     // MFMAs of position I out of buffer I & 1
 #define U_MFMA(I)                                                                                        \
-    if (!(dbg & 1) && PREC == 1) {                                                                       \
+    if (PREC == 1) {                                                                                     \
         const float* cA = cA0 + ((I) & 1) * SAW;                                                         \
         const float* cB = cB0 + ((I) & 1) * SB;                                                          \
         const float4 a0 = *reinterpret_cast<const float4*>(cA), a1 = *reinterpret_cast<const float4*>(cA + 4);  \
@@ -1029,7 +967,7 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
             PC_PRODUCTS(acc[n], ah, am, al, bh, bm, bl)                                                  \
         }                                                                                                \
     }                                                                                                    \
-    if (!(dbg & 1) && PREC == 0) {                                                                       \
+    if (PREC == 0) {                                                                                     \
         const float* cA = sAw + ((I) & 1) * SAW + r32 * LSTR + h * (KCH / 2);                            \
         const float* cB = sB + ((I) & 1) * SB + r32 * LSTR + h * (KCH / 2);                              \
         float4 a4[KQ];                                                                                   \
@@ -1058,7 +996,7 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
             }                                                                                            \
         }                                                                                                \
         if (PW) { o0 = RIN[0]; o1 = RIN[NLD - 1]; }                                                      \
-        if (!PW && !(dbg & 2)) {                                                                         \
+        if (!PW) {                                                                                       \
             const float* tw = twp;                                                                       \
             _Pragma("unroll") for (int dy = 0; dy < 3; ++dy)                                             \
                 _Pragma("unroll") for (int dx = 0; dx < 3; ++dx) {                                       \
@@ -1130,7 +1068,7 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
             }                                                                                            \
             st_n += (float)nw;                                                                           \
         }                                                                                                \
-        if (!(dbg & 4) && pw < a.M) {                                                                    \
+        if (pw < a.M) {                                                                                  \
             const int qi = lane & 3, qj = r32 >> 2;                                                      \
             float* dst = a.out + (size_t)(pw + 4 * h + qi) * a.ld_out + a.co_off + n0 + qj * 4;          \
             const bool full = pw + 32 <= a.M;             /* wave-uniform: one branch, not one per store */ \
@@ -1171,30 +1109,16 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
     U_STAGE(0)
     U_ISSUE()
     __syncthreads();
-    U_STAMP(2)
     // steady state: positions i (MFMA), i+1 (staging) and i+2 (loads) all exist -- no branch between the
     // MFMA block and the staging block, so the scheduler may interleave matrix and vector work
     // (unrolled by two -- total is even -- so that the LDS buffer of every access is a compile-time constant)
     int i = 0;
     for (; i + 3 < total; i += 2) {
-#ifdef PP_KERNEL_STAMPS
-        if (ust && blockIdx.x < 64 && i + 1 < 64) a.stamps[4096 * 8 + blockIdx.x * 64 + i + 1] = wall_clock64();
-#endif
-#ifdef PP_KERNEL_STAMPS   // phase boundaries of ONE iteration (i == 4), shader clock: tools/phase_stamps.py
-#define U_PH(k) { if (ust && blockIdx.x < 64 && i == 4) a.stamps[4096 * 8 + blockIdx.x * 64 + 40 + (k)] = clock64(); }
-#else
-#define U_PH(k) {}
-#endif
-        U_PH(0)
         U_MFMA(0)
-        U_PH(1)
         U_STAGE(1)
-        U_PH(2)
         U_ISSUE()
-        U_PH(3)
         if (++mm_kc == nchunks) U_EPILOGUE()
         __syncthreads();
-        U_PH(4)
         U_MFMA(1)
         U_STAGE(0)
         U_ISSUE()
@@ -1228,16 +1152,10 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
 #undef U_MFMA
 #undef U_STAGE
 #undef U_ISSUE
-#undef U_PH
 #undef U_EPILOGUE
 #undef U_ACT
 #undef U_LOAD_CHUNK
 #undef U_TILE_OFFSETS
-    U_STAMP(3)
-#ifdef PP_KERNEL_STAMPS
-    if (a.dbg & 64) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    U_STAMP(4)
-#endif
 }
 
 // persistent launch: WPS workgroups per CU (one wave per SIMD each), a multiple of 8 so that every XCD
@@ -1247,7 +1165,7 @@ template <int NT, int S, int WPS, int WPB>
 static void launch_u(const GemmArgs& a, int n_total, hipStream_t s) {
     const int ntiles = (a.M + 127) / 128;
     const int ny = n_total / NT;
-    const bool bf = a.wt16 != nullptr && split_precision(a.dbg);
+    const bool bf = a.wt16 != nullptr && split_precision();
     int slots = (g_num_cus * (bf ? WPB : WPS)) / ny;
     const int mine = ntiles - a.tile_lo;               // (a.tile_lo > 0: a launch over a sub-range of the batch's frames)
     int gx = mine < slots ? mine : slots;
@@ -1291,13 +1209,6 @@ int launch_sep_train(const SepTrainArgs& t, hipStream_t s) {
     gx = (gx + 7) & ~7;
     const dim3 grid((unsigned)gx, ny);
     const char* tg = t.tag ? t.tag : "k_sep_u_tr";
-    {   // measurement switches (wrong results): PP_TR_NOD=1 no depthwise-output store, PP_TR_NOACT=1 no activation on the way in
-        static int nod = -1, noact = -1;
-        if (nod < 0) { const char* e = getenv("PP_TR_NOD"); nod = (e && e[0] == '1') ? 1 : 0; }
-        if (noact < 0) { const char* e = getenv("PP_TR_NOACT"); noact = (e && e[0] == '1') ? 1 : 0; }
-        if (nod) a.tr_D = nullptr;
-        if (noact) a.tr_coef = nullptr;
-    }
     if (t.stride == 1) {
         if (nt == 128) PP_LAUNCH(tg, (k_sep_u<128, 1, 2, 1, 0, 1>), grid, dim3(256), 0, s, a, ntiles);
         else if (nt == 64) PP_LAUNCH(tg, (k_sep_u<64, 1, 3, 1, 0, 1>), grid, dim3(256), 0, s, a, ntiles);
@@ -1563,13 +1474,11 @@ static void launch_p(const GemmArgs& a, hipStream_t s) {
 #endif   // PP_SPLIT_MODE != 0
 
 // does k_sep_p run this separable layer?  (256 output channels, stride 1, dense input, two-piece builds, large enough
-// for the persistent kernels; PP_SEP_P=0: never)
-static bool sep_p_runs(const void* wt16, int stride, int cin, int cout, int n_total, long long M, const int* occ, int dbg) {
+// for the persistent kernels)
+static bool sep_p_runs(const void* wt16, int stride, int cin, int cout, int n_total, long long M, const int* occ) {
 #if PP_SPLIT_MODE != 0
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("PP_SEP_P"); v = (e && e[0] == '0') ? 0 : 1; }
     // (the 128-channel instantiation, where k_sep_u already computes the depthwise once, measured 32 us against 28.5)
-    return v != 0 && wt16 != nullptr && split_precision(dbg) && stride == 1 && occ == nullptr && cout == 256 &&
+    return wt16 != nullptr && split_precision() && stride == 1 && occ == nullptr && cout == 256 &&
            n_total == 256 && cin % 64 == 0 && cin <= 256 && M < (1 << 24);
 #else
     return false;
@@ -1751,10 +1660,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_sep_k4(GemmArgs a)
 // Measured crossover against k_sep_u (tools/k4_sweep.sh, cfg-A, B = 2..16): 1.5 workgroups per CU for
 // cin = 64, 2.5 for cin = 128, 3 for cin = 256 -- the longer the K chain, the later k_sep_u catches up.
 // PP_SEP_K4=0 turns it off, PP_SEP_K4=n sets the limit to n workgroups per CU for every layer.
-static bool sep_k4_runs(const void* wt16, int cin, int n_total, long long M, int dbg) {
+static bool sep_k4_runs(const void* wt16, int cin, int n_total, long long M) {
     static int force = -2;
     if (force == -2) { const char* e = getenv("PP_SEP_K4"); force = e ? atoi(e) : -1; }
-    if (force == 0 || wt16 == nullptr || !split_precision(dbg) || cin % 64 != 0 || cin > 256 || n_total % 64 != 0)
+    if (force == 0 || wt16 == nullptr || !split_precision() || cin % 64 != 0 || cin > 256 || n_total % 64 != 0)
         return false;
     const int half_cus = (force > 0) ? 2 * force : (cin <= 64 ? 3 : (cin <= 128 ? 5 : 6));
     return 2 * ((M + 31) / 32 * (n_total / 64)) <= (long long)half_cus * g_num_cus;
@@ -1763,9 +1672,7 @@ static bool sep_k4_runs(const void* wt16, int cin, int n_total, long long M, int
 // at B=1 (tools/latency_b1.py): block3.1-.5 8.1 -> 7.2 us; the 128-channel layers gain nothing (block2.x 5.8 -> 5.6,
 // block3.0 6.0 -> 7.0: one iteration per wave leaves nothing to pipeline) and keep four waves
 static bool sep_k8_runs(int cin, int n_total, long long M) {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("PP_SEP_K8"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v != 0 && cin % 256 == 0 && (M + 31) / 32 * (n_total / 64) <= (long long)g_num_cus;
+    return cin % 256 == 0 && (M + 31) / 32 * (n_total / 64) <= (long long)g_num_cus;
 }
 template <int S>
 static void launch_k4(const GemmArgs& a, int n_total, hipStream_t s) {
@@ -1787,7 +1694,7 @@ __device__ __forceinline__ void deconv_tile_epilogue(const GemmArgs& a, f32x16 (
     constexpr int NTILES = NT / 32;
     const int h = lane >> 5, r32 = lane & 31;
     const int pix = tile * 128 + wave * 32 + r32;
-    if ((a.dbg & 4) || tile * 128 + wave * 32 >= a.M) return;
+    if (tile * 128 + wave * 32 >= a.M) return;
     const bool ok = pix < a.M;
     const size_t orow = (size_t)(opix_tab[wave * 32 + r32] + delta);   // this lane's output pixel
     const bool heads = a.head_mode != 0;
@@ -1883,7 +1790,6 @@ __global__ __launch_bounds__(256, WPS) void k_deconv_u(GemmArgs a, int ntiles) {
     __shared__ int s_opix[2][128];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, r32 = lane & 31;
-    const int dbg = a.dbg;
 
     const int xcd = blockIdx.x & 7, gl = blockIdx.x >> 3, GL = gridDim.x >> 3;
     const int tbase = (int)(((long long)xcd * ntiles) >> 3), tend = (int)(((long long)(xcd + 1) * ntiles) >> 3);
@@ -1945,7 +1851,7 @@ __global__ __launch_bounds__(256, WPS) void k_deconv_u(GemmArgs a, int ntiles) {
 #define D_TILE_AOFF(TILE)                                                                                \
     {                                                                                                    \
         const int pix_ = (TILE) * 128 + wave * 32 + r32;                                                 \
-        avo = (pix_ < a.M && !(dbg & 8)) ? (unsigned)(pix_ * cin + h * 8) * 4u + PP_ZPAD_FLOATS * 4u : (unsigned)(h * 32); \
+        avo = (pix_ < a.M) ? (unsigned)(pix_ * cin + h * 8) * 4u + PP_ZPAD_FLOATS * 4u : (unsigned)(h * 32);  \
     }
 #define D_LOAD_A(R0, R1)                                                                                 \
     {                                                                                                    \
@@ -1989,7 +1895,7 @@ __global__ __launch_bounds__(256, WPS) void k_deconv_u(GemmArgs a, int ntiles) {
         bf16x8 ah_, am_, al_;                                                                            \
         split_bf16x3(av_, ah_, am_, al_);                                                                \
         if (i_ + 2 < total) D_LOAD_A(RA0, RA1)                                                           \
-        if (!(dbg & 1)) {                                                                                \
+        {                                                                                                \
             const float* cB_ = sB + (i_ & 1) * SB + r32 * 8 + ((h ^ ((r32 >> 3) & 1)) * 4);              \
             _Pragma("unroll") for (int n = 0; n < NTILES; ++n) {                                         \
                 const bf16x8 bh_ = *reinterpret_cast<const bf16x8*>(cB_ + n * 32 * 8);                   \
@@ -1998,7 +1904,7 @@ __global__ __launch_bounds__(256, WPS) void k_deconv_u(GemmArgs a, int ntiles) {
                 PC_PRODUCTS(acc[n], bh_, bm_, bl_, ah_, am_, al_)                                        \
             }                                                                                            \
         }                                                                                                \
-        if (i_ + 1 < total && !(dbg & 512)) D_STORE_B((i_ + 1) & 1)   /* weight tile of position i+1 -> LDS */ \
+        if (i_ + 1 < total) D_STORE_B((i_ + 1) & 1)   /* weight tile of position i+1 -> LDS */           \
         if (++mm_kc == nchunks) {                                                                        \
             deconv_tile_epilogue<NT>(a, acc, mm_tile, wave, lane, cbase, delta, s_opix[mm_slot], sHW, s_hbias);  \
             D_INIT_ACC()                                                                                 \
@@ -2009,11 +1915,10 @@ __global__ __launch_bounds__(256, WPS) void k_deconv_u(GemmArgs a, int ntiles) {
             D_FILL_OPIX(mm_tile + GL, mm_slot ^ 1)   /* table of the next tile, one tile ahead */        \
         }                                                                                                \
         if (i_ + 1 < total) {   /* weight loads of position i+2 (after the epilogue: not live across it) */ \
-            if (i_ + 2 < total && !(dbg & 512)) D_LOAD_B(lb_kc)                                          \
+            if (i_ + 2 < total) D_LOAD_B(lb_kc)                                                          \
             if (++lb_kc == nchunks) lb_kc = 0;                                                           \
         }                                                                                                \
-        /* tuning aid, bit 512: no weight staging and no barrier (wrong results): what resident weights could give */ \
-        if (!(dbg & 512)) __syncthreads();                                                               \
+        __syncthreads();                                                                                 \
     }
     for (int i = 0; i < total; i += 2) {
         D_STEP(i, ra0, ra1)
@@ -2048,15 +1953,6 @@ __global__ __launch_bounds__(256, WPS) void k_deconv_u(GemmArgs a, int ntiles) {
 //     branch: + head bias; later branches: + the partial sums fetched at the start of the unit).
 // cout == 128 (one tap = four n-tiles); CIN 64 / 128 / 256.  Same summation order per output as k_deconv_u
 // (chunks ascending, three products per chunk smallest first), so the two kernels agree bit for bit.
-#ifdef PP_DECONV_ABLATE   // tuning build: pp_bench_layer's ablation bits switch phases of k_deconv_r off (wrong results)
-#define R_ABL(BIT) (a.dbg & (BIT))
-// bit 64: shader-clock stamps of workgroups 0..63 (wave 0): [0] start, [1] after the prologue, per unit u of the run
-// [2 + 8u] unit start, [3 + 8u] input tile in registers, [4 + 8u .. 7 + 8u] n-tiles done, [8 + 8u] head row stored
-#define R_STAMP(IDX) { if ((a.dbg & 64) && a.stamps && blockIdx.x < 64 && tid == 0 && (IDX) < 64) a.stamps[4096 * 8 + blockIdx.x * 64 + (IDX)] = clock64(); }
-#else
-#define R_ABL(BIT) false
-#define R_STAMP(IDX) {}
-#endif
 template <int CIN>
 __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int upw) {
     constexpr int NCH = CIN / 16;                        // K-chunks
@@ -2083,7 +1979,6 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
     }
     const int u0 = wg * upw, u1 = min(u0 + upw, nunits);
     if (u0 >= u1) return;
-    R_STAMP(0)
     const int ntaps = a.k * a.k;
     const bool heads = a.head_mode != 0;
     const int hwpx = a.px_h * a.px_w, OW = a.px_w * a.k;
@@ -2103,7 +1998,7 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
     int ld_left = (u1 - u0) * NPU, ld_tap = tap, ld_p = 0;
 #define R_LOAD_NEXT()                                                                                    \
     {                                                                                                    \
-        if (ld_left > 0 && !R_ABL(512)) {                                                                \
+        if (ld_left > 0) {                                                                               \
             _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) {                                           \
                 const int fs_ = ld_p * 8 + (wave >> 1) + 2 * j_;                                         \
                 const int nt_ = fs_ / NCH, c_ = fs_ % NCH;                                               \
@@ -2114,7 +2009,7 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
         if (++ld_p == NPU) { ld_p = 0; if (++ld_tap == ntaps) ld_tap = 0; }                              \
     }
 #define R_STORE_W(SLOT)                                                                                  \
-    if (!R_ABL(512)) _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                    \
+    _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                                     \
         *reinterpret_cast<float4*>(sW + (SLOT) * PANEL + wdst + j_ * 1024) = rw[j_];
 
     // the first input tile's loads go out before anything else: they are the longest round trip of the prologue (every
@@ -2123,7 +2018,7 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
     const int pix0_ = tile * 128 + wave * 32 + r32;
     const bool ok0_ = pix0_ < a.M;
     {
-        const unsigned avo = (ok0_ && !R_ABL(8)) ? (unsigned)(pix0_ * CIN + h * 8) * 4u + PP_ZPAD_FLOATS * 4u : (unsigned)(h * 32);
+        const unsigned avo = ok0_ ? (unsigned)(pix0_ * CIN + h * 8) * 4u + PP_ZPAD_FLOATS * 4u : (unsigned)(h * 32);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             ra0[c][0] = buf_load16(rs_in, avo, (unsigned)c * 64u);
@@ -2140,7 +2035,6 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
     R_STORE_W(0)
     R_LOAD_NEXT()                        // panel 1: written at step 0 of panel 0
     __syncthreads();
-    R_STAMP(1)
 
     bf16x8 xh[NCH], xm[NCH];             // the wave's 32 pixels x CIN channels, two float16 pieces
     int tile_cur = tile, opix0;
@@ -2176,12 +2070,11 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
     float4 rn[PREF ? NCH : 1][2];
     int pre_tile = -1;
     for (int u = u0; u < u1; ++u) {
-        R_STAMP(2 + 8 * (u - u0))
         if (tile != tile_cur) {          // uniform: fetch and split this tile's input once
             tile_cur = tile;
             const int pix = tile * 128 + wave * 32 + r32;
             ok = pix < a.M;
-            const unsigned avo = (ok && !R_ABL(8)) ? (unsigned)(pix * CIN + h * 8) * 4u + PP_ZPAD_FLOATS * 4u : (unsigned)(h * 32);
+            const unsigned avo = ok ? (unsigned)(pix * CIN + h * 8) * 4u + PP_ZPAD_FLOATS * 4u : (unsigned)(h * 32);
             float4 ra[NCH][2];
             if (PREF && pre_tile == tile) {
 #pragma unroll
@@ -2204,12 +2097,11 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
                 split_bf16x3(av, xh[c], xm[c], lo_);
             }
         }
-        R_STAMP(3 + 8 * (u - u0))
         const int ti = tap / a.k;
         const size_t orow = (size_t)(opix0 + ti * OW + (tap - ti * a.k));      // this lane's output pixel
         float* const hrow = a.head + orow * PP_HEAD_COLS + 4 * h;              // its columns 4h + {0..3, 8.., 16.., 24..}
         f32x16 hacc;
-        if (a.head_mode == 2 && ok && !R_ABL(4)) {
+        if (a.head_mode == 2 && ok) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const float4 t = *reinterpret_cast<const float4*>(hrow + 8 * g);
@@ -2232,15 +2124,13 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
                     acc[4 * g] = t.x; acc[4 * g + 1] = t.y; acc[4 * g + 2] = t.z; acc[4 * g + 3] = t.w;
                 }
             }
-            if (s == 4) {                // publishes the panel written at step 0 (read from step 8 - PD on)
-                if (!R_ABL(512)) __syncthreads();
-            }
+            if (s == 4) __syncthreads();   // publishes the panel written at step 0 (read from step 8 - PD on)
             {   // fragments of step fs + PD
                 const float* w_ = (s + PD < 8) ? pcur + (s + PD) * 512 : pnxt + (s + PD - 8) * 512;
                 fh[(fs + PD) & 3] = *reinterpret_cast<const bf16x8*>(w_);
                 fm[(fs + PD) & 3] = *reinterpret_cast<const bf16x8*>(w_ + 256);
             }
-            if (!R_ABL(1)) { PC_PRODUCTS(acc, fh[fs & 3], fm[fs & 3], fm[fs & 3], xh[c], xm[c], xm[c]) }
+            PC_PRODUCTS(acc, fh[fs & 3], fm[fs & 3], fm[fs & 3], xh[c], xm[c], xm[c])
             if (s == 0) {                // the panel after this one -> its ring slot (fetched one panel ago)
                 const int ws = (slot + 1 == NB) ? 0 : slot + 1;
                 R_STORE_W(ws)
@@ -2251,7 +2141,7 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
                 // memory counter retires in order: issued in front of it, the store's wait also waited for these)
                 pre_tile = tile + 1;
                 const int pixn = pre_tile * 128 + wave * 32 + r32;
-                const unsigned avn = (pixn < a.M && !R_ABL(8)) ? (unsigned)(pixn * CIN + h * 8) * 4u + PP_ZPAD_FLOATS * 4u : (unsigned)(h * 32);
+                const unsigned avn = (pixn < a.M) ? (unsigned)(pixn * CIN + h * 8) * 4u + PP_ZPAD_FLOATS * 4u : (unsigned)(h * 32);
 #pragma unroll
                 for (int c = 0; c < (PREF ? NCH : 0); ++c) {
                     rn[c][0] = buf_load16(rs_in, avn, (unsigned)c * 64u);
@@ -2268,7 +2158,7 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
                 float v[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) v[r] = relu_keep_nan(acc[r]);
-                if (heads && !R_ABL(2)) {
+                if (heads) {
 #pragma unroll
                     for (int g = 0; g < 2; ++g) {
                         const float av[8] = {v[8 * g], v[8 * g + 1], v[8 * g + 2], v[8 * g + 3],
@@ -2286,11 +2176,10 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
                     for (int g = 0; g < 4; ++g)
                         *reinterpret_cast<float4*>(dst + nt * 32 + 8 * g) = make_float4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
                 }
-                R_STAMP(4 + nt + 8 * (u - u0))
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (heads && ok && !R_ABL(4)) {
+        if (heads && ok) {
 #pragma unroll
             for (int g = 0; g < 4; ++g)
                 *reinterpret_cast<float4*>(hrow + 8 * g) = make_float4(hacc[4 * g], hacc[4 * g + 1], hacc[4 * g + 2], hacc[4 * g + 3]);
@@ -2303,20 +2192,14 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
                 }
             }
         }
-        R_STAMP(8 + 8 * (u - u0))
         if (++tap == ntaps) { tap = 0; ++tile; }
     }
 #undef R_STORE_W
 #undef R_LOAD_NEXT
-#undef R_STAMP
-#undef R_ABL
 }
 
-// runs where k_deconv_u would and the shape fits (cout == 128, cin 64 / 128 / 256); PP_DECONV_R=0 turns it off
-static bool deconv_r_runs(const LayerDesc& L, int ablate) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("PP_DECONV_R"); on = (e && e[0] == '0') ? 0 : 1; }
-    if (!on || (ablate & 8192)) return false;
+// runs where k_deconv_u would and the shape fits (cout == 128, cin 64 / 128 / 256)
+static bool deconv_r_runs(const LayerDesc& L) {
     // kernel == stride 1 has one tap per tile: nothing is re-read or re-split, and k_deconv_u's two-chunk register
     // prefetch hides the tile changes better (deconv1 at B=64: 35.4 us against 37.1)
     return L.k > 1 && L.cout == 128 && (L.cin == 64 || L.cin == 128 || L.cin == 256);
@@ -2331,7 +2214,7 @@ static void launch_deconv_r(const GemmArgs& a, hipStream_t s) {
     PP_LAUNCH("k_deconv_r", (k_deconv_r<CIN>), dim3((unsigned)G), dim3(256), 0, s, a, (int)U, upw);
 }
 #else
-static bool deconv_r_runs(const LayerDesc&, int) { return false; }
+static bool deconv_r_runs(const LayerDesc&) { return false; }
 #endif
 
 // ---------------------------------------------------------------------------------------
@@ -2549,10 +2432,10 @@ __global__ __launch_bounds__(256, 2) void k_deconv_k4(GemmArgs a) {
 // runs while the layer has at most 1.5 workgroups per CU (measured crossover against k_deconv_u on cfg-A,
 // tools/k4_sweep.sh: ahead at B = 1, 2 (160 / 320 workgroups), behind from B = 4); PP_DECONV_K4=0: never,
 // =n: up to n per CU
-static bool deconv_k4_runs(const LayerDesc& L, long long M, int ablate) {
+static bool deconv_k4_runs(const LayerDesc& L, long long M) {
     static int force = -2;
     if (force == -2) { const char* e = getenv("PP_DECONV_K4"); force = e ? atoi(e) : -1; }
-    if (force == 0 || (ablate & 16) || L.cin % 64 != 0 || L.cin > 256) return false;
+    if (force == 0 || L.cin % 64 != 0 || L.cin > 256) return false;
     const int nt = L.cout % 128 == 0 ? 128 : (L.cout % 64 == 0 ? 64 : 32);
     const int half_cus = force > 0 ? 2 * force : 3;
     return 2 * ((M + 31) / 32 * (L.n_total / nt)) <= (long long)half_cus * g_num_cus;
@@ -2604,16 +2487,13 @@ static void launch_ws(const GemmArgs& a, int n_total, hipStream_t s) {
 }
 
 // separable layers: uniform-wave kernel (k_sep_u) or the producer/consumer kernel (k_gemm_ws).
-// k_sep_u is the default; PP_SEP_KERNEL=ws selects the other; pp_bench_layer's ablation bits 16 / 32
-// force u / ws.
-static bool sep_uniform(int ablate) {
+// k_sep_u is the default; PP_SEP_KERNEL=ws selects the other.
+static bool sep_uniform() {
     static int dflt = -1;
     if (dflt < 0) {
         const char* e = getenv("PP_SEP_KERNEL");
         dflt = (e && e[0] == 'w') ? 0 : 1;
     }
-    if (ablate & 16) return true;
-    if (ablate & 32) return false;
     return dflt == 1;
 }
 
@@ -2630,11 +2510,9 @@ static int sep_u_nt(const LayerDesc& L, int batch) {
     if (force == 64 || force == 128) return force;
     // split-precision path: the depthwise (VALU) is the larger half of a chunk, so recomputing it per
     // channel tile costs more than the thinner wave supply (measured: block3 at B=64 36 vs 40 us)
-    if (L.d_wt16 != nullptr && split_precision(0)) return 128;
+    if (L.d_wt16 != nullptr && split_precision()) return 128;
     return (waves128 * 2 < 5ll * g_num_cus * 4) ? 64 : 128;
 }
-
-long long* g_stamps = nullptr;   // tuning aid: device buffer for in-kernel stamps (pp_bench_layer, ablate & 64)
 
 // workgroups per CU of the split-precision k_sep_u<128, 1, ...> instantiation (its register budget: 256 / 168)
 #ifndef PP_SEP128_WPB
@@ -2654,16 +2532,15 @@ static bool use_ws(const LayerDesc& L) {
 
 // the split-precision uniform-wave deconv kernel runs when its operands exist (cin % 32 == 0: an even
 // number of 16-channel chunks) and, with fused heads, when one column tile covers the tap (NT == cout)
-static bool deconv_uniform(const LayerDesc& L, int ablate) {
-    if (L.kind != LAYER_DECONV || L.d_wt16 == nullptr || L.cin % 32 != 0 || !split_precision(ablate)) return false;
-    if (ablate & 32) return false;
+static bool deconv_uniform(const LayerDesc& L) {
+    if (L.kind != LAYER_DECONV || L.d_wt16 == nullptr || L.cin % 32 != 0 || !split_precision()) return false;
     if (L.head_mode != 0 && (L.d_head_wt16 == nullptr || !(L.cout == 32 || L.cout == 64 || L.cout == 128))) return false;
     return true;
 }
 
 // can layer L (a separable layer) read a sparse canvas at this batch size?  (the kernels with the cell-map lookup)
 bool sparse_input_supported(const LayerDesc& L, int batch) {
-    return L.kind == LAYER_SEP && use_ws(L) && sep_uniform(0) && L.d_wt16 != nullptr && split_precision(0) &&
+    return L.kind == LAYER_SEP && use_ws(L) && sep_uniform() && L.d_wt16 != nullptr && split_precision() &&
            (long long)batch * L.out_h * L.out_w < (1 << 24);
 }
 
@@ -2682,24 +2559,24 @@ std::string layer_kernel_name(const LayerDesc& L, int batch) {
     const int nt = (L.kind == LAYER_HEAD) ? 32 : (L.cout % 128 == 0 ? 128 : (L.cout % 64 == 0 ? 64 : 32));
     const int mode = (L.kind == LAYER_SEP) ? 0 : 1;
     char buf[64];
-    if (L.kind == LAYER_SEP && use_ws(L) && sep_uniform(0) && layer_rows(L, batch) < (1 << 24)) {
-        if (sep_k4_runs(L.d_wt16, L.cin, L.n_total, layer_rows(L, batch), 0)) {
+    if (L.kind == LAYER_SEP && use_ws(L) && sep_uniform() && layer_rows(L, batch) < (1 << 24)) {
+        if (sep_k4_runs(L.d_wt16, L.cin, L.n_total, layer_rows(L, batch))) {
             if (sep_k8_runs(L.cin, L.n_total, layer_rows(L, batch))) snprintf(buf, sizeof(buf), "k_sep_k4<64,%d,8>", L.stride);
             else snprintf(buf, sizeof(buf), "k_sep_k4<64,%d>", L.stride);
             return std::string(buf);
         }
-        if (sep_p_runs(L.d_wt16, L.stride, L.cin, L.cout, L.n_total, layer_rows(L, batch), L.d_occ, 0)) return std::string("k_sep_p");
+        if (sep_p_runs(L.d_wt16, L.stride, L.cin, L.cout, L.n_total, layer_rows(L, batch), L.d_occ)) return std::string("k_sep_p");
         const int unt = sep_u_nt(L, batch);
-        const bool bf = L.d_wt16 != nullptr && split_precision(0);
+        const bool bf = L.d_wt16 != nullptr && split_precision();
         int wps;   // workgroups per CU of the instantiation launch_layer picks (launch_u<NT, S, WPS, WPB>)
         if (L.stride == 1) wps = bf ? (unt == 128 ? PP_SEP128_WPB : (unt == 64 ? PP_SEP64_WPB : 3)) : (unt == 128 ? 3 : 4);
         else wps = bf ? (unt == 128 ? 2 : 3) : (unt == 128 ? 2 : (unt == 64 ? 3 : 4));
         snprintf(buf, sizeof(buf), "k_sep_u<%d,%d,%d,%d,%d>", unt, L.stride, wps, bf ? 1 : 0, (bf && L.d_occ) ? 1 : 0);
-    } else if (deconv_uniform(L, 0) && deconv_k4_runs(L, layer_rows(L, batch), 0)) {
+    } else if (deconv_uniform(L) && deconv_k4_runs(L, layer_rows(L, batch))) {
         snprintf(buf, sizeof(buf), "k_deconv_k4<%d>", nt);
-    } else if (deconv_uniform(L, 0) && deconv_r_runs(L, 0)) {
+    } else if (deconv_uniform(L) && deconv_r_runs(L)) {
         snprintf(buf, sizeof(buf), "k_deconv_r<%d>", L.cin);
-    } else if (deconv_uniform(L, 0)) {
+    } else if (deconv_uniform(L)) {
         snprintf(buf, sizeof(buf), "k_deconv_u<%d,3>", nt);
     } else if (use_ws(L)) {
         const int pxb = ws_small_tile(layer_rows(L, batch), L.n_total, nt) ? 64 : 128;
@@ -2713,7 +2590,7 @@ std::string layer_kernel_name(const LayerDesc& L, int batch) {
 // does layer L (the last fused-head deconv) leave the compact class-logit plane?  (the uniform-wave and
 // split-K deconv kernels do; the fallback generations do not and the post-process then scans the head rows)
 bool layer_writes_cls_plane(const LayerDesc& L) {
-    return L.kind == LAYER_DECONV && L.head_mode == 2 && L.d_cls_plane != nullptr && deconv_uniform(L, 0);
+    return L.kind == LAYER_DECONV && L.head_mode == 2 && L.d_cls_plane != nullptr && deconv_uniform(L);
 }
 
 // frame0 > 0 (separable layers on k_sep_u only, launch_layer_subrange_ok): the launch covers the frames [frame0, frame0 +
@@ -2725,7 +2602,7 @@ bool launch_layer_subrange_ok(const LayerDesc& L, int frame0, int batch, int tot
     return layer_kernel_name(L, batch).compare(0, 8, "k_sep_u<") == 0 && layer_kernel_name(L, total_batch).compare(0, 8, "k_sep_u<") == 0;
 }
 
-int launch_layer(const LayerDesc& L, int batch, float* d_head, hipStream_t s, int ablate, int frame0) {
+int launch_layer(const LayerDesc& L, int batch, float* d_head, hipStream_t s, int frame0) {
     if (batch <= 0) return 0;
     if (L.cin % KC != 0) return PP_ERR_UNSUPPORTED;
     {
@@ -2734,8 +2611,6 @@ int launch_layer(const LayerDesc& L, int batch, float* d_head, hipStream_t s, in
             (long long)batch * L.out_h * L.out_w * L.k * L.k >= (1ll << 31)) return PP_ERR_UNSUPPORTED;
     }
     GemmArgs a;
-    a.dbg = ablate;
-    a.stamps = g_stamps;
     a.tile_lo = 0;
     a.in = L.in; a.dw = L.d_dw; a.wt = L.d_wt; a.bias = L.d_bias; a.out = L.out;
     a.wt16 = reinterpret_cast<const unsigned short*>(L.d_wt16); a.n_total = L.n_total;
@@ -2758,18 +2633,18 @@ int launch_layer(const LayerDesc& L, int batch, float* d_head, hipStream_t s, in
         }
         if (L.cout % 32 != 0) return PP_ERR_UNSUPPORTED;
         // a sparse input is only understood by the split-precision uniform-wave / split-K kernels
-        if (a.occ != nullptr && !(sparse_input_supported(L, batch) && split_precision(ablate) && sep_uniform(ablate)))
+        if (a.occ != nullptr && !sparse_input_supported(L, batch))
             return PP_ERR_UNSUPPORTED;
-        if (use_ws(L) && sep_uniform(ablate) && a.M < (1 << 24)) {   // k_sep_u's float-reciprocal index math
+        if (use_ws(L) && sep_uniform() && a.M < (1 << 24)) {   // k_sep_u's float-reciprocal index math
             const int nt = sep_u_nt(L, batch);
             const long long msel = (long long)batch * L.out_h * L.out_w;    // rows of THIS launch (a.M is the end of its pixel range)
 #if PP_SPLIT_MODE != 0
-            if (!sep_k4_runs(a.wt16, a.cin, L.n_total, msel, ablate) &&
-                sep_p_runs(a.wt16, L.stride, a.cin, L.cout, L.n_total, msel, a.occ, ablate)) {   // depthwise once for 256 channels
+            if (!sep_k4_runs(a.wt16, a.cin, L.n_total, msel) &&
+                sep_p_runs(a.wt16, L.stride, a.cin, L.cout, L.n_total, msel, a.occ)) {   // depthwise once for 256 channels
                 launch_p(a, s);
             } else
 #endif
-            if (!(ablate & 16) && sep_k4_runs(a.wt16, a.cin, L.n_total, msel, ablate)) {   // small map
+            if (sep_k4_runs(a.wt16, a.cin, L.n_total, msel)) {   // small map
                 if (L.stride == 1) launch_k4<1>(a, L.n_total, s);
                 else launch_k4<2>(a, L.n_total, s);
             } else if (L.stride == 1) {
@@ -2800,17 +2675,17 @@ int launch_layer(const LayerDesc& L, int batch, float* d_head, hipStream_t s, in
         a.px_h = L.in_h; a.px_w = L.in_w; a.epi = 1;
         a.M = batch * L.in_h * L.in_w;
         if (L.cout % 32 != 0) return PP_ERR_UNSUPPORTED;
-        if (deconv_uniform(L, ablate) && deconv_k4_runs(L, a.M, ablate)) {   // small map: split-K
+        if (deconv_uniform(L) && deconv_k4_runs(L, a.M)) {   // small map: split-K
             if (L.cout % 128 == 0) launch_deconv_k4<128>(a, L.n_total, s);
             else if (L.cout % 64 == 0) launch_deconv_k4<64>(a, L.n_total, s);
             else launch_deconv_k4<32>(a, L.n_total, s);
 #if PP_SPLIT_MODE != 0
-        } else if (deconv_uniform(L, ablate) && deconv_r_runs(L, ablate)) {   // input resident in registers
+        } else if (deconv_uniform(L) && deconv_r_runs(L)) {   // input resident in registers
             if (L.cin == 256) launch_deconv_r<256>(a, s);
             else if (L.cin == 128) launch_deconv_r<128>(a, s);
             else launch_deconv_r<64>(a, s);
 #endif
-        } else if (deconv_uniform(L, ablate)) {
+        } else if (deconv_uniform(L)) {
             if (L.cout % 128 == 0) launch_deconv_u<128>(a, L.n_total, s);
             else if (L.cout % 64 == 0) launch_deconv_u<64>(a, L.n_total, s);
             else launch_deconv_u<32>(a, L.n_total, s);

@@ -272,11 +272,11 @@ __global__ __launch_bounds__(256) void k_pfn_canvas2(PfnParams p) {
     // a wave's PFN2_CW cells are spread over the map (cell = wave id + c * waves per frame), not contiguous:
     // points cluster (a person is a few dozen neighbouring cells with up to T points each), and a wave that owned
     // eight neighbouring crowded cells ran 30x longer than the average one -- the kernel's duration was its tail
-    // (sparse canvas: contiguous cells instead -- on a mostly empty grid whole waves then have nothing to do)
+    // (PIL: contiguous pillars of the list instead)
     // cell stride: waves per frame (NW * PFN2_CW >= ncanvas; the anchor-mask workgroup does not count) or 1
     const int bx = (int)blockIdx.x - amb;
-    const int NW = p.sparse ? 1 : ((int)gridDim.x - amb) * 4;
-    const int wid = (PIL || p.sparse) ? (bx * 4 + wave) * PFN2_CW : bx * 4 + wave;   // first cell (PIL: first pillar)
+    const int NW = PIL ? 1 : ((int)gridDim.x - amb) * 4;
+    const int wid = PIL ? (bx * 4 + wave) * PFN2_CW : bx * 4 + wave;   // first cell (PIL: first pillar)
     const int np_frame = PIL ? p.npillars[b] : 0;
     if (PIL ? (wid >= np_frame) : (wid >= ncanvas)) return;
     const int ncells = PIL ? min(PFN2_CW, np_frame - wid) : min(PFN2_CW, (ncanvas - wid + NW - 1) / NW);
@@ -321,8 +321,8 @@ __global__ __launch_bounds__(256) void k_pfn_canvas2(PfnParams p) {
             pid = p.cellmap[((size_t)b * nz + z) * ncanvas + wid + c * NW];
         }
     }
-    // sparse canvas: most waves of a mostly empty grid have nothing to write -- leave before any other work
-    if (p.sparse && __ballot(pid >= 0) == 0ull) return;
+    // sparse canvas (PIL): a wave with nothing to write leaves before any other work
+    if (PIL && __ballot(pid >= 0) == 0ull) return;
     if (lane < NS) {
         const int c = slot_cell;
         if (pid >= 0) {
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(256) void k_pfn_canvas2(PfnParams p) {
     const int incl = wave_inclusive_scan(cnt);
     const int excl = incl - cnt;
     const int tot = __builtin_amdgcn_readlane(incl, 63);
-    if (p.sparse && tot == 0) return;                 // sparse canvas: nothing to write for cells without pillars
+    if (PIL && tot == 0) return;                      // sparse canvas: nothing to write for cells without pillars
     const float* src = p.pts_sorted + (size_t)n0 * F;   // this frame's pillar-sorted points: a slot is one contiguous run
 
     // one batch = stream positions base..base+63, one per lane: slot, coordinates
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(256) void k_pfn_canvas2(PfnParams p) {
     auto write_cell = [&](int c) {
         // sparse canvas: cells without a pillar are not written at all (the first layer looks the cell up in
         // the cell map and reads zeros); writing the zeros of an almost empty grid is most of the traffic
-        if (ch_ok && (cell_dirty || !p.sparse)) {
+        if (ch_ok && (cell_dirty || !PIL)) {
             float* dst = PIL ? cbase + (size_t)__builtin_amdgcn_readlane(col_xy, c) * C + ch0 : cbase + (size_t)c * cstep + ch0;
             if constexpr (CPL == 4) *reinterpret_cast<float4*>(dst) = make_float4(acc[0], acc[1], acc[2], acc[3]);
             else if constexpr (CPL == 2) *reinterpret_cast<float2*>(dst) = make_float2(acc[0], acc[1]);
@@ -488,7 +488,7 @@ __global__ __launch_bounds__(256) void k_pfn_canvas2(PfnParams p) {
     while (cur_cell < ncells) { write_cell(cur_cell); ++cur_cell; }
 }
 
-// PP_PFN_KERNEL=1 selects the first-generation kernel for the fused path (A/B timing)
+// PP_PFN_KERNEL=1 selects the first-generation kernel for the fused path
 static bool pfn_first_generation();
 // the extra anchor-mask workgroups ride in the second-generation CSR kernel only (dense canvas, grid fits the LDS image)
 bool pfn_can_carry_anchor_mask(const PfnParams& p, bool padded_source) {
@@ -504,16 +504,10 @@ static bool pfn_first_generation() {
     return v == 1;
 }
 
-static bool pfn_cell_centric_sparse() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("PP_PFN_SPARSE_CELLS"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
-}
-
 // does launch_pfn run the pillar-centric kernel (the one that sets the occupancy bitmap) for these parameters?
 static bool pfn_pillar_centric(const PfnParams& p, bool padded) {
     return !padded && !p.with_distance && p.sparse && p.pillar_cell != nullptr && p.npillars != nullptr && PFN2_CW * p.nz <= 64 &&
-           !pfn_first_generation() && !pfn_cell_centric_sparse();
+           !pfn_first_generation();
 }
 bool pfn_writes_occbits(const PfnParams& p, bool padded) { return pfn_pillar_centric(p, padded); }
 
@@ -527,7 +521,7 @@ static void launch_pfn_t(const PfnParams& p, bool padded, hipStream_t s) {
     } else if (padded) {
         PP_LAUNCH("k_pfn_canvas", (k_pfn_canvas<CPL, F, true>), grid, dim3(256), 0, s, p);
     } else if (pfn_pillar_centric(p, padded)) {
-        // sparse canvas: a wave per PFN2_CW pillars of the voxeliser's list (PP_PFN_SPARSE_CELLS=1: the cell-centric walk)
+        // sparse canvas: a wave per PFN2_CW pillars of the voxeliser's list
         dim3 gridp((p.max_voxels + 4 * PFN2_CW - 1) / (4 * PFN2_CW), p.batch);
         PP_LAUNCH("k_pfn_canvas2", (k_pfn_canvas2<CPL, F, true>), gridp, dim3(256), 0, s, p);
     } else if (PFN2_CW * p.nz <= 64 && !pfn_first_generation()) {

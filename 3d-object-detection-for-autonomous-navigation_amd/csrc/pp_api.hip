@@ -67,7 +67,7 @@ struct pp_engine {
     bool vox_ahead = false;               // the resident batch was voxelised at upload time (pp_detect_async skips it)
     bool prevox_issued = false;           // a voxeliser launch is (or was) queued on the copy stream: a main-stream one waits for ev_up
     // ... and the other direction: a voxeliser launch is (or was) queued on the main stream (the zero-copy, synchronous and
-    // device feeds, PP_PREVOX=0, profiling, the stage call, training), so the next copy-stream one waits for ev_vox_main
+    // device feeds, profiling, the stage call, training), so the next copy-stream one waits for ev_vox_main
     bool main_vox_pending = false;
     hipEvent_t ev_vox_main = nullptr;     // recorded on the main stream (outside any capture) by that wait
     int results_buf = 0;                  // set the last pp_detect_async read (pp_fetch_intermediates)
@@ -107,7 +107,6 @@ struct pp_engine {
     int* d_integ = nullptr;
     unsigned long long* d_occbits = nullptr;   // [B][ny][occ_words(nx)] occupancy bitmap of the sparse-canvas passes
     bool occbits_live = false;                 // this pass's PFN launch wrote it (the pillar-centric kernel)
-    bool ablate_vox_done = false;              // PP_ABLATE_STAGES bit 1 (timing experiments)
     uint8_t* d_mask = nullptr;
     float* d_anchors = nullptr;
     int* d_cells = nullptr;
@@ -191,14 +190,6 @@ struct pp_engine {
 
 namespace {
 
-// PP_CU_PARTITION=n (measurement switch, default 0 = off): n compute units of every XCD are reserved for the upload /
-// voxeliser stream, the handles' own streams get the other 32 - n, and the persistent grids are sized for those
-static int cu_partition() {
-    static int v = -1;
-    if (v < 0) { const char* s = getenv("PP_CU_PARTITION"); v = s ? atoi(s) : 0; if (v < 0 || v > 16) v = 0; }
-    return v;
-}
-
 // process-wide upload stream of a device (created on first use, lives as long as the process)
 hipStream_t device_copy_stream(int device) {
     static std::mutex mu;
@@ -207,12 +198,7 @@ hipStream_t device_copy_stream(int device) {
     auto it = streams.find(device);
     if (it != streams.end()) return it->second;
     hipStream_t s = nullptr;
-    const int part = cu_partition();
-    if (part > 0) {   // experiment (PP_CU_PARTITION): the upload + voxeliser stream on `part` CUs of every XCD, the handles' on the rest
-        uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int i = 0; i < 8 * part; ++i) mask[i >> 5] |= 1u << (i & 31);
-        if (hipExtStreamCreateWithCUMask(&s, 8, mask) != hipSuccess) return nullptr;
-    } else if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return nullptr;
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return nullptr;
     streams[device] = s;
     return s;
 }
@@ -488,15 +474,11 @@ const unsigned* sorted_idx(pp_engine* e) {
     return (voxel_sort_passes(e->cfg.max_voxels) % 2 == 0) ? e->d_idxA : e->d_idxB;
 }
 
-// largest batch whose anchor masks ride in the PFN launch (PP_MASK_IN_PFN=0: never, =n: up to n frames).  Few frames
-// only: the 32 KB LDS image the extra workgroups declare caps EVERY workgroup of the launch at 5 per CU, and a full
-// chip of PFN workgroups lives on occupancy (B = 64: 73 -> 99 us with the masks inside, against 14 us for the three
-// mask kernels by themselves); on one frame the launch is 14.7 us instead of 12.2 + 8.8.
-static int anchor_mask_in_pfn_max_batch() {
-    static int v = -1;
-    if (v < 0) { const char* s = getenv("PP_MASK_IN_PFN"); v = s ? atoi(s) : 8; }
-    return v;
-}
+// largest batch whose anchor masks ride in the PFN launch.  Few frames only: the 32 KB LDS image the extra workgroups
+// declare caps EVERY workgroup of the launch at 5 per CU, and a full chip of PFN workgroups lives on occupancy (B = 64:
+// 73 -> 99 us with the masks inside, against 14 us for the three mask kernels by themselves); on one frame the launch
+// is 14.7 us instead of 12.2 + 8.8.
+static constexpr int kAnchorMaskInPfnMaxBatch = 8;
 
 int run_pfn(pp_engine* e, int batch, bool padded, float* feat_out, bool with_mask = false) {
     PfnParams p;
@@ -522,7 +504,7 @@ int run_pfn(pp_engine* e, int batch, bool padded, float* feat_out, bool with_mas
     if (!e->occbits_live) p.occbits = nullptr;
     e->vox[e->in_buf].occ_cleared = false;
     e->mask_in_pfn = false;
-    if (with_mask && batch <= anchor_mask_in_pfn_max_batch() && pfn_can_carry_anchor_mask(p, padded)) {
+    if (with_mask && batch <= kAnchorMaskInPfnMaxBatch && pfn_can_carry_anchor_mask(p, padded)) {
         // the anchor mask (needs the cell map only, read by the post-process only) rides in this launch
         p.am_cells = e->d_cells; p.am_A = e->A; p.am_threshold = e->cfg.anchor_area_threshold; p.am_mask = e->d_mask;
         e->mask_in_pfn = true;
@@ -536,9 +518,7 @@ int run_pfn(pp_engine* e, int batch, bool padded, float* feat_out, bool with_mas
 
 int run_anchor_mask(pp_engine* e, int batch) {
     ProfScope ps(e, nullptr);   // three kernels, each under its own name
-    static int bits = -1;       // PP_ANCHOR_MASK_BITS=0: the integral-image kernels on the sparse-canvas path too
-    if (bits < 0) { const char* s_ = getenv("PP_ANCHOR_MASK_BITS"); bits = (s_ && s_[0] == '0') ? 0 : 1; }
-    if (bits && e->occbits_live && e->nz == 1) {   // one z-cell: a bit of the occupancy bitmap is the pillar count
+    if (e->occbits_live && e->nz == 1) {   // one z-cell: a bit of the occupancy bitmap is the pillar count
         launch_anchor_mask_bits(e->d_occbits, batch, e->ny, e->nx, e->d_cells, e->A, e->cfg.anchor_area_threshold, e->d_mask,
                                 e->stream);
         HIPCHK(e, hipGetLastError());
@@ -621,7 +601,7 @@ int run_backbone(pp_engine* e, int batch) {
                 // sparse first layer: the occupancy bitmap when this pass's PFN launch left one, else the cell map
                 if (k == 0 && L.d_occ != nullptr) { L.d_occ = e->d_cellmap; L.d_occbits = e->occbits_live ? e->d_occbits : nullptr; }
                 ProfScope ps(e, e->layer_tags[k].c_str());
-                int st = launch_layer(L, nb, e->d_head, e->stream, 0, f0);
+                int st = launch_layer(L, nb, e->d_head, e->stream, f0);
                 if (st) return fail(e, st, "layer %s: unsupported shape (cin=%d cout=%d)", L.name, L.cin, L.cout);
             }
         }
@@ -763,24 +743,8 @@ int pp_create(const pp_config* cfg, int device, pp_handle* out) {
     pp_engine* e = new pp_engine();
     e->cfg = *cfg;
     e->device = device;
-    {   // PP_SUBBATCH=0 / PP_SUBBATCH_MB=n: the default of pp_set_cache_budget for handles of this process
-        const char* s0 = getenv("PP_SUBBATCH");
-        const char* s1 = getenv("PP_SUBBATCH_MB");
-        if (s1) e->cache_budget_mb = std::max(0, atoi(s1));
-        if (s0 && s0[0] == '0') e->cache_budget_mb = 0;
-    }
     hipError_t st = hipSetDevice(device);
-    if (st == hipSuccess) {
-        const int part = cu_partition();
-        if (part > 0) {
-            uint32_t mask[8];
-            for (int w = 0; w < 8; ++w) mask[w] = 0xffffffffu;
-            for (int i = 0; i < 8 * part; ++i) mask[i >> 5] &= ~(1u << (i & 31));
-            st = hipExtStreamCreateWithCUMask(&e->stream, 8, mask);
-        } else {
-            st = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
-        }
-    }
+    if (st == hipSuccess) st = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
     if (st != hipSuccess) {
         fail(nullptr, PP_ERR_HIP, "pp_create: %s", hipGetErrorString(st));
         delete e;
@@ -789,7 +753,7 @@ int pp_create(const pp_config* cfg, int device, pp_handle* out) {
     {
         int ncu = 0;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0)
-            g_num_cus = ncu - 8 * cu_partition();
+            g_num_cus = ncu;
     }
     for (int j = 0; j < 3; ++j) {
         e->geom.lo[j] = cfg->pc_range[j];
@@ -968,7 +932,7 @@ int pp_create(const pp_config* cfg, int device, pp_handle* out) {
             e->layer_tags.assign(e->layers.size(), std::string());
             const float* cur = e->d_canvas;
             int pp = 0;
-            if (e->fuse_heads && !getenv("PP_NO_CLS_PLANE")) {   // the last branch finishes the head sums
+            if (e->fuse_heads) {   // the last branch finishes the head sums
                 LayerDesc* last = nullptr;
                 for (LayerDesc& L : e->layers) if (L.kind == LAYER_DECONV) last = &L;
                 if (last && last->head_mode == 2) {
@@ -1148,8 +1112,7 @@ int pp_finalize_weights(pp_handle e) {
         const char* env = getenv("PP_DENSE_CANVAS");
         const long long cells = (long long)e->ny * e->nx;
         LayerDesc& L0 = e->layers[0];
-        const bool force = env && env[0] == '0';     // measurement switch: sparse wherever the kernels support it
-        e->sparse_canvas = !(env && env[0] == '1') && (force || (cells >= 32768 && 4ll * e->cfg.max_voxels <= cells)) &&
+        e->sparse_canvas = !(env && env[0] == '1') && cells >= 32768 && 4ll * e->cfg.max_voxels <= cells &&
                            L0.in == e->d_canvas && sparse_input_supported(L0, e->B);
         L0.d_occ = e->sparse_canvas ? e->d_cellmap : nullptr;
         L0.occ_nz = e->nz;
@@ -1206,11 +1169,6 @@ static bool pinned_block_holds(const void* p, size_t bytes) {
     if (it == g_pinned.begin()) return false;
     --it;
     return a >= it->first && a + bytes <= it->first + it->second;
-}
-static bool zero_copy_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* s = getenv("PP_NO_ZERO_COPY"); v = (s && s[0] == '1') ? 0 : 1; }
-    return v != 0;
 }
 
 // Small batch, page-locked points: nothing is copied and no HIP call is made besides one event query -- the
@@ -1269,7 +1227,7 @@ int pp_upload_points_async(pp_handle e, const float* points_pinned, const int32_
     int st = check_batch(e, batch); if (st) return st;
     if (frame_offsets && batch >= 1 && frame_offsets[batch] > 0 && !points_pinned)
         return fail(e, PP_ERR_ARG, "pp_upload_points_async: points is NULL");
-    if (frame_offsets && batch >= 1 && batch <= PP_ZC_MAX_BATCH && zero_copy_enabled()) {
+    if (frame_offsets && batch >= 1 && batch <= PP_ZC_MAX_BATCH) {
         st = feed_zero_copy(e, points_pinned, frame_offsets, batch);
         if (st != PP_ERR_UNSUPPORTED) return st;      // (not device-mapped memory: the copy below still works)
     }
@@ -1278,12 +1236,10 @@ int pp_upload_points_async(pp_handle e, const float* points_pinned, const int32_
     st = set_offsets(e, frame_offsets, batch, e->copy_stream); if (st) return st;
     const size_t n = (size_t)frame_offsets[batch];
     if (n) HIPCHK(e, hipMemcpyAsync(e->d_points, points_pinned, n * e->F * sizeof(float), hipMemcpyHostToDevice, e->copy_stream));
-    // Voxelise right here, behind the copy and beside the pass in flight (PP_PREVOX=0: inside pp_detect_async as before).
-    // Not while per-launch times are collected (their events belong to the main stream's pass) and not on a handle that
-    // trains (pp_train_step voxelises inside its own graphs).
-    static int prevox = -1;
-    if (prevox < 0) { const char* s_ = getenv("PP_PREVOX"); prevox = (s_ && s_[0] == '0') ? 0 : 1; }
-    if (prevox && e->prof <= 0 && e->train == nullptr) {
+    // Voxelise right here, behind the copy and beside the pass in flight.  Not while per-launch times are collected
+    // (their events belong to the main stream's pass) and not on a handle that trains (pp_train_step voxelises inside
+    // its own graphs).
+    if (e->prof <= 0 && e->train == nullptr) {
         // The voxeliser's scratch (cells, keys, sorted indices) exists once per handle: a voxeliser queued on the main
         // stream -- the pass in flight, if it was fed by zero-copy / pp_upload_points / pp_upload_points_device -- must
         // be through before this one overwrites it.  Only after such a pass: copy feed after copy feed adds no wait.
@@ -1386,28 +1342,12 @@ static int graph_bucket(const pp_engine* e, int max_n) {
 // the whole fused pipeline of one batch, enqueued on e->stream (plain launches or under stream capture)
 static int enqueue_detect(pp_engine* e, int B, int max_n) {
     int st;
-    // PP_ABLATE_STAGES (timing experiments only, WRONG results): bit 1 = the single-workgroup-per-frame voxeliser
-    // kernel is left out after the handle's first pass (later passes reuse its products), bit 2 = no post-process.
-    // What the step gains without them is what splitting them over more workgroups could gain at most.
-    static int abl = -1;
-    if (abl < 0) { const char* s_ = getenv("PP_ABLATE_STAGES"); abl = s_ ? atoi(s_) : 0; }
-    if (!e->vox_ahead && !((abl & 1) && e->ablate_vox_done)) {
-        if ((st = run_voxelize(e, B, max_n))) return st;
-        e->ablate_vox_done = true;
-    }
+    if (!e->vox_ahead && (st = run_voxelize(e, B, max_n))) return st;
     if ((st = run_pfn(e, B, false, nullptr, true))) return st;
     if (!e->mask_in_pfn && (st = run_anchor_mask(e, B))) return st;
     if ((st = run_backbone(e, B))) return st;
-    // the post-process stores its few kept detections per frame straight into the page-locked result buffers (PP_POST_COPY=1:
-    // the two device-to-host copy nodes of rounds 1-3 instead)
-    static int post_copy = -1;
-    if (post_copy < 0) { const char* s = getenv("PP_POST_COPY"); post_copy = (s && s[0] == '1') ? 1 : 0; }
-    if (!(abl & 2) && (st = run_post(e, B, post_copy == 0))) return st;
-    if (post_copy) {
-        HIPCHK(e, hipMemcpyAsync(e->h_dets, e->d_dets, (size_t)B * e->cfg.nms_post_max_size * sizeof(pp_detection), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(e, hipMemcpyAsync(e->h_ndets, e->d_ndets, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    }
-    return PP_OK;
+    // the post-process stores its few kept detections per frame straight into the page-locked result buffers
+    return run_post(e, B, true);
 }
 
 static bool graphs_enabled() {
@@ -1778,51 +1718,24 @@ const char* pp_layer_tag(pp_handle e, int32_t layer) {
     return e->layer_tags[layer].c_str();
 }
 
-extern long long* g_stamps;
-
 int pp_bench_layer(pp_handle e, int32_t layer, int32_t batch, int32_t reps, int32_t ablate, float* avg_ms) {
     if (!e) return PP_ERR_ARG;
     if (!avg_ms || reps < 1 || layer < 0 || layer >= (int)e->layers.size()) return fail(e, PP_ERR_ARG, "pp_bench_layer: bad argument");
+    if (ablate != 0) return fail(e, PP_ERR_ARG, "pp_bench_layer: ablate must be 0 (the kernel ablation bits were removed)");
     if (!e->weights_ready) return fail(e, PP_ERR_STATE, "pp_bench_layer: weights not finalised");
     (void)hipSetDevice(e->device);
     int st = check_batch(e, batch); if (st) return st;
     const LayerDesc& L = e->layers[layer];
-    if ((ablate & 64) && !g_stamps) HIPCHK(e, hipMalloc((void**)&g_stamps, (4096 * 8 + 64 * 64) * sizeof(long long)));
     for (int i = 0; i < 2; ++i)
-        if ((st = launch_layer(L, batch, e->d_head, e->stream, ablate))) return fail(e, st, "pp_bench_layer: unsupported layer");
+        if ((st = launch_layer(L, batch, e->d_head, e->stream))) return fail(e, st, "pp_bench_layer: unsupported layer");
     HIPCHK(e, hipEventRecord(e->t0, e->stream));
-    for (int i = 0; i < reps; ++i) launch_layer(L, batch, e->d_head, e->stream, ablate);
+    for (int i = 0; i < reps; ++i) launch_layer(L, batch, e->d_head, e->stream);
     HIPCHK(e, hipEventRecord(e->t1, e->stream));
     HIPCHK(e, hipEventSynchronize(e->t1));
     HIPCHK(e, hipGetLastError());
     float ms = 0.f;
     HIPCHK(e, hipEventElapsedTime(&ms, e->t0, e->t1));
     *avg_ms = ms / reps;
-    if (ablate & 64) {   // in-kernel stamps of one extra launch -> stderr (tuning aid)
-        const size_t n = 4096 * 8 + 64 * 64;
-        std::vector<long long> hs(n, 0);
-        HIPCHK(e, hipMemsetAsync(g_stamps, 0, n * sizeof(long long), e->stream));
-        launch_layer(L, batch, e->d_head, e->stream, ablate);
-        HIPCHK(e, hipMemcpyAsync(hs.data(), g_stamps, n * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (const char* path = getenv("PP_STAMPS_OUT")) {   // raw dump for offline analysis
-            if (FILE* f = fopen(path, "wb")) { fwrite(hs.data(), sizeof(long long), n, f); fclose(f); }
-        }
-        for (int blk : {0, 1, 8, 63}) {
-            for (int role = 0; role < 2; ++role) {
-                const long long* st = hs.data() + ((size_t)blk * 2 + role) * 160;
-                const long long t0 = hs[((size_t)blk * 2 + 0) * 160];
-                fprintf(stderr, "blk %2d %s:", blk, role ? "prod" : "cons");
-                for (int i = 0; i < 20; ++i) {
-                    if (!st[i * 4 + 3] && !st[i * 4]) continue;
-                    fprintf(stderr, " [%d: %lld %lld %lld %lld]", i, st[i * 4] ? st[i * 4] - t0 : -1, st[i * 4 + 1] ? st[i * 4 + 1] - t0 : -1,
-                            st[i * 4 + 2] ? st[i * 4 + 2] - t0 : -1, st[i * 4 + 3] ? st[i * 4 + 3] - t0 : -1);
-                }
-                if (!role) fprintf(stderr, " end=%lld", st[39 * 4 + 1] ? st[39 * 4 + 1] - t0 : -1);
-                fprintf(stderr, "\n");
-            }
-        }
-    }
     return PP_OK;
 }
 

@@ -614,32 +614,21 @@ static void gemm_tag(const std::string& what) {
     g_gemm_tag = pool.back()->c_str();
 }
 
-template <int WM, int WN, int KCH>
+// 64 x 64 tiles (WM = WN = 1)
+template <int KCH>
 static void launch_gemm2(const TGemm2& a2, bool akc, bool bkc, dim3 grid, hipStream_t s) {
-    if (akc && bkc) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2<WM, WN, true, true, KCH>), grid, dim3(256), 0, s, a2);
-    else if (akc) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2<WM, WN, true, false, KCH>), grid, dim3(256), 0, s, a2);
-    else if (bkc) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2<WM, WN, false, true, KCH>), grid, dim3(256), 0, s, a2);
-    else PP_LAUNCH(g_gemm_tag, (k_tr_gemm2<WM, WN, false, false, KCH>), grid, dim3(256), 0, s, a2);
+    if (akc && bkc) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2<1, 1, true, true, KCH>), grid, dim3(256), 0, s, a2);
+    else if (akc) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2<1, 1, true, false, KCH>), grid, dim3(256), 0, s, a2);
+    else if (bkc) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2<1, 1, false, true, KCH>), grid, dim3(256), 0, s, a2);
+    else PP_LAUNCH(g_gemm_tag, (k_tr_gemm2<1, 1, false, false, KCH>), grid, dim3(256), 0, s, a2);
 }
 
 // rows of the statistics partials a forward product leaves ([tiles][2][N]; 0: the split kernel did not run)
 static thread_local int g_last_stat_tiles = 0;
-static const int g_num_cus_train = 256;      // (MI355X; only a threshold for the tile choice below)
 
 // a launch with fewer workgroups than this lives on memory latency, not on throughput: 64-wide K chunks (half the
 // dependent load -> LDS -> MFMA rounds), and the two gradient products of a layer share one launch
-static long tr_latency_wgs() {      // PP_TRAIN_LATENCY_WGS (A/B measurements)
-    static long v = -1;
-    if (v < 0) { const char* e = getenv("PP_TRAIN_LATENCY_WGS"); v = e ? atol(e) : 512; }
-    return v;
-}
-#define TR_LATENCY_WGS tr_latency_wgs()
-// PP_TRAIN_WIDE=0: 32-wide chunks everywhere (A/B measurements)
-static bool wide_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("PP_TRAIN_WIDE"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v == 1;
-}
+static constexpr long TR_LATENCY_WGS = 512;
 
 // C[M][N] (+)= A(m,k) * B(k,n) [+ bias(n)],  A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn]
 // defer: a split-K product whose result only the optimizer reads (weight gradients) keeps its partial tiles in a
@@ -695,42 +684,19 @@ static void tr_gemm(const TrainCtx& cx, const GemmCall& c) {
         const bool akc = c.sak == 1, bkc = c.sbk == 1;
         int kper = ((K + ksplit - 1) / ksplit + 31) / 32 * 32;
         const long small = (long)((M + 63) / 64) * ((N + 63) / 64) * ((K + kper - 1) / kper);
-        const bool wide = small < TR_LATENCY_WGS && wide_enabled();        // 64-wide chunks
+        const bool wide = small < TR_LATENCY_WGS;        // 64-wide chunks
         if (wide) kper = (kper + 63) / 64 * 64;
         ksplit = (K + kper - 1) / kper;
         g.kper = kper;
         TGemm2 a2{g, (ksplit == 1) ? c.stat_part : nullptr, 0, 0, ksplit};
-        // 64 x 64 tiles everywhere by default: five workgroups per CU (88 VGPRs, 30 KB of LDS) whose load -> split ->
-        // LDS -> MFMA phases overlap each other's; the 128-row / 128-column instantiations (two or four accumulator
-        // tiles per wave sharing their fragments, two / three workgroups per CU) stay selectable for measurements.
-        // PP_TRAIN_TILE_THR = workgroups a launch must still have for a larger tile; products of a B=32 step:
-        // 128 -> 2.32 ms, 256 -> 2.22, 512 -> 2.16, 1024 -> 2.13, 2048 -> 2.05, 4096 -> 2.01, never -> 2.00
-        const long big = (long)((M + 127) / 128) * ((N + 127) / 128) * ksplit;
-        const long tall = (long)((M + 127) / 128) * ((N + 63) / 64) * ksplit;
-        static long thr = -1;
-        if (thr < 0) { const char* e = getenv("PP_TRAIN_TILE_THR"); thr = e ? atol(e) : (1l << 40); }
-        // ... except for the products that are bound by the matrix pipe, not by memory: a long K against few bytes per
-        // output (the transposed convolutions' forward and input-gradient products at a full-chip batch).  There the
-        // 128 x 128 tile reads each LDS fragment for two accumulator tiles (PP_TRAIN_BIG_FLOPB: least FLOPs per byte of
-        // operand + result traffic for the large tile; 0 = never)
-        static double big_fb = -1.0;
-        if (big_fb < 0) { const char* e = getenv("PP_TRAIN_BIG_FLOPB"); big_fb = e ? atof(e) : 0.0; }
-        const double flop_per_byte = 2.0 * M * (double)N * K / (4.0 * ((double)M * K + (double)K * N + (double)M * N));
-        const bool compute_bound = big_fb > 0.0 && flop_per_byte >= big_fb && big >= 2 * g_num_cus_train && ksplit == 1;
-        if (N >= 128 && M > 64 && (big >= thr || compute_bound)) {
-            dim3 grid((N + 127) / 128, (M + 127) / 128, ksplit);
-            if (a2.stat_part) g_last_stat_tiles = (int)grid.y;
-            launch_gemm2<2, 2, 32>(a2, akc, bkc, grid, cx.stream);
-        } else if (M > 64 && tall >= thr) {      // (M <= 64: half of a 128-row tile would be zero rows -- the 64-channel weight gradients)
-            dim3 grid((N + 63) / 64, (M + 127) / 128, ksplit);
-            if (a2.stat_part) g_last_stat_tiles = (int)grid.y;
-            launch_gemm2<2, 1, 32>(a2, akc, bkc, grid, cx.stream);
-        } else {
-            dim3 grid((N + 63) / 64, (M + 63) / 64, ksplit);
-            if (a2.stat_part) g_last_stat_tiles = (int)grid.y;
-            if (wide) launch_gemm2<1, 1, 64>(a2, akc, bkc, grid, cx.stream);
-            else launch_gemm2<1, 1, 32>(a2, akc, bkc, grid, cx.stream);
-        }
+        // 64 x 64 tiles: five workgroups per CU (88 VGPRs, 30 KB of LDS) whose load -> split -> LDS -> MFMA phases
+        // overlap each other's.  (Measured against 128-row / 128-column tiles, two or four accumulator tiles per wave
+        // sharing their fragments, by the workgroups a launch must still have for the larger tile; products of a B=32
+        // step: 128 -> 2.32 ms, 256 -> 2.22, 512 -> 2.16, 1024 -> 2.13, 2048 -> 2.05, 4096 -> 2.01, never -> 2.00)
+        dim3 grid((N + 63) / 64, (M + 63) / 64, ksplit);
+        if (a2.stat_part) g_last_stat_tiles = (int)grid.y;
+        if (wide) launch_gemm2<64>(a2, akc, bkc, grid, cx.stream);
+        else launch_gemm2<32>(a2, akc, bkc, grid, cx.stream);
         if (ksplit > 1) gemm_finish_split(cx, c, g, ksplit);
         return;
     }
@@ -749,20 +715,18 @@ static void tr_gemm(const TrainCtx& cx, const float* A, long sam, long sak, cons
 }
 
 // The weight-gradient product (w: TN form, split-K, deferred reduction) and the input-gradient product (d) of one
-// layer.  While both are a few hundred workgroups they go out as ONE launch (k_tr_gemm2_pair); otherwise one by one.
+// layer.  When both fit the split kernel's forms they go out as ONE launch (k_tr_gemm2_pair); otherwise one by one.
 static void tr_gemm_pair(const TrainCtx& cx, const GemmCall& w, const GemmCall& d) {
     const bool forms = w.sak != 1 && w.sbk != 1 && d.sak == 1;
     if (forms && gemm2_eligible(w) && gemm2_eligible(d) && w.defer && w.stat_part == nullptr && d.stat_part == nullptr) {
         // 64-wide chunks while the launch lives on latency, the 32-wide ones (five workgroups per CU) beyond: two
         // half-filled launches of a large batch -- block3's 640 + 640 workgroups at B=32 -- fill the chip together
-        static int pair_big = -1;      // PP_TRAIN_PAIR_BIG=0: pairs only in the latency regime (the round-3 first version)
-        if (pair_big < 0) { const char* e = getenv("PP_TRAIN_PAIR_BIG"); pair_big = (e && e[0] == '0') ? 0 : 1; }
         int ks1, ks2, kper1, kper2, n1, n2;
         TGemm g1 = gemm_args(cx, w, ks1);
         int ksd;
         (void)gemm_args(cx, d, ksd);
         const auto tiles = [](const GemmCall& c) { return (long)((c.M + 63) / 64) * ((c.N + 63) / 64); };
-        const bool wide = tiles(w) * ks1 + tiles(d) * ksd < 2 * TR_LATENCY_WGS && wide_enabled();
+        const bool wide = tiles(w) * ks1 + tiles(d) * ksd < 2 * TR_LATENCY_WGS;
         const int kround = wide ? 64 : 32;
         auto plan = [kround](const GemmCall& c, int ks, int& kper, int& nks) {
             kper = ((c.K + ks - 1) / ks + kround - 1) / kround * kround;
@@ -777,20 +741,18 @@ static void tr_gemm_pair(const TrainCtx& cx, const GemmCall& w, const GemmCall& 
         TGemm g2 = gemm_args(cx, d, ks2);
         g_arena_used = saved;
         const long wg2 = plan(d, ks2, kper2, n2);
-        if (wide || pair_big) {
-            g1.kper = kper1; g2.kper = kper2;
-            TGemm2 p1{g1, nullptr, (w.N + 63) / 64, (w.M + 63) / 64, n1};
-            TGemm2 p2{g2, nullptr, (d.N + 63) / 64, (d.M + 63) / 64, n2};
-            g_last_stat_tiles = 0;
-            const dim3 grid((unsigned)(wg1 + wg2));
-            if (d.sbk == 1 && wide) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2_pair<true, 64>), grid, dim3(256), 0, cx.stream, p1, p2);
-            else if (d.sbk == 1) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2_pair<true, 32>), grid, dim3(256), 0, cx.stream, p1, p2);
-            else if (wide) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2_pair<false, 64>), grid, dim3(256), 0, cx.stream, p1, p2);
-            else PP_LAUNCH(g_gemm_tag, (k_tr_gemm2_pair<false, 32>), grid, dim3(256), 0, cx.stream, p1, p2);
-            if (n1 > 1) gemm_finish_split(cx, w, g1, n1);                 // deferred: its region is now taken
-            if (n2 > 1) gemm_finish_split(cx, d, g2, n2);                 // reduced at once (from behind that region)
-            return;
-        }
+        g1.kper = kper1; g2.kper = kper2;
+        TGemm2 p1{g1, nullptr, (w.N + 63) / 64, (w.M + 63) / 64, n1};
+        TGemm2 p2{g2, nullptr, (d.N + 63) / 64, (d.M + 63) / 64, n2};
+        g_last_stat_tiles = 0;
+        const dim3 grid((unsigned)(wg1 + wg2));
+        if (d.sbk == 1 && wide) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2_pair<true, 64>), grid, dim3(256), 0, cx.stream, p1, p2);
+        else if (d.sbk == 1) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2_pair<true, 32>), grid, dim3(256), 0, cx.stream, p1, p2);
+        else if (wide) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2_pair<false, 64>), grid, dim3(256), 0, cx.stream, p1, p2);
+        else PP_LAUNCH(g_gemm_tag, (k_tr_gemm2_pair<false, 32>), grid, dim3(256), 0, cx.stream, p1, p2);
+        if (n1 > 1) gemm_finish_split(cx, w, g1, n1);                 // deferred: its region is now taken
+        if (n2 > 1) gemm_finish_split(cx, d, g2, n2);                 // reduced at once (from behind that region)
+        return;
     }
     tr_gemm(cx, w);
     tr_gemm(cx, d);
@@ -799,8 +761,7 @@ static void tr_gemm_pair(const TrainCtx& cx, const GemmCall& w, const GemmCall& 
 // weight gradients: K = rows (pixels); enough slices to fill the chip, bounded by the partial buffer
 static int wgrad_split(const TrainCtx& cx, int M, int N, int K) {
     const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64);
-    static long wgs = -1;      // PP_TRAIN_WGRAD_WGS: workgroups a weight-gradient product is cut into
-    if (wgs < 0) { const char* e = getenv("PP_TRAIN_WGRAD_WGS"); wgs = e ? atol(e) : 1024; }
+    const long wgs = 1024;     // workgroups a weight-gradient product is cut into
     long want = std::max<long>(1, wgs / tiles);
     want = std::min<long>(want, (K + 255) / 256);
     while (want > 1 && want * (long)M * N > cx.gemm_part_floats) --want;
@@ -2317,12 +2278,10 @@ int train_step(const TrainCtx& cx, const TrainShape& s, const std::vector<TrainE
 
     // fused forward of the separable layers (depthwise + product + statistics in one launch, launch_sep_train): from
     // PP_TRAIN_FUSED_MIN output pixels on (below that the layers are a handful of workgroups and the split-K product
-    // kernels are the shorter chain); PP_TRAIN_FUSED=0 turns it off
-    static int fused_on = -1;
+    // kernels are the shorter chain)
     static long fused_min = -1;
-    if (fused_on < 0) { const char* e = getenv("PP_TRAIN_FUSED"); fused_on = (e && e[0] == '0') ? 0 : 1; }
     if (fused_min < 0) { const char* e = getenv("PP_TRAIN_FUSED_MIN"); fused_min = e ? atol(e) : 32768; }
-    bool fused = fused_on && cx.pw16 != nullptr;
+    bool fused = cx.pw16 != nullptr;
     if (fused) {
         SplitPwTable t;
         memset(&t, 0, sizeof(t));
@@ -2375,13 +2334,11 @@ int train_step(const TrainCtx& cx, const TrainShape& s, const std::vector<TrainE
             if (stat_rows > 0) {
                 g_last_stat_tiles = stat_rows;
             } else {
-            static int dwp = -1;      // PP_TRAIN_DWFWD=0: the thread-per-output kernel everywhere (A/B measurements)
-            if (dwp < 0) { const char* e = getenv("PP_TRAIN_DWFWD"); dwp = (e && e[0] == '0') ? 0 : 1; }
             const long nthr = rows * (l.cin / 4);
-            static long dwg = -1, dwm = -1;   // PP_TRAIN_DWFWD_GRID / _MINPX: workgroups of the persistent kernel, least pixels per thread
-            if (dwg < 0) { const char* e = getenv("PP_TRAIN_DWFWD_GRID"); dwg = e ? atol(e) : 1024; }
-            if (dwm < 0) { const char* e = getenv("PP_TRAIN_DWFWD_MINPX"); dwm = e ? atol(e) : 2; }     // (B=32 sweep, grid x pixels: 1024 x 4 0.275 ms, 1280 x 4 0.281, 1280 x 2 0.271, 1024 x 2 0.271, 1280 x 1 0.271, 2048 x 2 0.275; thread-per-output 0.331)
-            if (dwp && nthr >= dwm * dwg * 256) {      // at least dwm pixels per thread on a one-round grid
+            // workgroups of the persistent kernel, least pixels per thread (B=32 sweep, grid x pixels: 1024 x 4 0.275 ms,
+            // 1280 x 4 0.281, 1280 x 2 0.271, 1024 x 2 0.271, 1280 x 1 0.271, 2048 x 2 0.275; thread-per-output 0.331)
+            const long dwg = 1024, dwm = 2;
+            if (nthr >= dwm * dwg * 256) {      // at least dwm pixels per thread on a one-round grid
                 PP_LAUNCH("k_tr_dw_fwd", k_tr_dw_fwd_p, dim3((unsigned)dwg), dim3(256), 0, cx.stream, cur, L.p(pre + "/depthwise_kernel"),
                           tb.D, B, l.in_h, l.in_w, l.out_h, l.out_w, l.cin, l.stride, cur_coef);
             } else {

@@ -405,9 +405,9 @@ class Engine:
         self._check(self._lib.pp_layer_count(self._h, ctypes.byref(n)), "pp_layer_count")
         return [self._lib.pp_layer_tag(self._h, i).decode() for i in range(n.value)]
 
-    def bench_layer(self, layer, batch, reps=20, ablate=0):
+    def bench_layer(self, layer, batch, reps=20):
         t = ctypes.c_float(0)
-        self._check(self._lib.pp_bench_layer(self._h, int(layer), int(batch), int(reps), int(ablate), ctypes.byref(t)),
+        self._check(self._lib.pp_bench_layer(self._h, int(layer), int(batch), int(reps), 0, ctypes.byref(t)),
                     "pp_bench_layer")
         return float(t.value)
 

@@ -177,7 +177,7 @@ int pp_upload_points(pp_handle h, const float* points, const int32_t* frame_offs
  * and the next pass's first kernel reads offsets and points straight from `points_pinned` over the host link while
  * it writes the device copies the later kernels use -- no copy-engine transfer, no event chain (batch 1, upload
  * included: 0.29 -> 0.25 ms).  `points_pinned` must then be device-mapped page-locked memory (pp_host_alloc and
- * hipHostMalloc are; memory that is not falls back to the copy); PP_NO_ZERO_COPY=1 always copies. */
+ * hipHostMalloc are; memory that is not falls back to the copy). */
 int pp_upload_points_async(pp_handle h, const float* points_pinned, const int32_t* frame_offsets, int32_t batch);
 /* Page-locked host memory for the staging buffers above (stateless; any thread). */
 int pp_host_alloc(int64_t bytes, void** out);
@@ -252,8 +252,8 @@ int pp_timer_stop(pp_handle h, float* elapsed_ms); /* records, waits, returns th
 
 /* Kernel-tuning aid: runs RPN layer `layer` (0-based, in launch order; the last one is
  * the heads) `reps` times on whatever the activation buffers hold for `batch` frames and
- * returns the average launch duration.  `ablate` is a debug bit mask (0 = the real
- * kernel; bits switch off phases of the GEMM kernel, results are then wrong). */
+ * returns the average launch duration.  `ablate` must be 0 (PP_ERR_ARG otherwise); the
+ * kernel is the one the pass would launch, chosen by the same environment switches. */
 int pp_bench_layer(pp_handle h, int32_t layer, int32_t batch, int32_t reps, int32_t ablate, float* avg_ms);
 /* Number of RPN layer launches per forward pass and the tag ("<kernel>:<layer>") of one. */
 int pp_layer_count(pp_handle h, int32_t* count);

@@ -215,3 +215,30 @@ def test_bench_accounts_per_launch_when_a_layer_is_walked_in_sub_ranges(pp):
     r = roofs["k_sep_u<64,1,3,1,0>"]
     assert abs(r["algorithmic_bytes_per_launch"] - (lb["block1.1"] + lb["block1.2"]) / 5) < 1.0
     assert abs(r["avg_launch_ms"] - 0.44 / 5) < 1e-9
+
+
+def test_runtime_switch_table_matches_the_code():
+    """INTEGRATION.md's switch table lists exactly the PP_* variables the library reads, and every name in it is read
+    by the library, the Python package or bench.py (no undocumented switch, no stale row)."""
+    pkg = os.path.join(ROOT, "3d-object-detection-for-autonomous-navigation_amd")
+    csrc = os.path.join(pkg, "csrc")
+    native = set()
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".h")):
+            with open(os.path.join(csrc, f)) as fh:
+                native |= set(re.findall(r'getenv\("(PP_[A-Z0-9_]*)"\)', fh.read()))
+    assert native, "no getenv(\"PP_...\") found in csrc"
+    python = set()
+    for path in [os.path.join(pkg, f) for f in os.listdir(pkg) if f.endswith(".py")] + [os.path.join(ROOT, "bench.py")]:
+        with open(path) as fh:
+            python |= set(re.findall(r'["\'](PP_[A-Z0-9_]*)["\']', fh.read()))
+    with open(os.path.join(ROOT, "INTEGRATION.md")) as fh:
+        doc = fh.read()
+    table = doc.split("## 5. Runtime switches", 1)[1].split("\n\n", 2)[1]
+    documented = set()
+    for line in table.splitlines():
+        cells = line.split(" | ")
+        if line.startswith("| `PP_"):
+            documented |= set(re.findall(r"`(PP_[A-Z0-9_]*)", cells[0]))
+    assert not native - documented, f"read by csrc but missing from INTEGRATION.md section 5: {sorted(native - documented)}"
+    assert not documented - native - python, f"documented but read nowhere: {sorted(documented - native - python)}"
