@@ -18,7 +18,7 @@ _INCLUDE = os.path.join(os.path.dirname(_PKG), "include", "pp_hip.h")
 SO_PATH = os.path.join(_PKG, os.environ.get("PP_HIP_LIB", "libpp_hip.so"))
 _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
 SOURCES = ["pp_api.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
-           "rotate_iou.hip", "loss.hip", "optim.hip", "train.hip", "targets.hip"]
+           "rotate_iou.hip", "loss.hip", "optim.hip", "train.hip", "targets.hip", "augment.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
@@ -35,6 +35,7 @@ EXPORTS = [
     "pp_train_layout", "pp_train_layout_entry", "pp_train_step", "pp_train_step_async", "pp_train_step_wait",
     "pp_train_graph_stats", "pp_stream", "pp_train_fetch_decisions",
     "pp_assign_targets", "pp_train_step_gt_async", "pp_train_step_gt",
+    "pp_augment", "pp_train_step_aug_async", "pp_train_step_aug", "pp_augment_selected",
 ]
 
 
@@ -87,6 +88,13 @@ class PPTargetConfig(ctypes.Structure):
         ("matched_threshold", ctypes.c_float),
         ("unmatched_threshold", ctypes.c_float),
         ("reserved", ctypes.c_int32 * 2),
+    ]
+
+
+class PPAugmentConfig(ctypes.Structure):
+    _fields_ = [
+        ("num_try", ctypes.c_int32),
+        ("global_rot_per_object", ctypes.c_int32),
     ]
 
 
@@ -260,6 +268,12 @@ def lib():
                                          ctypes.POINTER(PPTargetConfig)]
     L.pp_train_step_gt.argtypes = [vp, vp, vp, vp, f32p, vp, vp, i32, ctypes.POINTER(PPLossConfig),
                                    ctypes.POINTER(PPTargetConfig), f32p]
+    L.pp_augment.argtypes = [vp, f32p, vp, vp, vp, i32, ctypes.POINTER(PPAugmentConfig), vp, vp, f32p, f32p, vp, vp]
+    L.pp_train_step_aug_async.argtypes = [vp, vp, vp, vp, f32p, vp, vp, i32, ctypes.POINTER(PPLossConfig),
+                                          ctypes.POINTER(PPTargetConfig), vp, ctypes.POINTER(PPAugmentConfig), vp, vp]
+    L.pp_train_step_aug.argtypes = [vp, vp, vp, vp, f32p, vp, vp, i32, ctypes.POINTER(PPLossConfig),
+                                    ctypes.POINTER(PPTargetConfig), vp, ctypes.POINTER(PPAugmentConfig), vp, vp, f32p]
+    L.pp_augment_selected.argtypes = [vp, vp, i64, ctypes.POINTER(i64)]
     L.pp_adamw_step_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, i64, ctypes.c_float, ctypes.c_float,
                                        ctypes.c_float, ctypes.c_float, ctypes.c_float]
     for name in EXPORTS:

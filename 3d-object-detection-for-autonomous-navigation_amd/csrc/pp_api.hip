@@ -117,6 +117,21 @@ struct pp_engine {
     int* d_gt_cnt = nullptr;
     unsigned* d_gt_top = nullptr;      // per box: its best overlap (float bits), reset before every assignment
     uint8_t* d_tmask = nullptr;        // [B][A] the assignment's anchor mask (d_mask stays the inference pass's)
+    // training-time augmentation (pp_augment / pp_train_step_aug*), allocated on first use
+    bool aug_ready = false;
+    float* d_aug_pts = nullptr;        // [B * NMAX][F] the augmented cloud before it replaces the resident one
+    float* d_aug_gt_in = nullptr;      // [B * PP_MAX_GT_PER_FRAME][7] the boxes as given
+    int* d_aug_cls_in = nullptr;
+    uint8_t* d_aug_valid = nullptr;
+    int* d_aug_cnt_in = nullptr;
+    double* d_aug_draws = nullptr;     // [B * PP_MAX_GT_PER_FRAME][PP_AUG_MAX_TRY][5]
+    pp_aug_frame* d_aug_frames = nullptr;
+    AugBox* d_aug_rec = nullptr;
+    float* d_aug_box_tmp = nullptr;
+    uint8_t* d_aug_keep = nullptr;
+    int* d_aug_sel = nullptr;
+    double* d_aug_cs = nullptr;        // [B][2]          // [B * PP_MAX_GT_PER_FRAME] the selected try per input box (pp_augment_selected)
+    int64_t aug_total = 0;             // input boxes of the last augmentation
     int* d_tgt_index = nullptr;        // [B][A] optional outputs of pp_assign_targets, allocated on first use
     float* d_tgt_overlap = nullptr;
     float* d_calib = nullptr;
@@ -135,6 +150,7 @@ struct pp_engine {
     float* d_feat = nullptr;   size_t cap_feat = 0;
 
     int cur_batch = 0, cur_max_n = 0;
+    int cur_total = 0;                    // points of the resident frames (host copy of the last offset)
     int results_batch = 0;        // frames of the last enqueued pp_detect_async (0: no results to fetch)
     // frame offsets travel through a small pinned ring (a pageable source would be staged synchronously and a
     // single pinned buffer could be rewritten while its copy is still queued); a slot is reused only after the
@@ -631,6 +647,7 @@ int run_post(pp_engine* e, int batch, bool to_host = false) {
 void stage_call_done(pp_engine* e) {
     e->cur_batch = 0;
     e->cur_max_n = 0;
+    e->cur_total = 0;
     e->results_batch = 0;
 }
 
@@ -660,6 +677,7 @@ int set_offsets(pp_engine* e, const int32_t* off, int batch, hipStream_t stream)
     memcpy(ring, off, (size_t)(batch + 1) * sizeof(int));
     e->cur_batch = batch;
     e->cur_max_n = max_n;
+    e->cur_total = off[batch];
     const int nb = e->in_buf ^ 1;
     e->in_buf = nb;
     e->d_points = e->d_points_buf[nb];
@@ -1216,6 +1234,7 @@ static int feed_zero_copy(pp_engine* e, const float* points_pinned, const int32_
     e->vox_ahead = false;
     e->cur_batch = batch;
     e->cur_max_n = max_n;
+    e->cur_total = off[batch];
     e->up_pending = false;
     e->zc = true;
     return PP_OK;
@@ -1976,13 +1995,16 @@ int check_gt(pp_engine* e, const char* who, const float* gt_boxes, const int32_t
 // stream then waits for ev_tgt; or the main stream itself), the anchor mask of the resident frames is built from the
 // current cell map when `resident_mask` (else d_tmask holds the caller's), the per-box maxima are reset, then the two
 // passes write d_loss_labels / d_loss_regt (and the optional per-anchor outputs).
+// With `up` == nullptr the boxes, classes and counts are already on the device: the augmentation wrote all three
+// (classes 1 where the caller gave none), so d_gt_cls is read whatever `gt_classes` is.
 int enqueue_targets(pp_engine* e, int batch, const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts,
                     int64_t total, bool resident_mask, const pp_target_config* tc, bool extra, hipStream_t up) {
-    if (total > 0) HIPCHK(e, hipMemcpyAsync(e->d_gt_boxes, gt_boxes, (size_t)total * 7 * sizeof(float), hipMemcpyHostToDevice, up));
-    if (total > 0 && gt_classes)
+    if (up != nullptr && total > 0)
+        HIPCHK(e, hipMemcpyAsync(e->d_gt_boxes, gt_boxes, (size_t)total * 7 * sizeof(float), hipMemcpyHostToDevice, up));
+    if (up != nullptr && total > 0 && gt_classes)
         HIPCHK(e, hipMemcpyAsync(e->d_gt_cls, gt_classes, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice, up));
-    HIPCHK(e, hipMemcpyAsync(e->d_gt_cnt, gt_counts, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, up));
-    if (up != e->stream) {
+    if (up != nullptr) HIPCHK(e, hipMemcpyAsync(e->d_gt_cnt, gt_counts, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, up));
+    if (up != nullptr && up != e->stream) {
         HIPCHK(e, hipEventRecord(e->ev_tgt, up));
         HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_tgt, 0));
     }
@@ -2003,12 +2025,111 @@ int enqueue_targets(pp_engine* e, int batch, const float* gt_boxes, const int32_
     }
     TargetParams p;
     p.batch = batch; p.A = e->A; p.anchor_near = e->d_anchor_near; p.anchors = e->d_anchors; p.mask = mask;
-    p.gt = e->d_gt_boxes; p.gt_cls = gt_classes ? e->d_gt_cls : nullptr; p.gt_cnt = e->d_gt_cnt; p.top = e->d_gt_top;
+    p.gt = e->d_gt_boxes; p.gt_cls = (gt_classes || up == nullptr) ? e->d_gt_cls : nullptr; p.gt_cnt = e->d_gt_cnt;
+    p.top = e->d_gt_top;
     p.matched = tc->matched_threshold; p.unmatched = tc->unmatched_threshold;
     p.labels = e->d_loss_labels; p.reg_targets = e->d_loss_regt;
     p.gt_index = extra ? e->d_tgt_index : nullptr; p.overlap = extra ? e->d_tgt_overlap : nullptr;
     launch_targets(p, e->stream);
     HIPCHK(e, hipGetLastError());
+    return PP_OK;
+}
+
+// The augmentation's argument checks beyond check_gt's: the config, the draws, and the resident batch.
+int check_aug(pp_engine* e, const char* who, int batch, int64_t total, const pp_augment_config* ac,
+              const pp_aug_frame* frames, const double* box_draws) {
+    if (!ac || !frames) return fail(e, PP_ERR_ARG, "%s: null argument", who);
+    if (ac->num_try < 1 || ac->num_try > PP_AUG_MAX_TRY)
+        return fail(e, PP_ERR_ARG, "%s: num_try %d outside 1..%d", who, ac->num_try, PP_AUG_MAX_TRY);
+    if (e->cur_batch != batch)
+        return fail(e, PP_ERR_ARG, "%s: %d frames are resident, batch is %d", who, e->cur_batch, batch);
+    for (int b = 0; b < batch; ++b) {
+        const pp_aug_frame& f = frames[b];
+        if (!std::isfinite(f.theta) || !std::isfinite(f.scale) || !std::isfinite(f.t[0]) || !std::isfinite(f.t[1]) ||
+            !std::isfinite(f.t[2]))
+            return fail(e, PP_ERR_ARG, "%s: frame %d has a non-finite draw", who, b);
+        if (!(f.scale > 0.0)) return fail(e, PP_ERR_ARG, "%s: frame %d has scale %g <= 0", who, b, f.scale);
+    }
+    const int64_t nd = total * ac->num_try * 5;
+    if (nd > 0 && !box_draws) return fail(e, PP_ERR_ARG, "%s: box_draws is NULL", who);
+    // one branch-free pass over the bits (an exponent of all ones: inf or NaN); the failing box is looked up after
+    uint64_t bad = 0;
+    const uint64_t* bits = (const uint64_t*)box_draws;
+    for (int64_t i = 0; i < nd; ++i) bad |= (uint64_t)((bits[i] & 0x7ff0000000000000ull) == 0x7ff0000000000000ull);
+    if (bad)
+        for (int64_t i = 0; i < nd; ++i)
+            if (!std::isfinite(box_draws[i]))
+                return fail(e, PP_ERR_ARG, "%s: box draw %lld is not finite", who, (long long)(i / ((int64_t)ac->num_try * 5)));
+    return PP_OK;
+}
+
+// Queues the augmentation of the resident frames on the handle's stream.  The inputs go up on `up` (the copy stream:
+// the main stream then waits for ev_tgt; or the main stream).  A zero-copy feed is read from the caller's page-locked
+// points here and is replaced by device copies: the step that follows runs the copy-fed graph variant.  The result
+// lands in the resident input buffer; d_gt_boxes / d_gt_cls / d_gt_cnt receive the kept boxes.
+int enqueue_augment(pp_engine* e, int batch, const float* gt_boxes, const int32_t* gt_classes, const uint8_t* gt_valid,
+                    const int32_t* gt_counts, int64_t total, const pp_augment_config* ac, const pp_aug_frame* frames,
+                    const double* box_draws, hipStream_t up) {
+    int st;
+    if (!e->aug_ready) {
+        const size_t gmax = (size_t)e->B * PP_MAX_GT_PER_FRAME;
+        if ((st = dalloc(e, &e->d_aug_pts, (size_t)e->B * e->NMAX * e->F))) return st;
+        if ((st = dalloc(e, &e->d_aug_gt_in, gmax * 7))) return st;
+        if ((st = dalloc(e, &e->d_aug_cls_in, gmax))) return st;
+        if ((st = dalloc(e, &e->d_aug_valid, gmax))) return st;
+        if ((st = dalloc(e, &e->d_aug_cnt_in, (size_t)e->B))) return st;
+        if ((st = dalloc(e, &e->d_aug_draws, gmax * PP_AUG_MAX_TRY * 5))) return st;
+        if ((st = dalloc(e, &e->d_aug_frames, (size_t)e->B))) return st;
+        if ((st = dalloc(e, &e->d_aug_rec, gmax))) return st;
+        if ((st = dalloc(e, &e->d_aug_box_tmp, gmax * 7))) return st;
+        if ((st = dalloc(e, &e->d_aug_keep, gmax))) return st;
+        if ((st = dalloc(e, &e->d_aug_sel, gmax))) return st;
+        if ((st = dalloc(e, &e->d_aug_cs, (size_t)e->B * 2))) return st;
+        e->aug_ready = true;
+    }
+    if (total > 0) {
+        HIPCHK(e, hipMemcpyAsync(e->d_aug_gt_in, gt_boxes, (size_t)total * 7 * sizeof(float), hipMemcpyHostToDevice, up));
+        if (gt_classes)
+            HIPCHK(e, hipMemcpyAsync(e->d_aug_cls_in, gt_classes, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice, up));
+        if (gt_valid) HIPCHK(e, hipMemcpyAsync(e->d_aug_valid, gt_valid, (size_t)total, hipMemcpyHostToDevice, up));
+        HIPCHK(e, hipMemcpyAsync(e->d_aug_draws, box_draws, (size_t)total * ac->num_try * 5 * sizeof(double),
+                                 hipMemcpyHostToDevice, up));
+    }
+    HIPCHK(e, hipMemcpyAsync(e->d_aug_cnt_in, gt_counts, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, up));
+    HIPCHK(e, hipMemcpyAsync(e->d_aug_frames, frames, (size_t)batch * sizeof(pp_aug_frame), hipMemcpyHostToDevice, up));
+    if (up != e->stream) {
+        HIPCHK(e, hipEventRecord(e->ev_tgt, up));
+        HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_tgt, 0));
+    }
+    // the resident points: behind their upload; a zero-copy feed is materialised (offsets and points from the
+    // page-locked descriptor) so that the voxeliser reads device memory
+    if (e->up_pending || e->prevox_issued) {
+        HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_up, 0));
+        e->up_pending = false;
+        e->prevox_issued = false;
+    }
+    const PpFeed* f = e->h_feed[e->in_buf];
+    const float* src = e->d_points;
+    if (e->zc) {
+        HIPCHK(e, hipMemcpyAsync(e->d_offsets, f->offsets, (size_t)(batch + 1) * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        src = f->src;
+    }
+    ProfScope ps(e, nullptr);      // each launch under its own name
+    AugParams p;
+    p.batch = batch; p.F = e->F; p.T = ac->num_try; p.v2 = ac->global_rot_per_object ? 1 : 0;
+    p.pc[0] = e->cfg.pc_range[0]; p.pc[1] = e->cfg.pc_range[1]; p.pc[2] = e->cfg.pc_range[3]; p.pc[3] = e->cfg.pc_range[4];
+    p.offsets = e->d_offsets; p.pts_in = src; p.pts_out = e->d_aug_pts;
+    p.gt_in = e->d_aug_gt_in; p.cls_in = gt_classes ? e->d_aug_cls_in : nullptr; p.valid = gt_valid ? e->d_aug_valid : nullptr;
+    p.cnt_in = e->d_aug_cnt_in; p.draws = e->d_aug_draws; p.frames = e->d_aug_frames; p.frame_cs = e->d_aug_cs;
+    p.boxrec = e->d_aug_rec; p.box_tmp = e->d_aug_box_tmp; p.keep = e->d_aug_keep; p.sel = e->d_aug_sel;
+    p.gt_out = e->d_gt_boxes; p.cls_out = e->d_gt_cls; p.cnt_out = e->d_gt_cnt;
+    launch_augment(p, e->cur_max_n, e->stream);
+    HIPCHK(e, hipGetLastError());
+    e->aug_total = total;
+    const size_t n = (size_t)(e->zc ? f->offsets[batch] : e->cur_total);
+    if (n) HIPCHK(e, hipMemcpyAsync(e->d_points, e->d_aug_pts, n * e->F * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+    e->zc = false;
+    e->vox_ahead = false;
     return PP_OK;
 }
 
@@ -2072,7 +2193,8 @@ namespace {
 // pp_train_step_async and pp_train_step_gt_async: `targets` fills d_loss_labels / d_loss_regt between the two halves of
 // the step (plain stream work between the two graph replays, or between the two eager halves)
 int train_step_launch(pp_engine* e, const float* params_dev, float* grads_dev, float* state_dev, int32_t batch,
-                      const pp_loss_config* lc, const std::function<int()>& targets) {
+                      const pp_loss_config* lc, const std::function<int()>& targets,
+                      const std::function<int()>& pre = nullptr) {
     if (!params_dev || !grads_dev || !state_dev || !lc)
         return fail(e, PP_ERR_ARG, "pp_train_step: null argument");
     if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_train_step_async: the step before has not been waited for");
@@ -2091,6 +2213,7 @@ int train_step_launch(pp_engine* e, const float* params_dev, float* grads_dev, f
         e->prevox_issued = false;
     }
     prof_reset(e);
+    if (pre && (st = pre())) return st;   // plain launches ahead of the forward half (the augmentation)
     e->main_vox_pending = true;    // the step voxelises on the main stream (inside its graph, too)
     pp_engine::TrainState* t = e->train;
     TrainCtx& cx = t->cx;
@@ -2220,6 +2343,80 @@ int pp_train_step_gt_async(pp_handle e, const float* params_dev, float* grads_de
         return enqueue_targets(e, batch, gt_boxes, gt_classes, gt_counts, total, true, tc, false, e->copy_stream);
     };
     return train_step_launch(e, params_dev, grads_dev, state_dev, batch, lc, assign);
+}
+
+int pp_train_step_aug_async(pp_handle e, const float* params_dev, float* grads_dev, float* state_dev,
+                            const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts, int32_t batch,
+                            const pp_loss_config* lc, const pp_target_config* tc, const uint8_t* gt_valid,
+                            const pp_augment_config* ac, const pp_aug_frame* frames, const double* box_draws) {
+    if (!e) return PP_ERR_ARG;
+    int64_t total = 0;
+    int st = check_gt(e, "pp_train_step_aug", gt_boxes, gt_classes, gt_counts, batch, tc, &total);
+    if (st == PP_OK) st = check_aug(e, "pp_train_step_aug", batch, total, ac, frames, box_draws);
+    if (st) return st;
+    // boxes and draws go up on the copy stream; the augmentation runs on the main stream ahead of the forward replay
+    // (the augmented cloud replaces the resident one), the targets between the halves from the kept boxes
+    auto augment = [&]() -> int {
+        return enqueue_augment(e, batch, gt_boxes, gt_classes, gt_valid, gt_counts, total, ac, frames, box_draws,
+                               e->copy_stream);
+    };
+    auto assign = [&]() -> int { return enqueue_targets(e, batch, nullptr, nullptr, nullptr, 0, true, tc, false, nullptr); };
+    return train_step_launch(e, params_dev, grads_dev, state_dev, batch, lc, assign, augment);
+}
+
+int pp_train_step_aug(pp_handle e, const float* params_dev, float* grads_dev, float* state_dev, const float* gt_boxes,
+                      const int32_t* gt_classes, const int32_t* gt_counts, int32_t batch, const pp_loss_config* lc,
+                      const pp_target_config* tc, const uint8_t* gt_valid, const pp_augment_config* ac,
+                      const pp_aug_frame* frames, const double* box_draws, float* losses) {
+    if (!e) return PP_ERR_ARG;
+    if (!losses) return fail(e, PP_ERR_ARG, "pp_train_step_aug: null argument");
+    int st = pp_train_step_aug_async(e, params_dev, grads_dev, state_dev, gt_boxes, gt_classes, gt_counts, batch, lc, tc,
+                                     gt_valid, ac, frames, box_draws);
+    if (st) return st;
+    return pp_train_step_wait(e, losses);
+}
+
+int pp_augment(pp_handle e, const float* gt_boxes, const int32_t* gt_classes, const uint8_t* gt_valid,
+               const int32_t* gt_counts, int32_t batch, const pp_augment_config* ac, const pp_aug_frame* frames,
+               const double* box_draws, float* points_out, float* boxes_out, int32_t* classes_out, int32_t* counts_out) {
+    if (!e) return PP_ERR_ARG;
+    if (!points_out || !boxes_out || !classes_out || !counts_out) return fail(e, PP_ERR_ARG, "pp_augment: null argument");
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_augment: a training step is in flight");
+    const pp_target_config tc = {0.5f, 0.35f, {0, 0}};
+    int64_t total = 0;
+    int st = check_gt(e, "pp_augment", gt_boxes, gt_classes, gt_counts, batch, &tc, &total);
+    if (st == PP_OK) st = check_aug(e, "pp_augment", batch, total, ac, frames, box_draws);
+    if (st) return st;
+    (void)hipSetDevice(e->device);
+    prof_reset(e);
+    if ((st = enqueue_augment(e, batch, gt_boxes, gt_classes, gt_valid, gt_counts, total, ac, frames, box_draws, e->stream)))
+        return st;
+    HIPCHK(e, hipMemcpyAsync(counts_out, e->d_gt_cnt, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    int64_t kept = 0;
+    for (int b = 0; b < batch; ++b) kept += counts_out[b];
+    if (e->cur_total)
+        HIPCHK(e, hipMemcpyAsync(points_out, e->d_points, (size_t)e->cur_total * e->F * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (kept) {
+        HIPCHK(e, hipMemcpyAsync(boxes_out, e->d_gt_boxes, (size_t)kept * 7 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipMemcpyAsync(classes_out, e->d_gt_cls, (size_t)kept * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    }
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return PP_OK;
+}
+
+int pp_augment_selected(pp_handle e, int32_t* selected, int64_t capacity, int64_t* count) {
+    if (!e) return PP_ERR_ARG;
+    if (!count || (capacity > 0 && !selected)) return fail(e, PP_ERR_ARG, "pp_augment_selected: null argument");
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_augment_selected: a training step is in flight");
+    (void)hipSetDevice(e->device);
+    *count = e->aug_total;
+    const int64_t n = std::min<int64_t>(capacity, e->aug_total);
+    if (n > 0) {
+        HIPCHK(e, hipMemcpyAsync(selected, e->d_aug_sel, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+    }
+    return PP_OK;
 }
 
 int pp_train_step_gt(pp_handle e, const float* params_dev, float* grads_dev, float* state_dev, const float* gt_boxes,

@@ -324,3 +324,34 @@ struct TargetParams {
 };
 void launch_anchor_near(const float* anchors, int64_t A, float4* near, hipStream_t s);
 void launch_targets(const TargetParams& p, hipStream_t s);   // pass 1 (per-box maxima) + pass 2 (labels, targets)
+
+// augment.hip: training-time augmentation of the resident frames (augment.py)
+typedef pp_aug_frame AugFrame;
+struct AugBox {                // per box of a frame, written by k_aug_select for the point pass
+    double n[6][3], d[6];      // plane equations of the original 3-D box (outside: p . n + d >= 0)
+    double c[3];               // original centre
+    double loc[3], cr, sr;     // selected transform (zero when no try passed): shift, cos / sin of the turn
+    int valid;
+};
+struct AugParams {
+    int batch, F, T, v2;
+    double pc[4];              // pc_range x0 y0 x1 y1
+    const int* offsets;        // [batch + 1] resident frame offsets
+    const float* pts_in;       // [sum n][F] resident points
+    float* pts_out;            // [sum n][F] augmented, shuffled
+    const float* gt_in;        // [sum cnt_in][7]
+    const int* cls_in;         // [sum cnt_in] or NULL (all 1)
+    const uint8_t* valid;      // [sum cnt_in] or NULL (all valid)
+    const int* cnt_in;         // [batch]
+    const double* draws;       // [sum cnt_in][T][5]
+    const AugFrame* frames;    // [batch]
+    double* frame_cs;          // [batch][2] cos / sin of the frame's global rotation (k_aug_select -> k_aug_points)
+    AugBox* boxrec;            // [batch][PP_MAX_GT_PER_FRAME]
+    float* box_tmp;            // [batch][PP_MAX_GT_PER_FRAME][7] augmented boxes before compaction
+    uint8_t* keep;             // [batch][PP_MAX_GT_PER_FRAME]
+    int* sel;                  // [sum cnt_in] selected try (-1: none), or NULL
+    float* gt_out;             // [sum cnt_out][7] kept boxes, frames back to back
+    int* cls_out;              // [sum cnt_out]
+    int* cnt_out;              // [batch]
+};
+void launch_augment(const AugParams& p, int max_n, hipStream_t s);

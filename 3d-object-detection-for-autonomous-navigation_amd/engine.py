@@ -286,6 +286,7 @@ class Engine:
         """frames: list of [N_b,F] float32 clouds -> engine's resident input buffer."""
         pts, offs = self._pack(frames, self.d.num_point_features)
         self._check(self._lib.pp_upload_points(self._h, _ptr(pts), _ptr(offs), len(frames)), "pp_upload_points")
+        self._offsets = offs          # the resident frames' offsets (augment splits its output by them)
         if rect is not None:
             self.set_calib(rect, trv2c, len(frames))
 
@@ -308,6 +309,7 @@ class Engine:
         buffer must not be rewritten before the sync() that follows the detect_async() consuming it."""
         self._check(self._lib.pp_upload_points_async(self._h, _ptr(staging.points), _ptr(staging.offsets),
                                                      staging.offsets.shape[0] - 1), "pp_upload_points_async")
+        self._offsets = np.array(staging.offsets, np.int64)
         # The handle's two input buffers alternate and the library waits for the pass that read a buffer before it
         # re-stages it, so the buffers of the last two uploads are the ones a pass may still read: the engine keeps
         # them alive (a temporary Staging would otherwise be freed under the zero-copy kernel).
@@ -324,6 +326,7 @@ class Engine:
         ps = ctypes.c_void_p(int(producer_stream)) if producer_stream else None
         self._check(self._lib.pp_upload_points_device(self._h, ctypes.c_void_p(int(dev_ptr)), _ptr(offs),
                                                       offs.shape[0] - 1, ps), "pp_upload_points_device")
+        self._offsets = offs
 
     def _batches(self):
         up, res = ctypes.c_int32(0), ctypes.c_int32(0)
@@ -583,6 +586,78 @@ class Engine:
                                                      _ptr(boxes), _ptr(classes), _ptr(counts), len(counts),
                                                      ctypes.byref(lc), ctypes.byref(tc)), "pp_train_step_gt_async")
         self._train_targets = (boxes, classes, counts)   # the copy engine reads them while the forward pass runs
+
+    @staticmethod
+    def _aug_args(gt_valid, total, draws, aug_config):
+        from . import augment
+        if aug_config is None:
+            aug_config = augment.AugmentConfig.from_input_reader(None)
+        if not isinstance(draws, augment.Draws):
+            raise ValueError("draws: an augment.Draws (augment.draw) is required")
+        ac = _lib.PPAugmentConfig()
+        ac.num_try, ac.global_rot_per_object = aug_config.num_try, int(aug_config.global_rot_per_object)
+        valid = None
+        if isinstance(gt_valid, np.ndarray) and gt_valid.dtype == np.uint8 and gt_valid.ndim == 1:
+            valid = gt_valid            # already flat (Trainer.stage_gt's page-locked flags)
+        elif gt_valid is not None:
+            valid = np.ascontiguousarray(np.concatenate([np.asarray(v, bool).reshape(-1) for v in gt_valid])
+                                         if len(gt_valid) and not np.isscalar(gt_valid[0]) else np.asarray(gt_valid, bool),
+                                         dtype=np.uint8).reshape(-1)
+        if valid is not None and len(valid) != total:
+            raise ValueError(f"gt_valid: {len(valid)} flags for {total} boxes")
+        bd = np.ascontiguousarray(draws.boxes, np.float64)
+        if bd.shape[0] != total or (total and bd.shape[1] != aug_config.num_try):
+            raise ValueError(f"draws: {bd.shape[:2]} box draws for {total} boxes x {aug_config.num_try} tries")
+        return ac, valid, draws.frames_struct(), bd
+
+    def augment(self, gt_boxes, gt_classes=None, gt_valid=None, draws=None, aug_config=None):
+        """Training-time augmentation of the frames uploaded to this engine, on the GPU (pp_augment; augment.py lists the
+        stages).  The resident frames are replaced by the augmented ones (a following train step trains on them).
+        gt_boxes / gt_classes per frame as assign_targets; gt_valid per frame [G_b] bool (or None: all valid); draws:
+        augment.draw(rs, gt_boxes, aug_config).  Returns per frame (points [n_b, F], boxes [K_b, 7], classes [K_b]) --
+        the reference's debug_save_points view of the frame."""
+        boxes, cls, counts = self.pack_gt(gt_boxes, gt_classes)
+        ac, valid, frames, bd = self._aug_args(gt_valid, len(boxes), draws, aug_config)
+        B = len(counts)
+        off = np.asarray(self._offsets, np.int64) if getattr(self, "_offsets", None) is not None else None
+        n_total = int(off[-1]) if off is not None else 0
+        pts = np.empty((max(n_total, 1), self.d.num_point_features), np.float32)
+        bo = np.empty((max(len(boxes), 1), 7), np.float32)
+        co = np.empty((max(len(boxes), 1),), np.int32)
+        cnt = np.empty((B,), np.int32)
+        self._check(self._lib.pp_augment(self._h, _ptr(boxes), _ptr(cls), _ptr(valid), _ptr(counts), B, ctypes.byref(ac),
+                                         frames.ctypes.data, bd.ctypes.data, _ptr(pts), _ptr(bo), _ptr(co), _ptr(cnt)),
+                    "pp_augment")
+        out, g = [], 0
+        for b in range(B):
+            k = int(cnt[b])
+            out.append((pts[off[b]:off[b + 1]].copy(), bo[g:g + k].copy(), co[g:g + k].copy()))
+            g += k
+        return out
+
+    def augment_selected(self):
+        """The try each input box of the last augmentation took (-1: none, or an invalid box), in gt_boxes order
+        (pp_augment_selected)."""
+        n = ctypes.c_int64(0)
+        self._check(self._lib.pp_augment_selected(self._h, None, 0, ctypes.byref(n)), "pp_augment_selected")
+        out = np.empty(max(n.value, 1), np.int32)
+        self._check(self._lib.pp_augment_selected(self._h, _ptr(out), n.value, ctypes.byref(n)), "pp_augment_selected")
+        return out[:n.value].copy()
+
+    def train_step_aug_async(self, params_ptr, grads_ptr, state_ptr, boxes, classes, counts, valid, draws, aug_config):
+        """train_step_gt_async on the frames augmented on the GPU first (pp_train_step_aug_async): boxes / classes /
+        counts as pack_gt returns them, valid the concatenated flags (or None), draws an augment.Draws."""
+        boxes = _f32(boxes).reshape(-1, 7)
+        counts = _i32(counts).reshape(-1)
+        classes = None if classes is None else _i32(classes).reshape(-1)
+        ac, valid, frames, bd = self._aug_args(valid, len(boxes), draws, aug_config)
+        lc, tc = self.loss_config(), self.target_config()
+        self._check(self._lib.pp_train_step_aug_async(self._h, ctypes.c_void_p(int(params_ptr)),
+                                                      ctypes.c_void_p(int(grads_ptr)), ctypes.c_void_p(int(state_ptr)),
+                                                      _ptr(boxes), _ptr(classes), _ptr(counts), len(counts),
+                                                      ctypes.byref(lc), ctypes.byref(tc), _ptr(valid), ctypes.byref(ac),
+                                                      frames.ctypes.data, bd.ctypes.data), "pp_train_step_aug_async")
+        self._train_targets = (boxes, classes, counts, valid, frames, bd)
 
     def train_step_wait(self):
         """Wait for the step train_step_async() launched; returns the reference's loss scalars."""

@@ -3,6 +3,7 @@
     trainer = Trainer(config, weights, max_batch=2)            # one per GPU / rank
     out = trainer.step(frames, labels, reg_targets, dist)      # forward + loss + backward, all-reduce, AdamW
     out = trainer.step(frames, gt_boxes=boxes, dist=dist)      # ... with the targets assigned on the GPU from the boxes
+    trainer = Trainer(config, weights, augment=True, seed=0)   # ... and the frames augmented on the GPU first
     trainer.weights()                                          # Keras-layout dict (Engine.load_weights, save_npz)
 
 What runs where: the frames are uploaded and voxelised by the engine, `pp_train_step` (csrc/train.hip) runs the
@@ -12,7 +13,9 @@ flat float32 buffer; that buffer is averaged over the ranks with ONE all-reduce 
 AdamW kernel (csrc/optim.hip).  torch owns the flat device buffers and the communicator; no torch operator touches
 the numbers.  Labels / regression targets come either from `target_assigner` on the host (the reference's training
 dataloader) or, given the ground-truth boxes (`gt_boxes=`), from the same assignment on the GPU between the forward and
-the backward half of the step (csrc/targets.hip).
+the backward half of the step (csrc/targets.hip).  With `augment` on, a step given boxes first augments the frames
+and the boxes on the GPU as the reference's training loader does (csrc/augment.hip, augment.py); the random numbers
+are drawn from the trainer's own RandomState (`seed`) in the reference's order.
 """
 import numpy as np
 
@@ -25,20 +28,33 @@ class TrainBatch:
 
     labels = reg_targets = None          # stage(): the dense targets
     gt = None                            # stage_gt(): (boxes, classes or None, counts) as Engine.pack_gt lays them out
+    aug = None                           # stage_gt() of an augmenting trainer: (valid flags or None, augment.Draws)
 
     def close(self):
-        for k in ("points", "_lab", "_reg", "_gtb", "_gtc", "_gtn"):
+        for k in ("points", "_lab", "_reg", "_gtb", "_gtc", "_gtn", "_gtv", "_aug_frames", "_aug_boxes"):
             o = getattr(self, k, None)
             if o is not None:
                 o.close()
                 setattr(self, k, None)
-        self.labels = self.reg_targets = self.gt = None
+        self.labels = self.reg_targets = self.gt = self.aug = None
 
 
 class Trainer:
     def __init__(self, config, weights, max_batch=None, max_points_per_frame=32768, device=0, learning_rate=None,
-                 weight_decay=None):
+                 weight_decay=None, augment=None, seed=None):
         import torch
+        from . import augment as _augment
+        # augment: None / False = off; True = the config's train_input_reader keys (the shipped values without them);
+        # an augment.AugmentConfig = those settings
+        if augment is True:
+            tir = config.get("train_input_reader") if isinstance(config, dict) else None
+            augment = _augment.AugmentConfig.from_input_reader(tir)
+        elif augment is False:
+            augment = None
+        elif augment is not None and not isinstance(augment, _augment.AugmentConfig):
+            raise ValueError("augment: None, True or an augment.AugmentConfig")
+        self.augment = augment
+        self.rs = np.random.RandomState(seed)
         self.torch = torch
         self.engine = Engine(config, max_batch=max_batch, max_points_per_frame=max_points_per_frame, device=device)
         self._prefetched = None      # the TrainBatch whose points are already on their way (forward_backward(prefetch=))
@@ -156,10 +172,11 @@ class Trainer:
         st.reg_targets[...] = np.asarray(reg_targets, dtype=np.float32).reshape(B, d.num_anchors, 7)
         return st
 
-    def stage_gt(self, frames, gt_boxes, gt_classes=None):
+    def stage_gt(self, frames, gt_boxes, gt_classes=None, gt_valid=None, draws=None):
         """stage() with ground-truth boxes instead of dense targets: the points as an engine Staging, the boxes (per frame
         [G_b, 7]), their classes (per frame [G_b], or None: all 1) and the per-frame counts packed into page-locked
-        arrays (`.gt`).  The step assigns the targets on the GPU (csrc/targets.hip)."""
+        arrays (`.gt`).  The step assigns the targets on the GPU (csrc/targets.hip).  On an augmenting trainer the batch
+        also holds its augmentation draws (`draws`, or drawn here from the trainer's RandomState) and the valid flags."""
         boxes, cls, counts = self.engine.pack_gt(gt_boxes, gt_classes)
         if len(counts) != len(frames):
             raise ValueError(f"{len(frames)} frames but boxes for {len(counts)}")
@@ -173,16 +190,39 @@ class Trainer:
             st._gtc = self.engine.pinned(cls.shape, np.int32)
             st._gtc.array[...] = cls
         st.gt = (st._gtb.array, st._gtc.array if cls is not None else None, st._gtn.array)
+        if self.augment is not None:
+            if draws is None:
+                from . import augment as _augment
+                draws = _augment.draw(self.rs, gt_boxes, self.augment)
+            # the draws in page-locked memory next to the boxes: the step's copies are DMA transfers
+            from . import augment as _augment
+            if gt_valid is not None:
+                v = np.concatenate([np.asarray(x, bool).reshape(-1) for x in gt_valid]) if len(gt_valid) else \
+                    np.zeros(0, bool)
+                st._gtv = self.engine.pinned(v.shape, np.uint8)
+                st._gtv.array[...] = v
+                gt_valid = st._gtv.array
+            st._aug_frames = self.engine.pinned(draws.flip.shape, _augment.FRAME_DTYPE)
+            st._aug_frames.array[...] = draws.frames_struct()
+            st._aug_boxes = self.engine.pinned(draws.boxes.shape, np.float64)
+            st._aug_boxes.array[...] = draws.boxes
+            draws = _augment.Draws(draws.flip, draws.theta, draws.scale, draws.t, draws.seed, st._aug_boxes.array,
+                                   draws.counts, frames=st._aug_frames.array)
+            st.aug = (gt_valid, draws)
+        elif gt_valid is not None or draws is not None:
+            raise ValueError("gt_valid / draws need a trainer with augment on")
         return st
 
-    def _enqueue_step(self, labels, reg_targets, gt):
+    def _enqueue_step(self, labels, reg_targets, gt, aug=None):
         ptrs = (self.params.data_ptr(), self.grads.data_ptr(), self.state.data_ptr())
-        if gt is not None:
+        if aug is not None:
+            self.engine.train_step_aug_async(*ptrs, *gt, aug[0], aug[1], self.augment)
+        elif gt is not None:
             self.engine.train_step_gt_async(*ptrs, *gt)
         else:
             self.engine.train_step_async(*ptrs, labels, reg_targets)
 
-    def _launch(self, frames, labels, reg_targets, prefetch, gt_boxes=None, gt_classes=None):
+    def _launch(self, frames, labels, reg_targets, prefetch, gt_boxes=None, gt_classes=None, gt_valid=None):
         """Enqueue the step (and the upload of the next batch beside it); the caller waits with engine.train_step_wait().
         Targets: a TrainBatch's own (stage / stage_gt), else labels / reg_targets, else gt_boxes (+ gt_classes)."""
         if isinstance(frames, TrainBatch):
@@ -192,7 +232,9 @@ class Trainer:
             if self._prefetched is not tb:
                 self.engine.upload_async(tb.points)
             self._prefetched = None
-            self._enqueue_step(tb.labels, tb.reg_targets, tb.gt)
+            if self.augment is not None and tb.aug is None:
+                raise ValueError("an augmenting trainer trains on stage_gt() batches (dense labels cannot follow moved boxes)")
+            self._enqueue_step(tb.labels, tb.reg_targets, tb.gt, tb.aug)
             if isinstance(prefetch, TrainBatch):
                 self.engine.upload_async(prefetch.points)
                 self._prefetched = prefetch
@@ -206,17 +248,26 @@ class Trainer:
                 raise ValueError(f"{len(frames)} frames but boxes for {len(gt[2])}")
         elif gt_classes is not None:
             raise ValueError("gt_classes needs gt_boxes")
+        aug = None
+        if self.augment is not None:
+            if gt is None:
+                raise ValueError("augmentation needs gt_boxes= (dense labels cannot follow moved boxes)")
+            from . import augment as _augment
+            aug = (gt_valid, _augment.draw(self.rs, gt_boxes, self.augment))
+        elif gt_valid is not None:
+            raise ValueError("gt_valid needs a trainer with augment on")
         self._prefetched = None
         self.engine.upload(frames)
-        self._enqueue_step(labels, reg_targets, gt)
+        self._enqueue_step(labels, reg_targets, gt, aug)
 
-    def forward_backward(self, frames, labels=None, reg_targets=None, prefetch=None, gt_boxes=None, gt_classes=None):
+    def forward_backward(self, frames, labels=None, reg_targets=None, prefetch=None, gt_boxes=None, gt_classes=None,
+                         gt_valid=None):
         """frames: a list of clouds with labels / reg_targets (or gt_boxes / gt_classes: the targets are then assigned
         on the GPU), or one TrainBatch from stage() / stage_gt().
         prefetch: the TrainBatch of the NEXT step -- its points go to the GPU (the handle's other input buffer, the copy
         stream) while this step's kernels run, the loader's hand-over of train.py:228-304; pass that same batch as
         `frames` of the next call."""
-        self._launch(frames, labels, reg_targets, prefetch, gt_boxes, gt_classes)
+        self._launch(frames, labels, reg_targets, prefetch, gt_boxes, gt_classes, gt_valid)
         return self.engine.train_step_wait()
 
     def _engine_stream(self):
@@ -250,10 +301,11 @@ class Trainer:
         self._enqueue_update(dist)
         self._engine_stream().synchronize()
 
-    def step(self, frames, labels=None, reg_targets=None, dist=None, prefetch=None, gt_boxes=None, gt_classes=None):
+    def step(self, frames, labels=None, reg_targets=None, dist=None, prefetch=None, gt_boxes=None, gt_classes=None,
+             gt_valid=None):
         """One optimizer step: forward + loss + backward, gradient exchange, AdamW -- enqueued back to back on the engine's
         stream, ONE host wait at the end.  Targets as forward_backward takes them."""
-        self._launch(frames, labels, reg_targets, prefetch, gt_boxes, gt_classes)
+        self._launch(frames, labels, reg_targets, prefetch, gt_boxes, gt_classes, gt_valid)
         try:
             self._enqueue_update(dist)
         except BaseException:

@@ -33,7 +33,8 @@ def _np(x):
 
 
 class VoxelNet:
-    def __init__(self, config, writer=None, training=False, max_batch=None, max_points_per_frame=32768, device=0):
+    def __init__(self, config, writer=None, training=False, max_batch=None, max_points_per_frame=32768, device=0,
+                 augment=None, seed=None):
         self.config = config
         self.training = bool(training)
         self.d = Derived(config)
@@ -41,6 +42,10 @@ class VoxelNet:
         self.box_code_size = 7
         self.trainer = None
         self._ctor = dict(max_batch=max_batch or self.batch_size, max_points_per_frame=max_points_per_frame, device=device)
+        # training only: the loader's augmentation on the GPU (Trainer's augment= / seed=)
+        self._train_kw = dict(augment=augment, seed=seed)
+        if not self.training and augment:
+            raise ValueError("augment is a training option: build the net with training=True")
         if self.training:
             self.engine = None      # the Trainer (created by load_weights: it needs initial values) owns the engine
         else:
@@ -53,7 +58,7 @@ class VoxelNet:
         w = _weights.load_any(src, self.d) if isinstance(src, (str, os.PathLike)) else src
         if self.training:
             if self.trainer is None:
-                self.trainer = Trainer(self.config, w, **self._ctor)
+                self.trainer = Trainer(self.config, w, **self._ctor, **self._train_kw)
                 self.engine = self.trainer.engine
             else:
                 self.trainer.set_weights(w)
@@ -86,10 +91,13 @@ class VoxelNet:
                           if len(rows) else np.zeros((0, voxels.shape[2]), np.float32))
         return frames
 
-    def train_step(self, frames, labels=None, reg_targets=None, dist=None, apply=True, gt_boxes=None, gt_classes=None):
+    def train_step(self, frames, labels=None, reg_targets=None, dist=None, apply=True, gt_boxes=None, gt_classes=None,
+                   gt_valid=None):
         """Forward (training mode) + loss + backward on raw clouds; apply=True also runs the optimizer step.
         Targets: exactly one of labels + reg_targets (dense, per anchor) or gt_boxes (per frame [G_b, 7], with
-        gt_classes per frame or None: all 1; assigned on the GPU).  Returns the reference's loss scalars
+        gt_classes per frame or None: all 1; assigned on the GPU).  With augmentation on (VoxelNet(..., augment=True,
+        seed=...)) the frames and boxes are augmented on the GPU first; gt_valid marks the boxes that are only obstacles.
+        Returns the reference's loss scalars
         (model/voxelnet.py:1032-1043)."""
         if self.trainer is None:
             raise RuntimeError("VoxelNet(training=True): load_weights() with the initial values first")
@@ -98,7 +106,8 @@ class VoxelNet:
             raise ValueError("train_step needs exactly one of labels + reg_targets or gt_boxes")
         if dense and (labels is None or reg_targets is None):
             raise ValueError("train_step: labels and reg_targets go together")
-        out = self.trainer.forward_backward(frames, labels, reg_targets, gt_boxes=gt_boxes, gt_classes=gt_classes)
+        out = self.trainer.forward_backward(frames, labels, reg_targets, gt_boxes=gt_boxes, gt_classes=gt_classes,
+                                            gt_valid=gt_valid)
         if apply:
             self.apply_gradients(dist)
         return out

@@ -29,7 +29,8 @@ extern "C" {
 
 /* 3: PP_ERR_NUMERIC, pp_set_gemm_precision / pp_get_gemm_precision, pp_set_cache_budget.  4: pp_train_fetch_decisions;
  * later additions within 4 (nothing before them changed): pp_target_config, pp_assign_targets, pp_train_step_gt_async,
- * pp_train_step_gt. */
+ * pp_train_step_gt; then PP_AUG_MAX_TRY, pp_augment_config, pp_aug_frame, pp_augment, pp_train_step_aug_async,
+ * pp_train_step_aug, pp_augment_selected. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -379,6 +380,57 @@ int pp_train_step_gt_async(pp_handle h, const float* params_dev, float* grads_de
 int pp_train_step_gt(pp_handle h, const float* params_dev, float* grads_dev, float* state_dev, const float* gt_boxes,
                      const int32_t* gt_classes, const int32_t* gt_counts, int32_t batch, const pp_loss_config* lc,
                      const pp_target_config* tc, float* losses);
+
+/* ---- training-time augmentation -------------------------------------------------------- */
+/* prep_pointcloud's training branch after GT-database sampling (load_data.py:2751-2866): noise_per_object_v3_ (num_try
+ * tries per box, the first collision-free one wins), dropping the invalid boxes, random_flip, global_rotation,
+ * global_scaling_v2, global_translate, limit_period(yaw, 0.5, 2 pi), the point shuffle and
+ * filter_gt_box_outside_range_by_center.  The random numbers come from the caller (<package>/augment.py draw: the
+ * reference's numpy calls in its order); every decision is taken in float64, points are rounded to float32 once. */
+#define PP_AUG_MAX_TRY 128
+
+typedef struct pp_augment_config {
+    int32_t num_try;                /* tries per box, 1..PP_AUG_MAX_TRY (the loader passes 100) */
+    int32_t global_rot_per_object;  /* |global_random_rotation_range_per_object| >= 1e-3: noise_per_box_v2_'s rule */
+} pp_augment_config;
+
+/* One frame's global draws. */
+typedef struct pp_aug_frame {
+    double theta;   /* global_rotation's angle: points and centres turn by -theta, the yaw gains theta */
+    double scale;   /* global_scaling_v2's factor (> 0) */
+    double t[3];    /* global_translate's shift */
+    int32_t flip;   /* random_flip: y = -y, yaw = -yaw */
+    uint32_t seed;  /* key of the point shuffle (output point i = input point perm(seed, n)[i]) */
+} pp_aug_frame;
+
+/* Augments the RESIDENT frames in place (the next pp_train_step_gt* trains on them) and returns them with their boxes.
+ * gt_boxes / gt_classes / gt_counts as pp_assign_targets; gt_valid [sum(gt_counts)] uint8 or NULL (all valid): invalid
+ * boxes are obstacles for the others' tries and are dropped.  frames [batch]; box_draws [sum(gt_counts)][num_try][5]
+ * float64 (loc x y z, rot, global rot) per box.  Outputs (host): points_out [sum n, F] (the resident offsets),
+ * boxes_out [sum(gt_counts), 7] and classes_out [sum(gt_counts)] of which the first sum(counts_out) rows are written,
+ * counts_out [batch] (boxes kept per frame).  PP_ERR_ARG for what pp_assign_targets refuses, a non-finite draw, a
+ * scale <= 0, num_try outside 1..PP_AUG_MAX_TRY, or a batch other than the resident one; the handle stays usable.
+ * Synchronous. */
+int pp_augment(pp_handle h, const float* gt_boxes, const int32_t* gt_classes, const uint8_t* gt_valid,
+               const int32_t* gt_counts, int32_t batch, const pp_augment_config* ac, const pp_aug_frame* frames,
+               const double* box_draws, float* points_out, float* boxes_out, int32_t* classes_out, int32_t* counts_out);
+/* pp_train_step_gt_async / pp_train_step_gt on the augmented frames: the augmentation runs on the handle's stream
+ * before the forward half (plain launches, outside the step's graphs), and the targets are assigned from the augmented
+ * boxes.  Exactly what pp_augment followed by pp_train_step_gt on its outputs computes.  The host arrays must stay
+ * unchanged until pp_train_step_wait returns. */
+int pp_train_step_aug_async(pp_handle h, const float* params_dev, float* grads_dev, float* state_dev,
+                            const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts, int32_t batch,
+                            const pp_loss_config* lc, const pp_target_config* tc, const uint8_t* gt_valid,
+                            const pp_augment_config* ac, const pp_aug_frame* frames, const double* box_draws);
+int pp_train_step_aug(pp_handle h, const float* params_dev, float* grads_dev, float* state_dev, const float* gt_boxes,
+                      const int32_t* gt_classes, const int32_t* gt_counts, int32_t batch, const pp_loss_config* lc,
+                      const pp_target_config* tc, const uint8_t* gt_valid, const pp_augment_config* ac,
+                      const pp_aug_frame* frames, const double* box_draws, float* losses);
+
+/* Parity tap of the last augmentation (pp_augment or pp_train_step_aug*, after it finished): the try each input box
+ * took, -1 for none and for an invalid box, in the order of gt_boxes.  *count = the number of input boxes; at most
+ * `capacity` values are written. */
+int pp_augment_selected(pp_handle h, int32_t* selected, int64_t capacity, int64_t* count);
 
 /* The handle's HIP stream (hipStream_t as void*).  A caller that enqueues its own device work behind a pp_train_step_async
  * -- the gradient all-reduce and pp_adamw_step_device of the optimizer step (train.py:301) -- does it on this stream and
