@@ -13,8 +13,8 @@ import subprocess
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG, "csrc")
 _INCLUDE = os.path.join(os.path.dirname(_PKG), "include", "pp_hip.h")
-# PP_HIP_LIB: load (and build into) another library file -- A/B builds of compile-time variants, e.g.
-#   PP_HIP_LIB=libpp_hip_f16.so PP_HIPCC_EXTRA="-DPP_SPLIT_MODE=1" python -c "import pp_amd; pp_amd._lib.build()"
+# PP_HIP_LIB: load (and build into) another library file -- A/B builds with extra compiler flags, e.g.
+#   PP_HIP_LIB=libpp_hip_g.so PP_HIPCC_EXTRA="-g" python -c "import pp_amd; pp_amd._lib.build()"
 SO_PATH = os.path.join(_PKG, os.environ.get("PP_HIP_LIB", "libpp_hip.so"))
 _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
 SOURCES = ["pp_api.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",

@@ -31,36 +31,14 @@
 #include "pp_common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-// Split-precision operand pieces (PP_SPLIT_MODE, a build-time choice; pp_api.hip splits the weights the same way):
-//   0: three bfloat16 pieces per float32 value, six products (hi*hi, hi*mid, mid*hi, hi*lo, lo*hi, mid*mid)
-//   1: two float16 pieces (11 significand bits each), three products (hi*hi, hi*mid, mid*hi): the dropped
-//      mid*mid term and the two-piece representation are each ~2^-22 relative
-//   2: two float16 pieces, four products (+ mid*mid)
-#if PP_SPLIT_MODE == 0
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-#define PC_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, C, 0, 0, 0)
-#else
-typedef _Float16 bf16x8 __attribute__((ext_vector_type(8)));   // (name kept: "one 8-element piece operand")
+// Split-precision operands: two float16 pieces per float32 value (11 significand bits each; pp_api.hip splits the
+// weights the same way), three products (hi*hi, hi*mid, mid*hi): the dropped mid*mid term and the two-piece
+// representation are each ~2^-22 relative
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 #define PC_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_f16(A, B, C, 0, 0, 0)
-#endif
-// third (lowest) piece of a pre-split operand in LDS: exists only in the three-piece mode
-#if PP_SPLIT_MODE == 0
-#define PC_LO(PTR) (*reinterpret_cast<const bf16x8*>(PTR))
-#else
-#define PC_LO(PTR) (bf16x8{})
-#endif
 // ACC += X * Y with X the first MFMA operand; smallest terms first
-#if PP_SPLIT_MODE == 0
-#define PC_PRODUCTS(ACC, XH, XM, XL, YH, YM, YL) \
-    ACC = PC_MFMA(XL, YH, ACC); ACC = PC_MFMA(XH, YL, ACC); ACC = PC_MFMA(XM, YM, ACC); \
+#define PC_PRODUCTS(ACC, XH, XM, YH, YM) \
     ACC = PC_MFMA(XM, YH, ACC); ACC = PC_MFMA(XH, YM, ACC); ACC = PC_MFMA(XH, YH, ACC);
-#elif PP_SPLIT_MODE == 1
-#define PC_PRODUCTS(ACC, XH, XM, XL, YH, YM, YL) \
-    ACC = PC_MFMA(XM, YH, ACC); ACC = PC_MFMA(XH, YM, ACC); ACC = PC_MFMA(XH, YH, ACC);
-#else
-#define PC_PRODUCTS(ACC, XH, XM, XL, YH, YM, YL) \
-    ACC = PC_MFMA(XM, YM, ACC); ACC = PC_MFMA(XM, YH, ACC); ACC = PC_MFMA(XH, YM, ACC); ACC = PC_MFMA(XH, YH, ACC);
-#endif
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // 16-byte buffer load: address = SRD base + voffset (VGPR, bytes) + soffset (SGPR, bytes).  One VGPR
@@ -82,7 +60,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
 
 int g_num_cus = 256;   // set by pp_create from the device properties (persistent launches)
 
-// GEMM arithmetic: split-precision bf16 MFMA (default) or the float32 MFMA.  PP_GEMM_PREC=f32 selects the latter.
+// GEMM arithmetic: split-precision float16 MFMA (default) or the float32 MFMA.  PP_GEMM_PREC=f32 selects the latter.
 static bool split_precision() {
     static int dflt = -1;
     if (dflt < 0) {
@@ -91,6 +69,10 @@ static bool split_precision() {
     }
     return dflt == 1;
 }
+// does layer L run on the split-precision MFMA?  (its weights fit the float16 pieces and the precision is not forced)
+static bool split_operands(const LayerDesc& L) { return L.d_wt16 != nullptr && split_precision(); }
+// channel tile of the GEMM kernels: the widest of 128 / 64 / 32 that divides cout
+static int col_tile(int cout) { return cout % 128 == 0 ? 128 : (cout % 64 == 0 ? 64 : 32); }
 #define KC 32
 #define LDS_STRIDE 36
 
@@ -98,13 +80,13 @@ struct GemmArgs {
     const float* in;
     const float* dw;
     const float* wt;
-    const unsigned short* wt16;   // split weights: three bf16 pieces, [cin/16][3][n_total][16] (or NULL)
+    const unsigned short* wt16;   // split weights: two float16 pieces, [cin/16][2][n_total][16] (or NULL)
     int n_total;                  // rows of wt / wt16
     const float* bias;
     float* out;               // may be NULL when the layer's only consumer is the fused head GEMM
     float* head;              // fused head map [pixels][PP_HEAD_COLS]
     const float* head_wt;     // [PP_HEAD_COLS][cout] (deconv with fused heads)
-    const float* head_wt16;   // the same slice as three bf16 pieces, [cout/16][3][PP_HEAD_COLS][16] 16-bit words
+    const float* head_wt16;   // the same slice as two float16 pieces, [cout/16][2][PP_HEAD_COLS][16] 16-bit words
     const float* head_bias;   // [PP_HEAD_COLS]
     int head_mode;            // 0: none, 1: head = partial + bias, 2: head += partial
     int M;                // GEMM rows (pixels) < 2^31 (checked by the launcher)
@@ -676,38 +658,13 @@ __device__ __forceinline__ void quad_transpose4(float& r0, float& r1, float& r2,
     QUAD_XCH(r1, r3, b1, 0)
 }
 
-// float32 -> three bfloat16 pieces hi + mid + lo (round-to-nearest-even each; the two remainders are
-// exact float32 subtractions), 8 values at a time = one MFMA operand per piece.  a*b is then evaluated
-// as the six products whose weight is >= 2^-16 relative (hi*hi, hi*mid, mid*hi, hi*lo, lo*hi, mid*mid)
-// on the bf16 matrix pipe with float32 accumulation: float32-equivalent accuracy (the dropped terms
-// are < 2^-24 relative) at 6 x 32 instead of 8 x 64 matrix-pipe cycles per 16 channels.
+// float32 -> two float16 pieces, 8 values at a time = one MFMA operand per piece: hi = rne(v), mid = rne(v - hi)
+// (the subtraction is exact).  |v| must stay below 65504 (BN-folded weights and BN-normalised activations are
+// O(1)..O(100)); below ~0.1 the mid piece is a float16 subnormal, i.e. the pair carries an ABSOLUTE error of at
+// most 2^-25 instead of 2^-22 relative.
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
-#if PP_SPLIT_MODE == 0
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split_bf16x3(const float (&v)[8], bf16x8& hi, bf16x8& mid, bf16x8& lo) {
-    // two values at a time: one v_cvt_pk_bf16_f32 per pair and piece; the bf16 -> f32 widening is a shift / a mask
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-        const f32x2_t x = {v[j], v[j + 1]};
-        const bf16x2_t h = __builtin_convertvector(x, bf16x2_t);
-        const unsigned hu = __builtin_bit_cast(unsigned, h);
-        // (scalar subtractions on purpose: packed fp32 adds are slow beside MFMAs)
-        const f32x2_t r1 = {v[j] - __uint_as_float(hu << 16), v[j + 1] - __uint_as_float(hu & 0xffff0000u)};
-        const bf16x2_t m = __builtin_convertvector(r1, bf16x2_t);
-        const unsigned mu = __builtin_bit_cast(unsigned, m);
-        const f32x2_t r2 = {r1.x - __uint_as_float(mu << 16), r1.y - __uint_as_float(mu & 0xffff0000u)};
-        const bf16x2_t l = __builtin_convertvector(r2, bf16x2_t);
-        hi[j] = h.x; hi[j + 1] = h.y;
-        mid[j] = m.x; mid[j + 1] = m.y;
-        lo[j] = l.x; lo[j + 1] = l.y;
-    }
-}
-#else
-// two float16 pieces: hi = rne(v), mid = rne(v - hi) (the subtraction is exact).  |v| must stay below 65504
-// (BN-folded weights and BN-normalised activations are O(1)..O(100)); below ~0.1 the mid piece is a float16
-// subnormal, i.e. the pair carries an ABSOLUTE error of at most 2^-25 instead of 2^-22 relative.
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split_bf16x3(const float (&v)[8], bf16x8& hi, bf16x8& mid, bf16x8& lo) {
+__device__ __forceinline__ void split_f16x2(const float (&v)[8], f16x8& hi, f16x8& mid) {
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {
         const f32x2_t x = {v[j], v[j + 1]};
@@ -717,9 +674,7 @@ __device__ __forceinline__ void split_bf16x3(const float (&v)[8], bf16x8& hi, bf
         hi[j] = h.x; hi[j + 1] = h.y;
         mid[j] = m.x; mid[j + 1] = m.y;
     }
-    lo = mid;   // unused by the two-piece product sets
 }
-#endif
 
 // n / d and n % d for 0 <= n < 2^24 (exact in float32) with a precomputed reciprocal: a multiply, a
 // truncation and one correction step each way instead of the ~40-instruction integer division
@@ -745,7 +700,7 @@ __device__ __forceinline__ void fast_divmod(int n, int d, float inv_d, int& q, i
 // the scheduling grain is one wave per 32 pixels (tile quantisation costs less).  The epilogue
 // stores straight from the accumulators: for a fixed accumulator register the 32 lanes of a
 // half-wave hold 32 consecutive channels of one pixel = one full 128-byte line.
-// PREC 0: float32 MFMA (v_mfma_f32_32x32x2_f32); PREC 1: split-precision bf16 MFMA (see split_bf16x3).
+// PREC 0: float32 MFMA (v_mfma_f32_32x32x2_f32); PREC 1: split-precision float16 MFMA (see split_f16x2).
 // OCC 1: the input is the sparse canvas (only cells that hold a pillar were written): every window position
 // looks its cell up in the cell -> pillar map at tile start and reads the zero header when it is empty.
 // TR 1: the TRAINING-mode forward of the layer (train.hip, model/voxelnet.py:576-660 with training=True): the input is
@@ -767,7 +722,7 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
     constexpr int WW = S + 3;                        // input window width of 2 adjacent output pixels
     constexpr int NLD = PW ? 2 : 3 * WW;
     constexpr int SAW = 32 * LSTR;                   // one wave-private A buffer (floats)
-    // weight tile in LDS: PREC 0 [NT][16 + 4] floats; PREC 1 [3 pieces][NT][16 bf16 = 8 floats], the two
+    // weight tile in LDS: PREC 0 [NT][16 + 4] floats; PREC 1 [2 pieces][NT][16 f16 = 8 floats], the two
     // 16-byte halves of a row swapped on odd groups of 8 rows (conflict-free ds_read_b128 without padding)
     constexpr int SB = (PREC == 0) ? NT * LSTR : PP_NPIECE * NT * 8;
     constexpr int NB4 = (PREC == 0) ? (NT * G + 255) / 256 : (NT * 2 * PP_NPIECE + 255) / 256;   // 16-byte weight items per thread per chunk
@@ -958,13 +913,12 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
         const float* cB = cB0 + ((I) & 1) * SB;                                                          \
         const float4 a0 = *reinterpret_cast<const float4*>(cA), a1 = *reinterpret_cast<const float4*>(cA + 4);  \
         const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};                            \
-        bf16x8 ah, am, al;                                                                               \
-        split_bf16x3(av, ah, am, al);                                                                    \
+        f16x8 ah, am;                                                                                    \
+        split_f16x2(av, ah, am);                                                                         \
         _Pragma("unroll") for (int n = 0; n < NTILES; ++n) {                                             \
-            const bf16x8 bh = *reinterpret_cast<const bf16x8*>(cB + n * 32 * 8);                         \
-            const bf16x8 bm = *reinterpret_cast<const bf16x8*>(cB + NT * 8 + n * 32 * 8);                \
-            [[maybe_unused]] const bf16x8 bl = PC_LO(cB + 2 * NT * 8 + n * 32 * 8);            \
-            PC_PRODUCTS(acc[n], ah, am, al, bh, bm, bl)                                                  \
+            const f16x8 bh = *reinterpret_cast<const f16x8*>(cB + n * 32 * 8);                           \
+            const f16x8 bm = *reinterpret_cast<const f16x8*>(cB + NT * 8 + n * 32 * 8);                  \
+            PC_PRODUCTS(acc[n], ah, am, bh, bm)                                                          \
         }                                                                                                \
     }                                                                                                    \
     if (PREC == 0) {                                                                                     \
@@ -1158,22 +1112,28 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
 #undef U_TILE_OFFSETS
 }
 
-// persistent launch: WPS workgroups per CU (one wave per SIMD each), a multiple of 8 so that every XCD
-// gets the same number
-// WPS / WPB: workgroups per CU of the float32 / split-bf16 instantiation (register budgets differ)
-template <int NT, int S, int WPS, int WPB>
-static void launch_u(const GemmArgs& a, int n_total, hipStream_t s) {
+// workgroups per CU of k_sep_u<NT, S, ., PREC> (one wave per SIMD each): the register budgets of the float32 and
+// the split-precision instantiations differ (split-precision k_sep_u<128, 1>: 256 / 168)
+constexpr int SEP128_WPB = 2, SEP64_WPB = 3;
+constexpr int sep_u_wpc(int nt, int s, bool prec) {
+    return s == 1 ? (prec ? (nt == 128 ? SEP128_WPB : (nt == 64 ? SEP64_WPB : 3)) : (nt == 128 ? 3 : 4))
+                  : (prec ? (nt == 128 ? 2 : 3) : (nt == 128 ? 2 : (nt == 64 ? 3 : 4)));
+}
+
+// persistent launch: sep_u_wpc workgroups per CU, a multiple of 8 so that every XCD gets the same number
+template <int NT, int S>
+static void launch_u(const GemmArgs& a, int n_total, bool prec, bool occ, hipStream_t s) {
+    constexpr int WPS = sep_u_wpc(NT, S, false), WPB = sep_u_wpc(NT, S, true);
     const int ntiles = (a.M + 127) / 128;
     const int ny = n_total / NT;
-    const bool bf = a.wt16 != nullptr && split_precision();
-    int slots = (g_num_cus * (bf ? WPB : WPS)) / ny;
+    int slots = (g_num_cus * (prec ? WPB : WPS)) / ny;
     const int mine = ntiles - a.tile_lo;               // (a.tile_lo > 0: a launch over a sub-range of the batch's frames)
     int gx = mine < slots ? mine : slots;
     gx = (gx + 7) & ~7;
     dim3 grid((unsigned)gx, ny);
-    if (bf && a.occ != nullptr)
+    if (occ)
         PP_LAUNCH("k_sep_u", (k_sep_u<NT, S, WPB, 1, 1>), grid, dim3(256), 0, s, a, ntiles);
-    else if (bf)
+    else if (prec)
         PP_LAUNCH("k_sep_u", (k_sep_u<NT, S, WPB, 1>), grid, dim3(256), 0, s, a, ntiles);
     else
         PP_LAUNCH("k_sep_u", (k_sep_u<NT, S, WPS, 0>), grid, dim3(256), 0, s, a, ntiles);
@@ -1185,10 +1145,6 @@ static void launch_u(const GemmArgs& a, int n_total, hipStream_t s) {
 // Returns the number of statistics rows written ([rows][2][cout]), or 0 when the shape is not one the kernel takes
 // (the caller then runs the separate depthwise and product kernels).
 int launch_sep_train(const SepTrainArgs& t, hipStream_t s) {
-#if PP_SPLIT_MODE != 1
-    (void)t; (void)s;
-    return 0;
-#else
     const long long M = (long long)t.batch * t.out_h * t.out_w;
     const long long in_bytes = (long long)t.batch * t.in_h * t.in_w * t.cin * 4;
     if (t.cin % KC != 0 || t.cout % 32 != 0 || (t.stride != 1 && t.stride != 2) || t.out_w % 2 != 0 || M >= (1 << 24) ||
@@ -1219,17 +1175,12 @@ int launch_sep_train(const SepTrainArgs& t, hipStream_t s) {
         else PP_LAUNCH(tg, (k_sep_u<32, 2, 3, 1, 0, 1>), grid, dim3(256), 0, s, a, ntiles);
     }
     return gx;          // one statistics row per workgroup of a channel column
-#endif
 }
 
 // Training-mode forward of a plain product rows x K -> rows x N (a transposed convolution as a GEMM over its input
 // pixels, the heads): k_sep_u<..., TR = 2> -- no depthwise, the rest as launch_sep_train.  `in` needs no header.
 // Returns the statistics rows written (t.stat != NULL) or 1, 0 when the shape is not one the kernel takes.
 int launch_rows_train(const RowsTrainArgs& t, hipStream_t s) {
-#if PP_SPLIT_MODE != 1
-    (void)t; (void)s;
-    return 0;
-#else
     const long long M = t.rows;
     if (t.K % KC != 0 || t.N % 32 != 0 || M % 2 != 0 || M >= (1 << 24) || M * t.K * 4 >= (1ll << 31) - 4096 || t.ld_out % 4 != 0)
         return 0;
@@ -1253,11 +1204,10 @@ int launch_rows_train(const RowsTrainArgs& t, hipStream_t s) {
     else if (nt == 64) PP_LAUNCH(tg, (k_sep_u<64, 1, 3, 1, 0, 2>), grid, dim3(256), 0, s, a, ntiles);
     else PP_LAUNCH(tg, (k_sep_u<32, 1, 3, 1, 0, 2>), grid, dim3(256), 0, s, a, ntiles);
     return gx;
-#endif
 }
 
 // ---------------------------------------------------------------------------------------
-// Separable stride-1 layer with 256 output channels, depthwise computed ONCE per pixel (two-piece builds).
+// Separable stride-1 layer with 256 output channels, depthwise computed ONCE per pixel.
 //
 // k_sep_u runs a 256-channel layer as two columns of 128-channel workgroups, each computing the depthwise of its
 // pixels again (window loads and FMAs twice per pixel).  Here one 8-wave workgroup owns 128 pixels x all 256
@@ -1268,7 +1218,6 @@ int launch_rows_train(const RowsTrainArgs& t, hipStream_t s) {
 // iterations (each with twice the matrix work to overlap).  113 KB of LDS: one workgroup (two waves per SIMD) per CU,
 // the occupancy of the 200-register k_sep_u<128>.  Skeleton (persistent XCD-aware tile walk, load / stage / multiply
 // cursors, one barrier per position, transposing epilogue) as k_sep_u.  cin % 64 == 0.
-#if PP_SPLIT_MODE != 0
 template <int CO>   // output channels of the layer (256)
 __global__ __launch_bounds__(512, 1) void k_sep_p(GemmArgs a, int ntiles) {
     constexpr int KCH = 16, LSTR = KCH + 4, WW = 4, NLD = 12;
@@ -1372,13 +1321,12 @@ __global__ __launch_bounds__(512, 1) void k_sep_p(GemmArgs a, int ntiles) {
             const float* cB = cB0 + (((I) & 1) * 2 + c) * SB1;                                           \
             const float4 a0 = *reinterpret_cast<const float4*>(cA), a1 = *reinterpret_cast<const float4*>(cA + 4);  \
             const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};                        \
-            bf16x8 ah, am, al;                                                                           \
-            split_bf16x3(av, ah, am, al);                                                                \
+            f16x8 ah, am;                                                                                \
+            split_f16x2(av, ah, am);                                                                     \
             _Pragma("unroll") for (int n = 0; n < NTILES; ++n) {                                         \
-                const bf16x8 bh = *reinterpret_cast<const bf16x8*>(cB + n * 32 * 8);                     \
-                const bf16x8 bm = *reinterpret_cast<const bf16x8*>(cB + CO * 8 + n * 32 * 8);           \
-                [[maybe_unused]] const bf16x8 bl = PC_LO(cB);                                            \
-                PC_PRODUCTS(acc[n], ah, am, al, bh, bm, bl)                                              \
+                const f16x8 bh = *reinterpret_cast<const f16x8*>(cB + n * 32 * 8);                       \
+                const f16x8 bm = *reinterpret_cast<const f16x8*>(cB + CO * 8 + n * 32 * 8);             \
+                PC_PRODUCTS(acc[n], ah, am, bh, bm)                                                      \
             }                                                                                            \
         }                                                                                                \
     }
@@ -1471,18 +1419,13 @@ static void launch_p(const GemmArgs& a, hipStream_t s) {
     gx = (gx + 7) & ~7;
     PP_LAUNCH("k_sep_p", k_sep_p<256>, dim3((unsigned)gx), dim3(512), 0, s, a, ntiles);
 }
-#endif   // PP_SPLIT_MODE != 0
 
-// does k_sep_p run this separable layer?  (256 output channels, stride 1, dense input, two-piece builds, large enough
-// for the persistent kernels)
+// does k_sep_p run this separable layer?  (256 output channels, stride 1, dense input, large enough for the persistent
+// kernels)
 static bool sep_p_runs(const void* wt16, int stride, int cin, int cout, int n_total, long long M, const int* occ) {
-#if PP_SPLIT_MODE != 0
     // (the 128-channel instantiation, where k_sep_u already computes the depthwise once, measured 32 us against 28.5)
     return wt16 != nullptr && split_precision() && stride == 1 && occ == nullptr && cout == 256 &&
            n_total == 256 && cin % 64 == 0 && cin <= 256 && M < (1 << 24);
-#else
-    return false;
-#endif
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1494,7 +1437,7 @@ static bool sep_p_runs(const void* wt16, int stride, int cin, int cout, int n_to
 // w + 4, ...; each wave has its own A and weight tiles in LDS (no workgroup barrier inside the K loop),
 // and the four partial accumulators are added through LDS in a fixed order (deterministic), wave n
 // finishing channel tile n (bias, ReLU, 16-byte stores).  The chain is a quarter as long.
-// Split-precision bf16 only; cin % 64 == 0.
+// Split-precision float16 only; cin % 64 == 0.
 // NW: waves per workgroup = ways the K range is split (4, or 8 when even the 4-way kernel leaves the chip to less
 // than one workgroup per CU: the chain halves again, one workgroup per CU by LDS)
 template <int NT, int S, int NW = 4>
@@ -1502,7 +1445,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_sep_k4(GemmArgs a)
     constexpr int KCH = 16, LSTR = KCH + 4;
     constexpr int WW = S + 3, NLD = 3 * WW;
     constexpr int SAW = 32 * LSTR;              // one A buffer (floats)
-    constexpr int SB = PP_NPIECE * NT * 8;              // one weight buffer: [3 pieces][NT][16 bf16]
+    constexpr int SB = PP_NPIECE * NT * 8;              // one weight buffer: [2 pieces][NT][16 f16]
     constexpr int NTILES = NT / 32;
     constexpr int NBL = NT * 2 * PP_NPIECE / 64;            // 16-byte weight items per lane per chunk
     constexpr int WV = 2 * SAW + 2 * SB;        // floats per wave
@@ -1609,14 +1552,13 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_sep_k4(GemmArgs a)
             const float* cB = cB0 + buf * SB;
             const float4 a0 = *reinterpret_cast<const float4*>(cA), a1 = *reinterpret_cast<const float4*>(cA + 4);
             const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-            bf16x8 ah, am, al;
-            split_bf16x3(av, ah, am, al);
+            f16x8 ah, am;
+            split_f16x2(av, ah, am);
 #pragma unroll
             for (int n = 0; n < NTILES; ++n) {
-                const bf16x8 bh = *reinterpret_cast<const bf16x8*>(cB + n * 32 * 8);
-                const bf16x8 bm = *reinterpret_cast<const bf16x8*>(cB + NT * 8 + n * 32 * 8);
-                [[maybe_unused]] const bf16x8 bl = PC_LO(cB + 2 * NT * 8 + n * 32 * 8);
-                PC_PRODUCTS(acc[n], ah, am, al, bh, bm, bl)
+                const f16x8 bh = *reinterpret_cast<const f16x8*>(cB + n * 32 * 8);
+                const f16x8 bm = *reinterpret_cast<const f16x8*>(cB + NT * 8 + n * 32 * 8);
+                PC_PRODUCTS(acc[n], ah, am, bh, bm)
             }
         }
         if (j + 1 < niter) {
@@ -1675,9 +1617,9 @@ static bool sep_k8_runs(int cin, int n_total, long long M) {
     return cin % 256 == 0 && (M + 31) / 32 * (n_total / 64) <= (long long)g_num_cus;
 }
 template <int S>
-static void launch_k4(const GemmArgs& a, int n_total, hipStream_t s) {
+static void launch_k4(const GemmArgs& a, int n_total, bool k8, hipStream_t s) {
     dim3 grid((unsigned)((a.M + 31) / 32), n_total / 64);
-    if (sep_k8_runs(a.cin, n_total, a.M)) {
+    if (k8) {
         PP_LAUNCH("k_sep_k4", (k_sep_k4<64, S, 8>), grid, dim3(512), 0, s, a);
         return;
     }
@@ -1727,13 +1669,12 @@ __device__ __forceinline__ void deconv_tile_epilogue(const GemmArgs& a, f32x16 (
             for (int g = 0; g < 2; ++g) {
                 const float av[8] = {v[8 * g], v[8 * g + 1], v[8 * g + 2], v[8 * g + 3],
                                      v[8 * g + 4], v[8 * g + 5], v[8 * g + 6], v[8 * g + 7]};
-                bf16x8 xh, xm, xl;
-                split_bf16x3(av, xh, xm, xl);
+                f16x8 xh, xm;
+                split_f16x2(av, xh, xm);
                 const float* hW = sHW + ((n * 2 + g) * PP_NPIECE * 32 + r32) * 8 + ((h ^ ((r32 >> 3) & 1)) * 4);
-                const bf16x8 wh = *reinterpret_cast<const bf16x8*>(hW);
-                const bf16x8 wm = *reinterpret_cast<const bf16x8*>(hW + 32 * 8);
-                [[maybe_unused]] const bf16x8 wl = PC_LO(hW + 2 * 32 * 8);
-                PC_PRODUCTS(hacc, wh, wm, wl, xh, xm, xl)
+                const f16x8 wh = *reinterpret_cast<const f16x8*>(hW);
+                const f16x8 wm = *reinterpret_cast<const f16x8*>(hW + 32 * 8);
+                PC_PRODUCTS(hacc, wh, wm, xh, xm)
             }
         }
         if (dst != nullptr && ok) {   // concat slice (only when the heads are not fused): 4 consecutive channels per store
@@ -1758,13 +1699,13 @@ __device__ __forceinline__ void deconv_tile_epilogue(const GemmArgs& a, f32x16 (
 }
 
 // ---------------------------------------------------------------------------------------
-// Uniform-wave Conv2DTranspose (kernel == stride) + BN + ReLU [+ fused SSD heads], split-precision bf16.
+// Uniform-wave Conv2DTranspose (kernel == stride) + BN + ReLU [+ fused SSD heads], split-precision float16.
 //
 // Same skeleton as k_sep_u (persistent 4-wave workgroups, wave w owns input pixels 32w..32w+31 of a
 // 128-pixel tile, one barrier per 16-channel K-chunk for the shared weight tile), but the input operand
 // needs no LDS at all: lane (r, h) owns pixel r, channels 8h..8h+7 of the chunk, i.e. 32 contiguous
 // bytes of the input row, loaded straight into registers two K-chunks ahead (two register sets
-// alternate; every layer has an even number of chunks), split into three bf16 pieces and multiplied.
+// alternate; every layer has an even number of chunks), split into two float16 pieces and multiplied.
 // The MFMAs take the WEIGHT fragment as the A operand and the input fragment as B, so the accumulator
 // holds out^T: lane = pixel, registers = 16 channels of that pixel.  That layout is, up to a fixed
 // permutation of k, the B operand of the head GEMM head^T[32 x px] = Wh^T[32 x ch] . act^T[ch x px]:
@@ -1779,10 +1720,10 @@ template <int NT, int WPS>
 __global__ __launch_bounds__(256, WPS) void k_deconv_u(GemmArgs a, int ntiles) {
     constexpr int KCH = 16;
     constexpr int NTILES = NT / 32;
-    constexpr int SB = PP_NPIECE * NT * 8;                       // one weight buffer: [3 pieces][NT][8 floats]
+    constexpr int SB = PP_NPIECE * NT * 8;                       // one weight buffer: [2 pieces][NT][8 floats]
     constexpr int NBI = NT * 2 * PP_NPIECE;                          // 16-byte weight items per chunk
     constexpr int NB4 = (NBI + 255) / 256;
-    constexpr int SHW = (NT / 16) * PP_NPIECE * 32 * 8;          // head weights: [NT/16][3][32 cols][8 floats]
+    constexpr int SHW = (NT / 16) * PP_NPIECE * 32 * 8;          // head weights: [NT/16][2][32 cols][8 floats]
     __shared__ __attribute__((aligned(16))) float sB[2 * SB];
     __shared__ __attribute__((aligned(16))) float sHW[SHW];
     __shared__ float s_bias[NT];
@@ -1869,7 +1810,7 @@ __global__ __launch_bounds__(256, WPS) void k_deconv_u(GemmArgs a, int ntiles) {
     // bias and this branch's head-kernel slice -> LDS, after the first operand loads are in flight (the
     // prologue's memory round trips overlap)
     if (tid < NT) s_bias[tid] = a.bias[cbase + tid];
-    if (heads) {   // three bf16 pieces; 16-byte halves swapped on odd groups of 8 columns (bank conflicts)
+    if (heads) {   // two float16 pieces; 16-byte halves swapped on odd groups of 8 columns (bank conflicts)
         for (int e = tid; e < SHW / 4; e += 256)
             reinterpret_cast<float4*>(sHW)[e ^ ((e >> 4) & 1)] = reinterpret_cast<const float4*>(a.head_wt16)[e];
         if (tid < PP_HEAD_COLS) s_hbias[tid] = a.head_bias[tid];
@@ -1892,16 +1833,15 @@ __global__ __launch_bounds__(256, WPS) void k_deconv_u(GemmArgs a, int ntiles) {
     {                                                                                                    \
         const int i_ = (I);                                                                              \
         const float av_[8] = {RA0.x, RA0.y, RA0.z, RA0.w, RA1.x, RA1.y, RA1.z, RA1.w};                   \
-        bf16x8 ah_, am_, al_;                                                                            \
-        split_bf16x3(av_, ah_, am_, al_);                                                                \
+        f16x8 ah_, am_;                                                                                  \
+        split_f16x2(av_, ah_, am_);                                                                      \
         if (i_ + 2 < total) D_LOAD_A(RA0, RA1)                                                           \
         {                                                                                                \
             const float* cB_ = sB + (i_ & 1) * SB + r32 * 8 + ((h ^ ((r32 >> 3) & 1)) * 4);              \
             _Pragma("unroll") for (int n = 0; n < NTILES; ++n) {                                         \
-                const bf16x8 bh_ = *reinterpret_cast<const bf16x8*>(cB_ + n * 32 * 8);                   \
-                const bf16x8 bm_ = *reinterpret_cast<const bf16x8*>(cB_ + NT * 8 + n * 32 * 8);          \
-                [[maybe_unused]] const bf16x8 bl_ = PC_LO(cB_ + 2 * NT * 8 + n * 32 * 8);      \
-                PC_PRODUCTS(acc[n], bh_, bm_, bl_, ah_, am_, al_)                                        \
+                const f16x8 bh_ = *reinterpret_cast<const f16x8*>(cB_ + n * 32 * 8);                     \
+                const f16x8 bm_ = *reinterpret_cast<const f16x8*>(cB_ + NT * 8 + n * 32 * 8);            \
+                PC_PRODUCTS(acc[n], bh_, bm_, ah_, am_)                                                  \
             }                                                                                            \
         }                                                                                                \
         if (i_ + 1 < total) D_STORE_B((i_ + 1) & 1)   /* weight tile of position i+1 -> LDS */           \
@@ -1933,7 +1873,6 @@ __global__ __launch_bounds__(256, WPS) void k_deconv_u(GemmArgs a, int ntiles) {
 #undef D_FILL_OPIX
 }
 
-#if PP_SPLIT_MODE != 0
 // ---------------------------------------------------------------------------------------
 // Conv2DTranspose (kernel == stride) + BN + ReLU [+ fused SSD heads] with the INPUT operand resident in
 // registers (round 3).  k_deconv_u above gives every (pixel tile, tap) pair to a workgroup of its own tap
@@ -1962,7 +1901,6 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
     constexpr int NB = 3;                                // LDS ring of weight panels
     constexpr int PD = 2;                                // fragment reads run PD steps ahead of their products
     constexpr int SHW = (128 / 16) * 2 * 32 * 8;         // head weights: [cout/16][2 pieces][32 cols][8 floats]
-    static_assert(PP_NPIECE == 2, "two-piece operands");
     static_assert(STEPS % 4 == 0 && PD < 4, "fragment ring of four");
     __shared__ __attribute__((aligned(16))) float sW[NB * PANEL];
     __shared__ __attribute__((aligned(16))) float sHW[SHW];
@@ -2036,7 +1974,7 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
     R_LOAD_NEXT()                        // panel 1: written at step 0 of panel 0
     __syncthreads();
 
-    bf16x8 xh[NCH], xm[NCH];             // the wave's 32 pixels x CIN channels, two float16 pieces
+    f16x8 xh[NCH], xm[NCH];             // the wave's 32 pixels x CIN channels, two float16 pieces
     int tile_cur = tile, opix0;
     bool ok = ok0_;
     {
@@ -2047,8 +1985,7 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             const float av[8] = {ra0[c][0].x, ra0[c][0].y, ra0[c][0].z, ra0[c][0].w, ra0[c][1].x, ra0[c][1].y, ra0[c][1].z, ra0[c][1].w};
-            bf16x8 lo_;
-            split_bf16x3(av, xh[c], xm[c], lo_);
+            split_f16x2(av, xh[c], xm[c]);
         }
     }
     const float* const cW = sW + r32 * 8 + ((h ^ ((r32 >> 3) & 1)) * 4);
@@ -2057,11 +1994,11 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
     const float* pcur = cW;              // this lane's fragment base in that slot / in the next one
     const float* pnxt = cW + PANEL;
     // fragment ring: step fs uses entry fs % 4, requested PD steps earlier (also across panels and units)
-    bf16x8 fh[4], fm[4];
+    f16x8 fh[4], fm[4];
 #pragma unroll
     for (int i = 0; i < PD; ++i) {
-        fh[i] = *reinterpret_cast<const bf16x8*>(pcur + i * 512);
-        fm[i] = *reinterpret_cast<const bf16x8*>(pcur + i * 512 + 256);
+        fh[i] = *reinterpret_cast<const f16x8*>(pcur + i * 512);
+        fm[i] = *reinterpret_cast<const f16x8*>(pcur + i * 512 + 256);
     }
 
     // CIN <= 128: the raw input of the NEXT tile is fetched during the last unit of the current one (CIN / 4 more
@@ -2093,8 +2030,7 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
                 const float av[8] = {ra[c][0].x, ra[c][0].y, ra[c][0].z, ra[c][0].w, ra[c][1].x, ra[c][1].y, ra[c][1].z, ra[c][1].w};
-                bf16x8 lo_;
-                split_bf16x3(av, xh[c], xm[c], lo_);
+                split_f16x2(av, xh[c], xm[c]);
             }
         }
         const int ti = tap / a.k;
@@ -2127,10 +2063,10 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
             if (s == 4) __syncthreads();   // publishes the panel written at step 0 (read from step 8 - PD on)
             {   // fragments of step fs + PD
                 const float* w_ = (s + PD < 8) ? pcur + (s + PD) * 512 : pnxt + (s + PD - 8) * 512;
-                fh[(fs + PD) & 3] = *reinterpret_cast<const bf16x8*>(w_);
-                fm[(fs + PD) & 3] = *reinterpret_cast<const bf16x8*>(w_ + 256);
+                fh[(fs + PD) & 3] = *reinterpret_cast<const f16x8*>(w_);
+                fm[(fs + PD) & 3] = *reinterpret_cast<const f16x8*>(w_ + 256);
             }
-            PC_PRODUCTS(acc, fh[fs & 3], fm[fs & 3], fm[fs & 3], xh[c], xm[c], xm[c])
+            PC_PRODUCTS(acc, fh[fs & 3], fm[fs & 3], xh[c], xm[c])
             if (s == 0) {                // the panel after this one -> its ring slot (fetched one panel ago)
                 const int ws = (slot + 1 == NB) ? 0 : slot + 1;
                 R_STORE_W(ws)
@@ -2163,12 +2099,12 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
                     for (int g = 0; g < 2; ++g) {
                         const float av[8] = {v[8 * g], v[8 * g + 1], v[8 * g + 2], v[8 * g + 3],
                                              v[8 * g + 4], v[8 * g + 5], v[8 * g + 6], v[8 * g + 7]};
-                        bf16x8 yh, ym, yl;
-                        split_bf16x3(av, yh, ym, yl);
+                        f16x8 yh, ym;
+                        split_f16x2(av, yh, ym);
                         const float* hW = cHW + (nt * 2 + g) * 2 * 32 * 8;
-                        const bf16x8 gh = *reinterpret_cast<const bf16x8*>(hW);
-                        const bf16x8 gm = *reinterpret_cast<const bf16x8*>(hW + 32 * 8);
-                        PC_PRODUCTS(hacc, gh, gm, gm, yh, ym, yl)
+                        const f16x8 gh = *reinterpret_cast<const f16x8*>(hW);
+                        const f16x8 gm = *reinterpret_cast<const f16x8*>(hW + 32 * 8);
+                        PC_PRODUCTS(hacc, gh, gm, yh, ym)
                     }
                 }
                 if (dst != nullptr && ok) {
@@ -2213,9 +2149,6 @@ static void launch_deconv_r(const GemmArgs& a, hipStream_t s) {
     const int G = (int)((U + upw - 1) / upw);
     PP_LAUNCH("k_deconv_r", (k_deconv_r<CIN>), dim3((unsigned)G), dim3(256), 0, s, a, (int)U, upw);
 }
-#else
-static bool deconv_r_runs(const LayerDesc&) { return false; }
-#endif
 
 // ---------------------------------------------------------------------------------------
 // Split-K Conv2DTranspose (+ fused heads) for small maps: the four waves of a workgroup share one
@@ -2228,7 +2161,7 @@ template <int NT>
 __global__ __launch_bounds__(256, 2) void k_deconv_k4(GemmArgs a) {
     constexpr int KCH = 16;
     constexpr int NTILES = NT / 32;
-    constexpr int SB = PP_NPIECE * NT * 8;                       // one weight tile: [3 pieces][NT][8 floats]
+    constexpr int SB = PP_NPIECE * NT * 8;                       // one weight tile: [2 pieces][NT][8 floats]
     constexpr int NBL = NT * 2 * PP_NPIECE / 64;                     // 16-byte weight items per lane per chunk
     constexpr int SHW = (NT / 16) * PP_NPIECE * 32 * 8;
     constexpr int SLOT = 16 * 64;                        // one partial accumulator tile (floats)
@@ -2304,14 +2237,13 @@ __global__ __launch_bounds__(256, 2) void k_deconv_k4(GemmArgs a) {
                 for (int r = 0; r < NBL; ++r) rb[r] = buf_load16(rs_wt, boff[r], (unsigned)(wave + 4 * (j + 1)) * bstep);
             }
             const float av[8] = {ra[j][0].x, ra[j][0].y, ra[j][0].z, ra[j][0].w, ra[j][1].x, ra[j][1].y, ra[j][1].z, ra[j][1].w};
-            bf16x8 ah, am, al;
-            split_bf16x3(av, ah, am, al);
+            f16x8 ah, am;
+            split_f16x2(av, ah, am);
 #pragma unroll
             for (int n = 0; n < NTILES; ++n) {
-                const bf16x8 bh = *reinterpret_cast<const bf16x8*>(cB + n * 32 * 8);
-                const bf16x8 bm = *reinterpret_cast<const bf16x8*>(cB + NT * 8 + n * 32 * 8);
-                [[maybe_unused]] const bf16x8 bl = PC_LO(cB + 2 * NT * 8 + n * 32 * 8);
-                PC_PRODUCTS(acc[n], bh, bm, bl, ah, am, al)
+                const f16x8 bh = *reinterpret_cast<const f16x8*>(cB + n * 32 * 8);
+                const f16x8 bm = *reinterpret_cast<const f16x8*>(cB + NT * 8 + n * 32 * 8);
+                PC_PRODUCTS(acc[n], bh, bm, ah, am)
             }
         }
     }
@@ -2371,13 +2303,12 @@ __global__ __launch_bounds__(256, 2) void k_deconv_k4(GemmArgs a) {
             for (int g = 0; g < 2; ++g) {
                 const float av[8] = {v[8 * g], v[8 * g + 1], v[8 * g + 2], v[8 * g + 3],
                                      v[8 * g + 4], v[8 * g + 5], v[8 * g + 6], v[8 * g + 7]};
-                bf16x8 xh, xm, xl;
-                split_bf16x3(av, xh, xm, xl);
+                f16x8 xh, xm;
+                split_f16x2(av, xh, xm);
                 const float* hW = sHW + ((wave * 2 + g) * PP_NPIECE * 32 + r32) * 8 + ((h ^ ((r32 >> 3) & 1)) * 4);
-                const bf16x8 wh = *reinterpret_cast<const bf16x8*>(hW);
-                const bf16x8 wm = *reinterpret_cast<const bf16x8*>(hW + 32 * 8);
-                [[maybe_unused]] const bf16x8 wl = PC_LO(hW + 2 * 32 * 8);
-                PC_PRODUCTS(hpart, wh, wm, wl, xh, xm, xl)
+                const f16x8 wh = *reinterpret_cast<const f16x8*>(hW);
+                const f16x8 wm = *reinterpret_cast<const f16x8*>(hW + 32 * 8);
+                PC_PRODUCTS(hpart, wh, wm, xh, xm)
             }
         }
     }
@@ -2436,7 +2367,7 @@ static bool deconv_k4_runs(const LayerDesc& L, long long M) {
     static int force = -2;
     if (force == -2) { const char* e = getenv("PP_DECONV_K4"); force = e ? atoi(e) : -1; }
     if (force == 0 || L.cin % 64 != 0 || L.cin > 256) return false;
-    const int nt = L.cout % 128 == 0 ? 128 : (L.cout % 64 == 0 ? 64 : 32);
+    const int nt = col_tile(L.cout);
     const int half_cus = force > 0 ? 2 * force : 3;
     return 2 * ((M + 31) / 32 * (L.n_total / nt)) <= (long long)half_cus * g_num_cus;
 }
@@ -2476,8 +2407,8 @@ static bool ws_small_tile(long long M, int n_total, int NT) {
 }
 
 template <int NT, int MODE, int S>
-static void launch_ws(const GemmArgs& a, int n_total, hipStream_t s) {
-    if (ws_small_tile(a.M, n_total, NT)) {
+static void launch_ws(const GemmArgs& a, int n_total, int pxb, hipStream_t s) {
+    if (pxb == 64) {
         dim3 grid((unsigned)((a.M + 63) / 64), n_total / NT);
         PP_LAUNCH("k_gemm_ws", (k_gemm_ws<NT, MODE, S, 64>), grid, dim3(256), 0, s, a);
     } else {
@@ -2501,28 +2432,19 @@ static bool sep_uniform() {
 // the layer would otherwise put fewer than ~2.5 waves on a SIMD (small maps: a wave per 32 pixels x NT
 // channels is the scheduling grain; the depthwise is recomputed per channel tile, which the idle
 // vector pipe absorbs)
-static int sep_u_nt(const LayerDesc& L, int batch) {
+static int sep_u_nt(const LayerDesc& L, long long rows) {
     if (L.cout % 64 != 0) return 32;
     if (L.cout % 128 != 0) return 64;
-    const long long waves128 = ((long long)batch * L.out_h * L.out_w + 31) / 32 * (L.cout / 128);
+    const long long waves128 = (rows + 31) / 32 * (L.cout / 128);
     static int force = -1;
     if (force < 0) { const char* e = getenv("PP_SEP_NT"); force = e ? atoi(e) : 0; }
     if (force == 64 || force == 128) return force;
     // split-precision path: the depthwise (VALU) is the larger half of a chunk, so recomputing it per
     // channel tile costs more than the thinner wave supply (measured: block3 at B=64 36 vs 40 us)
-    if (L.d_wt16 != nullptr && split_precision()) return 128;
+    if (split_operands(L)) return 128;
     return (waves128 * 2 < 5ll * g_num_cus * 4) ? 64 : 128;
 }
 
-// workgroups per CU of the split-precision k_sep_u<128, 1, ...> instantiation (its register budget: 256 / 168)
-#ifndef PP_SEP128_WPB
-#define PP_SEP128_WPB 2
-#endif
-#ifndef PP_SEP64_WPB
-#define PP_SEP64_WPB 3
-#endif
-
-// which kernel runs layer L (shared by the launcher and the profiler tags)
 static bool use_ws(const LayerDesc& L) {
     // MODE 1 producers own 4 consecutive pixels, MODE 0 producers 2 of one row: the frame's pixel
     // count (hence every batch's) must be divisible accordingly, else the generic kernel runs
@@ -2530,59 +2452,109 @@ static bool use_ws(const LayerDesc& L) {
     return (L.stride == 1 || L.stride == 2) && (L.out_w % 2 == 0);
 }
 
+// the uniform-wave separable kernels (k_sep_u and the split-K / 256-channel ones chosen among them) run a separable
+// layer whose pixel range ends at m_end (k_sep_u's float-reciprocal index math)
+static bool sep_uniform_runs(const LayerDesc& L, long long m_end) {
+    return L.kind == LAYER_SEP && use_ws(L) && sep_uniform() && m_end < (1 << 24);
+}
+
+// one workgroup column covers the whole channel range of a deconv's tap (NT == cout): the fused head GEMM fits
+static bool one_column_tile(const LayerDesc& L) {
+    return L.cout == 32 || L.cout == 64 || L.cout == 128;
+}
+
 // the split-precision uniform-wave deconv kernel runs when its operands exist (cin % 32 == 0: an even
-// number of 16-channel chunks) and, with fused heads, when one column tile covers the tap (NT == cout)
+// number of 16-channel chunks) and, with fused heads, when one column tile covers the tap
 static bool deconv_uniform(const LayerDesc& L) {
-    if (L.kind != LAYER_DECONV || L.d_wt16 == nullptr || L.cin % 32 != 0 || !split_precision()) return false;
-    if (L.head_mode != 0 && (L.d_head_wt16 == nullptr || !(L.cout == 32 || L.cout == 64 || L.cout == 128))) return false;
+    if (L.kind != LAYER_DECONV || !split_operands(L) || L.cin % 32 != 0) return false;
+    if (L.head_mode != 0 && (L.d_head_wt16 == nullptr || !one_column_tile(L))) return false;
     return true;
 }
 
 // can layer L (a separable layer) read a sparse canvas at this batch size?  (the kernels with the cell-map lookup)
 bool sparse_input_supported(const LayerDesc& L, int batch) {
-    return L.kind == LAYER_SEP && use_ws(L) && sep_uniform() && L.d_wt16 != nullptr && split_precision() &&
-           (long long)batch * L.out_h * L.out_w < (1 << 24);
+    return sep_uniform_runs(L, (long long)batch * L.out_h * L.out_w) && split_operands(L);
 }
 
 // a deconv can carry the fused head GEMM when one workgroup column covers the tap's whole channel
-// range (NT == cout) and the wave-specialised kernel runs it
+// range and the wave-specialised kernel runs it
 bool deconv_can_fuse_heads(const LayerDesc& L) {
-    return L.kind == LAYER_DECONV && (L.cout == 32 || L.cout == 64 || L.cout == 128) && use_ws(L);
+    return L.kind == LAYER_DECONV && one_column_tile(L) && use_ws(L);
 }
 
 static long long layer_rows(const LayerDesc& L, int batch) {
     return (L.kind == LAYER_SEP) ? (long long)batch * L.out_h * L.out_w : (long long)batch * L.in_h * L.in_w;
 }
 
+// the kernel that runs one launch of a layer, with its template arguments
+enum class LayerKernel { SEP_K4, SEP_P, SEP_U, DECONV_K4, DECONV_R, DECONV_U, GEMM_WS, GEMM_LAYER };
+struct LayerPlan {
+    LayerKernel kernel;
+    int nt;      // channel tile NT (k_sep_u, k_deconv_k4 / _u, k_gemm_ws / _layer)
+    int cin;     // CIN (k_deconv_r)
+    int s;       // stride S (k_sep_k4, k_sep_u, k_gemm_ws)
+    int wpc;     // workgroups per CU (k_sep_u)
+    int prec;    // PREC, OCC (k_sep_u)
+    int occ;
+    int k8;      // the eight-way split (k_sep_k4)
+    int pxb;     // pixel tile (k_gemm_ws)
+    int mode;    // MODE (k_gemm_ws / _layer): 0 separable, 1 deconv or heads
+};
+
+// rows: the output rows of this launch (what the size heuristics weigh); m_end: the end of its pixel range (frame0 > 0:
+// a sub-range of a larger batch, see launch_layer)
+static LayerPlan plan_layer(const LayerDesc& L, long long rows, long long m_end) {
+    LayerPlan p = {};
+    p.nt = (L.kind == LAYER_HEAD) ? 32 : col_tile(L.cout);
+    p.mode = (L.kind == LAYER_SEP) ? 0 : 1;
+    p.s = (L.kind == LAYER_SEP) ? L.stride : 1;
+    if (sep_uniform_runs(L, m_end)) {
+        if (sep_k4_runs(L.d_wt16, L.cin, L.n_total, rows)) {   // small map
+            p.kernel = LayerKernel::SEP_K4;
+            p.k8 = sep_k8_runs(L.cin, L.n_total, rows);
+        } else if (sep_p_runs(L.d_wt16, L.stride, L.cin, L.cout, L.n_total, rows, L.d_occ)) {   // depthwise once for 256 channels
+            p.kernel = LayerKernel::SEP_P;
+        } else {
+            p.kernel = LayerKernel::SEP_U;
+            p.nt = sep_u_nt(L, rows);
+            p.prec = split_operands(L);
+            p.occ = p.prec && L.d_occ != nullptr;
+            p.wpc = sep_u_wpc(p.nt, p.s, p.prec);
+        }
+    } else if (deconv_uniform(L)) {
+        if (deconv_k4_runs(L, rows)) {   // small map: split-K
+            p.kernel = LayerKernel::DECONV_K4;
+        } else if (deconv_r_runs(L)) {   // input resident in registers
+            p.kernel = LayerKernel::DECONV_R;
+            p.cin = L.cin;
+        } else {
+            p.kernel = LayerKernel::DECONV_U;
+        }
+    } else if (use_ws(L)) {
+        p.kernel = LayerKernel::GEMM_WS;
+        p.pxb = ws_small_tile(rows, L.n_total, p.nt) ? 64 : 128;
+    } else {
+        p.kernel = LayerKernel::GEMM_LAYER;
+    }
+    return p;
+}
+
 // name of the template instantiation that runs layer L at this batch size (profiler tags)
 std::string layer_kernel_name(const LayerDesc& L, int batch) {
-    const int nt = (L.kind == LAYER_HEAD) ? 32 : (L.cout % 128 == 0 ? 128 : (L.cout % 64 == 0 ? 64 : 32));
-    const int mode = (L.kind == LAYER_SEP) ? 0 : 1;
+    const LayerPlan p = plan_layer(L, layer_rows(L, batch), layer_rows(L, batch));
     char buf[64];
-    if (L.kind == LAYER_SEP && use_ws(L) && sep_uniform() && layer_rows(L, batch) < (1 << 24)) {
-        if (sep_k4_runs(L.d_wt16, L.cin, L.n_total, layer_rows(L, batch))) {
-            if (sep_k8_runs(L.cin, L.n_total, layer_rows(L, batch))) snprintf(buf, sizeof(buf), "k_sep_k4<64,%d,8>", L.stride);
-            else snprintf(buf, sizeof(buf), "k_sep_k4<64,%d>", L.stride);
-            return std::string(buf);
-        }
-        if (sep_p_runs(L.d_wt16, L.stride, L.cin, L.cout, L.n_total, layer_rows(L, batch), L.d_occ)) return std::string("k_sep_p");
-        const int unt = sep_u_nt(L, batch);
-        const bool bf = L.d_wt16 != nullptr && split_precision();
-        int wps;   // workgroups per CU of the instantiation launch_layer picks (launch_u<NT, S, WPS, WPB>)
-        if (L.stride == 1) wps = bf ? (unt == 128 ? PP_SEP128_WPB : (unt == 64 ? PP_SEP64_WPB : 3)) : (unt == 128 ? 3 : 4);
-        else wps = bf ? (unt == 128 ? 2 : 3) : (unt == 128 ? 2 : (unt == 64 ? 3 : 4));
-        snprintf(buf, sizeof(buf), "k_sep_u<%d,%d,%d,%d,%d>", unt, L.stride, wps, bf ? 1 : 0, (bf && L.d_occ) ? 1 : 0);
-    } else if (deconv_uniform(L) && deconv_k4_runs(L, layer_rows(L, batch))) {
-        snprintf(buf, sizeof(buf), "k_deconv_k4<%d>", nt);
-    } else if (deconv_uniform(L) && deconv_r_runs(L)) {
-        snprintf(buf, sizeof(buf), "k_deconv_r<%d>", L.cin);
-    } else if (deconv_uniform(L)) {
-        snprintf(buf, sizeof(buf), "k_deconv_u<%d,3>", nt);
-    } else if (use_ws(L)) {
-        const int pxb = ws_small_tile(layer_rows(L, batch), L.n_total, nt) ? 64 : 128;
-        snprintf(buf, sizeof(buf), "k_gemm_ws<%d,%d,%d,%d>", nt, mode, mode == 0 ? L.stride : 1, pxb);
-    } else {
-        snprintf(buf, sizeof(buf), "k_gemm_layer<%d,%d>", nt, mode);
+    switch (p.kernel) {
+    case LayerKernel::SEP_K4:
+        if (p.k8) snprintf(buf, sizeof(buf), "k_sep_k4<64,%d,8>", p.s);
+        else snprintf(buf, sizeof(buf), "k_sep_k4<64,%d>", p.s);
+        break;
+    case LayerKernel::SEP_P: snprintf(buf, sizeof(buf), "k_sep_p"); break;
+    case LayerKernel::SEP_U: snprintf(buf, sizeof(buf), "k_sep_u<%d,%d,%d,%d,%d>", p.nt, p.s, p.wpc, p.prec, p.occ); break;
+    case LayerKernel::DECONV_K4: snprintf(buf, sizeof(buf), "k_deconv_k4<%d>", p.nt); break;
+    case LayerKernel::DECONV_R: snprintf(buf, sizeof(buf), "k_deconv_r<%d>", p.cin); break;
+    case LayerKernel::DECONV_U: snprintf(buf, sizeof(buf), "k_deconv_u<%d,3>", p.nt); break;
+    case LayerKernel::GEMM_WS: snprintf(buf, sizeof(buf), "k_gemm_ws<%d,%d,%d,%d>", p.nt, p.mode, p.s, p.pxb); break;
+    case LayerKernel::GEMM_LAYER: snprintf(buf, sizeof(buf), "k_gemm_layer<%d,%d>", p.nt, p.mode); break;
     }
     return std::string(buf);
 }
@@ -2599,7 +2571,17 @@ bool launch_layer_subrange_ok(const LayerDesc& L, int frame0, int batch, int tot
     if (L.kind != LAYER_SEP) return false;
     const long long hw = (long long)L.out_h * L.out_w;
     if ((frame0 * hw) % PX_TILE != 0) return false;
-    return layer_kernel_name(L, batch).compare(0, 8, "k_sep_u<") == 0 && layer_kernel_name(L, total_batch).compare(0, 8, "k_sep_u<") == 0;
+    return plan_layer(L, batch * hw, batch * hw).kernel == LayerKernel::SEP_U &&
+           plan_layer(L, total_batch * hw, total_batch * hw).kernel == LayerKernel::SEP_U;
+}
+
+// f(std::integral_constant<int, V>{}) for the V of Vs that equals v (the last one when none does): a plan's value as a
+// template argument
+template <int V, int... Vs, class F>
+static void with_value(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>{});
+    else if (v == V) f(std::integral_constant<int, V>{});
+    else with_value<Vs...>(v, f);
 }
 
 int launch_layer(const LayerDesc& L, int batch, float* d_head, hipStream_t s, int frame0) {
@@ -2635,75 +2617,43 @@ int launch_layer(const LayerDesc& L, int batch, float* d_head, hipStream_t s, in
         // a sparse input is only understood by the split-precision uniform-wave / split-K kernels
         if (a.occ != nullptr && !sparse_input_supported(L, batch))
             return PP_ERR_UNSUPPORTED;
-        if (use_ws(L) && sep_uniform() && a.M < (1 << 24)) {   // k_sep_u's float-reciprocal index math
-            const int nt = sep_u_nt(L, batch);
-            const long long msel = (long long)batch * L.out_h * L.out_w;    // rows of THIS launch (a.M is the end of its pixel range)
-#if PP_SPLIT_MODE != 0
-            if (!sep_k4_runs(a.wt16, a.cin, L.n_total, msel) &&
-                sep_p_runs(a.wt16, L.stride, a.cin, L.cout, L.n_total, msel, a.occ)) {   // depthwise once for 256 channels
-                launch_p(a, s);
-            } else
-#endif
-            if (sep_k4_runs(a.wt16, a.cin, L.n_total, msel)) {   // small map
-                if (L.stride == 1) launch_k4<1>(a, L.n_total, s);
-                else launch_k4<2>(a, L.n_total, s);
-            } else if (L.stride == 1) {
-                if (nt == 128) launch_u<128, 1, 3, PP_SEP128_WPB>(a, L.n_total, s);
-                else if (nt == 64) launch_u<64, 1, 4, PP_SEP64_WPB>(a, L.n_total, s);
-                else launch_u<32, 1, 4, 3>(a, L.n_total, s);
-            } else {
-                if (nt == 128) launch_u<128, 2, 2, 2>(a, L.n_total, s);
-                else if (nt == 64) launch_u<64, 2, 3, 3>(a, L.n_total, s);
-                else launch_u<32, 2, 4, 3>(a, L.n_total, s);
-            }
-        } else if (use_ws(L)) {
-            if (L.stride == 1) {
-                if (L.cout % 128 == 0) launch_ws<128, 0, 1>(a, L.n_total, s);
-                else if (L.cout % 64 == 0) launch_ws<64, 0, 1>(a, L.n_total, s);
-                else launch_ws<32, 0, 1>(a, L.n_total, s);
-            } else {
-                if (L.cout % 128 == 0) launch_ws<128, 0, 2>(a, L.n_total, s);
-                else if (L.cout % 64 == 0) launch_ws<64, 0, 2>(a, L.n_total, s);
-                else launch_ws<32, 0, 2>(a, L.n_total, s);
-            }
-        } else {
-            if (L.cout % 128 == 0) launch_t<128, 0>(a, L.n_total, s);
-            else if (L.cout % 64 == 0) launch_t<64, 0>(a, L.n_total, s);
-            else launch_t<32, 0>(a, L.n_total, s);
-        }
     } else if (L.kind == LAYER_DECONV) {
         a.px_h = L.in_h; a.px_w = L.in_w; a.epi = 1;
         a.M = batch * L.in_h * L.in_w;
         if (L.cout % 32 != 0) return PP_ERR_UNSUPPORTED;
-        if (deconv_uniform(L) && deconv_k4_runs(L, a.M)) {   // small map: split-K
-            if (L.cout % 128 == 0) launch_deconv_k4<128>(a, L.n_total, s);
-            else if (L.cout % 64 == 0) launch_deconv_k4<64>(a, L.n_total, s);
-            else launch_deconv_k4<32>(a, L.n_total, s);
-#if PP_SPLIT_MODE != 0
-        } else if (deconv_uniform(L) && deconv_r_runs(L)) {   // input resident in registers
-            if (L.cin == 256) launch_deconv_r<256>(a, s);
-            else if (L.cin == 128) launch_deconv_r<128>(a, s);
-            else launch_deconv_r<64>(a, s);
-#endif
-        } else if (deconv_uniform(L)) {
-            if (L.cout % 128 == 0) launch_deconv_u<128>(a, L.n_total, s);
-            else if (L.cout % 64 == 0) launch_deconv_u<64>(a, L.n_total, s);
-            else launch_deconv_u<32>(a, L.n_total, s);
-        } else if (use_ws(L)) {
-            if (L.cout % 128 == 0) launch_ws<128, 1, 1>(a, L.n_total, s);
-            else if (L.cout % 64 == 0) launch_ws<64, 1, 1>(a, L.n_total, s);
-            else launch_ws<32, 1, 1>(a, L.n_total, s);
-        } else {
-            if (L.cout % 128 == 0) launch_t<128, 1>(a, L.n_total, s);
-            else if (L.cout % 64 == 0) launch_t<64, 1>(a, L.n_total, s);
-            else launch_t<32, 1>(a, L.n_total, s);
-        }
     } else {
         a.px_h = L.in_h; a.px_w = L.in_w; a.epi = 2;
         a.M = batch * L.in_h * L.in_w;
         if (L.n_total != 32) return PP_ERR_UNSUPPORTED;
-        if (use_ws(L)) launch_ws<32, 1, 1>(a, L.n_total, s);
-        else launch_t<32, 1>(a, L.n_total, s);
+    }
+    const LayerPlan p = plan_layer(L, layer_rows(L, batch), a.M);
+    const int n = L.n_total;
+    switch (p.kernel) {
+    case LayerKernel::SEP_K4:
+        with_value<1, 2>(p.s, [&](auto S) { launch_k4<S>(a, n, p.k8, s); });
+        break;
+    case LayerKernel::SEP_P:
+        launch_p(a, s);
+        break;
+    case LayerKernel::SEP_U:
+        with_value<1, 2>(p.s, [&](auto S) { with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_u<NT, S>(a, n, p.prec, p.occ, s); }); });
+        break;
+    case LayerKernel::DECONV_K4:
+        with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_deconv_k4<NT>(a, n, s); });
+        break;
+    case LayerKernel::DECONV_R:
+        with_value<256, 128, 64>(p.cin, [&](auto CIN) { launch_deconv_r<CIN>(a, s); });
+        break;
+    case LayerKernel::DECONV_U:
+        with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_deconv_u<NT>(a, n, s); });
+        break;
+    case LayerKernel::GEMM_WS:   // (the deconv and head products run as MODE 1 with S = 1)
+        if (p.mode == 0) with_value<1, 2>(p.s, [&](auto S) { with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_ws<NT, 0, S>(a, n, p.pxb, s); }); });
+        else with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_ws<NT, 1, 1>(a, n, p.pxb, s); });
+        break;
+    case LayerKernel::GEMM_LAYER:
+        with_value<0, 1>(p.mode, [&](auto MODE) { with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_t<NT, MODE>(a, n, s); }); });
+        break;
     }
     return 0;
 }

@@ -55,14 +55,6 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
     __shared__ int s_bad;      // a non-finite class logit anywhere in the frame, or a non-finite value in a selected row
 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-#ifdef PP_POST_STAMPS   // diagnostic build: phase times of frame 0 (100 MHz ticks), printed by thread 0
-    long long pst[24];
-    int psn = 0;
-#define P_STAMP() { if (psn < 24) pst[psn++] = wall_clock64(); }
-#else
-#define P_STAMP() {}
-#endif
-    P_STAMP()
     const long long A = p.A;
     const int napl = p.napl;
     const int ncls = p.ncls;
@@ -175,7 +167,6 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
     });
     if (bad) s_bad = 1;
     __syncthreads();
-    P_STAMP()   // candidates gathered
     int ncand = s_ncand;
     bool in_lds = ncand <= CCAP;
 
@@ -243,7 +234,6 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
             }
         }
         __syncthreads();
-        P_STAMP()   // one select pass
       }
       __syncthreads();
     };
@@ -272,7 +262,6 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
         else run_select(false, 0);                                    // (adversarial order: the old way)
     }
     __syncthreads();
-    P_STAMP()
     {
         const int shift = s_shift;
         const unsigned long long prefix = s_prefix;
@@ -297,7 +286,6 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
         }
     }
     __syncthreads();
-    P_STAMP()   // selected keys collected
     const int K = min(s_cnt, KTOP);
     // ---- order by descending key (rank by counting; keys are unique) ----
     if (tid < K) {
@@ -307,7 +295,6 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
         s_order[rank] = tid;
     }
     __syncthreads();
-    P_STAMP()   // ordered
 
     // ---- decode + stand-up AABB (float32, the reference's operation order) ----
     if (tid < K) {
@@ -363,7 +350,6 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
         s_aabb[tid][0] = x0; s_aabb[tid][1] = y0; s_aabb[tid][2] = x1; s_aabb[tid][3] = y1;
     }
     __syncthreads();
-    P_STAMP()   // decoded
 
     // ---- NMS over the first min(K, pre_max) boxes (already score-descending) ----
     // suppression masks: 8 threads share a row i and take every 8th j > i (the float64 division keeps
@@ -397,7 +383,6 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
         }
     }
     __syncthreads();
-    P_STAMP()   // pair masks
     // greedy sweep by wave 0: lane l holds the mask rows l and l + 64 in registers; the kept boxes are walked
     // with find-first-set over "not yet visited and not removed" (scalar), a kept row's mask comes by readlane
     if (tid < 64) {
@@ -439,7 +424,6 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
         }
     }
     __syncthreads();
-    P_STAMP()   // sweep
 
     // ---- direction flip + lidar -> camera, in keep (descending score) order ----
     const int nk = s_nkeep;
@@ -471,15 +455,6 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
         p.dets[(size_t)b * p.post_max + tid] = d;
         if (p.dets_host != nullptr) p.dets_host[(size_t)b * p.post_max + tid] = d;
     }
-#ifdef PP_POST_STAMPS
-    __syncthreads();
-    P_STAMP()
-    if (tid == 0 && b == 0) {
-        printf("post ncand=%d K=%d nk=%d:", ncand, K, nk);
-        for (int q = 1; q < psn; ++q) printf(" %d", (int)(pst[q] - pst[q - 1]));
-        printf("\n");
-    }
-#endif
 }
 
 void launch_postprocess(const PostParams& p, hipStream_t s) {

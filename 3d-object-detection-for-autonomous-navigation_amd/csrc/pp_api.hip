@@ -160,7 +160,7 @@ struct pp_engine {
     hipEvent_t off_ev[OFF_RING] = {nullptr, nullptr, nullptr, nullptr};
     int off_slot = 0;
     hipEvent_t ev_in = nullptr;   // orders the engine's stream behind a producer stream (pp_upload_points_device)
-    // zero-copy feed of small batches (pp_upload_points_async, batch <= PP_ZC_MAX_BATCH): one page-locked descriptor
+    // zero-copy feed of small batches (pp_upload_points_async, batch <= ZC_MAX_BATCH): one page-locked descriptor
     // per input buffer, read by k_cell_first; no copy-engine transfer, no events
     PpFeed* h_feed[2] = {nullptr, nullptr};
     const PpFeed* d_feed[2] = {nullptr, nullptr};
@@ -361,47 +361,22 @@ int upload(pp_engine* e, float** d, const std::vector<float>& h) {
     return PP_OK;
 }
 
-// Split-precision operand for the bf16 matrix pipe: every float32 weight w becomes three bfloat16
-// pieces hi + mid + lo (round-to-nearest-even each, 24 mantissa bits in total, exact for finite w),
-// laid out [cin / 16][piece][n_total][16] so that one K-chunk's tile of one piece is contiguous
-// (what k_sep_u / the deconv kernel stage into LDS).  Returned as raw 16-bit words packed in floats.
-static inline uint16_t bf16_rne(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static inline float bf16_to_f32(uint16_t h) {
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-std::vector<float> split_weights_bf16x3(const std::vector<float>& wt, int n_total, int cin) {
+// Split-precision operand for the float16 matrix pipe: every float32 weight w becomes two float16 pieces hi + mid
+// (round-to-nearest-even each), laid out [cin / 16][piece][n_total][16] so that one K-chunk's tile of one piece is
+// contiguous (what k_sep_u / the deconv kernels stage into LDS).  Returned as raw 16-bit words packed in floats.
+std::vector<float> split_weights_f16x2(const std::vector<float>& wt, int n_total, int cin) {
     std::vector<uint16_t> out((size_t)n_total * cin * PP_NPIECE);
-    const int nch = cin / 16;
     for (int n = 0; n < n_total; ++n)
         for (int c = 0; c < cin; ++c) {
             const float w = wt[(size_t)n * cin + c];
-#if PP_SPLIT_MODE == 0
-            const uint16_t hi = bf16_rne(w);
-            const float r1 = w - bf16_to_f32(hi);
-            const uint16_t mid = bf16_rne(r1);
-            const float r2 = r1 - bf16_to_f32(mid);
-            const uint16_t lo = bf16_rne(r2);
-#else   // two float16 pieces (round-to-nearest-even conversions), the third slot of the layout stays zero
             const _Float16 hf = (_Float16)w;
             const _Float16 mf = (_Float16)(w - (float)hf);
-            uint16_t hi, mid;
-            memcpy(&hi, &hf, 2);
-            memcpy(&mid, &mf, 2);
-            const uint16_t lo = 0;
-#endif
+            uint16_t pcs[PP_NPIECE];
+            memcpy(&pcs[0], &hf, 2);
+            memcpy(&pcs[1], &mf, 2);
             const int kc = c / 16, cc = c % 16;
-            const uint16_t pcs[3] = {hi, mid, lo};
             for (int p = 0; p < PP_NPIECE; ++p) out[(((size_t)kc * PP_NPIECE + p) * n_total + n) * 16 + cc] = pcs[p];
         }
-    (void)nch;
     std::vector<float> packed(out.size() / 2);
     memcpy(packed.data(), out.data(), out.size() * 2);
     return packed;
@@ -413,14 +388,9 @@ std::vector<float> split_weights_bf16x3(const std::vector<float>& wt, int n_tota
 // no guard: below 2^-3 the mid piece is a float16 subnormal, so a weight carries an ABSOLUTE error of at most 2^-25,
 // which is what bounds the error of a dot product whose other terms are O(1).
 static bool f16_pair_range_ok(const std::vector<float>& wt) {
-#if PP_SPLIT_MODE == 0
-    (void)wt;
-    return true;          // bfloat16 pieces have float32's exponent range
-#else
     for (float w : wt)
         if (!(fabsf(w) < 32768.f)) return false;      // also catches NaN / inf
     return true;
-#endif
 }
 
 // canvas -> host (debug taps).  With the sparse canvas the cells without a pillar were never written: they are
@@ -1077,7 +1047,7 @@ int pp_finalize_weights(pp_handle e) {
             int st = upload(e, &L.d_dw, *dw); if (st) return st;
             st = upload(e, &L.d_wt, wt); if (st) return st;
             L.d_wt16 = nullptr;
-            if (!e->force_f32 && L.cin % 16 == 0 && f16_pair_range_ok(wt)) { st = upload(e, &L.d_wt16, split_weights_bf16x3(wt, L.n_total, L.cin)); if (st) return st; }
+            if (!e->force_f32 && L.cin % 16 == 0 && f16_pair_range_ok(wt)) { st = upload(e, &L.d_wt16, split_weights_f16x2(wt, L.n_total, L.cin)); if (st) return st; }
             else ++e->f32_fallback_layers;
             st = upload(e, &L.d_bias, sh); if (st) return st;
             ++li;
@@ -1093,7 +1063,7 @@ int pp_finalize_weights(pp_handle e) {
             int st = upload(e, &L.d_wt, wt); if (st) return st;
             L.d_wt16 = nullptr;
             L.d_head_wt16 = nullptr;
-            if (!e->force_f32 && L.cin % 16 == 0 && f16_pair_range_ok(wt)) { st = upload(e, &L.d_wt16, split_weights_bf16x3(wt, L.n_total, L.cin)); if (st) return st; }
+            if (!e->force_f32 && L.cin % 16 == 0 && f16_pair_range_ok(wt)) { st = upload(e, &L.d_wt16, split_weights_f16x2(wt, L.n_total, L.cin)); if (st) return st; }
             else ++e->f32_fallback_layers;
             st = upload(e, &L.d_bias, sh); if (st) return st;
             if (L.head_mode != 0) {   // this branch's [PP_HEAD_COLS][cout] slice of the head matrix
@@ -1112,7 +1082,7 @@ int pp_finalize_weights(pp_handle e) {
                             const int src = n * 32 + (j & 3) + 8 * (2 * g + (j >> 2)) + 4 * hh;
                             hwp[(size_t)o * L.cout + c] = hw[(size_t)o * L.cout + src];
                         }
-                    st = upload(e, &L.d_head_wt16, split_weights_bf16x3(hwp, PP_HEAD_COLS, L.cout)); if (st) return st;
+                    st = upload(e, &L.d_head_wt16, split_weights_f16x2(hwp, PP_HEAD_COLS, L.cout)); if (st) return st;
                 }
                 st = upload(e, &L.d_head_bias, headb); if (st) return st;
             }
@@ -1173,9 +1143,8 @@ int pp_upload_points(pp_handle e, const float* points, const int32_t* frame_offs
     return PP_OK;
 }
 
-#ifndef PP_ZC_MAX_BATCH
-#define PP_ZC_MAX_BATCH 4
-#endif
+// largest batch fed zero-copy (pp_upload_points_async)
+static constexpr int ZC_MAX_BATCH = 4;
 // live pp_host_alloc blocks (base -> bytes) whose device mapping is the identity; pp_host_free removes its entry
 // BEFORE the memory goes back to the runtime, so a later lookup of a recycled address cannot hit
 static std::mutex g_pinned_mu;
@@ -1246,7 +1215,7 @@ int pp_upload_points_async(pp_handle e, const float* points_pinned, const int32_
     int st = check_batch(e, batch); if (st) return st;
     if (frame_offsets && batch >= 1 && frame_offsets[batch] > 0 && !points_pinned)
         return fail(e, PP_ERR_ARG, "pp_upload_points_async: points is NULL");
-    if (frame_offsets && batch >= 1 && batch <= PP_ZC_MAX_BATCH) {
+    if (frame_offsets && batch >= 1 && batch <= ZC_MAX_BATCH) {
         st = feed_zero_copy(e, points_pinned, frame_offsets, batch);
         if (st != PP_ERR_UNSUPPORTED) return st;      // (not device-mapped memory: the copy below still works)
     }

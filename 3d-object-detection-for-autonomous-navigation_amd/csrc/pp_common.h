@@ -14,13 +14,9 @@
 #include "../../include/pp_hip.h"
 
 #define PP_WAVE 64
-// split-precision operand pieces of the GEMM kernels (backbone.hip explains the modes); pp_api.hip splits the
-// weights accordingly.  A build-time choice: -DPP_SPLIT_MODE=n
-#ifndef PP_SPLIT_MODE
-#define PP_SPLIT_MODE 1
-#endif
-// pieces per value in the pre-split weight layouts ([cin/16][PP_NPIECE][n][16] 16-bit words)
-#define PP_NPIECE ((PP_SPLIT_MODE == 0) ? 3 : 2)
+// float16 pieces per value of the split-precision GEMM operands (backbone.hip), i.e. in the weight layouts pp_api.hip
+// writes ([cin/16][PP_NPIECE][n][16] 16-bit words)
+#define PP_NPIECE 2
 // zeroed floats in front of every activation buffer (>= the widest layer input, 384 channels):
 // the GEMM producers read convolution zero-padding from there instead of masking loaded values
 #define PP_ZPAD_FLOATS 512

@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void k_tr_gemm(TGemm g) {
 // Split-precision GEMM (round 3): the same C = A . B contract as k_tr_gemm on the 16-bit matrix pipe.  Every
 // float32 operand value is carried as THREE bfloat16 pieces (hi + mid + lo: 24 significand bits, float32's exponent
 // range -- gradients of 1e-8 and activations of 1e3 alike) and a product as the six piece products of weight
-// >= 2^-16, accumulated in float32: float32-equivalent results (the inference kernels' PP_SPLIT_MODE 0 arithmetic)
+// >= 2^-16, accumulated in float32: float32-equivalent results
 // at 6 x 32 matrix-pipe cycles per 32x32x16 block instead of 8 x 64 with v_mfma_f32_32x32x2_f32.
 //   * a 4-wave workgroup owns a (64*WM) x (64*WN) tile, wave (wm, wn) a (32*WM) x (32*WN) part of it; K in chunks
 //     of 32 through LDS, the next chunk's global loads (16 bytes per lane) in flight while the current one is

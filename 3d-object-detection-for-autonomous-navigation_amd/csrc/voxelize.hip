@@ -170,14 +170,6 @@ __global__ __launch_bounds__(VT) void k_voxel_frame(
     // and the (pillar id, point index) pairs are packed into one 32-bit word and radix-sorted in LDS. ----
     int ib = 1;
     while ((1 << ib) < n) ++ib;                 // bits of a point index
-#ifdef PP_VOX_STAMPS   // diagnostic build: phase times of frame 0 (100 MHz ticks), printed by thread 0
-    long long vst[24];
-    int vsn = 0;
-#define V_STAMP() { if (vsn < 24) vst[vsn++] = wall_clock64(); }
-#else
-#define V_STAMP() {}
-#endif
-    V_STAMP()
     if (n <= CAP && npass * bits + ib <= 32 && (first != nullptr || (TABLES && ncell <= VL_CAP))) {
         const int ppt = (n + VT - 1) / VT;      // <= PPT
         const int i0 = tid * ppt;
@@ -211,7 +203,6 @@ __global__ __launch_bounds__(VT) void k_voxel_frame(
             for (int k = 0; k < PPT; ++k) f[k] = (c[k] >= 0) ? s_first[c[k]] : -1;
             __syncthreads();   // s_sort is written below
         }
-        V_STAMP()   // 1: cells loaded, first-of-cell known
         int* const s_map = reinterpret_cast<int*>(s_sort) + VL_CAP;   // cell -> pillar id (LDS copy of fmap)
         unsigned flags = 0;
 #pragma unroll
@@ -234,7 +225,6 @@ __global__ __launch_bounds__(VT) void k_voxel_frame(
                 }
         }
         __syncthreads();                        // cell map of this frame + break point visible to the block
-        V_STAMP()   // 2: pillar ids assigned, cell map written
         const int P = min(totp, max_voxels);
         const int ibreak = s_break;
         unsigned vmask = 0;
@@ -252,7 +242,6 @@ __global__ __launch_bounds__(VT) void k_voxel_frame(
                 if ((vmask >> k) & 1u) s_sort[basev + r++] = ((unsigned)key[k] << ib) | (unsigned)(i0 + k);
         }
         __syncthreads();
-        V_STAMP()   // 3: keys fetched, compaction done
         // stable LSD radix sort of the packed words by pillar id, LDS to LDS
         // in place: a pass holds every element in registers between its read and its scatter (barriers in
         // between), so source and destination are the same buffer
@@ -278,7 +267,6 @@ __global__ __launch_bounds__(VT) void k_voxel_frame(
                 ev[t] = (j < wend) ? sk[j] : 0u;
             }
             __syncthreads();
-            V_STAMP()   // pass: elements read, histogram cleared
             // (the peer set of a lane is kept as two 32-bit words and narrowed by one xnor + and per word and digit
             // bit: m = 0 / -1 from the lane's bit, peers &= ~(ballot ^ m); inactive lanes are outside the initial
             // mask and stay outside.  Count reads and group-leader adds are relaxed workgroup-scope LDS operations
@@ -323,7 +311,6 @@ __global__ __launch_bounds__(VT) void k_voxel_frame(
 #pragma unroll
             for (int t = 0; t < PPT; ++t) rank[t] += rbase[t];
             __syncthreads();
-            V_STAMP()   // pass: in-wave ranks + digit counts
             {
                 const int E = NB * VWAVES;
                 const int per = (E + VT - 1) / VT;
@@ -343,7 +330,6 @@ __global__ __launch_bounds__(VT) void k_voxel_frame(
                     }
             }
             __syncthreads();
-            V_STAMP()   // pass: block scan of the counts
 #pragma unroll
             for (int t = 0; t < PPT; ++t) {
                 if (wbeg + t * 64 + lane < wend) {
@@ -352,7 +338,6 @@ __global__ __launch_bounds__(VT) void k_voxel_frame(
                 }
             }
             __syncthreads();
-            V_STAMP()   // 4, 5: sort passes
         }
         // sorted point indices + CSR row starts
         int* ps = pillar_start + (size_t)b * (max_voxels + 1);
@@ -376,15 +361,6 @@ __global__ __launch_bounds__(VT) void k_voxel_frame(
             npillars[b] = P;
             nvalid_out[b] = nv;
         }
-#ifdef PP_VOX_STAMPS
-        __syncthreads();
-        V_STAMP()
-        if (tid == 0 && b == 0) {
-            printf("vox n=%d nv=%d:", n, nv);
-            for (int q = 1; q < vsn; ++q) printf(" %d", (int)(vst[q] - vst[q - 1]));
-            printf("\n");
-        }
-#endif
         return;
     }
 

@@ -15,7 +15,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-ZC_MAX = 4          # PP_ZC_MAX_BATCH: larger batches take the copy feed
+ZC_MAX = 4          # ZC_MAX_BATCH (pp_api.hip): larger batches take the copy feed
 
 
 def _snapshot(eng):

@@ -641,3 +641,44 @@ def test_small_and_large_batch_kernels_agree(pp, engines):
         assert n1[0] == n64[i]
         assert np.array_equal(d1[0]["anchor_index"][:n1[0]], dets64[i]["anchor_index"][:n64[i]])
         np.testing.assert_allclose(d1[0]["score"][:n1[0]], dets64[i]["score"][:n64[i]], rtol=1e-5, atol=1e-6)
+
+
+# What launch_layer runs for each layer, as Engine.layer_tags() names it: recorded on the MI355X with the default
+# switches (cfg-A at B = 1, 2 and 64, cfg-K at B = 32).
+_TAGS_A_SMALL = [
+    "k_sep_k4<64,1>:block1.0", "k_sep_k4<64,1>:block1.1", "k_sep_k4<64,1>:block1.2", "k_sep_k4<64,1>:block1.3",
+    "k_deconv_k4<128>:deconv1", "k_sep_k4<64,2>:block2.0", "k_sep_k4<64,1>:block2.1", "k_sep_k4<64,1>:block2.2",
+    "k_sep_k4<64,1>:block2.3", "k_sep_k4<64,1>:block2.4", "k_sep_k4<64,1>:block2.5", "k_deconv_k4<128>:deconv2",
+    "k_sep_k4<64,2>:block3.0", "k_sep_k4<64,1,8>:block3.1", "k_sep_k4<64,1,8>:block3.2", "k_sep_k4<64,1,8>:block3.3",
+    "k_sep_k4<64,1,8>:block3.4", "k_sep_k4<64,1,8>:block3.5", "k_deconv_k4<128>:deconv3",
+]
+_TAGS_A64 = [
+    "k_sep_u<64,1,3,1,0>:block1.0", "k_sep_u<64,1,3,1,0>:block1.1", "k_sep_u<64,1,3,1,0>:block1.2",
+    "k_sep_u<64,1,3,1,0>:block1.3", "k_deconv_u<128,3>:deconv1", "k_sep_u<128,2,2,1,0>:block2.0",
+    "k_sep_u<128,1,2,1,0>:block2.1", "k_sep_u<128,1,2,1,0>:block2.2", "k_sep_u<128,1,2,1,0>:block2.3",
+    "k_sep_u<128,1,2,1,0>:block2.4", "k_sep_u<128,1,2,1,0>:block2.5", "k_deconv_r<128>:deconv2",
+    "k_sep_u<128,2,2,1,0>:block3.0", "k_sep_p:block3.1", "k_sep_p:block3.2", "k_sep_p:block3.3", "k_sep_p:block3.4",
+    "k_sep_p:block3.5", "k_deconv_r<256>:deconv3",
+]
+_TAGS_K32 = [
+    "k_sep_u<64,2,3,1,1>:block1.0", "k_sep_u<64,1,3,1,0>:block1.1", "k_sep_u<64,1,3,1,0>:block1.2",
+    "k_sep_u<64,1,3,1,0>:block1.3", "k_deconv_u<128,3>:deconv1", "k_sep_u<128,2,2,1,0>:block2.0",
+    "k_sep_u<128,1,2,1,0>:block2.1", "k_sep_u<128,1,2,1,0>:block2.2", "k_sep_u<128,1,2,1,0>:block2.3",
+    "k_sep_u<128,1,2,1,0>:block2.4", "k_sep_u<128,1,2,1,0>:block2.5", "k_deconv_r<128>:deconv2",
+    "k_sep_u<128,2,2,1,0>:block3.0", "k_sep_p:block3.1", "k_sep_p:block3.2", "k_sep_p:block3.3", "k_sep_p:block3.4",
+    "k_sep_p:block3.5", "k_deconv_r<256>:deconv3",
+]
+
+
+@pytest.mark.gpu
+def test_layer_tags_name_the_recorded_kernel_choice(pp, engines):
+    """The split-K kernels at one and two frames, the persistent ones (k_sep_p, k_deconv_r among them) at 64, the
+    sparse-canvas k_sep_u on cfg-K's first layer: every layer's instantiation as recorded."""
+    rect, trv, _ = pp.synth.default_calib()
+    big = engines("net-A64", pp.config.pedestrian_d435i_config(64), max_batch=64, weights_seed=7)
+    for B, want in ((1, _TAGS_A_SMALL), (2, _TAGS_A_SMALL), (64, _TAGS_A64)):
+        big.detect([pp.synth.d435i_cloud(500 + i, 4096) for i in range(B)], np.stack([rect] * B), np.stack([trv] * B))
+        assert big.layer_tags() == want, B
+    k = engines("net-K32", pp.config.kitti_shaped_config(32), max_batch=32, nmax=8192, weights_seed=7)
+    k.detect([pp.synth.kitti_cloud(i, 5000) for i in range(32)], np.stack([rect] * 32), np.stack([trv] * 32))
+    assert k.layer_tags() == _TAGS_K32
