@@ -166,11 +166,11 @@ struct pp_engine {
     const PpFeed* d_feed[2] = {nullptr, nullptr};
     bool zc = false;              // the uploaded batch is fed that way
 
-    // training step (train.hip): shapes, flat layout and device buffers, set up by the first pp_train_* call
+    // training step (train.hip): shapes, plan (the flat layout among it) and device buffers, set up by the first
+    // pp_train_* call
     struct TrainState {
         TrainShape shape;
-        std::vector<TrainEntry> layout;
-        int64_t n_params = 0, n_state = 0;
+        TrainPlan plan;
         TrainCtx cx;
         bool buffers = false;
         // the ~250 launches of a step replay as one hipGraph while nothing they depend on changes; ONE GRAPH PER INPUT
@@ -1837,7 +1837,7 @@ int train_state(pp_engine* e) {
     s.head_h = e->head_h; s.head_w = e->head_w; s.napl = e->napl; s.ncls = e->ncls; s.use_dir = e->use_dir ? 1 : 0;
     s.CC = e->CC;
     s.layers = e->layers;
-    t->layout = train_layout(s, &t->n_params, &t->n_state);
+    t->plan = train_plan(s, e->B);
     e->train = t;
     return PP_OK;
 }
@@ -1869,29 +1869,18 @@ int train_buffers(pp_engine* e) {
     };
     A1(dalloc_hdr(&cx.canvas, B * s.ny * s.nx * s.C, 0));
     A1(dalloc(e, &cx.dcanvas, B * s.ny * s.nx * s.C));
-    size_t max_z = 1, max_d = 1;
-    long pw16_words = 0;
-    cx.lbuf.assign(s.layers.size(), TrainLayerBuf{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0});
-    for (size_t i = 0; i < s.layers.size(); ++i) {
-        const LayerDesc& l = s.layers[i];
-        TrainLayerBuf& tb = cx.lbuf[i];
+    const TrainPlan& plan = t->plan;
+    cx.lbuf.assign(plan.layers.size(), TrainLayerBuf{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
+    for (size_t j = 0; j < plan.layers.size(); ++j) {
+        const LayerDesc& l = s.layers[plan.layers[j].layer];
+        TrainLayerBuf& tb = cx.lbuf[j];
         if (l.kind == LAYER_SEP) {
             const size_t rows = B * l.out_h * l.out_w;
             A1(dalloc(e, &tb.D, rows * l.cin)); A1(dalloc_hdr(&tb.Z, rows * l.cout));
-            // the activation tensor only where it is read as one: the layer in front of a transposed convolution
-            if (i + 1 < s.layers.size() && s.layers[i + 1].kind == LAYER_DECONV) A1(dalloc_hdr(&tb.A, rows * l.cout, 0));
-            tb.pw16_off = pw16_words;
-            pw16_words += (long)2 * l.cin * l.cout;
+            if (plan.layers[j].keeps_a) A1(dalloc_hdr(&tb.A, rows * l.cout, 0));
             A1(dalloc(e, &tb.dA, rows * l.cout));
-            max_z = std::max(max_z, rows * l.cout); max_d = std::max(max_d, rows * l.cin);
-        } else if (l.kind == LAYER_DECONV) {
-            const size_t n = B * l.in_h * l.in_w * l.k * l.k * l.cout;
-            A1(dalloc(e, &tb.Z, n));
-            max_z = std::max(max_z, n);
-            tb.pw16_off = pw16_words;                       // the kernel as a GEMM operand [cin][k * k * cout], two float16 pieces
-            pw16_words += (long)2 * l.cin * l.k * l.k * l.cout;
         } else {
-            continue;
+            A1(dalloc(e, &tb.Z, B * l.in_h * l.in_w * l.k * l.k * l.cout));
         }
         A1(dalloc(e, &tb.stats, (size_t)2 * l.cout)); A1(dalloc(e, &tb.sums, (size_t)2 * l.cout));
         A1(dalloc(e, &tb.coef, (size_t)l.cout));
@@ -1899,19 +1888,10 @@ int train_buffers(pp_engine* e) {
     A1(dalloc(e, &cx.cat, B * HW * s.CC)); A1(dalloc(e, &cx.dcat, B * HW * s.CC));
     A1(dalloc(e, &cx.head_w, (size_t)s.CC * PP_HEAD_COLS)); A1(dalloc(e, &cx.head_b, (size_t)PP_HEAD_COLS));
     A1(dalloc(e, &cx.dhead_w, (size_t)s.CC * PP_HEAD_COLS)); A1(dalloc(e, &cx.dhead_b, (size_t)2 * PP_HEAD_COLS));
-    A1(dalloc(e, &cx.dZ, max_z)); A1(dalloc(e, &cx.dD, max_d));
-    A1(dalloc(e, &cx.part, train_part_floats(s)));
-    {   // one [2][N] row (+ its row count) per 64-row tile of the largest forward product (per 32 rows for the fused
-        // separable launches)
-        size_t need = 1;
-        for (const LayerDesc& l : s.layers) {
-            if (l.kind == LAYER_SEP) need = std::max(need, (B * l.out_h * l.out_w + 127) / 128 * 4 * (2 * (size_t)l.cout + 1));
-            else if (l.kind == LAYER_DECONV) need = std::max(need, ((B * l.in_h * l.in_w + 63) / 64 + 8) * (2 * (size_t)l.k * l.k * l.cout + 1));
-        }
-        A1(dalloc(e, &cx.stat_part, need));
-        cx.stat_part_floats = (long)need;
-    }
-    A1(dalloc(e, &cx.pw16, (size_t)std::max<long>(pw16_words, 8)));
+    A1(dalloc(e, &cx.dZ, plan.max_z)); A1(dalloc(e, &cx.dD, plan.max_d));
+    A1(dalloc(e, &cx.part, plan.part_floats));
+    A1(dalloc(e, &cx.stat_part, (size_t)plan.stat_part_floats));
+    A1(dalloc(e, &cx.pw16, (size_t)std::max<long>(plan.pw16_words, 8)));
     A1(dalloc(e, &cx.head_w16, (size_t)2 * s.CC * PP_HEAD_COLS));
     // split-K partial tiles + the regions of the step's deferred reductions (every weight gradient keeps its
     // partials until the end of the step): 64 MB at the reference's batch, 16 MB more per frame beyond 4
@@ -1923,9 +1903,7 @@ int train_buffers(pp_engine* e) {
     A1(dalloc(e, &cx.gemm_part, (size_t)cx.gemm_part_floats));
     // PP_TRAIN_ARENA_FLOATS=n: the step uses at most n floats of it (tests: the arena-exhausted branches of train.hip).
     // Where partial rows live and how many K slices a product gets change; what is computed does not.
-    static long arena_cap = -1;
-    if (arena_cap < 0) { const char* s_ = getenv("PP_TRAIN_ARENA_FLOATS"); arena_cap = s_ ? std::max(0l, atol(s_)) : 0; }
-    if (arena_cap > 0) cx.gemm_part_floats = std::min(cx.gemm_part_floats, arena_cap);
+    if (const long cap = train_switches().arena_floats) cx.gemm_part_floats = std::min(cx.gemm_part_floats, cap);
     if (st == PP_OK) st = ensure_loss_buffers(e);
     if (st == PP_OK) t->buffers = true;
     return st;
@@ -2137,17 +2115,18 @@ int pp_head_loss(pp_handle e, const int32_t* labels, const float* reg_targets, i
 int pp_train_layout(pp_handle e, int32_t* n_entries, int64_t* n_param_floats, int64_t* n_state_floats) {
     if (!e) return PP_ERR_ARG;
     int st = train_state(e); if (st) return st;
-    if (n_entries) *n_entries = (int32_t)e->train->layout.size();
-    if (n_param_floats) *n_param_floats = e->train->n_params;
-    if (n_state_floats) *n_state_floats = e->train->n_state;
+    const TrainPlan& plan = e->train->plan;
+    if (n_entries) *n_entries = (int32_t)plan.layout.size();
+    if (n_param_floats) *n_param_floats = plan.n_params;
+    if (n_state_floats) *n_state_floats = plan.n_state;
     return PP_OK;
 }
 
 int pp_train_layout_entry(pp_handle e, int32_t i, const char** name, int64_t* offset, int64_t* size, int32_t* is_state) {
     if (!e) return PP_ERR_ARG;
     int st = train_state(e); if (st) return st;
-    if (i < 0 || i >= (int)e->train->layout.size()) return fail(e, PP_ERR_ARG, "pp_train_layout_entry: index %d out of range", i);
-    const TrainEntry& t = e->train->layout[i];
+    if (i < 0 || i >= (int)e->train->plan.layout.size()) return fail(e, PP_ERR_ARG, "pp_train_layout_entry: index %d out of range", i);
+    const TrainEntry& t = e->train->plan.layout[i];
     if (name) *name = t.name.c_str();
     if (offset) *offset = t.offset;
     if (size) *size = t.size;
@@ -2198,7 +2177,7 @@ int train_step_launch(pp_engine* e, const float* params_dev, float* grads_dev, f
             int r = run_voxelize(e, batch, max_n);
             if (r) return r;
         }
-        return train_step(cx, t->shape, t->layout, params_dev, grads_dev, state_dev, batch, lp, phase);
+        return train_step(cx, t->shape, t->plan, params_dev, grads_dev, state_dev, batch, lp, phase);
     };
     bool launched = false;
     if (e->prof <= 0 && t->graph_state == 0 && graphs_enabled()) {
@@ -2485,26 +2464,22 @@ int pp_train_fetch_decisions(pp_handle e, int32_t layer, uint8_t* relu_mask, int
         HIPCHK(e, hipMemcpy(relu_mask, t->cx.pfn_arg, (size_t)n * 4, hipMemcpyDeviceToHost));
         return PP_OK;
     }
-    int k = -1;
-    for (size_t i = 0; i < t->shape.layers.size(); ++i) {
-        const LayerDesc& l = t->shape.layers[i];
-        if (l.kind != LAYER_SEP && l.kind != LAYER_DECONV) continue;
-        if (++k != layer) continue;
-        const int64_t n = (l.kind == LAYER_SEP) ? (int64_t)B * l.out_h * l.out_w * l.cout
-                                                : (int64_t)B * l.in_h * l.in_w * l.k * l.k * l.cout;
-        *count = n;
-        if (!relu_mask) return PP_OK;
-        if (capacity < n) return fail(e, PP_ERR_ARG, "pp_train_fetch_decisions: %lld bytes needed", (long long)n);
-        unsigned char* d = nullptr;
-        HIPCHK(e, hipMalloc(&d, (size_t)n));
-        launch_relu_mask(t->cx.lbuf[i].Z, t->cx.lbuf[i].coef, (long)n, l.cout, d, e->stream);
-        hipError_t he = hipStreamSynchronize(e->stream);
-        if (he == hipSuccess) he = hipMemcpy(relu_mask, d, (size_t)n, hipMemcpyDeviceToHost);
-        (void)hipFree(d);
-        if (he != hipSuccess) return fail(e, PP_ERR_HIP, "pp_train_fetch_decisions: %s", hipGetErrorString(he));
-        return PP_OK;
-    }
-    return fail(e, PP_ERR_ARG, "pp_train_fetch_decisions: layer %d out of range", layer);
+    if (layer >= (int)t->plan.layers.size())
+        return fail(e, PP_ERR_ARG, "pp_train_fetch_decisions: layer %d out of range", layer);
+    const LayerDesc& l = t->shape.layers[t->plan.layers[layer].layer];
+    const int64_t n = (l.kind == LAYER_SEP) ? (int64_t)B * l.out_h * l.out_w * l.cout
+                                            : (int64_t)B * l.in_h * l.in_w * l.k * l.k * l.cout;
+    *count = n;
+    if (!relu_mask) return PP_OK;
+    if (capacity < n) return fail(e, PP_ERR_ARG, "pp_train_fetch_decisions: %lld bytes needed", (long long)n);
+    unsigned char* d = nullptr;
+    HIPCHK(e, hipMalloc(&d, (size_t)n));
+    launch_relu_mask(t->cx.lbuf[layer].Z, t->cx.lbuf[layer].coef, (long)n, l.cout, d, e->stream);
+    hipError_t he = hipStreamSynchronize(e->stream);
+    if (he == hipSuccess) he = hipMemcpy(relu_mask, d, (size_t)n, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (he != hipSuccess) return fail(e, PP_ERR_HIP, "pp_train_fetch_decisions: %s", hipGetErrorString(he));
+    return PP_OK;
 }
 
 int pp_train_graph_stats(pp_handle e, int32_t* captures, int32_t* replays) {

@@ -20,17 +20,62 @@ struct TrainShape {
     std::vector<LayerDesc> layers;   // the engine's layer table (shapes only are read)
 };
 
-struct TrainLayerBuf {
+// One trainable layer of the plan (train_plan): the separable layers and transposed convolutions in table order -- the
+// numbering of pp_train_fetch_decisions.  Tensor offsets are floats into the params / grads buffers (moving statistics:
+// the state buffer), resolved once from the layout.
+struct TrainLayer {
+    int kind;                 // LAYER_SEP or LAYER_DECONV
+    int block, index;         // block (0-based) and index in the block (separable layers)
+    int layer;                // index in TrainShape::layers
+    int64_t dw, pw;           // depthwise and pointwise kernels (transposed convolution: pw = its kernel; dw unused)
+    int64_t gamma, beta, mean, var;
+    int src;                  // the layer whose output this one reads (-1: the canvas); its input gradient goes to that
+                              // layer's dA (the canvas's: dcanvas)
+    bool src_z;               // src's output is its pre-BatchNorm map Z read through its coef table (src keeps no A)
+    bool keeps_a;             // the activation A is a tensor (the layer in front of a transposed convolution)
+    bool accumulate;          // transposed convolution: its input gradient is added to src's dA (the next block's first
+                              // layer wrote it first)
+    int cat_off;              // transposed convolution: its channels in the concatenation
+    long pw16_off;            // offset (16-bit words) of its split forward kernel in TrainCtx::pw16
+    std::string fused_tag, fwd_tag, pair_tag;   // profiler names: k_sep_u_tr:block1.0, k_tr_gemm2:fwd.block1.0, ...
+};
+
+// Built once per handle from the shape and the engine's maximum batch: the layout, the layers, and the buffer sizes
+// the step's rules need.  `unsupported`: the step refuses the configuration (pp_train_layout still works).
+struct TrainPlan {
+    std::vector<TrainEntry> layout;
+    int64_t n_params = 0, n_state = 0;
+    std::vector<TrainLayer> layers;
+    int64_t pfn_w = 0, pfn_gamma = 0, pfn_beta = 0, pfn_mean = 0, pfn_var = 0;
+    int64_t box_k = 0, box_b = 0, cls_k = 0, cls_b = 0, dir_k = 0, dir_b = 0;   // without a direction head: dir = box
+    bool unsupported = false;
+    bool fused = false;       // the fused forward kernels are available (the split-weight table holds every layer)
+    long pw16_words = 0;
+    size_t max_z = 1, max_d = 1, part_floats = 0;
+    long stat_part_floats = 1;
+    // a fused or product forward of `rows` x `n` leaves its statistics partials in TrainCtx::stat_part
+    bool stat_room(long rows, long n) const { return ((rows + 127) / 128 + 8) * (2 * n + 1) <= stat_part_floats; }
+};
+
+struct TrainLayerBuf {   // per plan layer
     float* D;       // depthwise output [rows][cin] (separable layers)
     float* Z;       // pre-BatchNorm GEMM output [rows][cout] / [pixels][k*k*cout]
-    float* A;       // activation [rows][cout]: block-final separable layers only (the transposed convolution and the next
-                    // block read it as a tensor; in-block readers evaluate relu(bn(Z)) from Z and coef); NULL otherwise
+    float* A;       // activation [rows][cout] where TrainLayer::keeps_a (in-block readers evaluate relu(bn(Z)) from Z and
+                    // coef); NULL otherwise
     float* dA;      // gradient of A (separable layers)
     float* stats;   // [cout][2] batch mean, 1/sqrt(var + eps)
     float* sums;    // [2][cout] scratch of the reductions
     float4* coef;   // [cout] (sc, sh, inv, -mean * inv): act = z * sc + sh, zhat = z * inv + nmi (k_tr_bn_finalize)
-    long pw16_off;  // separable layers: offset (16-bit words) of the layer's split pointwise kernel in TrainCtx::pw16
 };
+
+// The PP_TRAIN_* switches, read from the environment once per process.
+struct TrainSwitches {
+    long fused_min;           // PP_TRAIN_FUSED_MIN: fused separable forward from this many output pixels on
+    bool split_gemm;          // PP_TRAIN_GEMM=f32 clears it: every product on k_tr_gemm
+    long fin256, fin64;       // PP_TRAIN_FIN_THR=a,b: BatchNorm finalize widths
+    long arena_floats;        // PP_TRAIN_ARENA_FLOATS: cap of the split-K / deferred-reduction arena (0: none)
+};
+const TrainSwitches& train_switches();
 
 struct TrainCtx {
     hipStream_t stream;
@@ -52,7 +97,7 @@ struct TrainCtx {
     float* canvas;       // [B][ny][nx][C]
     float* dcanvas;
     // RPN
-    std::vector<TrainLayerBuf> lbuf;
+    std::vector<TrainLayerBuf> lbuf;   // per TrainPlan::layers entry
     float* cat;          // [B * H' * W'][CC]
     float* dcat;
     float* head;         // [B * H' * W'][32] (the loss kernel's layout)
@@ -65,21 +110,20 @@ struct TrainCtx {
     float* dD;           // scratch [max rows * cin]
     float* part;         // partial sums of the persistent reductions
     float* stat_part;    // BatchNorm statistics partials of the forward products: [row tiles][2][GEMM columns]
+                         // (TrainPlan::stat_part_floats)
     float* gemm_part;    // split-K partial tiles
     long gemm_part_floats;
     // fused training forward of the separable layers (k_sep_u<..., TR = 1>): every pointwise kernel of the step as two
-    // float16 pieces, [cin / 16][2][cout][16] per layer (k_tr_split_pw, once per step); NULL: not available.  The
-    // maps those launches read (canvas, Z of in-block layers, A of block-final ones) carry a NaN header in front.
+    // float16 pieces, [cin / 16][2][cout][16] per layer (k_tr_split_pw, once per step).  The maps those launches read
+    // (canvas, Z of in-block layers, A of block-final ones) carry a NaN header in front.
     unsigned short* pw16;
     unsigned short* head_w16;   // the packed head matrix [CC][32] in the same form
-    long stat_part_floats;
 };
 
-std::vector<TrainEntry> train_layout(const TrainShape& s, int64_t* n_params, int64_t* n_state);
-size_t train_part_floats(const TrainShape& s);
+TrainPlan train_plan(const TrainShape& s, int max_batch);
 // forward (training mode) + loss + backward for `batch` resident, voxelised frames; grads overwritten, state updated
-int train_step(const TrainCtx& cx, const TrainShape& s, const std::vector<TrainEntry>& layout, const float* params,
-               float* grads, float* state, int batch, const LossParams& loss, int phase = 3);
+int train_step(const TrainCtx& cx, const TrainShape& s, const TrainPlan& plan, const float* params, float* grads,
+               float* state, int batch, const LossParams& loss, int phase = 3);
 
 // parity tap (pp_train_fetch_decisions): mask[i] = 1 where the backward pass lets the gradient through element i of
 // Z[n] ([rows][C]; the test the BatchNorm-backward kernels make: fmaf(z, sc, sh) > 0)

@@ -10,7 +10,7 @@
 // and the tf.GradientTape gradient of `loss` with respect to net.trainable_variables (train.py:265-304).
 //
 // Layout: float32 NHWC activations, one [rows][channels] matrix per tensor; the parameters live in ONE flat
-// device buffer owned by the caller (order: train_layout()), gradients go to a second flat buffer of the same
+// device buffer owned by the caller (order: train_plan()), gradients go to a second flat buffer of the same
 // order -- what the AdamW kernel (optim.hip) and the data-parallel all-reduce consume.
 //   * the 1x1 convolutions, the transposed convolutions (kernel == stride: a GEMM per input pixel) and the heads
 //     run as products on the 16-bit matrix pipe with float32-equivalent results (k_tr_gemm2: three bfloat16 pieces
@@ -29,6 +29,7 @@
 // BatchNorm feeds the unbiased variance, the PFN's rank-3 BatchNorm the biased one).  The PFN statistics run
 // over ALL P * T rows of the reference's padded tensor: the zero rows contribute nothing to the sums but count
 // in N, and a padded row that wins the max receives the gradient (it only reaches beta / gamma / the statistics).
+#include <assert.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -45,10 +46,8 @@ typedef float tf32x16 __attribute__((ext_vector_type(16)));
 #define TR_EPS 1e-3f
 // workgroups of the persistent reduction kernels (= rows of their partial-sum buffers): one per CU for the reference's
 // 2-frame batches (every launch is a few microseconds: more workgroups only add dispatch time), up to TR_NPART_MAX
-// for large per-GPU batches, where 256 workgroups leave the chip a quarter full.  Chosen per step by train_step.
+// for large per-GPU batches, where 256 workgroups leave the chip a quarter full.  Chosen per step by plan_step.
 #define TR_NPART_MAX 2048
-static thread_local int g_tr_npart = 256;   // (per-step scratch state is thread-local: distinct handles may step on distinct threads)
-#define TR_NPART g_tr_npart
 
 // ------------------------------------------------------------------------------------------------------------
 // float32 MFMA GEMM:  C[M][N] (+)= A(m,k) * B(k,n) [+ bias(n)],  A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn]
@@ -549,8 +548,19 @@ struct TMulti {
     int block_start[TR_MULTI_MAX + 1];
     int njobs;
 };
-static thread_local std::vector<ReduceJob> g_jobs;     // this step's deferred reductions (train_step resets it)
-static thread_local long g_arena_used = 0;             // floats of cx.gemm_part handed out to them
+
+// One call of train_step: what its launches share.  Nothing of it outlives the call.
+struct TrainStepState {
+    const TrainCtx& cx;
+    const TrainPlan& plan;
+    const float* params; float* grads; float* state;
+    int npart;                        // partial rows of the persistent reductions (plan_step)
+    std::vector<ReduceJob> jobs;      // deferred reductions
+    long arena_used = 0;              // floats of cx.gemm_part handed out to them
+    const float* p(int64_t off) const { return params + off; }
+    float* g(int64_t off) const { return grads + off; }
+    float* s(int64_t off) const { return state + off; }
+};
 
 __global__ __launch_bounds__(256) void k_tr_reduce_multi(TMulti m) {
     __shared__ float ssum[4][64];
@@ -579,52 +589,48 @@ __global__ __launch_bounds__(256) void k_tr_reduce_multi(TMulti m) {
     reduce_store(s, i, J.out, J.ldo, J.ncols, J.accumulate, J.scale);
 }
 
-static void flush_deferred(const TrainCtx& cx) {
+static void flush_deferred(TrainStepState& st) {
     size_t done = 0;
-    while (done < g_jobs.size()) {
+    while (done < st.jobs.size()) {
         TMulti m;
         m.njobs = 0;
         int blocks = 0;
-        while (done < g_jobs.size() && m.njobs < TR_MULTI_MAX) {
-            m.job[m.njobs] = g_jobs[done++];
+        while (done < st.jobs.size() && m.njobs < TR_MULTI_MAX) {
+            m.job[m.njobs] = st.jobs[done++];
             m.block_start[m.njobs] = blocks;
             blocks += (int)((m.job[m.njobs].n + 63) / 64);
             ++m.njobs;
         }
         m.block_start[m.njobs] = blocks;
         for (int k = m.njobs + 1; k <= TR_MULTI_MAX; ++k) m.block_start[k] = blocks;
-        PP_LAUNCH("k_tr_reduce_multi", k_tr_reduce_multi, dim3((unsigned)blocks), dim3(256), 0, cx.stream, m);
+        PP_LAUNCH("k_tr_reduce_multi", k_tr_reduce_multi, dim3((unsigned)blocks), dim3(256), 0, st.cx.stream, m);
     }
-    g_jobs.clear();
+    st.jobs.clear();
 }
 
-// PP_TRAIN_GEMM=f32 keeps every product on the float32 matrix instruction (k_tr_gemm)
-static bool train_split_gemm() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("PP_TRAIN_GEMM"); v = (e && e[0] == 'f') ? 0 : 1; }
-    return v == 1;
-}
-
-// profiler name of the next product launches ("k_tr_gemm2:<what>"; the profiler keeps the pointer: interned strings)
-static thread_local const char* g_gemm_tag = "k_tr_gemm2";
-static void gemm_tag(const std::string& what) {
-    static thread_local std::vector<std::string*> pool;
-    for (std::string* p : pool) if (*p == what) { g_gemm_tag = p->c_str(); return; }
-    pool.push_back(new std::string(what));
-    g_gemm_tag = pool.back()->c_str();
+const TrainSwitches& train_switches() {
+    static const TrainSwitches sw = [] {
+        TrainSwitches v{32768, true, 128, 32, 0};
+        if (const char* e = getenv("PP_TRAIN_FUSED_MIN")) v.fused_min = atol(e);
+        if (const char* e = getenv("PP_TRAIN_GEMM")) v.split_gemm = e[0] != 'f';
+        if (const char* e = getenv("PP_TRAIN_FIN_THR")) {
+            long a = 0, b = 0;
+            if (sscanf(e, "%ld,%ld", &a, &b) == 2 && a > 0 && b > 0) { v.fin256 = a; v.fin64 = b; }
+        }
+        if (const char* e = getenv("PP_TRAIN_ARENA_FLOATS")) v.arena_floats = std::max(0l, atol(e));
+        return v;
+    }();
+    return sw;
 }
 
 // 64 x 64 tiles (WM = WN = 1)
 template <int KCH>
-static void launch_gemm2(const TGemm2& a2, bool akc, bool bkc, dim3 grid, hipStream_t s) {
-    if (akc && bkc) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2<1, 1, true, true, KCH>), grid, dim3(256), 0, s, a2);
-    else if (akc) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2<1, 1, true, false, KCH>), grid, dim3(256), 0, s, a2);
-    else if (bkc) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2<1, 1, false, true, KCH>), grid, dim3(256), 0, s, a2);
-    else PP_LAUNCH(g_gemm_tag, (k_tr_gemm2<1, 1, false, false, KCH>), grid, dim3(256), 0, s, a2);
+static void launch_gemm2(const char* tag, const TGemm2& a2, bool akc, bool bkc, dim3 grid, hipStream_t s) {
+    if (akc && bkc) PP_LAUNCH(tag, (k_tr_gemm2<1, 1, true, true, KCH>), grid, dim3(256), 0, s, a2);
+    else if (akc) PP_LAUNCH(tag, (k_tr_gemm2<1, 1, true, false, KCH>), grid, dim3(256), 0, s, a2);
+    else if (bkc) PP_LAUNCH(tag, (k_tr_gemm2<1, 1, false, true, KCH>), grid, dim3(256), 0, s, a2);
+    else PP_LAUNCH(tag, (k_tr_gemm2<1, 1, false, false, KCH>), grid, dim3(256), 0, s, a2);
 }
-
-// rows of the statistics partials a forward product leaves ([tiles][2][N]; 0: the split kernel did not run)
-static thread_local int g_last_stat_tiles = 0;
 
 // a launch with fewer workgroups than this lives on memory latency, not on throughput: 64-wide K chunks (half the
 // dependent load -> LDS -> MFMA rounds), and the two gradient products of a layer share one launch
@@ -634,6 +640,7 @@ static constexpr long TR_LATENCY_WGS = 512;
 // defer: a split-K product whose result only the optimizer reads (weight gradients) keeps its partial tiles in a
 // region of its own and is reduced by the step's one deferred-reduction launch
 struct GemmCall {
+    const char* tag;     // profiler name of a k_tr_gemm2 launch ("k_tr_gemm2:<what>")
     const float* A; long sam, sak;
     const float* B; long sbk, sbn;
     float* C; long ldc;
@@ -649,36 +656,38 @@ static bool gemm2_eligible(const GemmCall& c) {
     const bool akc = c.sak == 1, bkc = c.sbk == 1;
     const bool a_ok = akc ? (c.sam % 4 == 0) : (c.sam == 1 && c.sak % 4 == 0 && c.M % 4 == 0);
     const bool b_ok = bkc ? (c.sbn % 4 == 0) : (c.sbn == 1 && c.sbk % 4 == 0 && c.N % 4 == 0);
-    return train_split_gemm() && a_ok && b_ok && c.K % 4 == 0 && ((uintptr_t)c.A % 16 == 0) && ((uintptr_t)c.B % 16 == 0);
+    return train_switches().split_gemm && a_ok && b_ok && c.K % 4 == 0 && ((uintptr_t)c.A % 16 == 0) && ((uintptr_t)c.B % 16 == 0);
 }
 
-static TGemm gemm_args(const TrainCtx& cx, const GemmCall& c, int& ksplit) {
+// partial tiles at arena offset `at` (the free tail, behind the regions of this step's deferred reductions)
+static TGemm gemm_args(const TrainStepState& st, const GemmCall& c, long at, int& ksplit) {
     TGemm g;
     g.A = c.A; g.sam = c.sam; g.sak = c.sak; g.B = c.B; g.sbk = c.sbk; g.sbn = c.sbn; g.C = c.C; g.ldc = c.ldc;
     g.M = c.M; g.N = c.N; g.K = c.K; g.bias = c.bias; g.accumulate = c.accumulate;
     ksplit = std::max(1, c.ksplit);
-    // partial tiles go to the free tail of the arena (behind the regions of this step's deferred reductions)
-    const long avail = cx.gemm_part_floats - g_arena_used;
+    const long avail = st.cx.gemm_part_floats - at;
     while (ksplit > 1 && (long)ksplit * c.M * c.N > avail) --ksplit;
-    g.Cpart = cx.gemm_part + g_arena_used;
+    g.Cpart = st.cx.gemm_part + at;
     g.kper = c.K;
     return g;
 }
 
-static void gemm_finish_split(const TrainCtx& cx, const GemmCall& c, const TGemm& g, int ks) {
+static void gemm_finish_split(TrainStepState& st, const GemmCall& c, const TGemm& g, int ks) {
     const long n = (long)c.M * c.N;
     if (c.defer) {
-        g_jobs.push_back(ReduceJob{g.Cpart, c.C, n, n, c.ldc, ks, c.N, c.accumulate, 1.0f});
-        g_arena_used += ((long)ks * n + 63) / 64 * 64;
+        st.jobs.push_back(ReduceJob{g.Cpart, c.C, n, n, c.ldc, ks, c.N, c.accumulate, 1.0f});
+        st.arena_used += ((long)ks * n + 63) / 64 * 64;
     } else {
-        tr_reduce(cx.stream, (const float*)g.Cpart, ks, n, n, c.C, c.ldc, c.N, c.accumulate, 1.0f);
+        tr_reduce(st.cx.stream, (const float*)g.Cpart, ks, n, n, c.C, c.ldc, c.N, c.accumulate, 1.0f);
     }
 }
 
-static void tr_gemm(const TrainCtx& cx, const GemmCall& c) {
+// returns the rows of the statistics partials the product left in cx.stat_part ([tiles][2][N]; 0: none)
+static int tr_gemm(TrainStepState& st, const GemmCall& c) {
+    const TrainCtx& cx = st.cx;
     int ksplit;
-    TGemm g = gemm_args(cx, c, ksplit);
-    g_last_stat_tiles = 0;
+    TGemm g = gemm_args(st, c, st.arena_used, ksplit);
+    int stat_tiles = 0;
     const int M = c.M, N = c.N, K = c.K;
     if (gemm2_eligible(c)) {
         const bool akc = c.sak == 1, bkc = c.sbk == 1;
@@ -694,37 +703,32 @@ static void tr_gemm(const TrainCtx& cx, const GemmCall& c) {
         // sharing their fragments, by the workgroups a launch must still have for the larger tile; products of a B=32
         // step: 128 -> 2.32 ms, 256 -> 2.22, 512 -> 2.16, 1024 -> 2.13, 2048 -> 2.05, 4096 -> 2.01, never -> 2.00)
         dim3 grid((N + 63) / 64, (M + 63) / 64, ksplit);
-        if (a2.stat_part) g_last_stat_tiles = (int)grid.y;
-        if (wide) launch_gemm2<64>(a2, akc, bkc, grid, cx.stream);
-        else launch_gemm2<32>(a2, akc, bkc, grid, cx.stream);
-        if (ksplit > 1) gemm_finish_split(cx, c, g, ksplit);
-        return;
+        if (a2.stat_part) stat_tiles = (int)grid.y;
+        if (wide) launch_gemm2<64>(c.tag, a2, akc, bkc, grid, cx.stream);
+        else launch_gemm2<32>(c.tag, a2, akc, bkc, grid, cx.stream);
+        if (ksplit > 1) gemm_finish_split(st, c, g, ksplit);
+        return stat_tiles;
     }
     int kper = ((K + ksplit - 1) / ksplit + 15) / 16 * 16;
     ksplit = (K + kper - 1) / kper;
     g.kper = kper;
     dim3 grid((N + 63) / 64, (M + 63) / 64, ksplit);
     PP_LAUNCH("k_tr_gemm", k_tr_gemm, grid, dim3(256), 0, cx.stream, g);
-    if (ksplit > 1) gemm_finish_split(cx, c, g, ksplit);
-}
-
-static void tr_gemm(const TrainCtx& cx, const float* A, long sam, long sak, const float* B, long sbk, long sbn, float* C,
-                    long ldc, int M, int N, int K, const float* bias, int accumulate, int ksplit, float* stat_part = nullptr,
-                    bool defer = false) {
-    tr_gemm(cx, GemmCall{A, sam, sak, B, sbk, sbn, C, ldc, M, N, K, bias, accumulate, ksplit, stat_part, defer});
+    if (ksplit > 1) gemm_finish_split(st, c, g, ksplit);
+    return stat_tiles;
 }
 
 // The weight-gradient product (w: TN form, split-K, deferred reduction) and the input-gradient product (d) of one
 // layer.  When both fit the split kernel's forms they go out as ONE launch (k_tr_gemm2_pair); otherwise one by one.
-static void tr_gemm_pair(const TrainCtx& cx, const GemmCall& w, const GemmCall& d) {
+static void tr_gemm_pair(TrainStepState& st, const GemmCall& w, const GemmCall& d) {
     const bool forms = w.sak != 1 && w.sbk != 1 && d.sak == 1;
     if (forms && gemm2_eligible(w) && gemm2_eligible(d) && w.defer && w.stat_part == nullptr && d.stat_part == nullptr) {
         // 64-wide chunks while the launch lives on latency, the 32-wide ones (five workgroups per CU) beyond: two
         // half-filled launches of a large batch -- block3's 640 + 640 workgroups at B=32 -- fill the chip together
         int ks1, ks2, kper1, kper2, n1, n2;
-        TGemm g1 = gemm_args(cx, w, ks1);
+        TGemm g1 = gemm_args(st, w, st.arena_used, ks1);
         int ksd;
-        (void)gemm_args(cx, d, ksd);
+        (void)gemm_args(st, d, st.arena_used, ksd);
         const auto tiles = [](const GemmCall& c) { return (long)((c.M + 63) / 64) * ((c.N + 63) / 64); };
         const bool wide = tiles(w) * ks1 + tiles(d) * ksd < 2 * TR_LATENCY_WGS;
         const int kround = wide ? 64 : 32;
@@ -736,35 +740,32 @@ static void tr_gemm_pair(const TrainCtx& cx, const GemmCall& w, const GemmCall& 
         const long wg1 = plan(w, ks1, kper1, n1);
         // (the second product's partial tiles, if it is split, lie behind the first one's region)
         const long region1 = (n1 > 1) ? ((long)n1 * w.M * w.N + 63) / 64 * 64 : 0;
-        const long saved = g_arena_used;
-        g_arena_used += region1;
-        TGemm g2 = gemm_args(cx, d, ks2);
-        g_arena_used = saved;
+        TGemm g2 = gemm_args(st, d, st.arena_used + region1, ks2);
         const long wg2 = plan(d, ks2, kper2, n2);
         g1.kper = kper1; g2.kper = kper2;
         TGemm2 p1{g1, nullptr, (w.N + 63) / 64, (w.M + 63) / 64, n1};
         TGemm2 p2{g2, nullptr, (d.N + 63) / 64, (d.M + 63) / 64, n2};
-        g_last_stat_tiles = 0;
         const dim3 grid((unsigned)(wg1 + wg2));
-        if (d.sbk == 1 && wide) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2_pair<true, 64>), grid, dim3(256), 0, cx.stream, p1, p2);
-        else if (d.sbk == 1) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2_pair<true, 32>), grid, dim3(256), 0, cx.stream, p1, p2);
-        else if (wide) PP_LAUNCH(g_gemm_tag, (k_tr_gemm2_pair<false, 64>), grid, dim3(256), 0, cx.stream, p1, p2);
-        else PP_LAUNCH(g_gemm_tag, (k_tr_gemm2_pair<false, 32>), grid, dim3(256), 0, cx.stream, p1, p2);
-        if (n1 > 1) gemm_finish_split(cx, w, g1, n1);                 // deferred: its region is now taken
-        if (n2 > 1) gemm_finish_split(cx, d, g2, n2);                 // reduced at once (from behind that region)
+        const hipStream_t s = st.cx.stream;
+        if (d.sbk == 1 && wide) PP_LAUNCH(w.tag, (k_tr_gemm2_pair<true, 64>), grid, dim3(256), 0, s, p1, p2);
+        else if (d.sbk == 1) PP_LAUNCH(w.tag, (k_tr_gemm2_pair<true, 32>), grid, dim3(256), 0, s, p1, p2);
+        else if (wide) PP_LAUNCH(w.tag, (k_tr_gemm2_pair<false, 64>), grid, dim3(256), 0, s, p1, p2);
+        else PP_LAUNCH(w.tag, (k_tr_gemm2_pair<false, 32>), grid, dim3(256), 0, s, p1, p2);
+        if (n1 > 1) gemm_finish_split(st, w, g1, n1);                 // deferred: its region is now taken
+        if (n2 > 1) gemm_finish_split(st, d, g2, n2);                 // reduced at once (from behind that region)
         return;
     }
-    tr_gemm(cx, w);
-    tr_gemm(cx, d);
+    tr_gemm(st, w);
+    tr_gemm(st, d);
 }
 
 // weight gradients: K = rows (pixels); enough slices to fill the chip, bounded by the partial buffer
-static int wgrad_split(const TrainCtx& cx, int M, int N, int K) {
+static int wgrad_split(const TrainStepState& st, int M, int N, int K) {
     const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64);
     const long wgs = 1024;     // workgroups a weight-gradient product is cut into
     long want = std::max<long>(1, wgs / tiles);
     want = std::min<long>(want, (K + 255) / 256);
-    while (want > 1 && want * (long)M * N > cx.gemm_part_floats) --want;
+    while (want > 1 && want * (long)M * N > st.cx.gemm_part_floats) --want;
     return (int)want;
 }
 
@@ -2059,128 +2060,215 @@ __global__ __launch_bounds__(256) void k_tr_split_pw(unsigned short* __restrict_
 // ------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------
-std::vector<TrainEntry> train_layout(const TrainShape& s, int64_t* n_params, int64_t* n_state) {
-    std::vector<TrainEntry> v;
-    int64_t po = 0, so = 0;
-    auto P = [&](const std::string& name, int64_t size) { v.push_back({name, po, size, 0}); po += size; };
-    auto S = [&](const std::string& name, int64_t size) { v.push_back({name, so, size, 1}); so += size; };
-    auto BN = [&](const std::string& pre, int c) {
-        P(pre + "/gamma", c); P(pre + "/beta", c);
-        S(pre + "/moving_mean", c); S(pre + "/moving_variance", c);
+// "block2/3" or "deconv2": the layout's tensor names join a layer's block and index with '/' ("rpn/block2/3/..."), the
+// profiler names with '.' ("k_tr_gemm2:fwd.block2.3")
+static std::string layer_name(int kind, int block, int index, char sep) {
+    return kind == LAYER_SEP ? "block" + std::to_string(block + 1) + sep + std::to_string(index)
+                             : "deconv" + std::to_string(block + 1);
+}
+
+TrainPlan train_plan(const TrainShape& s, int max_batch) {
+    TrainPlan pl;
+    int64_t& po = pl.n_params;
+    int64_t& so = pl.n_state;
+    auto P = [&](const std::string& name, int64_t size) { pl.layout.push_back({name, po, size, 0}); po += size; return po - size; };
+    auto S = [&](const std::string& name, int64_t size) { pl.layout.push_back({name, so, size, 1}); so += size; return so - size; };
+    auto BN = [&](const std::string& pre, int c, int64_t& gamma, int64_t& beta, int64_t& mean, int64_t& var) {
+        gamma = P(pre + "/gamma", c); beta = P(pre + "/beta", c);
+        mean = S(pre + "/moving_mean", c); var = S(pre + "/moving_variance", c);
     };
-    P("pfn/dense/kernel", (int64_t)s.FA * s.C);
-    BN("pfn/bn", s.C);
-    int bi = 0, li = 0;
-    for (const LayerDesc& L : s.layers) {
-        if (L.kind == LAYER_SEP) {
-            const std::string pre = "rpn/block" + std::to_string(bi + 1) + "/" + std::to_string(li);
-            P(pre + "/depthwise_kernel", (int64_t)9 * L.cin);
-            P(pre + "/pointwise_kernel", (int64_t)L.cin * L.cout);
-            BN(pre + "/bn", L.cout);
-            ++li;
-        } else if (L.kind == LAYER_DECONV) {
-            const std::string pre = "rpn/deconv" + std::to_string(bi + 1);
-            P(pre + "/kernel", (int64_t)L.k * L.k * L.cout * L.cin);
-            BN(pre + "/bn", L.cout);
-            ++bi; li = 0;
+    pl.pfn_w = P("pfn/dense/kernel", (int64_t)s.FA * s.C);
+    BN("pfn/bn", s.C, pl.pfn_gamma, pl.pfn_beta, pl.pfn_mean, pl.pfn_var);
+    // shapes the training kernels are written for (the reduction kernels: channel counts)
+    pl.unsupported = s.C > 256 || s.C % 4 != 0 || s.FA > 10;
+    size_t m = (size_t)2 * 512;      // floats of a row of TrainCtx::part
+    m = std::max(m, (size_t)10 * s.C);
+    const size_t B = (size_t)max_batch;
+    int block = 0, index = 0, cat_off = 0, last_sep = -1;
+    for (size_t i = 0; i < s.layers.size(); ++i) {
+        const LayerDesc& l = s.layers[i];
+        m = std::max(m, (size_t)11 * std::max(l.cin, l.cout));
+        if (l.kind == LAYER_HEAD) continue;
+        if (l.cin % 16 != 0 || l.cout < 32 || l.cout > 256 || (l.cout & (l.cout - 1)) != 0 || l.cin > 256 ||
+            (l.kind == LAYER_SEP && l.stride != 1 && l.stride != 2))
+            pl.unsupported = true;
+        TrainLayer q{};
+        q.kind = l.kind; q.block = block; q.index = index; q.layer = (int)i;
+        const std::string pre = "rpn/" + layer_name(l.kind, block, index, '/'), tag = layer_name(l.kind, block, index, '.');
+        q.fused_tag = "k_sep_u_tr:" + tag; q.fwd_tag = "k_tr_gemm2:fwd." + tag; q.pair_tag = "k_tr_gemm2:pair." + tag;
+        // every layer reads the last separable layer's output: its activation tensor, or its pre-BatchNorm map
+        q.src = last_sep;
+        q.src_z = last_sep >= 0 && !pl.layers[last_sep].keeps_a;
+        q.pw16_off = pl.pw16_words;
+        if (l.kind == LAYER_SEP) {
+            q.dw = P(pre + "/depthwise_kernel", (int64_t)9 * l.cin);
+            q.pw = P(pre + "/pointwise_kernel", (int64_t)l.cin * l.cout);
+            // the activation tensor only where it is read as one: the layer in front of a transposed convolution
+            q.keeps_a = i + 1 < s.layers.size() && s.layers[i + 1].kind == LAYER_DECONV;
+            // the depthwise backward reads its input as a tensor unless it runs in one pass (stride 1)
+            if (q.src_z && l.stride != 1) pl.unsupported = true;
+            const size_t rows = B * l.out_h * l.out_w;
+            pl.pw16_words += (long)2 * l.cin * l.cout;
+            pl.max_z = std::max(pl.max_z, rows * l.cout);
+            pl.max_d = std::max(pl.max_d, rows * l.cin);
+            // one [2][N] row (+ its row count) per 32 rows of the fused launches
+            pl.stat_part_floats = std::max<long>(pl.stat_part_floats, (rows + 127) / 128 * 4 * (2 * (size_t)l.cout + 1));
+            last_sep = (int)pl.layers.size();
+            ++index;
+        } else {
+            q.pw = P(pre + "/kernel", (int64_t)l.k * l.k * l.cout * l.cin);
+            // a block ends in a separable layer, whose activation the transposed convolution reads
+            if (i == 0 || s.layers[i - 1].kind != LAYER_SEP) pl.unsupported = true;
+            q.cat_off = cat_off;
+            cat_off += l.cout;
+            const size_t n = (size_t)l.k * l.k * l.cout;   // GEMM columns
+            pl.pw16_words += (long)2 * l.cin * n;           // the kernel as a GEMM operand [cin][k * k * cout]
+            pl.max_z = std::max(pl.max_z, B * l.in_h * l.in_w * n);
+            // one [2][N] row (+ its row count) per 64-row tile of the product
+            pl.stat_part_floats = std::max<long>(pl.stat_part_floats, ((B * l.in_h * l.in_w + 63) / 64 + 8) * (2 * n + 1));
+            ++block; index = 0;
         }
+        BN(pre + "/bn", l.cout, q.gamma, q.beta, q.mean, q.var);
+        pl.layers.push_back(q);
     }
+    // the backward pass walks blocks that end in a transposed convolution
+    if (!pl.layers.empty() && pl.layers.back().kind != LAYER_DECONV) pl.unsupported = true;
+    for (TrainLayer& q : pl.layers) q.accumulate = q.kind == LAYER_DECONV && q.block + 1 < block;
+    // the split-weight table of the fused forward kernels holds up to 40 layers
+    pl.fused = pl.layers.size() <= 40;
+    pl.part_floats = (size_t)TR_NPART_MAX * m;
     const int nb = s.napl * 7, nc = s.napl * s.ncls, nd = s.use_dir ? s.napl * 2 : 0;
-    P("rpn/conv_box/kernel", (int64_t)s.CC * nb); P("rpn/conv_box/bias", nb);
-    P("rpn/conv_cls/kernel", (int64_t)s.CC * nc); P("rpn/conv_cls/bias", nc);
-    if (nd) { P("rpn/conv_dir_cls/kernel", (int64_t)s.CC * nd); P("rpn/conv_dir_cls/bias", nd); }
-    if (n_params) *n_params = po;
-    if (n_state) *n_state = so;
-    return v;
+    pl.box_k = P("rpn/conv_box/kernel", (int64_t)s.CC * nb); pl.box_b = P("rpn/conv_box/bias", nb);
+    pl.cls_k = P("rpn/conv_cls/kernel", (int64_t)s.CC * nc); pl.cls_b = P("rpn/conv_cls/bias", nc);
+    pl.dir_k = pl.box_k; pl.dir_b = pl.box_b;
+    if (nd) { pl.dir_k = P("rpn/conv_dir_cls/kernel", (int64_t)s.CC * nd); pl.dir_b = P("rpn/conv_dir_cls/bias", nd); }
+    return pl;
 }
 
 namespace {
 
-struct Lookup {
-    const std::vector<TrainEntry>& v;
-    const float* params; float* grads; float* state;
-    const TrainEntry& e(const std::string& n) const {
-        for (const TrainEntry& t : v) if (t.name == n) return t;
-        static TrainEntry none{"", 0, 0, 0};
-        return none;
-    }
-    const float* p(const std::string& n) const { return params + e(n).offset; }
-    float* g(const std::string& n) const { return grads + e(n).offset; }
-    float* s(const std::string& n) const { return state + e(n).offset; }
+// depthwise forward on the persistent kernel: a one-round grid of this many workgroups, from two pixels per thread on
+// (B=32 sweep, grid x pixels: 1024 x 4 0.275 ms, 1280 x 4 0.281, 1280 x 2 0.271, 1024 x 2 0.271, 1280 x 1 0.271,
+// 2048 x 2 0.275; thread-per-output 0.331)
+constexpr long TR_DW_WGS = 1024, TR_DW_MIN_PIXELS = 2;
+
+// The choices of one step that depend on its batch.
+struct StepPlan {
+    struct Layer {
+        bool fused;           // the fused forward launch (else depthwise kernel + product / the product alone)
+        bool dw_persistent;   // separable layers: the depthwise forward on the persistent kernel
+        bool dw_bwd_fused;    // separable layers: the depthwise backward in one pass (k_tr_dw_bwd)
+    };
+    int npart;                // partial rows of the persistent reductions
+    std::vector<Layer> layers;
+    bool heads_fused;
 };
+
+StepPlan plan_step(const TrainPlan& plan, const TrainShape& s, int B) {
+    const TrainSwitches& sw = train_switches();
+    StepPlan sp;
+    // ~128 rows of the largest map per workgroup, one per CU at least
+    const long want = ((long)B * s.ny * s.nx / 128 + 255) / 256 * 256;
+    sp.npart = (int)std::min<long>(TR_NPART_MAX, std::max<long>(256, want));
+    for (const TrainLayer& q : plan.layers) {
+        const LayerDesc& l = s.layers[q.layer];
+        StepPlan::Layer c{false, false, false};
+        if (q.kind == LAYER_SEP) {
+            // fused forward (depthwise + product + statistics in one launch, launch_sep_train) from PP_TRAIN_FUSED_MIN
+            // output pixels on (below that the layers are a handful of workgroups and the split-K product kernels are
+            // the shorter chain)
+            const long rows = (long)B * l.out_h * l.out_w;
+            c.fused = plan.fused && rows >= sw.fused_min && plan.stat_room(rows, l.cout);
+            c.dw_persistent = rows * (l.cin / 4) >= TR_DW_MIN_PIXELS * TR_DW_WGS * 256;
+            // the input is the layer before's BatchNorm + ReLU of Z
+            c.dw_bwd_fused = q.src_z && l.stride == 1;
+        } else {
+            // (a product, not a map walk: what has to be large is the number of workgroup tiles -- deconv3 at B=32 is
+            // 10 240 rows x 2 048 columns = 1 280 tiles of 128 x 128)
+            const long m = (long)B * l.in_h * l.in_w;
+            const int N = l.k * l.k * l.cout;
+            const long wg_tiles = ((m + 127) / 128) * (long)(N / ((N % 128 == 0) ? 128 : ((N % 64 == 0) ? 64 : 32)));
+            c.fused = plan.fused && (m >= sw.fused_min || (sw.fused_min > 0 && wg_tiles >= 512)) && plan.stat_room(m, N);
+        }
+        sp.layers.push_back(c);
+    }
+    sp.heads_fused = plan.fused && (long)B * s.head_h * s.head_w >= sw.fused_min;
+    return sp;
+}
 
 unsigned blocks_for(long n) { return (unsigned)((n + 255) / 256); }
 
 // statistics from `nparts` partial rows [2][C * ntaps]; coef (with gamma, beta): the table the consumers of Z evaluate
-static void bn_finalize(const TrainCtx& cx, const float* part, int nparts, int C, float n_rows, const float* n_rows_dev,
+static void bn_finalize(const TrainStepState& st, const float* part, int nparts, int C, float n_rows, const float* n_rows_dev,
                         float momentum, int unbiased, float* stats, float* mmean, float* mvar, int ntaps,
                         const float* gamma = nullptr, const float* beta = nullptr, float4* coef = nullptr) {
     // lanes per channel by the number of (partial row, tap) pairs a channel has: a whole workgroup from 128 pairs on, a wave
     // from 32 (PP_TRAIN_FIN_THR="a,b" for A/B measurements; round 4, the 20 launches of a step: thresholds 2048 / 512 ->
     // 154 us at B=32 and 102 us at B=2; 512 / 128 -> 112 / 90; 128 / 32 -> 114 / 87: the launch is a chain of dependent
     // load rounds, and more lanes per channel make it shorter even when most of them carry one pair)
-    static long thr256 = -1, thr64 = -1;
-    if (thr256 < 0) {
-        thr256 = 128; thr64 = 32;
-        if (const char* e = getenv("PP_TRAIN_FIN_THR")) { long a = 0, b = 0; if (sscanf(e, "%ld,%ld", &a, &b) == 2 && a > 0 && b > 0) { thr256 = a; thr64 = b; } }
-    }
-    if ((long)nparts * ntaps >= thr256)
-        PP_LAUNCH("k_tr_bn_finalize:256", (k_tr_bn_finalize<256>), dim3(C), dim3(256), 0, cx.stream, part, nparts, C, n_rows,
+    const TrainSwitches& sw = train_switches();
+    const hipStream_t s = st.cx.stream;
+    if ((long)nparts * ntaps >= sw.fin256)
+        PP_LAUNCH("k_tr_bn_finalize:256", (k_tr_bn_finalize<256>), dim3(C), dim3(256), 0, s, part, nparts, C, n_rows,
                   n_rows_dev, momentum, unbiased, stats, mmean, mvar, ntaps, gamma, beta, coef);
-    else if ((long)nparts * ntaps >= thr64)
-        PP_LAUNCH("k_tr_bn_finalize:64", (k_tr_bn_finalize<64>), dim3((C + 3) / 4), dim3(256), 0, cx.stream, part, nparts, C, n_rows,
+    else if ((long)nparts * ntaps >= sw.fin64)
+        PP_LAUNCH("k_tr_bn_finalize:64", (k_tr_bn_finalize<64>), dim3((C + 3) / 4), dim3(256), 0, s, part, nparts, C, n_rows,
                   n_rows_dev, momentum, unbiased, stats, mmean, mvar, ntaps, gamma, beta, coef);
     else
-        PP_LAUNCH("k_tr_bn_finalize:16", (k_tr_bn_finalize<16>), dim3((C + 15) / 16), dim3(256), 0, cx.stream, part, nparts, C, n_rows,
+        PP_LAUNCH("k_tr_bn_finalize:16", (k_tr_bn_finalize<16>), dim3((C + 15) / 16), dim3(256), 0, s, part, nparts, C, n_rows,
                   n_rows_dev, momentum, unbiased, stats, mmean, mvar, ntaps, gamma, beta, coef);
 }
 
 // nparts partial rows of [2][C] (row stride pstride floats) -> sums[2][C] (and, when given, row 0 -> dup0[C], row 1 -> dup1[C])
-void col_reduce(const TrainCtx& cx, int C, float* sums, float* dup0 = nullptr, float* dup1 = nullptr,
+void col_reduce(const TrainStepState& st, int C, float* sums, float* dup0 = nullptr, float* dup1 = nullptr,
                 const float* part = nullptr, long pstride = 0, int nparts = 0) {
     const long n = (long)2 * C;
-    if (part == nullptr) { part = cx.part; pstride = n; nparts = TR_NPART; }
+    if (part == nullptr) { part = st.cx.part; pstride = n; nparts = st.npart; }
     if (nparts >= 1024)
-        PP_LAUNCH("k_tr_reduce", k_tr_reduce_cols_wg, dim3((unsigned)n), dim3(256), 0, cx.stream, part,
+        PP_LAUNCH("k_tr_reduce", k_tr_reduce_cols_wg, dim3((unsigned)n), dim3(256), 0, st.cx.stream, part,
                   nparts, n, pstride, sums, 0L, 0, 0, 1.0f, dup0, dup1, C);
     else
-        PP_LAUNCH("k_tr_reduce", k_tr_reduce_cols, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, cx.stream, part,
+        PP_LAUNCH("k_tr_reduce", k_tr_reduce_cols, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st.cx.stream, part,
                   nparts, n, pstride, sums, 0L, 0, 0, 1.0f, dup0, dup1, C);
 }
 
-// BatchNorm (training) statistics of Z[rows][C] -> stats + coefficient table, moving stats updated; with A != NULL the
-// activation relu(bn(Z)) is written too (mapped rows) -- only where somebody reads it as a tensor (the block-final
-// layers and the transposed convolutions); the in-block consumers evaluate it from Z and the table
+// BatchNorm (training) statistics of layer q's Z[rows][C] -> stats + coefficient table, moving stats updated; with
+// A != NULL the activation relu(bn(Z)) is written too (mapped rows) -- only where somebody reads it as a tensor (the
+// block-final layers and the transposed convolutions); the in-block consumers evaluate it from Z and the table
 // stat_tiles > 0: the product that wrote Z left centred per-row-tile partials in cx.stat_part ([stat_tiles][2][C * ntaps],
 // then the tiles' row counts)
-void bn_relu_forward(const TrainCtx& cx, const float* Z, long rows, int C, const float* gamma, const float* beta,
-                     float* stats, float4* coef, float* mmean, float* mvar, float momentum, float* A, int ld, int co_off,
-                     RowMap rm, int stat_tiles = 0, int ntaps = 1) {
+void bn_relu_forward(const TrainStepState& st, const TrainLayer& q, const TrainLayerBuf& tb, long rows, int C, float* A,
+                     int ld, int co_off, RowMap rm, int stat_tiles, int ntaps) {
+    const TrainCtx& cx = st.cx;
     if (stat_tiles > 0) {
-        bn_finalize(cx, cx.stat_part, stat_tiles, C, (float)rows, nullptr, momentum, 1, stats, mmean, mvar, ntaps, gamma, beta, coef);
+        bn_finalize(st, cx.stat_part, stat_tiles, C, (float)rows, nullptr, 0.99f, 1, tb.stats, st.s(q.mean), st.s(q.var),
+                    ntaps, st.p(q.gamma), st.p(q.beta), tb.coef);
     } else {
-        PP_LAUNCH("k_tr_colstats:bn", k_tr_colstats_c, dim3(TR_NPART), dim3(256), 0, cx.stream, Z, rows, C, cx.part);
-        bn_finalize(cx, cx.part, TR_NPART, C, (float)rows, nullptr, momentum, 1, stats, mmean, mvar, 1, gamma, beta, coef);
+        PP_LAUNCH("k_tr_colstats:bn", k_tr_colstats_c, dim3(st.npart), dim3(256), 0, cx.stream, (const float*)tb.Z, rows, C,
+                  cx.part);
+        bn_finalize(st, cx.part, st.npart, C, (float)rows, nullptr, 0.99f, 1, tb.stats, st.s(q.mean), st.s(q.var), 1,
+                    st.p(q.gamma), st.p(q.beta), tb.coef);
     }
     if (A != nullptr)
-        PP_LAUNCH("k_tr_bn_relu", k_tr_bn_relu, dim3(blocks_for(rows * (C / 4))), dim3(256), 0, cx.stream, Z, rows, C,
-                  (const float4*)coef, A, ld, co_off, rm);
+        PP_LAUNCH("k_tr_bn_relu", k_tr_bn_relu, dim3(blocks_for(rows * (C / 4))), dim3(256), 0, cx.stream, (const float*)tb.Z,
+                  rows, C, (const float4*)tb.coef, A, ld, co_off, rm);
 }
 
 // backward of the same: dA (mapped rows) -> dZ[rows][C]; d gamma, d beta written to the gradient buffer
-// sums_part != NULL: the sums of g and g * zhat already lie in TR_NPART partial rows (left by k_tr_dw_bwd)
-void bn_relu_backward(const TrainCtx& cx, const float* dA, int ld, int co_off, RowMap rm, const float* Z, long rows, int C,
-                      const float4* coef, float* sums, float* dgamma, float* dbeta, float* dZ,
-                      const float* sums_part = nullptr, long sums_pstride = 0, int sums_nparts = 0) {
+// sums_part != NULL: the sums of g and g * zhat already lie in partial rows (left by k_tr_dw_bwd)
+void bn_relu_backward(const TrainStepState& st, const TrainLayer& q, const TrainLayerBuf& tb, const float* dA, int ld,
+                      int co_off, RowMap rm, long rows, int C, float* dZ, const float* sums_part = nullptr,
+                      long sums_pstride = 0, int sums_nparts = 0) {
+    const TrainCtx& cx = st.cx;
     if (sums_part == nullptr) {
-        PP_LAUNCH("k_tr_bn_bwd_reduce", k_tr_bn_bwd_reduce, dim3(TR_NPART), dim3(256), 0, cx.stream, dA, ld, co_off, rm, Z, rows,
-                  C, coef, cx.part);
-        col_reduce(cx, C, sums, dbeta, dgamma);
+        PP_LAUNCH("k_tr_bn_bwd_reduce", k_tr_bn_bwd_reduce, dim3(st.npart), dim3(256), 0, cx.stream, dA, ld, co_off, rm,
+                  (const float*)tb.Z, rows, C, (const float4*)tb.coef, cx.part);
+        col_reduce(st, C, tb.sums, st.g(q.beta), st.g(q.gamma));
     } else {
-        col_reduce(cx, C, sums, dbeta, dgamma, sums_part, sums_pstride, sums_nparts);
+        col_reduce(st, C, tb.sums, st.g(q.beta), st.g(q.gamma), sums_part, sums_pstride, sums_nparts);
     }
     PP_LAUNCH("k_tr_bn_bwd_apply", k_tr_bn_bwd_apply, dim3(blocks_for(rows * (C / 4))), dim3(256), 0, cx.stream, dA, ld, co_off, rm,
-              Z, rows, C, coef, (const float*)sums, 1.0f / (float)rows, dZ);
+              (const float*)tb.Z, rows, C, (const float4*)tb.coef, (const float*)tb.sums, 1.0f / (float)rows, dZ);
 }
 
 // n_rows[0] = (sum of the frames' pillar counts) * T: the rows of the reference's padded [P, T, C] tensor
@@ -2198,208 +2286,160 @@ __global__ void k_tr_pfn_rows(const int* __restrict__ npillars, int batch, int T
 // Persistent PFN grids: one resident round of workgroups (a quarter-filled second round costs a whole one).  Resident
 // 4-wave workgroups per CU follow the kernels' register budgets: CPL 1 / 2 / 4 -> lin 8 / 7 / 4, max 7 / 5 / 4,
 // bwd_reduce 8 / 6 / 4, bwd_apply 5 / 3 / 2.
-static int pfn_blocks(int per_cu) { return std::min(TR_NPART, per_cu * 256); }
+static int pfn_blocks(const TrainStepState& st, int per_cu) { return std::min(st.npart, per_cu * 256); }
 
 template <int CPL>
-void pfn_forward(const TrainCtx& cx, const PfnT& p, const Lookup& L) {
+void pfn_forward(const TrainStepState& st, const PfnT& p) {
+    const TrainCtx& cx = st.cx;
+    const TrainPlan& pl = st.plan;
     PP_LAUNCH("k_tr_pfn_rows", k_tr_pfn_rows, dim3(1), dim3(64), 0, cx.stream, p.npillars, p.batch, p.T, cx.pfn_nrows,
               cx.pfn_prefix);
-    const int nlin = pfn_blocks(CPL == 4 ? 4 : 7), nmax = pfn_blocks(CPL == 4 ? 4 : 5);
+    const int nlin = pfn_blocks(st, CPL == 4 ? 4 : 7), nmax = pfn_blocks(st, CPL == 4 ? 4 : 5);
     PP_LAUNCH("k_tr_pfn_lin", (k_tr_pfn_lin<CPL>), dim3(nlin), dim3(256), 0, cx.stream, p, cx.part);
-    bn_finalize(cx, cx.part, nlin, p.C, 0.f, cx.pfn_nrows, 0.01f, 0, cx.pfn_stats, L.s("pfn/bn/moving_mean"),
-                L.s("pfn/bn/moving_variance"), 1);
+    bn_finalize(st, cx.part, nlin, p.C, 0.f, cx.pfn_nrows, 0.01f, 0, cx.pfn_stats, st.s(pl.pfn_mean), st.s(pl.pfn_var), 1);
     PP_LAUNCH("k_tr_pfn_max", (k_tr_pfn_max<CPL>), dim3(nmax), dim3(256), 0, cx.stream, p,
-              (const float*)cx.pfn_stats, L.p("pfn/bn/gamma"), L.p("pfn/bn/beta"), cx.pfn_feat, cx.pfn_arg);
+              (const float*)cx.pfn_stats, st.p(pl.pfn_gamma), st.p(pl.pfn_beta), cx.pfn_feat, cx.pfn_arg);
 }
 
 template <int CPL>
-void pfn_backward(const TrainCtx& cx, const PfnT& p, const Lookup& L, const float* dcanvas) {
+void pfn_backward(const TrainStepState& st, const PfnT& p) {
+    const TrainCtx& cx = st.cx;
+    const TrainPlan& pl = st.plan;
     // (register budgets with the pillar pipeline: bwd_reduce 54 / 79 / 115 VGPRs, bwd_apply 95 / 138 / 214)
-    const int nred = pfn_blocks(CPL == 4 ? 4 : 6), nblk = pfn_blocks(CPL == 4 ? 2 : (CPL == 2 ? 3 : 5));
+    const int nred = pfn_blocks(st, CPL == 4 ? 4 : 6), nblk = pfn_blocks(st, CPL == 4 ? 2 : (CPL == 2 ? 3 : 5));
     PP_LAUNCH("k_tr_pfn_bwd_reduce", (k_tr_pfn_bwd_reduce<CPL>), dim3(nred), dim3(256), 0, cx.stream, p,
-              (const float*)cx.pfn_stats, (const int*)cx.pfn_arg, dcanvas, cx.part);
-    col_reduce(cx, p.C, cx.pfn_sums, L.g("pfn/bn/beta"), L.g("pfn/bn/gamma"), cx.part, (long)2 * p.C, nred);
+              (const float*)cx.pfn_stats, (const int*)cx.pfn_arg, (const float*)cx.dcanvas, cx.part);
+    col_reduce(st, p.C, cx.pfn_sums, st.g(pl.pfn_beta), st.g(pl.pfn_gamma), cx.part, (long)2 * p.C, nred);
     PP_LAUNCH("k_tr_pfn_bwd_apply", (k_tr_pfn_bwd_apply<CPL>), dim3(nblk), dim3(256), 0, cx.stream, p,
-              (const float*)cx.pfn_stats, L.p("pfn/bn/gamma"), (const int*)cx.pfn_arg, dcanvas, (const float*)cx.pfn_sums,
-              (const float*)cx.pfn_nrows, cx.part);
+              (const float*)cx.pfn_stats, st.p(pl.pfn_gamma), (const int*)cx.pfn_arg, (const float*)cx.dcanvas,
+              (const float*)cx.pfn_sums, (const float*)cx.pfn_nrows, cx.part);
     const long n = (long)p.FA * p.C;
-    tr_reduce(cx.stream, (const float*)cx.part, nblk, n, n,
-              L.g("pfn/dense/kernel"), 0L, 0, 0, 1.0f);
+    tr_reduce(cx.stream, (const float*)cx.part, nblk, n, n, st.g(pl.pfn_w), 0L, 0, 0, 1.0f);
+}
+
+// Depthwise kernel gradient of a layer from `nblk` partial rows of n floats (the first 9 * cin: the kernel gradient) a
+// kernel writes: in a region of the arena of their own, added by the step's deferred-reduction launch.  The arena
+// exhausted, they go to the shared scratch and the kernel-gradient rows are added at once.
+float* dw_grad_region(TrainStepState& st, int nblk, long n) {
+    const bool room = st.arena_used + (long)nblk * n <= st.cx.gemm_part_floats;
+    return room ? st.cx.gemm_part + st.arena_used : st.cx.part;
+}
+void dw_grad_reduce(TrainStepState& st, const float* region, int nblk, long n, long nk, float* dw) {
+    if (region != st.cx.part) {
+        st.jobs.push_back(ReduceJob{region, dw, nk, n, 0L, nblk, 0, 0, 1.0f});
+        st.arena_used += ((long)nblk * n + 63) / 64 * 64;
+    } else {
+        tr_reduce(st.cx.stream, region, nblk, nk, n, dw, 0L, 0, 0, 1.0f);
+    }
 }
 
 }  // namespace
 
-size_t train_part_floats(const TrainShape& s) {
-    size_t m = (size_t)2 * 512;
-    m = std::max(m, (size_t)10 * s.C);
-    for (const LayerDesc& L : s.layers) m = std::max(m, (size_t)11 * std::max(L.cin, L.cout));
-    return (size_t)TR_NPART_MAX * m;
-}
-
-int train_step(const TrainCtx& cx, const TrainShape& s, const std::vector<TrainEntry>& layout, const float* params,
-               float* grads, float* state, int batch, const LossParams& loss_in, int phase) {
+int train_step(const TrainCtx& cx, const TrainShape& s, const TrainPlan& plan, const float* params, float* grads,
+               float* state, int batch, const LossParams& loss_in, int phase) {
     // phase bit 1: forward (PFN .. head maps); bit 2: loss + backward.  pp_train_step enqueues the two halves one after
     // the other with a wait for the target upload in between (the labels / regression targets travel on the copy
     // stream while the forward pass runs)
-    Lookup L{layout, params, grads, state};
+    if (plan.unsupported) return PP_ERR_UNSUPPORTED;
     const int B = batch;
-    g_jobs.clear();
-    g_arena_used = 0;
-    {   // partial rows of the persistent reductions: ~128 rows of the largest map per workgroup, one per CU at least
-        long want = ((long)B * s.ny * s.nx / 128 + 255) / 256 * 256;
-        g_tr_npart = (int)std::min<long>(TR_NPART_MAX, std::max<long>(256, want));
-    }
-    if (s.C > 256 || s.C % 4 != 0 || s.FA > 10) return PP_ERR_UNSUPPORTED;
-    for (const LayerDesc& l : s.layers)   // channel counts the reduction kernels are written for
-        if (l.kind != LAYER_HEAD && (l.cin % 16 != 0 || l.cout < 32 || l.cout > 256 || (l.cout & (l.cout - 1)) != 0 ||
-                                     l.cin > 256 || (l.kind == LAYER_SEP && l.stride != 1 && l.stride != 2)))
-            return PP_ERR_UNSUPPORTED;
+    const StepPlan sp = plan_step(plan, s, B);
+    TrainStepState st{cx, plan, params, grads, state, sp.npart, {}, 0};
+    const std::vector<TrainLayer>& Ls = plan.layers;
 
-    // ---------------- forward ----------------
     PfnT p;
     memset(&p, 0, sizeof(p));
     p.batch = B; p.nx = s.nx; p.ny = s.ny; p.C = s.C; p.F = s.F; p.FA = s.FA; p.T = s.T; p.max_voxels = s.max_voxels;
     p.with_distance = s.with_dist;
     p.vx = s.vx; p.vy = s.vy; p.x_off = s.x_off; p.y_off = s.y_off;
     p.pts_sorted = cx.pts_sorted; p.offsets = cx.offsets; p.pillar_start = cx.pillar_start; p.pillar_cell = cx.pillar_cell;
-    p.npillars = cx.npillars; p.W = L.p("pfn/dense/kernel"); p.pprefix = cx.pfn_prefix; p.rec = cx.pfn_rec;
+    p.npillars = cx.npillars; p.W = st.p(plan.pfn_w); p.pprefix = cx.pfn_prefix; p.rec = cx.pfn_rec;
     const int cpl = (s.C + 63) / 64;
     const RowMap ident{1, 0, 0};
-    const size_t HW = (size_t)s.head_h * s.head_w;
     const int nb = s.napl * 7, nc = s.napl * s.ncls, nd = s.use_dir ? s.napl * 2 : 0;
-    const long px = (long)B * HW;
+    const long px = (long)B * s.head_h * s.head_w;
+
+    // ---------------- forward ----------------
     if (phase & 1) {
-    if (cpl == 1) pfn_forward<1>(cx, p, L);
-    else if (cpl == 2) pfn_forward<2>(cx, p, L);
-    else pfn_forward<4>(cx, p, L);
+    if (cpl == 1) pfn_forward<1>(st, p);
+    else if (cpl == 2) pfn_forward<2>(st, p);
+    else pfn_forward<4>(st, p);
     const int ncanvas = s.nx * s.ny;
     PP_LAUNCH("k_tr_scatter", k_tr_scatter, dim3(blocks_for((long)B * ncanvas * (s.C / 4))), dim3(256), 0, cx.stream, cx.cellmap,
               (const float*)cx.pfn_feat, cx.canvas, B, s.nz, ncanvas, s.C, s.max_voxels);
 
-    // fused forward of the separable layers (depthwise + product + statistics in one launch, launch_sep_train): from
-    // PP_TRAIN_FUSED_MIN output pixels on (below that the layers are a handful of workgroups and the split-K product
-    // kernels are the shorter chain)
-    static long fused_min = -1;
-    if (fused_min < 0) { const char* e = getenv("PP_TRAIN_FUSED_MIN"); fused_min = e ? atol(e) : 32768; }
-    bool fused = cx.pw16 != nullptr;
-    if (fused) {
+    if (plan.fused && !Ls.empty()) {   // this step's forward kernels in the fused kernels' operand form
         SplitPwTable t;
         memset(&t, 0, sizeof(t));
-        int bi_ = 0, li_ = 0;
-        for (size_t i = 0; i < s.layers.size() && fused; ++i) {
-            const LayerDesc& l = s.layers[i];
-            if (l.kind != LAYER_SEP && l.kind != LAYER_DECONV) continue;
-            if (t.n >= 40) { fused = false; break; }
-            if (l.kind == LAYER_SEP) {
-                const std::string pre = "rpn/block" + std::to_string(bi_ + 1) + "/" + std::to_string(li_);
-                t.job[t.n] = SplitPwJob{L.p(pre + "/pointwise_kernel"), cx.lbuf[i].pw16_off, l.cin, l.cout, (long)l.cout, 1L, t.total};
+        for (const TrainLayer& q : Ls) {
+            const LayerDesc& l = s.layers[q.layer];
+            if (q.kind == LAYER_SEP) {
+                t.job[t.n] = SplitPwJob{st.p(q.pw), q.pw16_off, l.cin, l.cout, (long)l.cout, 1L, t.total};
                 t.total += (long)l.cin * l.cout;
-                ++li_;
             } else {
                 const int N = l.k * l.k * l.cout;
-                t.job[t.n] = SplitPwJob{L.p("rpn/deconv" + std::to_string(bi_ + 1) + "/kernel"), cx.lbuf[i].pw16_off, l.cin, N, 1L, (long)l.cin, t.total};
+                t.job[t.n] = SplitPwJob{st.p(q.pw), q.pw16_off, l.cin, N, 1L, (long)l.cin, t.total};
                 t.total += (long)l.cin * N;
-                ++bi_; li_ = 0;
             }
             ++t.n;
         }
-        if (fused && t.n > 0)
-            PP_LAUNCH("k_tr_split_pw", k_tr_split_pw, dim3(blocks_for(t.total)), dim3(256), 0, cx.stream, cx.pw16, t);
+        PP_LAUNCH("k_tr_split_pw", k_tr_split_pw, dim3(blocks_for(t.total)), dim3(256), 0, cx.stream, cx.pw16, t);
     }
 
-    // cur: what the next layer reads -- a tensor (cur_coef == NULL: the canvas, a block-final activation) or the
-    // pre-BatchNorm map of an in-block layer with its coefficient table (the activation is evaluated by the reader)
-    const float* cur = cx.canvas;
-    const float4* cur_coef = nullptr;
-    int bi = 0, li = 0, co_off = 0;
-    for (size_t i = 0; i < s.layers.size(); ++i) {
-        const LayerDesc& l = s.layers[i];
-        const TrainLayerBuf& tb = cx.lbuf[i];
-        if (l.kind == LAYER_SEP) {
-            const std::string pre = "rpn/block" + std::to_string(bi + 1) + "/" + std::to_string(li);
+    for (size_t j = 0; j < Ls.size(); ++j) {
+        const TrainLayer& q = Ls[j];
+        const LayerDesc& l = s.layers[q.layer];
+        const TrainLayerBuf& tb = cx.lbuf[j];
+        // the input: the canvas, a block-final activation, or the pre-BatchNorm map of an in-block layer with its
+        // coefficient table (the activation is evaluated by the reader)
+        const float* in = q.src < 0 ? cx.canvas : (q.src_z ? cx.lbuf[q.src].Z : cx.lbuf[q.src].A);
+        const float4* in_coef = q.src_z ? cx.lbuf[q.src].coef : nullptr;
+        int stat_tiles = 0;
+        if (q.kind == LAYER_SEP) {
             const long rows = (long)B * l.out_h * l.out_w;
-            int stat_rows = 0;
-            if (fused && rows >= fused_min && ((rows + 127) / 128 + 8) * (2 * l.cout + 1) <= cx.stat_part_floats) {
+            if (sp.layers[j].fused) {
                 SepTrainArgs t;
-                t.in = cur; t.coef = cur_coef; t.dw = L.p(pre + "/depthwise_kernel"); t.wt16 = cx.pw16 + tb.pw16_off;
+                t.in = in; t.coef = in_coef; t.dw = st.p(q.dw); t.wt16 = cx.pw16 + q.pw16_off;
                 t.Z = tb.Z; t.D = tb.D; t.stat = cx.stat_part;
                 t.batch = B; t.in_h = l.in_h; t.in_w = l.in_w; t.cin = l.cin; t.out_h = l.out_h; t.out_w = l.out_w;
-                t.cout = l.cout; t.stride = l.stride;
-                static thread_local std::string tags[64];     // (the profiler keeps the pointer)
-                std::string& tag = tags[i % 64];
-                tag = "k_sep_u_tr:block" + std::to_string(bi + 1) + "." + std::to_string(li);
-                t.tag = tag.c_str();
-                stat_rows = launch_sep_train(t, cx.stream);
+                t.cout = l.cout; t.stride = l.stride; t.tag = q.fused_tag.c_str();
+                stat_tiles = launch_sep_train(t, cx.stream);
             }
-            if (stat_rows > 0) {
-                g_last_stat_tiles = stat_rows;
-            } else {
-            const long nthr = rows * (l.cin / 4);
-            // workgroups of the persistent kernel, least pixels per thread (B=32 sweep, grid x pixels: 1024 x 4 0.275 ms,
-            // 1280 x 4 0.281, 1280 x 2 0.271, 1024 x 2 0.271, 1280 x 1 0.271, 2048 x 2 0.275; thread-per-output 0.331)
-            const long dwg = 1024, dwm = 2;
-            if (nthr >= dwm * dwg * 256) {      // at least dwm pixels per thread on a one-round grid
-                PP_LAUNCH("k_tr_dw_fwd", k_tr_dw_fwd_p, dim3((unsigned)dwg), dim3(256), 0, cx.stream, cur, L.p(pre + "/depthwise_kernel"),
-                          tb.D, B, l.in_h, l.in_w, l.out_h, l.out_w, l.cin, l.stride, cur_coef);
-            } else {
-                PP_LAUNCH("k_tr_dw_fwd", k_tr_dw_fwd, dim3(blocks_for(nthr)), dim3(256), 0, cx.stream, cur,
-                          L.p(pre + "/depthwise_kernel"), tb.D, (unsigned)nthr, l.in_h, l.in_w,
-                          make_div((unsigned)l.out_h), make_div((unsigned)l.out_w), make_div((unsigned)(l.cin / 4)), l.cin,
-                          l.stride, cur_coef);
+            if (stat_tiles == 0) {
+                const long nthr = rows * (l.cin / 4);
+                if (sp.layers[j].dw_persistent)
+                    PP_LAUNCH("k_tr_dw_fwd", k_tr_dw_fwd_p, dim3((unsigned)TR_DW_WGS), dim3(256), 0, cx.stream, in,
+                              st.p(q.dw), tb.D, B, l.in_h, l.in_w, l.out_h, l.out_w, l.cin, l.stride, in_coef);
+                else
+                    PP_LAUNCH("k_tr_dw_fwd", k_tr_dw_fwd, dim3(blocks_for(nthr)), dim3(256), 0, cx.stream, in, st.p(q.dw),
+                              tb.D, (unsigned)nthr, l.in_h, l.in_w, make_div((unsigned)l.out_h), make_div((unsigned)l.out_w),
+                              make_div((unsigned)(l.cin / 4)), l.cin, l.stride, in_coef);
+                stat_tiles = tr_gemm(st, GemmCall{q.fwd_tag.c_str(), tb.D, l.cin, 1, st.p(q.pw), l.cout, 1, tb.Z, l.cout,
+                                                  (int)rows, l.cout, l.cin, nullptr, 0, 1, cx.stat_part, false});
             }
-            gemm_tag("k_tr_gemm2:fwd.block" + std::to_string(bi + 1) + "." + std::to_string(li));
-            tr_gemm(cx, tb.D, l.cin, 1, L.p(pre + "/pointwise_kernel"), l.cout, 1, tb.Z, l.cout, (int)rows, l.cout, l.cin,
-                    nullptr, 0, 1, cx.stat_part);
-            }
-            // tb.A exists for the block-final layers only (the transposed convolution and the next block read it)
-            bn_relu_forward(cx, tb.Z, rows, l.cout, L.p(pre + "/bn/gamma"), L.p(pre + "/bn/beta"), tb.stats, tb.coef,
-                            L.s(pre + "/bn/moving_mean"), L.s(pre + "/bn/moving_variance"), 0.99f, tb.A, l.cout, 0, ident,
-                            g_last_stat_tiles, 1);
-            if (tb.A != nullptr) { cur = tb.A; cur_coef = nullptr; }
-            else { cur = tb.Z; cur_coef = tb.coef; }
-            ++li;
-        } else if (l.kind == LAYER_DECONV) {
-            const std::string pre = "rpn/deconv" + std::to_string(bi + 1);
+            bn_relu_forward(st, q, tb, rows, l.cout, tb.A, l.cout, 0, ident, stat_tiles, 1);
+        } else {
+            // Zs[m][tap * cout + co] = X[m][:] . K[tap][co][:]   (Keras Conv2DTranspose kernel [k, k, Cout, Cin])
             const long m = (long)B * l.in_h * l.in_w;
             const int N = l.k * l.k * l.cout;
-            if (cur_coef != nullptr) return PP_ERR_UNSUPPORTED;   // (a block always ends in a layer that keeps its activation)
-            // Zs[m][tap * cout + co] = X[m][:] . K[tap][co][:]   (Keras Conv2DTranspose kernel [k, k, Cout, Cin])
-            int stat_rows = 0;
-            // (a product, not a map walk: what has to be large is the number of workgroup tiles -- deconv3 at B=32 is
-            // 10 240 rows x 2 048 columns = 1 280 tiles of 128 x 128)
-            const long wg_tiles = ((m + 127) / 128) * (long)(N / ((N % 128 == 0) ? 128 : ((N % 64 == 0) ? 64 : 32)));
-            if (fused && (m >= fused_min || (fused_min > 0 && wg_tiles >= 512)) &&
-                ((m + 127) / 128 + 8) * (2 * (long)N + 1) <= cx.stat_part_floats) {
-                static thread_local std::string tags[64];
-                std::string& tag = tags[i % 64];
-                tag = "k_sep_u_tr:deconv" + std::to_string(bi + 1);
+            if (sp.layers[j].fused) {
                 RowsTrainArgs t;
-                t.in = cur; t.wt16 = cx.pw16 + tb.pw16_off; t.bias = nullptr; t.out = tb.Z; t.stat = cx.stat_part;
-                t.rows = m; t.K = l.cin; t.N = N; t.ld_out = N; t.tag = tag.c_str();
-                stat_rows = launch_rows_train(t, cx.stream);
+                t.in = in; t.wt16 = cx.pw16 + q.pw16_off; t.bias = nullptr; t.out = tb.Z; t.stat = cx.stat_part;
+                t.rows = m; t.K = l.cin; t.N = N; t.ld_out = N; t.tag = q.fused_tag.c_str();
+                stat_tiles = launch_rows_train(t, cx.stream);
             }
-            if (stat_rows > 0) {
-                g_last_stat_tiles = stat_rows;
-            } else {
-            gemm_tag("k_tr_gemm2:fwd.deconv" + std::to_string(bi + 1));
-            tr_gemm(cx, cur, l.cin, 1, L.p(pre + "/kernel"), 1, l.cin, tb.Z, N, (int)m, N, l.cin, nullptr, 0, 1, cx.stat_part);
-            }
-            const RowMap rm{l.k, l.in_h, l.in_w};
-            bn_relu_forward(cx, tb.Z, m * l.k * l.k, l.cout, L.p(pre + "/bn/gamma"), L.p(pre + "/bn/beta"), tb.stats, tb.coef,
-                            L.s(pre + "/bn/moving_mean"), L.s(pre + "/bn/moving_variance"), 0.99f, cx.cat, s.CC, co_off, rm,
-                            g_last_stat_tiles, l.k * l.k);
-            co_off += l.cout;
-            ++bi; li = 0;
+            if (stat_tiles == 0)
+                stat_tiles = tr_gemm(st, GemmCall{q.fwd_tag.c_str(), in, l.cin, 1, st.p(q.pw), 1, l.cin, tb.Z, N, (int)m, N,
+                                                  l.cin, nullptr, 0, 1, cx.stat_part, false});
+            bn_relu_forward(st, q, tb, m * l.k * l.k, l.cout, cx.cat, s.CC, q.cat_off, RowMap{l.k, l.in_h, l.in_w},
+                            stat_tiles, l.k * l.k);
         }
     }
     // heads: head[px][32] = cat[px][CC] . Wh[CC][32] + bias
-    const float* kd = nd ? L.p("rpn/conv_dir_cls/kernel") : L.p("rpn/conv_box/kernel");
-    const float* bd = nd ? L.p("rpn/conv_dir_cls/bias") : L.p("rpn/conv_box/bias");
     PP_LAUNCH("k_tr_pack_heads", k_tr_pack_heads, dim3(blocks_for((long)s.CC * PP_HEAD_COLS)), dim3(256), 0, cx.stream,
-              L.p("rpn/conv_box/kernel"), L.p("rpn/conv_cls/kernel"), kd, L.p("rpn/conv_box/bias"), L.p("rpn/conv_cls/bias"), bd,
+              st.p(plan.box_k), st.p(plan.cls_k), st.p(plan.dir_k), st.p(plan.box_b), st.p(plan.cls_b), st.p(plan.dir_b),
               s.CC, nb, nc, nd, cx.head_w, cx.head_b);
     int heads_done = 0;
-    if (fused && px >= fused_min && cx.head_w16 != nullptr) {
+    if (sp.heads_fused) {
         SplitPwTable t;
         memset(&t, 0, sizeof(t));
         t.n = 1; t.total = (long)s.CC * PP_HEAD_COLS;
@@ -2410,146 +2450,103 @@ int train_step(const TrainCtx& cx, const TrainShape& s, const std::vector<TrainE
         r.rows = px; r.K = s.CC; r.N = PP_HEAD_COLS; r.ld_out = PP_HEAD_COLS; r.tag = "k_sep_u_tr:heads";
         heads_done = launch_rows_train(r, cx.stream);
     }
-    if (!heads_done) {
-    gemm_tag("k_tr_gemm2:fwd.heads");
-    tr_gemm(cx, cx.cat, s.CC, 1, cx.head_w, PP_HEAD_COLS, 1, cx.head, PP_HEAD_COLS, (int)px, PP_HEAD_COLS, s.CC, cx.head_b, 0, 1);
-    }
+    if (!heads_done)
+        tr_gemm(st, GemmCall{"k_tr_gemm2:fwd.heads", cx.cat, s.CC, 1, cx.head_w, PP_HEAD_COLS, 1, cx.head, PP_HEAD_COLS,
+                             (int)px, PP_HEAD_COLS, s.CC, cx.head_b, 0, 1, nullptr, false});
     }   // forward
+    assert(st.jobs.empty() && st.arena_used == 0);   // (the deferred reductions all belong to the backward half)
     if (!(phase & 2)) return PP_OK;
 
     // ---------------- loss + gradient at the head maps ----------------
     LossParams lp = loss_in;
     lp.head = cx.head;
     lp.head_grad = cx.dhead;
-    int st = launch_head_loss(lp, cx.stream);
-    if (st) return st;
+    int rc = launch_head_loss(lp, cx.stream);
+    if (rc) return rc;
 
     // ---------------- backward ----------------
     // heads: dWh = cat^T . dhead, dbias = column sums, dcat = dhead . Wh^T
-    gemm_tag("k_tr_gemm2:wgrad.heads");
-    tr_gemm(cx, cx.cat, 1, s.CC, cx.dhead, PP_HEAD_COLS, 1, cx.dhead_w, PP_HEAD_COLS, s.CC, PP_HEAD_COLS, (int)px, nullptr, 0,
-            wgrad_split(cx, s.CC, PP_HEAD_COLS, (int)px));      // (reduced at once: k_tr_unpack_head_grads reads it next)
-    PP_LAUNCH("k_tr_colstats", k_tr_colstats, dim3(TR_NPART), dim3(256), 0, cx.stream, (const float*)cx.dhead, px, PP_HEAD_COLS,
+    tr_gemm(st, GemmCall{"k_tr_gemm2:wgrad.heads", cx.cat, 1, s.CC, cx.dhead, PP_HEAD_COLS, 1, cx.dhead_w, PP_HEAD_COLS, s.CC,
+                         PP_HEAD_COLS, (int)px, nullptr, 0, wgrad_split(st, s.CC, PP_HEAD_COLS, (int)px), nullptr, false});
+    // (reduced at once: k_tr_unpack_head_grads reads it next)
+    PP_LAUNCH("k_tr_colstats", k_tr_colstats, dim3(st.npart), dim3(256), 0, cx.stream, (const float*)cx.dhead, px, PP_HEAD_COLS,
               cx.part);
-    col_reduce(cx, PP_HEAD_COLS, cx.dhead_b);   // [0][c] = column sums (the [1][c] half is unused)
-    {
-        float* gkd = nd ? L.g("rpn/conv_dir_cls/kernel") : L.g("rpn/conv_box/kernel");
-        float* gbd = nd ? L.g("rpn/conv_dir_cls/bias") : L.g("rpn/conv_box/bias");
-        PP_LAUNCH("k_tr_unpack_head_grads", k_tr_unpack_head_grads, dim3(blocks_for((long)s.CC * PP_HEAD_COLS)), dim3(256), 0,
-                  cx.stream, (const float*)cx.dhead_w, (const float*)cx.dhead_b, s.CC, nb, nc, nd, L.g("rpn/conv_box/kernel"),
-                  L.g("rpn/conv_cls/kernel"), gkd, L.g("rpn/conv_box/bias"), L.g("rpn/conv_cls/bias"), gbd);
-    }
-    gemm_tag("k_tr_gemm2:dgrad.heads");
-    tr_gemm(cx, cx.dhead, PP_HEAD_COLS, 1, cx.head_w, 1, PP_HEAD_COLS, cx.dcat, s.CC, (int)px, s.CC, PP_HEAD_COLS, nullptr, 0, 1);
+    col_reduce(st, PP_HEAD_COLS, cx.dhead_b);   // [0][c] = column sums (the [1][c] half is unused)
+    PP_LAUNCH("k_tr_unpack_head_grads", k_tr_unpack_head_grads, dim3(blocks_for((long)s.CC * PP_HEAD_COLS)), dim3(256), 0,
+              cx.stream, (const float*)cx.dhead_w, (const float*)cx.dhead_b, s.CC, nb, nc, nd, st.g(plan.box_k),
+              st.g(plan.cls_k), st.g(plan.dir_k), st.g(plan.box_b), st.g(plan.cls_b), st.g(plan.dir_b));
+    tr_gemm(st, GemmCall{"k_tr_gemm2:dgrad.heads", cx.dhead, PP_HEAD_COLS, 1, cx.head_w, 1, PP_HEAD_COLS, cx.dcat, s.CC,
+                         (int)px, s.CC, PP_HEAD_COLS, nullptr, 0, 1, nullptr, false});
 
-    // blocks in reverse: the gradient of a block's output arrives from the next block's first layer (stored by
-    // its depthwise backward) and from its own transposed convolution (accumulated on top)
-    std::vector<int> first_of_block, deconv_of_block;
-    {
-        int start = 0;
-        for (size_t i = 0; i < s.layers.size(); ++i)
-            if (s.layers[i].kind == LAYER_DECONV) { first_of_block.push_back(start); deconv_of_block.push_back((int)i); start = (int)i + 1; }
-    }
-    const int nblocks = (int)deconv_of_block.size();
-    std::vector<int> cat_off(nblocks, 0);
-    for (int b = 1; b < nblocks; ++b) cat_off[b] = cat_off[b - 1] + s.layers[deconv_of_block[b - 1]].cout;
-    for (int b = nblocks - 1; b >= 0; --b) {
-        const int di = deconv_of_block[b];
-        const LayerDesc& d = s.layers[di];
-        const TrainLayerBuf& db = cx.lbuf[di];
-        const std::string dpre = "rpn/deconv" + std::to_string(b + 1);
-        const int last = di - 1;                                  // last separable layer of the block
-        const float* Xd = cx.lbuf[last].A;                        // the block's output = the deconv's input
-        const long m = (long)B * d.in_h * d.in_w;
-        const int N = d.k * d.k * d.cout;
-        const RowMap rm{d.k, d.in_h, d.in_w};
-        bn_relu_backward(cx, cx.dcat, s.CC, cat_off[b], rm, db.Z, m * d.k * d.k, d.cout, db.coef, db.sums,
-                         L.g(dpre + "/bn/gamma"), L.g(dpre + "/bn/beta"), cx.dZ);
-        // dK[n][cin] = dZs^T . X     dX[m][cin] (+)= dZs . K
-        float* dAct = cx.lbuf[last].dA;
-        gemm_tag("k_tr_gemm2:pair.deconv" + std::to_string(b + 1));
-        tr_gemm_pair(cx,
-                     GemmCall{cx.dZ, 1, N, Xd, d.cin, 1, L.g(dpre + "/kernel"), d.cin, N, d.cin, (int)m, nullptr, 0,
-                              wgrad_split(cx, N, d.cin, (int)m), nullptr, true},
-                     GemmCall{cx.dZ, N, 1, L.p(dpre + "/kernel"), d.cin, 1, dAct, d.cin, (int)m, d.cin, N, nullptr,
-                              (b + 1 < nblocks) ? 1 : 0, dgrad_split((int)m, d.cin, N), nullptr, false});
-        // BatchNorm-backward sums of layer i left by the fused depthwise backward of layer i + 1 (NULL: not yet)
-        const float* sums_part = nullptr;
-        long sums_pstride = 0;
-        int sums_nparts = 0;
-        for (int i = last; i >= first_of_block[b]; --i) {
-            const LayerDesc& l = s.layers[i];
-            const TrainLayerBuf& tb = cx.lbuf[i];
-            const std::string pre = "rpn/block" + std::to_string(b + 1) + "/" + std::to_string(i - first_of_block[b]);
-            const long rows = (long)B * l.out_h * l.out_w;
-            bn_relu_backward(cx, tb.dA, l.cout, 0, ident, tb.Z, rows, l.cout, tb.coef, tb.sums, L.g(pre + "/bn/gamma"),
-                             L.g(pre + "/bn/beta"), cx.dZ, sums_part, sums_pstride, sums_nparts);
-            sums_part = nullptr;
-            // dWp[cin][cout] = D^T . dZ      dD[rows][cin] = dZ . Wp^T
-            gemm_tag("k_tr_gemm2:pair.block" + std::to_string(b + 1) + "." + std::to_string(i - first_of_block[b]));
-            tr_gemm_pair(cx,
-                         GemmCall{tb.D, 1, l.cin, cx.dZ, l.cout, 1, L.g(pre + "/pointwise_kernel"), l.cout, l.cin, l.cout,
-                                  (int)rows, nullptr, 0, wgrad_split(cx, l.cin, l.cout, (int)rows), nullptr, true},
-                         GemmCall{cx.dZ, l.cout, 1, L.p(pre + "/pointwise_kernel"), 1, l.cout, cx.dD, l.cin, (int)rows, l.cin,
-                                  l.cout, nullptr, 0, 1, nullptr, false});
-            const bool in_block = i > first_of_block[b];          // the input is the layer before's BatchNorm + ReLU of Z
-            if (in_block && l.stride == 1 && cx.lbuf[i - 1].A == nullptr) {
-                // one pass: depthwise kernel gradient, input gradient, and the layer before's BatchNorm-backward sums;
-                // partial rows [TR_NPART][11][cin] in a region of their own (the kernel-gradient rows are added by the
-                // step's deferred-reduction launch, the two sum rows by the layer before's col_reduce)
-                const TrainLayerBuf& pb = cx.lbuf[i - 1];
-                const long n = (long)11 * l.cin;
-                // at most one resident round of workgroups (179 VGPRs with the nine window loads in flight: two per CU);
-                // 1 280 workgroups on 1 024 slots ran a quarter-filled second round
-                const int nblk = std::min(TR_NPART, 512);
-                // (arena exhausted: the partial rows go to the shared scratch and the kernel-gradient rows are added at
-                // once, as in the k_tr_dw_bwd_w branch below; the two sum rows are read by the next col_reduce before
-                // anything else writes the scratch)
-                const bool room = g_arena_used + (long)nblk * n <= cx.gemm_part_floats;
-                float* region = room ? cx.gemm_part + g_arena_used : cx.part;
-                PP_LAUNCH("k_tr_dw_bwd", k_tr_dw_bwd, dim3(nblk), dim3(256), 0, cx.stream, (const float*)cx.dD,
-                          L.p(pre + "/depthwise_kernel"), (const float*)pb.Z, (const float4*)pb.coef, pb.dA, region, B, l.in_h,
-                          l.in_w, l.cin);
-                if (room) {
-                    g_jobs.push_back(ReduceJob{region, L.g(pre + "/depthwise_kernel"), (long)9 * l.cin, n, 0L, nblk, 0, 0, 1.0f});
-                    g_arena_used += ((long)nblk * n + 63) / 64 * 64;
-                } else {
-                    tr_reduce(cx.stream, (const float*)region, nblk, (long)9 * l.cin, n, L.g(pre + "/depthwise_kernel"), 0L, 0, 0, 1.0f);
-                }
-                sums_part = region + (long)9 * l.cin;
-                sums_pstride = n;
-                sums_nparts = nblk;
-                continue;
-            }
-            const float* X = (i == 0) ? cx.canvas : cx.lbuf[i - 1 - ((i == first_of_block[b] && b > 0) ? 1 : 0)].A;
-            if (X == nullptr) return PP_ERR_UNSUPPORTED;
-            {   // partial rows [TR_NPART][9][cin] in a region of their own, added by the step's deferred-reduction launch
-                const long n = (long)9 * l.cin;
-                const int nbw = std::min(TR_NPART, 1024);       // (98 VGPRs: four workgroups per CU -- one resident round)
-                float* region = cx.part;
-                const bool room = g_arena_used + (long)nbw * n <= cx.gemm_part_floats;
-                if (room) region = cx.gemm_part + g_arena_used;
-                PP_LAUNCH("k_tr_dw_bwd_w", k_tr_dw_bwd_w, dim3(nbw), dim3(256), 0, cx.stream, X, (const float*)cx.dD, region, B,
-                          l.in_h, l.in_w, l.out_h, l.out_w, l.cin, l.stride);
-                if (room) {
-                    g_jobs.push_back(ReduceJob{region, L.g(pre + "/depthwise_kernel"), n, n, 0L, nbw, 0, 0, 1.0f});
-                    g_arena_used += ((long)nbw * n + 63) / 64 * 64;
-                } else {
-                    tr_reduce(cx.stream, (const float*)cx.part, nbw, n, n, L.g(pre + "/depthwise_kernel"), 0L, 0, 0, 1.0f);
-                }
-            }
-            // gradient of this layer's input: the previous layer's dA, the previous block's output gradient, or the canvas
-            float* dX = (i == 0) ? cx.dcanvas : cx.lbuf[i - 1 - ((i == first_of_block[b] && b > 0) ? 1 : 0)].dA;
-            PP_LAUNCH("k_tr_dw_bwd_in", k_tr_dw_bwd_in, dim3(blocks_for((long)B * l.in_h * l.in_w * (l.cin / 4))), dim3(256), 0,
-                      cx.stream, (const float*)cx.dD, L.p(pre + "/depthwise_kernel"), dX,
-                      (unsigned)((long)B * l.in_h * l.in_w * (l.cin / 4)), make_div((unsigned)l.in_h), make_div((unsigned)l.in_w),
-                      l.out_h, l.out_w, make_div((unsigned)(l.cin / 4)), l.cin, l.stride, 0);
+    // layers in reverse: the gradient of a block's output arrives from the next block's first layer (stored by its
+    // depthwise backward) and from its own transposed convolution (accumulated on top)
+    // BatchNorm-backward sums of a layer left by the fused depthwise backward of the layer after it (NULL: not yet)
+    const float* sums_part = nullptr;
+    long sums_pstride = 0;
+    int sums_nparts = 0;
+    for (int j = (int)Ls.size() - 1; j >= 0; --j) {
+        const TrainLayer& q = Ls[j];
+        const LayerDesc& l = s.layers[q.layer];
+        const TrainLayerBuf& tb = cx.lbuf[j];
+        const TrainLayerBuf& xb = cx.lbuf[std::max(q.src, 0)];    // (q.src < 0: the canvas)
+        if (q.kind == LAYER_DECONV) {
+            const long m = (long)B * l.in_h * l.in_w;
+            const int N = l.k * l.k * l.cout;
+            bn_relu_backward(st, q, tb, cx.dcat, s.CC, q.cat_off, RowMap{l.k, l.in_h, l.in_w}, m * l.k * l.k, l.cout, cx.dZ);
+            // dK[n][cin] = dZs^T . X     dX[m][cin] (+)= dZs . K
+            tr_gemm_pair(st,
+                         GemmCall{q.pair_tag.c_str(), cx.dZ, 1, N, xb.A, l.cin, 1, st.g(q.pw), l.cin, N, l.cin, (int)m,
+                                  nullptr, 0, wgrad_split(st, N, l.cin, (int)m), nullptr, true},
+                         GemmCall{q.pair_tag.c_str(), cx.dZ, N, 1, st.p(q.pw), l.cin, 1, xb.dA, l.cin, (int)m, l.cin, N,
+                                  nullptr, q.accumulate ? 1 : 0, dgrad_split((int)m, l.cin, N), nullptr, false});
+            continue;
         }
+        const long rows = (long)B * l.out_h * l.out_w;
+        bn_relu_backward(st, q, tb, tb.dA, l.cout, 0, ident, rows, l.cout, cx.dZ, sums_part, sums_pstride, sums_nparts);
+        sums_part = nullptr;
+        // dWp[cin][cout] = D^T . dZ      dD[rows][cin] = dZ . Wp^T
+        tr_gemm_pair(st,
+                     GemmCall{q.pair_tag.c_str(), tb.D, 1, l.cin, cx.dZ, l.cout, 1, st.g(q.pw), l.cout, l.cin, l.cout,
+                              (int)rows, nullptr, 0, wgrad_split(st, l.cin, l.cout, (int)rows), nullptr, true},
+                     GemmCall{q.pair_tag.c_str(), cx.dZ, l.cout, 1, st.p(q.pw), 1, l.cout, cx.dD, l.cin, (int)rows, l.cin,
+                              l.cout, nullptr, 0, 1, nullptr, false});
+        if (sp.layers[j].dw_bwd_fused) {
+            // one pass: depthwise kernel gradient, input gradient, and the layer before's BatchNorm-backward sums;
+            // partial rows [nblk][11][cin] (the two sum rows are read by the layer before's col_reduce before anything
+            // else writes the shared scratch)
+            const long n = (long)11 * l.cin;
+            // at most one resident round of workgroups (179 VGPRs with the nine window loads in flight: two per CU);
+            // 1 280 workgroups on 1 024 slots ran a quarter-filled second round
+            const int nblk = std::min(st.npart, 512);
+            float* region = dw_grad_region(st, nblk, n);
+            PP_LAUNCH("k_tr_dw_bwd", k_tr_dw_bwd, dim3(nblk), dim3(256), 0, cx.stream, (const float*)cx.dD, st.p(q.dw),
+                      (const float*)xb.Z, (const float4*)xb.coef, xb.dA, region, B, l.in_h, l.in_w, l.cin);
+            dw_grad_reduce(st, region, nblk, n, (long)9 * l.cin, st.g(q.dw));
+            sums_part = region + (long)9 * l.cin;
+            sums_pstride = n;
+            sums_nparts = nblk;
+            continue;
+        }
+        // the input and its gradient: the layer before's activation (the previous block's output) or the canvas
+        const float* X = q.src < 0 ? cx.canvas : xb.A;
+        float* dX = q.src < 0 ? cx.dcanvas : xb.dA;
+        {   // partial rows [nbw][9][cin]
+            const long n = (long)9 * l.cin;
+            const int nbw = std::min(st.npart, 1024);       // (98 VGPRs: four workgroups per CU -- one resident round)
+            float* region = dw_grad_region(st, nbw, n);
+            PP_LAUNCH("k_tr_dw_bwd_w", k_tr_dw_bwd_w, dim3(nbw), dim3(256), 0, cx.stream, X, (const float*)cx.dD, region, B,
+                      l.in_h, l.in_w, l.out_h, l.out_w, l.cin, l.stride);
+            dw_grad_reduce(st, region, nbw, n, n, st.g(q.dw));
+        }
+        PP_LAUNCH("k_tr_dw_bwd_in", k_tr_dw_bwd_in, dim3(blocks_for((long)B * l.in_h * l.in_w * (l.cin / 4))), dim3(256), 0,
+                  cx.stream, (const float*)cx.dD, st.p(q.dw), dX,
+                  (unsigned)((long)B * l.in_h * l.in_w * (l.cin / 4)), make_div((unsigned)l.in_h), make_div((unsigned)l.in_w),
+                  l.out_h, l.out_w, make_div((unsigned)(l.cin / 4)), l.cin, l.stride, 0);
     }
     // canvas -> pillar features -> PFN
-    if (cpl == 1) pfn_backward<1>(cx, p, L, cx.dcanvas);
-    else if (cpl == 2) pfn_backward<2>(cx, p, L, cx.dcanvas);
-    else pfn_backward<4>(cx, p, L, cx.dcanvas);
-    flush_deferred(cx);     // weight-gradient partial tiles + depthwise-gradient partial rows, one launch
+    if (cpl == 1) pfn_backward<1>(st, p);
+    else if (cpl == 2) pfn_backward<2>(st, p);
+    else pfn_backward<4>(st, p);
+    flush_deferred(st);     // weight-gradient partial tiles + depthwise-gradient partial rows, one launch
     return PP_OK;
 }
