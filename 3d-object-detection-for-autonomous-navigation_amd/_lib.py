@@ -36,6 +36,7 @@ EXPORTS = [
     "pp_train_graph_stats", "pp_stream", "pp_train_fetch_decisions",
     "pp_assign_targets", "pp_train_step_gt_async", "pp_train_step_gt",
     "pp_augment", "pp_train_step_aug_async", "pp_train_step_aug", "pp_augment_selected",
+    "pp_train_set_frozen", "pp_adamw_step_segments_device",
 ]
 
 
@@ -276,6 +277,9 @@ def lib():
     L.pp_augment_selected.argtypes = [vp, vp, i64, ctypes.POINTER(i64)]
     L.pp_adamw_step_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, i64, ctypes.c_float, ctypes.c_float,
                                        ctypes.c_float, ctypes.c_float, ctypes.c_float]
+    L.pp_train_set_frozen.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), i32]
+    L.pp_adamw_step_segments_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, i32, ctypes.c_float,
+                                                ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]
     for name in EXPORTS:
         fn = getattr(L, name)  # raises AttributeError if the symbol is not exported
         if name not in ("pp_last_error", "pp_layer_tag"):

@@ -7,6 +7,8 @@
 //   var -= lr_t * m / (sqrt(v) + epsilon),   lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t),  t = iterations + 1
 // with lr from the ExponentialDecay schedule (host side, optim.py).  One flat float32 buffer per state:
 // HBM-bound, 16 bytes read + 12 written per parameter, 16-byte accesses.
+#include <string.h>
+
 #include "pp_common.h"
 
 __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ w, const float* __restrict__ g,
@@ -52,4 +54,62 @@ void launch_adamw(float* w, const float* g, float* m, float* v, int64_t n, float
     if (n <= 0) return;
     const int64_t blocks = (n + 1023) / 1024;
     hipLaunchKernelGGL(k_adamw, dim3((unsigned)blocks), dim3(256), 0, s, w, g, m, v, n, lr_t, beta1, beta2, eps, wd);
+}
+
+// The same update over the trainable part of the buffer only (frozen layers, trainer.py): `nseg` (offset, size)
+// segments of it, in one launch per PP_ADAMW_SEGS segments; nothing outside them is read or written.  Per element the
+// arithmetic is k_adamw's, operation for operation, so an updated entry is bit-identical to a full-buffer launch's.
+// Segments need not start on a 16-byte boundary: a workgroup owns 1 024 consecutive floats of one segment and a thread
+// every 256th of them (coalesced 4-byte accesses; the update stays HBM-bound).
+#define PP_ADAMW_SEGS 64
+struct AdamwSegs {
+    int64_t off[PP_ADAMW_SEGS], size[PP_ADAMW_SEGS];
+    int block_start[PP_ADAMW_SEGS + 1];
+    int n;
+};
+
+__global__ __launch_bounds__(256) void k_adamw_seg(float* __restrict__ w, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v, AdamwSegs t,
+                                                   float lr_t, float beta1, float beta2, float eps, float wd) {
+    int j = 0;
+    while (j + 1 < t.n && (int)blockIdx.x >= t.block_start[j + 1]) ++j;     // uniform
+    const int64_t base = ((int64_t)blockIdx.x - t.block_start[j]) * 1024;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t e = base + k * 256 + threadIdx.x;
+        if (e >= t.size[j]) break;
+        const int64_t i = t.off[j] + e;
+        const float wv = w[i], gv = g[i];
+        float mv = m[i], vv = v[i];
+        const float wd_w = __fsub_rn(wv, __fmul_rn(wd, wv));
+        mv = __fadd_rn(__fmul_rn(beta1, mv), __fmul_rn(1.f - beta1, gv));
+        vv = __fadd_rn(__fmul_rn(beta2, vv), __fmul_rn(1.f - beta2, __fmul_rn(gv, gv)));
+        w[i] = __fsub_rn(wd_w, __fdiv_rn(__fmul_rn(lr_t, mv), __fadd_rn(__fsqrt_rn(vv), eps)));
+        m[i] = mv;
+        v[i] = vv;
+    }
+}
+
+void launch_adamw_segments(float* w, const float* g, float* m, float* v, const int64_t* seg, int nseg, float lr_t,
+                           float beta1, float beta2, float eps, float wd, hipStream_t s) {
+    for (int done = 0; done < nseg;) {
+        AdamwSegs t;
+        memset(&t, 0, sizeof(t));
+        int blocks = 0;
+        while (done < nseg && t.n < PP_ADAMW_SEGS) {
+            const int64_t size = seg[2 * done + 1];
+            if (size > 0) {
+                t.off[t.n] = seg[2 * done];
+                t.size[t.n] = size;
+                t.block_start[t.n] = blocks;
+                blocks += (int)((size + 1023) / 1024);
+                ++t.n;
+            }
+            ++done;
+        }
+        for (int k = t.n; k <= PP_ADAMW_SEGS; ++k) t.block_start[k] = blocks;
+        if (blocks > 0)
+            PP_LAUNCH("k_adamw_seg", k_adamw_seg, dim3((unsigned)blocks), dim3(256), 0, s, w, g, m, v, t, lr_t, beta1,
+                      beta2, eps, wd);
+    }
 }

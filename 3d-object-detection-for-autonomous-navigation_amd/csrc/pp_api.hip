@@ -182,6 +182,7 @@ struct pp_engine {
             int batch = -1, bucket = -1, zc = 0;
             const void *params = nullptr, *grads = nullptr, *state = nullptr;
             pp_loss_config loss;
+            std::vector<unsigned char> frozen;     // TrainPlan::frozen it was captured with
         } graph[2];
         int last_batch = 0;    // frames of the last step (pp_train_fetch_decisions)
         int graph_state = 0;   // -1: capture failed once, plain launches from then on
@@ -2185,7 +2186,8 @@ int train_step_launch(pp_engine* e, const float* params_dev, float* grads_dev, f
         pp_engine::TrainState::Graph& tg = t->graph[e->in_buf & 1];
         const bool hit = tg.exec != nullptr && tg.exec_bwd != nullptr && tg.batch == batch && tg.bucket == bucket &&
                          tg.zc == (e->zc ? 1 : 0) && tg.params == params_dev && tg.grads == grads_dev &&
-                         tg.state == state_dev && memcmp(&tg.loss, lc, sizeof(pp_loss_config)) == 0;
+                         tg.state == state_dev && memcmp(&tg.loss, lc, sizeof(pp_loss_config)) == 0 &&
+                         tg.frozen == t->plan.frozen;
         if (!hit) {
             if (tg.exec || tg.exec_bwd) {
                 HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -2214,6 +2216,7 @@ int train_step_launch(pp_engine* e, const float* params_dev, float* grads_dev, f
             if (all_ok) {
                 tg.batch = batch; tg.bucket = bucket; tg.zc = e->zc ? 1 : 0;
                 tg.params = params_dev; tg.grads = grads_dev; tg.state = state_dev; tg.loss = *lc;
+                tg.frozen = t->plan.frozen;
                 ++t->n_captures;
             } else {
                 if (tg.exec) (void)hipGraphExecDestroy(tg.exec);
@@ -2482,6 +2485,21 @@ int pp_train_fetch_decisions(pp_handle e, int32_t layer, uint8_t* relu_mask, int
     return PP_OK;
 }
 
+int pp_train_set_frozen(pp_handle e, const char* const* units, int32_t n) {
+    if (!e) return PP_ERR_ARG;
+    if (n < 0 || (n > 0 && !units)) return fail(e, PP_ERR_ARG, "pp_train_set_frozen: bad argument");
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_train_set_frozen: a training step is in flight");
+    int st = train_state(e); if (st) return st;
+    std::vector<std::string> names;
+    for (int32_t i = 0; i < n; ++i) {
+        if (!units[i]) return fail(e, PP_ERR_ARG, "pp_train_set_frozen: unit %d is NULL", i);
+        names.push_back(units[i]);
+    }
+    if (train_plan_freeze(e->train->plan, names) != PP_OK)
+        return fail(e, PP_ERR_ARG, "pp_train_set_frozen: unknown or repeated unit name, or every unit frozen");
+    return PP_OK;
+}
+
 int pp_train_graph_stats(pp_handle e, int32_t* captures, int32_t* replays) {
     if (!e) return PP_ERR_ARG;
     if (captures) *captures = e->train ? e->train->n_captures : 0;
@@ -2495,6 +2513,22 @@ int pp_adamw_step_device(int device, void* stream, float* params, const float* g
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, PP_ERR_HIP, "pp_adamw_step_device: hipSetDevice(%d) failed", device);
     launch_adamw(params, grads, m, v, n, lr_t, beta1, beta2, epsilon, weight_decay, (hipStream_t)stream);
     if (hipGetLastError() != hipSuccess) return fail(nullptr, PP_ERR_HIP, "pp_adamw_step_device: launch failed");
+    return PP_OK;
+}
+
+int pp_adamw_step_segments_device(int device, void* stream, float* params, const float* grads, float* m, float* v,
+                                  const int64_t* segments, int32_t n_segments, float lr_t, float beta1, float beta2,
+                                  float epsilon, float weight_decay) {
+    if (n_segments < 0 || (n_segments > 0 && (!params || !grads || !m || !v || !segments)))
+        return fail(nullptr, PP_ERR_ARG, "pp_adamw_step_segments_device: bad argument");
+    for (int32_t i = 0; i < n_segments; ++i)
+        if (segments[2 * i] < 0 || segments[2 * i + 1] < 0)
+            return fail(nullptr, PP_ERR_ARG, "pp_adamw_step_segments_device: segment %d is negative", i);
+    if (hipSetDevice(device) != hipSuccess)
+        return fail(nullptr, PP_ERR_HIP, "pp_adamw_step_segments_device: hipSetDevice(%d) failed", device);
+    launch_adamw_segments(params, grads, m, v, segments, n_segments, lr_t, beta1, beta2, epsilon, weight_decay,
+                          (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, PP_ERR_HIP, "pp_adamw_step_segments_device: launch failed");
     return PP_OK;
 }
 

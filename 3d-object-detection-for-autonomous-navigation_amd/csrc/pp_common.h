@@ -293,6 +293,9 @@ int launch_head_loss(const LossParams& p, hipStream_t s);   // 0 or PP_ERR_UNSUP
 // optim.hip: AdamW update of one flat parameter buffer
 void launch_adamw(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1, float beta2,
                   float eps, float wd, hipStream_t s);
+// ... of the (offset, size) segments seg[2 * i], seg[2 * i + 1] of it only (host array of nseg pairs)
+void launch_adamw_segments(float* w, const float* g, float* m, float* v, const int64_t* seg, int nseg, float lr_t,
+                           float beta1, float beta2, float eps, float wd, hipStream_t s);
 
 // rotate_iou.hip: rotated-box overlaps of the AP evaluator
 void launch_riou_corners(const float* boxes, int64_t n, float* corners, hipStream_t s);

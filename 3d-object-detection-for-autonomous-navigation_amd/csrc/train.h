@@ -2,6 +2,7 @@
 #pragma once
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "pp_common.h"
@@ -38,6 +39,13 @@ struct TrainLayer {
     int cat_off;              // transposed convolution: its channels in the concatenation
     long pw16_off;            // offset (16-bit words) of its split forward kernel in TrainCtx::pw16
     std::string fused_tag, fwd_tag, pair_tag;   // profiler names: k_sep_u_tr:block1.0, k_tr_gemm2:fwd.block1.0, ...
+    std::string dgrad_tag, wgrad_tag;           // ... the input- / weight-gradient product alone (frozen layers and
+                                                // layers with nothing trainable upstream): k_tr_gemm2:dgrad.block2.0
+    // freeze (train_plan_freeze): a frozen layer's BatchNorm runs on its moving statistics, and none of its tensors gets
+    // a gradient; the gradient still passes through it to trainable layers upstream
+    bool frozen = false;
+    bool needs_dx = true;     // a trainable unit lies upstream of this layer's input: its input gradient is wanted
+    bool needs_bwd = true;    // frozen == false or needs_dx: the layer has a backward step at all
 };
 
 // Built once per handle from the shape and the engine's maximum batch: the layout, the layers, and the buffer sizes
@@ -49,6 +57,16 @@ struct TrainPlan {
     int64_t pfn_w = 0, pfn_gamma = 0, pfn_beta = 0, pfn_mean = 0, pfn_var = 0;
     int64_t box_k = 0, box_b = 0, cls_k = 0, cls_b = 0, dir_k = 0, dir_b = 0;   // without a direction head: dir = box
     bool unsupported = false;
+    // freeze units (train_plan_freeze): "pfn", "rpn/block<b>/<j>", "rpn/deconv<b>", "rpn/conv_box", "rpn/conv_cls",
+    // "rpn/conv_dir_cls"; frozen[u] per unit, in that order (the graph key of pp_train_step)
+    std::vector<std::string> units;
+    std::vector<unsigned char> frozen;
+    bool any_frozen = false;
+    bool pfn_frozen = false;
+    bool head_frozen[3] = {false, false, false};        // box, cls, dir
+    bool heads_wgrad = true;  // some head is trainable
+    bool heads_dgrad = true;  // some layer in front of the heads has a backward step (dcat is wanted)
+    std::vector<std::pair<int64_t, int64_t>> frozen_params;   // (offset, size) ranges of frozen parameters, merged
     bool fused = false;       // the fused forward kernels are available (the split-weight table holds every layer)
     long pw16_words = 0;
     size_t max_z = 1, max_d = 1, part_floats = 0;
@@ -121,6 +139,9 @@ struct TrainCtx {
 };
 
 TrainPlan train_plan(const TrainShape& s, int max_batch);
+// Freeze the named units (none: train everything).  PP_ERR_ARG for an unknown or repeated name, or when nothing would be
+// left to train; the plan is unchanged then.
+int train_plan_freeze(TrainPlan& plan, const std::vector<std::string>& units);
 // forward (training mode) + loss + backward for `batch` resident, voxelised frames; grads overwritten, state updated
 int train_step(const TrainCtx& cx, const TrainShape& s, const TrainPlan& plan, const float* params, float* grads,
                float* state, int batch, const LossParams& loss, int phase = 3);

@@ -29,6 +29,9 @@
 // BatchNorm feeds the unbiased variance, the PFN's rank-3 BatchNorm the biased one).  The PFN statistics run
 // over ALL P * T rows of the reference's padded tensor: the zero rows contribute nothing to the sums but count
 // in N, and a padded row that wins the max receives the gradient (it only reaches beta / gamma / the statistics).
+// Frozen units (train_plan_freeze; the reference's set_trainable, train.py:62-113) behave as Keras layers with
+// trainable = False: BatchNorm from the moving statistics (k_tr_bn_frozen, no update), no gradient of their own, the
+// input gradient passed on only where a trainable unit lies in front (k_tr_bn_bwd_frozen + the input-gradient product).
 #include <assert.h>
 #include <math.h>
 #include <stdlib.h>
@@ -969,9 +972,12 @@ __global__ __launch_bounds__(256) void k_tr_dw_bwd_in(const float* __restrict__ 
 // A workgroup owns a CONTIGUOUS range of output pixels (the 3x3 windows of neighbouring pixels share their loads in
 // L1 / L2); a thread owns 4 channels (16-byte loads) of every (256 / (C / 4))-th pixel of the range; the per-thread
 // sums of the 9 taps meet in LDS and leave one partial row part[blk][9][C]; k_tr_reduce adds the rows in order.
+// XBN: X is a pre-BatchNorm map read through its coefficient table, x = relu(z * sc + sh) (stride 1: a trainable layer
+// behind a frozen in-block layer, whose backward does not run the fused k_tr_dw_bwd)
+template <bool XBN = false>
 __global__ __launch_bounds__(256) void k_tr_dw_bwd_w(const float* __restrict__ X, const float* __restrict__ dD,
                                                      float* __restrict__ part, int B, int ih, int iw, int oh, int ow,
-                                                     int C, int S) {
+                                                     int C, int S, const float4* __restrict__ xcoef = nullptr) {
     __shared__ float4 sred[3 * 256];                     // three taps at a time: 12 KB, eight workgroups per CU (the
                                                          // kernel is a few memory round trips per thread: it lives on
                                                          // resident waves; 36 KB for all nine taps allowed four)
@@ -984,6 +990,11 @@ __global__ __launch_bounds__(256) void k_tr_dw_bwd_w(const float* __restrict__ X
     float4 acc[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 cf[4];
+    if (XBN) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cf[j] = xcoef[4 * q + j];
+    }
     // (b, y, x) of the thread's first pixel by division once, then advanced by nps pixels per iteration
     int x = 0, y = 0, b = 0;
     if (p0 + ps < p1) {
@@ -1008,6 +1019,13 @@ __global__ __launch_bounds__(256) void k_tr_dw_bwd_w(const float* __restrict__ X
                 const bool ok = ((unsigned)yy < (unsigned)ih) & ((unsigned)xx < (unsigned)iw);
                 v[dy * 3 + dx] = *reinterpret_cast<const float4*>(xb + ((size_t)(ok ? yy : 0) * iw + (ok ? xx : 0)) * C);
                 m[dy * 3 + dx] = ok ? 1.f : 0.f;
+            }
+        }
+        if (XBN) {
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                v[t].x = fmaxf(fmaf(v[t].x, cf[0].x, cf[0].y), 0.f); v[t].y = fmaxf(fmaf(v[t].y, cf[1].x, cf[1].y), 0.f);
+                v[t].z = fmaxf(fmaf(v[t].z, cf[2].x, cf[2].y), 0.f); v[t].w = fmaxf(fmaf(v[t].w, cf[3].x, cf[3].y), 0.f);
             }
         }
 #pragma unroll
@@ -1185,6 +1203,28 @@ __global__ __launch_bounds__(256) void k_tr_bn_finalize(const float* __restrict_
     }
 }
 
+// BatchNorm of a frozen layer (inference mode inside the training step, as Keras runs a layer with trainable = False):
+// the coefficient table and the statistics from the moving statistics -- what k_tr_bn_finalize writes from the batch,
+// without touching the moving statistics.  One workgroup per layer of the table, all frozen layers in one launch at the
+// start of the step (their inputs are the parameters and the state buffer, which the step does not change).
+//   stats[c] = (moving_mean, 1/sqrt(moving_var + eps)),  coef[c] = (sc, sh, inv, -mean * inv), sc = inv * gamma
+struct FrozenBnJob { const float *gamma, *beta, *mean, *var; float* stats; float4* coef; int C; };
+#define TR_FROZEN_JOBS 40
+struct FrozenBnTable { int n; FrozenBnJob job[TR_FROZEN_JOBS]; };
+__global__ __launch_bounds__(256) void k_tr_bn_frozen(FrozenBnTable t) {
+    const FrozenBnJob& J = t.job[blockIdx.x];
+    for (int c = threadIdx.x; c < J.C; c += 256) {
+        const float mean = J.mean[c];
+        const float inv = 1.0f / sqrtf(J.var[c] + TR_EPS);
+        J.stats[2 * c] = mean;
+        J.stats[2 * c + 1] = inv;
+        if (J.coef != nullptr) {
+            const float sc = inv * J.gamma[c];
+            J.coef[c] = make_float4(sc, fmaf(-mean, sc, J.beta[c]), inv, -mean * inv);
+        }
+    }
+}
+
 // parity tap: the ReLU decisions of a layer as the backward kernels take them (k_tr_bn_bwd_reduce / _apply, k_tr_dw_bwd)
 __global__ __launch_bounds__(256) void k_tr_relu_mask(const float* __restrict__ Z, const float4* __restrict__ coef, long n, int C,
                                                       unsigned char* __restrict__ mask) {
@@ -1316,6 +1356,28 @@ __global__ __launch_bounds__(256) void k_tr_bn_bwd_apply(const float* __restrict
         const float zh = fmaf(zz[j], q.z, q.w);
         const float g = (act > 0.f) ? dd[j] : 0.f;
         o[j] = q.x * (g - mm1[j] * inv_n - zh * (mm2[j] * inv_n));
+    }
+    *reinterpret_cast<float4*>(dZ + (size_t)i * 4) = make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// backward of BN + ReLU of a frozen layer (inference mode: mean and variance are constants): one elementwise pass,
+// dZ[r][c] = dA * (act > 0) * sc -- no sums, no gamma / beta gradient
+__global__ __launch_bounds__(256) void k_tr_bn_bwd_frozen(const float* __restrict__ dA, int ld, int co_off, RowMap rm,
+                                                          const float* __restrict__ Z, long rows, int C,
+                                                          const float4* __restrict__ coef, float* __restrict__ dZ) {
+    const unsigned c4n = (unsigned)C >> 2;                   // C is a power of two (train_step checks)
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;      // (row, channel quad)
+    if ((long)i >= rows * (long)c4n) return;
+    const int c = (int)(i & (c4n - 1u)) * 4;
+    const long r = (long)(i / c4n);
+    const float4 z4 = *reinterpret_cast<const float4*>(Z + (size_t)i * 4);
+    const float4 d4 = *reinterpret_cast<const float4*>(dA + (size_t)map_row(rm, r) * ld + co_off + c);
+    const float zz[4] = {z4.x, z4.y, z4.z, z4.w}, dd[4] = {d4.x, d4.y, d4.z, d4.w};
+    float o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float4 q = coef[c + j];
+        o[j] = (fmaf(zz[j], q.x, q.y) > 0.f) ? dd[j] * q.x : 0.f;
     }
     *reinterpret_cast<float4*>(dZ + (size_t)i * 4) = make_float4(o[0], o[1], o[2], o[3]);
 }
@@ -2017,18 +2079,19 @@ __global__ __launch_bounds__(256) void k_tr_unpack_head_grads(const float* __res
                                                               int CC, int nb, int nc, int nd, float* __restrict__ gkb,
                                                               float* __restrict__ gkc, float* __restrict__ gkd,
                                                               float* __restrict__ gbb, float* __restrict__ gbc,
-                                                              float* __restrict__ gbd) {
+                                                              float* __restrict__ gbd, int skip) {
+    // skip: bit h set = head h (box, cls, dir) is frozen, its gradient is not written
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < CC * PP_HEAD_COLS) {
         const int cc = i / PP_HEAD_COLS, col = i % PP_HEAD_COLS;
-        if (col < nb) gkb[cc * nb + col] = dW[i];
-        else if (col < nb + nc) gkc[cc * nc + col - nb] = dW[i];
-        else if (col < nb + nc + nd) gkd[cc * nd + col - nb - nc] = dW[i];
+        if (col < nb) { if (!(skip & 1)) gkb[cc * nb + col] = dW[i]; }
+        else if (col < nb + nc) { if (!(skip & 2)) gkc[cc * nc + col - nb] = dW[i]; }
+        else if (col < nb + nc + nd) { if (!(skip & 4)) gkd[cc * nd + col - nb - nc] = dW[i]; }
     }
     if (i < PP_HEAD_COLS) {
-        if (i < nb) gbb[i] = dbias[i];
-        else if (i < nb + nc) gbc[i - nb] = dbias[i];
-        else if (i < nb + nc + nd) gbd[i - nb - nc] = dbias[i];
+        if (i < nb) { if (!(skip & 1)) gbb[i] = dbias[i]; }
+        else if (i < nb + nc) { if (!(skip & 2)) gbc[i - nb] = dbias[i]; }
+        else if (i < nb + nc + nd) { if (!(skip & 4)) gbd[i - nb - nc] = dbias[i]; }
     }
 }
 
@@ -2079,6 +2142,7 @@ TrainPlan train_plan(const TrainShape& s, int max_batch) {
     };
     pl.pfn_w = P("pfn/dense/kernel", (int64_t)s.FA * s.C);
     BN("pfn/bn", s.C, pl.pfn_gamma, pl.pfn_beta, pl.pfn_mean, pl.pfn_var);
+    pl.units.push_back("pfn");
     // shapes the training kernels are written for (the reduction kernels: channel counts)
     pl.unsupported = s.C > 256 || s.C % 4 != 0 || s.FA > 10;
     size_t m = (size_t)2 * 512;      // floats of a row of TrainCtx::part
@@ -2096,6 +2160,8 @@ TrainPlan train_plan(const TrainShape& s, int max_batch) {
         q.kind = l.kind; q.block = block; q.index = index; q.layer = (int)i;
         const std::string pre = "rpn/" + layer_name(l.kind, block, index, '/'), tag = layer_name(l.kind, block, index, '.');
         q.fused_tag = "k_sep_u_tr:" + tag; q.fwd_tag = "k_tr_gemm2:fwd." + tag; q.pair_tag = "k_tr_gemm2:pair." + tag;
+        q.dgrad_tag = "k_tr_gemm2:dgrad." + tag; q.wgrad_tag = "k_tr_gemm2:wgrad." + tag;
+        pl.units.push_back(pre);
         // every layer reads the last separable layer's output: its activation tensor, or its pre-BatchNorm map
         q.src = last_sep;
         q.src_z = last_sep >= 0 && !pl.layers[last_sep].keeps_a;
@@ -2142,7 +2208,57 @@ TrainPlan train_plan(const TrainShape& s, int max_batch) {
     pl.cls_k = P("rpn/conv_cls/kernel", (int64_t)s.CC * nc); pl.cls_b = P("rpn/conv_cls/bias", nc);
     pl.dir_k = pl.box_k; pl.dir_b = pl.box_b;
     if (nd) { pl.dir_k = P("rpn/conv_dir_cls/kernel", (int64_t)s.CC * nd); pl.dir_b = P("rpn/conv_dir_cls/bias", nd); }
+    pl.units.push_back("rpn/conv_box");
+    pl.units.push_back("rpn/conv_cls");
+    if (nd) pl.units.push_back("rpn/conv_dir_cls");
+    train_plan_freeze(pl, {});
     return pl;
+}
+
+// the freeze unit of a tensor of the layout: "pfn", "rpn/block2/3", "rpn/deconv1", "rpn/conv_box", ...
+static std::string unit_of(const std::string& name) {
+    if (name.compare(0, 4, "pfn/") == 0) return "pfn";
+    const size_t a = name.find('/'), b = name.find('/', a + 1);
+    if (name.compare(a + 1, 5, "block") == 0) return name.substr(0, name.find('/', b + 1));
+    return name.substr(0, b);
+}
+
+int train_plan_freeze(TrainPlan& pl, const std::vector<std::string>& names) {
+    std::vector<unsigned char> fz(pl.units.size(), 0);
+    for (const std::string& n : names) {
+        const auto it = std::find(pl.units.begin(), pl.units.end(), n);
+        if (it == pl.units.end() || fz[it - pl.units.begin()]) return PP_ERR_ARG;
+        fz[it - pl.units.begin()] = 1;
+    }
+    if (!names.empty() && names.size() == pl.units.size()) return PP_ERR_ARG;    // nothing left to train
+    pl.frozen = fz;
+    pl.any_frozen = !names.empty();
+    pl.pfn_frozen = fz[0] != 0;
+    const size_t L = pl.layers.size();
+    // a layer's input gradient is wanted when its source, or anything in front of the source, is trainable; a layer
+    // with neither a trainable tensor nor such a source has no backward step
+    for (size_t j = 0; j < L; ++j) {
+        TrainLayer& q = pl.layers[j];
+        q.frozen = fz[1 + j] != 0;
+        q.needs_dx = q.src < 0 ? !pl.pfn_frozen : pl.layers[q.src].needs_bwd;
+        q.needs_bwd = !q.frozen || q.needs_dx;
+    }
+    pl.heads_wgrad = false;
+    for (int h = 0; h < 3; ++h) {
+        pl.head_frozen[h] = 1 + L + h < fz.size() && fz[1 + L + h];
+        if (1 + L + h < fz.size() && !fz[1 + L + h]) pl.heads_wgrad = true;
+    }
+    pl.heads_dgrad = false;
+    for (const TrainLayer& q : pl.layers) pl.heads_dgrad |= q.kind == LAYER_DECONV && q.needs_bwd;
+    pl.frozen_params.clear();
+    for (const TrainEntry& t : pl.layout) {
+        if (t.is_state || !fz[std::find(pl.units.begin(), pl.units.end(), unit_of(t.name)) - pl.units.begin()]) continue;
+        if (!pl.frozen_params.empty() && pl.frozen_params.back().first + pl.frozen_params.back().second == t.offset)
+            pl.frozen_params.back().second += t.size;
+        else
+            pl.frozen_params.push_back({t.offset, t.size});
+    }
+    return PP_OK;
 }
 
 namespace {
@@ -2237,10 +2353,12 @@ void col_reduce(const TrainStepState& st, int C, float* sums, float* dup0 = null
 // block-final layers and the transposed convolutions); the in-block consumers evaluate it from Z and the table
 // stat_tiles > 0: the product that wrote Z left centred per-row-tile partials in cx.stat_part ([stat_tiles][2][C * ntaps],
 // then the tiles' row counts)
+// (a frozen layer: its table was filled from the moving statistics at the start of the step, k_tr_bn_frozen)
 void bn_relu_forward(const TrainStepState& st, const TrainLayer& q, const TrainLayerBuf& tb, long rows, int C, float* A,
                      int ld, int co_off, RowMap rm, int stat_tiles, int ntaps) {
     const TrainCtx& cx = st.cx;
-    if (stat_tiles > 0) {
+    if (q.frozen) {
+    } else if (stat_tiles > 0) {
         bn_finalize(st, cx.stat_part, stat_tiles, C, (float)rows, nullptr, 0.99f, 1, tb.stats, st.s(q.mean), st.s(q.var),
                     ntaps, st.p(q.gamma), st.p(q.beta), tb.coef);
     } else {
@@ -2296,7 +2414,10 @@ void pfn_forward(const TrainStepState& st, const PfnT& p) {
               cx.pfn_prefix);
     const int nlin = pfn_blocks(st, CPL == 4 ? 4 : 7), nmax = pfn_blocks(st, CPL == 4 ? 4 : 5);
     PP_LAUNCH("k_tr_pfn_lin", (k_tr_pfn_lin<CPL>), dim3(nlin), dim3(256), 0, cx.stream, p, cx.part);
-    bn_finalize(st, cx.part, nlin, p.C, 0.f, cx.pfn_nrows, 0.01f, 0, cx.pfn_stats, st.s(pl.pfn_mean), st.s(pl.pfn_var), 1);
+    // (frozen: the statistics came from the moving ones, k_tr_bn_frozen; the launch above still writes the pillar
+    // records, its partial sums go unread)
+    if (!pl.pfn_frozen)
+        bn_finalize(st, cx.part, nlin, p.C, 0.f, cx.pfn_nrows, 0.01f, 0, cx.pfn_stats, st.s(pl.pfn_mean), st.s(pl.pfn_var), 1);
     PP_LAUNCH("k_tr_pfn_max", (k_tr_pfn_max<CPL>), dim3(nmax), dim3(256), 0, cx.stream, p,
               (const float*)cx.pfn_stats, st.p(pl.pfn_gamma), st.p(pl.pfn_beta), cx.pfn_feat, cx.pfn_arg);
 }
@@ -2360,6 +2481,25 @@ int train_step(const TrainCtx& cx, const TrainShape& s, const TrainPlan& plan, c
 
     // ---------------- forward ----------------
     if (phase & 1) {
+    if (plan.any_frozen) {   // BatchNorm of the frozen layers from their moving statistics
+        FrozenBnTable t;
+        memset(&t, 0, sizeof(t));
+        auto flush = [&]() {
+            if (t.n) PP_LAUNCH("k_tr_bn_frozen", k_tr_bn_frozen, dim3((unsigned)t.n), dim3(256), 0, cx.stream, t);
+            t.n = 0;
+        };
+        if (plan.pfn_frozen)
+            t.job[t.n++] = FrozenBnJob{st.p(plan.pfn_gamma), st.p(plan.pfn_beta), st.s(plan.pfn_mean), st.s(plan.pfn_var),
+                                       cx.pfn_stats, nullptr, s.C};
+        for (size_t j = 0; j < Ls.size(); ++j) {
+            if (!Ls[j].frozen) continue;
+            if (t.n == TR_FROZEN_JOBS) flush();
+            const TrainLayer& q = Ls[j];
+            t.job[t.n++] = FrozenBnJob{st.p(q.gamma), st.p(q.beta), st.s(q.mean), st.s(q.var), cx.lbuf[j].stats,
+                                       cx.lbuf[j].coef, s.layers[q.layer].cout};
+        }
+        flush();
+    }
     if (cpl == 1) pfn_forward<1>(st, p);
     else if (cpl == 2) pfn_forward<2>(st, p);
     else pfn_forward<4>(st, p);
@@ -2465,18 +2605,27 @@ int train_step(const TrainCtx& cx, const TrainShape& s, const TrainPlan& plan, c
     if (rc) return rc;
 
     // ---------------- backward ----------------
+    // frozen tensors: their gradient entries are 0 (nothing below writes them; the all-reduce and the optimizer see
+    // the whole flat buffer)
+    for (const auto& r : plan.frozen_params)
+        PP_LAUNCH("k_tr_fill", k_tr_fill, dim3(blocks_for(r.second)), dim3(256), 0, cx.stream, st.g(r.first), (long)r.second, 0.f);
     // heads: dWh = cat^T . dhead, dbias = column sums, dcat = dhead . Wh^T
-    tr_gemm(st, GemmCall{"k_tr_gemm2:wgrad.heads", cx.cat, 1, s.CC, cx.dhead, PP_HEAD_COLS, 1, cx.dhead_w, PP_HEAD_COLS, s.CC,
-                         PP_HEAD_COLS, (int)px, nullptr, 0, wgrad_split(st, s.CC, PP_HEAD_COLS, (int)px), nullptr, false});
-    // (reduced at once: k_tr_unpack_head_grads reads it next)
-    PP_LAUNCH("k_tr_colstats", k_tr_colstats, dim3(st.npart), dim3(256), 0, cx.stream, (const float*)cx.dhead, px, PP_HEAD_COLS,
-              cx.part);
-    col_reduce(st, PP_HEAD_COLS, cx.dhead_b);   // [0][c] = column sums (the [1][c] half is unused)
-    PP_LAUNCH("k_tr_unpack_head_grads", k_tr_unpack_head_grads, dim3(blocks_for((long)s.CC * PP_HEAD_COLS)), dim3(256), 0,
-              cx.stream, (const float*)cx.dhead_w, (const float*)cx.dhead_b, s.CC, nb, nc, nd, st.g(plan.box_k),
-              st.g(plan.cls_k), st.g(plan.dir_k), st.g(plan.box_b), st.g(plan.cls_b), st.g(plan.dir_b));
-    tr_gemm(st, GemmCall{"k_tr_gemm2:dgrad.heads", cx.dhead, PP_HEAD_COLS, 1, cx.head_w, 1, PP_HEAD_COLS, cx.dcat, s.CC,
-                         (int)px, s.CC, PP_HEAD_COLS, nullptr, 0, 1, nullptr, false});
+    if (plan.heads_wgrad) {
+        tr_gemm(st, GemmCall{"k_tr_gemm2:wgrad.heads", cx.cat, 1, s.CC, cx.dhead, PP_HEAD_COLS, 1, cx.dhead_w, PP_HEAD_COLS,
+                             s.CC, PP_HEAD_COLS, (int)px, nullptr, 0, wgrad_split(st, s.CC, PP_HEAD_COLS, (int)px), nullptr,
+                             false});
+        // (reduced at once: k_tr_unpack_head_grads reads it next)
+        PP_LAUNCH("k_tr_colstats", k_tr_colstats, dim3(st.npart), dim3(256), 0, cx.stream, (const float*)cx.dhead, px,
+                  PP_HEAD_COLS, cx.part);
+        col_reduce(st, PP_HEAD_COLS, cx.dhead_b);   // [0][c] = column sums (the [1][c] half is unused)
+        const int skip = (plan.head_frozen[0] ? 1 : 0) | (plan.head_frozen[1] ? 2 : 0) | (plan.head_frozen[2] ? 4 : 0);
+        PP_LAUNCH("k_tr_unpack_head_grads", k_tr_unpack_head_grads, dim3(blocks_for((long)s.CC * PP_HEAD_COLS)), dim3(256),
+                  0, cx.stream, (const float*)cx.dhead_w, (const float*)cx.dhead_b, s.CC, nb, nc, nd, st.g(plan.box_k),
+                  st.g(plan.cls_k), st.g(plan.dir_k), st.g(plan.box_b), st.g(plan.cls_b), st.g(plan.dir_b), skip);
+    }
+    if (plan.heads_dgrad)
+        tr_gemm(st, GemmCall{"k_tr_gemm2:dgrad.heads", cx.dhead, PP_HEAD_COLS, 1, cx.head_w, 1, PP_HEAD_COLS, cx.dcat, s.CC,
+                             (int)px, s.CC, PP_HEAD_COLS, nullptr, 0, 1, nullptr, false});
 
     // layers in reverse: the gradient of a block's output arrives from the next block's first layer (stored by its
     // depthwise backward) and from its own transposed convolution (accumulated on top)
@@ -2489,28 +2638,55 @@ int train_step(const TrainCtx& cx, const TrainShape& s, const TrainPlan& plan, c
         const LayerDesc& l = s.layers[q.layer];
         const TrainLayerBuf& tb = cx.lbuf[j];
         const TrainLayerBuf& xb = cx.lbuf[std::max(q.src, 0)];    // (q.src < 0: the canvas)
+        // frozen: BatchNorm backward in inference mode and the input gradient alone; trainable with nothing trainable
+        // in front: the weight gradients alone; neither: nothing (train_plan_freeze)
+        if (!q.needs_bwd) continue;
         if (q.kind == LAYER_DECONV) {
             const long m = (long)B * l.in_h * l.in_w;
             const int N = l.k * l.k * l.cout;
-            bn_relu_backward(st, q, tb, cx.dcat, s.CC, q.cat_off, RowMap{l.k, l.in_h, l.in_w}, m * l.k * l.k, l.cout, cx.dZ);
+            const RowMap rm{l.k, l.in_h, l.in_w};
+            if (q.frozen)
+                PP_LAUNCH("k_tr_bn_bwd_frozen", k_tr_bn_bwd_frozen, dim3(blocks_for(m * l.k * l.k * (l.cout / 4))), dim3(256), 0,
+                          cx.stream, (const float*)cx.dcat, s.CC, q.cat_off, rm, (const float*)tb.Z, m * l.k * l.k, l.cout,
+                          (const float4*)tb.coef, cx.dZ);
+            else
+                bn_relu_backward(st, q, tb, cx.dcat, s.CC, q.cat_off, rm, m * l.k * l.k, l.cout, cx.dZ);
             // dK[n][cin] = dZs^T . X     dX[m][cin] (+)= dZs . K
-            tr_gemm_pair(st,
-                         GemmCall{q.pair_tag.c_str(), cx.dZ, 1, N, xb.A, l.cin, 1, st.g(q.pw), l.cin, N, l.cin, (int)m,
-                                  nullptr, 0, wgrad_split(st, N, l.cin, (int)m), nullptr, true},
-                         GemmCall{q.pair_tag.c_str(), cx.dZ, N, 1, st.p(q.pw), l.cin, 1, xb.dA, l.cin, (int)m, l.cin, N,
-                                  nullptr, q.accumulate ? 1 : 0, dgrad_split((int)m, l.cin, N), nullptr, false});
+            GemmCall w{q.pair_tag.c_str(), cx.dZ, 1, N, xb.A, l.cin, 1, st.g(q.pw), l.cin, N, l.cin, (int)m,
+                       nullptr, 0, wgrad_split(st, N, l.cin, (int)m), nullptr, true};
+            GemmCall d{q.pair_tag.c_str(), cx.dZ, N, 1, st.p(q.pw), l.cin, 1, xb.dA, l.cin, (int)m, l.cin, N,
+                       nullptr, q.accumulate ? 1 : 0, dgrad_split((int)m, l.cin, N), nullptr, false};
+            if (!q.frozen && q.needs_dx) {
+                tr_gemm_pair(st, w, d);
+            } else if (q.needs_dx) {
+                d.tag = q.dgrad_tag.c_str();
+                tr_gemm(st, d);
+            } else {
+                w.tag = q.wgrad_tag.c_str();
+                tr_gemm(st, w);
+            }
             continue;
         }
         const long rows = (long)B * l.out_h * l.out_w;
-        bn_relu_backward(st, q, tb, tb.dA, l.cout, 0, ident, rows, l.cout, cx.dZ, sums_part, sums_pstride, sums_nparts);
+        // dWp[cin][cout] = D^T . dZ      dD[rows][cin] = dZ . Wp^T   (dD: the depthwise kernel gradient needs it too)
+        GemmCall w{q.pair_tag.c_str(), tb.D, 1, l.cin, cx.dZ, l.cout, 1, st.g(q.pw), l.cout, l.cin, l.cout,
+                   (int)rows, nullptr, 0, wgrad_split(st, l.cin, l.cout, (int)rows), nullptr, true};
+        GemmCall d{q.pair_tag.c_str(), cx.dZ, l.cout, 1, st.p(q.pw), 1, l.cout, cx.dD, l.cin, (int)rows, l.cin,
+                   l.cout, nullptr, 0, 1, nullptr, false};
+        if (q.frozen) {
+            assert(sums_part == nullptr);
+            PP_LAUNCH("k_tr_bn_bwd_frozen", k_tr_bn_bwd_frozen, dim3(blocks_for(rows * (l.cout / 4))), dim3(256), 0, cx.stream,
+                      (const float*)tb.dA, l.cout, 0, ident, (const float*)tb.Z, rows, l.cout, (const float4*)tb.coef, cx.dZ);
+            d.tag = q.dgrad_tag.c_str();
+            tr_gemm(st, d);
+        } else {
+            bn_relu_backward(st, q, tb, tb.dA, l.cout, 0, ident, rows, l.cout, cx.dZ, sums_part, sums_pstride, sums_nparts);
+            tr_gemm_pair(st, w, d);
+        }
         sums_part = nullptr;
-        // dWp[cin][cout] = D^T . dZ      dD[rows][cin] = dZ . Wp^T
-        tr_gemm_pair(st,
-                     GemmCall{q.pair_tag.c_str(), tb.D, 1, l.cin, cx.dZ, l.cout, 1, st.g(q.pw), l.cout, l.cin, l.cout,
-                              (int)rows, nullptr, 0, wgrad_split(st, l.cin, l.cout, (int)rows), nullptr, true},
-                     GemmCall{q.pair_tag.c_str(), cx.dZ, l.cout, 1, st.p(q.pw), 1, l.cout, cx.dD, l.cin, (int)rows, l.cin,
-                              l.cout, nullptr, 0, 1, nullptr, false});
-        if (sp.layers[j].dw_bwd_fused) {
+        // the fused depthwise backward also leaves the layer before's BatchNorm-backward sums: for a trainable layer
+        // behind a trainable one only
+        if (sp.layers[j].dw_bwd_fused && !q.frozen && !Ls[q.src].frozen) {
             // one pass: depthwise kernel gradient, input gradient, and the layer before's BatchNorm-backward sums;
             // partial rows [nblk][11][cin] (the two sum rows are read by the layer before's col_reduce before anything
             // else writes the shared scratch)
@@ -2527,24 +2703,31 @@ int train_step(const TrainCtx& cx, const TrainShape& s, const TrainPlan& plan, c
             sums_nparts = nblk;
             continue;
         }
-        // the input and its gradient: the layer before's activation (the previous block's output) or the canvas
-        const float* X = q.src < 0 ? cx.canvas : xb.A;
+        // the input and its gradient: the layer before's activation (the previous block's output) or the canvas; an
+        // in-block layer's pre-BatchNorm map (behind a frozen in-block layer) is read through its coefficient table
+        const float* X = q.src < 0 ? cx.canvas : (q.src_z ? xb.Z : xb.A);
         float* dX = q.src < 0 ? cx.dcanvas : xb.dA;
-        {   // partial rows [nbw][9][cin]
+        if (!q.frozen) {   // partial rows [nbw][9][cin]
             const long n = (long)9 * l.cin;
             const int nbw = std::min(st.npart, 1024);       // (98 VGPRs: four workgroups per CU -- one resident round)
             float* region = dw_grad_region(st, nbw, n);
-            PP_LAUNCH("k_tr_dw_bwd_w", k_tr_dw_bwd_w, dim3(nbw), dim3(256), 0, cx.stream, X, (const float*)cx.dD, region, B,
-                      l.in_h, l.in_w, l.out_h, l.out_w, l.cin, l.stride);
+            if (q.src_z)
+                PP_LAUNCH("k_tr_dw_bwd_w", k_tr_dw_bwd_w<true>, dim3(nbw), dim3(256), 0, cx.stream, X, (const float*)cx.dD,
+                          region, B, l.in_h, l.in_w, l.out_h, l.out_w, l.cin, l.stride, (const float4*)xb.coef);
+            else
+                PP_LAUNCH("k_tr_dw_bwd_w", k_tr_dw_bwd_w<false>, dim3(nbw), dim3(256), 0, cx.stream, X, (const float*)cx.dD,
+                          region, B, l.in_h, l.in_w, l.out_h, l.out_w, l.cin, l.stride, (const float4*)nullptr);
             dw_grad_reduce(st, region, nbw, n, n, st.g(q.dw));
         }
-        PP_LAUNCH("k_tr_dw_bwd_in", k_tr_dw_bwd_in, dim3(blocks_for((long)B * l.in_h * l.in_w * (l.cin / 4))), dim3(256), 0,
-                  cx.stream, (const float*)cx.dD, st.p(q.dw), dX,
-                  (unsigned)((long)B * l.in_h * l.in_w * (l.cin / 4)), make_div((unsigned)l.in_h), make_div((unsigned)l.in_w),
-                  l.out_h, l.out_w, make_div((unsigned)(l.cin / 4)), l.cin, l.stride, 0);
+        if (q.needs_dx)
+            PP_LAUNCH("k_tr_dw_bwd_in", k_tr_dw_bwd_in, dim3(blocks_for((long)B * l.in_h * l.in_w * (l.cin / 4))), dim3(256),
+                      0, cx.stream, (const float*)cx.dD, st.p(q.dw), dX,
+                      (unsigned)((long)B * l.in_h * l.in_w * (l.cin / 4)), make_div((unsigned)l.in_h),
+                      make_div((unsigned)l.in_w), l.out_h, l.out_w, make_div((unsigned)(l.cin / 4)), l.cin, l.stride, 0);
     }
     // canvas -> pillar features -> PFN
-    if (cpl == 1) pfn_backward<1>(st, p);
+    if (plan.pfn_frozen) {
+    } else if (cpl == 1) pfn_backward<1>(st, p);
     else if (cpl == 2) pfn_backward<2>(st, p);
     else pfn_backward<4>(st, p);
     flush_deferred(st);     // weight-gradient partial tiles + depthwise-gradient partial rows, one launch

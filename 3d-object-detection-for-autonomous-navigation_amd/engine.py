@@ -478,6 +478,12 @@ class Engine:
             out.append((name.value.decode(), off.value, size.value, bool(st.value)))
         return out, npar.value, nst.value
 
+    def train_set_frozen(self, units):
+        """Freeze the named units for the following training steps (pp_train_set_frozen; () unfreezes everything)."""
+        names = [u.encode() for u in units]
+        arr = (ctypes.c_char_p * max(1, len(names)))(*names)
+        self._check(self._lib.pp_train_set_frozen(self._h, arr, len(names)), "pp_train_set_frozen")
+
     def train_graph_stats(self):
         """(captures, replays) of pp_train_step's hipGraphs: steady-state steps must replay."""
         c, r = ctypes.c_int32(0), ctypes.c_int32(0)

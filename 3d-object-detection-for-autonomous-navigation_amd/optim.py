@@ -51,6 +51,20 @@ class AdamW:
         self.weight_decay = float(weight_decay)
         self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
         self.iterations = 0
+        self.segments = None      # None: the whole buffer; else the trainable (offset, size) segments
+
+    def set_segments(self, segments):
+        """Update only these (offset, size) segments of the buffers (frozen layers: the trainable ones); None = all.
+        Entries outside them -- parameters and both moments -- are neither read nor written."""
+        import numpy as np
+        if segments is None:
+            self.segments = None
+            return
+        arr = np.ascontiguousarray(np.asarray(segments, dtype=np.int64).reshape(-1, 2))
+        n = self.params.numel()
+        if ((arr[:, 0] < 0) | (arr[:, 1] < 0) | (arr[:, 0] + arr[:, 1] > n)).any():
+            raise ValueError("segments must lie inside the parameter buffer")
+        self.segments = arr
 
     def lr_t(self):
         lr = self.learning_rate(self.iterations) if callable(self.learning_rate) else float(self.learning_rate)
@@ -64,6 +78,16 @@ class AdamW:
                 grads.device != self.params.device:
             raise ValueError("grads must match params (flat float32, same device)")
         stream = torch.cuda.current_stream(self.params.device).cuda_stream
+        if self.segments is not None:
+            st = _lib.lib().pp_adamw_step_segments_device(
+                self.params.device.index or 0, ctypes.c_void_p(stream), ctypes.c_void_p(self.params.data_ptr()),
+                ctypes.c_void_p(grads.data_ptr()), ctypes.c_void_p(self.m.data_ptr()), ctypes.c_void_p(self.v.data_ptr()),
+                self.segments.ctypes.data_as(ctypes.c_void_p), len(self.segments), self.lr_t(), self.beta_1,
+                self.beta_2, self.epsilon, self.weight_decay)
+            if st != 0:
+                raise RuntimeError("pp_adamw_step_segments_device failed: " + _lib.lib().pp_last_error(None).decode())
+            self.iterations += 1
+            return
         st = _lib.lib().pp_adamw_step_device(self.params.device.index or 0, ctypes.c_void_p(stream),
                                              ctypes.c_void_p(self.params.data_ptr()), ctypes.c_void_p(grads.data_ptr()),
                                              ctypes.c_void_p(self.m.data_ptr()), ctypes.c_void_p(self.v.data_ptr()),

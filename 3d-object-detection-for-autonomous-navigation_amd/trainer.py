@@ -5,6 +5,8 @@
     out = trainer.step(frames, gt_boxes=boxes, dist=dist)      # ... with the targets assigned on the GPU from the boxes
     trainer = Trainer(config, weights, augment=True, seed=0)   # ... and the frames augmented on the GPU first
     trainer.weights()                                          # Keras-layout dict (Engine.load_weights, save_npz)
+    trainer = Trainer(config, weights, frozen="reference")     # fine-tuning with the early layers frozen
+    trainer.set_trainable(False)                               # ... the reference's set_trainable(net, False)
 
 What runs where: the frames are uploaded and voxelised by the engine, `pp_train_step` (csrc/train.hip) runs the
 training-mode forward pass, the loss and the backward pass and leaves the gradients of all trainable tensors in one
@@ -16,11 +18,83 @@ dataloader) or, given the ground-truth boxes (`gt_boxes=`), from the same assign
 the backward half of the step (csrc/targets.hip).  With `augment` on, a step given boxes first augments the frames
 and the boxes on the GPU as the reference's training loader does (csrc/augment.hip, augment.py); the random numbers
 are drawn from the trainer's own RandomState (`seed`) in the reference's order.
+
+Frozen layers (`frozen=`, `set_frozen`, `set_trainable`): the reference's second training stage loads a checkpoint and
+fine-tunes it with the early layers frozen (train.py:62-113 set_trainable, :356-368).  A freeze unit is the PFN
+("pfn"), one separable layer with its BatchNorm ("rpn/block<b>/<j>"), one transposed convolution ("rpn/deconv<b>") or
+one head ("rpn/conv_box", "rpn/conv_cls", "rpn/conv_dir_cls").  A frozen unit behaves as a Keras layer with
+trainable = False does in TF 2.x: its BatchNorm normalises with the moving statistics even in the training step and does
+not update them, its tensors get no gradient (their entries of the flat gradient buffer are 0) and AdamW neither updates
+nor decays them.  The gradient still flows through a frozen unit to trainable units in front of it.  These are the
+documented Keras semantics; the reference flips `trainable` after its tf.function was first traced, and whether TF 2.2
+re-traces at that point has not been checked against a TF run.
 """
 import numpy as np
 
 from . import optim
 from .engine import Engine
+
+
+def train_units(d):
+    """Every freeze unit of config `d` (config.Derived), in the order of the network."""
+    from . import weights as _w
+    return ["pfn"] + [name for _, name, _ in _w.layer_table(d)]
+
+
+def unit_of(tensor_name):
+    """The freeze unit a tensor of the layout belongs to: "rpn/block2/3/bn/gamma" -> "rpn/block2/3"."""
+    parts = tensor_name.split("/")
+    if parts[0] == "pfn":
+        return "pfn"
+    return "/".join(parts[:3] if parts[1].startswith("block") else parts[:2])
+
+
+def reference_frozen_units(d):
+    """The units set_trainable(net, False) freezes (train.py:62-113): the PFN's Dense, BatchNorm and ReLU
+    (net.layers[1].layers[0].layers[0..2]) and, in each RPN block, layers 0..9 -- ZeroPadding and the first three
+    (SeparableConv2D, BatchNorm, ReLU) triples, i.e. rpn/block<b>/0..2.  A block with fewer than three separable layers
+    (layer_nums[b] < 2) makes the reference raise IndexError; this raises ValueError."""
+    for b, n in enumerate(d.layer_nums):
+        if n < 2:
+            raise ValueError(f"the reference's set_trainable needs layer_nums[{b}] >= 2 (block{b + 1} has {n + 1} "
+                             f"separable layers, it indexes layers 0..9 of the block)")
+    return ["pfn"] + [f"rpn/block{b + 1}/{j}" for b in range(3) for j in range(3)]
+
+
+def trainable_segments(layout, frozen):
+    """(offset, size) ranges of the parameter buffer that hold the tensors of units not in `frozen`, merged where
+    they touch (layout: Engine.train_layout()'s entries)."""
+    fz = set(frozen)
+    segs = []
+    for name, off, size, is_state in layout:
+        if is_state or unit_of(name) in fz:
+            continue
+        if segs and segs[-1][0] + segs[-1][1] == off:
+            segs[-1][1] += size
+        else:
+            segs.append([off, size])
+    return [tuple(s) for s in segs]
+
+
+def resolve_frozen(d, frozen):
+    """None / () -> (); "reference" -> reference_frozen_units(d); an iterable of unit names -> those, in network order.
+    ValueError for an unknown or repeated name and when every unit would be frozen."""
+    if frozen is None:
+        return ()
+    if isinstance(frozen, str):
+        if frozen != "reference":
+            raise ValueError(f"frozen: None, 'reference' or an iterable of unit names, not {frozen!r}")
+        frozen = reference_frozen_units(d)
+    names = list(frozen)
+    units = train_units(d)
+    for n in names:
+        if not isinstance(n, str) or n not in units:
+            raise ValueError(f"unknown freeze unit {n!r} (units: {', '.join(units)})")
+    if len(set(names)) != len(names):
+        raise ValueError(f"a freeze unit is named twice: {names}")
+    if names and len(names) == len(units):
+        raise ValueError("every unit frozen: nothing left to train")
+    return tuple(u for u in units if u in names)
 
 
 class TrainBatch:
@@ -41,7 +115,7 @@ class TrainBatch:
 
 class Trainer:
     def __init__(self, config, weights, max_batch=None, max_points_per_frame=32768, device=0, learning_rate=None,
-                 weight_decay=None, augment=None, seed=None):
+                 weight_decay=None, augment=None, seed=None, frozen=None):
         import torch
         from . import augment as _augment
         # augment: None / False = off; True = the config's train_input_reader keys (the shipped values without them);
@@ -88,6 +162,28 @@ class Trainer:
             else:
                 weight_decay = 1e-4
         self.optimizer = optim.AdamW(self.params, learning_rate, weight_decay)
+        self._frozen = ()
+        self.set_frozen(frozen)
+
+    # ---- frozen layers (the reference's set_trainable) ----
+    @property
+    def frozen(self):
+        """The frozen units, in network order (() = everything trains)."""
+        return self._frozen
+
+    def set_frozen(self, units):
+        """Freeze `units` for the following steps: None / () = train everything, "reference" = the selection of the
+        reference's set_trainable(net, False), or an iterable of unit names (train_units).  Parameters, moving
+        statistics and AdamW moments of the units are kept as they are; unfreezing continues from them."""
+        names = resolve_frozen(self.engine.d, units)
+        self.engine.train_set_frozen(names)
+        self._frozen = names
+        self.optimizer.set_segments(trainable_segments(self.layout, names) if names else None)
+
+    def set_trainable(self, trainable):
+        """The reference's set_trainable(net, trainable) (train.py:62-113): False freezes its selection (the PFN and
+        rpn/block<b>/0..2, reference_frozen_units), True unfreezes everything."""
+        self.set_frozen(None if trainable else "reference")
 
     # ---- Keras-layout dict <-> flat buffers ----
     def set_weights(self, w):
@@ -109,17 +205,23 @@ class Trainer:
         return out
 
     def weights(self):
+        """Every tensor (frozen ones included) as a Keras-layout dict under its usual name.  The reference brackets its
+        save_weights with set_trainable(True) / set_trainable(False) (train.py:406-408) only to keep Keras's variable
+        order stable; names here do not depend on the freeze, so nothing of the kind is needed."""
         from . import weights as _w
         shapes = _w.expected_shapes(self.engine.d)
         like = {k: np.empty(v, np.float32) for k, v in shapes.items()}
         return self._unflatten(self.params.cpu().numpy(), self.state.cpu().numpy(), like)
 
     def gradients(self):
-        """The last step's gradients as a Keras-layout dict (trainable tensors only)."""
+        """The last step's gradients as a Keras-layout dict (trainable tensors only: the tensors of frozen units are
+        left out, as they are not among net.trainable_variables; their entries of `grads` are 0)."""
         from . import weights as _w
         shapes = _w.expected_shapes(self.engine.d)
         g = self.grads.cpu().numpy()
-        return {name: g[off:off + size].reshape(shapes[name]).copy() for name, off, size, st in self.layout if not st}
+        fz = set(self._frozen)
+        return {name: g[off:off + size].reshape(shapes[name]).copy() for name, off, size, st in self.layout
+                if not st and unit_of(name) not in fz}
 
     def decisions(self):
         """Parity tap (pp_train_fetch_decisions): what the last step decided at its non-differentiable points.

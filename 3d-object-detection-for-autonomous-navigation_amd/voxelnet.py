@@ -112,6 +112,16 @@ class VoxelNet:
             self.apply_gradients(dist)
         return out
 
+    def set_trainable(self, trainable):
+        """The reference's set_trainable(net, trainable) (train.py:62-113) on a training net after load_weights():
+        False freezes the PFN and rpn/block<b>/0..2 for the following steps, True unfreezes everything
+        (Trainer.set_trainable)."""
+        if not self.training:
+            raise ValueError("set_trainable is a training option: build the net with training=True")
+        if self.trainer is None:
+            raise RuntimeError("VoxelNet(training=True): load_weights() with the initial values first")
+        self.trainer.set_trainable(trainable)
+
     def apply_gradients(self, dist=None):
         """optimizer.apply_gradients (train.py:301) on the flat buffers, after the data-parallel all-reduce."""
         self.trainer.apply_gradients(dist)      # ends with a stream synchronisation (see Trainer.apply_gradients)

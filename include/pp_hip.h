@@ -30,7 +30,7 @@ extern "C" {
 /* 3: PP_ERR_NUMERIC, pp_set_gemm_precision / pp_get_gemm_precision, pp_set_cache_budget.  4: pp_train_fetch_decisions;
  * later additions within 4 (nothing before them changed): pp_target_config, pp_assign_targets, pp_train_step_gt_async,
  * pp_train_step_gt; then PP_AUG_MAX_TRY, pp_augment_config, pp_aug_frame, pp_augment, pp_train_step_aug_async,
- * pp_train_step_aug, pp_augment_selected. */
+ * pp_train_step_aug, pp_augment_selected; then pp_train_set_frozen, pp_adamw_step_segments_device. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -311,6 +311,13 @@ int pp_head_loss(pp_handle h, const int32_t* labels, const float* reg_targets, i
 int pp_adamw_step_device(int device, void* stream, float* params, const float* grads, float* m, float* v,
                          int64_t n, float lr_t, float beta1, float beta2, float epsilon, float weight_decay);
 
+/* The same update over part of the buffers only (fine-tuning with frozen layers): `segments` is a HOST array of
+ * n_segments (offset, size) pairs in floats; entries outside them -- params, m and v alike -- are neither read nor
+ * written.  An updated entry is bit-identical to what pp_adamw_step_device computes for it. */
+int pp_adamw_step_segments_device(int device, void* stream, float* params, const float* grads, float* m, float* v,
+                                  const int64_t* segments, int32_t n_segments, float lr_t, float beta1, float beta2,
+                                  float epsilon, float weight_decay);
+
 /* ---- training step ---------------------------- */
 
 /* The trainable tensors live in ONE flat float32 device buffer owned by the caller (a second one of the same
@@ -451,6 +458,16 @@ int pp_train_fetch_decisions(pp_handle h, int32_t layer, uint8_t* relu_mask, int
 /* How often pp_train_step captured a hipGraph and how often it replayed one (one graph per input buffer of the
  * handle): steady-state steps must replay -- a regression check, not part of the reference's surface. */
 int pp_train_graph_stats(pp_handle h, int32_t* captures, int32_t* replays);
+
+/* Fine-tuning with frozen layers (the reference's set_trainable(net, False), train.py:62-113): the next training steps
+ * treat the `n` named units as Keras treats layers with trainable = False -- their BatchNorm normalises with the moving
+ * statistics (inference mode, even in a training step) and leaves them unchanged, and their tensors get no gradient
+ * (their entries of grads_dev are written as 0).  The gradient still flows through a frozen unit to trainable units in
+ * front of it.  Units: "pfn" (Dense + BatchNorm), "rpn/block<b>/<j>" (one separable layer with its BatchNorm),
+ * "rpn/deconv<b>", "rpn/conv_box", "rpn/conv_cls", "rpn/conv_dir_cls" (with a direction head).  n = 0 unfreezes
+ * everything.  PP_ERR_ARG for an unknown or repeated name, or when every unit would be frozen (the freeze then stays
+ * as it was).  The freeze is part of what a captured step graph is keyed on: a change re-captures it once. */
+int pp_train_set_frozen(pp_handle h, const char* const* units, int32_t n);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
