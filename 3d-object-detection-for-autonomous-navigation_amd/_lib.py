@@ -18,7 +18,7 @@ _INCLUDE = os.path.join(os.path.dirname(_PKG), "include", "pp_hip.h")
 SO_PATH = os.path.join(_PKG, os.environ.get("PP_HIP_LIB", "libpp_hip.so"))
 _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
 SOURCES = ["pp_api.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
-           "rotate_iou.hip", "loss.hip", "optim.hip", "train.hip", "targets.hip", "augment.hip"]
+           "rotate_iou.hip", "loss.hip", "optim.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
@@ -37,6 +37,7 @@ EXPORTS = [
     "pp_assign_targets", "pp_train_step_gt_async", "pp_train_step_gt",
     "pp_augment", "pp_train_step_aug_async", "pp_train_step_aug", "pp_augment_selected",
     "pp_train_set_frozen", "pp_adamw_step_segments_device",
+    "pp_gtdb_load", "pp_gt_sample", "pp_gt_sample_info", "pp_train_step_sample_async", "pp_train_step_sample",
 ]
 
 
@@ -96,6 +97,23 @@ class PPAugmentConfig(ctypes.Structure):
     _fields_ = [
         ("num_try", ctypes.c_int32),
         ("global_rot_per_object", ctypes.c_int32),
+    ]
+
+
+class PPGtSampleConfig(ctypes.Structure):
+    _fields_ = [
+        ("max_point_collision", ctypes.c_int32),
+        ("min_point_collision", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 2),
+    ]
+
+
+class PPGtsCand(ctypes.Structure):
+    _fields_ = [
+        ("object", ctypes.c_int32),
+        ("group", ctypes.c_int32),
+        ("low", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
     ]
 
 
@@ -280,6 +298,16 @@ def lib():
     L.pp_train_set_frozen.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), i32]
     L.pp_adamw_step_segments_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, i32, ctypes.c_float,
                                                 ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]
+    L.pp_gtdb_load.argtypes = [vp, f32p, vp, vp, vp, i64]
+    L.pp_gt_sample.argtypes = [vp, f32p, vp, vp, vp, i32, ctypes.POINTER(PPGtSampleConfig), vp, vp, f32p, i64, vp, f32p,
+                               vp, vp, vp]
+    L.pp_gt_sample_info.argtypes = [vp, vp, vp, vp, i32]
+    L.pp_train_step_sample_async.argtypes = [vp, vp, vp, vp, f32p, vp, vp, i32, ctypes.POINTER(PPLossConfig),
+                                             ctypes.POINTER(PPTargetConfig), vp, ctypes.POINTER(PPGtSampleConfig), vp, vp,
+                                             ctypes.POINTER(PPAugmentConfig), vp, vp]
+    L.pp_train_step_sample.argtypes = [vp, vp, vp, vp, f32p, vp, vp, i32, ctypes.POINTER(PPLossConfig),
+                                       ctypes.POINTER(PPTargetConfig), vp, ctypes.POINTER(PPGtSampleConfig), vp, vp,
+                                       ctypes.POINTER(PPAugmentConfig), vp, vp, f32p]
     for name in EXPORTS:
         fn = getattr(L, name)  # raises AttributeError if the symbol is not exported
         if name not in ("pp_last_error", "pp_layer_tag"):

@@ -130,8 +130,34 @@ struct pp_engine {
     float* d_aug_box_tmp = nullptr;
     uint8_t* d_aug_keep = nullptr;
     int* d_aug_sel = nullptr;
+    int* d_aug_draw_off = nullptr;     // [B] first draw row of each frame (the sampled step: rows are allotted per frame)
     double* d_aug_cs = nullptr;        // [B][2]          // [B * PP_MAX_GT_PER_FRAME] the selected try per input box (pp_augment_selected)
     int64_t aug_total = 0;             // input boxes of the last augmentation
+    // GT-database sampling (pp_gtdb_load / pp_gt_sample): the database is replaced as a whole, the per-batch buffers are
+    // allocated on first use
+    float* d_db_pts = nullptr;
+    int* d_db_off = nullptr;
+    double* d_db_box = nullptr;
+    int* d_db_cls = nullptr;
+    std::vector<int> h_draw_off;       // host side of d_aug_draw_off
+    std::vector<int> h_db_npts;        // points per object (the host-side bound on the pasted cloud)
+    int64_t db_n = -1;                 // objects loaded; -1: no database
+    bool gts_ready = false;
+    float* d_gts_gt_in = nullptr;      // [B * PP_MAX_GT_PER_FRAME][7] the boxes as given
+    int* d_gts_cls_in = nullptr;
+    uint8_t* d_gts_valid_in = nullptr;
+    int* d_gts_cnt_in = nullptr;
+    pp_gts_cand* d_gts_cands = nullptr;   // [B][PP_GTS_MAX_CAND]
+    int* d_gts_cand_counts = nullptr;     // [B][PP_GTS_MAX_ROUNDS]
+    GtsPlane* d_gts_planes = nullptr;
+    int *d_gts_status = nullptr, *d_gts_counts = nullptr, *d_gts_round = nullptr;
+    int *d_gts_acc_n = nullptr, *d_gts_acc_slot = nullptr, *d_gts_acc_pstart = nullptr, *d_gts_box_off = nullptr;
+    int* d_gts_offsets = nullptr;      // [B + 1] the frames' offsets after pasting
+    float* d_gts_gt_out = nullptr;     // [B * PP_MAX_GT_PER_FRAME][7]
+    int* d_gts_cls_out = nullptr;
+    uint8_t* d_gts_valid_out = nullptr;
+    int* d_gts_cnt_out = nullptr;
+    int gts_batch = 0;                 // frames of the last pp_gt_sample (pp_gt_sample_info)
     int* d_tgt_index = nullptr;        // [B][A] optional outputs of pp_assign_targets, allocated on first use
     float* d_tgt_overlap = nullptr;
     float* d_calib = nullptr;
@@ -151,6 +177,8 @@ struct pp_engine {
 
     int cur_batch = 0, cur_max_n = 0;
     int cur_total = 0;                    // points of the resident frames (host copy of the last offset)
+    std::vector<int> h_cur_off;           // host copy of the resident frames' offsets [cur_batch + 1]
+    bool off_host_exact = true;           // ... false after a fused sampling step: the sizes are then device values
     int results_batch = 0;        // frames of the last enqueued pp_detect_async (0: no results to fetch)
     // frame offsets travel through a small pinned ring (a pageable source would be staged synchronously and a
     // single pinned buffer could be rewritten while its copy is still queued); a slot is reused only after the
@@ -649,6 +677,8 @@ int set_offsets(pp_engine* e, const int32_t* off, int batch, hipStream_t stream)
     e->cur_batch = batch;
     e->cur_max_n = max_n;
     e->cur_total = off[batch];
+    e->h_cur_off.assign(off, off + batch + 1);
+    e->off_host_exact = true;
     const int nb = e->in_buf ^ 1;
     e->in_buf = nb;
     e->d_points = e->d_points_buf[nb];
@@ -952,6 +982,7 @@ int pp_destroy(pp_handle e) {
     graph_invalidate(e);
     for (void* p : e->allocs) (void)hipFree(p);
     for (void* p : e->wallocs) (void)hipFree(p);
+    for (void* p : {(void*)e->d_db_pts, (void*)e->d_db_off, (void*)e->d_db_box, (void*)e->d_db_cls}) if (p) (void)hipFree(p);
     if (e->train) for (auto& tg : e->train->graph) {
         if (tg.exec) (void)hipGraphExecDestroy(tg.exec);
         if (tg.exec_bwd) (void)hipGraphExecDestroy(tg.exec_bwd);
@@ -1205,6 +1236,8 @@ static int feed_zero_copy(pp_engine* e, const float* points_pinned, const int32_
     e->cur_batch = batch;
     e->cur_max_n = max_n;
     e->cur_total = off[batch];
+    e->h_cur_off.assign(off, off + batch + 1);
+    e->off_host_exact = true;
     e->up_pending = false;
     e->zc = true;
     return PP_OK;
@@ -1944,9 +1977,11 @@ int check_gt(pp_engine* e, const char* who, const float* gt_boxes, const int32_t
 // current cell map when `resident_mask` (else d_tmask holds the caller's), the per-box maxima are reset, then the two
 // passes write d_loss_labels / d_loss_regt (and the optional per-anchor outputs).
 // With `up` == nullptr the boxes, classes and counts are already on the device: the augmentation wrote all three
-// (classes 1 where the caller gave none), so d_gt_cls is read whatever `gt_classes` is.
+// (classes 1 where the caller gave none), so d_gt_cls is read whatever `gt_classes` is; `from_sampler`: the sampling
+// did (a sampled step without augmentation), into its own output buffers.
 int enqueue_targets(pp_engine* e, int batch, const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts,
-                    int64_t total, bool resident_mask, const pp_target_config* tc, bool extra, hipStream_t up) {
+                    int64_t total, bool resident_mask, const pp_target_config* tc, bool extra, hipStream_t up,
+                    bool from_sampler = false) {
     if (up != nullptr && total > 0)
         HIPCHK(e, hipMemcpyAsync(e->d_gt_boxes, gt_boxes, (size_t)total * 7 * sizeof(float), hipMemcpyHostToDevice, up));
     if (up != nullptr && total > 0 && gt_classes)
@@ -1974,6 +2009,7 @@ int enqueue_targets(pp_engine* e, int batch, const float* gt_boxes, const int32_
     TargetParams p;
     p.batch = batch; p.A = e->A; p.anchor_near = e->d_anchor_near; p.anchors = e->d_anchors; p.mask = mask;
     p.gt = e->d_gt_boxes; p.gt_cls = (gt_classes || up == nullptr) ? e->d_gt_cls : nullptr; p.gt_cnt = e->d_gt_cnt;
+    if (from_sampler) { p.gt = e->d_gts_gt_out; p.gt_cls = e->d_gts_cls_out; p.gt_cnt = e->d_gts_cnt_out; }   // (up == nullptr)
     p.top = e->d_gt_top;
     p.matched = tc->matched_threshold; p.unmatched = tc->unmatched_threshold;
     p.labels = e->d_loss_labels; p.reg_targets = e->d_loss_regt;
@@ -2017,11 +2053,14 @@ int check_aug(pp_engine* e, const char* who, int batch, int64_t total, const pp_
 // lands in the resident input buffer; d_gt_boxes / d_gt_cls / d_gt_cnt receive the kept boxes.
 int enqueue_augment(pp_engine* e, int batch, const float* gt_boxes, const int32_t* gt_classes, const uint8_t* gt_valid,
                     const int32_t* gt_counts, int64_t total, const pp_augment_config* ac, const pp_aug_frame* frames,
-                    const double* box_draws, hipStream_t up) {
+                    const double* box_draws, hipStream_t up, const std::vector<int>* draw_off = nullptr) {
     int st;
+    // draw_off: the boxes, classes, flags and counts are the sampling's outputs, already on the device (gt_* are not
+    // read); `total` then counts the draw rows, and frame b's boxes take the rows from (*draw_off)[b] on
+    const bool dev_boxes = draw_off != nullptr;
     if (!e->aug_ready) {
         const size_t gmax = (size_t)e->B * PP_MAX_GT_PER_FRAME;
-        if ((st = dalloc(e, &e->d_aug_pts, (size_t)e->B * e->NMAX * e->F))) return st;
+        if (!e->d_aug_pts && (st = dalloc(e, &e->d_aug_pts, (size_t)e->B * e->NMAX * e->F))) return st;   // (shared with pp_gt_sample)
         if ((st = dalloc(e, &e->d_aug_gt_in, gmax * 7))) return st;
         if ((st = dalloc(e, &e->d_aug_cls_in, gmax))) return st;
         if ((st = dalloc(e, &e->d_aug_valid, gmax))) return st;
@@ -2033,17 +2072,22 @@ int enqueue_augment(pp_engine* e, int batch, const float* gt_boxes, const int32_
         if ((st = dalloc(e, &e->d_aug_keep, gmax))) return st;
         if ((st = dalloc(e, &e->d_aug_sel, gmax))) return st;
         if ((st = dalloc(e, &e->d_aug_cs, (size_t)e->B * 2))) return st;
+        if ((st = dalloc(e, &e->d_aug_draw_off, (size_t)e->B))) return st;
         e->aug_ready = true;
     }
-    if (total > 0) {
+    if (total > 0 && !dev_boxes) {
         HIPCHK(e, hipMemcpyAsync(e->d_aug_gt_in, gt_boxes, (size_t)total * 7 * sizeof(float), hipMemcpyHostToDevice, up));
         if (gt_classes)
             HIPCHK(e, hipMemcpyAsync(e->d_aug_cls_in, gt_classes, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice, up));
         if (gt_valid) HIPCHK(e, hipMemcpyAsync(e->d_aug_valid, gt_valid, (size_t)total, hipMemcpyHostToDevice, up));
+    }
+    if (total > 0)
         HIPCHK(e, hipMemcpyAsync(e->d_aug_draws, box_draws, (size_t)total * ac->num_try * 5 * sizeof(double),
                                  hipMemcpyHostToDevice, up));
-    }
-    HIPCHK(e, hipMemcpyAsync(e->d_aug_cnt_in, gt_counts, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, up));
+    if (dev_boxes)
+        HIPCHK(e, hipMemcpyAsync(e->d_aug_draw_off, draw_off->data(), (size_t)batch * sizeof(int), hipMemcpyHostToDevice, up));
+    else
+        HIPCHK(e, hipMemcpyAsync(e->d_aug_cnt_in, gt_counts, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, up));
     HIPCHK(e, hipMemcpyAsync(e->d_aug_frames, frames, (size_t)batch * sizeof(pp_aug_frame), hipMemcpyHostToDevice, up));
     if (up != e->stream) {
         HIPCHK(e, hipEventRecord(e->ev_tgt, up));
@@ -2071,6 +2115,11 @@ int enqueue_augment(pp_engine* e, int batch, const float* gt_boxes, const int32_
     p.cnt_in = e->d_aug_cnt_in; p.draws = e->d_aug_draws; p.frames = e->d_aug_frames; p.frame_cs = e->d_aug_cs;
     p.boxrec = e->d_aug_rec; p.box_tmp = e->d_aug_box_tmp; p.keep = e->d_aug_keep; p.sel = e->d_aug_sel;
     p.gt_out = e->d_gt_boxes; p.cls_out = e->d_gt_cls; p.cnt_out = e->d_gt_cnt;
+    p.draw_off = nullptr;
+    if (dev_boxes) {
+        p.gt_in = e->d_gts_gt_out; p.cls_in = e->d_gts_cls_out; p.valid = e->d_gts_valid_out; p.cnt_in = e->d_gts_cnt_out;
+        p.draw_off = e->d_aug_draw_off;
+    }
     launch_augment(p, e->cur_max_n, e->stream);
     HIPCHK(e, hipGetLastError());
     e->aug_total = total;
@@ -2078,6 +2127,133 @@ int enqueue_augment(pp_engine* e, int batch, const float* gt_boxes, const int32_
     if (n) HIPCHK(e, hipMemcpyAsync(e->d_points, e->d_aug_pts, n * e->F * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
     e->zc = false;
     e->vox_ahead = false;
+    return PP_OK;
+}
+
+// The sampling's argument checks beyond check_gt's, and the host-known bounds on what it writes: the pasted cloud's
+// size is known on the device only, so every launch and copy behind it is sized from n_b + (points of all candidates
+// of one round), which is refused here when it does not fit.  *max_out_n: the largest frame's bound; *bound_total: the
+// sum of the frames' bounds.
+int check_gts(pp_engine* e, const char* who, const int32_t* gt_counts, int batch, const pp_gt_sample_config* sc,
+              const pp_gts_cand* cands, const int32_t* cand_counts, int* max_out_n_p, int64_t* bound_total_p) {
+    if (!sc || !cands || !cand_counts) return fail(e, PP_ERR_ARG, "%s: null argument", who);
+    if (e->db_n < 0) return fail(e, PP_ERR_STATE, "%s: no database loaded (pp_gtdb_load)", who);
+    if (e->cur_batch != batch)
+        return fail(e, PP_ERR_ARG, "%s: %d frames are resident, batch is %d", who, e->cur_batch, batch);
+    if (!e->off_host_exact)
+        return fail(e, PP_ERR_STATE, "%s: the resident frames were sampled inside a training step (upload frames first)", who);
+    int max_out_n = 0;
+    int64_t bound_total = 0;
+    // The pasted cloud's size is known on the device only: every launch and buffer is sized from the bound
+    // n_b + (points of all candidates of one round), which is refused here when it does not fit.
+    for (int b = 0; b < batch; ++b) {
+        const int32_t* cc = cand_counts + (size_t)b * PP_GTS_MAX_ROUNDS;
+        const pp_gts_cand* c = cands + (size_t)b * PP_GTS_MAX_CAND;
+        const int n_b = e->h_cur_off[b + 1] - e->h_cur_off[b];
+        int s0 = 0;
+        int64_t worst = 0;
+        for (int r = 0; r < PP_GTS_MAX_ROUNDS; ++r) {
+            if (cc[r] < 0 || s0 + (int64_t)cc[r] > PP_GTS_MAX_CAND)
+                return fail(e, PP_ERR_ARG, "%s: frame %d has more than %d candidates", who, b, PP_GTS_MAX_CAND);
+            if (gt_counts[b] + cc[r] > PP_MAX_GT_PER_FRAME)
+                return fail(e, PP_ERR_ARG, "%s: frame %d: %d boxes + %d candidates > %d", who, b, gt_counts[b], cc[r],
+                            PP_MAX_GT_PER_FRAME);
+            int64_t pts = 0;
+            for (int s = s0; s < s0 + cc[r]; ++s) {
+                if (c[s].object < 0 || c[s].object >= e->db_n)
+                    return fail(e, PP_ERR_ARG, "%s: frame %d slot %d: object %d outside the database (%lld objects)", who,
+                                b, s, c[s].object, (long long)e->db_n);
+                if (s > s0 && c[s].group < c[s - 1].group)
+                    return fail(e, PP_ERR_ARG, "%s: frame %d slot %d: groups out of order", who, b, s);
+                pts += e->h_db_npts[(size_t)c[s].object];
+            }
+            worst = std::max(worst, pts);
+            s0 += cc[r];
+        }
+        if (n_b + worst > e->NMAX)
+            return fail(e, PP_ERR_ARG, "%s: frame %d: %d points + up to %lld pasted > max_points_per_frame=%d", who, b, n_b,
+                        (long long)worst, e->NMAX);
+        max_out_n = std::max(max_out_n, (int)(n_b + worst));
+        bound_total += n_b + worst;
+    }
+    *max_out_n_p = max_out_n;
+    *bound_total_p = bound_total;
+    return PP_OK;
+}
+
+// Queues the sampling of the resident frames on the handle's stream; the inputs go up on `up` (the copy stream: the
+// main stream then waits for ev_tgt; or the main stream).  The grown cloud lands in the spare point buffer and the new
+// offsets in d_gts_offsets; the caller moves both into the resident buffers (by the counts read back, or by the bound).
+int enqueue_gt_sample(pp_engine* e, int batch, const float* gt_boxes, const int32_t* gt_classes, const uint8_t* gt_valid,
+                      const int32_t* gt_counts, int64_t total, const pp_gt_sample_config* sc, const pp_gts_cand* cands,
+                      const int32_t* cand_counts, int max_out_n, hipStream_t up) {
+    int st;
+    if (!e->gts_ready) {
+        const size_t gmax = (size_t)e->B * PP_MAX_GT_PER_FRAME, cmax = (size_t)e->B * PP_GTS_MAX_CAND;
+        if (!e->d_aug_pts && (st = dalloc(e, &e->d_aug_pts, (size_t)e->B * e->NMAX * e->F))) return st;
+        if ((st = dalloc(e, &e->d_gts_gt_in, gmax * 7))) return st;
+        if ((st = dalloc(e, &e->d_gts_cls_in, gmax))) return st;
+        if ((st = dalloc(e, &e->d_gts_valid_in, gmax))) return st;
+        if ((st = dalloc(e, &e->d_gts_cnt_in, (size_t)e->B))) return st;
+        if ((st = dalloc(e, &e->d_gts_cands, cmax))) return st;
+        if ((st = dalloc(e, &e->d_gts_cand_counts, (size_t)e->B * PP_GTS_MAX_ROUNDS))) return st;
+        if ((st = dalloc(e, &e->d_gts_planes, cmax))) return st;
+        if ((st = dalloc(e, &e->d_gts_status, cmax))) return st;
+        if ((st = dalloc(e, &e->d_gts_counts, cmax))) return st;
+        if ((st = dalloc(e, &e->d_gts_round, (size_t)e->B))) return st;
+        if ((st = dalloc(e, &e->d_gts_acc_n, (size_t)e->B))) return st;
+        if ((st = dalloc(e, &e->d_gts_acc_slot, cmax))) return st;
+        if ((st = dalloc(e, &e->d_gts_acc_pstart, (size_t)e->B * (PP_GTS_MAX_CAND + 1)))) return st;
+        if ((st = dalloc(e, &e->d_gts_box_off, 2 * ((size_t)e->B + 1)))) return st;
+        if ((st = dalloc(e, &e->d_gts_offsets, (size_t)e->B + 1))) return st;
+        if ((st = dalloc(e, &e->d_gts_gt_out, gmax * 7))) return st;
+        if ((st = dalloc(e, &e->d_gts_cls_out, gmax))) return st;
+        if ((st = dalloc(e, &e->d_gts_valid_out, gmax))) return st;
+        if ((st = dalloc(e, &e->d_gts_cnt_out, (size_t)e->B))) return st;
+        e->gts_ready = true;
+    }
+    hipStream_t s = up;
+    if (total > 0) {
+        HIPCHK(e, hipMemcpyAsync(e->d_gts_gt_in, gt_boxes, (size_t)total * 7 * sizeof(float), hipMemcpyHostToDevice, s));
+        if (gt_classes) HIPCHK(e, hipMemcpyAsync(e->d_gts_cls_in, gt_classes, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (gt_valid) HIPCHK(e, hipMemcpyAsync(e->d_gts_valid_in, gt_valid, (size_t)total, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(e, hipMemcpyAsync(e->d_gts_cnt_in, gt_counts, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->d_gts_cands, cands, (size_t)batch * PP_GTS_MAX_CAND * sizeof(pp_gts_cand), hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->d_gts_cand_counts, cand_counts, (size_t)batch * PP_GTS_MAX_ROUNDS * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (up != e->stream) {
+        HIPCHK(e, hipEventRecord(e->ev_tgt, up));
+        HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_tgt, 0));
+    }
+    s = e->stream;
+    // the resident points: behind their upload; a zero-copy feed is read from the caller's page-locked memory and
+    // replaced by device copies (as the augmentation does)
+    if (e->up_pending || e->prevox_issued) {
+        HIPCHK(e, hipStreamWaitEvent(s, e->ev_up, 0));
+        e->up_pending = false;
+        e->prevox_issued = false;
+    }
+    const PpFeed* f = e->h_feed[e->in_buf];
+    const float* src = e->d_points;
+    if (e->zc) {
+        HIPCHK(e, hipMemcpyAsync(e->d_offsets, f->offsets, (size_t)(batch + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+        src = f->src;
+    }
+    GtsParams p;
+    p.batch = batch; p.F = e->F; p.max_pc = sc->max_point_collision; p.min_pc = sc->min_point_collision;
+    p.offsets = e->d_offsets; p.pts_in = src; p.pts_out = e->d_aug_pts; p.offsets_out = e->d_gts_offsets;
+    p.gt_in = e->d_gts_gt_in; p.cls_in = gt_classes ? e->d_gts_cls_in : nullptr; p.valid_in = gt_valid ? e->d_gts_valid_in : nullptr;
+    p.cnt_in = e->d_gts_cnt_in; p.cands = e->d_gts_cands; p.cand_counts = e->d_gts_cand_counts;
+    p.db_pts = e->d_db_pts; p.db_off = e->d_db_off; p.db_box = e->d_db_box; p.db_cls = e->d_db_cls;
+    p.planes = e->d_gts_planes; p.status = e->d_gts_status; p.counts = e->d_gts_counts; p.round_used = e->d_gts_round;
+    p.acc_n = e->d_gts_acc_n; p.acc_slot = e->d_gts_acc_slot; p.acc_pstart = e->d_gts_acc_pstart; p.box_off = e->d_gts_box_off;
+    p.gt_out = e->d_gts_gt_out; p.cls_out = e->d_gts_cls_out; p.valid_out = e->d_gts_valid_out; p.cnt_out = e->d_gts_cnt_out;
+    {
+        ProfScope ps(e, nullptr);      // each launch under its own name
+        launch_gt_sample(p, e->cur_max_n, max_out_n, s);
+    }
+    HIPCHK(e, hipGetLastError());
+    e->gts_batch = batch;
     return PP_OK;
 }
 
@@ -2333,6 +2509,8 @@ int pp_augment(pp_handle e, const float* gt_boxes, const int32_t* gt_classes, co
     if (!e) return PP_ERR_ARG;
     if (!points_out || !boxes_out || !classes_out || !counts_out) return fail(e, PP_ERR_ARG, "pp_augment: null argument");
     if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_augment: a training step is in flight");
+    if (!e->off_host_exact)
+        return fail(e, PP_ERR_STATE, "pp_augment: the resident frames were sampled inside a training step (upload frames first)");
     const pp_target_config tc = {0.5f, 0.35f, {0, 0}};
     int64_t total = 0;
     int st = check_gt(e, "pp_augment", gt_boxes, gt_classes, gt_counts, batch, &tc, &total);
@@ -2356,10 +2534,190 @@ int pp_augment(pp_handle e, const float* gt_boxes, const int32_t* gt_classes, co
     return PP_OK;
 }
 
+// ---- GT-database sampling (gt_sample.hip) ----
+
+int pp_gtdb_load(pp_handle e, const float* points, const int64_t* point_offsets, const double* boxes,
+                 const int32_t* classes, int64_t n) {
+    if (!e) return PP_ERR_ARG;
+    if (n < 0 || !point_offsets || (n > 0 && (!boxes || !classes)))
+        return fail(e, PP_ERR_ARG, "pp_gtdb_load: null argument");
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_gtdb_load: a training step is in flight");
+    if (point_offsets[0] != 0) return fail(e, PP_ERR_ARG, "pp_gtdb_load: point_offsets[0] must be 0");
+    if (n > 0x7fffffff / 8) return fail(e, PP_ERR_ARG, "pp_gtdb_load: too many objects");
+    for (int64_t i = 0; i < n; ++i) {
+        if (point_offsets[i + 1] < point_offsets[i])
+            return fail(e, PP_ERR_ARG, "pp_gtdb_load: point_offsets not monotone at object %lld", (long long)i);
+        const double* q = boxes + i * 7;
+        for (int k = 0; k < 7; ++k)
+            if (!std::isfinite(q[k])) return fail(e, PP_ERR_ARG, "pp_gtdb_load: box %lld is not finite", (long long)i);
+        if (!(q[3] > 0.0 && q[4] > 0.0 && q[5] > 0.0))
+            return fail(e, PP_ERR_ARG, "pp_gtdb_load: box %lld has a size <= 0", (long long)i);
+        if (classes[i] < 1 || classes[i] > e->cfg.num_class)
+            return fail(e, PP_ERR_ARG, "pp_gtdb_load: object %lld has class %d (1..%d)", (long long)i, classes[i], e->cfg.num_class);
+    }
+    const int64_t total = point_offsets[n];
+    if (total > 0x7fffffff / (e->F > 0 ? e->F : 1)) return fail(e, PP_ERR_ARG, "pp_gtdb_load: too many points");
+    if (total > 0 && !points) return fail(e, PP_ERR_ARG, "pp_gtdb_load: points is NULL");
+    (void)hipSetDevice(e->device);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    for (void* p : {(void*)e->d_db_pts, (void*)e->d_db_off, (void*)e->d_db_box, (void*)e->d_db_cls}) if (p) (void)hipFree(p);
+    e->d_db_pts = nullptr; e->d_db_off = nullptr; e->d_db_box = nullptr; e->d_db_cls = nullptr;
+    e->db_n = -1;
+    std::vector<int> off32((size_t)n + 1);
+    e->h_db_npts.resize((size_t)n);
+    for (int64_t i = 0; i <= n; ++i) off32[(size_t)i] = (int)point_offsets[i];
+    for (int64_t i = 0; i < n; ++i) e->h_db_npts[(size_t)i] = (int)(point_offsets[i + 1] - point_offsets[i]);
+    HIPCHK(e, hipMalloc((void**)&e->d_db_pts, std::max<size_t>((size_t)total * e->F, 1) * sizeof(float)));
+    HIPCHK(e, hipMalloc((void**)&e->d_db_off, ((size_t)n + 1) * sizeof(int)));
+    HIPCHK(e, hipMalloc((void**)&e->d_db_box, std::max<size_t>((size_t)n * 7, 1) * sizeof(double)));
+    HIPCHK(e, hipMalloc((void**)&e->d_db_cls, std::max<size_t>((size_t)n, 1) * sizeof(int)));
+    if (total) HIPCHK(e, hipMemcpy(e->d_db_pts, points, (size_t)total * e->F * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(e->d_db_off, off32.data(), off32.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (n) HIPCHK(e, hipMemcpy(e->d_db_box, boxes, (size_t)n * 7 * sizeof(double), hipMemcpyHostToDevice));
+    if (n) HIPCHK(e, hipMemcpy(e->d_db_cls, classes, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    e->db_n = n;
+    return PP_OK;
+}
+
+int pp_gt_sample(pp_handle e, const float* gt_boxes, const int32_t* gt_classes, const uint8_t* gt_valid,
+                 const int32_t* gt_counts, int32_t batch, const pp_gt_sample_config* sc, const pp_gts_cand* cands,
+                 const int32_t* cand_counts, float* points_out, int64_t points_capacity, int32_t* offsets_out,
+                 float* boxes_out, int32_t* classes_out, uint8_t* valid_out, int32_t* counts_out) {
+    if (!e) return PP_ERR_ARG;
+    if (!points_out || !offsets_out || !boxes_out || !classes_out || !valid_out || !counts_out)
+        return fail(e, PP_ERR_ARG, "pp_gt_sample: null argument");
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_gt_sample: a training step is in flight");
+    if (e->db_n < 0) return fail(e, PP_ERR_STATE, "pp_gt_sample: no database loaded (pp_gtdb_load)");
+    const pp_target_config tc = {0.5f, 0.35f, {0, 0}};
+    int64_t total = 0, bound_total = 0;
+    int max_out_n = 0;
+    int st = check_gt(e, "pp_gt_sample", gt_boxes, gt_classes, gt_counts, batch, &tc, &total);
+    if (st == PP_OK) st = check_gts(e, "pp_gt_sample", gt_counts, batch, sc, cands, cand_counts, &max_out_n, &bound_total);
+    if (st) return st;
+    if (points_capacity < bound_total)
+        return fail(e, PP_ERR_ARG, "%s: points_out holds %lld points, up to %lld are written", "pp_gt_sample",
+                    (long long)points_capacity, (long long)bound_total);
+    (void)hipSetDevice(e->device);
+    prof_reset(e);
+    if ((st = enqueue_gt_sample(e, batch, gt_boxes, gt_classes, gt_valid, gt_counts, total, sc, cands, cand_counts, max_out_n,
+                                e->stream)))
+        return st;
+    hipStream_t s = e->stream;
+    HIPCHK(e, hipMemcpyAsync(offsets_out, e->d_gts_offsets, (size_t)(batch + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(counts_out, e->d_gts_cnt_out, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    // the counts read back replace the host's copy of the offsets: everything downstream is sized from them
+    const int64_t n_new = offsets_out[batch];
+    int64_t kept = 0;
+    int max_n = 0;
+    for (int b = 0; b < batch; ++b) {
+        kept += counts_out[b];
+        max_n = std::max(max_n, offsets_out[b + 1] - offsets_out[b]);
+    }
+    if (n_new > bound_total || max_n > e->NMAX) return fail(e, PP_ERR_HIP, "pp_gt_sample: the device wrote past its bound");
+    if (n_new) HIPCHK(e, hipMemcpyAsync(e->d_points, e->d_aug_pts, (size_t)n_new * e->F * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->d_offsets, e->d_gts_offsets, (size_t)(batch + 1) * sizeof(int), hipMemcpyDeviceToDevice, s));
+    if (n_new) HIPCHK(e, hipMemcpyAsync(points_out, e->d_aug_pts, (size_t)n_new * e->F * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (kept) {
+        HIPCHK(e, hipMemcpyAsync(boxes_out, e->d_gts_gt_out, (size_t)kept * 7 * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCHK(e, hipMemcpyAsync(classes_out, e->d_gts_cls_out, (size_t)kept * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(e, hipMemcpyAsync(valid_out, e->d_gts_valid_out, (size_t)kept, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(e, hipStreamSynchronize(s));
+    e->h_cur_off.assign(offsets_out, offsets_out + batch + 1);
+    e->cur_max_n = max_n;
+    e->cur_total = (int)n_new;
+    e->zc = false;
+    e->vox_ahead = false;
+    return PP_OK;
+}
+
+int pp_train_step_sample_async(pp_handle e, const float* params_dev, float* grads_dev, float* state_dev,
+                               const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts, int32_t batch,
+                               const pp_loss_config* lc, const pp_target_config* tc, const uint8_t* gt_valid,
+                               const pp_gt_sample_config* sc, const pp_gts_cand* cands, const int32_t* cand_counts,
+                               const pp_augment_config* ac, const pp_aug_frame* frames, const double* box_draws) {
+    if (!e) return PP_ERR_ARG;
+    int64_t total = 0, bound_total = 0;
+    int max_out_n = 0;
+    int st = check_gt(e, "pp_train_step_sample", gt_boxes, gt_classes, gt_counts, batch, tc, &total);
+    if (st == PP_OK)
+        st = check_gts(e, "pp_train_step_sample", gt_counts, batch, sc, cands, cand_counts, &max_out_n, &bound_total);
+    if (st) return st;
+    // the augmentation's draws: frame b has gt_counts[b] + (its largest round) rows, of which the first
+    // gt_counts[b] + accepted are used
+    int64_t rows = 0;
+    if (ac) {
+        if (ac->global_rot_per_object)
+            return fail(e, PP_ERR_UNSUPPORTED, "pp_train_step_sample: global_random_rotation_range_per_object draws depend on "
+                        "the box, which is chosen on the device");
+        e->h_draw_off.assign((size_t)batch, 0);
+        for (int b = 0; b < batch; ++b) {
+            int most = 0;
+            for (int r = 0; r < PP_GTS_MAX_ROUNDS; ++r) most = std::max(most, cand_counts[(size_t)b * PP_GTS_MAX_ROUNDS + r]);
+            e->h_draw_off[(size_t)b] = (int)rows;
+            rows += gt_counts[b] + most;
+        }
+        if ((st = check_aug(e, "pp_train_step_sample", batch, rows, ac, frames, box_draws))) return st;
+    }
+    auto sample = [&]() -> int {
+        int r = enqueue_gt_sample(e, batch, gt_boxes, gt_classes, gt_valid, gt_counts, total, sc, cands, cand_counts, max_out_n,
+                                  e->copy_stream);
+        if (r) return r;
+        // No read-back here: the grown frames become the resident ones by the host-known bound (the tail past a
+        // frame's device-side count is never read), and everything enqueued from here on is sized from it.
+        if (bound_total)
+            HIPCHK(e, hipMemcpyAsync(e->d_points, e->d_aug_pts, (size_t)bound_total * e->F * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+        HIPCHK(e, hipMemcpyAsync(e->d_offsets, e->d_gts_offsets, (size_t)(batch + 1) * sizeof(int), hipMemcpyDeviceToDevice, e->stream));
+        e->cur_max_n = max_out_n;
+        e->cur_total = (int)bound_total;
+        e->off_host_exact = false;
+        e->zc = false;
+        e->vox_ahead = false;
+        if (ac)
+            return enqueue_augment(e, batch, nullptr, nullptr, nullptr, nullptr, rows, ac, frames, box_draws, e->copy_stream,
+                                   &e->h_draw_off);
+        return PP_OK;          // (without augmentation the target kernels read the sampler's boxes where they are)
+    };
+    auto assign = [&]() -> int {
+        return enqueue_targets(e, batch, nullptr, nullptr, nullptr, 0, true, tc, false, nullptr, ac == nullptr);
+    };
+    return train_step_launch(e, params_dev, grads_dev, state_dev, batch, lc, assign, sample);
+}
+
+int pp_train_step_sample(pp_handle e, const float* params_dev, float* grads_dev, float* state_dev, const float* gt_boxes,
+                         const int32_t* gt_classes, const int32_t* gt_counts, int32_t batch, const pp_loss_config* lc,
+                         const pp_target_config* tc, const uint8_t* gt_valid, const pp_gt_sample_config* sc,
+                         const pp_gts_cand* cands, const int32_t* cand_counts, const pp_augment_config* ac,
+                         const pp_aug_frame* frames, const double* box_draws, float* losses) {
+    if (!e) return PP_ERR_ARG;
+    if (!losses) return fail(e, PP_ERR_ARG, "pp_train_step_sample: null argument");
+    int st = pp_train_step_sample_async(e, params_dev, grads_dev, state_dev, gt_boxes, gt_classes, gt_counts, batch, lc, tc,
+                                        gt_valid, sc, cands, cand_counts, ac, frames, box_draws);
+    if (st) return st;
+    return pp_train_step_wait(e, losses);
+}
+
+int pp_gt_sample_info(pp_handle e, int32_t* status, int32_t* point_counts, int32_t* round_used, int32_t batch) {
+    if (!e) return PP_ERR_ARG;
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_gt_sample_info: a training step is in flight");
+    if (e->gts_batch < 1) return fail(e, PP_ERR_STATE, "pp_gt_sample_info: no pp_gt_sample has run");
+    if (batch != e->gts_batch) return fail(e, PP_ERR_ARG, "pp_gt_sample_info: the last pp_gt_sample had %d frames, batch is %d", e->gts_batch, batch);
+    (void)hipSetDevice(e->device);
+    const size_t n = (size_t)batch * PP_GTS_MAX_CAND;
+    if (status) HIPCHK(e, hipMemcpyAsync(status, e->d_gts_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (point_counts) HIPCHK(e, hipMemcpyAsync(point_counts, e->d_gts_counts, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (round_used) HIPCHK(e, hipMemcpyAsync(round_used, e->d_gts_round, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return PP_OK;
+}
+
 int pp_augment_selected(pp_handle e, int32_t* selected, int64_t capacity, int64_t* count) {
     if (!e) return PP_ERR_ARG;
     if (!count || (capacity > 0 && !selected)) return fail(e, PP_ERR_ARG, "pp_augment_selected: null argument");
     if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_augment_selected: a training step is in flight");
+    if (!e->off_host_exact)      // the draw rows were allotted per frame: which of them are boxes is a device value
+        return fail(e, PP_ERR_STATE, "pp_augment_selected: the last augmentation ran inside a sampled training step");
     (void)hipSetDevice(e->device);
     *count = e->aug_total;
     const int64_t n = std::min<int64_t>(capacity, e->aug_total);

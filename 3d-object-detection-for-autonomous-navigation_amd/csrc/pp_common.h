@@ -343,6 +343,7 @@ struct AugParams {
     const uint8_t* valid;      // [sum cnt_in] or NULL (all valid)
     const int* cnt_in;         // [batch]
     const double* draws;       // [sum cnt_in][T][5]
+    const int* draw_off;       // [batch] first draw row of each frame, or NULL: its first box's index
     const AugFrame* frames;    // [batch]
     double* frame_cs;          // [batch][2] cos / sin of the frame's global rotation (k_aug_select -> k_aug_points)
     AugBox* boxrec;            // [batch][PP_MAX_GT_PER_FRAME]
@@ -354,3 +355,39 @@ struct AugParams {
     int* cnt_out;              // [batch]
 };
 void launch_augment(const AugParams& p, int max_n, hipStream_t s);
+
+// gt_sample.hip: GT-database sampling into the resident frames (gt_sampler.py)
+struct GtsPlane { double n[6][3], d[6]; };   // a surviving candidate's 3-D box (outside: p . n + d >= 0)
+struct GtsParams {
+    int batch, F;
+    int max_pc, min_pc;        // sampler_max_point_collision / sampler_min_point_collision
+    const int* offsets;        // [batch + 1] resident frame offsets
+    const float* pts_in;       // [sum n][F] resident points
+    float* pts_out;            // pasted objects' points, then the frame's own, frames back to back
+    int* offsets_out;          // [batch + 1]
+    const float* gt_in;        // [sum cnt_in][7]
+    const int* cls_in;         // [sum cnt_in] or NULL (all 1)
+    const uint8_t* valid_in;   // [sum cnt_in] or NULL (all valid)
+    const int* cnt_in;         // [batch]
+    const pp_gts_cand* cands;  // [batch][PP_GTS_MAX_CAND] the frame's rounds back to back
+    const int* cand_counts;    // [batch][PP_GTS_MAX_ROUNDS]
+    const float* db_pts;       // the database: points [.][F] centred on their box,
+    const int* db_off;         //   [n + 1] point offsets,
+    const double* db_box;      //   [n][7] boxes,
+    const int* db_cls;         //   [n] classes
+    GtsPlane* planes;          // [batch][PP_GTS_MAX_CAND]
+    int* status;               // [batch][PP_GTS_MAX_CAND] pp_gts_status; -1 between the kernels: survived the box test
+    int* counts;               // [batch][PP_GTS_MAX_CAND] frame points inside the candidate's box
+    int* round_used;           // [batch]
+    int* acc_n;                // [batch] accepted objects
+    int* acc_slot;             // [batch][PP_GTS_MAX_CAND] their slots, in order
+    int* acc_pstart;           // [batch][PP_GTS_MAX_CAND + 1] first pasted point of each within the frame
+    int* box_off;              // [2][batch + 1] scratch: first box of each frame, in and out
+    float* gt_out;             // [sum cnt_out][7] the frame's boxes, then the accepted objects'
+    int* cls_out;              // [sum cnt_out]
+    uint8_t* valid_out;        // [sum cnt_out]
+    int* cnt_out;              // [batch]
+};
+// select + count + decide; then paste.  max_n: the largest resident frame; max_out_n: an upper bound of the largest
+// frame after pasting (both host-known)
+void launch_gt_sample(const GtsParams& p, int max_n, int max_out_n, hipStream_t s);

@@ -594,7 +594,8 @@ class Engine:
         self._train_targets = (boxes, classes, counts)   # the copy engine reads them while the forward pass runs
 
     @staticmethod
-    def _aug_args(gt_valid, total, draws, aug_config):
+    def _aug_args(gt_valid, total, draws, aug_config, n_boxes=None):
+        """total: the draw rows; n_boxes: the boxes the flags describe (None: one draw row per box, the same number)."""
         from . import augment
         if aug_config is None:
             aug_config = augment.AugmentConfig.from_input_reader(None)
@@ -609,8 +610,9 @@ class Engine:
             valid = np.ascontiguousarray(np.concatenate([np.asarray(v, bool).reshape(-1) for v in gt_valid])
                                          if len(gt_valid) and not np.isscalar(gt_valid[0]) else np.asarray(gt_valid, bool),
                                          dtype=np.uint8).reshape(-1)
-        if valid is not None and len(valid) != total:
-            raise ValueError(f"gt_valid: {len(valid)} flags for {total} boxes")
+        n_boxes = total if n_boxes is None else n_boxes
+        if valid is not None and len(valid) != n_boxes:
+            raise ValueError(f"gt_valid: {len(valid)} flags for {n_boxes} boxes")
         bd = np.ascontiguousarray(draws.boxes, np.float64)
         if bd.shape[0] != total or (total and bd.shape[1] != aug_config.num_try):
             raise ValueError(f"draws: {bd.shape[:2]} box draws for {total} boxes x {aug_config.num_try} tries")
@@ -649,6 +651,114 @@ class Engine:
         out = np.empty(max(n.value, 1), np.int32)
         self._check(self._lib.pp_augment_selected(self._h, _ptr(out), n.value, ctypes.byref(n)), "pp_augment_selected")
         return out[:n.value].copy()
+
+    # ---- GT-database sampling (pp_gtdb_load / pp_gt_sample) ----
+    def load_gt_database(self, db):
+        """Uploads a gt_sampler.GtDatabase (pp_gtdb_load); it stays on the device until another one replaces it."""
+        from . import gt_sampler
+        if not isinstance(db, gt_sampler.GtDatabase):
+            raise ValueError("db: a gt_sampler.GtDatabase is required")
+        if db.num_point_features != self.d.num_point_features:
+            raise ValueError(f"db: objects have {db.num_point_features} point features, the engine "
+                             f"{self.d.num_point_features}")
+        pts, off = _f32(db.points), np.ascontiguousarray(db.offsets, np.int64)
+        boxes, cls = np.ascontiguousarray(db.boxes, np.float64), _i32(db.classes)
+        self._check(self._lib.pp_gtdb_load(self._h, _ptr(pts), _ptr(off), _ptr(boxes), _ptr(cls), len(db)), "pp_gtdb_load")
+        self._gt_db = db
+
+    def gt_sample(self, gt_boxes, gt_classes=None, gt_valid=None, candidates=None, sampler_config=None):
+        """GT-database sampling into the frames uploaded to this engine, on the GPU (pp_gt_sample; gt_sampler.py lists
+        the rules).  The resident frames are replaced by the sampled ones (a following augment / train step works on
+        them).  gt_boxes / gt_classes / gt_valid per frame as augment; candidates: gt_sampler.draw_candidates(...).
+        Returns per frame (points [n_b + pasted, F], boxes [G_b + K_b, 7], classes, valid)."""
+        from . import gt_sampler
+        db = getattr(self, "_gt_db", None)
+        cfg = sampler_config if sampler_config is not None else (db.config if db is not None else None)
+        if not isinstance(candidates, gt_sampler.Candidates):
+            raise ValueError("candidates: a gt_sampler.Candidates (gt_sampler.draw_candidates) is required")
+        boxes, cls, counts = self.pack_gt(gt_boxes, gt_classes)
+        B, total = len(counts), len(boxes)
+        if len(candidates) != B:
+            raise ValueError(f"candidates: {len(candidates)} frames, gt_boxes: {B}")
+        valid = None
+        if gt_valid is not None:
+            valid = np.ascontiguousarray(np.concatenate([np.asarray(v, bool).reshape(-1) for v in gt_valid] or
+                                                        [np.zeros(0, bool)]), dtype=np.uint8)
+            if len(valid) != total:
+                raise ValueError(f"gt_valid: {len(valid)} flags for {total} boxes")
+        sc = _lib.PPGtSampleConfig()
+        if cfg is not None:
+            sc.max_point_collision, sc.min_point_collision = cfg.max_point_collision, cfg.min_point_collision
+        off = getattr(self, "_offsets", None)
+        n_in = int(off[-1]) if off is not None else 0
+        cap = n_in + (int(np.diff(db.offsets)[candidates.cands["object"].clip(0, len(db) - 1)].sum())
+                      if db is not None and len(db) else 0)
+        F = self.d.num_point_features
+        pts = np.empty((max(cap, 1), F), np.float32)
+        offs = np.zeros((B + 1,), np.int32)
+        rows = total + B * gt_sampler.PP_GTS_MAX_CAND
+        bo, co, vo = np.empty((rows, 7), np.float32), np.empty((rows,), np.int32), np.empty((rows,), np.uint8)
+        cnt = np.empty((B,), np.int32)
+        self._check(self._lib.pp_gt_sample(self._h, _ptr(boxes), _ptr(cls), _ptr(valid), _ptr(counts), B, ctypes.byref(sc),
+                                           candidates.cands.ctypes.data, candidates.counts.ctypes.data, _ptr(pts), cap,
+                                           _ptr(offs), _ptr(bo), _ptr(co), _ptr(vo), _ptr(cnt)), "pp_gt_sample")
+        self._offsets = offs          # the resident frames grew
+        self._gts_batch = B
+        out, g = [], 0
+        for b in range(B):
+            k = int(cnt[b])
+            out.append((pts[offs[b]:offs[b + 1]].copy(), bo[g:g + k].copy(), co[g:g + k].copy(),
+                        vo[g:g + k].astype(bool)))
+            g += k
+        return out
+
+    def train_step_sample_async(self, params_ptr, grads_ptr, state_ptr, boxes, classes, counts, valid, candidates,
+                                sampler_config, draws=None, aug_config=None):
+        """train_step_gt_async on frames sampled -- and, with `draws`, augmented -- on the GPU first
+        (pp_train_step_sample_async): boxes / classes / counts as pack_gt returns them, valid the concatenated flags (or
+        None), candidates a gt_sampler.Candidates; draws: an augment.Draws with counts[b] + (slots of frame b's largest
+        round) box rows per frame."""
+        boxes = _f32(boxes).reshape(-1, 7)
+        counts = _i32(counts).reshape(-1)
+        classes = None if classes is None else _i32(classes).reshape(-1)
+        B = len(counts)
+        if len(candidates) != B:
+            raise ValueError(f"candidates: {len(candidates)} frames, gt_boxes: {B}")
+        sc = _lib.PPGtSampleConfig()
+        sc.max_point_collision, sc.min_point_collision = sampler_config.max_point_collision, sampler_config.min_point_collision
+        ac = frames = bd = None
+        if draws is not None:
+            rows = int((counts + candidates.counts.max(axis=1)).sum())
+            ac, valid, frames, bd = self._aug_args(valid, rows, draws, aug_config, n_boxes=len(boxes))
+        elif valid is not None:
+            if not (isinstance(valid, np.ndarray) and valid.ndim == 1):
+                valid = np.concatenate([np.asarray(v, bool).reshape(-1) for v in valid] or [np.zeros(0, bool)])
+            valid = np.ascontiguousarray(valid, np.uint8).reshape(-1)
+            if len(valid) != len(boxes):
+                raise ValueError(f"gt_valid: {len(valid)} flags for {len(boxes)} boxes")
+        lc, tc = self.loss_config(), self.target_config()
+        self._check(self._lib.pp_train_step_sample_async(
+            self._h, ctypes.c_void_p(int(params_ptr)), ctypes.c_void_p(int(grads_ptr)), ctypes.c_void_p(int(state_ptr)),
+            _ptr(boxes), _ptr(classes), _ptr(counts), B, ctypes.byref(lc), ctypes.byref(tc), _ptr(valid), ctypes.byref(sc),
+            candidates.cands.ctypes.data, candidates.counts.ctypes.data, None if ac is None else ctypes.byref(ac),
+            None if frames is None else frames.ctypes.data, None if bd is None else bd.ctypes.data),
+            "pp_train_step_sample_async")
+        self._train_targets = (boxes, classes, counts, valid, candidates, frames, bd)
+        self._gts_batch = B           # frames of the last sampling (gt_sample_info): a prefetch may replace _offsets
+
+    def gt_sample_info(self):
+        """Parity tap of the last gt_sample / sampled training step (pp_gt_sample_info): per frame and candidate slot its status
+        (gt_sampler.STATUS_NAMES) and the frame points inside its box, and per frame the round that was pasted (-1:
+        none)."""
+        from . import gt_sampler
+        B = getattr(self, "_gts_batch", 0)
+        if B < 1:
+            raise RuntimeError("gt_sample_info: no sampling has run on this engine")
+        st = np.empty((B, gt_sampler.PP_GTS_MAX_CAND), np.int32)
+        pc = np.empty((B, gt_sampler.PP_GTS_MAX_CAND), np.int32)
+        ru = np.empty((B,), np.int32)
+        self._check(self._lib.pp_gt_sample_info(self._h, _ptr(st), _ptr(pc), _ptr(ru), B), "pp_gt_sample_info")
+        return {"status": st, "point_counts": pc, "round_used": ru}
 
     def train_step_aug_async(self, params_ptr, grads_ptr, state_ptr, boxes, classes, counts, valid, draws, aug_config):
         """train_step_gt_async on the frames augmented on the GPU first (pp_train_step_aug_async): boxes / classes /

@@ -103,21 +103,50 @@ class TrainBatch:
     labels = reg_targets = None          # stage(): the dense targets
     gt = None                            # stage_gt(): (boxes, classes or None, counts) as Engine.pack_gt lays them out
     aug = None                           # stage_gt() of an augmenting trainer: (valid flags or None, augment.Draws)
+    cand = None                          # stage_gt() of a sampling trainer: the gt_sampler.Candidates
 
     def close(self):
-        for k in ("points", "_lab", "_reg", "_gtb", "_gtc", "_gtn", "_gtv", "_aug_frames", "_aug_boxes"):
+        for k in ("points", "_lab", "_reg", "_gtb", "_gtc", "_gtn", "_gtv", "_aug_frames", "_aug_boxes", "_cands", "_candn"):
             o = getattr(self, k, None)
             if o is not None:
                 o.close()
                 setattr(self, k, None)
-        self.labels = self.reg_targets = self.gt = self.aug = None
+        self.labels = self.reg_targets = self.gt = self.aug = self.cand = None
 
 
 class Trainer:
     def __init__(self, config, weights, max_batch=None, max_points_per_frame=32768, device=0, learning_rate=None,
-                 weight_decay=None, augment=None, seed=None, frozen=None):
+                 weight_decay=None, augment=None, seed=None, frozen=None, gt_database=None, sampler=None):
+        import random
         import torch
         from . import augment as _augment
+        from . import gt_sampler as _gts
+        # sampler: None / False = off; True = the config's train_input_reader keys (the shipped values without them);
+        # a gt_sampler.SamplerConfig = those settings.  It needs gt_database (a gt_sampler.GtDatabase) and the reverse:
+        # no configuration key turns sampling on by itself.
+        if sampler is True:
+            tir = config.get("train_input_reader") if isinstance(config, dict) else None
+            sampler = _gts.SamplerConfig.from_input_reader(tir)
+            if sampler is None:
+                raise ValueError("sampler=True, but train_input_reader switches sampling off (sample_classes: None)")
+        elif sampler is False:
+            sampler = None
+        elif sampler is not None and not isinstance(sampler, _gts.SamplerConfig):
+            raise ValueError("sampler: None, True or a gt_sampler.SamplerConfig")
+        if (sampler is None) != (gt_database is None):
+            raise ValueError("sampler and gt_database go together: pass both or neither")
+        if gt_database is not None and not isinstance(gt_database, _gts.GtDatabase):
+            raise ValueError("gt_database: a gt_sampler.GtDatabase is required")
+        if augment is not None and augment is not False and sampler is not None:
+            ac = augment if isinstance(augment, _augment.AugmentConfig) else _augment.AugmentConfig.from_input_reader(
+                config.get("train_input_reader") if isinstance(config, dict) else None)
+            if ac.global_rot_per_object:
+                raise ValueError("sampler with global_random_rotation_range_per_object: those draws depend on the box, "
+                                 "which the sampler chooses on the GPU")
+        self.sampler, self.gt_database = sampler, gt_database
+        self.pyrandom = random.Random(seed)
+        self.frames_left_without_boxes = 0     # frames without boxes whose sampling rounds all failed (counted per step)
+        self._boxless = None
         # augment: None / False = off; True = the config's train_input_reader keys (the shipped values without them);
         # an augment.AugmentConfig = those settings
         if augment is True:
@@ -131,6 +160,8 @@ class Trainer:
         self.rs = np.random.RandomState(seed)
         self.torch = torch
         self.engine = Engine(config, max_batch=max_batch, max_points_per_frame=max_points_per_frame, device=device)
+        if gt_database is not None:
+            self.engine.load_gt_database(gt_database)
         self._prefetched = None      # the TrainBatch whose points are already on their way (forward_backward(prefetch=))
         self._ext_stream = None      # torch.cuda.ExternalStream over the engine's stream (_engine_stream)
         self.time_allreduce = False  # True: every step's gradient all-reduce is bracketed by an event pair (allreduce_ms)
@@ -292,10 +323,17 @@ class Trainer:
             st._gtc = self.engine.pinned(cls.shape, np.int32)
             st._gtc.array[...] = cls
         st.gt = (st._gtb.array, st._gtc.array if cls is not None else None, st._gtn.array)
+        if self.sampler is not None:
+            cand = self._draw_candidates(gt_boxes, gt_classes)
+            from . import gt_sampler as _gts
+            st._cands = self.engine.pinned(cand.cands.shape, _gts.CAND_DTYPE)
+            st._cands.array[...] = cand.cands
+            st._candn = self.engine.pinned(cand.counts.shape, np.int32)
+            st._candn.array[...] = cand.counts
+            st.cand = _gts.Candidates(st._cands.array, st._candn.array)
         if self.augment is not None:
             if draws is None:
-                from . import augment as _augment
-                draws = _augment.draw(self.rs, gt_boxes, self.augment)
+                draws = self._draw_augment(gt_boxes, st.cand)
             # the draws in page-locked memory next to the boxes: the step's copies are DMA transfers
             from . import augment as _augment
             if gt_valid is not None:
@@ -311,13 +349,40 @@ class Trainer:
             draws = _augment.Draws(draws.flip, draws.theta, draws.scale, draws.t, draws.seed, st._aug_boxes.array,
                                    draws.counts, frames=st._aug_frames.array)
             st.aug = (gt_valid, draws)
-        elif gt_valid is not None or draws is not None:
-            raise ValueError("gt_valid / draws need a trainer with augment on")
+        elif draws is not None:
+            raise ValueError("draws need a trainer with augment on")
+        elif gt_valid is not None:
+            if self.sampler is None:
+                raise ValueError("gt_valid needs a trainer with augment or sampler on")
+            v = np.concatenate([np.asarray(x, bool).reshape(-1) for x in gt_valid] or [np.zeros(0, bool)])
+            st._gtv = self.engine.pinned(v.shape, np.uint8)
+            st._gtv.array[...] = v
+            st.aug = (st._gtv.array, None)       # the flags ride through the sampling; no draws
         return st
 
-    def _enqueue_step(self, labels, reg_targets, gt, aug=None):
+    def _draw_candidates(self, gt_boxes, gt_classes):
+        from . import gt_sampler as _gts
+        cls = [np.ones(len(np.asarray(g).reshape(-1, 7)), np.int32) for g in gt_boxes] if gt_classes is None else gt_classes
+        return _gts.draw_candidates(self.gt_database, cls, self.pyrandom)
+
+    def _draw_augment(self, gt_boxes, cand):
+        """The augmentation draws of a batch; on a sampling trainer for counts[b] + (slots of frame b's largest round)
+        rows per frame, of which the step uses the first counts[b] + accepted."""
+        from . import augment as _augment
+        if cand is not None:
+            extra = cand.counts.max(axis=1)
+            gt_boxes = [np.concatenate([np.asarray(g, np.float64).reshape(-1, 7), np.zeros((int(x), 7))], 0)
+                        for g, x in zip(gt_boxes, extra)]
+        return _augment.draw(self.rs, gt_boxes, self.augment)
+
+    def _enqueue_step(self, labels, reg_targets, gt, aug=None, cand=None):
         ptrs = (self.params.data_ptr(), self.grads.data_ptr(), self.state.data_ptr())
-        if aug is not None:
+        self._boxless = None
+        if cand is not None:
+            valid, draws = aug if aug is not None else (None, None)
+            self.engine.train_step_sample_async(*ptrs, *gt, valid, cand, self.sampler, draws, self.augment)
+            self._boxless = np.flatnonzero(np.asarray(gt[2]) == 0)
+        elif aug is not None:
             self.engine.train_step_aug_async(*ptrs, *gt, aug[0], aug[1], self.augment)
         elif gt is not None:
             self.engine.train_step_gt_async(*ptrs, *gt)
@@ -336,7 +401,9 @@ class Trainer:
             self._prefetched = None
             if self.augment is not None and tb.aug is None:
                 raise ValueError("an augmenting trainer trains on stage_gt() batches (dense labels cannot follow moved boxes)")
-            self._enqueue_step(tb.labels, tb.reg_targets, tb.gt, tb.aug)
+            if self.sampler is not None and tb.cand is None:
+                raise ValueError("a sampling trainer trains on stage_gt() batches (dense labels cannot follow pasted objects)")
+            self._enqueue_step(tb.labels, tb.reg_targets, tb.gt, tb.aug, tb.cand)
             if isinstance(prefetch, TrainBatch):
                 self.engine.upload_async(prefetch.points)
                 self._prefetched = prefetch
@@ -350,17 +417,23 @@ class Trainer:
                 raise ValueError(f"{len(frames)} frames but boxes for {len(gt[2])}")
         elif gt_classes is not None:
             raise ValueError("gt_classes needs gt_boxes")
-        aug = None
+        aug = cand = None
+        if self.sampler is not None:
+            if gt is None:
+                raise ValueError("sampling needs gt_boxes= (dense labels cannot follow pasted objects)")
+            cand = self._draw_candidates(gt_boxes, gt_classes)
         if self.augment is not None:
             if gt is None:
                 raise ValueError("augmentation needs gt_boxes= (dense labels cannot follow moved boxes)")
-            from . import augment as _augment
-            aug = (gt_valid, _augment.draw(self.rs, gt_boxes, self.augment))
+            aug = (gt_valid, self._draw_augment(gt_boxes, cand))
+        elif gt_valid is not None and cand is None:
+            raise ValueError("gt_valid needs a trainer with augment or sampler on")
         elif gt_valid is not None:
-            raise ValueError("gt_valid needs a trainer with augment on")
+            v = np.concatenate([np.asarray(x, bool).reshape(-1) for x in gt_valid] or [np.zeros(0, bool)])
+            aug = (np.ascontiguousarray(v, np.uint8), None)      # the flags ride through the sampling; no draws
         self._prefetched = None
         self.engine.upload(frames)
-        self._enqueue_step(labels, reg_targets, gt, aug)
+        self._enqueue_step(labels, reg_targets, gt, aug, cand)
 
     def forward_backward(self, frames, labels=None, reg_targets=None, prefetch=None, gt_boxes=None, gt_classes=None,
                          gt_valid=None):
@@ -370,7 +443,16 @@ class Trainer:
         stream) while this step's kernels run, the loader's hand-over of train.py:228-304; pass that same batch as
         `frames` of the next call."""
         self._launch(frames, labels, reg_targets, prefetch, gt_boxes, gt_classes, gt_valid)
-        return self.engine.train_step_wait()
+        return self._wait()
+
+    def _wait(self):
+        losses = self.engine.train_step_wait()
+        if self._boxless is not None and len(self._boxless):
+            # frames that came without boxes: the sampler's rounds may all have failed (the reference would go on trying)
+            used = self.engine.gt_sample_info()["round_used"]
+            self.frames_left_without_boxes += int((used[self._boxless] < 0).sum())
+        self._boxless = None
+        return losses
 
     def _engine_stream(self):
         """torch's view of the engine's own stream: the all-reduce and the AdamW kernel are enqueued THERE, behind the
@@ -415,7 +497,7 @@ class Trainer:
             # and forget the prefetch -- the next call uploads its batch itself
             self._abandon_step()
             raise
-        return self.engine.train_step_wait()
+        return self._wait()
 
     def _abandon_step(self):
         self._prefetched = None

@@ -30,7 +30,9 @@ extern "C" {
 /* 3: PP_ERR_NUMERIC, pp_set_gemm_precision / pp_get_gemm_precision, pp_set_cache_budget.  4: pp_train_fetch_decisions;
  * later additions within 4 (nothing before them changed): pp_target_config, pp_assign_targets, pp_train_step_gt_async,
  * pp_train_step_gt; then PP_AUG_MAX_TRY, pp_augment_config, pp_aug_frame, pp_augment, pp_train_step_aug_async,
- * pp_train_step_aug, pp_augment_selected; then pp_train_set_frozen, pp_adamw_step_segments_device. */
+ * pp_train_step_aug, pp_augment_selected; then pp_train_set_frozen, pp_adamw_step_segments_device; then PP_GTS_MAX_CAND,
+ * PP_GTS_MAX_ROUNDS, pp_gt_sample_config, pp_gts_cand, pp_gtdb_load, pp_gt_sample, pp_gt_sample_info,
+ * pp_train_step_sample_async, pp_train_step_sample. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -436,8 +438,94 @@ int pp_train_step_aug(pp_handle h, const float* params_dev, float* grads_dev, fl
 
 /* Parity tap of the last augmentation (pp_augment or pp_train_step_aug*, after it finished): the try each input box
  * took, -1 for none and for an invalid box, in the order of gt_boxes.  *count = the number of input boxes; at most
- * `capacity` values are written. */
+ * `capacity` values are written.  PP_ERR_STATE after a pp_train_step_sample* (its draw rows are allotted per frame; which
+ * of them belong to boxes is known on the device only). */
 int pp_augment_selected(pp_handle h, int32_t* selected, int64_t capacity, int64_t* count);
+
+/* ---- GT-database sampling (SURVEY section 8f, row 15 -- the loader's first step) ------------------------------------ */
+/* prep_pointcloud's sampling step (load_data.py:2702-2751: sample_all :1690-1921 on the BatchSamplers' candidates
+ * :1344-1409): stored objects are pasted into the resident frames where they collide with no box (box_collision_test as
+ * pp_augment executes it) and pass the point test against the frame's original points.  Which objects are candidates
+ * and the `low` coin of every slot come from the caller (<package>/gt_sampler.py draw_candidates: the reference's
+ * cursor and getrandbits calls); every decision is taken in float64 in the reference's operation order, a pasted point
+ * is its stored float32 value plus the float64 box centre, rounded to float32 once.
+ * Deviation: a frame without boxes is retried at most PP_GTS_MAX_ROUNDS times (the reference: without limit); a frame
+ * whose rounds all fail comes back unchanged. */
+#define PP_GTS_MAX_CAND 32   /* candidate slots per frame, all classes and rounds together */
+#define PP_GTS_MAX_ROUNDS 4  /* rounds drawn per frame; a frame that has boxes uses the first only */
+
+/* status of a candidate slot (pp_gt_sample_info) */
+enum pp_gts_status {
+    PP_GTS_ACCEPTED = 0,
+    PP_GTS_BOX_COLLISION = 1,   /* hit a frame box, an accepted earlier object or a candidate of its group not yet walked */
+    PP_GTS_TOO_MANY_POINTS = 2, /* frame points inside >= max_point_collision */
+    PP_GTS_TOO_FEW_POINTS = 3,  /* fewer than min_point_collision and not (nearer than 2.5 m with its `low` coin set) */
+    PP_GTS_EMPTY_OBJECT = 4,    /* the stored object has no points */
+    PP_GTS_ROUND_NOT_USED = 5   /* a later round of a frame that has boxes, or behind the round that succeeded */
+};
+
+typedef struct pp_gt_sample_config {
+    int32_t max_point_collision;  /* train_input_reader.sampler_max_point_collision (500) */
+    int32_t min_point_collision;  /* ...sampler_min_point_collision (1) */
+    int32_t reserved[2];          /* 0 */
+} pp_gt_sample_config;
+
+/* One candidate slot of a frame's round. */
+typedef struct pp_gts_cand {
+    int32_t object;   /* index into the loaded database */
+    int32_t group;    /* position of its class in sample_classes: groups are walked in ascending order, a later group
+                         avoids the objects accepted for the earlier ones; non-decreasing within a round */
+    int32_t low;      /* the `low` coin of the k-th SURVIVOR of the box test of this round, k = this slot's position in
+                         its round (the reference draws it per survivor, in order) */
+    int32_t reserved; /* 0 */
+} pp_gts_cand;
+
+/* Uploads the object database (replaces the one loaded before; freed with the handle): points [point_offsets[n], F] float32
+ * centred on their box, point_offsets [n + 1], boxes [n, 7] float64 x y z w l h r (after BatchSampler.random_translate),
+ * classes [n] (1..num_class).  The points have the handle's num_point_features columns; the call cannot check that (a
+ * buffer of another width is read with the wrong stride).  PP_ERR_ARG for non-monotone offsets, a non-finite box, a size <= 0 or a class outside
+ * 1..num_class.  Waits for the handle's stream. */
+int pp_gtdb_load(pp_handle h, const float* points, const int64_t* point_offsets, const double* boxes,
+                 const int32_t* classes, int64_t n);
+
+/* Samples into the RESIDENT frames, which the result replaces (pasted points first, then the frame's own), and returns
+ * them with their boxes.  gt_boxes / gt_classes / gt_valid / gt_counts as pp_augment (invalid boxes are obstacles like
+ * the others and keep their flag).  cands [batch][PP_GTS_MAX_CAND]: the frame's rounds back to back; cand_counts
+ * [batch][PP_GTS_MAX_ROUNDS]: slots per round (sum <= PP_GTS_MAX_CAND).  Outputs (host): points_out with room for
+ * sum(n_b) + the points of every candidate, offsets_out [batch + 1], boxes_out / classes_out / valid_out with room for
+ * sum(gt_counts) + batch * PP_GTS_MAX_CAND rows, counts_out [batch].  PP_ERR_STATE without a database; PP_ERR_ARG for
+ * what pp_augment refuses in the boxes, an object index outside the database, groups out of order, a frame whose points
+ * plus those of one round's candidates exceed max_points_per_frame, or whose boxes plus one round's candidates exceed
+ * PP_MAX_GT_PER_FRAME -- before anything is launched; the handle stays usable.  Synchronous. */
+int pp_gt_sample(pp_handle h, const float* gt_boxes, const int32_t* gt_classes, const uint8_t* gt_valid,
+                 const int32_t* gt_counts, int32_t batch, const pp_gt_sample_config* sc, const pp_gts_cand* cands,
+                 const int32_t* cand_counts, float* points_out, int64_t points_capacity, int32_t* offsets_out,
+                 float* boxes_out, int32_t* classes_out, uint8_t* valid_out, int32_t* counts_out);
+
+/* pp_train_step_gt_async / pp_train_step_gt on frames sampled -- and, with ac != NULL, augmented -- on the GPU first: plain
+ * launches on the handle's stream ahead of the forward half; the targets are assigned from the final boxes.  Exactly what
+ * pp_gt_sample, then pp_augment on its outputs, then pp_train_step_gt on theirs compute.  Nothing is read back in
+ * between: everything behind the sampling is sized from its bound (pp_gt_sample's refusals apply), and the handle then
+ * knows the resident frames' sizes on the device only -- pp_gt_sample and pp_augment return PP_ERR_STATE until the next
+ * upload.  box_draws: frame b has gt_counts[b] + (the slots of its largest round) rows of [num_try][5], of which the first
+ * gt_counts[b] + accepted are used, in the order of pp_gt_sample's boxes_out.  PP_ERR_UNSUPPORTED with
+ * ac->global_rot_per_object (those draws depend on the box, which is chosen on the device).  The host arrays must stay
+ * unchanged until pp_train_step_wait returns. */
+int pp_train_step_sample_async(pp_handle h, const float* params_dev, float* grads_dev, float* state_dev,
+                               const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts, int32_t batch,
+                               const pp_loss_config* lc, const pp_target_config* tc, const uint8_t* gt_valid,
+                               const pp_gt_sample_config* sc, const pp_gts_cand* cands, const int32_t* cand_counts,
+                               const pp_augment_config* ac, const pp_aug_frame* frames, const double* box_draws);
+int pp_train_step_sample(pp_handle h, const float* params_dev, float* grads_dev, float* state_dev, const float* gt_boxes,
+                         const int32_t* gt_classes, const int32_t* gt_counts, int32_t batch, const pp_loss_config* lc,
+                         const pp_target_config* tc, const uint8_t* gt_valid, const pp_gt_sample_config* sc,
+                         const pp_gts_cand* cands, const int32_t* cand_counts, const pp_augment_config* ac,
+                         const pp_aug_frame* frames, const double* box_draws, float* losses);
+
+/* Parity tap of the last pp_gt_sample: per candidate slot [batch][PP_GTS_MAX_CAND] its enum pp_gts_status (slots past a
+ * round's count: PP_GTS_ROUND_NOT_USED) and the number of the frame's original points inside its box (0 for a slot that
+ * did not survive the box test); round_used [batch]: the round whose objects were pasted, -1 for none. */
+int pp_gt_sample_info(pp_handle h, int32_t* status, int32_t* point_counts, int32_t* round_used, int32_t batch);
 
 /* The handle's HIP stream (hipStream_t as void*).  A caller that enqueues its own device work behind a pp_train_step_async
  * -- the gradient all-reduce and pp_adamw_step_device of the optimizer step (train.py:301) -- does it on this stream and
