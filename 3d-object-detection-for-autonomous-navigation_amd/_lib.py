@@ -18,7 +18,7 @@ _INCLUDE = os.path.join(os.path.dirname(_PKG), "include", "pp_hip.h")
 SO_PATH = os.path.join(_PKG, os.environ.get("PP_HIP_LIB", "libpp_hip.so"))
 _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
 SOURCES = ["pp_api.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
-           "rotate_iou.hip", "loss.hip", "optim.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip"]
+           "rotate_iou.hip", "loss.hip", "optim.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
@@ -38,6 +38,7 @@ EXPORTS = [
     "pp_augment", "pp_train_step_aug_async", "pp_train_step_aug", "pp_augment_selected",
     "pp_train_set_frozen", "pp_adamw_step_segments_device",
     "pp_gtdb_load", "pp_gt_sample", "pp_gt_sample_info", "pp_train_step_sample_async", "pp_train_step_sample",
+    "pp_ingest_pointcloud2", "pp_ingest_pointcloud2_async", "pp_ingest_info",
 ]
 
 
@@ -114,6 +115,31 @@ class PPGtsCand(ctypes.Structure):
         ("group", ctypes.c_int32),
         ("low", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
+    ]
+
+
+class PPPc2Layout(ctypes.Structure):
+    _fields_ = [
+        ("width", ctypes.c_int32),
+        ("height", ctypes.c_int32),
+        ("point_step", ctypes.c_int32),
+        ("row_step", ctypes.c_int32),
+        ("x_offset", ctypes.c_int32),
+        ("y_offset", ctypes.c_int32),
+        ("z_offset", ctypes.c_int32),
+        ("datatype", ctypes.c_int32),
+        ("is_bigendian", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class PPIngestConfig(ctypes.Structure):
+    _fields_ = [
+        ("first", ctypes.c_int32),
+        ("decimate", ctypes.c_int32),
+        ("r", ctypes.c_double * 9),
+        ("r2", ctypes.c_double * 9),
+        ("lift", ctypes.c_double * 3),
     ]
 
 
@@ -308,6 +334,9 @@ def lib():
     L.pp_train_step_sample.argtypes = [vp, vp, vp, vp, f32p, vp, vp, i32, ctypes.POINTER(PPLossConfig),
                                        ctypes.POINTER(PPTargetConfig), vp, ctypes.POINTER(PPGtSampleConfig), vp, vp,
                                        ctypes.POINTER(PPAugmentConfig), vp, vp, f32p]
+    L.pp_ingest_pointcloud2.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(PPIngestConfig), f32p, i64]
+    L.pp_ingest_pointcloud2_async.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(PPIngestConfig)]
+    L.pp_ingest_info.argtypes = [vp, vp, vp, i32]
     for name in EXPORTS:
         fn = getattr(L, name)  # raises AttributeError if the symbol is not exported
         if name not in ("pp_last_error", "pp_layer_tag"):

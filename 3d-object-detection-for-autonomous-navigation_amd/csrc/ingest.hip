@@ -1,0 +1,181 @@
+// Live-camera ingest (pp_ingest_pointcloud2*): raw sensor_msgs/PointCloud2 bytes -> the float32 [sum n_b, 3] lidar-frame
+// points and the frame offsets the voxeliser reads, without the host touching a point.  Restates
+// ingest.pointcloud2_to_xyz(...)[first::decimate] followed by ingest.realsense_to_lidar (load_data.py:2433-2443):
+//
+//   record i = row * width + col of a frame sits at row * row_step + col * point_step; x y z are read at their field
+//   offsets (FLOAT32 or FLOAT64, either byte order, no alignment assumed);
+//   a record is finite when its three coordinates are; rank = finite records before it in message order;
+//   it is kept when finite, rank >= first and (rank - first) % decimate == 0, as output row (rank - first) / decimate;
+//   a kept point becomes ((p . r) . r2) + lift in float64 -- every 3-term dot product summed left to right, no fused
+//   multiply-add, which is what numpy's dot computes for these shapes -- and is rounded to float32 once.
+//
+// Three launches, ordered by the stream alone (no workgroup waits for another):
+//   k_ingest_count    one wave per chunk of ING_CHUNK records: ballot + popcount of the finite flags -> chunk counts
+//   k_ingest_scan     one workgroup: a wave per frame scans its chunk counts -> chunk bases, the frame's finite and kept
+//                     counts; then the frame offsets
+//   k_ingest_scatter  re-reads the chunks; a finite record's rank is its chunk's base + the finite lanes below it
+#include "pp_common.h"
+
+namespace {
+
+constexpr int ING_ITER = 8;                       // 64-record steps of a wave
+constexpr int ING_CHUNK = PP_WAVE * ING_ITER;     // records per chunk (one wave)
+constexpr int ING_WAVES = 4;                      // chunks per workgroup
+
+// four bytes at any address (nothing in a message is assumed to sit on a boundary): one unaligned dword load
+__device__ __forceinline__ uint32_t ing_load32(const uint8_t* p) {
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
+}
+
+// one coordinate as float64 (a float32 field widens exactly)
+__device__ __forceinline__ double ing_coord(const uint8_t* p, const IngFrame& f) {
+    if (f.f64) {
+        const uint32_t a = ing_load32(p), b = ing_load32(p + 4);
+        unsigned long long v = ((unsigned long long)b << 32) | a;
+        if (f.big_endian) v = __builtin_bswap64(v);
+        return __longlong_as_double((long long)v);
+    }
+    uint32_t v = ing_load32(p);
+    if (f.big_endian) v = __builtin_bswap32(v);
+    return (double)__uint_as_float(v);
+}
+
+__device__ __forceinline__ bool ing_finite(double v) {
+    return (((unsigned long long)__double_as_longlong(v) >> 52) & 0x7ffull) != 0x7ffull;
+}
+
+__device__ __forceinline__ const uint8_t* ing_record(const uint8_t* base, const IngFrame& f, int i) {
+    // (the host hands a frame whose rows are tight over as ONE row: no division then)
+    if (f.width >= f.n_rec) return base + (long long)i * f.point_step;
+    const int row = i / f.width, col = i - row * f.width;
+    return base + (long long)row * f.row_step + (long long)col * f.point_step;
+}
+
+__device__ __forceinline__ bool ing_read(const uint8_t* base, const IngFrame& f, int i, double p[3]) {
+    const uint8_t* rec = ing_record(base, f, i);
+    p[0] = ing_coord(rec + f.x_off, f);
+    p[1] = ing_coord(rec + f.y_off, f);
+    p[2] = ing_coord(rec + f.z_off, f);
+    return ing_finite(p[0]) && ing_finite(p[1]) && ing_finite(p[2]);
+}
+
+__global__ __launch_bounds__(PP_WAVE * ING_WAVES) void k_ingest_count(const uint8_t* __restrict__ raw,
+                                                                     const IngFrame* __restrict__ frames, int stride,
+                                                                     int* __restrict__ chunk_cnt) {
+    const int b = blockIdx.y;
+    const IngFrame f = frames[b];
+    const int lane = threadIdx.x & (PP_WAVE - 1);
+    const int c = blockIdx.x * ING_WAVES + (threadIdx.x >> 6);
+    if (c >= f.nchunks) return;                    // (the same for every lane of the wave)
+    const uint8_t* base = raw + f.byte_off;
+    int cnt = 0;
+#pragma unroll 2
+    for (int k = 0; k < ING_ITER; ++k) {
+        const int i = c * ING_CHUNK + k * PP_WAVE + lane;
+        double p[3];
+        const bool fin = i < f.n_rec && ing_read(base, f, i, p);
+        cnt += __popcll(__ballot(fin));
+    }
+    if (lane == 0) chunk_cnt[(size_t)b * stride + c] = cnt;
+}
+
+// One workgroup of 16 waves; wave w scans frames w, w + 16, ...; thread 0 then sums the kept counts into the offsets.
+__global__ __launch_bounds__(1024) void k_ingest_scan(const IngFrame* __restrict__ frames, int batch, int stride,
+                                                      int first, int decimate, const int* __restrict__ chunk_cnt,
+                                                      int* __restrict__ chunk_base, int* __restrict__ finite,
+                                                      int* __restrict__ kept, int* __restrict__ offsets) {
+    const int lane = threadIdx.x & (PP_WAVE - 1), wave = threadIdx.x >> 6;
+    for (int b = wave; b < batch; b += 16) {
+        const int nchunks = frames[b].nchunks;
+        int carry = 0;
+        for (int c0 = 0; c0 < nchunks; c0 += PP_WAVE) {
+            const int c = c0 + lane;
+            const int v = c < nchunks ? chunk_cnt[(size_t)b * stride + c] : 0;
+            const int incl = wave_inclusive_scan(v);
+            if (c < nchunks) chunk_base[(size_t)b * stride + c] = carry + incl - v;
+            carry += __builtin_amdgcn_readlane(incl, PP_WAVE - 1);
+        }
+        if (lane == 0) {
+            finite[b] = carry;
+            kept[b] = carry > first ? (carry - first + decimate - 1) / decimate : 0;
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int off = 0;
+        offsets[0] = 0;
+        for (int b = 0; b < batch; ++b) { off += kept[b]; offsets[b + 1] = off; }
+    }
+}
+
+struct IngXform { double r[9], r2[9], lift[3]; };
+
+// ((p . r) . r2) + lift, each sum left to right, products and sums rounded separately
+__device__ __forceinline__ void ing_transform(const double p[3], const IngXform& x, float out[3]) {
+#pragma clang fp contract(off)
+    double q[3], s[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) q[j] = (p[0] * x.r[j] + p[1] * x.r[3 + j]) + p[2] * x.r[6 + j];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) s[j] = (q[0] * x.r2[j] + q[1] * x.r2[3 + j]) + q[2] * x.r2[6 + j];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) out[j] = (float)(s[j] + x.lift[j]);
+}
+
+__global__ __launch_bounds__(PP_WAVE * ING_WAVES) void k_ingest_scatter(const uint8_t* __restrict__ raw,
+                                                                       const IngFrame* __restrict__ frames, int stride,
+                                                                       int first, int decimate, IngXform xf,
+                                                                       const int* __restrict__ chunk_base,
+                                                                       const int* __restrict__ offsets,
+                                                                       float* __restrict__ out, long long out_rows) {
+    const int b = blockIdx.y;
+    const IngFrame f = frames[b];
+    const int lane = threadIdx.x & (PP_WAVE - 1);
+    const int c = blockIdx.x * ING_WAVES + (threadIdx.x >> 6);
+    if (c >= f.nchunks) return;
+    const uint8_t* base = raw + f.byte_off;
+    const long long row0 = offsets[b];
+    int run = chunk_base[(size_t)b * stride + c];
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int k = 0; k < ING_ITER; ++k) {
+        const int i = c * ING_CHUNK + k * PP_WAVE + lane;
+        double p[3];
+        const bool fin = i < f.n_rec && ing_read(base, f, i, p);
+        const unsigned long long m = __ballot(fin);
+        const int r = run + __popcll(m & below) - first;
+        run += __popcll(m);
+        if (fin && r >= 0 && r % decimate == 0) {
+            const long long row = row0 + r / decimate;
+            if (row < out_rows) {                  // (always: the host sized the call from the frames' bounds)
+                float o[3];
+                ing_transform(p, xf, o);
+                out[row * 3 + 0] = o[0];
+                out[row * 3 + 1] = o[1];
+                out[row * 3 + 2] = o[2];
+            }
+        }
+    }
+}
+
+}  // namespace
+
+int ingest_chunks(int n_rec) { return (n_rec + ING_CHUNK - 1) / ING_CHUNK; }
+
+void launch_ingest(const IngestParams& p, hipStream_t s) {
+    if (p.batch <= 0) return;
+    const dim3 grid((p.stride + ING_WAVES - 1) / ING_WAVES, p.batch), block(PP_WAVE * ING_WAVES);
+    if (p.stride > 0)
+        PP_LAUNCH("k_ingest_count", k_ingest_count, grid, block, 0, s, p.raw, p.frames, p.stride, p.chunk_cnt);
+    PP_LAUNCH("k_ingest_scan", k_ingest_scan, dim3(1), dim3(1024), 0, s, p.frames, p.batch, p.stride, p.first, p.decimate,
+              p.chunk_cnt, p.chunk_base, p.finite, p.kept, p.offsets);
+    if (p.stride > 0) {
+        IngXform xf;
+        for (int i = 0; i < 9; ++i) { xf.r[i] = p.r[i]; xf.r2[i] = p.r2[i]; }
+        for (int i = 0; i < 3; ++i) xf.lift[i] = p.lift[i];
+        PP_LAUNCH("k_ingest_scatter", k_ingest_scatter, grid, block, 0, s, p.raw, p.frames, p.stride, p.first, p.decimate,
+                  xf, p.chunk_base, p.offsets, p.out, p.out_rows);
+    }
+}

@@ -158,6 +158,14 @@ struct pp_engine {
     uint8_t* d_gts_valid_out = nullptr;
     int* d_gts_cnt_out = nullptr;
     int gts_batch = 0;                 // frames of the last pp_gt_sample (pp_gt_sample_info)
+    // live PointCloud2 ingest (pp_ingest_pointcloud2*, ingest.hip): allocated on first use; the byte staging and the
+    // chunk tables grow to the largest call seen
+    uint8_t* d_ing_raw = nullptr;  size_t cap_ing_raw = 0;       // the messages' bytes
+    int* d_ing_chunks = nullptr;   size_t cap_ing_chunks = 0;    // [2][batch * stride]: chunk counts, chunk bases
+    IngFrame* d_ing_frames = nullptr;  // [B]
+    IngFrame* h_ing_ring = nullptr;    // pinned [OFF_RING][B]: travels with the offsets' ring slots
+    int *d_ing_finite = nullptr, *d_ing_kept = nullptr;          // [B]
+    int ing_batch = 0;                 // frames of the last ingest (pp_ingest_info)
     int* d_tgt_index = nullptr;        // [B][A] optional outputs of pp_assign_targets, allocated on first use
     float* d_tgt_overlap = nullptr;
     float* d_calib = nullptr;
@@ -989,6 +997,9 @@ int pp_destroy(pp_handle e) {
     }
     delete e->train;
     if (e->h_off_ring) (void)hipHostFree(e->h_off_ring);
+    if (e->h_ing_ring) (void)hipHostFree(e->h_ing_ring);
+    if (e->d_ing_raw) (void)hipFree(e->d_ing_raw);
+    if (e->d_ing_chunks) (void)hipFree(e->d_ing_chunks);
     for (hipEvent_t ev : e->off_ev) if (ev) (void)hipEventDestroy(ev);
     if (e->ev_in) (void)hipEventDestroy(e->ev_in);
     for (PpFeed* f : e->h_feed) if (f) (void)hipHostFree(f);
@@ -1320,6 +1331,201 @@ int pp_upload_points_device(pp_handle e, const void* points_dev, const int32_t* 
         HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_in, 0));
     }
     if (n) HIPCHK(e, hipMemcpyAsync(e->d_points, points_dev, n * e->F * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+    return PP_OK;
+}
+
+// ---- live PointCloud2 ingest (ingest.hip) ----
+
+namespace {
+
+struct IngestPlan {
+    std::vector<IngFrame> frames;
+    std::vector<int> bound_off;    // [batch + 1] prefix sums of the frames' kept bounds
+    int max_bound = 0, stride = 0;
+    int64_t bytes = 0;             // byte_offsets[batch] - byte_offsets[0]
+};
+
+// Everything pp_ingest_pointcloud2* refuses, before anything is queued.
+int check_ingest(pp_engine* e, const char* who, const uint8_t* data, const int64_t* bo, const pp_pc2_layout* L, int batch,
+                 const pp_ingest_config* c, IngestPlan* plan) {
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "%s: a training step is in flight", who);
+    if (e->F != 3)
+        return fail(e, PP_ERR_UNSUPPORTED, "%s: num_point_features is %d, the live path delivers x y z only (3)", who, e->F);
+    if (!bo || !L || !c) return fail(e, PP_ERR_ARG, "%s: null argument", who);
+    int st = check_batch(e, batch); if (st) return st;
+    if (c->decimate < 1) return fail(e, PP_ERR_ARG, "%s: decimate %d < 1", who, c->decimate);
+    if (c->first < 0) return fail(e, PP_ERR_ARG, "%s: first %d < 0", who, c->first);
+    plan->frames.assign((size_t)batch, IngFrame());
+    plan->bound_off.assign((size_t)batch + 1, 0);
+    for (int b = 0; b < batch; ++b) {
+        const pp_pc2_layout& l = L[b];
+        if (l.width < 0 || l.height < 0 || l.point_step < 1 || l.row_step < 0)
+            return fail(e, PP_ERR_ARG, "%s: frame %d: width %d, height %d, point_step %d, row_step %d", who, b, l.width,
+                        l.height, l.point_step, l.row_step);
+        const int64_t n_rec = (int64_t)l.width * l.height;
+        if (n_rec > (1ll << 30)) return fail(e, PP_ERR_ARG, "%s: frame %d: width %d x height %d records", who, b, l.width, l.height);
+        if (l.datatype >> 8)
+            return fail(e, PP_ERR_UNSUPPORTED, "%s: frame %d: datatype: x, y and z differ (%d, %d, %d)", who, b,
+                        l.datatype & 255, (l.datatype >> 8) & 255, (l.datatype >> 16) & 255);
+        if (l.datatype >= 1 && l.datatype <= 6)
+            return fail(e, PP_ERR_UNSUPPORTED, "%s: frame %d: datatype %d is an integer type (7 FLOAT32 or 8 FLOAT64)", who, b, l.datatype);
+        if (l.datatype != 7 && l.datatype != 8)
+            return fail(e, PP_ERR_ARG, "%s: frame %d: unknown datatype %d", who, b, l.datatype);
+        const int size = l.datatype == 8 ? 8 : 4;
+        const int offs[3] = {l.x_offset, l.y_offset, l.z_offset};
+        static const char* const names[3] = {"x_offset", "y_offset", "z_offset"};
+        for (int k = 0; k < 3; ++k)
+            if (offs[k] < 0 || (int64_t)offs[k] + size > l.point_step)
+                return fail(e, PP_ERR_ARG, "%s: frame %d: %s %d (%d bytes) does not fit point_step %d", who, b, names[k], offs[k],
+                            size, l.point_step);
+        if ((int64_t)l.row_step < (int64_t)l.width * l.point_step)
+            return fail(e, PP_ERR_ARG, "%s: frame %d: row_step %d < width %d x point_step %d", who, b, l.row_step, l.width, l.point_step);
+        const int64_t need = (int64_t)l.height * l.row_step;
+        if (bo[b] < 0 || bo[b + 1] < bo[b] || bo[b + 1] - bo[b] < need)
+            return fail(e, PP_ERR_ARG, "%s: frame %d: byte_offsets give it %lld bytes, height %d x row_step %d = %lld needed", who, b,
+                        (long long)(bo[b + 1] - bo[b]), l.height, l.row_step, (long long)need);
+        const int64_t bound = n_rec > c->first ? (n_rec - c->first + c->decimate - 1) / c->decimate : 0;
+        if (bound > e->NMAX)
+            return fail(e, PP_ERR_ARG, "%s: frame %d: width %d x height %d keeps up to %lld points > max_points_per_frame=%d", who, b,
+                        l.width, l.height, (long long)bound, e->NMAX);
+        IngFrame& f = plan->frames[(size_t)b];
+        f.byte_off = bo[b] - bo[0];
+        f.n_rec = (int)n_rec;
+        const bool tight = l.row_step == l.width * l.point_step || l.height <= 1;
+        f.width = tight ? (int)n_rec : l.width;
+        f.point_step = l.point_step; f.row_step = l.row_step;
+        f.x_off = l.x_offset; f.y_off = l.y_offset; f.z_off = l.z_offset;
+        f.f64 = l.datatype == 8; f.big_endian = l.is_bigendian != 0;
+        f.nchunks = ingest_chunks(f.n_rec);
+        plan->stride = std::max(plan->stride, f.nchunks);
+        plan->max_bound = std::max(plan->max_bound, (int)bound);
+        plan->bound_off[(size_t)b + 1] = plan->bound_off[(size_t)b] + (int)bound;
+    }
+    plan->bytes = bo[batch] - bo[0];
+    if (plan->bytes > 0 && !data) return fail(e, PP_ERR_ARG, "%s: data is NULL", who);
+    return PP_OK;
+}
+
+// Flips to the other input buffer (as set_offsets does) and queues bytes -> staging -> points + offsets on `stream`
+// (the main stream, or the copy stream: it first waits for the pass that last read that buffer).
+int enqueue_ingest(pp_engine* e, const uint8_t* data, const int64_t* bo, int batch, const pp_ingest_config* c,
+                   const IngestPlan& plan, hipStream_t stream) {
+    int st;
+    if (!e->d_ing_frames) {
+        if ((st = dalloc(e, &e->d_ing_frames, (size_t)e->B))) return st;
+        if ((st = dalloc(e, &e->d_ing_finite, (size_t)e->B))) return st;
+        if ((st = dalloc(e, &e->d_ing_kept, (size_t)e->B))) return st;
+        HIPCHK(e, hipHostMalloc((void**)&e->h_ing_ring, (size_t)pp_engine::OFF_RING * e->B * sizeof(IngFrame)));
+    }
+    const size_t tables = 2 * (size_t)batch * plan.stride;
+    if ((size_t)plan.bytes > e->cap_ing_raw || tables > e->cap_ing_chunks) {
+        // an ingest queued earlier on the copy stream may still read what dgrow frees (it waits for the main stream only)
+        HIPCHK(e, hipStreamSynchronize(e->copy_stream));
+        if ((st = dgrow(e, &e->d_ing_raw, &e->cap_ing_raw, (size_t)plan.bytes))) return st;
+        if ((st = dgrow(e, &e->d_ing_chunks, &e->cap_ing_chunks, tables))) return st;
+    }
+    e->zc = false;
+    const int slot = e->off_slot;
+    e->off_slot = (slot + 1) % pp_engine::OFF_RING;
+    HIPCHK(e, hipEventSynchronize(e->off_ev[slot]));   // the copy that last used this slot has been consumed
+    IngFrame* ring = e->h_ing_ring + (size_t)slot * e->B;
+    memcpy(ring, plan.frames.data(), (size_t)batch * sizeof(IngFrame));
+    // the kept counts are device values: everything behind this call is sized from the frames' bounds
+    e->cur_batch = batch;
+    e->cur_max_n = plan.max_bound;
+    e->cur_total = plan.bound_off[(size_t)batch];
+    e->h_cur_off = plan.bound_off;
+    e->off_host_exact = false;
+    e->ing_batch = batch;
+    const int nb = e->in_buf ^ 1;
+    e->in_buf = nb;
+    e->d_points = e->d_points_buf[nb];
+    e->d_offsets = e->d_offsets_buf[nb];
+    use_vox_set(e, nb);
+    e->vox_ahead = false;
+    HIPCHK(e, hipStreamWaitEvent(stream, e->ev_read[nb], 0));
+    if (plan.bytes) HIPCHK(e, hipMemcpyAsync(e->d_ing_raw, data + bo[0], (size_t)plan.bytes, hipMemcpyHostToDevice, stream));
+    HIPCHK(e, hipMemcpyAsync(e->d_ing_frames, ring, (size_t)batch * sizeof(IngFrame), hipMemcpyHostToDevice, stream));
+    HIPCHK(e, hipEventRecord(e->off_ev[slot], stream));
+    IngestParams p;
+    memset(&p, 0, sizeof(p));
+    p.raw = e->d_ing_raw; p.frames = e->d_ing_frames; p.batch = batch; p.stride = plan.stride;
+    p.first = c->first; p.decimate = c->decimate;
+    memcpy(p.r, c->r, sizeof(p.r)); memcpy(p.r2, c->r2, sizeof(p.r2)); memcpy(p.lift, c->lift, sizeof(p.lift));
+    p.chunk_cnt = e->d_ing_chunks; p.chunk_base = e->d_ing_chunks + (size_t)batch * plan.stride;
+    p.finite = e->d_ing_finite; p.kept = e->d_ing_kept; p.offsets = e->d_offsets; p.out = e->d_points;
+    p.out_rows = (long long)e->B * e->NMAX;
+    {
+        ProfScope ps(e, nullptr);
+        launch_ingest(p, stream);
+    }
+    HIPCHK(e, hipGetLastError());
+    return PP_OK;
+}
+
+}  // namespace
+
+int pp_ingest_pointcloud2(pp_handle e, const uint8_t* data, const int64_t* byte_offsets, const pp_pc2_layout* layouts,
+                          int32_t batch, const pp_ingest_config* cfg, float* points_out, int64_t points_out_capacity) {
+    if (!e) return PP_ERR_ARG;
+    (void)hipSetDevice(e->device);
+    IngestPlan plan;
+    int st = check_ingest(e, "pp_ingest_pointcloud2", data, byte_offsets, layouts, batch, cfg, &plan);
+    if (st) return st;
+    // an asynchronous ingest still running on the copy stream uses the same staging and chunk tables
+    HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_up, 0));
+    prof_reset(e);
+    if ((st = enqueue_ingest(e, data, byte_offsets, batch, cfg, plan, e->stream))) return st;
+    e->up_pending = false;
+    HIPCHK(e, hipStreamSynchronize(e->stream));      // the host buffers may be pageable / reused by the caller
+    if (points_out) {
+        int total = 0;
+        HIPCHK(e, hipMemcpy(&total, e->d_offsets + batch, sizeof(int), hipMemcpyDeviceToHost));
+        if (points_out_capacity < total)
+            return fail(e, PP_ERR_ARG, "pp_ingest_pointcloud2: points_out holds %lld points, %d were kept",
+                        (long long)points_out_capacity, total);
+        if (total) HIPCHK(e, hipMemcpy(points_out, e->d_points, (size_t)total * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return PP_OK;
+}
+
+int pp_ingest_pointcloud2_async(pp_handle e, const uint8_t* data_pinned, const int64_t* byte_offsets,
+                                const pp_pc2_layout* layouts, int32_t batch, const pp_ingest_config* cfg) {
+    if (!e) return PP_ERR_ARG;
+    (void)hipSetDevice(e->device);
+    IngestPlan plan;
+    int st = check_ingest(e, "pp_ingest_pointcloud2_async", data_pinned, byte_offsets, layouts, batch, cfg, &plan);
+    if (st) return st;
+    prof_reset(e);
+    if ((st = enqueue_ingest(e, data_pinned, byte_offsets, batch, cfg, plan, e->copy_stream))) return st;
+    // voxelise right behind, as pp_upload_points_async does (same conditions, same wait for a main-stream voxeliser that
+    // still reads the shared scratch)
+    if (e->prof <= 0 && e->train == nullptr) {
+        if (e->main_vox_pending) {
+            HIPCHK(e, hipEventRecord(e->ev_vox_main, e->stream));
+            HIPCHK(e, hipStreamWaitEvent(e->copy_stream, e->ev_vox_main, 0));
+            e->main_vox_pending = false;
+        }
+        if ((st = run_voxelize(e, batch, e->cur_max_n, e->copy_stream))) return st;
+        e->vox_ahead = true;
+        e->prevox_issued = true;
+    }
+    HIPCHK(e, hipEventRecord(e->ev_up, e->copy_stream));
+    e->up_pending = true;
+    return PP_OK;
+}
+
+int pp_ingest_info(pp_handle e, int32_t* finite_counts, int32_t* kept_counts, int32_t batch) {
+    if (!e) return PP_ERR_ARG;
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_ingest_info: a training step is in flight");
+    if (e->ing_batch < 1) return fail(e, PP_ERR_STATE, "pp_ingest_info: no ingest has run");
+    if (batch != e->ing_batch) return fail(e, PP_ERR_ARG, "pp_ingest_info: the last ingest had %d frames, batch is %d", e->ing_batch, batch);
+    (void)hipSetDevice(e->device);
+    HIPCHK(e, hipEventSynchronize(e->ev_up));        // an asynchronous ingest runs on the copy stream
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const size_t n = (size_t)batch * sizeof(int32_t);
+    if (finite_counts) HIPCHK(e, hipMemcpy(finite_counts, e->d_ing_finite, n, hipMemcpyDeviceToHost));
+    if (kept_counts) HIPCHK(e, hipMemcpy(kept_counts, e->d_ing_kept, n, hipMemcpyDeviceToHost));
     return PP_OK;
 }
 
@@ -2141,7 +2347,7 @@ int check_gts(pp_engine* e, const char* who, const int32_t* gt_counts, int batch
     if (e->cur_batch != batch)
         return fail(e, PP_ERR_ARG, "%s: %d frames are resident, batch is %d", who, e->cur_batch, batch);
     if (!e->off_host_exact)
-        return fail(e, PP_ERR_STATE, "%s: the resident frames were sampled inside a training step (upload frames first)", who);
+        return fail(e, PP_ERR_STATE, "%s: the resident frames were sampled inside a training step or ingested from camera messages, their sizes are device values (upload frames first)", who);
     int max_out_n = 0;
     int64_t bound_total = 0;
     // The pasted cloud's size is known on the device only: every launch and buffer is sized from the bound
@@ -2510,7 +2716,7 @@ int pp_augment(pp_handle e, const float* gt_boxes, const int32_t* gt_classes, co
     if (!points_out || !boxes_out || !classes_out || !counts_out) return fail(e, PP_ERR_ARG, "pp_augment: null argument");
     if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_augment: a training step is in flight");
     if (!e->off_host_exact)
-        return fail(e, PP_ERR_STATE, "pp_augment: the resident frames were sampled inside a training step (upload frames first)");
+        return fail(e, PP_ERR_STATE, "pp_augment: the resident frames were sampled inside a training step or ingested from camera messages, their sizes are device values (upload frames first)");
     const pp_target_config tc = {0.5f, 0.35f, {0, 0}};
     int64_t total = 0;
     int st = check_gt(e, "pp_augment", gt_boxes, gt_classes, gt_counts, batch, &tc, &total);

@@ -391,3 +391,29 @@ struct GtsParams {
 // select + count + decide; then paste.  max_n: the largest resident frame; max_out_n: an upper bound of the largest
 // frame after pasting (both host-known)
 void launch_gt_sample(const GtsParams& p, int max_n, int max_out_n, hipStream_t s);
+
+// ingest.hip: live PointCloud2 messages -> the resident float32 points and frame offsets (ingest.py)
+struct IngFrame {              // one message of a call, as the kernels see it
+    long long byte_off;        // its first byte within the staged bytes
+    int width, n_rec;          // records per row; records in all (a frame with tight rows is handed over as one row)
+    int point_step, row_step;
+    int x_off, y_off, z_off;   // byte offsets of the fields within a record
+    int f64, big_endian;       // FLOAT64 fields (else FLOAT32); byte order
+    int nchunks;               // ingest_chunks(n_rec)
+};
+struct IngestParams {
+    const uint8_t* raw;        // the messages' bytes, staged on the device
+    const IngFrame* frames;    // [batch]
+    int batch, stride;         // stride: chunks of the largest frame (row length of the two chunk tables)
+    int first, decimate;
+    double r[9], r2[9], lift[3];
+    int* chunk_cnt;            // [batch][stride] finite records per chunk
+    int* chunk_base;           // [batch][stride] finite records of the frame in front of the chunk
+    int* finite;               // [batch] out: finite records
+    int* kept;                 // [batch] out: points written
+    int* offsets;              // [batch + 1] out: the frames' row offsets in `out`
+    float* out;                // [sum kept][3]
+    long long out_rows;        // rows `out` holds
+};
+int ingest_chunks(int n_rec);
+void launch_ingest(const IngestParams& p, hipStream_t s);

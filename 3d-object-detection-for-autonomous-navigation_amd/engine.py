@@ -108,6 +108,69 @@ class PinnedArray:
             pass
 
 
+class MessageStaging:
+    """The bytes of a batch of sensor_msgs/PointCloud2 messages in one page-locked buffer, with their layouts: what
+    `Engine.ingest_pointcloud2_async` takes.  `.bytes` (uint8) may be refilled in place between uses by messages of the
+    same layouts; `.byte_offsets` [batch + 1]; `.layouts`: the ctypes array of pp_pc2_layout."""
+
+    def __init__(self, lib, msgs):
+        from . import ingest
+        tuples = [ingest.as_tuple(m) for m in msgs]
+        self.byte_offsets, self.layouts, bufs = _pack_messages(tuples)
+        self._pinned = PinnedArray(lib, (max(int(self.byte_offsets[-1]), 4),), np.uint8)
+        self.bytes = self._pinned.array
+        for b, buf in enumerate(bufs):
+            self.bytes[self.byte_offsets[b]:self.byte_offsets[b] + buf.size] = buf
+        self._users = weakref.WeakSet()
+
+    def close(self):
+        """Frees the buffer after every engine that was fed from it has finished the pass that reads it.  As with
+        Staging.close, that wait covers the engine's main stream: an ingest_pointcloud2_async with no detect_async behind
+        it is not waited for -- consume (or ingest_info()) what was fed before closing."""
+        if self._pinned is not None:
+            for eng in list(self._users):
+                if getattr(eng, "_h", None):
+                    eng.sync()
+            self._users.clear()
+            self.bytes = None
+            self._pinned.close()
+            self._pinned = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _pack_messages(tuples):
+    """[(data, width, height, point_step, row_step, fields, is_bigendian)] -> (byte_offsets [B + 1] int64, ctypes array
+    of pp_pc2_layout, the messages' byte views cut to height * row_step)."""
+    from . import ingest
+    layouts = (_lib.PPPc2Layout * max(len(tuples), 1))()
+    offs = np.zeros((len(tuples) + 1,), np.int64)
+    bufs = []
+    for b, t in enumerate(tuples):
+        lay = ingest.layout_of(t)
+        for k in ingest.LAYOUT_KEYS:
+            setattr(layouts[b], k, lay[k])
+        buf = np.frombuffer(t[0], dtype=np.uint8)[:lay["height"] * lay["row_step"]]
+        bufs.append(buf)
+        offs[b + 1] = offs[b] + buf.size
+    return offs, layouts, bufs
+
+
+def _ingest_config(first, decimate, lift):
+    from . import ingest
+    c = _lib.PPIngestConfig()
+    c.first, c.decimate = int(first), int(decimate)
+    r, r2 = ingest._matrices()
+    c.r[:] = [float(v) for v in np.asarray(r, np.float64).reshape(-1)]
+    c.r2[:] = [float(v) for v in np.asarray(r2, np.float64).reshape(-1)]
+    c.lift[:] = [0.0, 0.0, float(lift)]
+    return c
+
+
 class Engine:
     """config: reference-schema dict (or a config.Derived).  max_batch /
     max_points_per_frame size the device workspaces."""
@@ -328,6 +391,13 @@ class Engine:
                                                       offs.shape[0] - 1, ps), "pp_upload_points_device")
         self._offsets = offs
 
+    def _need_host_offsets(self, what):
+        """augment / gt_sample split their outputs by the resident frames' offsets, which the host knows after an upload
+        only: an ingest (and a sampled training step) leaves the sizes on the device."""
+        if getattr(self, "_offsets", None) is None:
+            raise RuntimeError(f"{what}: the resident frames' sizes are known on the device only (they were ingested from "
+                               "camera messages, or nothing was uploaded): upload frames first")
+
     def _batches(self):
         up, res = ctypes.c_int32(0), ctypes.c_int32(0)
         self._check(self._lib.pp_current_batch(self._h, ctypes.byref(up), ctypes.byref(res)), "pp_current_batch")
@@ -356,6 +426,9 @@ class Engine:
         matrix instruction (it stays there: `gemm_precision()`), run the still-resident frames again and return those
         results; "raise": propagate.  A network that overflows float32 itself always raises."""
         self.upload(frames, rect, trv2c)
+        return self._detect_resident(on_numeric)
+
+    def _detect_resident(self, on_numeric):
         self.detect_async()
         self.sync()
         try:
@@ -367,6 +440,67 @@ class Engine:
         self.detect_async()
         self.sync()
         return self.detections()
+
+    # ---- live-camera ingest (pp_ingest_pointcloud2*; ingest.py states the rule) ----
+    def ingest_pointcloud2(self, msgs, first=1, decimate=4, lift=None, return_points=False):
+        """Raw sensor_msgs/PointCloud2 messages -> the engine's resident frames, on the GPU: x y z out of the bytes,
+        non-finite records dropped, every `decimate`-th survivor from index `first`, camera axes turned into lidar axes
+        and lifted by `lift` (ingest.SENSOR_HEIGHT) -- `ingest.realsense_to_lidar(ingest.pointcloud2_to_xyz(...))`
+        exactly.  msgs: list of messages (`ingest.as_tuple`).  The engine needs max_points_per_frame >=
+        ingest.kept_bound(width, height, first, decimate) (76800 for a 640 x 480 cloud at 1, 4).  There is no host
+        fallback: a layout the library refuses raises with its text.  return_points: the resident points, one [n_b, 3]
+        float32 array per frame (the parity tap)."""
+        from . import ingest
+        tuples = [ingest.as_tuple(m) for m in msgs]
+        offs, layouts, bufs = _pack_messages(tuples)
+        data = (bufs[0] if len(bufs) == 1 else np.concatenate(bufs)) if bufs and offs[-1] else np.zeros((1,), np.uint8)
+        cfg = _ingest_config(first, decimate, ingest.SENSOR_HEIGHT if lift is None else lift)
+        pts, cap = None, 0
+        if return_points:
+            cap = sum(ingest.kept_bound(t[1], t[2], max(int(first), 0), max(int(decimate), 1)) for t in tuples)
+            pts = np.empty((max(cap, 1), 3), np.float32)
+        self._check(self._lib.pp_ingest_pointcloud2(self._h, _ptr(data), _ptr(offs), layouts, len(tuples),
+                                                    ctypes.byref(cfg), _ptr(pts), ctypes.c_int64(cap)),
+                    "pp_ingest_pointcloud2")
+        self._offsets = None          # the resident frames' sizes are device values (ingest_info reads them back)
+        self._ing_batch = len(tuples)
+        if not return_points:
+            return None
+        off = np.concatenate([[0], np.cumsum(self.ingest_info()["kept"])])
+        return [pts[off[b]:off[b + 1]].copy() for b in range(len(tuples))]
+
+    def ingest_info(self):
+        """Per frame of the last ingest: `finite` records and points `kept` (pp_ingest_info; waits for the ingest)."""
+        B = getattr(self, "_ing_batch", 0)
+        fin, kept = np.zeros((max(B, 1),), np.int32), np.zeros((max(B, 1),), np.int32)
+        self._check(self._lib.pp_ingest_info(self._h, _ptr(fin), _ptr(kept), B), "pp_ingest_info")
+        return {"finite": fin[:B], "kept": kept[:B]}
+
+    def staging_pointcloud2(self, msgs):
+        """Packs messages into a page-locked MessageStaging for ingest_pointcloud2_async (the counterpart of staging())."""
+        return MessageStaging(self._lib, msgs)
+
+    def ingest_pointcloud2_async(self, staging, first=1, decimate=4, lift=None):
+        """ingest_pointcloud2 without waiting (pp_ingest_pointcloud2_async): the bytes of a MessageStaging travel on the
+        copy stream and are ingested and voxelised there, beside the pass in flight; the buffer must not be rewritten
+        before the sync() that follows the detect_async() consuming these frames.  Mixes freely with upload_async."""
+        from . import ingest
+        cfg = _ingest_config(first, decimate, ingest.SENSOR_HEIGHT if lift is None else lift)
+        self._check(self._lib.pp_ingest_pointcloud2_async(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets),
+                                                          staging.layouts, staging.byte_offsets.shape[0] - 1,
+                                                          ctypes.byref(cfg)), "pp_ingest_pointcloud2_async")
+        self._offsets = None
+        self._ing_batch = staging.byte_offsets.shape[0] - 1
+        staging._users.add(self)
+        self._staged.append(staging)      # kept alive while a copy may still read it (see upload_async)
+
+    def detect_pointcloud2(self, msgs, rect=None, trv2c=None, on_numeric="f32"):
+        """ingest_pointcloud2 + detect_async + sync + detections: `detect` for raw camera messages (the reference's
+        production mode, train.py:810-828).  rect / trv2c / on_numeric as `detect`."""
+        self.ingest_pointcloud2(msgs)
+        if rect is not None:
+            self.set_calib(rect, trv2c, len(msgs))
+        return self._detect_resident(on_numeric)
 
     def intermediates(self, canvas=False):
         d, B = self.d, max(self._batches()[1], 1)
@@ -627,8 +761,9 @@ class Engine:
         boxes, cls, counts = self.pack_gt(gt_boxes, gt_classes)
         ac, valid, frames, bd = self._aug_args(gt_valid, len(boxes), draws, aug_config)
         B = len(counts)
-        off = np.asarray(self._offsets, np.int64) if getattr(self, "_offsets", None) is not None else None
-        n_total = int(off[-1]) if off is not None else 0
+        self._need_host_offsets("augment")
+        off = np.asarray(self._offsets, np.int64)
+        n_total = int(off[-1])
         pts = np.empty((max(n_total, 1), self.d.num_point_features), np.float32)
         bo = np.empty((max(len(boxes), 1), 7), np.float32)
         co = np.empty((max(len(boxes), 1),), np.int32)
@@ -689,8 +824,8 @@ class Engine:
         sc = _lib.PPGtSampleConfig()
         if cfg is not None:
             sc.max_point_collision, sc.min_point_collision = cfg.max_point_collision, cfg.min_point_collision
-        off = getattr(self, "_offsets", None)
-        n_in = int(off[-1]) if off is not None else 0
+        self._need_host_offsets("gt_sample")
+        n_in = int(self._offsets[-1])
         cap = n_in + (int(np.diff(db.offsets)[candidates.cands["object"].clip(0, len(db) - 1)].sum())
                       if db is not None and len(db) else 0)
         F = self.d.num_point_features

@@ -74,3 +74,41 @@ def default_calib():
     trv2c = np.array([[0, -1, 0, 0], [0, 0, -1, 0], [1, 0, 0, 0], [0, 0, 0, 1]], dtype=np.float32)
     p2 = np.eye(4, dtype=np.float32)
     return rect, trv2c, p2
+
+
+def pointcloud2_from_xyz(xyz, width, height, point_step=20, row_pad=0, datatype=7, bigendian=False, offsets=(0, 4, 8),
+                         seed=977):
+    """[width * height, 3] camera-frame coordinates (NaN / inf allowed) -> a sensor_msgs/PointCloud2 as the tuple
+    `ingest.pointcloud2_to_xyz` takes: (data, width, height, point_step, row_step, fields, is_bigendian).  Records of
+    `point_step` bytes in rows padded by `row_pad` bytes; x y z (datatype 7 FLOAT32 or 8 FLOAT64) at `offsets`; every
+    other byte is random."""
+    rng = np.random.default_rng(seed)
+    n = int(width) * int(height)
+    cam = np.asarray(xyz, np.float64).reshape(n, 3)
+    dt = np.dtype((">" if bigendian else "<") + ("f8" if datatype == 8 else "f4"))
+    if max(offsets) + dt.itemsize > point_step:
+        raise ValueError(f"offsets {offsets} do not fit point_step {point_step}")
+    rec = rng.integers(0, 256, (n, point_step), dtype=np.uint8)
+    for k, off in enumerate(offsets):
+        rec[:, off:off + dt.itemsize] = np.ascontiguousarray(cam[:, k].astype(dt)).view(np.uint8).reshape(n, dt.itemsize)
+    row_step = width * point_step + int(row_pad)
+    rows = rng.integers(0, 256, (height, row_step), dtype=np.uint8)
+    rows[:, :width * point_step] = rec.reshape(height, width * point_step)
+    fields = [("x", offsets[0], datatype, 1), ("y", offsets[1], datatype, 1), ("z", offsets[2], datatype, 1)]
+    if point_step >= max(offsets) + dt.itemsize + 4:
+        fields.append(("rgb", max(offsets) + dt.itemsize, 7, 1))
+    return (rows.tobytes(), int(width), int(height), int(point_step), row_step, fields, bool(bigendian))
+
+
+def pointcloud2_message(frame, width=640, height=480, point_step=20, row_pad=0, nan_fraction=0.3, datatype=7,
+                        bigendian=False, offsets=(0, 4, 8), seed=977):
+    """A seeded camera message (`pointcloud2_from_xyz`): the points are a `d435i_cloud` turned back into camera axes
+    (x right, y down, z depth; the ingest's lift undone), and `nan_fraction` of the records carry a NaN coordinate, as
+    a depth camera's invalid pixels do.  The d435i driver's own layout is point_step 20 (x y z float32, rgb at 16)."""
+    rng = np.random.default_rng(seed + int(frame))
+    n = int(width) * int(height)
+    lidar = d435i_cloud(frame, max(n, 1), seed=seed)[:n].astype(np.float64)
+    cam = np.stack([-lidar[:, 1], 1.0 - lidar[:, 2], lidar[:, 0]], axis=1)
+    bad = rng.random(n) < nan_fraction
+    cam[bad, rng.integers(0, 3, int(bad.sum()))] = np.nan
+    return pointcloud2_from_xyz(cam, width, height, point_step, row_pad, datatype, bigendian, offsets, seed + int(frame))

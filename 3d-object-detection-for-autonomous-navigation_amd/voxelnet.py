@@ -8,7 +8,8 @@ Mirror of model/voxelnet.py::VoxelNet for the eval path (train.py:575-771):
 `example` is the positional 10-tuple (voxels, num_points, coordinates, rect,
 Trv2c, P2, anchors, anchors_mask, image_idx, image_shape); elements may be
 numpy arrays or anything with `.numpy()` (the reference passes TF tensors).
-`detect(frames, ...)` is the fused raw-points path the reference does not have.
+`detect(frames, ...)` is the fused raw-points path the reference does not have; `detect_pointcloud2(msgs, ...)` is the
+same from raw sensor_msgs/PointCloud2 messages (the reference's production mode, ingested on the GPU).
 
 Training mode (model/voxelnet.py:922-1049 + train.py:265-304), `VoxelNet(config, writer, training=True)`:
     ret = net(voxels, num_points, coors, batch_anchors, labels, reg_targets)   # the reference's loss dict (scalars)
@@ -142,6 +143,13 @@ class VoxelNet:
         dets, n = self.engine.detect(frames, rect, trv2c)
         idx = image_idx if image_idx is not None else list(range(len(frames)))
         return [self._to_dict(dets[b], int(n[b]), idx[b]) for b in range(len(frames))]
+
+    def detect_pointcloud2(self, msgs, rect=None, trv2c=None, image_idx=None):
+        """Fused path from raw sensor_msgs/PointCloud2 messages (the reference's production mode: ingest on the GPU,
+        Engine.detect_pointcloud2) -> the same list of prediction dicts as `detect`."""
+        dets, n = self.engine.detect_pointcloud2(msgs, rect, trv2c)
+        idx = image_idx if image_idx is not None else list(range(len(msgs)))
+        return [self._to_dict(dets[b], int(n[b]), idx[b]) for b in range(len(msgs))]
 
     @staticmethod
     def _to_dict(dets, n, img_idx):

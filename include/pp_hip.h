@@ -32,7 +32,8 @@ extern "C" {
  * pp_train_step_gt; then PP_AUG_MAX_TRY, pp_augment_config, pp_aug_frame, pp_augment, pp_train_step_aug_async,
  * pp_train_step_aug, pp_augment_selected; then pp_train_set_frozen, pp_adamw_step_segments_device; then PP_GTS_MAX_CAND,
  * PP_GTS_MAX_ROUNDS, pp_gt_sample_config, pp_gts_cand, pp_gtdb_load, pp_gt_sample, pp_gt_sample_info,
- * pp_train_step_sample_async, pp_train_step_sample. */
+ * pp_train_step_sample_async, pp_train_step_sample; then pp_pc2_layout, pp_ingest_config, pp_ingest_pointcloud2,
+ * pp_ingest_pointcloud2_async, pp_ingest_info. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -526,6 +527,55 @@ int pp_train_step_sample(pp_handle h, const float* params_dev, float* grads_dev,
  * round's count: PP_GTS_ROUND_NOT_USED) and the number of the frame's original points inside its box (0 for a slot that
  * did not survive the box test); round_used [batch]: the round whose objects were pasted, -1 for none. */
 int pp_gt_sample_info(pp_handle h, int32_t* status, int32_t* point_counts, int32_t* round_used, int32_t batch);
+
+/* ---- live-camera ingest --------------------------------------------------------------- */
+/* The reference's production mode in front of the network (load_data.py:2433-2443, train.py:810-828):
+ * ros_numpy.point_cloud2.pointcloud2_to_xyz_array(msg) (x y z out of the message bytes, records with a non-finite
+ * coordinate dropped), points[first::decimate], np.dot(np.dot(points, r), r2) + lift -- on the GPU, from the raw bytes of
+ * `batch` sensor_msgs/PointCloud2 messages to the resident frames of the next pp_detect_async.  Per record (message order,
+ * i = row * width + col at row * row_step + col * point_step): finite = x, y and z finite (+-inf is not); rank = finite
+ * records in front of it; kept when finite, rank >= first and (rank - first) % decimate == 0, as row (rank - first) /
+ * decimate of its frame; a kept point is ((p . r) . r2) + lift in float64 -- each 3-term dot product summed left to right,
+ * products and sums rounded separately, which is bit for bit what numpy computes -- rounded to float32 once.  The result
+ * equals <package>/ingest.py's realsense_to_lidar(pointcloud2_to_xyz(...), decimate, first, lift) exactly. */
+typedef struct pp_pc2_layout {   /* one sensor_msgs/PointCloud2, without its bytes */
+    int32_t width, height, point_step, row_step;
+    int32_t x_offset, y_offset, z_offset;   /* PointField.offset of x, y, z; nothing needs to be aligned */
+    int32_t datatype;            /* 7 FLOAT32 or 8 FLOAT64, the same for x y z.  Integer types (1..6) are refused with
+                                    PP_ERR_UNSUPPORTED; a message whose three fields differ is passed as
+                                    x | y << 8 | z << 16 and refused the same way */
+    int32_t is_bigendian;
+    int32_t reserved;            /* 0 */
+} pp_pc2_layout;
+typedef struct pp_ingest_config {
+    int32_t first, decimate;     /* reference: 1, 4 */
+    double r[9], r2[9], lift[3]; /* row-major; the caller's scipy matrices (their cos 90 deg entries are ~1e-16, not 0,
+                                    and depend on the scipy build) and [0, 0, sensor height] */
+} pp_ingest_config;
+
+/* Ingests `batch` messages into the handle's other input buffer (as pp_upload_points does: the frames are then resident
+ * for pp_detect_async) and waits.  data: the messages' bytes; message b occupies data[byte_offsets[b] ..
+ * byte_offsets[b + 1]) and holds at least height * row_step bytes.  points_out (may be NULL): receives the resident
+ * points [sum kept, 3], frames back to back -- the parity tap; points_out_capacity is in points, PP_ERR_ARG when it is
+ * below the kept total (the frames stay resident).  The kept counts exist on the device only (pp_ingest_info reads them
+ * back): everything behind the call is sized from the host-side bound max(0, ceil((width * height - first) / decimate))
+ * per frame.  Refused before anything is queued, pp_last_error naming the frame and the field: PP_ERR_ARG when that bound
+ * exceeds max_points_per_frame (a 640 x 480 cloud at 1, 4 needs max_points_per_frame >= 76800), row_step < width *
+ * point_step, a field that does not fit point_step, a message shorter than height * row_step, decimate < 1, first < 0;
+ * PP_ERR_STATE while a training step is in flight; PP_ERR_UNSUPPORTED for integer field datatypes, x / y / z of different
+ * datatypes, and a handle whose num_point_features is not 3 (the reference's live path is xyz only).  Frames that keep no
+ * point are legal. */
+int pp_ingest_pointcloud2(pp_handle h, const uint8_t* data, const int64_t* byte_offsets, const pp_pc2_layout* layouts,
+                          int32_t batch, const pp_ingest_config* cfg, float* points_out, int64_t points_out_capacity);
+/* Same without waiting: `data_pinned` is page-locked (pp_host_alloc) and stays unchanged until the pass that consumes the
+ * frames has finished; byte_offsets / layouts / cfg are copied before the call returns.  The bytes travel on the handle's
+ * copy stream, the ingest kernels and the voxeliser run behind them there, beside the pass in flight; the ordering rules
+ * are pp_upload_points_async's, and the two may be mixed freely. */
+int pp_ingest_pointcloud2_async(pp_handle h, const uint8_t* data_pinned, const int64_t* byte_offsets,
+                                const pp_pc2_layout* layouts, int32_t batch, const pp_ingest_config* cfg);
+/* Parity tap of the last ingest (waits for it): per frame the finite records and the points kept.  Either pointer may be
+ * NULL.  PP_ERR_STATE when none has run, PP_ERR_ARG when `batch` is not that call's. */
+int pp_ingest_info(pp_handle h, int32_t* finite_counts, int32_t* kept_counts, int32_t batch);
 
 /* The handle's HIP stream (hipStream_t as void*).  A caller that enqueues its own device work behind a pp_train_step_async
  * -- the gradient all-reduce and pp_adamw_step_device of the optimizer step (train.py:301) -- does it on this stream and
