@@ -158,6 +158,16 @@ struct pp_engine {
     uint8_t* d_gts_valid_out = nullptr;
     int* d_gts_cnt_out = nullptr;
     int gts_batch = 0;                 // frames of the last pp_gt_sample (pp_gt_sample_info)
+    // building the object database from the resident frames (pp_gtdb_build / pp_gtdb_count, gt_database.hip): allocated
+    // on first use; the cut-out points grow to the largest build seen
+    bool gdb_ready = false;
+    double* d_gdb_boxes = nullptr;     // [B * PP_MAX_GT_PER_FRAME][7]
+    int *d_gdb_cnt = nullptr, *d_gdb_boxoff = nullptr;   // [B], [B + 1]
+    GtsPlane* d_gdb_planes = nullptr;  // [B * PP_MAX_GT_PER_FRAME]
+    int* d_gdb_chunks = nullptr;       // [B][ceil(NMAX / PP_GDB_CHUNK)][PP_MAX_GT_PER_FRAME]
+    int* d_gdb_totals = nullptr;       // [B * PP_MAX_GT_PER_FRAME]
+    long long* d_gdb_off = nullptr;    // [B * PP_MAX_GT_PER_FRAME + 1]
+    float* d_gdb_out = nullptr;  size_t cap_gdb_out = 0;
     // live PointCloud2 ingest (pp_ingest_pointcloud2*, ingest.hip): allocated on first use; the byte staging and the
     // chunk tables grow to the largest call seen
     uint8_t* d_ing_raw = nullptr;  size_t cap_ing_raw = 0;       // the messages' bytes
@@ -1000,6 +1010,7 @@ int pp_destroy(pp_handle e) {
     if (e->h_ing_ring) (void)hipHostFree(e->h_ing_ring);
     if (e->d_ing_raw) (void)hipFree(e->d_ing_raw);
     if (e->d_ing_chunks) (void)hipFree(e->d_ing_chunks);
+    if (e->d_gdb_out) (void)hipFree(e->d_gdb_out);
     for (hipEvent_t ev : e->off_ev) if (ev) (void)hipEventDestroy(ev);
     if (e->ev_in) (void)hipEventDestroy(e->ev_in);
     for (PpFeed* f : e->h_feed) if (f) (void)hipHostFree(f);
@@ -2836,6 +2847,116 @@ int pp_gt_sample(pp_handle e, const float* gt_boxes, const int32_t* gt_classes, 
     e->zc = false;
     e->vox_ahead = false;
     return PP_OK;
+}
+
+// ---- building the object database from the resident frames (gt_database.hip) ----
+
+namespace {
+
+int gtdb_run(pp_engine* e, const char* who, const double* boxes, const int32_t* box_counts, int32_t batch,
+             int32_t* counts_out, int64_t* offsets_out, float* points_out, int64_t points_capacity, bool gather) {
+    if (!box_counts || !counts_out || (gather && (!offsets_out || points_capacity < 0)))
+        return fail(e, PP_ERR_ARG, "%s: null argument", who);
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "%s: a training step is in flight", who);
+    int st = check_batch(e, batch); if (st) return st;
+    if (e->cur_batch != batch) return fail(e, PP_ERR_ARG, "%s: %d frames are resident, batch is %d", who, e->cur_batch, batch);
+    if (!e->off_host_exact)
+        return fail(e, PP_ERR_STATE, "%s: the resident frames were sampled inside a training step or ingested from camera messages, their sizes are device values (upload frames first)", who);
+    // k_gdb_offsets scans 32-bit partial sums inside a wave: 64 threads x max_batch objects x max_points_per_frame points
+    if ((int64_t)e->B * e->NMAX > (1ll << 25))
+        return fail(e, PP_ERR_UNSUPPORTED, "%s: max_batch x max_points_per_frame above 2^25", who);
+    int64_t total = 0;
+    std::vector<int> boxoff((size_t)batch + 1, 0);
+    for (int b = 0; b < batch; ++b) {
+        if (box_counts[b] < 0 || box_counts[b] > PP_MAX_GT_PER_FRAME)
+            return fail(e, PP_ERR_ARG, "%s: frame %d has %d boxes (0..%d)", who, b, box_counts[b], PP_MAX_GT_PER_FRAME);
+        total += box_counts[b];
+        boxoff[(size_t)b + 1] = (int)total;
+    }
+    if (total > 0 && !boxes) return fail(e, PP_ERR_ARG, "%s: boxes is NULL", who);
+    for (int64_t i = 0; i < total; ++i) {
+        const double* q = boxes + i * 7;
+        for (int k = 0; k < 7; ++k)
+            if (!std::isfinite(q[k])) return fail(e, PP_ERR_ARG, "%s: box %lld is not finite", who, (long long)i);
+        if (!(q[3] > 0.0 && q[4] > 0.0 && q[5] > 0.0))
+            return fail(e, PP_ERR_ARG, "%s: box %lld has a size <= 0", who, (long long)i);
+    }
+    (void)hipSetDevice(e->device);
+    const int stride = (e->NMAX + PP_GDB_CHUNK - 1) / PP_GDB_CHUNK;
+    if (!e->gdb_ready) {
+        const size_t gmax = (size_t)e->B * PP_MAX_GT_PER_FRAME;
+        if ((st = dalloc(e, &e->d_gdb_boxes, gmax * 7))) return st;
+        if ((st = dalloc(e, &e->d_gdb_cnt, (size_t)e->B))) return st;
+        if ((st = dalloc(e, &e->d_gdb_boxoff, (size_t)e->B + 1))) return st;
+        if ((st = dalloc(e, &e->d_gdb_planes, gmax))) return st;
+        if ((st = dalloc(e, &e->d_gdb_chunks, gmax * stride))) return st;
+        if ((st = dalloc(e, &e->d_gdb_totals, gmax))) return st;
+        if ((st = dalloc(e, &e->d_gdb_off, gmax + 1))) return st;
+        e->gdb_ready = true;
+    }
+    hipStream_t s = e->stream;
+    prof_reset(e);
+    if (total) HIPCHK(e, hipMemcpyAsync(e->d_gdb_boxes, boxes, (size_t)total * 7 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->d_gdb_cnt, box_counts, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->d_gdb_boxoff, boxoff.data(), ((size_t)batch + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+    // the resident points: behind their upload; a zero-copy feed is read where it lies, in the caller's page-locked
+    // memory (the frames stay as they are: a later pp_detect_async reads the same feed)
+    if (e->up_pending || e->prevox_issued) {
+        HIPCHK(e, hipStreamWaitEvent(s, e->ev_up, 0));
+        e->up_pending = false;
+        e->prevox_issued = false;
+    }
+    const PpFeed* f = e->h_feed[e->in_buf];
+    GdbParams p;
+    p.batch = batch; p.F = e->F;
+    p.offsets = e->d_offsets; p.pts = e->d_points;
+    if (e->zc) {
+        HIPCHK(e, hipMemcpyAsync(e->d_offsets, f->offsets, (size_t)(batch + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+        p.pts = f->src;
+    }
+    p.boxes = e->d_gdb_boxes; p.box_cnt = e->d_gdb_cnt; p.box_off = e->d_gdb_boxoff; p.planes = e->d_gdb_planes;
+    p.chunk_cnt = e->d_gdb_chunks; p.chunk_stride = stride; p.totals = e->d_gdb_totals; p.obj_off = e->d_gdb_off;
+    p.out = nullptr;
+    {
+        ProfScope ps(e, nullptr);      // each launch under its own name
+        launch_gtdb_count(p, (int)total, e->cur_max_n, s);
+    }
+    HIPCHK(e, hipGetLastError());
+    std::vector<long long> off((size_t)total + 1, 0);
+    if (total) HIPCHK(e, hipMemcpyAsync(counts_out, e->d_gdb_totals, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(off.data(), e->d_gdb_off, ((size_t)total + 1) * sizeof(long long), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    if (!gather) return PP_OK;
+    const int64_t rows = off[(size_t)total];
+    if (rows > points_capacity)
+        return fail(e, PP_ERR_ARG, "%s: points_out holds %lld points, %lld are written", who, (long long)points_capacity,
+                    (long long)rows);
+    if (rows > 0 && !points_out) return fail(e, PP_ERR_ARG, "%s: points_out is NULL", who);
+    for (int64_t i = 0; i <= total; ++i) offsets_out[i] = off[(size_t)i];
+    if (rows == 0) return PP_OK;
+    if ((st = dgrow(e, &e->d_gdb_out, &e->cap_gdb_out, (size_t)rows * e->F))) return st;
+    p.out = e->d_gdb_out;
+    {
+        ProfScope ps(e, nullptr);
+        launch_gtdb_gather(p, e->cur_max_n, s);
+    }
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(points_out, e->d_gdb_out, (size_t)rows * e->F * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    return PP_OK;
+}
+
+}  // namespace
+
+int pp_gtdb_count(pp_handle e, const double* boxes, const int32_t* box_counts, int32_t batch, int32_t* counts_out) {
+    if (!e) return PP_ERR_ARG;
+    return gtdb_run(e, "pp_gtdb_count", boxes, box_counts, batch, counts_out, nullptr, nullptr, 0, false);
+}
+
+int pp_gtdb_build(pp_handle e, const double* boxes, const int32_t* box_counts, int32_t batch, int32_t* counts_out,
+                  int64_t* offsets_out, float* points_out, int64_t points_capacity) {
+    if (!e) return PP_ERR_ARG;
+    return gtdb_run(e, "pp_gtdb_build", boxes, box_counts, batch, counts_out, offsets_out, points_out, points_capacity, true);
 }
 
 int pp_train_step_sample_async(pp_handle e, const float* params_dev, float* grads_dev, float* state_dev,

@@ -392,6 +392,26 @@ struct GtsParams {
 // frame after pasting (both host-known)
 void launch_gt_sample(const GtsParams& p, int max_n, int max_out_n, hipStream_t s);
 
+// gt_database.hip: the labelled objects of the resident frames, cut out and centred (gt_database.py)
+#define PP_GDB_CHUNK 256       // points per workgroup of the count / gather passes
+struct GdbParams {
+    int batch, F;
+    const int* offsets;        // [batch + 1] resident frame offsets
+    const float* pts;          // [sum n][F] resident points (only read)
+    const double* boxes;       // [sum G][7] x y z w l h r, the frames' boxes back to back
+    const int* box_cnt;        // [batch]
+    const int* box_off;        // [batch + 1] first box of each frame
+    GtsPlane* planes;          // [sum G]
+    int* chunk_cnt;            // [batch][chunk_stride][PP_MAX_GT_PER_FRAME]: members per (chunk, box); after the scan the
+    int chunk_stride;          //   chunk's base inside its object.  chunk_stride: chunks of a max_points_per_frame frame
+    int* totals;               // [sum G] points per object
+    long long* obj_off;        // [sum G + 1] first output row of each object
+    float* out;                // [obj_off[sum G]][F]
+};
+// planes + count + scans (totals, obj_off, chunk bases); then the gather.  max_n: the largest resident frame
+void launch_gtdb_count(const GdbParams& p, int total_boxes, int max_n, hipStream_t s);
+void launch_gtdb_gather(const GdbParams& p, int max_n, hipStream_t s);
+
 // ingest.hip: live PointCloud2 messages -> the resident float32 points and frame offsets (ingest.py)
 struct IngFrame {              // one message of a call, as the kernels see it
     long long byte_off;        // its first byte within the staged bytes

@@ -847,6 +847,56 @@ class Engine:
             g += k
         return out
 
+    # ---- building the object database from the resident frames (pp_gtdb_build / pp_gtdb_count) ----
+    @staticmethod
+    def _pack_lidar_boxes(gt_boxes):
+        boxes = [np.asarray(g, dtype=np.float64).reshape(-1, 7) for g in gt_boxes]
+        counts = np.array([len(g) for g in boxes], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(boxes, axis=0) if boxes else np.zeros((0, 7), np.float64))
+        return flat, counts
+
+    def count_points_in_gt(self, gt_boxes):
+        """The points of each frame uploaded to this engine inside each of its boxes, on the GPU (pp_gtdb_count;
+        gt_database.py lists the rule): the reference's num_points_in_gt.  gt_boxes: per frame [G_b, 7] float64 lidar
+        boxes x y z w l h r.  Returns per frame an int32 array [G_b].  The resident frames are only read."""
+        boxes, counts = self._pack_lidar_boxes(gt_boxes)
+        out = np.zeros(max(len(boxes), 1), np.int32)
+        self._check(self._lib.pp_gtdb_count(self._h, _ptr(boxes), _ptr(counts), len(counts), _ptr(out)), "pp_gtdb_count")
+        ends = np.cumsum(counts)
+        return [out[e - c:e].copy() for c, e in zip(counts, ends)]
+
+    def build_gt_objects(self, gt_boxes, return_counts=False, capacity=None):
+        """The labelled objects of the frames uploaded to this engine, cut out on the GPU (pp_gtdb_build; gt_database.py
+        lists the rule): per frame a list of G_b float32 arrays [n, F], the points inside each box in the frame's order,
+        centred on the box -- what create_groundtruth_database writes per object.  gt_boxes as count_points_in_gt.
+        return_counts: (per-frame counts as count_points_in_gt returns them, objects).  capacity: the size of the
+        output buffer in points (default: sized here, and grown once from the returned counts when it is too small; a
+        given capacity that is too small raises).  The resident frames are only read."""
+        boxes, counts = self._pack_lidar_boxes(gt_boxes)
+        B, total, F = len(counts), len(boxes), self.d.num_point_features
+        cnt = np.full(max(total, 1), -1, np.int32)
+        off = np.zeros(total + 1, np.int64)
+        fixed = capacity is not None
+        resident = getattr(self, "_offsets", None)
+        cap = int(capacity) if fixed else max(getattr(self, "_gdb_cap", 0), int(resident[-1]) if resident is not None else 0)
+        while True:
+            pts = np.empty((max(cap, 1), F), np.float32)
+            st = self._lib.pp_gtdb_build(self._h, _ptr(boxes), _ptr(counts), B, _ptr(cnt), _ptr(off), _ptr(pts), cap)
+            # too small: only the counts were written; size the buffer from them and call again
+            if st == 1 and not fixed and total and (cnt[:total] >= 0).all() and int(cnt[:total].sum()) > cap:
+                cap = int(cnt[:total].sum())
+                fixed = True
+                continue
+            self._check(st, "pp_gtdb_build")
+            break
+        self._gdb_cap = max(getattr(self, "_gdb_cap", 0), cap)
+        objs, per_frame, g = [], [], 0
+        for b in range(B):
+            objs.append([pts[off[g + i]:off[g + i + 1]].copy() for i in range(counts[b])])
+            per_frame.append(cnt[g:g + counts[b]].copy())
+            g += counts[b]
+        return (per_frame, objs) if return_counts else objs
+
     def train_step_sample_async(self, params_ptr, grads_ptr, state_ptr, boxes, classes, counts, valid, candidates,
                                 sampler_config, draws=None, aug_config=None):
         """train_step_gt_async on frames sampled -- and, with `draws`, augmented -- on the GPU first

@@ -234,6 +234,16 @@ class GtDatabase:
                 points[name].append(a if a.ndim == 2 else a.reshape(0, int(num_point_features)))
         return cls(infos, points, config, rs, pyrandom, num_point_features, **kw)
 
+    @classmethod
+    def from_frames(cls, engine, infos, clouds, config, rs, pyrandom, num_point_features, used_classes=None,
+                    bev_only=False, coors_range=None, **kw):
+        """From labelled frames, without the reference's files: gt_database.create_groundtruth_database (on the GPU of
+        `engine`) over the frame infos and their float32 clouds, then the constructor."""
+        from . import gt_database
+        infos, points = gt_database.create_groundtruth_database(engine, infos, clouds, used_classes=used_classes,
+                                                                bev_only=bev_only, coors_range=coors_range)
+        return cls(infos, points, config, rs, pyrandom, num_point_features, **kw)
+
 
 class Candidates:
     """One batch's candidate slots: cands [B, PP_GTS_MAX_CAND] CAND_DTYPE (a frame's rounds back to back), counts

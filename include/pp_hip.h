@@ -33,7 +33,7 @@ extern "C" {
  * pp_train_step_aug, pp_augment_selected; then pp_train_set_frozen, pp_adamw_step_segments_device; then PP_GTS_MAX_CAND,
  * PP_GTS_MAX_ROUNDS, pp_gt_sample_config, pp_gts_cand, pp_gtdb_load, pp_gt_sample, pp_gt_sample_info,
  * pp_train_step_sample_async, pp_train_step_sample; then pp_pc2_layout, pp_ingest_config, pp_ingest_pointcloud2,
- * pp_ingest_pointcloud2_async, pp_ingest_info. */
+ * pp_ingest_pointcloud2_async, pp_ingest_info; then pp_gtdb_build, pp_gtdb_count. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -527,6 +527,25 @@ int pp_train_step_sample(pp_handle h, const float* params_dev, float* grads_dev,
  * round's count: PP_GTS_ROUND_NOT_USED) and the number of the frame's original points inside its box (0 for a slot that
  * did not survive the box test); round_used [batch]: the round whose objects were pasted, -1 for none. */
 int pp_gt_sample_info(pp_handle h, int32_t* status, int32_t* point_counts, int32_t* round_used, int32_t batch);
+
+/* ---- building the object database ------------------------------------------------------------------- */
+/* create_groundtruth_database (create_data.py:365-551) on the RESIDENT frames, which are only read (a pp_detect_async
+ * after it sees them unchanged): every point of frame b against each of its box_counts[b] labelled boxes -- boxes
+ * [sum box_counts][7] float64 LIDAR boxes x y z w l h r, the frames' back to back (the camera -> lidar conversion is the
+ * caller's: <package>/gt_database.py box_camera_to_lidar).  A point is inside a box iff ((x n0 + y n1) + z n2) + d < 0 for
+ * all six faces, in float64 on the widened float32 coordinates, planes as points_in_rbbox builds them; a point inside
+ * several boxes goes to each.  Host outputs: counts_out [sum box_counts] points per box; offsets_out [sum box_counts + 1]
+ * first row of each object in points_out; points_out [offsets_out[last]][F]: an object's points in the frame's order,
+ * x y z as (float)((double)p - centre) -- one rounding, what `float32 array -= float64 centre` gives --, the other columns
+ * copied.  points_capacity (in points) too small: PP_ERR_ARG with only counts_out written, so the caller can size the buffer
+ * from it and call again.  PP_ERR_ARG, before anything is launched, for a non-finite box, a size <= 0, a count outside
+ * 0..PP_MAX_GT_PER_FRAME or a batch other than the resident one; PP_ERR_STATE when the resident frames' sizes are device
+ * values (after a pp_train_step_sample* or an ingest) or a training step is in flight; the handle stays usable.  The
+ * result is the same bytes on every run.  Synchronous. */
+int pp_gtdb_build(pp_handle h, const double* boxes, const int32_t* box_counts, int32_t batch, int32_t* counts_out,
+                  int64_t* offsets_out, float* points_out, int64_t points_capacity);
+/* The same without the cut-out: counts_out only -- _calculate_num_points_in_gt (create_data.py:28-93). */
+int pp_gtdb_count(pp_handle h, const double* boxes, const int32_t* box_counts, int32_t batch, int32_t* counts_out);
 
 /* ---- live-camera ingest --------------------------------------------------------------- */
 /* The reference's production mode in front of the network (load_data.py:2433-2443, train.py:810-828):
