@@ -19,7 +19,7 @@ SO_PATH = os.path.join(_PKG, os.environ.get("PP_HIP_LIB", "libpp_hip.so"))
 _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
 SOURCES = ["pp_api.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
            "rotate_iou.hip", "loss.hip", "optim.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip",
-           "gt_database.hip"]
+           "gt_database.hip", "eval_stats.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
@@ -41,6 +41,7 @@ EXPORTS = [
     "pp_gtdb_load", "pp_gt_sample", "pp_gt_sample_info", "pp_train_step_sample_async", "pp_train_step_sample",
     "pp_ingest_pointcloud2", "pp_ingest_pointcloud2_async", "pp_ingest_info",
     "pp_gtdb_build", "pp_gtdb_count",
+    "pp_eval_match", "pp_eval_pr",
 ]
 
 
@@ -341,6 +342,9 @@ def lib():
     L.pp_ingest_info.argtypes = [vp, vp, vp, i32]
     L.pp_gtdb_build.argtypes = [vp, vp, vp, i32, vp, vp, f32p, i64]
     L.pp_gtdb_count.argtypes = [vp, vp, vp, i32, vp]
+    L.pp_eval_match.argtypes = [ctypes.c_int, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
+    L.pp_eval_pr.argtypes = [ctypes.c_int, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp,
+                             vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)  # raises AttributeError if the symbol is not exported
         if name not in ("pp_last_error", "pp_layer_tag"):

@@ -303,6 +303,35 @@ void launch_riou_pairs(const float* bc, int64_t N, const float* qc, int64_t K, i
 void launch_d3_finish(const double* boxes, int64_t N, const double* qboxes, int64_t K, int criterion,
                       const float* rinc, double* out, hipStream_t s);
 
+// eval_stats.hip: the AP evaluator's greedy matching and tp / fp / fn / similarity statistics (kitti_eval.py)
+struct EvalStatsParams {
+    int nframes, K;            // frames; overlap tiers
+    int total_gt;              // gt_off[nframes]: row length of `matched`
+    const int* gt_off;         // [nframes + 1] first ground truth / detection / DontCare box of each frame
+    const int* dt_off;
+    const int* dc_off;         // (counting pass only)
+    const long long* ov_off;   // [nframes + 1] first overlap of each frame
+    const double* overlaps;    // per frame [G][D]
+    const double* scores;      // [sum D]
+    const int* ign_gt;         // [sum G] 0 counts, 1 neutral, -1 other class
+    const int* ign_dt;         // [sum D]
+    const double* min_overlaps;   // [K]
+    int* matched;              // matching pass out: [K][total_gt] frame-local detection index of a true positive, or -1
+    // counting pass
+    const double* gt_alpha;    // [sum G]
+    const double* dt_alpha;    // [sum D]
+    const double* dt_box;      // [sum D][4]
+    const double* dc_box;      // [sum C][4]
+    const double* thresholds;  // [K][PP_EVAL_NTHRESH]
+    const int* nthresh;        // [K] thresholds in use, each <= PP_EVAL_NTHRESH
+    int metric, compute_aos;
+    double* partial;           // [nframes][K][PP_EVAL_NTHRESH][4] tp, fp, fn, similarity of one frame (slots in use only)
+    double* pr;                // out: [K][PP_EVAL_NTHRESH][4]
+};
+void launch_eval_match(const EvalStatsParams& p, hipStream_t s);
+void launch_eval_count(const EvalStatsParams& p, hipStream_t s);
+void launch_eval_reduce(const EvalStatsParams& p, hipStream_t s);   // partial -> pr, frames added in a fixed order
+
 // targets.hip: training targets from ground-truth boxes on the device (create_target_np, load_data.py:331-532)
 struct TargetParams {
     int batch;

@@ -8,8 +8,11 @@ Mirrors the call surface of the reference's second/utils/eval.py:
   get_thresholds            :18-37     image_box_overlap :97-124
 The rotated-rectangle overlaps (bev_box_overlap :127-129, d3_box_overlap :159-163; numba-CUDA in
 the reference) run on the GPU through the C-ABI (`pp_rotate_iou_eval`, `pp_d3_box_overlap`,
-csrc/rotate_iou.hip) -- there is no CPU fallback for them; everything else is host bookkeeping
-on a few boxes per frame.
+csrc/rotate_iou.hip) -- there is no CPU fallback for them.  The greedy matching and the tp / fp / fn /
+similarity counts run on the host by default (`statistics="host"`: `compute_statistics`, once per frame
+and once more per frame and threshold) or, with `statistics="gpu"`, on the GPU for every frame, overlap
+tier and threshold of a (class, difficulty) at once (`pp_eval_match`, `pp_eval_pr`, csrc/eval_stats.hip);
+everything else is host bookkeeping on a few boxes per frame.
 
 Differences from the reference, none of which change a result it can produce:
   * the greedy gt<->detection matching is evaluated per ground-truth box with array operations
@@ -18,6 +21,7 @@ Differences from the reference, none of which change a result it can produce:
     in the reference to batch the IoU kernel; results are per frame either way), so fewer than
     `num_parts` frames work here (the reference raises on an empty part).
 """
+import ctypes
 import io
 
 import numpy as np
@@ -247,6 +251,109 @@ def compute_statistics(overlaps, gt_datas, dt_datas, ignored_gt, ignored_det, dc
     return tp, fp, fn, similarity, np.array(tp_scores, dtype=np.float64)
 
 
+# ------------------------------------------------------------------------------------------
+# the same statistics on the GPU: every frame, tier and threshold of a (class, difficulty) at once
+# ------------------------------------------------------------------------------------------
+MAX_BOXES_PER_FRAME = 1024      # PP_EVAL_MAX_BOXES
+
+
+def pack_frames(overlaps, gt_list, dt_list, ign_gt, ign_dt, dcs):
+    """Flat arrays + offsets of the per-frame lists `_prepare_data` and `calculate_iou_partly` give, as
+    `pp_eval_match` / `pp_eval_pr` take them.  overlaps[i] is [D_i, G_i] (detections x ground truths, as
+    `compute_statistics` takes it) and is packed ground-truth major ([G_i][D_i]) at ov_off[i]."""
+    n = len(gt_list)
+    if not (len(overlaps) == len(dt_list) == len(ign_gt) == len(ign_dt) == len(dcs) == n):
+        raise ValueError("pack_frames: per-frame lists differ in length")
+    ng = np.array([g.shape[0] for g in gt_list], dtype=np.int64)
+    nd = np.array([d.shape[0] for d in dt_list], dtype=np.int64)
+    nc = np.array([np.asarray(c).reshape(-1, 4).shape[0] for c in dcs], dtype=np.int64)
+    for i in range(n):
+        if tuple(overlaps[i].shape) != (nd[i], ng[i]):
+            raise ValueError(f"pack_frames: frame {i}: overlaps {tuple(overlaps[i].shape)} is not "
+                             f"[detections={nd[i]}, ground truths={ng[i]}]")
+        if len(ign_gt[i]) != ng[i] or len(ign_dt[i]) != nd[i]:
+            raise ValueError(f"pack_frames: frame {i}: ignore flags do not match the boxes")
+
+    def offsets(counts, dtype):
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(counts, out=off[1:])
+        if dtype == np.int32 and off[-1] >= 2 ** 31:
+            raise ValueError("pack_frames: more than 2^31 boxes")
+        return off.astype(dtype)
+
+    def cat(parts, width, dtype):
+        shape = (0,) if width is None else (0, width)
+        parts = [np.asarray(a, dtype=dtype).reshape((-1,) if width is None else (-1, width)) for a in parts]
+        return np.ascontiguousarray(np.concatenate(parts, 0) if parts else np.zeros(shape, dtype=dtype))
+
+    gt = cat(gt_list, 5, np.float64)
+    dt = cat(dt_list, 6, np.float64)
+    return {
+        "nframes": n,
+        "gt_off": offsets(ng, np.int32), "dt_off": offsets(nd, np.int32), "dc_off": offsets(nc, np.int32),
+        "ov_off": offsets(ng * nd, np.int64),
+        "overlaps": cat([np.asarray(o, dtype=np.float64).T for o in overlaps], None, np.float64),
+        "scores": np.ascontiguousarray(dt[:, 5]), "dt_alphas": np.ascontiguousarray(dt[:, 4]),
+        "dt_boxes": np.ascontiguousarray(dt[:, :4]), "gt_alphas": np.ascontiguousarray(gt[:, 4]),
+        "ign_gt": cat(ign_gt, None, np.int32), "ign_dt": cat(ign_dt, None, np.int32),
+        "dc_boxes": cat(dcs, 4, np.float64),
+    }
+
+
+def _ptr(a):
+    return a.ctypes.data if a.size else None
+
+
+def match_frames_gpu(packed, min_overlaps, device_id=0, kernel_ms=None):
+    """Pass 1 (`compute_statistics(..., compute_fp=False)`) of every frame at every tier in one call.
+    Returns [K, total ground truths] int32: the frame-local index of the detection counted as a true
+    positive, or -1.  `kernel_ms`, a list, receives the kernel's device time."""
+    mo = np.ascontiguousarray(min_overlaps, dtype=np.float64).reshape(-1)
+    out = np.full((mo.shape[0], int(packed["gt_off"][-1])), -1, dtype=np.int32)
+    ms = ctypes.c_float(0.0)
+    p = packed
+    _check(_lib.lib().pp_eval_match(int(device_id), p["nframes"], _ptr(p["gt_off"]), _ptr(p["dt_off"]), _ptr(p["ov_off"]),
+                                    _ptr(p["overlaps"]), _ptr(p["scores"]), _ptr(p["ign_gt"]), _ptr(p["ign_dt"]),
+                                    _ptr(mo), mo.shape[0], _ptr(out), ctypes.addressof(ms)), "match_frames_gpu")
+    if kernel_ms is not None:
+        kernel_ms.append(ms.value)
+    return out
+
+
+def matched_scores(packed, matched_row):
+    """The true positives' scores of one tier, in frame and ground-truth order (what the host loop collects)."""
+    frame_of_gt = np.repeat(np.arange(packed["nframes"]), np.diff(packed["gt_off"]))
+    hit = matched_row >= 0
+    return packed["scores"][packed["dt_off"][:-1][frame_of_gt[hit]] + matched_row[hit]]
+
+
+def pr_frames_gpu(packed, min_overlaps, thresholds, nthresh, metric, compute_aos=False, device_id=0, kernel_ms=None):
+    """Pass 2 (`compute_fp=True`) of every frame at every tier and threshold, summed over the frames.
+    thresholds [K, 41] float64 with nthresh[k] in use.  Returns pr [K, 41, 4] = tp, fp, fn, similarity."""
+    mo = np.ascontiguousarray(min_overlaps, dtype=np.float64).reshape(-1)
+    th = np.ascontiguousarray(thresholds, dtype=np.float64)
+    nt = np.ascontiguousarray(nthresh, dtype=np.int32).reshape(-1)
+    if th.shape != (mo.shape[0], N_SAMPLE_PTS) or nt.shape[0] != mo.shape[0]:
+        raise ValueError(f"pr_frames_gpu: thresholds must be [{mo.shape[0]}, {N_SAMPLE_PTS}] with one count per tier")
+    pr = np.zeros((mo.shape[0], N_SAMPLE_PTS, 4), dtype=np.float64)
+    ms = ctypes.c_float(0.0)
+    p = packed
+    _check(_lib.lib().pp_eval_pr(int(device_id), p["nframes"], _ptr(p["gt_off"]), _ptr(p["dt_off"]), _ptr(p["ov_off"]),
+                                 _ptr(p["overlaps"]), _ptr(p["scores"]), _ptr(p["ign_gt"]), _ptr(p["ign_dt"]), _ptr(mo),
+                                 mo.shape[0], _ptr(p["gt_alphas"]), _ptr(p["dt_alphas"]), _ptr(p["dt_boxes"]),
+                                 _ptr(p["dc_off"]), _ptr(p["dc_boxes"]), int(metric), int(bool(compute_aos)), _ptr(th),
+                                 _ptr(nt), _ptr(pr), ctypes.addressof(ms)), "pr_frames_gpu")
+    if kernel_ms is not None:
+        kernel_ms.append(ms.value)
+    return pr
+
+
+def _statistics_mode(statistics):
+    if statistics not in ("host", "gpu"):
+        raise ValueError(f"statistics must be 'host' or 'gpu', not {statistics!r}")
+    return statistics
+
+
 def get_thresholds(scores, num_gt, num_sample_pts=41):
     """Scores at which recall crosses the 41 sample points."""
     scores = np.sort(np.asarray(scores))[::-1]
@@ -278,9 +385,11 @@ def _prepare_data(gt_annos, dt_annos, current_class, difficulty):
 
 
 def eval_class_v3(gt_annos, dt_annos, current_classes, difficultys, metric, min_overlaps, compute_aos=False,
-                  num_parts=50, overlap_fns=None):
-    """precision / recall / orientation arrays [class, difficulty, overlap tier, 41]."""
+                  num_parts=50, overlap_fns=None, statistics="host", device_id=0):
+    """precision / recall / orientation arrays [class, difficulty, overlap tier, 41].  statistics="gpu": the
+    two per-frame loops run on the GPU, all tiers of a (class, difficulty) in two calls."""
     assert len(gt_annos) == len(dt_annos)
+    _statistics_mode(statistics)
     overlaps, _, _, _ = calculate_iou_partly(dt_annos, gt_annos, metric, num_parts, overlap_fns)
     shape = [len(current_classes), len(difficultys), len(min_overlaps), N_SAMPLE_PTS]
     precision, recall, aos = np.zeros(shape), np.zeros(shape), np.zeros(shape)
@@ -288,23 +397,38 @@ def eval_class_v3(gt_annos, dt_annos, current_classes, difficultys, metric, min_
     for m, current_class in enumerate(current_classes):
         for l, difficulty in enumerate(difficultys):
             gt_list, dt_list, ign_gt, ign_dt, dcs, total_valid = _prepare_data(gt_annos, dt_annos, current_class, difficulty)
-            for k, min_overlap in enumerate(min_overlaps[:, metric, m]):
-                tp_scores = []
-                for i in range(nframes):
-                    tp_scores += compute_statistics(overlaps[i], gt_list[i], dt_list[i], ign_gt[i], ign_dt[i], dcs[i],
-                                                    metric, min_overlap, 0.0, False)[4].tolist()
-                thresholds = np.array(get_thresholds(np.array(tp_scores), total_valid))
-                pr = np.zeros([len(thresholds), 4])
-                for i in range(nframes):
-                    for t, thresh in enumerate(thresholds):
-                        tp, fp, fn, sim, _ = compute_statistics(overlaps[i], gt_list[i], dt_list[i], ign_gt[i], ign_dt[i],
-                                                                dcs[i], metric, min_overlap, thresh, True, compute_aos)
-                        pr[t, 0] += tp
-                        pr[t, 1] += fp
-                        pr[t, 2] += fn
-                        if sim != -1:
-                            pr[t, 3] += sim
-                nt = len(thresholds)
+            tiers = np.ascontiguousarray(min_overlaps[:, metric, m], dtype=np.float64)
+            if statistics == "gpu":
+                packed = pack_frames(overlaps, gt_list, dt_list, ign_gt, ign_dt, dcs)
+                matched = match_frames_gpu(packed, tiers, device_id)
+                tier_thresholds = np.zeros((len(tiers), N_SAMPLE_PTS))
+                tier_nt = np.zeros(len(tiers), dtype=np.int32)
+                for k in range(len(tiers)):
+                    th = get_thresholds(matched_scores(packed, matched[k]), total_valid)
+                    tier_nt[k] = len(th)
+                    tier_thresholds[k, :len(th)] = th
+                tier_pr = pr_frames_gpu(packed, tiers, tier_thresholds, tier_nt, metric, compute_aos, device_id)
+            for k, min_overlap in enumerate(tiers):
+                if statistics == "gpu":
+                    pr = tier_pr[k, :tier_nt[k]]
+                else:
+                    tp_scores = []
+                    for i in range(nframes):
+                        tp_scores += compute_statistics(overlaps[i], gt_list[i], dt_list[i], ign_gt[i], ign_dt[i], dcs[i],
+                                                        metric, min_overlap, 0.0, False)[4].tolist()
+                    thresholds = np.array(get_thresholds(np.array(tp_scores), total_valid))
+                    pr = np.zeros([len(thresholds), 4])
+                    for i in range(nframes):
+                        for t, thresh in enumerate(thresholds):
+                            tp, fp, fn, sim, _ = compute_statistics(overlaps[i], gt_list[i], dt_list[i], ign_gt[i],
+                                                                    ign_dt[i], dcs[i], metric, min_overlap, thresh, True,
+                                                                    compute_aos)
+                            pr[t, 0] += tp
+                            pr[t, 1] += fp
+                            pr[t, 2] += fn
+                            if sim != -1:
+                                pr[t, 3] += sim
+                nt = pr.shape[0]
                 with np.errstate(divide="ignore", invalid="ignore"):
                     recall[m, l, k, :nt] = pr[:, 0] / (pr[:, 0] + pr[:, 2])
                     precision[m, l, k, :nt] = pr[:, 0] / (pr[:, 0] + pr[:, 1])
@@ -324,30 +448,33 @@ def get_mAP_v2(prec):
 
 
 def do_eval_v2(gt_annos, dt_annos, current_classes, min_overlaps, compute_aos=False, difficultys=(0, 1, 2),
-               compute_bbox=True, overlap_fns=None):
+               compute_bbox=True, overlap_fns=None, statistics="host", device_id=0):
     """min_overlaps [tier, metric, class] -> mAP arrays [class, difficulty, tier] for bbox, bev, 3d, aos."""
+    _statistics_mode(statistics)
+    kw = dict(overlap_fns=overlap_fns, statistics=statistics, device_id=device_id)
     mAP_bbox = None
     if compute_bbox:
-        ret = eval_class_v3(gt_annos, dt_annos, current_classes, difficultys, 0, min_overlaps, compute_aos,
-                            overlap_fns=overlap_fns)
+        ret = eval_class_v3(gt_annos, dt_annos, current_classes, difficultys, 0, min_overlaps, compute_aos, **kw)
         mAP_bbox = get_mAP_v2(ret["precision"])
-    ret = eval_class_v3(gt_annos, dt_annos, current_classes, difficultys, 1, min_overlaps, compute_aos,
-                        overlap_fns=overlap_fns)
+    ret = eval_class_v3(gt_annos, dt_annos, current_classes, difficultys, 1, min_overlaps, compute_aos, **kw)
     mAP_bev = get_mAP_v2(ret["precision"])
     mAP_aos = get_mAP_v2(ret["orientation"]) if compute_aos else None
-    ret = eval_class_v3(gt_annos, dt_annos, current_classes, difficultys, 2, min_overlaps, overlap_fns=overlap_fns)
+    ret = eval_class_v3(gt_annos, dt_annos, current_classes, difficultys, 2, min_overlaps, **kw)
     mAP_3d = get_mAP_v2(ret["precision"])
     return mAP_bbox, mAP_bev, mAP_3d, mAP_aos
 
 
-def do_coco_style_eval(gt_annos, dt_annos, current_classes, overlap_ranges, compute_aos, overlap_fns=None):
+def do_coco_style_eval(gt_annos, dt_annos, current_classes, overlap_ranges, compute_aos, overlap_fns=None,
+                       statistics="host", device_id=0):
     """overlap_ranges [3 = (lo, hi, count), metric, class] -> means over the `count` tiers."""
+    _statistics_mode(statistics)
     min_overlaps = np.zeros([10, *overlap_ranges.shape[1:]])
     for i in range(overlap_ranges.shape[1]):
         for j in range(overlap_ranges.shape[2]):
             lo, hi, cnt = overlap_ranges[:, i, j]
             min_overlaps[:, i, j] = np.linspace(lo, hi, int(cnt))
-    res = do_eval_v2(gt_annos, dt_annos, current_classes, min_overlaps, compute_aos, overlap_fns=overlap_fns)
+    res = do_eval_v2(gt_annos, dt_annos, current_classes, min_overlaps, compute_aos, overlap_fns=overlap_fns,
+                     statistics=statistics, device_id=device_id)
     return tuple(None if r is None else r.mean(-1) for r in res)
 
 
@@ -389,13 +516,16 @@ def official_min_overlaps():
 
 
 def get_official_eval_result(gt_annos, dt_annos, current_classes, difficultys=[0, 1, 2], return_data=True,
-                             compute_bbox=True, overlap_fns=None):
-    """The report `train.py evaluate` prints (train.py:899-901) plus the mAP arrays."""
+                             compute_bbox=True, overlap_fns=None, statistics="host", device_id=0):
+    """The report `train.py evaluate` prints (train.py:899-901) plus the mAP arrays.  statistics="gpu" runs the
+    matching and the tp / fp / fn counts on HIP device `device_id`; the report is the same."""
+    _statistics_mode(statistics)
     current_classes = _class_ids(current_classes)
     min_overlaps = official_min_overlaps()[:, :, current_classes]
     compute_aos = _has_alpha(dt_annos)
     mAPbbox, mAPbev, mAP3d, mAPaos = do_eval_v2(gt_annos, dt_annos, current_classes, min_overlaps, compute_aos,
-                                                difficultys, compute_bbox=compute_bbox, overlap_fns=overlap_fns)
+                                                difficultys, compute_bbox=compute_bbox, overlap_fns=overlap_fns,
+                                                statistics=statistics, device_id=device_id)
     result = ''
     for j, curcls in enumerate(current_classes):
         for i in range(min_overlaps.shape[0]):
@@ -417,14 +547,16 @@ _COCO_RANGE = {0: [0.5, 0.95, 10], 1: [0.25, 0.7, 10], 2: [0.25, 0.7, 10], 3: [0
                5: [0.5, 0.95, 10], 6: [0.5, 0.95, 10], 7: [0.5, 0.95, 10]}
 
 
-def get_coco_eval_result(gt_annos, dt_annos, current_classes, overlap_fns=None):
+def get_coco_eval_result(gt_annos, dt_annos, current_classes, overlap_fns=None, statistics="host", device_id=0):
+    _statistics_mode(statistics)
     current_classes = _class_ids(current_classes)
     overlap_ranges = np.zeros([3, 3, len(current_classes)])
     for i, curcls in enumerate(current_classes):
         overlap_ranges[:, :, i] = np.array(_COCO_RANGE[curcls])[:, np.newaxis]
     compute_aos = _has_alpha(dt_annos)
     mAPbbox, mAPbev, mAP3d, mAPaos = do_coco_style_eval(gt_annos, dt_annos, current_classes, overlap_ranges,
-                                                        compute_aos, overlap_fns=overlap_fns)
+                                                        compute_aos, overlap_fns=overlap_fns,
+                                                        statistics=statistics, device_id=device_id)
     result = ''
     for j, curcls in enumerate(current_classes):
         o_range = np.array(_COCO_RANGE[curcls])[[0, 2, 1]]

@@ -278,6 +278,35 @@ int pp_rotate_iou_eval(int device, const float* boxes, int64_t n, const float* q
 int pp_d3_box_overlap(int device, const double* boxes, int64_t n, const double* query_boxes, int64_t k,
                       int32_t criterion, double* out);
 
+/* ---- AP-evaluator statistics ----------------- */
+
+#define PP_EVAL_NTHRESH 41     /* recall sample points: thresholds per overlap tier */
+#define PP_EVAL_MAX_BOXES 1024 /* most ground truths, and most detections, one frame may hold */
+
+/* Replace the per-frame loops over compute_statistics_jit (second/utils/eval.py:166-287) of eval_class_v3
+ * (:552-660, fused_compute_statistics :298-345) for all `ntiers` overlap tiers of one (class, difficulty).
+ * Stateless; host pointers; `device` is the HIP device.  Frame f holds ground truths gt_off[f] .. gt_off[f+1],
+ * detections dt_off[f] .. dt_off[f+1] and its overlaps at ov_off[f], packed [G][D] (ground truth major), float64;
+ * every offset array has nframes + 1 entries and starts at 0.  ignored_gt / ignored_det: 0 counts, 1 neutral,
+ * -1 another class (clean_data).  A frame with more than PP_EVAL_MAX_BOXES ground truths or detections is
+ * PP_ERR_ARG.  No frames, or no boxes at all, is PP_OK with zeroed output.  kernel_ms (may be NULL) receives the
+ * device time of the call's kernels.
+ *
+ * pp_eval_match: the pass with compute_fp = False.  matched [ntiers, gt_off[nframes]] int32: per tier and ground
+ * truth the frame-local index of the detection counted as a true positive, or -1.
+ * pp_eval_pr: the pass with compute_fp = True at thresholds [ntiers, PP_EVAL_NTHRESH] (nthresh[k] in use), summed
+ * over the frames in a fixed order: pr [ntiers, PP_EVAL_NTHRESH, 4] float64 = tp, fp, fn, similarity sum; slots
+ * past nthresh[k] are zero.  metric 0 takes the DontCare boxes (dc_off, dc_boxes [.,4]) off the false positives;
+ * compute_aos adds (1 + cos(gt_alpha - dt_alpha)) / 2 per true positive. */
+int pp_eval_match(int device, int32_t nframes, const int32_t* gt_off, const int32_t* dt_off, const int64_t* ov_off,
+                  const double* overlaps, const double* scores, const int32_t* ignored_gt, const int32_t* ignored_det,
+                  const double* min_overlaps, int32_t ntiers, int32_t* matched, float* kernel_ms);
+int pp_eval_pr(int device, int32_t nframes, const int32_t* gt_off, const int32_t* dt_off, const int64_t* ov_off,
+               const double* overlaps, const double* scores, const int32_t* ignored_gt, const int32_t* ignored_det,
+               const double* min_overlaps, int32_t ntiers, const double* gt_alphas, const double* dt_alphas,
+               const double* dt_boxes, const int32_t* dc_off, const double* dc_boxes, int32_t metric,
+               int32_t compute_aos, const double* thresholds, const int32_t* nthresh, double* pr, float* kernel_ms);
+
 /* ---- training loss at the head maps ---------- */
 
 /* Mirrors model.second.loss / pos_class_weight / ... of configs/train.yaml:147-167. */
