@@ -17,7 +17,7 @@ _INCLUDE = os.path.join(os.path.dirname(_PKG), "include", "pp_hip.h")
 #   PP_HIP_LIB=libpp_hip_g.so PP_HIPCC_EXTRA="-g" python -c "import pp_amd; pp_amd._lib.build()"
 SO_PATH = os.path.join(_PKG, os.environ.get("PP_HIP_LIB", "libpp_hip.so"))
 _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
-SOURCES = ["pp_api.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
+SOURCES = ["pp_api.hip", "api_ingest.hip", "api_eval.hip", "api_train.hip", "api_dataprep.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
            "rotate_iou.hip", "loss.hip", "optim.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip",
            "gt_database.hip", "eval_stats.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD

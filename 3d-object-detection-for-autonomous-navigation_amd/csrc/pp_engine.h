@@ -1,0 +1,348 @@
+// Host side of the C-ABI (include/pp_hip.h), shared by its translation units: the handle, the error / allocation
+// helpers and what one unit calls in another.  pp_api.hip: lifetime, weights, feeds, the inference pipeline;
+// api_ingest.hip: PointCloud2 ingest; api_train.hip: loss, training step, optimizer; api_dataprep.hip: targets,
+// augmentation, GT sampling, object database; api_eval.hip: the AP evaluator (needs no handle).
+#pragma once
+
+#include <cmath>
+#include <algorithm>
+#include <functional>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "pp_common.h"
+#include "train.h"
+
+struct KTime { const char* name; int ev; };
+
+// Ground-truth boxes on the device, the frames' boxes back to back (a kernel reads cls == NULL as class 1, valid == NULL as all valid)
+struct GtSet {
+    float* boxes = nullptr;      // [B * PP_MAX_GT_PER_FRAME][7]
+    int* cls = nullptr;          // [B * PP_MAX_GT_PER_FRAME]
+    uint8_t* valid = nullptr;
+    int* cnt = nullptr;          // [B]
+};
+
+struct pp_engine {
+    pp_config cfg;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    VoxGeom geom;
+    int nx = 0, ny = 0, nz = 0, ncell = 0;
+    int head_h = 0, head_w = 0, napl = 0, ncls = 1;
+    bool use_dir = true, with_dist = false;
+    int64_t A = 0;
+    int C = 0, F = 0, T = 0, FA = 0, CC = 0;
+    int B = 0, NMAX = 0;
+
+    std::map<std::string, std::vector<float>> hw;
+    std::map<std::string, std::vector<int64_t>> hshape;
+    bool weights_ready = false, anchors_ready = false;
+    std::vector<void*> allocs;    // device memory released by pp_destroy (dalloc)
+    std::vector<void*> wallocs;   // weight buffers: released and re-made by every pp_finalize_weights
+
+    // raw points and frame offsets are double-buffered: an upload fills the buffer the previous pass is NOT
+    // reading (pp_upload_points_async on the copy stream, so the copy of batch k+1 runs beside the kernels of
+    // batch k); d_points / d_offsets point at the buffer the next pp_detect_async consumes
+    float* d_points_buf[2] = {nullptr, nullptr};
+    int* d_offsets_buf[2] = {nullptr, nullptr};
+    int in_buf = 0;                       // index of d_points / d_offsets (and of the voxeliser products: vox[])
+    // The voxeliser's products exist twice as well (round 4): pp_upload_points_async voxelises batch k+1 right behind
+    // its copy, on the copy stream, while batch k's PFN .. post-process read the other set -- the single-workgroup-
+    // per-frame voxeliser (36 us on 64 of 256 CUs at B = 64) is then off the pass's chain of dependent launches.
+    // The d_* members below always point at set in_buf (flip_input).
+    struct VoxSet {
+        float* points_sorted = nullptr;
+        int *cellmap = nullptr, *pstart = nullptr, *pcell = nullptr, *npillars = nullptr, *nvalid = nullptr;
+        unsigned long long* occbits = nullptr;
+        bool occ_cleared = false;         // its k_cell_first cleared the occupancy bitmap (consumed by run_pfn)
+    } vox[2];
+    int cache_budget_mb = 256;            // run_backbone's frame sub-ranges (pp_set_cache_budget; 0 = off)
+    bool vox_ahead = false;               // the resident batch was voxelised at upload time (pp_detect_async skips it)
+    bool prevox_issued = false;           // a voxeliser launch is (or was) queued on the copy stream: a main-stream one waits for ev_up
+    // ... and the other direction: a voxeliser launch is (or was) queued on the main stream (the zero-copy, synchronous and
+    // device feeds, profiling, the stage call, training), so the next copy-stream one waits for ev_vox_main
+    bool main_vox_pending = false;
+    hipEvent_t ev_vox_main = nullptr;     // recorded on the main stream (outside any capture) by that wait
+    int results_buf = 0;                  // set the last pp_detect_async read (pp_fetch_intermediates)
+    hipStream_t copy_stream = nullptr;   // the device's shared upload stream (not owned by the handle)
+    hipEvent_t ev_up = nullptr;           // recorded on the copy stream behind an asynchronous upload
+    hipEvent_t ev_tgt = nullptr;          // ... behind the labels / boxes / draws of a training step (copies_done)
+    bool up_pending = false;              // the next reader of the resident frames must wait for ev_up (wait_for_upload)
+    hipEvent_t ev_read[2] = {nullptr, nullptr};   // recorded on the main stream behind the pass that read buffer i
+    float* d_points = nullptr;
+    float* d_points_sorted = nullptr;   // pillar-sorted copy left by k_sort_points (what the PFN streams)
+    int* d_offsets = nullptr;
+    float* spare_pts = nullptr;         // [B * NMAX][F] where the augmentation and the GT sampling write the new cloud
+                                        // before it replaces the resident one (ensure_spare_pts: first use by either)
+    int* d_cell = nullptr;
+    int* d_first = nullptr;
+    int* d_cellmap = nullptr;
+    unsigned *d_keyA = nullptr, *d_idxA = nullptr, *d_keyB = nullptr, *d_idxB = nullptr;
+    int* d_pstart = nullptr;
+    int* d_pcell = nullptr;
+    int* d_npillars = nullptr;
+    int* d_nvalid = nullptr;
+    float *d_pfn_w = nullptr, *d_pfn_b = nullptr;
+    float* d_canvas = nullptr;
+    float* d_act[2] = {nullptr, nullptr};
+    float* d_concat = nullptr;
+    float* d_head = nullptr;      // fused head map [B][H'*W'][PP_HEAD_COLS]
+    float* d_cls = nullptr;       // compact class-logit plane [B][H'*W'][napl*ncls] (last fused-head deconv -> post-process)
+    bool cls_plane_live = false;  // the last forward pass wrote d_cls (fused path with the uniform deconv kernels)
+    bool fuse_heads = false;      // heads computed in the deconv epilogues (no concat buffer, no head launch)
+    bool sparse_canvas = false;   // PFN writes occupied cells only; layer 0 consults the cell map (pp_finalize_weights)
+    int* d_integ = nullptr;
+    unsigned long long* d_occbits = nullptr;   // [B][ny][occ_words(nx)] occupancy bitmap of the sparse-canvas passes
+    bool occbits_live = false;                 // this pass's PFN launch wrote it (the pillar-centric kernel)
+    uint8_t* d_mask = nullptr;
+    float* d_anchors = nullptr;
+    int* d_cells = nullptr;
+    float4* d_anchor_near = nullptr;   // [A] nearest standing / lying box of every anchor (target assignment)
+    float* d_calib = nullptr;
+    pp_detection* d_dets = nullptr;
+    int* d_ndets = nullptr;
+    pp_detection* h_dets = nullptr;  // pinned
+    int* h_ndets = nullptr;          // pinned
+    std::vector<LayerDesc> layers;
+    std::vector<std::string> layer_tags;  // "<kernel symbol>:<layer>" for the profiler (for batch tag_batch)
+    int tag_batch = -1;
+
+    // compat scratch (grow-only)
+    float* d_voxels = nullptr; size_t cap_voxels = 0;
+    int* d_numpts = nullptr;   size_t cap_numpts = 0;
+    int* d_coors = nullptr;    size_t cap_coors = 0;
+    float* d_feat = nullptr;   size_t cap_feat = 0;
+
+    // the resident batch: written by set_resident only
+    int cur_batch = 0, cur_max_n = 0;
+    int cur_total = 0;                    // points of the resident frames (host copy of the last offset)
+    std::vector<int> h_cur_off;           // host copy of the resident frames' offsets [cur_batch + 1]
+    bool off_host_exact = true;           // ... false: they are bounds, the sizes are device values (require_host_exact)
+    int results_batch = 0;        // frames of the last enqueued pp_detect_async (0: no results to fetch)
+    // frame offsets travel through a small pinned ring (a pageable source would be staged synchronously and a
+    // single pinned buffer could be rewritten while its copy is still queued); a slot is reused only after the
+    // event recorded behind its copy has passed
+    static constexpr int OFF_RING = 4;
+    int* h_off_ring = nullptr;    // pinned [OFF_RING][B + 1]
+    hipEvent_t off_ev[OFF_RING] = {nullptr, nullptr, nullptr, nullptr};
+    int off_slot = 0;
+    hipEvent_t ev_in = nullptr;   // orders the engine's stream behind a producer stream (pp_upload_points_device)
+    // zero-copy feed of small batches (pp_upload_points_async, batch <= ZC_MAX_BATCH): one page-locked descriptor
+    // per input buffer, read by k_cell_first; no copy-engine transfer, no events
+    PpFeed* h_feed[2] = {nullptr, nullptr};
+    const PpFeed* d_feed[2] = {nullptr, nullptr};
+    bool zc = false;              // the uploaded batch is fed that way
+
+    // ---- the subsystems' buffers; all but `tgt` are allocated on first use, by the ensure_*() next to their user ----
+    struct Loss {                          // pp_head_loss and the training step (api_train.hip: ensure_loss_buffers)
+        int* labels = nullptr;             // [B][A]
+        float* regt = nullptr;             // [B][A][7]
+        int* npos = nullptr;
+        double* partials = nullptr;
+        float* out = nullptr;              // [8]
+        float* head_grad = nullptr;
+    } loss;
+    struct Tgt {                           // target assignment from boxes (pp_assign_targets / pp_train_step_gt*)
+        GtSet gt;                          // the boxes the assignment reads (no `valid`): uploaded, or the augmentation's output
+        unsigned* top = nullptr;           // per box: its best overlap (float bits), reset before every assignment
+        uint8_t* mask = nullptr;           // [B][A] the assignment's anchor mask (d_mask stays the inference pass's)
+        int* index = nullptr;              // [B][A] optional outputs of pp_assign_targets, allocated on first use
+        float* overlap = nullptr;
+    } tgt;
+    struct Aug {                           // training-time augmentation (pp_augment / pp_train_step_aug*)
+        bool ready = false;
+        GtSet in;                          // the boxes as given
+        double* draws = nullptr;           // [B * PP_MAX_GT_PER_FRAME][PP_AUG_MAX_TRY][5]
+        pp_aug_frame* frames = nullptr;
+        AugBox* rec = nullptr;
+        float* box_tmp = nullptr;
+        uint8_t* keep = nullptr;
+        int* sel = nullptr;                // [B * PP_MAX_GT_PER_FRAME] the selected try per input box (pp_augment_selected)
+        int* draw_off = nullptr;           // [B] first draw row of each frame (the sampled step: rows are allotted per frame)
+        std::vector<int> h_draw_off;       // its host side
+        double* cs = nullptr;              // [B][2]
+        int64_t total = 0;                 // input boxes of the last augmentation
+    } aug;
+    struct Db {                            // the loaded object database (pp_gtdb_load): replaced as a whole, not in `allocs`
+        float* pts = nullptr;
+        int* off = nullptr;
+        double* box = nullptr;
+        int* cls = nullptr;
+        std::vector<int> h_npts;           // points per object (the host-side bound on the pasted cloud)
+        int64_t n = -1;                    // objects loaded; -1: no database
+    } db;
+    struct Gts {                           // GT-database sampling (pp_gt_sample / pp_train_step_sample*)
+        bool ready = false;
+        GtSet in, out;                     // the boxes as given; the frame's boxes, then the accepted objects'
+        pp_gts_cand* cands = nullptr;      // [B][PP_GTS_MAX_CAND]
+        int* cand_counts = nullptr;        // [B][PP_GTS_MAX_ROUNDS]
+        GtsPlane* planes = nullptr;
+        int *status = nullptr, *counts = nullptr, *round = nullptr;
+        int *acc_n = nullptr, *acc_slot = nullptr, *acc_pstart = nullptr, *box_off = nullptr;
+        int* offsets = nullptr;            // [B + 1] the frames' offsets after pasting
+        int batch = 0;                     // frames of the last pp_gt_sample (pp_gt_sample_info)
+    } gts;
+    struct Gdb {                           // building the object database from the resident frames (pp_gtdb_build / _count)
+        bool ready = false;
+        double* boxes = nullptr;           // [B * PP_MAX_GT_PER_FRAME][7]
+        int *cnt = nullptr, *boxoff = nullptr;   // [B], [B + 1]
+        GtsPlane* planes = nullptr;        // [B * PP_MAX_GT_PER_FRAME]
+        int* chunks = nullptr;             // [B][ceil(NMAX / PP_GDB_CHUNK)][PP_MAX_GT_PER_FRAME]
+        int* totals = nullptr;             // [B * PP_MAX_GT_PER_FRAME]
+        long long* off = nullptr;          // [B * PP_MAX_GT_PER_FRAME + 1]
+        float* out = nullptr;  size_t cap_out = 0;   // the cut-out points grow to the largest build seen (dgrow)
+    } gdb;
+    struct Ing {                           // live PointCloud2 ingest (pp_ingest_pointcloud2*); raw / chunks grow (dgrow)
+        uint8_t* raw = nullptr;  size_t cap_raw = 0;       // the messages' bytes
+        int* chunks = nullptr;   size_t cap_chunks = 0;    // [2][batch * stride]: chunk counts, chunk bases
+        IngFrame* frames = nullptr;        // [B]
+        IngFrame* h_ring = nullptr;        // pinned [OFF_RING][B]: travels with the offsets' ring slots
+        int *finite = nullptr, *kept = nullptr;            // [B]
+        int batch = 0;                     // frames of the last ingest (pp_ingest_info)
+    } ing;
+
+    // training step (train.hip): shapes, plan (the flat layout among it) and device buffers, set up by the first
+    // pp_train_* call
+    struct TrainState {
+        TrainShape shape;
+        TrainPlan plan;
+        TrainCtx cx;
+        bool buffers = false;
+        // the ~250 launches of a step replay as one hipGraph while nothing they depend on changes; ONE GRAPH PER INPUT
+        // BUFFER: every upload flips the handle's input buffer (the kernels' point / offset pointers), so a single
+        // graph would be re-captured on every optimizer step
+        struct Graph {
+            hipGraphExec_t exec = nullptr;     // voxelise + forward
+            hipGraphExec_t exec_bwd = nullptr; // loss + backward (launched behind the target upload's event)
+            int batch = -1, bucket = -1, zc = 0;
+            const void *params = nullptr, *grads = nullptr, *state = nullptr;
+            pp_loss_config loss;
+            std::vector<unsigned char> frozen;     // TrainPlan::frozen it was captured with
+        } graph[2];
+        int last_batch = 0;    // frames of the last step (pp_train_fetch_decisions)
+        int graph_state = 0;   // -1: capture failed once, plain launches from then on
+        int n_captures = 0, n_replays = 0;   // pp_train_graph_stats
+    };
+    TrainState* train = nullptr;
+    float* h_train_losses = nullptr;      // page-locked [8]: the losses of a step launched by pp_train_step_async
+    bool train_pending = false;           // ... which pp_train_step_wait has not collected yet
+    bool mask_in_pfn = false;      // the last run_pfn also computed the anchor mask (few frames)
+    int f32_fallback_layers = 0;   // layers whose folded weights do not fit float16 pieces (pp_finalize_weights)
+    bool force_f32 = false;        // pp_set_gemm_precision(PP_PREC_F32): no layer gets split weights
+
+    int prof = 0;
+    // pp_detect_async as one hipGraph launch (captured on first use per (batch, max points per frame))
+    struct GraphSlot { hipGraphExec_t exec = nullptr; int batch = -1, bucket = -1, buf = -1, zc = 0, vox = 0; unsigned long long used = 0; };
+    GraphSlot graphs[8];          // small LRU keyed by (batch, point-count bucket, input buffer)
+    unsigned long long graph_tick = 0;
+    int graph_state = 0;          // 0: try, -1: capture failed once (use plain launches)
+    std::vector<hipEvent_t> events;
+    std::vector<KTime> ktimes;
+    int ev_used = 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+};
+
+// records the message on the handle (e == NULL: for pp_last_error(NULL)) and returns `code`
+int fail(pp_engine* e, int code, const char* fmt, ...);
+
+#define HIPCHK(e, call)                                                                              \
+    do {                                                                                             \
+        hipError_t _st = (call);                                                                     \
+        if (_st != hipSuccess)                                                                       \
+            return fail(e, PP_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_st), __FILE__, __LINE__); \
+    } while (0)
+
+template <typename Tp>
+int dalloc(pp_engine* e, Tp** p, size_t count) {
+    void* q = nullptr;
+    size_t bytes = count * sizeof(Tp);
+    if (bytes == 0) bytes = sizeof(Tp);
+    HIPCHK(e, hipMalloc(&q, bytes));
+    e->allocs.push_back(q);
+    *p = (Tp*)q;
+    return PP_OK;
+}
+// a run of allocations that stops at the first failure: `DevAlloc A{e}; A(&p, n); A(&q, m); return A.st;`
+struct DevAlloc {
+    pp_engine* e;
+    int st = PP_OK;
+    template <typename Tp> void operator()(Tp** p, size_t count) { if (st == PP_OK) st = dalloc(e, p, count); }
+};
+template <typename Tp>
+int dgrow(pp_engine* e, Tp** p, size_t* cap, size_t count) {
+    if (count <= *cap && *p) return PP_OK;
+    if (*p) { (void)hipStreamSynchronize(e->stream); (void)hipFree(*p); *p = nullptr; *cap = 0; }
+    void* q = nullptr;
+    HIPCHK(e, hipMalloc(&q, (count ? count : 1) * sizeof(Tp)));
+    *p = (Tp*)q;
+    *cap = count;
+    return PP_OK;
+}
+
+// ---- profiling: an event pair around each kernel launch ----
+inline void prof_reset(pp_engine* e) { e->ktimes.clear(); e->ev_used = 0; }
+int prof_event(pp_engine* e);
+
+// Stage scope: the kernel launches inside record their own start / stop events (PP_LAUNCH) under `name`
+// (NULL: under each launch site's kernel name); non-kernel work (a memset) is bracketed with plain event records.
+struct ProfScope {
+    pp_engine* e;
+    int e1 = -1;
+    PpProf saved;          // scopes nest (pp_train_step wraps the voxeliser's named scopes)
+    ProfScope(pp_engine* en, const char* name, bool bracket = false) : e(en), saved(g_pp_prof) {
+        if (e->prof <= 0) return;
+        if (bracket) {
+            int e0 = prof_event(e);
+            e1 = prof_event(e);
+            if (e0 < 0 || e1 < 0) { e1 = -1; return; }
+            (void)hipEventRecord(e->events[e0], e->stream);
+            e->ktimes.push_back({name, e0});
+        } else {
+            g_pp_prof.e = e;
+            g_pp_prof.tag = name;
+        }
+    }
+    ~ProfScope() {
+        if (e1 >= 0) (void)hipEventRecord(e->events[e1], e->stream);
+        g_pp_prof = saved;
+    }
+};
+
+// ---- pp_api.hip: the pipeline stages (all enqueue on e->stream; run_voxelize on `vs` when given) ----
+int run_voxelize(pp_engine* e, int batch, int max_n, hipStream_t vs = nullptr);
+int finish_async_upload(pp_engine* e, int batch);  // voxelises behind a copy-stream upload (where allowed), records ev_up
+int check_batch(pp_engine* e, int batch);
+int graph_bucket(const pp_engine* e, int max_n);
+bool graphs_enabled();
+// ---- pp_api.hip: the resident frames' state, one function per transition ----
+int wait_for_upload(pp_engine* e, hipStream_t s);       // `s` behind an upload / voxeliser queued on the copy stream
+int copies_done(pp_engine* e, hipStream_t up);          // the main stream behind the copies queued on `up` (ev_tgt)
+int flip_input(pp_engine* e);                           // to the other input buffer and voxeliser set; returns its index
+void set_resident(pp_engine* e, int batch, const int* off, int max_n, bool exact);
+int require_host_exact(pp_engine* e, const char* who);  // refuses frames whose sizes only the device knows
+int resident_points(pp_engine* e, int batch, hipStream_t s, bool materialise, const float** src);
+int ensure_spare_pts(pp_engine* e);
+
+int ensure_loss_buffers(pp_engine* e);                  // api_train.hip
+// ---- api_dataprep.hip: what the fused training steps (api_train.hip) queue ----
+int check_gt(pp_engine* e, const char* who, const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts,
+             int batch, const pp_target_config* tc, int64_t* total);
+int check_aug(pp_engine* e, const char* who, int batch, int64_t total, const pp_augment_config* ac,
+              const pp_aug_frame* frames, const double* box_draws);
+int check_gts(pp_engine* e, const char* who, const int32_t* gt_counts, int batch, const pp_gt_sample_config* sc,
+              const pp_gts_cand* cands, const int32_t* cand_counts, int* max_out_n, std::vector<int>* bound_off);
+int enqueue_targets(pp_engine* e, int batch, const GtSet& gt, bool resident_mask, const pp_target_config* tc, bool extra);
+int targets_from_host(pp_engine* e, int batch, const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts,
+                      int64_t total, bool resident_mask, const pp_target_config* tc, bool extra, hipStream_t up);
+int enqueue_augment(pp_engine* e, int batch, const GtSet& in, int64_t total, const pp_augment_config* ac,
+                    const pp_aug_frame* frames, const double* box_draws, hipStream_t up,
+                    const std::vector<int>* draw_off = nullptr);
+int augment_from_host(pp_engine* e, int batch, const float* gt_boxes, const int32_t* gt_classes, const uint8_t* gt_valid,
+                      const int32_t* gt_counts, int64_t total, const pp_augment_config* ac, const pp_aug_frame* frames,
+                      const double* box_draws, hipStream_t up);
+int enqueue_gt_sample(pp_engine* e, int batch, const float* gt_boxes, const int32_t* gt_classes, const uint8_t* gt_valid,
+                      const int32_t* gt_counts, int64_t total, const pp_gt_sample_config* sc, const pp_gts_cand* cands,
+                      const int32_t* cand_counts, int max_out_n, hipStream_t up);

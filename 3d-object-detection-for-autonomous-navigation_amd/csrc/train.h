@@ -1,4 +1,4 @@
-// Training step (train.hip): shapes, the flat parameter layout and the device buffers pp_api.hip hands over.
+// Training step (train.hip): shapes, the flat parameter layout and the device buffers api_train.hip hands over.
 #pragma once
 
 #include <string>
