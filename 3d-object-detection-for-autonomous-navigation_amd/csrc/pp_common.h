@@ -466,3 +466,21 @@ struct IngestParams {
 };
 int ingest_chunks(int n_rec);
 void launch_ingest(const IngestParams& p, hipStream_t s);
+
+// frustum_crop.hip: the resident frames cropped to the camera frustum (frustum.py), frames compacted in order
+struct CropParams {
+    const float* in;           // [sum n_b][F] the resident points (device memory, or a zero-copy feed's page-locked block)
+    const int* offsets_in;     // [batch + 1] their frame offsets
+    const double* planes;      // [batch][6][4] n0 n1 n2 d per face; a point is removed iff ((x n0 + y n1) + z n2) + d >= 0 for one
+    int batch, F, stride;      // stride: crop_chunks(largest frame) (row length of the two chunk tables)
+    int back;                  // column 0 is negated first (tested and stored negated)
+    int* chunk_cnt;            // [batch][stride] kept points per chunk
+    int* chunk_base;           // [batch][stride] kept points of the frame in front of the chunk
+    int* kept;                 // [batch] out: points kept
+    int* offsets_out;          // [batch + 1] out: the frames' row offsets in `out`
+    float* out;                // [sum kept][F]
+    long long out_rows;        // rows `out` holds
+};
+int crop_chunks(int n);
+int crop_max_features();     // widest row (num_point_features) the kernels move
+void launch_frustum_crop(const CropParams& p, hipStream_t s);

@@ -1,6 +1,6 @@
 // Host side of the C-ABI (include/pp_hip.h), shared by its translation units: the handle, the error / allocation
 // helpers and what one unit calls in another.  pp_api.hip: lifetime, weights, feeds, the inference pipeline;
-// api_ingest.hip: PointCloud2 ingest; api_train.hip: loss, training step, optimizer; api_dataprep.hip: targets,
+// api_ingest.hip: PointCloud2 ingest; api_crop.hip: the frustum crop; api_train.hip: loss, training step, optimizer; api_dataprep.hip: targets,
 // augmentation, GT sampling, object database; api_eval.hip: the AP evaluator (needs no handle).
 #pragma once
 
@@ -203,6 +203,14 @@ struct pp_engine {
         int *finite = nullptr, *kept = nullptr;            // [B]
         int batch = 0;                     // frames of the last ingest (pp_ingest_info)
     } ing;
+    struct Crop {                          // frustum crop of the resident frames (pp_frustum_crop*; api_crop.hip: ensure_crop)
+        double* planes = nullptr;          // [B][6][4]
+        double* h_ring = nullptr;          // pinned [OFF_RING][B][6][4]: the planes travel like the offsets, slot by slot
+        int* chunks = nullptr;             // [2][B * crop_chunks(NMAX)]: chunk counts, chunk bases
+        int* kept = nullptr;               // [B]
+        hipEvent_t ev_main = nullptr;      // orders an asynchronous crop (copy stream) behind the main stream
+        int batch = 0;                     // frames of the last crop (pp_frustum_crop_info)
+    } crop;
 
     // training step (train.hip): shapes, plan (the flat layout among it) and device buffers, set up by the first
     // pp_train_* call

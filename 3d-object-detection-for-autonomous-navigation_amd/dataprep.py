@@ -10,8 +10,14 @@ anchors, anchors_mask, image_idx, image_shape).
 import numpy as np
 
 
-def prep_example(engine, points, rect, trv2c, p2, image_idx=0, image_shape=(375, 1242)):
-    """One frame -> reference-shaped example dict (eval mode)."""
+def prep_example(engine, points, rect, trv2c, p2, image_idx=0, image_shape=(375, 1242), remove_outside=False):
+    """One frame -> reference-shaped example dict (eval mode).  remove_outside: the cloud is first cropped to the
+    frustum of the image (p2, image_shape) on the GPU, as the reference's `velodyne_reduced` files are."""
+    if remove_outside:
+        from . import frustum
+        engine.upload([points])
+        points = engine.crop_to_image(frustum.frustum_planes(rect, trv2c, p2, image_shape)[np.newaxis],
+                                      return_points=True)[1][0]
     voxels, coors, num = engine.points_to_voxel(points)
     ex = {
         "voxels": voxels, "num_points": num, "coordinates": coors,

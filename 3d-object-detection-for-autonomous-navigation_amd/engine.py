@@ -420,12 +420,25 @@ class Engine:
         self._check(self._lib.pp_get_detections(self._h, _ptr(dets), _ptr(n)), "pp_get_detections")
         return dets, n
 
-    def detect(self, frames, rect=None, trv2c=None, on_numeric="f32"):
+    def detect(self, frames, rect=None, trv2c=None, on_numeric="f32", p2=None, image_shape=None):
         """upload + detect_async + sync + detections.  on_numeric: what to do when the default arithmetic reports
         activations outside the float16 pieces' range (NumericError) -- "f32": switch this engine to the float32
         matrix instruction (it stays there: `gemm_precision()`), run the still-resident frames again and return those
-        results; "raise": propagate.  A network that overflows float32 itself always raises."""
+        results; "raise": propagate.  A network that overflows float32 itself always raises.
+        p2 ([4, 4] or [B, 4, 4]) and image_shape ((height, width) or [B, 2]), both or neither: the uploaded frames are
+        cropped to the camera frustum on the GPU (crop_to_image) before the pass -- once: the float32 re-run reads the
+        cropped frames; rect and trv2c are then required."""
+        if (p2 is None) != (image_shape is None):
+            raise ValueError("detect: p2 and image_shape go together (both crop the frames to the image, neither does not)")
+        if p2 is not None and (rect is None or trv2c is None):
+            raise ValueError("detect: the frustum crop needs rect and trv2c")
         self.upload(frames, rect, trv2c)
+        if p2 is not None:
+            from . import frustum
+            B = len(frames)
+            r4, t4, p4 = (np.broadcast_to(np.asarray(m, np.float64), (B, 4, 4)) for m in (rect, trv2c, p2))
+            shp = np.broadcast_to(np.asarray(image_shape), (B, 2))
+            self.crop_to_image(np.stack([frustum.frustum_planes(r4[b], t4[b], p4[b], shp[b]) for b in range(B)]))
         return self._detect_resident(on_numeric)
 
     def _detect_resident(self, on_numeric):
@@ -440,6 +453,54 @@ class Engine:
         self.detect_async()
         self.sync()
         return self.detections()
+
+    # ---- frustum crop of the resident frames (pp_frustum_crop*; frustum.py states the rule) ----
+    @staticmethod
+    def _crop_planes(planes):
+        pl = np.ascontiguousarray(planes, np.float64)
+        if pl.ndim != 3 or pl.shape[1:] != (6, 4):
+            raise ValueError(f"planes must be [batch, 6, 4] (frustum.frustum_planes per frame), got {pl.shape}")
+        return pl
+
+    def crop_to_image(self, planes, back=False, return_points=False):
+        """Crops the frames uploaded to this engine to their camera frustums, on the GPU (pp_frustum_crop): what the
+        reference's remove_outside_points does to a KITTI cloud.  planes: [B, 6, 4] float64, frustum.frustum_planes of
+        each frame's calibration; back: negate x first (the `_back` files).  The cropped frames replace the resident
+        ones, as after an upload: detect_async, count_points_in_gt, build_gt_objects, augment ... see them.  Returns the
+        kept counts, int32 [B]; return_points: (counts, [B float32 arrays [kept_b, F]])."""
+        pl = self._crop_planes(planes)
+        B, F = len(pl), self.d.num_point_features
+        kept = np.zeros(max(B, 1), np.int32)
+        resident = getattr(self, "_offsets", None)
+        cap = int(resident[-1]) if return_points and resident is not None else 0
+        pts = np.empty((max(cap, 1), F), np.float32) if return_points else None
+        self._check(self._lib.pp_frustum_crop(self._h, _ptr(pl), B, _lib.PP_CROP_BACK if back else 0, _ptr(kept), _ptr(pts),
+                                              ctypes.c_int64(cap)), "pp_frustum_crop")
+        kept = kept[:B]
+        off = np.zeros(B + 1, np.int32)
+        off[1:] = np.cumsum(kept)
+        self._offsets = off
+        self._crop_batch = B
+        if not return_points:
+            return kept
+        return kept, [pts[off[b]:off[b + 1]].copy() for b in range(B)]
+
+    def crop_to_image_async(self, planes, back=False):
+        """crop_to_image without waiting (pp_frustum_crop_async): on the copy stream behind an upload_async, the voxeliser
+        behind it; the kept counts stay on the device (crop_info reads them back) and the engine is left as after an
+        ingest: detect_async works, the calls that need the frames' sizes on the host are refused until the next upload."""
+        pl = self._crop_planes(planes)
+        self._check(self._lib.pp_frustum_crop_async(self._h, _ptr(pl), len(pl), _lib.PP_CROP_BACK if back else 0),
+                    "pp_frustum_crop_async")
+        self._offsets = None
+        self._crop_batch = len(pl)
+
+    def crop_info(self):
+        """The kept counts of the last crop, int32 [B] (pp_frustum_crop_info; waits for it)."""
+        B = getattr(self, "_crop_batch", 0)
+        kept = np.zeros(max(B, 1), np.int32)
+        self._check(self._lib.pp_frustum_crop_info(self._h, _ptr(kept), B), "pp_frustum_crop_info")
+        return kept[:B]
 
     # ---- live-camera ingest (pp_ingest_pointcloud2*; ingest.py states the rule) ----
     def ingest_pointcloud2(self, msgs, first=1, decimate=4, lift=None, return_points=False):

@@ -19,8 +19,11 @@ which tools/gen_golden_gtdb.py produces by running the reference's own functions
 dataset-level functions below runs that restatement instead -- a choice the caller spells out, for machines without a
 GPU and for the tests' oracle; an Engine never falls back to it.
 
-Not built: the frustum crop (box_np_ops.remove_outside_points).  The reference skips it for the custom dataset
-(custom_dataset = True, the shipped configuration), and so does this module: clouds are taken as they are.
+The frustum crop (box_np_ops.remove_outside_points; frustum.py states the rule, csrc/frustum_crop.hip runs it): the
+reference applies it to KITTI clouds before steps 2-4 and skips it for the custom dataset (custom_dataset = True, the
+shipped configuration).  Here it is `remove_outside=True`, off by default; with an Engine the uploaded batch is cropped
+on the GPU (Engine.crop_to_image) and the count / build runs on the cropped frames.  `create_reduced_point_cloud` writes
+the cropped clouds as _create_reduced_point_cloud (create_data.py:275-323) names them.
 """
 import itertools
 import pathlib
@@ -28,7 +31,7 @@ import pickle
 
 import numpy as np
 
-from . import augment
+from . import augment, frustum
 
 PP_MAX_GT_PER_FRAME = 256
 # kitti_common.get_classes() without DontCare: the default used_classes
@@ -155,11 +158,12 @@ class _Feeder:
 
 
 def _run(engine, frames, want_points):
-    """frames: iterable of (cloud, lidar boxes).  Yields per frame (counts, objects or None), `max_batch` frames per
-    device call, the next batch's upload queued before the current one is unpacked."""
+    """frames: iterable of (cloud, lidar boxes, frustum planes or None).  Yields per frame (counts, objects or None),
+    `max_batch` frames per device call, the next batch's upload queued before the current one is unpacked.  Planes: the
+    frame is cropped to them first (all frames of a run, or none)."""
     if engine is None:
-        for cloud, boxes in frames:
-            counts, objs = build_objects_np(cloud, boxes)
+        for cloud, boxes, planes in frames:
+            counts, objs = build_objects_np(cloud if planes is None else frustum.crop_np(cloud, planes), boxes)
             yield counts, (objs if want_points else None)
         return
     F = engine.d.num_point_features
@@ -167,25 +171,29 @@ def _run(engine, frames, want_points):
     pending = None
     for chunk in itertools.chain(_batches(engine, frames), [None]):
         if chunk is not None:
-            chunk = [(_check_cloud(c, F), _check_boxes(b)) for c, b in chunk]
+            chunk = [(_check_cloud(c, F), _check_boxes(b), pl) for c, b, pl in chunk]
         if pending is not None:
-            boxes = [b for _, b in pending]
+            boxes = [b for _, b, _ in pending]
+            if pending[0][2] is not None:
+                engine.crop_to_image(np.stack([pl for _, _, pl in pending]))
             if want_points:
                 counts, objs = engine.build_gt_objects(boxes, return_counts=True)
             else:
                 counts, objs = engine.count_points_in_gt(boxes), [None] * len(boxes)
             if chunk is not None:
-                feeder.upload([c for c, _ in chunk])
+                feeder.upload([c for c, _, _ in chunk])
             yield from zip(counts, objs)
         elif chunk is not None:
-            feeder.upload([c for c, _ in chunk])
+            feeder.upload([c for c, _, _ in chunk])
         pending = chunk
 
 
-def calculate_num_points_in_gt(engine, infos, clouds):
-    """_calculate_num_points_in_gt (create_data.py:28-93) for the custom dataset: fills info["annos"]["num_points_in_gt"]
-    (int32) of every info -- the points inside each of the first num_obj (names other than DontCare) boxes, -1 for the
-    rest.  clouds: float32 [n, F] arrays parallel to infos.  engine None: on the host (build_objects_np)."""
+def calculate_num_points_in_gt(engine, infos, clouds, remove_outside=False):
+    """_calculate_num_points_in_gt (create_data.py:28-93): fills info["annos"]["num_points_in_gt"] (int32) of every info --
+    the points inside each of the first num_obj (names other than DontCare) boxes, -1 for the rest.  clouds: float32
+    [n, F] arrays parallel to infos.  remove_outside: count after the frustum crop (info["img_shape"], calib/P2; the
+    reference's default for KITTI is True, the custom dataset's and this function's False).  engine None: on the host
+    (build_objects_np, frustum.crop_np)."""
     infos = list(infos)
 
     def frames():
@@ -194,7 +202,8 @@ def calculate_num_points_in_gt(engine, infos, clouds):
             num_obj = len([n for n in annos["name"] if n != "DontCare"])
             cam = np.concatenate([annos["location"][:num_obj], annos["dimensions"][:num_obj],
                                   np.asarray(annos["rotation_y"])[:num_obj][..., np.newaxis]], axis=1)
-            yield _check_cloud(cloud), box_camera_to_lidar(cam, info["calib/R0_rect"], info["calib/Tr_velo_to_cam"])
+            yield (_check_cloud(cloud), box_camera_to_lidar(cam, info["calib/R0_rect"], info["calib/Tr_velo_to_cam"]),
+                   frustum.info_planes(info) if remove_outside else None)
 
     for k, (counts, _) in enumerate(_run(engine, frames(), False)):
         annos = infos[k]["annos"]
@@ -203,14 +212,15 @@ def calculate_num_points_in_gt(engine, infos, clouds):
 
 
 def create_groundtruth_database(engine, infos, clouds, used_classes=None, bev_only=False, coors_range=None,
-                                database_name="gt_database"):
+                                database_name="gt_database", remove_outside=False):
     """create_groundtruth_database (create_data.py:365-551) without the files: returns (all_db_infos, points), the pair
     GtDatabase(infos, points, ...) takes.  all_db_infos[name]: the reference's dicts (name, path, image_idx, gt_idx,
     box3d_lidar, num_points_in_gt, difficulty, group_id, and score when the annotations have one); points[name]: the
     objects' float32 [n, F] arrays, parallel to it.  The group_dict is per frame, the group_counter global; used_classes
     (default: the KITTI classes without DontCare) filters the infos only.  clouds: any iterable of float32 [n, F]
     arrays parallel to infos; frames go through the engine max_batch at a time, the next batch's upload queued while
-    the current one is unpacked.  engine None: on the host (build_objects_np).  No frustum crop (see the module text)."""
+    the current one is unpacked.  engine None: on the host (build_objects_np).  remove_outside: every cloud is cropped
+    to its image's frustum first (info["img_shape"], calib/P2), as the reference does for KITTI; off by default."""
     infos = list(infos)
     if bev_only and coors_range is None:
         raise ValueError("bev_only needs coors_range (z and h are set to its limits)")
@@ -222,7 +232,7 @@ def create_groundtruth_database(engine, infos, clouds, used_classes=None, bev_on
     def frames():
         for info, cloud in _pairs(infos, clouds):
             lidar.append(frame_boxes(info, bev_only, coors_range))
-            yield _check_cloud(cloud), lidar[-1]
+            yield _check_cloud(cloud), lidar[-1], (frustum.info_planes(info) if remove_outside else None)
 
     group_counter = 0
     for k, (counts, objs) in enumerate(_run(engine, frames(), True)):
@@ -249,6 +259,45 @@ def create_groundtruth_database(engine, infos, clouds, used_classes=None, bev_on
             all_db_infos[names[i]].append(db_info)
             points[names[i]].append(objs[i])
     return all_db_infos, points
+
+
+def create_reduced_point_cloud(engine, infos, clouds, save_dir, back=False):
+    """_create_reduced_point_cloud (create_data.py:275-323) with a save path: every cloud cropped to its image's frustum
+    and written with `tofile` (raw float32) as save_dir / <name of info["velodyne_path"]>, `_back` appended when `back`
+    (x negated first).  Frames go through the engine max_batch at a time, the next batch's upload queued while the
+    current one is written.  engine None: on the host (frustum.crop_np).  Returns the kept counts, int32 [len(infos)]."""
+    infos = list(infos)
+    save_dir = pathlib.Path(save_dir)
+    save_dir.mkdir(parents=True, exist_ok=True)
+    F = None if engine is None else engine.d.num_point_features
+
+    def frames():
+        for info, cloud in _pairs(infos, clouds):
+            yield info, _check_cloud(cloud, F), frustum.info_planes(info)
+
+    def cropped():
+        if engine is None:
+            for info, cloud, planes in frames():
+                yield info, frustum.crop_np(cloud, planes, back)
+            return
+        feeder = _Feeder(engine)
+        pending = None
+        for chunk in itertools.chain(_batches(engine, frames()), [None]):
+            if pending is not None:
+                _, pts = engine.crop_to_image(np.stack([pl for _, _, pl in pending]), back=back, return_points=True)
+                if chunk is not None:
+                    feeder.upload([c for _, c, _ in chunk])
+                yield from zip([i for i, _, _ in pending], pts)
+            elif chunk is not None:
+                feeder.upload([c for _, c, _ in chunk])
+            pending = chunk
+
+    kept = []
+    for info, pts in cropped():
+        name = pathlib.Path(info["velodyne_path"]).name + ("_back" if back else "")
+        np.ascontiguousarray(pts, np.float32).tofile(str(save_dir / name))
+        kept.append(len(pts))
+    return np.array(kept, np.int32)
 
 
 def write_reference_files(all_db_infos, points, root, custom_dataset=True, info_name="kitti_dbinfos_train.pkl"):

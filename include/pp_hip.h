@@ -33,7 +33,8 @@ extern "C" {
  * pp_train_step_aug, pp_augment_selected; then pp_train_set_frozen, pp_adamw_step_segments_device; then PP_GTS_MAX_CAND,
  * PP_GTS_MAX_ROUNDS, pp_gt_sample_config, pp_gts_cand, pp_gtdb_load, pp_gt_sample, pp_gt_sample_info,
  * pp_train_step_sample_async, pp_train_step_sample; then pp_pc2_layout, pp_ingest_config, pp_ingest_pointcloud2,
- * pp_ingest_pointcloud2_async, pp_ingest_info; then pp_gtdb_build, pp_gtdb_count. */
+ * pp_ingest_pointcloud2_async, pp_ingest_info; then pp_gtdb_build, pp_gtdb_count; then PP_CROP_BACK, pp_frustum_crop,
+ * pp_frustum_crop_async, pp_frustum_crop_info. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -624,6 +625,40 @@ int pp_ingest_pointcloud2_async(pp_handle h, const uint8_t* data_pinned, const i
 /* Parity tap of the last ingest (waits for it): per frame the finite records and the points kept.  Either pointer may be
  * NULL.  PP_ERR_STATE when none has run, PP_ERR_ARG when `batch` is not that call's. */
 int pp_ingest_info(pp_handle h, int32_t* finite_counts, int32_t* kept_counts, int32_t batch);
+
+/* ---- frustum crop (box_np_ops.remove_outside_points) ----------------------------------------------------- */
+/* Crops the RESIDENT frames to the camera image's frustum on the GPU: what _create_reduced_point_cloud,
+ * _calculate_num_points_in_gt(remove_outside=True) and create_groundtruth_database do to a KITTI cloud first.  planes
+ * [batch][6][4] float64: per frame the six faces (n0, n1, n2, d) exactly as surface_equ_3d_jit returns them for the
+ * frustum's lidar corners -- the caller's (<package>/frustum.py frustum_planes: a LAPACK inverse and a QR stand behind
+ * them); the normals are not unit length and are used as they are.  Per point, s_k = ((x n0 + y n1) + z n2) + d in
+ * float64 on the widened float32 coordinates, summed left to right, products and sums rounded separately; the point is
+ * removed iff s_k >= 0 for some face, so a point with a NaN coordinate is kept and +-inf follows IEEE arithmetic.  Kept
+ * points keep the frame's order and all F columns, bit for bit.  flags: PP_CROP_BACK negates column 0 first (exact); the
+ * test is made on the negated value and the negated value is stored (the reference's `_back` files).  The same frames
+ * give the same bytes on every run.
+ * The frames are read where they lie (a zero-copy feed in the caller's page-locked memory) and written back to back into
+ * the handle's other input buffer, which becomes the resident one, as after an upload.  Refused before anything is
+ * queued, the handle staying usable: PP_ERR_ARG for a non-finite plane value (pp_last_error names the frame), a batch
+ * other than the resident one or unknown flag bits; PP_ERR_STATE with no frames resident, when the resident frames' sizes
+ * are device values (after an ingest, a sampled training step or pp_frustum_crop_async: crops do not chain) or while a
+ * training step is in flight. */
+#define PP_CROP_BACK 1
+/* Synchronous: waits, writes kept_out [batch] and takes the kept counts as the frames' sizes -- pp_gtdb_build,
+ * pp_gtdb_count, pp_augment, pp_detect_async, the stage taps and the training steps then see the cropped frames like any
+ * upload.  points_out (may be NULL): receives the resident points [sum kept][F], frames back to back -- the parity tap;
+ * points_capacity is in points, PP_ERR_ARG when it is below the kept total (kept_out is written and the frames stay
+ * resident and cropped). */
+int pp_frustum_crop(pp_handle h, const double* planes, int32_t batch, int32_t flags, int32_t* kept_out, float* points_out,
+                    int64_t points_capacity);
+/* Same without waiting, on the handle's copy stream behind the frames' upload, the voxeliser behind it there; planes is
+ * copied before the call returns; the ordering rules are pp_upload_points_async's.  The kept counts stay on the device
+ * (pp_frustum_crop_info reads them back): the handle is left as after an ingest, everything behind the call sized from
+ * the frames' sizes before the crop, and the calls an ingest bars are barred the same way until the next upload. */
+int pp_frustum_crop_async(pp_handle h, const double* planes, int32_t batch, int32_t flags);
+/* The kept counts of the last crop (waits for it).  PP_ERR_STATE when none has run, PP_ERR_ARG when `batch` is not that
+ * call's. */
+int pp_frustum_crop_info(pp_handle h, int32_t* kept_out, int32_t batch);
 
 /* The handle's HIP stream (hipStream_t as void*).  A caller that enqueues its own device work behind a pp_train_step_async
  * -- the gradient all-reduce and pp_adamw_step_device of the optimizer step (train.py:301) -- does it on this stream and
