@@ -197,6 +197,9 @@ class Derived:
         self.nms_post_max_size = int(s["nms_post_max_size"])
         self.nms_score_threshold = float(s["nms_score_threshold"])
         self.nms_iou_threshold = float(s["nms_iou_threshold"])
+        # not a key of the reference's YAML (absent = False): suppress on the rotated IoU of the decoded boxes
+        # (rotate_nms_gpu, which the reference ships but never wires in) instead of predict()'s stand-up boxes
+        self.use_rotate_nms = bool(s.get("use_rotate_nms", False))
         er = config["eval_input_reader"]
         self.batch_size = int(er["batch_size"])
         self.anchor_area_threshold = er["anchor_area_threshold"]
@@ -214,4 +217,5 @@ class Derived:
     def nms_dict(self):
         return {"nms_score_threshold": self.nms_score_threshold, "nms_pre_max_size": self.nms_pre_max_size,
                 "nms_post_max_size": self.nms_post_max_size, "nms_iou_threshold": self.nms_iou_threshold,
-                "num_class": self.num_class, "use_direction_classifier": self.use_direction_classifier}
+                "num_class": self.num_class, "use_direction_classifier": self.use_direction_classifier,
+                "use_rotate_nms": self.use_rotate_nms}

@@ -1,0 +1,74 @@
+// C-ABI, non-maximum suppression: the detector's rule (per handle; the kernel instantiations are in postprocess.hip) and
+// the standalone rotated NMS (kernels: rotate_nms.hip).  The latter needs no handle: host buffers in, host buffers out,
+// device memory for the call's duration.
+#include "pp_engine.h"
+
+namespace {
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+};
+}  // namespace
+
+extern "C" {
+
+int pp_set_nms_mode(pp_handle e, int32_t mode) {
+    if (!e) return PP_ERR_ARG;
+    if (mode != PP_NMS_STANDUP && mode != PP_NMS_ROTATED) return fail(e, PP_ERR_ARG, "pp_set_nms_mode: unknown mode %d", mode);
+    if (mode == e->nms_mode) return PP_OK;
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_set_nms_mode: a training step is in flight");
+    e->nms_mode = mode;      // read by the next run_post; a captured pass is keyed on it (pp_detect_async)
+    return PP_OK;
+}
+
+int pp_get_nms_mode(pp_handle e, int32_t* mode) {
+    if (!e || !mode) return PP_ERR_ARG;
+    *mode = e->nms_mode;
+    return PP_OK;
+}
+
+int pp_rotate_nms(int device, const float* dets, int64_t n, float iou_threshold, int32_t pre_max_size,
+                  int32_t post_max_size, int32_t* keep, int64_t* n_keep) {
+    const char* who = "pp_rotate_nms";
+    if (n < 0 || (n > 0 && !dets) || !n_keep) return fail(nullptr, PP_ERR_ARG, "%s: bad argument", who);
+    *n_keep = 0;
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(dets[6 * i + 5])) return fail(nullptr, PP_ERR_ARG, "%s: score of box %lld is not finite", who, (long long)i);
+    const int64_t m = (pre_max_size > 0 && pre_max_size < n) ? (int64_t)pre_max_size : n;
+    if (m > PP_RNMS_MAX_BOXES)
+        return fail(nullptr, PP_ERR_ARG, "%s: %lld boxes enter the suppression; at most PP_RNMS_MAX_BOXES = %d (set pre_max_size)",
+                    who, (long long)m, PP_RNMS_MAX_BOXES);
+    if (n > (int64_t)1 << 24) return fail(nullptr, PP_ERR_ARG, "%s: at most %d boxes per call (got %lld)", who, 1 << 24, (long long)n);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, PP_ERR_HIP, "%s: no HIP device available (this library has no CPU fallback)", who);
+    if (device < 0 || device >= ndev) return fail(nullptr, PP_ERR_ARG, "%s: device %d not in [0,%d)", who, device, ndev);
+    if (m == 0) return PP_OK;
+    if (!keep) return fail(nullptr, PP_ERR_ARG, "%s: keep is null", who);
+#define NCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(nullptr, PP_ERR_HIP, "%s: %s", who, hipGetErrorString(e_)); } while (0)
+    NCHK(hipSetDevice(device));
+    const size_t cb = (size_t)((m + 63) / 64);
+    DevBuf d_dets, d_order, d_sorted, d_corners, d_mask, d_keep, d_nk;
+    NCHK(d_dets.alloc(sizeof(float) * 6 * (size_t)n));
+    NCHK(d_order.alloc(sizeof(int) * (size_t)m));
+    NCHK(d_sorted.alloc(sizeof(float) * 5 * (size_t)m));
+    NCHK(d_corners.alloc(sizeof(float) * 9 * (size_t)m));
+    NCHK(d_mask.alloc(sizeof(unsigned long long) * (size_t)m * cb));
+    NCHK(d_keep.alloc(sizeof(int) * (size_t)m));
+    NCHK(d_nk.alloc(sizeof(long long)));
+    NCHK(hipMemcpy(d_dets.p, dets, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice));
+    const int post = (post_max_size > 0 && post_max_size < m) ? post_max_size : (int)m;
+    launch_rnms((const float*)d_dets.p, (int)n, (int)m, iou_threshold, post, (int*)d_order.p, (float*)d_sorted.p,
+                (float*)d_corners.p, (unsigned long long*)d_mask.p, (int*)d_keep.p, (long long*)d_nk.p, nullptr);
+    NCHK(hipGetLastError());
+    long long nk = 0;
+    NCHK(hipMemcpy(&nk, d_nk.p, sizeof(nk), hipMemcpyDeviceToHost));
+    if (nk < 0 || nk > m) return fail(nullptr, PP_ERR_HIP, "%s: the sweep returned %lld of %lld boxes", who, nk, (long long)m);
+    if (nk > 0) NCHK(hipMemcpy(keep, d_keep.p, sizeof(int) * (size_t)nk, hipMemcpyDeviceToHost));
+#undef NCHK
+    *n_keep = nk;
+    return PP_OK;
+}
+
+}  // extern "C"

@@ -19,9 +19,16 @@
 // implementation-defined.  NMS IoU follows iou_device exactly: AABB with `+1`
 // on widths (pixel convention applied to metres), differences in float32, the
 // rest in float64, strict `>` threshold.
+//
+// NMS rule (template parameter, pp_set_nms_mode): PP_NMS_STANDUP is the above.  PP_NMS_ROTATED replaces only the
+// mask computation by rotate_nms_kernel's (second/core/non_max_suppression/nms_gpu.py:419-452, which the reference
+// ships but never wires in): devRotateIoU of the decoded [x, y, w, l, r] before the direction flip (boxes_for_nms,
+// model/voxelnet.py:1233), the higher-scoring box as first argument, float32, strict `>`.  The <= 100 * 99 / 2 pairs
+// are spread over the workgroup; the clip's polygon scratch ([8][1024] x 3 floats, riou_dev.h) lies on s_ckey, whose
+// candidate keys are dead once the top set is in s_key -- the footprint grows by the corner table only.
 #include <type_traits>
 
-#include "pp_common.h"
+#include "riou_dev.h"
 
 #define PT 1024
 #define KMAX 128   // >= the reference's hard-coded top-100
@@ -33,6 +40,7 @@ __device__ __forceinline__ unsigned long long comp_key(float logit, unsigned a) 
     return ((unsigned long long)u << 32) | (unsigned long long)(~a);
 }
 
+template <int NMS>
 __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
     __shared__ int s_hist[256];
     __shared__ int s_cum[256];
@@ -53,6 +61,12 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
     __shared__ int s_keep[KMAX];
     __shared__ int s_nkeep;
     __shared__ int s_bad;      // a non-finite class logit anywhere in the frame, or a non-finite value in a selected row
+
+    float (*s_rc)[9] = nullptr;     // rotated rule only: corners + area of the decoded boxes (riou_box_corners)
+    if constexpr (NMS == PP_NMS_ROTATED) {
+        __shared__ float s_corners[KMAX][9];
+        s_rc = s_corners;
+    }
 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const long long A = p.A;
@@ -348,6 +362,7 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
             else { x0 = fminf(x0, rx); x1 = fmaxf(x1, rx); y0 = fminf(y0, ry); y1 = fmaxf(y1, ry); }
         }
         s_aabb[tid][0] = x0; s_aabb[tid][1] = y0; s_aabb[tid][2] = x1; s_aabb[tid][3] = y1;
+        if constexpr (NMS == PP_NMS_ROTATED) riou_box_corners(xg, yg, wg, lg, rg, s_rc[tid]);
     }
     __syncthreads();
 
@@ -357,7 +372,22 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
     const int n = min(K, p.pre_max);
     if (tid < 2 * KMAX) reinterpret_cast<unsigned long long*>(s_mask)[tid] = 0ull;
     __syncthreads();
-    {
+    if constexpr (NMS == PP_NMS_ROTATED) {
+        // all (i, j) of the n x n square, 64 consecutive j of one row per wavefront; j <= i has nothing to do
+        static_assert(sizeof(s_ckey) >= 3 * RIOU_MAXP * PT * sizeof(float), "the polygon scratch lies on the candidate keys");
+        float* s_px = reinterpret_cast<float*>(s_ckey);
+        float* s_py = s_px + RIOU_MAXP * PT;
+        float* s_vs = s_py + RIOU_MAXP * PT;
+        for (int q = tid; q < n * n; q += PT) {
+            const int i = q / n, j = q - i * n;
+            if (j <= i) continue;
+            float c1[8], c2[8];      // c1: the earlier, higher-scoring box (first argument of devRotateIoU)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { c1[k] = s_rc[i][k]; c2[k] = s_rc[j][k]; }
+            const float iou = riou_iou<PT>(c1, s_rc[i][8], c2, s_rc[j][8], s_px, s_py, s_vs, tid);
+            if (iou > p.iou_thr) atomicOr(&s_mask[i][j >> 6], 1ull << (j & 63));
+        }
+    } else {
         const int row = tid >> 3, sub = tid & 7;
         if (row < n) {
             unsigned long long m0 = 0ull, m1 = 0ull;
@@ -459,5 +489,6 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
 
 void launch_postprocess(const PostParams& p, hipStream_t s) {
     if (p.batch <= 0) return;
-    PP_LAUNCH("k_postprocess", k_postprocess, dim3(p.batch), dim3(PT), 0, s, p);
+    if (p.nms_mode == PP_NMS_ROTATED) PP_LAUNCH("k_postprocess", k_postprocess<PP_NMS_ROTATED>, dim3(p.batch), dim3(PT), 0, s, p);
+    else PP_LAUNCH("k_postprocess", k_postprocess<PP_NMS_STANDUP>, dim3(p.batch), dim3(PT), 0, s, p);
 }

@@ -347,6 +347,7 @@ static int run_post(pp_engine* e, int batch, bool to_host = false) {
     p.head = e->d_head; p.cls = e->cls_plane_live ? e->d_cls : nullptr; p.napl = e->napl; p.ncls = e->ncls; p.use_dir = e->use_dir ? 1 : 0; p.mask = e->d_mask; p.anchors = e->d_anchors;
     p.calib = e->d_calib; p.dets = e->d_dets; p.n_dets = e->d_ndets;
     p.dets_host = to_host ? e->h_dets : nullptr; p.n_dets_host = to_host ? e->h_ndets : nullptr;
+    p.nms_mode = e->nms_mode;
     ProfScope ps(e, "k_postprocess");
     launch_postprocess(p, e->stream);
     HIPCHK(e, hipGetLastError());
@@ -1155,7 +1156,7 @@ int pp_detect_async(pp_handle e) {
         pp_engine::GraphSlot* lru = &e->graphs[0];
         for (auto& g : e->graphs) {
             if (g.exec && g.batch == B && g.bucket == bucket && g.buf == e->in_buf && g.zc == (e->zc ? 1 : 0) &&
-                g.vox == (e->vox_ahead ? 1 : 0)) slot = &g;
+                g.vox == (e->vox_ahead ? 1 : 0) && g.nms == e->nms_mode) slot = &g;
             if (g.used < lru->used) lru = &g;
         }
         if (slot == nullptr) {
@@ -1176,6 +1177,7 @@ int pp_detect_async(pp_handle e) {
                 slot->buf = e->in_buf;
                 slot->zc = e->zc ? 1 : 0;
                 slot->vox = e->vox_ahead ? 1 : 0;
+                slot->nms = e->nms_mode;
             } else {
                 slot->exec = nullptr;
                 e->graph_state = -1;           // fall back to plain launches for the life of the handle

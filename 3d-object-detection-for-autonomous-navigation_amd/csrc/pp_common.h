@@ -264,6 +264,7 @@ struct PostParams {
     // bytes -- stored straight over the host link they replace two copy nodes (9 us of a replayed step)
     pp_detection* dets_host;
     int* n_dets_host;
+    int nms_mode;          // enum pp_nms_mode: which instantiation of the kernel runs
 };
 void launch_postprocess(const PostParams& p, hipStream_t s);
 
@@ -302,6 +303,11 @@ void launch_riou_corners(const float* boxes, int64_t n, float* corners, hipStrea
 void launch_riou_pairs(const float* bc, int64_t N, const float* qc, int64_t K, int criterion, float* out, hipStream_t s);
 void launch_d3_finish(const double* boxes, int64_t N, const double* qboxes, int64_t K, int criterion,
                       const float* rinc, double* out, hipStream_t s);
+
+// rotate_nms.hip: rotated-box NMS of n boxes dets [n][6] (x, y, x size, y size, angle, score), the m best by score:
+// order [m], sorted [m][5], corners [m][9], mask [m][ceil(m / 64)] are scratch; keep [m] and *n_keep the result
+void launch_rnms(const float* dets, int n, int m, float thr, int post_max, int* order, float* sorted, float* corners,
+                 unsigned long long* mask, int* keep, long long* n_keep, hipStream_t s);
 
 // eval_stats.hip: the AP evaluator's greedy matching and tp / fp / fn / similarity statistics (kitti_eval.py)
 struct EvalStatsParams {

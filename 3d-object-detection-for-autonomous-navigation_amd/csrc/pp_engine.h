@@ -1,7 +1,7 @@
 // Host side of the C-ABI (include/pp_hip.h), shared by its translation units: the handle, the error / allocation
 // helpers and what one unit calls in another.  pp_api.hip: lifetime, weights, feeds, the inference pipeline;
 // api_ingest.hip: PointCloud2 ingest; api_crop.hip: the frustum crop; api_train.hip: loss, training step, optimizer; api_dataprep.hip: targets,
-// augmentation, GT sampling, object database; api_eval.hip: the AP evaluator (needs no handle).
+// augmentation, GT sampling, object database; api_eval.hip: the AP evaluator (needs no handle); api_nms.hip: the detector's NMS rule and the standalone rotated NMS.
 #pragma once
 
 #include <cmath>
@@ -240,11 +240,12 @@ struct pp_engine {
     bool mask_in_pfn = false;      // the last run_pfn also computed the anchor mask (few frames)
     int f32_fallback_layers = 0;   // layers whose folded weights do not fit float16 pieces (pp_finalize_weights)
     bool force_f32 = false;        // pp_set_gemm_precision(PP_PREC_F32): no layer gets split weights
+    int nms_mode = PP_NMS_STANDUP; // pp_set_nms_mode: the post-process instantiation of the next pass (part of a graph's key)
 
     int prof = 0;
     // pp_detect_async as one hipGraph launch (captured on first use per (batch, max points per frame))
-    struct GraphSlot { hipGraphExec_t exec = nullptr; int batch = -1, bucket = -1, buf = -1, zc = 0, vox = 0; unsigned long long used = 0; };
-    GraphSlot graphs[8];          // small LRU keyed by (batch, point-count bucket, input buffer)
+    struct GraphSlot { hipGraphExec_t exec = nullptr; int batch = -1, bucket = -1, buf = -1, zc = 0, vox = 0, nms = 0; unsigned long long used = 0; };
+    GraphSlot graphs[8];          // small LRU keyed by (batch, point-count bucket, input buffer, NMS rule)
     unsigned long long graph_tick = 0;
     int graph_state = 0;          // 0: try, -1: capture failed once (use plain launches)
     std::vector<hipEvent_t> events;

@@ -19,6 +19,7 @@ _STATUS = {1: "PP_ERR_ARG", 2: "PP_ERR_STATE", 3: "PP_ERR_HIP", 4: "PP_ERR_SHAPE
            6: "PP_ERR_NUMERIC"}
 PP_ERR_NUMERIC = 6
 _PRECISIONS = {"split_f16": 0, "f32": 1}
+_NMS_MODES = {"standup": _lib.PP_NMS_STANDUP, "rotated": _lib.PP_NMS_ROTATED}
 
 
 class NumericError(RuntimeError):
@@ -212,6 +213,8 @@ class Engine:
         self._check(self._lib.pp_set_anchors(self._h, _ptr(self.anchors), _ptr(self.anchor_cells),
                                              ctypes.c_int64(self.anchors.shape[0])), "pp_set_anchors")
         self.weights_loaded = False
+        if d.use_rotate_nms:
+            self.set_nms_mode("rotated")
         if weights is not None:
             self.load_weights(weights)
 
@@ -233,6 +236,21 @@ class Engine:
         if precision not in _PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}")
         self._check(self._lib.pp_set_gemm_precision(self._h, _PRECISIONS[precision]), "pp_set_gemm_precision")
+
+    # ---- suppression rule of the post-process (pp_set_nms_mode) ----
+    def set_nms_mode(self, mode):
+        """'standup' (default: the reference's predict() rule, stand-up boxes with `+1` on metre widths) or 'rotated'
+        (rotate_nms_gpu's rule: rotated IoU of the decoded boxes).  Takes effect from the next predict / detect; the
+        config key model.second.use_rotate_nms selects 'rotated' at construction."""
+        if mode not in _NMS_MODES:
+            raise ValueError(f"mode must be one of {sorted(_NMS_MODES)}")
+        self._check(self._lib.pp_set_nms_mode(self._h, _NMS_MODES[mode]), "pp_set_nms_mode")
+
+    @property
+    def nms_mode(self):
+        v = ctypes.c_int32(0)
+        self._check(self._lib.pp_get_nms_mode(self._h, ctypes.byref(v)), "pp_get_nms_mode")
+        return {v_: k for k, v_ in _NMS_MODES.items()}[v.value]
 
     def set_cache_budget(self, megabytes):
         """Last-level-cache budget of a pass in MiB (pp_set_cache_budget; default 256, 0 = off): layers whose maps exceed

@@ -34,7 +34,8 @@ extern "C" {
  * PP_GTS_MAX_ROUNDS, pp_gt_sample_config, pp_gts_cand, pp_gtdb_load, pp_gt_sample, pp_gt_sample_info,
  * pp_train_step_sample_async, pp_train_step_sample; then pp_pc2_layout, pp_ingest_config, pp_ingest_pointcloud2,
  * pp_ingest_pointcloud2_async, pp_ingest_info; then pp_gtdb_build, pp_gtdb_count; then PP_CROP_BACK, pp_frustum_crop,
- * pp_frustum_crop_async, pp_frustum_crop_info. */
+ * pp_frustum_crop_async, pp_frustum_crop_info; then pp_nms_mode, pp_set_nms_mode, pp_get_nms_mode, PP_RNMS_MAX_BOXES,
+ * pp_rotate_nms. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -54,6 +55,15 @@ enum pp_gemm_precision {
                             * fails runs in PP_PREC_F32 by itself) and |activation| < 65504 (checked on the device:
                             * a frame whose activations leave the range ends in PP_ERR_NUMERIC) */
     PP_PREC_F32 = 1        /* every layer on the float32 matrix instruction (v_mfma_f32_32x32x2_f32): float32's range */
+};
+
+/* Suppression rule of the detector's post-process (pp_set_nms_mode) */
+enum pp_nms_mode {
+    PP_NMS_STANDUP = 0, /* default, the reference's predict(): the stand-up axis-aligned box of every decoded box, `+1` on
+                         * widths measured in metres (iou_device) -- boxes within about 0.6 m of each other count as
+                         * IoU > 0.5 */
+    PP_NMS_ROTATED = 1  /* rotate_nms_kernel's rule (second/core/non_max_suppression/nms_gpu.py:419-452, shipped by the
+                         * reference but never wired in): devRotateIoU of the decoded [x, y, w, l, r] */
 };
 
 typedef struct pp_engine* pp_handle;
@@ -222,6 +232,13 @@ int pp_get_detections(pp_handle h, pp_detection* dets, int32_t* n_dets);
  * environment (PP_GEMM_PREC=f32) or is PP_PREC_SPLIT_F16. */
 int pp_set_gemm_precision(pp_handle h, int32_t precision);
 int pp_get_gemm_precision(pp_handle h, int32_t* precision);
+/* Selects the suppression rule (enum pp_nms_mode) of this handle's post-process: pp_predict and the fused path.  Takes
+ * effect from the next pp_detect* / pp_predict; everything else of the post-process (candidates, top-100, decode, caps,
+ * flip, camera transform, PP_ERR_NUMERIC) is the same in both modes, and with the default every output is what it was
+ * before the mode existed.  PP_ERR_ARG for an unknown mode, PP_ERR_STATE while a training step is in flight (the rule
+ * then stays as it was).  The rule is part of what a captured pass is keyed on: a change captures once more. */
+int pp_set_nms_mode(pp_handle h, int32_t mode);
+int pp_get_nms_mode(pp_handle h, int32_t* mode);
 /* Last-level-cache budget of a pass, in MiB (default 256, 0 = off).  Layers whose input + output maps exceed it are run
  * over sub-ranges of the batch's frames, a block's consecutive separable layers sub-range by sub-range, so that a layer
  * reads what the layer before has just written while it still sits in the 256 MB cache (KITTI-shaped B = 32: -5 % per
@@ -278,6 +295,24 @@ int pp_rotate_iou_eval(int device, const float* boxes, int64_t n, const float* q
  * (float32, as above with criterion 2) x height overlap / {union | box volume | query volume | 1}. */
 int pp_d3_box_overlap(int device, const double* boxes, int64_t n, const double* query_boxes, int64_t k,
                       int32_t criterion, double* out);
+
+/* ---- rotated-box NMS ------------------------- */
+
+#define PP_RNMS_MAX_BOXES 16384 /* most boxes that enter the suppression (after pre_max_size): the 64 x 64-bit mask takes
+                                 * n * ceil(n / 64) * 8 bytes of device memory, 32 MB here */
+
+/* Replaces rotate_nms_gpu (second/core/non_max_suppression/nms_gpu.py:455-490; kernel :419-452, device functions
+ * :180-415, host sweep :111-128) with the caps of nms() around it (libraries/eval_helper_functions.py:463-492).
+ * dets [n,6] float32 rows (centre x, centre y, x size, y size, angle, score).  pre_max_size <= 0: every box goes in,
+ * otherwise the min(n, pre_max_size) best by score; boxes are walked by descending score (equal scores: lower index
+ * first), a box is dropped when devRotateIoU(an earlier kept box, it) > iou_threshold (float32, strict: a NaN IoU --
+ * two zero-area boxes -- suppresses nothing); at most post_max_size are kept (<= 0: no cap).  keep: room for
+ * min(n, pre_max_size) (n without a cap) int32 indices into dets, written in walk order; *n_keep their number.  n = 0 is
+ * PP_OK with *n_keep = 0.  PP_ERR_ARG for a non-finite score (checked on the host, nothing launched) or more than
+ * PP_RNMS_MAX_BOXES boxes entering.  Stateless; host pointers; `device` is the HIP device.  The same input gives the same
+ * bytes on every run. */
+int pp_rotate_nms(int device, const float* dets, int64_t n, float iou_threshold, int32_t pre_max_size,
+                  int32_t post_max_size, int32_t* keep, int64_t* n_keep);
 
 /* ---- AP-evaluator statistics ----------------- */
 
