@@ -11,6 +11,8 @@ import pickle
 
 import numpy as np
 
+from .projection import clip_bbox_to_image
+
 _ANNO_KEYS = ("bbox", "name", "truncated", "occluded", "alpha", "dimensions", "location", "rotation_y", "score")
 
 
@@ -24,11 +26,14 @@ def empty_result_anno():
 
 
 def predict_kitti_to_anno(example, class_names, predictions_dicts, center_limit_range=None, lidar_input=False,
-                          global_set=None):
+                          global_set=None, clip_to_image=False):
     """One anno dict per frame; coordinates in camera space (KITTI style).  `example[9]` (image
-    shapes) is read like the reference does but not used by this branch."""
+    shapes) is read like the reference does but not used by this branch -- unless clip_to_image: then a detection
+    whose bbox lies wholly outside the frame's image (height, width) = example[9][i] is dropped and the others' bbox
+    is clipped to it (projection.clip_bbox_to_image: upstream SECOND's rule, which the reference deleted together
+    with the projection -- for projected boxes, model.second.project_bbox)."""
     annos = []
-    for preds in predictions_dicts:
+    for i, preds in enumerate(predictions_dicts):
         batch_idx = preds["batch_idx"]
         anno = None
         if preds["box3d_camera"] is not None:
@@ -36,6 +41,11 @@ def predict_kitti_to_anno(example, class_names, predictions_dicts, center_limit_
             limit = None if center_limit_range is None else np.array(center_limit_range)
             for box_2d, box, box_lidar, score, label in zip(preds["bbox"], preds["box3d_camera"], preds["box3d_lidar"],
                                                              preds["scores"], preds["label_preds"]):
+                if clip_to_image:
+                    box_2d, inside = clip_bbox_to_image(box_2d, np.asarray(example[9])[i])
+                    if not inside[0]:
+                        continue
+                    box_2d = box_2d[0]
                 if limit is not None and (np.any(box_lidar[:3] < limit[:3]) or np.any(box_lidar[:3] > limit[3:])):
                     continue
                 rows["name"].append(class_names[int(label)])

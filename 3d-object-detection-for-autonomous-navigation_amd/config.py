@@ -200,6 +200,9 @@ class Derived:
         # not a key of the reference's YAML (absent = False): suppress on the rotated IoU of the decoded boxes
         # (rotate_nms_gpu, which the reference ships but never wires in) instead of predict()'s stand-up boxes
         self.use_rotate_nms = bool(s.get("use_rotate_nms", False))
+        # not a key of the reference's YAML either (absent = False): "bbox" of a prediction is the projection of its camera
+        # box by the frame's P2 (box3d_to_bbox, which the reference's predict() commented out) instead of the placeholder
+        self.project_bbox = bool(s.get("project_bbox", False))
         er = config["eval_input_reader"]
         self.batch_size = int(er["batch_size"])
         self.anchor_area_threshold = er["anchor_area_threshold"]
@@ -218,4 +221,4 @@ class Derived:
         return {"nms_score_threshold": self.nms_score_threshold, "nms_pre_max_size": self.nms_pre_max_size,
                 "nms_post_max_size": self.nms_post_max_size, "nms_iou_threshold": self.nms_iou_threshold,
                 "num_class": self.num_class, "use_direction_classifier": self.use_direction_classifier,
-                "use_rotate_nms": self.use_rotate_nms}
+                "use_rotate_nms": self.use_rotate_nms, "project_bbox": self.project_bbox}

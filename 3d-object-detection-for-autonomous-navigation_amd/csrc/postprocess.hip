@@ -26,8 +26,14 @@
 // model/voxelnet.py:1233), the higher-scoring box as first argument, float32, strict `>`.  The <= 100 * 99 / 2 pairs
 // are spread over the workgroup; the clip's polygon scratch ([8][1024] x 3 floats, riou_dev.h) lies on s_ckey, whose
 // candidate keys are dead once the top set is in s_key -- the footprint grows by the corner table only.
+//
+// Image boxes (template parameter, pp_set_projection): the lane that assembles a kept detection's box3d_camera also
+// projects it (box3d_to_bbox of second/core/box_np_ops.py:849-857, box_project_dev.h) with the frame's P2 and stores the
+// four doubles beside the detections.  The reference's predict() has this commented out and returns a constant
+// (model/voxelnet.py:1336-1360); off (the default) is the instantiation without a trace of it.
 #include <type_traits>
 
+#include "box_project_dev.h"
 #include "riou_dev.h"
 
 #define PT 1024
@@ -40,7 +46,7 @@ __device__ __forceinline__ unsigned long long comp_key(float logit, unsigned a) 
     return ((unsigned long long)u << 32) | (unsigned long long)(~a);
 }
 
-template <int NMS>
+template <int NMS, bool PROJ>
 __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
     __shared__ int s_hist[256];
     __shared__ int s_cum[256];
@@ -484,11 +490,28 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
         d.reserved = 0;
         p.dets[(size_t)b * p.post_max + tid] = d;
         if (p.dets_host != nullptr) p.dets_host[(size_t)b * p.post_max + tid] = d;
+        if constexpr (PROJ) {
+            const double* M2 = p.p2 + (size_t)b * 16;
+            double P[9], bb[4];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) { P[3 * q] = M2[4 * q]; P[3 * q + 1] = M2[4 * q + 1]; P[3 * q + 2] = M2[4 * q + 2]; }
+            box3d_to_bbox_dev(d.box3d_camera, P, bb);
+            double* o = p.bbox + ((size_t)b * p.post_max + tid) * 4;
+            double* oh = (p.bbox_host != nullptr) ? p.bbox_host + ((size_t)b * p.post_max + tid) * 4 : nullptr;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { o[q] = bb[q]; if (oh != nullptr) oh[q] = bb[q]; }
+        }
     }
 }
 
 void launch_postprocess(const PostParams& p, hipStream_t s) {
     if (p.batch <= 0) return;
-    if (p.nms_mode == PP_NMS_ROTATED) PP_LAUNCH("k_postprocess", k_postprocess<PP_NMS_ROTATED>, dim3(p.batch), dim3(PT), 0, s, p);
-    else PP_LAUNCH("k_postprocess", k_postprocess<PP_NMS_STANDUP>, dim3(p.batch), dim3(PT), 0, s, p);
+    const bool proj = p.p2 != nullptr;
+    if (p.nms_mode == PP_NMS_ROTATED) {
+        if (proj) PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_ROTATED, true>), dim3(p.batch), dim3(PT), 0, s, p);
+        else PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_ROTATED, false>), dim3(p.batch), dim3(PT), 0, s, p);
+    } else {
+        if (proj) PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_STANDUP, true>), dim3(p.batch), dim3(PT), 0, s, p);
+        else PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_STANDUP, false>), dim3(p.batch), dim3(PT), 0, s, p);
+    }
 }

@@ -348,6 +348,11 @@ static int run_post(pp_engine* e, int batch, bool to_host = false) {
     p.calib = e->d_calib; p.dets = e->d_dets; p.n_dets = e->d_ndets;
     p.dets_host = to_host ? e->h_dets : nullptr; p.n_dets_host = to_host ? e->h_ndets : nullptr;
     p.nms_mode = e->nms_mode;
+    const bool proj = e->proj.on;
+    if (proj && batch > e->proj.batch)
+        return fail(e, PP_ERR_STATE, "pp_set_projection gave matrices for %d frames; this pass has %d", e->proj.batch, batch);
+    p.p2 = proj ? e->proj.d_p2 : nullptr; p.bbox = proj ? e->proj.d_bbox : nullptr;
+    p.bbox_host = (proj && to_host) ? e->proj.h_bbox : nullptr;
     ProfScope ps(e, "k_postprocess");
     launch_postprocess(p, e->stream);
     HIPCHK(e, hipGetLastError());
@@ -362,6 +367,7 @@ static void stage_call_done(pp_engine* e) {
     e->cur_max_n = 0;
     e->cur_total = 0;
     e->results_batch = 0;
+    e->proj.results = 0;
 }
 
 int check_batch(pp_engine* e, int batch) {
@@ -784,7 +790,7 @@ int pp_destroy(pp_handle e) {
     }
     delete e->train;
     for (void* p : {(void*)e->h_off_ring, (void*)e->ing.h_ring, (void*)e->crop.h_ring, (void*)e->h_feed[0], (void*)e->h_feed[1], (void*)e->h_train_losses,
-                    (void*)e->h_dets, (void*)e->h_ndets})
+                    (void*)e->h_dets, (void*)e->h_ndets, (void*)e->proj.h_bbox})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t ev : {e->off_ev[0], e->off_ev[1], e->off_ev[2], e->off_ev[3], e->ev_in, e->ev_up, e->ev_vox_main, e->ev_tgt, e->crop.ev_main,
                           e->ev_read[0], e->ev_read[1], e->t0, e->t1})
@@ -1156,7 +1162,7 @@ int pp_detect_async(pp_handle e) {
         pp_engine::GraphSlot* lru = &e->graphs[0];
         for (auto& g : e->graphs) {
             if (g.exec && g.batch == B && g.bucket == bucket && g.buf == e->in_buf && g.zc == (e->zc ? 1 : 0) &&
-                g.vox == (e->vox_ahead ? 1 : 0) && g.nms == e->nms_mode) slot = &g;
+                g.vox == (e->vox_ahead ? 1 : 0) && g.nms == e->nms_mode && g.proj == (e->proj.on ? 1 : 0)) slot = &g;
             if (g.used < lru->used) lru = &g;
         }
         if (slot == nullptr) {
@@ -1178,6 +1184,7 @@ int pp_detect_async(pp_handle e) {
                 slot->zc = e->zc ? 1 : 0;
                 slot->vox = e->vox_ahead ? 1 : 0;
                 slot->nms = e->nms_mode;
+                slot->proj = e->proj.on ? 1 : 0;
             } else {
                 slot->exec = nullptr;
                 e->graph_state = -1;           // fall back to plain launches for the life of the handle
@@ -1191,6 +1198,7 @@ int pp_detect_async(pp_handle e) {
             HIPCHK(e, hipEventRecord(e->ev_read[e->in_buf], e->stream));
             e->results_batch = B;
             e->results_buf = e->in_buf;
+            e->proj.results = e->proj.on ? B : 0;
             return PP_OK;
         }
     }
@@ -1199,6 +1207,7 @@ int pp_detect_async(pp_handle e) {
         HIPCHK(e, hipEventRecord(e->ev_read[e->in_buf], e->stream));
         e->results_batch = B;
         e->results_buf = e->in_buf;
+        e->proj.results = e->proj.on ? B : 0;
     }
     return st;
 }
@@ -1211,7 +1220,8 @@ int pp_sync(pp_handle e) {
 }
 
 // k_postprocess flags a frame whose head maps hold a non-finite value in bit PP_NDETS_NONFINITE of its count
-static int check_numeric(pp_engine* e, const int* n_dets, int B, const char* who) {
+}  // extern "C"
+int check_numeric(pp_engine* e, const int* n_dets, int B, const char* who) {
     int bad = 0, first = -1;
     for (int b = 0; b < B; ++b)
         if (n_dets[b] & PP_NDETS_NONFINITE) { if (first < 0) first = b; ++bad; }
@@ -1221,6 +1231,7 @@ static int check_numeric(pp_engine* e, const int* n_dets, int B, const char* who
                              : "an activation left the range of the float16 operand pieces (|x| < 65504): "
                                "pp_set_gemm_precision(h, PP_PREC_F32) and run the frames again");
 }
+extern "C" {
 
 int pp_set_gemm_precision(pp_handle e, int32_t precision) {
     if (!e) return PP_ERR_ARG;
@@ -1387,8 +1398,14 @@ int pp_predict(pp_handle e, const float* box_preds, const float* cls_preds, cons
     if ((st = run_post(e, batch))) return st;
     HIPCHK(e, hipMemcpyAsync(dets, e->d_dets, (size_t)batch * e->cfg.nms_post_max_size * sizeof(pp_detection), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipMemcpyAsync(n_dets, e->d_ndets, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    if (e->proj.on)
+        HIPCHK(e, hipMemcpyAsync(e->proj.h_bbox, e->proj.d_bbox, (size_t)batch * e->cfg.nms_post_max_size * 4 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     stage_call_done(e);
+    if (e->proj.on) {      // pp_get_bboxes reads the counts beside the boxes (flags included: it reports PP_ERR_NUMERIC too)
+        memcpy(e->h_ndets, n_dets, (size_t)batch * sizeof(int));
+        e->proj.results = batch;
+    }
     // non-finite predictions: the reference's predict() would hand NaN boxes on (np.argpartition over NaN scores);
     // this one says so instead (documented deviation)
     if ((st = check_numeric(e, n_dets, batch, "pp_predict"))) {

@@ -265,6 +265,11 @@ struct PostParams {
     pp_detection* dets_host;
     int* n_dets_host;
     int nms_mode;          // enum pp_nms_mode: which instantiation of the kernel runs
+    // pp_set_projection (NULL: off, the other instantiation): p2 [batch][16] float64 row-major; every kept detection's image
+    // box (box_project_dev.h) goes to bbox [batch * post_max][4] and, with dets_host, to its page-locked twin
+    const double* p2;
+    double* bbox;
+    double* bbox_host;
 };
 void launch_postprocess(const PostParams& p, hipStream_t s);
 
@@ -308,6 +313,11 @@ void launch_d3_finish(const double* boxes, int64_t N, const double* qboxes, int6
 // order [m], sorted [m][5], corners [m][9], mask [m][ceil(m / 64)] are scratch; keep [m] and *n_keep the result
 void launch_rnms(const float* dets, int n, int m, float thr, int post_max, int* order, float* sorted, float* corners,
                  unsigned long long* mask, int* keep, long long* n_keep, hipStream_t s);
+
+// box_project.hip: image boxes of n camera-frame boxes [n][7]; frame_start [frames + 1] is the exclusive prefix of the
+// frames' box counts, p2 [frames][16], bbox [n][4]
+void launch_box3d_to_bbox(const double* boxes, long long n, const long long* frame_start, int frames, const double* p2,
+                          double* bbox, hipStream_t s);
 
 // eval_stats.hip: the AP evaluator's greedy matching and tp / fp / fn / similarity statistics (kitti_eval.py)
 struct EvalStatsParams {

@@ -1,7 +1,8 @@
 // Host side of the C-ABI (include/pp_hip.h), shared by its translation units: the handle, the error / allocation
 // helpers and what one unit calls in another.  pp_api.hip: lifetime, weights, feeds, the inference pipeline;
 // api_ingest.hip: PointCloud2 ingest; api_crop.hip: the frustum crop; api_train.hip: loss, training step, optimizer; api_dataprep.hip: targets,
-// augmentation, GT sampling, object database; api_eval.hip: the AP evaluator (needs no handle); api_nms.hip: the detector's NMS rule and the standalone rotated NMS.
+// augmentation, GT sampling, object database; api_eval.hip: the AP evaluator (needs no handle); api_nms.hip: the detector's NMS rule and the standalone rotated NMS;
+// api_project.hip: the detector's image boxes and the standalone projection.
 #pragma once
 
 #include <cmath>
@@ -241,11 +242,21 @@ struct pp_engine {
     int f32_fallback_layers = 0;   // layers whose folded weights do not fit float16 pieces (pp_finalize_weights)
     bool force_f32 = false;        // pp_set_gemm_precision(PP_PREC_F32): no layer gets split weights
     int nms_mode = PP_NMS_STANDUP; // pp_set_nms_mode: the post-process instantiation of the next pass (part of a graph's key)
+    // pp_set_projection: image boxes of the kept detections (allocated on first use; `on` is part of a graph's key)
+    struct Projection {
+        bool on = false;
+        int batch = 0;                 // frames the matrices were given for
+        std::vector<double> h_p2;      // what d_p2 holds (an unchanged set is not uploaded again)
+        double* d_p2 = nullptr;        // [B][16]
+        double* d_bbox = nullptr;      // [B * nms_post_max_size][4]
+        double* h_bbox = nullptr;      // pinned twin: the fused path's kernel stores into it, pp_predict copies into it
+        int results = 0;               // frames of the last pass that projected (pp_get_bboxes; 0: none, or projection off)
+    } proj;
 
     int prof = 0;
     // pp_detect_async as one hipGraph launch (captured on first use per (batch, max points per frame))
-    struct GraphSlot { hipGraphExec_t exec = nullptr; int batch = -1, bucket = -1, buf = -1, zc = 0, vox = 0, nms = 0; unsigned long long used = 0; };
-    GraphSlot graphs[8];          // small LRU keyed by (batch, point-count bucket, input buffer, NMS rule)
+    struct GraphSlot { hipGraphExec_t exec = nullptr; int batch = -1, bucket = -1, buf = -1, zc = 0, vox = 0, nms = 0, proj = 0; unsigned long long used = 0; };
+    GraphSlot graphs[8];          // small LRU keyed by (batch, point-count bucket, input buffer, NMS rule, projection on / off)
     unsigned long long graph_tick = 0;
     int graph_state = 0;          // 0: try, -1: capture failed once (use plain launches)
     std::vector<hipEvent_t> events;
@@ -324,6 +335,7 @@ struct ProfScope {
 int run_voxelize(pp_engine* e, int batch, int max_n, hipStream_t vs = nullptr);
 int finish_async_upload(pp_engine* e, int batch);  // voxelises behind a copy-stream upload (where allowed), records ev_up
 int check_batch(pp_engine* e, int batch);
+int check_numeric(pp_engine* e, const int* n_dets, int B, const char* who);   // PP_ERR_NUMERIC for a flagged frame
 int graph_bucket(const pp_engine* e, int max_n);
 bool graphs_enabled();
 // ---- pp_api.hip: the resident frames' state, one function per transition ----

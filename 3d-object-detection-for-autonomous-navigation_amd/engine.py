@@ -252,6 +252,36 @@ class Engine:
         self._check(self._lib.pp_get_nms_mode(self._h, ctypes.byref(v)), "pp_get_nms_mode")
         return {v_: k for k, v_ in _NMS_MODES.items()}[v.value]
 
+    # ---- image boxes of the kept detections (pp_set_projection) ----
+    def set_projection(self, p2):
+        """p2 [4,4] (every frame) or [B,4,4] (frame b of a pass uses matrix b), or None: off (the default).  With it on,
+        the post-process also projects every kept detection's camera box into the image (projection.py states the
+        rule) and `bboxes()` returns the result.  Takes effect from the next predict / detect."""
+        if p2 is None:
+            self._check(self._lib.pp_set_projection(self._h, None, 0), "pp_set_projection")
+            return
+        p = np.asarray(p2, np.float64)
+        if p.ndim == 2:
+            p = np.broadcast_to(p, (self.max_batch,) + p.shape)
+        if p.ndim != 3 or p.shape[1:] != (4, 4):
+            raise ValueError(f"p2 must be [4,4] or [B,4,4], got {np.asarray(p2).shape}")
+        p = np.ascontiguousarray(p).reshape(p.shape[0], 16)
+        self._check(self._lib.pp_set_projection(self._h, _ptr(p), int(p.shape[0])), "pp_set_projection")
+
+    @property
+    def projection(self):
+        v = ctypes.c_int32(0)
+        self._check(self._lib.pp_get_projection(self._h, ctypes.byref(v)), "pp_get_projection")
+        return bool(v.value)
+
+    def bboxes(self, batch=None):
+        """[B, nms_post_max_size, 4] float64 image boxes (min u, min v, max u, max v) of the last pass, row i of frame b
+        beside detection i; rows at or beyond the frame's count are zero.  Raises when that pass ran with projection off."""
+        post = self.d.nms_post_max_size
+        out = np.zeros((self.max_batch, post, 4), dtype=np.float64)
+        self._check(self._lib.pp_get_bboxes(self._h, _ptr(out)), "pp_get_bboxes")
+        return out if batch is None else out[:batch]
+
     def set_cache_budget(self, megabytes):
         """Last-level-cache budget of a pass in MiB (pp_set_cache_budget; default 256, 0 = off): layers whose maps exceed
         it run over sub-ranges of the batch's frames.  Right for one engine in flight per GPU; set 0 when several
@@ -338,8 +368,11 @@ class Engine:
         return out
 
     # ---- a8-a12 ----
-    def predict(self, box_preds, cls_preds, dir_cls_preds, anchors_mask, rect, trv2c):
+    def predict(self, box_preds, cls_preds, dir_cls_preds, anchors_mask, rect, trv2c, p2=None):
+        """p2 ([4,4] or [batch,4,4]): set_projection(p2) first -- `bboxes(batch)` then holds the image boxes."""
         batch = box_preds.shape[0]
+        if p2 is not None:
+            self.set_projection(np.broadcast_to(np.asarray(p2, np.float64), (batch, 4, 4)))
         post = self.d.nms_post_max_size
         dets = np.zeros((batch, post), dtype=DET_DTYPE)
         n = np.zeros((batch,), dtype=np.int32)
@@ -438,20 +471,27 @@ class Engine:
         self._check(self._lib.pp_get_detections(self._h, _ptr(dets), _ptr(n)), "pp_get_detections")
         return dets, n
 
-    def detect(self, frames, rect=None, trv2c=None, on_numeric="f32", p2=None, image_shape=None):
+    def detect(self, frames, rect=None, trv2c=None, on_numeric="f32", p2=None, image_shape=None, bbox=False):
         """upload + detect_async + sync + detections.  on_numeric: what to do when the default arithmetic reports
         activations outside the float16 pieces' range (NumericError) -- "f32": switch this engine to the float32
         matrix instruction (it stays there: `gemm_precision()`), run the still-resident frames again and return those
         results; "raise": propagate.  A network that overflows float32 itself always raises.
         p2 ([4, 4] or [B, 4, 4]) and image_shape ((height, width) or [B, 2]), both or neither: the uploaded frames are
         cropped to the camera frustum on the GPU (crop_to_image) before the pass -- once: the float32 re-run reads the
-        cropped frames; rect and trv2c are then required."""
-        if (p2 is None) != (image_shape is None):
-            raise ValueError("detect: p2 and image_shape go together (both crop the frames to the image, neither does not)")
-        if p2 is not None and (rect is None or trv2c is None):
+        cropped frames; rect and trv2c are then required.
+        bbox=True (needs p2; image_shape only when the frames are to be cropped as well): set_projection(p2) for this
+        pass -- `bboxes(len(frames))` then holds the detections' image boxes."""
+        if bbox and p2 is None:
+            raise ValueError("detect: bbox=True needs p2 (the camera matrix the boxes are projected by)")
+        if (image_shape is not None and p2 is None) or (p2 is not None and image_shape is None and not bbox):
+            raise ValueError("detect: p2 and image_shape go together (both crop the frames to the image, neither does not); "
+                             "p2 alone projects, with bbox=True")
+        if image_shape is not None and (rect is None or trv2c is None):
             raise ValueError("detect: the frustum crop needs rect and trv2c")
+        if bbox:
+            self.set_projection(np.broadcast_to(np.asarray(p2, np.float64), (len(frames), 4, 4)))
         self.upload(frames, rect, trv2c)
-        if p2 is not None:
+        if image_shape is not None:
             from . import frustum
             B = len(frames)
             r4, t4, p4 = (np.broadcast_to(np.asarray(m, np.float64), (B, 4, 4)) for m in (rect, trv2c, p2))

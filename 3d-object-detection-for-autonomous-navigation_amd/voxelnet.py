@@ -52,6 +52,14 @@ class VoxelNet:
         else:
             self.engine = Engine(self.d, **self._ctor)
 
+    def _bboxes(self, batch):
+        """The image boxes of the pass that has just run; None (the placeholder) without model.second.project_bbox."""
+        return self.engine.bboxes(batch) if self.d.project_bbox else None
+
+    def _need_p2(self, p2, who):
+        if self.d.project_bbox and p2 is None:
+            raise ValueError(f"{who}: model.second.project_bbox is on: pass p2 (the frames' camera matrices)")
+
     # net.load_weights (train.py:731-734).  Accepts a dict name -> array (Keras layouts, weights.py), an .npz written by
     # weights.save_npz, or the reference's own checkpoint file (`model_weights_<epoch>.h5`, Keras save_weights,
     # train.py:407,436: weights.load_keras_h5, with h5py when it is installed and the built-in reader otherwise).
@@ -135,31 +143,44 @@ class VoxelNet:
         mask, img_idx = _np(example[7]), _np(example[8])
         batch = int(_np(example[6]).shape[0])
         dirp = _np(preds_dict["dir_cls_preds"]) if self.d.use_direction_classifier else None
-        dets, n = self.engine.predict(_np(preds_dict["box_preds"]), _np(preds_dict["cls_preds"]), dirp, mask, rect, trv2c)
-        return [self._to_dict(dets[b], int(n[b]), img_idx[b]) for b in range(batch)]
+        # model.second.project_bbox: "bbox" is the projection by example[5] (P2), as upstream SECOND's predict()
+        p2 = _np(example[5]) if self.d.project_bbox else None
+        self._need_p2(p2, "predict")
+        dets, n = self.engine.predict(_np(preds_dict["box_preds"]), _np(preds_dict["cls_preds"]), dirp, mask, rect, trv2c, p2=p2)
+        bb = self._bboxes(batch)
+        return [self._to_dict(dets[b], int(n[b]), img_idx[b], None if bb is None else bb[b]) for b in range(batch)]
 
-    def detect(self, frames, rect=None, trv2c=None, image_idx=None):
-        """Fused path: list of raw clouds -> list of prediction dicts."""
-        dets, n = self.engine.detect(frames, rect, trv2c)
+    def detect(self, frames, rect=None, trv2c=None, image_idx=None, p2=None):
+        """Fused path: list of raw clouds -> list of prediction dicts.  p2 ([4,4] or [B,4,4]): required with
+        model.second.project_bbox, which puts the projected image boxes into "bbox"."""
+        self._need_p2(p2, "detect")
+        on = self.d.project_bbox
+        dets, n = self.engine.detect(frames, rect, trv2c, p2=p2 if on else None, bbox=on)
+        bb = self._bboxes(len(frames))
         idx = image_idx if image_idx is not None else list(range(len(frames)))
-        return [self._to_dict(dets[b], int(n[b]), idx[b]) for b in range(len(frames))]
+        return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(frames))]
 
-    def detect_pointcloud2(self, msgs, rect=None, trv2c=None, image_idx=None):
+    def detect_pointcloud2(self, msgs, rect=None, trv2c=None, image_idx=None, p2=None):
         """Fused path from raw sensor_msgs/PointCloud2 messages (the reference's production mode: ingest on the GPU,
-        Engine.detect_pointcloud2) -> the same list of prediction dicts as `detect`."""
+        Engine.detect_pointcloud2) -> the same list of prediction dicts as `detect`; p2 as there."""
+        self._need_p2(p2, "detect_pointcloud2")
+        if self.d.project_bbox:
+            self.engine.set_projection(np.broadcast_to(np.asarray(p2, np.float64), (len(msgs), 4, 4)))
         dets, n = self.engine.detect_pointcloud2(msgs, rect, trv2c)
+        bb = self._bboxes(len(msgs))
         idx = image_idx if image_idx is not None else list(range(len(msgs)))
-        return [self._to_dict(dets[b], int(n[b]), idx[b]) for b in range(len(msgs))]
+        return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(msgs))]
 
     @staticmethod
-    def _to_dict(dets, n, img_idx):
+    def _to_dict(dets, n, img_idx, bbox=None):
         # model/voxelnet.py:1362-1379: all-None dict (except batch_idx) when nothing survives
         if n == 0:
             return {"bbox": None, "box3d_camera": None, "box3d_lidar": None, "scores": None,
                     "label_preds": None, "batch_idx": img_idx}
         d = dets[:n]
         return {
-            "bbox": np.tile(np.array([[400., 200., 500., 400.]]), (n, 1)),  # model/voxelnet.py:1357-1360
+            # the placeholder of model/voxelnet.py:1357-1360, or (model.second.project_bbox) the projected rows
+            "bbox": np.tile(np.array([[400., 200., 500., 400.]]), (n, 1)) if bbox is None else np.array(bbox[:n], np.float64),
             "box3d_camera": d["box3d_camera"].copy(),
             "box3d_lidar": d["box3d_lidar"].copy(),
             "scores": d["score"].copy(),

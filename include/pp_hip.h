@@ -35,7 +35,7 @@ extern "C" {
  * pp_train_step_sample_async, pp_train_step_sample; then pp_pc2_layout, pp_ingest_config, pp_ingest_pointcloud2,
  * pp_ingest_pointcloud2_async, pp_ingest_info; then pp_gtdb_build, pp_gtdb_count; then PP_CROP_BACK, pp_frustum_crop,
  * pp_frustum_crop_async, pp_frustum_crop_info; then pp_nms_mode, pp_set_nms_mode, pp_get_nms_mode, PP_RNMS_MAX_BOXES,
- * pp_rotate_nms. */
+ * pp_rotate_nms; then pp_set_projection, pp_get_projection, pp_get_bboxes, pp_box3d_to_bbox. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -239,6 +239,26 @@ int pp_get_gemm_precision(pp_handle h, int32_t* precision);
  * then stays as it was).  The rule is part of what a captured pass is keyed on: a change captures once more. */
 int pp_set_nms_mode(pp_handle h, int32_t mode);
 int pp_get_nms_mode(pp_handle h, int32_t* mode);
+/* Image boxes of the kept detections, computed at the end of this handle's post-process (pp_predict and the fused path):
+ * box3d_to_bbox of second/core/box_np_ops.py:849-857 -- the eight corners of box3d_camera projected by the frame's P2,
+ * min / max over them, float64 -- which the reference's predict() replaced by a constant (model/voxelnet.py:1336-1360).
+ * p2 [batch,16]: the frames' 4 x 4 camera matrices, row-major; frame b of a pass uses matrix b, so a pass of more than
+ * `batch` frames is refused (PP_ERR_STATE).  NULL switches the projection off (`batch` is then ignored); off is the
+ * default, and then every output is what it was before the switch existed.  As the reference's project_to_image
+ * appends zeros, not ones, as the homogeneous coordinate, only the left 3 x 3 of each matrix enters; nothing clips to the
+ * image and nothing treats corners behind the camera (w' < 0 mirrors them, w' = 0 gives inf / NaN).  Takes effect from
+ * the next pp_detect* / pp_predict; pp_detection and everything else of the post-process are the same either way.  The
+ * matrices live in device memory written on the handle's stream (the call waits for it), so a replayed pass reads the
+ * current ones; on / off is part of what a captured pass is keyed on.  An unchanged set is not uploaded again.
+ * PP_ERR_ARG for a batch outside 1..max_batch, PP_ERR_STATE while a training step is in flight (the setting then stays
+ * as it was). */
+int pp_set_projection(pp_handle h, const double* p2, int32_t batch);
+int pp_get_projection(pp_handle h, int32_t* on);
+/* The image boxes of the last pass (pp_detect_async or pp_predict), bbox [batch*nms_post_max_size,4] float64 rows
+ * (min u, min v, max u, max v), row b * nms_post_max_size + i beside detection i of frame b.  Waits for the handle's
+ * stream first, and returns PP_ERR_NUMERIC where pp_get_detections would; PP_ERR_STATE when that pass ran with the
+ * projection off or there are no results.  Rows at or beyond a frame's n_dets are not written. */
+int pp_get_bboxes(pp_handle h, double* bbox);
 /* Last-level-cache budget of a pass, in MiB (default 256, 0 = off).  Layers whose input + output maps exceed it are run
  * over sub-ranges of the batch's frames, a block's consecutive separable layers sub-range by sub-range, so that a layer
  * reads what the layer before has just written while it still sits in the 256 MB cache (KITTI-shaped B = 32: -5 % per
@@ -313,6 +333,16 @@ int pp_d3_box_overlap(int device, const double* boxes, int64_t n, const double* 
  * bytes on every run. */
 int pp_rotate_nms(int device, const float* dets, int64_t n, float iou_threshold, int32_t pre_max_size,
                   int32_t post_max_size, int32_t* keep, int64_t* n_keep);
+
+/* ---- image boxes of camera-frame boxes ------- */
+
+/* box3d_to_bbox (second/core/box_np_ops.py:849-857) of any boxes, without a handle: labels, database boxes.
+ * boxes_camera [n,7] float64 rows (x, y, z, l, h, w, ry) of `frames` frames laid end to end, box_counts [frames] boxes
+ * per frame (n is their sum), p2 [frames,16] the frames' matrices; bbox [n,4].  The arithmetic is the function the
+ * detector's post-process calls (pp_set_projection): the same seven doubles give the same bits.  n = 0 or frames = 0 is
+ * PP_OK with nothing written.  PP_ERR_ARG for a negative count.  Stateless; host pointers; `device` is the HIP device. */
+int pp_box3d_to_bbox(int device, const double* boxes_camera, const int32_t* box_counts, int32_t frames, const double* p2,
+                     double* bbox);
 
 /* ---- AP-evaluator statistics ----------------- */
 
