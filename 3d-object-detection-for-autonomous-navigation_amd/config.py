@@ -180,10 +180,17 @@ class Derived:
         n_sizes = int(np.array(ag["sizes"]).reshape([-1, 3]).shape[0])
         self.num_anchor_per_loc = len(ag["rotations"]) * n_sizes
         self.num_class = int(s["num_class"])
-        if not s["encode_background_as_zeros"] or s["use_multi_class_nms"]:
+        if not s["encode_background_as_zeros"]:
             raise NotImplementedError(
-                "only encode_background_as_zeros / single-pass NMS is implemented "
-                "in the reference's predict() (model/voxelnet.py:1152-1157, :1167 are TF stubs)")
+                "only encode_background_as_zeros is implemented "
+                "in the reference's predict() (model/voxelnet.py:1152-1157 is a TF stub)")
+        # model/voxelnet.py:1170-1171 is `pass` in the reference; built here as what the key names: the single pass of
+        # :1172-1286 once per class on that class's score alone (Engine.set_class_nms("per_class"))
+        self.use_multi_class_nms = bool(s["use_multi_class_nms"])
+        if self.use_multi_class_nms and self.num_class < 2:
+            raise NotImplementedError(
+                "use_multi_class_nms needs num_class >= 2: with one class the single pass of predict() "
+                "(model/voxelnet.py:1172-1286) already is the per-class pass -- leave the key off")
         # model/voxelnet.py:690,714,1093,1297: without it the RPN has no conv_dir_cls and predict() does not flip
         self.use_direction_classifier = bool(s["use_direction_classifier"])
         # num_class > 1 is a TF stub in the reference's predict() (model/voxelnet.py:1183-1185: reduce_max /
@@ -221,4 +228,5 @@ class Derived:
         return {"nms_score_threshold": self.nms_score_threshold, "nms_pre_max_size": self.nms_pre_max_size,
                 "nms_post_max_size": self.nms_post_max_size, "nms_iou_threshold": self.nms_iou_threshold,
                 "num_class": self.num_class, "use_direction_classifier": self.use_direction_classifier,
-                "use_rotate_nms": self.use_rotate_nms, "project_bbox": self.project_bbox}
+                "use_rotate_nms": self.use_rotate_nms, "project_bbox": self.project_bbox,
+                "use_multi_class_nms": self.use_multi_class_nms}

@@ -30,10 +30,11 @@ int pp_set_projection(pp_handle e, const double* p2, int32_t batch) {
     if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_set_projection: a training step is in flight");
     (void)hipSetDevice(e->device);
     if (pj.d_p2 == nullptr) {
-        const size_t rows = (size_t)e->B * e->cfg.nms_post_max_size;
+        const size_t rows = (size_t)e->B * e->ncls * e->cfg.nms_post_max_size;   // the per-class mode's rows (pp_set_class_nms)
         DevAlloc A{e};
         A(&pj.d_p2, (size_t)e->B * 16);
         A(&pj.d_bbox, rows * 4);
+        A(&pj.d_cls_bbox, rows * 4);
         if (A.st != PP_OK) { pj.d_p2 = nullptr; return A.st; }
         HIPCHK(e, hipHostMalloc((void**)&pj.h_bbox, rows * 4 * sizeof(double)));
     }
@@ -61,7 +62,9 @@ int pp_get_bboxes(pp_handle e, double* bbox) {
     (void)hipSetDevice(e->device);
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (int st = check_numeric(e, e->h_ndets, B, "pp_get_bboxes")) return st;
-    const size_t pm = (size_t)e->cfg.nms_post_max_size;
+    if (e->results_rows != det_rows(e))
+        return fail(e, PP_ERR_STATE, "pp_get_bboxes: the last pass ran in the other class mode (pp_set_class_nms): run a new one");
+    const size_t pm = (size_t)e->results_rows;
     for (int b = 0; b < B; ++b) {
         const size_t n = (size_t)std::max(0, std::min(e->h_ndets[b], (int)pm));
         memcpy(bbox + (size_t)b * pm * 4, e->proj.h_bbox + (size_t)b * pm * 4, n * 4 * sizeof(double));

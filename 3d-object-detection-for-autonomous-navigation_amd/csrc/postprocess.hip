@@ -31,6 +31,12 @@
 // projects it (box3d_to_bbox of second/core/box_np_ops.py:849-857, box_project_dev.h) with the frame's P2 and stores the
 // four doubles beside the detections.  The reference's predict() has this commented out and returns a constant
 // (model/voxelnet.py:1336-1360); off (the default) is the instantiation without a trace of it.
+//
+// Per-class suppression (template parameter, pp_set_class_nms): the branch model.second.use_multi_class_nms names and the
+// reference leaves as `pass` (model/voxelnet.py:1170-1171).  The grid is (batch, num_class); workgroup (b, c) runs the very
+// same pass with class c's logit as the anchor's score and c as its label -- threshold, top-100, NMS and the caps are per
+// class -- and stores its kept rows into segment (b, c) of a scratch buffer.  k_gather_classes, one workgroup per frame
+// behind it on the stream, lays the segments end to end (class 0's rows first) and writes the frame's total.
 #include <type_traits>
 
 #include "box_project_dev.h"
@@ -46,7 +52,7 @@ __device__ __forceinline__ unsigned long long comp_key(float logit, unsigned a) 
     return ((unsigned long long)u << 32) | (unsigned long long)(~a);
 }
 
-template <int NMS, bool PROJ>
+template <int NMS, bool PROJ, bool PERCLS>
 __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
     __shared__ int s_hist[256];
     __shared__ int s_cum[256];
@@ -75,6 +81,7 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
     }
 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int kc = PERCLS ? (int)blockIdx.y : 0;   // per-class rule: the class this workgroup scores and suppresses
     const long long A = p.A;
     const int napl = p.napl;
     const int ncls = p.ncls;
@@ -99,7 +106,10 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
                                              : head + px * PP_HEAD_COLS + nb + (int)(a - px * napl) * ncls;
         float m = q[0];
         bad |= !pp_finite(m);
-        for (int k = 1; k < ncls; ++k) { bad |= !pp_finite(q[k]); m = fmaxf(m, q[k]); }
+        for (int k = 1; k < ncls; ++k) {
+            bad |= !pp_finite(q[k]);
+            if constexpr (PERCLS) m = (k == kc) ? q[k] : m; else m = fmaxf(m, q[k]);
+        }
         return m;
     };
     const float thr = p.score_thr;
@@ -144,7 +154,11 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
                         float m = lf[i * nc];
                         bad |= !pp_finite(m);
 #pragma unroll
-                        for (int k = 1; k < nc; ++k) { const float v = lf[i * nc + k]; bad |= !pp_finite(v); m = fmaxf(m, v); }
+                        for (int k = 1; k < nc; ++k) {
+                            const float v = lf[i * nc + k];
+                            bad |= !pp_finite(v);
+                            if constexpr (PERCLS) m = (k == kc) ? v : m; else m = fmaxf(m, v);   // (a select: lf stays in registers)
+                        }
                         if (((mw[i >> 2] >> (8 * (i & 3))) & 0xffu) != 1u) continue;
                         if (thr > 0.f) {
                             const float sc = 1.f / (1.f + expf(-m));
@@ -337,11 +351,13 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
         zg = __fsub_rn(zg, __fdiv_rn(hg, 2.f));
         s_box[tid][0] = xg; s_box[tid][1] = yg; s_box[tid][2] = zg;
         s_box[tid][3] = wg; s_box[tid][4] = lg; s_box[tid][5] = hg; s_box[tid][6] = rg;
-        float lgt = hrow[nb + ar * ncls];
-        int lab = 0;
-        for (int k = 1; k < ncls; ++k) {
-            const float v = hrow[nb + ar * ncls + k];
-            if (v > lgt) { lgt = v; lab = k; }   // argmax: first maximum
+        float lgt = hrow[nb + ar * ncls + kc];
+        int lab = kc;
+        if constexpr (!PERCLS) {
+            for (int k = 1; k < ncls; ++k) {
+                const float v = hrow[nb + ar * ncls + k];
+                if (v > lgt) { lgt = v; lab = k; }   // argmax: first maximum
+            }
         }
         s_label[tid] = lab;
         s_score[tid] = 1.f / (1.f + expf(-lgt));
@@ -455,8 +471,12 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
         if (lane == 0) {
             s_nkeep = nk;
             const int flagged = nk | (s_bad ? PP_NDETS_NONFINITE : 0);   // pp_get_detections / pp_predict: PP_ERR_NUMERIC
-            p.n_dets[b] = flagged;
-            if (p.n_dets_host != nullptr) p.n_dets_host[b] = flagged;
+            if constexpr (PERCLS) {
+                p.cls_cnt[(size_t)b * ncls + kc] = flagged;     // k_gather_classes sums the counts and ORs the flags
+            } else {
+                p.n_dets[b] = flagged;
+                if (p.n_dets_host != nullptr) p.n_dets_host[b] = flagged;
+            }
         }
     }
     __syncthreads();
@@ -488,30 +508,89 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
         d.dir_label = s_dir[i];
         d.anchor_index = s_anchor[i];
         d.reserved = 0;
-        p.dets[(size_t)b * p.post_max + tid] = d;
-        if (p.dets_host != nullptr) p.dets_host[(size_t)b * p.post_max + tid] = d;
+        if constexpr (PERCLS) {     // segment (b, kc) of the scratch k_gather_classes reads
+            p.cls_dets[((size_t)b * ncls + kc) * p.post_max + tid] = d;
+        } else {
+            p.dets[(size_t)b * p.post_max + tid] = d;
+            if (p.dets_host != nullptr) p.dets_host[(size_t)b * p.post_max + tid] = d;
+        }
         if constexpr (PROJ) {
             const double* M2 = p.p2 + (size_t)b * 16;
             double P[9], bb[4];
 #pragma unroll
             for (int q = 0; q < 3; ++q) { P[3 * q] = M2[4 * q]; P[3 * q + 1] = M2[4 * q + 1]; P[3 * q + 2] = M2[4 * q + 2]; }
             box3d_to_bbox_dev(d.box3d_camera, P, bb);
-            double* o = p.bbox + ((size_t)b * p.post_max + tid) * 4;
-            double* oh = (p.bbox_host != nullptr) ? p.bbox_host + ((size_t)b * p.post_max + tid) * 4 : nullptr;
+            double* o = PERCLS ? p.cls_bbox + (((size_t)b * ncls + kc) * p.post_max + tid) * 4
+                               : p.bbox + ((size_t)b * p.post_max + tid) * 4;
+            double* oh = (!PERCLS && p.bbox_host != nullptr) ? p.bbox_host + ((size_t)b * p.post_max + tid) * 4 : nullptr;
 #pragma unroll
             for (int q = 0; q < 4; ++q) { o[q] = bb[q]; if (oh != nullptr) oh[q] = bb[q]; }
         }
     }
 }
 
+// Per-class rule, second launch: one workgroup per frame lays the classes' segments end to end.  The running sum of the
+// (clamped) class counts is the exclusive prefix every thread needs; rows are copied as 8-byte words, coalesced, to the
+// device rows and -- the fused path -- their page-locked twins.  The frame's count is the total, flagged when any class's
+// workgroup flagged the frame.
+#define GT 256
+static_assert(sizeof(pp_detection) % 8 == 0, "k_gather_classes copies detections as 8-byte words");
+__global__ __launch_bounds__(GT) void k_gather_classes(PostParams p) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int ncls = p.ncls, pm = p.post_max;
+    const size_t rows = (size_t)ncls * pm;       // row stride of a frame in dets / bbox
+    constexpr int DW = (int)(sizeof(pp_detection) / 8);
+    unsigned long long* dd = reinterpret_cast<unsigned long long*>(p.dets + (size_t)b * rows);
+    unsigned long long* dh = (p.dets_host != nullptr) ? reinterpret_cast<unsigned long long*>(p.dets_host + (size_t)b * rows) : nullptr;
+    int off = 0, flag = 0;
+    for (int c = 0; c < ncls; ++c) {
+        const int raw = p.cls_cnt[(size_t)b * ncls + c];
+        flag |= raw & PP_NDETS_NONFINITE;
+        const int cnt = min(max(raw & ~PP_NDETS_NONFINITE, 0), pm);
+        const size_t seg = ((size_t)b * ncls + c) * pm;
+        const unsigned long long* sd = reinterpret_cast<const unsigned long long*>(p.cls_dets + seg);
+        for (int w = tid; w < cnt * DW; w += GT) {
+            const unsigned long long v = sd[w];
+            dd[(size_t)off * DW + w] = v;
+            if (dh != nullptr) dh[(size_t)off * DW + w] = v;
+        }
+        if (p.p2 != nullptr) {
+            const double* sb = p.cls_bbox + seg * 4;
+            double* ob = p.bbox + ((size_t)b * rows + off) * 4;
+            double* oh = (p.bbox_host != nullptr) ? p.bbox_host + ((size_t)b * rows + off) * 4 : nullptr;
+            for (int w = tid; w < cnt * 4; w += GT) {
+                const double v = sb[w];
+                ob[w] = v;
+                if (oh != nullptr) oh[w] = v;
+            }
+        }
+        off += cnt;
+    }
+    if (tid == 0) {
+        p.n_dets[b] = off | flag;
+        if (p.n_dets_host != nullptr) p.n_dets_host[b] = off | flag;
+    }
+}
+
+template <bool PERCLS>
+static void launch_post_rule(const PostParams& p, hipStream_t s) {
+    const bool proj = p.p2 != nullptr;
+    const dim3 grid = PERCLS ? dim3(p.batch, p.ncls) : dim3(p.batch);
+    if (p.nms_mode == PP_NMS_ROTATED) {
+        if (proj) PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_ROTATED, true, PERCLS>), grid, dim3(PT), 0, s, p);
+        else PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_ROTATED, false, PERCLS>), grid, dim3(PT), 0, s, p);
+    } else {
+        if (proj) PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_STANDUP, true, PERCLS>), grid, dim3(PT), 0, s, p);
+        else PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_STANDUP, false, PERCLS>), grid, dim3(PT), 0, s, p);
+    }
+}
+
 void launch_postprocess(const PostParams& p, hipStream_t s) {
     if (p.batch <= 0) return;
-    const bool proj = p.p2 != nullptr;
-    if (p.nms_mode == PP_NMS_ROTATED) {
-        if (proj) PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_ROTATED, true>), dim3(p.batch), dim3(PT), 0, s, p);
-        else PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_ROTATED, false>), dim3(p.batch), dim3(PT), 0, s, p);
+    if (p.class_nms == PP_CLASS_NMS_PER_CLASS) {
+        launch_post_rule<true>(p, s);
+        PP_LAUNCH("k_gather_classes", k_gather_classes, dim3(p.batch), dim3(GT), 0, s, p);
     } else {
-        if (proj) PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_STANDUP, true>), dim3(p.batch), dim3(PT), 0, s, p);
-        else PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_STANDUP, false>), dim3(p.batch), dim3(PT), 0, s, p);
+        launch_post_rule<false>(p, s);
     }
 }

@@ -353,7 +353,8 @@ static int run_post(pp_engine* e, int batch, bool to_host = false) {
         return fail(e, PP_ERR_STATE, "pp_set_projection gave matrices for %d frames; this pass has %d", e->proj.batch, batch);
     p.p2 = proj ? e->proj.d_p2 : nullptr; p.bbox = proj ? e->proj.d_bbox : nullptr;
     p.bbox_host = (proj && to_host) ? e->proj.h_bbox : nullptr;
-    ProfScope ps(e, "k_postprocess");
+    p.class_nms = e->class_nms; p.cls_dets = e->d_cls_dets; p.cls_cnt = e->d_cls_cnt; p.cls_bbox = proj ? e->proj.d_cls_bbox : nullptr;
+    ProfScope ps(e, nullptr);      // the launch sites' own names: k_postprocess and, per-class mode, k_gather_classes
     launch_postprocess(p, e->stream);
     HIPCHK(e, hipGetLastError());
     return PP_OK;
@@ -367,6 +368,7 @@ static void stage_call_done(pp_engine* e) {
     e->cur_max_n = 0;
     e->cur_total = 0;
     e->results_batch = 0;
+    e->results_rows = 0;
     e->proj.results = 0;
 }
 
@@ -708,9 +710,12 @@ int pp_create(const pp_config* cfg, int device, pp_handle* out) {
             A1(dalloc(q, &e->tgt.top, (size_t)e->B * PP_MAX_GT_PER_FRAME));
             A1(dalloc(q, &e->tgt.mask, (size_t)e->B * e->A));
             A1(dalloc(q, &e->d_calib, (size_t)e->B * 16));
-            A1(dalloc(q, &e->d_dets, (size_t)e->B * cfg->nms_post_max_size));
+            // result rows per frame: num_class * nms_post_max_size (the per-class mode's; the joint mode uses the first nms_post_max_size * B)
+            A1(dalloc(q, &e->d_dets, (size_t)e->B * e->ncls * cfg->nms_post_max_size));
+            A1(dalloc(q, &e->d_cls_dets, (size_t)e->B * e->ncls * cfg->nms_post_max_size));
+            A1(dalloc(q, &e->d_cls_cnt, (size_t)e->B * e->ncls));
             A1(dalloc(q, &e->d_ndets, (size_t)e->B));
-            if (st2 == PP_OK && hipHostMalloc((void**)&e->h_dets, (size_t)e->B * cfg->nms_post_max_size * sizeof(pp_detection)) != hipSuccess) st2 = PP_ERR_HIP;
+            if (st2 == PP_OK && hipHostMalloc((void**)&e->h_dets, (size_t)e->B * e->ncls * cfg->nms_post_max_size * sizeof(pp_detection)) != hipSuccess) st2 = PP_ERR_HIP;
             if (st2 == PP_OK && hipHostMalloc((void**)&e->h_ndets, (size_t)e->B * sizeof(int)) != hipSuccess) st2 = PP_ERR_HIP;
             if (st2 == PP_OK && (hipEventCreate(&e->t0) != hipSuccess || hipEventCreate(&e->t1) != hipSuccess)) st2 = PP_ERR_HIP;
             if (st2 == PP_OK && hipHostMalloc((void**)&e->h_off_ring, (size_t)pp_engine::OFF_RING * (e->B + 1) * sizeof(int)) != hipSuccess) st2 = PP_ERR_HIP;
@@ -1162,7 +1167,7 @@ int pp_detect_async(pp_handle e) {
         pp_engine::GraphSlot* lru = &e->graphs[0];
         for (auto& g : e->graphs) {
             if (g.exec && g.batch == B && g.bucket == bucket && g.buf == e->in_buf && g.zc == (e->zc ? 1 : 0) &&
-                g.vox == (e->vox_ahead ? 1 : 0) && g.nms == e->nms_mode && g.proj == (e->proj.on ? 1 : 0)) slot = &g;
+                g.vox == (e->vox_ahead ? 1 : 0) && g.nms == e->nms_mode && g.proj == (e->proj.on ? 1 : 0) && g.cnms == e->class_nms) slot = &g;
             if (g.used < lru->used) lru = &g;
         }
         if (slot == nullptr) {
@@ -1185,6 +1190,7 @@ int pp_detect_async(pp_handle e) {
                 slot->vox = e->vox_ahead ? 1 : 0;
                 slot->nms = e->nms_mode;
                 slot->proj = e->proj.on ? 1 : 0;
+                slot->cnms = e->class_nms;
             } else {
                 slot->exec = nullptr;
                 e->graph_state = -1;           // fall back to plain launches for the life of the handle
@@ -1199,6 +1205,7 @@ int pp_detect_async(pp_handle e) {
             e->results_batch = B;
             e->results_buf = e->in_buf;
             e->proj.results = e->proj.on ? B : 0;
+            e->results_rows = det_rows(e);
             return PP_OK;
         }
     }
@@ -1208,6 +1215,7 @@ int pp_detect_async(pp_handle e) {
         e->results_batch = B;
         e->results_buf = e->in_buf;
         e->proj.results = e->proj.on ? B : 0;
+        e->results_rows = det_rows(e);
     }
     return st;
 }
@@ -1268,7 +1276,9 @@ int pp_get_detections(pp_handle e, pp_detection* dets, int32_t* n_dets) {
     (void)hipSetDevice(e->device);
     HIPCHK(e, hipStreamSynchronize(e->stream));   // immediate after pp_sync; never hands out a half-written buffer
     // the kept detections of every frame, zeros behind them (the kernel writes only what it keeps)
-    const size_t pm = (size_t)e->cfg.nms_post_max_size;
+    if (e->results_rows != det_rows(e))
+        return fail(e, PP_ERR_STATE, "pp_get_detections: the last pass ran in the other class mode (pp_set_class_nms): run a new one");
+    const size_t pm = (size_t)e->results_rows;    // row stride of that pass: nms_post_max_size, or num_class times that
     if (int st = check_numeric(e, e->h_ndets, B, "pp_get_detections")) return st;
     for (int b = 0; b < B; ++b) {
         size_t n = (size_t)std::max(0, std::min(e->h_ndets[b], (int)pm));
@@ -1396,15 +1406,17 @@ int pp_predict(pp_handle e, const float* box_preds, const float* cls_preds, cons
     HIPCHK(e, hipMemcpyAsync(e->d_mask, anchors_mask, (size_t)batch * e->A, hipMemcpyHostToDevice, e->stream));
     prof_reset(e);
     if ((st = run_post(e, batch))) return st;
-    HIPCHK(e, hipMemcpyAsync(dets, e->d_dets, (size_t)batch * e->cfg.nms_post_max_size * sizeof(pp_detection), hipMemcpyDeviceToHost, e->stream));
+    const size_t rows = (size_t)det_rows(e);
+    HIPCHK(e, hipMemcpyAsync(dets, e->d_dets, (size_t)batch * rows * sizeof(pp_detection), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipMemcpyAsync(n_dets, e->d_ndets, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, e->stream));
     if (e->proj.on)
-        HIPCHK(e, hipMemcpyAsync(e->proj.h_bbox, e->proj.d_bbox, (size_t)batch * e->cfg.nms_post_max_size * 4 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipMemcpyAsync(e->proj.h_bbox, e->proj.d_bbox, (size_t)batch * rows * 4 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     stage_call_done(e);
     if (e->proj.on) {      // pp_get_bboxes reads the counts beside the boxes (flags included: it reports PP_ERR_NUMERIC too)
         memcpy(e->h_ndets, n_dets, (size_t)batch * sizeof(int));
         e->proj.results = batch;
+        e->results_rows = (int)rows;
     }
     // non-finite predictions: the reference's predict() would hand NaN boxes on (np.argpartition over NaN scores);
     // this one says so instead (documented deviation)

@@ -270,6 +270,13 @@ struct PostParams {
     const double* p2;
     double* bbox;
     double* bbox_host;
+    // pp_set_class_nms (enum pp_class_nms).  PP_CLASS_NMS_PER_CLASS: workgroup (b, c) runs the whole pass on class c's score
+    // alone and leaves its kept rows in segment (b, c) of the scratch buffers; k_gather_classes then lays the segments end to
+    // end into dets / bbox (row stride ncls * post_max), sums the counts into n_dets and fills the page-locked twins
+    int class_nms;
+    pp_detection* cls_dets;   // [batch][ncls][post_max]
+    int* cls_cnt;             // [batch][ncls], each with its own PP_NDETS_NONFINITE flag
+    double* cls_bbox;         // [batch][ncls][post_max][4] (with p2)
 };
 void launch_postprocess(const PostParams& p, hipStream_t s);
 

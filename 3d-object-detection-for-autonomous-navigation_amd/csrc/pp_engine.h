@@ -2,7 +2,7 @@
 // helpers and what one unit calls in another.  pp_api.hip: lifetime, weights, feeds, the inference pipeline;
 // api_ingest.hip: PointCloud2 ingest; api_crop.hip: the frustum crop; api_train.hip: loss, training step, optimizer; api_dataprep.hip: targets,
 // augmentation, GT sampling, object database; api_eval.hip: the AP evaluator (needs no handle); api_nms.hip: the detector's NMS rule and the standalone rotated NMS;
-// api_project.hip: the detector's image boxes and the standalone projection.
+// api_project.hip: the detector's image boxes and the standalone projection; api_class_nms.hip: joint / per-class suppression.
 #pragma once
 
 #include <cmath>
@@ -242,21 +242,28 @@ struct pp_engine {
     int f32_fallback_layers = 0;   // layers whose folded weights do not fit float16 pieces (pp_finalize_weights)
     bool force_f32 = false;        // pp_set_gemm_precision(PP_PREC_F32): no layer gets split weights
     int nms_mode = PP_NMS_STANDUP; // pp_set_nms_mode: the post-process instantiation of the next pass (part of a graph's key)
+    // pp_set_class_nms: joint (one pass for all classes) or per class.  The result buffers (d_dets, h_dets, the projection's
+    // boxes) hold ncls * nms_post_max_size rows per frame; a pass uses the row stride of the mode it ran in (det_rows)
+    int class_nms = PP_CLASS_NMS_JOINT;   // the next pass's mode (part of a graph's key)
+    int results_rows = 0;                 // row stride of the last pass whose results can be fetched (pp_get_detections, pp_get_bboxes)
+    pp_detection* d_cls_dets = nullptr;   // [B][ncls][nms_post_max_size]: the classes' segments, before k_gather_classes
+    int* d_cls_cnt = nullptr;             // [B][ncls]
     // pp_set_projection: image boxes of the kept detections (allocated on first use; `on` is part of a graph's key)
     struct Projection {
         bool on = false;
         int batch = 0;                 // frames the matrices were given for
         std::vector<double> h_p2;      // what d_p2 holds (an unchanged set is not uploaded again)
         double* d_p2 = nullptr;        // [B][16]
-        double* d_bbox = nullptr;      // [B * nms_post_max_size][4]
+        double* d_bbox = nullptr;      // [B * ncls * nms_post_max_size][4] (row stride of a pass: det_rows)
+        double* d_cls_bbox = nullptr;  // [B][ncls][nms_post_max_size][4]: the per-class segments
         double* h_bbox = nullptr;      // pinned twin: the fused path's kernel stores into it, pp_predict copies into it
         int results = 0;               // frames of the last pass that projected (pp_get_bboxes; 0: none, or projection off)
     } proj;
 
     int prof = 0;
     // pp_detect_async as one hipGraph launch (captured on first use per (batch, max points per frame))
-    struct GraphSlot { hipGraphExec_t exec = nullptr; int batch = -1, bucket = -1, buf = -1, zc = 0, vox = 0, nms = 0, proj = 0; unsigned long long used = 0; };
-    GraphSlot graphs[8];          // small LRU keyed by (batch, point-count bucket, input buffer, NMS rule, projection on / off)
+    struct GraphSlot { hipGraphExec_t exec = nullptr; int batch = -1, bucket = -1, buf = -1, zc = 0, vox = 0, nms = 0, proj = 0, cnms = 0; unsigned long long used = 0; };
+    GraphSlot graphs[8];          // small LRU keyed by (batch, point-count bucket, input buffer, NMS rule, projection on / off, class mode)
     unsigned long long graph_tick = 0;
     int graph_state = 0;          // 0: try, -1: capture failed once (use plain launches)
     std::vector<hipEvent_t> events;
@@ -336,6 +343,10 @@ int run_voxelize(pp_engine* e, int batch, int max_n, hipStream_t vs = nullptr);
 int finish_async_upload(pp_engine* e, int batch);  // voxelises behind a copy-stream upload (where allowed), records ev_up
 int check_batch(pp_engine* e, int batch);
 int check_numeric(pp_engine* e, const int* n_dets, int B, const char* who);   // PP_ERR_NUMERIC for a flagged frame
+// result rows per frame in the handle's current class mode (pp_get_detection_rows)
+inline int det_rows(const pp_engine* e) {
+    return (e->class_nms == PP_CLASS_NMS_PER_CLASS ? e->ncls : 1) * e->cfg.nms_post_max_size;
+}
 int graph_bucket(const pp_engine* e, int max_n);
 bool graphs_enabled();
 // ---- pp_api.hip: the resident frames' state, one function per transition ----

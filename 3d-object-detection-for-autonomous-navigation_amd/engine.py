@@ -20,6 +20,7 @@ _STATUS = {1: "PP_ERR_ARG", 2: "PP_ERR_STATE", 3: "PP_ERR_HIP", 4: "PP_ERR_SHAPE
 PP_ERR_NUMERIC = 6
 _PRECISIONS = {"split_f16": 0, "f32": 1}
 _NMS_MODES = {"standup": _lib.PP_NMS_STANDUP, "rotated": _lib.PP_NMS_ROTATED}
+_CLASS_NMS = {"joint": _lib.PP_CLASS_NMS_JOINT, "per_class": _lib.PP_CLASS_NMS_PER_CLASS}
 
 
 class NumericError(RuntimeError):
@@ -215,6 +216,8 @@ class Engine:
         self.weights_loaded = False
         if d.use_rotate_nms:
             self.set_nms_mode("rotated")
+        if d.use_multi_class_nms:
+            self.set_class_nms("per_class")
         if weights is not None:
             self.load_weights(weights)
 
@@ -252,6 +255,32 @@ class Engine:
         self._check(self._lib.pp_get_nms_mode(self._h, ctypes.byref(v)), "pp_get_nms_mode")
         return {v_: k for k, v_ in _NMS_MODES.items()}[v.value]
 
+    # ---- one suppression pass for all classes, or one per class (pp_set_class_nms) ----
+    def set_class_nms(self, mode):
+        """'joint' (default: the reference's predict() -- an anchor's score is its largest class score, one top-100 and
+        one NMS serve all classes) or 'per_class' (model.second.use_multi_class_nms, which selects it at construction:
+        threshold, top-100, NMS and both caps run per class on that class's score alone; a frame's detections are class
+        0's kept boxes in descending score, then class 1's, ..., up to num_class * nms_post_max_size rows, and an anchor
+        may appear under several labels).  Takes effect from the next predict / detect; `detection_rows` follows it, and
+        the results of a pass run in the other mode can no longer be fetched."""
+        if mode not in _CLASS_NMS:
+            raise ValueError(f"mode must be one of {sorted(_CLASS_NMS)}")
+        self._check(self._lib.pp_set_class_nms(self._h, _CLASS_NMS[mode]), "pp_set_class_nms")
+
+    @property
+    def class_nms(self):
+        v = ctypes.c_int32(0)
+        self._check(self._lib.pp_get_class_nms(self._h, ctypes.byref(v)), "pp_get_class_nms")
+        return {v_: k for k, v_ in _CLASS_NMS.items()}[v.value]
+
+    @property
+    def detection_rows(self):
+        """Rows per frame of the arrays predict / detections / detect / bboxes return in the current class mode:
+        nms_post_max_size ('joint') or num_class * nms_post_max_size ('per_class')."""
+        v = ctypes.c_int32(0)
+        self._check(self._lib.pp_get_detection_rows(self._h, ctypes.byref(v)), "pp_get_detection_rows")
+        return v.value
+
     # ---- image boxes of the kept detections (pp_set_projection) ----
     def set_projection(self, p2):
         """p2 [4,4] (every frame) or [B,4,4] (frame b of a pass uses matrix b), or None: off (the default).  With it on,
@@ -275,9 +304,9 @@ class Engine:
         return bool(v.value)
 
     def bboxes(self, batch=None):
-        """[B, nms_post_max_size, 4] float64 image boxes (min u, min v, max u, max v) of the last pass, row i of frame b
+        """[B, detection_rows, 4] float64 image boxes (min u, min v, max u, max v) of the last pass, row i of frame b
         beside detection i; rows at or beyond the frame's count are zero.  Raises when that pass ran with projection off."""
-        post = self.d.nms_post_max_size
+        post = self.detection_rows
         out = np.zeros((self.max_batch, post, 4), dtype=np.float64)
         self._check(self._lib.pp_get_bboxes(self._h, _ptr(out)), "pp_get_bboxes")
         return out if batch is None else out[:batch]
@@ -373,7 +402,7 @@ class Engine:
         batch = box_preds.shape[0]
         if p2 is not None:
             self.set_projection(np.broadcast_to(np.asarray(p2, np.float64), (batch, 4, 4)))
-        post = self.d.nms_post_max_size
+        post = self.detection_rows
         dets = np.zeros((batch, post), dtype=DET_DTYPE)
         n = np.zeros((batch,), dtype=np.int32)
         m = np.ascontiguousarray(anchors_mask, dtype=np.uint8).reshape(batch, -1)
@@ -462,12 +491,14 @@ class Engine:
 
     def detections(self, out=None):
         """Results of the last detect_async (waits for it).  out: optional (dets, n) arrays to fill."""
-        B, post = self._batches()[1], self.d.nms_post_max_size
+        B, post = self._batches()[1], self.detection_rows
         if out is None:
             out = (np.zeros((max(B, 1), post), dtype=DET_DTYPE), np.zeros((max(B, 1),), dtype=np.int32))
         dets, n = out
         if dets.shape[0] < B or n.shape[0] < B:
             raise ValueError("detections(out=...): arrays smaller than the batch")
+        if dets.ndim != 2 or dets.shape[1] != post:
+            raise ValueError(f"detections(out=...): dets must have detection_rows = {post} rows per frame, got {dets.shape}")
         self._check(self._lib.pp_get_detections(self._h, _ptr(dets), _ptr(n)), "pp_get_detections")
         return dets, n
 

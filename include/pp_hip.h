@@ -35,7 +35,8 @@ extern "C" {
  * pp_train_step_sample_async, pp_train_step_sample; then pp_pc2_layout, pp_ingest_config, pp_ingest_pointcloud2,
  * pp_ingest_pointcloud2_async, pp_ingest_info; then pp_gtdb_build, pp_gtdb_count; then PP_CROP_BACK, pp_frustum_crop,
  * pp_frustum_crop_async, pp_frustum_crop_info; then pp_nms_mode, pp_set_nms_mode, pp_get_nms_mode, PP_RNMS_MAX_BOXES,
- * pp_rotate_nms; then pp_set_projection, pp_get_projection, pp_get_bboxes, pp_box3d_to_bbox. */
+ * pp_rotate_nms; then pp_set_projection, pp_get_projection, pp_get_bboxes, pp_box3d_to_bbox; then pp_class_nms,
+ * pp_set_class_nms, pp_get_class_nms, pp_get_detection_rows. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -64,6 +65,16 @@ enum pp_nms_mode {
                          * IoU > 0.5 */
     PP_NMS_ROTATED = 1  /* rotate_nms_kernel's rule (second/core/non_max_suppression/nms_gpu.py:419-452, shipped by the
                          * reference but never wired in): devRotateIoU of the decoded [x, y, w, l, r] */
+};
+
+/* How the detector's post-process treats more than one class (pp_set_class_nms) */
+enum pp_class_nms {
+    PP_CLASS_NMS_JOINT = 0,     /* default, the reference's predict() (model/voxelnet.py:1172-1286): an anchor's score is
+                                 * its largest class score, its label the argmax; one top-100 and one suppression pass
+                                 * serve all classes together */
+    PP_CLASS_NMS_PER_CLASS = 1  /* model.second.use_multi_class_nms, the branch the reference leaves as `pass`
+                                 * (model/voxelnet.py:1170-1171): the same pass once per class on that class's score
+                                 * alone -- threshold, top-100, suppression and both caps per class */
 };
 
 typedef struct pp_engine* pp_handle;
@@ -169,8 +180,8 @@ int pp_forward_voxels(pp_handle h, const float* voxels, const int32_t* num_point
 
 /* VoxelNet.predict(example, preds_dict) (model/voxelnet.py:1060-1390) on the
  * head maps.  anchors_mask [batch,A] u8; rect, trv2c [batch,16] row-major 4x4.
- * dets [batch * nms_post_max_size]; n_dets [batch] (0 == the reference's
- * all-None dict). */
+ * dets [batch * nms_post_max_size] (pp_get_detection_rows rows per frame after
+ * pp_set_class_nms); n_dets [batch] (0 == the reference's all-None dict). */
 int pp_predict(pp_handle h, const float* box_preds, const float* cls_preds, const float* dir_cls_preds,
                const uint8_t* anchors_mask, const float* rect, const float* trv2c, int32_t batch,
                pp_detection* dets, int32_t* n_dets);
@@ -259,6 +270,23 @@ int pp_get_projection(pp_handle h, int32_t* on);
  * stream first, and returns PP_ERR_NUMERIC where pp_get_detections would; PP_ERR_STATE when that pass ran with the
  * projection off or there are no results.  Rows at or beyond a frame's n_dets are not written. */
 int pp_get_bboxes(pp_handle h, double* bbox);
+/* Selects how this handle's post-process treats the classes (enum pp_class_nms): pp_predict and the fused path.  With
+ * PP_CLASS_NMS_PER_CLASS every class c = 0 .. num_class-1 goes through the whole pass by itself: candidates are the masked
+ * anchors whose class-c score passes nms_score_threshold, the top 100 of them by class-c score are decoded and suppressed
+ * (the rule of pp_set_nms_mode) over the first nms_pre_max_size, at most nms_post_max_size are kept, and each kept box
+ * gets label c.  A frame's detections are class 0's kept boxes in descending score, then class 1's, and so on; n_dets is
+ * their total, at most num_class * nms_post_max_size, and the same anchor may appear under several classes.  The result
+ * rows per frame follow the mode: see pp_get_detection_rows -- every buffer handed to pp_get_detections, pp_detect,
+ * pp_predict and pp_get_bboxes has that many rows per frame.  PP_ERR_NUMERIC is raised as in the joint mode.  Takes effect
+ * from the next pp_predict / pp_detect_async; results of a pass that ran in the other mode can no longer be fetched
+ * (PP_ERR_STATE) until a new pass has run.  With the default every output is what it was before the mode existed.
+ * PP_ERR_ARG for an unknown mode, PP_ERR_STATE while a training step is in flight (the mode then stays as it was).  The
+ * mode is part of what a captured pass is keyed on: a change captures once more. */
+int pp_set_class_nms(pp_handle h, int32_t mode);
+int pp_get_class_nms(pp_handle h, int32_t* mode);
+/* Rows per frame that pp_get_detections, pp_detect, pp_predict and pp_get_bboxes write in the handle's current mode:
+ * nms_post_max_size with PP_CLASS_NMS_JOINT, num_class * nms_post_max_size with PP_CLASS_NMS_PER_CLASS. */
+int pp_get_detection_rows(pp_handle h, int32_t* rows);
 /* Last-level-cache budget of a pass, in MiB (default 256, 0 = off).  Layers whose input + output maps exceed it are run
  * over sub-ranges of the batch's frames, a block's consecutive separable layers sub-range by sub-range, so that a layer
  * reads what the layer before has just written while it still sits in the 256 MB cache (KITTI-shaped B = 32: -5 % per
