@@ -17,8 +17,8 @@ _INCLUDE = os.path.join(os.path.dirname(_PKG), "include", "pp_hip.h")
 #   PP_HIP_LIB=libpp_hip_g.so PP_HIPCC_EXTRA="-g" python -c "import pp_amd; pp_amd._lib.build()"
 SO_PATH = os.path.join(_PKG, os.environ.get("PP_HIP_LIB", "libpp_hip.so"))
 _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
-SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_nms.hip", "api_project.hip", "api_class_nms.hip", "api_train.hip", "api_dataprep.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
-           "rotate_iou.hip", "rotate_nms.hip", "box_project.hip", "loss.hip", "optim.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip",
+SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_nms.hip", "api_project.hip", "api_class_nms.hip", "api_metrics.hip", "api_train.hip", "api_dataprep.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
+           "rotate_iou.hip", "rotate_nms.hip", "box_project.hip", "loss.hip", "metrics.hip", "optim.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip",
            "gt_database.hip", "eval_stats.hip", "frustum_crop.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
@@ -46,6 +46,7 @@ EXPORTS = [
     "pp_set_nms_mode", "pp_get_nms_mode", "pp_rotate_nms",
     "pp_set_projection", "pp_get_projection", "pp_get_bboxes", "pp_box3d_to_bbox",
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
+    "pp_head_metrics", "pp_set_train_metrics", "pp_get_train_metrics_enabled", "pp_get_train_metrics",
 ]
 
 
@@ -151,6 +152,7 @@ class PPIngestConfig(ctypes.Structure):
 
 
 PP_CROP_BACK = 1      # pp_frustum_crop* flags: bit 0
+PP_METRICS_COUNTS = 32      # int64 values of pp_head_metrics / pp_get_train_metrics
 PP_CLASS_NMS_JOINT, PP_CLASS_NMS_PER_CLASS = 0, 1      # enum pp_class_nms
 PP_NMS_STANDUP, PP_NMS_ROTATED = 0, 1      # enum pp_nms_mode
 
@@ -367,6 +369,10 @@ def lib():
     L.pp_set_class_nms.argtypes = [vp, i32]
     L.pp_get_class_nms.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_get_detection_rows.argtypes = [vp, ctypes.POINTER(i32)]
+    L.pp_head_metrics.argtypes = [vp, vp, i32, f32p, vp]
+    L.pp_set_train_metrics.argtypes = [vp, i32]
+    L.pp_get_train_metrics_enabled.argtypes = [vp, ctypes.POINTER(i32)]
+    L.pp_get_train_metrics.argtypes = [vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)  # raises AttributeError if the symbol is not exported
         if name not in ("pp_last_error", "pp_layer_tag"):

@@ -140,6 +140,12 @@ int train_step_launch(pp_engine* e, const float* params_dev, float* grads_dev, f
     cx.head = e->d_head; cx.dhead = e->loss.head_grad;
     LossParams lp;
     fill_loss_params(e, lc, batch, lp);
+    cx.metrics = nullptr;
+    if (e->metrics.on) {      // counted inside the second half, right behind the loss (pp_set_train_metrics)
+        if ((st = ensure_metrics(e))) return st;
+        fill_metrics_params(e, batch, e->metrics.step);
+        cx.metrics = &e->metrics.step;
+    }
     // the step in two halves: 1 = voxelise + forward, 2 = loss + backward
     auto enqueue = [&](int max_n, int phase) -> int {
         if (phase & 1) {
@@ -155,7 +161,7 @@ int train_step_launch(pp_engine* e, const float* params_dev, float* grads_dev, f
         const bool hit = tg.exec != nullptr && tg.exec_bwd != nullptr && tg.batch == batch && tg.bucket == bucket &&
                          tg.zc == (e->zc ? 1 : 0) && tg.params == params_dev && tg.grads == grads_dev &&
                          tg.state == state_dev && memcmp(&tg.loss, lc, sizeof(pp_loss_config)) == 0 &&
-                         tg.frozen == t->plan.frozen;
+                         tg.frozen == t->plan.frozen && tg.metrics == e->metrics.on;
         if (!hit) {
             if (tg.exec || tg.exec_bwd) {
                 HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -185,6 +191,7 @@ int train_step_launch(pp_engine* e, const float* params_dev, float* grads_dev, f
                 tg.batch = batch; tg.bucket = bucket; tg.zc = e->zc ? 1 : 0;
                 tg.params = params_dev; tg.grads = grads_dev; tg.state = state_dev; tg.loss = *lc;
                 tg.frozen = t->plan.frozen;
+                tg.metrics = e->metrics.on;
                 ++t->n_captures;
             } else {
                 if (tg.exec) (void)hipGraphExecDestroy(tg.exec);
@@ -216,6 +223,9 @@ int train_step_launch(pp_engine* e, const float* params_dev, float* grads_dev, f
         return fail(e, PP_ERR_HIP, "pp_train_step: hipHostMalloc failed");
     }
     HIPCHK(e, hipMemcpyAsync(e->h_train_losses, e->loss.out, 8 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (e->metrics.on)
+        HIPCHK(e, hipMemcpyAsync(e->metrics.h_counts, e->metrics.counts, PP_METRICS_COUNTS * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
+    e->metrics.step_counted = e->metrics.on;
     // this input buffer (and its zero-copy descriptor) is free again once the step is through: the NEXT batch may be
     // uploaded into the other one while this step runs (pp_upload_points_async between _async and _wait)
     HIPCHK(e, hipEventRecord(e->ev_read[e->in_buf], e->stream));

@@ -303,6 +303,21 @@ struct LossParams {
 int loss_blocks(int npx);
 int launch_head_loss(const LossParams& p, hipStream_t s);   // 0 or PP_ERR_UNSUPPORTED (anchors per pixel > 3)
 
+// metrics.hip: training metrics at the head map -- accuracy and precision / recall counts of one step
+#define PP_METRICS_NTHRESH 7
+struct MetricsParams {
+    int batch;
+    int64_t A;             // anchors per frame (= npx * napl)
+    int npx, napl, ncls;
+    const float* logits;   // class logit c of anchor r of pixel px of frame b: [(b * npx + px) * row_stride + col_off + r * ncls + c]
+    int row_stride, col_off;   // the head map: PP_HEAD_COLS, napl * 7; a plain [batch][A][ncls] array: napl * ncls, 0
+    const int* labels;     // [batch][A]  (>0 class, 0 background, -1 ignored)
+    int* partials;         // [batch * metrics_blocks(npx)][PP_METRICS_COUNTS] scratch
+    long long* counts;     // [PP_METRICS_COUNTS] out (pp_hip.h: acc_hit, n_pos, n_neg, tp[7], fp[7], then zeros)
+};
+int metrics_blocks(int npx);
+int launch_head_metrics(const MetricsParams& p, hipStream_t s);   // 0 or PP_ERR_UNSUPPORTED (as launch_head_loss)
+
 // optim.hip: AdamW update of one flat parameter buffer
 void launch_adamw(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1, float beta2,
                   float eps, float wd, hipStream_t s);

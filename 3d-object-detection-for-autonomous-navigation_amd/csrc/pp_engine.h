@@ -2,7 +2,8 @@
 // helpers and what one unit calls in another.  pp_api.hip: lifetime, weights, feeds, the inference pipeline;
 // api_ingest.hip: PointCloud2 ingest; api_crop.hip: the frustum crop; api_train.hip: loss, training step, optimizer; api_dataprep.hip: targets,
 // augmentation, GT sampling, object database; api_eval.hip: the AP evaluator (needs no handle); api_nms.hip: the detector's NMS rule and the standalone rotated NMS;
-// api_project.hip: the detector's image boxes and the standalone projection; api_class_nms.hip: joint / per-class suppression.
+// api_project.hip: the detector's image boxes and the standalone projection; api_class_nms.hip: joint / per-class suppression;
+// api_metrics.hip: the training metrics' counts.
 #pragma once
 
 #include <cmath>
@@ -213,6 +214,16 @@ struct pp_engine {
         int batch = 0;                     // frames of the last crop (pp_frustum_crop_info)
     } crop;
 
+    struct Metrics {                       // training metrics (pp_head_metrics / pp_set_train_metrics; api_metrics.hip: ensure_metrics)
+        bool on = false;                   // pp_set_train_metrics: the following steps count (part of a training graph's key)
+        int* partials = nullptr;           // [B * metrics_blocks(H' * W')][PP_METRICS_COUNTS]
+        long long* counts = nullptr;       // [PP_METRICS_COUNTS]
+        long long* h_counts = nullptr;     // pinned twin: a step's counts travel behind its losses
+        float* logits = nullptr;           // [B][A][ncls] the cls_preds handed to pp_head_metrics (allocated on first use)
+        bool step_counted = false;         // the last launched step ran with the switch on (pp_get_train_metrics)
+        MetricsParams step;                // what that step's launch reads (TrainCtx::metrics)
+    } metrics;
+
     // training step (train.hip): shapes, plan (the flat layout among it) and device buffers, set up by the first
     // pp_train_* call
     struct TrainState {
@@ -230,6 +241,7 @@ struct pp_engine {
             const void *params = nullptr, *grads = nullptr, *state = nullptr;
             pp_loss_config loss;
             std::vector<unsigned char> frozen;     // TrainPlan::frozen it was captured with
+            bool metrics = false;                  // pp_set_train_metrics it was captured with
         } graph[2];
         int last_batch = 0;    // frames of the last step (pp_train_fetch_decisions)
         int graph_state = 0;   // -1: capture failed once, plain launches from then on
@@ -359,6 +371,8 @@ int resident_points(pp_engine* e, int batch, hipStream_t s, bool materialise, co
 int ensure_spare_pts(pp_engine* e);
 
 int ensure_loss_buffers(pp_engine* e);                  // api_train.hip
+int ensure_metrics(pp_engine* e);                       // api_metrics.hip
+void fill_metrics_params(pp_engine* e, int batch, MetricsParams& p);   // ... on the handle's head map and loss.labels
 // ---- api_dataprep.hip: what the fused training steps (api_train.hip) queue ----
 int check_gt(pp_engine* e, const char* who, const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts,
              int batch, const pp_target_config* tc, int64_t* total);

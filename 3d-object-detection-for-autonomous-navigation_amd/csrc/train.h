@@ -136,6 +136,8 @@ struct TrainCtx {
     // (canvas, Z of in-block layers, A of block-final ones) carry a NaN header in front.
     unsigned short* pw16;
     unsigned short* head_w16;   // the packed head matrix [CC][32] in the same form
+    // pp_set_train_metrics: launched right behind the loss on the step's head map and labels (NULL: off, nothing added)
+    const MetricsParams* metrics = nullptr;
 };
 
 TrainPlan train_plan(const TrainShape& s, int max_batch);

@@ -2603,6 +2603,8 @@ int train_step(const TrainCtx& cx, const TrainShape& s, const TrainPlan& plan, c
     lp.head_grad = cx.dhead;
     int rc = launch_head_loss(lp, cx.stream);
     if (rc) return rc;
+    // the step's metrics (pp_set_train_metrics): a pure read of the head map and the labels the loss has just read
+    if (cx.metrics && (rc = launch_head_metrics(*cx.metrics, cx.stream))) return rc;
 
     // ---------------- backward ----------------
     // frozen tensors: their gradient entries are 0 (nothing below writes them; the all-reduce and the optimizer see

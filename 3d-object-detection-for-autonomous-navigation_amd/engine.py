@@ -749,6 +749,46 @@ class Engine:
                 out["dir_cls_preds_grad"] = grad[:, :, nb + nc:nb + nc + 2 * na].reshape(batch, hh, hw, 2 * na)
         return out
 
+    # ---- training metrics (f8) ----
+    def head_metrics(self, labels, cls_preds=None):
+        """The monitoring counts of one step (pp_head_metrics; libraries/metrics.py's Accuracy and PrecisionRecall,
+        metrics.py here): labels [B, A] int32 against the class logits of the head map the last forward pass or training
+        step left on the device, or against cls_preds [B, A, num_class] (any shape of that size) when given.  Returns
+        metrics.unpack_counts' dict (acc_hit, n_pos, n_neg, tp, fp, fn, tn) plus "counts", the raw int64[32]."""
+        from . import metrics as _metrics
+        labels = _i32(np.asarray(labels))
+        batch = labels.shape[0]
+        if labels.shape != (batch, self.d.num_anchors):
+            raise ValueError(f"labels must be [B, {self.d.num_anchors}]")
+        if cls_preds is not None:
+            cls_preds = _f32(np.asarray(cls_preds))
+            if cls_preds.size != batch * self.d.num_anchors * self.d.num_class or cls_preds.shape[0] != batch:
+                raise ValueError(f"cls_preds must hold [B, {self.d.num_anchors}, {self.d.num_class}] logits")
+        counts = np.zeros(_lib.PP_METRICS_COUNTS, np.int64)
+        self._check(self._lib.pp_head_metrics(self._h, _ptr(labels), batch, _ptr(cls_preds) if cls_preds is not None else None,
+                                              _ptr(counts)), "pp_head_metrics")
+        out = _metrics.unpack_counts(counts)
+        out["counts"] = counts
+        return out
+
+    def set_train_metrics(self, on):
+        """Count the monitoring metrics inside every following training step (pp_set_train_metrics); off by default."""
+        self._check(self._lib.pp_set_train_metrics(self._h, 1 if on else 0), "pp_set_train_metrics")
+
+    @property
+    def train_metrics(self):
+        """Whether training steps count their metrics (pp_get_train_metrics_enabled)."""
+        v = ctypes.c_int32(0)
+        self._check(self._lib.pp_get_train_metrics_enabled(self._h, ctypes.byref(v)), "pp_get_train_metrics_enabled")
+        return bool(v.value)
+
+    def train_metrics_counts(self):
+        """int64[32] counts of the last training step, after train_step_wait() (pp_get_train_metrics); raises when that
+        step ran with the metrics off."""
+        counts = np.zeros(_lib.PP_METRICS_COUNTS, np.int64)
+        self._check(self._lib.pp_get_train_metrics(self._h, _ptr(counts)), "pp_get_train_metrics")
+        return counts
+
     # ---- training step (f3) ----
     def train_layout(self):
         """[(name, offset, size, is_state)] of the flat parameter / BatchNorm-state buffers (pp_train_layout)."""

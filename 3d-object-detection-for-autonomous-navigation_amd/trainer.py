@@ -7,6 +7,8 @@
     trainer.weights()                                          # Keras-layout dict (Engine.load_weights, save_npz)
     trainer = Trainer(config, weights, frozen="reference")     # fine-tuning with the early layers frozen
     trainer.set_trainable(False)                               # ... the reference's set_trainable(net, False)
+    trainer = Trainer(config, weights, metrics=True)           # every step counts accuracy / precision / recall on the GPU
+    trainer.metrics(dist)                                      # ... the reference's update_metrics dict (metrics.py)
 
 What runs where: the frames are uploaded and voxelised by the engine, `pp_train_step` (csrc/train.hip) runs the
 training-mode forward pass, the loss and the backward pass and leaves the gradients of all trainable tensors in one
@@ -116,7 +118,7 @@ class TrainBatch:
 
 class Trainer:
     def __init__(self, config, weights, max_batch=None, max_points_per_frame=32768, device=0, learning_rate=None,
-                 weight_decay=None, augment=None, seed=None, frozen=None, gt_database=None, sampler=None):
+                 weight_decay=None, augment=None, seed=None, frozen=None, gt_database=None, sampler=None, metrics=False):
         import random
         import torch
         from . import augment as _augment
@@ -195,6 +197,14 @@ class Trainer:
         self.optimizer = optim.AdamW(self.params, learning_rate, weight_decay)
         self._frozen = ()
         self.set_frozen(frozen)
+        # metrics: True = every step counts the reference's monitoring metrics on the GPU (csrc/metrics.hip) and feeds a
+        # metrics.TrainMetrics; no configuration key turns it on.  metrics_steps is how often the reference's loop would
+        # report them (train_config.net_metrics_steps, 500 in the shipped YAML): informational
+        from . import metrics as _metrics
+        self.metrics_steps = int(tc["net_metrics_steps"]) if tc and "net_metrics_steps" in tc else 500
+        self._metrics = _metrics.TrainMetrics() if metrics else None
+        if metrics:
+            self.engine.set_train_metrics(True)
 
     # ---- frozen layers (the reference's set_trainable) ----
     @property
@@ -452,7 +462,26 @@ class Trainer:
             used = self.engine.gt_sample_info()["round_used"]
             self.frames_left_without_boxes += int((used[self._boxless] < 0).sum())
         self._boxless = None
+        if self._metrics is not None:
+            self._metrics.update(self.engine.train_metrics_counts(), losses["cls_loss_reduced"], losses["loc_loss_reduced"])
         return losses
+
+    # ---- monitoring (the reference's update_metrics) ----
+    def metrics(self, dist=None):
+        """The reference's metrics dict (libraries/metrics.py:187-196: cls_loss, cls_loss_rt, loc_loss, loc_loss_rt,
+        rpn_acc, prec@10, rec@10, ... rec@95) over the steps since the last reset_metrics(); with `dist`
+        (torch.distributed) the totals of all ranks.  Needs Trainer(..., metrics=True)."""
+        if self._metrics is None:
+            raise RuntimeError("Trainer(..., metrics=True) counts the metrics; this trainer was built without")
+        if dist is not None and dist.is_initialized() and dist.get_world_size() > 1:
+            dev = self.device if dist.get_backend() == "nccl" else None
+            return self._metrics.allreduce(dist, device=dev).result()
+        return self._metrics.result()
+
+    def reset_metrics(self):
+        if self._metrics is None:
+            raise RuntimeError("Trainer(..., metrics=True) counts the metrics; this trainer was built without")
+        self._metrics.reset()
 
     def _engine_stream(self):
         """torch's view of the engine's own stream: the all-reduce and the AdamW kernel are enqueued THERE, behind the

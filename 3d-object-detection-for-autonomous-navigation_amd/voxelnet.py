@@ -35,7 +35,7 @@ def _np(x):
 
 class VoxelNet:
     def __init__(self, config, writer=None, training=False, max_batch=None, max_points_per_frame=32768, device=0,
-                 augment=None, seed=None):
+                 augment=None, seed=None, metrics=False):
         self.config = config
         self.training = bool(training)
         self.d = Derived(config)
@@ -44,7 +44,9 @@ class VoxelNet:
         self.trainer = None
         self._ctor = dict(max_batch=max_batch or self.batch_size, max_points_per_frame=max_points_per_frame, device=device)
         # training only: the loader's augmentation on the GPU (Trainer's augment= / seed=)
-        self._train_kw = dict(augment=augment, seed=seed)
+        self._train_kw = dict(augment=augment, seed=seed, metrics=bool(metrics))
+        if not self.training and metrics:
+            raise ValueError("metrics is a training option: build the net with training=True")
         if not self.training and augment:
             raise ValueError("augment is a training option: build the net with training=True")
         if self.training:
@@ -107,7 +109,7 @@ class VoxelNet:
         gt_classes per frame or None: all 1; assigned on the GPU).  With augmentation on (VoxelNet(..., augment=True,
         seed=...)) the frames and boxes are augmented on the GPU first; gt_valid marks the boxes that are only obstacles.
         Returns the reference's loss scalars
-        (model/voxelnet.py:1032-1043)."""
+        (model/voxelnet.py:1032-1043); a net built with metrics=True adds "metrics", the reference's update_metrics dict."""
         if self.trainer is None:
             raise RuntimeError("VoxelNet(training=True): load_weights() with the initial values first")
         dense = labels is not None or reg_targets is not None
@@ -119,6 +121,9 @@ class VoxelNet:
                                             gt_valid=gt_valid)
         if apply:
             self.apply_gradients(dist)
+        if self._train_kw["metrics"]:      # the reference's update_metrics dict over the steps so far (Trainer.metrics)
+            out = dict(out)
+            out["metrics"] = self.trainer.metrics(dist)
         return out
 
     def set_trainable(self, trainable):

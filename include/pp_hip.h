@@ -36,7 +36,8 @@ extern "C" {
  * pp_ingest_pointcloud2_async, pp_ingest_info; then pp_gtdb_build, pp_gtdb_count; then PP_CROP_BACK, pp_frustum_crop,
  * pp_frustum_crop_async, pp_frustum_crop_info; then pp_nms_mode, pp_set_nms_mode, pp_get_nms_mode, PP_RNMS_MAX_BOXES,
  * pp_rotate_nms; then pp_set_projection, pp_get_projection, pp_get_bboxes, pp_box3d_to_bbox; then pp_class_nms,
- * pp_set_class_nms, pp_get_class_nms, pp_get_detection_rows. */
+ * pp_set_class_nms, pp_get_class_nms, pp_get_detection_rows; then PP_METRICS_COUNTS, pp_head_metrics,
+ * pp_set_train_metrics, pp_get_train_metrics_enabled, pp_get_train_metrics. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -782,6 +783,34 @@ int pp_train_graph_stats(pp_handle h, int32_t* captures, int32_t* replays);
  * everything.  PP_ERR_ARG for an unknown or repeated name, or when every unit would be frozen (the freeze then stays
  * as it was).  The freeze is part of what a captured step graph is keyed on: a change re-captures it once. */
 int pp_train_set_frozen(pp_handle h, const char* const* units, int32_t n);
+
+/* ---- training metrics -------------------------------------------------------------------- */
+
+#define PP_METRICS_COUNTS 32 /* int64 values per result: [0] acc_hit, [1] n_pos, [2] n_neg, [3..9] tp, [10..16] fp at the
+                              * score thresholds 0.1 0.3 0.5 0.7 0.8 0.9 0.95 (as float32); the rest 0 */
+
+/* The per-step counts behind the reference's monitoring block (libraries/metrics.py: Accuracy.call :60-83,
+ * PrecisionRecall.call and _calc_binary_metrics :103-161, as update_metrics :164-198 calls them with weights = cared),
+ * for encode_background_as_zeros and use_sigmoid_score both true.  Per anchor, in float32: s_c = 1 / (1 + exp(-x_c)),
+ * score = max_c s_c; predicted label = (first maximum of x_c) + 1 where any s_c > 0.5, else 0.  acc_hit counts predicted
+ * label == label over all anchors (an ignored anchor, label -1, never matches), n_pos label > 0, n_neg label == 0,
+ * tp[i] label > 0 and score > t_i, fp[i] label == 0 and score > t_i; fn[i] = n_pos - tp[i], tn[i] = n_neg - fp[i].  A NaN
+ * logit compares false everywhere.  labels [batch][A] int32 (>0 class, 0 background, -1 ignored).  cls_preds NULL: the head
+ * map the last forward pass or training step of this handle left on the device, as pp_head_loss reads it; otherwise
+ * [batch][A][num_class] float32 logits, which are uploaded and counted instead.  counts [PP_METRICS_COUNTS].  Integer
+ * sums: the same input gives the same bytes on every run.  Host pointers; synchronous.  PP_ERR_STATE while a training step
+ * is in flight, PP_ERR_UNSUPPORTED for the shapes pp_head_loss refuses. */
+int pp_head_metrics(pp_handle h, const int32_t* labels, int32_t batch, const float* cls_preds, int64_t* counts);
+
+/* on = 1: every following training step (pp_train_step*, all four entry points) counts the same on the labels it trains on,
+ * inside its captured graph right behind the loss (two more graph nodes); on = 0, the default: nothing is added and every
+ * output is what it was before the switch existed.  The switch is part of what a captured step graph is keyed on: a
+ * change re-captures it once.  PP_ERR_ARG for another value, PP_ERR_STATE while a step is in flight. */
+int pp_set_train_metrics(pp_handle h, int32_t on);
+int pp_get_train_metrics_enabled(pp_handle h, int32_t* on);
+/* The counts of the last step, after its pp_train_step_wait.  PP_ERR_STATE when that step ran with the switch off, when no
+ * step has run, or while one is in flight. */
+int pp_get_train_metrics(pp_handle h, int64_t* counts);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
