@@ -18,7 +18,7 @@ _INCLUDE = os.path.join(os.path.dirname(_PKG), "include", "pp_hip.h")
 SO_PATH = os.path.join(_PKG, os.environ.get("PP_HIP_LIB", "libpp_hip.so"))
 _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
 SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_nms.hip", "api_project.hip", "api_class_nms.hip", "api_metrics.hip", "api_train.hip", "api_dataprep.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
-           "rotate_iou.hip", "rotate_nms.hip", "box_project.hip", "loss.hip", "metrics.hip", "optim.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip",
+           "rotate_iou.hip", "rotate_nms.hip", "box_project.hip", "loss.hip", "metrics.hip", "optim.hip", "grad_clip.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip",
            "gt_database.hip", "eval_stats.hip", "frustum_crop.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
@@ -47,6 +47,7 @@ EXPORTS = [
     "pp_set_projection", "pp_get_projection", "pp_get_bboxes", "pp_box3d_to_bbox",
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
     "pp_head_metrics", "pp_set_train_metrics", "pp_get_train_metrics_enabled", "pp_get_train_metrics",
+    "pp_grad_clip_workspace_bytes", "pp_grad_norm_device", "pp_adamw_step_clipped_device",
 ]
 
 
@@ -109,6 +110,14 @@ class PPAugmentConfig(ctypes.Structure):
     ]
 
 
+class PPGradClipConfig(ctypes.Structure):
+    _fields_ = [
+        ("mode", ctypes.c_int32),
+        ("clip", ctypes.c_float),
+        ("skip_nonfinite", ctypes.c_int32),
+    ]
+
+
 class PPGtSampleConfig(ctypes.Structure):
     _fields_ = [
         ("max_point_collision", ctypes.c_int32),
@@ -155,6 +164,7 @@ PP_CROP_BACK = 1      # pp_frustum_crop* flags: bit 0
 PP_METRICS_COUNTS = 32      # int64 values of pp_head_metrics / pp_get_train_metrics
 PP_CLASS_NMS_JOINT, PP_CLASS_NMS_PER_CLASS = 0, 1      # enum pp_class_nms
 PP_NMS_STANDUP, PP_NMS_ROTATED = 0, 1      # enum pp_nms_mode
+PP_CLIP_NONE, PP_CLIP_VALUE, PP_CLIP_NORM, PP_CLIP_GLOBAL_NORM = 0, 1, 2, 3      # enum pp_grad_clip_mode
 
 
 class PPDetection(ctypes.Structure):
@@ -373,6 +383,11 @@ def lib():
     L.pp_set_train_metrics.argtypes = [vp, i32]
     L.pp_get_train_metrics_enabled.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_get_train_metrics.argtypes = [vp, vp]
+    L.pp_grad_clip_workspace_bytes.argtypes = [i64, i32, i32, ctypes.POINTER(i64)]
+    L.pp_grad_norm_device.argtypes = [ctypes.c_int, vp, vp, i64, vp, i32, vp, i32, vp]
+    L.pp_adamw_step_clipped_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, i64, vp, i32, vp, i32,
+                                               ctypes.POINTER(PPGradClipConfig), vp, ctypes.c_float, ctypes.c_float,
+                                               ctypes.c_float, ctypes.c_float, ctypes.c_float]
     for name in EXPORTS:
         fn = getattr(L, name)  # raises AttributeError if the symbol is not exported
         if name not in ("pp_last_error", "pp_layer_tag"):

@@ -1,5 +1,6 @@
 // C-ABI, training: the head loss (loss.hip), the training step (train.hip) with its graph cache
-// and its fused variants (targets, augmentation, GT sampling: api_dataprep.hip's enqueue_*), the AdamW update (optim.hip).
+// and its fused variants (targets, augmentation, GT sampling: api_dataprep.hip's enqueue_*), the AdamW update (optim.hip),
+// gradient clipping and the non-finite guard in front of it (grad_clip.hip).
 #include "pp_engine.h"
 
 int ensure_loss_buffers(pp_engine* e) {
@@ -243,6 +244,26 @@ int step_and_wait(pp_engine* e, const char* who, float* losses, Launch launch) {
     if (!losses) return fail(e, PP_ERR_ARG, "%s: null argument", who);
     const int st = launch();
     return st ? st : pp_train_step_wait(e, losses);
+}
+
+// pp_grad_norm_device / pp_adamw_step_clipped_device: everything the kernels index with is checked here
+int check_clip_table(const char* who, int64_t n, const int64_t* segments, int32_t n_segments, const int32_t* groups,
+                     int32_t n_groups, const void* workspace, bool reduce) {
+    if (n < 0 || n_segments < 0 || n_groups < 1 || (n_segments > 0 && !segments))
+        return fail(nullptr, PP_ERR_ARG, "%s: bad argument", who);
+    if (!groups && n_groups != 1) return fail(nullptr, PP_ERR_ARG, "%s: groups is NULL but n_groups is %d", who, n_groups);
+    for (int32_t i = 0; i < n_segments; ++i) {
+        const int64_t off = segments[2 * i], size = segments[2 * i + 1];
+        if (off < 0 || size < 0 || off > n || size > n - off)
+            return fail(nullptr, PP_ERR_ARG, "%s: segment %d lies outside [0, %lld)", who, i, (long long)n);
+        if (groups && (groups[i] < 0 || groups[i] >= n_groups))
+            return fail(nullptr, PP_ERR_ARG, "%s: segment %d is in group %d of %d", who, i, groups[i], n_groups);
+    }
+    if (!reduce) return PP_OK;
+    if (!workspace || ((uintptr_t)workspace & 7)) return fail(nullptr, PP_ERR_ARG, "%s: workspace is NULL or not 8-byte aligned", who);
+    if (grad_clip_partials(segments, n_segments) > grad_clip_layout(n, n_segments, n_groups).max_partials)
+        return fail(nullptr, PP_ERR_ARG, "%s: segments overlap (more partial sums than the workspace holds)", who);
+    return PP_OK;
 }
 
 }  // namespace
@@ -528,6 +549,47 @@ int pp_adamw_step_segments_device(int device, void* stream, float* params, const
     launch_adamw_segments(params, grads, m, v, segments, n_segments, lr_t, beta1, beta2, epsilon, weight_decay,
                           (hipStream_t)stream);
     if (hipGetLastError() != hipSuccess) return fail(nullptr, PP_ERR_HIP, "pp_adamw_step_segments_device: launch failed");
+    return PP_OK;
+}
+
+int pp_grad_clip_workspace_bytes(int64_t n_floats, int32_t n_segments, int32_t n_groups, int64_t* bytes) {
+    if (n_floats < 0 || n_segments < 0 || n_groups < 1 || !bytes)
+        return fail(nullptr, PP_ERR_ARG, "pp_grad_clip_workspace_bytes: bad argument");
+    *bytes = grad_clip_layout(n_floats, n_segments, n_groups).bytes;
+    return PP_OK;
+}
+
+int pp_grad_norm_device(int device, void* stream, const float* grads, int64_t n, const int64_t* segments,
+                        int32_t n_segments, const int32_t* groups, int32_t n_groups, void* workspace) {
+    const char* who = "pp_grad_norm_device";
+    if (n > 0 && !grads) return fail(nullptr, PP_ERR_ARG, "%s: bad argument", who);
+    int st = check_clip_table(who, n, segments, n_segments, groups, n_groups, workspace, true);
+    if (st) return st;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, PP_ERR_HIP, "%s: hipSetDevice(%d) failed", who, device);
+    launch_grad_norm(grads, segments, n_segments, groups, n_groups, PP_CLIP_NONE, 0.f, 0, workspace, n, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, PP_ERR_HIP, "%s: launch failed", who);
+    return PP_OK;
+}
+
+int pp_adamw_step_clipped_device(int device, void* stream, float* params, const float* grads, float* m, float* v,
+                                 int64_t n, const int64_t* segments, int32_t n_segments, const int32_t* groups,
+                                 int32_t n_groups, const pp_grad_clip_config* cfg, void* workspace, float lr_t,
+                                 float beta1, float beta2, float epsilon, float weight_decay) {
+    const char* who = "pp_adamw_step_clipped_device";
+    if (!cfg || (n > 0 && (!params || !grads || !m || !v))) return fail(nullptr, PP_ERR_ARG, "%s: bad argument", who);
+    if (cfg->mode < PP_CLIP_NONE || cfg->mode > PP_CLIP_GLOBAL_NORM) return fail(nullptr, PP_ERR_ARG, "%s: unknown mode %d", who, cfg->mode);
+    if (cfg->mode != PP_CLIP_NONE && !(cfg->clip > 0.f && std::isfinite(cfg->clip)))
+        return fail(nullptr, PP_ERR_ARG, "%s: clip must be positive and finite", who);
+    const int skip = cfg->skip_nonfinite ? 1 : 0;
+    const bool reduce = cfg->mode != PP_CLIP_VALUE || skip;          // (monitor mode takes the norms, too)
+    int st = check_clip_table(who, n, segments, n_segments, groups, n_groups, workspace, reduce);
+    if (st) return st;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, PP_ERR_HIP, "%s: hipSetDevice(%d) failed", who, device);
+    if (reduce)
+        launch_grad_norm(grads, segments, n_segments, groups, n_groups, cfg->mode, cfg->clip, skip, workspace, n, (hipStream_t)stream);
+    launch_adamw_segments_clipped(params, grads, m, v, segments, n_segments, groups, n_groups, cfg->mode, cfg->clip, skip,
+                                  reduce ? workspace : nullptr, lr_t, beta1, beta2, epsilon, weight_decay, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, PP_ERR_HIP, "%s: launch failed", who);
     return PP_OK;
 }
 

@@ -61,13 +61,27 @@ void launch_adamw(float* w, const float* g, float* m, float* v, int64_t n, float
 // arithmetic is k_adamw's, operation for operation, so an updated entry is bit-identical to a full-buffer launch's.
 // Segments need not start on a 16-byte boundary: a workgroup owns 1 024 consecutive floats of one segment and a thread
 // every 256th of them (coalesced 4-byte accesses; the update stays HBM-bound).
-#define PP_ADAMW_SEGS 64
-struct AdamwSegs {
-    int64_t off[PP_ADAMW_SEGS], size[PP_ADAMW_SEGS];
-    int block_start[PP_ADAMW_SEGS + 1];
-    int n;
-};
+int adamw_fill_table(AdamwSegs& t, const int64_t* seg, int nseg, int* done, int* src) {
+    memset(&t, 0, sizeof(t));
+    int blocks = 0;
+    while (*done < nseg && t.n < PP_ADAMW_SEGS) {
+        const int64_t size = seg[2 * *done + 1];
+        if (size > 0) {
+            t.off[t.n] = seg[2 * *done];
+            t.size[t.n] = size;
+            t.block_start[t.n] = blocks;
+            if (src) src[t.n] = *done;
+            blocks += (int)((size + 1023) / 1024);
+            ++t.n;
+        }
+        ++*done;
+    }
+    for (int k = t.n; k <= PP_ADAMW_SEGS; ++k) t.block_start[k] = blocks;
+    return blocks;
+}
 
+// (k_adamw_seg_clip in grad_clip.hip is this kernel on a clipped gradient: same table, same map, same operations --
+// a change here belongs there, too; tests/test_gpu_grad_clip.py holds the two to bit-identity)
 __global__ __launch_bounds__(256) void k_adamw_seg(float* __restrict__ w, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, AdamwSegs t,
                                                    float lr_t, float beta1, float beta2, float eps, float wd) {
@@ -94,20 +108,7 @@ void launch_adamw_segments(float* w, const float* g, float* m, float* v, const i
                            float beta1, float beta2, float eps, float wd, hipStream_t s) {
     for (int done = 0; done < nseg;) {
         AdamwSegs t;
-        memset(&t, 0, sizeof(t));
-        int blocks = 0;
-        while (done < nseg && t.n < PP_ADAMW_SEGS) {
-            const int64_t size = seg[2 * done + 1];
-            if (size > 0) {
-                t.off[t.n] = seg[2 * done];
-                t.size[t.n] = size;
-                t.block_start[t.n] = blocks;
-                blocks += (int)((size + 1023) / 1024);
-                ++t.n;
-            }
-            ++done;
-        }
-        for (int k = t.n; k <= PP_ADAMW_SEGS; ++k) t.block_start[k] = blocks;
+        const int blocks = adamw_fill_table(t, seg, nseg, &done, nullptr);
         if (blocks > 0)
             PP_LAUNCH("k_adamw_seg", k_adamw_seg, dim3((unsigned)blocks), dim3(256), 0, s, w, g, m, v, t, lr_t, beta1,
                       beta2, eps, wd);

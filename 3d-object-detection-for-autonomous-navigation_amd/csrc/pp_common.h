@@ -322,8 +322,34 @@ int launch_head_metrics(const MetricsParams& p, hipStream_t s);   // 0 or PP_ERR
 void launch_adamw(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1, float beta2,
                   float eps, float wd, hipStream_t s);
 // ... of the (offset, size) segments seg[2 * i], seg[2 * i + 1] of it only (host array of nseg pairs)
+#define PP_ADAMW_SEGS 64      // segments per update launch (the table travels as a kernel argument)
+struct AdamwSegs {
+    int64_t off[PP_ADAMW_SEGS], size[PP_ADAMW_SEGS];
+    int block_start[PP_ADAMW_SEGS + 1];      // a workgroup owns 1 024 consecutive floats of one segment
+    int n;
+};
+// The table of one update launch, shared by k_adamw_seg and k_adamw_seg_clip (grad_clip.hip): the next non-empty
+// segments from seg[*done] on, PP_ADAMW_SEGS at most; *done advances past what was taken (empty ones included), src[j]
+// (may be NULL) is the index in `seg` of table entry j.  Returns the launch's workgroups.
+int adamw_fill_table(AdamwSegs& t, const int64_t* seg, int nseg, int* done, int* src);
 void launch_adamw_segments(float* w, const float* g, float* m, float* v, const int64_t* seg, int nseg, float lr_t,
                            float beta1, float beta2, float eps, float wd, hipStream_t s);
+
+// grad_clip.hip: gradient norms per group of segments (float64 sums in a fixed order) and the AdamW update on the
+// clipped gradient.  The caller's workspace: the statistics block of pp_hip.h, then the group sums, the partial sums
+// and their groups (byte offsets below; max_partials bounds what disjoint segments of n_floats floats can need).
+struct GradClipLayout {
+    int64_t stats_words, gsum_off, partial_off, pgroup_off, bytes, max_partials;
+};
+GradClipLayout grad_clip_layout(int64_t n_floats, int n_segments, int n_groups);
+int64_t grad_clip_partials(const int64_t* seg, int nseg);      // partial sums these segments produce
+// the reduction: one launch per 128 non-empty segments, then one that writes the statistics block for (mode, clip, skip)
+void launch_grad_norm(const float* g, const int64_t* seg, int nseg, const int32_t* groups, int ngroups, int mode,
+                      float clip, int skip, void* ws, int64_t n_floats, hipStream_t s);
+// the update; `ws` (the finished statistics block) may be NULL for PP_CLIP_NONE / PP_CLIP_VALUE without the guard
+void launch_adamw_segments_clipped(float* w, const float* g, float* m, float* v, const int64_t* seg, int nseg,
+                                   const int32_t* groups, int ngroups, int mode, float clip, int skip, const void* ws,
+                                   float lr_t, float beta1, float beta2, float eps, float wd, hipStream_t s);
 
 // rotate_iou.hip: rotated-box overlaps of the AP evaluator
 void launch_riou_corners(const float* boxes, int64_t n, float* corners, hipStream_t s);

@@ -9,6 +9,8 @@
     trainer.set_trainable(False)                               # ... the reference's set_trainable(net, False)
     trainer = Trainer(config, weights, metrics=True)           # every step counts accuracy / precision / recall on the GPU
     trainer.metrics(dist)                                      # ... the reference's update_metrics dict (metrics.py)
+    trainer = Trainer(config, weights, grad_clip=optim.GradClip("global_norm", 1.0, skip_nonfinite=True))
+    trainer.grad_stats()                                       # ... the last step's gradient norm, scale, skip flag
 
 What runs where: the frames are uploaded and voxelised by the engine, `pp_train_step` (csrc/train.hip) runs the
 training-mode forward pass, the loss and the backward pass and leaves the gradients of all trainable tensors in one
@@ -30,6 +32,13 @@ not update them, its tensors get no gradient (their entries of the flat gradient
 nor decays them.  The gradient still flows through a frozen unit to trainable units in front of it.  These are the
 documented Keras semantics; the reference flips `trainable` after its tf.function was first traced, and whether TF 2.2
 re-traces at that point has not been checked against a TF run.
+
+Gradient clipping (`grad_clip=`): the lines trainStep carries commented out above optimizer.apply_gradients
+(train.py:293-294) and the non-finite step guard, inside the optimizer step (optim.GradClip, csrc/grad_clip.hip).  The
+norm is taken AFTER the all-reduce, from the averaged buffer, so every rank takes the same decision; only the trainable
+tensors take part.  The clipped gradient exists inside the update kernel only: `grads` / gradients() keep the raw values
+and grad_stats() says which scale was applied.  A skipped step (guard on, a NaN or Inf gradient) leaves parameters,
+moments and the optimizer's step count as they were and is counted in `steps_skipped`.
 """
 import numpy as np
 
@@ -78,6 +87,14 @@ def trainable_segments(layout, frozen):
     return [tuple(s) for s in segs]
 
 
+def trainable_tensor_segments(layout, frozen):
+    """One (offset, size) segment per trainable tensor, unmerged, and the tensors' names: the groups of per-tensor
+    clipping (optim.GradClip("norm"))."""
+    fz = set(frozen)
+    keep = [(name, off, size) for name, off, size, is_state in layout if not is_state and unit_of(name) not in fz]
+    return [(off, size) for _, off, size in keep], [name for name, _, _ in keep]
+
+
 def resolve_frozen(d, frozen):
     """None / () -> (); "reference" -> reference_frozen_units(d); an iterable of unit names -> those, in network order.
     ValueError for an unknown or repeated name and when every unit would be frozen."""
@@ -118,7 +135,8 @@ class TrainBatch:
 
 class Trainer:
     def __init__(self, config, weights, max_batch=None, max_points_per_frame=32768, device=0, learning_rate=None,
-                 weight_decay=None, augment=None, seed=None, frozen=None, gt_database=None, sampler=None, metrics=False):
+                 weight_decay=None, augment=None, seed=None, frozen=None, gt_database=None, sampler=None, metrics=False,
+                 grad_clip=None):
         import random
         import torch
         from . import augment as _augment
@@ -159,6 +177,24 @@ class Trainer:
         elif augment is not None and not isinstance(augment, _augment.AugmentConfig):
             raise ValueError("augment: None, True or an augment.AugmentConfig")
         self.augment = augment
+        # grad_clip: None / False = off; True = train_config.gradient_clipping (an error when the key is absent); an
+        # optim.GradClip = those settings.  No configuration key turns it on by itself.
+        if grad_clip is True:
+            tcfg = config.get("train_config") if isinstance(config, dict) else None
+            grad_clip = optim.GradClip.from_config(tcfg)
+            if grad_clip is None:
+                raise ValueError("grad_clip=True, but train_config has no gradient_clipping key")
+        elif grad_clip is False:
+            grad_clip = None
+        elif grad_clip is not None and not isinstance(grad_clip, optim.GradClip):
+            raise ValueError("grad_clip: None, True or an optim.GradClip")
+        self.grad_clip = grad_clip
+        self.grad_groups = None      # with per-tensor norms: the tensor name of each group of grad_stats()["norms"]
+        self.steps_skipped = 0       # steps the non-finite guard left without an update
+        self._grad_stats = None
+        self._stats_host = None      # page-locked copy of the statistics block, filled behind the update
+        self._stats_pinned = None
+        self._stats_pending = False
         self.rs = np.random.RandomState(seed)
         self.torch = torch
         self.engine = Engine(config, max_batch=max_batch, max_points_per_frame=max_points_per_frame, device=device)
@@ -220,6 +256,15 @@ class Trainer:
         self.engine.train_set_frozen(names)
         self._frozen = names
         self.optimizer.set_segments(trainable_segments(self.layout, names) if names else None)
+        if self.grad_clip is not None:      # segments and groups of the clipped step follow the freeze
+            self._drop_stats_buffer()
+            if self.grad_clip.mode == "norm":
+                segs, self.grad_groups = trainable_tensor_segments(self.layout, names)
+                self.optimizer.set_segments(segs)
+                self.optimizer.set_clip(self.grad_clip, np.arange(len(segs), dtype=np.int32))
+            else:
+                self.optimizer.set_segments(trainable_segments(self.layout, names))
+                self.optimizer.set_clip(self.grad_clip)
 
     def set_trainable(self, trainable):
         """The reference's set_trainable(net, trainable) (train.py:62-113): False freezes its selection (the PFN and
@@ -256,7 +301,8 @@ class Trainer:
 
     def gradients(self):
         """The last step's gradients as a Keras-layout dict (trainable tensors only: the tensors of frozen units are
-        left out, as they are not among net.trainable_variables; their entries of `grads` are 0)."""
+        left out, as they are not among net.trainable_variables; their entries of `grads` are 0).  With grad_clip on
+        these are still the RAW gradients: clipping happens inside the update kernel, grad_stats() reports the scales."""
         from . import weights as _w
         shapes = _w.expected_shapes(self.engine.d)
         g = self.grads.cpu().numpy()
@@ -464,7 +510,50 @@ class Trainer:
         self._boxless = None
         if self._metrics is not None:
             self._metrics.update(self.engine.train_metrics_counts(), losses["cls_loss_reduced"], losses["loc_loss_reduced"])
+        if self._stats_pending:      # step(): the update ran behind the backward pass, its statistics came along
+            self._take_stats()
+            gs = self._grad_stats      # (None: "value" without the guard measures nothing)
+            losses["grad_norm"] = gs["global_norm"] if gs else None
+            losses["step_skipped"] = bool(gs and gs["skipped"])
         return losses
+
+    # ---- gradient clipping / non-finite guard (optim.GradClip) ----
+    def _take_stats(self):
+        """The statistics block of the update that has just been waited for; a skipped step gives the optimizer its
+        step count back, so the next step runs with the learning rate this one would have had."""
+        self._stats_pending = False
+        if not self.grad_clip.needs_norm:
+            self._grad_stats = None
+            return
+        self._grad_stats = optim.AdamW.decode_stats(self._stats_pinned.array)
+        if self._grad_stats["skipped"]:
+            self.optimizer.iterations -= 1
+            self.steps_skipped += 1
+
+    def set_grad_clip(self, grad_clip):
+        """Switch clipping on a live trainer: an optim.GradClip, or None = off (the step is the unclipped calls again)."""
+        if grad_clip is not None and not isinstance(grad_clip, optim.GradClip):
+            raise ValueError("set_grad_clip: an optim.GradClip or None")
+        self.grad_clip = grad_clip
+        self.grad_groups = self._grad_stats = None
+        self.optimizer.set_clip(None)
+        self.set_frozen(self._frozen)
+
+    def _drop_stats_buffer(self):
+        """Frees the page-locked statistics copy (nothing may be in flight into it: callers have waited)."""
+        self._stats_host, self._stats_pending = None, False
+        if self._stats_pinned is not None:
+            self._stats_pinned.close()
+            self._stats_pinned = None
+
+    def grad_stats(self):
+        """The last waited step's gradient statistics: global_norm, scale, nonfinite, skipped, norms, scales (per
+        group: one group, or one per trainable tensor -- `grad_groups` -- with GradClip("norm")).  The norms are those
+        of the raw, all-reduced gradient over the trainable tensors.  None before the first update; a GradClip("value")
+        without the guard measures nothing (None, too).  Needs Trainer(..., grad_clip=...)."""
+        if self.grad_clip is None:
+            raise RuntimeError("Trainer(..., grad_clip=...) takes the statistics; this trainer was built without")
+        return self._grad_stats
 
     # ---- monitoring (the reference's update_metrics) ----
     def metrics(self, dist=None):
@@ -500,6 +589,16 @@ class Trainer:
                 ev[1].record()
                 self._allreduce_events.append(ev)
             self.optimizer.apply_gradients(self.grads)
+            if self.grad_clip is not None and self.grad_clip.needs_norm:
+                words = self.optimizer.stats_words()
+                if self._stats_host is None:
+                    # the engine's own page-locked memory, not torch's: torch's host allocator would note the engine's
+                    # stream against the block and record an event on it when the block is freed -- after close(), on a
+                    # stream that no longer exists
+                    self._stats_pinned = self.engine.pinned((words.numel(),), np.int32)
+                    self._stats_host = self.torch.from_numpy(self._stats_pinned.array)
+                self._stats_host.copy_(words, non_blocking=True)      # read at the wait the step has anyway
+            self._stats_pending = self.grad_clip is not None
 
     def allreduce_ms(self):
         """Device time (ms) of each gradient exchange since `time_allreduce` was set (call after the steps were waited
@@ -513,6 +612,8 @@ class Trainer:
         returns when both are through, so a caller may read the parameters."""
         self._enqueue_update(dist)
         self._engine_stream().synchronize()
+        if self._stats_pending:
+            self._take_stats()
 
     def step(self, frames, labels=None, reg_targets=None, dist=None, prefetch=None, gt_boxes=None, gt_classes=None,
              gt_valid=None):
@@ -530,10 +631,12 @@ class Trainer:
 
     def _abandon_step(self):
         self._prefetched = None
+        self._stats_pending = False
         try:
             self.engine.train_step_wait()
         except Exception:      # noqa: BLE001 -- the caller's exception is the one to report
             pass
 
     def close(self):
-        self.engine.close()
+        self.engine.close()          # waits for the handle's streams
+        self._drop_stats_buffer()

@@ -35,7 +35,7 @@ def _np(x):
 
 class VoxelNet:
     def __init__(self, config, writer=None, training=False, max_batch=None, max_points_per_frame=32768, device=0,
-                 augment=None, seed=None, metrics=False):
+                 augment=None, seed=None, metrics=False, grad_clip=None):
         self.config = config
         self.training = bool(training)
         self.d = Derived(config)
@@ -44,7 +44,7 @@ class VoxelNet:
         self.trainer = None
         self._ctor = dict(max_batch=max_batch or self.batch_size, max_points_per_frame=max_points_per_frame, device=device)
         # training only: the loader's augmentation on the GPU (Trainer's augment= / seed=)
-        self._train_kw = dict(augment=augment, seed=seed, metrics=bool(metrics))
+        self._train_kw = dict(augment=augment, seed=seed, metrics=bool(metrics), grad_clip=grad_clip)
         if not self.training and metrics:
             raise ValueError("metrics is a training option: build the net with training=True")
         if not self.training and augment:

@@ -37,7 +37,8 @@ extern "C" {
  * pp_frustum_crop_async, pp_frustum_crop_info; then pp_nms_mode, pp_set_nms_mode, pp_get_nms_mode, PP_RNMS_MAX_BOXES,
  * pp_rotate_nms; then pp_set_projection, pp_get_projection, pp_get_bboxes, pp_box3d_to_bbox; then pp_class_nms,
  * pp_set_class_nms, pp_get_class_nms, pp_get_detection_rows; then PP_METRICS_COUNTS, pp_head_metrics,
- * pp_set_train_metrics, pp_get_train_metrics_enabled, pp_get_train_metrics. */
+ * pp_set_train_metrics, pp_get_train_metrics_enabled, pp_get_train_metrics; then pp_grad_clip_mode, pp_grad_clip_config,
+ * pp_grad_clip_workspace_bytes, pp_grad_norm_device, pp_adamw_step_clipped_device. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -444,6 +445,61 @@ int pp_adamw_step_device(int device, void* stream, float* params, const float* g
 int pp_adamw_step_segments_device(int device, void* stream, float* params, const float* grads, float* m, float* v,
                                   const int64_t* segments, int32_t n_segments, float lr_t, float beta1, float beta2,
                                   float epsilon, float weight_decay);
+
+/* Gradient clipping and the non-finite step guard in front of that update (the lines the reference's trainStep carries
+ * commented out above optimizer.apply_gradients, train.py:293-294, plus TensorFlow's global-norm rule).  The rules, per
+ * element g of the trainable segments, in float32 with one rounding per written operation; c = cfg->clip:
+ *   PP_CLIP_NONE         g' = g          (monitor: the norms are taken, and the guard if it is on)
+ *   PP_CLIP_VALUE        g' = min(max(g, -c), c); a NaN stays a NaN                        (tf.clip_by_value)
+ *   PP_CLIP_NORM         g' = (g * c) / max(norm of g's group, c), TensorFlow's order      (tf.clip_by_norm, per group)
+ *   PP_CLIP_GLOBAL_NORM  g' = g * scale, scale = c * min(1 / global norm, 1 / c); NaN when the norm is not finite
+ *                                                                                          (tf.clip_by_global_norm)
+ * g' exists in the update kernel's registers only: `grads` is never written.  A group is a set of segments (`groups`: a
+ * HOST int32 per segment, values in [0, n_groups); NULL = one group, n_groups must then be 1); its norm is
+ * (float)sqrt(sum of (double)g * (double)g), summed in an order fixed by the segment table alone (no floating-point
+ * atomics: the same buffer gives the same bits on every run); the global sum adds the group sums in group order.
+ * nonfinite = !isfinite(global sum): exactly when a trainable entry is NaN or Inf.  With skip_nonfinite != 0 and the flag
+ * set the update leaves params, m and v untouched (decided on the device; the caller learns it from `skipped`).  It does
+ * the same when the flag is clear but the float32 global norm is Inf (finite gradients with a norm beyond FLT_MAX:
+ * PP_CLIP_GLOBAL_NORM would scale by NaN): skipped = skip_nonfinite && (nonfinite || !isfinite(global norm)).
+ *
+ * The statistics block, the first (4 + 2 * n_groups) 32-bit words of the workspace, written on the device:
+ *   [0] float global norm   [1] float global scale (1 unless PP_CLIP_GLOBAL_NORM)   [2] int32 nonfinite   [3] int32 skipped
+ *   [4 .. 4 + n_groups) float norm per group
+ *   [4 + n_groups .. 4 + 2 n_groups) float scale per group: PP_CLIP_NORM c / max(norm, c) (what the rule above amounts
+ *   to, up to its two roundings), PP_CLIP_GLOBAL_NORM the global scale, else 1
+ * Launches: PP_CLIP_VALUE and PP_CLIP_NONE without the guard launch the update only (pp_adamw_step_clipped_device; no
+ * workspace needed); every other combination runs the reduction first: one launch per 128 non-empty segments plus one
+ * that finishes the statistics, then the update (one launch per 64 non-empty segments, as pp_adamw_step_segments_device). */
+enum pp_grad_clip_mode { PP_CLIP_NONE = 0, PP_CLIP_VALUE = 1, PP_CLIP_NORM = 2, PP_CLIP_GLOBAL_NORM = 3 };
+
+typedef struct pp_grad_clip_config {
+    int32_t mode;            /* enum pp_grad_clip_mode */
+    float clip;              /* c: > 0 and finite for a clipping mode; ignored for PP_CLIP_NONE */
+    int32_t skip_nonfinite;  /* != 0: a step whose trainable gradient holds a NaN or Inf changes nothing */
+} pp_grad_clip_config;
+
+/* *bytes: the size of the device workspace (statistics block included) for buffers of n_floats floats, n_segments
+ * segments and n_groups groups; the caller allocates it once, 8-byte aligned, and need not clear it.  PP_ERR_ARG for a
+ * negative argument, n_groups < 1 or a NULL `bytes`. */
+int pp_grad_clip_workspace_bytes(int64_t n_floats, int32_t n_segments, int32_t n_groups, int64_t* bytes);
+
+/* The reduction alone (monitoring, tests): fills the statistics block with the norms, scales of 1, the nonfinite flag
+ * and skipped = 0.  DEVICE pointers grads (n floats) and workspace (sized by pp_grad_clip_workspace_bytes(n, n_segments,
+ * n_groups)); `segments` as in pp_adamw_step_segments_device; asynchronous on `stream`; stateless.  PP_ERR_ARG for a
+ * segment outside [0, n), overlapping segments (more partial sums than the workspace holds), a group outside
+ * [0, n_groups), or a null / misaligned workspace. */
+int pp_grad_norm_device(int device, void* stream, const float* grads, int64_t n, const int64_t* segments,
+                        int32_t n_segments, const int32_t* groups, int32_t n_groups, void* workspace);
+
+/* pp_adamw_step_segments_device on the clipped gradient: the reduction if the mode or the guard needs it, then the
+ * update; from g' on an updated entry is bit-identical to what pp_adamw_step_segments_device makes of a buffer that
+ * holds g'.  Buffers of n floats.  PP_ERR_ARG as above, for an unknown mode, and for a clipping mode whose clip is <= 0 or
+ * not finite; `workspace` may be NULL where no reduction runs. */
+int pp_adamw_step_clipped_device(int device, void* stream, float* params, const float* grads, float* m, float* v,
+                                 int64_t n, const int64_t* segments, int32_t n_segments, const int32_t* groups,
+                                 int32_t n_groups, const pp_grad_clip_config* cfg, void* workspace, float lr_t,
+                                 float beta1, float beta2, float epsilon, float weight_decay);
 
 /* ---- training step ---------------------------- */
 
