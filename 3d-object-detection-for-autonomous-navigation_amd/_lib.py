@@ -17,9 +17,9 @@ _INCLUDE = os.path.join(os.path.dirname(_PKG), "include", "pp_hip.h")
 #   PP_HIP_LIB=libpp_hip_g.so PP_HIPCC_EXTRA="-g" python -c "import pp_amd; pp_amd._lib.build()"
 SO_PATH = os.path.join(_PKG, os.environ.get("PP_HIP_LIB", "libpp_hip.so"))
 _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
-SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_nms.hip", "api_project.hip", "api_class_nms.hip", "api_metrics.hip", "api_train.hip", "api_dataprep.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
+SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_nms.hip", "api_project.hip", "api_class_nms.hip", "api_metrics.hip", "api_publish.hip", "api_train.hip", "api_dataprep.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
            "rotate_iou.hip", "rotate_nms.hip", "box_project.hip", "loss.hip", "metrics.hip", "optim.hip", "grad_clip.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip",
-           "gt_database.hip", "eval_stats.hip", "frustum_crop.hip"]
+           "gt_database.hip", "eval_stats.hip", "frustum_crop.hip", "weight_publish.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
@@ -48,6 +48,7 @@ EXPORTS = [
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
     "pp_head_metrics", "pp_set_train_metrics", "pp_get_train_metrics_enabled", "pp_get_train_metrics",
     "pp_grad_clip_workspace_bytes", "pp_grad_norm_device", "pp_adamw_step_clipped_device",
+    "pp_publish_train_weights", "pp_publish_info",
 ]
 
 
@@ -115,6 +116,15 @@ class PPGradClipConfig(ctypes.Structure):
         ("mode", ctypes.c_int32),
         ("clip", ctypes.c_float),
         ("skip_nonfinite", ctypes.c_int32),
+    ]
+
+
+class PPPublishStats(ctypes.Structure):
+    _fields_ = [
+        ("publishes", ctypes.c_int64),
+        ("reallocations", ctypes.c_int64),
+        ("graph_invalidations", ctypes.c_int64),
+        ("f32_fallback_layers", ctypes.c_int64),
     ]
 
 
@@ -388,6 +398,8 @@ def lib():
     L.pp_adamw_step_clipped_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, i64, vp, i32, vp, i32,
                                                ctypes.POINTER(PPGradClipConfig), vp, ctypes.c_float, ctypes.c_float,
                                                ctypes.c_float, ctypes.c_float, ctypes.c_float]
+    L.pp_publish_train_weights.argtypes = [vp, vp, vp]
+    L.pp_publish_info.argtypes = [vp, ctypes.POINTER(PPPublishStats)]
     for name in EXPORTS:
         fn = getattr(L, name)  # raises AttributeError if the symbol is not exported
         if name not in ("pp_last_error", "pp_layer_tag"):

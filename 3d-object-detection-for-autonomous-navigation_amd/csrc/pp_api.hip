@@ -825,6 +825,7 @@ int pp_finalize_weights(pp_handle e) {
     e->weights_ready = false;
     for (void* p : e->wallocs) (void)hipFree(p);   // the previous weight set (the stream is idle)
     e->wallocs.clear();
+    e->pub.live = false;          // ... a published one included
     std::vector<float> sc, sh;
     // PFN: dense [Fa,C] * scale, bias = shift
     {
@@ -919,23 +920,27 @@ int pp_finalize_weights(pp_handle e) {
             st = upload(e, &L.d_bias, headb); if (st) return st;
         }
     }
-    // sparse canvas: on a large, mostly empty BEV grid (KITTI-shaped: 214 k cells, <= 12 k pillars) writing and
-    // re-reading the zeros of the pseudo-image is most of the PFN's and the first layer's traffic.  The PFN then
-    // writes only the cells that hold a pillar and the first layer looks every window position up in the cell
-    // map.  Needs the kernels that know the lookup (sparse_input_supported); PP_DENSE_CANVAS=1 turns it off.
-    {
-        const char* env = getenv("PP_DENSE_CANVAS");
-        const long long cells = (long long)e->ny * e->nx;
-        LayerDesc& L0 = e->layers[0];
-        e->sparse_canvas = !(env && env[0] == '1') && cells >= 32768 && 4ll * e->cfg.max_voxels <= cells &&
-                           L0.in == e->d_canvas && sparse_input_supported(L0, e->B);
-        L0.d_occ = e->sparse_canvas ? e->d_cellmap : nullptr;
-        L0.occ_nz = e->nz;
-    }
+    decide_sparse_canvas(e);
     e->tag_batch = -1;            // which kernel runs a layer may depend on its weights (float16 range fallback)
     e->weights_ready = true;
     return PP_OK;
 }
+
+}  // extern "C"
+// sparse canvas: on a large, mostly empty BEV grid (KITTI-shaped: 214 k cells, <= 12 k pillars) writing and
+// re-reading the zeros of the pseudo-image is most of the PFN's and the first layer's traffic.  The PFN then
+// writes only the cells that hold a pillar and the first layer looks every window position up in the cell
+// map.  Needs the kernels that know the lookup (sparse_input_supported); PP_DENSE_CANVAS=1 turns it off.
+void decide_sparse_canvas(pp_engine* e) {
+    const char* env = getenv("PP_DENSE_CANVAS");
+    const long long cells = (long long)e->ny * e->nx;
+    LayerDesc& L0 = e->layers[0];
+    e->sparse_canvas = !(env && env[0] == '1') && cells >= 32768 && 4ll * e->cfg.max_voxels <= cells &&
+                       L0.in == e->d_canvas && sparse_input_supported(L0, e->B);
+    L0.d_occ = e->sparse_canvas ? e->d_cellmap : nullptr;
+    L0.occ_nz = e->nz;
+}
+extern "C" {
 
 int pp_set_anchors(pp_handle e, const float* anchors, const int32_t* cells, int64_t num_anchors) {
     if (e) graph_invalidate(e);
@@ -1122,6 +1127,8 @@ int graph_bucket(const pp_engine* e, int max_n) {
     return b < e->cfg.max_points_per_frame ? b : e->cfg.max_points_per_frame;
 }
 
+void drop_detect_graphs(pp_engine* e) { graph_invalidate(e); }
+
 // the whole fused pipeline of one batch, enqueued on e->stream (plain launches or under stream capture)
 static int enqueue_detect(pp_engine* e, int B, int max_n) {
     int st;
@@ -1249,6 +1256,7 @@ int pp_set_gemm_precision(pp_handle e, int32_t precision) {
     if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_set_gemm_precision: a training step is in flight");
     e->force_f32 = f32;
     if (!e->weights_ready) return PP_OK;
+    if (e->pub.live) return publish_reapply(e);   // published weights: re-derived from their folded arrays, on the device
     return pp_finalize_weights(e);       // waits for the stream, drops the graphs, rebuilds the device weights
 }
 

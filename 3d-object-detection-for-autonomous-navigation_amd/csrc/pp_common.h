@@ -548,3 +548,38 @@ struct CropParams {
 int crop_chunks(int n);
 int crop_max_features();     // widest row (num_point_features) the kernels move
 void launch_frustum_crop(const CropParams& p, hipStream_t s);
+
+// weight_publish.hip: the trainer's flat parameter / state buffers -> the detector's weight arrays, on the device
+enum PubKind {
+    PUB_PFN_W,       // out [FA][cout] = params[src] * scale[c]
+    PUB_SHIFT,       // out [n] = beta - mean * scale
+    PUB_COPY,        // out [n] = params[src]
+    PUB_SEP_WT,      // out [cout][cin] = params[src] ([cin][cout]) * scale[co]
+    PUB_DEC_WT,      // out [n_total][cin] = params[src] * scale[n % cout]
+    PUB_HEAD_WT,     // out [PP_HEAD_COLS][cout] = columns co_off .. co_off + cout of the head matrix
+    PUB_HEAD_BIAS,   // out [PP_HEAD_COLS]
+    PUB_SPLIT,       // out16 [cin / 16][PP_NPIECE][n_total][16] = float16 pieces of wt [n_total][cin]
+    PUB_SPLIT_HEAD   // ... of a head slice, its channels in the deconv kernels' accumulator-register order
+};
+struct PubTask {
+    int kind;
+    int n;                      // threads: output elements (fold kinds), 16-channel groups (split kinds)
+    int block0;                 // first workgroup of the task within its launch
+    int cin, cout, n_total;
+    int co_off;                 // PUB_HEAD_WT
+    int flag;                   // split kinds: the range flag the task raises
+    long long src;              // offsets (floats) into the parameter buffer ...
+    long long gamma, beta;
+    long long mean, var;        // ... and into the state buffer
+    float* out;
+    const float* wt;            // split kinds: the folded float32 array (written by the fold launch in front)
+    unsigned short* out16;
+};
+struct PubHead {                // the three head kernels [CC][n*] and biases in the parameter buffer
+    long long box_k, box_b, cls_k, cls_b, dir_k, dir_b;
+    int nb, nc, nd;
+};
+int publish_blocks(int n);     // workgroups of a task of n threads
+void launch_publish_fold(const PubTask* tasks, int ntasks, int blocks, const PubHead& hd, const float* params,
+                         const float* state, hipStream_t s);
+void launch_publish_split(const PubTask* tasks, int ntasks, int blocks, int* flags, hipStream_t s);

@@ -3,7 +3,7 @@
 // api_ingest.hip: PointCloud2 ingest; api_crop.hip: the frustum crop; api_train.hip: loss, training step, optimizer; api_dataprep.hip: targets,
 // augmentation, GT sampling, object database; api_eval.hip: the AP evaluator (needs no handle); api_nms.hip: the detector's NMS rule and the standalone rotated NMS;
 // api_project.hip: the detector's image boxes and the standalone projection; api_class_nms.hip: joint / per-class suppression;
-// api_metrics.hip: the training metrics' counts.
+// api_metrics.hip: the training metrics' counts; api_publish.hip: a trainer's weights into the detector, on the device.
 #pragma once
 
 #include <cmath>
@@ -253,6 +253,20 @@ struct pp_engine {
     bool mask_in_pfn = false;      // the last run_pfn also computed the anchor mask (few frames)
     int f32_fallback_layers = 0;   // layers whose folded weights do not fit float16 pieces (pp_finalize_weights)
     bool force_f32 = false;        // pp_set_gemm_precision(PP_PREC_F32): no layer gets split weights
+    // pp_publish_train_weights (api_publish.hip): the weight arrays written on the device from a trainer's buffers.  They
+    // live in `wallocs` like a host-loaded set, so pp_finalize_weights replaces them (live = false) and the next
+    // publish allocates again.
+    struct Publish {
+        bool live = false;                      // the handle's weights are the published arrays
+        std::vector<float*> wt16, head_wt16;    // per layer: the float16 array of an eligible layer (NULL: not eligible),
+                                                // allocated once whether or not the layer runs on it (LayerDesc::d_wt16)
+        std::vector<int> h_flags;               // [2 * layers] range flags of the last publish: d_wt, d_head_wt
+        int* d_flags = nullptr;
+        PubTask *d_fold = nullptr, *d_split = nullptr;
+        int n_fold = 0, n_split = 0, fold_blocks = 0, split_blocks = 0;
+        PubHead head;
+        int64_t publishes = 0, reallocations = 0, graph_invalidations = 0;
+    } pub;
     int nms_mode = PP_NMS_STANDUP; // pp_set_nms_mode: the post-process instantiation of the next pass (part of a graph's key)
     // pp_set_class_nms: joint (one pass for all classes) or per class.  The result buffers (d_dets, h_dets, the projection's
     // boxes) hold ncls * nms_post_max_size rows per frame; a pass uses the row stride of the mode it ran in (det_rows)
@@ -361,6 +375,9 @@ inline int det_rows(const pp_engine* e) {
 }
 int graph_bucket(const pp_engine* e, int max_n);
 bool graphs_enabled();
+void drop_detect_graphs(pp_engine* e);                  // waits for the stream, destroys the captured inference passes
+void decide_sparse_canvas(pp_engine* e);                // from layer 0's weights (pp_finalize_weights, a publish)
+int publish_reapply(pp_engine* e);                      // api_publish.hip: pp_set_gemm_precision on published weights
 // ---- pp_api.hip: the resident frames' state, one function per transition ----
 int wait_for_upload(pp_engine* e, hipStream_t s);       // `s` behind an upload / voxeliser queued on the copy stream
 int copies_done(pp_engine* e, hipStream_t up);          // the main stream behind the copies queued on `up` (ev_tgt)

@@ -345,6 +345,23 @@ class Engine:
         self._check(self._lib.pp_finalize_weights(self._h), "pp_finalize_weights")
         self.weights_loaded = True
 
+    def publish_weights(self, params_ptr, state_ptr):
+        """The detector's weights from a trainer's flat device buffers (train_layout; Trainer.params / .state), folded
+        on the GPU (pp_publish_train_weights, csrc/weight_publish.hip): the bytes load_weights(trainer.weights()) would
+        leave, without the trip through the host.  Runs on the engine's stream, behind a step or update enqueued there;
+        returns with the weights usable.  After the first call the arrays are rewritten in place and the captured
+        inference graphs survive (publish_info)."""
+        self._check(self._lib.pp_publish_train_weights(self._h, ctypes.c_void_p(int(params_ptr)),
+                                                       ctypes.c_void_p(int(state_ptr))), "pp_publish_train_weights")
+        self.weights_loaded = True
+
+    def publish_info(self):
+        """{"publishes", "reallocations", "graph_invalidations"} of publish_weights on this engine, and
+        "f32_fallback_layers": the layers of the CURRENT weights (published or loaded) on the float32 fallback."""
+        s = _lib.PPPublishStats()
+        self._check(self._lib.pp_publish_info(self._h, ctypes.byref(s)), "pp_publish_info")
+        return {k: int(getattr(s, k)) for k, _ in _lib.PPPublishStats._fields_}
+
     # ---- a1 ----
     def points_to_voxel(self, points):
         d = self.d

@@ -543,7 +543,16 @@ def get_official_eval_result(gt_annos, dt_annos, current_classes, difficultys=[0
     return result
 
 
-_COCO_RANGE = {0: [0.5, 0.95, 10], 1: [0.25, 0.7, 10], 2: [0.25, 0.7, 10], 3: [0.5, 0.95, 10], 4: [0.25, 0.7, 10],
+def eval_score(mAP3d, mAPbev, mAPaos):
+    """The number the reference's train() ranks checkpoints by after each epoch's evaluation (train.py:418, :926): the
+    first class's 3d, aos and bev AP over the three difficulties at the two overlap tiers it prints, 18 values, averaged.
+        _, _, mAPbev, mAP3d, mAPaos = get_official_eval_result(gt_annos, dt_annos, classes)
+        score = eval_score(mAP3d, mAPbev, mAPaos)
+        if score > best: best = score; weights.save_npz(path, trainer.weights())"""
+    return (np.asarray(mAP3d)[0][0].sum() + np.asarray(mAPaos)[0][0].sum() + np.asarray(mAPbev)[0][0].sum()) / 18
+
+
+_COCO_RANGE ={0: [0.5, 0.95, 10], 1: [0.25, 0.7, 10], 2: [0.25, 0.7, 10], 3: [0.5, 0.95, 10], 4: [0.25, 0.7, 10],
                5: [0.5, 0.95, 10], 6: [0.5, 0.95, 10], 7: [0.5, 0.95, 10]}
 
 

@@ -11,6 +11,7 @@
     trainer.metrics(dist)                                      # ... the reference's update_metrics dict (metrics.py)
     trainer = Trainer(config, weights, grad_clip=optim.GradClip("global_norm", 1.0, skip_nonfinite=True))
     trainer.grad_stats()                                       # ... the last step's gradient norm, scale, skip flag
+    dets, n = trainer.detect(frames)                           # detect with the CURRENT weights (published on the GPU)
 
 What runs where: the frames are uploaded and voxelised by the engine, `pp_train_step` (csrc/train.hip) runs the
 training-mode forward pass, the loss and the backward pass and leaves the gradients of all trainable tensors in one
@@ -39,6 +40,12 @@ norm is taken AFTER the all-reduce, from the averaged buffer, so every rank take
 tensors take part.  The clipped gradient exists inside the update kernel only: `grads` / gradients() keep the raw values
 and grad_stats() says which scale was applied.  A skipped step (guard on, a NaN or Inf gradient) leaves parameters,
 moments and the optimizer's step count as they were and is counted in `steps_skipped`.
+
+Detection during training (`detect`, `publish`): the reference evaluates with the current weights after every epoch
+(train.py:403-444).  `publish()` folds the flat `params` / `state` buffers into the engine's inference weights on the GPU
+(csrc/weight_publish.hip) -- the bytes `engine.load_weights(trainer.weights())` would leave, without the host round trip,
+written in place so the captured inference graphs survive -- and does nothing while the weights have not changed since
+the last publish.  `detect()` publishes when needed and is `Engine.detect`; training is not disturbed by it.
 """
 import numpy as np
 
@@ -201,6 +208,7 @@ class Trainer:
         if gt_database is not None:
             self.engine.load_gt_database(gt_database)
         self._prefetched = None      # the TrainBatch whose points are already on their way (forward_backward(prefetch=))
+        self._dirty = True           # params / state changed since the last publish() (set_weights, every step and update)
         self._ext_stream = None      # torch.cuda.ExternalStream over the engine's stream (_engine_stream)
         self.time_allreduce = False  # True: every step's gradient all-reduce is bracketed by an event pair (allreduce_ms)
         self._allreduce_events = []
@@ -273,6 +281,7 @@ class Trainer:
 
     # ---- Keras-layout dict <-> flat buffers ----
     def set_weights(self, w):
+        self._dirty = True
         p = np.zeros(self.params.numel(), np.float32)
         s = np.zeros(self.state.numel(), np.float32)
         for name, off, size, is_state in self.layout:
@@ -448,6 +457,7 @@ class Trainer:
     def _launch(self, frames, labels, reg_targets, prefetch, gt_boxes=None, gt_classes=None, gt_valid=None):
         """Enqueue the step (and the upload of the next batch beside it); the caller waits with engine.train_step_wait().
         Targets: a TrainBatch's own (stage / stage_gt), else labels / reg_targets, else gt_boxes (+ gt_classes)."""
+        self._dirty = True      # every step moves the BatchNorm statistics, whether or not an update follows
         if isinstance(frames, TrainBatch):
             tb = frames
             if gt_boxes is not None or gt_classes is not None:
@@ -610,6 +620,7 @@ class Trainer:
         """optimizer.apply_gradients (train.py:301) after the data-parallel mean of the flat gradient buffer.  The
         all-reduce and the AdamW kernel run on the engine's stream (behind the step that produced the gradients); this
         returns when both are through, so a caller may read the parameters."""
+        self._dirty = True
         self._enqueue_update(dist)
         self._engine_stream().synchronize()
         if self._stats_pending:
@@ -628,6 +639,26 @@ class Trainer:
             self._abandon_step()
             raise
         return self._wait()
+
+    # ---- detection with the current weights (the reference's per-epoch evaluation, train.py:403-444) ----
+    def publish(self):
+        """The engine's inference weights from `params` / `state`, on the GPU (Engine.publish_weights); nothing when
+        they have not changed since the last publish.  Returns whether it published."""
+        if not self._dirty:
+            return False
+        self.engine.publish_weights(self.params.data_ptr(), self.state.data_ptr())
+        self._dirty = False
+        return True
+
+    def detect(self, frames, rect=None, trv2c=None, **kw):
+        """Engine.detect(frames, rect, trv2c, **kw) with the trainer's current weights (publish() first when they
+        changed).  Between steps only: a batch prefetched by forward_backward(prefetch=) is resident in the engine and
+        the detection's upload would replace it."""
+        if self._prefetched is not None:
+            raise RuntimeError("Trainer.detect: a prefetched training batch is pending (forward_backward(prefetch=...)); "
+                               "run its step first -- detect() would replace the resident points")
+        self.publish()
+        return self.engine.detect(frames, rect, trv2c, **kw)
 
     def _abandon_step(self):
         self._prefetched = None

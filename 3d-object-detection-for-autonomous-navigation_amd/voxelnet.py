@@ -15,7 +15,9 @@ Training mode (model/voxelnet.py:922-1049 + train.py:265-304), `VoxelNet(config,
     ret = net(voxels, num_points, coors, batch_anchors, labels, reg_targets)   # the reference's loss dict (scalars)
     net.apply_gradients(dist=None)        # optimizer.apply_gradients: one all-reduce over the ranks + AdamW
 or, from raw clouds, `net.train_step(frames, labels, reg_targets, dist)` -- or `net.train_step(frames, gt_boxes=boxes)`,
-which assigns the targets on the GPU (the loader's target_assigner.assign, csrc/targets.hip).  The forward pass, the loss and the
+which assigns the targets on the GPU (the loader's target_assigner.assign, csrc/targets.hip).  A training net detects
+with its current weights (`detect`, `detect_pointcloud2`): they are folded into the detector on the GPU first
+(Trainer.publish, csrc/weight_publish.hip).  The forward pass, the loss and the
 gradients of a call come from one `pp_train_step` (csrc/train.hip); the padded voxel tensor is unpadded on the
 host into the pillar-ordered point list it was built from (the voxeliser then reproduces the same pillars).
 """
@@ -155,12 +157,23 @@ class VoxelNet:
         bb = self._bboxes(batch)
         return [self._to_dict(dets[b], int(n[b]), img_idx[b], None if bb is None else bb[b]) for b in range(batch)]
 
+    def _detector(self):
+        """What detects: the engine, or -- training mode -- the trainer, whose current weights are published first."""
+        if not self.training:
+            return self.engine
+        if self.trainer is None:
+            raise RuntimeError("VoxelNet(training=True): load_weights() with the initial values first")
+        if self.trainer._prefetched is not None:
+            raise RuntimeError("VoxelNet.detect: a prefetched training batch is pending; run its step first")
+        self.trainer.publish()
+        return self.trainer
+
     def detect(self, frames, rect=None, trv2c=None, image_idx=None, p2=None):
         """Fused path: list of raw clouds -> list of prediction dicts.  p2 ([4,4] or [B,4,4]): required with
         model.second.project_bbox, which puts the projected image boxes into "bbox"."""
         self._need_p2(p2, "detect")
         on = self.d.project_bbox
-        dets, n = self.engine.detect(frames, rect, trv2c, p2=p2 if on else None, bbox=on)
+        dets, n = self._detector().detect(frames, rect, trv2c, p2=p2 if on else None, bbox=on)
         bb = self._bboxes(len(frames))
         idx = image_idx if image_idx is not None else list(range(len(frames)))
         return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(frames))]
@@ -169,6 +182,7 @@ class VoxelNet:
         """Fused path from raw sensor_msgs/PointCloud2 messages (the reference's production mode: ingest on the GPU,
         Engine.detect_pointcloud2) -> the same list of prediction dicts as `detect`; p2 as there."""
         self._need_p2(p2, "detect_pointcloud2")
+        self._detector()
         if self.d.project_bbox:
             self.engine.set_projection(np.broadcast_to(np.asarray(p2, np.float64), (len(msgs), 4, 4)))
         dets, n = self.engine.detect_pointcloud2(msgs, rect, trv2c)

@@ -38,7 +38,8 @@ extern "C" {
  * pp_rotate_nms; then pp_set_projection, pp_get_projection, pp_get_bboxes, pp_box3d_to_bbox; then pp_class_nms,
  * pp_set_class_nms, pp_get_class_nms, pp_get_detection_rows; then PP_METRICS_COUNTS, pp_head_metrics,
  * pp_set_train_metrics, pp_get_train_metrics_enabled, pp_get_train_metrics; then pp_grad_clip_mode, pp_grad_clip_config,
- * pp_grad_clip_workspace_bytes, pp_grad_norm_device, pp_adamw_step_clipped_device. */
+ * pp_grad_clip_workspace_bytes, pp_grad_norm_device, pp_adamw_step_clipped_device; then pp_publish_stats,
+ * pp_publish_train_weights, pp_publish_info. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -867,6 +868,31 @@ int pp_get_train_metrics_enabled(pp_handle h, int32_t* on);
 /* The counts of the last step, after its pp_train_step_wait.  PP_ERR_STATE when that step ran with the switch off, when no
  * step has run, or while one is in flight. */
 int pp_get_train_metrics(pp_handle h, int64_t* counts);
+
+/* ---- detection during training: a trainer's weights into the detector, on the device --------------------------------- */
+
+typedef struct pp_publish_stats {
+    int64_t publishes;           /* successful pp_publish_train_weights calls on this handle */
+    int64_t reallocations;       /* ... of them, those that allocated the weight arrays (the first; the first after a
+                                  * pp_finalize_weights) */
+    int64_t graph_invalidations; /* times published weights dropped the captured inference graphs: every reallocation,
+                                  * and every change of the set of layers on the float32 fallback (a publish, or
+                                  * pp_set_gemm_precision on published weights) */
+    int64_t f32_fallback_layers; /* separable layers and transposed convolutions of the handle's CURRENT weights that run on
+                                  * the float32 matrix instruction -- also for weights loaded by pp_finalize_weights */
+} pp_publish_stats;
+
+/* params_dev / state_dev: the flat device buffers of pp_train_layout (only read).  Kernels on the handle's stream -- so
+ * behind a training step or optimizer update enqueued there -- write every array pp_finalize_weights would produce from
+ * the same tensors, with the same bytes: BatchNorm folded from the MOVING statistics (frozen or not), transposed
+ * kernels, the head matrix, the float16 piece pairs and their range rule (a layer with a folded |w| >= 32768 runs in
+ * PP_PREC_F32 by itself).  Returns with the weights usable (one small read-back of the range flags).  The first publish
+ * on a handle allocates the arrays -- pp_set_weight need never have been called; a later one writes the same
+ * allocations and keeps the captured inference graphs unless the set of fallback layers changed.  The published values are
+ * the handle's weights from then on (pp_set_gemm_precision re-derives from them); a later pp_set_weight +
+ * pp_finalize_weights replaces them.  PP_ERR_STATE while a training step is in flight. */
+int pp_publish_train_weights(pp_handle h, const float* params_dev, const float* state_dev);
+int pp_publish_info(pp_handle h, pp_publish_stats* out);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
