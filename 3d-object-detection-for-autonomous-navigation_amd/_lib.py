@@ -19,7 +19,7 @@ SO_PATH = os.path.join(_PKG, os.environ.get("PP_HIP_LIB", "libpp_hip.so"))
 _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
 SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_nms.hip", "api_project.hip", "api_class_nms.hip", "api_metrics.hip", "api_publish.hip", "api_train.hip", "api_dataprep.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
            "rotate_iou.hip", "rotate_nms.hip", "box_project.hip", "loss.hip", "metrics.hip", "optim.hip", "grad_clip.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip",
-           "gt_database.hip", "eval_stats.hip", "frustum_crop.hip", "weight_publish.hip"]
+           "gt_database.hip", "eval_stats.hip", "frustum_crop.hip", "weight_publish.hip", "soft_nms.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
@@ -49,6 +49,7 @@ EXPORTS = [
     "pp_head_metrics", "pp_set_train_metrics", "pp_get_train_metrics_enabled", "pp_get_train_metrics",
     "pp_grad_clip_workspace_bytes", "pp_grad_norm_device", "pp_adamw_step_clipped_device",
     "pp_publish_train_weights", "pp_publish_info",
+    "pp_set_soft_nms", "pp_get_soft_nms", "pp_soft_nms",
 ]
 
 
@@ -173,7 +174,9 @@ class PPIngestConfig(ctypes.Structure):
 PP_CROP_BACK = 1      # pp_frustum_crop* flags: bit 0
 PP_METRICS_COUNTS = 32      # int64 values of pp_head_metrics / pp_get_train_metrics
 PP_CLASS_NMS_JOINT, PP_CLASS_NMS_PER_CLASS = 0, 1      # enum pp_class_nms
-PP_NMS_STANDUP, PP_NMS_ROTATED = 0, 1      # enum pp_nms_mode
+PP_NMS_STANDUP, PP_NMS_ROTATED, PP_NMS_SOFT = 0, 1, 2      # enum pp_nms_mode
+PP_SOFT_NMS_HARD, PP_SOFT_NMS_LINEAR, PP_SOFT_NMS_GAUSSIAN = 0, 1, 2      # enum pp_soft_nms_method
+PP_SNMS_MAX_BOXES = 4096      # most boxes that enter pp_soft_nms after pre_max_size
 PP_CLIP_NONE, PP_CLIP_VALUE, PP_CLIP_NORM, PP_CLIP_GLOBAL_NORM = 0, 1, 2, 3      # enum pp_grad_clip_mode
 
 
@@ -382,6 +385,10 @@ def lib():
     L.pp_set_nms_mode.argtypes = [vp, i32]
     L.pp_get_nms_mode.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_rotate_nms.argtypes = [ctypes.c_int, f32p, i64, ctypes.c_float, i32, i32, vp, ctypes.POINTER(i64)]
+    L.pp_set_soft_nms.argtypes = [vp, i32, ctypes.c_float, ctypes.c_float]
+    L.pp_get_soft_nms.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.pp_soft_nms.argtypes = [ctypes.c_int, f32p, i64, i32, ctypes.c_float, ctypes.c_float, ctypes.c_float, i32, i32, vp, vp,
+                              ctypes.POINTER(i64)]
     L.pp_set_projection.argtypes = [vp, vp, i32]
     L.pp_get_projection.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_get_bboxes.argtypes = [vp, vp]

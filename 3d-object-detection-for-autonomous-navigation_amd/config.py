@@ -207,6 +207,20 @@ class Derived:
         # not a key of the reference's YAML (absent = False): suppress on the rotated IoU of the decoded boxes
         # (rotate_nms_gpu, which the reference ships but never wires in) instead of predict()'s stand-up boxes
         self.use_rotate_nms = bool(s.get("use_rotate_nms", False))
+        # not keys of the reference's YAML either (absent = False / the defaults of soft_nms_jit): decay the score of a box
+        # that overlaps a selected one (soft_nms_jit, which the reference compiles but never calls) instead of deleting
+        # it; soft_nms: {method: hard | linear | gaussian, sigma, score_floor}
+        self.use_soft_nms = bool(s.get("use_soft_nms", False))
+        if self.use_soft_nms and self.use_rotate_nms:
+            raise ValueError("use_soft_nms together with use_rotate_nms: soft re-scoring on the rotated overlap is not "
+                             "built (no reference code defines it) -- choose one")
+        sn = s.get("soft_nms")
+        if sn is not None:
+            unknown = set(sn) - {"method", "sigma", "score_floor"}
+            if unknown:
+                raise ValueError(f"model.second.soft_nms: unknown keys {sorted(unknown)}")
+            sn = dict(sn)
+        self.soft_nms = sn
         # not a key of the reference's YAML either (absent = False): "bbox" of a prediction is the projection of its camera
         # box by the frame's P2 (box3d_to_bbox, which the reference's predict() commented out) instead of the placeholder
         self.project_bbox = bool(s.get("project_bbox", False))
@@ -229,4 +243,5 @@ class Derived:
                 "nms_post_max_size": self.nms_post_max_size, "nms_iou_threshold": self.nms_iou_threshold,
                 "num_class": self.num_class, "use_direction_classifier": self.use_direction_classifier,
                 "use_rotate_nms": self.use_rotate_nms, "project_bbox": self.project_bbox,
+                "use_soft_nms": self.use_soft_nms, "soft_nms": self.soft_nms,
                 "use_multi_class_nms": self.use_multi_class_nms}

@@ -27,6 +27,12 @@
 // are spread over the workgroup; the clip's polygon scratch ([8][1024] x 3 floats, riou_dev.h) lies on s_ckey, whose
 // candidate keys are dead once the top set is in s_key -- the footprint grows by the corner table only.
 //
+// PP_NMS_SOFT replaces the masks and the sweep by the rounds of soft_nms_jit (second/core/non_max_suppression/nms_cpu.py:
+// 79-169, soft_nms_dev.h; pp_set_soft_nms) on the same stand-up boxes: wave 0 holds boxes `lane` and `lane + 64` with their
+// current scores in registers, a round is an argmax butterfly, a broadcast read of the selected box and one float64
+// overlap per lane; a kept row's score is its decayed score.  Method hard with a floor below every score is the default
+// rule, byte for byte.
+//
 // Image boxes (template parameter, pp_set_projection): the lane that assembles a kept detection's box3d_camera also
 // projects it (box3d_to_bbox of second/core/box_np_ops.py:849-857, box_project_dev.h) with the frame's P2 and stores the
 // four doubles beside the detections.  The reference's predict() has this commented out and returns a constant
@@ -41,6 +47,7 @@
 
 #include "box_project_dev.h"
 #include "riou_dev.h"
+#include "soft_nms_dev.h"
 
 #define PT 1024
 #define KMAX 128   // >= the reference's hard-coded top-100
@@ -394,7 +401,9 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
     const int n = min(K, p.pre_max);
     if (tid < 2 * KMAX) reinterpret_cast<unsigned long long*>(s_mask)[tid] = 0ull;
     __syncthreads();
-    if constexpr (NMS == PP_NMS_ROTATED) {
+    if constexpr (NMS == PP_NMS_SOFT) {
+        // no n x n matrix (the zeroed masks stay unused): a round below forms the overlaps with its selected box
+    } else if constexpr (NMS == PP_NMS_ROTATED) {
         // all (i, j) of the n x n square, 64 consecutive j of one row per wavefront; j <= i has nothing to do
         static_assert(sizeof(s_ckey) >= 3 * RIOU_MAXP * PT * sizeof(float), "the polygon scratch lies on the candidate keys");
         float* s_px = reinterpret_cast<float*>(s_ckey);
@@ -438,36 +447,44 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
     // greedy sweep by wave 0: lane l holds the mask rows l and l + 64 in registers; the kept boxes are walked
     // with find-first-set over "not yet visited and not removed" (scalar), a kept row's mask comes by readlane
     if (tid < 64) {
-        const unsigned long long a0 = (lane < n) ? s_mask[lane][0] : 0ull, a1 = (lane < n) ? s_mask[lane][1] : 0ull;
-        const unsigned long long b0 = (lane + 64 < n) ? s_mask[lane + 64][0] : 0ull;
-        const unsigned long long b1 = (lane + 64 < n) ? s_mask[lane + 64][1] : 0ull;
-        auto rdl = [](unsigned long long v, int l) -> unsigned long long {
-            const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v & 0xffffffffull), l);
-            const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-            return ((unsigned long long)hi << 32) | lo;
-        };
-        unsigned long long todo0 = (n >= 64) ? ~0ull : ((1ull << n) - 1ull);
-        unsigned long long todo1 = (n <= 64) ? 0ull : ((n - 64 >= 64) ? ~0ull : ((1ull << (n - 64)) - 1ull));
-        unsigned long long r0 = 0ull, r1 = 0ull;
-        int nk = 0, k0 = 0, k1 = 0;
-        while (nk < p.post_max) {
-            const unsigned long long c0 = todo0 & ~r0, c1 = todo1 & ~r1;
-            if ((c0 | c1) == 0ull) break;
-            int i = c0 ? __builtin_ctzll(c0) : 64 + __builtin_ctzll(c1);
-            i = __builtin_amdgcn_readfirstlane(i);
-            if (lane == (nk & 63)) { if (nk < 64) k0 = i; else k1 = i; }   // lane l remembers kept boxes l and l + 64
-            ++nk;
-            if (i < 64) {
-                todo0 &= ~((2ull << i) - 1ull);       // i = 63: 2 << 63 wraps to 0, minus 1 = all ones
-                r0 |= rdl(a0, i); r1 |= rdl(a1, i);
-            } else {
-                todo0 = 0ull;
-                todo1 &= ~((2ull << (i - 64)) - 1ull);
-                r0 |= rdl(b0, i - 64); r1 |= rdl(b1, i - 64);
+        int nk = 0;
+        if constexpr (NMS == PP_NMS_SOFT) {
+            static_assert(KMAX <= 2 * 64, "wave 0 holds two boxes per lane");
+            nk = snms_rounds<64, 2>(s_aabb, s_score, n, min(p.post_max, KMAX), p.soft_method, p.iou_thr, p.soft_sigma,
+                                    p.soft_floor, lane, (float (*)[1])nullptr, (int (*)[1])nullptr,
+                                    [&](int r, int idx, float sc) { s_keep[r] = idx; s_score[idx] = sc; });
+        } else {
+            const unsigned long long a0 = (lane < n) ? s_mask[lane][0] : 0ull, a1 = (lane < n) ? s_mask[lane][1] : 0ull;
+            const unsigned long long b0 = (lane + 64 < n) ? s_mask[lane + 64][0] : 0ull;
+            const unsigned long long b1 = (lane + 64 < n) ? s_mask[lane + 64][1] : 0ull;
+            auto rdl = [](unsigned long long v, int l) -> unsigned long long {
+                const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v & 0xffffffffull), l);
+                const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
+                return ((unsigned long long)hi << 32) | lo;
+            };
+            unsigned long long todo0 = (n >= 64) ? ~0ull : ((1ull << n) - 1ull);
+            unsigned long long todo1 = (n <= 64) ? 0ull : ((n - 64 >= 64) ? ~0ull : ((1ull << (n - 64)) - 1ull));
+            unsigned long long r0 = 0ull, r1 = 0ull;
+            int k0 = 0, k1 = 0;
+            while (nk < p.post_max) {
+                const unsigned long long c0 = todo0 & ~r0, c1 = todo1 & ~r1;
+                if ((c0 | c1) == 0ull) break;
+                int i = c0 ? __builtin_ctzll(c0) : 64 + __builtin_ctzll(c1);
+                i = __builtin_amdgcn_readfirstlane(i);
+                if (lane == (nk & 63)) { if (nk < 64) k0 = i; else k1 = i; }   // lane l remembers kept boxes l and l + 64
+                ++nk;
+                if (i < 64) {
+                    todo0 &= ~((2ull << i) - 1ull);       // i = 63: 2 << 63 wraps to 0, minus 1 = all ones
+                    r0 |= rdl(a0, i); r1 |= rdl(a1, i);
+                } else {
+                    todo0 = 0ull;
+                    todo1 &= ~((2ull << (i - 64)) - 1ull);
+                    r0 |= rdl(b0, i - 64); r1 |= rdl(b1, i - 64);
+                }
             }
+            if (lane < nk) s_keep[lane] = k0;
+            if (lane + 64 < nk) s_keep[lane + 64] = k1;
         }
-        if (lane < nk) s_keep[lane] = k0;
-        if (lane + 64 < nk) s_keep[lane + 64] = k1;
         if (lane == 0) {
             s_nkeep = nk;
             const int flagged = nk | (s_bad ? PP_NDETS_NONFINITE : 0);   // pp_get_detections / pp_predict: PP_ERR_NUMERIC
@@ -579,6 +596,9 @@ static void launch_post_rule(const PostParams& p, hipStream_t s) {
     if (p.nms_mode == PP_NMS_ROTATED) {
         if (proj) PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_ROTATED, true, PERCLS>), grid, dim3(PT), 0, s, p);
         else PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_ROTATED, false, PERCLS>), grid, dim3(PT), 0, s, p);
+    } else if (p.nms_mode == PP_NMS_SOFT) {
+        if (proj) PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_SOFT, true, PERCLS>), grid, dim3(PT), 0, s, p);
+        else PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_SOFT, false, PERCLS>), grid, dim3(PT), 0, s, p);
     } else {
         if (proj) PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_STANDUP, true, PERCLS>), grid, dim3(PT), 0, s, p);
         else PP_LAUNCH("k_postprocess", (k_postprocess<PP_NMS_STANDUP, false, PERCLS>), grid, dim3(PT), 0, s, p);

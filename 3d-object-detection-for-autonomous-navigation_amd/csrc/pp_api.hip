@@ -348,6 +348,7 @@ static int run_post(pp_engine* e, int batch, bool to_host = false) {
     p.calib = e->d_calib; p.dets = e->d_dets; p.n_dets = e->d_ndets;
     p.dets_host = to_host ? e->h_dets : nullptr; p.n_dets_host = to_host ? e->h_ndets : nullptr;
     p.nms_mode = e->nms_mode;
+    p.soft_method = e->soft_method; p.soft_sigma = e->soft_sigma; p.soft_floor = e->soft_floor;
     const bool proj = e->proj.on;
     if (proj && batch > e->proj.batch)
         return fail(e, PP_ERR_STATE, "pp_set_projection gave matrices for %d frames; this pass has %d", e->proj.batch, batch);
@@ -1174,7 +1175,8 @@ int pp_detect_async(pp_handle e) {
         pp_engine::GraphSlot* lru = &e->graphs[0];
         for (auto& g : e->graphs) {
             if (g.exec && g.batch == B && g.bucket == bucket && g.buf == e->in_buf && g.zc == (e->zc ? 1 : 0) &&
-                g.vox == (e->vox_ahead ? 1 : 0) && g.nms == e->nms_mode && g.proj == (e->proj.on ? 1 : 0) && g.cnms == e->class_nms) slot = &g;
+                g.vox == (e->vox_ahead ? 1 : 0) && g.nms == e->nms_mode && g.proj == (e->proj.on ? 1 : 0) && g.cnms == e->class_nms &&
+                (e->nms_mode != PP_NMS_SOFT || (g.smethod == e->soft_method && g.ssigma == e->soft_sigma && g.sfloor == e->soft_floor))) slot = &g;
             if (g.used < lru->used) lru = &g;
         }
         if (slot == nullptr) {
@@ -1196,6 +1198,7 @@ int pp_detect_async(pp_handle e) {
                 slot->zc = e->zc ? 1 : 0;
                 slot->vox = e->vox_ahead ? 1 : 0;
                 slot->nms = e->nms_mode;
+                slot->smethod = e->soft_method; slot->ssigma = e->soft_sigma; slot->sfloor = e->soft_floor;
                 slot->proj = e->proj.on ? 1 : 0;
                 slot->cnms = e->class_nms;
             } else {

@@ -277,6 +277,10 @@ struct PostParams {
     pp_detection* cls_dets;   // [batch][ncls][post_max]
     int* cls_cnt;             // [batch][ncls], each with its own PP_NDETS_NONFINITE flag
     double* cls_bbox;         // [batch][ncls][post_max][4] (with p2)
+    // pp_set_soft_nms (read by the PP_NMS_SOFT instantiation only): enum pp_soft_nms_method, sigma of the Gaussian
+    // weight, the score under which a re-scored box is dropped.  Nt is iou_thr
+    int soft_method;
+    float soft_sigma, soft_floor;
 };
 void launch_postprocess(const PostParams& p, hipStream_t s);
 
@@ -361,6 +365,11 @@ void launch_d3_finish(const double* boxes, int64_t N, const double* qboxes, int6
 // order [m], sorted [m][5], corners [m][9], mask [m][ceil(m / 64)] are scratch; keep [m] and *n_keep the result
 void launch_rnms(const float* dets, int n, int m, float thr, int post_max, int* order, float* sorted, float* corners,
                  unsigned long long* mask, int* keep, long long* n_keep, hipStream_t s);
+
+// soft_nms.hip: Soft-NMS of n boxes dets [n][5] (x1, y1, x2, y2, score), the m best by score (m <= PP_SNMS_MAX_BOXES):
+// enter [n] and order [m] are scratch (used when m < n); keep [post_max], scores [post_max] and *n_keep the result
+void launch_soft_nms(const float* dets, int n, int m, int method, float nt, float sigma, float score_floor, int post_max,
+                     int* enter, int* order, int* keep, float* scores, long long* n_keep, hipStream_t s);
 
 // box_project.hip: image boxes of n camera-frame boxes [n][7]; frame_start [frames + 1] is the exclusive prefix of the
 // frames' box counts, p2 [frames][16], bbox [n][4]

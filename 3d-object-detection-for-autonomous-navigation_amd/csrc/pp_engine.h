@@ -268,6 +268,9 @@ struct pp_engine {
         int64_t publishes = 0, reallocations = 0, graph_invalidations = 0;
     } pub;
     int nms_mode = PP_NMS_STANDUP; // pp_set_nms_mode: the post-process instantiation of the next pass (part of a graph's key)
+    // pp_set_soft_nms: kernel arguments of the PP_NMS_SOFT instantiation, so part of a graph's key as well
+    int soft_method = PP_SOFT_NMS_GAUSSIAN;
+    float soft_sigma = 0.5f, soft_floor = 0.001f;
     // pp_set_class_nms: joint (one pass for all classes) or per class.  The result buffers (d_dets, h_dets, the projection's
     // boxes) hold ncls * nms_post_max_size rows per frame; a pass uses the row stride of the mode it ran in (det_rows)
     int class_nms = PP_CLASS_NMS_JOINT;   // the next pass's mode (part of a graph's key)
@@ -288,8 +291,8 @@ struct pp_engine {
 
     int prof = 0;
     // pp_detect_async as one hipGraph launch (captured on first use per (batch, max points per frame))
-    struct GraphSlot { hipGraphExec_t exec = nullptr; int batch = -1, bucket = -1, buf = -1, zc = 0, vox = 0, nms = 0, proj = 0, cnms = 0; unsigned long long used = 0; };
-    GraphSlot graphs[8];          // small LRU keyed by (batch, point-count bucket, input buffer, NMS rule, projection on / off, class mode)
+    struct GraphSlot { hipGraphExec_t exec = nullptr; int batch = -1, bucket = -1, buf = -1, zc = 0, vox = 0, nms = 0, proj = 0, cnms = 0; int smethod = 0; float ssigma = 0.f, sfloor = 0.f; unsigned long long used = 0; };
+    GraphSlot graphs[8];          // small LRU keyed by (batch, point-count bucket, input buffer, NMS rule with the soft rule's parameters, projection on / off, class mode)
     unsigned long long graph_tick = 0;
     int graph_state = 0;          // 0: try, -1: capture failed once (use plain launches)
     std::vector<hipEvent_t> events;

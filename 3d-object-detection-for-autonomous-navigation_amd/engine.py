@@ -11,6 +11,7 @@ import weakref
 import numpy as np
 
 from . import _lib
+from . import soft_nms as _soft
 from .anchors import build_anchor_cells, build_anchors
 from .config import Derived
 from .weights import check_weights
@@ -19,7 +20,7 @@ _STATUS = {1: "PP_ERR_ARG", 2: "PP_ERR_STATE", 3: "PP_ERR_HIP", 4: "PP_ERR_SHAPE
            6: "PP_ERR_NUMERIC"}
 PP_ERR_NUMERIC = 6
 _PRECISIONS = {"split_f16": 0, "f32": 1}
-_NMS_MODES = {"standup": _lib.PP_NMS_STANDUP, "rotated": _lib.PP_NMS_ROTATED}
+_NMS_MODES = {"standup": _lib.PP_NMS_STANDUP, "rotated": _lib.PP_NMS_ROTATED, "soft": _lib.PP_NMS_SOFT}
 _CLASS_NMS = {"joint": _lib.PP_CLASS_NMS_JOINT, "per_class": _lib.PP_CLASS_NMS_PER_CLASS}
 
 
@@ -216,6 +217,10 @@ class Engine:
         self.weights_loaded = False
         if d.use_rotate_nms:
             self.set_nms_mode("rotated")
+        if d.soft_nms is not None:
+            self.set_soft_nms(**d.soft_nms)
+        if d.use_soft_nms:
+            self.set_nms_mode("soft")
         if d.use_multi_class_nms:
             self.set_class_nms("per_class")
         if weights is not None:
@@ -242,12 +247,36 @@ class Engine:
 
     # ---- suppression rule of the post-process (pp_set_nms_mode) ----
     def set_nms_mode(self, mode):
-        """'standup' (default: the reference's predict() rule, stand-up boxes with `+1` on metre widths) or 'rotated'
-        (rotate_nms_gpu's rule: rotated IoU of the decoded boxes).  Takes effect from the next predict / detect; the
-        config key model.second.use_rotate_nms selects 'rotated' at construction."""
+        """'standup' (default: the reference's predict() rule, stand-up boxes with `+1` on metre widths), 'rotated'
+        (rotate_nms_gpu's rule: rotated IoU of the decoded boxes) or 'soft' (soft_nms_jit's rule on the stand-up boxes: a
+        neighbour of a selected box keeps its place with a decayed score, see set_soft_nms).  Takes effect from the next
+        predict / detect; the config keys model.second.use_rotate_nms / use_soft_nms select 'rotated' / 'soft' at
+        construction.  'rotated' <-> 'soft' goes through 'standup': soft re-scoring on the rotated overlap is not built."""
         if mode not in _NMS_MODES:
             raise ValueError(f"mode must be one of {sorted(_NMS_MODES)}")
         self._check(self._lib.pp_set_nms_mode(self._h, _NMS_MODES[mode]), "pp_set_nms_mode")
+
+    # ---- parameters of the 'soft' rule (pp_set_soft_nms) ----
+    def set_soft_nms(self, method=None, sigma=None, score_floor=None):
+        """method 'hard' / 'linear' / 'gaussian' (default 'gaussian'), sigma of the Gaussian weight (0.5), score_floor under
+        which a re-scored box is dropped (0.001): soft_nms_jit's defaults.  None leaves a value as it is.  Read by the
+        'soft' mode only, from the next predict / detect; Nt is model.second.nms_iou_threshold."""
+        cur = self.soft_nms
+        m = _soft.method_id(cur["method"] if method is None else method)
+        try:
+            sg = float(cur["sigma"] if sigma is None else sigma)
+            fl = float(cur["score_floor"] if score_floor is None else score_floor)
+        except (TypeError, ValueError):
+            raise ValueError(f"sigma and score_floor must be numbers, got {sigma!r}, {score_floor!r}")
+        _soft.check_params(sg, fl)
+        self._check(self._lib.pp_set_soft_nms(self._h, m, ctypes.c_float(sg), ctypes.c_float(fl)), "pp_set_soft_nms")
+
+    @property
+    def soft_nms(self):
+        """{'method', 'sigma', 'score_floor'} of the 'soft' rule, as set (float32 values)."""
+        m, sg, fl = ctypes.c_int32(0), ctypes.c_float(0), ctypes.c_float(0)
+        self._check(self._lib.pp_get_soft_nms(self._h, ctypes.byref(m), ctypes.byref(sg), ctypes.byref(fl)), "pp_get_soft_nms")
+        return {"method": {v: k for k, v in _soft.METHODS.items()}[m.value], "sigma": sg.value, "score_floor": fl.value}
 
     @property
     def nms_mode(self):

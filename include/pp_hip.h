@@ -39,7 +39,8 @@ extern "C" {
  * pp_set_class_nms, pp_get_class_nms, pp_get_detection_rows; then PP_METRICS_COUNTS, pp_head_metrics,
  * pp_set_train_metrics, pp_get_train_metrics_enabled, pp_get_train_metrics; then pp_grad_clip_mode, pp_grad_clip_config,
  * pp_grad_clip_workspace_bytes, pp_grad_norm_device, pp_adamw_step_clipped_device; then pp_publish_stats,
- * pp_publish_train_weights, pp_publish_info. */
+ * pp_publish_train_weights, pp_publish_info; then PP_NMS_SOFT, pp_soft_nms_method, pp_set_soft_nms, pp_get_soft_nms,
+ * PP_SNMS_MAX_BOXES, pp_soft_nms. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -66,8 +67,20 @@ enum pp_nms_mode {
     PP_NMS_STANDUP = 0, /* default, the reference's predict(): the stand-up axis-aligned box of every decoded box, `+1` on
                          * widths measured in metres (iou_device) -- boxes within about 0.6 m of each other count as
                          * IoU > 0.5 */
-    PP_NMS_ROTATED = 1  /* rotate_nms_kernel's rule (second/core/non_max_suppression/nms_gpu.py:419-452, shipped by the
+    PP_NMS_ROTATED = 1, /* rotate_nms_kernel's rule (second/core/non_max_suppression/nms_gpu.py:419-452, shipped by the
                          * reference but never wired in): devRotateIoU of the decoded [x, y, w, l, r] */
+    PP_NMS_SOFT = 2     /* soft_nms_jit's rule (second/core/non_max_suppression/nms_cpu.py:79-169, compiled by the reference
+                         * but never called) on the stand-up boxes and their `+1` overlap: a neighbour of a selected box is
+                         * not deleted, its score is decayed by the overlap (pp_set_soft_nms) and the caller's score cut
+                         * decides */
+};
+
+/* How PP_NMS_SOFT and pp_soft_nms decay the score of a box that overlaps a selected one by `ov` (the reference's `method`
+ * values; Nt is the IoU threshold) */
+enum pp_soft_nms_method {
+    PP_SOFT_NMS_HARD = 0,     /* ov > Nt ? 0 : 1 -- with a floor above 0 the greedy rule */
+    PP_SOFT_NMS_LINEAR = 1,   /* ov > Nt ? 1 - ov : 1 */
+    PP_SOFT_NMS_GAUSSIAN = 2  /* exp(-ov * ov / sigma) */
 };
 
 /* How the detector's post-process treats more than one class (pp_set_class_nms) */
@@ -253,6 +266,19 @@ int pp_get_gemm_precision(pp_handle h, int32_t* precision);
  * then stays as it was).  The rule is part of what a captured pass is keyed on: a change captures once more. */
 int pp_set_nms_mode(pp_handle h, int32_t mode);
 int pp_get_nms_mode(pp_handle h, int32_t* mode);
+/* Parameters of PP_NMS_SOFT (they are kept, but read by no other mode): method (enum pp_soft_nms_method), sigma of the
+ * Gaussian weight, and score_floor, the score under which a re-scored box is dropped.  Defaults: PP_SOFT_NMS_GAUSSIAN,
+ * 0.5, 0.001 (soft_nms_jit's); Nt is nms_iou_threshold.  In that mode the first min(100, nms_pre_max_size) candidates go
+ * through the rounds of pp_soft_nms (equal current scores: the earlier candidate, i.e. the lower anchor index, first), at
+ * most nms_post_max_size selections are returned in selection order, and pp_detection.score is the decayed score;
+ * everything else of the post-process is the same.  With PP_SOFT_NMS_HARD, a floor > 0 below every score and Nt =
+ * nms_iou_threshold the mode returns the default mode's bytes.  Takes effect from the next pp_detect* / pp_predict.
+ * PP_ERR_ARG for an unknown method, a sigma that is not finite or <= 0, a floor that is not finite or < 0 (the settings
+ * then stay as they were); PP_ERR_STATE while a training step is in flight.  The three values are part of what a captured
+ * pass is keyed on.  pp_set_nms_mode between PP_NMS_ROTATED and PP_NMS_SOFT is PP_ERR_UNSUPPORTED (soft re-scoring on the
+ * rotated overlap is not built): go through PP_NMS_STANDUP. */
+int pp_set_soft_nms(pp_handle h, int32_t method, float sigma, float score_floor);
+int pp_get_soft_nms(pp_handle h, int32_t* method, float* sigma, float* score_floor);
 /* Image boxes of the kept detections, computed at the end of this handle's post-process (pp_predict and the fused path):
  * box3d_to_bbox of second/core/box_np_ops.py:849-857 -- the eight corners of box3d_camera projected by the frame's P2,
  * min / max over them, float64 -- which the reference's predict() replaced by a constant (model/voxelnet.py:1336-1360).
@@ -364,6 +390,26 @@ int pp_d3_box_overlap(int device, const double* boxes, int64_t n, const double* 
  * bytes on every run. */
 int pp_rotate_nms(int device, const float* dets, int64_t n, float iou_threshold, int32_t pre_max_size,
                   int32_t post_max_size, int32_t* keep, int64_t* n_keep);
+
+/* ---- Soft-NMS -------------------------------- */
+
+#define PP_SNMS_MAX_BOXES 4096 /* most boxes that enter the rounds (after pre_max_size): they stay in one workgroup's LDS */
+
+/* Replaces soft_nms_jit (second/core/non_max_suppression/nms_cpu.py:79-169) with the caps of nms() around it
+ * (libraries/eval_helper_functions.py:463-492).  dets [n,5] float32 rows (x1, y1, x2, y2, score).  pre_max_size <= 0: every
+ * box goes in, otherwise the min(n, pre_max_size) best by score (equal scores: lower index first).  Each round selects the
+ * alive box with the largest current score (equal scores: lower index first) -- that score is final -- and multiplies the
+ * score of every other alive box whose `+1` overlap with it has positive width and height by the method's weight (enum
+ * pp_soft_nms_method; float64 as numba types it, rounded to float32 once); a box re-scored to below score_floor is
+ * dropped, a box that never overlaps a selected one is never dropped.  At most post_max_size rounds (<= 0: no cap).  keep
+ * and scores: room for min(n, pre_max_size, post_max_size) entries (caps <= 0 not counted) -- int32 indices into dets in
+ * selection order and the final scores, which are non-increasing; *n_keep their number.  n = 0 is PP_OK with *n_keep = 0.
+ * PP_ERR_ARG for a non-finite score (checked on the host, nothing launched), an unknown method, a sigma that is not finite
+ * or <= 0, a floor that is not finite or < 0, or more than PP_SNMS_MAX_BOXES boxes entering.  Stateless; host pointers;
+ * `device` is the HIP device.  The same input gives the same bytes on every run. */
+int pp_soft_nms(int device, const float* dets, int64_t n, int32_t method, float sigma, float iou_threshold,
+                float score_floor, int32_t pre_max_size, int32_t post_max_size, int32_t* keep, float* scores,
+                int64_t* n_keep);
 
 /* ---- image boxes of camera-frame boxes ------- */
 
