@@ -15,19 +15,13 @@
 //                     counts; then the frame offsets
 //   k_ingest_scatter  re-reads the chunks; a finite record's rank is its chunk's base + the finite lanes below it
 #include "pp_common.h"
+#include "ingest_dev.h"
 
 namespace {
 
 constexpr int ING_ITER = 8;                       // 64-record steps of a wave
 constexpr int ING_CHUNK = PP_WAVE * ING_ITER;     // records per chunk (one wave)
 constexpr int ING_WAVES = 4;                      // chunks per workgroup
-
-// four bytes at any address (nothing in a message is assumed to sit on a boundary): one unaligned dword load
-__device__ __forceinline__ uint32_t ing_load32(const uint8_t* p) {
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
 
 // one coordinate as float64 (a float32 field widens exactly)
 __device__ __forceinline__ double ing_coord(const uint8_t* p, const IngFrame& f) {
@@ -81,48 +75,13 @@ __global__ __launch_bounds__(PP_WAVE * ING_WAVES) void k_ingest_count(const uint
     if (lane == 0) chunk_cnt[(size_t)b * stride + c] = cnt;
 }
 
-// One workgroup of 16 waves; wave w scans frames w, w + 16, ...; thread 0 then sums the kept counts into the offsets.
+// One workgroup of 16 waves; wave w scans frames w, w + 16, ...; thread 0 then sums the kept counts into the offsets
+// (ingest_dev.h: the depth-image ingest runs the same scan).
 __global__ __launch_bounds__(1024) void k_ingest_scan(const IngFrame* __restrict__ frames, int batch, int stride,
                                                       int first, int decimate, const int* __restrict__ chunk_cnt,
                                                       int* __restrict__ chunk_base, int* __restrict__ finite,
                                                       int* __restrict__ kept, int* __restrict__ offsets) {
-    const int lane = threadIdx.x & (PP_WAVE - 1), wave = threadIdx.x >> 6;
-    for (int b = wave; b < batch; b += 16) {
-        const int nchunks = frames[b].nchunks;
-        int carry = 0;
-        for (int c0 = 0; c0 < nchunks; c0 += PP_WAVE) {
-            const int c = c0 + lane;
-            const int v = c < nchunks ? chunk_cnt[(size_t)b * stride + c] : 0;
-            const int incl = wave_inclusive_scan(v);
-            if (c < nchunks) chunk_base[(size_t)b * stride + c] = carry + incl - v;
-            carry += __builtin_amdgcn_readlane(incl, PP_WAVE - 1);
-        }
-        if (lane == 0) {
-            finite[b] = carry;
-            kept[b] = carry > first ? (carry - first + decimate - 1) / decimate : 0;
-        }
-    }
-    __threadfence_block();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int off = 0;
-        offsets[0] = 0;
-        for (int b = 0; b < batch; ++b) { off += kept[b]; offsets[b + 1] = off; }
-    }
-}
-
-struct IngXform { double r[9], r2[9], lift[3]; };
-
-// ((p . r) . r2) + lift, each sum left to right, products and sums rounded separately
-__device__ __forceinline__ void ing_transform(const double p[3], const IngXform& x, float out[3]) {
-#pragma clang fp contract(off)
-    double q[3], s[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) q[j] = (p[0] * x.r[j] + p[1] * x.r[3 + j]) + p[2] * x.r[6 + j];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) s[j] = (q[0] * x.r2[j] + q[1] * x.r2[3 + j]) + q[2] * x.r2[6 + j];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) out[j] = (float)(s[j] + x.lift[j]);
+    ingest_scan_frames(frames, batch, stride, first, decimate, chunk_cnt, chunk_base, finite, kept, offsets);
 }
 
 __global__ __launch_bounds__(PP_WAVE * ING_WAVES) void k_ingest_scatter(const uint8_t* __restrict__ raw,
@@ -172,9 +131,7 @@ void launch_ingest(const IngestParams& p, hipStream_t s) {
     PP_LAUNCH("k_ingest_scan", k_ingest_scan, dim3(1), dim3(1024), 0, s, p.frames, p.batch, p.stride, p.first, p.decimate,
               p.chunk_cnt, p.chunk_base, p.finite, p.kept, p.offsets);
     if (p.stride > 0) {
-        IngXform xf;
-        for (int i = 0; i < 9; ++i) { xf.r[i] = p.r[i]; xf.r2[i] = p.r2[i]; }
-        for (int i = 0; i < 3; ++i) xf.lift[i] = p.lift[i];
+        const IngXform xf = ing_xform_of(p);
         PP_LAUNCH("k_ingest_scatter", k_ingest_scatter, grid, block, 0, s, p.raw, p.frames, p.stride, p.first, p.decimate,
                   xf, p.chunk_base, p.offsets, p.out, p.out_rows);
     }

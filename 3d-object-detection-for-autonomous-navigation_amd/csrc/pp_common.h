@@ -523,22 +523,39 @@ struct IngFrame {              // one message of a call, as the kernels see it
     int f64, big_endian;       // FLOAT64 fields (else FLOAT32); byte order
     int nchunks;               // ingest_chunks(n_rec)
 };
-struct IngestParams {
+// depth_ingest.hip: raw depth images (sensor_msgs/Image, 16UC1 or 32FC1) -> the same resident points and offsets
+struct DepthFrame {            // one image of a call, as the kernels see it
+    long long byte_off;        // its first byte within the staged bytes
+    int width, n_pix;          // pixels per row (the true width: the deprojection needs row and column); pixels in all
+    int row_step;              // bytes per row
+    int tight;                 // pixel i sits at i * itemsize (no row padding): no division for its address
+    int f32, big_endian;       // 32FC1 metres (else 16UC1 units of depth_scale); byte order
+    int nchunks;               // depth_chunks(n_pix)
+    float fx, fy, ppx, ppy;    // pinhole intrinsics
+    float depth_scale;         // metres per unit of a 16UC1 pixel
+    float z_min, z_max;        // a pixel is valid only when z > z_min && z <= z_max
+};
+template <typename Frame>
+struct IngestParamsT {
     const uint8_t* raw;        // the messages' bytes, staged on the device
-    const IngFrame* frames;    // [batch]
+    const Frame* frames;       // [batch]
     int batch, stride;         // stride: chunks of the largest frame (row length of the two chunk tables)
     int first, decimate;
     double r[9], r2[9], lift[3];
-    int* chunk_cnt;            // [batch][stride] finite records per chunk
-    int* chunk_base;           // [batch][stride] finite records of the frame in front of the chunk
-    int* finite;               // [batch] out: finite records
+    int* chunk_cnt;            // [batch][stride] finite records (valid pixels) per chunk
+    int* chunk_base;           // [batch][stride] finite records (valid pixels) of the frame in front of the chunk
+    int* finite;               // [batch] out: finite records (valid pixels)
     int* kept;                 // [batch] out: points written
     int* offsets;              // [batch + 1] out: the frames' row offsets in `out`
     float* out;                // [sum kept][3]
     long long out_rows;        // rows `out` holds
 };
+typedef IngestParamsT<IngFrame> IngestParams;
+typedef IngestParamsT<DepthFrame> DepthIngestParams;
 int ingest_chunks(int n_rec);
 void launch_ingest(const IngestParams& p, hipStream_t s);
+int depth_chunks(int n_pix);
+void launch_depth_ingest(const DepthIngestParams& p, hipStream_t s);
 
 // frustum_crop.hip: the resident frames cropped to the camera frustum (frustum.py), frames compacted in order
 struct CropParams {

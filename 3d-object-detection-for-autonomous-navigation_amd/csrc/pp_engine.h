@@ -1,6 +1,6 @@
 // Host side of the C-ABI (include/pp_hip.h), shared by its translation units: the handle, the error / allocation
 // helpers and what one unit calls in another.  pp_api.hip: lifetime, weights, feeds, the inference pipeline;
-// api_ingest.hip: PointCloud2 ingest; api_crop.hip: the frustum crop; api_train.hip: loss, training step, optimizer; api_dataprep.hip: targets,
+// api_ingest.hip: PointCloud2 and depth-image ingest; api_crop.hip: the frustum crop; api_train.hip: loss, training step, optimizer; api_dataprep.hip: targets,
 // augmentation, GT sampling, object database; api_eval.hip: the AP evaluator (needs no handle); api_nms.hip: the detector's NMS rule and the standalone rotated NMS;
 // api_project.hip: the detector's image boxes and the standalone projection; api_class_nms.hip: joint / per-class suppression;
 // api_metrics.hip: the training metrics' counts; api_publish.hip: a trainer's weights into the detector, on the device.
@@ -197,12 +197,13 @@ struct pp_engine {
         long long* off = nullptr;          // [B * PP_MAX_GT_PER_FRAME + 1]
         float* out = nullptr;  size_t cap_out = 0;   // the cut-out points grow to the largest build seen (dgrow)
     } gdb;
-    struct Ing {                           // live PointCloud2 ingest (pp_ingest_pointcloud2*); raw / chunks grow (dgrow)
-        uint8_t* raw = nullptr;  size_t cap_raw = 0;       // the messages' bytes
+    struct Ing {                           // live-camera ingest (pp_ingest_pointcloud2*, pp_ingest_depth*); raw / chunks grow (dgrow)
+        union Slot { IngFrame pc2; DepthFrame depth; };    // room for a frame of either feed (a call packs its own type tightly)
+        uint8_t* raw = nullptr;  size_t cap_raw = 0;       // the messages' (images') bytes
         int* chunks = nullptr;   size_t cap_chunks = 0;    // [2][batch * stride]: chunk counts, chunk bases
-        IngFrame* frames = nullptr;        // [B]
-        IngFrame* h_ring = nullptr;        // pinned [OFF_RING][B]: travels with the offsets' ring slots
-        int *finite = nullptr, *kept = nullptr;            // [B]
+        Slot* frames = nullptr;            // [B]
+        Slot* h_ring = nullptr;            // pinned [OFF_RING][B]: travels with the offsets' ring slots
+        int *finite = nullptr, *kept = nullptr;            // [B] finite records (valid pixels), points kept
         int batch = 0;                     // frames of the last ingest (pp_ingest_info)
     } ing;
     struct Crop {                          // frustum crop of the resident frames (pp_frustum_crop*; api_crop.hip: ensure_crop)

@@ -120,6 +120,9 @@ class MessageStaging:
         from . import ingest
         tuples = [ingest.as_tuple(m) for m in msgs]
         self.byte_offsets, self.layouts, bufs = _pack_messages(tuples)
+        self._fill(lib, bufs)
+
+    def _fill(self, lib, bufs):
         self._pinned = PinnedArray(lib, (max(int(self.byte_offsets[-1]), 4),), np.uint8)
         self.bytes = self._pinned.array
         for b, buf in enumerate(bufs):
@@ -144,6 +147,48 @@ class MessageStaging:
             self.close()
         except Exception:
             pass
+
+
+class DepthStaging(MessageStaging):
+    """The bytes of a batch of depth images (sensor_msgs/Image, 16UC1 / mono16 / 32FC1) in one page-locked buffer: what
+    `Engine.ingest_depth_async` takes.  `.bytes` may be refilled in place between uses by images of the same geometry;
+    `.images`: their (width, height, step, encoding, is_bigendian).  The intrinsics are given with each ingest, so
+    there is no `.layouts`."""
+
+    def __init__(self, lib, images):
+        from . import ingest
+        tuples = [ingest.image_as_tuple(m) for m in images]
+        self.byte_offsets, bufs = _pack_images(tuples)
+        self.images = [t[1:] for t in tuples]
+        self.layouts = None
+        self._fill(lib, bufs)
+
+
+def _pack_images(tuples):
+    """[(data, width, height, step, encoding, is_bigendian)] -> (byte_offsets [B + 1] int64, the images' byte views cut to
+    height * step)."""
+    offs = np.zeros((len(tuples) + 1,), np.int64)
+    bufs = []
+    for b, t in enumerate(tuples):
+        buf = np.frombuffer(t[0], dtype=np.uint8)[:t[2] * t[3]]
+        bufs.append(buf)
+        offs[b + 1] = offs[b] + buf.size
+    return offs, bufs
+
+
+def _depth_layouts(tuples, intrinsics, depth_scale, z_min, z_max):
+    """The ctypes array of pp_depth_layout of a batch of images.  intrinsics: one set for the batch (anything
+    `ingest.intrinsics_of` takes), or a list with one set per frame."""
+    from . import ingest
+    per_frame = isinstance(intrinsics, list) and not (len(intrinsics) in (4, 9) and all(np.ndim(v) == 0 for v in intrinsics))
+    if per_frame and len(intrinsics) != len(tuples):
+        raise ValueError(f"{len(intrinsics)} sets of intrinsics for {len(tuples)} images")
+    layouts = (_lib.PPDepthLayout * max(len(tuples), 1))()
+    for b, t in enumerate(tuples):
+        lay = ingest.depth_layout_of(t, intrinsics[b] if per_frame else intrinsics, depth_scale, z_min, z_max)
+        for k in ingest.DEPTH_LAYOUT_KEYS:
+            setattr(layouts[b], k, lay[k])
+    return layouts
 
 
 def _pack_messages(tuples):
@@ -696,6 +741,65 @@ class Engine:
         self.ingest_pointcloud2(msgs)
         if rect is not None:
             self.set_calib(rect, trv2c, len(msgs))
+        return self._detect_resident(on_numeric)
+
+    # ---- depth-image ingest (pp_ingest_depth*; ingest.py states the rule) ----
+    def ingest_depth(self, images, intrinsics, first=1, decimate=4, lift=None, depth_scale=0.001, z_min=0.0, z_max=np.inf,
+                     return_points=False):
+        """Raw depth images (sensor_msgs/Image: 16UC1 / mono16 units of `depth_scale`, or 32FC1 metres) -> the engine's
+        resident frames, on the GPU: valid pixels deprojected through the pinhole `intrinsics`, every `decimate`-th from
+        index `first`, turned into lidar axes and lifted -- `ingest.depth_ingest_np` exactly, i.e. what
+        ingest_pointcloud2 gives for the message a point-cloud node computes from the image
+        (`ingest.depth_to_pointcloud2`).  images: list of images (`ingest.image_as_tuple`); intrinsics: one set for the
+        batch (`ingest.intrinsics_of`: a CameraInfo, (K, D) or (fx, fy, ppx, ppy)) or a list with one per frame; a pixel
+        is valid only when z_min < z <= z_max.  The engine needs max_points_per_frame >=
+        ingest.depth_kept_bound(width, height, first, decimate).  No host fallback; return_points as ingest_pointcloud2;
+        ingest_info() reads the valid and kept counts back."""
+        from . import ingest
+        tuples = [ingest.image_as_tuple(m) for m in images]
+        layouts = _depth_layouts(tuples, intrinsics, depth_scale, z_min, z_max)
+        offs, bufs = _pack_images(tuples)
+        data = (bufs[0] if len(bufs) == 1 else np.concatenate(bufs)) if bufs and offs[-1] else np.zeros((1,), np.uint8)
+        cfg = _ingest_config(first, decimate, ingest.SENSOR_HEIGHT if lift is None else lift)
+        pts, cap = None, 0
+        if return_points:
+            cap = sum(ingest.depth_kept_bound(t[1], t[2], max(int(first), 0), max(int(decimate), 1)) for t in tuples)
+            pts = np.empty((max(cap, 1), 3), np.float32)
+        self._check(self._lib.pp_ingest_depth(self._h, _ptr(data), _ptr(offs), layouts, len(tuples), ctypes.byref(cfg),
+                                              _ptr(pts), ctypes.c_int64(cap)), "pp_ingest_depth")
+        self._offsets = None          # the resident frames' sizes are device values (ingest_info reads them back)
+        self._ing_batch = len(tuples)
+        if not return_points:
+            return None
+        off = np.concatenate([[0], np.cumsum(self.ingest_info()["kept"])])
+        return [pts[off[b]:off[b + 1]].copy() for b in range(len(tuples))]
+
+    def staging_depth(self, images):
+        """Packs depth images into a page-locked DepthStaging for ingest_depth_async (the counterpart of staging())."""
+        return DepthStaging(self._lib, images)
+
+    def ingest_depth_async(self, staging, intrinsics, first=1, decimate=4, lift=None, depth_scale=0.001, z_min=0.0,
+                           z_max=np.inf):
+        """ingest_depth without waiting (pp_ingest_depth_async), from a DepthStaging: as ingest_pointcloud2_async, and
+        mixes freely with it and with upload_async."""
+        from . import ingest
+        tuples = [(staging.bytes[staging.byte_offsets[b]:staging.byte_offsets[b + 1]],) + tuple(g)
+                  for b, g in enumerate(staging.images)]
+        layouts = _depth_layouts(tuples, intrinsics, depth_scale, z_min, z_max)
+        cfg = _ingest_config(first, decimate, ingest.SENSOR_HEIGHT if lift is None else lift)
+        self._check(self._lib.pp_ingest_depth_async(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets), layouts,
+                                                    len(tuples), ctypes.byref(cfg)), "pp_ingest_depth_async")
+        self._offsets = None
+        self._ing_batch = len(tuples)
+        staging._users.add(self)
+        self._staged.append(staging)      # kept alive while a copy may still read it (see upload_async)
+
+    def detect_depth(self, images, intrinsics, rect=None, trv2c=None, on_numeric="f32"):
+        """ingest_depth + detect_async + sync + detections: `detect_pointcloud2` for the depth images the messages are
+        computed from.  rect / trv2c / on_numeric as `detect`."""
+        self.ingest_depth(images, intrinsics)
+        if rect is not None:
+            self.set_calib(rect, trv2c, len(images))
         return self._detect_resident(on_numeric)
 
     def intermediates(self, canvas=False):

@@ -27,6 +27,10 @@ The functions above are the host restatement and the yardstick.  The live path i
 of the finite flags for NaN removal and decimation together, the two products summed left to right without fused
 multiply-adds -- which `ingest_np` assembles; the tests hold all of them to `realsense_to_lidar(pointcloud2_to_xyz(...))`
 bit for bit.
+
+The second half of the module is the same for depth images (`Engine.ingest_depth` / `detect_depth`,
+csrc/depth_ingest.hip): the image the camera's point-cloud topic is computed from goes to the GPU instead of the
+message, `depth_to_xyz` / `depth_ingest_np` state the rule, and `depth_to_pointcloud2` builds the message it is held to.
 """
 import numpy as np
 
@@ -191,3 +195,167 @@ def ingest_np(msg, first=1, decimate=4, lift=SENSOR_HEIGHT):
     fin = np.isfinite(xyz).all(axis=1)
     keep = select_np(fin, first, decimate)
     return transform_ordered64(xyz[keep], lift).astype(np.float32), int(fin.sum())
+
+
+# ---- depth images (Engine.ingest_depth / detect_depth, csrc/depth_ingest.hip) ---------------------------------------
+# The d435i's point-cloud topic is computed on the robot's CPU from a 16-bit depth image a tenth to a sixteenth of its
+# size.  The functions below state the rule that takes the image itself to the resident points:
+#
+#   16UC1 / mono16: z = depth_scale * float32(d), one float32 product; valid when d != 0
+#   32FC1:          z is the stored value; valid when it is finite and > 0 (depth_scale is not applied: REP 118)
+#   both:           valid only when z > z_min and z <= z_max (0 and +inf leave the conditions above as they are)
+#   a valid pixel (v, u) is the float32 point x = z * ((u - ppx) / fx), y = z * ((v - ppy) / fy), z -- every operation
+#   rounded separately: the pinhole (no distortion) case of the camera vendor's published rs2_deproject_pixel_to_point
+#
+# PARITY WITH THE BYTES THE CAMERA DRIVER'S POINT-CLOUD BLOCK PUBLISHES IS NOT PINNED: neither the vendor library nor its
+# ROS node is available to this project's tests.  What is pinned is everything behind the point: `depth_ingest_np` (and
+# the GPU path) equals `realsense_to_lidar(pointcloud2_to_xyz(*depth_to_pointcloud2(...)), decimate, first, lift)` bit for
+# bit.  Not done, and refused by name rather than approximated: lens distortion (`intrinsics_of`), alignment of depth to
+# the colour stream, dropping points by texture coordinate, RGB or any feature beyond x y z, the vendor's filters.
+
+DEPTH_ENCODINGS = {"16UC1": ("u2", 0), "mono16": ("u2", 0), "32FC1": ("f4", 1)}     # name -> (numpy type, PP_DEPTH_*)
+DEPTH_LAYOUT_KEYS = ("width", "height", "row_step", "encoding", "is_bigendian", "fx", "fy", "ppx", "ppy", "depth_scale",
+                     "z_min", "z_max")
+
+
+def image_as_tuple(msg):
+    """A depth image as (data, width, height, step, encoding, is_bigendian).  msg: that tuple already (is_bigendian
+    optional), or any object with those attributes -- a sensor_msgs/Image (ROS is not imported)."""
+    if isinstance(msg, (tuple, list)):
+        if len(msg) not in (5, 6):
+            raise ValueError(f"an Image tuple has 5 or 6 entries (data, width, height, step, encoding[, is_bigendian]), "
+                             f"got {len(msg)}")
+        t = tuple(msg) + ((False,) if len(msg) == 5 else ())
+    else:
+        t = (msg.data, msg.width, msg.height, msg.step, msg.encoding, getattr(msg, "is_bigendian", False))
+    return (t[0], int(t[1]), int(t[2]), int(t[3]), str(t[4]), bool(t[5]))
+
+
+def intrinsics_of(camera_info):
+    """fx, fy, ppx, ppy as float32 (K[0], K[4], K[2], K[5] of the float64 K, cast once).  camera_info: a
+    sensor_msgs/CameraInfo (attributes K and D, or k and d), a (K, D) or (K,) tuple with K of 9 entries, or the four
+    numbers (fx, fy, ppx, ppy) themselves.  A non-zero distortion coefficient D is refused: the deprojection is the
+    pinhole one (the d435i depth stream's coefficients are zero)."""
+    K = D = None
+    if isinstance(camera_info, (tuple, list, np.ndarray)):
+        if len(camera_info) == 4 and all(np.ndim(v) == 0 for v in camera_info):
+            fx, fy, ppx, ppy = (np.float32(v) for v in camera_info)
+            return fx, fy, ppx, ppy
+        if isinstance(camera_info, np.ndarray) or len(camera_info) not in (1, 2):
+            K = camera_info
+        else:
+            K = camera_info[0]
+            D = camera_info[1] if len(camera_info) == 2 else None
+    else:
+        K = getattr(camera_info, "K", None)
+        K = getattr(camera_info, "k", None) if K is None else K
+        D = getattr(camera_info, "D", None)
+        D = getattr(camera_info, "d", None) if D is None else D
+        if K is None:
+            raise ValueError("intrinsics_of: no K in the camera info")
+    K = np.asarray(K, np.float64).reshape(-1)
+    if K.size != 9:
+        raise ValueError(f"intrinsics_of: K has {K.size} entries, 9 expected")
+    if D is not None:
+        D = np.asarray(D, np.float64).reshape(-1)
+        if np.any(D != 0.0) or np.any(np.isnan(D)):
+            raise ValueError(f"intrinsics_of: D {D.tolist()} has a non-zero distortion coefficient; only the pinhole "
+                             "model is supported")
+    return np.float32(K[0]), np.float32(K[4]), np.float32(K[2]), np.float32(K[5])
+
+
+def depth_layout_of(image, intrinsics, depth_scale=0.001, z_min=0.0, z_max=np.inf):
+    """The pp_depth_layout fields of one frame (DEPTH_LAYOUT_KEYS) as a dict; `image_as_tuple` and `intrinsics_of` say
+    what the first two arguments are.  Raises a ValueError that names the field for: step < width * itemsize, an unknown
+    encoding, fx or fy zero or non-finite, ppx or ppy non-finite, depth_scale <= 0 or non-finite on 16UC1, z_min > z_max,
+    a data buffer shorter than height * step."""
+    data, width, height, step, encoding, big = image_as_tuple(image)
+    if encoding not in DEPTH_ENCODINGS:
+        raise ValueError(f"encoding {encoding!r} is not a depth encoding ({', '.join(DEPTH_ENCODINGS)})")
+    typ, code = DEPTH_ENCODINGS[encoding]
+    size = np.dtype(typ).itemsize
+    if width < 0 or height < 0:
+        raise ValueError(f"width {width}, height {height}")
+    if step < width * size:
+        raise ValueError(f"step {step} < width {width} x {size} bytes")
+    have = np.frombuffer(data, dtype=np.uint8).size
+    if have < height * step:
+        raise ValueError(f"Image data holds {have} bytes, {height} rows of step {step} needed")
+    fx, fy, ppx, ppy = intrinsics_of(intrinsics)
+    for name, v in (("fx", fx), ("fy", fy)):
+        if not np.isfinite(v) or v == 0:
+            raise ValueError(f"{name} {v} is not a finite non-zero focal length")
+    for name, v in (("ppx", ppx), ("ppy", ppy)):
+        if not np.isfinite(v):
+            raise ValueError(f"{name} {v} is not finite")
+    scale, lo, hi = np.float32(depth_scale), np.float32(z_min), np.float32(z_max)
+    if code == 0 and not (np.isfinite(scale) and scale > 0):
+        raise ValueError(f"depth_scale {depth_scale} is not a finite positive number")
+    if not lo <= hi:
+        raise ValueError(f"z_min {z_min} > z_max {z_max}")
+    return {"width": width, "height": height, "row_step": step, "encoding": code, "is_bigendian": int(big),
+            "fx": float(fx), "fy": float(fy), "ppx": float(ppx), "ppy": float(ppy), "depth_scale": float(scale),
+            "z_min": float(lo), "z_max": float(hi)}
+
+
+def _depth_planes(image, intrinsics, depth_scale, z_min, z_max):
+    """Rule 2-3 for every pixel: (x, y, z float32 [height, width], valid bool [height, width])."""
+    lay = depth_layout_of(image, intrinsics, depth_scale, z_min, z_max)
+    data, width, height, step, encoding, big = image_as_tuple(image)
+    typ = np.dtype((">" if big else "<") + DEPTH_ENCODINGS[encoding][0])
+    rows = np.frombuffer(data, dtype=np.uint8)[:height * step].reshape(height, step)[:, :width * typ.itemsize]
+    raw = np.ascontiguousarray(rows).view(typ).reshape(height, width)
+    f32 = np.float32
+    with np.errstate(all="ignore"):
+        if lay["encoding"] == 0:
+            z = f32(lay["depth_scale"]) * raw.astype(f32)
+            valid = raw != 0
+        else:
+            z = raw.astype(f32)
+            valid = np.isfinite(z) & (z > 0)
+        valid = valid & (z > f32(lay["z_min"])) & (z <= f32(lay["z_max"]))
+        tx = (np.arange(width, dtype=f32) - f32(lay["ppx"])) / f32(lay["fx"])
+        ty = (np.arange(height, dtype=f32) - f32(lay["ppy"])) / f32(lay["fy"])
+        x = z * tx[None, :]
+        y = z * ty[:, None]
+    return x, y, z, valid
+
+
+def depth_to_xyz(image, intrinsics, depth_scale=0.001, z_min=0.0, z_max=np.inf):
+    """The float32 [N, 3] camera-frame points (x right, y down, z depth) of the valid pixels of a depth image, in
+    row-major order: the rule at the head of this section in numpy float32."""
+    x, y, z, valid = _depth_planes(image, intrinsics, depth_scale, z_min, z_max)
+    return np.stack([x[valid], y[valid], z[valid]], axis=-1).astype(np.float32).reshape(-1, 3)
+
+
+def depth_to_pointcloud2(image, intrinsics, depth_scale=0.001, z_min=0.0, z_max=np.inf, ordered=False, point_step=16):
+    """The message tuple (`as_tuple`) a point-cloud node would publish for the image: FLOAT32 x y z at offsets 0 / 4 / 8 of
+    `point_step`-byte records, little-endian.  Unordered: the valid pixels only, height 1.  Ordered: every pixel, width x
+    height as the image, the invalid ones NaN."""
+    if point_step < 12:
+        raise ValueError(f"point_step {point_step} < 12")
+    x, y, z, valid = _depth_planes(image, intrinsics, depth_scale, z_min, z_max)
+    if ordered:
+        xyz = np.stack([x, y, z], axis=-1).astype(np.float32).reshape(-1, 3)
+        xyz[~valid.reshape(-1)] = np.nan
+        height, width = valid.shape
+    else:
+        xyz = np.stack([x[valid], y[valid], z[valid]], axis=-1).astype(np.float32).reshape(-1, 3)
+        height, width = 1, len(xyz)
+    rec = np.zeros((len(xyz), point_step), np.uint8)
+    rec[:, :12] = np.ascontiguousarray(xyz.astype("<f4")).view(np.uint8).reshape(len(xyz), 12)
+    fields = [("x", 0, 7, 1), ("y", 4, 7, 1), ("z", 8, 7, 1)]
+    return (rec.tobytes(), width, height, int(point_step), width * int(point_step), fields, False)
+
+
+def depth_kept_bound(width, height, first=1, decimate=4):
+    """Most points a width x height depth image can keep: `kept_bound` of its pixels."""
+    return kept_bound(width, height, first, decimate)
+
+
+def depth_ingest_np(image, intrinsics, first=1, decimate=4, lift=SENSOR_HEIGHT, depth_scale=0.001, z_min=0.0, z_max=np.inf):
+    """What the GPU depth ingest computes for one image, on the host by its own rule: `depth_to_xyz` -> `select_np` ->
+    `transform_ordered64` -> float32.  Returns (points [kept, 3] float32, valid pixels)."""
+    xyz = depth_to_xyz(image, intrinsics, depth_scale, z_min, z_max)
+    keep = select_np(np.ones(len(xyz), bool), first, decimate)
+    return transform_ordered64(xyz[keep], lift).astype(np.float32), len(xyz)

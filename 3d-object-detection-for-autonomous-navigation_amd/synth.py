@@ -112,3 +112,50 @@ def pointcloud2_message(frame, width=640, height=480, point_step=20, row_pad=0, 
     bad = rng.random(n) < nan_fraction
     cam[bad, rng.integers(0, 3, int(bad.sum()))] = np.nan
     return pointcloud2_from_xyz(cam, width, height, point_step, row_pad, datatype, bigendian, offsets, seed + int(frame))
+
+
+def depth_from_z(z, encoding="16UC1", step_pad=0, bigendian=False, depth_scale=0.001, seed=977):
+    """[height, width] depths in metres (0 / NaN / inf / negatives allowed for 32FC1; 16UC1 stores round(z / depth_scale),
+    0 for an invalid pixel) -> a sensor_msgs/Image as the tuple `ingest.image_as_tuple` gives: (data, width, height, step,
+    encoding, is_bigendian).  Rows are padded by `step_pad` random bytes."""
+    rng = np.random.default_rng(seed)
+    z = np.asarray(z)
+    height, width = z.shape
+    if encoding == "32FC1":
+        dt = np.dtype((">" if bigendian else "<") + "f4")
+        px = z.astype(dt)
+    else:
+        dt = np.dtype((">" if bigendian else "<") + "u2")
+        with np.errstate(invalid="ignore"):
+            units = np.where(np.isfinite(z) & (z > 0), np.rint(np.asarray(z, np.float64) / depth_scale), 0.0)
+        px = np.clip(units, 0, 65535).astype(dt)
+    step = width * dt.itemsize + int(step_pad)
+    rows = rng.integers(0, 256, (height, step), dtype=np.uint8)
+    rows[:, :width * dt.itemsize] = np.ascontiguousarray(px).view(np.uint8).reshape(height, width * dt.itemsize)
+    return (rows.tobytes(), int(width), int(height), step, encoding, bool(bigendian))
+
+
+def depth_image(frame, width=640, height=480, encoding="16UC1", step_pad=0, bigendian=False, invalid_fraction=0.3,
+                depth_scale=0.001, scale=1.0, seed=977):
+    """A seeded depth image of a d435i-like camera 1 m above a floor, looking at a wall 7 m away with a few person-sized
+    columns in front of it (all distances times `scale`: a small grid wants a small scene); `invalid_fraction` of the
+    pixels are 0 (no depth), as a stereo camera's holes are.  Returns
+    (image tuple of `depth_from_z`, (fx, fy, ppx, ppy))."""
+    rng = np.random.default_rng(seed + int(frame))
+    fx = fy = 0.6 * max(width, 1)
+    ppx, ppy = 0.5 * width - 0.5 + 0.37, 0.5 * height - 0.5 - 0.21
+    tx = (np.arange(width) - ppx) / fx
+    ty = (np.arange(height) - ppy) / fy
+    z = np.full((height, width), 7.0)
+    with np.errstate(divide="ignore"):
+        floor = np.where(ty > 1e-3, 1.0 / np.maximum(ty, 1e-3), np.inf)
+    z = np.minimum(z, floor[:, None])
+    for _ in range(4):
+        depth, cx, half = rng.uniform(2.0, 5.5), rng.uniform(-1.5, 1.5), rng.uniform(0.2, 0.35)
+        cols = np.abs(tx * depth - cx) < half
+        rows_ = (ty * depth > -0.7) & (ty * depth < 1.0)
+        z = np.where(rows_[:, None] & cols[None, :], np.minimum(z, depth), z)
+    z = (z + 0.01 * rng.standard_normal(z.shape)) * scale
+    z[rng.random(z.shape) < invalid_fraction] = 0.0
+    img = depth_from_z(z, encoding, step_pad, bigendian, depth_scale, seed + int(frame))
+    return img, (float(fx), float(fy), float(ppx), float(ppy))

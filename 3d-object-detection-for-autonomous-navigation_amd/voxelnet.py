@@ -9,14 +9,15 @@ Mirror of model/voxelnet.py::VoxelNet for the eval path (train.py:575-771):
 Trv2c, P2, anchors, anchors_mask, image_idx, image_shape); elements may be
 numpy arrays or anything with `.numpy()` (the reference passes TF tensors).
 `detect(frames, ...)` is the fused raw-points path the reference does not have; `detect_pointcloud2(msgs, ...)` is the
-same from raw sensor_msgs/PointCloud2 messages (the reference's production mode, ingested on the GPU).
+same from raw sensor_msgs/PointCloud2 messages (the reference's production mode, ingested on the GPU), and
+`detect_depth(images, intrinsics, ...)` from the depth images those messages are computed from.
 
 Training mode (model/voxelnet.py:922-1049 + train.py:265-304), `VoxelNet(config, writer, training=True)`:
     ret = net(voxels, num_points, coors, batch_anchors, labels, reg_targets)   # the reference's loss dict (scalars)
     net.apply_gradients(dist=None)        # optimizer.apply_gradients: one all-reduce over the ranks + AdamW
 or, from raw clouds, `net.train_step(frames, labels, reg_targets, dist)` -- or `net.train_step(frames, gt_boxes=boxes)`,
 which assigns the targets on the GPU (the loader's target_assigner.assign, csrc/targets.hip).  A training net detects
-with its current weights (`detect`, `detect_pointcloud2`): they are folded into the detector on the GPU first
+with its current weights (`detect`, `detect_pointcloud2`, `detect_depth`): they are folded into the detector on the GPU first
 (Trainer.publish, csrc/weight_publish.hip).  The forward pass, the loss and the
 gradients of a call come from one `pp_train_step` (csrc/train.hip); the padded voxel tensor is unpadded on the
 host into the pillar-ordered point list it was built from (the voxeliser then reproduces the same pillars).
@@ -189,6 +190,19 @@ class VoxelNet:
         bb = self._bboxes(len(msgs))
         idx = image_idx if image_idx is not None else list(range(len(msgs)))
         return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(msgs))]
+
+    def detect_depth(self, images, intrinsics, rect=None, trv2c=None, image_idx=None, p2=None):
+        """Fused path from raw depth images (sensor_msgs/Image, 16UC1 or 32FC1) and the camera's intrinsics
+        (Engine.detect_depth: deprojection and ingest on the GPU) -> the same list of prediction dicts as
+        `detect_pointcloud2` on the messages a point-cloud node computes from those images; p2 as in `detect`."""
+        self._need_p2(p2, "detect_depth")
+        self._detector()
+        if self.d.project_bbox:
+            self.engine.set_projection(np.broadcast_to(np.asarray(p2, np.float64), (len(images), 4, 4)))
+        dets, n = self.engine.detect_depth(images, intrinsics, rect, trv2c)
+        bb = self._bboxes(len(images))
+        idx = image_idx if image_idx is not None else list(range(len(images)))
+        return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(images))]
 
     @staticmethod
     def _to_dict(dets, n, img_idx, bbox=None):

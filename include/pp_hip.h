@@ -40,7 +40,8 @@ extern "C" {
  * pp_set_train_metrics, pp_get_train_metrics_enabled, pp_get_train_metrics; then pp_grad_clip_mode, pp_grad_clip_config,
  * pp_grad_clip_workspace_bytes, pp_grad_norm_device, pp_adamw_step_clipped_device; then pp_publish_stats,
  * pp_publish_train_weights, pp_publish_info; then PP_NMS_SOFT, pp_soft_nms_method, pp_set_soft_nms, pp_get_soft_nms,
- * PP_SNMS_MAX_BOXES, pp_soft_nms. */
+ * PP_SNMS_MAX_BOXES, pp_soft_nms.  Then PP_DEPTH_U16, PP_DEPTH_F32, pp_depth_layout, pp_ingest_depth,
+ * pp_ingest_depth_async (declared behind pp_ingest_info, whose counts serve both feeds). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -822,6 +823,49 @@ int pp_ingest_pointcloud2_async(pp_handle h, const uint8_t* data_pinned, const i
 /* Parity tap of the last ingest (waits for it): per frame the finite records and the points kept.  Either pointer may be
  * NULL.  PP_ERR_STATE when none has run, PP_ERR_ARG when `batch` is not that call's. */
 int pp_ingest_info(pp_handle h, int32_t* finite_counts, int32_t* kept_counts, int32_t batch);
+
+/* ---- depth-image ingest -------------------------------------------------------------------------------- */
+/* The same resident frames from the depth camera's raw sensor_msgs/Image instead of the PointCloud2 message a point-cloud
+ * node computes from it (a 640 x 480 16UC1 image is 0.6 MB, its message 6 to 10 MB).  Per pixel (v, u), in float32:
+ *   16UC1 / mono16: z = depth_scale * (float)d (one product), valid when d != 0;
+ *   32FC1: z is the stored value, valid when it is finite and > 0 (depth_scale is not applied: REP 118);
+ *   both: valid only when z > z_min && z <= z_max (0 and +inf leave the conditions above as they are);
+ *   a valid pixel is the point x = z * (((float)u - ppx) / fx), y = z * (((float)v - ppy) / fy), z -- every operation
+ *   rounded separately, IEEE division: the pinhole (no distortion) case of the camera vendor's published
+ *   rs2_deproject_pixel_to_point.  Parity with the bytes the camera driver's point-cloud block publishes is NOT pinned
+ *   (neither the vendor library nor its ROS node is available to this project's tests); everything behind the point is:
+ *   rank = valid pixels in front of it in row-major order, then the selection, the float64 transform and the single
+ *   rounding of pp_ingest_pointcloud2, from the same pp_ingest_config.  The result equals <package>/ingest.py's
+ *   depth_ingest_np, and realsense_to_lidar(pointcloud2_to_xyz(depth_to_pointcloud2(...)), decimate, first, lift), exactly.
+ * Not done, and not approximated: lens distortion (the caller refuses a CameraInfo with a non-zero D; the d435i depth
+ * stream's coefficients are zero), alignment of depth to the colour stream, dropping points by texture coordinate, RGB
+ * or any feature beyond x y z, the vendor's spatial and temporal filters. */
+#define PP_DEPTH_U16 0           /* 16UC1 / mono16 */
+#define PP_DEPTH_F32 1           /* 32FC1 */
+typedef struct pp_depth_layout { /* one sensor_msgs/Image with the intrinsics of its camera, without its bytes */
+    int32_t width, height, row_step;        /* Image.step: any value >= width * itemsize, odd ones included */
+    int32_t encoding;                       /* PP_DEPTH_U16 or PP_DEPTH_F32 */
+    int32_t is_bigendian;
+    float fx, fy, ppx, ppy;                 /* CameraInfo K[0], K[4], K[2], K[5] cast to float32 once */
+    float depth_scale;                      /* metres per unit of a 16UC1 pixel (d435i: 0.001f); read for PP_DEPTH_U16 only */
+    float z_min, z_max;                     /* 0, +inf: no clip */
+} pp_depth_layout;
+
+/* pp_ingest_pointcloud2 for depth images: image b occupies data[byte_offsets[b] .. byte_offsets[b + 1]) and holds at
+ * least height * row_step bytes; points_out / points_out_capacity, the input-buffer flip, the staging and the host-side
+ * bound max(0, ceil((width * height - first) / decimate)) per frame are that call's, and pp_ingest_info reads the counts
+ * back (finite_counts = valid pixels).  Everything an ingest bars afterwards is barred the same way.  Refused before
+ * anything is queued, pp_last_error naming the frame and the field: PP_ERR_ARG when the bound exceeds
+ * max_points_per_frame, for row_step < width * itemsize, an unknown encoding, byte_offsets that give a frame fewer than
+ * height * row_step bytes, fx or fy zero or not finite, ppx or ppy not finite, depth_scale <= 0 or not finite on
+ * PP_DEPTH_U16, z_min > z_max (or a NaN), decimate < 1, first < 0, batch > max_batch; PP_ERR_STATE while a training step
+ * is in flight; PP_ERR_UNSUPPORTED for a handle whose num_point_features is not 3. */
+int pp_ingest_depth(pp_handle h, const uint8_t* data, const int64_t* byte_offsets, const pp_depth_layout* layouts,
+                    int32_t batch, const pp_ingest_config* cfg, float* points_out, int64_t points_out_capacity);
+/* Same without waiting, as pp_ingest_pointcloud2_async: page-locked bytes on the copy stream, the kernels and the
+ * voxeliser behind them there; mixes freely with that call and with pp_upload_points_async. */
+int pp_ingest_depth_async(pp_handle h, const uint8_t* data_pinned, const int64_t* byte_offsets,
+                          const pp_depth_layout* layouts, int32_t batch, const pp_ingest_config* cfg);
 
 /* ---- frustum crop (box_np_ops.remove_outside_points) ----------------------------------------------------- */
 /* Crops the RESIDENT frames to the camera image's frustum on the GPU: what _create_reduced_point_cloud,
