@@ -13,10 +13,19 @@
 // the GPU and back for a numba NMS kernel (1.4-2.2 ms per call); here the head
 // maps never leave HBM and the whole tail is one launch.
 //
-// Selection is done on the logit (sigmoid is monotone), with an order-preserving
-// integer key and the anchor index as tie-break (lower index first), i.e. a
-// deterministic refinement of np.argpartition / argsort whose tie order is
-// implementation-defined.  NMS IoU follows iou_device exactly: AABB with `+1`
+// Selection is done on the logit, not on the score, with a 64-bit key (comp_key):
+// the float's bits mapped to an order-preserving unsigned integer in the high
+// word, the complemented anchor index in the low word.  The order it implements:
+//   1. logit descending, as a float value;
+//   2. +0.0 above -0.0 (their bit patterns differ, their float values do not);
+//   3. anchor index ascending.
+// The reference orders float32 *scores* with np.argpartition / argsort, whose
+// tie order is implementation-defined.  Sigmoid is monotone, so descending logit
+// is non-increasing score: this order is a deterministic refinement of the
+// reference's.  It is finer where float32 sigmoid maps different logits to one
+// score (every logit above about 17 scores 1.0): those are ordered by logit.
+// tests/postprocess_ref.py restates the rule; tests/test_gpu_select.py holds the
+// kernel to it.  NMS IoU follows iou_device exactly: AABB with `+1`
 // on widths (pixel convention applied to metres), differences in float32, the
 // rest in float64, strict `>` threshold.
 //
