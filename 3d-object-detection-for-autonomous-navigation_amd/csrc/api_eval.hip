@@ -3,37 +3,24 @@
 #include "pp_engine.h"
 
 namespace {
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-int check_device(const char* who, int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, PP_ERR_HIP, "%s: no HIP device available (this library has no CPU fallback)", who);
-    if (device < 0 || device >= ndev) return fail(nullptr, PP_ERR_ARG, "%s: device %d not in [0,%d)", who, device, ndev);
-    return PP_OK;
-}
 int riou_common(int device, const float* boxes, int64_t n, const float* qboxes, int64_t k, int32_t criterion,
                 DevBuf& d_out, const char* who) {
     if (int st = check_device(who, device)) return st;
     if (n < 0 || k < 0 || (n > 0 && !boxes) || (k > 0 && !qboxes)) return fail(nullptr, PP_ERR_ARG, "%s: bad argument", who);
     if (criterion < -1 || criterion > 2) return fail(nullptr, PP_ERR_ARG, "%s: criterion %d not in {-1,0,1,2}", who, criterion);
     if (n > 200000) return fail(nullptr, PP_ERR_ARG, "%s: at most 200000 boxes per call (got %lld)", who, (long long)n);
-#define RCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(nullptr, PP_ERR_HIP, "%s: %s", who, hipGetErrorString(e_)); } while (0)
-    RCHK(hipSetDevice(device));
+    DEVCHK(hipSetDevice(device));
     DevBuf d_b, d_q, d_bc, d_qc;
-    RCHK(d_b.alloc(sizeof(float) * 5 * n)); RCHK(d_q.alloc(sizeof(float) * 5 * k));
-    RCHK(d_bc.alloc(sizeof(float) * 9 * n)); RCHK(d_qc.alloc(sizeof(float) * 9 * k));
-    RCHK(d_out.alloc(sizeof(float) * n * k));
+    DEVCHK(d_b.alloc(sizeof(float) * 5 * n)); DEVCHK(d_q.alloc(sizeof(float) * 5 * k));
+    DEVCHK(d_bc.alloc(sizeof(float) * 9 * n)); DEVCHK(d_qc.alloc(sizeof(float) * 9 * k));
+    DEVCHK(d_out.alloc(sizeof(float) * n * k));
     if (n == 0 || k == 0) return PP_OK;
-    RCHK(hipMemcpy(d_b.p, boxes, sizeof(float) * 5 * n, hipMemcpyHostToDevice));
-    RCHK(hipMemcpy(d_q.p, qboxes, sizeof(float) * 5 * k, hipMemcpyHostToDevice));
+    DEVCHK(hipMemcpy(d_b.p, boxes, sizeof(float) * 5 * n, hipMemcpyHostToDevice));
+    DEVCHK(hipMemcpy(d_q.p, qboxes, sizeof(float) * 5 * k, hipMemcpyHostToDevice));
     launch_riou_corners((const float*)d_b.p, n, (float*)d_bc.p, nullptr);
     launch_riou_corners((const float*)d_q.p, k, (float*)d_qc.p, nullptr);
     launch_riou_pairs((const float*)d_bc.p, n, (const float*)d_qc.p, k, criterion, (float*)d_out.p, nullptr);
-    RCHK(hipGetLastError());
+    DEVCHK(hipGetLastError());
     return PP_OK;
 }
 }  // namespace
@@ -47,7 +34,7 @@ int pp_rotate_iou_eval(int device, const float* boxes, int64_t n, const float* q
     if (st || n == 0 || k == 0) return st;
     if (!out) return fail(nullptr, PP_ERR_ARG, "pp_rotate_iou_eval: out is null");
     const char* who = "pp_rotate_iou_eval";
-    RCHK(hipMemcpy(out, d_out.p, sizeof(float) * n * k, hipMemcpyDeviceToHost));
+    DEVCHK(hipMemcpy(out, d_out.p, sizeof(float) * n * k, hipMemcpyDeviceToHost));
     return PP_OK;
 }
 
@@ -66,12 +53,12 @@ int pp_d3_box_overlap(int device, const double* boxes, int64_t n, const double* 
     if (!out) return fail(nullptr, PP_ERR_ARG, "%s: out is null", who);
     if (criterion < -1 || criterion > 2) return fail(nullptr, PP_ERR_ARG, "%s: criterion %d not in {-1,0,1,2}", who, criterion);
     DevBuf d_b, d_q, d_o;
-    RCHK(d_b.alloc(sizeof(double) * 7 * n)); RCHK(d_q.alloc(sizeof(double) * 7 * k)); RCHK(d_o.alloc(sizeof(double) * n * k));
-    RCHK(hipMemcpy(d_b.p, boxes, sizeof(double) * 7 * n, hipMemcpyHostToDevice));
-    RCHK(hipMemcpy(d_q.p, query_boxes, sizeof(double) * 7 * k, hipMemcpyHostToDevice));
+    DEVCHK(d_b.alloc(sizeof(double) * 7 * n)); DEVCHK(d_q.alloc(sizeof(double) * 7 * k)); DEVCHK(d_o.alloc(sizeof(double) * n * k));
+    DEVCHK(hipMemcpy(d_b.p, boxes, sizeof(double) * 7 * n, hipMemcpyHostToDevice));
+    DEVCHK(hipMemcpy(d_q.p, query_boxes, sizeof(double) * 7 * k, hipMemcpyHostToDevice));
     launch_d3_finish((const double*)d_b.p, n, (const double*)d_q.p, k, criterion, (const float*)d_rinc.p, (double*)d_o.p, nullptr);
-    RCHK(hipGetLastError());
-    RCHK(hipMemcpy(out, d_o.p, sizeof(double) * n * k, hipMemcpyDeviceToHost));
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipMemcpy(out, d_o.p, sizeof(double) * n * k, hipMemcpyDeviceToHost));
     return PP_OK;
 }
 
@@ -108,10 +95,10 @@ struct EvalUpload {
         const int64_t total_ov = nframes > 0 ? ov_off_h[nframes] : 0;
         if ((total_gt > 0 && !ign_gt_h) || (total_dt > 0 && (!ign_dt_h || !scores_h)) || (total_ov > 0 && !overlaps))
             return fail(nullptr, PP_ERR_ARG, "%s: NULL box array", who);
-        RCHK(hipSetDevice(device));
+        DEVCHK(hipSetDevice(device));
         if (nframes == 0 || K == 0) return PP_OK;
         const size_t nf1 = (size_t)nframes + 1;
-#define EV_UP(buf, src, bytes) do { RCHK(buf.alloc(bytes)); if ((bytes) > 0) RCHK(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice)); } while (0)
+#define EV_UP(buf, src, bytes) do { DEVCHK(buf.alloc(bytes)); if ((bytes) > 0) DEVCHK(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice)); } while (0)
         EV_UP(gt_off, gt_off_h, sizeof(int32_t) * nf1);
         EV_UP(dt_off, dt_off_h, sizeof(int32_t) * nf1);
         EV_UP(ov_off, ov_off_h, sizeof(int64_t) * nf1);
@@ -143,16 +130,16 @@ int pp_eval_match(int device, int32_t nframes, const int32_t* gt_off, const int3
     if (nframes == 0 || nout == 0) return PP_OK;
     if (!matched) return fail(nullptr, PP_ERR_ARG, "%s: matched is null", who);
     DevBuf d_m;
-    RCHK(d_m.alloc(sizeof(int32_t) * nout));
+    DEVCHK(d_m.alloc(sizeof(int32_t) * nout));
     p.matched = (int*)d_m.p;
     EvEvents ev;
-    RCHK(hipEventCreate(&ev.a)); RCHK(hipEventCreate(&ev.b));
-    RCHK(hipEventRecord(ev.a, nullptr));
+    DEVCHK(hipEventCreate(&ev.a)); DEVCHK(hipEventCreate(&ev.b));
+    DEVCHK(hipEventRecord(ev.a, nullptr));
     launch_eval_match(p, nullptr);
-    RCHK(hipEventRecord(ev.b, nullptr));
-    RCHK(hipGetLastError());
-    RCHK(hipMemcpy(matched, d_m.p, sizeof(int32_t) * nout, hipMemcpyDeviceToHost));
-    if (kernel_ms) RCHK(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    DEVCHK(hipEventRecord(ev.b, nullptr));
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipMemcpy(matched, d_m.p, sizeof(int32_t) * nout, hipMemcpyDeviceToHost));
+    if (kernel_ms) DEVCHK(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
     return PP_OK;
 }
 
@@ -199,29 +186,28 @@ int pp_eval_pr(int device, int32_t nframes, const int32_t* gt_off, const int32_t
         EV_UP(d_dco, dc_off, sizeof(int32_t) * nf1);
         EV_UP(d_dcb, dc_boxes, sizeof(double) * 4 * (size_t)total_dc);
     } else {                                            // the kernel reads dc_off only to find no boxes
-        RCHK(d_dco.alloc(sizeof(int32_t) * nf1));
-        RCHK(hipMemset(d_dco.p, 0, sizeof(int32_t) * nf1));
+        DEVCHK(d_dco.alloc(sizeof(int32_t) * nf1));
+        DEVCHK(hipMemset(d_dco.p, 0, sizeof(int32_t) * nf1));
     }
     EV_UP(d_th, thresholds, sizeof(double) * (size_t)ntiers * PP_EVAL_NTHRESH);
     EV_UP(d_nt, nthresh, sizeof(int32_t) * (size_t)ntiers);
-    RCHK(d_part.alloc(sizeof(double) * npr * (size_t)nframes));
-    RCHK(d_pr.alloc(sizeof(double) * npr));
+    DEVCHK(d_part.alloc(sizeof(double) * npr * (size_t)nframes));
+    DEVCHK(d_pr.alloc(sizeof(double) * npr));
     p.gt_alpha = (const double*)d_ga.p; p.dt_alpha = (const double*)d_da.p; p.dt_box = (const double*)d_db.p;
     p.dc_off = (const int*)d_dco.p; p.dc_box = (const double*)d_dcb.p;
     p.thresholds = (const double*)d_th.p; p.nthresh = (const int*)d_nt.p;
     p.metric = metric; p.compute_aos = compute_aos ? 1 : 0;
     p.partial = (double*)d_part.p; p.pr = (double*)d_pr.p;
     EvEvents ev;
-    RCHK(hipEventCreate(&ev.a)); RCHK(hipEventCreate(&ev.b));
-    RCHK(hipEventRecord(ev.a, nullptr));
+    DEVCHK(hipEventCreate(&ev.a)); DEVCHK(hipEventCreate(&ev.b));
+    DEVCHK(hipEventRecord(ev.a, nullptr));
     launch_eval_count(p, nullptr);
     launch_eval_reduce(p, nullptr);
-    RCHK(hipEventRecord(ev.b, nullptr));
-    RCHK(hipGetLastError());
-    RCHK(hipMemcpy(pr, d_pr.p, sizeof(double) * npr, hipMemcpyDeviceToHost));
-    if (kernel_ms) RCHK(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    DEVCHK(hipEventRecord(ev.b, nullptr));
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipMemcpy(pr, d_pr.p, sizeof(double) * npr, hipMemcpyDeviceToHost));
+    if (kernel_ms) DEVCHK(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
 #undef EV_UP
-#undef RCHK
     return PP_OK;
 }
 

@@ -3,32 +3,24 @@
 // handle: host buffers in, host buffers out, device memory for the call's duration.
 #include "pp_engine.h"
 
-namespace {
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-}  // namespace
-
 extern "C" {
 
 int pp_set_nms_mode(pp_handle e, int32_t mode) {
     if (!e) return PP_ERR_ARG;
     if (mode != PP_NMS_STANDUP && mode != PP_NMS_ROTATED && mode != PP_NMS_SOFT)
         return fail(e, PP_ERR_ARG, "pp_set_nms_mode: unknown mode %d", mode);
-    if (mode == e->nms_mode) return PP_OK;
+    if (mode == e->rule.nms_mode) return PP_OK;
     if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_set_nms_mode: a training step is in flight");
-    if (mode + e->nms_mode == PP_NMS_ROTATED + PP_NMS_SOFT)
+    if (mode + e->rule.nms_mode == PP_NMS_ROTATED + PP_NMS_SOFT)
         return fail(e, PP_ERR_UNSUPPORTED, "pp_set_nms_mode: soft re-scoring on the rotated overlap is not built; switch "
                                            "between PP_NMS_ROTATED and PP_NMS_SOFT through PP_NMS_STANDUP");
-    e->nms_mode = mode;      // read by the next run_post; a captured pass is keyed on it (pp_detect_async)
+    e->rule.nms_mode = mode;
     return PP_OK;
 }
 
 int pp_get_nms_mode(pp_handle e, int32_t* mode) {
     if (!e || !mode) return PP_ERR_ARG;
-    *mode = e->nms_mode;
+    *mode = e->rule.nms_mode;
     return PP_OK;
 }
 
@@ -43,19 +35,16 @@ int pp_set_soft_nms(pp_handle e, int32_t method, float sigma, float score_floor)
     if (!e) return PP_ERR_ARG;
     if (const char* why = soft_nms_args(method, sigma, score_floor))
         return fail(e, PP_ERR_ARG, "pp_set_soft_nms: %s (method %d, sigma %g, score_floor %g)", why, method, sigma, score_floor);
-    if (method == e->soft_method && sigma == e->soft_sigma && score_floor == e->soft_floor) return PP_OK;
+    PostRule& r = e->rule;
+    if (method == r.soft_method && sigma == r.soft_sigma && score_floor == r.soft_floor) return PP_OK;
     if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_set_soft_nms: a training step is in flight");
-    e->soft_method = method;      // kernel arguments of the next run_post; a captured pass is keyed on them
-    e->soft_sigma = sigma;
-    e->soft_floor = score_floor;
+    r.soft_method = method; r.soft_sigma = sigma; r.soft_floor = score_floor;
     return PP_OK;
 }
 
 int pp_get_soft_nms(pp_handle e, int32_t* method, float* sigma, float* score_floor) {
     if (!e || !method || !sigma || !score_floor) return PP_ERR_ARG;
-    *method = e->soft_method;
-    *sigma = e->soft_sigma;
-    *score_floor = e->soft_floor;
+    *method = e->rule.soft_method; *sigma = e->rule.soft_sigma; *score_floor = e->rule.soft_floor;
     return PP_OK;
 }
 
@@ -73,34 +62,29 @@ int pp_soft_nms(int device, const float* dets, int64_t n, int32_t method, float 
         return fail(nullptr, PP_ERR_ARG, "%s: %lld boxes enter the rounds; at most PP_SNMS_MAX_BOXES = %d (set pre_max_size)",
                     who, (long long)m, PP_SNMS_MAX_BOXES);
     if (n > (int64_t)1 << 24) return fail(nullptr, PP_ERR_ARG, "%s: at most %d boxes per call (got %lld)", who, 1 << 24, (long long)n);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, PP_ERR_HIP, "%s: no HIP device available (this library has no CPU fallback)", who);
-    if (device < 0 || device >= ndev) return fail(nullptr, PP_ERR_ARG, "%s: device %d not in [0,%d)", who, device, ndev);
+    if (int st = check_device(who, device)) return st;
     if (m == 0) return PP_OK;
     if (!keep || !scores) return fail(nullptr, PP_ERR_ARG, "%s: keep or scores is null", who);
-#define NCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(nullptr, PP_ERR_HIP, "%s: %s", who, hipGetErrorString(e_)); } while (0)
-    NCHK(hipSetDevice(device));
+    DEVCHK(hipSetDevice(device));
     const int post = (post_max_size > 0 && post_max_size < m) ? post_max_size : (int)m;
     DevBuf d_dets, d_enter, d_order, d_keep, d_scores, d_nk;
-    NCHK(d_dets.alloc(sizeof(float) * 5 * (size_t)n));
-    NCHK(d_enter.alloc(sizeof(int) * (size_t)n));
-    NCHK(d_order.alloc(sizeof(int) * (size_t)m));
-    NCHK(d_keep.alloc(sizeof(int) * (size_t)post));
-    NCHK(d_scores.alloc(sizeof(float) * (size_t)post));
-    NCHK(d_nk.alloc(sizeof(long long)));
-    NCHK(hipMemcpy(d_dets.p, dets, sizeof(float) * 5 * (size_t)n, hipMemcpyHostToDevice));
+    DEVCHK(d_dets.alloc(sizeof(float) * 5 * (size_t)n));
+    DEVCHK(d_enter.alloc(sizeof(int) * (size_t)n));
+    DEVCHK(d_order.alloc(sizeof(int) * (size_t)m));
+    DEVCHK(d_keep.alloc(sizeof(int) * (size_t)post));
+    DEVCHK(d_scores.alloc(sizeof(float) * (size_t)post));
+    DEVCHK(d_nk.alloc(sizeof(long long)));
+    DEVCHK(hipMemcpy(d_dets.p, dets, sizeof(float) * 5 * (size_t)n, hipMemcpyHostToDevice));
     launch_soft_nms((const float*)d_dets.p, (int)n, (int)m, method, iou_threshold, sigma, score_floor, post, (int*)d_enter.p,
                     (int*)d_order.p, (int*)d_keep.p, (float*)d_scores.p, (long long*)d_nk.p, nullptr);
-    NCHK(hipGetLastError());
+    DEVCHK(hipGetLastError());
     long long nk = 0;
-    NCHK(hipMemcpy(&nk, d_nk.p, sizeof(nk), hipMemcpyDeviceToHost));
+    DEVCHK(hipMemcpy(&nk, d_nk.p, sizeof(nk), hipMemcpyDeviceToHost));
     if (nk < 0 || nk > post) return fail(nullptr, PP_ERR_HIP, "%s: the rounds returned %lld of at most %d boxes", who, nk, post);
     if (nk > 0) {
-        NCHK(hipMemcpy(keep, d_keep.p, sizeof(int) * (size_t)nk, hipMemcpyDeviceToHost));
-        NCHK(hipMemcpy(scores, d_scores.p, sizeof(float) * (size_t)nk, hipMemcpyDeviceToHost));
+        DEVCHK(hipMemcpy(keep, d_keep.p, sizeof(int) * (size_t)nk, hipMemcpyDeviceToHost));
+        DEVCHK(hipMemcpy(scores, d_scores.p, sizeof(float) * (size_t)nk, hipMemcpyDeviceToHost));
     }
-#undef NCHK
     *n_keep = nk;
     return PP_OK;
 }
@@ -117,33 +101,28 @@ int pp_rotate_nms(int device, const float* dets, int64_t n, float iou_threshold,
         return fail(nullptr, PP_ERR_ARG, "%s: %lld boxes enter the suppression; at most PP_RNMS_MAX_BOXES = %d (set pre_max_size)",
                     who, (long long)m, PP_RNMS_MAX_BOXES);
     if (n > (int64_t)1 << 24) return fail(nullptr, PP_ERR_ARG, "%s: at most %d boxes per call (got %lld)", who, 1 << 24, (long long)n);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, PP_ERR_HIP, "%s: no HIP device available (this library has no CPU fallback)", who);
-    if (device < 0 || device >= ndev) return fail(nullptr, PP_ERR_ARG, "%s: device %d not in [0,%d)", who, device, ndev);
+    if (int st = check_device(who, device)) return st;
     if (m == 0) return PP_OK;
     if (!keep) return fail(nullptr, PP_ERR_ARG, "%s: keep is null", who);
-#define NCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(nullptr, PP_ERR_HIP, "%s: %s", who, hipGetErrorString(e_)); } while (0)
-    NCHK(hipSetDevice(device));
+    DEVCHK(hipSetDevice(device));
     const size_t cb = (size_t)((m + 63) / 64);
     DevBuf d_dets, d_order, d_sorted, d_corners, d_mask, d_keep, d_nk;
-    NCHK(d_dets.alloc(sizeof(float) * 6 * (size_t)n));
-    NCHK(d_order.alloc(sizeof(int) * (size_t)m));
-    NCHK(d_sorted.alloc(sizeof(float) * 5 * (size_t)m));
-    NCHK(d_corners.alloc(sizeof(float) * 9 * (size_t)m));
-    NCHK(d_mask.alloc(sizeof(unsigned long long) * (size_t)m * cb));
-    NCHK(d_keep.alloc(sizeof(int) * (size_t)m));
-    NCHK(d_nk.alloc(sizeof(long long)));
-    NCHK(hipMemcpy(d_dets.p, dets, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice));
+    DEVCHK(d_dets.alloc(sizeof(float) * 6 * (size_t)n));
+    DEVCHK(d_order.alloc(sizeof(int) * (size_t)m));
+    DEVCHK(d_sorted.alloc(sizeof(float) * 5 * (size_t)m));
+    DEVCHK(d_corners.alloc(sizeof(float) * 9 * (size_t)m));
+    DEVCHK(d_mask.alloc(sizeof(unsigned long long) * (size_t)m * cb));
+    DEVCHK(d_keep.alloc(sizeof(int) * (size_t)m));
+    DEVCHK(d_nk.alloc(sizeof(long long)));
+    DEVCHK(hipMemcpy(d_dets.p, dets, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice));
     const int post = (post_max_size > 0 && post_max_size < m) ? post_max_size : (int)m;
     launch_rnms((const float*)d_dets.p, (int)n, (int)m, iou_threshold, post, (int*)d_order.p, (float*)d_sorted.p,
                 (float*)d_corners.p, (unsigned long long*)d_mask.p, (int*)d_keep.p, (long long*)d_nk.p, nullptr);
-    NCHK(hipGetLastError());
+    DEVCHK(hipGetLastError());
     long long nk = 0;
-    NCHK(hipMemcpy(&nk, d_nk.p, sizeof(nk), hipMemcpyDeviceToHost));
+    DEVCHK(hipMemcpy(&nk, d_nk.p, sizeof(nk), hipMemcpyDeviceToHost));
     if (nk < 0 || nk > m) return fail(nullptr, PP_ERR_HIP, "%s: the sweep returned %lld of %lld boxes", who, nk, (long long)m);
-    if (nk > 0) NCHK(hipMemcpy(keep, d_keep.p, sizeof(int) * (size_t)nk, hipMemcpyDeviceToHost));
-#undef NCHK
+    if (nk > 0) DEVCHK(hipMemcpy(keep, d_keep.p, sizeof(int) * (size_t)nk, hipMemcpyDeviceToHost));
     *n_keep = nk;
     return PP_OK;
 }

@@ -5,28 +5,20 @@
 
 #include "pp_engine.h"
 
-namespace {
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-}  // namespace
-
 extern "C" {
 
 int pp_set_projection(pp_handle e, const double* p2, int32_t batch) {
     if (!e) return PP_ERR_ARG;
     pp_engine::Projection& pj = e->proj;
     if (p2 == nullptr) {
-        if (!pj.on) return PP_OK;
+        if (!e->rule.proj) return PP_OK;
         if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_set_projection: a training step is in flight");
-        pj.on = false;       // read by the next run_post; a captured pass is keyed on it (pp_detect_async)
+        e->rule.proj = 0;
         return PP_OK;
     }
     if (batch < 1 || batch > e->B) return fail(e, PP_ERR_ARG, "pp_set_projection: batch=%d outside [1, max_batch=%d]", batch, e->B);
     const size_t n = (size_t)batch * 16;
-    if (pj.on && pj.batch == batch && memcmp(pj.h_p2.data(), p2, n * sizeof(double)) == 0) return PP_OK;
+    if (e->rule.proj && pj.batch == batch && memcmp(pj.h_p2.data(), p2, n * sizeof(double)) == 0) return PP_OK;
     if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_set_projection: a training step is in flight");
     (void)hipSetDevice(e->device);
     if (pj.d_p2 == nullptr) {
@@ -44,13 +36,13 @@ int pp_set_projection(pp_handle e, const double* p2, int32_t batch) {
     HIPCHK(e, hipStreamSynchronize(e->stream));
     pj.h_p2.assign(p2, p2 + n);
     pj.batch = batch;
-    pj.on = true;
+    e->rule.proj = 1;
     return PP_OK;
 }
 
 int pp_get_projection(pp_handle e, int32_t* on) {
     if (!e || !on) return PP_ERR_ARG;
-    *on = e->proj.on ? 1 : 0;
+    *on = e->rule.proj;
     return PP_OK;
 }
 
@@ -85,25 +77,20 @@ int pp_box3d_to_bbox(int device, const double* boxes_camera, const int32_t* box_
     if (n == 0) return PP_OK;
     if (!boxes_camera || !bbox) return fail(nullptr, PP_ERR_ARG, "%s: NULL boxes", who);
     if (n > (1ll << 31) * 256 - 256) return fail(nullptr, PP_ERR_ARG, "%s: too many boxes (%lld)", who, n);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, PP_ERR_HIP, "%s: no HIP device available (this library has no CPU fallback)", who);
-    if (device < 0 || device >= ndev) return fail(nullptr, PP_ERR_ARG, "%s: device %d not in [0,%d)", who, device, ndev);
-#define JCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(nullptr, PP_ERR_HIP, "%s: %s", who, hipGetErrorString(e_)); } while (0)
-    JCHK(hipSetDevice(device));
+    if (int st = check_device(who, device)) return st;
+    DEVCHK(hipSetDevice(device));
     DevBuf d_boxes, d_start, d_p2, d_bbox;
-    JCHK(d_boxes.alloc(sizeof(double) * 7 * (size_t)n));
-    JCHK(d_start.alloc(sizeof(long long) * start.size()));
-    JCHK(d_p2.alloc(sizeof(double) * 16 * (size_t)frames));
-    JCHK(d_bbox.alloc(sizeof(double) * 4 * (size_t)n));
-    JCHK(hipMemcpy(d_boxes.p, boxes_camera, sizeof(double) * 7 * (size_t)n, hipMemcpyHostToDevice));
-    JCHK(hipMemcpy(d_start.p, start.data(), sizeof(long long) * start.size(), hipMemcpyHostToDevice));
-    JCHK(hipMemcpy(d_p2.p, p2, sizeof(double) * 16 * (size_t)frames, hipMemcpyHostToDevice));
+    DEVCHK(d_boxes.alloc(sizeof(double) * 7 * (size_t)n));
+    DEVCHK(d_start.alloc(sizeof(long long) * start.size()));
+    DEVCHK(d_p2.alloc(sizeof(double) * 16 * (size_t)frames));
+    DEVCHK(d_bbox.alloc(sizeof(double) * 4 * (size_t)n));
+    DEVCHK(hipMemcpy(d_boxes.p, boxes_camera, sizeof(double) * 7 * (size_t)n, hipMemcpyHostToDevice));
+    DEVCHK(hipMemcpy(d_start.p, start.data(), sizeof(long long) * start.size(), hipMemcpyHostToDevice));
+    DEVCHK(hipMemcpy(d_p2.p, p2, sizeof(double) * 16 * (size_t)frames, hipMemcpyHostToDevice));
     launch_box3d_to_bbox((const double*)d_boxes.p, n, (const long long*)d_start.p, frames, (const double*)d_p2.p,
                          (double*)d_bbox.p, nullptr);
-    JCHK(hipGetLastError());
-    JCHK(hipMemcpy(bbox, d_bbox.p, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToHost));
-#undef JCHK
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipMemcpy(bbox, d_bbox.p, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToHost));
     return PP_OK;
 }
 

@@ -112,6 +112,16 @@ int train_buffers(pp_engine* e) {
     return st;
 }
 
+TrainKey train_key(const pp_engine* e, int batch, int bucket, const void* params, const void* grads, const void* state,
+                   const pp_loss_config* lc) {
+    TrainKey k;
+    k.batch = batch; k.bucket = bucket; k.zc = e->zc ? 1 : 0;
+    k.params = params; k.grads = grads; k.state = state; k.loss = *lc;
+    k.frozen = e->train->plan.frozen;
+    k.metrics = e->metrics.on;
+    return k;
+}
+
 // pp_train_step_async and pp_train_step_gt_async: `targets` fills loss.labels / loss.regt between the two halves of
 // the step (plain stream work between the two graph replays, or between the two eager halves)
 int train_step_launch(pp_engine* e, const float* params_dev, float* grads_dev, float* state_dev, int32_t batch,
@@ -159,47 +169,26 @@ int train_step_launch(pp_engine* e, const float* params_dev, float* grads_dev, f
     if (e->prof <= 0 && t->graph_state == 0 && graphs_enabled()) {
         const int bucket = graph_bucket(e, e->cur_max_n);
         pp_engine::TrainState::Graph& tg = t->graph[e->in_buf & 1];
-        const bool hit = tg.exec != nullptr && tg.exec_bwd != nullptr && tg.batch == batch && tg.bucket == bucket &&
-                         tg.zc == (e->zc ? 1 : 0) && tg.params == params_dev && tg.grads == grads_dev &&
-                         tg.state == state_dev && memcmp(&tg.loss, lc, sizeof(pp_loss_config)) == 0 &&
-                         tg.frozen == t->plan.frozen && tg.metrics == e->metrics.on;
-        if (!hit) {
+        const TrainKey key = train_key(e, batch, bucket, params_dev, grads_dev, state_dev, lc);
+        if (!(tg.exec != nullptr && tg.exec_bwd != nullptr && tg.key == key)) {
             if (tg.exec || tg.exec_bwd) {
                 HIPCHK(e, hipStreamSynchronize(e->stream));
-                if (tg.exec) (void)hipGraphExecDestroy(tg.exec);
-                if (tg.exec_bwd) (void)hipGraphExecDestroy(tg.exec_bwd);
-                tg.exec = tg.exec_bwd = nullptr;
+                destroy_exec(&tg.exec); destroy_exec(&tg.exec_bwd);
             }
-            bool all_ok = true;
-            for (int phase = 1; phase <= 2 && all_ok; ++phase) {
-                hipGraph_t g = nullptr;
-                bool ok = hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                st = ok ? enqueue(bucket, phase) : PP_ERR_HIP;
-                if (ok && hipStreamEndCapture(e->stream, &g) != hipSuccess) { ok = false; g = nullptr; }
-                if (ok && st == PP_ERR_UNSUPPORTED) {
-                    if (g) (void)hipGraphDestroy(g);
-                    if (tg.exec) { (void)hipGraphExecDestroy(tg.exec); tg.exec = nullptr; }
+            bool ok = true;
+            for (int phase = 1; phase <= 2 && ok; ++phase) {
+                ok = capture_exec(e, [&] { return enqueue(bucket, phase); }, phase == 1 ? &tg.exec : &tg.exec_bwd, &st);
+                if (st == PP_ERR_UNSUPPORTED) {      // no capture failure: graph_state stays, a forward half already built goes
+                    destroy_exec(&tg.exec);
                     return fail(e, st, "pp_train_step: configuration not supported by the training kernels");
                 }
-                hipGraphExec_t* slot = (phase == 1) ? &tg.exec : &tg.exec_bwd;
-                if (!(ok && st == PP_OK && g != nullptr && hipGraphInstantiate(slot, g, nullptr, nullptr, 0) == hipSuccess)) {
-                    *slot = nullptr;
-                    all_ok = false;
-                }
-                if (g) (void)hipGraphDestroy(g);
             }
-            if (all_ok) {
-                tg.batch = batch; tg.bucket = bucket; tg.zc = e->zc ? 1 : 0;
-                tg.params = params_dev; tg.grads = grads_dev; tg.state = state_dev; tg.loss = *lc;
-                tg.frozen = t->plan.frozen;
-                tg.metrics = e->metrics.on;
+            if (ok) {
+                tg.key = key;
                 ++t->n_captures;
             } else {
-                if (tg.exec) (void)hipGraphExecDestroy(tg.exec);
-                if (tg.exec_bwd) (void)hipGraphExecDestroy(tg.exec_bwd);
-                tg.exec = tg.exec_bwd = nullptr;
+                destroy_exec(&tg.exec); destroy_exec(&tg.exec_bwd);
                 t->graph_state = -1;
-                (void)hipGetLastError();
             }
         }
         if (tg.exec != nullptr && tg.exec_bwd != nullptr) {

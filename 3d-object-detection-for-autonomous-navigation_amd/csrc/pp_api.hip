@@ -23,6 +23,14 @@ int fail(pp_engine* e, int code, const char* fmt, ...) {
     return code;
 }
 
+int check_device(const char* who, int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, PP_ERR_HIP, "%s: no HIP device available (this library has no CPU fallback)", who);
+    if (device < 0 || device >= ndev) return fail(nullptr, PP_ERR_ARG, "%s: device %d not in [0,%d)", who, device, ndev);
+    return PP_OK;
+}
+
 int prof_event(pp_engine* e) {
     if (e->ev_used == (int)e->events.size()) {
         hipEvent_t ev;
@@ -347,14 +355,14 @@ static int run_post(pp_engine* e, int batch, bool to_host = false) {
     p.head = e->d_head; p.cls = e->cls_plane_live ? e->d_cls : nullptr; p.napl = e->napl; p.ncls = e->ncls; p.use_dir = e->use_dir ? 1 : 0; p.mask = e->d_mask; p.anchors = e->d_anchors;
     p.calib = e->d_calib; p.dets = e->d_dets; p.n_dets = e->d_ndets;
     p.dets_host = to_host ? e->h_dets : nullptr; p.n_dets_host = to_host ? e->h_ndets : nullptr;
-    p.nms_mode = e->nms_mode;
-    p.soft_method = e->soft_method; p.soft_sigma = e->soft_sigma; p.soft_floor = e->soft_floor;
-    const bool proj = e->proj.on;
+    const PostRule& r = e->rule;
+    const bool proj = r.proj != 0;
     if (proj && batch > e->proj.batch)
         return fail(e, PP_ERR_STATE, "pp_set_projection gave matrices for %d frames; this pass has %d", e->proj.batch, batch);
-    p.p2 = proj ? e->proj.d_p2 : nullptr; p.bbox = proj ? e->proj.d_bbox : nullptr;
+    p.nms_mode = r.nms_mode; p.soft_method = r.soft_method; p.soft_sigma = r.soft_sigma; p.soft_floor = r.soft_floor;
+    p.class_nms = r.class_nms; p.cls_dets = e->d_cls_dets; p.cls_cnt = e->d_cls_cnt;
+    p.p2 = proj ? e->proj.d_p2 : nullptr; p.bbox = proj ? e->proj.d_bbox : nullptr; p.cls_bbox = proj ? e->proj.d_cls_bbox : nullptr;
     p.bbox_host = (proj && to_host) ? e->proj.h_bbox : nullptr;
-    p.class_nms = e->class_nms; p.cls_dets = e->d_cls_dets; p.cls_cnt = e->d_cls_cnt; p.cls_bbox = proj ? e->proj.d_cls_bbox : nullptr;
     ProfScope ps(e, nullptr);      // the launch sites' own names: k_postprocess and, per-class mode, k_gather_classes
     launch_postprocess(p, e->stream);
     HIPCHK(e, hipGetLastError());
@@ -566,10 +574,7 @@ int pp_create(const pp_config* cfg, int device, pp_handle* out) {
         return fail(nullptr, PP_ERR_UNSUPPORTED, "pp_create: num_anchor_per_loc * (7 + num_class + 2) must fit the %d-column head row", PP_HEAD_COLS);
     if (cfg->nms_post_max_size < 1 || cfg->nms_pre_max_size < 1)
         return fail(nullptr, PP_ERR_ARG, "pp_create: nms sizes must be >= 1");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, PP_ERR_HIP, "pp_create: no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(nullptr, PP_ERR_ARG, "pp_create: device %d not in [0,%d)", device, ndev);
+    if (int st = check_device("pp_create", device)) return st;
     pp_engine* e = new pp_engine();
     e->cfg = *cfg;
     e->device = device;
@@ -790,10 +795,7 @@ int pp_destroy(pp_handle e) {
     for (void* p : {(void*)e->db.pts, (void*)e->db.off, (void*)e->db.box, (void*)e->db.cls, (void*)e->ing.raw, (void*)e->ing.chunks,
                     (void*)e->gdb.out, (void*)e->d_voxels, (void*)e->d_numpts, (void*)e->d_coors, (void*)e->d_feat})
         if (p) (void)hipFree(p);
-    if (e->train) for (auto& tg : e->train->graph) {
-        if (tg.exec) (void)hipGraphExecDestroy(tg.exec);
-        if (tg.exec_bwd) (void)hipGraphExecDestroy(tg.exec_bwd);
-    }
+    if (e->train) for (auto& tg : e->train->graph) { destroy_exec(&tg.exec); destroy_exec(&tg.exec_bwd); }
     delete e->train;
     for (void* p : {(void*)e->h_off_ring, (void*)e->ing.h_ring, (void*)e->crop.h_ring, (void*)e->h_feed[0], (void*)e->h_feed[1], (void*)e->h_train_losses,
                     (void*)e->h_dets, (void*)e->h_ndets, (void*)e->proj.h_bbox, (void*)e->metrics.h_counts})
@@ -1112,7 +1114,7 @@ static void graph_invalidate(pp_engine* e) {
     // outlive it
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (auto& g : e->graphs) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+        destroy_exec(&g.exec);
         g = pp_engine::GraphSlot();
     }
 }
@@ -1139,6 +1141,29 @@ static int enqueue_detect(pp_engine* e, int B, int max_n) {
     if ((st = run_backbone(e, B))) return st;
     // the post-process stores its few kept detections per frame straight into the page-locked result buffers
     return run_post(e, B, true);
+}
+
+// The soft parameters count only while the soft rule runs: in the other modes the key carries fixed values, so changing
+// sigma there costs neither a capture nor an LRU slot.
+static DetectKey detect_key(const pp_engine* e, int B, int bucket) {
+    DetectKey k;
+    k.batch = B; k.bucket = bucket; k.buf = e->in_buf; k.zc = e->zc ? 1 : 0; k.vox = e->vox_ahead ? 1 : 0;
+    k.rule = e->rule;
+    if (k.rule.nms_mode != PP_NMS_SOFT) { k.rule.soft_method = 0; k.rule.soft_sigma = k.rule.soft_floor = 0.f; }
+    return k;
+}
+
+bool capture_exec(pp_engine* e, const std::function<int()>& enqueue, hipGraphExec_t* out, int* enqueue_status) {
+    *out = nullptr;
+    hipGraph_t g = nullptr;
+    bool ok = hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+    const int st = ok ? enqueue() : PP_ERR_HIP;
+    if (ok && hipStreamEndCapture(e->stream, &g) != hipSuccess) { ok = false; g = nullptr; }
+    ok = ok && st == PP_OK && g != nullptr && hipGraphInstantiate(out, g, nullptr, nullptr, 0) == hipSuccess;
+    if (g) (void)hipGraphDestroy(g);
+    if (!ok) { *out = nullptr; (void)hipGetLastError(); }
+    if (enqueue_status) *enqueue_status = st;
+    return ok;
 }
 
 bool graphs_enabled() {
@@ -1169,14 +1194,13 @@ int pp_detect_async(pp_handle e) {
     // ~35 launches per batch replay as ONE graph launch: every kernel argument is a device pointer or a
     // per-(batch, max points) constant, so the captured graph is reusable until either changes (profiling
     // needs the per-launch events and uses plain launches)
+    bool launched = false;
     if (e->prof <= 0 && e->graph_state == 0 && graphs_enabled()) {
-        const int bucket = graph_bucket(e, e->cur_max_n);
+        const DetectKey key = detect_key(e, B, graph_bucket(e, e->cur_max_n));
         pp_engine::GraphSlot* slot = nullptr;
         pp_engine::GraphSlot* lru = &e->graphs[0];
         for (auto& g : e->graphs) {
-            if (g.exec && g.batch == B && g.bucket == bucket && g.buf == e->in_buf && g.zc == (e->zc ? 1 : 0) &&
-                g.vox == (e->vox_ahead ? 1 : 0) && g.nms == e->nms_mode && g.proj == (e->proj.on ? 1 : 0) && g.cnms == e->class_nms &&
-                (e->nms_mode != PP_NMS_SOFT || (g.smethod == e->soft_method && g.ssigma == e->soft_sigma && g.sfloor == e->soft_floor))) slot = &g;
+            if (g.exec && g.key == key) slot = &g;
             if (g.used < lru->used) lru = &g;
         }
         if (slot == nullptr) {
@@ -1184,50 +1208,26 @@ int pp_detect_async(pp_handle e) {
             if (slot->exec) {
                 // LRU eviction: the evicted graph may still be replaying (pp_detect_async does not wait)
                 HIPCHK(e, hipStreamSynchronize(e->stream));
-                (void)hipGraphExecDestroy(slot->exec);
+                destroy_exec(&slot->exec);
             }
             *slot = pp_engine::GraphSlot();
-            hipGraph_t g = nullptr;
-            bool ok = hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-            int st = ok ? enqueue_detect(e, B, bucket) : PP_ERR_HIP;
-            if (ok && hipStreamEndCapture(e->stream, &g) != hipSuccess) { ok = false; g = nullptr; }
-            if (ok && st == PP_OK && g != nullptr && hipGraphInstantiate(&slot->exec, g, nullptr, nullptr, 0) == hipSuccess) {
-                slot->batch = B;
-                slot->bucket = bucket;
-                slot->buf = e->in_buf;
-                slot->zc = e->zc ? 1 : 0;
-                slot->vox = e->vox_ahead ? 1 : 0;
-                slot->nms = e->nms_mode;
-                slot->smethod = e->soft_method; slot->ssigma = e->soft_sigma; slot->sfloor = e->soft_floor;
-                slot->proj = e->proj.on ? 1 : 0;
-                slot->cnms = e->class_nms;
-            } else {
-                slot->exec = nullptr;
-                e->graph_state = -1;           // fall back to plain launches for the life of the handle
-                (void)hipGetLastError();
-            }
-            if (g) (void)hipGraphDestroy(g);
+            if (capture_exec(e, [&] { return enqueue_detect(e, B, key.bucket); }, &slot->exec, nullptr)) slot->key = key;
+            else e->graph_state = -1;          // fall back to plain launches for the life of the handle
         }
         if (slot->exec != nullptr) {
             slot->used = ++e->graph_tick;
             HIPCHK(e, hipGraphLaunch(slot->exec, e->stream));
-            HIPCHK(e, hipEventRecord(e->ev_read[e->in_buf], e->stream));
-            e->results_batch = B;
-            e->results_buf = e->in_buf;
-            e->proj.results = e->proj.on ? B : 0;
-            e->results_rows = det_rows(e);
-            return PP_OK;
+            launched = true;
         }
     }
-    int st = enqueue_detect(e, B, e->cur_max_n);
-    if (st == PP_OK) {
-        HIPCHK(e, hipEventRecord(e->ev_read[e->in_buf], e->stream));
-        e->results_batch = B;
-        e->results_buf = e->in_buf;
-        e->proj.results = e->proj.on ? B : 0;
-        e->results_rows = det_rows(e);
-    }
-    return st;
+    if (!launched)
+        if (int st = enqueue_detect(e, B, e->cur_max_n)) return st;
+    HIPCHK(e, hipEventRecord(e->ev_read[e->in_buf], e->stream));
+    e->results_batch = B;
+    e->results_buf = e->in_buf;
+    e->proj.results = e->rule.proj ? B : 0;
+    e->results_rows = det_rows(e);
+    return PP_OK;
 }
 
 int pp_sync(pp_handle e) {
@@ -1420,11 +1420,11 @@ int pp_predict(pp_handle e, const float* box_preds, const float* cls_preds, cons
     const size_t rows = (size_t)det_rows(e);
     HIPCHK(e, hipMemcpyAsync(dets, e->d_dets, (size_t)batch * rows * sizeof(pp_detection), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipMemcpyAsync(n_dets, e->d_ndets, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    if (e->proj.on)
+    if (e->rule.proj)
         HIPCHK(e, hipMemcpyAsync(e->proj.h_bbox, e->proj.d_bbox, (size_t)batch * rows * 4 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     stage_call_done(e);
-    if (e->proj.on) {      // pp_get_bboxes reads the counts beside the boxes (flags included: it reports PP_ERR_NUMERIC too)
+    if (e->rule.proj) {      // pp_get_bboxes reads the counts beside the boxes (flags included: it reports PP_ERR_NUMERIC too)
         memcpy(e->h_ndets, n_dets, (size_t)batch * sizeof(int));
         e->proj.results = batch;
         e->results_rows = (int)rows;

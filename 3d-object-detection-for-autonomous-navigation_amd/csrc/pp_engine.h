@@ -26,6 +26,44 @@ struct GtSet {
     int* cnt = nullptr;          // [B]
 };
 
+// The detector's post-process settings: what pp_set_nms_mode, pp_set_soft_nms, pp_set_class_nms and the on / off half of
+// pp_set_projection write and the next run_post reads.  The soft parameters are kernel arguments of the PP_NMS_SOFT
+// instantiation only.
+struct PostRule {
+    int nms_mode = PP_NMS_STANDUP;
+    int soft_method = PP_SOFT_NMS_GAUSSIAN;
+    float soft_sigma = 0.5f, soft_floor = 0.001f;
+    int class_nms = PP_CLASS_NMS_JOINT;   // joint (one pass for all classes) or per class
+    int proj = 0;                         // image boxes of the kept detections on / off
+    bool operator==(const PostRule& o) const {
+        return nms_mode == o.nms_mode && soft_method == o.soft_method && soft_sigma == o.soft_sigma &&
+               soft_floor == o.soft_floor && class_nms == o.class_nms && proj == o.proj;
+    }
+};
+
+// Everything a captured inference pass depends on, apart from what graph_invalidate drops the passes for (weights, cache
+// budget): frames, point-count bucket, input buffer, zero-copy feed, voxelised at upload time, and the rule.
+struct DetectKey {
+    int batch = -1, bucket = -1, buf = -1, zc = 0, vox = 0;
+    PostRule rule;
+    bool operator==(const DetectKey& o) const {
+        return batch == o.batch && bucket == o.bucket && buf == o.buf && zc == o.zc && vox == o.vox && rule == o.rule;
+    }
+};
+
+// What the two halves of a training step were captured with; train_key (api_train.hip) is the only place to extend it.
+struct TrainKey {
+    int batch = -1, bucket = -1, zc = 0;
+    const void *params = nullptr, *grads = nullptr, *state = nullptr;
+    pp_loss_config loss = {};
+    std::vector<unsigned char> frozen;     // TrainPlan::frozen
+    bool metrics = false;                  // pp_set_train_metrics
+    bool operator==(const TrainKey& o) const {
+        return batch == o.batch && bucket == o.bucket && zc == o.zc && params == o.params && grads == o.grads &&
+               state == o.state && memcmp(&loss, &o.loss, sizeof(loss)) == 0 && frozen == o.frozen && metrics == o.metrics;
+    }
+};
+
 struct pp_engine {
     pp_config cfg;
     int device = 0;
@@ -216,7 +254,7 @@ struct pp_engine {
     } crop;
 
     struct Metrics {                       // training metrics (pp_head_metrics / pp_set_train_metrics; api_metrics.hip: ensure_metrics)
-        bool on = false;                   // pp_set_train_metrics: the following steps count (part of a training graph's key)
+        bool on = false;                   // pp_set_train_metrics: the following steps count
         int* partials = nullptr;           // [B * metrics_blocks(H' * W')][PP_METRICS_COUNTS]
         long long* counts = nullptr;       // [PP_METRICS_COUNTS]
         long long* h_counts = nullptr;     // pinned twin: a step's counts travel behind its losses
@@ -238,11 +276,7 @@ struct pp_engine {
         struct Graph {
             hipGraphExec_t exec = nullptr;     // voxelise + forward
             hipGraphExec_t exec_bwd = nullptr; // loss + backward (launched behind the target upload's event)
-            int batch = -1, bucket = -1, zc = 0;
-            const void *params = nullptr, *grads = nullptr, *state = nullptr;
-            pp_loss_config loss;
-            std::vector<unsigned char> frozen;     // TrainPlan::frozen it was captured with
-            bool metrics = false;                  // pp_set_train_metrics it was captured with
+            TrainKey key;
         } graph[2];
         int last_batch = 0;    // frames of the last step (pp_train_fetch_decisions)
         int graph_state = 0;   // -1: capture failed once, plain launches from then on
@@ -268,19 +302,14 @@ struct pp_engine {
         PubHead head;
         int64_t publishes = 0, reallocations = 0, graph_invalidations = 0;
     } pub;
-    int nms_mode = PP_NMS_STANDUP; // pp_set_nms_mode: the post-process instantiation of the next pass (part of a graph's key)
-    // pp_set_soft_nms: kernel arguments of the PP_NMS_SOFT instantiation, so part of a graph's key as well
-    int soft_method = PP_SOFT_NMS_GAUSSIAN;
-    float soft_sigma = 0.5f, soft_floor = 0.001f;
-    // pp_set_class_nms: joint (one pass for all classes) or per class.  The result buffers (d_dets, h_dets, the projection's
-    // boxes) hold ncls * nms_post_max_size rows per frame; a pass uses the row stride of the mode it ran in (det_rows)
-    int class_nms = PP_CLASS_NMS_JOINT;   // the next pass's mode (part of a graph's key)
+    PostRule rule;                        // the next pass's post-process settings
+    // The result buffers (d_dets, h_dets, the projection's boxes) hold ncls * nms_post_max_size rows per frame; a pass uses
+    // the row stride of the class mode it ran in (det_rows)
     int results_rows = 0;                 // row stride of the last pass whose results can be fetched (pp_get_detections, pp_get_bboxes)
     pp_detection* d_cls_dets = nullptr;   // [B][ncls][nms_post_max_size]: the classes' segments, before k_gather_classes
     int* d_cls_cnt = nullptr;             // [B][ncls]
-    // pp_set_projection: image boxes of the kept detections (allocated on first use; `on` is part of a graph's key)
+    // pp_set_projection: image boxes of the kept detections (allocated on first use; on / off is rule.proj)
     struct Projection {
-        bool on = false;
         int batch = 0;                 // frames the matrices were given for
         std::vector<double> h_p2;      // what d_p2 holds (an unchanged set is not uploaded again)
         double* d_p2 = nullptr;        // [B][16]
@@ -291,9 +320,15 @@ struct pp_engine {
     } proj;
 
     int prof = 0;
-    // pp_detect_async as one hipGraph launch (captured on first use per (batch, max points per frame))
-    struct GraphSlot { hipGraphExec_t exec = nullptr; int batch = -1, bucket = -1, buf = -1, zc = 0, vox = 0, nms = 0, proj = 0, cnms = 0; int smethod = 0; float ssigma = 0.f, sfloor = 0.f; unsigned long long used = 0; };
-    GraphSlot graphs[8];          // small LRU keyed by (batch, point-count bucket, input buffer, NMS rule with the soft rule's parameters, projection on / off, class mode)
+    // pp_detect_async as one hipGraph launch, captured on first use per key.  The key is a DetectKey: whatever a pass
+    // reads that is neither behind a device pointer nor dropped by graph_invalidate.  detect_key (pp_api.hip) builds it and
+    // is the only place to extend it: lookup and fill-in compare and assign the value as a whole.
+    struct GraphSlot {
+        hipGraphExec_t exec = nullptr;
+        DetectKey key;
+        unsigned long long used = 0;      // graph_tick of its last launch
+    };
+    GraphSlot graphs[8];          // small LRU
     unsigned long long graph_tick = 0;
     int graph_state = 0;          // 0: try, -1: capture failed once (use plain launches)
     std::vector<hipEvent_t> events;
@@ -311,6 +346,16 @@ int fail(pp_engine* e, int code, const char* fmt, ...);
         if (_st != hipSuccess)                                                                       \
             return fail(e, PP_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_st), __FILE__, __LINE__); \
     } while (0)
+
+// ---- the calls that need no handle: host buffers in, host buffers out, device memory for the call's duration ----
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+};
+int check_device(const char* who, int device);          // pp_api.hip: a HIP device exists and `device` names one
+// (expects the entry point's name in a local `who`)
+#define DEVCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(nullptr, PP_ERR_HIP, "%s: %s", who, hipGetErrorString(e_)); } while (0)
 
 template <typename Tp>
 int dalloc(pp_engine* e, Tp** p, size_t count) {
@@ -375,10 +420,14 @@ int check_batch(pp_engine* e, int batch);
 int check_numeric(pp_engine* e, const int* n_dets, int B, const char* who);   // PP_ERR_NUMERIC for a flagged frame
 // result rows per frame in the handle's current class mode (pp_get_detection_rows)
 inline int det_rows(const pp_engine* e) {
-    return (e->class_nms == PP_CLASS_NMS_PER_CLASS ? e->ncls : 1) * e->cfg.nms_post_max_size;
+    return (e->rule.class_nms == PP_CLASS_NMS_PER_CLASS ? e->ncls : 1) * e->cfg.nms_post_max_size;
 }
 int graph_bucket(const pp_engine* e, int max_n);
 bool graphs_enabled();
+// Captures what `enqueue` queues on e->stream (thread-local capture) and instantiates it into *out.  false, with *out
+// NULL and the sticky HIP error cleared, when a step of that fails; *enqueue_status (optional) is what `enqueue` returned.
+bool capture_exec(pp_engine* e, const std::function<int()>& enqueue, hipGraphExec_t* out, int* enqueue_status);
+inline void destroy_exec(hipGraphExec_t* x) { if (*x) (void)hipGraphExecDestroy(*x); *x = nullptr; }
 void drop_detect_graphs(pp_engine* e);                  // waits for the stream, destroys the captured inference passes
 void decide_sparse_canvas(pp_engine* e);                // from layer 0's weights (pp_finalize_weights, a publish)
 int publish_reapply(pp_engine* e);                      // api_publish.hip: pp_set_gemm_precision on published weights
