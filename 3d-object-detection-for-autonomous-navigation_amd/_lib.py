@@ -18,7 +18,7 @@ _INCLUDE = os.path.join(os.path.dirname(_PKG), "include", "pp_hip.h")
 SO_PATH = os.path.join(_PKG, os.environ.get("PP_HIP_LIB", "libpp_hip.so"))
 _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
 SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_nms.hip", "api_project.hip", "api_class_nms.hip", "api_metrics.hip", "api_publish.hip", "api_train.hip", "api_dataprep.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
-           "rotate_iou.hip", "rotate_nms.hip", "box_project.hip", "loss.hip", "metrics.hip", "optim.hip", "grad_clip.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip", "depth_ingest.hip",
+           "rotate_iou.hip", "rotate_nms.hip", "box_project.hip", "loss.hip", "metrics.hip", "optim.hip", "grad_clip.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip", "depth_ingest.hip", "rig_ingest.hip",
            "gt_database.hip", "eval_stats.hip", "frustum_crop.hip", "weight_publish.hip", "soft_nms.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
@@ -41,6 +41,8 @@ EXPORTS = [
     "pp_gtdb_load", "pp_gt_sample", "pp_gt_sample_info", "pp_train_step_sample_async", "pp_train_step_sample",
     "pp_ingest_pointcloud2", "pp_ingest_pointcloud2_async", "pp_ingest_info",
     "pp_ingest_depth", "pp_ingest_depth_async",
+    "pp_ingest_rig_depth", "pp_ingest_rig_depth_async", "pp_ingest_rig_pointcloud2", "pp_ingest_rig_pointcloud2_async",
+    "pp_ingest_rig_info",
     "pp_gtdb_build", "pp_gtdb_count",
     "pp_eval_match", "pp_eval_pr",
     "pp_frustum_crop", "pp_frustum_crop_async", "pp_frustum_crop_info",
@@ -190,6 +192,7 @@ class PPDepthLayout(ctypes.Structure):
 
 
 PP_DEPTH_U16, PP_DEPTH_F32 = 0, 1      # pp_depth_layout.encoding
+PP_RIG_MAX_SOURCES = 16      # sources per frame of a pp_ingest_rig_* call
 PP_CROP_BACK = 1      # pp_frustum_crop* flags: bit 0
 PP_METRICS_COUNTS = 32      # int64 values of pp_head_metrics / pp_get_train_metrics
 PP_CLASS_NMS_JOINT, PP_CLASS_NMS_PER_CLASS = 0, 1      # enum pp_class_nms
@@ -395,6 +398,10 @@ def lib():
     L.pp_ingest_info.argtypes = [vp, vp, vp, i32]
     L.pp_ingest_depth.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(PPIngestConfig), f32p, i64]
     L.pp_ingest_depth_async.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(PPIngestConfig)]
+    for name in ("pp_ingest_rig_depth", "pp_ingest_rig_pointcloud2"):      # (cfgs: an array of PPIngestConfig)
+        getattr(L, name).argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, f32p, i64]
+        getattr(L, name + "_async").argtypes = [vp, vp, vp, vp, vp, vp, i32, i32]
+    L.pp_ingest_rig_info.argtypes = [vp, vp, vp, i32]
     L.pp_gtdb_build.argtypes = [vp, vp, vp, i32, vp, vp, f32p, i64]
     L.pp_gtdb_count.argtypes = [vp, vp, vp, i32, vp]
     L.pp_eval_match.argtypes = [ctypes.c_int, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]

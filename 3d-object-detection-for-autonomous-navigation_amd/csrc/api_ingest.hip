@@ -1,6 +1,8 @@
 // C-ABI, live-camera ingest (pp_ingest_*): PointCloud2 messages (kernels: ingest.hip) or raw depth images (kernels:
 // depth_ingest.hip) -> the resident points and offsets.  The two feeds differ in their checks, their frame records and
-// their three launches; the staging, the input-buffer flip and the ordering are one path (enqueue_ingest).
+// their three launches; the staging, the input-buffer flip and the ordering are one path (enqueue_ingest).  A rig call
+// (pp_ingest_rig_*; kernels: rig_ingest.hip) takes the same path with one record per SOURCE and the sources' own
+// selections and transforms in a table beside them.
 #include "pp_engine.h"
 
 namespace {
@@ -11,6 +13,7 @@ struct IngestPlanT {
     std::vector<int> bound_off;    // [batch + 1] prefix sums of the frames' kept bounds
     int max_bound = 0, stride = 0;
     int64_t bytes = 0;             // byte_offsets[batch] - byte_offsets[0]
+    std::vector<RigSource> rig;    // a rig call: one entry per source, `frames` then holds the SOURCES' records; else empty
 };
 typedef IngestPlanT<IngFrame> IngestPlan;
 typedef IngestPlanT<DepthFrame> DepthPlan;
@@ -22,57 +25,128 @@ int check_ingest_call(pp_engine* e, const char* who, const int64_t* bo, const vo
         return fail(e, PP_ERR_UNSUPPORTED, "%s: num_point_features is %d, the live path delivers x y z only (3)", who, e->F);
     if (!bo || !L || !c) return fail(e, PP_ERR_ARG, "%s: null argument", who);
     int st = check_batch(e, batch); if (st) return st;
-    if (c->decimate < 1) return fail(e, PP_ERR_ARG, "%s: decimate %d < 1", who, c->decimate);
-    if (c->first < 0) return fail(e, PP_ERR_ARG, "%s: first %d < 0", who, c->first);
     return PP_OK;
 }
 
-// Everything pp_ingest_pointcloud2* refuses, before anything is queued.
-int check_ingest(pp_engine* e, const char* who, const uint8_t* data, const int64_t* bo, const pp_pc2_layout* L, int batch,
-                 const pp_ingest_config* c, IngestPlan* plan) {
+// `at`: "" for the one configuration of a plain call, "source 3: " for a rig's
+int check_selection(pp_engine* e, const char* who, const char* at, const pp_ingest_config* c) {
+    if (c->decimate < 1) return fail(e, PP_ERR_ARG, "%s: %sdecimate %d < 1", who, at, c->decimate);
+    if (c->first < 0) return fail(e, PP_ERR_ARG, "%s: %sfirst %d < 0", who, at, c->first);
+    return PP_OK;
+}
+
+inline int64_t kept_bound(int64_t n, const pp_ingest_config* c) {
+    return n > c->first ? (n - c->first + c->decimate - 1) / c->decimate : 0;
+}
+
+// What is refused about one message (`at`: "frame 1" or "source 3"; its bytes are data[bo[i] .. bo[i + 1])); fills its
+// record and the bound on the points it keeps under `c`.
+int check_pc2_one(pp_engine* e, const char* who, const char* at, const int64_t* bo, int i, const pp_pc2_layout& l,
+                  const pp_ingest_config* c, IngFrame* f, int64_t* bound) {
+    if (l.width < 0 || l.height < 0 || l.point_step < 1 || l.row_step < 0)
+        return fail(e, PP_ERR_ARG, "%s: %s: width %d, height %d, point_step %d, row_step %d", who, at, l.width,
+                    l.height, l.point_step, l.row_step);
+    const int64_t n_rec = (int64_t)l.width * l.height;
+    if (n_rec > (1ll << 30)) return fail(e, PP_ERR_ARG, "%s: %s: width %d x height %d records", who, at, l.width, l.height);
+    if (l.datatype >> 8)
+        return fail(e, PP_ERR_UNSUPPORTED, "%s: %s: datatype: x, y and z differ (%d, %d, %d)", who, at,
+                    l.datatype & 255, (l.datatype >> 8) & 255, (l.datatype >> 16) & 255);
+    if (l.datatype >= 1 && l.datatype <= 6)
+        return fail(e, PP_ERR_UNSUPPORTED, "%s: %s: datatype %d is an integer type (7 FLOAT32 or 8 FLOAT64)", who, at, l.datatype);
+    if (l.datatype != 7 && l.datatype != 8)
+        return fail(e, PP_ERR_ARG, "%s: %s: unknown datatype %d", who, at, l.datatype);
+    const int size = l.datatype == 8 ? 8 : 4;
+    const int offs[3] = {l.x_offset, l.y_offset, l.z_offset};
+    static const char* const names[3] = {"x_offset", "y_offset", "z_offset"};
+    for (int k = 0; k < 3; ++k)
+        if (offs[k] < 0 || (int64_t)offs[k] + size > l.point_step)
+            return fail(e, PP_ERR_ARG, "%s: %s: %s %d (%d bytes) does not fit point_step %d", who, at, names[k], offs[k],
+                        size, l.point_step);
+    if ((int64_t)l.row_step < (int64_t)l.width * l.point_step)
+        return fail(e, PP_ERR_ARG, "%s: %s: row_step %d < width %d x point_step %d", who, at, l.row_step, l.width, l.point_step);
+    const int64_t need = (int64_t)l.height * l.row_step;
+    if (bo[i] < 0 || bo[i + 1] < bo[i] || bo[i + 1] - bo[i] < need)
+        return fail(e, PP_ERR_ARG, "%s: %s: byte_offsets give it %lld bytes, height %d x row_step %d = %lld needed", who, at,
+                    (long long)(bo[i + 1] - bo[i]), l.height, l.row_step, (long long)need);
+    *bound = kept_bound(n_rec, c);
+    f->byte_off = bo[i] - bo[0];
+    f->n_rec = (int)n_rec;
+    const bool tight = l.row_step == l.width * l.point_step || l.height <= 1;
+    f->width = tight ? (int)n_rec : l.width;
+    f->point_step = l.point_step; f->row_step = l.row_step;
+    f->x_off = l.x_offset; f->y_off = l.y_offset; f->z_off = l.z_offset;
+    f->f64 = l.datatype == 8; f->big_endian = l.is_bigendian != 0;
+    f->nchunks = ingest_chunks(f->n_rec);
+    return PP_OK;
+}
+
+// The same for one depth image.
+int check_depth_one(pp_engine* e, const char* who, const char* at, const int64_t* bo, int i, const pp_depth_layout& l,
+                    const pp_ingest_config* c, DepthFrame* f, int64_t* bound) {
+    if (l.width < 0 || l.height < 0 || l.row_step < 0)
+        return fail(e, PP_ERR_ARG, "%s: %s: width %d, height %d, row_step %d", who, at, l.width, l.height, l.row_step);
+    const int64_t n_pix = (int64_t)l.width * l.height;
+    if (n_pix > (1ll << 30)) return fail(e, PP_ERR_ARG, "%s: %s: width %d x height %d pixels", who, at, l.width, l.height);
+    if (l.encoding != PP_DEPTH_U16 && l.encoding != PP_DEPTH_F32)
+        return fail(e, PP_ERR_ARG, "%s: %s: unknown encoding %d (PP_DEPTH_U16 %d or PP_DEPTH_F32 %d)", who, at, l.encoding,
+                    (int)PP_DEPTH_U16, (int)PP_DEPTH_F32);
+    const int size = l.encoding == PP_DEPTH_F32 ? 4 : 2;
+    if ((int64_t)l.row_step < (int64_t)l.width * size)
+        return fail(e, PP_ERR_ARG, "%s: %s: row_step %d < width %d x %d bytes", who, at, l.row_step, l.width, size);
+    const int64_t need = (int64_t)l.height * l.row_step;
+    if (bo[i] < 0 || bo[i + 1] < bo[i] || bo[i + 1] - bo[i] < need)
+        return fail(e, PP_ERR_ARG, "%s: %s: byte_offsets give it %lld bytes, height %d x row_step %d = %lld needed", who, at,
+                    (long long)(bo[i + 1] - bo[i]), l.height, l.row_step, (long long)need);
+    const float focal[2] = {l.fx, l.fy}, centre[2] = {l.ppx, l.ppy};
+    static const char* const fnames[2] = {"fx", "fy"};
+    static const char* const cnames[2] = {"ppx", "ppy"};
+    for (int k = 0; k < 2; ++k) {
+        if (!std::isfinite(focal[k]) || focal[k] == 0.0f)
+            return fail(e, PP_ERR_ARG, "%s: %s: %s %g is not a finite non-zero focal length", who, at, fnames[k], (double)focal[k]);
+        if (!std::isfinite(centre[k]))
+            return fail(e, PP_ERR_ARG, "%s: %s: %s %g is not finite", who, at, cnames[k], (double)centre[k]);
+    }
+    if (l.encoding == PP_DEPTH_U16 && !(std::isfinite(l.depth_scale) && l.depth_scale > 0.0f))
+        return fail(e, PP_ERR_ARG, "%s: %s: depth_scale %g is not a finite positive number", who, at, (double)l.depth_scale);
+    if (!(l.z_min <= l.z_max))
+        return fail(e, PP_ERR_ARG, "%s: %s: z_min %g > z_max %g (or one is NaN)", who, at, (double)l.z_min, (double)l.z_max);
+    *bound = kept_bound(n_pix, c);
+    f->byte_off = bo[i] - bo[0];
+    f->width = l.width; f->n_pix = (int)n_pix; f->row_step = l.row_step;
+    f->tight = l.row_step == l.width * size || l.height <= 1;
+    f->f32 = l.encoding == PP_DEPTH_F32; f->big_endian = l.is_bigendian != 0;
+    f->nchunks = depth_chunks(f->n_pix);
+    f->fx = l.fx; f->fy = l.fy; f->ppx = l.ppx; f->ppy = l.ppy;
+    f->depth_scale = l.depth_scale; f->z_min = l.z_min; f->z_max = l.z_max;
+    return PP_OK;
+}
+
+inline int check_one(pp_engine* e, const char* who, const char* at, const int64_t* bo, int i, const pp_pc2_layout& l,
+                     const pp_ingest_config* c, IngFrame* f, int64_t* bound) {
+    return check_pc2_one(e, who, at, bo, i, l, c, f, bound);
+}
+inline int check_one(pp_engine* e, const char* who, const char* at, const int64_t* bo, int i, const pp_depth_layout& l,
+                     const pp_ingest_config* c, DepthFrame* f, int64_t* bound) {
+    return check_depth_one(e, who, at, bo, i, l, c, f, bound);
+}
+
+// Everything pp_ingest_pointcloud2* / pp_ingest_depth* refuse, before anything is queued.
+template <typename Layout, typename Frame>
+int check_frames(pp_engine* e, const char* who, const uint8_t* data, const int64_t* bo, const Layout* L, int batch,
+                 const pp_ingest_config* c, IngestPlanT<Frame>* plan) {
     int st = check_ingest_call(e, who, bo, L, batch, c); if (st) return st;
-    plan->frames.assign((size_t)batch, IngFrame());
+    if ((st = check_selection(e, who, "", c))) return st;
+    plan->frames.assign((size_t)batch, Frame());
     plan->bound_off.assign((size_t)batch + 1, 0);
     for (int b = 0; b < batch; ++b) {
-        const pp_pc2_layout& l = L[b];
-        if (l.width < 0 || l.height < 0 || l.point_step < 1 || l.row_step < 0)
-            return fail(e, PP_ERR_ARG, "%s: frame %d: width %d, height %d, point_step %d, row_step %d", who, b, l.width,
-                        l.height, l.point_step, l.row_step);
-        const int64_t n_rec = (int64_t)l.width * l.height;
-        if (n_rec > (1ll << 30)) return fail(e, PP_ERR_ARG, "%s: frame %d: width %d x height %d records", who, b, l.width, l.height);
-        if (l.datatype >> 8)
-            return fail(e, PP_ERR_UNSUPPORTED, "%s: frame %d: datatype: x, y and z differ (%d, %d, %d)", who, b,
-                        l.datatype & 255, (l.datatype >> 8) & 255, (l.datatype >> 16) & 255);
-        if (l.datatype >= 1 && l.datatype <= 6)
-            return fail(e, PP_ERR_UNSUPPORTED, "%s: frame %d: datatype %d is an integer type (7 FLOAT32 or 8 FLOAT64)", who, b, l.datatype);
-        if (l.datatype != 7 && l.datatype != 8)
-            return fail(e, PP_ERR_ARG, "%s: frame %d: unknown datatype %d", who, b, l.datatype);
-        const int size = l.datatype == 8 ? 8 : 4;
-        const int offs[3] = {l.x_offset, l.y_offset, l.z_offset};
-        static const char* const names[3] = {"x_offset", "y_offset", "z_offset"};
-        for (int k = 0; k < 3; ++k)
-            if (offs[k] < 0 || (int64_t)offs[k] + size > l.point_step)
-                return fail(e, PP_ERR_ARG, "%s: frame %d: %s %d (%d bytes) does not fit point_step %d", who, b, names[k], offs[k],
-                            size, l.point_step);
-        if ((int64_t)l.row_step < (int64_t)l.width * l.point_step)
-            return fail(e, PP_ERR_ARG, "%s: frame %d: row_step %d < width %d x point_step %d", who, b, l.row_step, l.width, l.point_step);
-        const int64_t need = (int64_t)l.height * l.row_step;
-        if (bo[b] < 0 || bo[b + 1] < bo[b] || bo[b + 1] - bo[b] < need)
-            return fail(e, PP_ERR_ARG, "%s: frame %d: byte_offsets give it %lld bytes, height %d x row_step %d = %lld needed", who, b,
-                        (long long)(bo[b + 1] - bo[b]), l.height, l.row_step, (long long)need);
-        const int64_t bound = n_rec > c->first ? (n_rec - c->first + c->decimate - 1) / c->decimate : 0;
+        char at[32];
+        snprintf(at, sizeof(at), "frame %d", b);
+        int64_t bound = 0;
+        Frame& f = plan->frames[(size_t)b];
+        if ((st = check_one(e, who, at, bo, b, L[b], c, &f, &bound))) return st;
         if (bound > e->NMAX)
             return fail(e, PP_ERR_ARG, "%s: frame %d: width %d x height %d keeps up to %lld points > max_points_per_frame=%d", who, b,
-                        l.width, l.height, (long long)bound, e->NMAX);
-        IngFrame& f = plan->frames[(size_t)b];
-        f.byte_off = bo[b] - bo[0];
-        f.n_rec = (int)n_rec;
-        const bool tight = l.row_step == l.width * l.point_step || l.height <= 1;
-        f.width = tight ? (int)n_rec : l.width;
-        f.point_step = l.point_step; f.row_step = l.row_step;
-        f.x_off = l.x_offset; f.y_off = l.y_offset; f.z_off = l.z_offset;
-        f.f64 = l.datatype == 8; f.big_endian = l.is_bigendian != 0;
-        f.nchunks = ingest_chunks(f.n_rec);
+                        L[b].width, L[b].height, (long long)bound, e->NMAX);
         plan->stride = std::max(plan->stride, f.nchunks);
         plan->max_bound = std::max(plan->max_bound, (int)bound);
         plan->bound_off[(size_t)b + 1] = plan->bound_off[(size_t)b] + (int)bound;
@@ -82,58 +156,70 @@ int check_ingest(pp_engine* e, const char* who, const uint8_t* data, const int64
     return PP_OK;
 }
 
-// Everything pp_ingest_depth* refuses, before anything is queued.
+int check_ingest(pp_engine* e, const char* who, const uint8_t* data, const int64_t* bo, const pp_pc2_layout* L, int batch,
+                 const pp_ingest_config* c, IngestPlan* plan) {
+    return check_frames(e, who, data, bo, L, batch, c, plan);
+}
 int check_depth(pp_engine* e, const char* who, const uint8_t* data, const int64_t* bo, const pp_depth_layout* L, int batch,
                 const pp_ingest_config* c, DepthPlan* plan) {
-    int st = check_ingest_call(e, who, bo, L, batch, c); if (st) return st;
-    plan->frames.assign((size_t)batch, DepthFrame());
-    plan->bound_off.assign((size_t)batch + 1, 0);
-    for (int b = 0; b < batch; ++b) {
-        const pp_depth_layout& l = L[b];
-        if (l.width < 0 || l.height < 0 || l.row_step < 0)
-            return fail(e, PP_ERR_ARG, "%s: frame %d: width %d, height %d, row_step %d", who, b, l.width, l.height, l.row_step);
-        const int64_t n_pix = (int64_t)l.width * l.height;
-        if (n_pix > (1ll << 30)) return fail(e, PP_ERR_ARG, "%s: frame %d: width %d x height %d pixels", who, b, l.width, l.height);
-        if (l.encoding != PP_DEPTH_U16 && l.encoding != PP_DEPTH_F32)
-            return fail(e, PP_ERR_ARG, "%s: frame %d: unknown encoding %d (PP_DEPTH_U16 %d or PP_DEPTH_F32 %d)", who, b, l.encoding,
-                        (int)PP_DEPTH_U16, (int)PP_DEPTH_F32);
-        const int size = l.encoding == PP_DEPTH_F32 ? 4 : 2;
-        if ((int64_t)l.row_step < (int64_t)l.width * size)
-            return fail(e, PP_ERR_ARG, "%s: frame %d: row_step %d < width %d x %d bytes", who, b, l.row_step, l.width, size);
-        const int64_t need = (int64_t)l.height * l.row_step;
-        if (bo[b] < 0 || bo[b + 1] < bo[b] || bo[b + 1] - bo[b] < need)
-            return fail(e, PP_ERR_ARG, "%s: frame %d: byte_offsets give it %lld bytes, height %d x row_step %d = %lld needed", who, b,
-                        (long long)(bo[b + 1] - bo[b]), l.height, l.row_step, (long long)need);
-        const float focal[2] = {l.fx, l.fy}, centre[2] = {l.ppx, l.ppy};
-        static const char* const fnames[2] = {"fx", "fy"};
-        static const char* const cnames[2] = {"ppx", "ppy"};
-        for (int k = 0; k < 2; ++k) {
-            if (!std::isfinite(focal[k]) || focal[k] == 0.0f)
-                return fail(e, PP_ERR_ARG, "%s: frame %d: %s %g is not a finite non-zero focal length", who, b, fnames[k], (double)focal[k]);
-            if (!std::isfinite(centre[k]))
-                return fail(e, PP_ERR_ARG, "%s: frame %d: %s %g is not finite", who, b, cnames[k], (double)centre[k]);
-        }
-        if (l.encoding == PP_DEPTH_U16 && !(std::isfinite(l.depth_scale) && l.depth_scale > 0.0f))
-            return fail(e, PP_ERR_ARG, "%s: frame %d: depth_scale %g is not a finite positive number", who, b, (double)l.depth_scale);
-        if (!(l.z_min <= l.z_max))
-            return fail(e, PP_ERR_ARG, "%s: frame %d: z_min %g > z_max %g (or one is NaN)", who, b, (double)l.z_min, (double)l.z_max);
-        const int64_t bound = n_pix > c->first ? (n_pix - c->first + c->decimate - 1) / c->decimate : 0;
-        if (bound > e->NMAX)
-            return fail(e, PP_ERR_ARG, "%s: frame %d: width %d x height %d keeps up to %lld points > max_points_per_frame=%d", who, b,
-                        l.width, l.height, (long long)bound, e->NMAX);
-        DepthFrame& f = plan->frames[(size_t)b];
-        f.byte_off = bo[b] - bo[0];
-        f.width = l.width; f.n_pix = (int)n_pix; f.row_step = l.row_step;
-        f.tight = l.row_step == l.width * size || l.height <= 1;
-        f.f32 = l.encoding == PP_DEPTH_F32; f.big_endian = l.is_bigendian != 0;
-        f.nchunks = depth_chunks(f.n_pix);
-        f.fx = l.fx; f.fy = l.fy; f.ppx = l.ppx; f.ppy = l.ppy;
-        f.depth_scale = l.depth_scale; f.z_min = l.z_min; f.z_max = l.z_max;
-        plan->stride = std::max(plan->stride, f.nchunks);
-        plan->max_bound = std::max(plan->max_bound, (int)bound);
-        plan->bound_off[(size_t)b + 1] = plan->bound_off[(size_t)b] + (int)bound;
+    return check_frames(e, who, data, bo, L, batch, c, plan);
+}
+
+// Everything pp_ingest_rig_* refuse, before anything is queued: the frame map, then per source what the single-camera
+// calls refuse per frame, then the frames' summed bounds.
+template <typename Layout, typename Frame>
+int check_rig(pp_engine* e, const char* who, const uint8_t* data, const int64_t* bo, const Layout* L,
+              const pp_ingest_config* cfgs, const int32_t* source_frame, int sources, int batch, IngestPlanT<Frame>* plan) {
+    int st = check_ingest_call(e, who, bo, L, batch, cfgs); if (st) return st;
+    if (!source_frame) return fail(e, PP_ERR_ARG, "%s: null argument", who);
+    if (sources < 1) return fail(e, PP_ERR_ARG, "%s: sources %d < 1", who, sources);
+    if (source_frame[0] != 0)
+        return fail(e, PP_ERR_ARG, "%s: source 0: source_frame %d, the frame map starts at frame 0", who, source_frame[0]);
+    for (int s = 1, run = 1; s < sources; ++s) {
+        const int prev = source_frame[s - 1], cur = source_frame[s];
+        if (cur < prev)
+            return fail(e, PP_ERR_ARG, "%s: source %d: source_frame %d < %d of the source before it (the frame map never decreases)",
+                        who, s, cur, prev);
+        if (cur > prev + 1)
+            return fail(e, PP_ERR_ARG, "%s: source %d: source_frame %d skips frame %d (every frame has at least one source)", who, s,
+                        cur, prev + 1);
+        run = cur == prev ? run + 1 : 1;
+        if (run > PP_RIG_MAX_SOURCES)
+            return fail(e, PP_ERR_ARG, "%s: source %d: frame %d has more than PP_RIG_MAX_SOURCES=%d sources", who, s, cur,
+                        PP_RIG_MAX_SOURCES);
     }
-    plan->bytes = bo[batch] - bo[0];
+    if (source_frame[sources - 1] != batch - 1)
+        return fail(e, PP_ERR_ARG, "%s: source %d: source_frame %d, the frame map ends at frame batch - 1 = %d", who, sources - 1,
+                    source_frame[sources - 1], batch - 1);
+    plan->frames.assign((size_t)sources, Frame());
+    plan->rig.assign((size_t)sources, RigSource());
+    plan->bound_off.assign((size_t)batch + 1, 0);
+    std::vector<int64_t> sum((size_t)batch, 0);
+    for (int s = 0; s < sources; ++s) {
+        char at[32];
+        snprintf(at, sizeof(at), "source %d: ", s);
+        const pp_ingest_config* c = cfgs + s;
+        if ((st = check_selection(e, who, at, c))) return st;
+        snprintf(at, sizeof(at), "source %d", s);
+        int64_t bound = 0;
+        Frame& f = plan->frames[(size_t)s];
+        if ((st = check_one(e, who, at, bo, s, L[s], c, &f, &bound))) return st;
+        const int b = source_frame[s];
+        sum[(size_t)b] += bound;
+        if (sum[(size_t)b] > e->NMAX)
+            return fail(e, PP_ERR_ARG, "%s: source %d: frame %d keeps up to %lld points with it (width %d x height %d: %lld) > "
+                        "max_points_per_frame=%d", who, s, b, (long long)sum[(size_t)b], L[s].width, L[s].height, (long long)bound,
+                        e->NMAX);
+        RigSource& g = plan->rig[(size_t)s];
+        g.frame = b; g.first = c->first; g.decimate = c->decimate; g.reserved = 0;
+        memcpy(g.r, c->r, sizeof(g.r)); memcpy(g.r2, c->r2, sizeof(g.r2)); memcpy(g.lift, c->lift, sizeof(g.lift));
+        plan->stride = std::max(plan->stride, f.nchunks);
+    }
+    for (int b = 0; b < batch; ++b) {
+        plan->max_bound = std::max(plan->max_bound, (int)sum[(size_t)b]);
+        plan->bound_off[(size_t)b + 1] = plan->bound_off[(size_t)b] + (int)sum[(size_t)b];
+    }
+    plan->bytes = bo[sources] - bo[0];
     if (plan->bytes > 0 && !data) return fail(e, PP_ERR_ARG, "%s: data is NULL", who);
     return PP_OK;
 }
@@ -147,17 +233,37 @@ int ensure_ing(pp_engine* e) {
     return A.st;
 }
 
+// the per-source tables of a rig call, for the most sources a call can have
+int ensure_rig(pp_engine* e) {
+    pp_engine::Ing::Rig& r = e->ing.rig;
+    if (r.frames) return PP_OK;
+    const size_t cap = (size_t)PP_RIG_MAX_SOURCES * e->B;
+    if (!r.h_frames) HIPCHK(e, hipHostMalloc((void**)&r.h_frames, (size_t)pp_engine::OFF_RING * cap * sizeof(pp_engine::Ing::Slot)));
+    if (!r.h_src) HIPCHK(e, hipHostMalloc((void**)&r.h_src, (size_t)pp_engine::OFF_RING * cap * sizeof(RigSource)));
+    r.sources_cap = (int)cap;
+    DevAlloc A{e};
+    A(&r.src, cap); A(&r.finite, cap); A(&r.kept, cap); A(&r.out_base, cap); A(&r.frames, cap);     // (frames last: the ready flag)
+    return A.st;
+}
+
 inline void launch_frames(const IngestParams& p, hipStream_t s) { launch_ingest(p, s); }
 inline void launch_frames(const DepthIngestParams& p, hipStream_t s) { launch_depth_ingest(p, s); }
 
 // Flips to the other input buffer (as set_offsets does) and queues bytes -> staging -> points + offsets on `stream`
-// (the main stream, or the copy stream: it first waits for the pass that last read that buffer).
+// (the main stream, or the copy stream: it first waits for the pass that last read that buffer).  A plain call has one
+// record per frame and one configuration `c`; a rig call (plan.rig not empty, c == NULL) one record and one RigSource per
+// source, in the rig's own tables.
 template <typename Frame>
 int enqueue_ingest(pp_engine* e, const uint8_t* data, const int64_t* bo, int batch, const pp_ingest_config* c,
                    const IngestPlanT<Frame>& plan, hipStream_t stream) {
     int st;
+    const bool rig = !plan.rig.empty();
+    const int records = (int)plan.frames.size();          // frames, or sources
     if ((st = ensure_ing(e))) return st;
-    const size_t tables = 2 * (size_t)batch * plan.stride;
+    if (rig && (st = ensure_rig(e))) return st;
+    if (rig && records > e->ing.rig.sources_cap)
+        return fail(e, PP_ERR_ARG, "%d sources, the handle holds %d", records, e->ing.rig.sources_cap);
+    const size_t tables = 2 * (size_t)records * plan.stride;
     if ((size_t)plan.bytes > e->ing.cap_raw || tables > e->ing.cap_chunks) {
         // an ingest queued earlier on the copy stream may still read what dgrow frees (it waits for the main stream only)
         HIPCHK(e, hipStreamSynchronize(e->copy_stream));
@@ -168,25 +274,47 @@ int enqueue_ingest(pp_engine* e, const uint8_t* data, const int64_t* bo, int bat
     const int slot = e->off_slot;
     e->off_slot = (slot + 1) % pp_engine::OFF_RING;
     HIPCHK(e, hipEventSynchronize(e->off_ev[slot]));   // the copy that last used this slot has been consumed
-    Frame* ring = (Frame*)(e->ing.h_ring + (size_t)slot * e->B);
-    memcpy(ring, plan.frames.data(), (size_t)batch * sizeof(Frame));
+    pp_engine::Ing::Rig& R = e->ing.rig;
+    Frame* ring = (Frame*)(rig ? R.h_frames + (size_t)slot * R.sources_cap : e->ing.h_ring + (size_t)slot * e->B);
+    pp_engine::Ing::Slot* d_frames = rig ? R.frames : e->ing.frames;
+    memcpy(ring, plan.frames.data(), (size_t)records * sizeof(Frame));
     // the kept counts are device values: everything behind this call is sized from the frames' bounds
     set_resident(e, batch, plan.bound_off.data(), plan.max_bound, false);
     e->ing.batch = batch;
+    R.sources = rig ? records : 0;
     const int nb = flip_input(e);
     HIPCHK(e, hipStreamWaitEvent(stream, e->ev_read[nb], 0));
     if (plan.bytes) HIPCHK(e, hipMemcpyAsync(e->ing.raw, data + bo[0], (size_t)plan.bytes, hipMemcpyHostToDevice, stream));
-    HIPCHK(e, hipMemcpyAsync(e->ing.frames, ring, (size_t)batch * sizeof(Frame), hipMemcpyHostToDevice, stream));
+    HIPCHK(e, hipMemcpyAsync(d_frames, ring, (size_t)records * sizeof(Frame), hipMemcpyHostToDevice, stream));
+    if (rig) {
+        RigSource* src_ring = R.h_src + (size_t)slot * R.sources_cap;
+        memcpy(src_ring, plan.rig.data(), (size_t)records * sizeof(RigSource));
+        HIPCHK(e, hipMemcpyAsync(R.src, src_ring, (size_t)records * sizeof(RigSource), hipMemcpyHostToDevice, stream));
+    }
     HIPCHK(e, hipEventRecord(e->off_ev[slot], stream));
-    IngestParamsT<Frame> p;
-    memset(&p, 0, sizeof(p));
-    p.raw = e->ing.raw; p.frames = (const Frame*)e->ing.frames; p.batch = batch; p.stride = plan.stride;
-    p.first = c->first; p.decimate = c->decimate;
-    memcpy(p.r, c->r, sizeof(p.r)); memcpy(p.r2, c->r2, sizeof(p.r2)); memcpy(p.lift, c->lift, sizeof(p.lift));
-    p.chunk_cnt = e->ing.chunks; p.chunk_base = e->ing.chunks + (size_t)batch * plan.stride;
-    p.finite = e->ing.finite; p.kept = e->ing.kept; p.offsets = e->d_offsets; p.out = e->d_points;
-    p.out_rows = (long long)e->B * e->NMAX;
-    {
+    int* const chunk_cnt = e->ing.chunks;
+    int* const chunk_base = e->ing.chunks + (size_t)records * plan.stride;
+    const long long out_rows = (long long)e->B * e->NMAX;
+    if (rig) {
+        RigParamsT<Frame> p;
+        memset(&p, 0, sizeof(p));
+        p.raw = e->ing.raw; p.frames = (const Frame*)d_frames; p.src = R.src;
+        p.sources = records; p.batch = batch; p.stride = plan.stride;
+        p.chunk_cnt = chunk_cnt; p.chunk_base = chunk_base;
+        p.src_finite = R.finite; p.src_kept = R.kept; p.out_base = R.out_base;
+        p.finite = e->ing.finite; p.kept = e->ing.kept; p.offsets = e->d_offsets; p.out = e->d_points;
+        p.out_rows = out_rows;
+        ProfScope ps(e, nullptr);
+        launch_rig_ingest(p, stream);
+    } else {
+        IngestParamsT<Frame> p;
+        memset(&p, 0, sizeof(p));
+        p.raw = e->ing.raw; p.frames = (const Frame*)d_frames; p.batch = batch; p.stride = plan.stride;
+        p.first = c->first; p.decimate = c->decimate;
+        memcpy(p.r, c->r, sizeof(p.r)); memcpy(p.r2, c->r2, sizeof(p.r2)); memcpy(p.lift, c->lift, sizeof(p.lift));
+        p.chunk_cnt = chunk_cnt; p.chunk_base = chunk_base;
+        p.finite = e->ing.finite; p.kept = e->ing.kept; p.offsets = e->d_offsets; p.out = e->d_points;
+        p.out_rows = out_rows;
         ProfScope ps(e, nullptr);
         launch_frames(p, stream);
     }
@@ -261,6 +389,70 @@ int pp_ingest_depth_async(pp_handle e, const uint8_t* data_pinned, const int64_t
     prof_reset(e);
     if ((st = enqueue_ingest(e, data_pinned, byte_offsets, batch, cfg, plan, e->copy_stream))) return st;
     return finish_async_upload(e, batch);     // as pp_upload_points_async does
+}
+
+int pp_ingest_rig_depth(pp_handle e, const uint8_t* data, const int64_t* byte_offsets, const pp_depth_layout* layouts,
+                        const pp_ingest_config* cfgs, const int32_t* source_frame, int32_t sources, int32_t batch,
+                        float* points_out, int64_t points_out_capacity) {
+    if (!e) return PP_ERR_ARG;
+    (void)hipSetDevice(e->device);
+    DepthPlan plan;
+    int st = check_rig(e, "pp_ingest_rig_depth", data, byte_offsets, layouts, cfgs, source_frame, sources, batch, &plan);
+    if (st) return st;
+    return ingest_sync(e, "pp_ingest_rig_depth", data, byte_offsets, batch, nullptr, plan, points_out, points_out_capacity);
+}
+
+int pp_ingest_rig_depth_async(pp_handle e, const uint8_t* data_pinned, const int64_t* byte_offsets,
+                              const pp_depth_layout* layouts, const pp_ingest_config* cfgs, const int32_t* source_frame,
+                              int32_t sources, int32_t batch) {
+    if (!e) return PP_ERR_ARG;
+    (void)hipSetDevice(e->device);
+    DepthPlan plan;
+    int st = check_rig(e, "pp_ingest_rig_depth_async", data_pinned, byte_offsets, layouts, cfgs, source_frame, sources, batch, &plan);
+    if (st) return st;
+    prof_reset(e);
+    if ((st = enqueue_ingest(e, data_pinned, byte_offsets, batch, nullptr, plan, e->copy_stream))) return st;
+    return finish_async_upload(e, batch);     // as pp_upload_points_async does
+}
+
+int pp_ingest_rig_pointcloud2(pp_handle e, const uint8_t* data, const int64_t* byte_offsets, const pp_pc2_layout* layouts,
+                              const pp_ingest_config* cfgs, const int32_t* source_frame, int32_t sources, int32_t batch,
+                              float* points_out, int64_t points_out_capacity) {
+    if (!e) return PP_ERR_ARG;
+    (void)hipSetDevice(e->device);
+    IngestPlan plan;
+    int st = check_rig(e, "pp_ingest_rig_pointcloud2", data, byte_offsets, layouts, cfgs, source_frame, sources, batch, &plan);
+    if (st) return st;
+    return ingest_sync(e, "pp_ingest_rig_pointcloud2", data, byte_offsets, batch, nullptr, plan, points_out, points_out_capacity);
+}
+
+int pp_ingest_rig_pointcloud2_async(pp_handle e, const uint8_t* data_pinned, const int64_t* byte_offsets,
+                                    const pp_pc2_layout* layouts, const pp_ingest_config* cfgs, const int32_t* source_frame,
+                                    int32_t sources, int32_t batch) {
+    if (!e) return PP_ERR_ARG;
+    (void)hipSetDevice(e->device);
+    IngestPlan plan;
+    int st = check_rig(e, "pp_ingest_rig_pointcloud2_async", data_pinned, byte_offsets, layouts, cfgs, source_frame, sources, batch,
+                       &plan);
+    if (st) return st;
+    prof_reset(e);
+    if ((st = enqueue_ingest(e, data_pinned, byte_offsets, batch, nullptr, plan, e->copy_stream))) return st;
+    return finish_async_upload(e, batch);     // as pp_upload_points_async does
+}
+
+int pp_ingest_rig_info(pp_handle e, int32_t* finite_counts, int32_t* kept_counts, int32_t sources) {
+    if (!e) return PP_ERR_ARG;
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_ingest_rig_info: a training step is in flight");
+    if (e->ing.batch < 1 || e->ing.rig.sources < 1) return fail(e, PP_ERR_STATE, "pp_ingest_rig_info: the last ingest was no rig call");
+    if (sources != e->ing.rig.sources)
+        return fail(e, PP_ERR_ARG, "pp_ingest_rig_info: the last rig ingest had %d sources, sources is %d", e->ing.rig.sources, sources);
+    (void)hipSetDevice(e->device);
+    HIPCHK(e, hipEventSynchronize(e->ev_up));        // an asynchronous ingest runs on the copy stream
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const size_t n = (size_t)sources * sizeof(int32_t);
+    if (finite_counts) HIPCHK(e, hipMemcpy(finite_counts, e->ing.rig.finite, n, hipMemcpyDeviceToHost));
+    if (kept_counts) HIPCHK(e, hipMemcpy(kept_counts, e->ing.rig.kept, n, hipMemcpyDeviceToHost));
+    return PP_OK;
 }
 
 int pp_ingest_info(pp_handle e, int32_t* finite_counts, int32_t* kept_counts, int32_t batch) {

@@ -26,48 +26,12 @@
 
 namespace {
 
-constexpr int DEP_ITER = 8;                       // 64-pixel steps of a wave
-constexpr int DEP_CHUNK = PP_WAVE * DEP_ITER;     // pixels per chunk (one wave)
-constexpr int DEP_WAVES = 4;                      // chunks per workgroup
+// the chunking is ingest.hip's (ingest_dev.h): rig_ingest.hip runs both feeds' records through one set of kernels
+constexpr int DEP_ITER = ING_ITER;                // 64-pixel steps of a wave
+constexpr int DEP_CHUNK = ING_CHUNK;              // pixels per chunk (one wave)
+constexpr int DEP_WAVES = ING_WAVES;              // chunks per workgroup
 
-// depth and validity of pixel i (i < n_pix) of a frame
-__device__ __forceinline__ bool dep_read(const uint8_t* base, const DepthFrame& f, int i, float& z) {
-    const int isz = f.f32 ? 4 : 2;
-    const uint8_t* px;
-    if (f.tight) {
-        px = base + (long long)i * isz;
-    } else {                                       // (only padded rows pay this division)
-        const int v = i / f.width, u = i - v * f.width;
-        px = base + (long long)v * f.row_step + (long long)u * isz;
-    }
-    bool ok;
-    if (f.f32) {
-        uint32_t w = ing_load32(px);
-        if (f.big_endian) w = __builtin_bswap32(w);
-        z = __uint_as_float(w);
-        ok = ((w >> 23) & 0xffu) != 0xffu && z > 0.0f;
-    } else {
-        uint16_t d;
-        __builtin_memcpy(&d, px, 2);
-        if (f.big_endian) d = __builtin_bswap16(d);
-        z = f.depth_scale * (float)d;
-        ok = d != 0;
-    }
-    return ok && z > f.z_min && z <= f.z_max;
-}
-
-// the camera-frame point of pixel i with depth z, widened to float64
-__device__ __forceinline__ void dep_deproject(const DepthFrame& f, int i, float z, double p[3]) {
-#pragma clang fp contract(off)
-    const int v = i / f.width, u = i - v * f.width;
-    const float tx = ((float)u - f.ppx) / f.fx;
-    const float ty = ((float)v - f.ppy) / f.fy;
-    const float x = z * tx;
-    const float y = z * ty;
-    p[0] = (double)x;
-    p[1] = (double)y;
-    p[2] = (double)z;
-}
+// (dep_read / dep_deproject, the per-pixel decode and validity: ingest_dev.h, shared with rig_ingest.hip)
 
 __global__ __launch_bounds__(PP_WAVE * DEP_WAVES) void k_depth_count(const uint8_t* __restrict__ raw,
                                                                     const DepthFrame* __restrict__ frames, int stride,

@@ -19,42 +19,7 @@
 
 namespace {
 
-constexpr int ING_ITER = 8;                       // 64-record steps of a wave
-constexpr int ING_CHUNK = PP_WAVE * ING_ITER;     // records per chunk (one wave)
-constexpr int ING_WAVES = 4;                      // chunks per workgroup
-
-// one coordinate as float64 (a float32 field widens exactly)
-__device__ __forceinline__ double ing_coord(const uint8_t* p, const IngFrame& f) {
-    if (f.f64) {
-        const uint32_t a = ing_load32(p), b = ing_load32(p + 4);
-        unsigned long long v = ((unsigned long long)b << 32) | a;
-        if (f.big_endian) v = __builtin_bswap64(v);
-        return __longlong_as_double((long long)v);
-    }
-    uint32_t v = ing_load32(p);
-    if (f.big_endian) v = __builtin_bswap32(v);
-    return (double)__uint_as_float(v);
-}
-
-__device__ __forceinline__ bool ing_finite(double v) {
-    return (((unsigned long long)__double_as_longlong(v) >> 52) & 0x7ffull) != 0x7ffull;
-}
-
-__device__ __forceinline__ const uint8_t* ing_record(const uint8_t* base, const IngFrame& f, int i) {
-    // (the host hands a frame whose rows are tight over as ONE row: no division then)
-    if (f.width >= f.n_rec) return base + (long long)i * f.point_step;
-    const int row = i / f.width, col = i - row * f.width;
-    return base + (long long)row * f.row_step + (long long)col * f.point_step;
-}
-
-__device__ __forceinline__ bool ing_read(const uint8_t* base, const IngFrame& f, int i, double p[3]) {
-    const uint8_t* rec = ing_record(base, f, i);
-    p[0] = ing_coord(rec + f.x_off, f);
-    p[1] = ing_coord(rec + f.y_off, f);
-    p[2] = ing_coord(rec + f.z_off, f);
-    return ing_finite(p[0]) && ing_finite(p[1]) && ing_finite(p[2]);
-}
-
+// (the chunking and the per-record decode / validity functions: ingest_dev.h, shared with rig_ingest.hip)
 __global__ __launch_bounds__(PP_WAVE * ING_WAVES) void k_ingest_count(const uint8_t* __restrict__ raw,
                                                                      const IngFrame* __restrict__ frames, int stride,
                                                                      int* __restrict__ chunk_cnt) {

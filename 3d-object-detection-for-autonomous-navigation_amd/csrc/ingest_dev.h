@@ -1,6 +1,7 @@
 // What the two live-camera ingests share on the device (ingest.hip: PointCloud2 messages; depth_ingest.hip: raw depth
-// images): the unaligned dword load, the scan of the chunk counts and the float64 camera -> lidar transform.  Both
-// translation units wrap ingest_scan_frames in a kernel of their own, so each keeps its kernel name and its frame type.
+// images; rig_ingest.hip: several sources of either kind per frame): the chunking, the unaligned dword load, the per-record
+// decode and validity of both feeds, the scan of the chunk counts and the float64 camera -> lidar transform.  ingest.hip
+// and depth_ingest.hip wrap ingest_scan_frames in a kernel of their own, so each keeps its kernel name and its frame type.
 #pragma once
 
 #include "pp_common.h"
@@ -10,6 +11,83 @@ __device__ __forceinline__ uint32_t ing_load32(const uint8_t* p) {
     uint32_t v;
     __builtin_memcpy(&v, p, 4);
     return v;
+}
+
+constexpr int ING_ITER = 8;                       // 64-record steps of a wave
+constexpr int ING_CHUNK = PP_WAVE * ING_ITER;     // records per chunk (one wave)
+constexpr int ING_WAVES = 4;                      // chunks per workgroup
+
+// ---- PointCloud2 records (IngFrame): decode and validity, as k_ingest_count / k_ingest_scatter and the rig kernels use them
+// one coordinate as float64 (a float32 field widens exactly)
+__device__ __forceinline__ double ing_coord(const uint8_t* p, const IngFrame& f) {
+    if (f.f64) {
+        const uint32_t a = ing_load32(p), b = ing_load32(p + 4);
+        unsigned long long v = ((unsigned long long)b << 32) | a;
+        if (f.big_endian) v = __builtin_bswap64(v);
+        return __longlong_as_double((long long)v);
+    }
+    uint32_t v = ing_load32(p);
+    if (f.big_endian) v = __builtin_bswap32(v);
+    return (double)__uint_as_float(v);
+}
+
+__device__ __forceinline__ bool ing_finite(double v) {
+    return (((unsigned long long)__double_as_longlong(v) >> 52) & 0x7ffull) != 0x7ffull;
+}
+
+__device__ __forceinline__ const uint8_t* ing_record(const uint8_t* base, const IngFrame& f, int i) {
+    // (the host hands a frame whose rows are tight over as ONE row: no division then)
+    if (f.width >= f.n_rec) return base + (long long)i * f.point_step;
+    const int row = i / f.width, col = i - row * f.width;
+    return base + (long long)row * f.row_step + (long long)col * f.point_step;
+}
+
+__device__ __forceinline__ bool ing_read(const uint8_t* base, const IngFrame& f, int i, double p[3]) {
+    const uint8_t* rec = ing_record(base, f, i);
+    p[0] = ing_coord(rec + f.x_off, f);
+    p[1] = ing_coord(rec + f.y_off, f);
+    p[2] = ing_coord(rec + f.z_off, f);
+    return ing_finite(p[0]) && ing_finite(p[1]) && ing_finite(p[2]);
+}
+
+// ---- depth pixels (DepthFrame): decode, validity and deprojection, as k_depth_count / k_depth_scatter and the rig kernels use them
+// depth and validity of pixel i (i < n_pix) of a frame
+__device__ __forceinline__ bool dep_read(const uint8_t* base, const DepthFrame& f, int i, float& z) {
+    const int isz = f.f32 ? 4 : 2;
+    const uint8_t* px;
+    if (f.tight) {
+        px = base + (long long)i * isz;
+    } else {                                       // (only padded rows pay this division)
+        const int v = i / f.width, u = i - v * f.width;
+        px = base + (long long)v * f.row_step + (long long)u * isz;
+    }
+    bool ok;
+    if (f.f32) {
+        uint32_t w = ing_load32(px);
+        if (f.big_endian) w = __builtin_bswap32(w);
+        z = __uint_as_float(w);
+        ok = ((w >> 23) & 0xffu) != 0xffu && z > 0.0f;
+    } else {
+        uint16_t d;
+        __builtin_memcpy(&d, px, 2);
+        if (f.big_endian) d = __builtin_bswap16(d);
+        z = f.depth_scale * (float)d;
+        ok = d != 0;
+    }
+    return ok && z > f.z_min && z <= f.z_max;
+}
+
+// the camera-frame point of pixel i with depth z, widened to float64
+__device__ __forceinline__ void dep_deproject(const DepthFrame& f, int i, float z, double p[3]) {
+#pragma clang fp contract(off)
+    const int v = i / f.width, u = i - v * f.width;
+    const float tx = ((float)u - f.ppx) / f.fx;
+    const float ty = ((float)v - f.ppy) / f.fy;
+    const float x = z * tx;
+    const float y = z * ty;
+    p[0] = (double)x;
+    p[1] = (double)y;
+    p[2] = (double)z;
 }
 
 // The body of a one-workgroup scan kernel of 16 waves (1024 threads): wave w scans the chunk counts of frames w, w + 16,

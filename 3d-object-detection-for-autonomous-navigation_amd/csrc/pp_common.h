@@ -556,6 +556,33 @@ int ingest_chunks(int n_rec);
 void launch_ingest(const IngestParams& p, hipStream_t s);
 int depth_chunks(int n_pix);
 void launch_depth_ingest(const DepthIngestParams& p, hipStream_t s);
+// rig_ingest.hip: several sources (cameras) per frame, each under its own selection and transform; a frame's points are
+// its sources' kept points in source order, back to back.  The per-source records are IngFrame or DepthFrame as above.
+struct RigSource {             // what a source has of its own besides its IngFrame / DepthFrame
+    int frame;                 // the frame it belongs to (non-decreasing over the sources, every frame present)
+    int first, decimate;
+    int reserved;
+    double r[9], r2[9], lift[3];
+};
+template <typename Frame>
+struct RigParamsT {
+    const uint8_t* raw;        // the sources' bytes, staged on the device
+    const Frame* frames;       // [sources] one record per SOURCE
+    const RigSource* src;      // [sources]
+    int sources, batch, stride;   // stride: chunks of the largest source (row length of the two chunk tables)
+    int* chunk_cnt;            // [sources][stride] finite records (valid pixels) per chunk
+    int* chunk_base;           // [sources][stride] finite records (valid pixels) of the source in front of the chunk
+    int* src_finite;           // [sources] out: finite records (valid pixels)
+    int* src_kept;             // [sources] out: points written
+    int* out_base;             // [sources] out: kept points of the earlier sources of its frame
+    int* finite;               // [batch] out: the frames' sums of src_finite
+    int* kept;                 // [batch] out: the frames' sums of src_kept
+    int* offsets;              // [batch + 1] out: the frames' row offsets in `out`
+    float* out;                // [sum kept][3]
+    long long out_rows;        // rows `out` holds
+};
+void launch_rig_ingest(const RigParamsT<IngFrame>& p, hipStream_t s);
+void launch_rig_ingest(const RigParamsT<DepthFrame>& p, hipStream_t s);
 
 // frustum_crop.hip: the resident frames cropped to the camera frustum (frustum.py), frames compacted in order
 struct CropParams {

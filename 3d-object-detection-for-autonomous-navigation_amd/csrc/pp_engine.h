@@ -1,6 +1,6 @@
 // Host side of the C-ABI (include/pp_hip.h), shared by its translation units: the handle, the error / allocation
 // helpers and what one unit calls in another.  pp_api.hip: lifetime, weights, feeds, the inference pipeline;
-// api_ingest.hip: PointCloud2 and depth-image ingest; api_crop.hip: the frustum crop; api_train.hip: loss, training step, optimizer; api_dataprep.hip: targets,
+// api_ingest.hip: PointCloud2, depth-image and camera-rig ingest; api_crop.hip: the frustum crop; api_train.hip: loss, training step, optimizer; api_dataprep.hip: targets,
 // augmentation, GT sampling, object database; api_eval.hip: the AP evaluator (needs no handle); api_nms.hip: the detector's NMS rule and the standalone rotated NMS;
 // api_project.hip: the detector's image boxes and the standalone projection; api_class_nms.hip: joint / per-class suppression;
 // api_metrics.hip: the training metrics' counts; api_publish.hip: a trainer's weights into the detector, on the device.
@@ -235,7 +235,7 @@ struct pp_engine {
         long long* off = nullptr;          // [B * PP_MAX_GT_PER_FRAME + 1]
         float* out = nullptr;  size_t cap_out = 0;   // the cut-out points grow to the largest build seen (dgrow)
     } gdb;
-    struct Ing {                           // live-camera ingest (pp_ingest_pointcloud2*, pp_ingest_depth*); raw / chunks grow (dgrow)
+    struct Ing {                           // live-camera ingest (pp_ingest_pointcloud2*, pp_ingest_depth*, pp_ingest_rig_*); raw / chunks grow (dgrow)
         union Slot { IngFrame pc2; DepthFrame depth; };    // room for a frame of either feed (a call packs its own type tightly)
         uint8_t* raw = nullptr;  size_t cap_raw = 0;       // the messages' (images') bytes
         int* chunks = nullptr;   size_t cap_chunks = 0;    // [2][batch * stride]: chunk counts, chunk bases
@@ -243,6 +243,17 @@ struct pp_engine {
         Slot* h_ring = nullptr;            // pinned [OFF_RING][B]: travels with the offsets' ring slots
         int *finite = nullptr, *kept = nullptr;            // [B] finite records (valid pixels), points kept
         int batch = 0;                     // frames of the last ingest (pp_ingest_info)
+        // a rig call (pp_ingest_rig_*) has one record per SOURCE: tables of their own, sized by sources_cap =
+        // PP_RIG_MAX_SOURCES * B on first use (api_ingest.hip: ensure_rig); finite / kept above then hold the frames' sums
+        struct Rig {
+            Slot* frames = nullptr;        // [sources_cap]
+            RigSource* src = nullptr;      // [sources_cap]
+            Slot* h_frames = nullptr;      // pinned [OFF_RING][sources_cap]: travel with the offsets' ring slots
+            RigSource* h_src = nullptr;    // pinned [OFF_RING][sources_cap]
+            int *finite = nullptr, *kept = nullptr, *out_base = nullptr;   // [sources_cap]
+            int sources_cap = 0;
+            int sources = 0;               // sources of the last ingest when it was a rig call, else 0 (pp_ingest_rig_info)
+        } rig;
     } ing;
     struct Crop {                          // frustum crop of the resident frames (pp_frustum_crop*; api_crop.hip: ensure_crop)
         double* planes = nullptr;          // [B][6][4]

@@ -219,6 +219,55 @@ def _ingest_config(first, decimate, lift):
     return c
 
 
+def _rig_configs(rig, batch):
+    """The ctypes array of pp_ingest_config of a rig call: one per source, the rig's cameras repeated for every frame."""
+    n = len(rig)
+    cfgs = (_lib.PPIngestConfig * (n * batch))()
+    for s in range(n * batch):
+        c, m = cfgs[s], rig.mounts[s % n]
+        c.first, c.decimate = int(rig.first[s % n]), int(rig.decimate[s % n])
+        c.r[:] = [float(v) for v in m.r.reshape(-1)]
+        c.r2[:] = [float(v) for v in m.r2.reshape(-1)]
+        c.lift[:] = [float(v) for v in m.lift]
+    return cfgs
+
+
+def _rig_depth_layouts(tuples, rig):
+    """The ctypes array of pp_depth_layout of a rig call's images (frames back to back, a frame's cameras in rig order)."""
+    from . import ingest
+    n = len(rig)
+    if any(k is None for k in rig.intrinsics):
+        raise ValueError("a rig of depth cameras needs intrinsics (CameraRig(mounts, intrinsics=...))")
+    layouts = (_lib.PPDepthLayout * max(len(tuples), 1))()
+    for s, t in enumerate(tuples):
+        c = s % n
+        lay = ingest.depth_layout_of(t, rig.intrinsics[c], rig.depth_scale[c], rig.z_min[c], rig.z_max[c])
+        for k in ingest.DEPTH_LAYOUT_KEYS:
+            setattr(layouts[s], k, lay[k])
+    return layouts
+
+
+class RigDepthStaging(DepthStaging):
+    """DepthStaging for `Engine.ingest_rig_depth_async`: the images of B frames, one per camera of a rig, frames back to
+    back.  `.source_frame`: the frame of every image."""
+
+    def __init__(self, lib, frames, rig):
+        from . import ingest
+        flat, self.source_frame = ingest.rig_frame_map(frames, rig, "staging_rig_depth")
+        self.batch = len(frames)
+        super().__init__(lib, flat)
+
+
+class RigMessageStaging(MessageStaging):
+    """MessageStaging for `Engine.ingest_rig_pointcloud2_async`, as RigDepthStaging."""
+
+    def __init__(self, lib, frames, rig):
+        from . import ingest
+        flat, self.source_frame = ingest.rig_frame_map(frames, rig, "staging_rig_pointcloud2")
+        self.batch = len(frames)
+        super().__init__(lib, flat)
+
+
 class Engine:
     """config: reference-schema dict (or a config.Derived).  max_batch /
     max_points_per_frame size the device workspaces."""
@@ -800,6 +849,103 @@ class Engine:
         self.ingest_depth(images, intrinsics)
         if rect is not None:
             self.set_calib(rect, trv2c, len(images))
+        return self._detect_resident(on_numeric)
+
+    # ---- camera-rig ingest (pp_ingest_rig_*; ingest.py states the rule) ----
+    def _ingest_rig(self, name, data, offs, layouts, rig, fmap, batch, bounds, return_points):
+        pts, cap = None, 0
+        if return_points:
+            cap = int(sum(bounds))
+            pts = np.empty((max(cap, 1), 3), np.float32)
+        cfgs = _rig_configs(rig, batch)
+        self._check(getattr(self._lib, name)(self._h, _ptr(data), _ptr(offs), layouts, cfgs, _ptr(fmap), len(fmap), batch,
+                                             _ptr(pts), ctypes.c_int64(cap)), name)
+        self._offsets = None          # the resident frames' sizes are device values (ingest_info reads them back)
+        self._ing_batch, self._rig_shape = batch, (batch, len(rig))
+        if not return_points:
+            return None
+        off = np.concatenate([[0], np.cumsum(self.ingest_info()["kept"])])
+        return [pts[off[b]:off[b + 1]].copy() for b in range(batch)]
+
+    def ingest_rig_depth(self, frames, rig, return_points=False):
+        """The depth images of a camera rig -> the engine's resident frames, on the GPU: frame b holds the kept points of
+        its cameras in rig order, back to back, each camera under its own mount, intrinsics and selection --
+        `ingest.rig_depth_ingest_np(frames[b], rig)` exactly.  frames: list of B lists of images, one per camera of the
+        rig (`ingest.CameraRig`).  The engine needs max_points_per_frame >= ingest.rig_kept_bound(sizes, rig).  No host
+        fallback; return_points as ingest_depth; ingest_info() then reads the frames' sums, ingest_rig_info() the
+        cameras' own counts."""
+        from . import ingest
+        flat, fmap = ingest.rig_frame_map(frames, rig, "ingest_rig_depth")
+        tuples = [ingest.image_as_tuple(m) for m in flat]
+        layouts = _rig_depth_layouts(tuples, rig)
+        offs, bufs = _pack_images(tuples)
+        data = (bufs[0] if len(bufs) == 1 else np.concatenate(bufs)) if offs[-1] else np.zeros((1,), np.uint8)
+        bounds = [ingest.kept_bound(t[1], t[2], rig.first[s % len(rig)], rig.decimate[s % len(rig)]) for s, t in enumerate(tuples)]
+        return self._ingest_rig("pp_ingest_rig_depth", data, offs, layouts, rig, fmap, len(frames), bounds, return_points)
+
+    def ingest_rig_pointcloud2(self, frames, rig, return_points=False):
+        """ingest_rig_depth for PointCloud2 messages: `ingest.rig_ingest_np(frames[b], rig)` exactly (the rig's intrinsics,
+        depth_scale and clip are not read)."""
+        from . import ingest
+        flat, fmap = ingest.rig_frame_map(frames, rig, "ingest_rig_pointcloud2")
+        tuples = [ingest.as_tuple(m) for m in flat]
+        offs, layouts, bufs = _pack_messages(tuples)
+        data = (bufs[0] if len(bufs) == 1 else np.concatenate(bufs)) if offs[-1] else np.zeros((1,), np.uint8)
+        bounds = [ingest.kept_bound(t[1], t[2], rig.first[s % len(rig)], rig.decimate[s % len(rig)]) for s, t in enumerate(tuples)]
+        return self._ingest_rig("pp_ingest_rig_pointcloud2", data, offs, layouts, rig, fmap, len(frames), bounds, return_points)
+
+    def ingest_rig_info(self):
+        """Per camera of the last rig ingest: `finite` records (valid pixels) and points `kept`, int32 [B, cameras]
+        (pp_ingest_rig_info; waits for the ingest)."""
+        B, C = getattr(self, "_rig_shape", (0, 0))
+        fin, kept = np.zeros((max(B * C, 1),), np.int32), np.zeros((max(B * C, 1),), np.int32)
+        self._check(self._lib.pp_ingest_rig_info(self._h, _ptr(fin), _ptr(kept), B * C), "pp_ingest_rig_info")
+        return {"finite": fin[:B * C].reshape(B, C), "kept": kept[:B * C].reshape(B, C)}
+
+    def staging_rig_depth(self, frames, rig):
+        """Packs the depth images of B rig frames into a page-locked RigDepthStaging for ingest_rig_depth_async."""
+        return RigDepthStaging(self._lib, frames, rig)
+
+    def staging_rig_pointcloud2(self, frames, rig):
+        """Packs the messages of B rig frames into a page-locked RigMessageStaging for ingest_rig_pointcloud2_async."""
+        return RigMessageStaging(self._lib, frames, rig)
+
+    def _ingest_rig_async(self, name, staging, layouts, rig):
+        S, B = len(staging.source_frame), staging.batch
+        if S != B * len(rig):
+            raise ValueError(f"{name}: the staging holds {S} sources in {B} frames, the rig has {len(rig)} cameras")
+        cfgs = _rig_configs(rig, B)
+        self._check(getattr(self._lib, name)(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets), layouts, cfgs,
+                                             _ptr(staging.source_frame), S, B), name)
+        self._offsets = None
+        self._ing_batch, self._rig_shape = B, (B, len(rig))
+        staging._users.add(self)
+        self._staged.append(staging)      # kept alive while a copy may still read it (see upload_async)
+
+    def ingest_rig_depth_async(self, staging, rig):
+        """ingest_rig_depth without waiting (pp_ingest_rig_depth_async), from a RigDepthStaging: as ingest_depth_async, and
+        mixes freely with it, with ingest_pointcloud2_async and with upload_async."""
+        tuples = [(staging.bytes[staging.byte_offsets[s]:staging.byte_offsets[s + 1]],) + tuple(g)
+                  for s, g in enumerate(staging.images)]
+        self._ingest_rig_async("pp_ingest_rig_depth_async", staging, _rig_depth_layouts(tuples, rig), rig)
+
+    def ingest_rig_pointcloud2_async(self, staging, rig):
+        """ingest_rig_pointcloud2 without waiting (pp_ingest_rig_pointcloud2_async), from a RigMessageStaging."""
+        self._ingest_rig_async("pp_ingest_rig_pointcloud2_async", staging, staging.layouts, rig)
+
+    def detect_rig_depth(self, frames, rig, rect=None, trv2c=None, on_numeric="f32"):
+        """ingest_rig_depth + detect_async + sync + detections: `detect_depth` for a rig's images.  rect / trv2c /
+        on_numeric as `detect`."""
+        self.ingest_rig_depth(frames, rig)
+        if rect is not None:
+            self.set_calib(rect, trv2c, len(frames))
+        return self._detect_resident(on_numeric)
+
+    def detect_rig_pointcloud2(self, frames, rig, rect=None, trv2c=None, on_numeric="f32"):
+        """ingest_rig_pointcloud2 + detect_async + sync + detections."""
+        self.ingest_rig_pointcloud2(frames, rig)
+        if rect is not None:
+            self.set_calib(rect, trv2c, len(frames))
         return self._detect_resident(on_numeric)
 
     def intermediates(self, canvas=False):

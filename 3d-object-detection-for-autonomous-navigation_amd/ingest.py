@@ -176,7 +176,7 @@ def cells_agree(points64, voxel_size, pc_range):
 
 
 def transform_ordered64(points_xyz, lift=SENSOR_HEIGHT, matrices=None):
-    """((p . r) . r2) + [0, 0, lift] in float64 with every 3-term dot product summed left to right, products and sums
+    """((p . r) . r2) + [0, 0, lift] (or + lift, when it is a vector of 3) in float64 with every 3-term dot product summed left to right, products and sums
     rounded separately (no fused multiply-add): the GPU ingest's arithmetic, restated.  Bit-identical to
     `realsense_to_lidar64(points, decimate=1, first=0)` wherever numpy's dot sums a row of three in that order (the
     kernel's contract is this function)."""
@@ -185,16 +185,27 @@ def transform_ordered64(points_xyz, lift=SENSOR_HEIGHT, matrices=None):
     out = p
     for m in (np.asarray(r, np.float64), np.asarray(r2, np.float64)):
         out = np.stack([(out[:, 0] * m[0, j] + out[:, 1] * m[1, j]) + out[:, 2] * m[2, j] for j in range(3)], axis=-1)
-    return out + np.array([0.0, 0.0, lift])
+    return out + _lift_vector(lift)
 
 
-def ingest_np(msg, first=1, decimate=4, lift=SENSOR_HEIGHT):
+def _lift_vector(lift):
+    """pp_ingest_config.lift: [0, 0, lift] for a sensor height, or the three numbers themselves."""
+    if np.ndim(lift) == 0:
+        return np.array([0.0, 0.0, float(lift)])
+    v = np.asarray(lift, np.float64).reshape(-1)
+    if v.size != 3:
+        raise ValueError(f"lift has {v.size} entries, a height or a vector of 3 expected")
+    return v
+
+
+def ingest_np(msg, first=1, decimate=4, lift=SENSOR_HEIGHT, matrices=None):
     """What the GPU ingest computes for one message, on the host by its own rule: records -> finite flags -> `select_np`
-    -> `transform_ordered64` -> float32.  Returns (points [kept, 3] float32, finite count)."""
+    -> `transform_ordered64` -> float32.  Returns (points [kept, 3] float32, finite count).  matrices: (r, r2) of another
+    mount than the reference's (`Mount`); lift may then be a vector of 3."""
     xyz = pointcloud2_to_xyz(*as_tuple(msg), remove_nans=False)
     fin = np.isfinite(xyz).all(axis=1)
     keep = select_np(fin, first, decimate)
-    return transform_ordered64(xyz[keep], lift).astype(np.float32), int(fin.sum())
+    return transform_ordered64(xyz[keep], lift, matrices).astype(np.float32), int(fin.sum())
 
 
 # ---- depth images (Engine.ingest_depth / detect_depth, csrc/depth_ingest.hip) ---------------------------------------
@@ -353,9 +364,166 @@ def depth_kept_bound(width, height, first=1, decimate=4):
     return kept_bound(width, height, first, decimate)
 
 
-def depth_ingest_np(image, intrinsics, first=1, decimate=4, lift=SENSOR_HEIGHT, depth_scale=0.001, z_min=0.0, z_max=np.inf):
+def depth_ingest_np(image, intrinsics, first=1, decimate=4, lift=SENSOR_HEIGHT, depth_scale=0.001, z_min=0.0, z_max=np.inf,
+                    matrices=None):
     """What the GPU depth ingest computes for one image, on the host by its own rule: `depth_to_xyz` -> `select_np` ->
-    `transform_ordered64` -> float32.  Returns (points [kept, 3] float32, valid pixels)."""
+    `transform_ordered64` -> float32.  Returns (points [kept, 3] float32, valid pixels).  matrices / lift as `ingest_np`."""
     xyz = depth_to_xyz(image, intrinsics, depth_scale, z_min, z_max)
     keep = select_np(np.ones(len(xyz), bool), first, decimate)
-    return transform_ordered64(xyz[keep], lift).astype(np.float32), len(xyz)
+    return transform_ordered64(xyz[keep], lift, matrices).astype(np.float32), len(xyz)
+
+
+# ---- camera rigs (Engine.ingest_rig_depth / ingest_rig_pointcloud2, csrc/rig_ingest.hip; DESIGN 7.1n) ------------------
+# A robot carries two to four depth cameras, each with its own mount.  A rig call puts the cameras of one instant into ONE
+# frame: the frame's points are the kept points of its cameras in camera order, back to back, each camera computed exactly
+# as the single-camera ingest computes it alone under its own (first, decimate, r, r2, lift) -- validity, rank, selection,
+# transform and rounding restart per camera.  The reference has no such path (one camera, one frame, load_data.py:2433);
+# what is pinned is its single-camera chain, per source.  Not done: time synchronisation, de-duplication where the cameras
+# overlap, lens distortion, cameras of both kinds (images and messages) in one call, more than RIG_MAX_SOURCES per frame.
+
+RIG_MAX_SOURCES = 16
+
+
+class Mount:
+    """Where a camera sits: the (r, r2, lift) of pp_ingest_config -- a point (row vector, camera axes) becomes
+    ((p . r) . r2) + lift.  r, r2: [3, 3] float64 (r2 defaults to the identity); lift: a height (-> [0, 0, lift]) or a
+    vector of 3."""
+
+    def __init__(self, r, r2=None, lift=0.0):
+        self.r = np.array(r, np.float64).reshape(3, 3)
+        self.r2 = np.eye(3) if r2 is None else np.array(r2, np.float64).reshape(3, 3)
+        self.lift = _lift_vector(lift)
+        if not (np.isfinite(self.r).all() and np.isfinite(self.r2).all() and np.isfinite(self.lift).all()):
+            raise ValueError("Mount: r, r2 and lift must be finite")
+
+    @property
+    def matrices(self):
+        return self.r, self.r2
+
+    @classmethod
+    def realsense(cls, lift=SENSOR_HEIGHT):
+        """The reference's mount (load_data.py:2437-2443): its two scipy matrices and [0, 0, lift]."""
+        r, r2 = _matrices()
+        return cls(r, r2, lift)
+
+    @classmethod
+    def from_matrix(cls, T):
+        """A general extrinsic [R | t], [4, 4] or [3, 4], taking a camera-frame COLUMN vector to the lidar frame
+        (p' = R p + t): r = R transposed, r2 = identity, lift = t -- the existing three steps, no new arithmetic."""
+        T = np.asarray(T, np.float64)
+        if T.shape not in ((4, 4), (3, 4)):
+            raise ValueError(f"Mount.from_matrix: a [4, 4] or [3, 4] matrix expected, got {T.shape}")
+        if T.shape == (4, 4) and not np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]):
+            raise ValueError(f"Mount.from_matrix: the last row is {T[3].tolist()}, not [0, 0, 0, 1]")
+        return cls(T[:3, :3].T.copy(), None, T[:3, 3].copy())
+
+
+class CameraRig:
+    """The cameras of one frame, in the order their points are laid down.  mounts: one `Mount` per camera.  intrinsics
+    (depth images only: anything `intrinsics_of` takes), first, decimate, depth_scale, z_min, z_max: one value for every
+    camera, or a list with one per camera."""
+
+    def __init__(self, mounts, intrinsics=None, first=1, decimate=4, depth_scale=0.001, z_min=0.0, z_max=np.inf):
+        self.mounts = list(mounts)
+        n = len(self.mounts)
+        if not 1 <= n <= RIG_MAX_SOURCES:
+            raise ValueError(f"a rig has 1 to {RIG_MAX_SOURCES} cameras, got {n}")
+        if not all(isinstance(m, Mount) for m in self.mounts):
+            raise ValueError("CameraRig: mounts must be Mount objects (Mount.realsense(), Mount.from_matrix(T))")
+        one_set = intrinsics is None or not isinstance(intrinsics, list) or (
+            len(intrinsics) in (4, 9) and all(np.ndim(v) == 0 for v in intrinsics))
+        if not one_set and len(intrinsics) != n:
+            raise ValueError(f"{len(intrinsics)} sets of intrinsics for {n} cameras")
+        self.intrinsics = [intrinsics] * n if one_set else list(intrinsics)
+
+        def per(name, v, cast):
+            if np.ndim(v) == 0:
+                return [cast(v)] * n
+            if len(v) != n:
+                raise ValueError(f"{len(v)} values of {name} for {n} cameras")
+            return [cast(x) for x in v]
+
+        self.first, self.decimate = per("first", first, int), per("decimate", decimate, int)
+        self.depth_scale, self.z_min, self.z_max = (per(k, v, float) for k, v in
+                                                    (("depth_scale", depth_scale), ("z_min", z_min), ("z_max", z_max)))
+        for c in range(n):
+            kept_bound(0, 0, self.first[c], self.decimate[c])         # (raises for first < 0, decimate < 1)
+
+    def __len__(self):
+        return len(self.mounts)
+
+    def depth_kwargs(self, c):
+        """The keyword arguments of `depth_ingest_np` for camera c (behind image and intrinsics)."""
+        m = self.mounts[c]
+        return dict(first=self.first[c], decimate=self.decimate[c], lift=m.lift, depth_scale=self.depth_scale[c],
+                    z_min=self.z_min[c], z_max=self.z_max[c], matrices=m.matrices)
+
+    def _cameras(self, sources, what):
+        if len(sources) != len(self):
+            raise ValueError(f"{what}: {len(sources)} sources for a rig of {len(self)} cameras")
+        return range(len(self))
+
+
+def _rig_concat(parts):
+    pts = [p for p, _ in parts]
+    return (np.concatenate(pts).astype(np.float32).reshape(-1, 3), np.array([n for _, n in parts], np.int64),
+            np.array([len(p) for p in pts], np.int64))
+
+
+def rig_depth_ingest_np(images, rig):
+    """What the GPU rig ingest computes for ONE frame of depth images (one per camera of the rig), on the host: the
+    concatenation, in camera order, of `depth_ingest_np` of each camera alone under its own mount and selection.  Returns
+    (points [sum kept, 3] float32, valid pixels per camera, kept points per camera)."""
+    if any(k is None for k in rig.intrinsics):
+        raise ValueError("rig_depth_ingest_np: the rig has no intrinsics")
+    return _rig_concat([depth_ingest_np(images[c], rig.intrinsics[c], **rig.depth_kwargs(c))
+                        for c in rig._cameras(images, "rig_depth_ingest_np")])
+
+
+def rig_ingest_np(msgs, rig):
+    """`rig_depth_ingest_np` for PointCloud2 messages: the concatenation of `ingest_np` per camera.  Returns (points,
+    finite records per camera, kept points per camera)."""
+    return _rig_concat([ingest_np(msgs[c], rig.first[c], rig.decimate[c], rig.mounts[c].lift, rig.mounts[c].matrices)
+                        for c in rig._cameras(msgs, "rig_ingest_np")])
+
+
+def rig_kept_bound(sizes, rig):
+    """Most points ONE frame of the rig can keep: the sum over its cameras of `kept_bound(width, height, first, decimate)`
+    -- what the engine's max_points_per_frame must reach.  sizes: one (width, height) per camera."""
+    return sum(kept_bound(sizes[c][0], sizes[c][1], rig.first[c], rig.decimate[c]) for c in rig._cameras(sizes, "rig_kept_bound"))
+
+
+def rig_frame_map(frames, rig, what="rig"):
+    """frames: list of B lists with one source per camera -> (the sources in call order, source_frame int32 [B * cameras]);
+    raises when a frame has another number of sources than the rig has cameras."""
+    flat, fmap = [], []
+    for b, fr in enumerate(frames):
+        if len(fr) != len(rig):
+            raise ValueError(f"{what}: frame {b} has {len(fr)} sources, the rig has {len(rig)} cameras")
+        flat.extend(fr)
+        fmap.extend([b] * len(fr))
+    if not flat:
+        raise ValueError(f"{what}: no frames")
+    return flat, np.array(fmap, np.int32)
+
+
+def check_frame_map(source_frame, batch):
+    """The rules pp_ingest_rig_* hold a frame map to, on the host: it starts at 0, never decreases, skips no frame, ends at
+    batch - 1, and no frame has more than RIG_MAX_SOURCES sources.  Raises a ValueError that names the source."""
+    m = [int(v) for v in source_frame]
+    if not m:
+        raise ValueError("the frame map is empty")
+    if m[0] != 0:
+        raise ValueError(f"source 0: source_frame {m[0]}, the frame map starts at frame 0")
+    run = 1
+    for s in range(1, len(m)):
+        if m[s] < m[s - 1]:
+            raise ValueError(f"source {s}: source_frame {m[s]} < {m[s - 1]} of the source before it (the frame map never decreases)")
+        if m[s] > m[s - 1] + 1:
+            raise ValueError(f"source {s}: source_frame {m[s]} skips frame {m[s - 1] + 1}")
+        run = run + 1 if m[s] == m[s - 1] else 1
+        if run > RIG_MAX_SOURCES:
+            raise ValueError(f"source {s}: frame {m[s]} has more than {RIG_MAX_SOURCES} sources")
+    if m[-1] != int(batch) - 1:
+        raise ValueError(f"source {len(m) - 1}: source_frame {m[-1]}, the frame map ends at frame batch - 1 = {int(batch) - 1}")
+    return np.array(m, np.int32)

@@ -10,7 +10,8 @@ Trv2c, P2, anchors, anchors_mask, image_idx, image_shape); elements may be
 numpy arrays or anything with `.numpy()` (the reference passes TF tensors).
 `detect(frames, ...)` is the fused raw-points path the reference does not have; `detect_pointcloud2(msgs, ...)` is the
 same from raw sensor_msgs/PointCloud2 messages (the reference's production mode, ingested on the GPU), and
-`detect_depth(images, intrinsics, ...)` from the depth images those messages are computed from.
+`detect_depth(images, intrinsics, ...)` from the depth images those messages are computed from;
+`detect_rig_depth(frames, rig, ...)` / `detect_rig_pointcloud2` put the cameras of a rig into one frame each.
 
 Training mode (model/voxelnet.py:922-1049 + train.py:265-304), `VoxelNet(config, writer, training=True)`:
     ret = net(voxels, num_points, coors, batch_anchors, labels, reg_targets)   # the reference's loss dict (scalars)
@@ -203,6 +204,26 @@ class VoxelNet:
         bb = self._bboxes(len(images))
         idx = image_idx if image_idx is not None else list(range(len(images)))
         return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(images))]
+
+    def _detect_rig(self, who, frames, rig, rect, trv2c, image_idx, p2):
+        self._need_p2(p2, who)
+        self._detector()
+        if self.d.project_bbox:
+            self.engine.set_projection(np.broadcast_to(np.asarray(p2, np.float64), (len(frames), 4, 4)))
+        dets, n = getattr(self.engine, who)(frames, rig, rect, trv2c)
+        bb = self._bboxes(len(frames))
+        idx = image_idx if image_idx is not None else list(range(len(frames)))
+        return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(frames))]
+
+    def detect_rig_depth(self, frames, rig, rect=None, trv2c=None, image_idx=None, p2=None):
+        """Fused path from the depth images of a camera rig (Engine.detect_rig_depth: every frame holds the points of all
+        its cameras, each under its own mount -- ingest.CameraRig) -> the same list of prediction dicts as `detect` on
+        the host-concatenated frames; p2 as there."""
+        return self._detect_rig("detect_rig_depth", frames, rig, rect, trv2c, image_idx, p2)
+
+    def detect_rig_pointcloud2(self, frames, rig, rect=None, trv2c=None, image_idx=None, p2=None):
+        """`detect_rig_depth` for the PointCloud2 messages of a camera rig (Engine.detect_rig_pointcloud2)."""
+        return self._detect_rig("detect_rig_pointcloud2", frames, rig, rect, trv2c, image_idx, p2)
 
     @staticmethod
     def _to_dict(dets, n, img_idx, bbox=None):

@@ -41,7 +41,9 @@ extern "C" {
  * pp_grad_clip_workspace_bytes, pp_grad_norm_device, pp_adamw_step_clipped_device; then pp_publish_stats,
  * pp_publish_train_weights, pp_publish_info; then PP_NMS_SOFT, pp_soft_nms_method, pp_set_soft_nms, pp_get_soft_nms,
  * PP_SNMS_MAX_BOXES, pp_soft_nms.  Then PP_DEPTH_U16, PP_DEPTH_F32, pp_depth_layout, pp_ingest_depth,
- * pp_ingest_depth_async (declared behind pp_ingest_info, whose counts serve both feeds). */
+ * pp_ingest_depth_async (declared behind pp_ingest_info, whose counts serve both feeds).  Then PP_RIG_MAX_SOURCES,
+ * pp_ingest_rig_depth, pp_ingest_rig_depth_async, pp_ingest_rig_pointcloud2, pp_ingest_rig_pointcloud2_async,
+ * pp_ingest_rig_info. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -866,6 +868,44 @@ int pp_ingest_depth(pp_handle h, const uint8_t* data, const int64_t* byte_offset
  * voxeliser behind them there; mixes freely with that call and with pp_upload_points_async. */
 int pp_ingest_depth_async(pp_handle h, const uint8_t* data_pinned, const int64_t* byte_offsets,
                           const pp_depth_layout* layouts, int32_t batch, const pp_ingest_config* cfg);
+
+/* ---- camera-rig ingest ---------------------------------------------------------------------------------- */
+/* Several sensors into one frame.  A call takes `sources` sources of ONE kind (depth images, or PointCloud2 messages) and
+ * `batch` frames.  Source s occupies data[byte_offsets[s] .. byte_offsets[s + 1]), has its own layout layouts[s] and its own
+ * cfgs[s] (first, decimate, r, r2, lift), and belongs to frame source_frame[s]; the map is non-decreasing, starts at 0, ends
+ * at batch - 1, and gives every frame 1 to PP_RIG_MAX_SOURCES sources.  The resident points of frame b are the kept points
+ * of its sources in source order, back to back, each source computed exactly as pp_ingest_depth / pp_ingest_pointcloud2
+ * compute it alone under cfgs[s]: validity, finiteness, rank, selection, transform and rounding restart per source
+ * (<package>/ingest.py: rig_depth_ingest_np, rig_ingest_np).  A general extrinsic [R | t] (p' = R p + t, p a column vector)
+ * is r = R transposed, r2 = identity, lift = t.  One source per frame with equal cfgs leaves the bytes of the plain calls.
+ * The reference has no such path (one camera, one frame); what is pinned is its single-camera chain, per source.
+ * points_out / points_out_capacity, the staging, the input-buffer flip and what is barred afterwards are
+ * pp_ingest_pointcloud2's; pp_ingest_info then reports the frames' sums, pp_ingest_rig_info the sources' own counts.
+ * Refused before anything is queued, pp_last_error naming the source and the field: whatever the single-camera call
+ * refuses about a frame, about the source; PP_ERR_ARG for a frame map that decreases, skips a frame, does not start at 0
+ * or end at batch - 1, or gives a frame more than PP_RIG_MAX_SOURCES sources, for batch > max_batch, and for a frame whose
+ * sources' summed bounds max(0, ceil((width * height - first) / decimate)) exceed max_points_per_frame; PP_ERR_STATE while a
+ * training step is in flight; PP_ERR_UNSUPPORTED for a handle whose num_point_features is not 3.  Not done: time
+ * synchronisation, de-duplication where cameras overlap, lens distortion, sources of both kinds in one call. */
+#define PP_RIG_MAX_SOURCES 16    /* sources per frame */
+int pp_ingest_rig_depth(pp_handle h, const uint8_t* data, const int64_t* byte_offsets, const pp_depth_layout* layouts,
+                        const pp_ingest_config* cfgs, const int32_t* source_frame, int32_t sources, int32_t batch,
+                        float* points_out, int64_t points_out_capacity);
+/* Same without waiting, as pp_ingest_depth_async: page-locked bytes on the copy stream, the kernels and the voxeliser
+ * behind them there; layouts / cfgs / source_frame are copied before the call returns. */
+int pp_ingest_rig_depth_async(pp_handle h, const uint8_t* data_pinned, const int64_t* byte_offsets,
+                              const pp_depth_layout* layouts, const pp_ingest_config* cfgs, const int32_t* source_frame,
+                              int32_t sources, int32_t batch);
+int pp_ingest_rig_pointcloud2(pp_handle h, const uint8_t* data, const int64_t* byte_offsets, const pp_pc2_layout* layouts,
+                              const pp_ingest_config* cfgs, const int32_t* source_frame, int32_t sources, int32_t batch,
+                              float* points_out, int64_t points_out_capacity);
+int pp_ingest_rig_pointcloud2_async(pp_handle h, const uint8_t* data_pinned, const int64_t* byte_offsets,
+                                    const pp_pc2_layout* layouts, const pp_ingest_config* cfgs, const int32_t* source_frame,
+                                    int32_t sources, int32_t batch);
+/* Parity tap of the last ingest when it was a rig call (waits for it): per source the finite records (valid pixels) and the
+ * points kept.  Either pointer may be NULL.  PP_ERR_STATE when the last ingest was no rig call, PP_ERR_ARG when `sources`
+ * is not that call's. */
+int pp_ingest_rig_info(pp_handle h, int32_t* finite_counts, int32_t* kept_counts, int32_t sources);
 
 /* ---- frustum crop (box_np_ops.remove_outside_points) ----------------------------------------------------- */
 /* Crops the RESIDENT frames to the camera image's frustum on the GPU: what _create_reduced_point_cloud,
