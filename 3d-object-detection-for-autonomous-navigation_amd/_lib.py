@@ -43,6 +43,8 @@ EXPORTS = [
     "pp_ingest_depth", "pp_ingest_depth_async",
     "pp_ingest_rig_depth", "pp_ingest_rig_depth_async", "pp_ingest_rig_pointcloud2", "pp_ingest_rig_pointcloud2_async",
     "pp_ingest_rig_info",
+    "pp_ingest_pointcloud2_fields", "pp_ingest_pointcloud2_fields_async",
+    "pp_ingest_rig_pointcloud2_fields", "pp_ingest_rig_pointcloud2_fields_async",
     "pp_gtdb_build", "pp_gtdb_count",
     "pp_eval_match", "pp_eval_pr",
     "pp_frustum_crop", "pp_frustum_crop_async", "pp_frustum_crop_info",
@@ -171,6 +173,15 @@ class PPIngestConfig(ctypes.Structure):
         ("r", ctypes.c_double * 9),
         ("r2", ctypes.c_double * 9),
         ("lift", ctypes.c_double * 3),
+    ]
+
+
+class PPPc2Feature(ctypes.Structure):
+    _fields_ = [
+        ("offset", ctypes.c_int32),
+        ("datatype", ctypes.c_int32),
+        ("scale", ctypes.c_double),
+        ("bias", ctypes.c_double),
     ]
 
 
@@ -402,6 +413,11 @@ def lib():
         getattr(L, name).argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, f32p, i64]
         getattr(L, name + "_async").argtypes = [vp, vp, vp, vp, vp, vp, i32, i32]
     L.pp_ingest_rig_info.argtypes = [vp, vp, vp, i32]
+    # (features: an array of PPPc2Feature, [frames or sources][nfeat])
+    L.pp_ingest_pointcloud2_fields.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(PPIngestConfig), vp, i32, f32p, i64]
+    L.pp_ingest_pointcloud2_fields_async.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(PPIngestConfig), vp, i32]
+    L.pp_ingest_rig_pointcloud2_fields.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, f32p, i64]
+    L.pp_ingest_rig_pointcloud2_fields_async.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32]
     L.pp_gtdb_build.argtypes = [vp, vp, vp, i32, vp, vp, f32p, i64]
     L.pp_gtdb_count.argtypes = [vp, vp, vp, i32, vp]
     L.pp_eval_match.argtypes = [ctypes.c_int, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]

@@ -2,7 +2,8 @@
 // depth_ingest.hip) -> the resident points and offsets.  The two feeds differ in their checks, their frame records and
 // their three launches; the staging, the input-buffer flip and the ordering are one path (enqueue_ingest).  A rig call
 // (pp_ingest_rig_*; kernels: rig_ingest.hip) takes the same path with one record per SOURCE and the sources' own
-// selections and transforms in a table beside them.
+// selections and transforms in a table beside them.  The pp_ingest_*pointcloud2_fields* calls add a table of feature
+// columns, one row per frame or source, which travels as the frame records do.
 #include "pp_engine.h"
 
 namespace {
@@ -14,15 +15,26 @@ struct IngestPlanT {
     int max_bound = 0, stride = 0;
     int64_t bytes = 0;             // byte_offsets[batch] - byte_offsets[0]
     std::vector<RigSource> rig;    // a rig call: one entry per source, `frames` then holds the SOURCES' records; else empty
+    std::vector<IngFeat> feats;    // a _fields call: [frames or sources][nfeat]; else empty
+    int nfeat = 0;
 };
 typedef IngestPlanT<IngFrame> IngestPlan;
 typedef IngestPlanT<DepthFrame> DepthPlan;
 
-// What both feeds refuse before they look at a frame.
-int check_ingest_call(pp_engine* e, const char* who, const int64_t* bo, const void* L, int batch, const pp_ingest_config* c) {
+// What both feeds refuse before they look at a frame.  nfeat: the feature columns of a _fields call, or -1 for a call
+// that delivers x y z only.
+int check_ingest_call(pp_engine* e, const char* who, const int64_t* bo, const void* L, int batch, const pp_ingest_config* c,
+                      const pp_pc2_feature* features, int nfeat) {
     if (e->train_pending) return fail(e, PP_ERR_STATE, "%s: a training step is in flight", who);
-    if (e->F != 3)
-        return fail(e, PP_ERR_UNSUPPORTED, "%s: num_point_features is %d, the live path delivers x y z only (3)", who, e->F);
+    if (nfeat < 0) {
+        if (e->F != 3)
+            return fail(e, PP_ERR_UNSUPPORTED, "%s: num_point_features is %d, the live path delivers x y z only (3)", who, e->F);
+    } else {
+        if (nfeat > 0 && !features) return fail(e, PP_ERR_ARG, "%s: features is NULL, nfeat is %d", who, nfeat);
+        if (nfeat != e->F - 3)
+            return fail(e, PP_ERR_ARG, "%s: nfeat %d, num_point_features is %d: x y z and %d feature column(s) expected", who,
+                        nfeat, e->F, e->F - 3);
+    }
     if (!bo || !L || !c) return fail(e, PP_ERR_ARG, "%s: null argument", who);
     int st = check_batch(e, batch); if (st) return st;
     return PP_OK;
@@ -80,6 +92,29 @@ int check_pc2_one(pp_engine* e, const char* who, const char* at, const int64_t* 
     return PP_OK;
 }
 
+// What is refused about the feature columns of one message (`at` as above); fills their records.
+int check_features_one(pp_engine* e, const char* who, const char* at, const pp_pc2_layout& l, const pp_pc2_feature* ft,
+                       int nfeat, IngFeat* out) {
+    static const int sizes[9] = {0, 1, 1, 2, 2, 4, 4, 4, 8};
+    for (int j = 0; j < nfeat; ++j) {
+        const pp_pc2_feature& t = ft[j];
+        if (t.datatype < 0 || t.datatype > 8)
+            return fail(e, PP_ERR_ARG, "%s: %s: feature %d: unknown datatype %d (0 constant, 1 INT8 ... 8 FLOAT64)", who, at, j,
+                        t.datatype);
+        const int size = sizes[t.datatype];
+        if (t.datatype != 0 && (t.offset < 0 || (int64_t)t.offset + size > l.point_step))
+            return fail(e, PP_ERR_ARG, "%s: %s: feature %d: offset %d (%d bytes) does not fit point_step %d", who, at, j, t.offset,
+                        size, l.point_step);
+        if (!std::isfinite(t.scale)) return fail(e, PP_ERR_ARG, "%s: %s: feature %d: scale %g is not finite", who, at, j, t.scale);
+        if (!std::isfinite(t.bias)) return fail(e, PP_ERR_ARG, "%s: %s: feature %d: bias %g is not finite", who, at, j, t.bias);
+        out[j].off = t.datatype ? t.offset : 0; out[j].type = t.datatype; out[j].scale = t.scale; out[j].bias = t.bias;
+    }
+    return PP_OK;
+}
+inline int check_features_one(pp_engine*, const char*, const char*, const pp_depth_layout&, const pp_pc2_feature*, int, IngFeat*) {
+    return PP_OK;                                  // (an image has no field: the depth calls pass nfeat -1)
+}
+
 // The same for one depth image.
 int check_depth_one(pp_engine* e, const char* who, const char* at, const int64_t* bo, int i, const pp_depth_layout& l,
                     const pp_ingest_config* c, DepthFrame* f, int64_t* bound) {
@@ -133,9 +168,11 @@ inline int check_one(pp_engine* e, const char* who, const char* at, const int64_
 // Everything pp_ingest_pointcloud2* / pp_ingest_depth* refuse, before anything is queued.
 template <typename Layout, typename Frame>
 int check_frames(pp_engine* e, const char* who, const uint8_t* data, const int64_t* bo, const Layout* L, int batch,
-                 const pp_ingest_config* c, IngestPlanT<Frame>* plan) {
-    int st = check_ingest_call(e, who, bo, L, batch, c); if (st) return st;
+                 const pp_ingest_config* c, IngestPlanT<Frame>* plan, const pp_pc2_feature* features = nullptr, int nfeat = -1) {
+    int st = check_ingest_call(e, who, bo, L, batch, c, features, nfeat); if (st) return st;
     if ((st = check_selection(e, who, "", c))) return st;
+    plan->nfeat = std::max(nfeat, 0);
+    plan->feats.assign((size_t)batch * plan->nfeat, IngFeat());
     plan->frames.assign((size_t)batch, Frame());
     plan->bound_off.assign((size_t)batch + 1, 0);
     for (int b = 0; b < batch; ++b) {
@@ -144,6 +181,8 @@ int check_frames(pp_engine* e, const char* who, const uint8_t* data, const int64
         int64_t bound = 0;
         Frame& f = plan->frames[(size_t)b];
         if ((st = check_one(e, who, at, bo, b, L[b], c, &f, &bound))) return st;
+        if (plan->nfeat && (st = check_features_one(e, who, at, L[b], features + (size_t)b * nfeat, nfeat,
+                                                    plan->feats.data() + (size_t)b * nfeat))) return st;
         if (bound > e->NMAX)
             return fail(e, PP_ERR_ARG, "%s: frame %d: width %d x height %d keeps up to %lld points > max_points_per_frame=%d", who, b,
                         L[b].width, L[b].height, (long long)bound, e->NMAX);
@@ -157,8 +196,8 @@ int check_frames(pp_engine* e, const char* who, const uint8_t* data, const int64
 }
 
 int check_ingest(pp_engine* e, const char* who, const uint8_t* data, const int64_t* bo, const pp_pc2_layout* L, int batch,
-                 const pp_ingest_config* c, IngestPlan* plan) {
-    return check_frames(e, who, data, bo, L, batch, c, plan);
+                 const pp_ingest_config* c, IngestPlan* plan, const pp_pc2_feature* features = nullptr, int nfeat = -1) {
+    return check_frames(e, who, data, bo, L, batch, c, plan, features, nfeat);
 }
 int check_depth(pp_engine* e, const char* who, const uint8_t* data, const int64_t* bo, const pp_depth_layout* L, int batch,
                 const pp_ingest_config* c, DepthPlan* plan) {
@@ -169,8 +208,9 @@ int check_depth(pp_engine* e, const char* who, const uint8_t* data, const int64_
 // calls refuse per frame, then the frames' summed bounds.
 template <typename Layout, typename Frame>
 int check_rig(pp_engine* e, const char* who, const uint8_t* data, const int64_t* bo, const Layout* L,
-              const pp_ingest_config* cfgs, const int32_t* source_frame, int sources, int batch, IngestPlanT<Frame>* plan) {
-    int st = check_ingest_call(e, who, bo, L, batch, cfgs); if (st) return st;
+              const pp_ingest_config* cfgs, const int32_t* source_frame, int sources, int batch, IngestPlanT<Frame>* plan,
+              const pp_pc2_feature* features = nullptr, int nfeat = -1) {
+    int st = check_ingest_call(e, who, bo, L, batch, cfgs, features, nfeat); if (st) return st;
     if (!source_frame) return fail(e, PP_ERR_ARG, "%s: null argument", who);
     if (sources < 1) return fail(e, PP_ERR_ARG, "%s: sources %d < 1", who, sources);
     if (source_frame[0] != 0)
@@ -191,6 +231,8 @@ int check_rig(pp_engine* e, const char* who, const uint8_t* data, const int64_t*
     if (source_frame[sources - 1] != batch - 1)
         return fail(e, PP_ERR_ARG, "%s: source %d: source_frame %d, the frame map ends at frame batch - 1 = %d", who, sources - 1,
                     source_frame[sources - 1], batch - 1);
+    plan->nfeat = std::max(nfeat, 0);
+    plan->feats.assign((size_t)sources * plan->nfeat, IngFeat());
     plan->frames.assign((size_t)sources, Frame());
     plan->rig.assign((size_t)sources, RigSource());
     plan->bound_off.assign((size_t)batch + 1, 0);
@@ -204,6 +246,8 @@ int check_rig(pp_engine* e, const char* who, const uint8_t* data, const int64_t*
         int64_t bound = 0;
         Frame& f = plan->frames[(size_t)s];
         if ((st = check_one(e, who, at, bo, s, L[s], c, &f, &bound))) return st;
+        if (plan->nfeat && (st = check_features_one(e, who, at, L[s], features + (size_t)s * nfeat, nfeat,
+                                                    plan->feats.data() + (size_t)s * nfeat))) return st;
         const int b = source_frame[s];
         sum[(size_t)b] += bound;
         if (sum[(size_t)b] > e->NMAX)
@@ -228,7 +272,10 @@ int ensure_ing(pp_engine* e) {
     pp_engine::Ing& g = e->ing;
     if (g.frames) return PP_OK;
     HIPCHK(e, hipHostMalloc((void**)&g.h_ring, (size_t)pp_engine::OFF_RING * e->B * sizeof(pp_engine::Ing::Slot)));
+    const size_t nf = (size_t)std::max(e->F - 3, 1);
+    if (!g.h_feats) HIPCHK(e, hipHostMalloc((void**)&g.h_feats, (size_t)pp_engine::OFF_RING * e->B * nf * sizeof(IngFeat)));
     DevAlloc A{e};
+    A(&g.feats, (size_t)e->B * nf);
     A(&g.finite, (size_t)e->B); A(&g.kept, (size_t)e->B); A(&g.frames, (size_t)e->B);     // (frames last: the ready flag)
     return A.st;
 }
@@ -240,8 +287,11 @@ int ensure_rig(pp_engine* e) {
     const size_t cap = (size_t)PP_RIG_MAX_SOURCES * e->B;
     if (!r.h_frames) HIPCHK(e, hipHostMalloc((void**)&r.h_frames, (size_t)pp_engine::OFF_RING * cap * sizeof(pp_engine::Ing::Slot)));
     if (!r.h_src) HIPCHK(e, hipHostMalloc((void**)&r.h_src, (size_t)pp_engine::OFF_RING * cap * sizeof(RigSource)));
+    const size_t nf = (size_t)std::max(e->F - 3, 1);
+    if (!r.h_feats) HIPCHK(e, hipHostMalloc((void**)&r.h_feats, (size_t)pp_engine::OFF_RING * cap * nf * sizeof(IngFeat)));
     r.sources_cap = (int)cap;
     DevAlloc A{e};
+    A(&r.feats, cap * nf);
     A(&r.src, cap); A(&r.finite, cap); A(&r.kept, cap); A(&r.out_base, cap); A(&r.frames, cap);     // (frames last: the ready flag)
     return A.st;
 }
@@ -291,6 +341,14 @@ int enqueue_ingest(pp_engine* e, const uint8_t* data, const int64_t* bo, int bat
         memcpy(src_ring, plan.rig.data(), (size_t)records * sizeof(RigSource));
         HIPCHK(e, hipMemcpyAsync(R.src, src_ring, (size_t)records * sizeof(RigSource), hipMemcpyHostToDevice, stream));
     }
+    // the feature columns of a _fields call: a table beside the records, through the same ring slot on the same stream
+    IngFeat* const d_feats = rig ? R.feats : e->ing.feats;
+    if (plan.nfeat) {
+        const size_t nfe = (size_t)records * plan.nfeat;
+        IngFeat* feat_ring = rig ? R.h_feats + (size_t)slot * R.sources_cap * plan.nfeat : e->ing.h_feats + (size_t)slot * e->B * plan.nfeat;
+        memcpy(feat_ring, plan.feats.data(), nfe * sizeof(IngFeat));
+        HIPCHK(e, hipMemcpyAsync(d_feats, feat_ring, nfe * sizeof(IngFeat), hipMemcpyHostToDevice, stream));
+    }
     HIPCHK(e, hipEventRecord(e->off_ev[slot], stream));
     int* const chunk_cnt = e->ing.chunks;
     int* const chunk_base = e->ing.chunks + (size_t)records * plan.stride;
@@ -304,6 +362,7 @@ int enqueue_ingest(pp_engine* e, const uint8_t* data, const int64_t* bo, int bat
         p.src_finite = R.finite; p.src_kept = R.kept; p.out_base = R.out_base;
         p.finite = e->ing.finite; p.kept = e->ing.kept; p.offsets = e->d_offsets; p.out = e->d_points;
         p.out_rows = out_rows;
+        p.feats = d_feats; p.nfeat = plan.nfeat;
         ProfScope ps(e, nullptr);
         launch_rig_ingest(p, stream);
     } else {
@@ -315,6 +374,7 @@ int enqueue_ingest(pp_engine* e, const uint8_t* data, const int64_t* bo, int bat
         p.chunk_cnt = chunk_cnt; p.chunk_base = chunk_base;
         p.finite = e->ing.finite; p.kept = e->ing.kept; p.offsets = e->d_offsets; p.out = e->d_points;
         p.out_rows = out_rows;
+        p.feats = d_feats; p.nfeat = plan.nfeat;
         ProfScope ps(e, nullptr);
         launch_frames(p, stream);
     }
@@ -338,7 +398,7 @@ int ingest_sync(pp_engine* e, const char* who, const uint8_t* data, const int64_
         HIPCHK(e, hipMemcpy(&total, e->d_offsets + batch, sizeof(int), hipMemcpyDeviceToHost));
         if (points_out_capacity < total)
             return fail(e, PP_ERR_ARG, "%s: points_out holds %lld points, %d were kept", who, (long long)points_out_capacity, total);
-        if (total) HIPCHK(e, hipMemcpy(points_out, e->d_points, (size_t)total * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        if (total) HIPCHK(e, hipMemcpy(points_out, e->d_points, (size_t)total * (3 + plan.nfeat) * sizeof(float), hipMemcpyDeviceToHost));
     }
     return PP_OK;
 }
@@ -434,6 +494,64 @@ int pp_ingest_rig_pointcloud2_async(pp_handle e, const uint8_t* data_pinned, con
     IngestPlan plan;
     int st = check_rig(e, "pp_ingest_rig_pointcloud2_async", data_pinned, byte_offsets, layouts, cfgs, source_frame, sources, batch,
                        &plan);
+    if (st) return st;
+    prof_reset(e);
+    if ((st = enqueue_ingest(e, data_pinned, byte_offsets, batch, nullptr, plan, e->copy_stream))) return st;
+    return finish_async_upload(e, batch);     // as pp_upload_points_async does
+}
+
+int pp_ingest_pointcloud2_fields(pp_handle e, const uint8_t* data, const int64_t* byte_offsets, const pp_pc2_layout* layouts,
+                                 int32_t batch, const pp_ingest_config* cfg, const pp_pc2_feature* features, int32_t nfeat,
+                                 float* points_out, int64_t points_out_capacity) {
+    if (!e) return PP_ERR_ARG;
+    (void)hipSetDevice(e->device);
+    static const char* const who = "pp_ingest_pointcloud2_fields";
+    if (nfeat < 0) return fail(e, PP_ERR_ARG, "%s: nfeat %d < 0", who, nfeat);
+    IngestPlan plan;
+    int st = check_ingest(e, who, data, byte_offsets, layouts, batch, cfg, &plan, features, nfeat);
+    if (st) return st;
+    return ingest_sync(e, who, data, byte_offsets, batch, cfg, plan, points_out, points_out_capacity);
+}
+
+int pp_ingest_pointcloud2_fields_async(pp_handle e, const uint8_t* data_pinned, const int64_t* byte_offsets,
+                                       const pp_pc2_layout* layouts, int32_t batch, const pp_ingest_config* cfg,
+                                       const pp_pc2_feature* features, int32_t nfeat) {
+    if (!e) return PP_ERR_ARG;
+    (void)hipSetDevice(e->device);
+    static const char* const who = "pp_ingest_pointcloud2_fields_async";
+    if (nfeat < 0) return fail(e, PP_ERR_ARG, "%s: nfeat %d < 0", who, nfeat);
+    IngestPlan plan;
+    int st = check_ingest(e, who, data_pinned, byte_offsets, layouts, batch, cfg, &plan, features, nfeat);
+    if (st) return st;
+    prof_reset(e);
+    if ((st = enqueue_ingest(e, data_pinned, byte_offsets, batch, cfg, plan, e->copy_stream))) return st;
+    return finish_async_upload(e, batch);     // as pp_upload_points_async does
+}
+
+int pp_ingest_rig_pointcloud2_fields(pp_handle e, const uint8_t* data, const int64_t* byte_offsets, const pp_pc2_layout* layouts,
+                                     const pp_ingest_config* cfgs, const int32_t* source_frame, int32_t sources, int32_t batch,
+                                     const pp_pc2_feature* features, int32_t nfeat, float* points_out,
+                                     int64_t points_out_capacity) {
+    if (!e) return PP_ERR_ARG;
+    (void)hipSetDevice(e->device);
+    static const char* const who = "pp_ingest_rig_pointcloud2_fields";
+    if (nfeat < 0) return fail(e, PP_ERR_ARG, "%s: nfeat %d < 0", who, nfeat);
+    IngestPlan plan;
+    int st = check_rig(e, who, data, byte_offsets, layouts, cfgs, source_frame, sources, batch, &plan, features, nfeat);
+    if (st) return st;
+    return ingest_sync(e, who, data, byte_offsets, batch, nullptr, plan, points_out, points_out_capacity);
+}
+
+int pp_ingest_rig_pointcloud2_fields_async(pp_handle e, const uint8_t* data_pinned, const int64_t* byte_offsets,
+                                           const pp_pc2_layout* layouts, const pp_ingest_config* cfgs,
+                                           const int32_t* source_frame, int32_t sources, int32_t batch,
+                                           const pp_pc2_feature* features, int32_t nfeat) {
+    if (!e) return PP_ERR_ARG;
+    (void)hipSetDevice(e->device);
+    static const char* const who = "pp_ingest_rig_pointcloud2_fields_async";
+    if (nfeat < 0) return fail(e, PP_ERR_ARG, "%s: nfeat %d < 0", who, nfeat);
+    IngestPlan plan;
+    int st = check_rig(e, who, data_pinned, byte_offsets, layouts, cfgs, source_frame, sources, batch, &plan, features, nfeat);
     if (st) return st;
     prof_reset(e);
     if ((st = enqueue_ingest(e, data_pinned, byte_offsets, batch, nullptr, plan, e->copy_stream))) return st;

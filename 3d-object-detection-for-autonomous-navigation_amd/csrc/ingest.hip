@@ -14,6 +14,10 @@
 //   k_ingest_scan     one workgroup: a wave per frame scans its chunk counts -> chunk bases, the frame's finite and kept
 //                     counts; then the frame offsets
 //   k_ingest_scatter  re-reads the chunks; a finite record's rank is its chunk's base + the finite lanes below it
+//
+// pp_ingest_pointcloud2_fields* (rows of F > 3 floats): the count and the scan are the same launches -- validity is x y z's
+// alone --, and k_ingest_scatter_f<F> writes x y z and the frame's F - 3 feature columns (ingest_dev.h: ing_feature) as one
+// row, one 16-byte store for F = 4.
 #include "pp_common.h"
 #include "ingest_dev.h"
 
@@ -84,6 +88,48 @@ __global__ __launch_bounds__(PP_WAVE * ING_WAVES) void k_ingest_scatter(const ui
     }
 }
 
+// k_ingest_scatter for rows of F floats: columns 3 ... F - 1 are the frame's feature columns feats[b][0 ... F - 4]
+template <int F>
+__global__ __launch_bounds__(PP_WAVE * ING_WAVES) void k_ingest_scatter_f(const uint8_t* __restrict__ raw,
+                                                                         const IngFrame* __restrict__ frames,
+                                                                         const IngFeat* __restrict__ feats, int stride,
+                                                                         int first, int decimate, IngXform xf,
+                                                                         const int* __restrict__ chunk_base,
+                                                                         const int* __restrict__ offsets,
+                                                                         float* __restrict__ out, long long out_rows) {
+    const int b = blockIdx.y;
+    const IngFrame f = frames[b];
+    const int lane = threadIdx.x & (PP_WAVE - 1);
+    const int c = blockIdx.x * ING_WAVES + (threadIdx.x >> 6);
+    if (c >= f.nchunks) return;
+    IngFeat ft[F - 3];
+#pragma unroll
+    for (int j = 0; j < F - 3; ++j) ft[j] = feats[(size_t)b * (F - 3) + j];
+    const uint8_t* base = raw + f.byte_off;
+    const long long row0 = offsets[b];
+    int run = chunk_base[(size_t)b * stride + c];
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int k = 0; k < ING_ITER; ++k) {
+        const int i = c * ING_CHUNK + k * PP_WAVE + lane;
+        double p[3];
+        const bool fin = i < f.n_rec && ing_read(base, f, i, p);
+        const unsigned long long m = __ballot(fin);
+        const int r = run + __popcll(m & below) - first;
+        run += __popcll(m);
+        if (fin && r >= 0 && r % decimate == 0) {
+            const long long row = row0 + r / decimate;
+            if (row < out_rows) {                  // (always: the host sized the call from the frames' bounds)
+                float o[F];
+                ing_transform(p, xf, o);
+                const uint8_t* rec = ing_record(base, f, i);
+#pragma unroll
+                for (int j = 0; j < F - 3; ++j) o[3 + j] = ing_feature(rec, ft[j], f.big_endian != 0);
+                ing_store_row<F>(out, row, o);
+            }
+        }
+    }
+}
+
 }  // namespace
 
 int ingest_chunks(int n_rec) { return (n_rec + ING_CHUNK - 1) / ING_CHUNK; }
@@ -97,7 +143,11 @@ void launch_ingest(const IngestParams& p, hipStream_t s) {
               p.chunk_cnt, p.chunk_base, p.finite, p.kept, p.offsets);
     if (p.stride > 0) {
         const IngXform xf = ing_xform_of(p);
-        PP_LAUNCH("k_ingest_scatter", k_ingest_scatter, grid, block, 0, s, p.raw, p.frames, p.stride, p.first, p.decimate,
-                  xf, p.chunk_base, p.offsets, p.out, p.out_rows);
+        if (p.nfeat == 0)
+            PP_LAUNCH("k_ingest_scatter", k_ingest_scatter, grid, block, 0, s, p.raw, p.frames, p.stride, p.first, p.decimate,
+                      xf, p.chunk_base, p.offsets, p.out, p.out_rows);
+        else            // (nfeat == 1: the C-ABI holds nfeat to F - 3 and pp_create F to 3 or 4)
+            PP_LAUNCH("k_ingest_scatter_f<4>", k_ingest_scatter_f<4>, grid, block, 0, s, p.raw, p.frames, p.feats, p.stride,
+                      p.first, p.decimate, xf, p.chunk_base, p.offsets, p.out, p.out_rows);
     }
 }

@@ -50,6 +50,72 @@ __device__ __forceinline__ bool ing_read(const uint8_t* base, const IngFrame& f,
     return ing_finite(p[0]) && ing_finite(p[1]) && ing_finite(p[2]);
 }
 
+// ---- feature columns (IngFeat): what the scatter kernels of pp_ingest_pointcloud2_fields* write behind x y z
+// the raw element at any address, byte-swapped when the message is big-endian, widened exactly to float64
+template <typename T>
+__device__ __forceinline__ T ing_load(const uint8_t* p) {
+    T v;
+    __builtin_memcpy(&v, p, sizeof(T));
+    return v;
+}
+
+__device__ __forceinline__ double ing_raw(const uint8_t* p, int type, bool big_endian) {
+    switch (type) {                                // (the same for every lane of the wave: a scalar branch)
+        case 1: return (double)ing_load<int8_t>(p);
+        case 2: return (double)ing_load<uint8_t>(p);
+        case 3: {
+            uint16_t v = ing_load<uint16_t>(p);
+            if (big_endian) v = __builtin_bswap16(v);
+            return (double)(int16_t)v;
+        }
+        case 4: {
+            uint16_t v = ing_load<uint16_t>(p);
+            if (big_endian) v = __builtin_bswap16(v);
+            return (double)v;
+        }
+        case 5: {
+            uint32_t v = ing_load<uint32_t>(p);
+            if (big_endian) v = __builtin_bswap32(v);
+            return (double)(int32_t)v;
+        }
+        case 6: {
+            uint32_t v = ing_load<uint32_t>(p);
+            if (big_endian) v = __builtin_bswap32(v);
+            return (double)v;
+        }
+        case 7: {
+            uint32_t v = ing_load<uint32_t>(p);
+            if (big_endian) v = __builtin_bswap32(v);
+            return (double)__uint_as_float(v);
+        }
+        default: {                                 // 8 (the host refused every other code)
+            unsigned long long v = ing_load<unsigned long long>(p);
+            if (big_endian) v = __builtin_bswap64(v);
+            return __longlong_as_double((long long)v);
+        }
+    }
+}
+
+// float32(float64(raw) * scale + bias), product and sum rounded separately; a constant column (type 0) reads nothing.
+// A non-finite value is carried through as it is.
+__device__ __forceinline__ float ing_feature(const uint8_t* rec, const IngFeat& t, bool big_endian) {
+#pragma clang fp contract(off)
+    if (t.type == 0) return (float)t.bias;
+    const double prod = ing_raw(rec + t.off, t.type, big_endian) * t.scale;
+    return (float)(prod + t.bias);
+}
+
+// one row of F floats, written once: a single 16-byte store for F = 4 (the rows of `out` are 16-byte aligned then)
+template <int F>
+__device__ __forceinline__ void ing_store_row(float* __restrict__ out, long long row, const float (&o)[F]) {
+    if constexpr (F == 4) {
+        *reinterpret_cast<float4*>(out + row * 4) = make_float4(o[0], o[1], o[2], o[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < F; ++j) out[row * F + j] = o[j];
+    }
+}
+
 // ---- depth pixels (DepthFrame): decode, validity and deprojection, as k_depth_count / k_depth_scatter and the rig kernels use them
 // depth and validity of pixel i (i < n_pix) of a frame
 __device__ __forceinline__ bool dep_read(const uint8_t* base, const DepthFrame& f, int i, float& z) {

@@ -523,6 +523,12 @@ struct IngFrame {              // one message of a call, as the kernels see it
     int f64, big_endian;       // FLOAT64 fields (else FLOAT32); byte order
     int nchunks;               // ingest_chunks(n_rec)
 };
+// One feature column (row entry 3 ... F - 1) of one message (pp_ingest_pointcloud2_fields*): the value is
+// float32(float64(raw) * scale + bias), raw read at record + off; type 0 reads nothing, the value is float32(bias)
+struct IngFeat {
+    int off, type;             // byte offset within a record; PointField code 1 INT8 ... 8 FLOAT64, or 0: constant
+    double scale, bias;
+};
 // depth_ingest.hip: raw depth images (sensor_msgs/Image, 16UC1 or 32FC1) -> the same resident points and offsets
 struct DepthFrame {            // one image of a call, as the kernels see it
     long long byte_off;        // its first byte within the staged bytes
@@ -547,8 +553,10 @@ struct IngestParamsT {
     int* finite;               // [batch] out: finite records (valid pixels)
     int* kept;                 // [batch] out: points written
     int* offsets;              // [batch + 1] out: the frames' row offsets in `out`
-    float* out;                // [sum kept][3]
+    float* out;                // [sum kept][3 + nfeat]
     long long out_rows;        // rows `out` holds
+    const IngFeat* feats;      // [batch][nfeat] feature columns behind x y z (PointCloud2 only), or nfeat == 0
+    int nfeat;
 };
 typedef IngestParamsT<IngFrame> IngestParams;
 typedef IngestParamsT<DepthFrame> DepthIngestParams;
@@ -578,8 +586,10 @@ struct RigParamsT {
     int* finite;               // [batch] out: the frames' sums of src_finite
     int* kept;                 // [batch] out: the frames' sums of src_kept
     int* offsets;              // [batch + 1] out: the frames' row offsets in `out`
-    float* out;                // [sum kept][3]
+    float* out;                // [sum kept][3 + nfeat]
     long long out_rows;        // rows `out` holds
+    const IngFeat* feats;      // [sources][nfeat] feature columns behind x y z (PointCloud2 only), or nfeat == 0
+    int nfeat;
 };
 void launch_rig_ingest(const RigParamsT<IngFrame>& p, hipStream_t s);
 void launch_rig_ingest(const RigParamsT<DepthFrame>& p, hipStream_t s);

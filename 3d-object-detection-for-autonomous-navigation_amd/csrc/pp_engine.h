@@ -242,6 +242,8 @@ struct pp_engine {
         Slot* frames = nullptr;            // [B]
         Slot* h_ring = nullptr;            // pinned [OFF_RING][B]: travels with the offsets' ring slots
         int *finite = nullptr, *kept = nullptr;            // [B] finite records (valid pixels), points kept
+        IngFeat* feats = nullptr;          // [B][F - 3] feature columns of a pp_ingest_pointcloud2_fields* call
+        IngFeat* h_feats = nullptr;        // pinned [OFF_RING][B][F - 3]: travels with the frame records
         int batch = 0;                     // frames of the last ingest (pp_ingest_info)
         // a rig call (pp_ingest_rig_*) has one record per SOURCE: tables of their own, sized by sources_cap =
         // PP_RIG_MAX_SOURCES * B on first use (api_ingest.hip: ensure_rig); finite / kept above then hold the frames' sums
@@ -250,6 +252,8 @@ struct pp_engine {
             RigSource* src = nullptr;      // [sources_cap]
             Slot* h_frames = nullptr;      // pinned [OFF_RING][sources_cap]: travel with the offsets' ring slots
             RigSource* h_src = nullptr;    // pinned [OFF_RING][sources_cap]
+            IngFeat* feats = nullptr;      // [sources_cap][F - 3], as Ing::feats
+            IngFeat* h_feats = nullptr;    // pinned [OFF_RING][sources_cap][F - 3]
             int *finite = nullptr, *kept = nullptr, *out_base = nullptr;   // [sources_cap]
             int sources_cap = 0;
             int sources = 0;               // sources of the last ingest when it was a rig call, else 0 (pp_ingest_rig_info)

@@ -13,6 +13,9 @@
 //   k_rig_scatter  grid (chunks, source): a kept record of source s goes to row offsets[frame(s)] + out_base[s] +
 //                  (rank - first) / decimate, transformed by the source's own matrices (read from the source table: S x 168
 //                  bytes do not fit a kernel argument)
+//
+// pp_ingest_rig_pointcloud2_fields* (rows of F > 3 floats): the same count and scan, and k_rig_scatter_f<F>, which writes
+// x y z and the source's F - 3 feature columns (ingest_dev.h: ing_feature) as one row, one 16-byte store for F = 4.
 #include "pp_common.h"
 #include "ingest_dev.h"
 
@@ -149,6 +152,64 @@ __global__ __launch_bounds__(PP_WAVE * ING_WAVES) void k_rig_scatter(const uint8
     }
 }
 
+// k_rig_scatter<IngFrame> for rows of F floats: columns 3 ... F - 1 are the source's feature columns feats[s][0 ... F - 4]
+template <int F>
+__global__ __launch_bounds__(PP_WAVE * ING_WAVES) void k_rig_scatter_f(const uint8_t* __restrict__ raw,
+                                                                      const IngFrame* __restrict__ frames,
+                                                                      const RigSource* __restrict__ src,
+                                                                      const IngFeat* __restrict__ feats, int batch, int stride,
+                                                                      const int* __restrict__ chunk_base,
+                                                                      const int* __restrict__ out_base,
+                                                                      const int* __restrict__ offsets,
+                                                                      float* __restrict__ out, long long out_rows) {
+    const int s = blockIdx.y;
+    const IngFrame f = frames[s];
+    const int lane = threadIdx.x & (PP_WAVE - 1);
+    const int c = blockIdx.x * ING_WAVES + (threadIdx.x >> 6);
+    if (c >= f.nchunks) return;
+    const RigSource& g = src[s];
+    const int frame = g.frame, first = g.first, decimate = g.decimate;
+    if (frame < 0 || frame >= batch) return;       // (never: the host checked the frame map)
+    IngXform xf;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { xf.r[k] = g.r[k]; xf.r2[k] = g.r2[k]; }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) xf.lift[k] = g.lift[k];
+    IngFeat ft[F - 3];
+#pragma unroll
+    for (int j = 0; j < F - 3; ++j) ft[j] = feats[(size_t)s * (F - 3) + j];
+    const uint8_t* base = raw + f.byte_off;
+    const long long row0 = (long long)offsets[frame] + out_base[s];
+    int run = chunk_base[(size_t)s * stride + c];
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int k = 0; k < ING_ITER; ++k) {
+        const int i = c * ING_CHUNK + k * PP_WAVE + lane;
+        double p[3];
+        const bool ok = i < f.n_rec && ing_read(base, f, i, p);
+        const unsigned long long m = __ballot(ok);
+        const int r = run + __popcll(m & below) - first;
+        run += __popcll(m);
+        if (ok && r >= 0 && r % decimate == 0) {
+            const long long row = row0 + r / decimate;
+            if (row >= 0 && row < out_rows) {      // (always: the host sized the call from the sources' bounds)
+                float o[F];
+                ing_transform(p, xf, o);
+                const uint8_t* rec = ing_record(base, f, i);
+#pragma unroll
+                for (int j = 0; j < F - 3; ++j) o[3 + j] = ing_feature(rec, ft[j], f.big_endian != 0);
+                ing_store_row<F>(out, row, o);
+            }
+        }
+    }
+}
+
+inline void launch_rig_scatter_f(const RigParamsT<DepthFrame>&, hipStream_t, dim3, dim3) {}    // (an image has no field)
+inline void launch_rig_scatter_f(const RigParamsT<IngFrame>& p, hipStream_t s, dim3 grid, dim3 block) {
+    // (nfeat == 1: the C-ABI holds nfeat to F - 3 and pp_create F to 3 or 4)
+    PP_LAUNCH("k_rig_scatter_f<4>", k_rig_scatter_f<4>, grid, block, 0, s, p.raw, p.frames, p.src, p.feats, p.batch, p.stride,
+              p.chunk_base, p.out_base, p.offsets, p.out, p.out_rows);
+}
+
 template <typename Frame>
 void launch_rig(const RigParamsT<Frame>& p, hipStream_t s, const char* n_count, const char* n_scan, const char* n_scatter) {
     if (p.batch <= 0 || p.sources <= 0) return;
@@ -157,7 +218,9 @@ void launch_rig(const RigParamsT<Frame>& p, hipStream_t s, const char* n_count, 
         PP_LAUNCH(n_count, k_rig_count<Frame>, grid, block, 0, s, p.raw, p.frames, p.stride, p.chunk_cnt);
     PP_LAUNCH(n_scan, k_rig_scan<Frame>, dim3(1), dim3(1024), 0, s, p.frames, p.src, p.sources, p.batch, p.stride, p.chunk_cnt,
               p.chunk_base, p.src_finite, p.src_kept, p.out_base, p.finite, p.kept, p.offsets);
-    if (p.stride > 0)
+    if (p.stride > 0 && p.nfeat > 0)
+        launch_rig_scatter_f(p, s, grid, block);
+    else if (p.stride > 0)
         PP_LAUNCH(n_scatter, k_rig_scatter<Frame>, grid, block, 0, s, p.raw, p.frames, p.src, p.batch, p.stride, p.chunk_base,
                   p.out_base, p.offsets, p.out, p.out_rows);
 }

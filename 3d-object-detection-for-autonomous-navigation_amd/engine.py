@@ -114,12 +114,16 @@ class PinnedArray:
 class MessageStaging:
     """The bytes of a batch of sensor_msgs/PointCloud2 messages in one page-locked buffer, with their layouts: what
     `Engine.ingest_pointcloud2_async` takes.  `.bytes` (uint8) may be refilled in place between uses by messages of the
-    same layouts; `.byte_offsets` [batch + 1]; `.layouts`: the ctypes array of pp_pc2_layout."""
+    same layouts; `.byte_offsets` [batch + 1]; `.layouts`: the ctypes array of pp_pc2_layout.  features (a list of
+    `ingest.FeatureField`s, or None): resolved against every message's fields here and kept -- `.features`, the ctypes array
+    of pp_pc2_feature [batch][nfeat], and `.nfeat`; the ingest then writes rows of 3 + nfeat floats."""
 
-    def __init__(self, lib, msgs):
+    def __init__(self, lib, msgs, features=None):
         from . import ingest
         tuples = [ingest.as_tuple(m) for m in msgs]
         self.byte_offsets, self.layouts, bufs = _pack_messages(tuples)
+        self.fields = [t[1:] for t in tuples]       # what a later features= is resolved against (the bytes stay in .bytes)
+        self.features, self.nfeat = _feature_table(tuples, None if features is None else ingest.rig_features(features, len(tuples)))
         self._fill(lib, bufs)
 
     def _fill(self, lib, bufs):
@@ -208,15 +212,44 @@ def _pack_messages(tuples):
     return offs, layouts, bufs
 
 
-def _ingest_config(first, decimate, lift):
+def _ingest_config(first, decimate, lift, mount=None):
+    """pp_ingest_config of a plain call.  mount None: the reference's RealSense matrices and [0, 0, lift] (lift None: the
+    sensor height); else the `ingest.Mount`'s own r, r2 and lift (a lidar: Mount(np.eye(3), np.eye(3), 0.0))."""
     from . import ingest
     c = _lib.PPIngestConfig()
     c.first, c.decimate = int(first), int(decimate)
-    r, r2 = ingest._matrices()
+    if mount is None:
+        r, r2 = ingest._matrices()
+        lift3 = [0.0, 0.0, float(ingest.SENSOR_HEIGHT if lift is None else lift)]
+    else:
+        if not isinstance(mount, ingest.Mount):
+            raise ValueError("mount must be an ingest.Mount (Mount.realsense(), Mount.from_matrix(T), Mount(r, r2, lift))")
+        if lift is not None:
+            raise ValueError("lift and mount are both given: the mount carries its own lift")
+        r, r2, lift3 = mount.r, mount.r2, [float(v) for v in mount.lift]
     c.r[:] = [float(v) for v in np.asarray(r, np.float64).reshape(-1)]
     c.r2[:] = [float(v) for v in np.asarray(r2, np.float64).reshape(-1)]
-    c.lift[:] = [0.0, 0.0, float(lift)]
+    c.lift[:] = lift3
     return c
+
+
+def _feature_table(tuples, per_message):
+    """The ctypes array of pp_pc2_feature [len(tuples)][nfeat] of a _fields call and nfeat.  per_message: one list of
+    `ingest.FeatureField`s per message (each resolved against its own message: `ingest.feature_layout_of`), or None ->
+    (None, None): the call that delivers x y z only."""
+    from . import ingest
+    if per_message is None:
+        return None, None
+    rows = [ingest.feature_layout_of(t, f) for t, f in zip(tuples, per_message)]
+    nf = len(rows[0]) if rows else 0
+    if any(len(r) != nf for r in rows):
+        raise ValueError(f"the messages' feature lists differ in length: {sorted({len(r) for r in rows})}")
+    arr = (_lib.PPPc2Feature * max(len(rows) * nf, 1))()
+    for b, row in enumerate(rows):
+        for j, (off, typ, scale, bias) in enumerate(row):
+            e = arr[b * nf + j]
+            e.offset, e.datatype, e.scale, e.bias = int(off), int(typ), float(scale), float(bias)
+    return arr, nf
 
 
 def _rig_configs(rig, batch):
@@ -259,13 +292,24 @@ class RigDepthStaging(DepthStaging):
 
 
 class RigMessageStaging(MessageStaging):
-    """MessageStaging for `Engine.ingest_rig_pointcloud2_async`, as RigDepthStaging."""
+    """MessageStaging for `Engine.ingest_rig_pointcloud2_async`, as RigDepthStaging.  features: `ingest.rig_features`."""
 
-    def __init__(self, lib, frames, rig):
+    def __init__(self, lib, frames, rig, features=None):
         from . import ingest
         flat, self.source_frame = ingest.rig_frame_map(frames, rig, "staging_rig_pointcloud2")
         self.batch = len(frames)
         super().__init__(lib, flat)
+        if features is not None:
+            self.features, self.nfeat = _rig_feature_table([ingest.as_tuple(m) for m in flat], rig, features)
+
+
+def _rig_feature_table(tuples, rig, features):
+    """`_feature_table` of a rig call's messages (frames back to back, a frame's cameras in rig order)."""
+    from . import ingest
+    if features is None:
+        return None, None
+    per = ingest.rig_features(features, len(rig))
+    return _feature_table(tuples, [per[s % len(rig)] for s in range(len(tuples))])
 
 
 class Engine:
@@ -732,26 +776,39 @@ class Engine:
         return kept[:B]
 
     # ---- live-camera ingest (pp_ingest_pointcloud2*; ingest.py states the rule) ----
-    def ingest_pointcloud2(self, msgs, first=1, decimate=4, lift=None, return_points=False):
+    def ingest_pointcloud2(self, msgs, first=1, decimate=4, lift=None, return_points=False, features=None, mount=None):
         """Raw sensor_msgs/PointCloud2 messages -> the engine's resident frames, on the GPU: x y z out of the bytes,
         non-finite records dropped, every `decimate`-th survivor from index `first`, camera axes turned into lidar axes
         and lifted by `lift` (ingest.SENSOR_HEIGHT) -- `ingest.realsense_to_lidar(ingest.pointcloud2_to_xyz(...))`
         exactly.  msgs: list of messages (`ingest.as_tuple`).  The engine needs max_points_per_frame >=
         ingest.kept_bound(width, height, first, decimate) (76800 for a 640 x 480 cloud at 1, 4).  There is no host
-        fallback: a layout the library refuses raises with its text.  return_points: the resident points, one [n_b, 3]
-        float32 array per frame (the parity tap)."""
+        fallback: a layout the library refuses raises with its text.  return_points: the resident points, one [n_b, F]
+        float32 array per frame (the parity tap).
+        features: a list of F - 3 `ingest.FeatureField`s for an engine with num_point_features F > 3 (x y z intensity: one)
+        -- row columns 3 ... come out of the messages' own fields, float32(float64(raw) * scale + bias), exactly
+        `ingest.ingest_np(msg, ..., features=features)` (pp_ingest_pointcloud2_fields).  Validity and selection are x y
+        z's alone; a non-finite feature value is carried through as it is.  None: x y z only, which an engine with F != 3
+        refuses.  Messages that name or scale the field differently: a list with one such list per message
+        (`ingest.rig_features`).  mount: an `ingest.Mount` in place of the reference's RealSense matrices and `lift` (a lidar:
+        Mount(np.eye(3), np.eye(3), 0.0))."""
         from . import ingest
         tuples = [ingest.as_tuple(m) for m in msgs]
         offs, layouts, bufs = _pack_messages(tuples)
         data = (bufs[0] if len(bufs) == 1 else np.concatenate(bufs)) if bufs and offs[-1] else np.zeros((1,), np.uint8)
-        cfg = _ingest_config(first, decimate, ingest.SENSOR_HEIGHT if lift is None else lift)
+        cfg = _ingest_config(first, decimate, lift, mount)
+        table, nf = _feature_table(tuples, None if features is None else ingest.rig_features(features, len(tuples)))
         pts, cap = None, 0
         if return_points:
             cap = sum(ingest.kept_bound(t[1], t[2], max(int(first), 0), max(int(decimate), 1)) for t in tuples)
-            pts = np.empty((max(cap, 1), 3), np.float32)
-        self._check(self._lib.pp_ingest_pointcloud2(self._h, _ptr(data), _ptr(offs), layouts, len(tuples),
-                                                    ctypes.byref(cfg), _ptr(pts), ctypes.c_int64(cap)),
-                    "pp_ingest_pointcloud2")
+            pts = np.empty((max(cap, 1), 3 + (nf or 0)), np.float32)
+        if table is None:
+            self._check(self._lib.pp_ingest_pointcloud2(self._h, _ptr(data), _ptr(offs), layouts, len(tuples),
+                                                        ctypes.byref(cfg), _ptr(pts), ctypes.c_int64(cap)),
+                        "pp_ingest_pointcloud2")
+        else:
+            self._check(self._lib.pp_ingest_pointcloud2_fields(self._h, _ptr(data), _ptr(offs), layouts, len(tuples),
+                                                               ctypes.byref(cfg), table, nf, _ptr(pts), ctypes.c_int64(cap)),
+                        "pp_ingest_pointcloud2_fields")
         self._offsets = None          # the resident frames' sizes are device values (ingest_info reads them back)
         self._ing_batch = len(tuples)
         if not return_points:
@@ -766,28 +823,49 @@ class Engine:
         self._check(self._lib.pp_ingest_info(self._h, _ptr(fin), _ptr(kept), B), "pp_ingest_info")
         return {"finite": fin[:B], "kept": kept[:B]}
 
-    def staging_pointcloud2(self, msgs):
-        """Packs messages into a page-locked MessageStaging for ingest_pointcloud2_async (the counterpart of staging())."""
-        return MessageStaging(self._lib, msgs)
+    def staging_pointcloud2(self, msgs, features=None, mount=None):
+        """Packs messages into a page-locked MessageStaging for ingest_pointcloud2_async (the counterpart of staging()).
+        features (as ingest_pointcloud2) are resolved against the messages here and kept with the staging; so is `mount`
+        (an `ingest.Mount`), which ingest_pointcloud2_async then uses unless it is given one."""
+        st = MessageStaging(self._lib, msgs, features)
+        st.mount = mount
+        return st
 
-    def ingest_pointcloud2_async(self, staging, first=1, decimate=4, lift=None):
+    def ingest_pointcloud2_async(self, staging, first=1, decimate=4, lift=None, features=None, mount=None):
         """ingest_pointcloud2 without waiting (pp_ingest_pointcloud2_async): the bytes of a MessageStaging travel on the
         copy stream and are ingested and voxelised there, beside the pass in flight; the buffer must not be rewritten
-        before the sync() that follows the detect_async() consuming these frames.  Mixes freely with upload_async."""
-        from . import ingest
-        cfg = _ingest_config(first, decimate, ingest.SENSOR_HEIGHT if lift is None else lift)
-        self._check(self._lib.pp_ingest_pointcloud2_async(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets),
-                                                          staging.layouts, staging.byte_offsets.shape[0] - 1,
-                                                          ctypes.byref(cfg)), "pp_ingest_pointcloud2_async")
+        before the sync() that follows the detect_async() consuming these frames.  Mixes freely with upload_async.
+        features / mount: None -> the staging's own (staging_pointcloud2(msgs, features=..., mount=...)); given here, they
+        are resolved against the staged messages' fields for this call (pp_ingest_pointcloud2_fields_async)."""
+        B = staging.byte_offsets.shape[0] - 1
+        if mount is None and lift is None:
+            mount = getattr(staging, "mount", None)
+        cfg = _ingest_config(first, decimate, lift, mount)
+        table, nf = staging.features, staging.nfeat
+        if features is not None:
+            tuples = [(staging.bytes[staging.byte_offsets[b]:staging.byte_offsets[b + 1]],) + tuple(g)
+                      for b, g in enumerate(staging.fields)]
+            from . import ingest
+            table, nf = _feature_table(tuples, ingest.rig_features(features, B))
+        if table is None:
+            self._check(self._lib.pp_ingest_pointcloud2_async(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets),
+                                                              staging.layouts, B, ctypes.byref(cfg)),
+                        "pp_ingest_pointcloud2_async")
+        else:
+            self._check(self._lib.pp_ingest_pointcloud2_fields_async(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets),
+                                                                     staging.layouts, B, ctypes.byref(cfg), table, nf),
+                        "pp_ingest_pointcloud2_fields_async")
         self._offsets = None
         self._ing_batch = staging.byte_offsets.shape[0] - 1
         staging._users.add(self)
         self._staged.append(staging)      # kept alive while a copy may still read it (see upload_async)
 
-    def detect_pointcloud2(self, msgs, rect=None, trv2c=None, on_numeric="f32"):
+    def detect_pointcloud2(self, msgs, rect=None, trv2c=None, on_numeric="f32", features=None, mount=None, first=1, decimate=4):
         """ingest_pointcloud2 + detect_async + sync + detections: `detect` for raw camera messages (the reference's
-        production mode, train.py:810-828).  rect / trv2c / on_numeric as `detect`."""
-        self.ingest_pointcloud2(msgs)
+        production mode, train.py:810-828).  rect / trv2c / on_numeric as `detect`; features / mount / first / decimate as
+        ingest_pointcloud2 (a lidar feeding a 4-feature model: features=[FeatureField("intensity")],
+        mount=Mount(np.eye(3), np.eye(3), 0.0), first=0, decimate=1)."""
+        self.ingest_pointcloud2(msgs, first=first, decimate=decimate, features=features, mount=mount)
         if rect is not None:
             self.set_calib(rect, trv2c, len(msgs))
         return self._detect_resident(on_numeric)
@@ -852,14 +930,19 @@ class Engine:
         return self._detect_resident(on_numeric)
 
     # ---- camera-rig ingest (pp_ingest_rig_*; ingest.py states the rule) ----
-    def _ingest_rig(self, name, data, offs, layouts, rig, fmap, batch, bounds, return_points):
+    def _ingest_rig(self, name, data, offs, layouts, rig, fmap, batch, bounds, return_points, table=None, nf=None):
         pts, cap = None, 0
         if return_points:
             cap = int(sum(bounds))
-            pts = np.empty((max(cap, 1), 3), np.float32)
+            pts = np.empty((max(cap, 1), 3 + (nf or 0)), np.float32)
         cfgs = _rig_configs(rig, batch)
-        self._check(getattr(self._lib, name)(self._h, _ptr(data), _ptr(offs), layouts, cfgs, _ptr(fmap), len(fmap), batch,
-                                             _ptr(pts), ctypes.c_int64(cap)), name)
+        if table is None:
+            self._check(getattr(self._lib, name)(self._h, _ptr(data), _ptr(offs), layouts, cfgs, _ptr(fmap), len(fmap), batch,
+                                                 _ptr(pts), ctypes.c_int64(cap)), name)
+        else:
+            name += "_fields"
+            self._check(getattr(self._lib, name)(self._h, _ptr(data), _ptr(offs), layouts, cfgs, _ptr(fmap), len(fmap), batch,
+                                                 table, nf, _ptr(pts), ctypes.c_int64(cap)), name)
         self._offsets = None          # the resident frames' sizes are device values (ingest_info reads them back)
         self._ing_batch, self._rig_shape = batch, (batch, len(rig))
         if not return_points:
@@ -883,16 +966,20 @@ class Engine:
         bounds = [ingest.kept_bound(t[1], t[2], rig.first[s % len(rig)], rig.decimate[s % len(rig)]) for s, t in enumerate(tuples)]
         return self._ingest_rig("pp_ingest_rig_depth", data, offs, layouts, rig, fmap, len(frames), bounds, return_points)
 
-    def ingest_rig_pointcloud2(self, frames, rig, return_points=False):
+    def ingest_rig_pointcloud2(self, frames, rig, return_points=False, features=None):
         """ingest_rig_depth for PointCloud2 messages: `ingest.rig_ingest_np(frames[b], rig)` exactly (the rig's intrinsics,
-        depth_scale and clip are not read)."""
+        depth_scale and clip are not read).  features (`ingest.rig_features`: one list of FeatureFields for every camera, or
+        one list per camera): rows of 3 + nf floats as ingest_pointcloud2(features=...) writes them,
+        `ingest.rig_ingest_np(frames[b], rig, features)` exactly (pp_ingest_rig_pointcloud2_fields)."""
         from . import ingest
         flat, fmap = ingest.rig_frame_map(frames, rig, "ingest_rig_pointcloud2")
         tuples = [ingest.as_tuple(m) for m in flat]
         offs, layouts, bufs = _pack_messages(tuples)
         data = (bufs[0] if len(bufs) == 1 else np.concatenate(bufs)) if offs[-1] else np.zeros((1,), np.uint8)
         bounds = [ingest.kept_bound(t[1], t[2], rig.first[s % len(rig)], rig.decimate[s % len(rig)]) for s, t in enumerate(tuples)]
-        return self._ingest_rig("pp_ingest_rig_pointcloud2", data, offs, layouts, rig, fmap, len(frames), bounds, return_points)
+        table, nf = _rig_feature_table(tuples, rig, features)
+        return self._ingest_rig("pp_ingest_rig_pointcloud2", data, offs, layouts, rig, fmap, len(frames), bounds, return_points,
+                                table, nf)
 
     def ingest_rig_info(self):
         """Per camera of the last rig ingest: `finite` records (valid pixels) and points `kept`, int32 [B, cameras]
@@ -906,17 +993,23 @@ class Engine:
         """Packs the depth images of B rig frames into a page-locked RigDepthStaging for ingest_rig_depth_async."""
         return RigDepthStaging(self._lib, frames, rig)
 
-    def staging_rig_pointcloud2(self, frames, rig):
-        """Packs the messages of B rig frames into a page-locked RigMessageStaging for ingest_rig_pointcloud2_async."""
-        return RigMessageStaging(self._lib, frames, rig)
+    def staging_rig_pointcloud2(self, frames, rig, features=None):
+        """Packs the messages of B rig frames into a page-locked RigMessageStaging for ingest_rig_pointcloud2_async;
+        features (as ingest_rig_pointcloud2) are resolved against the messages here and kept with the staging."""
+        return RigMessageStaging(self._lib, frames, rig, features)
 
-    def _ingest_rig_async(self, name, staging, layouts, rig):
+    def _ingest_rig_async(self, name, staging, layouts, rig, table=None, nf=None):
         S, B = len(staging.source_frame), staging.batch
         if S != B * len(rig):
             raise ValueError(f"{name}: the staging holds {S} sources in {B} frames, the rig has {len(rig)} cameras")
         cfgs = _rig_configs(rig, B)
-        self._check(getattr(self._lib, name)(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets), layouts, cfgs,
-                                             _ptr(staging.source_frame), S, B), name)
+        if table is None:
+            self._check(getattr(self._lib, name)(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets), layouts, cfgs,
+                                                 _ptr(staging.source_frame), S, B), name)
+        else:
+            name = name.replace("_async", "_fields_async")
+            self._check(getattr(self._lib, name)(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets), layouts, cfgs,
+                                                 _ptr(staging.source_frame), S, B, table, nf), name)
         self._offsets = None
         self._ing_batch, self._rig_shape = B, (B, len(rig))
         staging._users.add(self)
@@ -929,9 +1022,16 @@ class Engine:
                   for s, g in enumerate(staging.images)]
         self._ingest_rig_async("pp_ingest_rig_depth_async", staging, _rig_depth_layouts(tuples, rig), rig)
 
-    def ingest_rig_pointcloud2_async(self, staging, rig):
-        """ingest_rig_pointcloud2 without waiting (pp_ingest_rig_pointcloud2_async), from a RigMessageStaging."""
-        self._ingest_rig_async("pp_ingest_rig_pointcloud2_async", staging, staging.layouts, rig)
+    def ingest_rig_pointcloud2_async(self, staging, rig, features=None):
+        """ingest_rig_pointcloud2 without waiting (pp_ingest_rig_pointcloud2_async), from a RigMessageStaging.  features:
+        None -> the staging's own (staging_rig_pointcloud2(frames, rig, features=...)); given here, they are resolved
+        against the staged messages' fields for this call."""
+        table, nf = staging.features, staging.nfeat
+        if features is not None:
+            tuples = [(staging.bytes[staging.byte_offsets[s]:staging.byte_offsets[s + 1]],) + tuple(g)
+                      for s, g in enumerate(staging.fields)]
+            table, nf = _rig_feature_table(tuples, rig, features)
+        self._ingest_rig_async("pp_ingest_rig_pointcloud2_async", staging, staging.layouts, rig, table, nf)
 
     def detect_rig_depth(self, frames, rig, rect=None, trv2c=None, on_numeric="f32"):
         """ingest_rig_depth + detect_async + sync + detections: `detect_depth` for a rig's images.  rect / trv2c /
@@ -941,9 +1041,9 @@ class Engine:
             self.set_calib(rect, trv2c, len(frames))
         return self._detect_resident(on_numeric)
 
-    def detect_rig_pointcloud2(self, frames, rig, rect=None, trv2c=None, on_numeric="f32"):
-        """ingest_rig_pointcloud2 + detect_async + sync + detections."""
-        self.ingest_rig_pointcloud2(frames, rig)
+    def detect_rig_pointcloud2(self, frames, rig, rect=None, trv2c=None, on_numeric="f32", features=None):
+        """ingest_rig_pointcloud2 + detect_async + sync + detections; features as ingest_rig_pointcloud2."""
+        self.ingest_rig_pointcloud2(frames, rig, features=features)
         if rect is not None:
             self.set_calib(rect, trv2c, len(frames))
         return self._detect_resident(on_numeric)

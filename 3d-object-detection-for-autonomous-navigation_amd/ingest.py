@@ -28,6 +28,11 @@ of the finite flags for NaN removal and decimation together, the two products su
 multiply-adds -- which `ingest_np` assembles; the tests hold all of them to `realsense_to_lidar(pointcloud2_to_xyz(...))`
 bit for bit.
 
+A model with more than three point features (x y z intensity: `config.kitti_shaped_config`) is fed from the message's own
+fields: `FeatureField` names a field, `feature_layout_of` resolves it against a message, `pointcloud2_to_points` and
+`ingest_np(..., features=...)` state the rule -- column j is float32(float64(raw) * scale + bias), validity is x y z's
+alone -- and `Engine.ingest_pointcloud2(..., features=...)` runs it on the GPU.
+
 The second half of the module is the same for depth images (`Engine.ingest_depth` / `detect_depth`,
 csrc/depth_ingest.hip): the image the camera's point-cloud topic is computed from goes to the GPU instead of the
 message, `depth_to_xyz` / `depth_ingest_np` state the rule, and `depth_to_pointcloud2` builds the message it is held to.
@@ -115,6 +120,87 @@ def layout_of(msg):
             "datatype": tx if tx == ty == tz else tx | ty << 8 | tz << 16, "is_bigendian": int(big)}
 
 
+class FeatureField:
+    """One feature column (row entry 3, 4, ...) of a message: the field `name`, element `index` of it when its count is
+    above 1, as float32(float64(raw) * scale + bias).  Any PointField datatype (INT8 ... FLOAT64); every integer type and
+    float32 widen exactly to float64, the product and the sum are rounded separately in float64 (no fused multiply-add),
+    the result is rounded once to float32.  A non-finite value is carried through as it is (NaN as NaN, +-inf as +-inf):
+    a record is dropped only when x, y or z is non-finite.  `FeatureField.constant(value)`: a column that reads nothing
+    and holds float32(value) -- for a sensor without the field the model was trained with."""
+
+    def __init__(self, name, scale=1.0, bias=0.0, index=0):
+        self.name = None if name is None else str(name)
+        self.scale, self.bias, self.index = float(scale), float(bias), int(index)
+        if not (np.isfinite(self.scale) and np.isfinite(self.bias)):
+            raise ValueError(f"FeatureField {name!r}: scale {scale} and bias {bias} must be finite")
+        if self.index < 0:
+            raise ValueError(f"FeatureField {name!r}: index {index} < 0")
+
+    @classmethod
+    def constant(cls, value):
+        return cls(None, 1.0, value)
+
+    def __repr__(self):
+        if self.name is None:
+            return f"FeatureField.constant({self.bias!r})"
+        return f"FeatureField({self.name!r}, scale={self.scale!r}, bias={self.bias!r}, index={self.index})"
+
+
+def _as_feature(f):
+    return f if isinstance(f, FeatureField) else FeatureField(*f) if isinstance(f, (tuple, list)) else FeatureField(f)
+
+
+def feature_layout_of(msg, features):
+    """The pp_pc2_feature entries of `features` (FeatureFields, or field names) for ONE message: a list of (offset,
+    datatype, scale, bias), datatype 0 for a constant.  offset is the byte offset of the element within a record (field
+    offset + index * itemsize).  Raises a ValueError that names the message's fields when a name is missing or index >=
+    the field's count."""
+    data, width, height, point_step, row_step, fields, big = as_tuple(msg)
+    _, fl, _, _, _, _ = _parse(data, width, height, point_step, row_step, fields, big)
+    by = {f[0]: f for f in fl}
+    have = ", ".join(f"{n} (datatype {t}, count {c})" for n, _, t, c in fl)
+    out = []
+    for j, f in enumerate(_as_feature(f) for f in features):
+        if f.name is None:
+            out.append((0, 0, 1.0, f.bias))
+            continue
+        if f.name not in by:
+            raise ValueError(f"feature {j}: the message has no field {f.name!r}; its fields are {have}")
+        _, off, typ, cnt = by[f.name]
+        if f.index >= max(cnt, 1):
+            raise ValueError(f"feature {j}: index {f.index} >= count {max(cnt, 1)} of field {f.name!r}; the message's fields "
+                             f"are {have}")
+        out.append((off + f.index * np.dtype(_PF_TYPES[typ]).itemsize, typ, f.scale, f.bias))
+    return out
+
+
+def pointcloud2_to_points(msg, features, remove_nans=True):
+    """A message (`as_tuple`) -> [N, 3 + len(features)]: x y z as `pointcloud2_to_xyz` gives them, then one column per
+    FeatureField, `(rec[name].astype(np.float64) * scale + bias).astype(np.float32)` (a constant: float32(value)).  The
+    array has the dtype of x y z (float32 or float64; a float32 feature value is exact in either).  remove_nans drops the
+    records whose x, y or z is non-finite, as ros_numpy's remove_nans does; a non-finite FEATURE value stays."""
+    t = as_tuple(msg)
+    data, width, height, point_step, row_step, fields, big = t
+    dt, _, width, height, row_step, buf = _parse(data, width, height, point_step, row_step, fields, big)
+    table = feature_layout_of(t, features)          # (raises for a missing name / index)
+    rows = buf[:height * row_step].reshape(height, row_step)[:, :width * point_step]
+    rec = np.ascontiguousarray(rows).reshape(-1).view(dt)
+    xyz = np.stack([rec["x"], rec["y"], rec["z"]], axis=-1)
+    cols = []
+    with np.errstate(all="ignore"):
+        for f, (_, typ, scale, bias) in zip((_as_feature(f) for f in features), table):
+            if typ == 0:
+                cols.append(np.full(len(rec), np.float32(bias), np.float32))
+                continue
+            raw = rec[f.name]
+            raw = raw[:, f.index] if raw.ndim == 2 else raw
+            cols.append((raw.astype(np.float64) * scale + bias).astype(np.float32))
+    pts = np.concatenate([xyz] + [c.astype(xyz.dtype)[:, None] for c in cols], axis=1) if cols else xyz
+    if remove_nans:
+        pts = pts[np.isfinite(xyz).all(axis=1)]
+    return pts
+
+
 def kept_bound(width, height, first=1, decimate=4):
     """Most points a width x height message can keep: max(0, ceil((width * height - first) / decimate)) -- the host-side
     size of everything behind the GPU ingest, whose true counts exist on the device only."""
@@ -198,14 +284,23 @@ def _lift_vector(lift):
     return v
 
 
-def ingest_np(msg, first=1, decimate=4, lift=SENSOR_HEIGHT, matrices=None):
+def ingest_np(msg, first=1, decimate=4, lift=SENSOR_HEIGHT, matrices=None, features=None):
     """What the GPU ingest computes for one message, on the host by its own rule: records -> finite flags -> `select_np`
     -> `transform_ordered64` -> float32.  Returns (points [kept, 3] float32, finite count).  matrices: (r, r2) of another
-    mount than the reference's (`Mount`); lift may then be a vector of 3."""
-    xyz = pointcloud2_to_xyz(*as_tuple(msg), remove_nans=False)
+    mount than the reference's (`Mount`); lift may then be a vector of 3.  features: a list of nf `FeatureField`s -- the
+    points are then [kept, 3 + nf], the columns behind x y z as `pointcloud2_to_points` gives them for the kept records
+    (validity and selection do not look at them; a non-finite feature value is carried through)."""
+    if features is None:
+        xyz = pointcloud2_to_xyz(*as_tuple(msg), remove_nans=False)
+    else:
+        full = pointcloud2_to_points(msg, features, remove_nans=False)
+        xyz = full[:, :3]
     fin = np.isfinite(xyz).all(axis=1)
     keep = select_np(fin, first, decimate)
-    return transform_ordered64(xyz[keep], lift, matrices).astype(np.float32), int(fin.sum())
+    pts = transform_ordered64(xyz[keep], lift, matrices).astype(np.float32)
+    if features is not None:
+        pts = np.concatenate([pts, full[keep, 3:].astype(np.float32)], axis=1)
+    return pts, int(fin.sum())
 
 
 # ---- depth images (Engine.ingest_depth / detect_depth, csrc/depth_ingest.hip) ---------------------------------------
@@ -464,9 +559,25 @@ class CameraRig:
         return range(len(self))
 
 
+def rig_features(features, cameras):
+    """The `features` of a rig call, per camera (of a plain call: per message): None; one list of FeatureFields for every
+    camera; or a list with one such list per camera (the cameras' messages may name, scale or lack the field differently)."""
+    if features is None:
+        return [None] * cameras
+    features = list(features)
+    if features and all(isinstance(f, (list, tuple)) and all(isinstance(g, FeatureField) for g in f) for f in features):
+        if len(features) != cameras:
+            raise ValueError(f"{len(features)} feature lists for a rig of {cameras} cameras")
+        widths = {len(f) for f in features}
+        if len(widths) != 1:
+            raise ValueError(f"the cameras' feature lists differ in length: {sorted(widths)}")
+        return [list(f) for f in features]
+    return [features] * cameras
+
+
 def _rig_concat(parts):
     pts = [p for p, _ in parts]
-    return (np.concatenate(pts).astype(np.float32).reshape(-1, 3), np.array([n for _, n in parts], np.int64),
+    return (np.concatenate(pts).astype(np.float32).reshape(-1, pts[0].shape[1]), np.array([n for _, n in parts], np.int64),
             np.array([len(p) for p in pts], np.int64))
 
 
@@ -480,10 +591,11 @@ def rig_depth_ingest_np(images, rig):
                         for c in rig._cameras(images, "rig_depth_ingest_np")])
 
 
-def rig_ingest_np(msgs, rig):
+def rig_ingest_np(msgs, rig, features=None):
     """`rig_depth_ingest_np` for PointCloud2 messages: the concatenation of `ingest_np` per camera.  Returns (points,
-    finite records per camera, kept points per camera)."""
-    return _rig_concat([ingest_np(msgs[c], rig.first[c], rig.decimate[c], rig.mounts[c].lift, rig.mounts[c].matrices)
+    finite records per camera, kept points per camera).  features: `rig_features` -- the points are then [sum kept, 3 + nf]."""
+    per = rig_features(features, len(rig))
+    return _rig_concat([ingest_np(msgs[c], rig.first[c], rig.decimate[c], rig.mounts[c].lift, rig.mounts[c].matrices, per[c])
                         for c in rig._cameras(msgs, "rig_ingest_np")])
 
 

@@ -100,6 +100,51 @@ def pointcloud2_from_xyz(xyz, width, height, point_step=20, row_pad=0, datatype=
     return (rows.tobytes(), int(width), int(height), int(point_step), row_step, fields, bool(bigendian))
 
 
+_PF_NUMPY = {1: "i1", 2: "u1", 3: "i2", 4: "u2", 5: "i4", 6: "u4", 7: "f4", 8: "f8"}      # PointField datatype codes
+
+
+def pointcloud2_from_points(points, width, height, feature_fields=(("intensity", 7, 12),), point_step=16, row_pad=0,
+                            datatype=7, bigendian=False, offsets=(0, 4, 8), extra_fields=(), seed=977):
+    """[width * height, 3 + nf] rows (x y z and nf further columns; NaN / inf allowed) -> a sensor_msgs/PointCloud2 tuple as
+    `pointcloud2_from_xyz` gives it, with one more field per column.  feature_fields: one (name, datatype, offset[, count[,
+    index]]) per column -- the column's values are stored as that PointField datatype (1 INT8 ... 8 FLOAT64; an integer
+    type takes the values as they are, so give it integers in its range) at byte `offset` of a record; with count > 1
+    the field has `count` elements, the values go to element `index` and the others are random.  extra_fields: further
+    (name, offset, datatype, count) fields that are declared and left random (a lidar driver's `ring`, `time`).  x y z,
+    point_step, row_pad, datatype, bigendian, offsets and the random filling as `pointcloud2_from_xyz`."""
+    rng = np.random.default_rng(seed)
+    n = int(width) * int(height)
+    feature_fields = [tuple(f) for f in feature_fields]
+    pts = np.asarray(points, np.float64).reshape(n, 3 + len(feature_fields))
+    order = ">" if bigendian else "<"
+    dt = np.dtype(order + ("f8" if datatype == 8 else "f4"))
+    if max(offsets) + dt.itemsize > point_step:
+        raise ValueError(f"offsets {offsets} do not fit point_step {point_step}")
+    rec = rng.integers(0, 256, (n, point_step), dtype=np.uint8)
+    for k, off in enumerate(offsets):
+        rec[:, off:off + dt.itemsize] = np.ascontiguousarray(pts[:, k].astype(dt)).view(np.uint8).reshape(n, dt.itemsize)
+    fields = [("x", offsets[0], datatype, 1), ("y", offsets[1], datatype, 1), ("z", offsets[2], datatype, 1)]
+    for j, ff in enumerate(feature_fields):
+        name, typ, off = ff[0], int(ff[1]), int(ff[2])
+        count = int(ff[3]) if len(ff) > 3 else 1
+        index = int(ff[4]) if len(ff) > 4 else 0
+        if typ not in _PF_NUMPY:
+            raise ValueError(f"feature field {name}: unknown datatype {typ}")
+        fdt = np.dtype(order + _PF_NUMPY[typ])
+        if off < 0 or off + fdt.itemsize * count > point_step or not 0 <= index < count:
+            raise ValueError(f"feature field {name}: offset {off}, count {count}, index {index} do not fit point_step {point_step}")
+        at = off + index * fdt.itemsize
+        with np.errstate(invalid="ignore", over="ignore"):
+            vals = pts[:, 3 + j].astype(fdt)
+        rec[:, at:at + fdt.itemsize] = np.ascontiguousarray(vals).view(np.uint8).reshape(n, fdt.itemsize)
+        fields.append((str(name), off, typ, count))
+    fields.extend((str(nm), int(o), int(t), int(c)) for nm, o, t, c in extra_fields)
+    row_step = width * point_step + int(row_pad)
+    rows = rng.integers(0, 256, (height, row_step), dtype=np.uint8)
+    rows[:, :width * point_step] = rec.reshape(height, width * point_step)
+    return (rows.tobytes(), int(width), int(height), int(point_step), row_step, fields, bool(bigendian))
+
+
 def pointcloud2_message(frame, width=640, height=480, point_step=20, row_pad=0, nan_fraction=0.3, datatype=7,
                         bigendian=False, offsets=(0, 4, 8), seed=977):
     """A seeded camera message (`pointcloud2_from_xyz`): the points are a `d435i_cloud` turned back into camera axes

@@ -180,14 +180,17 @@ class VoxelNet:
         idx = image_idx if image_idx is not None else list(range(len(frames)))
         return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(frames))]
 
-    def detect_pointcloud2(self, msgs, rect=None, trv2c=None, image_idx=None, p2=None):
+    def detect_pointcloud2(self, msgs, rect=None, trv2c=None, image_idx=None, p2=None, features=None, mount=None, first=1,
+                           decimate=4):
         """Fused path from raw sensor_msgs/PointCloud2 messages (the reference's production mode: ingest on the GPU,
-        Engine.detect_pointcloud2) -> the same list of prediction dicts as `detect`; p2 as there."""
+        Engine.detect_pointcloud2) -> the same list of prediction dicts as `detect`; p2 as there.  features / mount / first /
+        decimate as Engine.ingest_pointcloud2: a model with 4 point features takes its intensity column from the messages'
+        own field (features=[ingest.FeatureField("intensity")]), a lidar the identity mount."""
         self._need_p2(p2, "detect_pointcloud2")
         self._detector()
         if self.d.project_bbox:
             self.engine.set_projection(np.broadcast_to(np.asarray(p2, np.float64), (len(msgs), 4, 4)))
-        dets, n = self.engine.detect_pointcloud2(msgs, rect, trv2c)
+        dets, n = self.engine.detect_pointcloud2(msgs, rect, trv2c, features=features, mount=mount, first=first, decimate=decimate)
         bb = self._bboxes(len(msgs))
         idx = image_idx if image_idx is not None else list(range(len(msgs)))
         return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(msgs))]
@@ -205,12 +208,12 @@ class VoxelNet:
         idx = image_idx if image_idx is not None else list(range(len(images)))
         return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(images))]
 
-    def _detect_rig(self, who, frames, rig, rect, trv2c, image_idx, p2):
+    def _detect_rig(self, who, frames, rig, rect, trv2c, image_idx, p2, **feed):
         self._need_p2(p2, who)
         self._detector()
         if self.d.project_bbox:
             self.engine.set_projection(np.broadcast_to(np.asarray(p2, np.float64), (len(frames), 4, 4)))
-        dets, n = getattr(self.engine, who)(frames, rig, rect, trv2c)
+        dets, n = getattr(self.engine, who)(frames, rig, rect, trv2c, **feed)
         bb = self._bboxes(len(frames))
         idx = image_idx if image_idx is not None else list(range(len(frames)))
         return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(frames))]
@@ -221,9 +224,10 @@ class VoxelNet:
         the host-concatenated frames; p2 as there."""
         return self._detect_rig("detect_rig_depth", frames, rig, rect, trv2c, image_idx, p2)
 
-    def detect_rig_pointcloud2(self, frames, rig, rect=None, trv2c=None, image_idx=None, p2=None):
-        """`detect_rig_depth` for the PointCloud2 messages of a camera rig (Engine.detect_rig_pointcloud2)."""
-        return self._detect_rig("detect_rig_pointcloud2", frames, rig, rect, trv2c, image_idx, p2)
+    def detect_rig_pointcloud2(self, frames, rig, rect=None, trv2c=None, image_idx=None, p2=None, features=None):
+        """`detect_rig_depth` for the PointCloud2 messages of a camera rig (Engine.detect_rig_pointcloud2); features as
+        Engine.ingest_rig_pointcloud2."""
+        return self._detect_rig("detect_rig_pointcloud2", frames, rig, rect, trv2c, image_idx, p2, features=features)
 
     @staticmethod
     def _to_dict(dets, n, img_idx, bbox=None):

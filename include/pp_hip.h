@@ -43,7 +43,8 @@ extern "C" {
  * PP_SNMS_MAX_BOXES, pp_soft_nms.  Then PP_DEPTH_U16, PP_DEPTH_F32, pp_depth_layout, pp_ingest_depth,
  * pp_ingest_depth_async (declared behind pp_ingest_info, whose counts serve both feeds).  Then PP_RIG_MAX_SOURCES,
  * pp_ingest_rig_depth, pp_ingest_rig_depth_async, pp_ingest_rig_pointcloud2, pp_ingest_rig_pointcloud2_async,
- * pp_ingest_rig_info. */
+ * pp_ingest_rig_info.  Then pp_pc2_feature, pp_ingest_pointcloud2_fields, pp_ingest_pointcloud2_fields_async,
+ * pp_ingest_rig_pointcloud2_fields, pp_ingest_rig_pointcloud2_fields_async (declared behind pp_ingest_rig_info). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -906,6 +907,44 @@ int pp_ingest_rig_pointcloud2_async(pp_handle h, const uint8_t* data_pinned, con
  * points kept.  Either pointer may be NULL.  PP_ERR_STATE when the last ingest was no rig call, PP_ERR_ARG when `sources`
  * is not that call's. */
 int pp_ingest_rig_info(pp_handle h, int32_t* finite_counts, int32_t* kept_counts, int32_t sources);
+
+/* ---- PointCloud2 feature fields -------------------------------------------------------------------------- */
+/* A model with num_point_features F > 3 (x y z intensity: F = 4) fed from messages: row columns 3 ... F - 1 come out of the
+ * message's own fields, one pp_pc2_feature per column and per message.  datatype 1 ... 8 (INT8 ... FLOAT64): the raw
+ * element is read at record + offset in the message's byte order, nothing assumed aligned, widened exactly to float64, and
+ * the column is float32(float64(raw) * scale + bias) -- product and sum rounded separately, no fused multiply-add, one
+ * rounding to float32: numpy's (rec[name].astype(float64) * scale + bias).astype(float32).  datatype 0: a constant column,
+ * nothing is read, the value is float32(bias).  Validity, rank and selection are pp_ingest_pointcloud2's, from x y z alone:
+ * finite, kept, the offsets and columns 0 - 2 of every row are what that call gives; a non-finite FEATURE value is carried
+ * through as it is (NaN as NaN, +-inf as +-inf).  Equals <package>/ingest.py's ingest_np(msg, ..., features=...) exactly.
+ * Not done: feature-based validity, unpacking a packed rgb float into channels, depth images (an image has no field:
+ * pp_ingest_depth* and pp_ingest_rig_depth* keep refusing F != 3). */
+typedef struct pp_pc2_feature {
+    int32_t offset;              /* byte offset of the element within a record (element index of a count > 1 field folded in) */
+    int32_t datatype;            /* PointField code 1 ... 8, or 0: constant */
+    double scale, bias;          /* finite */
+} pp_pc2_feature;
+/* pp_ingest_pointcloud2 / _async with `features` [batch][nfeat] behind cfg; nfeat must be num_point_features - 3, and with
+ * nfeat 0 (features may be NULL) on a 3-feature handle these ARE those calls.  points_out is [sum kept, 3 + nfeat].
+ * pp_ingest_info serves them unchanged.  Refused before anything is queued with PP_ERR_ARG, pp_last_error naming the frame and
+ * the feature index: features NULL with nfeat > 0, nfeat != num_point_features - 3, a datatype outside 0 ... 8, offset < 0 or
+ * offset + size > point_step, a non-finite scale or bias -- and everything the twin call refuses. */
+int pp_ingest_pointcloud2_fields(pp_handle h, const uint8_t* data, const int64_t* byte_offsets, const pp_pc2_layout* layouts,
+                                 int32_t batch, const pp_ingest_config* cfg, const pp_pc2_feature* features, int32_t nfeat,
+                                 float* points_out, int64_t points_out_capacity);
+int pp_ingest_pointcloud2_fields_async(pp_handle h, const uint8_t* data_pinned, const int64_t* byte_offsets,
+                                       const pp_pc2_layout* layouts, int32_t batch, const pp_ingest_config* cfg,
+                                       const pp_pc2_feature* features, int32_t nfeat);
+/* The same for pp_ingest_rig_pointcloud2 / _async: `features` is [sources][nfeat], the refusals name the source;
+ * pp_ingest_rig_info serves them unchanged. */
+int pp_ingest_rig_pointcloud2_fields(pp_handle h, const uint8_t* data, const int64_t* byte_offsets, const pp_pc2_layout* layouts,
+                                     const pp_ingest_config* cfgs, const int32_t* source_frame, int32_t sources, int32_t batch,
+                                     const pp_pc2_feature* features, int32_t nfeat, float* points_out,
+                                     int64_t points_out_capacity);
+int pp_ingest_rig_pointcloud2_fields_async(pp_handle h, const uint8_t* data_pinned, const int64_t* byte_offsets,
+                                           const pp_pc2_layout* layouts, const pp_ingest_config* cfgs,
+                                           const int32_t* source_frame, int32_t sources, int32_t batch,
+                                           const pp_pc2_feature* features, int32_t nfeat);
 
 /* ---- frustum crop (box_np_ops.remove_outside_points) ----------------------------------------------------- */
 /* Crops the RESIDENT frames to the camera image's frustum on the GPU: what _create_reduced_point_cloud,
