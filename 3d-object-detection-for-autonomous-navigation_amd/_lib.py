@@ -18,7 +18,7 @@ _INCLUDE = os.path.join(os.path.dirname(_PKG), "include", "pp_hip.h")
 SO_PATH = os.path.join(_PKG, os.environ.get("PP_HIP_LIB", "libpp_hip.so"))
 _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
 SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_nms.hip", "api_project.hip", "api_class_nms.hip", "api_metrics.hip", "api_publish.hip", "api_train.hip", "api_dataprep.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
-           "rotate_iou.hip", "rotate_nms.hip", "box_project.hip", "loss.hip", "metrics.hip", "optim.hip", "grad_clip.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip", "depth_ingest.hip", "rig_ingest.hip",
+           "rotate_iou.hip", "rotate_nms.hip", "box_project.hip", "loss.hip", "metrics.hip", "optim.hip", "grad_clip.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip",
            "gt_database.hip", "eval_stats.hip", "frustum_crop.hip", "weight_publish.hip", "soft_nms.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")

@@ -1,9 +1,10 @@
-// C-ABI, live-camera ingest (pp_ingest_*): PointCloud2 messages (kernels: ingest.hip) or raw depth images (kernels:
-// depth_ingest.hip) -> the resident points and offsets.  The two feeds differ in their checks, their frame records and
-// their three launches; the staging, the input-buffer flip and the ordering are one path (enqueue_ingest).  A rig call
-// (pp_ingest_rig_*; kernels: rig_ingest.hip) takes the same path with one record per SOURCE and the sources' own
-// selections and transforms in a table beside them.  The pp_ingest_*pointcloud2_fields* calls add a table of feature
-// columns, one row per frame or source, which travels as the frame records do.
+// C-ABI, live-camera ingest (pp_ingest_*): PointCloud2 messages or raw depth images (kernels: ingest.hip) -> the resident
+// points and offsets.  Every exported call is one argument record handed to ingest_call: the two feeds differ in what
+// check_one refuses and fills (their layouts and frame records); the checks around it, the staging, the input-buffer flip
+// and the ordering are one path (check_call, enqueue_ingest).  A rig call (pp_ingest_rig_*) takes the same path with one
+// record per SOURCE and the sources' own selections and transforms in a table beside them.  The
+// pp_ingest_*pointcloud2_fields* calls add a table of feature columns, one row per frame or source, which travels as the
+// frame records do.
 #include "pp_engine.h"
 
 namespace {
@@ -13,32 +14,32 @@ struct IngestPlanT {
     std::vector<Frame> frames;
     std::vector<int> bound_off;    // [batch + 1] prefix sums of the frames' kept bounds
     int max_bound = 0, stride = 0;
-    int64_t bytes = 0;             // byte_offsets[batch] - byte_offsets[0]
+    int64_t bytes = 0;             // byte_offsets[records] - byte_offsets[0]
     std::vector<RigSource> rig;    // a rig call: one entry per source, `frames` then holds the SOURCES' records; else empty
     std::vector<IngFeat> feats;    // a _fields call: [frames or sources][nfeat]; else empty
     int nfeat = 0;
 };
-typedef IngestPlanT<IngFrame> IngestPlan;
-typedef IngestPlanT<DepthFrame> DepthPlan;
+template <typename Layout> struct FrameOf;
+template <> struct FrameOf<pp_pc2_layout> { typedef IngFrame type; };
+template <> struct FrameOf<pp_depth_layout> { typedef DepthFrame type; };
 
-// What both feeds refuse before they look at a frame.  nfeat: the feature columns of a _fields call, or -1 for a call
-// that delivers x y z only.
-int check_ingest_call(pp_engine* e, const char* who, const int64_t* bo, const void* L, int batch, const pp_ingest_config* c,
-                      const pp_pc2_feature* features, int nfeat) {
-    if (e->train_pending) return fail(e, PP_ERR_STATE, "%s: a training step is in flight", who);
-    if (nfeat < 0) {
-        if (e->F != 3)
-            return fail(e, PP_ERR_UNSUPPORTED, "%s: num_point_features is %d, the live path delivers x y z only (3)", who, e->F);
-    } else {
-        if (nfeat > 0 && !features) return fail(e, PP_ERR_ARG, "%s: features is NULL, nfeat is %d", who, nfeat);
-        if (nfeat != e->F - 3)
-            return fail(e, PP_ERR_ARG, "%s: nfeat %d, num_point_features is %d: x y z and %d feature column(s) expected", who,
-                        nfeat, e->F, e->F - 3);
-    }
-    if (!bo || !L || !c) return fail(e, PP_ERR_ARG, "%s: null argument", who);
-    int st = check_batch(e, batch); if (st) return st;
-    return PP_OK;
-}
+// What an exported call was given.  A plain call: one configuration, source_frame NULL, sources 0; one without ING_FIELDS:
+// features NULL and nfeat 0, neither looked at; an asynchronous one: no tap.
+enum { ING_RIG = 1, ING_FIELDS = 2, ING_ASYNC = 4 };
+template <typename Layout>
+struct IngestArgs {
+    const uint8_t* data;
+    const int64_t* bo;             // [records + 1] byte offsets; records: frames, or the sources of a rig call
+    const Layout* L;               // [records]
+    const pp_ingest_config* cfgs;  // one, or [sources]
+    const int32_t* source_frame;   // [sources]
+    int sources, batch;
+    const pp_pc2_feature* features;
+    int nfeat;
+    float* points_out;             // the parity tap and the points it holds
+    int64_t points_out_capacity;
+    int kind;                      // ING_RIG | ING_FIELDS | ING_ASYNC
+};
 
 // `at`: "" for the one configuration of a plain call, "source 3: " for a rig's
 int check_selection(pp_engine* e, const char* who, const char* at, const pp_ingest_config* c) {
@@ -53,8 +54,8 @@ inline int64_t kept_bound(int64_t n, const pp_ingest_config* c) {
 
 // What is refused about one message (`at`: "frame 1" or "source 3"; its bytes are data[bo[i] .. bo[i + 1])); fills its
 // record and the bound on the points it keeps under `c`.
-int check_pc2_one(pp_engine* e, const char* who, const char* at, const int64_t* bo, int i, const pp_pc2_layout& l,
-                  const pp_ingest_config* c, IngFrame* f, int64_t* bound) {
+int check_one(pp_engine* e, const char* who, const char* at, const int64_t* bo, int i, const pp_pc2_layout& l,
+              const pp_ingest_config* c, IngFrame* f, int64_t* bound) {
     if (l.width < 0 || l.height < 0 || l.point_step < 1 || l.row_step < 0)
         return fail(e, PP_ERR_ARG, "%s: %s: width %d, height %d, point_step %d, row_step %d", who, at, l.width,
                     l.height, l.point_step, l.row_step);
@@ -112,12 +113,12 @@ int check_features_one(pp_engine* e, const char* who, const char* at, const pp_p
     return PP_OK;
 }
 inline int check_features_one(pp_engine*, const char*, const char*, const pp_depth_layout&, const pp_pc2_feature*, int, IngFeat*) {
-    return PP_OK;                                  // (an image has no field: the depth calls pass nfeat -1)
+    return PP_OK;                                  // (an image has no field)
 }
 
 // The same for one depth image.
-int check_depth_one(pp_engine* e, const char* who, const char* at, const int64_t* bo, int i, const pp_depth_layout& l,
-                    const pp_ingest_config* c, DepthFrame* f, int64_t* bound) {
+int check_one(pp_engine* e, const char* who, const char* at, const int64_t* bo, int i, const pp_depth_layout& l,
+              const pp_ingest_config* c, DepthFrame* f, int64_t* bound) {
     if (l.width < 0 || l.height < 0 || l.row_step < 0)
         return fail(e, PP_ERR_ARG, "%s: %s: width %d, height %d, row_step %d", who, at, l.width, l.height, l.row_step);
     const int64_t n_pix = (int64_t)l.width * l.height;
@@ -150,121 +151,102 @@ int check_depth_one(pp_engine* e, const char* who, const char* at, const int64_t
     f->width = l.width; f->n_pix = (int)n_pix; f->row_step = l.row_step;
     f->tight = l.row_step == l.width * size || l.height <= 1;
     f->f32 = l.encoding == PP_DEPTH_F32; f->big_endian = l.is_bigendian != 0;
-    f->nchunks = depth_chunks(f->n_pix);
+    f->nchunks = ingest_chunks(f->n_pix);
     f->fx = l.fx; f->fy = l.fy; f->ppx = l.ppx; f->ppy = l.ppy;
     f->depth_scale = l.depth_scale; f->z_min = l.z_min; f->z_max = l.z_max;
     return PP_OK;
 }
 
-inline int check_one(pp_engine* e, const char* who, const char* at, const int64_t* bo, int i, const pp_pc2_layout& l,
-                     const pp_ingest_config* c, IngFrame* f, int64_t* bound) {
-    return check_pc2_one(e, who, at, bo, i, l, c, f, bound);
-}
-inline int check_one(pp_engine* e, const char* who, const char* at, const int64_t* bo, int i, const pp_depth_layout& l,
-                     const pp_ingest_config* c, DepthFrame* f, int64_t* bound) {
-    return check_depth_one(e, who, at, bo, i, l, c, f, bound);
-}
-
-// Everything pp_ingest_pointcloud2* / pp_ingest_depth* refuse, before anything is queued.
+// Everything a pp_ingest_* call refuses, before anything is queued: what every call refuses before it looks at a record;
+// a rig's frame map; per record (frame, or source) its selection, its layout, its feature columns and the bound of its
+// frame; fills the plan.
 template <typename Layout, typename Frame>
-int check_frames(pp_engine* e, const char* who, const uint8_t* data, const int64_t* bo, const Layout* L, int batch,
-                 const pp_ingest_config* c, IngestPlanT<Frame>* plan, const pp_pc2_feature* features = nullptr, int nfeat = -1) {
-    int st = check_ingest_call(e, who, bo, L, batch, c, features, nfeat); if (st) return st;
-    if ((st = check_selection(e, who, "", c))) return st;
-    plan->nfeat = std::max(nfeat, 0);
-    plan->feats.assign((size_t)batch * plan->nfeat, IngFeat());
-    plan->frames.assign((size_t)batch, Frame());
-    plan->bound_off.assign((size_t)batch + 1, 0);
-    for (int b = 0; b < batch; ++b) {
-        char at[32];
-        snprintf(at, sizeof(at), "frame %d", b);
-        int64_t bound = 0;
-        Frame& f = plan->frames[(size_t)b];
-        if ((st = check_one(e, who, at, bo, b, L[b], c, &f, &bound))) return st;
-        if (plan->nfeat && (st = check_features_one(e, who, at, L[b], features + (size_t)b * nfeat, nfeat,
-                                                    plan->feats.data() + (size_t)b * nfeat))) return st;
-        if (bound > e->NMAX)
-            return fail(e, PP_ERR_ARG, "%s: frame %d: width %d x height %d keeps up to %lld points > max_points_per_frame=%d", who, b,
-                        L[b].width, L[b].height, (long long)bound, e->NMAX);
-        plan->stride = std::max(plan->stride, f.nchunks);
-        plan->max_bound = std::max(plan->max_bound, (int)bound);
-        plan->bound_off[(size_t)b + 1] = plan->bound_off[(size_t)b] + (int)bound;
+int check_call(pp_engine* e, const char* who, const IngestArgs<Layout>& a, IngestPlanT<Frame>* plan) {
+    const bool rig = (a.kind & ING_RIG) != 0;
+    const bool fields = (a.kind & ING_FIELDS) != 0;             // else: a call that delivers x y z only
+    const int nfeat = fields ? a.nfeat : 0;
+    const int batch = a.batch, records = rig ? a.sources : a.batch;
+    const int64_t* bo = a.bo;
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "%s: a training step is in flight", who);
+    if (!fields) {
+        if (e->F != 3)
+            return fail(e, PP_ERR_UNSUPPORTED, "%s: num_point_features is %d, the live path delivers x y z only (3)", who, e->F);
+    } else {
+        if (nfeat > 0 && !a.features) return fail(e, PP_ERR_ARG, "%s: features is NULL, nfeat is %d", who, nfeat);
+        if (nfeat != e->F - 3)
+            return fail(e, PP_ERR_ARG, "%s: nfeat %d, num_point_features is %d: x y z and %d feature column(s) expected", who,
+                        nfeat, e->F, e->F - 3);
     }
-    plan->bytes = bo[batch] - bo[0];
-    if (plan->bytes > 0 && !data) return fail(e, PP_ERR_ARG, "%s: data is NULL", who);
-    return PP_OK;
-}
-
-int check_ingest(pp_engine* e, const char* who, const uint8_t* data, const int64_t* bo, const pp_pc2_layout* L, int batch,
-                 const pp_ingest_config* c, IngestPlan* plan, const pp_pc2_feature* features = nullptr, int nfeat = -1) {
-    return check_frames(e, who, data, bo, L, batch, c, plan, features, nfeat);
-}
-int check_depth(pp_engine* e, const char* who, const uint8_t* data, const int64_t* bo, const pp_depth_layout* L, int batch,
-                const pp_ingest_config* c, DepthPlan* plan) {
-    return check_frames(e, who, data, bo, L, batch, c, plan);
-}
-
-// Everything pp_ingest_rig_* refuse, before anything is queued: the frame map, then per source what the single-camera
-// calls refuse per frame, then the frames' summed bounds.
-template <typename Layout, typename Frame>
-int check_rig(pp_engine* e, const char* who, const uint8_t* data, const int64_t* bo, const Layout* L,
-              const pp_ingest_config* cfgs, const int32_t* source_frame, int sources, int batch, IngestPlanT<Frame>* plan,
-              const pp_pc2_feature* features = nullptr, int nfeat = -1) {
-    int st = check_ingest_call(e, who, bo, L, batch, cfgs, features, nfeat); if (st) return st;
-    if (!source_frame) return fail(e, PP_ERR_ARG, "%s: null argument", who);
-    if (sources < 1) return fail(e, PP_ERR_ARG, "%s: sources %d < 1", who, sources);
-    if (source_frame[0] != 0)
-        return fail(e, PP_ERR_ARG, "%s: source 0: source_frame %d, the frame map starts at frame 0", who, source_frame[0]);
-    for (int s = 1, run = 1; s < sources; ++s) {
-        const int prev = source_frame[s - 1], cur = source_frame[s];
-        if (cur < prev)
-            return fail(e, PP_ERR_ARG, "%s: source %d: source_frame %d < %d of the source before it (the frame map never decreases)",
-                        who, s, cur, prev);
-        if (cur > prev + 1)
-            return fail(e, PP_ERR_ARG, "%s: source %d: source_frame %d skips frame %d (every frame has at least one source)", who, s,
-                        cur, prev + 1);
-        run = cur == prev ? run + 1 : 1;
-        if (run > PP_RIG_MAX_SOURCES)
-            return fail(e, PP_ERR_ARG, "%s: source %d: frame %d has more than PP_RIG_MAX_SOURCES=%d sources", who, s, cur,
-                        PP_RIG_MAX_SOURCES);
+    if (!bo || !a.L || !a.cfgs) return fail(e, PP_ERR_ARG, "%s: null argument", who);
+    int st = check_batch(e, batch); if (st) return st;
+    if (!rig) {
+        if ((st = check_selection(e, who, "", a.cfgs))) return st;
+    } else {
+        const int32_t* source_frame = a.source_frame;
+        const int sources = a.sources;
+        if (!source_frame) return fail(e, PP_ERR_ARG, "%s: null argument", who);
+        if (sources < 1) return fail(e, PP_ERR_ARG, "%s: sources %d < 1", who, sources);
+        if (source_frame[0] != 0)
+            return fail(e, PP_ERR_ARG, "%s: source 0: source_frame %d, the frame map starts at frame 0", who, source_frame[0]);
+        for (int s = 1, run = 1; s < sources; ++s) {
+            const int prev = source_frame[s - 1], cur = source_frame[s];
+            if (cur < prev)
+                return fail(e, PP_ERR_ARG, "%s: source %d: source_frame %d < %d of the source before it (the frame map never decreases)",
+                            who, s, cur, prev);
+            if (cur > prev + 1)
+                return fail(e, PP_ERR_ARG, "%s: source %d: source_frame %d skips frame %d (every frame has at least one source)", who, s,
+                            cur, prev + 1);
+            run = cur == prev ? run + 1 : 1;
+            if (run > PP_RIG_MAX_SOURCES)
+                return fail(e, PP_ERR_ARG, "%s: source %d: frame %d has more than PP_RIG_MAX_SOURCES=%d sources", who, s, cur,
+                            PP_RIG_MAX_SOURCES);
+        }
+        if (source_frame[sources - 1] != batch - 1)
+            return fail(e, PP_ERR_ARG, "%s: source %d: source_frame %d, the frame map ends at frame batch - 1 = %d", who, sources - 1,
+                        source_frame[sources - 1], batch - 1);
     }
-    if (source_frame[sources - 1] != batch - 1)
-        return fail(e, PP_ERR_ARG, "%s: source %d: source_frame %d, the frame map ends at frame batch - 1 = %d", who, sources - 1,
-                    source_frame[sources - 1], batch - 1);
-    plan->nfeat = std::max(nfeat, 0);
-    plan->feats.assign((size_t)sources * plan->nfeat, IngFeat());
-    plan->frames.assign((size_t)sources, Frame());
-    plan->rig.assign((size_t)sources, RigSource());
+    plan->nfeat = nfeat;
+    plan->feats.assign((size_t)records * plan->nfeat, IngFeat());
+    plan->frames.assign((size_t)records, Frame());
+    plan->rig.assign(rig ? (size_t)records : 0, RigSource());
     plan->bound_off.assign((size_t)batch + 1, 0);
-    std::vector<int64_t> sum((size_t)batch, 0);
-    for (int s = 0; s < sources; ++s) {
+    std::vector<int64_t> sum((size_t)batch, 0);         // the frames' bounds: a rig's frame sums its sources'
+    for (int i = 0; i < records; ++i) {
+        const pp_ingest_config* c = rig ? a.cfgs + i : a.cfgs;
         char at[32];
-        snprintf(at, sizeof(at), "source %d: ", s);
-        const pp_ingest_config* c = cfgs + s;
-        if ((st = check_selection(e, who, at, c))) return st;
-        snprintf(at, sizeof(at), "source %d", s);
+        if (rig) {
+            snprintf(at, sizeof(at), "source %d: ", i);
+            if ((st = check_selection(e, who, at, c))) return st;
+        }
+        snprintf(at, sizeof(at), rig ? "source %d" : "frame %d", i);
         int64_t bound = 0;
-        Frame& f = plan->frames[(size_t)s];
-        if ((st = check_one(e, who, at, bo, s, L[s], c, &f, &bound))) return st;
-        if (plan->nfeat && (st = check_features_one(e, who, at, L[s], features + (size_t)s * nfeat, nfeat,
-                                                    plan->feats.data() + (size_t)s * nfeat))) return st;
-        const int b = source_frame[s];
+        Frame& f = plan->frames[(size_t)i];
+        if ((st = check_one(e, who, at, bo, i, a.L[i], c, &f, &bound))) return st;
+        if (plan->nfeat && (st = check_features_one(e, who, at, a.L[i], a.features + (size_t)i * nfeat, nfeat,
+                                                    plan->feats.data() + (size_t)i * nfeat))) return st;
+        const int b = rig ? a.source_frame[i] : i;
         sum[(size_t)b] += bound;
-        if (sum[(size_t)b] > e->NMAX)
+        if (sum[(size_t)b] > e->NMAX) {
+            if (!rig)
+                return fail(e, PP_ERR_ARG, "%s: frame %d: width %d x height %d keeps up to %lld points > max_points_per_frame=%d", who, b,
+                            a.L[i].width, a.L[i].height, (long long)bound, e->NMAX);
             return fail(e, PP_ERR_ARG, "%s: source %d: frame %d keeps up to %lld points with it (width %d x height %d: %lld) > "
-                        "max_points_per_frame=%d", who, s, b, (long long)sum[(size_t)b], L[s].width, L[s].height, (long long)bound,
+                        "max_points_per_frame=%d", who, i, b, (long long)sum[(size_t)b], a.L[i].width, a.L[i].height, (long long)bound,
                         e->NMAX);
-        RigSource& g = plan->rig[(size_t)s];
-        g.frame = b; g.first = c->first; g.decimate = c->decimate; g.reserved = 0;
-        memcpy(g.r, c->r, sizeof(g.r)); memcpy(g.r2, c->r2, sizeof(g.r2)); memcpy(g.lift, c->lift, sizeof(g.lift));
+        }
+        if (rig) {
+            RigSource& g = plan->rig[(size_t)i];
+            g.frame = b; g.first = c->first; g.decimate = c->decimate; g.reserved = 0;
+            memcpy(g.r, c->r, sizeof(g.r)); memcpy(g.r2, c->r2, sizeof(g.r2)); memcpy(g.lift, c->lift, sizeof(g.lift));
+        }
         plan->stride = std::max(plan->stride, f.nchunks);
     }
     for (int b = 0; b < batch; ++b) {
         plan->max_bound = std::max(plan->max_bound, (int)sum[(size_t)b]);
         plan->bound_off[(size_t)b + 1] = plan->bound_off[(size_t)b] + (int)sum[(size_t)b];
     }
-    plan->bytes = bo[sources] - bo[0];
-    if (plan->bytes > 0 && !data) return fail(e, PP_ERR_ARG, "%s: data is NULL", who);
+    plan->bytes = bo[records] - bo[0];
+    if (plan->bytes > 0 && !a.data) return fail(e, PP_ERR_ARG, "%s: data is NULL", who);
     return PP_OK;
 }
 
@@ -296,13 +278,27 @@ int ensure_rig(pp_engine* e) {
     return A.st;
 }
 
-inline void launch_frames(const IngestParams& p, hipStream_t s) { launch_ingest(p, s); }
-inline void launch_frames(const DepthIngestParams& p, hipStream_t s) { launch_depth_ingest(p, s); }
+// Where the records of a call travel: a plain call's through the handle's per-frame tables, a rig call's through the rig's
+// per-source ones; the ring slot's part of each pinned ring, and the device tables behind them.
+template <typename Frame>
+struct IngTables {
+    Frame* ring;                   // pinned, this slot's records
+    pp_engine::Ing::Slot* frames;  // device records
+    IngFeat* feat_ring;            // pinned, this slot's feature table
+    IngFeat* feats;                // device feature table
+};
+template <typename Frame>
+IngTables<Frame> ing_tables(pp_engine* e, bool rig, int slot, int nfeat) {
+    pp_engine::Ing& g = e->ing;
+    if (rig) return {(Frame*)(g.rig.h_frames + (size_t)slot * g.rig.sources_cap), g.rig.frames,
+                     g.rig.h_feats + (size_t)slot * g.rig.sources_cap * nfeat, g.rig.feats};
+    return {(Frame*)(g.h_ring + (size_t)slot * e->B), g.frames, g.h_feats + (size_t)slot * e->B * nfeat, g.feats};
+}
 
 // Flips to the other input buffer (as set_offsets does) and queues bytes -> staging -> points + offsets on `stream`
 // (the main stream, or the copy stream: it first waits for the pass that last read that buffer).  A plain call has one
-// record per frame and one configuration `c`; a rig call (plan.rig not empty, c == NULL) one record and one RigSource per
-// source, in the rig's own tables.
+// record per frame and one configuration `c`; a rig call (plan.rig not empty) one record and one RigSource per source, in
+// the rig's own tables.
 template <typename Frame>
 int enqueue_ingest(pp_engine* e, const uint8_t* data, const int64_t* bo, int batch, const pp_ingest_config* c,
                    const IngestPlanT<Frame>& plan, hipStream_t stream) {
@@ -325,9 +321,8 @@ int enqueue_ingest(pp_engine* e, const uint8_t* data, const int64_t* bo, int bat
     e->off_slot = (slot + 1) % pp_engine::OFF_RING;
     HIPCHK(e, hipEventSynchronize(e->off_ev[slot]));   // the copy that last used this slot has been consumed
     pp_engine::Ing::Rig& R = e->ing.rig;
-    Frame* ring = (Frame*)(rig ? R.h_frames + (size_t)slot * R.sources_cap : e->ing.h_ring + (size_t)slot * e->B);
-    pp_engine::Ing::Slot* d_frames = rig ? R.frames : e->ing.frames;
-    memcpy(ring, plan.frames.data(), (size_t)records * sizeof(Frame));
+    const IngTables<Frame> T = ing_tables<Frame>(e, rig, slot, plan.nfeat);
+    memcpy(T.ring, plan.frames.data(), (size_t)records * sizeof(Frame));
     // the kept counts are device values: everything behind this call is sized from the frames' bounds
     set_resident(e, batch, plan.bound_off.data(), plan.max_bound, false);
     e->ing.batch = batch;
@@ -335,49 +330,34 @@ int enqueue_ingest(pp_engine* e, const uint8_t* data, const int64_t* bo, int bat
     const int nb = flip_input(e);
     HIPCHK(e, hipStreamWaitEvent(stream, e->ev_read[nb], 0));
     if (plan.bytes) HIPCHK(e, hipMemcpyAsync(e->ing.raw, data + bo[0], (size_t)plan.bytes, hipMemcpyHostToDevice, stream));
-    HIPCHK(e, hipMemcpyAsync(d_frames, ring, (size_t)records * sizeof(Frame), hipMemcpyHostToDevice, stream));
+    HIPCHK(e, hipMemcpyAsync(T.frames, T.ring, (size_t)records * sizeof(Frame), hipMemcpyHostToDevice, stream));
     if (rig) {
         RigSource* src_ring = R.h_src + (size_t)slot * R.sources_cap;
         memcpy(src_ring, plan.rig.data(), (size_t)records * sizeof(RigSource));
         HIPCHK(e, hipMemcpyAsync(R.src, src_ring, (size_t)records * sizeof(RigSource), hipMemcpyHostToDevice, stream));
     }
     // the feature columns of a _fields call: a table beside the records, through the same ring slot on the same stream
-    IngFeat* const d_feats = rig ? R.feats : e->ing.feats;
     if (plan.nfeat) {
         const size_t nfe = (size_t)records * plan.nfeat;
-        IngFeat* feat_ring = rig ? R.h_feats + (size_t)slot * R.sources_cap * plan.nfeat : e->ing.h_feats + (size_t)slot * e->B * plan.nfeat;
-        memcpy(feat_ring, plan.feats.data(), nfe * sizeof(IngFeat));
-        HIPCHK(e, hipMemcpyAsync(d_feats, feat_ring, nfe * sizeof(IngFeat), hipMemcpyHostToDevice, stream));
+        memcpy(T.feat_ring, plan.feats.data(), nfe * sizeof(IngFeat));
+        HIPCHK(e, hipMemcpyAsync(T.feats, T.feat_ring, nfe * sizeof(IngFeat), hipMemcpyHostToDevice, stream));
     }
     HIPCHK(e, hipEventRecord(e->off_ev[slot], stream));
-    int* const chunk_cnt = e->ing.chunks;
-    int* const chunk_base = e->ing.chunks + (size_t)records * plan.stride;
-    const long long out_rows = (long long)e->B * e->NMAX;
+    IngestParamsT<Frame> p;
+    memset(&p, 0, sizeof(p));
+    p.raw = e->ing.raw; p.frames = (const Frame*)T.frames; p.records = records; p.batch = batch; p.stride = plan.stride;
     if (rig) {
-        RigParamsT<Frame> p;
-        memset(&p, 0, sizeof(p));
-        p.raw = e->ing.raw; p.frames = (const Frame*)d_frames; p.src = R.src;
-        p.sources = records; p.batch = batch; p.stride = plan.stride;
-        p.chunk_cnt = chunk_cnt; p.chunk_base = chunk_base;
-        p.src_finite = R.finite; p.src_kept = R.kept; p.out_base = R.out_base;
-        p.finite = e->ing.finite; p.kept = e->ing.kept; p.offsets = e->d_offsets; p.out = e->d_points;
-        p.out_rows = out_rows;
-        p.feats = d_feats; p.nfeat = plan.nfeat;
-        ProfScope ps(e, nullptr);
-        launch_rig_ingest(p, stream);
+        p.src = R.src; p.src_finite = R.finite; p.src_kept = R.kept; p.out_base = R.out_base;
     } else {
-        IngestParamsT<Frame> p;
-        memset(&p, 0, sizeof(p));
-        p.raw = e->ing.raw; p.frames = (const Frame*)d_frames; p.batch = batch; p.stride = plan.stride;
         p.first = c->first; p.decimate = c->decimate;
         memcpy(p.r, c->r, sizeof(p.r)); memcpy(p.r2, c->r2, sizeof(p.r2)); memcpy(p.lift, c->lift, sizeof(p.lift));
-        p.chunk_cnt = chunk_cnt; p.chunk_base = chunk_base;
-        p.finite = e->ing.finite; p.kept = e->ing.kept; p.offsets = e->d_offsets; p.out = e->d_points;
-        p.out_rows = out_rows;
-        p.feats = d_feats; p.nfeat = plan.nfeat;
-        ProfScope ps(e, nullptr);
-        launch_frames(p, stream);
     }
+    p.chunk_cnt = e->ing.chunks; p.chunk_base = e->ing.chunks + (size_t)records * plan.stride;
+    p.finite = e->ing.finite; p.kept = e->ing.kept; p.offsets = e->d_offsets; p.out = e->d_points;
+    p.out_rows = (long long)e->B * e->NMAX;
+    p.feats = T.feats; p.nfeat = plan.nfeat;
+    ProfScope ps(e, nullptr);
+    launch_ingest(p, stream);
     HIPCHK(e, hipGetLastError());
     return PP_OK;
 }
@@ -403,159 +383,121 @@ int ingest_sync(pp_engine* e, const char* who, const uint8_t* data, const int64_
     return PP_OK;
 }
 
+// Every exported ingest: the checks, then the synchronous tail or the asynchronous one (as pp_upload_points_async does).
+template <typename Layout>
+int ingest_call(pp_engine* e, const char* who, const IngestArgs<Layout>& a) {
+    if (!e) return PP_ERR_ARG;
+    (void)hipSetDevice(e->device);
+    if ((a.kind & ING_FIELDS) && a.nfeat < 0) return fail(e, PP_ERR_ARG, "%s: nfeat %d < 0", who, a.nfeat);
+    IngestPlanT<typename FrameOf<Layout>::type> plan;
+    int st = check_call(e, who, a, &plan);
+    if (st) return st;
+    if (!(a.kind & ING_ASYNC))
+        return ingest_sync(e, who, a.data, a.bo, a.batch, a.cfgs, plan, a.points_out, a.points_out_capacity);
+    prof_reset(e);
+    if ((st = enqueue_ingest(e, a.data, a.bo, a.batch, a.cfgs, plan, e->copy_stream))) return st;
+    return finish_async_upload(e, a.batch);
+}
+
+// the counts of the last ingest, once it has run: n of each table (NULL: not wanted)
+int read_counts(pp_engine* e, int32_t* finite_counts, const int* d_finite, int32_t* kept_counts, const int* d_kept, int n) {
+    (void)hipSetDevice(e->device);
+    HIPCHK(e, hipEventSynchronize(e->ev_up));        // an asynchronous ingest runs on the copy stream
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (finite_counts) HIPCHK(e, hipMemcpy(finite_counts, d_finite, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (kept_counts) HIPCHK(e, hipMemcpy(kept_counts, d_kept, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return PP_OK;
+}
+
+typedef IngestArgs<pp_pc2_layout> Pc2Args;
+typedef IngestArgs<pp_depth_layout> DepthArgs;
+
 }  // namespace
 
 extern "C" {
 
 int pp_ingest_pointcloud2(pp_handle e, const uint8_t* data, const int64_t* byte_offsets, const pp_pc2_layout* layouts,
                           int32_t batch, const pp_ingest_config* cfg, float* points_out, int64_t points_out_capacity) {
-    if (!e) return PP_ERR_ARG;
-    (void)hipSetDevice(e->device);
-    IngestPlan plan;
-    int st = check_ingest(e, "pp_ingest_pointcloud2", data, byte_offsets, layouts, batch, cfg, &plan);
-    if (st) return st;
-    return ingest_sync(e, "pp_ingest_pointcloud2", data, byte_offsets, batch, cfg, plan, points_out, points_out_capacity);
+    return ingest_call(e, "pp_ingest_pointcloud2", Pc2Args{data, byte_offsets, layouts, cfg, nullptr, 0, batch, nullptr, 0,
+                                                           points_out, points_out_capacity, 0});
 }
 
 int pp_ingest_pointcloud2_async(pp_handle e, const uint8_t* data_pinned, const int64_t* byte_offsets,
                                 const pp_pc2_layout* layouts, int32_t batch, const pp_ingest_config* cfg) {
-    if (!e) return PP_ERR_ARG;
-    (void)hipSetDevice(e->device);
-    IngestPlan plan;
-    int st = check_ingest(e, "pp_ingest_pointcloud2_async", data_pinned, byte_offsets, layouts, batch, cfg, &plan);
-    if (st) return st;
-    prof_reset(e);
-    if ((st = enqueue_ingest(e, data_pinned, byte_offsets, batch, cfg, plan, e->copy_stream))) return st;
-    return finish_async_upload(e, batch);     // as pp_upload_points_async does
+    return ingest_call(e, "pp_ingest_pointcloud2_async", Pc2Args{data_pinned, byte_offsets, layouts, cfg, nullptr, 0, batch,
+                                                                 nullptr, 0, nullptr, 0, ING_ASYNC});
 }
 
 int pp_ingest_depth(pp_handle e, const uint8_t* data, const int64_t* byte_offsets, const pp_depth_layout* layouts,
                     int32_t batch, const pp_ingest_config* cfg, float* points_out, int64_t points_out_capacity) {
-    if (!e) return PP_ERR_ARG;
-    (void)hipSetDevice(e->device);
-    DepthPlan plan;
-    int st = check_depth(e, "pp_ingest_depth", data, byte_offsets, layouts, batch, cfg, &plan);
-    if (st) return st;
-    return ingest_sync(e, "pp_ingest_depth", data, byte_offsets, batch, cfg, plan, points_out, points_out_capacity);
+    return ingest_call(e, "pp_ingest_depth", DepthArgs{data, byte_offsets, layouts, cfg, nullptr, 0, batch, nullptr, 0,
+                                                       points_out, points_out_capacity, 0});
 }
 
 int pp_ingest_depth_async(pp_handle e, const uint8_t* data_pinned, const int64_t* byte_offsets,
                           const pp_depth_layout* layouts, int32_t batch, const pp_ingest_config* cfg) {
-    if (!e) return PP_ERR_ARG;
-    (void)hipSetDevice(e->device);
-    DepthPlan plan;
-    int st = check_depth(e, "pp_ingest_depth_async", data_pinned, byte_offsets, layouts, batch, cfg, &plan);
-    if (st) return st;
-    prof_reset(e);
-    if ((st = enqueue_ingest(e, data_pinned, byte_offsets, batch, cfg, plan, e->copy_stream))) return st;
-    return finish_async_upload(e, batch);     // as pp_upload_points_async does
+    return ingest_call(e, "pp_ingest_depth_async", DepthArgs{data_pinned, byte_offsets, layouts, cfg, nullptr, 0, batch,
+                                                             nullptr, 0, nullptr, 0, ING_ASYNC});
 }
 
 int pp_ingest_rig_depth(pp_handle e, const uint8_t* data, const int64_t* byte_offsets, const pp_depth_layout* layouts,
                         const pp_ingest_config* cfgs, const int32_t* source_frame, int32_t sources, int32_t batch,
                         float* points_out, int64_t points_out_capacity) {
-    if (!e) return PP_ERR_ARG;
-    (void)hipSetDevice(e->device);
-    DepthPlan plan;
-    int st = check_rig(e, "pp_ingest_rig_depth", data, byte_offsets, layouts, cfgs, source_frame, sources, batch, &plan);
-    if (st) return st;
-    return ingest_sync(e, "pp_ingest_rig_depth", data, byte_offsets, batch, nullptr, plan, points_out, points_out_capacity);
+    return ingest_call(e, "pp_ingest_rig_depth", DepthArgs{data, byte_offsets, layouts, cfgs, source_frame, sources, batch,
+                                                           nullptr, 0, points_out, points_out_capacity, ING_RIG});
 }
 
 int pp_ingest_rig_depth_async(pp_handle e, const uint8_t* data_pinned, const int64_t* byte_offsets,
                               const pp_depth_layout* layouts, const pp_ingest_config* cfgs, const int32_t* source_frame,
                               int32_t sources, int32_t batch) {
-    if (!e) return PP_ERR_ARG;
-    (void)hipSetDevice(e->device);
-    DepthPlan plan;
-    int st = check_rig(e, "pp_ingest_rig_depth_async", data_pinned, byte_offsets, layouts, cfgs, source_frame, sources, batch, &plan);
-    if (st) return st;
-    prof_reset(e);
-    if ((st = enqueue_ingest(e, data_pinned, byte_offsets, batch, nullptr, plan, e->copy_stream))) return st;
-    return finish_async_upload(e, batch);     // as pp_upload_points_async does
+    return ingest_call(e, "pp_ingest_rig_depth_async", DepthArgs{data_pinned, byte_offsets, layouts, cfgs, source_frame, sources,
+                                                                 batch, nullptr, 0, nullptr, 0, ING_RIG | ING_ASYNC});
 }
 
 int pp_ingest_rig_pointcloud2(pp_handle e, const uint8_t* data, const int64_t* byte_offsets, const pp_pc2_layout* layouts,
                               const pp_ingest_config* cfgs, const int32_t* source_frame, int32_t sources, int32_t batch,
                               float* points_out, int64_t points_out_capacity) {
-    if (!e) return PP_ERR_ARG;
-    (void)hipSetDevice(e->device);
-    IngestPlan plan;
-    int st = check_rig(e, "pp_ingest_rig_pointcloud2", data, byte_offsets, layouts, cfgs, source_frame, sources, batch, &plan);
-    if (st) return st;
-    return ingest_sync(e, "pp_ingest_rig_pointcloud2", data, byte_offsets, batch, nullptr, plan, points_out, points_out_capacity);
+    return ingest_call(e, "pp_ingest_rig_pointcloud2", Pc2Args{data, byte_offsets, layouts, cfgs, source_frame, sources, batch,
+                                                               nullptr, 0, points_out, points_out_capacity, ING_RIG});
 }
 
 int pp_ingest_rig_pointcloud2_async(pp_handle e, const uint8_t* data_pinned, const int64_t* byte_offsets,
                                     const pp_pc2_layout* layouts, const pp_ingest_config* cfgs, const int32_t* source_frame,
                                     int32_t sources, int32_t batch) {
-    if (!e) return PP_ERR_ARG;
-    (void)hipSetDevice(e->device);
-    IngestPlan plan;
-    int st = check_rig(e, "pp_ingest_rig_pointcloud2_async", data_pinned, byte_offsets, layouts, cfgs, source_frame, sources, batch,
-                       &plan);
-    if (st) return st;
-    prof_reset(e);
-    if ((st = enqueue_ingest(e, data_pinned, byte_offsets, batch, nullptr, plan, e->copy_stream))) return st;
-    return finish_async_upload(e, batch);     // as pp_upload_points_async does
+    return ingest_call(e, "pp_ingest_rig_pointcloud2_async", Pc2Args{data_pinned, byte_offsets, layouts, cfgs, source_frame,
+                                                                     sources, batch, nullptr, 0, nullptr, 0, ING_RIG | ING_ASYNC});
 }
 
 int pp_ingest_pointcloud2_fields(pp_handle e, const uint8_t* data, const int64_t* byte_offsets, const pp_pc2_layout* layouts,
                                  int32_t batch, const pp_ingest_config* cfg, const pp_pc2_feature* features, int32_t nfeat,
                                  float* points_out, int64_t points_out_capacity) {
-    if (!e) return PP_ERR_ARG;
-    (void)hipSetDevice(e->device);
-    static const char* const who = "pp_ingest_pointcloud2_fields";
-    if (nfeat < 0) return fail(e, PP_ERR_ARG, "%s: nfeat %d < 0", who, nfeat);
-    IngestPlan plan;
-    int st = check_ingest(e, who, data, byte_offsets, layouts, batch, cfg, &plan, features, nfeat);
-    if (st) return st;
-    return ingest_sync(e, who, data, byte_offsets, batch, cfg, plan, points_out, points_out_capacity);
+    return ingest_call(e, "pp_ingest_pointcloud2_fields", Pc2Args{data, byte_offsets, layouts, cfg, nullptr, 0, batch, features,
+                                                                  nfeat, points_out, points_out_capacity, ING_FIELDS});
 }
 
 int pp_ingest_pointcloud2_fields_async(pp_handle e, const uint8_t* data_pinned, const int64_t* byte_offsets,
                                        const pp_pc2_layout* layouts, int32_t batch, const pp_ingest_config* cfg,
                                        const pp_pc2_feature* features, int32_t nfeat) {
-    if (!e) return PP_ERR_ARG;
-    (void)hipSetDevice(e->device);
-    static const char* const who = "pp_ingest_pointcloud2_fields_async";
-    if (nfeat < 0) return fail(e, PP_ERR_ARG, "%s: nfeat %d < 0", who, nfeat);
-    IngestPlan plan;
-    int st = check_ingest(e, who, data_pinned, byte_offsets, layouts, batch, cfg, &plan, features, nfeat);
-    if (st) return st;
-    prof_reset(e);
-    if ((st = enqueue_ingest(e, data_pinned, byte_offsets, batch, cfg, plan, e->copy_stream))) return st;
-    return finish_async_upload(e, batch);     // as pp_upload_points_async does
+    return ingest_call(e, "pp_ingest_pointcloud2_fields_async", Pc2Args{data_pinned, byte_offsets, layouts, cfg, nullptr, 0, batch,
+                                                                        features, nfeat, nullptr, 0, ING_FIELDS | ING_ASYNC});
 }
 
 int pp_ingest_rig_pointcloud2_fields(pp_handle e, const uint8_t* data, const int64_t* byte_offsets, const pp_pc2_layout* layouts,
                                      const pp_ingest_config* cfgs, const int32_t* source_frame, int32_t sources, int32_t batch,
                                      const pp_pc2_feature* features, int32_t nfeat, float* points_out,
                                      int64_t points_out_capacity) {
-    if (!e) return PP_ERR_ARG;
-    (void)hipSetDevice(e->device);
-    static const char* const who = "pp_ingest_rig_pointcloud2_fields";
-    if (nfeat < 0) return fail(e, PP_ERR_ARG, "%s: nfeat %d < 0", who, nfeat);
-    IngestPlan plan;
-    int st = check_rig(e, who, data, byte_offsets, layouts, cfgs, source_frame, sources, batch, &plan, features, nfeat);
-    if (st) return st;
-    return ingest_sync(e, who, data, byte_offsets, batch, nullptr, plan, points_out, points_out_capacity);
+    return ingest_call(e, "pp_ingest_rig_pointcloud2_fields",
+                       Pc2Args{data, byte_offsets, layouts, cfgs, source_frame, sources, batch, features, nfeat, points_out,
+                               points_out_capacity, ING_RIG | ING_FIELDS});
 }
 
 int pp_ingest_rig_pointcloud2_fields_async(pp_handle e, const uint8_t* data_pinned, const int64_t* byte_offsets,
                                            const pp_pc2_layout* layouts, const pp_ingest_config* cfgs,
                                            const int32_t* source_frame, int32_t sources, int32_t batch,
                                            const pp_pc2_feature* features, int32_t nfeat) {
-    if (!e) return PP_ERR_ARG;
-    (void)hipSetDevice(e->device);
-    static const char* const who = "pp_ingest_rig_pointcloud2_fields_async";
-    if (nfeat < 0) return fail(e, PP_ERR_ARG, "%s: nfeat %d < 0", who, nfeat);
-    IngestPlan plan;
-    int st = check_rig(e, who, data_pinned, byte_offsets, layouts, cfgs, source_frame, sources, batch, &plan, features, nfeat);
-    if (st) return st;
-    prof_reset(e);
-    if ((st = enqueue_ingest(e, data_pinned, byte_offsets, batch, nullptr, plan, e->copy_stream))) return st;
-    return finish_async_upload(e, batch);     // as pp_upload_points_async does
+    return ingest_call(e, "pp_ingest_rig_pointcloud2_fields_async",
+                       Pc2Args{data_pinned, byte_offsets, layouts, cfgs, source_frame, sources, batch, features, nfeat, nullptr, 0,
+                               ING_RIG | ING_FIELDS | ING_ASYNC});
 }
 
 int pp_ingest_rig_info(pp_handle e, int32_t* finite_counts, int32_t* kept_counts, int32_t sources) {
@@ -564,13 +506,7 @@ int pp_ingest_rig_info(pp_handle e, int32_t* finite_counts, int32_t* kept_counts
     if (e->ing.batch < 1 || e->ing.rig.sources < 1) return fail(e, PP_ERR_STATE, "pp_ingest_rig_info: the last ingest was no rig call");
     if (sources != e->ing.rig.sources)
         return fail(e, PP_ERR_ARG, "pp_ingest_rig_info: the last rig ingest had %d sources, sources is %d", e->ing.rig.sources, sources);
-    (void)hipSetDevice(e->device);
-    HIPCHK(e, hipEventSynchronize(e->ev_up));        // an asynchronous ingest runs on the copy stream
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    const size_t n = (size_t)sources * sizeof(int32_t);
-    if (finite_counts) HIPCHK(e, hipMemcpy(finite_counts, e->ing.rig.finite, n, hipMemcpyDeviceToHost));
-    if (kept_counts) HIPCHK(e, hipMemcpy(kept_counts, e->ing.rig.kept, n, hipMemcpyDeviceToHost));
-    return PP_OK;
+    return read_counts(e, finite_counts, e->ing.rig.finite, kept_counts, e->ing.rig.kept, sources);
 }
 
 int pp_ingest_info(pp_handle e, int32_t* finite_counts, int32_t* kept_counts, int32_t batch) {
@@ -578,13 +514,7 @@ int pp_ingest_info(pp_handle e, int32_t* finite_counts, int32_t* kept_counts, in
     if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_ingest_info: a training step is in flight");
     if (e->ing.batch < 1) return fail(e, PP_ERR_STATE, "pp_ingest_info: no ingest has run");
     if (batch != e->ing.batch) return fail(e, PP_ERR_ARG, "pp_ingest_info: the last ingest had %d frames, batch is %d", e->ing.batch, batch);
-    (void)hipSetDevice(e->device);
-    HIPCHK(e, hipEventSynchronize(e->ev_up));        // an asynchronous ingest runs on the copy stream
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    const size_t n = (size_t)batch * sizeof(int32_t);
-    if (finite_counts) HIPCHK(e, hipMemcpy(finite_counts, e->ing.finite, n, hipMemcpyDeviceToHost));
-    if (kept_counts) HIPCHK(e, hipMemcpy(kept_counts, e->ing.kept, n, hipMemcpyDeviceToHost));
-    return PP_OK;
+    return read_counts(e, finite_counts, e->ing.finite, kept_counts, e->ing.kept, batch);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
-// What the two live-camera ingests share on the device (ingest.hip: PointCloud2 messages; depth_ingest.hip: raw depth
-// images; rig_ingest.hip: several sources of either kind per frame): the chunking, the unaligned dword load, the per-record
-// decode and validity of both feeds, the scan of the chunk counts and the float64 camera -> lidar transform.  ingest.hip
-// and depth_ingest.hip wrap ingest_scan_frames in a kernel of their own, so each keeps its kernel name and its frame type.
+// What the live-camera ingests share on the device (ingest.hip; PointCloud2 messages, raw depth images, and rigs of several
+// sources of either kind per frame): the chunking, the unaligned dword load, the per-record decode and validity of both
+// feeds, the float64 camera -> lidar transform, and ONE body per phase -- ing_count_chunk, ing_scan_chunks,
+// ing_scatter_chunk -- written against three per-frame-type overloads (ing_records, ing_probe, ing_point).  The kernels of
+// ingest.hip only say where a chunk's record, selection, matrices and first output row come from.
 #pragma once
 
 #include "pp_common.h"
@@ -156,9 +157,76 @@ __device__ __forceinline__ void dep_deproject(const DepthFrame& f, int i, float 
     p[2] = (double)z;
 }
 
-// The body of a one-workgroup scan kernel of 16 waves (1024 threads): wave w scans the chunk counts of frames w, w + 16,
-// ... into chunk bases and the frame's finite (valid) and kept counts; thread 0 then sums the kept counts into the
-// offsets.  Frame: any per-frame record with an `nchunks` member.
+// ---- what the phase bodies need of either record type: records in all; validity of record i plus what its point is
+// computed from (a PointCloud2 record: its three coordinates; a depth pixel: its float32 z, so that only kept pixels pay
+// dep_deproject's divisions); the float64 camera-frame point of a kept record
+template <typename Frame> struct IngProbe;
+template <> struct IngProbe<IngFrame> { double p[3]; };
+template <> struct IngProbe<DepthFrame> { float z = 0.0f; };
+__device__ __forceinline__ int ing_records(const IngFrame& f) { return f.n_rec; }
+__device__ __forceinline__ int ing_records(const DepthFrame& f) { return f.n_pix; }
+__device__ __forceinline__ bool ing_probe(const uint8_t* base, const IngFrame& f, int i, IngProbe<IngFrame>& s) {
+    return ing_read(base, f, i, s.p);
+}
+__device__ __forceinline__ bool ing_probe(const uint8_t* base, const DepthFrame& f, int i, IngProbe<DepthFrame>& s) {
+    return dep_read(base, f, i, s.z);
+}
+__device__ __forceinline__ void ing_point(const IngFrame&, int, const IngProbe<IngFrame>& s, double p[3]) {
+    p[0] = s.p[0]; p[1] = s.p[1]; p[2] = s.p[2];
+}
+__device__ __forceinline__ void ing_point(const DepthFrame& f, int i, const IngProbe<DepthFrame>& s, double p[3]) {
+    dep_deproject(f, i, s.z, p);
+}
+
+// the chunk of this wave (grid.x * ING_WAVES chunks per record, grid.y records; the same for every lane of the wave)
+__device__ __forceinline__ int ing_wave_chunk() { return blockIdx.x * ING_WAVES + (threadIdx.x >> 6); }
+
+// The count body: one wave per chunk of ING_CHUNK records of record `y` (a frame, or a source of a rig): ballot + popcount
+// of the valid flags -> chunk_cnt[y][chunk].
+template <typename Frame>
+__device__ __forceinline__ void ing_count_chunk(const uint8_t* __restrict__ raw, const Frame* __restrict__ frames, int stride,
+                                                int* __restrict__ chunk_cnt) {
+    const int y = blockIdx.y;
+    const Frame f = frames[y];
+    const int lane = threadIdx.x & (PP_WAVE - 1);
+    const int c = ing_wave_chunk();
+    if (c >= f.nchunks) return;
+    const uint8_t* base = raw + f.byte_off;
+    const int n = ing_records(f);
+    int cnt = 0;
+#pragma unroll 2
+    for (int k = 0; k < ING_ITER; ++k) {
+        const int i = c * ING_CHUNK + k * PP_WAVE + lane;
+        IngProbe<Frame> s;
+        const bool ok = i < n && ing_probe(base, f, i, s);
+        cnt += __popcll(__ballot(ok));
+    }
+    if (lane == 0) chunk_cnt[(size_t)y * stride + c] = cnt;
+}
+
+// The scan body, for one wave: a record's chunk counts -> the valid records in front of each chunk; returns their sum
+// (the same in every lane).
+__device__ __forceinline__ int ing_scan_chunks(const int* __restrict__ cnt, int* __restrict__ base, size_t row, int nchunks) {
+    const int lane = threadIdx.x & (PP_WAVE - 1);
+    int carry = 0;
+    for (int c0 = 0; c0 < nchunks; c0 += PP_WAVE) {
+        const int c = c0 + lane;
+        const int v = c < nchunks ? cnt[row + c] : 0;
+        const int incl = wave_inclusive_scan(v);
+        if (c < nchunks) base[row + c] = carry + incl - v;
+        carry += __builtin_amdgcn_readlane(incl, PP_WAVE - 1);
+    }
+    return carry;
+}
+
+// points kept of `valid` under a selection
+__device__ __forceinline__ int ing_kept(int valid, int first, int decimate) {
+    return valid > first ? (valid - first + decimate - 1) / decimate : 0;
+}
+
+// The body of a one-workgroup scan kernel of 16 waves (1024 threads) of a plain call: wave w scans the chunk counts of
+// frames w, w + 16, ... into chunk bases and the frame's finite (valid) and kept counts; thread 0 then sums the kept
+// counts into the offsets.
 template <typename Frame>
 __device__ __forceinline__ void ingest_scan_frames(const Frame* __restrict__ frames, int batch, int stride, int first,
                                                    int decimate, const int* __restrict__ chunk_cnt,
@@ -166,18 +234,10 @@ __device__ __forceinline__ void ingest_scan_frames(const Frame* __restrict__ fra
                                                    int* __restrict__ kept, int* __restrict__ offsets) {
     const int lane = threadIdx.x & (PP_WAVE - 1), wave = threadIdx.x >> 6;
     for (int b = wave; b < batch; b += 16) {
-        const int nchunks = frames[b].nchunks;
-        int carry = 0;
-        for (int c0 = 0; c0 < nchunks; c0 += PP_WAVE) {
-            const int c = c0 + lane;
-            const int v = c < nchunks ? chunk_cnt[(size_t)b * stride + c] : 0;
-            const int incl = wave_inclusive_scan(v);
-            if (c < nchunks) chunk_base[(size_t)b * stride + c] = carry + incl - v;
-            carry += __builtin_amdgcn_readlane(incl, PP_WAVE - 1);
-        }
+        const int carry = ing_scan_chunks(chunk_cnt, chunk_base, (size_t)b * stride, frames[b].nchunks);
         if (lane == 0) {
             finite[b] = carry;
-            kept[b] = carry > first ? (carry - first + decimate - 1) / decimate : 0;
+            kept[b] = ing_kept(carry, first, decimate);
         }
     }
     __threadfence_block();
@@ -203,10 +263,56 @@ __device__ __forceinline__ void ing_transform(const double p[3], const IngXform&
     for (int j = 0; j < 3; ++j) out[j] = (float)(s[j] + x.lift[j]);
 }
 
-template <typename Params>
-inline IngXform ing_xform_of(const Params& p) {
+inline IngXform ing_xform_of(const double* r, const double* r2, const double* lift) {
     IngXform xf;
-    for (int i = 0; i < 9; ++i) { xf.r[i] = p.r[i]; xf.r2[i] = p.r2[i]; }
-    for (int i = 0; i < 3; ++i) xf.lift[i] = p.lift[i];
+    for (int i = 0; i < 9; ++i) { xf.r[i] = r[i]; xf.r2[i] = r2[i]; }
+    for (int i = 0; i < 3; ++i) xf.lift[i] = lift[i];
     return xf;
+}
+
+// the F - 3 feature columns of one record of a _fields call (none for F = 3)
+template <int N> struct IngCols { IngFeat c[N]; };
+template <> struct IngCols<0> {};
+
+// The scatter body: re-reads chunk c of record f; a valid record's rank is `run` (the valid records of f in front of the
+// chunk) + the valid lanes below it + the steps before; it is kept when rank >= first and (rank - first) % decimate == 0,
+// as row row0 + (rank - first) / decimate of `out`: its point, transformed, and for F > 3 (PointCloud2 only) its feature
+// columns behind it -- three dword stores for F = 3, one 16-byte store for F = 4.
+// row0 >= 0 (a rank never lowers a row: the callers' concern).
+// Everything is taken by value: by reference costs the PointCloud2 instantiations one more computation of the record's
+// address per step.
+template <typename Frame, int F>
+__device__ __forceinline__ void ing_scatter_chunk(const uint8_t* __restrict__ base, const Frame f, int c, int run, int first,
+                                                  int decimate, const IngXform xf, const IngCols<F - 3> ft, long long row0,
+                                                  float* __restrict__ out, long long out_rows) {
+    const int lane = threadIdx.x & (PP_WAVE - 1);
+    const int n = ing_records(f);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    // a PointCloud2 chunk's eight steps are unrolled (eight records' loads in flight), a depth chunk's are not: said here,
+    // so that a row width or a frame type more does not leave it to the unroller's size estimate
+    constexpr int steps_unrolled = std::is_same<Frame, IngFrame>::value ? ING_ITER : 1;
+#pragma unroll steps_unrolled
+    for (int k = 0; k < ING_ITER; ++k) {
+        const int i = c * ING_CHUNK + k * PP_WAVE + lane;
+        IngProbe<Frame> s;
+        const bool ok = i < n && ing_probe(base, f, i, s);
+        const unsigned long long m = __ballot(ok);
+        const int r = run + __popcll(m & below) - first;
+        run += __popcll(m);
+        if (ok && r >= 0 && r % decimate == 0) {
+            const long long row = row0 + r / decimate;
+            if (row < out_rows) {                  // (always: the host sized the call from the records' bounds)
+                double p[3];
+                float o[F];
+                ing_point(f, i, s, p);
+                ing_transform(p, xf, o);
+                if constexpr (F > 3) {
+                    const uint8_t* rec = ing_record(base, f, i);
+#pragma unroll
+                    for (int j = 0; j < F - 3; ++j) o[3 + j] = ing_feature(rec, ft.c[j], f.big_endian != 0);
+                }
+                ing_store_row<F>(out, row, o);
+            }
+        }
+    }
 }

@@ -529,70 +529,52 @@ struct IngFeat {
     int off, type;             // byte offset within a record; PointField code 1 INT8 ... 8 FLOAT64, or 0: constant
     double scale, bias;
 };
-// depth_ingest.hip: raw depth images (sensor_msgs/Image, 16UC1 or 32FC1) -> the same resident points and offsets
+// ingest.hip: raw depth images (sensor_msgs/Image, 16UC1 or 32FC1) -> the same resident points and offsets
 struct DepthFrame {            // one image of a call, as the kernels see it
     long long byte_off;        // its first byte within the staged bytes
     int width, n_pix;          // pixels per row (the true width: the deprojection needs row and column); pixels in all
     int row_step;              // bytes per row
     int tight;                 // pixel i sits at i * itemsize (no row padding): no division for its address
     int f32, big_endian;       // 32FC1 metres (else 16UC1 units of depth_scale); byte order
-    int nchunks;               // depth_chunks(n_pix)
+    int nchunks;               // ingest_chunks(n_pix)
     float fx, fy, ppx, ppy;    // pinhole intrinsics
     float depth_scale;         // metres per unit of a 16UC1 pixel
     float z_min, z_max;        // a pixel is valid only when z > z_min && z <= z_max
 };
-template <typename Frame>
-struct IngestParamsT {
-    const uint8_t* raw;        // the messages' bytes, staged on the device
-    const Frame* frames;       // [batch]
-    int batch, stride;         // stride: chunks of the largest frame (row length of the two chunk tables)
-    int first, decimate;
-    double r[9], r2[9], lift[3];
-    int* chunk_cnt;            // [batch][stride] finite records (valid pixels) per chunk
-    int* chunk_base;           // [batch][stride] finite records (valid pixels) of the frame in front of the chunk
-    int* finite;               // [batch] out: finite records (valid pixels)
-    int* kept;                 // [batch] out: points written
-    int* offsets;              // [batch + 1] out: the frames' row offsets in `out`
-    float* out;                // [sum kept][3 + nfeat]
-    long long out_rows;        // rows `out` holds
-    const IngFeat* feats;      // [batch][nfeat] feature columns behind x y z (PointCloud2 only), or nfeat == 0
-    int nfeat;
-};
-typedef IngestParamsT<IngFrame> IngestParams;
-typedef IngestParamsT<DepthFrame> DepthIngestParams;
-int ingest_chunks(int n_rec);
-void launch_ingest(const IngestParams& p, hipStream_t s);
-int depth_chunks(int n_pix);
-void launch_depth_ingest(const DepthIngestParams& p, hipStream_t s);
-// rig_ingest.hip: several sources (cameras) per frame, each under its own selection and transform; a frame's points are
-// its sources' kept points in source order, back to back.  The per-source records are IngFrame or DepthFrame as above.
+// ingest.hip, a rig call: several sources (cameras) per frame, each under its own selection and transform; a frame's
+// points are its sources' kept points in source order, back to back.  The per-source records are IngFrame or DepthFrame.
 struct RigSource {             // what a source has of its own besides its IngFrame / DepthFrame
     int frame;                 // the frame it belongs to (non-decreasing over the sources, every frame present)
     int first, decimate;
     int reserved;
     double r[9], r2[9], lift[3];
 };
+// One call of either feed.  A record is a frame of a plain call (records == batch, src NULL, one selection and one
+// transform for all of them: first ... lift) or a source of a rig call (src: the sources' own, and the rig-only outputs).
 template <typename Frame>
-struct RigParamsT {
-    const uint8_t* raw;        // the sources' bytes, staged on the device
-    const Frame* frames;       // [sources] one record per SOURCE
-    const RigSource* src;      // [sources]
-    int sources, batch, stride;   // stride: chunks of the largest source (row length of the two chunk tables)
-    int* chunk_cnt;            // [sources][stride] finite records (valid pixels) per chunk
-    int* chunk_base;           // [sources][stride] finite records (valid pixels) of the source in front of the chunk
-    int* src_finite;           // [sources] out: finite records (valid pixels)
-    int* src_kept;             // [sources] out: points written
-    int* out_base;             // [sources] out: kept points of the earlier sources of its frame
-    int* finite;               // [batch] out: the frames' sums of src_finite
-    int* kept;                 // [batch] out: the frames' sums of src_kept
+struct IngestParamsT {
+    const uint8_t* raw;        // the records' bytes, staged on the device
+    const Frame* frames;       // [records]
+    const RigSource* src;      // [records], or NULL: a plain call
+    int records, batch, stride;   // stride: chunks of the largest record (row length of the two chunk tables)
+    int first, decimate;       // a plain call
+    double r[9], r2[9], lift[3];
+    int* chunk_cnt;            // [records][stride] finite records (valid pixels) per chunk
+    int* chunk_base;           // [records][stride] finite records (valid pixels) of the record in front of the chunk
+    int* src_finite;           // [records] out, rig only: finite records (valid pixels) of each source
+    int* src_kept;             // [records] out, rig only: points written of each source
+    int* out_base;             // [records] out, rig only: kept points of the earlier sources of its frame
+    int* finite;               // [batch] out: finite records (valid pixels), a rig's summed over the frame's sources
+    int* kept;                 // [batch] out: points written, likewise
     int* offsets;              // [batch + 1] out: the frames' row offsets in `out`
     float* out;                // [sum kept][3 + nfeat]
     long long out_rows;        // rows `out` holds
-    const IngFeat* feats;      // [sources][nfeat] feature columns behind x y z (PointCloud2 only), or nfeat == 0
+    const IngFeat* feats;      // [records][nfeat] feature columns behind x y z (PointCloud2 only), or nfeat == 0
     int nfeat;
 };
-void launch_rig_ingest(const RigParamsT<IngFrame>& p, hipStream_t s);
-void launch_rig_ingest(const RigParamsT<DepthFrame>& p, hipStream_t s);
+int ingest_chunks(int n);      // chunks of a record of n points or pixels
+void launch_ingest(const IngestParamsT<IngFrame>& p, hipStream_t s);
+void launch_ingest(const IngestParamsT<DepthFrame>& p, hipStream_t s);
 
 // frustum_crop.hip: the resident frames cropped to the camera frustum (frustum.py), frames compacted in order
 struct CropParams {

@@ -118,6 +118,8 @@ class MessageStaging:
     `ingest.FeatureField`s, or None): resolved against every message's fields here and kept -- `.features`, the ctypes array
     of pp_pc2_feature [batch][nfeat], and `.nfeat`; the ingest then writes rows of 3 + nfeat floats."""
 
+    _records = "fields"             # the public attribute that holds the staged tuples without their data (tuples())
+
     def __init__(self, lib, msgs, features=None):
         from . import ingest
         tuples = [ingest.as_tuple(m) for m in msgs]
@@ -132,6 +134,11 @@ class MessageStaging:
         for b, buf in enumerate(bufs):
             self.bytes[self.byte_offsets[b]:self.byte_offsets[b] + buf.size] = buf
         self._users = weakref.WeakSet()
+
+    def tuples(self):
+        """The staged records as the tuples they were packed from (`ingest.as_tuple` / `ingest.image_as_tuple`), their
+        data the pinned bytes as they are now."""
+        return [(self.bytes[self.byte_offsets[b]:self.byte_offsets[b + 1]],) + tuple(g) for b, g in enumerate(getattr(self, self._records))]
 
     def close(self):
         """Frees the buffer after every engine that was fed from it has finished the pass that reads it.  As with
@@ -159,6 +166,8 @@ class DepthStaging(MessageStaging):
     `.images`: their (width, height, step, encoding, is_bigendian).  The intrinsics are given with each ingest, so
     there is no `.layouts`."""
 
+    _records = "images"
+
     def __init__(self, lib, images):
         from . import ingest
         tuples = [ingest.image_as_tuple(m) for m in images]
@@ -168,16 +177,43 @@ class DepthStaging(MessageStaging):
         self._fill(lib, bufs)
 
 
-def _pack_images(tuples):
-    """[(data, width, height, step, encoding, is_bigendian)] -> (byte_offsets [B + 1] int64, the images' byte views cut to
-    height * step)."""
+def _pack(tuples, nbytes):
+    """Records (data first) -> (byte_offsets [B + 1] int64, their byte views cut to nbytes[b])."""
     offs = np.zeros((len(tuples) + 1,), np.int64)
     bufs = []
     for b, t in enumerate(tuples):
-        buf = np.frombuffer(t[0], dtype=np.uint8)[:t[2] * t[3]]
-        bufs.append(buf)
-        offs[b + 1] = offs[b] + buf.size
+        bufs.append(np.frombuffer(t[0], dtype=np.uint8)[:nbytes[b]])
+        offs[b + 1] = offs[b] + bufs[b].size
     return offs, bufs
+
+
+def _concat(bufs, offs):
+    """The records' bytes as one array for a synchronous call (a single record: its own view; nothing: one zero byte)."""
+    return (bufs[0] if len(bufs) == 1 else np.concatenate(bufs)) if bufs and offs[-1] else np.zeros((1,), np.uint8)
+
+
+def _fill_layouts(ctype, keys, lays):
+    """The ctypes array of `ctype` (pp_pc2_layout / pp_depth_layout) of a call's records from their layout dicts."""
+    arr = (ctype * max(len(lays), 1))()
+    for b, lay in enumerate(lays):
+        for k in keys:
+            setattr(arr[b], k, lay[k])
+    return arr
+
+
+def _pack_images(tuples):
+    """[(data, width, height, step, encoding, is_bigendian)] -> (byte_offsets [B + 1] int64, the images' byte views cut to
+    height * step)."""
+    return _pack(tuples, [t[2] * t[3] for t in tuples])
+
+
+def _pack_messages(tuples):
+    """[(data, width, height, point_step, row_step, fields, is_bigendian)] -> (byte_offsets [B + 1] int64, ctypes array
+    of pp_pc2_layout, the messages' byte views cut to height * row_step)."""
+    from . import ingest
+    lays = [ingest.layout_of(t) for t in tuples]
+    offs, bufs = _pack(tuples, [lay["height"] * lay["row_step"] for lay in lays])
+    return offs, _fill_layouts(_lib.PPPc2Layout, ingest.LAYOUT_KEYS, lays), bufs
 
 
 def _depth_layouts(tuples, intrinsics, depth_scale, z_min, z_max):
@@ -187,50 +223,53 @@ def _depth_layouts(tuples, intrinsics, depth_scale, z_min, z_max):
     per_frame = isinstance(intrinsics, list) and not (len(intrinsics) in (4, 9) and all(np.ndim(v) == 0 for v in intrinsics))
     if per_frame and len(intrinsics) != len(tuples):
         raise ValueError(f"{len(intrinsics)} sets of intrinsics for {len(tuples)} images")
-    layouts = (_lib.PPDepthLayout * max(len(tuples), 1))()
-    for b, t in enumerate(tuples):
-        lay = ingest.depth_layout_of(t, intrinsics[b] if per_frame else intrinsics, depth_scale, z_min, z_max)
-        for k in ingest.DEPTH_LAYOUT_KEYS:
-            setattr(layouts[b], k, lay[k])
-    return layouts
+    return _fill_layouts(_lib.PPDepthLayout, ingest.DEPTH_LAYOUT_KEYS,
+                         [ingest.depth_layout_of(t, intrinsics[b] if per_frame else intrinsics, depth_scale, z_min, z_max)
+                          for b, t in enumerate(tuples)])
 
 
-def _pack_messages(tuples):
-    """[(data, width, height, point_step, row_step, fields, is_bigendian)] -> (byte_offsets [B + 1] int64, ctypes array
-    of pp_pc2_layout, the messages' byte views cut to height * row_step)."""
+def _rig_depth_layouts(tuples, rig):
+    """The ctypes array of pp_depth_layout of a rig call's images (frames back to back, a frame's cameras in rig order)."""
     from . import ingest
-    layouts = (_lib.PPPc2Layout * max(len(tuples), 1))()
-    offs = np.zeros((len(tuples) + 1,), np.int64)
-    bufs = []
-    for b, t in enumerate(tuples):
-        lay = ingest.layout_of(t)
-        for k in ingest.LAYOUT_KEYS:
-            setattr(layouts[b], k, lay[k])
-        buf = np.frombuffer(t[0], dtype=np.uint8)[:lay["height"] * lay["row_step"]]
-        bufs.append(buf)
-        offs[b + 1] = offs[b] + buf.size
-    return offs, layouts, bufs
+    n = len(rig)
+    if any(k is None for k in rig.intrinsics):
+        raise ValueError("a rig of depth cameras needs intrinsics (CameraRig(mounts, intrinsics=...))")
+    return _fill_layouts(_lib.PPDepthLayout, ingest.DEPTH_LAYOUT_KEYS,
+                         [ingest.depth_layout_of(t, rig.intrinsics[s % n], rig.depth_scale[s % n], rig.z_min[s % n], rig.z_max[s % n])
+                          for s, t in enumerate(tuples)])
+
+
+def _fill_config(c, first, decimate, r, r2, lift):
+    """One pp_ingest_config: the selection, the two 3 x 3 matrices and the three lift terms."""
+    c.first, c.decimate = int(first), int(decimate)
+    c.r[:] = np.asarray(r, np.float64).reshape(-1).tolist()
+    c.r2[:] = np.asarray(r2, np.float64).reshape(-1).tolist()
+    c.lift[:] = [float(v) for v in lift]
+    return c
 
 
 def _ingest_config(first, decimate, lift, mount=None):
     """pp_ingest_config of a plain call.  mount None: the reference's RealSense matrices and [0, 0, lift] (lift None: the
     sensor height); else the `ingest.Mount`'s own r, r2 and lift (a lidar: Mount(np.eye(3), np.eye(3), 0.0))."""
     from . import ingest
-    c = _lib.PPIngestConfig()
-    c.first, c.decimate = int(first), int(decimate)
     if mount is None:
-        r, r2 = ingest._matrices()
-        lift3 = [0.0, 0.0, float(ingest.SENSOR_HEIGHT if lift is None else lift)]
-    else:
-        if not isinstance(mount, ingest.Mount):
-            raise ValueError("mount must be an ingest.Mount (Mount.realsense(), Mount.from_matrix(T), Mount(r, r2, lift))")
-        if lift is not None:
-            raise ValueError("lift and mount are both given: the mount carries its own lift")
-        r, r2, lift3 = mount.r, mount.r2, [float(v) for v in mount.lift]
-    c.r[:] = [float(v) for v in np.asarray(r, np.float64).reshape(-1)]
-    c.r2[:] = [float(v) for v in np.asarray(r2, np.float64).reshape(-1)]
-    c.lift[:] = lift3
-    return c
+        return _fill_config(_lib.PPIngestConfig(), first, decimate, *ingest._matrices(),
+                            [0.0, 0.0, ingest.SENSOR_HEIGHT if lift is None else lift])
+    if not isinstance(mount, ingest.Mount):
+        raise ValueError("mount must be an ingest.Mount (Mount.realsense(), Mount.from_matrix(T), Mount(r, r2, lift))")
+    if lift is not None:
+        raise ValueError("lift and mount are both given: the mount carries its own lift")
+    return _fill_config(_lib.PPIngestConfig(), first, decimate, mount.r, mount.r2, mount.lift)
+
+
+def _rig_configs(rig, batch):
+    """The ctypes array of pp_ingest_config of a rig call: one per source, the rig's cameras repeated for every frame."""
+    n = len(rig)
+    cfgs = (_lib.PPIngestConfig * (n * batch))()
+    for s in range(n * batch):
+        m = rig.mounts[s % n]
+        _fill_config(cfgs[s], rig.first[s % n], rig.decimate[s % n], m.r, m.r2, m.lift)
+    return cfgs
 
 
 def _feature_table(tuples, per_message):
@@ -252,32 +291,28 @@ def _feature_table(tuples, per_message):
     return arr, nf
 
 
-def _rig_configs(rig, batch):
-    """The ctypes array of pp_ingest_config of a rig call: one per source, the rig's cameras repeated for every frame."""
-    n = len(rig)
-    cfgs = (_lib.PPIngestConfig * (n * batch))()
-    for s in range(n * batch):
-        c, m = cfgs[s], rig.mounts[s % n]
-        c.first, c.decimate = int(rig.first[s % n]), int(rig.decimate[s % n])
-        c.r[:] = [float(v) for v in m.r.reshape(-1)]
-        c.r2[:] = [float(v) for v in m.r2.reshape(-1)]
-        c.lift[:] = [float(v) for v in m.lift]
-    return cfgs
+def _rig_feature_table(tuples, rig, features):
+    """`_feature_table` of a rig call's messages (frames back to back, a frame's cameras in rig order)."""
+    from . import ingest
+    if features is None:
+        return None, None
+    per = ingest.rig_features(features, len(rig))
+    return _feature_table(tuples, [per[s % len(rig)] for s in range(len(tuples))])
 
 
-def _rig_depth_layouts(tuples, rig):
-    """The ctypes array of pp_depth_layout of a rig call's images (frames back to back, a frame's cameras in rig order)."""
+def _tap_rows(tuples, first, decimate):
+    """The points the parity tap of a plain call must hold: the sum of its records' `ingest.kept_bound`s (first / decimate
+    held to what kept_bound takes: the library refuses such a call)."""
+    from . import ingest
+    first, decimate = max(int(first), 0), max(int(decimate), 1)
+    return sum(ingest.kept_bound(t[1], t[2], first, decimate) for t in tuples)
+
+
+def _rig_tap_rows(tuples, rig):
+    """The same for a rig call's records (frames back to back, a frame's cameras in rig order)."""
     from . import ingest
     n = len(rig)
-    if any(k is None for k in rig.intrinsics):
-        raise ValueError("a rig of depth cameras needs intrinsics (CameraRig(mounts, intrinsics=...))")
-    layouts = (_lib.PPDepthLayout * max(len(tuples), 1))()
-    for s, t in enumerate(tuples):
-        c = s % n
-        lay = ingest.depth_layout_of(t, rig.intrinsics[c], rig.depth_scale[c], rig.z_min[c], rig.z_max[c])
-        for k in ingest.DEPTH_LAYOUT_KEYS:
-            setattr(layouts[s], k, lay[k])
-    return layouts
+    return int(sum(ingest.kept_bound(t[1], t[2], rig.first[s % n], rig.decimate[s % n]) for s, t in enumerate(tuples)))
 
 
 class RigDepthStaging(DepthStaging):
@@ -301,15 +336,6 @@ class RigMessageStaging(MessageStaging):
         super().__init__(lib, flat)
         if features is not None:
             self.features, self.nfeat = _rig_feature_table([ingest.as_tuple(m) for m in flat], rig, features)
-
-
-def _rig_feature_table(tuples, rig, features):
-    """`_feature_table` of a rig call's messages (frames back to back, a frame's cameras in rig order)."""
-    from . import ingest
-    if features is None:
-        return None, None
-    per = ingest.rig_features(features, len(rig))
-    return _feature_table(tuples, [per[s % len(rig)] for s in range(len(tuples))])
 
 
 class Engine:
@@ -775,7 +801,37 @@ class Engine:
         self._check(self._lib.pp_frustum_crop_info(self._h, _ptr(kept), B), "pp_frustum_crop_info")
         return kept[:B]
 
-    # ---- live-camera ingest (pp_ingest_pointcloud2*; ingest.py states the rule) ----
+    # ---- live-camera ingest (pp_ingest_*; ingest.py states the rule) ----
+    def _ingest_sync(self, name, args, batch, cap, nf, cameras=None):
+        """One synchronous pp_ingest_* call.  args: what the call takes between the handle and the parity tap; cap: the
+        points the tap must hold, or None for no tap; nf: feature columns (None: x y z only); cameras: of a rig call.
+        Returns the tap's points, one [n_b, 3 + nf] float32 array per frame, or None."""
+        pts = None if cap is None else np.empty((max(cap, 1), 3 + (nf or 0)), np.float32)
+        self._check(getattr(self._lib, name)(self._h, *args, _ptr(pts), ctypes.c_int64(cap or 0)), name)
+        self._offsets = None          # the resident frames' sizes are device values (ingest_info reads them back)
+        self._ing_batch = batch
+        if cameras is not None:       # (a plain call leaves the last rig's shape: the library refuses ingest_rig_info then)
+            self._rig_shape = (batch, cameras)
+        if pts is None:
+            return None
+        off = np.concatenate([[0], np.cumsum(self.ingest_info()["kept"])])
+        return [pts[off[b]:off[b + 1]].copy() for b in range(batch)]
+
+    def _ingest_async(self, name, staging, args, batch, cameras=None):
+        """One pp_ingest_*_async call from a staging.  args: what the call takes behind the bytes and their offsets."""
+        self._check(getattr(self._lib, name)(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets), *args), name)
+        self._offsets = None
+        self._ing_batch = batch
+        if cameras is not None:
+            self._rig_shape = (batch, cameras)
+        staging._users.add(self)
+        self._staged.append(staging)      # kept alive while a copy may still read it (see upload_async)
+
+    def _detect_after_ingest(self, batch, rect, trv2c, on_numeric):
+        if rect is not None:
+            self.set_calib(rect, trv2c, batch)
+        return self._detect_resident(on_numeric)
+
     def ingest_pointcloud2(self, msgs, first=1, decimate=4, lift=None, return_points=False, features=None, mount=None):
         """Raw sensor_msgs/PointCloud2 messages -> the engine's resident frames, on the GPU: x y z out of the bytes,
         non-finite records dropped, every `decimate`-th survivor from index `first`, camera axes turned into lidar axes
@@ -794,27 +850,12 @@ class Engine:
         from . import ingest
         tuples = [ingest.as_tuple(m) for m in msgs]
         offs, layouts, bufs = _pack_messages(tuples)
-        data = (bufs[0] if len(bufs) == 1 else np.concatenate(bufs)) if bufs and offs[-1] else np.zeros((1,), np.uint8)
         cfg = _ingest_config(first, decimate, lift, mount)
         table, nf = _feature_table(tuples, None if features is None else ingest.rig_features(features, len(tuples)))
-        pts, cap = None, 0
-        if return_points:
-            cap = sum(ingest.kept_bound(t[1], t[2], max(int(first), 0), max(int(decimate), 1)) for t in tuples)
-            pts = np.empty((max(cap, 1), 3 + (nf or 0)), np.float32)
-        if table is None:
-            self._check(self._lib.pp_ingest_pointcloud2(self._h, _ptr(data), _ptr(offs), layouts, len(tuples),
-                                                        ctypes.byref(cfg), _ptr(pts), ctypes.c_int64(cap)),
-                        "pp_ingest_pointcloud2")
-        else:
-            self._check(self._lib.pp_ingest_pointcloud2_fields(self._h, _ptr(data), _ptr(offs), layouts, len(tuples),
-                                                               ctypes.byref(cfg), table, nf, _ptr(pts), ctypes.c_int64(cap)),
-                        "pp_ingest_pointcloud2_fields")
-        self._offsets = None          # the resident frames' sizes are device values (ingest_info reads them back)
-        self._ing_batch = len(tuples)
-        if not return_points:
-            return None
-        off = np.concatenate([[0], np.cumsum(self.ingest_info()["kept"])])
-        return [pts[off[b]:off[b + 1]].copy() for b in range(len(tuples))]
+        name, args = "pp_ingest_pointcloud2", (_ptr(_concat(bufs, offs)), _ptr(offs), layouts, len(tuples), ctypes.byref(cfg))
+        if table is not None:
+            name, args = "pp_ingest_pointcloud2_fields", args + (table, nf)
+        return self._ingest_sync(name, args, len(tuples), _tap_rows(tuples, first, decimate) if return_points else None, nf)
 
     def ingest_info(self):
         """Per frame of the last ingest: `finite` records and points `kept` (pp_ingest_info; waits for the ingest)."""
@@ -837,28 +878,18 @@ class Engine:
         before the sync() that follows the detect_async() consuming these frames.  Mixes freely with upload_async.
         features / mount: None -> the staging's own (staging_pointcloud2(msgs, features=..., mount=...)); given here, they
         are resolved against the staged messages' fields for this call (pp_ingest_pointcloud2_fields_async)."""
+        from . import ingest
         B = staging.byte_offsets.shape[0] - 1
         if mount is None and lift is None:
             mount = getattr(staging, "mount", None)
         cfg = _ingest_config(first, decimate, lift, mount)
         table, nf = staging.features, staging.nfeat
         if features is not None:
-            tuples = [(staging.bytes[staging.byte_offsets[b]:staging.byte_offsets[b + 1]],) + tuple(g)
-                      for b, g in enumerate(staging.fields)]
-            from . import ingest
-            table, nf = _feature_table(tuples, ingest.rig_features(features, B))
-        if table is None:
-            self._check(self._lib.pp_ingest_pointcloud2_async(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets),
-                                                              staging.layouts, B, ctypes.byref(cfg)),
-                        "pp_ingest_pointcloud2_async")
-        else:
-            self._check(self._lib.pp_ingest_pointcloud2_fields_async(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets),
-                                                                     staging.layouts, B, ctypes.byref(cfg), table, nf),
-                        "pp_ingest_pointcloud2_fields_async")
-        self._offsets = None
-        self._ing_batch = staging.byte_offsets.shape[0] - 1
-        staging._users.add(self)
-        self._staged.append(staging)      # kept alive while a copy may still read it (see upload_async)
+            table, nf = _feature_table(staging.tuples(), ingest.rig_features(features, B))
+        name, args = "pp_ingest_pointcloud2_async", (staging.layouts, B, ctypes.byref(cfg))
+        if table is not None:
+            name, args = "pp_ingest_pointcloud2_fields_async", args + (table, nf)
+        self._ingest_async(name, staging, args, B)
 
     def detect_pointcloud2(self, msgs, rect=None, trv2c=None, on_numeric="f32", features=None, mount=None, first=1, decimate=4):
         """ingest_pointcloud2 + detect_async + sync + detections: `detect` for raw camera messages (the reference's
@@ -866,11 +897,9 @@ class Engine:
         ingest_pointcloud2 (a lidar feeding a 4-feature model: features=[FeatureField("intensity")],
         mount=Mount(np.eye(3), np.eye(3), 0.0), first=0, decimate=1)."""
         self.ingest_pointcloud2(msgs, first=first, decimate=decimate, features=features, mount=mount)
-        if rect is not None:
-            self.set_calib(rect, trv2c, len(msgs))
-        return self._detect_resident(on_numeric)
+        return self._detect_after_ingest(len(msgs), rect, trv2c, on_numeric)
 
-    # ---- depth-image ingest (pp_ingest_depth*; ingest.py states the rule, DESIGN 7.1m) ----
+    # ---- depth-image ingest (pp_ingest_depth*) ----
     def ingest_depth(self, images, intrinsics, first=1, decimate=4, lift=None, depth_scale=0.001, z_min=0.0, z_max=np.inf,
                      return_points=False):
         """Raw depth images (sensor_msgs/Image: 16UC1 / mono16 units of `depth_scale`, or 32FC1 metres) -> the engine's
@@ -886,20 +915,9 @@ class Engine:
         tuples = [ingest.image_as_tuple(m) for m in images]
         layouts = _depth_layouts(tuples, intrinsics, depth_scale, z_min, z_max)
         offs, bufs = _pack_images(tuples)
-        data = (bufs[0] if len(bufs) == 1 else np.concatenate(bufs)) if bufs and offs[-1] else np.zeros((1,), np.uint8)
-        cfg = _ingest_config(first, decimate, ingest.SENSOR_HEIGHT if lift is None else lift)
-        pts, cap = None, 0
-        if return_points:
-            cap = sum(ingest.depth_kept_bound(t[1], t[2], max(int(first), 0), max(int(decimate), 1)) for t in tuples)
-            pts = np.empty((max(cap, 1), 3), np.float32)
-        self._check(self._lib.pp_ingest_depth(self._h, _ptr(data), _ptr(offs), layouts, len(tuples), ctypes.byref(cfg),
-                                              _ptr(pts), ctypes.c_int64(cap)), "pp_ingest_depth")
-        self._offsets = None          # the resident frames' sizes are device values (ingest_info reads them back)
-        self._ing_batch = len(tuples)
-        if not return_points:
-            return None
-        off = np.concatenate([[0], np.cumsum(self.ingest_info()["kept"])])
-        return [pts[off[b]:off[b + 1]].copy() for b in range(len(tuples))]
+        cfg = _ingest_config(first, decimate, lift)
+        return self._ingest_sync("pp_ingest_depth", (_ptr(_concat(bufs, offs)), _ptr(offs), layouts, len(tuples), ctypes.byref(cfg)),
+                                 len(tuples), _tap_rows(tuples, first, decimate) if return_points else None, None)
 
     def staging_depth(self, images):
         """Packs depth images into a page-locked DepthStaging for ingest_depth_async (the counterpart of staging())."""
@@ -909,47 +927,18 @@ class Engine:
                            z_max=np.inf):
         """ingest_depth without waiting (pp_ingest_depth_async), from a DepthStaging: as ingest_pointcloud2_async, and
         mixes freely with it and with upload_async."""
-        from . import ingest
-        tuples = [(staging.bytes[staging.byte_offsets[b]:staging.byte_offsets[b + 1]],) + tuple(g)
-                  for b, g in enumerate(staging.images)]
+        tuples = staging.tuples()
         layouts = _depth_layouts(tuples, intrinsics, depth_scale, z_min, z_max)
-        cfg = _ingest_config(first, decimate, ingest.SENSOR_HEIGHT if lift is None else lift)
-        self._check(self._lib.pp_ingest_depth_async(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets), layouts,
-                                                    len(tuples), ctypes.byref(cfg)), "pp_ingest_depth_async")
-        self._offsets = None
-        self._ing_batch = len(tuples)
-        staging._users.add(self)
-        self._staged.append(staging)      # kept alive while a copy may still read it (see upload_async)
+        cfg = _ingest_config(first, decimate, lift)
+        self._ingest_async("pp_ingest_depth_async", staging, (layouts, len(tuples), ctypes.byref(cfg)), len(tuples))
 
     def detect_depth(self, images, intrinsics, rect=None, trv2c=None, on_numeric="f32"):
         """ingest_depth + detect_async + sync + detections: `detect_pointcloud2` for the depth images the messages are
         computed from.  rect / trv2c / on_numeric as `detect`."""
         self.ingest_depth(images, intrinsics)
-        if rect is not None:
-            self.set_calib(rect, trv2c, len(images))
-        return self._detect_resident(on_numeric)
+        return self._detect_after_ingest(len(images), rect, trv2c, on_numeric)
 
-    # ---- camera-rig ingest (pp_ingest_rig_*; ingest.py states the rule, DESIGN 7.1n) ----
-    def _ingest_rig(self, name, data, offs, layouts, rig, fmap, batch, bounds, return_points, table=None, nf=None):
-        pts, cap = None, 0
-        if return_points:
-            cap = int(sum(bounds))
-            pts = np.empty((max(cap, 1), 3 + (nf or 0)), np.float32)
-        cfgs = _rig_configs(rig, batch)
-        if table is None:
-            self._check(getattr(self._lib, name)(self._h, _ptr(data), _ptr(offs), layouts, cfgs, _ptr(fmap), len(fmap), batch,
-                                                 _ptr(pts), ctypes.c_int64(cap)), name)
-        else:
-            name += "_fields"
-            self._check(getattr(self._lib, name)(self._h, _ptr(data), _ptr(offs), layouts, cfgs, _ptr(fmap), len(fmap), batch,
-                                                 table, nf, _ptr(pts), ctypes.c_int64(cap)), name)
-        self._offsets = None          # the resident frames' sizes are device values (ingest_info reads them back)
-        self._ing_batch, self._rig_shape = batch, (batch, len(rig))
-        if not return_points:
-            return None
-        off = np.concatenate([[0], np.cumsum(self.ingest_info()["kept"])])
-        return [pts[off[b]:off[b + 1]].copy() for b in range(batch)]
-
+    # ---- camera-rig ingest (pp_ingest_rig_*) ----
     def ingest_rig_depth(self, frames, rig, return_points=False):
         """The depth images of a camera rig -> the engine's resident frames, on the GPU: frame b holds the kept points of
         its cameras in rig order, back to back, each camera under its own mount, intrinsics and selection --
@@ -962,9 +951,9 @@ class Engine:
         tuples = [ingest.image_as_tuple(m) for m in flat]
         layouts = _rig_depth_layouts(tuples, rig)
         offs, bufs = _pack_images(tuples)
-        data = (bufs[0] if len(bufs) == 1 else np.concatenate(bufs)) if offs[-1] else np.zeros((1,), np.uint8)
-        bounds = [ingest.kept_bound(t[1], t[2], rig.first[s % len(rig)], rig.decimate[s % len(rig)]) for s, t in enumerate(tuples)]
-        return self._ingest_rig("pp_ingest_rig_depth", data, offs, layouts, rig, fmap, len(frames), bounds, return_points)
+        B, cap = len(frames), _rig_tap_rows(tuples, rig)
+        args = (_ptr(_concat(bufs, offs)), _ptr(offs), layouts, _rig_configs(rig, B), _ptr(fmap), len(fmap), B)
+        return self._ingest_sync("pp_ingest_rig_depth", args, B, cap if return_points else None, None, len(rig))
 
     def ingest_rig_pointcloud2(self, frames, rig, return_points=False, features=None):
         """ingest_rig_depth for PointCloud2 messages: `ingest.rig_ingest_np(frames[b], rig)` exactly (the rig's intrinsics,
@@ -975,11 +964,13 @@ class Engine:
         flat, fmap = ingest.rig_frame_map(frames, rig, "ingest_rig_pointcloud2")
         tuples = [ingest.as_tuple(m) for m in flat]
         offs, layouts, bufs = _pack_messages(tuples)
-        data = (bufs[0] if len(bufs) == 1 else np.concatenate(bufs)) if offs[-1] else np.zeros((1,), np.uint8)
-        bounds = [ingest.kept_bound(t[1], t[2], rig.first[s % len(rig)], rig.decimate[s % len(rig)]) for s, t in enumerate(tuples)]
+        B, cap = len(frames), _rig_tap_rows(tuples, rig)
         table, nf = _rig_feature_table(tuples, rig, features)
-        return self._ingest_rig("pp_ingest_rig_pointcloud2", data, offs, layouts, rig, fmap, len(frames), bounds, return_points,
-                                table, nf)
+        name, args = "pp_ingest_rig_pointcloud2", (_ptr(_concat(bufs, offs)), _ptr(offs), layouts, _rig_configs(rig, B), _ptr(fmap),
+                                                   len(fmap), B)
+        if table is not None:
+            name, args = "pp_ingest_rig_pointcloud2_fields", args + (table, nf)
+        return self._ingest_sync(name, args, B, cap if return_points else None, nf, len(rig))
 
     def ingest_rig_info(self):
         """Per camera of the last rig ingest: `finite` records (valid pixels) and points `kept`, int32 [B, cameras]
@@ -998,29 +989,20 @@ class Engine:
         features (as ingest_rig_pointcloud2) are resolved against the messages here and kept with the staging."""
         return RigMessageStaging(self._lib, frames, rig, features)
 
-    def _ingest_rig_async(self, name, staging, layouts, rig, table=None, nf=None):
+    @staticmethod
+    def _rig_async_args(name, staging, layouts, rig):
+        """What a pp_ingest_rig_*_async call takes behind the bytes and their offsets."""
         S, B = len(staging.source_frame), staging.batch
         if S != B * len(rig):
             raise ValueError(f"{name}: the staging holds {S} sources in {B} frames, the rig has {len(rig)} cameras")
-        cfgs = _rig_configs(rig, B)
-        if table is None:
-            self._check(getattr(self._lib, name)(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets), layouts, cfgs,
-                                                 _ptr(staging.source_frame), S, B), name)
-        else:
-            name = name.replace("_async", "_fields_async")
-            self._check(getattr(self._lib, name)(self._h, _ptr(staging.bytes), _ptr(staging.byte_offsets), layouts, cfgs,
-                                                 _ptr(staging.source_frame), S, B, table, nf), name)
-        self._offsets = None
-        self._ing_batch, self._rig_shape = B, (B, len(rig))
-        staging._users.add(self)
-        self._staged.append(staging)      # kept alive while a copy may still read it (see upload_async)
+        return (layouts, _rig_configs(rig, B), _ptr(staging.source_frame), S, B)
 
     def ingest_rig_depth_async(self, staging, rig):
         """ingest_rig_depth without waiting (pp_ingest_rig_depth_async), from a RigDepthStaging: as ingest_depth_async, and
         mixes freely with it, with ingest_pointcloud2_async and with upload_async."""
-        tuples = [(staging.bytes[staging.byte_offsets[s]:staging.byte_offsets[s + 1]],) + tuple(g)
-                  for s, g in enumerate(staging.images)]
-        self._ingest_rig_async("pp_ingest_rig_depth_async", staging, _rig_depth_layouts(tuples, rig), rig)
+        name = "pp_ingest_rig_depth_async"
+        args = self._rig_async_args(name, staging, _rig_depth_layouts(staging.tuples(), rig), rig)
+        self._ingest_async(name, staging, args, staging.batch, len(rig))
 
     def ingest_rig_pointcloud2_async(self, staging, rig, features=None):
         """ingest_rig_pointcloud2 without waiting (pp_ingest_rig_pointcloud2_async), from a RigMessageStaging.  features:
@@ -1028,25 +1010,23 @@ class Engine:
         against the staged messages' fields for this call."""
         table, nf = staging.features, staging.nfeat
         if features is not None:
-            tuples = [(staging.bytes[staging.byte_offsets[s]:staging.byte_offsets[s + 1]],) + tuple(g)
-                      for s, g in enumerate(staging.fields)]
-            table, nf = _rig_feature_table(tuples, rig, features)
-        self._ingest_rig_async("pp_ingest_rig_pointcloud2_async", staging, staging.layouts, rig, table, nf)
+            table, nf = _rig_feature_table(staging.tuples(), rig, features)
+        name = "pp_ingest_rig_pointcloud2_async"
+        args = self._rig_async_args(name, staging, staging.layouts, rig)
+        if table is not None:
+            name, args = "pp_ingest_rig_pointcloud2_fields_async", args + (table, nf)
+        self._ingest_async(name, staging, args, staging.batch, len(rig))
 
     def detect_rig_depth(self, frames, rig, rect=None, trv2c=None, on_numeric="f32"):
         """ingest_rig_depth + detect_async + sync + detections: `detect_depth` for a rig's images.  rect / trv2c /
         on_numeric as `detect`."""
         self.ingest_rig_depth(frames, rig)
-        if rect is not None:
-            self.set_calib(rect, trv2c, len(frames))
-        return self._detect_resident(on_numeric)
+        return self._detect_after_ingest(len(frames), rect, trv2c, on_numeric)
 
     def detect_rig_pointcloud2(self, frames, rig, rect=None, trv2c=None, on_numeric="f32", features=None):
         """ingest_rig_pointcloud2 + detect_async + sync + detections; features as ingest_rig_pointcloud2."""
         self.ingest_rig_pointcloud2(frames, rig, features=features)
-        if rect is not None:
-            self.set_calib(rect, trv2c, len(frames))
-        return self._detect_resident(on_numeric)
+        return self._detect_after_ingest(len(frames), rect, trv2c, on_numeric)
 
     def intermediates(self, canvas=False):
         d, B = self.d, max(self._batches()[1], 1)

@@ -36,6 +36,10 @@ def layout_cases(pp):
         "finite_2": _sparse(pp, 2, point_step=32),
         "finite_5": _sparse(pp, 5, datatype=8, point_step=24, offsets=(0, 8, 16)),
         "no_records": s.pointcloud2_from_xyz(np.zeros((0, 3)), 0, 0),
+        # one record short of a chunk of 512, exactly one, one more (511 x 1, 64 x 8, 27 x 19 = 513)
+        "chunk_minus_1": s.pointcloud2_message(12, 511, 1, point_step=20),
+        "chunk_exact": s.pointcloud2_message(13, 64, 8, point_step=20),
+        "chunk_plus_1": s.pointcloud2_message(14, 27, 19, point_step=20),
     }
     # +-inf entries beside NaN ones: a record with an infinite coordinate is dropped like a NaN one
     xyz = rng.uniform(-3.0, 6.0, (40 * 25, 3))

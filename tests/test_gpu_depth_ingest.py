@@ -1,4 +1,4 @@
-"""Depth-image ingest on the GPU (csrc/depth_ingest.hip, pp_ingest_depth*): the resident points and the counts against
+"""Depth-image ingest on the GPU (csrc/ingest.hip, pp_ingest_depth*): the resident points and the counts against
 ingest.depth_ingest_np -- exactly, for every case of depth_cases.py --, detections from depth images against detections
 from the equivalent PointCloud2 messages and from host-ingested frames, mixed asynchronous feeds, and every refusal.
 No test provokes a fault: every refusal is decided on the host before a launch."""

@@ -1,4 +1,4 @@
-"""Camera-rig ingest on the GPU (csrc/rig_ingest.hip, pp_ingest_rig_*): several sources per frame, each under its own
+"""Camera-rig ingest on the GPU (csrc/ingest.hip, pp_ingest_rig_*): several sources per frame, each under its own
 mount and selection, against ingest.rig_depth_ingest_np / rig_ingest_np -- exactly: every comparison is on the float32
 bytes, no tolerance, no excluded rows.  One source per frame against the single-camera calls, chunk and scan boundaries,
 more sources than the scan has waves, PointCloud2 rigs, detections (synchronous, asynchronous, mixed with the other feeds)

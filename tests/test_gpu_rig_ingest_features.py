@@ -1,4 +1,4 @@
-"""PointCloud2 feature fields through the GPU rig ingest (csrc/rig_ingest.hip: k_rig_scatter_f,
+"""PointCloud2 feature fields through the GPU rig ingest (csrc/ingest.hip: k_rig_scatter_f,
 pp_ingest_rig_pointcloud2_fields*): several sources per frame, each under its own mount, selection and feature layout,
 against ingest.rig_ingest_np(..., features) -- bit for bit, NaN by class.  One source per frame against the plain call,
 three sources with three layouts, chunk and scan boundaries, the asynchronous call and the refusals.  No test provokes a

@@ -174,4 +174,6 @@ def test_rig_calls_are_declared_exported_and_bound(pp, hip_lib):
         assert name in pp._lib.EXPORTS and hasattr(hip_lib, name)
     m = re.search(r"#define\s+PP_RIG_MAX_SOURCES\s+(\d+)", hdr)
     assert m and int(m.group(1)) == pp._lib.PP_RIG_MAX_SOURCES == pp.ingest.RIG_MAX_SOURCES == 16
-    assert "rig_ingest.hip" in pp._lib.SOURCES
+    # the rig kernels are built: they live in ingest.hip beside the single-camera ones, in no file of their own
+    assert "ingest.hip" in pp._lib.SOURCES
+    assert "rig_ingest.hip" not in pp._lib.SOURCES and "depth_ingest.hip" not in pp._lib.SOURCES

@@ -1,5 +1,5 @@
-"""Feeding the detector the depth image (csrc/depth_ingest.hip) vs the PointCloud2 message computed from it
-(csrc/ingest.hip); prints one JSON line.
+"""Feeding the detector the depth image (csrc/ingest.hip: k_depth_*) vs the PointCloud2 message computed from it
+(the same file: k_ingest_*); prints one JSON line.
 
 One synthetic 640 x 480 16UC1 image with 30 % invalid pixels and the equivalent ordered messages at point_step 20 and 32
 (ingest.depth_to_pointcloud2: invalid pixels NaN), all in one process on one engine; p50 over --reps repetitions of

@@ -1,4 +1,4 @@
-"""Feeding the detector a camera rig (csrc/rig_ingest.hip) vs ingesting every camera on the host and uploading the
+"""Feeding the detector a camera rig (csrc/ingest.hip) vs ingesting every camera on the host and uploading the
 concatenated points, and vs the single-camera depth ingest; prints one JSON line.
 
 Synthetic 640 x 480 16UC1 images with 30 % invalid pixels, 1, 2 and 4 cameras per frame at batch 1 (camera 0 under the
