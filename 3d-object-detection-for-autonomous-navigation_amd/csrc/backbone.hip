@@ -686,6 +686,51 @@ __device__ __forceinline__ void fast_divmod(int n, int d, float inv_d, int& q, i
 }
 
 // ---------------------------------------------------------------------------------------
+// Shared window columns of the stride-1 separable kernels (k_sep_u<..., SH = 1>, k_sep_p<., 1>).
+//
+// Lane (q = lane >> 2, c4 = lane & 3) owns the output pixels 2q, 2q + 1 of its wave's 32 and the channels 4 c4..+3 of
+// a chunk.  Its 3 x 4 window's column 0 is own-pixel column 2 of lane q - 1, four lanes down, and its column 3 is
+// own-pixel column 1 of lane q + 1: both are in registers of the same wave already.  v_mov_b32_dpp row_shr:4 /
+// row_shl:4 moves a value four lanes up / down INSIDE a row of 16 lanes (4 values of q = 8 pixels); a lane whose
+// source lies outside its row keeps `old` (bound_ctrl off), which here is the halo column that very lane loaded.
+// Why the output width must be a multiple of 8: the neighbour's register holds the neighbour PIXEL in the same image
+// row of the same frame, fetched under the same row validity, only when no image-row, frame or end-of-data (M = frames
+// x height x width) boundary falls inside a DPP row's 8 consecutive pixels.  Wave tiles start at multiples of 32
+// pixels, so DPP rows start at multiples of 8: with width % 8 == 0 every such boundary is a multiple of 8 as well and
+// sits BETWEEN two DPP rows, where the halo is a load (zero header when out of the map), exactly as before.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ float dpp_row_shr4(float old, float src) {   // lane i <- src of lane i - 4 of its row, else old
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), 0x114, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float dpp_row_shl4(float old, float src) {   // lane i <- src of lane i + 4 of its row, else old
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), 0x104, 0xf, 0xf, false));
+}
+// WIN[0..3] = the four window columns of one row from the pair's own columns C0, C1 and the loaded halo column H
+#define SEP_SHARED_WINDOW(WIN, C0, C1, H)                                                                \
+    {                                                                                                    \
+        WIN[0] = make_float4(dpp_row_shr4(H.x, C1.x), dpp_row_shr4(H.y, C1.y), dpp_row_shr4(H.z, C1.z), dpp_row_shr4(H.w, C1.w)); \
+        WIN[1] = C0;                                                                                     \
+        WIN[2] = C1;                                                                                     \
+        WIN[3] = make_float4(dpp_row_shl4(H.x, C0.x), dpp_row_shl4(H.y, C0.y), dpp_row_shl4(H.z, C0.z), dpp_row_shl4(H.w, C0.w)); \
+    }
+// byte offsets AOFF[dy * 3 + {0, 1, 2}] of the own columns 1, 2 and of the halo column of window row dy: column 0 in the
+// first quad of a DPP row, column 3 in the last; the quads between read nothing (offset beyond the buffer's range:
+// the load returns 0 without a fetch).  ROWOK / COLOK as for the full window; ROWOFF: byte offset of the pair's first
+// pixel in window row dy; CIN4: bytes per pixel.
+#define SEP_SHARED_OFFSETS(AOFF, Q, ROWOK, COLOK, ROWOFF, CIN4, C4)                                      \
+    {                                                                                                    \
+        const int qm_ = (Q) & 3;                                                                         \
+        const bool hcol_ = qm_ == 0 ? COLOK[0] : COLOK[3];                                               \
+        const bool hload_ = (qm_ == 0) | (qm_ == 3);                                                     \
+        const unsigned hoff_ = qm_ == 0 ? 0u - (unsigned)(CIN4) : 2u * (unsigned)(CIN4);                 \
+        _Pragma("unroll") for (int dy_ = 0; dy_ < 3; ++dy_) {                                            \
+            AOFF[dy_ * 3 + 0] = ((ROWOK[dy_] & COLOK[1]) ? ROWOFF[dy_] : 0u) + (unsigned)((C4) * 16);    \
+            AOFF[dy_ * 3 + 1] = ((ROWOK[dy_] & COLOK[2]) ? ROWOFF[dy_] + (unsigned)(CIN4) : 0u) + (unsigned)((C4) * 16); \
+            AOFF[dy_ * 3 + 2] = hload_ ? ((ROWOK[dy_] & hcol_) ? ROWOFF[dy_] + hoff_ : 0u) + (unsigned)((C4) * 16) : 0x80000000u; \
+        }                                                                                                \
+    }
+
+// ---------------------------------------------------------------------------------------
 // Uniform-wave separable layer (every wave prepares AND multiplies).
 //
 // A 4-wave workgroup owns 128 output pixels x NT channels; wave w owns pixels 32w..32w+31 for the
@@ -709,9 +754,16 @@ __device__ __forceinline__ void fast_divmod(int n, int d, float inv_d, int& q, i
 // no window element is ever masked or selected); the depthwise output is also stored (the weight-gradient product's
 // operand); the epilogue writes the raw product (this layer's pre-BatchNorm map) and the centred column statistics
 // of each wave's 32 rows for the batch statistics (k_tr_bn_finalize).  PREC 1 only.
-template <int NT, int S, int WPS, int PREC, int OCC = 0, int TR = 0>
+// SH 1 (stride 1, split-precision, dense input, inference; output width a multiple of 8 -- see sep_shared_window): the
+// lanes of a DPP row share their window columns.  A lane loads the two columns of its OWN pixel pair and one halo
+// column per row -- the left one in the first lane quad of a row of 16 lanes, the right one in the last, nothing in
+// the two between (an out-of-range offset: no fetch) -- and takes its left / right window column from the quad before /
+// after it with one v_mov_b32_dpp row_shr:4 / row_shl:4 per value at staging time: 9 window loads instead of 12, 7.5
+// instead of 12 KB through the vector-memory return path per wave and chunk, the same values into the same FMAs.
+template <int NT, int S, int WPS, int PREC, int OCC = 0, int TR = 0, int SH = 0>
 __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
     static_assert(TR == 0 || (PREC == 1 && OCC == 0), "training forward: split-precision, dense input");
+    static_assert(SH == 0 || (S == 1 && PREC == 1 && OCC == 0 && TR == 0), "shared window: stride 1, dense input, inference");
     // TR 2: the same launch WITHOUT the depthwise -- a plain product rows x cin -> rows x n_total of the training forward
     // (transposed convolutions as GEMMs over their input pixels, the heads): the "window" is the pixel pair itself, the
     // A tile is staged unchanged, epilogue and statistics as TR 1 (+ bias when given).  Rows past M read as zeros
@@ -720,7 +772,7 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
     constexpr int NTAP = (TR == 1) ? 11 : 9;         // tap vectors per channel group in LDS (TR 1: + sc, sh)
     constexpr int KCH = 16, LSTR = KCH + 4, G = 4;
     constexpr int WW = S + 3;                        // input window width of 2 adjacent output pixels
-    constexpr int NLD = PW ? 2 : 3 * WW;
+    constexpr int NLD = PW ? 2 : (SH ? 9 : 3 * WW);  // (SH: per row the pair's own two columns, then the halo column)
     constexpr int SAW = 32 * LSTR;                   // one wave-private A buffer (floats)
     // weight tile in LDS: PREC 0 [NT][16 + 4] floats; PREC 1 [2 pieces][NT][16 f16 = 8 floats], the two
     // 16-byte halves of a row swapped on odd groups of 8 rows (conflict-free ds_read_b128 without padding)
@@ -814,6 +866,9 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
                 wbits_[dy_] = (unsigned)((lo_ >> sh_) | ((hi_ << 1) << (63 - sh_)));                     \
             }                                                                                            \
         }                                                                                                \
+        if constexpr (SH != 0) {                                                                         \
+            SEP_SHARED_OFFSETS(aoff, q, rowok_, colok_, rowoff_, cin4, c4)                               \
+        } else {                                                                                         \
         _Pragma("unroll") for (int e = 0; e < NLD; ++e) {                                                \
             const int dy_ = e / WW, dx_ = e % WW;                                                        \
             bool ok_ = rowok_[dy_] & colok_[dx_];                                                        \
@@ -829,6 +884,7 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
                 }                                                                                        \
             }                                                                                            \
             aoff[e] = (ok_ ? rowoff_[dy_] + coloff_[dx_] : 0u) + (unsigned)(c4 * 16);                    \
+        }                                                                                                \
         }                                                                                                \
         }                                                                                                \
     }
@@ -952,15 +1008,19 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
         if (PW) { o0 = RIN[0]; o1 = RIN[NLD - 1]; }                                                      \
         if (!PW) {                                                                                       \
             const float* tw = twp;                                                                       \
-            _Pragma("unroll") for (int dy = 0; dy < 3; ++dy)                                             \
+            _Pragma("unroll") for (int dy = 0; dy < 3; ++dy) {                                           \
+                [[maybe_unused]] float4 win_[4];                                                         \
+                if constexpr (SH != 0) SEP_SHARED_WINDOW(win_, RIN[dy * 3], RIN[dy * 3 + 1], RIN[dy * 3 + 2]) \
                 _Pragma("unroll") for (int dx = 0; dx < 3; ++dx) {                                       \
                     const float4 w4 = *reinterpret_cast<const float4*>(tw + (dy * 3 + dx) * 4);          \
-                    const float4 v0 = RIN[PW ? 0 : dy * WW + dx], v1 = RIN[PW ? 0 : dy * WW + S + dx];   \
+                    const float4 v0 = SH ? win_[dx] : RIN[(PW || SH) ? 0 : dy * WW + dx];                \
+                    const float4 v1 = SH ? win_[dx + 1] : RIN[(PW || SH) ? 0 : dy * WW + S + dx];        \
                     o0.x = fmaf(v0.x, w4.x, o0.x); o0.y = fmaf(v0.y, w4.y, o0.y);                        \
                     o0.z = fmaf(v0.z, w4.z, o0.z); o0.w = fmaf(v0.w, w4.w, o0.w);                        \
                     o1.x = fmaf(v1.x, w4.x, o1.x); o1.y = fmaf(v1.y, w4.y, o1.y);                        \
                     o1.z = fmaf(v1.z, w4.z, o1.z); o1.w = fmaf(v1.w, w4.w, o1.w);                        \
                 }                                                                                        \
+            }                                                                                            \
         }                                                                                                \
         float* dA = sAw + buf * SAW + (2 * q) * LSTR + c4 * 4;                                           \
         *reinterpret_cast<float4*>(dA) = o0;                                                             \
@@ -1120,6 +1180,13 @@ constexpr int sep_u_wpc(int nt, int s, bool prec) {
                   : (prec ? (nt == 128 ? 2 : 3) : (nt == 128 ? 2 : (nt == 64 ? 3 : 4)));
 }
 
+// may this stride-1 launch share window columns between the lanes of a DPP row?  (SEP_SHARED_WINDOW: the output width
+// a multiple of 8 -- a DPP row's 8 pixels then never straddle an image row, a frame or the end of the data -- and the
+// input map the size of the output map)
+static bool sep_shared_window(const GemmArgs& a) {
+    return a.stride == 1 && a.px_w % 8 == 0 && a.in_w == a.px_w && a.in_h == a.px_h;
+}
+
 // persistent launch: sep_u_wpc workgroups per CU, a multiple of 8 so that every XCD gets the same number
 template <int NT, int S>
 static void launch_u(const GemmArgs& a, int n_total, bool prec, bool occ, hipStream_t s) {
@@ -1131,12 +1198,22 @@ static void launch_u(const GemmArgs& a, int n_total, bool prec, bool occ, hipStr
     int gx = mine < slots ? mine : slots;
     gx = (gx + 7) & ~7;
     dim3 grid((unsigned)gx, ny);
-    if (occ)
+    if (occ) {
         PP_LAUNCH("k_sep_u", (k_sep_u<NT, S, WPB, 1, 1>), grid, dim3(256), 0, s, a, ntiles);
-    else if (prec)
+    } else if (prec) {
+        // shared window columns: the 64-channel instantiation only.  Measured per layer at B = 64 ("Shared
+        // window columns"): k_sep_u<64,1,3> 38.8 -> 37.5 us (block1.0 59 -> 55.5), k_sep_u<128,1,2> 26.3 -> 26.9 us -- the
+        // 128-channel kernel does not get faster with three loads fewer, so it keeps the full window
+        if constexpr (S == 1 && NT == 64) {
+            if (sep_shared_window(a)) {
+                PP_LAUNCH("k_sep_u", (k_sep_u<NT, S, WPB, 1, 0, 0, 1>), grid, dim3(256), 0, s, a, ntiles);
+                return;
+            }
+        }
         PP_LAUNCH("k_sep_u", (k_sep_u<NT, S, WPB, 1>), grid, dim3(256), 0, s, a, ntiles);
-    else
+    } else {
         PP_LAUNCH("k_sep_u", (k_sep_u<NT, S, WPS, 0>), grid, dim3(256), 0, s, a, ntiles);
+    }
 }
 
 // Training-mode forward of one separable layer as ONE launch (SepTrainArgs, pp_common.h): depthwise (with the input's
@@ -1218,9 +1295,9 @@ int launch_rows_train(const RowsTrainArgs& t, hipStream_t s) {
 // iterations (each with twice the matrix work to overlap).  113 KB of LDS: one workgroup (two waves per SIMD) per CU,
 // the occupancy of the 200-register k_sep_u<128>.  Skeleton (persistent XCD-aware tile walk, load / stage / multiply
 // cursors, one barrier per position, transposing epilogue) as k_sep_u.  cin % 64 == 0.
-template <int CO>   // output channels of the layer (256)
+template <int CO, int SH = 0>   // output channels of the layer (256); SH 1: shared window columns (see SEP_SHARED_WINDOW)
 __global__ __launch_bounds__(512, 1) void k_sep_p(GemmArgs a, int ntiles) {
-    constexpr int KCH = 16, LSTR = KCH + 4, WW = 4, NLD = 12;
+    constexpr int KCH = 16, LSTR = KCH + 4, WW = 4, NLD = SH ? 9 : 12;
     constexpr int SAW = 32 * LSTR;                   // one A tile (floats)
     constexpr int SB1 = PP_NPIECE * CO * 8;          // weights of one chunk: [pieces][CO][16 f16]
     constexpr int NTILES = CO / 64;                  // channel tiles of a wave (half the channels)
@@ -1260,10 +1337,15 @@ __global__ __launch_bounds__(512, 1) void k_sep_p(GemmArgs a, int ntiles) {
         bool rowok_[3], colok_[WW];                                                                      \
         _Pragma("unroll") for (int dy_ = 0; dy_ < 3; ++dy_) rowok_[dy_] = pvalid_ & ((unsigned)(y_ - 1 + dy_) < (unsigned)a.in_h); \
         _Pragma("unroll") for (int dx_ = 0; dx_ < WW; ++dx_) colok_[dx_] = (unsigned)(x0_ - 1 + dx_) < (unsigned)a.in_w; \
+        if constexpr (SH != 0) {                                                                         \
+            const unsigned rowoff_[3] = {cbase_ - (unsigned)rs4, cbase_, cbase_ + (unsigned)rs4};        \
+            SEP_SHARED_OFFSETS(aoff, q, rowok_, colok_, rowoff_, cin4, c4)                               \
+        } else {                                                                                         \
         _Pragma("unroll") for (int e = 0; e < NLD; ++e) {                                                \
             const int dy_ = e / WW, dx_ = e % WW;                                                        \
             const bool ok_ = rowok_[dy_] & colok_[dx_];                                                  \
             aoff[e] = (ok_ ? cbase_ + (unsigned)((dy_ - 1) * rs4) + (unsigned)((dx_ - 1) * cin4) : 0u) + (unsigned)(c4 * 16); \
+        }                                                                                                \
         }                                                                                                \
     }
     // weight items of a position: [chunk of the pair][piece][row][half]
@@ -1337,15 +1419,19 @@ __global__ __launch_bounds__(512, 1) void k_sep_p(GemmArgs a, int ntiles) {
         constexpr int buf = (P) & 1;                                                                     \
         const float* tw = sDW + ((2 * st_pos + grp) * 4 + c4) * 36;                                      \
         float4 o0 = make_float4(0.f, 0.f, 0.f, 0.f), o1 = o0;                                            \
-        _Pragma("unroll") for (int dy = 0; dy < 3; ++dy)                                                 \
+        _Pragma("unroll") for (int dy = 0; dy < 3; ++dy) {                                               \
+            [[maybe_unused]] float4 win_[4];                                                             \
+            if constexpr (SH != 0) SEP_SHARED_WINDOW(win_, rin[dy * 3], rin[dy * 3 + 1], rin[dy * 3 + 2]) \
             _Pragma("unroll") for (int dx = 0; dx < 3; ++dx) {                                           \
                 const float4 w4 = *reinterpret_cast<const float4*>(tw + (dy * 3 + dx) * 4);              \
-                const float4 v0 = rin[dy * WW + dx], v1 = rin[dy * WW + 1 + dx];                         \
+                const float4 v0 = SH ? win_[dx] : rin[SH ? 0 : dy * WW + dx];                            \
+                const float4 v1 = SH ? win_[dx + 1] : rin[SH ? 0 : dy * WW + 1 + dx];                    \
                 o0.x = fmaf(v0.x, w4.x, o0.x); o0.y = fmaf(v0.y, w4.y, o0.y);                            \
                 o0.z = fmaf(v0.z, w4.z, o0.z); o0.w = fmaf(v0.w, w4.w, o0.w);                            \
                 o1.x = fmaf(v1.x, w4.x, o1.x); o1.y = fmaf(v1.y, w4.y, o1.y);                            \
                 o1.z = fmaf(v1.z, w4.z, o1.z); o1.w = fmaf(v1.w, w4.w, o1.w);                            \
             }                                                                                            \
+        }                                                                                                \
         float* dA = sA + pg * (4 * SAW) + (grp * 2 + buf) * SAW + (2 * q) * LSTR + c4 * 4;               \
         *reinterpret_cast<float4*>(dA) = o0;                                                             \
         *reinterpret_cast<float4*>(dA + LSTR) = o1;                                                      \
@@ -1417,7 +1503,8 @@ static void launch_p(const GemmArgs& a, hipStream_t s) {
     const int ntiles = (a.M + 127) / 128;
     int gx = ntiles < g_num_cus ? ntiles : g_num_cus;
     gx = (gx + 7) & ~7;
-    PP_LAUNCH("k_sep_p", k_sep_p<256>, dim3((unsigned)gx), dim3(512), 0, s, a, ntiles);
+    if (sep_shared_window(a)) PP_LAUNCH("k_sep_p", (k_sep_p<256, 1>), dim3((unsigned)gx), dim3(512), 0, s, a, ntiles);
+    else PP_LAUNCH("k_sep_p", k_sep_p<256>, dim3((unsigned)gx), dim3(512), 0, s, a, ntiles);
 }
 
 // does k_sep_p run this separable layer?  (256 output channels, stride 1, dense input, large enough for the persistent

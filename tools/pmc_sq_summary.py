@@ -49,6 +49,13 @@ for k, d in agg.items():
             if c in v:
                 v[key] = v[c] / v["SQ_WAVE_CYCLES"]
     out[k] = {c: (round(x, 4) if isinstance(x, float) and x < 10 else round(x)) for c, x in v.items()}
+# k_sep_u's seventh template parameter (SH: window columns shared between lanes) is the launcher's choice at run time and
+# not part of a layer's tag; the bench line looks a kernel up under the six-parameter symbol, so the variant with the most
+# launches is listed under that name as well
+for k in list(out):
+    m = re.match(r"(k_sep_u<(?:-?\d+,){5}-?\d+),\d+>$", k)
+    if m and out.get(m.group(1) + ">", {}).get("launches_sampled", -1) < out[k]["launches_sampled"]:
+        out[m.group(1) + ">"] = dict(out[k], alias_of=k)
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import csrc_sha16  # noqa: E402
 head = os.environ.get("PP_GIT_HEAD", "")

@@ -34,6 +34,13 @@ for k in sorted(set(fetch) | set(write)):
     w_b = write.get(k, 0.0) * 1024
     out[short(k)] = {"fetch_bytes_per_launch": f_b, "write_bytes_per_launch": w_b,
                      "hbm_bytes_per_launch": f_b + w_b, "launches_sampled": nf.get(k, 0)}
+# k_sep_u's seventh template parameter (SH: window columns shared between lanes) is the launcher's choice at run time and
+# not part of a layer's tag; the bench line looks a kernel up under the six-parameter symbol, so the variant with the most
+# launches is listed under that name as well
+for k in list(out):
+    m = re.match(r"(k_sep_u<(?:-?\d+,){5}-?\d+),\d+>$", k)
+    if m and out.get(m.group(1) + ">", {}).get("launches_sampled", -1) < out[k]["launches_sampled"]:
+        out[m.group(1) + ">"] = dict(out[k], alias_of=k)
 import os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import csrc_sha16  # noqa: E402
