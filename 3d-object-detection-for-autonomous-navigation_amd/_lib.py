@@ -19,7 +19,8 @@ SO_PATH = os.path.join(_PKG, os.environ.get("PP_HIP_LIB", "libpp_hip.so"))
 _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
 SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_nms.hip", "api_project.hip", "api_class_nms.hip", "api_metrics.hip", "api_publish.hip", "api_train.hip", "api_dataprep.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
            "rotate_iou.hip", "rotate_nms.hip", "box_project.hip", "loss.hip", "metrics.hip", "optim.hip", "grad_clip.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip",
-           "gt_database.hip", "eval_stats.hip", "frustum_crop.hip", "weight_publish.hip", "soft_nms.hip"]
+           "gt_database.hip", "eval_stats.hip", "frustum_crop.hip", "weight_publish.hip", "soft_nms.hip",
+           "api_track.hip", "track.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
@@ -55,6 +56,8 @@ EXPORTS = [
     "pp_grad_clip_workspace_bytes", "pp_grad_norm_device", "pp_adamw_step_clipped_device",
     "pp_publish_train_weights", "pp_publish_info",
     "pp_set_soft_nms", "pp_get_soft_nms", "pp_soft_nms",
+    "pp_set_tracking", "pp_get_tracking", "pp_set_track_dt", "pp_get_tracks", "pp_track_update", "pp_track_reset",
+    "pp_track_info",
 ]
 
 
@@ -210,6 +213,8 @@ PP_CLASS_NMS_JOINT, PP_CLASS_NMS_PER_CLASS = 0, 1      # enum pp_class_nms
 PP_NMS_STANDUP, PP_NMS_ROTATED, PP_NMS_SOFT = 0, 1, 2      # enum pp_nms_mode
 PP_SOFT_NMS_HARD, PP_SOFT_NMS_LINEAR, PP_SOFT_NMS_GAUSSIAN = 0, 1, 2      # enum pp_soft_nms_method
 PP_SNMS_MAX_BOXES = 4096      # most boxes that enter pp_soft_nms after pre_max_size
+PP_TRACK_MAX = 64      # tracks per stream (pp_set_tracking)
+PP_TRACK_MASK_ROWS = 128      # detection rows per frame the tracking step takes
 PP_CLIP_NONE, PP_CLIP_VALUE, PP_CLIP_NORM, PP_CLIP_GLOBAL_NORM = 0, 1, 2, 3      # enum pp_grad_clip_mode
 
 
@@ -221,6 +226,39 @@ class PPDetection(ctypes.Structure):
         ("label", ctypes.c_int32),
         ("dir_label", ctypes.c_int32),
         ("anchor_index", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class PPTrackConfig(ctypes.Structure):
+    _fields_ = [
+        ("gate", ctypes.c_double),
+        ("q_acc", ctypes.c_double),
+        ("r_pos", ctypes.c_double),
+        ("p0_pos", ctypes.c_double),
+        ("p0_vel", ctypes.c_double),
+        ("size_alpha", ctypes.c_double),
+        ("birth_score", ctypes.c_double),
+        ("period", ctypes.c_double),
+        ("max_misses", ctypes.c_int32),
+        ("min_hits", ctypes.c_int32),
+        ("class_aware", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class PPTrack(ctypes.Structure):
+    _fields_ = [
+        ("state", ctypes.c_double * 6),
+        ("size", ctypes.c_double * 3),
+        ("yaw", ctypes.c_double),
+        ("score", ctypes.c_float),
+        ("id", ctypes.c_int32),
+        ("label", ctypes.c_int32),
+        ("hits", ctypes.c_int32),
+        ("misses", ctypes.c_int32),
+        ("confirmed", ctypes.c_int32),
+        ("det_row", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
     ]
 
@@ -433,6 +471,13 @@ def lib():
     L.pp_get_soft_nms.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.pp_soft_nms.argtypes = [ctypes.c_int, f32p, i64, i32, ctypes.c_float, ctypes.c_float, ctypes.c_float, i32, i32, vp, vp,
                               ctypes.POINTER(i64)]
+    L.pp_set_tracking.argtypes = [vp, ctypes.POINTER(PPTrackConfig)]
+    L.pp_get_tracking.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(PPTrackConfig)]
+    L.pp_set_track_dt.argtypes = [vp, vp, i32]
+    L.pp_get_tracks.argtypes = [vp, vp, vp, vp]
+    L.pp_track_update.argtypes = [vp, vp, vp, i32, i32, vp]
+    L.pp_track_reset.argtypes = [vp, i32]
+    L.pp_track_info.argtypes = [vp, vp, vp, vp]
     L.pp_set_projection.argtypes = [vp, vp, i32]
     L.pp_get_projection.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_get_bboxes.argtypes = [vp, vp]

@@ -224,6 +224,20 @@ class Derived:
         # not a key of the reference's YAML either (absent = False): "bbox" of a prediction is the projection of its camera
         # box by the frame's P2 (box3d_to_bbox, which the reference's predict() commented out) instead of the placeholder
         self.project_bbox = bool(s.get("project_bbox", False))
+        # not a key of the reference's YAML either (absent or False = off; True = the defaults): a dict of the
+        # tracking.TrackConfig fields -- the engine then keeps one track table per stream on the GPU, advanced behind every
+        # pass (tracking.py states the rule).  Echoed in its full dict form.
+        tk = s.get("tracking")
+        if tk is None or tk is False:
+            self.tracking = None
+        else:
+            from .tracking import TrackConfig
+            if not (tk is True or isinstance(tk, dict)):
+                raise ValueError(f"model.second.tracking: a dict of TrackConfig fields, True or False, got {tk!r}")
+            try:
+                self.tracking = TrackConfig.from_any(tk).to_dict()
+            except ValueError as err:
+                raise ValueError(f"model.second.tracking: {err}")
         er = config["eval_input_reader"]
         self.batch_size = int(er["batch_size"])
         self.anchor_area_threshold = er["anchor_area_threshold"]

@@ -797,6 +797,7 @@ int pp_destroy(pp_handle e) {
         if (p) (void)hipFree(p);
     if (e->train) for (auto& tg : e->train->graph) { destroy_exec(&tg.exec); destroy_exec(&tg.exec_bwd); }
     delete e->train;
+    track_release(e);
     for (void* p : {(void*)e->h_off_ring, (void*)e->ing.h_ring, (void*)e->ing.rig.h_frames, (void*)e->ing.rig.h_src, (void*)e->ing.h_feats, (void*)e->ing.rig.h_feats, (void*)e->crop.h_ring, (void*)e->h_feed[0], (void*)e->h_feed[1], (void*)e->h_train_losses,
                     (void*)e->h_dets, (void*)e->h_ndets, (void*)e->proj.h_bbox, (void*)e->metrics.h_counts})
         if (p) (void)hipHostFree(p);
@@ -1140,7 +1141,8 @@ static int enqueue_detect(pp_engine* e, int B, int max_n) {
     if (!e->mask_in_pfn && (st = run_anchor_mask(e, B))) return st;
     if ((st = run_backbone(e, B))) return st;
     // the post-process stores its few kept detections per frame straight into the page-locked result buffers
-    return run_post(e, B, true);
+    if ((st = run_post(e, B, true))) return st;
+    return e->rule.track ? run_track(e, B) : PP_OK;
 }
 
 // The soft parameters count only while the soft rule runs: in the other modes the key carries fixed values, so changing
@@ -1182,6 +1184,7 @@ int pp_detect_async(pp_handle e) {
     if (!e->weights_ready) return fail(e, PP_ERR_STATE, "pp_detect_async: weights not finalised");
     if (!e->anchors_ready) return fail(e, PP_ERR_STATE, "pp_detect_async: anchors not set");
     if (e->cur_batch < 1) return fail(e, PP_ERR_STATE, "pp_detect_async: no frames uploaded");
+    if (int st = track_check_pass(e)) return st;
     (void)hipSetDevice(e->device);
     const int B = e->cur_batch;
     prof_reset(e);
@@ -1227,6 +1230,8 @@ int pp_detect_async(pp_handle e) {
     e->results_buf = e->in_buf;
     e->proj.results = e->rule.proj ? B : 0;
     e->results_rows = det_rows(e);
+    e->trk.results = e->rule.track ? B : 0;
+    e->trk.from_pass = true;
     return PP_OK;
 }
 

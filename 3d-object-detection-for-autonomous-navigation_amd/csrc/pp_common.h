@@ -284,6 +284,35 @@ struct PostParams {
 };
 void launch_postprocess(const PostParams& p, hipStream_t s);
 
+// track.hip: one track table per stream (pp_set_tracking; tracking.py states the rule).  One slot of a stream's table:
+struct TrkSlot {
+    double x[6];           // x y z vx vy vz
+    double p[3];           // p00 p01 p11, shared by the three axes
+    double size[3];        // w l h
+    double yaw;
+    float score;
+    int id, label, hits, misses, confirmed;
+    int live;              // 0: the slot is free (its other fields are then meaningless)
+};
+#define PP_TRACK_MASK_ROWS 128     // detection rows per frame the free-row bitmask of k_track_step holds (2 x 64 bits)
+struct TrackParams {
+    int batch;                 // streams 0 .. batch - 1 advance by one step
+    int rows;                  // row stride of dets (<= PP_TRACK_MASK_ROWS)
+    const pp_detection* dets;  // [batch][rows]
+    const int* n_dets;         // [batch]; a count with PP_NDETS_NONFINITE leaves its stream untouched
+    const pp_track_config* cfg;   // device memory: changing a parameter re-captures nothing
+    double* dt;                // [batch] seconds of this step per stream; <= 0: cfg->period.  Consumed (zeroed) by the step,
+                               // also for a flagged stream
+    TrkSlot* state;            // [B][PP_TRACK_MAX]
+    int* next_id;              // [B]
+    int* overflow;             // [B]
+    // page-locked host memory the kernel fills itself (only pp_get_tracks reads them):
+    pp_track* out;             // [batch][PP_TRACK_MAX] the live tracks, ascending slot
+    int* n_out;                // [batch]
+    int* overflow_out;         // [batch]
+};
+void launch_track_step(const TrackParams& p, hipStream_t s);
+
 // loss.hip: training loss at the head maps + gradient with respect to them
 struct LossParams {
     int batch;

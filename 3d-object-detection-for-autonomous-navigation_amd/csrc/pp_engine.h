@@ -3,7 +3,8 @@
 // api_ingest.hip: PointCloud2, depth-image and camera-rig ingest; api_crop.hip: the frustum crop; api_train.hip: loss, training step, optimizer; api_dataprep.hip: targets,
 // augmentation, GT sampling, object database; api_eval.hip: the AP evaluator (needs no handle); api_nms.hip: the detector's NMS rule and the standalone rotated NMS;
 // api_project.hip: the detector's image boxes and the standalone projection; api_class_nms.hip: joint / per-class suppression;
-// api_metrics.hip: the training metrics' counts; api_publish.hip: a trainer's weights into the detector, on the device.
+// api_metrics.hip: the training metrics' counts; api_publish.hip: a trainer's weights into the detector, on the device;
+// api_track.hip: the per-stream track tables behind the detector's post-process.
 #pragma once
 
 #include <cmath>
@@ -35,9 +36,10 @@ struct PostRule {
     float soft_sigma = 0.5f, soft_floor = 0.001f;
     int class_nms = PP_CLASS_NMS_JOINT;   // joint (one pass for all classes) or per class
     int proj = 0;                         // image boxes of the kept detections on / off
+    int track = 0;                        // pp_set_tracking: k_track_step behind the post-process on / off
     bool operator==(const PostRule& o) const {
         return nms_mode == o.nms_mode && soft_method == o.soft_method && soft_sigma == o.soft_sigma &&
-               soft_floor == o.soft_floor && class_nms == o.class_nms && proj == o.proj;
+               soft_floor == o.soft_floor && class_nms == o.class_nms && proj == o.proj && track == o.track;
     }
 };
 
@@ -334,6 +336,27 @@ struct pp_engine {
         int results = 0;               // frames of the last pass that projected (pp_get_bboxes; 0: none, or projection off)
     } proj;
 
+    // pp_set_tracking: one track table per stream (frame b of a pass is stream b), advanced by k_track_step behind the
+    // post-process (on / off is rule.track).  Allocated on first use (api_track.hip: ensure_track).
+    struct Track {
+        bool ready = false;
+        bool configured = false;       // pp_set_tracking has given a configuration
+        pp_track_config cfg = {};      // what d_cfg holds
+        pp_track_config* d_cfg = nullptr;
+        TrkSlot* state = nullptr;      // [B][PP_TRACK_MAX]
+        int *next_id = nullptr, *overflow = nullptr;   // [B]
+        double* d_dt = nullptr;        // [B] seconds of the next step per stream (0: the configuration's period)
+        double* h_dt_ring = nullptr;   // pinned [OFF_RING][B]: pp_set_track_dt's values travel like the frame offsets
+        hipEvent_t dt_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        int dt_slot = 0;
+        pp_track* h_out = nullptr;     // pinned [B][PP_TRACK_MAX]: the kernel stores the live rows straight into it (nothing on
+        int *h_nout = nullptr, *h_overflow = nullptr;   // the device reads them: no device copy, no copy node behind the pass)
+        pp_detection* in_dets = nullptr;   // [B][PP_TRACK_MASK_ROWS] pp_track_update's rows (d_dets stays a pass's)
+        int* in_n = nullptr;               // [B]
+        int results = 0;               // streams of the last tracked pass or pp_track_update (pp_get_tracks; 0: none)
+        bool from_pass = false;        // ... it was a pass: pp_get_tracks consults its frames' numeric flags
+    } trk;
+
     int prof = 0;
     // pp_detect_async as one hipGraph launch, captured on first use per key.  The key is a DetectKey: whatever a pass
     // reads that is neither behind a device pointer nor dropped by graph_invalidate.  detect_key (pp_api.hip) builds it and
@@ -456,6 +479,9 @@ int resident_points(pp_engine* e, int batch, hipStream_t s, bool materialise, co
 int ensure_spare_pts(pp_engine* e);
 
 int ensure_loss_buffers(pp_engine* e);                  // api_train.hip
+int track_check_pass(pp_engine* e);                     // api_track.hip: what a tracked pass refuses, before anything is queued
+int run_track(pp_engine* e, int batch);                 // api_track.hip: k_track_step on this pass's d_dets / d_ndets
+void track_release(pp_engine* e);                       // ... what pp_destroy frees of it (page-locked memory, events)
 int ensure_metrics(pp_engine* e);                       // api_metrics.hip
 void fill_metrics_params(pp_engine* e, int batch, MetricsParams& p);   // ... on the handle's head map and loss.labels
 // ---- api_dataprep.hip: what the fused training steps (api_train.hip) queue ----

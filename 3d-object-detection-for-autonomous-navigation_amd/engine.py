@@ -6,12 +6,14 @@ RuntimeError carrying pp_last_error().
 """
 import collections
 import ctypes
+import dataclasses
 import weakref
 
 import numpy as np
 
 from . import _lib
 from . import soft_nms as _soft
+from . import tracking as _trk
 from .anchors import build_anchor_cells, build_anchors
 from .config import Derived
 from .weights import check_weights
@@ -387,6 +389,9 @@ class Engine:
             self.set_nms_mode("soft")
         if d.use_multi_class_nms:
             self.set_class_nms("per_class")
+        self._last_stamp = np.full(self.max_batch, np.nan)      # per stream: the last time stamp a detect* was given
+        if d.tracking is not None:
+            self.set_tracking(d.tracking)
         if weights is not None:
             self.load_weights(weights)
 
@@ -503,6 +508,98 @@ class Engine:
         out = np.zeros((self.max_batch, post, 4), dtype=np.float64)
         self._check(self._lib.pp_get_bboxes(self._h, _ptr(out)), "pp_get_bboxes")
         return out if batch is None else out[:batch]
+
+    # ---- tracking across frames (pp_set_tracking; tracking.py states the rule) ----
+    def set_tracking(self, cfg):
+        """A tracking.TrackConfig, a dict of its fields or True (the defaults): from the next detect_async every pass
+        advances one track table per stream (frame b is stream b) behind its post-process, on the GPU -- `tracks()` then
+        returns ids and velocities.  None: off (the default); the tables and the configuration are kept.  The config key
+        model.second.tracking selects it at construction."""
+        if cfg is None or cfg is False:
+            self._check(self._lib.pp_set_tracking(self._h, None), "pp_set_tracking")
+            return
+        c = _trk.TrackConfig.from_any(cfg)
+        pc = _lib.PPTrackConfig()
+        for f, v in c.to_dict().items():
+            setattr(pc, f, int(v) if f in ("max_misses", "min_hits", "class_aware") else v)
+        self._check(self._lib.pp_set_tracking(self._h, ctypes.byref(pc)), "pp_set_tracking")
+
+    def _get_tracking(self):
+        on, pc = ctypes.c_int32(0), _lib.PPTrackConfig()
+        self._check(self._lib.pp_get_tracking(self._h, ctypes.byref(on), ctypes.byref(pc)), "pp_get_tracking")
+        return bool(on.value), pc
+
+    @property
+    def tracking_on(self):
+        return self._get_tracking()[0]
+
+    @property
+    def tracking(self):
+        """The TrackConfig the passes track with, or None while tracking is off."""
+        on, pc = self._get_tracking()
+        if not on:
+            return None
+        return _trk.TrackConfig(**{f.name: getattr(pc, f.name) for f in dataclasses.fields(_trk.TrackConfig)})
+
+    def set_track_dt(self, dt):
+        """Seconds by which the next tracked pass advances streams 0 .. len(dt) - 1 (pp_set_track_dt; queued on the
+        engine's stream, consumed by that pass; a stream without a value advances by the configuration's period)."""
+        d = np.ascontiguousarray(dt, np.float64).reshape(-1)
+        self._check(self._lib.pp_set_track_dt(self._h, _ptr(d), int(d.shape[0])), "pp_set_track_dt")
+
+    def _track_out(self, B):
+        tr = np.zeros((max(B, 1), _lib.PP_TRACK_MAX), _trk.TRACK_DTYPE)
+        return tr, np.zeros(max(B, 1), np.int32), np.zeros(max(B, 1), np.int32)
+
+    def tracks(self, batch=None):
+        """(tracks [B, 64] tracking.TRACK_DTYPE, n_tracks [B], overflow [B]) of the last tracked pass or track_update (waits
+        for it): the live tracks of stream b in ascending slot order, zeros behind them.  Raises when the last pass ran
+        untracked, and NumericError where `detections()` would."""
+        tr, n, ov = self._track_out(self.max_batch)
+        n[:] = -1                       # the call fills the streams of that pass (or track_update) only
+        self._check(self._lib.pp_get_tracks(self._h, _ptr(tr), _ptr(n), _ptr(ov)), "pp_get_tracks")
+        B = int(batch) if batch is not None else int(np.count_nonzero(n >= 0))
+        return tr[:B], n[:B], ov[:B]
+
+    def track_update(self, dets, n_dets, dt=None):
+        """One tracking step on host-given rows (pp_track_update; the same kernel, on this engine's same tables): dets
+        [batch, rows] DET_DTYPE, n_dets [batch], dt [batch] seconds or None (the period).  Returns `tracks(batch)`."""
+        n = _i32(np.asarray(n_dets).reshape(-1))
+        d = np.ascontiguousarray(dets, DET_DTYPE)
+        if d.ndim != 2 or d.shape[0] != n.shape[0]:
+            raise ValueError(f"track_update: dets must be [batch, rows] with one count per frame, got {d.shape} and {n.shape}")
+        t = None if dt is None else np.ascontiguousarray(dt, np.float64).reshape(-1)
+        if t is not None and t.shape[0] != n.shape[0]:
+            raise ValueError(f"track_update: {t.shape[0]} dt values for {n.shape[0]} streams")
+        self._check(self._lib.pp_track_update(self._h, _ptr(d), _ptr(n), int(d.shape[1]), int(d.shape[0]), _ptr(t)),
+                    "pp_track_update")
+        return self.tracks(int(d.shape[0]))
+
+    def track_reset(self, stream=None):
+        """Frees every track of `stream` (None: of all streams); its ids start at 1 again, its overflow count and its last
+        time stamp are forgotten."""
+        s = -1 if stream is None else int(stream)
+        self._check(self._lib.pp_track_reset(self._h, s), "pp_track_reset")
+        if s < 0:
+            self._last_stamp[:] = np.nan
+        else:
+            self._last_stamp[s] = np.nan
+
+    def track_info(self):
+        """Per stream, [max_batch] int32 each: `live` tracks, `next_id`, `overflow`."""
+        live, nid, ov = (np.zeros(self.max_batch, np.int32) for _ in range(3))
+        self._check(self._lib.pp_track_info(self._h, _ptr(live), _ptr(nid), _ptr(ov)), "pp_track_info")
+        return {"live": live, "next_id": nid, "overflow": ov}
+
+    def _stamps_dt(self, stamps, batch):
+        """stamps of a detect*: (dt, the streams' new last stamps), or None without stamps.  Raises before anything is
+        queued; `_detect_resident` commits."""
+        if stamps is None:
+            return None
+        on, pc = self._get_tracking()
+        if not on:
+            raise ValueError("stamps: tracking is off (set_tracking first)")
+        return _trk.stamps_to_dt(self._last_stamp, stamps, batch, pc.period)
 
     def set_cache_budget(self, megabytes):
         """Last-level-cache budget of a pass in MiB (pp_set_cache_budget; default 256, 0 = off): layers whose maps exceed
@@ -712,7 +809,7 @@ class Engine:
         self._check(self._lib.pp_get_detections(self._h, _ptr(dets), _ptr(n)), "pp_get_detections")
         return dets, n
 
-    def detect(self, frames, rect=None, trv2c=None, on_numeric="f32", p2=None, image_shape=None, bbox=False):
+    def detect(self, frames, rect=None, trv2c=None, on_numeric="f32", p2=None, image_shape=None, bbox=False, stamps=None):
         """upload + detect_async + sync + detections.  on_numeric: what to do when the default arithmetic reports
         activations outside the float16 pieces' range (NumericError) -- "f32": switch this engine to the float32
         matrix instruction (it stays there: `gemm_precision()`), run the still-resident frames again and return those
@@ -721,7 +818,15 @@ class Engine:
         cropped to the camera frustum on the GPU (crop_to_image) before the pass -- once: the float32 re-run reads the
         cropped frames; rect and trv2c are then required.
         bbox=True (needs p2; image_shape only when the frames are to be cropped as well): set_projection(p2) for this
-        pass -- `bboxes(len(frames))` then holds the detections' image boxes."""
+        pass -- `bboxes(len(frames))` then holds the detections' image boxes.
+        stamps (tracking on): one time stamp in seconds per frame; stream b advances by the difference to its previous
+        stamp (the configuration's period the first time).  A stamp that does not increase raises ValueError before
+        anything is queued.  Without stamps every stream advances by the period.
+        With tracking on, on_numeric="f32" does NOT run a flagged pass again: the pass has advanced the streams of its
+        unflagged frames, a second run would advance them twice.  The engine switches to "f32" and the NumericError is
+        raised; the flagged frames' streams did not move (their dt and their stamps are spent), the next pass runs in
+        float32."""
+        dts = self._stamps_dt(stamps, len(frames))
         if bbox and p2 is None:
             raise ValueError("detect: bbox=True needs p2 (the camera matrix the boxes are projected by)")
         if (image_shape is not None and p2 is None) or (p2 is not None and image_shape is None and not bbox):
@@ -738,15 +843,21 @@ class Engine:
             r4, t4, p4 = (np.broadcast_to(np.asarray(m, np.float64), (B, 4, 4)) for m in (rect, trv2c, p2))
             shp = np.broadcast_to(np.asarray(image_shape), (B, 2))
             self.crop_to_image(np.stack([frustum.frustum_planes(r4[b], t4[b], p4[b], shp[b]) for b in range(B)]))
-        return self._detect_resident(on_numeric)
+        return self._detect_resident(on_numeric, dts)
 
-    def _detect_resident(self, on_numeric):
+    def _detect_resident(self, on_numeric, dts=None):
+        if dts is not None:
+            self.set_track_dt(dts[0])
+            self._last_stamp = dts[1]
         self.detect_async()
         self.sync()
         try:
             return self.detections()
         except NumericError:
             if on_numeric != "f32" or self.gemm_precision() == "f32":
+                raise
+            if self.tracking_on:      # the pass has stepped its unflagged streams: running it again would step them twice
+                self.set_gemm_precision("f32")
                 raise
         self.set_gemm_precision("f32")
         self.detect_async()
@@ -827,10 +938,10 @@ class Engine:
         staging._users.add(self)
         self._staged.append(staging)      # kept alive while a copy may still read it (see upload_async)
 
-    def _detect_after_ingest(self, batch, rect, trv2c, on_numeric):
+    def _detect_after_ingest(self, batch, rect, trv2c, on_numeric, dts=None):
         if rect is not None:
             self.set_calib(rect, trv2c, batch)
-        return self._detect_resident(on_numeric)
+        return self._detect_resident(on_numeric, dts)
 
     def ingest_pointcloud2(self, msgs, first=1, decimate=4, lift=None, return_points=False, features=None, mount=None):
         """Raw sensor_msgs/PointCloud2 messages -> the engine's resident frames, on the GPU: x y z out of the bytes,
@@ -891,13 +1002,15 @@ class Engine:
             name, args = "pp_ingest_pointcloud2_fields_async", args + (table, nf)
         self._ingest_async(name, staging, args, B)
 
-    def detect_pointcloud2(self, msgs, rect=None, trv2c=None, on_numeric="f32", features=None, mount=None, first=1, decimate=4):
+    def detect_pointcloud2(self, msgs, rect=None, trv2c=None, on_numeric="f32", features=None, mount=None, first=1, decimate=4,
+                           stamps=None):
         """ingest_pointcloud2 + detect_async + sync + detections: `detect` for raw camera messages (the reference's
         production mode, train.py:810-828).  rect / trv2c / on_numeric as `detect`; features / mount / first / decimate as
         ingest_pointcloud2 (a lidar feeding a 4-feature model: features=[FeatureField("intensity")],
-        mount=Mount(np.eye(3), np.eye(3), 0.0), first=0, decimate=1)."""
+        mount=Mount(np.eye(3), np.eye(3), 0.0), first=0, decimate=1); stamps as `detect`."""
+        dts = self._stamps_dt(stamps, len(msgs))
         self.ingest_pointcloud2(msgs, first=first, decimate=decimate, features=features, mount=mount)
-        return self._detect_after_ingest(len(msgs), rect, trv2c, on_numeric)
+        return self._detect_after_ingest(len(msgs), rect, trv2c, on_numeric, dts)
 
     # ---- depth-image ingest (pp_ingest_depth*) ----
     def ingest_depth(self, images, intrinsics, first=1, decimate=4, lift=None, depth_scale=0.001, z_min=0.0, z_max=np.inf,
@@ -932,11 +1045,12 @@ class Engine:
         cfg = _ingest_config(first, decimate, lift)
         self._ingest_async("pp_ingest_depth_async", staging, (layouts, len(tuples), ctypes.byref(cfg)), len(tuples))
 
-    def detect_depth(self, images, intrinsics, rect=None, trv2c=None, on_numeric="f32"):
+    def detect_depth(self, images, intrinsics, rect=None, trv2c=None, on_numeric="f32", stamps=None):
         """ingest_depth + detect_async + sync + detections: `detect_pointcloud2` for the depth images the messages are
-        computed from.  rect / trv2c / on_numeric as `detect`."""
+        computed from.  rect / trv2c / on_numeric / stamps as `detect`."""
+        dts = self._stamps_dt(stamps, len(images))
         self.ingest_depth(images, intrinsics)
-        return self._detect_after_ingest(len(images), rect, trv2c, on_numeric)
+        return self._detect_after_ingest(len(images), rect, trv2c, on_numeric, dts)
 
     # ---- camera-rig ingest (pp_ingest_rig_*) ----
     def ingest_rig_depth(self, frames, rig, return_points=False):
@@ -1017,16 +1131,19 @@ class Engine:
             name, args = "pp_ingest_rig_pointcloud2_fields_async", args + (table, nf)
         self._ingest_async(name, staging, args, staging.batch, len(rig))
 
-    def detect_rig_depth(self, frames, rig, rect=None, trv2c=None, on_numeric="f32"):
+    def detect_rig_depth(self, frames, rig, rect=None, trv2c=None, on_numeric="f32", stamps=None):
         """ingest_rig_depth + detect_async + sync + detections: `detect_depth` for a rig's images.  rect / trv2c /
-        on_numeric as `detect`."""
+        on_numeric / stamps as `detect`."""
+        dts = self._stamps_dt(stamps, len(frames))
         self.ingest_rig_depth(frames, rig)
-        return self._detect_after_ingest(len(frames), rect, trv2c, on_numeric)
+        return self._detect_after_ingest(len(frames), rect, trv2c, on_numeric, dts)
 
-    def detect_rig_pointcloud2(self, frames, rig, rect=None, trv2c=None, on_numeric="f32", features=None):
-        """ingest_rig_pointcloud2 + detect_async + sync + detections; features as ingest_rig_pointcloud2."""
+    def detect_rig_pointcloud2(self, frames, rig, rect=None, trv2c=None, on_numeric="f32", features=None, stamps=None):
+        """ingest_rig_pointcloud2 + detect_async + sync + detections; features as ingest_rig_pointcloud2, stamps as
+        `detect`."""
+        dts = self._stamps_dt(stamps, len(frames))
         self.ingest_rig_pointcloud2(frames, rig, features=features)
-        return self._detect_after_ingest(len(frames), rect, trv2c, on_numeric)
+        return self._detect_after_ingest(len(frames), rect, trv2c, on_numeric, dts)
 
     def intermediates(self, canvas=False):
         d, B = self.d, max(self._batches()[1], 1)

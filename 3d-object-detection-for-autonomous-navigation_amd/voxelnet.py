@@ -27,6 +27,7 @@ import os
 
 import numpy as np
 
+from . import tracking as _tracking
 from . import weights as _weights
 from .config import Derived
 from .engine import Engine
@@ -170,18 +171,32 @@ class VoxelNet:
         self.trainer.publish()
         return self.trainer
 
-    def detect(self, frames, rect=None, trv2c=None, image_idx=None, p2=None):
+    def _dicts(self, dets, n, batch, image_idx):
+        """The prediction dicts of the pass that has just run.  With tracking on (model.second.tracking, or
+        engine.set_tracking) each carries "track_id" ([n] int32, -1 for a row without a track) and "velocity" ([n, 3] float64,
+        the matched track's; zeros for none) -- None, like the other values, when nothing survives."""
+        bb = self._bboxes(batch)
+        idx = image_idx if image_idx is not None else list(range(batch))
+        out = [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(batch)]
+        if isinstance(self.engine, Engine) and self.engine.tracking_on:
+            tr, nt, _ = self.engine.tracks(batch)
+            for b, o in enumerate(out):
+                k = int(n[b])
+                o["track_id"] = _tracking.det_track_ids(tr[b], nt[b], k) if k else None
+                o["velocity"] = _tracking.det_track_velocity(tr[b], nt[b], k) if k else None
+        return out
+
+    def detect(self, frames, rect=None, trv2c=None, image_idx=None, p2=None, stamps=None):
         """Fused path: list of raw clouds -> list of prediction dicts.  p2 ([4,4] or [B,4,4]): required with
-        model.second.project_bbox, which puts the projected image boxes into "bbox"."""
+        model.second.project_bbox, which puts the projected image boxes into "bbox".  stamps (tracking on): the frames'
+        time stamps in seconds (Engine.detect)."""
         self._need_p2(p2, "detect")
         on = self.d.project_bbox
-        dets, n = self._detector().detect(frames, rect, trv2c, p2=p2 if on else None, bbox=on)
-        bb = self._bboxes(len(frames))
-        idx = image_idx if image_idx is not None else list(range(len(frames)))
-        return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(frames))]
+        dets, n = self._detector().detect(frames, rect, trv2c, p2=p2 if on else None, bbox=on, stamps=stamps)
+        return self._dicts(dets, n, len(frames), image_idx)
 
     def detect_pointcloud2(self, msgs, rect=None, trv2c=None, image_idx=None, p2=None, features=None, mount=None, first=1,
-                           decimate=4):
+                           decimate=4, stamps=None):
         """Fused path from raw sensor_msgs/PointCloud2 messages (the reference's production mode: ingest on the GPU,
         Engine.detect_pointcloud2) -> the same list of prediction dicts as `detect`; p2 as there.  features / mount / first /
         decimate as Engine.ingest_pointcloud2: a model with 4 point features takes its intensity column from the messages'
@@ -190,12 +205,11 @@ class VoxelNet:
         self._detector()
         if self.d.project_bbox:
             self.engine.set_projection(np.broadcast_to(np.asarray(p2, np.float64), (len(msgs), 4, 4)))
-        dets, n = self.engine.detect_pointcloud2(msgs, rect, trv2c, features=features, mount=mount, first=first, decimate=decimate)
-        bb = self._bboxes(len(msgs))
-        idx = image_idx if image_idx is not None else list(range(len(msgs)))
-        return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(msgs))]
+        dets, n = self.engine.detect_pointcloud2(msgs, rect, trv2c, features=features, mount=mount, first=first, decimate=decimate,
+                                                 stamps=stamps)
+        return self._dicts(dets, n, len(msgs), image_idx)
 
-    def detect_depth(self, images, intrinsics, rect=None, trv2c=None, image_idx=None, p2=None):
+    def detect_depth(self, images, intrinsics, rect=None, trv2c=None, image_idx=None, p2=None, stamps=None):
         """Fused path from raw depth images (sensor_msgs/Image, 16UC1 or 32FC1) and the camera's intrinsics
         (Engine.detect_depth: deprojection and ingest on the GPU) -> the same list of prediction dicts as
         `detect_pointcloud2` on the messages a point-cloud node computes from those images; p2 as in `detect`."""
@@ -203,10 +217,8 @@ class VoxelNet:
         self._detector()
         if self.d.project_bbox:
             self.engine.set_projection(np.broadcast_to(np.asarray(p2, np.float64), (len(images), 4, 4)))
-        dets, n = self.engine.detect_depth(images, intrinsics, rect, trv2c)
-        bb = self._bboxes(len(images))
-        idx = image_idx if image_idx is not None else list(range(len(images)))
-        return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(images))]
+        dets, n = self.engine.detect_depth(images, intrinsics, rect, trv2c, stamps=stamps)
+        return self._dicts(dets, n, len(images), image_idx)
 
     def _detect_rig(self, who, frames, rig, rect, trv2c, image_idx, p2, **feed):
         self._need_p2(p2, who)
@@ -214,20 +226,18 @@ class VoxelNet:
         if self.d.project_bbox:
             self.engine.set_projection(np.broadcast_to(np.asarray(p2, np.float64), (len(frames), 4, 4)))
         dets, n = getattr(self.engine, who)(frames, rig, rect, trv2c, **feed)
-        bb = self._bboxes(len(frames))
-        idx = image_idx if image_idx is not None else list(range(len(frames)))
-        return [self._to_dict(dets[b], int(n[b]), idx[b], None if bb is None else bb[b]) for b in range(len(frames))]
+        return self._dicts(dets, n, len(frames), image_idx)
 
-    def detect_rig_depth(self, frames, rig, rect=None, trv2c=None, image_idx=None, p2=None):
+    def detect_rig_depth(self, frames, rig, rect=None, trv2c=None, image_idx=None, p2=None, stamps=None):
         """Fused path from the depth images of a camera rig (Engine.detect_rig_depth: every frame holds the points of all
         its cameras, each under its own mount -- ingest.CameraRig) -> the same list of prediction dicts as `detect` on
         the host-concatenated frames; p2 as there."""
-        return self._detect_rig("detect_rig_depth", frames, rig, rect, trv2c, image_idx, p2)
+        return self._detect_rig("detect_rig_depth", frames, rig, rect, trv2c, image_idx, p2, stamps=stamps)
 
-    def detect_rig_pointcloud2(self, frames, rig, rect=None, trv2c=None, image_idx=None, p2=None, features=None):
+    def detect_rig_pointcloud2(self, frames, rig, rect=None, trv2c=None, image_idx=None, p2=None, features=None, stamps=None):
         """`detect_rig_depth` for the PointCloud2 messages of a camera rig (Engine.detect_rig_pointcloud2); features as
         Engine.ingest_rig_pointcloud2."""
-        return self._detect_rig("detect_rig_pointcloud2", frames, rig, rect, trv2c, image_idx, p2, features=features)
+        return self._detect_rig("detect_rig_pointcloud2", frames, rig, rect, trv2c, image_idx, p2, features=features, stamps=stamps)
 
     @staticmethod
     def _to_dict(dets, n, img_idx, bbox=None):

@@ -44,7 +44,9 @@ extern "C" {
  * pp_ingest_depth_async (declared behind pp_ingest_info, whose counts serve both feeds).  Then PP_RIG_MAX_SOURCES,
  * pp_ingest_rig_depth, pp_ingest_rig_depth_async, pp_ingest_rig_pointcloud2, pp_ingest_rig_pointcloud2_async,
  * pp_ingest_rig_info.  Then pp_pc2_feature, pp_ingest_pointcloud2_fields, pp_ingest_pointcloud2_fields_async,
- * pp_ingest_rig_pointcloud2_fields, pp_ingest_rig_pointcloud2_fields_async (declared behind pp_ingest_rig_info). */
+ * pp_ingest_rig_pointcloud2_fields, pp_ingest_rig_pointcloud2_fields_async (declared behind pp_ingest_rig_info).  Then
+ * PP_TRACK_MAX, pp_track_config, pp_track, pp_set_tracking, pp_get_tracking, pp_set_track_dt, pp_get_tracks,
+ * pp_track_update, pp_track_reset, pp_track_info. */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -1062,6 +1064,83 @@ typedef struct pp_publish_stats {
  * pp_finalize_weights replaces them.  PP_ERR_STATE while a training step is in flight. */
 int pp_publish_train_weights(pp_handle h, const float* params_dev, const float* state_dev);
 int pp_publish_info(pp_handle h, pp_publish_stats* out);
+
+/* ---- tracking: identities and velocities across the frames of a live feed ---------------------------------------------
+ * One track table per STREAM: frame b of every pass belongs to stream b, a handle has max_batch streams, and a pass that
+ * ran with tracking on advances each of its `batch` streams by one step behind its post-process (one more kernel in the
+ * pass's chain and its captured graph; the state never leaves the device).  The step, in float64 with + - * / and
+ * comparisons only (tracking.py of the Python package restates it operation for operation, and the kernel equals it bit
+ * for bit): predict every live track by the stream's dt (constant velocity, white-acceleration process noise q_acc);
+ * associate tracks and detection rows greedily by the smallest (BEV squared distance, slot, row) among the pairs with
+ * d2 <= gate * gate (and, class_aware, equal labels); update the matched tracks (scalar-gain Kalman update per axis,
+ * measurement variance r_pos; sizes blended by size_alpha; yaw, score, label from the row); age the others (freed after
+ * more than max_misses misses in a row); open a track in the lowest free slot for every unmatched row with
+ * score >= birth_score, in row order (no slot left: the row is dropped and the stream's overflow count goes up); output
+ * the live tracks in ascending slot order.  The reference has no tracker: nothing here is parity with it. */
+#define PP_TRACK_MAX 64 /* tracks per stream */
+
+typedef struct pp_track_config {
+    double gate;        /* association gate in metres (BEV centre distance, inclusive), > 0 */
+    double q_acc;       /* variance of the white acceleration, (m/s^2)^2, > 0 */
+    double r_pos;       /* measurement variance of a detection's centre per axis, m^2, > 0 */
+    double p0_pos;      /* position variance of a new track, m^2, > 0 */
+    double p0_vel;      /* velocity variance of a new track, (m/s)^2, > 0 */
+    double size_alpha;  /* weight of the new row in the size blend, 0 .. 1 */
+    double birth_score; /* least score of a row that may open a track */
+    double period;      /* seconds a stream advances by when pp_set_track_dt gave no value, > 0 */
+    int32_t max_misses; /* >= 0: a track is freed at its (max_misses + 1)-th miss in a row */
+    int32_t min_hits;   /* >= 1: `confirmed` becomes 1 at that many hits and stays */
+    int32_t class_aware;/* != 0: a pair must have equal labels */
+    int32_t reserved;
+} pp_track_config;
+
+typedef struct pp_track {
+    double state[6];    /* x y z vx vy vz (lidar frame; after the step's update) */
+    double size[3];     /* w l h */
+    double yaw;         /* of the last matched row */
+    float score;        /* of the last matched row */
+    int32_t id;         /* per stream, from 1, never reused until a reset */
+    int32_t label;
+    int32_t hits, misses, confirmed;
+    int32_t det_row;    /* the row of this step's detections the track was matched with or opened from, else -1 */
+    int32_t reserved;
+} pp_track;
+
+/* cfg == NULL: tracking off (the default); the tables and the configuration are kept.  Otherwise the configuration is
+ * validated (PP_ERR_ARG naming the field: a non-finite value, gate / q_acc / r_pos / p0_pos / p0_vel / period <= 0,
+ * size_alpha outside 0..1, max_misses < 0, min_hits < 1), written to device memory and tracking is on from the next
+ * pp_detect_async.  On / off is part of what a captured pass is keyed on; the parameters are not (the kernel reads them
+ * from device memory).  PP_ERR_UNSUPPORTED when the handle's rows per frame (pp_get_detection_rows) exceed the 128 the
+ * step's row bitmask holds -- also raised by the pass and by pp_track_update after a later change of the class mode;
+ * PP_ERR_STATE while a training step is in flight.  The stage calls (pp_predict ...) never track. */
+int pp_set_tracking(pp_handle h, const pp_track_config* cfg);
+/* *on: 0 / 1; cfg_out (may be NULL): the last configuration given (zeros before the first). */
+int pp_get_tracking(pp_handle h, int32_t* on, pp_track_config* cfg_out);
+/* Seconds by which the NEXT tracked step advances streams 0 .. batch - 1 (each finite and > 0, else PP_ERR_ARG naming the
+ * stream).  The values travel through a page-locked ring slot into device memory on the handle's stream, ahead of the pass
+ * that consumes them: two passes queued without a pp_sync each see their own.  A stream without a value advances by
+ * cfg.period.  A value is spent by the next tracked pass (or pp_track_update) that covers its stream, also when that pass
+ * flags the stream's frame; an UNTRACKED pass in between does not touch it.  PP_ERR_STATE before the first
+ * pp_set_tracking and while a training step is in flight. */
+int pp_set_track_dt(pp_handle h, const double* dt, int32_t batch);
+/* The tables of the last tracked pass or pp_track_update (waits for the stream): tracks [batch][PP_TRACK_MAX] (the live
+ * tracks of stream b in ascending slot order, zeros behind them), n_tracks [batch], overflow [batch] (rows dropped for
+ * want of a slot since the last reset; may be NULL).  PP_ERR_STATE when the last pass ran untracked (or none has run);
+ * PP_ERR_NUMERIC where pp_get_detections would return it -- a flagged frame leaves its stream's table untouched. */
+int pp_get_tracks(pp_handle h, pp_track* tracks, int32_t* n_tracks, int32_t* overflow);
+/* The same step on the handle's same tables, on host-given rows: dets [batch][rows] (rows 0 .. n_dets[b] - 1 of stream b
+ * are read: box3d_lidar, score, label), 0 <= n_dets[b] <= rows <= 128, dt [batch] or NULL (cfg.period).  Uploads into
+ * scratch of its own (a pass's results stay fetchable with pp_get_detections), synchronous; pp_get_tracks then returns
+ * this step's tables.  PP_ERR_ARG for rows < 1; PP_ERR_STATE before the first pp_set_tracking (tracking need not be on) and
+ * while a training step is in flight. */
+int pp_track_update(pp_handle h, const pp_detection* dets, const int32_t* n_dets, int32_t rows, int32_t batch,
+                    const double* dt);
+/* stream 0 .. max_batch - 1, or -1 for all: frees every track, the next id is 1 again, overflow 0 (waits for the stream).
+ * PP_ERR_STATE while a training step is in flight, like every tracking call that queues work or writes the tables. */
+int pp_track_reset(pp_handle h, int32_t stream);
+/* Per stream, [max_batch] each (any may be NULL): live tracks, the next id, overflow.  Waits for the stream and only
+ * reads, so it is allowed while a training step is in flight (it then waits for that step's launches as well). */
+int pp_track_info(pp_handle h, int32_t* live, int32_t* next_id, int32_t* overflow);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
