@@ -107,10 +107,14 @@ __global__ __launch_bounds__(LT) void k_loss_pixels(LossParams p) {
                 } else {
                     acc[3] += (double)l;
                 }
-                // d/dx: ce' = sigmoid(x) - t (inside the clip range); (1 - p_t)' = (1 - 2t) p (1 - p)
+                // d/dx: ce' = sigmoid(x) - t inside the clip range; (1 - p_t)' = (1 - 2t) p (1 - p).  At the two points
+                // where the reference's graph is not differentiable its gradient ops decide, and the kernel follows them:
+                // clip_by_value passes the gradient on its bounds and abs has gradient sign(0) = 0, so a logit of exactly
+                // +-0 (a zero-initialised head) gets ce' = 1 - t, not 1/2 - t; past the upper clip bound ce' = -t
+                const float dce = (x == 0.f) ? 1.f - t : (x > 10000.f ? -t : pr - t);
                 float dmod = 0.f;
                 if (p.gamma != 0.f) dmod = p.gamma * powf(om, p.gamma - 1.f) * (1.f - 2.f * t) * pr * (1.f - pr);
-                grow[nb + r * NCLS + c] = w * aw * (dmod * ce + mod * (pr - t)) * inv_b * p.cls_weight;
+                grow[nb + r * NCLS + c] = w * aw * (dmod * ce + mod * dce) * inv_b * p.cls_weight;
             }
             // ---- localisation: smooth L1 (sigma) on the code, the angle through sin(a - b) = sin a cos b - cos a sin b ----
             {

@@ -377,11 +377,14 @@ __global__ __launch_bounds__(PT) void k_postprocess(PostParams p) {
         }
         s_label[tid] = lab;
         s_score[tid] = 1.f / (1.f + expf(-lgt));
+        // without the direction head the row has no direction pair: columns nb + nc + 2 ar (+ 1) are padding or, with 27
+        // columns in use (3 anchors x (7 + 2 classes)), the first column of the NEXT pixel's row -- not read
         const float* d = hrow + nb + nc + ar * 2;
-        s_dir[tid] = (p.use_dir && d[1] > d[0]) ? 1 : 0;  // np.argmax: first maximum
+        const float d0 = p.use_dir ? d[0] : 0.f, d1 = p.use_dir ? d[1] : 0.f;
+        s_dir[tid] = (d1 > d0) ? 1 : 0;  // np.argmax: first maximum
         s_anchor[tid] = (int)a;
         {
-            bool rb = !pp_finite(d[0]) || !pp_finite(d[1]);
+            bool rb = !pp_finite(d0) || !pp_finite(d1);
 #pragma unroll
             for (int q = 0; q < 7; ++q) rb |= !pp_finite(e[q]);
             if (rb) s_bad = 1;      // (the class logits were checked by the scan)
