@@ -20,6 +20,7 @@ _VARIANT = os.path.splitext(os.path.basename(SO_PATH))[0]
 SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_nms.hip", "api_project.hip", "api_class_nms.hip", "api_metrics.hip", "api_publish.hip", "api_train.hip", "api_dataprep.hip", "voxelize.hip", "pfn.hip", "anchor_mask.hip", "backbone.hip", "postprocess.hip",
            "rotate_iou.hip", "rotate_nms.hip", "box_project.hip", "loss.hip", "metrics.hip", "optim.hip", "grad_clip.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip",
            "gt_database.hip", "eval_stats.hip", "frustum_crop.hip", "weight_publish.hip", "soft_nms.hip",
+           "api_sweeps.hip", "sweeps.hip",
            "api_track.hip", "track.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
@@ -49,6 +50,7 @@ EXPORTS = [
     "pp_gtdb_build", "pp_gtdb_count",
     "pp_eval_match", "pp_eval_pr",
     "pp_frustum_crop", "pp_frustum_crop_async", "pp_frustum_crop_info",
+    "pp_set_sweeps", "pp_get_sweeps", "pp_sweeps_accumulate", "pp_sweeps_accumulate_async", "pp_sweeps_info", "pp_sweeps_reset",
     "pp_set_nms_mode", "pp_get_nms_mode", "pp_rotate_nms",
     "pp_set_projection", "pp_get_projection", "pp_get_bboxes", "pp_box3d_to_bbox",
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
@@ -208,6 +210,7 @@ class PPDepthLayout(ctypes.Structure):
 PP_DEPTH_U16, PP_DEPTH_F32 = 0, 1      # pp_depth_layout.encoding
 PP_RIG_MAX_SOURCES = 16      # sources per frame of a pp_ingest_rig_* call
 PP_CROP_BACK = 1      # pp_frustum_crop* flags: bit 0
+PP_SWEEP_MAX = 8      # past sweeps per stream (pp_set_sweeps)
 PP_METRICS_COUNTS = 32      # int64 values of pp_head_metrics / pp_get_train_metrics
 PP_CLASS_NMS_JOINT, PP_CLASS_NMS_PER_CLASS = 0, 1      # enum pp_class_nms
 PP_NMS_STANDUP, PP_NMS_ROTATED, PP_NMS_SOFT = 0, 1, 2      # enum pp_nms_mode
@@ -244,6 +247,16 @@ class PPTrackConfig(ctypes.Structure):
         ("min_hits", ctypes.c_int32),
         ("class_aware", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
+    ]
+
+
+class PPSweepConfig(ctypes.Structure):
+    _fields_ = [
+        ("max_age", ctypes.c_double),
+        ("history", ctypes.c_int32),
+        ("capacity", ctypes.c_int32),
+        ("history_decimate", ctypes.c_int32),
+        ("time_feature", ctypes.c_int32),
     ]
 
 
@@ -464,6 +477,12 @@ def lib():
     L.pp_frustum_crop.argtypes = [vp, vp, i32, i32, vp, f32p, i64]
     L.pp_frustum_crop_async.argtypes = [vp, vp, i32, i32]
     L.pp_frustum_crop_info.argtypes = [vp, vp, i32]
+    L.pp_set_sweeps.argtypes = [vp, ctypes.POINTER(PPSweepConfig)]
+    L.pp_get_sweeps.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(PPSweepConfig)]
+    L.pp_sweeps_accumulate.argtypes = [vp, vp, vp, i32, vp, f32p, i64]
+    L.pp_sweeps_accumulate_async.argtypes = [vp, vp, vp, i32]
+    L.pp_sweeps_info.argtypes = [vp, vp, vp, vp, vp, i32]
+    L.pp_sweeps_reset.argtypes = [vp, i32]
     L.pp_set_nms_mode.argtypes = [vp, i32]
     L.pp_get_nms_mode.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_rotate_nms.argtypes = [ctypes.c_int, f32p, i64, ctypes.c_float, i32, i32, vp, ctypes.POINTER(i64)]

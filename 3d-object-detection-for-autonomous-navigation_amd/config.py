@@ -238,6 +238,23 @@ class Derived:
                 self.tracking = TrackConfig.from_any(tk).to_dict()
             except ValueError as err:
                 raise ValueError(f"model.second.tracking: {err}")
+        # not a key of the reference's YAML either (absent or False = off; True = the defaults): a dict of the
+        # sweeps.SweepConfig fields -- the engine then keeps the last sweeps of every stream on the GPU and
+        # Engine.accumulate_sweeps (or poses= of a detect*) carries them into the current frame (sweeps.py states the
+        # rule).  Echoed as a dict (capacity None: the engine's max_points_per_frame).
+        sw = s.get("sweeps")
+        if sw is None or sw is False:
+            self.sweeps = None
+        else:
+            from .sweeps import SweepConfig
+            if not (sw is True or isinstance(sw, dict)):
+                raise ValueError(f"model.second.sweeps: a dict of SweepConfig fields, True or False, got {sw!r}")
+            try:
+                c = SweepConfig.from_any(sw)
+                c.resolved(self.num_point_features, 1)      # (time_feature against this model's features)
+                self.sweeps = c.to_dict()
+            except ValueError as err:
+                raise ValueError(f"model.second.sweeps: {err}")
         er = config["eval_input_reader"]
         self.batch_size = int(er["batch_size"])
         self.anchor_area_threshold = er["anchor_area_threshold"]

@@ -623,6 +623,51 @@ int crop_chunks(int n);
 int crop_max_features();     // widest row (num_point_features) the kernels move
 void launch_frustum_crop(const CropParams& p, hipStream_t s);
 
+// sweeps.hip: the resident frames plus their streams' stored sweeps, carried into the current sensor frame (sweeps.py)
+struct SweepXf {               // p_c = M p_s + u of one used sweep, and its time lag
+    double m[9], u[3];
+    float dt;
+    int pad;
+};
+struct SweepChunk {            // up to SWEEP_CHUNK rows of one segment: the current rows, a used sweep, or the ring push
+    const float* src;          // first source row (rows `stride` apart)
+    float* dst;                // first destination row (rows back to back)
+    int rows;
+    int xf;                    // >= 0: index into the transform table; SWEEP_XF_CUR: current rows; SWEEP_XF_PUSH: raw copy
+    int stride;
+    int pad;
+};
+constexpr int SWEEP_CHUNK = 256;
+constexpr int SWEEP_XF_CUR = -1, SWEEP_XF_PUSH = -2;
+struct SweepParams {
+    const float* in;           // [sum n_b][F] the resident points (device memory, or a zero-copy feed's page-locked block)
+    const int* offsets_in;     // [batch + 1] their frame offsets: DEVICE values, the host holds bounds
+    float* out;                // [sum count_b][F] the other input buffer
+    int* offsets_out;          // [batch + 1]
+    int batch, F, nmax;        // nmax: max_points_per_frame, the cut of an output frame
+    int history, capacity, decimate, time_feature;
+    double max_age;
+    const double* call;        // [batch][13]: the current pose (12), the current stamp
+    // the streams' rings, slots = history + 1 per stream
+    float* ring;               // [B][slots][capacity][F]
+    int* slot_cnt;             // [B][slots] rows stored
+    int* slot_valid;           // [B][slots] the slot holds a sweep
+    double* slot_pose;         // [B][slots][12]
+    double* slot_stamp;        // [B][slots]
+    int* head;                 // [B] the slot the next call writes (the oldest sweep's)
+    SweepXf* xf;               // [batch][history]
+    SweepChunk* segs;          // [batch][history + 2] the frames' segments, as chunks of any length (plan scratch)
+    int* seg_chunk0;           // [batch][history + 2] first chunk of each segment
+    int* frame_chunks;         // [batch + 1] chunks per frame -> their exclusive scan
+    SweepChunk* chunks;        // [chunk_cap] the move launch's table
+    int* nchunks;              // [1] entries written
+    int chunk_cap;
+    int chunk_bound;           // the host's bound on *nchunks: the move launch's grid
+    int *count, *used, *truncated, *push_truncated;   // [batch] pp_sweeps_info
+};
+int sweep_chunks(int n);       // chunks of a segment of n rows
+void launch_sweeps(const SweepParams& p, hipStream_t s);
+
 // weight_publish.hip: the trainer's flat parameter / state buffers -> the detector's weight arrays, on the device
 enum PubKind {
     PUB_PFN_W,       // out [FA][cout] = params[src] * scale[c]

@@ -4,7 +4,8 @@
 // augmentation, GT sampling, object database; api_eval.hip: the AP evaluator (needs no handle); api_nms.hip: the detector's NMS rule and the standalone rotated NMS;
 // api_project.hip: the detector's image boxes and the standalone projection; api_class_nms.hip: joint / per-class suppression;
 // api_metrics.hip: the training metrics' counts; api_publish.hip: a trainer's weights into the detector, on the device;
-// api_track.hip: the per-stream track tables behind the detector's post-process.
+// api_track.hip: the per-stream track tables behind the detector's post-process; api_sweeps.hip: the per-stream sweep rings
+// in front of the pass.
 #pragma once
 
 #include <cmath>
@@ -269,6 +270,25 @@ struct pp_engine {
         hipEvent_t ev_main = nullptr;      // orders an asynchronous crop (copy stream) behind the main stream
         int batch = 0;                     // frames of the last crop (pp_frustum_crop_info)
     } crop;
+    struct Sweeps {                        // multi-sweep accumulation (pp_set_sweeps, pp_sweeps_accumulate*; api_sweeps.hip)
+        bool on = false;                   // pp_set_sweeps gave a configuration and has not taken it back
+        pp_sweep_config cfg = {};          // the configuration in force, capacity filled in (history 0: no ring yet)
+        // the streams' rings (SweepParams), made by pp_set_sweeps and freed by sweeps_release: not in `allocs`
+        float* ring = nullptr;
+        int *slot_cnt = nullptr, *slot_valid = nullptr, *head = nullptr;
+        double *slot_pose = nullptr, *slot_stamp = nullptr;
+        SweepXf* xf = nullptr;
+        SweepChunk *segs = nullptr, *chunks = nullptr;
+        int *seg_chunk0 = nullptr, *frame_chunks = nullptr, *nchunks = nullptr;
+        int chunk_cap = 0;
+        int* info = nullptr;               // [4][B]: count, used, truncated, push_truncated
+        double* d_call = nullptr;          // [B][13] the call's poses and stamps
+        double* h_ring = nullptr;          // pinned [OFF_RING][B][13]: they travel like the offsets, slot by slot
+        hipEvent_t ev_main = nullptr;      // orders an asynchronous call (copy stream) behind the main stream
+        std::vector<double> last_stamp;    // [B] per stream: the last stamp accepted (NaN: none)
+        std::vector<int> stored;           // [B] per stream: sweeps its ring holds at most (the host's bound)
+        int batch = 0;                     // frames of the last call (pp_sweeps_info)
+    } swp;
 
     struct Metrics {                       // training metrics (pp_head_metrics / pp_set_train_metrics; api_metrics.hip: ensure_metrics)
         bool on = false;                   // pp_set_train_metrics: the following steps count
@@ -482,6 +502,7 @@ int ensure_loss_buffers(pp_engine* e);                  // api_train.hip
 int track_check_pass(pp_engine* e);                     // api_track.hip: what a tracked pass refuses, before anything is queued
 int run_track(pp_engine* e, int batch);                 // api_track.hip: k_track_step on this pass's d_dets / d_ndets
 void track_release(pp_engine* e);                       // ... what pp_destroy frees of it (page-locked memory, events)
+void sweeps_release(pp_engine* e);                      // api_sweeps.hip: what pp_destroy frees of the sweep rings
 int ensure_metrics(pp_engine* e);                       // api_metrics.hip
 void fill_metrics_params(pp_engine* e, int batch, MetricsParams& p);   // ... on the handle's head map and loss.labels
 // ---- api_dataprep.hip: what the fused training steps (api_train.hip) queue ----

@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib
 from . import soft_nms as _soft
 from . import tracking as _trk
+from . import sweeps as _swp
 from .anchors import build_anchor_cells, build_anchors
 from .config import Derived
 from .weights import check_weights
@@ -392,6 +393,9 @@ class Engine:
         self._last_stamp = np.full(self.max_batch, np.nan)      # per stream: the last time stamp a detect* was given
         if d.tracking is not None:
             self.set_tracking(d.tracking)
+        self._sweep_last = np.full(self.max_batch, np.nan)      # per stream: the last stamp an accumulate_sweeps* was given
+        if d.sweeps is not None:
+            self.set_sweeps(d.sweeps)
         if weights is not None:
             self.load_weights(weights)
 
@@ -809,7 +813,8 @@ class Engine:
         self._check(self._lib.pp_get_detections(self._h, _ptr(dets), _ptr(n)), "pp_get_detections")
         return dets, n
 
-    def detect(self, frames, rect=None, trv2c=None, on_numeric="f32", p2=None, image_shape=None, bbox=False, stamps=None):
+    def detect(self, frames, rect=None, trv2c=None, on_numeric="f32", p2=None, image_shape=None, bbox=False, stamps=None,
+               poses=None):
         """upload + detect_async + sync + detections.  on_numeric: what to do when the default arithmetic reports
         activations outside the float16 pieces' range (NumericError) -- "f32": switch this engine to the float32
         matrix instruction (it stays there: `gemm_precision()`), run the still-resident frames again and return those
@@ -825,8 +830,10 @@ class Engine:
         With tracking on, on_numeric="f32" does NOT run a flagged pass again: the pass has advanced the streams of its
         unflagged frames, a second run would advance them twice.  The engine switches to "f32" and the NumericError is
         raised; the flagged frames' streams did not move (their dt and their stamps are spent), the next pass runs in
-        float32."""
-        dts = self._stamps_dt(stamps, len(frames))
+        float32.
+        poses ([B, 3, 4] sensor-to-fixed transforms; needs set_sweeps and stamps): accumulate_sweeps(poses, stamps) runs
+        between the upload (and the crop) and the pass -- once: the float32 re-run reads the accumulated frames."""
+        sweep, dts = self._pose_args(poses, stamps, len(frames), "detect")
         if bbox and p2 is None:
             raise ValueError("detect: bbox=True needs p2 (the camera matrix the boxes are projected by)")
         if (image_shape is not None and p2 is None) or (p2 is not None and image_shape is None and not bbox):
@@ -843,9 +850,11 @@ class Engine:
             r4, t4, p4 = (np.broadcast_to(np.asarray(m, np.float64), (B, 4, 4)) for m in (rect, trv2c, p2))
             shp = np.broadcast_to(np.asarray(image_shape), (B, 2))
             self.crop_to_image(np.stack([frustum.frustum_planes(r4[b], t4[b], p4[b], shp[b]) for b in range(B)]))
-        return self._detect_resident(on_numeric, dts)
+        return self._detect_resident(on_numeric, dts, sweep)
 
-    def _detect_resident(self, on_numeric, dts=None):
+    def _detect_resident(self, on_numeric, dts=None, sweep=None):
+        if sweep is not None:         # (before the pass, and not again before the float32 re-run below)
+            self.accumulate_sweeps(*sweep)
         if dts is not None:
             self.set_track_dt(dts[0])
             self._last_stamp = dts[1]
@@ -912,6 +921,108 @@ class Engine:
         self._check(self._lib.pp_frustum_crop_info(self._h, _ptr(kept), B), "pp_frustum_crop_info")
         return kept[:B]
 
+    # ---- multi-sweep accumulation (pp_set_sweeps, pp_sweeps_accumulate*; sweeps.py states the rule) ----
+    def set_sweeps(self, cfg):
+        """A sweeps.SweepConfig, a dict of its fields or True (the defaults): the engine keeps the last `history` sweeps of
+        every stream (frame b is stream b) on the GPU and `accumulate_sweeps` carries them into the current frame.  The ring
+        is allocated here; a configuration with another history or capacity forgets the streams' history.  None: off (the
+        default); the ring is kept.  The config key model.second.sweeps selects it at construction."""
+        if cfg is None or cfg is False:
+            self._check(self._lib.pp_set_sweeps(self._h, None), "pp_set_sweeps")
+            return
+        c = _swp.SweepConfig.from_any(cfg).resolved(self.d.num_point_features, self.max_points_per_frame)
+        pc = _lib.PPSweepConfig()
+        for f, v in c.to_dict().items():
+            setattr(pc, f, v)
+        on, old = self._get_sweeps()
+        self._check(self._lib.pp_set_sweeps(self._h, ctypes.byref(pc)), "pp_set_sweeps")
+        if (old.history, old.capacity) != (c.history, c.capacity):      # the ring was re-made: the stamps went with it
+            self._sweep_last[:] = np.nan
+
+    def _get_sweeps(self):
+        on, pc = ctypes.c_int32(0), _lib.PPSweepConfig()
+        self._check(self._lib.pp_get_sweeps(self._h, ctypes.byref(on), ctypes.byref(pc)), "pp_get_sweeps")
+        return bool(on.value), pc
+
+    def sweeps(self):
+        """The SweepConfig in force (capacity filled in), or None while the stage is off."""
+        on, pc = self._get_sweeps()
+        if not on:
+            return None
+        return _swp.SweepConfig(**{f.name: getattr(pc, f.name) for f in dataclasses.fields(_swp.SweepConfig)})
+
+    def _sweep_call(self, poses, stamps, who):
+        """What accumulate_sweeps* refuse before anything is queued; returns (poses, stamps, the streams' new stamps)."""
+        if not self._get_sweeps()[0]:
+            raise RuntimeError(f"{who}: sweeps are not configured (set_sweeps first)")
+        B = np.asarray(poses).shape[0] if np.asarray(poses).ndim == 3 else -1
+        if B > self.max_batch:
+            raise ValueError(f"{who}: {B} poses, the engine has {self.max_batch} streams")
+        return _swp.check_call(poses, stamps, B, self._sweep_last[:max(B, 0)])
+
+    def accumulate_sweeps(self, poses, stamps, return_points=False):
+        """Carries every stream's stored sweeps into the resident frames, on the GPU (pp_sweeps_accumulate), exactly as
+        sweeps.SweepAccumulator.accumulate does on the host; then stores the original frames in the streams' rings.  poses:
+        [B, 3, 4] float64 sensor-to-fixed transforms (sweeps.pose_from_xyyaw / pose_from_matrix), stamps: [B] seconds.
+        Works on any resident frames, also ingested ones whose sizes only the device knows.  The accumulated frames replace
+        the resident ones, as after an upload.  Returns the output frames' rows, int32 [B]; return_points: (counts, [B
+        float32 arrays [count_b, F]])."""
+        P, S, new_last = self._sweep_call(poses, stamps, "accumulate_sweeps")
+        B, F = len(P), self.d.num_point_features
+        counts = np.zeros(max(B, 1), np.int32)
+        cap = B * self.max_points_per_frame if return_points else 0
+        pts = np.empty((max(cap, 1), F), np.float32) if return_points else None
+        self._check(self._lib.pp_sweeps_accumulate(self._h, _ptr(P), _ptr(S), B, _ptr(counts), _ptr(pts), ctypes.c_int64(cap)),
+                    "pp_sweeps_accumulate")
+        self._sweep_last[:B] = new_last
+        counts = counts[:B]
+        off = np.zeros(B + 1, np.int32)
+        off[1:] = np.cumsum(counts)
+        self._offsets = off
+        self._sweep_batch = B
+        if not return_points:
+            return counts
+        return counts, [pts[off[b]:off[b + 1]].copy() for b in range(B)]
+
+    def accumulate_sweeps_async(self, poses, stamps):
+        """accumulate_sweeps without waiting (pp_sweeps_accumulate_async): on the copy stream behind an upload_async, an
+        asynchronous ingest or crop, the voxeliser behind it; the counts stay on the device (sweeps_info reads them back)
+        and the engine is left as after an ingest."""
+        P, S, new_last = self._sweep_call(poses, stamps, "accumulate_sweeps_async")
+        self._check(self._lib.pp_sweeps_accumulate_async(self._h, _ptr(P), _ptr(S), len(P)), "pp_sweeps_accumulate_async")
+        self._sweep_last[:len(P)] = new_last
+        self._offsets = None
+        self._sweep_batch = len(P)
+
+    def sweeps_info(self):
+        """Per frame of the last accumulate (waits for it), int32 [B] each: `count` output rows, `used` sweeps, rows
+        `truncated` at max_points_per_frame, rows `push_truncated` at the capacity when the frame was stored."""
+        B = getattr(self, "_sweep_batch", 0)
+        out = {k: np.zeros(max(B, 1), np.int32) for k in ("count", "used", "truncated", "push_truncated")}
+        self._check(self._lib.pp_sweeps_info(self._h, *(_ptr(v) for v in out.values()), B), "pp_sweeps_info")
+        return {k: v[:B] for k, v in out.items()}
+
+    def sweeps_reset(self, stream=None):
+        """Forgets the stored sweeps and the last stamp of `stream` (None: of all streams)."""
+        s = -1 if stream is None else int(stream)
+        self._check(self._lib.pp_sweeps_reset(self._h, s), "pp_sweeps_reset")
+        if s < 0:
+            self._sweep_last[:] = np.nan
+        else:
+            self._sweep_last[s] = np.nan
+
+    def _pose_args(self, poses, stamps, batch, who):
+        """poses= of a detect*: checked before anything is queued (None: no accumulation); stamps then serve the sweeps, and
+        the tracker too when tracking is on."""
+        if poses is None:
+            return None, self._stamps_dt(stamps, batch)
+        if stamps is None:
+            raise ValueError(f"{who}: poses needs stamps (one time stamp in seconds per frame)")
+        if np.asarray(poses).shape[:1] != (batch,):
+            raise ValueError(f"{who}: {np.asarray(poses).shape[0] if np.asarray(poses).ndim else 0} poses for {batch} frames")
+        self._sweep_call(poses, stamps, who)
+        return (poses, stamps), (self._stamps_dt(stamps, batch) if self.tracking_on else None)
+
     # ---- live-camera ingest (pp_ingest_*; ingest.py states the rule; DESIGN 7.1c, 7.1m, 7.1n, 7.1o) ----
     def _ingest_sync(self, name, args, batch, cap, nf, cameras=None):
         """One synchronous pp_ingest_* call.  args: what the call takes between the handle and the parity tap; cap: the
@@ -938,10 +1049,10 @@ class Engine:
         staging._users.add(self)
         self._staged.append(staging)      # kept alive while a copy may still read it (see upload_async)
 
-    def _detect_after_ingest(self, batch, rect, trv2c, on_numeric, dts=None):
+    def _detect_after_ingest(self, batch, rect, trv2c, on_numeric, dts=None, sweep=None):
         if rect is not None:
             self.set_calib(rect, trv2c, batch)
-        return self._detect_resident(on_numeric, dts)
+        return self._detect_resident(on_numeric, dts, sweep)
 
     def ingest_pointcloud2(self, msgs, first=1, decimate=4, lift=None, return_points=False, features=None, mount=None):
         """Raw sensor_msgs/PointCloud2 messages -> the engine's resident frames, on the GPU: x y z out of the bytes,
@@ -1003,14 +1114,14 @@ class Engine:
         self._ingest_async(name, staging, args, B)
 
     def detect_pointcloud2(self, msgs, rect=None, trv2c=None, on_numeric="f32", features=None, mount=None, first=1, decimate=4,
-                           stamps=None):
+                           stamps=None, poses=None):
         """ingest_pointcloud2 + detect_async + sync + detections: `detect` for raw camera messages (the reference's
         production mode, train.py:810-828).  rect / trv2c / on_numeric as `detect`; features / mount / first / decimate as
         ingest_pointcloud2 (a lidar feeding a 4-feature model: features=[FeatureField("intensity")],
-        mount=Mount(np.eye(3), np.eye(3), 0.0), first=0, decimate=1); stamps as `detect`."""
-        dts = self._stamps_dt(stamps, len(msgs))
+        mount=Mount(np.eye(3), np.eye(3), 0.0), first=0, decimate=1); stamps and poses as `detect`."""
+        sweep, dts = self._pose_args(poses, stamps, len(msgs), "detect_pointcloud2")
         self.ingest_pointcloud2(msgs, first=first, decimate=decimate, features=features, mount=mount)
-        return self._detect_after_ingest(len(msgs), rect, trv2c, on_numeric, dts)
+        return self._detect_after_ingest(len(msgs), rect, trv2c, on_numeric, dts, sweep)
 
     # ---- depth-image ingest (pp_ingest_depth*) ----
     def ingest_depth(self, images, intrinsics, first=1, decimate=4, lift=None, depth_scale=0.001, z_min=0.0, z_max=np.inf,
@@ -1045,12 +1156,12 @@ class Engine:
         cfg = _ingest_config(first, decimate, lift)
         self._ingest_async("pp_ingest_depth_async", staging, (layouts, len(tuples), ctypes.byref(cfg)), len(tuples))
 
-    def detect_depth(self, images, intrinsics, rect=None, trv2c=None, on_numeric="f32", stamps=None):
+    def detect_depth(self, images, intrinsics, rect=None, trv2c=None, on_numeric="f32", stamps=None, poses=None):
         """ingest_depth + detect_async + sync + detections: `detect_pointcloud2` for the depth images the messages are
-        computed from.  rect / trv2c / on_numeric / stamps as `detect`."""
-        dts = self._stamps_dt(stamps, len(images))
+        computed from.  rect / trv2c / on_numeric / stamps / poses as `detect`."""
+        sweep, dts = self._pose_args(poses, stamps, len(images), "detect_depth")
         self.ingest_depth(images, intrinsics)
-        return self._detect_after_ingest(len(images), rect, trv2c, on_numeric, dts)
+        return self._detect_after_ingest(len(images), rect, trv2c, on_numeric, dts, sweep)
 
     # ---- camera-rig ingest (pp_ingest_rig_*) ----
     def ingest_rig_depth(self, frames, rig, return_points=False):
@@ -1131,19 +1242,20 @@ class Engine:
             name, args = "pp_ingest_rig_pointcloud2_fields_async", args + (table, nf)
         self._ingest_async(name, staging, args, staging.batch, len(rig))
 
-    def detect_rig_depth(self, frames, rig, rect=None, trv2c=None, on_numeric="f32", stamps=None):
+    def detect_rig_depth(self, frames, rig, rect=None, trv2c=None, on_numeric="f32", stamps=None, poses=None):
         """ingest_rig_depth + detect_async + sync + detections: `detect_depth` for a rig's images.  rect / trv2c /
-        on_numeric / stamps as `detect`."""
-        dts = self._stamps_dt(stamps, len(frames))
+        on_numeric / stamps / poses as `detect`."""
+        sweep, dts = self._pose_args(poses, stamps, len(frames), "detect_rig_depth")
         self.ingest_rig_depth(frames, rig)
-        return self._detect_after_ingest(len(frames), rect, trv2c, on_numeric, dts)
+        return self._detect_after_ingest(len(frames), rect, trv2c, on_numeric, dts, sweep)
 
-    def detect_rig_pointcloud2(self, frames, rig, rect=None, trv2c=None, on_numeric="f32", features=None, stamps=None):
-        """ingest_rig_pointcloud2 + detect_async + sync + detections; features as ingest_rig_pointcloud2, stamps as
-        `detect`."""
-        dts = self._stamps_dt(stamps, len(frames))
+    def detect_rig_pointcloud2(self, frames, rig, rect=None, trv2c=None, on_numeric="f32", features=None, stamps=None,
+                               poses=None):
+        """ingest_rig_pointcloud2 + detect_async + sync + detections; features as ingest_rig_pointcloud2, stamps and
+        poses as `detect`."""
+        sweep, dts = self._pose_args(poses, stamps, len(frames), "detect_rig_pointcloud2")
         self.ingest_rig_pointcloud2(frames, rig, features=features)
-        return self._detect_after_ingest(len(frames), rect, trv2c, on_numeric, dts)
+        return self._detect_after_ingest(len(frames), rect, trv2c, on_numeric, dts, sweep)
 
     def intermediates(self, canvas=False):
         d, B = self.d, max(self._batches()[1], 1)

@@ -46,7 +46,9 @@ extern "C" {
  * pp_ingest_rig_info.  Then pp_pc2_feature, pp_ingest_pointcloud2_fields, pp_ingest_pointcloud2_fields_async,
  * pp_ingest_rig_pointcloud2_fields, pp_ingest_rig_pointcloud2_fields_async (declared behind pp_ingest_rig_info).  Then
  * PP_TRACK_MAX, pp_track_config, pp_track, pp_set_tracking, pp_get_tracking, pp_set_track_dt, pp_get_tracks,
- * pp_track_update, pp_track_reset, pp_track_info. */
+ * pp_track_update, pp_track_reset, pp_track_info.  Then PP_SWEEP_MAX, pp_sweep_config, pp_set_sweeps, pp_get_sweeps,
+ * pp_sweeps_accumulate, pp_sweeps_accumulate_async, pp_sweeps_info, pp_sweeps_reset (declared behind
+ * pp_frustum_crop_info: the stage sits where the crop sits). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -981,6 +983,64 @@ int pp_frustum_crop_async(pp_handle h, const double* planes, int32_t batch, int3
 /* The kept counts of the last crop (waits for it).  PP_ERR_STATE when none has run, PP_ERR_ARG when `batch` is not that
  * call's. */
 int pp_frustum_crop_info(pp_handle h, int32_t* kept_out, int32_t batch);
+
+/* ---- multi-sweep accumulation (sweeps.py of the Python package states the rule) --------------------------- */
+/* Carries the last few sweeps of every stream (frame b of a call is stream b) into the current sensor frame under the ego
+ * poses, on the GPU, between the feed and the pass: the RESIDENT frames become the resident frames plus their history.
+ * A pose is 12 float64, the rows of [R | t] (3 x 4), mapping the sensor frame to a fixed frame: p_fixed = R p + t.  Per
+ * stream a ring of history + 1 slots lives on the device (rows, row count, pose, stamp per slot).  One call, per stream:
+ *   1. the used sweeps: the stored ones, newest first, with 0 < stamp_c - stamp_s <= max_age (float64);
+ *   2. per used sweep M = R_c^T R_s, every entry ((a0 b0 + a1 b1) + a2 b2), d = t_s - t_c, u = R_c^T d in the same order
+ *      -- float64, + - * only, products and sums rounded separately, computed on the device;
+ *   3. output: the current rows, bit-unchanged (column time_feature, when >= 0, set to 0.0f); then each used sweep's rows
+ *      in stored order, x' = (float)(((M00 x + M01 y) + M02 z) + u0) on the widened float32 coordinates (y', z' alike),
+ *      column time_feature = (float)(stamp_c - stamp_s), every other column copied bitwise;
+ *   4. the output frame is cut at max_points_per_frame rows (`truncated` counts the rows dropped; the cut may fall inside
+ *      a sweep); frames are packed back to back;
+ *   5. the ORIGINAL current frame is stored as its rows 0, j, 2j ... (j = history_decimate), cut at `capacity`
+ *      (`push_truncated`), with its pose and stamp, in the slot that holds the oldest sweep -- never one this call reads.
+ * The reference has no such path: nothing here is parity with it.  The same calls give the same bytes on every run. */
+#define PP_SWEEP_MAX 8 /* past sweeps per stream */
+
+typedef struct pp_sweep_config {
+    double max_age;           /* seconds, finite and > 0: stored sweeps older than this are not used */
+    int32_t history;          /* 1 .. PP_SWEEP_MAX past sweeps kept per stream */
+    int32_t capacity;         /* rows per stored sweep, 1 .. ; 0: max_points_per_frame */
+    int32_t history_decimate; /* j >= 1 */
+    int32_t time_feature;     /* -1, or the column 3 .. num_point_features - 1 overwritten with the time lag */
+} pp_sweep_config;
+
+/* cfg == NULL: the stage is off (the default); the ring and its history are kept.  Otherwise the configuration is
+ * validated (PP_ERR_ARG naming the field) and the ring is allocated here: max_batch x (history + 1) x capacity rows;
+ * PP_ERR_HIP naming the bytes when the device cannot hold it (the stage is then off).  A configuration with another
+ * history or capacity re-makes the ring and forgets every stream's history; one that differs in the other fields keeps
+ * it.  PP_ERR_UNSUPPORTED for rows wider than the frustum crop moves; PP_ERR_STATE while a training step is in flight. */
+int pp_set_sweeps(pp_handle h, const pp_sweep_config* cfg);
+/* *on: 0 / 1; cfg_out (may be NULL): the configuration in force, capacity filled in (zeros before the first). */
+int pp_get_sweeps(pp_handle h, int32_t* on, pp_sweep_config* cfg_out);
+/* One call on the resident frames: poses [batch][12], stamps [batch] (seconds).  The frames are read where they lie --
+ * their sizes are read on the DEVICE, so the state after any pp_ingest_* or pp_frustum_crop_async is accepted -- and the
+ * output is written into the handle's other input buffer, which becomes the resident one.  Refused before anything is
+ * queued, the handle and the history untouched: PP_ERR_STATE when pp_set_sweeps has not turned the stage on, with no
+ * frames resident or while a training step is in flight; PP_ERR_ARG for a batch other than the resident one, a
+ * non-finite pose or stamp, a rotation whose R R^T differs from the identity by more than 1e-6 in an entry, or a stamp
+ * that does not increase over the stream's previous one (pp_last_error names the stream).
+ * Synchronous, on the handle's stream: waits, writes counts_out [batch] (the output frames' rows) and takes them as the
+ * frames' sizes, as pp_frustum_crop does.  points_out (may be NULL): the output frames [sum counts][F], back to back;
+ * points_capacity in points, PP_ERR_ARG when it is below the total (the call has happened all the same). */
+int pp_sweeps_accumulate(pp_handle h, const double* poses, const double* stamps, int32_t batch, int32_t* counts_out,
+                         float* points_out, int64_t points_capacity);
+/* Same without waiting, on the copy stream behind an asynchronous upload, ingest or crop, the voxeliser behind it there;
+ * poses and stamps are copied before the call returns.  The counts stay on the device (pp_sweeps_info): the handle is
+ * left as after an ingest, everything behind the call sized from bounds. */
+int pp_sweeps_accumulate_async(pp_handle h, const double* poses, const double* stamps, int32_t batch);
+/* Of the last call (waits for it), [batch] each, any may be NULL: output rows, used sweeps, rows dropped at
+ * max_points_per_frame, rows cut at `capacity` when the frame was stored.  PP_ERR_STATE when none has run, PP_ERR_ARG
+ * when `batch` is not that call's. */
+int pp_sweeps_info(pp_handle h, int32_t* counts, int32_t* used, int32_t* truncated, int32_t* push_truncated, int32_t batch);
+/* stream 0 .. max_batch - 1, or -1 for all: forgets the stream's stored sweeps and its last stamp (waits for the work
+ * queued).  PP_ERR_STATE while a training step is in flight. */
+int pp_sweeps_reset(pp_handle h, int32_t stream);
 
 /* The handle's HIP stream (hipStream_t as void*).  A caller that enqueues its own device work behind a pp_train_step_async
  * -- the gradient all-reduce and pp_adamw_step_device of the optimizer step (train.py:301) -- does it on this stream and
