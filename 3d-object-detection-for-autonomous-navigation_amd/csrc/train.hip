@@ -1243,7 +1243,8 @@ void launch_relu_mask(const float* Z, const float4* coef, long n, int C, unsigne
 struct RowMap { int k, in_h, in_w; };
 __device__ __forceinline__ long map_row(const RowMap& m, long r) {
     if (m.k <= 1) return r;
-    // rows < 2^31 (launcher): 32-bit arithmetic; kernel == stride k is 1, 2 or 4: the tap split is a shift
+    // rows < 2^31 (launcher): 32-bit arithmetic; kernel == stride k of 2 or 4 (every shipped layout): the tap split is a
+    // shift; any other k (8 with upsample_strides [2,4,8]) divides
     const unsigned kk = (unsigned)(m.k * m.k), ur = (unsigned)r;
     unsigned p, tapr;
     if (m.k == 2) { p = ur >> 2; tapr = ur & 3u; }
