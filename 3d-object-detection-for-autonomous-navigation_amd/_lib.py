@@ -51,6 +51,7 @@ EXPORTS = [
     "pp_eval_match", "pp_eval_pr",
     "pp_frustum_crop", "pp_frustum_crop_async", "pp_frustum_crop_info",
     "pp_set_sweeps", "pp_get_sweeps", "pp_sweeps_accumulate", "pp_sweeps_accumulate_async", "pp_sweeps_info", "pp_sweeps_reset",
+    "pp_set_track_pose", "pp_get_tracks_fixed",
     "pp_set_nms_mode", "pp_get_nms_mode", "pp_rotate_nms",
     "pp_set_projection", "pp_get_projection", "pp_get_bboxes", "pp_box3d_to_bbox",
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
@@ -497,6 +498,8 @@ def lib():
     L.pp_track_update.argtypes = [vp, vp, vp, i32, i32, vp]
     L.pp_track_reset.argtypes = [vp, i32]
     L.pp_track_info.argtypes = [vp, vp, vp, vp]
+    L.pp_set_track_pose.argtypes = [vp, vp, i32]
+    L.pp_get_tracks_fixed.argtypes = [vp, vp, vp]
     L.pp_set_projection.argtypes = [vp, vp, i32]
     L.pp_get_projection.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_get_bboxes.argtypes = [vp, vp]

@@ -8,8 +8,6 @@ static_assert(sizeof(SweepChunk) == 32 && sizeof(SweepXf) == 104, "sweeps.hip re
 
 namespace {
 
-constexpr double ORTHO_TOL = 1e-6;
-
 void free_ring(pp_engine* e) {
     pp_engine::Sweeps& g = e->swp;
     for (void* p : {(void*)g.ring, (void*)g.slot_cnt, (void*)g.slot_valid, (void*)g.head, (void*)g.slot_pose, (void*)g.slot_stamp,
@@ -97,15 +95,9 @@ int check_sweeps(pp_engine* e, const char* who, const double* poses, const doubl
     if (batch != e->cur_batch) return fail(e, PP_ERR_ARG, "%s: %d frames are resident, batch is %d", who, e->cur_batch, batch);
     for (int b = 0; b < batch; ++b) {
         const double* P = poses + (size_t)b * 12;
-        for (int i = 0; i < 12; ++i)
-            if (!std::isfinite(P[i])) return fail(e, PP_ERR_ARG, "%s: poses: stream %d: row %d, column %d is not finite", who, b, i / 4, i % 4);
+        if (int st = pose_check_finite(e, who, P, b)) return st;
         if (!std::isfinite(stamps[b])) return fail(e, PP_ERR_ARG, "%s: stamps: the stamp of stream %d is not finite", who, b);
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                const double gij = (P[i * 4] * P[j * 4] + P[i * 4 + 1] * P[j * 4 + 1]) + P[i * 4 + 2] * P[j * 4 + 2];
-                if (!(std::fabs(gij - (i == j ? 1.0 : 0.0)) <= ORTHO_TOL))
-                    return fail(e, PP_ERR_ARG, "%s: poses: the rotation of stream %d is not orthonormal (R R^T [%d][%d] = %.9g)", who, b, i, j, gij);
-            }
+        if (int st = pose_check_orthonormal(e, who, P, b)) return st;
         const double last = g.last_stamp[(size_t)b];
         if (!std::isnan(last) && !(stamps[b] > last))
             return fail(e, PP_ERR_ARG, "%s: stamps: the stamp of stream %d does not increase (%.17g after %.17g)", who, b, stamps[b], last);

@@ -20,12 +20,20 @@ int ensure_track(pp_engine* e) {
     A(&t.d_dt, B);
     A(&t.in_dets, B * PP_TRACK_MASK_ROWS);
     A(&t.in_n, B);
+    A(&t.d_pose_q, B);
+    A(&t.d_pose_prev, B);
     if (A.st) return A.st;
     HIPCHK(e, hipHostMalloc((void**)&t.h_dt_ring, (size_t)pp_engine::OFF_RING * B * sizeof(double)));
     HIPCHK(e, hipHostMalloc((void**)&t.h_out, B * PP_TRACK_MAX * sizeof(pp_track)));
     HIPCHK(e, hipHostMalloc((void**)&t.h_nout, B * sizeof(int)));
     HIPCHK(e, hipHostMalloc((void**)&t.h_overflow, B * sizeof(int)));
+    HIPCHK(e, hipHostMalloc((void**)&t.h_pose_ring, (size_t)pp_engine::OFF_RING * B * sizeof(TrkPose)));
+    HIPCHK(e, hipHostMalloc((void**)&t.h_out_fixed, B * PP_TRACK_MAX * sizeof(pp_track)));
+    HIPCHK(e, hipHostMalloc((void**)&t.h_nout_fixed, B * sizeof(int)));
     for (int i = 0; i < pp_engine::OFF_RING; ++i) HIPCHK(e, hipEventCreateWithFlags(&t.dt_ev[i], hipEventDisableTiming));
+    for (int i = 0; i < pp_engine::OFF_RING; ++i) HIPCHK(e, hipEventCreateWithFlags(&t.pose_ev[i], hipEventDisableTiming));
+    HIPCHK(e, hipMemset(t.d_pose_q, 0, B * sizeof(TrkPose)));
+    HIPCHK(e, hipMemset(t.d_pose_prev, 0, B * sizeof(TrkPose)));
     HIPCHK(e, hipMemset(t.state, 0, B * PP_TRACK_MAX * sizeof(TrkSlot)));
     HIPCHK(e, hipMemset(t.overflow, 0, B * sizeof(int)));
     HIPCHK(e, hipMemset(t.d_dt, 0, B * sizeof(double)));
@@ -34,6 +42,7 @@ int ensure_track(pp_engine* e) {
     HIPCHK(e, hipMemcpy(t.next_id, ones.data(), B * sizeof(int), hipMemcpyHostToDevice));
     memset(t.h_nout, 0, B * sizeof(int));
     memset(t.h_overflow, 0, B * sizeof(int));
+    for (size_t b = 0; b < B; ++b) t.h_nout_fixed[b] = -1;
     t.ready = true;
     return PP_OK;
 }
@@ -49,7 +58,9 @@ void fill_params(pp_engine* e, TrackParams& p, int batch, int rows, const pp_det
     pp_engine::Track& t = e->trk;
     p.batch = batch; p.rows = rows; p.dets = dets; p.n_dets = n_dets; p.cfg = t.d_cfg; p.dt = t.d_dt;
     p.state = t.state; p.next_id = t.next_id; p.overflow = t.overflow;
+    p.pose_q = t.d_pose_q; p.pose_prev = t.d_pose_prev;
     p.out = t.h_out; p.n_out = t.h_nout; p.overflow_out = t.h_overflow;
+    p.out_fixed = t.h_out_fixed; p.n_out_fixed = t.h_nout_fixed;
 }
 
 // the seconds of the next step, through a ring slot of their own into d_dt, on the handle's stream
@@ -63,6 +74,25 @@ int queue_dt(pp_engine* e, const double* dt, int batch) {
     else memset(ring, 0, (size_t)batch * sizeof(double));
     HIPCHK(e, hipMemcpyAsync(t.d_dt, ring, (size_t)batch * sizeof(double), hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipEventRecord(t.dt_ev[slot], e->stream));
+    return PP_OK;
+}
+
+// the poses of the next step, armed, through a ring slot of their own into d_pose_q, on the handle's stream
+int queue_pose(pp_engine* e, const double* poses, int batch) {
+    pp_engine::Track& t = e->trk;
+    const int slot = t.pose_slot;
+    t.pose_slot = (slot + 1) % pp_engine::OFF_RING;
+    HIPCHK(e, hipEventSynchronize(t.pose_ev[slot]));   // the copy that last used this slot has been consumed
+    TrkPose* ring = t.h_pose_ring + (size_t)slot * e->B;
+    for (int b = 0; b < batch; ++b) {
+        const double* P = poses + (size_t)b * 12;
+        memcpy(ring[b].m, P, 12 * sizeof(double));
+        ring[b].psi = std::atan2(P[4], P[0]);          // the yaw of the sensor's x axis in the fixed frame: atan2(R10, R00)
+        ring[b].has = 1;
+        ring[b].pad = 0;
+    }
+    HIPCHK(e, hipMemcpyAsync(t.d_pose_q, ring, (size_t)batch * sizeof(TrkPose), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipEventRecord(t.pose_ev[slot], e->stream));
     return PP_OK;
 }
 
@@ -92,9 +122,12 @@ int run_track(pp_engine* e, int batch) {
 
 void track_release(pp_engine* e) {
     pp_engine::Track& t = e->trk;
-    for (void* p : {(void*)t.h_dt_ring, (void*)t.h_out, (void*)t.h_nout, (void*)t.h_overflow})
+    for (void* p : {(void*)t.h_dt_ring, (void*)t.h_out, (void*)t.h_nout, (void*)t.h_overflow, (void*)t.h_pose_ring,
+                    (void*)t.h_out_fixed, (void*)t.h_nout_fixed})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t ev : t.dt_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : t.pose_ev)
         if (ev) (void)hipEventDestroy(ev);
     t = pp_engine::Track();
 }
@@ -151,6 +184,38 @@ int pp_set_track_dt(pp_handle e, const double* dt, int32_t batch) {
     return queue_dt(e, dt, batch);
 }
 
+int pp_set_track_pose(pp_handle e, const double* poses, int32_t batch) {
+    if (!e) return fail(nullptr, PP_ERR_ARG, "pp_set_track_pose: NULL handle");
+    if (!poses) return fail(e, PP_ERR_ARG, "pp_set_track_pose: poses is NULL");
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_set_track_pose: a training step is in flight");
+    if (int st = check_batch(e, batch)) return st;
+    if (!e->trk.configured) return fail(e, PP_ERR_STATE, "pp_set_track_pose: pp_set_tracking has given no configuration");
+    for (int b = 0; b < batch; ++b) {
+        if (int st = pose_check_finite(e, "pp_set_track_pose", poses + (size_t)b * 12, b)) return st;
+        if (int st = pose_check_orthonormal(e, "pp_set_track_pose", poses + (size_t)b * 12, b)) return st;
+    }
+    (void)hipSetDevice(e->device);
+    return queue_pose(e, poses, batch);
+}
+
+int pp_get_tracks_fixed(pp_handle e, pp_track* tracks, int32_t* n_tracks) {
+    if (!e) return PP_ERR_ARG;
+    if (!tracks || !n_tracks) return fail(e, PP_ERR_ARG, "pp_get_tracks_fixed: NULL argument");
+    const int B = e->trk.results;
+    if (B < 1) return fail(e, PP_ERR_STATE, "pp_get_tracks_fixed: the last pass ran untracked, or none has run (pp_set_tracking, then a pass)");
+    (void)hipSetDevice(e->device);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (e->trk.from_pass)
+        if (int st = check_numeric(e, e->h_ndets, B, "pp_get_tracks_fixed")) return st;
+    for (int b = 0; b < B; ++b) {
+        const size_t n = (size_t)std::max(0, std::min(e->trk.h_nout_fixed[b], PP_TRACK_MAX));
+        memcpy(tracks + (size_t)b * PP_TRACK_MAX, e->trk.h_out_fixed + (size_t)b * PP_TRACK_MAX, n * sizeof(pp_track));
+        memset(tracks + (size_t)b * PP_TRACK_MAX + n, 0, (PP_TRACK_MAX - n) * sizeof(pp_track));
+    }
+    memcpy(n_tracks, e->trk.h_nout_fixed, (size_t)B * sizeof(int));
+    return PP_OK;
+}
+
 int pp_get_tracks(pp_handle e, pp_track* tracks, int32_t* n_tracks, int32_t* overflow) {
     if (!e) return PP_ERR_ARG;
     if (!tracks || !n_tracks) return fail(e, PP_ERR_ARG, "pp_get_tracks: NULL argument");
@@ -179,8 +244,8 @@ int pp_track_update(pp_handle e, const pp_detection* dets, const int32_t* n_dets
     if (rows < 1) return fail(e, PP_ERR_ARG, "pp_track_update: rows = %d must be >= 1", rows);
     if (int st = check_rows(e, "pp_track_update", rows)) return st;
     if (!e->trk.configured) return fail(e, PP_ERR_STATE, "pp_track_update: pp_set_tracking has given no configuration");
-    for (int b = 0; b < batch; ++b)
-        if (n_dets[b] < 0 || n_dets[b] > rows)
+    for (int b = 0; b < batch; ++b)     // (a count a pass flagged may come back as it is: its stream stays untouched)
+        if (n_dets[b] < 0 || (!(n_dets[b] & PP_NDETS_NONFINITE) && n_dets[b] > rows))
             return fail(e, PP_ERR_ARG, "pp_track_update: n_dets[%d] = %d outside [0, rows = %d]", b, n_dets[b], rows);
     if (dt)
         if (int st = check_dt(e, "pp_track_update", dt, batch)) return st;
@@ -215,6 +280,7 @@ int pp_track_reset(pp_handle e, int32_t stream) {
     const size_t b0 = stream < 0 ? 0 : (size_t)stream, nb = stream < 0 ? (size_t)e->B : 1;
     HIPCHK(e, hipMemset(t.state + b0 * PP_TRACK_MAX, 0, nb * PP_TRACK_MAX * sizeof(TrkSlot)));
     HIPCHK(e, hipMemset(t.overflow + b0, 0, nb * sizeof(int)));
+    HIPCHK(e, hipMemset(t.d_pose_prev + b0, 0, nb * sizeof(TrkPose)));      // the previous pose goes; an armed one stays
     std::vector<int> ones(nb, 1);
     HIPCHK(e, hipMemcpy(t.next_id + b0, ones.data(), nb * sizeof(int), hipMemcpyHostToDevice));
     return PP_OK;

@@ -295,6 +295,14 @@ struct TrkSlot {
     int live;              // 0: the slot is free (its other fields are then meaningless)
 };
 #define PP_TRACK_MASK_ROWS 128     // detection rows per frame the free-row bitmask of k_track_step holds (2 x 64 bits)
+// One stream's ego pose on the device (pp_set_track_pose): the [3][4] sensor-to-fixed [R | t], row-major, and
+// psi = atan2(R10, R00) from the host -- the kernel only adds and subtracts it
+struct TrkPose {
+    double m[12];
+    double psi;
+    int has;               // the queued record: armed for the next step; the previous record: a posed step has run
+    int pad;
+};
 struct TrackParams {
     int batch;                 // streams 0 .. batch - 1 advance by one step
     int rows;                  // row stride of dets (<= PP_TRACK_MASK_ROWS)
@@ -306,10 +314,16 @@ struct TrackParams {
     TrkSlot* state;            // [B][PP_TRACK_MAX]
     int* next_id;              // [B]
     int* overflow;             // [B]
+    TrkPose* pose_q;           // [B] the pose of this step per stream; `has` == 0: none (the step runs exactly as without
+                               // ego motion).  Consumed (`has` zeroed) by the step, also for a flagged stream
+    TrkPose* pose_prev;        // [B] the pose of the stream's last posed step that ran; rewritten by a posed step
     // page-locked host memory the kernel fills itself (only pp_get_tracks reads them):
     pp_track* out;             // [batch][PP_TRACK_MAX] the live tracks, ascending slot
     int* n_out;                // [batch]
     int* overflow_out;         // [batch]
+    // ... and pp_get_tracks_fixed:
+    pp_track* out_fixed;       // [batch][PP_TRACK_MAX] the same rows in the fixed frame of the step's pose
+    int* n_out_fixed;          // [batch]; -1: the stream's step had no pose
 };
 void launch_track_step(const TrackParams& p, hipStream_t s);
 

@@ -373,7 +373,14 @@ struct pp_engine {
         int *h_nout = nullptr, *h_overflow = nullptr;   // the device reads them: no device copy, no copy node behind the pass)
         pp_detection* in_dets = nullptr;   // [B][PP_TRACK_MASK_ROWS] pp_track_update's rows (d_dets stays a pass's)
         int* in_n = nullptr;               // [B]
-        int results = 0;               // streams of the last tracked pass or pp_track_update (pp_get_tracks; 0: none)
+        // pp_set_track_pose: the ego pose of the next step per stream, and of the last posed step that ran
+        TrkPose *d_pose_q = nullptr, *d_pose_prev = nullptr;   // [B] each
+        TrkPose* h_pose_ring = nullptr;    // pinned [OFF_RING][B]: the poses travel as the dt values do
+        hipEvent_t pose_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        int pose_slot = 0;
+        pp_track* h_out_fixed = nullptr;   // pinned [B][PP_TRACK_MAX]: the step's rows in the fixed frame (pp_get_tracks_fixed)
+        int* h_nout_fixed = nullptr;       // pinned [B]; -1: the stream's step had no pose
+        int results = 0;              // streams of the last tracked pass or pp_track_update (pp_get_tracks; 0: none)
         bool from_pass = false;        // ... it was a pass: pp_get_tracks consults its frames' numeric flags
     } trk;
 
@@ -404,6 +411,24 @@ int fail(pp_engine* e, int code, const char* fmt, ...);
         if (_st != hipSuccess)                                                                       \
             return fail(e, PP_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_st), __FILE__, __LINE__); \
     } while (0)
+
+// ---- what every call that takes ego poses refuses (pp_sweeps_accumulate*, pp_set_track_pose): P is stream b's [3][4]
+// sensor-to-fixed [R | t], row-major ----
+constexpr double PP_POSE_ORTHO_TOL = 1e-6;      // largest |R R^T - I| entry of an accepted rotation (sweeps.ORTHO_TOL)
+inline int pose_check_finite(pp_engine* e, const char* who, const double* P, int b) {
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(P[i])) return fail(e, PP_ERR_ARG, "%s: poses: stream %d: row %d, column %d is not finite", who, b, i / 4, i % 4);
+    return PP_OK;
+}
+inline int pose_check_orthonormal(pp_engine* e, const char* who, const double* P, int b) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double gij = (P[i * 4] * P[j * 4] + P[i * 4 + 1] * P[j * 4 + 1]) + P[i * 4 + 2] * P[j * 4 + 2];
+            if (!(std::fabs(gij - (i == j ? 1.0 : 0.0)) <= PP_POSE_ORTHO_TOL))
+                return fail(e, PP_ERR_ARG, "%s: poses: the rotation of stream %d is not orthonormal (R R^T [%d][%d] = %.9g)", who, b, i, j, gij);
+        }
+    return PP_OK;
+}
 
 // ---- the calls that need no handle: host buffers in, host buffers out, device memory for the call's duration ----
 struct DevBuf {

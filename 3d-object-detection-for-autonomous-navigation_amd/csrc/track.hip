@@ -10,6 +10,10 @@
 // the lanes whose best row has just been taken scan again -- rows only ever leave, so every other lane's best stands.
 // The free rows are a 2 x 64-bit mask in registers (PP_TRACK_MASK_ROWS); births and the compacted output positions come
 // from ballots and popcounts.  No LDS, no atomics; the rounds' dependent cross-lane chain is what the kernel costs.
+//
+// Ego motion (pp_set_track_pose): a stream that was given a pose for this step first carries its live tracks from the sensor
+// frame of its previous posed step into the current one (stage 0), and its rows go out a second time in the fixed frame.
+// The poses and psi = atan2(R10, R00) come from the host; the kernel multiplies, adds and subtracts.
 #include "pp_common.h"
 
 namespace {
@@ -45,7 +49,10 @@ __global__ __launch_bounds__(PP_WAVE) void k_track_step(TrackParams p) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const int raw = p.n_dets[b];
     if (raw & PP_NDETS_NONFINITE) {              // the whole wave: the stream's table and outputs stay as they are
-        if (lane == 0) p.dt[b] = 0.0;            // ... but the step's dt is spent: it must not reach a later pass
+        if (lane == 0) {                         // ... but the step's dt and pose are spent: they must not reach a later
+            p.dt[b] = 0.0;                       // pass (the previous pose stays: the next posed step carries over the
+            p.pose_q[b].has = 0;                 // whole motion since the last step that ran)
+        }
         return;
     }
     const int n = min(max(raw, 0), p.rows);
@@ -56,6 +63,44 @@ __global__ __launch_bounds__(PP_WAVE) void k_track_step(TrackParams p) {
     TrkSlot* slot = p.state + (size_t)b * PP_TRACK_MAX + lane;
     TrkSlot t = *slot;
     bool live = t.live != 0;
+
+    // ---- 0. ego motion: carry the live tracks from the previous posed sensor frame into this step's ----
+    // Every address below is the stream's alone, so the pose, M, u and the yaw step are the same in every lane.  Every lane
+    // has read the previous pose into registers here, long before lane 0 rewrites it in the closing block.  A step without
+    // a pose runs none of this -- not even with an identity, which would turn -0.0 into +0.0.
+    const bool posed = p.pose_q[b].has != 0;
+    double R[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, psi = 0.0;
+    if (posed) {
+        const TrkPose* q = p.pose_q + b;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) R[i] = q->m[i];
+        psi = q->psi;
+        const TrkPose* pv = p.pose_prev + b;
+        if (pv->has != 0) {
+            double S[12];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) S[i] = pv->m[i];
+            const double dpsi = psi - pv->psi;
+            // sweeps.relative_transform(P_c, prev): M = R_c^T R_s, u = R_c^T (t_s - t_c), in that function's order
+            const double d0 = S[3] - R[3], d1 = S[7] - R[7], d2 = S[11] - R[11];
+            double M[9], u[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) M[i * 3 + j] = (R[i] * S[j] + R[4 + i] * S[4 + j]) + R[8 + i] * S[8 + j];
+                u[i] = (R[i] * d0 + R[4 + i] * d1) + R[8 + i] * d2;
+            }
+            if (live) {
+                const double x = t.x[0], y = t.x[1], z = t.x[2], vx = t.x[3], vy = t.x[4], vz = t.x[5];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    t.x[i] = ((M[i * 3] * x + M[i * 3 + 1] * y) + M[i * 3 + 2] * z) + u[i];
+                    t.x[3 + i] = (M[i * 3] * vx + M[i * 3 + 1] * vy) + M[i * 3 + 2] * vz;
+                }
+                t.yaw = t.yaw + dpsi;
+            }
+        }
+    }
 
     // ---- 1. predict ----
     if (live) {
@@ -181,6 +226,15 @@ __global__ __launch_bounds__(PP_WAVE) void k_track_step(TrackParams p) {
         o.reserved = 0;
         const size_t at = (size_t)b * PP_TRACK_MAX + __popcll(alive & below);
         p.out[at] = o;
+        if (posed) {                             // the same row in the fixed frame of this step's pose
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                o.state[i] = ((R[i * 4] * t.x[0] + R[i * 4 + 1] * t.x[1]) + R[i * 4 + 2] * t.x[2]) + R[i * 4 + 3];
+                o.state[3 + i] = (R[i * 4] * t.x[3] + R[i * 4 + 1] * t.x[4]) + R[i * 4 + 2] * t.x[5];
+            }
+            o.yaw = t.yaw + psi;
+            p.out_fixed[at] = o;
+        }
     }
     if (lane == 0) {
         const int cnt = __popcll(alive);
@@ -189,6 +243,15 @@ __global__ __launch_bounds__(PP_WAVE) void k_track_step(TrackParams p) {
         p.dt[b] = 0.0;                           // consumed: the next step uses the period unless pp_set_track_dt speaks again
         p.n_out[b] = cnt;
         p.overflow_out[b] = overflow;
+        p.n_out_fixed[b] = posed ? cnt : -1;
+        if (posed) {                             // consumed likewise; this step's pose is the next posed step's previous one
+            TrkPose* pv = p.pose_prev + b;
+#pragma unroll
+            for (int i = 0; i < 12; ++i) pv->m[i] = R[i];
+            pv->psi = psi;
+            pv->has = 1;
+            p.pose_q[b].has = 0;
+        }
     }
 }
 

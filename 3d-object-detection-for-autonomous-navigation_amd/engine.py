@@ -391,6 +391,7 @@ class Engine:
         if d.use_multi_class_nms:
             self.set_class_nms("per_class")
         self._last_stamp = np.full(self.max_batch, np.nan)      # per stream: the last time stamp a detect* was given
+        self._track_ego = False                                 # set_track_ego: poses= of a detect* also go to the tracker
         if d.tracking is not None:
             self.set_tracking(d.tracking)
         self._sweep_last = np.full(self.max_batch, np.nan)      # per stream: the last stamp an accumulate_sweeps* was given
@@ -565,9 +566,46 @@ class Engine:
         B = int(batch) if batch is not None else int(np.count_nonzero(n >= 0))
         return tr[:B], n[:B], ov[:B]
 
-    def track_update(self, dets, n_dets, dt=None):
+    def set_track_pose(self, poses):
+        """The ego poses of the next tracked step (pp_set_track_pose): [k, 3, 4] float64 sensor-to-fixed transforms
+        (sweeps.pose_from_xyyaw / pose_from_matrix) for streams 0 .. k - 1.  That step -- the next tracked pass's or
+        track_update's -- first carries each posed stream's tracks from the sensor frame of its previous posed step into
+        the current one, so ids survive the sensor's own motion and velocities are over ground (tracking.py states the
+        rule); `tracks_fixed()` then gives its rows in the fixed frame.  Queued on the engine's stream and spent by that
+        step, as set_track_dt's values are."""
+        P = np.ascontiguousarray(poses, np.float64)
+        if P.ndim != 3 or P.shape[1:] != (3, 4):
+            raise ValueError(f"set_track_pose: poses must be [streams, 3, 4] (sensor to fixed frame, [R | t]), got {P.shape}")
+        self._check(self._lib.pp_set_track_pose(self._h, _ptr(P), int(P.shape[0])), "pp_set_track_pose")
+
+    def tracks_fixed(self, batch=None):
+        """(tracks [B, 64] tracking.TRACK_DTYPE, n_tracks [B]) of the last tracked pass or track_update in the FIXED frame
+        of the poses that step was given (pp_get_tracks_fixed): `tracks()`'s rows with position, velocity and yaw mapped by
+        the stream's pose; n_tracks is -1 (rows zero) for a stream whose step had no pose.  Raises where `tracks()` does."""
+        tr, n, _ = self._track_out(self.max_batch)
+        n[:] = -2                       # the call fills the streams of that pass (or track_update) only
+        self._check(self._lib.pp_get_tracks_fixed(self._h, _ptr(tr), _ptr(n)), "pp_get_tracks_fixed")
+        B = int(batch) if batch is not None else int(np.count_nonzero(n >= -1))
+        return tr[:B], n[:B]
+
+    def set_track_ego(self, on):
+        """on: the poses= (and stamps=) of detect, detect_pointcloud2, detect_depth, detect_rig_depth and
+        detect_rig_pointcloud2 also go to the tracker (set_track_pose beside set_track_dt), and are accepted without
+        set_sweeps -- they then serve the tracker alone; with sweeps configured both consume the same poses.  Off (the
+        default): poses= means sweeps only, as before.  A policy of this class: the library knows nothing of it.  Needs
+        tracking on."""
+        if on and not self.tracking_on:
+            raise ValueError("set_track_ego: tracking is off (set_tracking first)")
+        self._track_ego = bool(on)
+
+    @property
+    def track_ego(self):
+        return self._track_ego
+
+    def track_update(self, dets, n_dets, dt=None, poses=None):
         """One tracking step on host-given rows (pp_track_update; the same kernel, on this engine's same tables): dets
-        [batch, rows] DET_DTYPE, n_dets [batch], dt [batch] seconds or None (the period).  Returns `tracks(batch)`."""
+        [batch, rows] DET_DTYPE, n_dets [batch], dt [batch] seconds or None (the period), poses as `set_track_pose` takes
+        them or None.  Returns `tracks(batch)`."""
         n = _i32(np.asarray(n_dets).reshape(-1))
         d = np.ascontiguousarray(dets, DET_DTYPE)
         if d.ndim != 2 or d.shape[0] != n.shape[0]:
@@ -575,13 +613,17 @@ class Engine:
         t = None if dt is None else np.ascontiguousarray(dt, np.float64).reshape(-1)
         if t is not None and t.shape[0] != n.shape[0]:
             raise ValueError(f"track_update: {t.shape[0]} dt values for {n.shape[0]} streams")
+        if poses is not None:
+            if np.asarray(poses).ndim != 3 or not 1 <= np.asarray(poses).shape[0] <= n.shape[0]:
+                raise ValueError(f"track_update: poses {np.asarray(poses).shape} for {n.shape[0]} streams")
+            self.set_track_pose(poses)
         self._check(self._lib.pp_track_update(self._h, _ptr(d), _ptr(n), int(d.shape[1]), int(d.shape[0]), _ptr(t)),
                     "pp_track_update")
         return self.tracks(int(d.shape[0]))
 
     def track_reset(self, stream=None):
-        """Frees every track of `stream` (None: of all streams); its ids start at 1 again, its overflow count and its last
-        time stamp are forgotten."""
+        """Frees every track of `stream` (None: of all streams); its ids start at 1 again, its overflow count, its last
+        time stamp and its previous ego pose are forgotten."""
         s = -1 if stream is None else int(stream)
         self._check(self._lib.pp_track_reset(self._h, s), "pp_track_reset")
         if s < 0:
@@ -832,8 +874,9 @@ class Engine:
         raised; the flagged frames' streams did not move (their dt and their stamps are spent), the next pass runs in
         float32.
         poses ([B, 3, 4] sensor-to-fixed transforms; needs set_sweeps and stamps): accumulate_sweeps(poses, stamps) runs
-        between the upload (and the crop) and the pass -- once: the float32 re-run reads the accumulated frames."""
-        sweep, dts = self._pose_args(poses, stamps, len(frames), "detect")
+        between the upload (and the crop) and the pass -- once: the float32 re-run reads the accumulated frames.  Under
+        set_track_ego(True) the poses also go to the pass's tracking step (set_track_pose) and need no set_sweeps."""
+        sweep, dts, ego = self._pose_args(poses, stamps, len(frames), "detect")
         if bbox and p2 is None:
             raise ValueError("detect: bbox=True needs p2 (the camera matrix the boxes are projected by)")
         if (image_shape is not None and p2 is None) or (p2 is not None and image_shape is None and not bbox):
@@ -850,14 +893,16 @@ class Engine:
             r4, t4, p4 = (np.broadcast_to(np.asarray(m, np.float64), (B, 4, 4)) for m in (rect, trv2c, p2))
             shp = np.broadcast_to(np.asarray(image_shape), (B, 2))
             self.crop_to_image(np.stack([frustum.frustum_planes(r4[b], t4[b], p4[b], shp[b]) for b in range(B)]))
-        return self._detect_resident(on_numeric, dts, sweep)
+        return self._detect_resident(on_numeric, dts, sweep, ego)
 
-    def _detect_resident(self, on_numeric, dts=None, sweep=None):
+    def _detect_resident(self, on_numeric, dts=None, sweep=None, ego=None):
         if sweep is not None:         # (before the pass, and not again before the float32 re-run below)
             self.accumulate_sweeps(*sweep)
         if dts is not None:
             self.set_track_dt(dts[0])
             self._last_stamp = dts[1]
+        if ego is not None:           # (set_track_ego: the pass's tracking step carries its streams under these poses)
+            self.set_track_pose(ego)
         self.detect_async()
         self.sync()
         try:
@@ -1013,15 +1058,22 @@ class Engine:
 
     def _pose_args(self, poses, stamps, batch, who):
         """poses= of a detect*: checked before anything is queued (None: no accumulation); stamps then serve the sweeps, and
-        the tracker too when tracking is on."""
+        the tracker too when tracking is on.  Returns (what accumulate_sweeps takes or None, what _stamps_dt returns, the
+        poses for the tracker or None); the last only under set_track_ego with tracking on, and then the poses are accepted
+        without sweeps as well (and, the sweeps off, without stamps: the streams advance by the period)."""
         if poses is None:
-            return None, self._stamps_dt(stamps, batch)
+            return None, self._stamps_dt(stamps, batch), None
+        ego = self._track_ego and self.tracking_on
+        if ego and not self._get_sweeps()[0]:
+            if np.asarray(poses).shape[:1] != (batch,):
+                raise ValueError(f"{who}: {np.asarray(poses).shape[0] if np.asarray(poses).ndim else 0} poses for {batch} frames")
+            return None, self._stamps_dt(stamps, batch), _swp.check_poses(poses, batch)
         if stamps is None:
             raise ValueError(f"{who}: poses needs stamps (one time stamp in seconds per frame)")
         if np.asarray(poses).shape[:1] != (batch,):
             raise ValueError(f"{who}: {np.asarray(poses).shape[0] if np.asarray(poses).ndim else 0} poses for {batch} frames")
-        self._sweep_call(poses, stamps, who)
-        return (poses, stamps), (self._stamps_dt(stamps, batch) if self.tracking_on else None)
+        P = self._sweep_call(poses, stamps, who)[0]
+        return (poses, stamps), (self._stamps_dt(stamps, batch) if self.tracking_on else None), (P if ego else None)
 
     # ---- live-camera ingest (pp_ingest_*; ingest.py states the rule; DESIGN 7.1c, 7.1m, 7.1n, 7.1o) ----
     def _ingest_sync(self, name, args, batch, cap, nf, cameras=None):
@@ -1049,10 +1101,10 @@ class Engine:
         staging._users.add(self)
         self._staged.append(staging)      # kept alive while a copy may still read it (see upload_async)
 
-    def _detect_after_ingest(self, batch, rect, trv2c, on_numeric, dts=None, sweep=None):
+    def _detect_after_ingest(self, batch, rect, trv2c, on_numeric, dts=None, sweep=None, ego=None):
         if rect is not None:
             self.set_calib(rect, trv2c, batch)
-        return self._detect_resident(on_numeric, dts, sweep)
+        return self._detect_resident(on_numeric, dts, sweep, ego)
 
     def ingest_pointcloud2(self, msgs, first=1, decimate=4, lift=None, return_points=False, features=None, mount=None):
         """Raw sensor_msgs/PointCloud2 messages -> the engine's resident frames, on the GPU: x y z out of the bytes,
@@ -1119,9 +1171,9 @@ class Engine:
         production mode, train.py:810-828).  rect / trv2c / on_numeric as `detect`; features / mount / first / decimate as
         ingest_pointcloud2 (a lidar feeding a 4-feature model: features=[FeatureField("intensity")],
         mount=Mount(np.eye(3), np.eye(3), 0.0), first=0, decimate=1); stamps and poses as `detect`."""
-        sweep, dts = self._pose_args(poses, stamps, len(msgs), "detect_pointcloud2")
+        sweep, dts, ego = self._pose_args(poses, stamps, len(msgs), "detect_pointcloud2")
         self.ingest_pointcloud2(msgs, first=first, decimate=decimate, features=features, mount=mount)
-        return self._detect_after_ingest(len(msgs), rect, trv2c, on_numeric, dts, sweep)
+        return self._detect_after_ingest(len(msgs), rect, trv2c, on_numeric, dts, sweep, ego)
 
     # ---- depth-image ingest (pp_ingest_depth*) ----
     def ingest_depth(self, images, intrinsics, first=1, decimate=4, lift=None, depth_scale=0.001, z_min=0.0, z_max=np.inf,
@@ -1159,9 +1211,9 @@ class Engine:
     def detect_depth(self, images, intrinsics, rect=None, trv2c=None, on_numeric="f32", stamps=None, poses=None):
         """ingest_depth + detect_async + sync + detections: `detect_pointcloud2` for the depth images the messages are
         computed from.  rect / trv2c / on_numeric / stamps / poses as `detect`."""
-        sweep, dts = self._pose_args(poses, stamps, len(images), "detect_depth")
+        sweep, dts, ego = self._pose_args(poses, stamps, len(images), "detect_depth")
         self.ingest_depth(images, intrinsics)
-        return self._detect_after_ingest(len(images), rect, trv2c, on_numeric, dts, sweep)
+        return self._detect_after_ingest(len(images), rect, trv2c, on_numeric, dts, sweep, ego)
 
     # ---- camera-rig ingest (pp_ingest_rig_*) ----
     def ingest_rig_depth(self, frames, rig, return_points=False):
@@ -1245,17 +1297,17 @@ class Engine:
     def detect_rig_depth(self, frames, rig, rect=None, trv2c=None, on_numeric="f32", stamps=None, poses=None):
         """ingest_rig_depth + detect_async + sync + detections: `detect_depth` for a rig's images.  rect / trv2c /
         on_numeric / stamps / poses as `detect`."""
-        sweep, dts = self._pose_args(poses, stamps, len(frames), "detect_rig_depth")
+        sweep, dts, ego = self._pose_args(poses, stamps, len(frames), "detect_rig_depth")
         self.ingest_rig_depth(frames, rig)
-        return self._detect_after_ingest(len(frames), rect, trv2c, on_numeric, dts, sweep)
+        return self._detect_after_ingest(len(frames), rect, trv2c, on_numeric, dts, sweep, ego)
 
     def detect_rig_pointcloud2(self, frames, rig, rect=None, trv2c=None, on_numeric="f32", features=None, stamps=None,
                                poses=None):
         """ingest_rig_pointcloud2 + detect_async + sync + detections; features as ingest_rig_pointcloud2, stamps and
         poses as `detect`."""
-        sweep, dts = self._pose_args(poses, stamps, len(frames), "detect_rig_pointcloud2")
+        sweep, dts, ego = self._pose_args(poses, stamps, len(frames), "detect_rig_pointcloud2")
         self.ingest_rig_pointcloud2(frames, rig, features=features)
-        return self._detect_after_ingest(len(frames), rect, trv2c, on_numeric, dts, sweep)
+        return self._detect_after_ingest(len(frames), rect, trv2c, on_numeric, dts, sweep, ego)
 
     def intermediates(self, canvas=False):
         d, B = self.d, max(self._batches()[1], 1)

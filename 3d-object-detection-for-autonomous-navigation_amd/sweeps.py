@@ -108,15 +108,44 @@ def pose_from_matrix(T4x4):
     return np.ascontiguousarray(T[:3, :4])
 
 
-def check_call(poses, stamps, batch, last):
-    """What every accumulate refuses before anything is queued.  poses -> [batch, 3, 4] float64, stamps -> [batch]
-    float64; `last`: the streams' previous stamps (NaN: none).  Raises ValueError naming the stream; returns
-    (poses, stamps, new_last) -- `last` itself is not changed."""
+def _poses_array(poses, batch):
     P = np.ascontiguousarray(poses, np.float64)
     if P.ndim != 3 or P.shape[1:] != (3, 4):
         raise ValueError(f"poses: [batch, 3, 4] (sensor to fixed frame, [R | t]), got {P.shape}")
     if P.shape[0] != batch:
         raise ValueError(f"poses: {P.shape[0]} poses for {batch} frames")
+    return P
+
+
+def _pose_finite(P, b):
+    if not np.isfinite(P[b]).all():
+        raise ValueError(f"poses: the pose of stream {b} is not finite")
+
+
+def _pose_orthonormal(P, b):
+    R = P[b, :, :3]
+    for i in range(3):
+        for j in range(3):
+            g = (R[i, 0] * R[j, 0] + R[i, 1] * R[j, 1]) + R[i, 2] * R[j, 2]
+            if not abs(g - (1.0 if i == j else 0.0)) <= ORTHO_TOL:
+                raise ValueError(f"poses: the rotation of stream {b} is not orthonormal (R R^T [{i}][{j}] = {g!r})")
+
+
+def check_poses(poses, batch):
+    """The pose half of check_call, for a caller without stamps (the tracker): poses -> [batch, 3, 4] float64, each
+    finite and orthonormal to ORTHO_TOL.  Raises ValueError naming the stream."""
+    P = _poses_array(poses, batch)
+    for b in range(batch):
+        _pose_finite(P, b)
+        _pose_orthonormal(P, b)
+    return P
+
+
+def check_call(poses, stamps, batch, last):
+    """What every accumulate refuses before anything is queued.  poses -> [batch, 3, 4] float64, stamps -> [batch]
+    float64; `last`: the streams' previous stamps (NaN: none).  Raises ValueError naming the stream; returns
+    (poses, stamps, new_last) -- `last` itself is not changed."""
+    P = _poses_array(poses, batch)
     if stamps is None:
         raise ValueError("stamps: one time stamp per frame is required with poses")
     s = np.ascontiguousarray(stamps, np.float64).reshape(-1)
@@ -124,16 +153,10 @@ def check_call(poses, stamps, batch, last):
         raise ValueError(f"stamps: {s.shape[0]} values for {batch} frames")
     new = np.array(last, np.float64)
     for b in range(batch):
-        if not np.isfinite(P[b]).all():
-            raise ValueError(f"poses: the pose of stream {b} is not finite")
+        _pose_finite(P, b)
         if not math.isfinite(s[b]):
             raise ValueError(f"stamps: the stamp of stream {b} is not finite")
-        R = P[b, :, :3]
-        for i in range(3):
-            for j in range(3):
-                g = (R[i, 0] * R[j, 0] + R[i, 1] * R[j, 1]) + R[i, 2] * R[j, 2]
-                if not abs(g - (1.0 if i == j else 0.0)) <= ORTHO_TOL:
-                    raise ValueError(f"poses: the rotation of stream {b} is not orthonormal (R R^T [{i}][{j}] = {g!r})")
+        _pose_orthonormal(P, b)
         if not math.isnan(new[b]) and not s[b] > new[b]:
             raise ValueError(f"stamps: the stamp of stream {b} does not increase ({s[b]!r} after {new[b]!r})")
         new[b] = s[b]

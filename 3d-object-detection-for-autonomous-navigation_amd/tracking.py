@@ -22,12 +22,36 @@ One track table per STREAM (frame b of every pass is stream b), PP_TRACK_MAX slo
 6. output the live tracks in ascending slot order, `det_row` = the matched or birth row, else -1.
 
 A frame whose count carries the post-process's non-finite flag leaves its stream untouched.
+
+EGO MOTION.  The tracks of a stream stay in the sensor frame of its latest step, so `det_row`, the association and the
+output keep their meaning while the sensor moves.  A step may be given a POSE per stream (sweeps.py's [3, 4] float64
+sensor-to-fixed [R | t]); per stream the tracker keeps prev_pose, prev_psi and has_prev.  A step of stream b with pose P_c:
+
+0. psi_c = math.atan2(P_c[1][0], P_c[0][0]) -- on the host (std::atan2 in the C library); the device only adds and
+   subtracts it.  If has_prev: (M, u) = sweeps.relative_transform(P_c, prev_pose), and every live slot is CARRIED from the
+   previous posed sensor frame into the current one before stage 1:
+       x' = ((M00 * x + M01 * y) + M02 * z) + u0          (y', z' alike, all from the old x y z)
+       vx' = (M00 * vx + M01 * vy) + M02 * vz             (vy', vz' alike)
+       yaw' = yaw + (psi_c - prev_psi)                    (no wrap)
+   The covariance triple is isotropic: a rotation leaves it as it is.
+   Then stages 1 to 6, unchanged; at the end prev_pose = P_c, prev_psi = psi_c, has_prev = True.
+
+A step WITHOUT a pose for the stream is stages 1 to 6 alone and leaves prev_* untouched: no carry runs, not even with an
+identity (((1 * x + 0 * y) + 0 * z) + 0 would turn -0.0 into +0.0).  A flagged frame leaves table and prev_* untouched and
+spends the pose, as it spends dt: the next posed step carries over the whole motion since the last step that ran.
+reset(stream) forgets the previous pose; a stream's first posed step carries nothing.  After a carry a track's velocity is
+the object's velocity over ground, in the current sensor axes.
+
+The same step also gives the live tracks in the FIXED frame (tracks_fixed), for the streams it had a pose for: position
+((R00 * x + R01 * y) + R02 * z) + t0 (y, z alike), velocity (R00 * vx + R01 * vy) + R02 * vz (alike), yaw + psi_c, every
+other field copied; a stream whose step had no pose reports a count of -1 there.
 """
 import dataclasses
 import math
 
 import numpy as np
 
+from . import sweeps as _swp
 from ._lib import PP_TRACK_MAX, PP_TRACK_MASK_ROWS as MAX_ROWS      # slots per stream; rows per frame the GPU step takes
 
 _NONFINITE = 1 << 30            # PP_NDETS_NONFINITE
@@ -132,7 +156,7 @@ def stamps_to_dt(last, stamps, batch, period):
 
 class Tracker:
     """The rule, on the host: `streams` track tables with the state of the GPU step.  step(dets, n, dt) advances streams
-    0 .. len(n) - 1; tracks() returns what pp_get_tracks returns for them."""
+    0 .. len(n) - 1; tracks() returns what pp_get_tracks returns for them, tracks_fixed() what pp_get_tracks_fixed does."""
 
     def __init__(self, config=None, streams=1):
         self.cfg = TrackConfig.from_any(config if config is not None else True)
@@ -154,12 +178,18 @@ class Tracker:
         self._out = np.zeros((S, M), TRACK_DTYPE)
         self._nout = np.zeros(S, np.int32)
         self._batch = 0
+        self.prev_pose = np.zeros((S, 3, 4), np.float64)
+        self.prev_psi = np.zeros(S, np.float64)
+        self.has_prev = np.zeros(S, bool)
+        self._outf = np.zeros((S, M), TRACK_DTYPE)
+        self._noutf = np.full(S, -1, np.int32)
 
     def reset(self, stream=None):
         for s in (range(self.streams) if stream is None or stream < 0 else [int(stream)]):
             self.live[s] = False
             self.next_id[s] = 1
             self.overflow[s] = 0
+            self.has_prev[s] = False
 
     # ---- the pieces of a step (float64 scalars; the order of the operations is the rule) ----
     @staticmethod
@@ -212,11 +242,42 @@ class Tracker:
             d2[s, :] = np.inf
             d2[:, r] = np.inf
 
-    def _step_stream(self, s, dets, n, dt):
+    def _carry(self, s, pose, psi):
+        """Stage 0: the live slots of stream s from the previous posed sensor frame into the frame of `pose`."""
+        M, u = _swp.relative_transform(pose, self.prev_pose[s])
+        dpsi = np.float64(psi) - self.prev_psi[s]
+        x = self.x[s]
+        for k in np.nonzero(self.live[s])[0]:
+            px, py, pz, vx, vy, vz = x[k]
+            for i in range(3):
+                x[k, i] = ((M[i, 0] * px + M[i, 1] * py) + M[i, 2] * pz) + u[i]
+                x[k, 3 + i] = (M[i, 0] * vx + M[i, 1] * vy) + M[i, 2] * vz
+            self.yaw[s, k] = self.yaw[s, k] + dpsi
+
+    def _fixed_out(self, s, pose, psi):
+        """The rows of _out[s] in the fixed frame of `pose`."""
+        m = int(self._nout[s])
+        o = self._outf[s]
+        o[:] = self._out[s]
+        st = self._out[s]["state"]
+        for k in range(m):
+            px, py, pz, vx, vy, vz = st[k]
+            for i in range(3):
+                o["state"][k, i] = ((pose[i, 0] * px + pose[i, 1] * py) + pose[i, 2] * pz) + pose[i, 3]
+                o["state"][k, 3 + i] = (pose[i, 0] * vx + pose[i, 1] * vy) + pose[i, 2] * vz
+            o["yaw"][k] = self._out[s]["yaw"][k] + np.float64(psi)
+        self._noutf[s] = m
+
+    def _step_stream(self, s, dets, n, dt, pose=None):
         c = self.cfg
         M = PP_TRACK_MAX
         x, p, live = self.x[s], self.p[s], self.live[s]
         dt = np.float64(dt)
+        psi = None
+        if pose is not None:
+            psi = math.atan2(float(pose[1, 0]), float(pose[0, 0]))
+            if self.has_prev[s]:
+                self._carry(s, pose, psi)
         for k in np.nonzero(live)[0]:
             for q in range(3):
                 x[k, q] = self.predict_axis(x[k, q], x[k, q + 3], dt)
@@ -284,10 +345,19 @@ class Tracker:
             out[f][:m] = getattr(self, f)[s, idx]
         out["det_row"][:m] = det_row[idx]
         self._nout[s] = m
+        if pose is None:
+            self._noutf[s] = -1
+        else:
+            self._fixed_out(s, pose, psi)
+            self.prev_pose[s] = pose
+            self.prev_psi[s] = psi
+            self.has_prev[s] = True
 
-    def step(self, dets, n_dets, dt=None):
+    def step(self, dets, n_dets, dt=None, poses=None):
         """dets [batch, rows] (engine.DET_DTYPE rows: box3d_lidar, score, label are read), n_dets [batch], dt [batch]
-        seconds or None (the period).  A count with the non-finite flag leaves its stream untouched.  Returns tracks()."""
+        seconds or None (the period), poses [k, 3, 4] sensor-to-fixed transforms for streams 0 .. k - 1 (1 <= k <= batch;
+        the others step without one) or None.  A count with the non-finite flag leaves its stream untouched.  Returns
+        tracks()."""
         n_dets = np.asarray(n_dets).reshape(-1)
         batch = int(n_dets.shape[0])
         if batch < 1 or batch > self.streams:
@@ -301,11 +371,17 @@ class Tracker:
         for b in range(batch):
             if not (math.isfinite(dts[b]) and dts[b] > 0.0):
                 raise ValueError(f"dt of stream {b} is {dts[b]} (must be finite and > 0)")
+        P = None
+        if poses is not None:
+            k = np.asarray(poses).shape[0] if np.asarray(poses).ndim == 3 else -1
+            if k == 0 or k > batch:
+                raise ValueError(f"poses: {k} poses for {batch} streams")
+            P = _swp.check_poses(poses, k)
         for b in range(batch):
             raw = int(n_dets[b])
             if raw & _NONFINITE:
                 continue
-            self._step_stream(b, dets[b], min(max(raw, 0), dets.shape[1]), dts[b])
+            self._step_stream(b, dets[b], min(max(raw, 0), dets.shape[1]), dts[b], P[b] if P is not None and b < len(P) else None)
         self._batch = batch
         return self.tracks()
 
@@ -315,18 +391,27 @@ class Tracker:
         b = self._batch if batch is None else int(batch)
         return self._out[:b].copy(), self._nout[:b].copy(), self.overflow[:b].copy()
 
+    def tracks_fixed(self, batch=None):
+        """(tracks [batch, PP_TRACK_MAX], n_tracks [batch]) of the last step in the FIXED frame of its poses: tracks()'s
+        rows with position, velocity and yaw mapped by the stream's pose; n_tracks is -1 for a stream whose step had none."""
+        b = self._batch if batch is None else int(batch)
+        tr, n = self._outf[:b].copy(), self._noutf[:b].copy()
+        for s in range(b):
+            tr[s, max(int(n[s]), 0):] = np.zeros((), TRACK_DTYPE)
+        return tr, n
+
     def info(self):
         return {"live": self.live.sum(axis=1).astype(np.int32), "next_id": self.next_id.copy(), "overflow": self.overflow.copy()}
 
 
-def track_np(config, frames, dts=None, streams=None):
-    """Functional form: frames = [(dets, n_dets), ...] in time order, dts = per-step dt ([batch] each, or None: the period).
-    Returns the list of tracks() after every step."""
+def track_np(config, frames, dts=None, streams=None, poses=None):
+    """Functional form: frames = [(dets, n_dets), ...] in time order, dts = per-step dt ([batch] each, or None: the period),
+    poses = per-step poses (as Tracker.step takes them, or None).  Returns the list of tracks() after every step."""
     frames = list(frames)
     if streams is None:
         streams = max((len(np.asarray(n).reshape(-1)) for _, n in frames), default=1)
     t = Tracker(config, streams)
-    return [t.step(d, n, None if dts is None else dts[i]) for i, (d, n) in enumerate(frames)]
+    return [t.step(d, n, None if dts is None else dts[i], None if poses is None else poses[i]) for i, (d, n) in enumerate(frames)]
 
 
 def det_track_ids(tracks, n_tracks, rows):

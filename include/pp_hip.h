@@ -48,7 +48,8 @@ extern "C" {
  * PP_TRACK_MAX, pp_track_config, pp_track, pp_set_tracking, pp_get_tracking, pp_set_track_dt, pp_get_tracks,
  * pp_track_update, pp_track_reset, pp_track_info.  Then PP_SWEEP_MAX, pp_sweep_config, pp_set_sweeps, pp_get_sweeps,
  * pp_sweeps_accumulate, pp_sweeps_accumulate_async, pp_sweeps_info, pp_sweeps_reset (declared behind
- * pp_frustum_crop_info: the stage sits where the crop sits). */
+ * pp_frustum_crop_info: the stage sits where the crop sits).  Then pp_set_track_pose, pp_get_tracks_fixed (declared
+ * behind pp_track_info). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -1191,16 +1192,36 @@ int pp_get_tracks(pp_handle h, pp_track* tracks, int32_t* n_tracks, int32_t* ove
 /* The same step on the handle's same tables, on host-given rows: dets [batch][rows] (rows 0 .. n_dets[b] - 1 of stream b
  * are read: box3d_lidar, score, label), 0 <= n_dets[b] <= rows <= 128, dt [batch] or NULL (cfg.period).  Uploads into
  * scratch of its own (a pass's results stay fetchable with pp_get_detections), synchronous; pp_get_tracks then returns
- * this step's tables.  PP_ERR_ARG for rows < 1; PP_ERR_STATE before the first pp_set_tracking (tracking need not be on) and
+ * this step's tables.  A count with bit 30 set (how a pass marks a frame whose head maps were not finite) is taken as
+ * it is: that stream stays untouched, as in a pass.  PP_ERR_ARG for rows < 1; PP_ERR_STATE before the first pp_set_tracking (tracking need not be on) and
  * while a training step is in flight. */
 int pp_track_update(pp_handle h, const pp_detection* dets, const int32_t* n_dets, int32_t rows, int32_t batch,
                     const double* dt);
-/* stream 0 .. max_batch - 1, or -1 for all: frees every track, the next id is 1 again, overflow 0 (waits for the stream).
+/* stream 0 .. max_batch - 1, or -1 for all: frees every track, the next id is 1 again, overflow 0, the previous ego pose
+ * (pp_set_track_pose) forgotten (waits for the stream).
  * PP_ERR_STATE while a training step is in flight, like every tracking call that queues work or writes the tables. */
 int pp_track_reset(pp_handle h, int32_t stream);
 /* Per stream, [max_batch] each (any may be NULL): live tracks, the next id, overflow.  Waits for the stream and only
  * reads, so it is allowed while a training step is in flight (it then waits for that step's launches as well). */
 int pp_track_info(pp_handle h, int32_t* live, int32_t* next_id, int32_t* overflow);
+/* Ego motion.  The tracks of a stream live in the sensor frame of its latest step.  poses [batch][3][4]: the
+ * sensor-to-fixed transforms [R | t] (row-major, as pp_sweeps_accumulate takes them) of the NEXT tracked step -- the
+ * pass's or pp_track_update's -- for streams 0 .. batch - 1.  Before its predict stage that step carries the live tracks of
+ * a posed stream from the sensor frame of the stream's previous posed step into the current one: with
+ * M = R_c^T R_p, u = R_c^T (t_p - t_c) (pp_sweeps_accumulate's operation order), x' = ((M00 x + M01 y) + M02 z) + u0,
+ * vx' = (M00 vx + M01 vy) + M02 vz (the other axes alike) and yaw' = yaw + (psi_c - psi_p), psi = atan2(R10, R00) taken
+ * on the host; a track's velocity is then the object's velocity over ground in the current sensor axes.  A stream's
+ * first posed step carries nothing; a stream without a pose steps exactly as without this call and keeps its previous
+ * pose.  The poses travel as pp_set_track_dt's values do and are spent likewise, also by a step that flags the stream's
+ * frame (the previous pose then stays: the next posed step carries over the whole motion); pp_track_update does not
+ * clear them; pp_track_reset forgets the stream's previous pose.  Refused before anything is queued: PP_ERR_ARG for a
+ * NULL handle or argument, a batch out of range, a pose that is not finite or whose rotation is further than 1e-6 from
+ * orthonormal (naming the stream); PP_ERR_STATE before the first pp_set_tracking and while a training step is in flight. */
+int pp_set_track_pose(pp_handle h, const double* poses /* [batch][3][4] */, int32_t batch);
+/* pp_get_tracks' rows of the same step in the FIXED frame: position R x + t, velocity R v, yaw + psi_c, every other
+ * field copied; n_tracks[b] is -1 (and the stream's rows zero) for a stream whose step had no pose.  Errors as
+ * pp_get_tracks. */
+int pp_get_tracks_fixed(pp_handle h, pp_track* tracks, int32_t* n_tracks);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
