@@ -21,6 +21,7 @@ SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_
            "rotate_iou.hip", "rotate_nms.hip", "box_project.hip", "loss.hip", "metrics.hip", "optim.hip", "grad_clip.hip", "train.hip", "targets.hip", "augment.hip", "gt_sample.hip", "ingest.hip",
            "gt_database.hip", "eval_stats.hip", "frustum_crop.hip", "weight_publish.hip", "soft_nms.hip",
            "api_sweeps.hip", "sweeps.hip",
+           "api_costmap.hip", "costmap.hip",
            "api_track.hip", "track.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
@@ -52,6 +53,7 @@ EXPORTS = [
     "pp_frustum_crop", "pp_frustum_crop_async", "pp_frustum_crop_info",
     "pp_set_sweeps", "pp_get_sweeps", "pp_sweeps_accumulate", "pp_sweeps_accumulate_async", "pp_sweeps_info", "pp_sweeps_reset",
     "pp_set_track_pose", "pp_get_tracks_fixed",
+    "pp_set_costmap", "pp_get_costmap_config", "pp_costmap_async", "pp_get_costmaps", "pp_costmap_info",
     "pp_set_nms_mode", "pp_get_nms_mode", "pp_rotate_nms",
     "pp_set_projection", "pp_get_projection", "pp_get_bboxes", "pp_box3d_to_bbox",
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
@@ -219,6 +221,8 @@ PP_SOFT_NMS_HARD, PP_SOFT_NMS_LINEAR, PP_SOFT_NMS_GAUSSIAN = 0, 1, 2      # enum
 PP_SNMS_MAX_BOXES = 4096      # most boxes that enter pp_soft_nms after pre_max_size
 PP_TRACK_MAX = 64      # tracks per stream (pp_set_tracking)
 PP_TRACK_MASK_ROWS = 128      # detection rows per frame the tracking step takes
+PP_COSTMAP_MAX_STEPS = 8      # predicted footprints per track (pp_set_costmap)
+PP_COSTMAP_MAX_CELLS = 262144      # width * height of a costmap
 PP_CLIP_NONE, PP_CLIP_VALUE, PP_CLIP_NORM, PP_CLIP_GLOBAL_NORM = 0, 1, 2, 3      # enum pp_grad_clip_mode
 
 
@@ -258,6 +262,28 @@ class PPSweepConfig(ctypes.Structure):
         ("capacity", ctypes.c_int32),
         ("history_decimate", ctypes.c_int32),
         ("time_feature", ctypes.c_int32),
+    ]
+
+
+class PPCostmapConfig(ctypes.Structure):
+    _fields_ = [
+        ("x_min", ctypes.c_double),
+        ("y_min", ctypes.c_double),
+        ("resolution", ctypes.c_double),
+        ("z_min", ctypes.c_double),
+        ("z_max", ctypes.c_double),
+        ("pad", ctypes.c_double),
+        ("min_score", ctypes.c_double),
+        ("horizon_dt", ctypes.c_double),
+        ("width", ctypes.c_int32),
+        ("height", ctypes.c_int32),
+        ("min_points", ctypes.c_int32),
+        ("objects", ctypes.c_int32),
+        ("confirmed_only", ctypes.c_int32),
+        ("horizon_steps", ctypes.c_int32),
+        ("point_cost", ctypes.c_int32),
+        ("object_cost", ctypes.c_int32),
+        ("predict_cost", ctypes.c_int32 * PP_COSTMAP_MAX_STEPS),
     ]
 
 
@@ -500,6 +526,11 @@ def lib():
     L.pp_track_info.argtypes = [vp, vp, vp, vp]
     L.pp_set_track_pose.argtypes = [vp, vp, i32]
     L.pp_get_tracks_fixed.argtypes = [vp, vp, vp]
+    L.pp_set_costmap.argtypes = [vp, ctypes.POINTER(PPCostmapConfig)]
+    L.pp_get_costmap_config.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(PPCostmapConfig)]
+    L.pp_costmap_async.argtypes = [vp]
+    L.pp_get_costmaps.argtypes = [vp, vp, vp, i32]
+    L.pp_costmap_info.argtypes = [vp, vp, vp, i32]
     L.pp_set_projection.argtypes = [vp, vp, i32]
     L.pp_get_projection.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_get_bboxes.argtypes = [vp, vp]

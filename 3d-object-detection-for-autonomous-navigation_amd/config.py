@@ -255,6 +255,20 @@ class Derived:
                 self.sweeps = c.to_dict()
             except ValueError as err:
                 raise ValueError(f"model.second.sweeps: {err}")
+        # not a key of the reference's YAML either (absent or False = off; True = the defaults): a dict of the
+        # costmap.CostmapConfig fields -- Engine.costmaps then gives one obstacle grid per frame from the resident points
+        # and the pass's detections or tracks (costmap.py states the rule).  Echoed in its full dict form.
+        cm = s.get("costmap")
+        if cm is None or cm is False:
+            self.costmap = None
+        else:
+            from .costmap import CostmapConfig
+            if not (cm is True or isinstance(cm, dict)):
+                raise ValueError(f"model.second.costmap: a dict of CostmapConfig fields, True or False, got {cm!r}")
+            try:
+                self.costmap = CostmapConfig.from_any(cm).to_dict()
+            except ValueError as err:
+                raise ValueError(f"model.second.costmap: {err}")
         er = config["eval_input_reader"]
         self.batch_size = int(er["batch_size"])
         self.anchor_area_threshold = er["anchor_area_threshold"]

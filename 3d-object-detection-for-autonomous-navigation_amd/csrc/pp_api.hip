@@ -374,6 +374,7 @@ static int run_post(pp_engine* e, int batch, bool to_host = false) {
 // frames and the last results of the fused path are gone, and the calls that would read them say so.
 static void stage_call_done(pp_engine* e) {
     e->cur_batch = 0;
+    ++e->resident_gen;
     e->cur_max_n = 0;
     e->cur_total = 0;
     e->results_batch = 0;
@@ -427,6 +428,7 @@ int flip_input(pp_engine* e) {
 // What the host knows of the resident frames: their offsets `off` [batch + 1], or (`exact` false) prefix sums of per-frame bounds
 void set_resident(pp_engine* e, int batch, const int* off, int max_n, bool exact) {
     e->cur_batch = batch;
+    ++e->resident_gen;
     e->cur_max_n = max_n;
     e->cur_total = off[batch];
     e->h_cur_off.assign(off, off + batch + 1);
@@ -799,6 +801,7 @@ int pp_destroy(pp_handle e) {
     delete e->train;
     track_release(e);
     sweeps_release(e);
+    costmap_release(e);
     for (void* p : {(void*)e->h_off_ring, (void*)e->ing.h_ring, (void*)e->ing.rig.h_frames, (void*)e->ing.rig.h_src, (void*)e->ing.h_feats, (void*)e->ing.rig.h_feats, (void*)e->crop.h_ring, (void*)e->h_feed[0], (void*)e->h_feed[1], (void*)e->h_train_losses,
                     (void*)e->h_dets, (void*)e->h_ndets, (void*)e->proj.h_bbox, (void*)e->metrics.h_counts})
         if (p) (void)hipHostFree(p);
@@ -1228,6 +1231,7 @@ int pp_detect_async(pp_handle e) {
         if (int st = enqueue_detect(e, B, e->cur_max_n)) return st;
     HIPCHK(e, hipEventRecord(e->ev_read[e->in_buf], e->stream));
     e->results_batch = B;
+    e->results_gen = e->resident_gen;
     e->results_buf = e->in_buf;
     e->proj.results = e->rule.proj ? B : 0;
     e->results_rows = det_rows(e);

@@ -682,6 +682,37 @@ struct SweepParams {
 int sweep_chunks(int n);       // chunks of a segment of n rows
 void launch_sweeps(const SweepParams& p, hipStream_t s);
 
+// costmap.hip: the resident points, the last pass's detections or the streams' tracks -> one int8 grid per frame
+// (pp_set_costmap; costmap.py states the rule).  One footprint of a frame's table, with a conservative cell box:
+struct CmFootprint {
+    double ox, oy, c, s, hx, hy;
+    int cost;
+    int ix0, ix1, iy0, iy1;        // no cell outside the box has its centre in the rectangle (an empty box: ix0 > ix1)
+    int pad;
+};
+#define PP_CM_TRACK_ROWS (PP_TRACK_MAX * (1 + PP_COSTMAP_MAX_STEPS))   // footprints of a stream's tracks at most
+struct CostmapParams {
+    pp_costmap_config cfg;
+    int batch, F;
+    int pitch;                     // cells of a row in words / grid / tap: width rounded up to 4
+    int max_n;                     // the host's bound on the rows of a frame
+    const float* points;           // the resident rows [.][F]
+    const int* offsets;            // [batch + 1] device values
+    const pp_detection* dets;      // objects = detections: [batch][det_rows]
+    const int* n_dets;             // [batch], PP_NDETS_NONFINITE: the frame takes no objects
+    int det_rows;
+    const TrkSlot* slots;          // objects = tracks: [B][PP_TRACK_MAX]
+    CmFootprint* table;            // [batch][table_rows], the frame's footprints compacted in source order
+    int table_rows;
+    int* n_fp;                     // [batch] footprints written
+    int* flagged;                  // [batch] 1: the frame's detections were flagged non-finite
+    int* in_grid;                  // [batch] points inside the grid (cleared with the words)
+    unsigned* words;               // [batch][height * pitch]: bits 0..30 the count, bit 31 observed without a count
+    int8_t* grid;                  // [batch][height * pitch]
+    int* tap;                      // [batch][height * pitch] the counts
+};
+void launch_costmap(const CostmapParams& p, hipStream_t s);
+
 // weight_publish.hip: the trainer's flat parameter / state buffers -> the detector's weight arrays, on the device
 enum PubKind {
     PUB_PFN_W,       // out [FA][cout] = params[src] * scale[c]

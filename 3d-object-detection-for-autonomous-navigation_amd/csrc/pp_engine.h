@@ -5,7 +5,7 @@
 // api_project.hip: the detector's image boxes and the standalone projection; api_class_nms.hip: joint / per-class suppression;
 // api_metrics.hip: the training metrics' counts; api_publish.hip: a trainer's weights into the detector, on the device;
 // api_track.hip: the per-stream track tables behind the detector's post-process; api_sweeps.hip: the per-stream sweep rings
-// in front of the pass.
+// in front of the pass; api_costmap.hip: the obstacle grid per frame behind it.
 #pragma once
 
 #include <cmath>
@@ -384,6 +384,27 @@ struct pp_engine {
         bool from_pass = false;        // ... it was a pass: pp_get_tracks consults its frames' numeric flags
     } trk;
 
+    // pp_set_costmap: one obstacle grid per frame from the resident points and the pass's detections or the streams'
+    // tracks (api_costmap.hip).  A stage behind the pass: plain launches, nothing of it in PostRule or a captured pass.
+    struct Costmap {
+        bool on = false;                   // pp_set_costmap gave a configuration and has not taken it back
+        pp_costmap_config cfg = {};        // the last configuration given
+        int pitch = 0;                     // cells of a row in the buffers below: width rounded up to 4
+        size_t cells = 0;                  // height * pitch, what the buffers were allocated for (0: none yet)
+        int hdr = 0;                       // int32 words in front of the count words: the frames' in-grid tallies
+        // made by pp_set_costmap and freed by costmap_release: not in `allocs`
+        unsigned* words = nullptr;         // [hdr + B * cells]: cleared before every run
+        int8_t* grid = nullptr;            // [B * cells]
+        int* tap = nullptr;                // [B * cells]
+        CmFootprint* table = nullptr;      // [B][table_rows]
+        int table_rows = 0;
+        int* info = nullptr;               // [2][B]: footprints, flagged
+        int batch = 0;                     // frames of the last run (pp_get_costmaps; 0: none)
+        int run_pitch = 0, run_w = 0, run_h = 0, run_objects = 0;   // ... and its grid
+    } cmap;
+    unsigned long long resident_gen = 0;   // counts the changes of the resident frames (set_resident, a stage call)
+    unsigned long long results_gen = 0;    // resident_gen of the last pp_detect_async
+
     int prof = 0;
     // pp_detect_async as one hipGraph launch, captured on first use per key.  The key is a DetectKey: whatever a pass
     // reads that is neither behind a device pointer nor dropped by graph_invalidate.  detect_key (pp_api.hip) builds it and
@@ -528,6 +549,7 @@ int track_check_pass(pp_engine* e);                     // api_track.hip: what a
 int run_track(pp_engine* e, int batch);                 // api_track.hip: k_track_step on this pass's d_dets / d_ndets
 void track_release(pp_engine* e);                       // ... what pp_destroy frees of it (page-locked memory, events)
 void sweeps_release(pp_engine* e);                      // api_sweeps.hip: what pp_destroy frees of the sweep rings
+void costmap_release(pp_engine* e);                     // api_costmap.hip: what pp_destroy frees of the costmap stage
 int ensure_metrics(pp_engine* e);                       // api_metrics.hip
 void fill_metrics_params(pp_engine* e, int batch, MetricsParams& p);   // ... on the handle's head map and loss.labels
 // ---- api_dataprep.hip: what the fused training steps (api_train.hip) queue ----

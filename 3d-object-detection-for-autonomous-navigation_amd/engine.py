@@ -15,6 +15,7 @@ from . import _lib
 from . import soft_nms as _soft
 from . import tracking as _trk
 from . import sweeps as _swp
+from . import costmap as _cm
 from .anchors import build_anchor_cells, build_anchors
 from .config import Derived
 from .weights import check_weights
@@ -397,6 +398,9 @@ class Engine:
         self._sweep_last = np.full(self.max_batch, np.nan)      # per stream: the last stamp an accumulate_sweeps* was given
         if d.sweeps is not None:
             self.set_sweeps(d.sweeps)
+        self._costmap_queued = False                            # a costmap_async whose grids costmaps() has not fetched
+        if d.costmap is not None:
+            self.set_costmap(d.costmap)
         if weights is not None:
             self.load_weights(weights)
 
@@ -1055,6 +1059,63 @@ class Engine:
             self._sweep_last[:] = np.nan
         else:
             self._sweep_last[s] = np.nan
+
+    # ---- obstacle costmap per frame (pp_set_costmap, pp_costmap_async, pp_get_costmaps; costmap.py states the rule) ----
+    def set_costmap(self, cfg):
+        """A costmap.CostmapConfig, a dict of its fields or True (the defaults): `costmaps()` then turns the resident
+        points and -- `objects` -- the pass's detections or the streams' tracks into one int8 grid per frame on the GPU, in
+        the layout of nav_msgs/OccupancyGrid (costmap.to_occupancy_grid makes the message's dict).  None: the stage off (the
+        default); its buffers are kept.  The config key model.second.costmap selects it at construction."""
+        if cfg is None or cfg is False:
+            self._check(self._lib.pp_set_costmap(self._h, None), "pp_set_costmap")
+            return
+        c = _cm.CostmapConfig.from_any(cfg)
+        pc = _lib.PPCostmapConfig()
+        for f, v in c.to_dict().items():
+            if f == "predict_cost":
+                pc.predict_cost[:] = v
+            else:
+                setattr(pc, f, v)
+        self._check(self._lib.pp_set_costmap(self._h, ctypes.byref(pc)), "pp_set_costmap")
+
+    @property
+    def costmap(self):
+        """The CostmapConfig in force, or None while the stage is off."""
+        on, pc = ctypes.c_int32(0), _lib.PPCostmapConfig()
+        self._check(self._lib.pp_get_costmap_config(self._h, ctypes.byref(on), ctypes.byref(pc)), "pp_get_costmap_config")
+        if not on.value:
+            return None
+        return _cm.CostmapConfig(**{f.name: (tuple(pc.predict_cost) if f.name == "predict_cost" else getattr(pc, f.name))
+                                    for f in dataclasses.fields(_cm.CostmapConfig)})
+
+    def costmap_async(self):
+        """Queues the stage on the resident frames behind whatever the engine's stream holds (pp_costmap_async) and returns
+        at once: behind a detect_async it reads that pass's detections or the tables its tracking step leaves."""
+        self._check(self._lib.pp_costmap_async(self._h), "pp_costmap_async")
+        self._costmap_queued = True
+        self._costmap_batch = self._batches()[0]
+        self._costmap_shape = (self.costmap.height, self.costmap.width)
+
+    def costmaps(self, batch=None, counts=False):
+        """The grids int8 [B, H, W] of the resident frames (waits for them): of the costmap_async still unfetched, else the
+        stage is queued here first.  counts=True: (grids, counts int32 [B, H, W]), the points counted per cell.  Raises
+        NumericError where `detections()` would (objects = detections; the grids are written all the same)."""
+        if not self._costmap_queued:
+            self.costmap_async()
+        self._costmap_queued = False
+        B = int(batch) if batch is not None else self._costmap_batch
+        H, W = self._costmap_shape
+        grid = np.zeros((max(B, 1), H, W), np.int8)
+        cnt = np.zeros((max(B, 1), H, W), np.int32) if counts else None
+        self._check(self._lib.pp_get_costmaps(self._h, _ptr(grid), _ptr(cnt), B), "pp_get_costmaps")
+        return (grid[:B], cnt[:B]) if counts else grid[:B]
+
+    def costmap_info(self):
+        """Per frame of the last costmap run (waits for it), int32 [B] each: `points_in_grid`, `footprints`."""
+        B = getattr(self, "_costmap_batch", 0)
+        out = {k: np.zeros(max(B, 1), np.int32) for k in ("points_in_grid", "footprints")}
+        self._check(self._lib.pp_costmap_info(self._h, *(_ptr(v) for v in out.values()), B), "pp_costmap_info")
+        return {k: v[:B] for k, v in out.items()}
 
     def _pose_args(self, poses, stamps, batch, who):
         """poses= of a detect*: checked before anything is queued (None: no accumulation); stamps then serve the sweeps, and

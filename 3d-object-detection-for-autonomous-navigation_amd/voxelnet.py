@@ -63,6 +63,10 @@ class VoxelNet:
         """The image boxes of the pass that has just run; None (the placeholder) without model.second.project_bbox."""
         return self.engine.bboxes(batch) if self.d.project_bbox else None
 
+    def costmaps(self, batch=None, counts=False):
+        """Engine.costmaps of the pass that has just run (model.second.costmap, or engine.set_costmap)."""
+        return self.engine.costmaps(batch, counts)
+
     def _need_p2(self, p2, who):
         if self.d.project_bbox and p2 is None:
             raise ValueError(f"{who}: model.second.project_bbox is on: pass p2 (the frames' camera matrices)")

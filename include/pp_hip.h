@@ -49,7 +49,9 @@ extern "C" {
  * pp_track_update, pp_track_reset, pp_track_info.  Then PP_SWEEP_MAX, pp_sweep_config, pp_set_sweeps, pp_get_sweeps,
  * pp_sweeps_accumulate, pp_sweeps_accumulate_async, pp_sweeps_info, pp_sweeps_reset (declared behind
  * pp_frustum_crop_info: the stage sits where the crop sits).  Then pp_set_track_pose, pp_get_tracks_fixed (declared
- * behind pp_track_info). */
+ * behind pp_track_info).  Then PP_COSTMAP_MAX_STEPS, PP_COSTMAP_MAX_CELLS, pp_costmap_config, pp_set_costmap,
+ * pp_get_costmap_config, pp_costmap_async, pp_get_costmaps, pp_costmap_info (declared behind pp_get_tracks_fixed: the
+ * stage reads what a pass and its tracking step leave on the device). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -1222,6 +1224,55 @@ int pp_set_track_pose(pp_handle h, const double* poses /* [batch][3][4] */, int3
  * field copied; n_tracks[b] is -1 (and the stream's rows zero) for a stream whose step had no pose.  Errors as
  * pp_get_tracks. */
 int pp_get_tracks_fixed(pp_handle h, pp_track* tracks, int32_t* n_tracks);
+
+/* ---- Obstacle costmap per frame (costmap.py states the rule): the resident points, the last pass's detections or the
+ * streams' tracks as one int8 grid per frame in the layout of nav_msgs/OccupancyGrid: -1 unknown, 0 free, up to 100
+ * lethal; row-major grid[iy * width + ix], origin (x_min, y_min), in the sensor frame of that frame.  An opt-in stage
+ * behind the pass: plain launches on the handle's stream, not part of a captured pass. ---- */
+#define PP_COSTMAP_MAX_STEPS 8      /* predicted footprints per track */
+#define PP_COSTMAP_MAX_CELLS 262144 /* width * height */
+
+typedef struct pp_costmap_config {
+    double x_min;          /* the grid's origin, metres */
+    double y_min;
+    double resolution;     /* metres per cell, > 0 */
+    double z_min;          /* a point counts as an obstacle with z_min <= z <= z_max */
+    double z_max;
+    double pad;            /* metres added to a footprint's half extents, >= 0 */
+    double min_score;      /* detections under it leave no footprint */
+    double horizon_dt;     /* seconds between two predicted footprints of a track, > 0 */
+    int32_t width;         /* cells; width, height >= 1, width * height <= PP_COSTMAP_MAX_CELLS */
+    int32_t height;
+    int32_t min_points;    /* >= 1: counted points that make a cell an obstacle */
+    int32_t objects;       /* 0 none, 1 the last pass's detections, 2 the streams' tracks */
+    int32_t confirmed_only;/* tracks: only the confirmed ones */
+    int32_t horizon_steps; /* 0 .. PP_COSTMAP_MAX_STEPS predicted footprints per track */
+    int32_t point_cost;    /* 0 .. 100 */
+    int32_t object_cost;   /* 0 .. 100 */
+    int32_t predict_cost[PP_COSTMAP_MAX_STEPS]; /* 0 .. 100 each of the first horizon_steps; the rest is ignored */
+} pp_costmap_config;
+
+/* cfg == NULL: the stage off (the default); its buffers are kept.  Otherwise the configuration is validated (PP_ERR_ARG
+ * naming the field) and max_batch x cells x (4 + 1) bytes of count words and grid, the count tap (4 bytes a cell) and
+ * the footprint tables are allocated (rows padded to 4 cells); PP_ERR_HIP naming the bytes when the device cannot hold
+ * them.  PP_ERR_STATE while a training step is in flight. */
+int pp_set_costmap(pp_handle h, const pp_costmap_config* cfg);
+/* *on: 0 / 1; cfg_out (may be NULL): the last configuration given (zeros before the first). */
+int pp_get_costmap_config(pp_handle h, int32_t* on, pp_costmap_config* cfg_out);
+/* Queues the stage on the resident frames behind whatever the handle's stream holds: a clear of the count words, then
+ * three launches whatever the batch (footprints, points, compose).  The stage's read of the resident frames is ordered
+ * against a later upload or flip as a pass's read is.  Refused before anything is queued with PP_ERR_STATE: the stage is
+ * off; no frames are resident; a training step is in flight; objects = detections and no pass has run on the resident
+ * batch; objects = tracks before the first pp_set_tracking. */
+int pp_costmap_async(pp_handle h);
+/* The grids of the last pp_costmap_async (waits for the stream): grid int8 [batch][height][width]; counts int32 of the
+ * same shape (the points counted per cell) or NULL.  PP_ERR_STATE when no stage has run, PP_ERR_ARG when batch is not
+ * that run's.  With objects = detections, PP_ERR_NUMERIC where pp_get_detections would return it: a flagged frame takes
+ * no objects; every frame's grid is still written. */
+int pp_get_costmaps(pp_handle h, int8_t* grid, int32_t* counts, int32_t batch);
+/* Per frame of that run, [batch] each (either may be NULL): the frame's points inside the grid, its footprints.
+ * Errors as pp_get_costmaps, without PP_ERR_NUMERIC. */
+int pp_costmap_info(pp_handle h, int32_t* points_in_grid, int32_t* footprints, int32_t batch);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
