@@ -22,6 +22,7 @@ SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_
            "gt_database.hip", "eval_stats.hip", "frustum_crop.hip", "weight_publish.hip", "soft_nms.hip",
            "api_sweeps.hip", "sweeps.hip",
            "api_costmap.hip", "costmap.hip",
+           "api_occupancy.hip", "occupancy.hip",
            "api_track.hip", "track.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
@@ -54,6 +55,8 @@ EXPORTS = [
     "pp_set_sweeps", "pp_get_sweeps", "pp_sweeps_accumulate", "pp_sweeps_accumulate_async", "pp_sweeps_info", "pp_sweeps_reset",
     "pp_set_track_pose", "pp_get_tracks_fixed",
     "pp_set_costmap", "pp_get_costmap_config", "pp_costmap_async", "pp_get_costmaps", "pp_costmap_info",
+    "pp_set_occupancy", "pp_get_occupancy_config", "pp_occupancy_update_async", "pp_get_occupancy", "pp_occupancy_info",
+    "pp_occupancy_reset",
     "pp_set_nms_mode", "pp_get_nms_mode", "pp_rotate_nms",
     "pp_set_projection", "pp_get_projection", "pp_get_bboxes", "pp_box3d_to_bbox",
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
@@ -223,6 +226,7 @@ PP_TRACK_MAX = 64      # tracks per stream (pp_set_tracking)
 PP_TRACK_MASK_ROWS = 128      # detection rows per frame the tracking step takes
 PP_COSTMAP_MAX_STEPS = 8      # predicted footprints per track (pp_set_costmap)
 PP_COSTMAP_MAX_CELLS = 262144      # width * height of a costmap
+PP_OCC_MAX_CELLS = 1048576      # width * height of an occupancy window (pp_set_occupancy)
 PP_CLIP_NONE, PP_CLIP_VALUE, PP_CLIP_NORM, PP_CLIP_GLOBAL_NORM = 0, 1, 2, 3      # enum pp_grad_clip_mode
 
 
@@ -284,6 +288,21 @@ class PPCostmapConfig(ctypes.Structure):
         ("point_cost", ctypes.c_int32),
         ("object_cost", ctypes.c_int32),
         ("predict_cost", ctypes.c_int32 * PP_COSTMAP_MAX_STEPS),
+    ]
+
+
+class PPOccupancyConfig(ctypes.Structure):
+    _fields_ = [
+        ("resolution", ctypes.c_double),
+        ("z_min", ctypes.c_double),
+        ("z_max", ctypes.c_double),
+        ("max_range", ctypes.c_double),
+        ("width", ctypes.c_int32),
+        ("height", ctypes.c_int32),
+        ("l_hit", ctypes.c_int32),
+        ("l_miss", ctypes.c_int32),
+        ("l_min", ctypes.c_int32),
+        ("l_max", ctypes.c_int32),
     ]
 
 
@@ -531,6 +550,12 @@ def lib():
     L.pp_costmap_async.argtypes = [vp]
     L.pp_get_costmaps.argtypes = [vp, vp, vp, i32]
     L.pp_costmap_info.argtypes = [vp, vp, vp, i32]
+    L.pp_set_occupancy.argtypes = [vp, ctypes.POINTER(PPOccupancyConfig), vp, i32]
+    L.pp_get_occupancy_config.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(PPOccupancyConfig)]
+    L.pp_occupancy_update_async.argtypes = [vp, vp, i32]
+    L.pp_get_occupancy.argtypes = [vp, vp, vp, vp, i32]
+    L.pp_occupancy_info.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32]
+    L.pp_occupancy_reset.argtypes = [vp, i32]
     L.pp_set_projection.argtypes = [vp, vp, i32]
     L.pp_get_projection.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_get_bboxes.argtypes = [vp, vp]

@@ -802,6 +802,7 @@ int pp_destroy(pp_handle e) {
     track_release(e);
     sweeps_release(e);
     costmap_release(e);
+    occupancy_release(e);
     for (void* p : {(void*)e->h_off_ring, (void*)e->ing.h_ring, (void*)e->ing.rig.h_frames, (void*)e->ing.rig.h_src, (void*)e->ing.h_feats, (void*)e->ing.rig.h_feats, (void*)e->crop.h_ring, (void*)e->h_feed[0], (void*)e->h_feed[1], (void*)e->h_train_losses,
                     (void*)e->h_dets, (void*)e->h_ndets, (void*)e->proj.h_bbox, (void*)e->metrics.h_counts})
         if (p) (void)hipHostFree(p);

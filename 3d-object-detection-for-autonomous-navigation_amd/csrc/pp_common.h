@@ -713,6 +713,39 @@ struct CostmapParams {
 };
 void launch_costmap(const CostmapParams& p, hipStream_t s);
 
+// occupancy.hip: the resident points under a pose per stream -> the stream's rolling log-odds window and its int8 grid
+// (pp_set_occupancy; occupancy.py states the rule).  What one stream of a call needs, read from a device buffer:
+struct OccCall {
+    double r0[3], tx;              // row 0 of the pose [R | t]
+    double r1[3], ty;              // row 1
+    int ox, oy;                    // the new window's origin, global cell indices
+    int sdx, sdy;                  // a cell of the new window was cell (ix + sdx, iy + sdy) of the old one
+    int fresh;                     // 1: nothing of an old window is kept (none yet, a reset, a jump past the window)
+    int src;                       // which of the two state copies holds the old window; the new one goes to 1 - src
+    int pad[2];
+};
+#define PP_OCC_HIT 1u              // mark bits of an end cell of a frame
+#define PP_OCC_GROUND 2u
+#define PP_OCC_INFO 8              // int32 per stream: hits, ground, ignored, cells_hit, cells_free, listed cells, 2 spare
+struct OccParams {
+    pp_occupancy_config cfg;
+    int batch, F;
+    int pitch;                     // cells of a row in every buffer below: width rounded up to 4
+    int max_n;                     // the host's bound on the rows of a frame
+    int list_cap;                  // entries of a stream's list
+    const float* points;           // the resident rows [.][F]
+    const int* offsets;            // [batch + 1] device values
+    const OccCall* call;           // [batch]
+    unsigned* marks;               // [batch][height * pitch] the end cells' bits, cleared before the launches
+    unsigned char* passed;         // [batch][height * pitch] 1: a ray crossed the cell; cleared likewise
+    int* list;                     // [batch][list_cap]: the cells that took an endpoint, each once, in no fixed order
+    int* info;                     // [batch][PP_OCC_INFO], cleared before the launches
+    int16_t* logodds[2];           // [B][height * pitch] each: the two state copies
+    int8_t* grid[2];               // [B][height * pitch] each; -1 is also the state's "not known"
+    const int8_t* table;           // [l_max - l_min + 1]
+};
+void launch_occupancy(const OccParams& p, hipStream_t s);
+
 // weight_publish.hip: the trainer's flat parameter / state buffers -> the detector's weight arrays, on the device
 enum PubKind {
     PUB_PFN_W,       // out [FA][cout] = params[src] * scale[c]

@@ -5,7 +5,8 @@
 // api_project.hip: the detector's image boxes and the standalone projection; api_class_nms.hip: joint / per-class suppression;
 // api_metrics.hip: the training metrics' counts; api_publish.hip: a trainer's weights into the detector, on the device;
 // api_track.hip: the per-stream track tables behind the detector's post-process; api_sweeps.hip: the per-stream sweep rings
-// in front of the pass; api_costmap.hip: the obstacle grid per frame behind it.
+// in front of the pass; api_costmap.hip: the obstacle grid per frame behind it; api_occupancy.hip: the rolling occupancy
+// map per stream.
 #pragma once
 
 #include <cmath>
@@ -402,6 +403,35 @@ struct pp_engine {
         int batch = 0;                     // frames of the last run (pp_get_costmaps; 0: none)
         int run_pitch = 0, run_w = 0, run_h = 0, run_objects = 0;   // ... and its grid
     } cmap;
+
+    // pp_set_occupancy: one rolling log-odds window per stream in the fixed frame, updated from the resident frames under
+    // a pose per stream (api_occupancy.hip).  Plain launches on the handle's stream, nothing of it in a captured pass.
+    struct Occupancy {
+        static constexpr int RING = 4;     // calls whose poses may be on their way to the device at once
+        bool on = false;                   // pp_set_occupancy gave a configuration and has not taken it back
+        pp_occupancy_config cfg = {};      // the last configuration given
+        int pitch = 0;                     // cells of a row in the buffers below: width rounded up to 4
+        size_t cells = 0;                  // height * pitch, what the buffers were allocated for (0: none yet)
+        int list_cap = 0;
+        // made by pp_set_occupancy and freed by occupancy_release: not in `allocs`
+        unsigned* marks = nullptr;         // [B * cells]
+        unsigned char* passed = nullptr;   // [B * cells]
+        int* list = nullptr;               // [B][list_cap]
+        int* info = nullptr;               // [B][PP_OCC_INFO]
+        int16_t* logodds[2] = {nullptr, nullptr};   // [B * cells] each
+        int8_t* grid[2] = {nullptr, nullptr};       // [B * cells] each
+        int8_t* table = nullptr;           // [2001]
+        OccCall* d_call = nullptr;         // [B]
+        OccCall* h_call = nullptr;         // pinned [RING][B]
+        hipEvent_t call_ev[RING] = {nullptr, nullptr, nullptr, nullptr};
+        int call_slot = 0;
+        // per stream, [B]: what the host knows of the map (the window's origin is the host's own arithmetic)
+        std::vector<char> has;             // a window exists
+        std::vector<int> ox, oy;           // its origin cell
+        std::vector<int> cur;              // the state copy that holds it
+        std::vector<int> cleared;          // pp_occupancy_info: of the stream's last update
+        int batch = 0;                     // streams of the last update (pp_get_occupancy; 0: none)
+    } occ;
     unsigned long long resident_gen = 0;   // counts the changes of the resident frames (set_resident, a stage call)
     unsigned long long results_gen = 0;    // resident_gen of the last pp_detect_async
 
@@ -550,6 +580,7 @@ int run_track(pp_engine* e, int batch);                 // api_track.hip: k_trac
 void track_release(pp_engine* e);                       // ... what pp_destroy frees of it (page-locked memory, events)
 void sweeps_release(pp_engine* e);                      // api_sweeps.hip: what pp_destroy frees of the sweep rings
 void costmap_release(pp_engine* e);                     // api_costmap.hip: what pp_destroy frees of the costmap stage
+void occupancy_release(pp_engine* e);                   // api_occupancy.hip: what pp_destroy frees of the occupancy maps
 int ensure_metrics(pp_engine* e);                       // api_metrics.hip
 void fill_metrics_params(pp_engine* e, int batch, MetricsParams& p);   // ... on the handle's head map and loss.labels
 // ---- api_dataprep.hip: what the fused training steps (api_train.hip) queue ----

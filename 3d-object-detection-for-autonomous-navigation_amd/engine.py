@@ -16,6 +16,7 @@ from . import soft_nms as _soft
 from . import tracking as _trk
 from . import sweeps as _swp
 from . import costmap as _cm
+from . import occupancy as _occ
 from .anchors import build_anchor_cells, build_anchors
 from .config import Derived
 from .weights import check_weights
@@ -1116,6 +1117,83 @@ class Engine:
         out = {k: np.zeros(max(B, 1), np.int32) for k in ("points_in_grid", "footprints")}
         self._check(self._lib.pp_costmap_info(self._h, *(_ptr(v) for v in out.values()), B), "pp_costmap_info")
         return {k: v[:B] for k, v in out.items()}
+
+    # ---- rolling occupancy map per stream (pp_set_occupancy, pp_occupancy_update_async, pp_get_occupancy; occupancy.py states the rule) ----
+    def set_occupancy(self, cfg):
+        """An occupancy.OccupancyConfig, a dict of its fields or True (the defaults): the engine keeps one rolling
+        log-odds map per stream (frame b is stream b) in the fixed frame on the GPU; `occupancy_update_async(poses)`
+        updates the maps from the resident frames -- hits where returns end, free space along the rays -- and
+        `occupancy_maps()` fetches them as int8 grids in the layout of nav_msgs/OccupancyGrid with their origins
+        (occupancy.to_occupancy_grid makes the message's dict).  A configuration with another width, height, resolution
+        or log-odds field forgets every stream's map.  None: the stage off (the default); buffers and maps are kept."""
+        if cfg is None or cfg is False:
+            self._check(self._lib.pp_set_occupancy(self._h, None, None, 0), "pp_set_occupancy")
+            return
+        c = _occ.OccupancyConfig.from_any(cfg)
+        pc = _lib.PPOccupancyConfig()
+        for f, v in c.to_dict().items():
+            setattr(pc, f, v)
+        table = np.ascontiguousarray(_occ.cost_table(c), np.int8)
+        self._check(self._lib.pp_set_occupancy(self._h, ctypes.byref(pc), _ptr(table), len(table)), "pp_set_occupancy")
+
+    def _get_occupancy(self):
+        on, pc = ctypes.c_int32(0), _lib.PPOccupancyConfig()
+        self._check(self._lib.pp_get_occupancy_config(self._h, ctypes.byref(on), ctypes.byref(pc)), "pp_get_occupancy_config")
+        return bool(on.value), pc
+
+    @property
+    def occupancy(self):
+        """The OccupancyConfig in force, or None while the stage is off."""
+        on, pc = self._get_occupancy()
+        if not on:
+            return None
+        return _occ.OccupancyConfig(**{f.name: getattr(pc, f.name) for f in dataclasses.fields(_occ.OccupancyConfig)})
+
+    def occupancy_update_async(self, poses):
+        """Updates the maps of streams 0 .. B - 1 from the resident frames under poses [B, 3, 4] float64, the
+        sensor-to-fixed transforms (sweeps.pose_from_xyyaw / pose_from_matrix), exactly as occupancy.OccupancyMap.update
+        does on the host (pp_occupancy_update_async): queued behind whatever the engine's stream holds, returns at once.
+        B must be the resident batch; the other streams' maps stay as they are.  The update reads whatever is resident:
+        call it between the upload or ingest and accumulate_sweeps, whose carried rows would cast rays from the current
+        sensor position."""
+        if not self._get_occupancy()[0]:
+            raise RuntimeError("occupancy_update_async: the occupancy stage is not configured (set_occupancy first)")
+        P = np.asarray(poses)
+        B = P.shape[0] if P.ndim == 3 else -1
+        if B > self.max_batch:
+            raise ValueError(f"occupancy_update_async: {B} poses, the engine has {self.max_batch} streams")
+        P = _swp.check_poses(poses, B)
+        c = self.occupancy
+        for b in range(B):
+            _occ.window_origin(c, P[b])
+        self._check(self._lib.pp_occupancy_update_async(self._h, _ptr(P), B), "pp_occupancy_update_async")
+        self._occ_batch = B
+        self._occ_shape = (c.height, c.width)
+
+    def occupancy_maps(self, batch=None, logodds=False):
+        """(grids int8 [B, H, W], origins float64 [B, 2]) of the streams of the last occupancy_update_async (waits for
+        it; queues nothing): origins[b] is the fixed-frame (x, y) of grid b's cell [0, 0].  logodds=True: a third value,
+        the log-odds int16 [B, H, W] (0 where unknown).  A stream reset since the update reads all unknown with a NaN
+        origin.  Raises when no update has run, or when `batch` is not that update's."""
+        B = int(batch) if batch is not None else getattr(self, "_occ_batch", 0)
+        H, W = getattr(self, "_occ_shape", (1, 1))
+        grid = np.zeros((max(B, 1), H, W), np.int8)
+        lo = np.zeros((max(B, 1), H, W), np.int16) if logodds else None
+        org = np.zeros((max(B, 1), 2), np.float64)
+        self._check(self._lib.pp_get_occupancy(self._h, _ptr(grid), _ptr(lo), _ptr(org), B), "pp_get_occupancy")
+        return (grid[:B], org[:B], lo[:B]) if logodds else (grid[:B], org[:B])
+
+    def occupancy_info(self):
+        """Per frame of the last occupancy update (waits for it), int32 [B] each: rows `hits`, `ground`, `ignored`;
+        `cells_hit`, `cells_free` (passed and not hit); `cleared`, the cells of the new window the old one did not hold."""
+        B = getattr(self, "_occ_batch", 0)
+        out = {k: np.zeros(max(B, 1), np.int32) for k in ("hits", "ground", "ignored", "cells_hit", "cells_free", "cleared")}
+        self._check(self._lib.pp_occupancy_info(self._h, *(_ptr(v) for v in out.values()), B), "pp_occupancy_info")
+        return {k: v[:B] for k, v in out.items()}
+
+    def occupancy_reset(self, stream=None):
+        """Forgets the map of `stream` (None: of all streams): its next update starts from an unknown window."""
+        self._check(self._lib.pp_occupancy_reset(self._h, -1 if stream is None else int(stream)), "pp_occupancy_reset")
 
     def _pose_args(self, poses, stamps, batch, who):
         """poses= of a detect*: checked before anything is queued (None: no accumulation); stamps then serve the sweeps, and

@@ -67,6 +67,15 @@ class VoxelNet:
         """Engine.costmaps of the pass that has just run (model.second.costmap, or engine.set_costmap)."""
         return self.engine.costmaps(batch, counts)
 
+    def occupancy_update(self, poses):
+        """Engine.occupancy_update_async on the resident frames (engine.set_occupancy first): call it between the upload
+        or ingest and a sweep accumulation."""
+        return self.engine.occupancy_update_async(poses)
+
+    def occupancy_maps(self, batch=None, logodds=False):
+        """Engine.occupancy_maps of the last occupancy_update."""
+        return self.engine.occupancy_maps(batch, logodds)
+
     def _need_p2(self, p2, who):
         if self.d.project_bbox and p2 is None:
             raise ValueError(f"{who}: model.second.project_bbox is on: pass p2 (the frames' camera matrices)")

@@ -51,7 +51,9 @@ extern "C" {
  * pp_frustum_crop_info: the stage sits where the crop sits).  Then pp_set_track_pose, pp_get_tracks_fixed (declared
  * behind pp_track_info).  Then PP_COSTMAP_MAX_STEPS, PP_COSTMAP_MAX_CELLS, pp_costmap_config, pp_set_costmap,
  * pp_get_costmap_config, pp_costmap_async, pp_get_costmaps, pp_costmap_info (declared behind pp_get_tracks_fixed: the
- * stage reads what a pass and its tracking step leave on the device). */
+ * stage reads what a pass and its tracking step leave on the device).  Then PP_OCC_MAX_CELLS, pp_occupancy_config,
+ * pp_set_occupancy, pp_get_occupancy_config, pp_occupancy_update_async, pp_get_occupancy, pp_occupancy_info,
+ * pp_occupancy_reset (declared behind pp_costmap_info). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -1273,6 +1275,61 @@ int pp_get_costmaps(pp_handle h, int8_t* grid, int32_t* counts, int32_t batch);
 /* Per frame of that run, [batch] each (either may be NULL): the frame's points inside the grid, its footprints.
  * Errors as pp_get_costmaps, without PP_ERR_NUMERIC. */
 int pp_costmap_info(pp_handle h, int32_t* points_in_grid, int32_t* footprints, int32_t batch);
+
+/* ---- Rolling occupancy map per stream in the fixed (odometry) frame (occupancy.py states the rule): the resident points
+ * of frame b, under the stream's sensor-to-fixed pose, update an int16 log-odds grid (units of 0.01 nat) of width x
+ * height cells that stays centred on the sensor: the cell of an endpoint in the height band takes +l_hit, every cell a ray
+ * from the sensor's cell to an endpoint's cell crosses takes -l_miss (one ray per end cell, an integer walk from the
+ * sensor outwards), clamped to [l_min, l_max].  Published as int8 in the layout of nav_msgs/OccupancyGrid: -1 unknown,
+ * else cost_table[L - l_min] (0 .. 100); row-major grid[iy * width + ix], origin (ox, oy) * resolution in the fixed frame.
+ * An opt-in stage: plain launches on the handle's stream, not part of a captured pass. ---- */
+#define PP_OCC_MAX_CELLS 1048576 /* width * height */
+
+typedef struct pp_occupancy_config {
+    double resolution;     /* metres per cell, > 0 */
+    double z_min;          /* a used row with z >= z_min is a hit, below it a ground return (sensor-frame z) */
+    double z_max;          /* rows above it are ignored */
+    double max_range;      /* metres in the sensor's x y plane, > 0; rows beyond it are ignored */
+    int32_t width;         /* cells; width, height >= 1, width * height <= PP_OCC_MAX_CELLS */
+    int32_t height;
+    int32_t l_hit;         /* 1 .. 1000 */
+    int32_t l_miss;        /* 1 .. 1000 */
+    int32_t l_min;         /* -1000 <= l_min < 0 */
+    int32_t l_max;         /* 0 < l_max <= 1000 */
+} pp_occupancy_config;
+
+/* cfg == NULL: the stage off (the default); buffers and maps are kept.  Otherwise the configuration is validated
+ * (PP_ERR_ARG naming the field) and, for another shape, max_batch x cells x (4 + 1 + 2 x (2 + 1)) bytes of marks and two
+ * copies of log-odds and grid are allocated (rows padded to 4 cells; PP_ERR_HIP naming the bytes when the device cannot
+ * hold them).  cost_table: n_table = l_max - l_min + 1 values 0 .. 100, table[i] the cost of L = l_min + i; NULL (n_table
+ * ignored): floor(100 / (1 + exp(-(l_min + i) / 100)) + 0.5), computed here on the host.  A configuration with another
+ * width, height, resolution or log-odds field than the last forgets every stream's map; z_min, z_max, max_range and the
+ * table may change under a map.  Waits for the stream.  PP_ERR_STATE while a training step is in flight. */
+int pp_set_occupancy(pp_handle h, const pp_occupancy_config* cfg, const int8_t* cost_table, int32_t n_table);
+/* *on: 0 / 1; cfg_out (may be NULL): the last configuration given (zeros before the first). */
+int pp_get_occupancy_config(pp_handle h, int32_t* on, pp_occupancy_config* cfg_out);
+/* Updates the maps of streams 0 .. batch - 1 from the resident frames 0 .. batch - 1 under poses [batch][3][4], the
+ * sensor-to-fixed transforms [R | t] (row-major, as pp_sweeps_accumulate takes them): queued behind whatever the handle's
+ * stream holds -- the poses through a small device buffer, a clear of the marks, then three launches whatever the batch
+ * (endpoints, rays, apply).  The other streams' maps stay as they are.  The read of the resident frames is ordered
+ * against a later upload or flip as a pass's read is.  Refused before anything is queued: PP_ERR_STATE when the stage is
+ * off, no frames are resident or a training step is in flight; PP_ERR_ARG for a NULL argument, a batch that is not the
+ * resident one, a pose that is not finite or further than 1e-6 from orthonormal (naming the stream), or a translation
+ * with |t_x| / resolution or |t_y| / resolution >= 2^30. */
+int pp_occupancy_update_async(pp_handle h, const double* poses /* [batch][3][4] */, int32_t batch);
+/* The maps of the streams of the last update (waits for the stream): grid int8 [batch][height][width], logodds int16 of
+ * the same shape or NULL, origins [batch][2] the fixed-frame x y of each window's cell (0, 0).  A stream reset since then
+ * reads all unknown, with a NaN origin.  PP_ERR_STATE when no update has run since the map's configuration was given,
+ * PP_ERR_ARG when batch is not that update's. */
+int pp_get_occupancy(pp_handle h, int8_t* grid, int16_t* logodds, double* origins, int32_t batch);
+/* Per frame of that update, [batch] each (any may be NULL): rows that hit, ground rows, ignored rows, cells that took a
+ * hit, cells that were passed and not hit, cells of the new window that started unknown because the old window did not
+ * hold them (all of them at a stream's first update).  Errors as pp_get_occupancy. */
+int pp_occupancy_info(pp_handle h, int32_t* hits, int32_t* ground, int32_t* ignored, int32_t* cells_hit,
+                      int32_t* cells_free, int32_t* cleared, int32_t batch);
+/* stream 0 .. max_batch - 1, or -1 for all: forgets the stream's map; its next update starts from an unknown window.
+ * PP_ERR_STATE while a training step is in flight. */
+int pp_occupancy_reset(pp_handle h, int32_t stream);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
