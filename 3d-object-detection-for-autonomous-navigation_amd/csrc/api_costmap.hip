@@ -10,28 +10,21 @@ namespace {
 
 void free_buffers(pp_engine* e) {
     pp_engine::Costmap& g = e->cmap;
-    for (void* p : {(void*)g.words, (void*)g.grid, (void*)g.tap, (void*)g.table, (void*)g.info})
-        if (p) (void)hipFree(p);
-    g.words = nullptr; g.grid = nullptr; g.tap = nullptr; g.table = nullptr; g.info = nullptr;
+    g.mem.release();
     g.cells = 0; g.pitch = 0; g.table_rows = 0; g.batch = 0;
 }
 
 // Everything pp_set_costmap refuses of a configuration, by field name.
 int check_config(pp_engine* e, const pp_costmap_config& c) {
-    const struct { const char* name; double v; bool finite; } dbl[] = {
-        {"x_min", c.x_min, true}, {"y_min", c.y_min, true}, {"resolution", c.resolution, true}, {"z_min", c.z_min, false},
-        {"z_max", c.z_max, false}, {"pad", c.pad, true}, {"min_score", c.min_score, true}, {"horizon_dt", c.horizon_dt, true}};
-    for (const auto& f : dbl)
-        if (std::isnan(f.v) || (f.finite && !std::isfinite(f.v))) return fail(e, PP_ERR_ARG, "pp_set_costmap: %s is not finite", f.name);
+    const char* who = "pp_set_costmap";
+    if (int st = check_cfg_doubles(e, who, {{"x_min", c.x_min, true}, {"y_min", c.y_min, true}, {"resolution", c.resolution, true},
+                                            {"z_min", c.z_min, false}, {"z_max", c.z_max, false}, {"pad", c.pad, true},
+                                            {"min_score", c.min_score, true}, {"horizon_dt", c.horizon_dt, true}})) return st;
     if (!(c.resolution > 0.0)) return fail(e, PP_ERR_ARG, "pp_set_costmap: resolution = %g must be > 0", c.resolution);
     if (!(c.pad >= 0.0)) return fail(e, PP_ERR_ARG, "pp_set_costmap: pad = %g must be >= 0", c.pad);
     if (!(c.horizon_dt > 0.0)) return fail(e, PP_ERR_ARG, "pp_set_costmap: horizon_dt = %g must be > 0", c.horizon_dt);
     if (c.z_min > c.z_max) return fail(e, PP_ERR_ARG, "pp_set_costmap: z_min = %g above z_max = %g", c.z_min, c.z_max);
-    if (c.width < 1) return fail(e, PP_ERR_ARG, "pp_set_costmap: width = %d must be >= 1", c.width);
-    if (c.height < 1) return fail(e, PP_ERR_ARG, "pp_set_costmap: height = %d must be >= 1", c.height);
-    if ((long long)c.width * c.height > PP_COSTMAP_MAX_CELLS)
-        return fail(e, PP_ERR_ARG, "pp_set_costmap: width * height = %lld cells, at most PP_COSTMAP_MAX_CELLS = %d",
-                    (long long)c.width * c.height, PP_COSTMAP_MAX_CELLS);
+    if (int st = check_cfg_window(e, who, c.width, c.height, PP_COSTMAP_MAX_CELLS, "PP_COSTMAP_MAX_CELLS")) return st;
     if (c.min_points < 1) return fail(e, PP_ERR_ARG, "pp_set_costmap: min_points = %d must be >= 1", c.min_points);
     if (c.objects < 0 || c.objects > 2) return fail(e, PP_ERR_ARG, "pp_set_costmap: objects = %d (0 none, 1 detections, 2 tracks)", c.objects);
     if (c.horizon_steps < 0 || c.horizon_steps > PP_COSTMAP_MAX_STEPS)
@@ -50,14 +43,10 @@ int make_buffers(pp_engine* e, int pitch, size_t cells) {
     const int hdr = (int)((B + 3) & ~(size_t)3);          // the count words stay 16-byte aligned behind the tallies
     const int rows = std::max((int)PP_CM_TRACK_ROWS, e->ncls * e->cfg.nms_post_max_size);
     const size_t bytes = (hdr + B * cells) * 4 + B * cells + B * cells * 4 + B * rows * sizeof(CmFootprint) + 2 * B * sizeof(int);
-    hipError_t st = hipMalloc((void**)&g.words, (hdr + B * cells) * sizeof(unsigned));
-    if (st == hipSuccess) st = hipMalloc((void**)&g.grid, B * cells);
-    if (st == hipSuccess) st = hipMalloc((void**)&g.tap, B * cells * sizeof(int));
-    if (st == hipSuccess) st = hipMalloc((void**)&g.table, B * rows * sizeof(CmFootprint));
-    if (st == hipSuccess) st = hipMalloc((void**)&g.info, 2 * B * sizeof(int));
-    if (st != hipSuccess) {
+    StageMem& M = g.mem;
+    M(&g.words, hdr + B * cells); M(&g.grid, B * cells); M(&g.tap, B * cells); M(&g.table, B * rows); M(&g.info, 2 * B);
+    if (hipError_t st = M.failed()) {
         (void)hipGetLastError();
-        free_buffers(e);
         return fail(e, PP_ERR_HIP, "pp_set_costmap: %d streams x %zu cells (rows of %d) need %zu bytes of device memory and the "
                     "device cannot hold them (%s): lower width or height", e->B, cells, pitch, bytes, hipGetErrorString(st));
     }
@@ -108,8 +97,7 @@ int pp_costmap_async(pp_handle e) {
     if (!e) return PP_ERR_ARG;
     pp_engine::Costmap& g = e->cmap;
     if (!g.on) return fail(e, PP_ERR_STATE, "pp_costmap_async: the costmap stage is not configured (pp_set_costmap first)");
-    if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_costmap_async: a training step is in flight");
-    if (e->cur_batch < 1) return fail(e, PP_ERR_STATE, "pp_costmap_async: no frames are resident (upload or ingest frames first)");
+    if (int st = check_resident_call(e, "pp_costmap_async", e->cur_batch, "upload or ingest frames first")) return st;   // (the call has no batch of its own)
     const pp_costmap_config& c = g.cfg;
     const int B = e->cur_batch;
     if (c.objects == 1 && (e->results_batch != B || e->results_gen != e->resident_gen || e->results_rows < 1))
@@ -148,8 +136,8 @@ int pp_get_costmaps(pp_handle e, int8_t* grid, int32_t* counts, int32_t batch) {
     if (!e) return PP_ERR_ARG;
     if (!grid) return fail(e, PP_ERR_ARG, "pp_get_costmaps: grid is NULL");
     pp_engine::Costmap& g = e->cmap;
-    if (g.batch < 1 || !g.grid) return fail(e, PP_ERR_STATE, "pp_get_costmaps: no costmap stage has run (pp_costmap_async first)");
-    if (batch != g.batch) return fail(e, PP_ERR_ARG, "pp_get_costmaps: the last run had %d frames, batch is %d", g.batch, batch);
+    if (int st = check_last_run(e, "pp_get_costmaps", g.grid ? g.batch : 0, batch, true,
+                                "no costmap stage has run (pp_costmap_async first)", "run", "frames")) return st;
     (void)hipSetDevice(e->device);
     HIPCHK(e, hipStreamSynchronize(e->stream));
     // rows of `pitch` cells on the device, of `width` on the host; the frames lie row behind row in both
@@ -168,8 +156,8 @@ int pp_get_costmaps(pp_handle e, int8_t* grid, int32_t* counts, int32_t batch) {
 int pp_costmap_info(pp_handle e, int32_t* points_in_grid, int32_t* footprints, int32_t batch) {
     if (!e) return PP_ERR_ARG;
     pp_engine::Costmap& g = e->cmap;
-    if (g.batch < 1 || !g.grid) return fail(e, PP_ERR_STATE, "pp_costmap_info: no costmap stage has run (pp_costmap_async first)");
-    if (batch != g.batch) return fail(e, PP_ERR_ARG, "pp_costmap_info: the last run had %d frames, batch is %d", g.batch, batch);
+    if (int st = check_last_run(e, "pp_costmap_info", g.grid ? g.batch : 0, batch, true,
+                                "no costmap stage has run (pp_costmap_async first)", "run", "frames")) return st;
     (void)hipSetDevice(e->device);
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (points_in_grid) HIPCHK(e, hipMemcpy(points_in_grid, g.words, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost));

@@ -253,9 +253,9 @@ int check_call(pp_engine* e, const char* who, const IngestArgs<Layout>& a, Inges
 int ensure_ing(pp_engine* e) {
     pp_engine::Ing& g = e->ing;
     if (g.frames) return PP_OK;
-    HIPCHK(e, hipHostMalloc((void**)&g.h_ring, (size_t)pp_engine::OFF_RING * e->B * sizeof(pp_engine::Ing::Slot)));
     const size_t nf = (size_t)std::max(e->F - 3, 1);
-    if (!g.h_feats) HIPCHK(e, hipHostMalloc((void**)&g.h_feats, (size_t)pp_engine::OFF_RING * e->B * nf * sizeof(IngFeat)));
+    HIPCHK(e, g.h_ring.alloc(e->ring, (size_t)e->B));
+    HIPCHK(e, g.h_feats.alloc(e->ring, (size_t)e->B * nf));
     DevAlloc A{e};
     A(&g.feats, (size_t)e->B * nf);
     A(&g.finite, (size_t)e->B); A(&g.kept, (size_t)e->B); A(&g.frames, (size_t)e->B);     // (frames last: the ready flag)
@@ -267,32 +267,15 @@ int ensure_rig(pp_engine* e) {
     pp_engine::Ing::Rig& r = e->ing.rig;
     if (r.frames) return PP_OK;
     const size_t cap = (size_t)PP_RIG_MAX_SOURCES * e->B;
-    if (!r.h_frames) HIPCHK(e, hipHostMalloc((void**)&r.h_frames, (size_t)pp_engine::OFF_RING * cap * sizeof(pp_engine::Ing::Slot)));
-    if (!r.h_src) HIPCHK(e, hipHostMalloc((void**)&r.h_src, (size_t)pp_engine::OFF_RING * cap * sizeof(RigSource)));
     const size_t nf = (size_t)std::max(e->F - 3, 1);
-    if (!r.h_feats) HIPCHK(e, hipHostMalloc((void**)&r.h_feats, (size_t)pp_engine::OFF_RING * cap * nf * sizeof(IngFeat)));
+    HIPCHK(e, r.h_frames.alloc(e->ring, cap));
+    HIPCHK(e, r.h_src.alloc(e->ring, cap));
+    HIPCHK(e, r.h_feats.alloc(e->ring, cap * nf));
     r.sources_cap = (int)cap;
     DevAlloc A{e};
     A(&r.feats, cap * nf);
     A(&r.src, cap); A(&r.finite, cap); A(&r.kept, cap); A(&r.out_base, cap); A(&r.frames, cap);     // (frames last: the ready flag)
     return A.st;
-}
-
-// Where the records of a call travel: a plain call's through the handle's per-frame tables, a rig call's through the rig's
-// per-source ones; the ring slot's part of each pinned ring, and the device tables behind them.
-template <typename Frame>
-struct IngTables {
-    Frame* ring;                   // pinned, this slot's records
-    pp_engine::Ing::Slot* frames;  // device records
-    IngFeat* feat_ring;            // pinned, this slot's feature table
-    IngFeat* feats;                // device feature table
-};
-template <typename Frame>
-IngTables<Frame> ing_tables(pp_engine* e, bool rig, int slot, int nfeat) {
-    pp_engine::Ing& g = e->ing;
-    if (rig) return {(Frame*)(g.rig.h_frames + (size_t)slot * g.rig.sources_cap), g.rig.frames,
-                     g.rig.h_feats + (size_t)slot * g.rig.sources_cap * nfeat, g.rig.feats};
-    return {(Frame*)(g.h_ring + (size_t)slot * e->B), g.frames, g.h_feats + (size_t)slot * e->B * nfeat, g.feats};
 }
 
 // Flips to the other input buffer (as set_offsets does) and queues bytes -> staging -> points + offsets on `stream`
@@ -317,35 +300,37 @@ int enqueue_ingest(pp_engine* e, const uint8_t* data, const int64_t* bo, int bat
         if ((st = dgrow(e, &e->ing.chunks, &e->ing.cap_chunks, tables))) return st;
     }
     e->zc = false;
-    const int slot = e->off_slot;
-    e->off_slot = (slot + 1) % pp_engine::OFF_RING;
-    HIPCHK(e, hipEventSynchronize(e->off_ev[slot]));   // the copy that last used this slot has been consumed
-    pp_engine::Ing::Rig& R = e->ing.rig;
-    const IngTables<Frame> T = ing_tables<Frame>(e, rig, slot, plan.nfeat);
-    memcpy(T.ring, plan.frames.data(), (size_t)records * sizeof(Frame));
+    int slot;
+    HIPCHK(e, e->ring.take(&slot));
+    // a plain call's records travel through the handle's per-frame tables, a rig call's through the rig's per-source ones
+    pp_engine::Ing& G = e->ing;
+    pp_engine::Ing::Rig& R = G.rig;
+    Frame* h_frames = (Frame*)(rig ? R.h_frames : G.h_ring).at(slot);      // (a call packs its own record type tightly)
+    pp_engine::Ing::Slot* d_frames = rig ? R.frames : G.frames;
+    const RingArray<IngFeat>& h_feats = rig ? R.h_feats : G.h_feats;
+    IngFeat* d_feats = rig ? R.feats : G.feats;
+    memcpy(h_frames, plan.frames.data(), (size_t)records * sizeof(Frame));
     // the kept counts are device values: everything behind this call is sized from the frames' bounds
     set_resident(e, batch, plan.bound_off.data(), plan.max_bound, false);
     e->ing.batch = batch;
     R.sources = rig ? records : 0;
-    const int nb = flip_input(e);
-    HIPCHK(e, hipStreamWaitEvent(stream, e->ev_read[nb], 0));
+    if ((st = flip_for_write(e, stream))) return st;
     if (plan.bytes) HIPCHK(e, hipMemcpyAsync(e->ing.raw, data + bo[0], (size_t)plan.bytes, hipMemcpyHostToDevice, stream));
-    HIPCHK(e, hipMemcpyAsync(T.frames, T.ring, (size_t)records * sizeof(Frame), hipMemcpyHostToDevice, stream));
+    HIPCHK(e, hipMemcpyAsync(d_frames, h_frames, (size_t)records * sizeof(Frame), hipMemcpyHostToDevice, stream));
     if (rig) {
-        RigSource* src_ring = R.h_src + (size_t)slot * R.sources_cap;
-        memcpy(src_ring, plan.rig.data(), (size_t)records * sizeof(RigSource));
-        HIPCHK(e, hipMemcpyAsync(R.src, src_ring, (size_t)records * sizeof(RigSource), hipMemcpyHostToDevice, stream));
+        memcpy(R.h_src.at(slot), plan.rig.data(), (size_t)records * sizeof(RigSource));
+        HIPCHK(e, R.h_src.send(slot, R.src, (size_t)records, stream));
     }
     // the feature columns of a _fields call: a table beside the records, through the same ring slot on the same stream
     if (plan.nfeat) {
         const size_t nfe = (size_t)records * plan.nfeat;
-        memcpy(T.feat_ring, plan.feats.data(), nfe * sizeof(IngFeat));
-        HIPCHK(e, hipMemcpyAsync(T.feats, T.feat_ring, nfe * sizeof(IngFeat), hipMemcpyHostToDevice, stream));
+        memcpy(h_feats.at(slot), plan.feats.data(), nfe * sizeof(IngFeat));
+        HIPCHK(e, h_feats.send(slot, d_feats, nfe, stream));
     }
-    HIPCHK(e, hipEventRecord(e->off_ev[slot], stream));
+    HIPCHK(e, e->ring.sent(slot, stream));
     IngestParamsT<Frame> p;
     memset(&p, 0, sizeof(p));
-    p.raw = e->ing.raw; p.frames = (const Frame*)T.frames; p.records = records; p.batch = batch; p.stride = plan.stride;
+    p.raw = e->ing.raw; p.frames = (const Frame*)d_frames; p.records = records; p.batch = batch; p.stride = plan.stride;
     if (rig) {
         p.src = R.src; p.src_finite = R.finite; p.src_kept = R.kept; p.out_base = R.out_base;
     } else {
@@ -355,7 +340,7 @@ int enqueue_ingest(pp_engine* e, const uint8_t* data, const int64_t* bo, int bat
     p.chunk_cnt = e->ing.chunks; p.chunk_base = e->ing.chunks + (size_t)records * plan.stride;
     p.finite = e->ing.finite; p.kept = e->ing.kept; p.offsets = e->d_offsets; p.out = e->d_points;
     p.out_rows = (long long)e->B * e->NMAX;
-    p.feats = T.feats; p.nfeat = plan.nfeat;
+    p.feats = d_feats; p.nfeat = plan.nfeat;
     ProfScope ps(e, nullptr);
     launch_ingest(p, stream);
     HIPCHK(e, hipGetLastError());
@@ -402,8 +387,7 @@ int ingest_call(pp_engine* e, const char* who, const IngestArgs<Layout>& a) {
 // the counts of the last ingest, once it has run: n of each table (NULL: not wanted)
 int read_counts(pp_engine* e, int32_t* finite_counts, const int* d_finite, int32_t* kept_counts, const int* d_kept, int n) {
     (void)hipSetDevice(e->device);
-    HIPCHK(e, hipEventSynchronize(e->ev_up));        // an asynchronous ingest runs on the copy stream
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (int st = quiesce(e)) return st;              // (an asynchronous ingest runs on the copy stream)
     if (finite_counts) HIPCHK(e, hipMemcpy(finite_counts, d_finite, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (kept_counts) HIPCHK(e, hipMemcpy(kept_counts, d_kept, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return PP_OK;
@@ -511,9 +495,7 @@ int pp_ingest_rig_info(pp_handle e, int32_t* finite_counts, int32_t* kept_counts
 
 int pp_ingest_info(pp_handle e, int32_t* finite_counts, int32_t* kept_counts, int32_t batch) {
     if (!e) return PP_ERR_ARG;
-    if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_ingest_info: a training step is in flight");
-    if (e->ing.batch < 1) return fail(e, PP_ERR_STATE, "pp_ingest_info: no ingest has run");
-    if (batch != e->ing.batch) return fail(e, PP_ERR_ARG, "pp_ingest_info: the last ingest had %d frames, batch is %d", e->ing.batch, batch);
+    if (int st = check_last_run(e, "pp_ingest_info", e->ing.batch, batch, false, "no ingest has run", "ingest", "frames")) return st;
     return read_counts(e, finite_counts, e->ing.finite, kept_counts, e->ing.kept, batch);
 }
 

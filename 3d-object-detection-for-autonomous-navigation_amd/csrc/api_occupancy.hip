@@ -15,10 +15,7 @@ constexpr double OCC_CELL_LIMIT = 1073741824.0;   // |t| / resolution from which
 
 void free_buffers(pp_engine* e) {
     pp_engine::Occupancy& g = e->occ;
-    for (void* p : {(void*)g.marks, (void*)g.passed, (void*)g.list, (void*)g.logodds[0], (void*)g.logodds[1], (void*)g.grid[0], (void*)g.grid[1]})
-        if (p) (void)hipFree(p);
-    g.marks = nullptr; g.passed = nullptr; g.list = nullptr;
-    g.logodds[0] = g.logodds[1] = nullptr; g.grid[0] = g.grid[1] = nullptr;
+    g.mem.release();
     g.cells = 0; g.pitch = 0; g.list_cap = 0; g.batch = 0;
 }
 
@@ -29,18 +26,13 @@ void forget(pp_engine* e, int b0, int nb) {
 
 // Everything pp_set_occupancy refuses of a configuration, by field name.
 int check_config(pp_engine* e, const pp_occupancy_config& c) {
-    const struct { const char* name; double v; bool finite; } dbl[] = {
-        {"resolution", c.resolution, true}, {"z_min", c.z_min, false}, {"z_max", c.z_max, false}, {"max_range", c.max_range, true}};
-    for (const auto& f : dbl)
-        if (std::isnan(f.v) || (f.finite && !std::isfinite(f.v))) return fail(e, PP_ERR_ARG, "pp_set_occupancy: %s is not finite", f.name);
+    const char* who = "pp_set_occupancy";
+    if (int st = check_cfg_doubles(e, who, {{"resolution", c.resolution, true}, {"z_min", c.z_min, false}, {"z_max", c.z_max, false},
+                                            {"max_range", c.max_range, true}})) return st;
     if (!(c.resolution > 0.0)) return fail(e, PP_ERR_ARG, "pp_set_occupancy: resolution = %g must be > 0", c.resolution);
     if (!(c.max_range > 0.0)) return fail(e, PP_ERR_ARG, "pp_set_occupancy: max_range = %g must be > 0", c.max_range);
     if (c.z_min > c.z_max) return fail(e, PP_ERR_ARG, "pp_set_occupancy: z_min = %g above z_max = %g", c.z_min, c.z_max);
-    if (c.width < 1) return fail(e, PP_ERR_ARG, "pp_set_occupancy: width = %d must be >= 1", c.width);
-    if (c.height < 1) return fail(e, PP_ERR_ARG, "pp_set_occupancy: height = %d must be >= 1", c.height);
-    if ((long long)c.width * c.height > PP_OCC_MAX_CELLS)
-        return fail(e, PP_ERR_ARG, "pp_set_occupancy: width * height = %lld cells, at most PP_OCC_MAX_CELLS = %d",
-                    (long long)c.width * c.height, PP_OCC_MAX_CELLS);
+    if (int st = check_cfg_window(e, who, c.width, c.height, PP_OCC_MAX_CELLS, "PP_OCC_MAX_CELLS")) return st;
     if (c.l_hit < 1 || c.l_hit > 1000) return fail(e, PP_ERR_ARG, "pp_set_occupancy: l_hit = %d outside [1, 1000]", c.l_hit);
     if (c.l_miss < 1 || c.l_miss > 1000) return fail(e, PP_ERR_ARG, "pp_set_occupancy: l_miss = %d outside [1, 1000]", c.l_miss);
     if (c.l_min < -1000 || c.l_min >= 0) return fail(e, PP_ERR_ARG, "pp_set_occupancy: l_min = %d outside [-1000, -1]", c.l_min);
@@ -55,29 +47,22 @@ int make_fixed(pp_engine* e) {
     if (g.has.size() != B) {
         g.has.assign(B, 0); g.ox.assign(B, 0); g.oy.assign(B, 0); g.cur.assign(B, 0); g.cleared.assign(B, 0);
     }
-    if (!g.table) HIPCHK(e, hipMalloc((void**)&g.table, OCC_TABLE_MAX));
-    if (!g.info) HIPCHK(e, hipMalloc((void**)&g.info, B * PP_OCC_INFO * sizeof(int)));
-    if (!g.d_call) HIPCHK(e, hipMalloc((void**)&g.d_call, B * sizeof(OccCall)));
-    if (!g.h_call) HIPCHK(e, hipHostMalloc((void**)&g.h_call, (size_t)pp_engine::Occupancy::RING * B * sizeof(OccCall)));
-    for (hipEvent_t& ev : g.call_ev)
-        if (!ev) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    return PP_OK;
+    HIPCHK(e, g.h_call.alloc(g.ring, B));
+    if (g.d_call) return PP_OK;
+    DevAlloc A{e};
+    A(&g.table, OCC_TABLE_MAX); A(&g.info, B * PP_OCC_INFO); A(&g.d_call, B);     // (d_call last: the ready flag)
+    return A.st;
 }
 
 int make_buffers(pp_engine* e, int pitch, size_t cells, int list_cap) {
     pp_engine::Occupancy& g = e->occ;
     const size_t B = (size_t)e->B;
     const size_t bytes = B * cells * (4 + 1 + 2 * (2 + 1)) + B * (size_t)list_cap * sizeof(int);
-    hipError_t st = hipMalloc((void**)&g.marks, B * cells * sizeof(unsigned));
-    if (st == hipSuccess) st = hipMalloc((void**)&g.passed, B * cells);
-    if (st == hipSuccess) st = hipMalloc((void**)&g.list, B * (size_t)list_cap * sizeof(int));
-    for (int k = 0; k < 2; ++k) {
-        if (st == hipSuccess) st = hipMalloc((void**)&g.logodds[k], B * cells * sizeof(int16_t));
-        if (st == hipSuccess) st = hipMalloc((void**)&g.grid[k], B * cells);
-    }
-    if (st != hipSuccess) {
+    StageMem& M = g.mem;
+    M(&g.marks, B * cells); M(&g.passed, B * cells); M(&g.list, B * (size_t)list_cap);
+    for (int k = 0; k < 2; ++k) { M(&g.logodds[k], B * cells); M(&g.grid[k], B * cells); }
+    if (hipError_t st = M.failed()) {
         (void)hipGetLastError();
-        free_buffers(e);
         return fail(e, PP_ERR_HIP, "pp_set_occupancy: %d streams x %zu cells (rows of %d) need %zu bytes of device memory and the "
                     "device cannot hold them (%s): lower width or height", e->B, cells, pitch, bytes, hipGetErrorString(st));
     }
@@ -88,14 +73,9 @@ int make_buffers(pp_engine* e, int pitch, size_t cells, int list_cap) {
 }  // namespace
 
 void occupancy_release(pp_engine* e) {
-    pp_engine::Occupancy& g = e->occ;
     free_buffers(e);
-    for (void* p : {(void*)g.table, (void*)g.info, (void*)g.d_call})
-        if (p) (void)hipFree(p);
-    if (g.h_call) (void)hipHostFree(g.h_call);
-    for (hipEvent_t ev : g.call_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    g = pp_engine::Occupancy();
+    e->occ.ring.release();
+    e->occ = pp_engine::Occupancy();
 }
 
 extern "C" {
@@ -157,24 +137,19 @@ int pp_occupancy_update_async(pp_handle e, const double* poses, int32_t batch) {
     const char* who = "pp_occupancy_update_async";
     pp_engine::Occupancy& g = e->occ;
     if (!g.on) return fail(e, PP_ERR_STATE, "%s: the occupancy stage is not configured (pp_set_occupancy first)", who);
-    if (e->train_pending) return fail(e, PP_ERR_STATE, "%s: a training step is in flight", who);
     if (!poses) return fail(e, PP_ERR_ARG, "%s: poses is NULL", who);
-    if (e->cur_batch < 1) return fail(e, PP_ERR_STATE, "%s: no frames are resident (upload or ingest frames first)", who);
-    if (int st = check_batch(e, batch)) return st;
-    if (batch != e->cur_batch) return fail(e, PP_ERR_ARG, "%s: %d frames are resident, batch is %d", who, e->cur_batch, batch);
+    if (int st = check_resident_call(e, who, batch, "upload or ingest frames first")) return st;
     const pp_occupancy_config& c = g.cfg;
-    for (int b = 0; b < batch; ++b) {
-        const double* P = poses + (size_t)b * 12;
-        if (int st = pose_check_finite(e, who, P, b)) return st;
-        if (int st = pose_check_orthonormal(e, who, P, b)) return st;
+    if (int st = check_poses(e, who, poses, nullptr, batch, [&](int b, const double* P) {
         if (!(std::fabs(P[3] / c.resolution) < OCC_CELL_LIMIT) || !(std::fabs(P[7] / c.resolution) < OCC_CELL_LIMIT))
             return fail(e, PP_ERR_ARG, "%s: poses: the translation of stream %d (%g, %g) is 2^30 cells of %g m or more from the origin",
                         who, b, P[3], P[7], c.resolution);
-    }
+        return (int)PP_OK;
+    })) return st;
     (void)hipSetDevice(e->device);
-    const int slot = g.call_slot;
-    HIPCHK(e, hipEventSynchronize(g.call_ev[slot]));      // the copy that last used this slot has been consumed
-    OccCall* call = g.h_call + (size_t)slot * e->B;
+    int slot;
+    HIPCHK(e, g.ring.take(&slot));
+    OccCall* call = g.h_call.at(slot);
     std::vector<int> cleared((size_t)batch, 0);
     const int W = c.width, H = c.height;
     for (int b = 0; b < batch; ++b) {
@@ -196,7 +171,6 @@ int pp_occupancy_update_async(pp_handle e, const double* poses, int32_t batch) {
     OccParams p;
     memset(&p, 0, sizeof(p));
     if (int st = resident_points(e, batch, e->stream, false, &p.points)) return st;
-    g.call_slot = (slot + 1) % pp_engine::Occupancy::RING;
     p.cfg = c;
     p.batch = batch; p.F = e->F; p.pitch = g.pitch; p.max_n = std::min(e->cur_max_n, e->NMAX); p.list_cap = g.list_cap;
     p.offsets = e->d_offsets;
@@ -206,8 +180,8 @@ int pp_occupancy_update_async(pp_handle e, const double* poses, int32_t batch) {
     p.grid[0] = g.grid[0]; p.grid[1] = g.grid[1];
     p.table = g.table;
     prof_reset(e);
-    HIPCHK(e, hipMemcpyAsync(g.d_call, call, (size_t)batch * sizeof(OccCall), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipEventRecord(g.call_ev[slot], e->stream));
+    HIPCHK(e, g.h_call.send(slot, g.d_call, (size_t)batch, e->stream));
+    HIPCHK(e, g.ring.sent(slot, e->stream));
     // the marks and the tallies of this call's streams
     HIPCHK(e, hipMemsetAsync(g.marks, 0, (size_t)batch * g.cells * sizeof(unsigned), e->stream));
     HIPCHK(e, hipMemsetAsync(g.passed, 0, (size_t)batch * g.cells, e->stream));
@@ -234,8 +208,8 @@ int pp_get_occupancy(pp_handle e, int8_t* grid, int16_t* logodds, double* origin
     if (!grid) return fail(e, PP_ERR_ARG, "pp_get_occupancy: grid is NULL");
     if (!origins) return fail(e, PP_ERR_ARG, "pp_get_occupancy: origins is NULL");
     pp_engine::Occupancy& g = e->occ;
-    if (g.batch < 1 || !g.marks) return fail(e, PP_ERR_STATE, "pp_get_occupancy: no update has run (pp_occupancy_update_async first)");
-    if (batch != g.batch) return fail(e, PP_ERR_ARG, "pp_get_occupancy: the last update had %d streams, batch is %d", g.batch, batch);
+    if (int st = check_last_run(e, "pp_get_occupancy", g.marks ? g.batch : 0, batch, true,
+                                "no update has run (pp_occupancy_update_async first)", "update", "streams")) return st;
     (void)hipSetDevice(e->device);
     HIPCHK(e, hipStreamSynchronize(e->stream));
     // rows of `pitch` cells on the device, of `width` on the host
@@ -262,8 +236,8 @@ int pp_occupancy_info(pp_handle e, int32_t* hits, int32_t* ground, int32_t* igno
                       int32_t* cleared, int32_t batch) {
     if (!e) return PP_ERR_ARG;
     pp_engine::Occupancy& g = e->occ;
-    if (g.batch < 1 || !g.marks) return fail(e, PP_ERR_STATE, "pp_occupancy_info: no update has run (pp_occupancy_update_async first)");
-    if (batch != g.batch) return fail(e, PP_ERR_ARG, "pp_occupancy_info: the last update had %d streams, batch is %d", g.batch, batch);
+    if (int st = check_last_run(e, "pp_occupancy_info", g.marks ? g.batch : 0, batch, true,
+                                "no update has run (pp_occupancy_update_async first)", "update", "streams")) return st;
     (void)hipSetDevice(e->device);
     HIPCHK(e, hipStreamSynchronize(e->stream));
     std::vector<int> info((size_t)batch * PP_OCC_INFO, 0);

@@ -9,23 +9,8 @@ static_assert(sizeof(SweepChunk) == 32 && sizeof(SweepXf) == 104, "sweeps.hip re
 namespace {
 
 void free_ring(pp_engine* e) {
-    pp_engine::Sweeps& g = e->swp;
-    for (void* p : {(void*)g.ring, (void*)g.slot_cnt, (void*)g.slot_valid, (void*)g.head, (void*)g.slot_pose, (void*)g.slot_stamp,
-                    (void*)g.xf, (void*)g.segs, (void*)g.chunks, (void*)g.seg_chunk0, (void*)g.frame_chunks, (void*)g.nchunks,
-                    (void*)g.info, (void*)g.d_call})
-        if (p) (void)hipFree(p);
-    g.ring = nullptr; g.slot_cnt = g.slot_valid = g.head = nullptr; g.slot_pose = g.slot_stamp = nullptr;
-    g.xf = nullptr; g.segs = g.chunks = nullptr; g.seg_chunk0 = g.frame_chunks = g.nchunks = nullptr;
-    g.info = nullptr; g.d_call = nullptr;
-    g.chunk_cap = 0;
-    g.cfg.history = 0;
-}
-
-// both streams idle: nothing queued reads the ring or the tables any more
-int quiesce(pp_engine* e) {
-    HIPCHK(e, hipEventSynchronize(e->ev_up));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return PP_OK;
+    e->swp.mem.release();
+    e->swp.chunk_cap = e->swp.cfg.history = 0;
 }
 
 // forgets the history of streams b0 .. b0 + nb - 1 (the device is idle)
@@ -39,9 +24,6 @@ int forget(pp_engine* e, size_t b0, size_t nb) {
     return PP_OK;
 }
 
-template <typename Tp>
-hipError_t ring_alloc(Tp** p, size_t count) { return hipMalloc((void**)p, std::max(count, (size_t)1) * sizeof(Tp)); }
-
 // The ring and the tables of configuration c (capacity filled in): max_batch streams.
 int make_ring(pp_engine* e, const pp_sweep_config& c) {
     pp_engine::Sweeps& g = e->swp;
@@ -52,23 +34,15 @@ int make_ring(pp_engine* e, const pp_sweep_config& c) {
     const size_t cap = B * per_frame;
     if (cap > (size_t)INT32_MAX)
         return fail(e, PP_ERR_ARG, "pp_set_sweeps: history %d x capacity %d on %d streams needs %zu chunk records", c.history, c.capacity, e->B, cap);
-    hipError_t st = ring_alloc(&g.ring, ring_floats);
-    if (st == hipSuccess) st = ring_alloc(&g.slot_cnt, B * slots);
-    if (st == hipSuccess) st = ring_alloc(&g.slot_valid, B * slots);
-    if (st == hipSuccess) st = ring_alloc(&g.head, B);
-    if (st == hipSuccess) st = ring_alloc(&g.slot_pose, B * slots * 12);
-    if (st == hipSuccess) st = ring_alloc(&g.slot_stamp, B * slots);
-    if (st == hipSuccess) st = ring_alloc(&g.xf, B * H);
-    if (st == hipSuccess) st = ring_alloc(&g.segs, B * (H + 2));
-    if (st == hipSuccess) st = ring_alloc(&g.seg_chunk0, B * (H + 2));
-    if (st == hipSuccess) st = ring_alloc(&g.frame_chunks, B + 1);
-    if (st == hipSuccess) st = ring_alloc(&g.chunks, cap);
-    if (st == hipSuccess) st = ring_alloc(&g.nchunks, 1);
-    if (st == hipSuccess) st = ring_alloc(&g.info, 4 * B);
-    if (st == hipSuccess) st = ring_alloc(&g.d_call, B * 13);
-    if (st != hipSuccess) {
+    StageMem& M = g.mem;
+    M(&g.ring, ring_floats);
+    M(&g.slot_cnt, B * slots); M(&g.slot_valid, B * slots); M(&g.head, B);
+    M(&g.slot_pose, B * slots * 12); M(&g.slot_stamp, B * slots);
+    M(&g.xf, B * H); M(&g.segs, B * (H + 2)); M(&g.seg_chunk0, B * (H + 2)); M(&g.frame_chunks, B + 1);
+    M(&g.chunks, cap); M(&g.nchunks, 1);
+    M(&g.info, 4 * B); M(&g.d_call, B * 13);
+    if (hipError_t st = M.failed()) {
         (void)hipGetLastError();
-        free_ring(e);
         return fail(e, PP_ERR_HIP, "pp_set_sweeps: the ring of %d streams x %d slots x capacity %d rows x %d floats needs %zu bytes "
                     "of device memory and the device cannot hold it (%s): lower history or capacity, or raise history_decimate",
                     e->B, (int)slots, c.capacity, e->F, ring_floats * sizeof(float), hipGetErrorString(st));
@@ -87,49 +61,38 @@ int make_ring(pp_engine* e, const pp_sweep_config& c) {
 int check_sweeps(pp_engine* e, const char* who, const double* poses, const double* stamps, int batch) {
     const pp_engine::Sweeps& g = e->swp;
     if (!g.on) return fail(e, PP_ERR_STATE, "%s: sweeps are not configured (pp_set_sweeps first)", who);
-    if (e->train_pending) return fail(e, PP_ERR_STATE, "%s: a training step is in flight", who);
     if (!poses) return fail(e, PP_ERR_ARG, "%s: poses is NULL", who);
     if (!stamps) return fail(e, PP_ERR_ARG, "%s: stamps is NULL", who);
-    if (e->cur_batch < 1) return fail(e, PP_ERR_STATE, "%s: no frames are resident (upload or ingest frames first)", who);
-    if (int st = check_batch(e, batch)) return st;
-    if (batch != e->cur_batch) return fail(e, PP_ERR_ARG, "%s: %d frames are resident, batch is %d", who, e->cur_batch, batch);
-    for (int b = 0; b < batch; ++b) {
-        const double* P = poses + (size_t)b * 12;
-        if (int st = pose_check_finite(e, who, P, b)) return st;
-        if (!std::isfinite(stamps[b])) return fail(e, PP_ERR_ARG, "%s: stamps: the stamp of stream %d is not finite", who, b);
-        if (int st = pose_check_orthonormal(e, who, P, b)) return st;
+    if (int st = check_resident_call(e, who, batch, "upload or ingest frames first")) return st;
+    return check_poses(e, who, poses, stamps, batch, [&](int b, const double*) {
         const double last = g.last_stamp[(size_t)b];
         if (!std::isnan(last) && !(stamps[b] > last))
             return fail(e, PP_ERR_ARG, "%s: stamps: the stamp of stream %d does not increase (%.17g after %.17g)", who, b, stamps[b], last);
-    }
-    return PP_OK;
+        return (int)PP_OK;
+    });
 }
 
-// Queues poses and stamps -> device and the two kernels on `stream` (the main stream, or the copy stream): the resident
-// frames are read where they lie, their sizes on the device, and the output goes to the other input buffer, to which the
-// handle flips.  The host then knows bounds only: set_resident, not exact.
+// Queues poses and stamps -> device and the two kernels on `stream` along the rewrite path (pp_engine.h): the resident
+// frames' sizes are read on the device, the host then knows bounds only.
 int enqueue_sweeps(pp_engine* e, const double* poses, const double* stamps, int batch, hipStream_t stream) {
     pp_engine::Sweeps& g = e->swp;
     const pp_sweep_config& c = g.cfg;
-    const int slot = e->off_slot;
-    e->off_slot = (slot + 1) % pp_engine::OFF_RING;
-    HIPCHK(e, hipEventSynchronize(e->off_ev[slot]));   // the copy that last used this slot has been consumed
-    double* ring = g.h_ring + (size_t)slot * e->B * 13;
+    int slot;
+    HIPCHK(e, e->ring.take(&slot));
+    double* ring = g.h_ring.at(slot);
     for (int b = 0; b < batch; ++b) {
         memcpy(ring + (size_t)b * 13, poses + (size_t)b * 12, 12 * sizeof(double));
         ring[(size_t)b * 13 + 12] = stamps[b];
     }
-    SweepParams p;
-    memset(&p, 0, sizeof(p));
     int st;
-    if ((st = resident_points(e, batch, stream, true, &p.in))) return st;
-    p.offsets_in = e->d_offsets;
+    Rewrite w;
+    if ((st = rewrite_begin(e, batch, stream, &w))) return st;
     // the host's bounds: rows of an output frame, chunks of the move launch
     std::vector<int> bound((size_t)batch + 1, 0);
     int max_n = 0;
     long long chunk_bound = 0;
     for (int b = 0; b < batch; ++b) {
-        const int n_in = e->h_cur_off[(size_t)b + 1] - e->h_cur_off[(size_t)b];
+        const int n_in = w.bound[(size_t)b + 1] - w.bound[(size_t)b];
         const long long full = (long long)n_in + (long long)g.stored[(size_t)b] * c.capacity;
         const int n_out = (int)std::min<long long>(full, e->NMAX);
         const int n_push = std::min((n_in + c.history_decimate - 1) / c.history_decimate, c.capacity);
@@ -137,11 +100,13 @@ int enqueue_sweeps(pp_engine* e, const double* poses, const double* stamps, int 
         max_n = std::max(max_n, n_out);
         chunk_bound += sweep_chunks(n_in) + (long long)g.stored[(size_t)b] * sweep_chunks(c.capacity) + sweep_chunks(n_push);
     }
-    const int old = e->in_buf;
-    const int nb = flip_input(e);
-    HIPCHK(e, hipStreamWaitEvent(stream, e->ev_read[nb], 0));   // the pass that last read the buffer written here
-    HIPCHK(e, hipMemcpyAsync(g.d_call, ring, (size_t)batch * 13 * sizeof(double), hipMemcpyHostToDevice, stream));
-    HIPCHK(e, hipEventRecord(e->off_ev[slot], stream));
+    w.bound.swap(bound);
+    w.max_n = max_n;
+    HIPCHK(e, g.h_ring.send(slot, g.d_call, (size_t)batch * 13, stream));
+    HIPCHK(e, e->ring.sent(slot, stream));
+    SweepParams p;
+    memset(&p, 0, sizeof(p));
+    p.in = w.src; p.offsets_in = w.offsets_in;
     p.out = e->d_points; p.offsets_out = e->d_offsets;
     p.batch = batch; p.F = e->F; p.nmax = e->NMAX;
     p.history = c.history; p.capacity = c.capacity; p.decimate = c.history_decimate; p.time_feature = c.time_feature;
@@ -157,10 +122,7 @@ int enqueue_sweeps(pp_engine* e, const double* poses, const double* stamps, int 
         ProfScope ps(e, nullptr);
         launch_sweeps(p, stream);
     }
-    HIPCHK(e, hipGetLastError());
-    // the next upload flips back to the buffer read here: its writer waits for this event as for a pass
-    if (stream != e->stream) HIPCHK(e, hipEventRecord(e->ev_read[old], stream));
-    set_resident(e, batch, bound.data(), max_n, false);
+    if ((st = rewrite_end(e, batch, w, stream))) return st;
     for (int b = 0; b < batch; ++b) {
         g.last_stamp[(size_t)b] = stamps[b];
         g.stored[(size_t)b] = std::min(g.stored[(size_t)b] + 1, c.history);
@@ -172,11 +134,8 @@ int enqueue_sweeps(pp_engine* e, const double* poses, const double* stamps, int 
 }  // namespace
 
 void sweeps_release(pp_engine* e) {
-    pp_engine::Sweeps& g = e->swp;
     free_ring(e);
-    if (g.h_ring) (void)hipHostFree(g.h_ring);
-    if (g.ev_main) (void)hipEventDestroy(g.ev_main);
-    g = pp_engine::Sweeps();
+    e->swp = pp_engine::Sweeps();
 }
 
 extern "C" {
@@ -200,8 +159,7 @@ int pp_set_sweeps(pp_handle e, const pp_sweep_config* cfg) {
     if (e->F > crop_max_features())
         return fail(e, PP_ERR_UNSUPPORTED, "pp_set_sweeps: num_point_features is %d, rows of up to %d are moved", e->F, crop_max_features());
     (void)hipSetDevice(e->device);
-    if (!g.ev_main) HIPCHK(e, hipEventCreateWithFlags(&g.ev_main, hipEventDisableTiming));
-    if (!g.h_ring) HIPCHK(e, hipHostMalloc((void**)&g.h_ring, (size_t)pp_engine::OFF_RING * e->B * 13 * sizeof(double)));
+    HIPCHK(e, g.h_ring.alloc(e->ring, (size_t)e->B * 13));
     if (g.cfg.history != c.history || g.cfg.capacity != c.capacity) {
         if (int st = quiesce(e)) return st;
         g.on = false;
@@ -226,53 +184,21 @@ int pp_sweeps_accumulate(pp_handle e, const double* poses, const double* stamps,
     if (!counts_out) return fail(e, PP_ERR_ARG, "pp_sweeps_accumulate: counts_out is NULL");
     int st = check_sweeps(e, "pp_sweeps_accumulate", poses, stamps, batch);
     if (st) return st;
-    (void)hipSetDevice(e->device);
-    // an asynchronous call still running on the copy stream uses the same ring and tables
-    HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_up, 0));
-    prof_reset(e);
-    if ((st = enqueue_sweeps(e, poses, stamps, batch, e->stream))) return st;
-    HIPCHK(e, hipMemcpyAsync(counts_out, e->swp.info, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    // the counts read back become the host's copy of the offsets: everything downstream is sized from them
-    std::vector<int> off((size_t)batch + 1, 0);
-    int max_n = 0;
-    for (int b = 0; b < batch; ++b) {
-        const int bound = e->h_cur_off[(size_t)b + 1] - e->h_cur_off[(size_t)b];
-        if (counts_out[b] < 0 || counts_out[b] > bound)
-            return fail(e, PP_ERR_HIP, "pp_sweeps_accumulate: frame %d: the device wrote %d rows, the host's bound is %d", b, counts_out[b], bound);
-        off[(size_t)b + 1] = off[(size_t)b] + counts_out[b];
-        max_n = std::max(max_n, counts_out[b]);
-    }
-    set_resident(e, batch, off.data(), max_n, true);
-    if (points_out) {
-        const int total = off[(size_t)batch];
-        if (points_capacity < total)
-            return fail(e, PP_ERR_ARG, "pp_sweeps_accumulate: points_out holds %lld points, the frames have %d", (long long)points_capacity, total);
-        if (total) HIPCHK(e, hipMemcpy(points_out, e->d_points, (size_t)total * e->F * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    return PP_OK;
+    if ((st = rewrite_run(e, batch, false, [&](hipStream_t s) { return enqueue_sweeps(e, poses, stamps, batch, s); }))) return st;
+    return rewrite_sync_tail(e, "pp_sweeps_accumulate", "%s: frame %d: the device wrote %d rows, the host's bound is %d",
+                             "%s: points_out holds %lld points, the frames have %d", e->swp.info, batch, counts_out, points_out, points_capacity);
 }
 
 int pp_sweeps_accumulate_async(pp_handle e, const double* poses, const double* stamps, int32_t batch) {
     if (!e) return PP_ERR_ARG;
-    int st = check_sweeps(e, "pp_sweeps_accumulate_async", poses, stamps, batch);
-    if (st) return st;
-    (void)hipSetDevice(e->device);
-    // frames fed on the main stream must have arrived, the pass in flight reads the buffer this call writes, and a
-    // synchronous call's kernels use the same ring and tables: the copy stream waits for what the main stream holds now
-    HIPCHK(e, hipEventRecord(e->swp.ev_main, e->stream));
-    HIPCHK(e, hipStreamWaitEvent(e->copy_stream, e->swp.ev_main, 0));
-    prof_reset(e);
-    if ((st = enqueue_sweeps(e, poses, stamps, batch, e->copy_stream))) return st;
-    return finish_async_upload(e, batch);     // as pp_upload_points_async does
+    if (int st = check_sweeps(e, "pp_sweeps_accumulate_async", poses, stamps, batch)) return st;
+    return rewrite_run(e, batch, true, [&](hipStream_t s) { return enqueue_sweeps(e, poses, stamps, batch, s); });
 }
 
 int pp_sweeps_info(pp_handle e, int32_t* counts, int32_t* used, int32_t* truncated, int32_t* push_truncated, int32_t batch) {
     if (!e) return PP_ERR_ARG;
     const pp_engine::Sweeps& g = e->swp;
-    if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_sweeps_info: a training step is in flight");
-    if (g.batch < 1 || !g.info) return fail(e, PP_ERR_STATE, "pp_sweeps_info: no accumulate has run");
-    if (batch != g.batch) return fail(e, PP_ERR_ARG, "pp_sweeps_info: the last call had %d frames, batch is %d", g.batch, batch);
+    if (int st = check_last_run(e, "pp_sweeps_info", g.info ? g.batch : 0, batch, false, "no accumulate has run", "call", "frames")) return st;
     (void)hipSetDevice(e->device);
     if (int st = quiesce(e)) return st;
     int32_t* outs[4] = {counts, used, truncated, push_truncated};

@@ -23,15 +23,13 @@ int ensure_track(pp_engine* e) {
     A(&t.d_pose_q, B);
     A(&t.d_pose_prev, B);
     if (A.st) return A.st;
-    HIPCHK(e, hipHostMalloc((void**)&t.h_dt_ring, (size_t)pp_engine::OFF_RING * B * sizeof(double)));
+    HIPCHK(e, t.h_dt.alloc(t.dt_ring, B));
+    HIPCHK(e, t.h_pose.alloc(t.pose_ring, B));
     HIPCHK(e, hipHostMalloc((void**)&t.h_out, B * PP_TRACK_MAX * sizeof(pp_track)));
     HIPCHK(e, hipHostMalloc((void**)&t.h_nout, B * sizeof(int)));
     HIPCHK(e, hipHostMalloc((void**)&t.h_overflow, B * sizeof(int)));
-    HIPCHK(e, hipHostMalloc((void**)&t.h_pose_ring, (size_t)pp_engine::OFF_RING * B * sizeof(TrkPose)));
     HIPCHK(e, hipHostMalloc((void**)&t.h_out_fixed, B * PP_TRACK_MAX * sizeof(pp_track)));
     HIPCHK(e, hipHostMalloc((void**)&t.h_nout_fixed, B * sizeof(int)));
-    for (int i = 0; i < pp_engine::OFF_RING; ++i) HIPCHK(e, hipEventCreateWithFlags(&t.dt_ev[i], hipEventDisableTiming));
-    for (int i = 0; i < pp_engine::OFF_RING; ++i) HIPCHK(e, hipEventCreateWithFlags(&t.pose_ev[i], hipEventDisableTiming));
     HIPCHK(e, hipMemset(t.d_pose_q, 0, B * sizeof(TrkPose)));
     HIPCHK(e, hipMemset(t.d_pose_prev, 0, B * sizeof(TrkPose)));
     HIPCHK(e, hipMemset(t.state, 0, B * PP_TRACK_MAX * sizeof(TrkSlot)));
@@ -63,27 +61,24 @@ void fill_params(pp_engine* e, TrackParams& p, int batch, int rows, const pp_det
     p.out_fixed = t.h_out_fixed; p.n_out_fixed = t.h_nout_fixed;
 }
 
-// the seconds of the next step, through a ring slot of their own into d_dt, on the handle's stream
-int queue_dt(pp_engine* e, const double* dt, int batch) {
+// the seconds of the next step, through `slot` of their own ring (taken by the caller before it queued anything) into
+// d_dt, on the handle's stream
+int queue_dt(pp_engine* e, const double* dt, int batch, int slot) {
     pp_engine::Track& t = e->trk;
-    const int slot = t.dt_slot;
-    t.dt_slot = (slot + 1) % pp_engine::OFF_RING;
-    HIPCHK(e, hipEventSynchronize(t.dt_ev[slot]));     // the copy that last used this slot has been consumed
-    double* ring = t.h_dt_ring + (size_t)slot * e->B;
+    double* ring = t.h_dt.at(slot);
     if (dt) memcpy(ring, dt, (size_t)batch * sizeof(double));
     else memset(ring, 0, (size_t)batch * sizeof(double));
-    HIPCHK(e, hipMemcpyAsync(t.d_dt, ring, (size_t)batch * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipEventRecord(t.dt_ev[slot], e->stream));
+    HIPCHK(e, t.h_dt.send(slot, t.d_dt, (size_t)batch, e->stream));
+    HIPCHK(e, t.dt_ring.sent(slot, e->stream));
     return PP_OK;
 }
 
 // the poses of the next step, armed, through a ring slot of their own into d_pose_q, on the handle's stream
 int queue_pose(pp_engine* e, const double* poses, int batch) {
     pp_engine::Track& t = e->trk;
-    const int slot = t.pose_slot;
-    t.pose_slot = (slot + 1) % pp_engine::OFF_RING;
-    HIPCHK(e, hipEventSynchronize(t.pose_ev[slot]));   // the copy that last used this slot has been consumed
-    TrkPose* ring = t.h_pose_ring + (size_t)slot * e->B;
+    int slot;
+    HIPCHK(e, t.pose_ring.take(&slot));
+    TrkPose* ring = t.h_pose.at(slot);
     for (int b = 0; b < batch; ++b) {
         const double* P = poses + (size_t)b * 12;
         memcpy(ring[b].m, P, 12 * sizeof(double));
@@ -91,8 +86,8 @@ int queue_pose(pp_engine* e, const double* poses, int batch) {
         ring[b].has = 1;
         ring[b].pad = 0;
     }
-    HIPCHK(e, hipMemcpyAsync(t.d_pose_q, ring, (size_t)batch * sizeof(TrkPose), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipEventRecord(t.pose_ev[slot], e->stream));
+    HIPCHK(e, t.h_pose.send(slot, t.d_pose_q, (size_t)batch, e->stream));
+    HIPCHK(e, t.pose_ring.sent(slot, e->stream));
     return PP_OK;
 }
 
@@ -122,13 +117,10 @@ int run_track(pp_engine* e, int batch) {
 
 void track_release(pp_engine* e) {
     pp_engine::Track& t = e->trk;
-    for (void* p : {(void*)t.h_dt_ring, (void*)t.h_out, (void*)t.h_nout, (void*)t.h_overflow, (void*)t.h_pose_ring,
-                    (void*)t.h_out_fixed, (void*)t.h_nout_fixed})
+    for (void* p : {(void*)t.h_out, (void*)t.h_nout, (void*)t.h_overflow, (void*)t.h_out_fixed, (void*)t.h_nout_fixed})
         if (p) (void)hipHostFree(p);
-    for (hipEvent_t ev : t.dt_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : t.pose_ev)
-        if (ev) (void)hipEventDestroy(ev);
+    t.dt_ring.release();
+    t.pose_ring.release();
     t = pp_engine::Track();
 }
 
@@ -181,7 +173,9 @@ int pp_set_track_dt(pp_handle e, const double* dt, int32_t batch) {
     if (!e->trk.configured) return fail(e, PP_ERR_STATE, "pp_set_track_dt: pp_set_tracking has given no configuration");
     if (int st = check_dt(e, "pp_set_track_dt", dt, batch)) return st;
     (void)hipSetDevice(e->device);
-    return queue_dt(e, dt, batch);
+    int slot;
+    HIPCHK(e, e->trk.dt_ring.take(&slot));
+    return queue_dt(e, dt, batch, slot);
 }
 
 int pp_set_track_pose(pp_handle e, const double* poses, int32_t batch) {
@@ -190,48 +184,38 @@ int pp_set_track_pose(pp_handle e, const double* poses, int32_t batch) {
     if (e->train_pending) return fail(e, PP_ERR_STATE, "pp_set_track_pose: a training step is in flight");
     if (int st = check_batch(e, batch)) return st;
     if (!e->trk.configured) return fail(e, PP_ERR_STATE, "pp_set_track_pose: pp_set_tracking has given no configuration");
-    for (int b = 0; b < batch; ++b) {
-        if (int st = pose_check_finite(e, "pp_set_track_pose", poses + (size_t)b * 12, b)) return st;
-        if (int st = pose_check_orthonormal(e, "pp_set_track_pose", poses + (size_t)b * 12, b)) return st;
-    }
+    if (int st = check_poses(e, "pp_set_track_pose", poses, nullptr, batch, [](int, const double*) { return (int)PP_OK; })) return st;
     (void)hipSetDevice(e->device);
     return queue_pose(e, poses, batch);
 }
 
-int pp_get_tracks_fixed(pp_handle e, pp_track* tracks, int32_t* n_tracks) {
-    if (!e) return PP_ERR_ARG;
-    if (!tracks || !n_tracks) return fail(e, PP_ERR_ARG, "pp_get_tracks_fixed: NULL argument");
+// the rows and counts the last step left in page-locked memory (`out`, `n_out`), frame by frame, zeros behind the live rows
+static int copy_tracks(pp_engine* e, const char* who, const pp_track* out, const int* n_out, pp_track* tracks, int32_t* n_tracks) {
+    if (!tracks || !n_tracks) return fail(e, PP_ERR_ARG, "%s: NULL argument", who);
     const int B = e->trk.results;
-    if (B < 1) return fail(e, PP_ERR_STATE, "pp_get_tracks_fixed: the last pass ran untracked, or none has run (pp_set_tracking, then a pass)");
+    if (B < 1) return fail(e, PP_ERR_STATE, "%s: the last pass ran untracked, or none has run (pp_set_tracking, then a pass)", who);
     (void)hipSetDevice(e->device);
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (e->trk.from_pass)
-        if (int st = check_numeric(e, e->h_ndets, B, "pp_get_tracks_fixed")) return st;
+        if (int st = check_numeric(e, e->h_ndets, B, who)) return st;
     for (int b = 0; b < B; ++b) {
-        const size_t n = (size_t)std::max(0, std::min(e->trk.h_nout_fixed[b], PP_TRACK_MAX));
-        memcpy(tracks + (size_t)b * PP_TRACK_MAX, e->trk.h_out_fixed + (size_t)b * PP_TRACK_MAX, n * sizeof(pp_track));
+        const size_t n = (size_t)std::max(0, std::min(n_out[b], PP_TRACK_MAX));
+        memcpy(tracks + (size_t)b * PP_TRACK_MAX, out + (size_t)b * PP_TRACK_MAX, n * sizeof(pp_track));
         memset(tracks + (size_t)b * PP_TRACK_MAX + n, 0, (PP_TRACK_MAX - n) * sizeof(pp_track));
     }
-    memcpy(n_tracks, e->trk.h_nout_fixed, (size_t)B * sizeof(int));
+    memcpy(n_tracks, n_out, (size_t)B * sizeof(int));
     return PP_OK;
+}
+
+int pp_get_tracks_fixed(pp_handle e, pp_track* tracks, int32_t* n_tracks) {
+    if (!e) return PP_ERR_ARG;
+    return copy_tracks(e, "pp_get_tracks_fixed", e->trk.h_out_fixed, e->trk.h_nout_fixed, tracks, n_tracks);
 }
 
 int pp_get_tracks(pp_handle e, pp_track* tracks, int32_t* n_tracks, int32_t* overflow) {
     if (!e) return PP_ERR_ARG;
-    if (!tracks || !n_tracks) return fail(e, PP_ERR_ARG, "pp_get_tracks: NULL argument");
-    const int B = e->trk.results;
-    if (B < 1) return fail(e, PP_ERR_STATE, "pp_get_tracks: the last pass ran untracked, or none has run (pp_set_tracking, then a pass)");
-    (void)hipSetDevice(e->device);
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (e->trk.from_pass)
-        if (int st = check_numeric(e, e->h_ndets, B, "pp_get_tracks")) return st;
-    for (int b = 0; b < B; ++b) {
-        const size_t n = (size_t)std::max(0, std::min(e->trk.h_nout[b], PP_TRACK_MAX));
-        memcpy(tracks + (size_t)b * PP_TRACK_MAX, e->trk.h_out + (size_t)b * PP_TRACK_MAX, n * sizeof(pp_track));
-        memset(tracks + (size_t)b * PP_TRACK_MAX + n, 0, (PP_TRACK_MAX - n) * sizeof(pp_track));
-    }
-    memcpy(n_tracks, e->trk.h_nout, (size_t)B * sizeof(int));
-    if (overflow) memcpy(overflow, e->trk.h_overflow, (size_t)B * sizeof(int));
+    if (int st = copy_tracks(e, "pp_get_tracks", e->trk.h_out, e->trk.h_nout, tracks, n_tracks)) return st;
+    if (overflow) memcpy(overflow, e->trk.h_overflow, (size_t)e->trk.results * sizeof(int));
     return PP_OK;
 }
 
@@ -251,9 +235,11 @@ int pp_track_update(pp_handle e, const pp_detection* dets, const int32_t* n_dets
         if (int st = check_dt(e, "pp_track_update", dt, batch)) return st;
     (void)hipSetDevice(e->device);
     pp_engine::Track& t = e->trk;
+    int slot;
+    HIPCHK(e, t.dt_ring.take(&slot));
     HIPCHK(e, hipMemcpyAsync(t.in_dets, dets, (size_t)batch * rows * sizeof(pp_detection), hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipMemcpyAsync(t.in_n, n_dets, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, e->stream));
-    if (int st = queue_dt(e, dt, batch)) return st;
+    if (int st = queue_dt(e, dt, batch, slot)) return st;
     TrackParams p;
     fill_params(e, p, batch, rows, t.in_dets, t.in_n);
     prof_reset(e);

@@ -478,16 +478,13 @@ static int set_offsets(pp_engine* e, const int32_t* off, int batch, hipStream_t 
     int max_n = 0;
     if (int st = check_offsets(e, off, batch, &max_n)) return st;
     e->zc = false;                                     // inputs arrive by copy: the first kernel reads device memory
-    const int slot = e->off_slot;
-    e->off_slot = (slot + 1) % pp_engine::OFF_RING;
-    HIPCHK(e, hipEventSynchronize(e->off_ev[slot]));   // the copy that last used this slot has been consumed
-    int* ring = e->h_off_ring + (size_t)slot * (e->B + 1);
-    memcpy(ring, off, (size_t)(batch + 1) * sizeof(int));
+    int slot;
+    HIPCHK(e, e->ring.take(&slot));
+    memcpy(e->h_off.at(slot), off, (size_t)(batch + 1) * sizeof(int));
     set_resident(e, batch, off, max_n, true);
-    const int nb = flip_input(e);
-    HIPCHK(e, hipStreamWaitEvent(stream, e->ev_read[nb], 0));   // (a no-op on the main stream, which is ordered anyway)
-    HIPCHK(e, hipMemcpyAsync(e->d_offsets, ring, (batch + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIPCHK(e, hipEventRecord(e->off_ev[slot], stream));
+    if (int st = flip_for_write(e, stream)) return st;
+    HIPCHK(e, e->h_off.send(slot, e->d_offsets, (size_t)batch + 1, stream));
+    HIPCHK(e, e->ring.sent(slot, stream));
     return PP_OK;
 }
 
@@ -726,10 +723,9 @@ int pp_create(const pp_config* cfg, int device, pp_handle* out) {
             if (st2 == PP_OK && hipHostMalloc((void**)&e->h_dets, (size_t)e->B * e->ncls * cfg->nms_post_max_size * sizeof(pp_detection)) != hipSuccess) st2 = PP_ERR_HIP;
             if (st2 == PP_OK && hipHostMalloc((void**)&e->h_ndets, (size_t)e->B * sizeof(int)) != hipSuccess) st2 = PP_ERR_HIP;
             if (st2 == PP_OK && (hipEventCreate(&e->t0) != hipSuccess || hipEventCreate(&e->t1) != hipSuccess)) st2 = PP_ERR_HIP;
-            if (st2 == PP_OK && hipHostMalloc((void**)&e->h_off_ring, (size_t)pp_engine::OFF_RING * (e->B + 1) * sizeof(int)) != hipSuccess) st2 = PP_ERR_HIP;
-            for (int i = 0; i < pp_engine::OFF_RING && st2 == PP_OK; ++i)
-                if (hipEventCreateWithFlags(&e->off_ev[i], hipEventDisableTiming) != hipSuccess) st2 = PP_ERR_HIP;
+            if (st2 == PP_OK && e->h_off.alloc(e->ring, (size_t)e->B + 1) != hipSuccess) st2 = PP_ERR_HIP;
             if (st2 == PP_OK && hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming) != hipSuccess) st2 = PP_ERR_HIP;
+            if (st2 == PP_OK && hipEventCreateWithFlags(&e->ev_main, hipEventDisableTiming) != hipSuccess) st2 = PP_ERR_HIP;
             for (int i = 0; i < 2 && st2 == PP_OK; ++i) {
                 void* dp = nullptr;
                 if (hipHostMalloc((void**)&e->h_feed[i], sizeof(PpFeed) + (size_t)(e->B + 1) * sizeof(int)) != hipSuccess ||
@@ -799,14 +795,14 @@ int pp_destroy(pp_handle e) {
         if (p) (void)hipFree(p);
     if (e->train) for (auto& tg : e->train->graph) { destroy_exec(&tg.exec); destroy_exec(&tg.exec_bwd); }
     delete e->train;
+    e->ring.release();      // with the riders' arrays (before the stages reset the structs those live in)
     track_release(e);
     sweeps_release(e);
     costmap_release(e);
     occupancy_release(e);
-    for (void* p : {(void*)e->h_off_ring, (void*)e->ing.h_ring, (void*)e->ing.rig.h_frames, (void*)e->ing.rig.h_src, (void*)e->ing.h_feats, (void*)e->ing.rig.h_feats, (void*)e->crop.h_ring, (void*)e->h_feed[0], (void*)e->h_feed[1], (void*)e->h_train_losses,
-                    (void*)e->h_dets, (void*)e->h_ndets, (void*)e->proj.h_bbox, (void*)e->metrics.h_counts})
+    for (void* p : {(void*)e->h_feed[0], (void*)e->h_feed[1], (void*)e->h_train_losses, (void*)e->h_dets, (void*)e->h_ndets, (void*)e->proj.h_bbox, (void*)e->metrics.h_counts})
         if (p) (void)hipHostFree(p);
-    for (hipEvent_t ev : {e->off_ev[0], e->off_ev[1], e->off_ev[2], e->off_ev[3], e->ev_in, e->ev_up, e->ev_vox_main, e->ev_tgt, e->crop.ev_main,
+    for (hipEvent_t ev : {e->ev_in, e->ev_main, e->ev_up, e->ev_vox_main, e->ev_tgt,
                           e->ev_read[0], e->ev_read[1], e->t0, e->t1})
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->events) (void)hipEventDestroy(ev);

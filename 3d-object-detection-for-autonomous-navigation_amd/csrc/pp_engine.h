@@ -6,7 +6,7 @@
 // api_metrics.hip: the training metrics' counts; api_publish.hip: a trainer's weights into the detector, on the device;
 // api_track.hip: the per-stream track tables behind the detector's post-process; api_sweeps.hip: the per-stream sweep rings
 // in front of the pass; api_costmap.hip: the obstacle grid per frame behind it; api_occupancy.hip: the rolling occupancy
-// map per stream.
+// map per stream.  pp_ring.h: the pinned call ring and the stages' memory owner, which the handle's members are made of.
 #pragma once
 
 #include <cmath>
@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include "pp_common.h"
+#include "pp_ring.h"
 #include "train.h"
 
 struct KTime { const char* name; int ev; };
@@ -166,13 +167,9 @@ struct pp_engine {
     std::vector<int> h_cur_off;           // host copy of the resident frames' offsets [cur_batch + 1]
     bool off_host_exact = true;           // ... false: they are bounds, the sizes are device values (require_host_exact)
     int results_batch = 0;        // frames of the last enqueued pp_detect_async (0: no results to fetch)
-    // frame offsets travel through a small pinned ring (a pageable source would be staged synchronously and a
-    // single pinned buffer could be rewritten while its copy is still queued); a slot is reused only after the
-    // event recorded behind its copy has passed
-    static constexpr int OFF_RING = 4;
-    int* h_off_ring = nullptr;    // pinned [OFF_RING][B + 1]
-    hipEvent_t off_ev[OFF_RING] = {nullptr, nullptr, nullptr, nullptr};
-    int off_slot = 0;
+    CallRing ring;                // the handle's call ring (pp_ring.h): the frame offsets and their riders
+    RingArray<int> h_off;         // [B + 1] per slot
+    hipEvent_t ev_main = nullptr; // orders an asynchronous rewrite of the frames (copy stream) behind the main stream
     hipEvent_t ev_in = nullptr;   // orders the engine's stream behind a producer stream (pp_upload_points_device)
     // zero-copy feed of small batches (pp_upload_points_async, batch <= ZC_MAX_BATCH): one page-locked descriptor
     // per input buffer, read by k_cell_first; no copy-engine transfer, no events
@@ -244,20 +241,20 @@ struct pp_engine {
         uint8_t* raw = nullptr;  size_t cap_raw = 0;       // the messages' (images') bytes
         int* chunks = nullptr;   size_t cap_chunks = 0;    // [2][batch * stride]: chunk counts, chunk bases
         Slot* frames = nullptr;            // [B]
-        Slot* h_ring = nullptr;            // pinned [OFF_RING][B]: travels with the offsets' ring slots
+        RingArray<Slot> h_ring;            // [B] per slot of the handle's ring
         int *finite = nullptr, *kept = nullptr;            // [B] finite records (valid pixels), points kept
         IngFeat* feats = nullptr;          // [B][F - 3] feature columns of a pp_ingest_pointcloud2_fields* call
-        IngFeat* h_feats = nullptr;        // pinned [OFF_RING][B][F - 3]: travels with the frame records
+        RingArray<IngFeat> h_feats;        // [B][F - 3] per slot
         int batch = 0;                     // frames of the last ingest (pp_ingest_info)
         // a rig call (pp_ingest_rig_*) has one record per SOURCE: tables of their own, sized by sources_cap =
         // PP_RIG_MAX_SOURCES * B on first use (api_ingest.hip: ensure_rig); finite / kept above then hold the frames' sums
         struct Rig {
             Slot* frames = nullptr;        // [sources_cap]
             RigSource* src = nullptr;      // [sources_cap]
-            Slot* h_frames = nullptr;      // pinned [OFF_RING][sources_cap]: travel with the offsets' ring slots
-            RigSource* h_src = nullptr;    // pinned [OFF_RING][sources_cap]
+            RingArray<Slot> h_frames;      // [sources_cap] per slot of the handle's ring
+            RingArray<RigSource> h_src;    // [sources_cap] per slot
             IngFeat* feats = nullptr;      // [sources_cap][F - 3], as Ing::feats
-            IngFeat* h_feats = nullptr;    // pinned [OFF_RING][sources_cap][F - 3]
+            RingArray<IngFeat> h_feats;    // [sources_cap][F - 3] per slot
             int *finite = nullptr, *kept = nullptr, *out_base = nullptr;   // [sources_cap]
             int sources_cap = 0;
             int sources = 0;               // sources of the last ingest when it was a rig call, else 0 (pp_ingest_rig_info)
@@ -265,16 +262,15 @@ struct pp_engine {
     } ing;
     struct Crop {                          // frustum crop of the resident frames (pp_frustum_crop*; api_crop.hip: ensure_crop)
         double* planes = nullptr;          // [B][6][4]
-        double* h_ring = nullptr;          // pinned [OFF_RING][B][6][4]: the planes travel like the offsets, slot by slot
+        RingArray<double> h_ring;          // [B][6][4] per slot of the handle's ring
         int* chunks = nullptr;             // [2][B * crop_chunks(NMAX)]: chunk counts, chunk bases
         int* kept = nullptr;               // [B]
-        hipEvent_t ev_main = nullptr;      // orders an asynchronous crop (copy stream) behind the main stream
         int batch = 0;                     // frames of the last crop (pp_frustum_crop_info)
     } crop;
     struct Sweeps {                        // multi-sweep accumulation (pp_set_sweeps, pp_sweeps_accumulate*; api_sweeps.hip)
         bool on = false;                   // pp_set_sweeps gave a configuration and has not taken it back
         pp_sweep_config cfg = {};          // the configuration in force, capacity filled in (history 0: no ring yet)
-        // the streams' rings (SweepParams), made by pp_set_sweeps and freed by sweeps_release: not in `allocs`
+        StageMem mem;                      // owns the streams' rings and tables below (SweepParams): not in `allocs`
         float* ring = nullptr;
         int *slot_cnt = nullptr, *slot_valid = nullptr, *head = nullptr;
         double *slot_pose = nullptr, *slot_stamp = nullptr;
@@ -284,8 +280,7 @@ struct pp_engine {
         int chunk_cap = 0;
         int* info = nullptr;               // [4][B]: count, used, truncated, push_truncated
         double* d_call = nullptr;          // [B][13] the call's poses and stamps
-        double* h_ring = nullptr;          // pinned [OFF_RING][B][13]: they travel like the offsets, slot by slot
-        hipEvent_t ev_main = nullptr;      // orders an asynchronous call (copy stream) behind the main stream
+        RingArray<double> h_ring;          // [B][13] per slot of the handle's ring
         std::vector<double> last_stamp;    // [B] per stream: the last stamp accepted (NaN: none)
         std::vector<int> stored;           // [B] per stream: sweeps its ring holds at most (the host's bound)
         int batch = 0;                     // frames of the last call (pp_sweeps_info)
@@ -367,18 +362,16 @@ struct pp_engine {
         TrkSlot* state = nullptr;      // [B][PP_TRACK_MAX]
         int *next_id = nullptr, *overflow = nullptr;   // [B]
         double* d_dt = nullptr;        // [B] seconds of the next step per stream (0: the configuration's period)
-        double* h_dt_ring = nullptr;   // pinned [OFF_RING][B]: pp_set_track_dt's values travel like the frame offsets
-        hipEvent_t dt_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-        int dt_slot = 0;
+        CallRing dt_ring;              // pp_set_track_dt's values, consumed on the main stream
+        RingArray<double> h_dt;        // [B] per slot
         pp_track* h_out = nullptr;     // pinned [B][PP_TRACK_MAX]: the kernel stores the live rows straight into it (nothing on
         int *h_nout = nullptr, *h_overflow = nullptr;   // the device reads them: no device copy, no copy node behind the pass)
         pp_detection* in_dets = nullptr;   // [B][PP_TRACK_MASK_ROWS] pp_track_update's rows (d_dets stays a pass's)
         int* in_n = nullptr;               // [B]
         // pp_set_track_pose: the ego pose of the next step per stream, and of the last posed step that ran
         TrkPose *d_pose_q = nullptr, *d_pose_prev = nullptr;   // [B] each
-        TrkPose* h_pose_ring = nullptr;    // pinned [OFF_RING][B]: the poses travel as the dt values do
-        hipEvent_t pose_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-        int pose_slot = 0;
+        CallRing pose_ring;                // the poses travel as the dt values do, on a ring of their own
+        RingArray<TrkPose> h_pose;         // [B] per slot
         pp_track* h_out_fixed = nullptr;   // pinned [B][PP_TRACK_MAX]: the step's rows in the fixed frame (pp_get_tracks_fixed)
         int* h_nout_fixed = nullptr;       // pinned [B]; -1: the stream's step had no pose
         int results = 0;              // streams of the last tracked pass or pp_track_update (pp_get_tracks; 0: none)
@@ -393,7 +386,7 @@ struct pp_engine {
         int pitch = 0;                     // cells of a row in the buffers below: width rounded up to 4
         size_t cells = 0;                  // height * pitch, what the buffers were allocated for (0: none yet)
         int hdr = 0;                       // int32 words in front of the count words: the frames' in-grid tallies
-        // made by pp_set_costmap and freed by costmap_release: not in `allocs`
+        StageMem mem;                      // owns the buffers below, made by pp_set_costmap: not in `allocs`
         unsigned* words = nullptr;         // [hdr + B * cells]: cleared before every run
         int8_t* grid = nullptr;            // [B * cells]
         int* tap = nullptr;                // [B * cells]
@@ -407,24 +400,22 @@ struct pp_engine {
     // pp_set_occupancy: one rolling log-odds window per stream in the fixed frame, updated from the resident frames under
     // a pose per stream (api_occupancy.hip).  Plain launches on the handle's stream, nothing of it in a captured pass.
     struct Occupancy {
-        static constexpr int RING = 4;     // calls whose poses may be on their way to the device at once
         bool on = false;                   // pp_set_occupancy gave a configuration and has not taken it back
         pp_occupancy_config cfg = {};      // the last configuration given
         int pitch = 0;                     // cells of a row in the buffers below: width rounded up to 4
         size_t cells = 0;                  // height * pitch, what the buffers were allocated for (0: none yet)
         int list_cap = 0;
-        // made by pp_set_occupancy and freed by occupancy_release: not in `allocs`
+        StageMem mem;                      // owns the window-shaped buffers, made by pp_set_occupancy: not in `allocs`
         unsigned* marks = nullptr;         // [B * cells]
         unsigned char* passed = nullptr;   // [B * cells]
         int* list = nullptr;               // [B][list_cap]
-        int* info = nullptr;               // [B][PP_OCC_INFO]
         int16_t* logodds[2] = {nullptr, nullptr};   // [B * cells] each
         int8_t* grid[2] = {nullptr, nullptr};       // [B * cells] each
+        int* info = nullptr;               // [B][PP_OCC_INFO]; this and the next two whatever the window's shape (`allocs`)
         int8_t* table = nullptr;           // [2001]
         OccCall* d_call = nullptr;         // [B]
-        OccCall* h_call = nullptr;         // pinned [RING][B]
-        hipEvent_t call_ev[RING] = {nullptr, nullptr, nullptr, nullptr};
-        int call_slot = 0;
+        CallRing ring;                     // the calls' records, consumed on the main stream
+        RingArray<OccCall> h_call;         // [B] per slot
         // per stream, [B]: what the host knows of the map (the window's origin is the host's own arithmetic)
         std::vector<char> has;             // a window exists
         std::vector<int> ox, oy;           // its origin cell
@@ -478,6 +469,18 @@ inline int pose_check_orthonormal(pp_engine* e, const char* who, const double* P
             if (!(std::fabs(gij - (i == j ? 1.0 : 0.0)) <= PP_POSE_ORTHO_TOL))
                 return fail(e, PP_ERR_ARG, "%s: poses: the rotation of stream %d is not orthonormal (R R^T [%d][%d] = %.9g)", who, b, i, j, gij);
         }
+    return PP_OK;
+}
+// Both, stream by stream: finite, the stream's stamp (stamps NULL: the call has none), orthonormal, then `more(b, P)`
+template <typename More>
+int check_poses(pp_engine* e, const char* who, const double* poses, const double* stamps, int batch, More more) {
+    for (int b = 0; b < batch; ++b) {
+        const double* P = poses + (size_t)b * 12;
+        if (int st = pose_check_finite(e, who, P, b)) return st;
+        if (stamps && !std::isfinite(stamps[b])) return fail(e, PP_ERR_ARG, "%s: stamps: the stamp of stream %d is not finite", who, b);
+        if (int st = pose_check_orthonormal(e, who, P, b)) return st;
+        if (int st = more(b, P)) return st;
+    }
     return PP_OK;
 }
 
@@ -602,3 +605,111 @@ int augment_from_host(pp_engine* e, int batch, const float* gt_boxes, const int3
 int enqueue_gt_sample(pp_engine* e, int batch, const float* gt_boxes, const int32_t* gt_classes, const uint8_t* gt_valid,
                       const int32_t* gt_counts, int64_t total, const pp_gt_sample_config* sc, const pp_gts_cand* cands,
                       const int32_t* cand_counts, int max_out_n, hipStream_t up);
+
+// ---- the stages on the resident frames: one entry check, one rewrite path ----
+// What every call on the resident frames refuses before it looks at its own values (`hint`: how frames get there) ...
+inline int check_resident_call(pp_engine* e, const char* who, int batch, const char* hint) {
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "%s: a training step is in flight", who);
+    if (e->cur_batch < 1) return fail(e, PP_ERR_STATE, "%s: no frames are resident (%s)", who, hint);
+    if (int st = check_batch(e, batch)) return st;
+    if (batch != e->cur_batch) return fail(e, PP_ERR_ARG, "%s: %d frames are resident, batch is %d", who, e->cur_batch, batch);
+    return PP_OK;
+}
+// ... and what a reader of a stage's last run refuses (last_batch 0: there was none; `while_training`: it may run then)
+inline int check_last_run(pp_engine* e, const char* who, int last_batch, int batch, bool while_training, const char* none,
+                          const char* run, const char* unit) {
+    if (!while_training && e->train_pending) return fail(e, PP_ERR_STATE, "%s: a training step is in flight", who);
+    if (last_batch < 1) return fail(e, PP_ERR_STATE, "%s: %s", who, none);
+    if (batch != last_batch) return fail(e, PP_ERR_ARG, "%s: the last %s had %d %s, batch is %d", who, run, last_batch, unit, batch);
+    return PP_OK;
+}
+// both streams idle: nothing queued reads a stage's tables any more
+inline int quiesce(pp_engine* e) {
+    HIPCHK(e, hipEventSynchronize(e->ev_up));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return PP_OK;
+}
+
+// What pp_set_costmap and pp_set_occupancy refuse alike: a NaN in any double (an infinity where `finite`), a window that
+// is empty or larger than max_cells
+struct CfgDouble { const char* name; double v; bool finite; };
+inline int check_cfg_doubles(pp_engine* e, const char* who, std::initializer_list<CfgDouble> f) {
+    for (const CfgDouble& d : f)
+        if (std::isnan(d.v) || (d.finite && !std::isfinite(d.v))) return fail(e, PP_ERR_ARG, "%s: %s is not finite", who, d.name);
+    return PP_OK;
+}
+inline int check_cfg_window(pp_engine* e, const char* who, int width, int height, int max_cells, const char* max_name) {
+    if (width < 1) return fail(e, PP_ERR_ARG, "%s: width = %d must be >= 1", who, width);
+    if (height < 1) return fail(e, PP_ERR_ARG, "%s: height = %d must be >= 1", who, height);
+    if ((long long)width * height > max_cells)
+        return fail(e, PP_ERR_ARG, "%s: width * height = %lld cells, at most %s = %d", who, (long long)width * height, max_name, max_cells);
+    return PP_OK;
+}
+
+// Every writer of a new set of frames starts here: the other input buffer, `stream` behind the pass that last read it
+inline int flip_for_write(pp_engine* e, hipStream_t stream) {
+    const int nb = flip_input(e);
+    HIPCHK(e, hipStreamWaitEvent(stream, e->ev_read[nb], 0));
+    return PP_OK;
+}
+// A stage that replaces the resident frames (crop, sweeps) reads them where they lie and writes the new cloud into the
+// other input buffer:  rewrite_run(enqueue: rewrite_begin, the stage's copies and launch, rewrite_end) [rewrite_sync_tail]
+struct Rewrite {
+    const float* src = nullptr;        // the frames as the stage's kernels read them, and their offsets
+    const int* offsets_in = nullptr;
+    int old = 0;                       // the input buffer they lie in
+    std::vector<int> bound;            // the host's offsets (bounds) of the frames read; the stage may put the bounds of
+    int max_n = 0;                     // what it writes in their place -- rewrite_end makes them the resident ones
+};
+inline int rewrite_begin(pp_engine* e, int batch, hipStream_t stream, Rewrite* w) {
+    if (int st = resident_points(e, batch, stream, true, &w->src)) return st;
+    w->offsets_in = e->d_offsets;
+    w->bound = e->h_cur_off;           // (set_resident assigns the vector it would otherwise read)
+    w->max_n = e->cur_max_n;
+    w->old = e->in_buf;
+    return flip_for_write(e, stream);
+}
+// behind the stage's launch; the host then knows bounds only: set_resident, not exact
+inline int rewrite_end(pp_engine* e, int batch, const Rewrite& w, hipStream_t stream) {
+    HIPCHK(e, hipGetLastError());
+    // the next upload flips back to the buffer read here: its writer waits for this event as for a pass
+    if (stream != e->stream) HIPCHK(e, hipEventRecord(e->ev_read[w.old], stream));
+    set_resident(e, batch, w.bound.data(), w.max_n, false);
+    return PP_OK;
+}
+// Either entry point of such a stage, its checks passed: `enqueue(stream)` on the main stream behind an asynchronous call
+// that may still use the stage's tables, or on the copy stream behind what the main stream holds now (frames fed there, the
+// pass reading the buffer written, a synchronous call on the same tables), then as pp_upload_points_async ends.
+template <typename Enqueue>
+int rewrite_run(pp_engine* e, int batch, bool asynchronous, Enqueue enqueue) {
+    (void)hipSetDevice(e->device);
+    if (asynchronous) {
+        HIPCHK(e, hipEventRecord(e->ev_main, e->stream));
+        HIPCHK(e, hipStreamWaitEvent(e->copy_stream, e->ev_main, 0));
+    } else HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_up, 0));
+    prof_reset(e);
+    if (int st = enqueue(asynchronous ? e->copy_stream : e->stream)) return st;
+    return asynchronous ? finish_async_upload(e, batch) : PP_OK;
+}
+// The synchronous tail: the frames' counts come back, are held against the host's bounds and become the host's offsets;
+// the points are handed out when asked for.  Formats: bad_count (who, frame, count, bound), small_out (who, capacity, total).
+inline int rewrite_sync_tail(pp_engine* e, const char* who, const char* bad_count, const char* small_out, const int* d_counts,
+                             int batch, int32_t* counts_out, float* points_out, int64_t points_capacity) {
+    HIPCHK(e, hipMemcpyAsync(counts_out, d_counts, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    std::vector<int> off((size_t)batch + 1, 0);
+    int max_n = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int bound = e->h_cur_off[(size_t)b + 1] - e->h_cur_off[(size_t)b];
+        if (counts_out[b] < 0 || counts_out[b] > bound) return fail(e, PP_ERR_HIP, bad_count, who, b, counts_out[b], bound);
+        off[(size_t)b + 1] = off[(size_t)b] + counts_out[b];
+        max_n = std::max(max_n, counts_out[b]);
+    }
+    set_resident(e, batch, off.data(), max_n, true);
+    if (points_out) {
+        const int total = off[(size_t)batch];
+        if (points_capacity < total) return fail(e, PP_ERR_ARG, small_out, who, (long long)points_capacity, total);
+        if (total) HIPCHK(e, hipMemcpy(points_out, e->d_points, (size_t)total * e->F * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return PP_OK;
+}

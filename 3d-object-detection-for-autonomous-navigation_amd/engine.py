@@ -7,6 +7,7 @@ RuntimeError carrying pp_last_error().
 import collections
 import ctypes
 import dataclasses
+import operator
 import weakref
 
 import numpy as np
@@ -50,6 +51,26 @@ def _f32(a):
 
 def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _to_struct(ctype, cfg):
+    """A stage's config dataclass as its ctypes mirror, by the struct's field types: an array field is filled element by
+    element, an integer field takes the value's index (a bool counts, a float does not), the rest as they are."""
+    pc, vals = ctype(), cfg.to_dict()
+    for name, typ in ctype._fields_:
+        if name not in vals:
+            continue                                   # (a reserved word of the struct)
+        if issubclass(typ, ctypes.Array):
+            getattr(pc, name)[:] = vals[name]
+        else:
+            setattr(pc, name, operator.index(vals[name]) if typ is ctypes.c_int32 else vals[name])
+    return pc
+
+
+def _from_struct(cls, pc):
+    """... and back: the dataclass `cls` from the struct the library filled (an array field as a tuple)."""
+    vals = {f.name: getattr(pc, f.name) for f in dataclasses.fields(cls)}
+    return cls(**{k: tuple(v) if isinstance(v, ctypes.Array) else v for k, v in vals.items()})
 
 
 class Staging:
@@ -525,19 +546,23 @@ class Engine:
         advances one track table per stream (frame b is stream b) behind its post-process, on the GPU -- `tracks()` then
         returns ids and velocities.  None: off (the default); the tables and the configuration are kept.  The config key
         model.second.tracking selects it at construction."""
-        if cfg is None or cfg is False:
-            self._check(self._lib.pp_set_tracking(self._h, None), "pp_set_tracking")
-            return
-        c = _trk.TrackConfig.from_any(cfg)
-        pc = _lib.PPTrackConfig()
-        for f, v in c.to_dict().items():
-            setattr(pc, f, int(v) if f in ("max_misses", "min_hits", "class_aware") else v)
-        self._check(self._lib.pp_set_tracking(self._h, ctypes.byref(pc)), "pp_set_tracking")
+        pc = None if cfg is None or cfg is False else ctypes.byref(_to_struct(_lib.PPTrackConfig, _trk.TrackConfig.from_any(cfg)))
+        self._check(self._lib.pp_set_tracking(self._h, pc), "pp_set_tracking")
+
+    def _stage_config(self, getter, ctype):
+        """(on, the ctypes struct) of a stage's pp_get_* call."""
+        on, pc = ctypes.c_int32(0), ctype()
+        self._check(getattr(self._lib, getter)(self._h, ctypes.byref(on), ctypes.byref(pc)), getter)
+        return bool(on.value), pc
+
+    def _stage_info(self, call, keys, n):
+        """A stage's int32 counts of its last run, `n` per key (waits for the run): {key: [n]}."""
+        out = {k: np.zeros(max(n, 1), np.int32) for k in keys}
+        self._check(getattr(self._lib, call)(self._h, *(_ptr(v) for v in out.values()), n), call)
+        return {k: v[:n] for k, v in out.items()}
 
     def _get_tracking(self):
-        on, pc = ctypes.c_int32(0), _lib.PPTrackConfig()
-        self._check(self._lib.pp_get_tracking(self._h, ctypes.byref(on), ctypes.byref(pc)), "pp_get_tracking")
-        return bool(on.value), pc
+        return self._stage_config("pp_get_tracking", _lib.PPTrackConfig)
 
     @property
     def tracking_on(self):
@@ -547,9 +572,7 @@ class Engine:
     def tracking(self):
         """The TrackConfig the passes track with, or None while tracking is off."""
         on, pc = self._get_tracking()
-        if not on:
-            return None
-        return _trk.TrackConfig(**{f.name: getattr(pc, f.name) for f in dataclasses.fields(_trk.TrackConfig)})
+        return _from_struct(_trk.TrackConfig, pc) if on else None
 
     def set_track_dt(self, dt):
         """Seconds by which the next tracked pass advances streams 0 .. len(dt) - 1 (pp_set_track_dt; queued on the
@@ -966,10 +989,7 @@ class Engine:
 
     def crop_info(self):
         """The kept counts of the last crop, int32 [B] (pp_frustum_crop_info; waits for it)."""
-        B = getattr(self, "_crop_batch", 0)
-        kept = np.zeros(max(B, 1), np.int32)
-        self._check(self._lib.pp_frustum_crop_info(self._h, _ptr(kept), B), "pp_frustum_crop_info")
-        return kept[:B]
+        return self._stage_info("pp_frustum_crop_info", ("kept",), getattr(self, "_crop_batch", 0))["kept"]
 
     # ---- multi-sweep accumulation (pp_set_sweeps, pp_sweeps_accumulate*; sweeps.py states the rule; DESIGN 7.1r) ----
     def set_sweeps(self, cfg):
@@ -981,25 +1001,19 @@ class Engine:
             self._check(self._lib.pp_set_sweeps(self._h, None), "pp_set_sweeps")
             return
         c = _swp.SweepConfig.from_any(cfg).resolved(self.d.num_point_features, self.max_points_per_frame)
-        pc = _lib.PPSweepConfig()
-        for f, v in c.to_dict().items():
-            setattr(pc, f, v)
+        pc = _to_struct(_lib.PPSweepConfig, c)
         on, old = self._get_sweeps()
         self._check(self._lib.pp_set_sweeps(self._h, ctypes.byref(pc)), "pp_set_sweeps")
         if (old.history, old.capacity) != (c.history, c.capacity):      # the ring was re-made: the stamps went with it
             self._sweep_last[:] = np.nan
 
     def _get_sweeps(self):
-        on, pc = ctypes.c_int32(0), _lib.PPSweepConfig()
-        self._check(self._lib.pp_get_sweeps(self._h, ctypes.byref(on), ctypes.byref(pc)), "pp_get_sweeps")
-        return bool(on.value), pc
+        return self._stage_config("pp_get_sweeps", _lib.PPSweepConfig)
 
     def sweeps(self):
         """The SweepConfig in force (capacity filled in), or None while the stage is off."""
         on, pc = self._get_sweeps()
-        if not on:
-            return None
-        return _swp.SweepConfig(**{f.name: getattr(pc, f.name) for f in dataclasses.fields(_swp.SweepConfig)})
+        return _from_struct(_swp.SweepConfig, pc) if on else None
 
     def _sweep_call(self, poses, stamps, who):
         """What accumulate_sweeps* refuse before anything is queued; returns (poses, stamps, the streams' new stamps)."""
@@ -1047,10 +1061,7 @@ class Engine:
     def sweeps_info(self):
         """Per frame of the last accumulate (waits for it), int32 [B] each: `count` output rows, `used` sweeps, rows
         `truncated` at max_points_per_frame, rows `push_truncated` at the capacity when the frame was stored."""
-        B = getattr(self, "_sweep_batch", 0)
-        out = {k: np.zeros(max(B, 1), np.int32) for k in ("count", "used", "truncated", "push_truncated")}
-        self._check(self._lib.pp_sweeps_info(self._h, *(_ptr(v) for v in out.values()), B), "pp_sweeps_info")
-        return {k: v[:B] for k, v in out.items()}
+        return self._stage_info("pp_sweeps_info", ("count", "used", "truncated", "push_truncated"), getattr(self, "_sweep_batch", 0))
 
     def sweeps_reset(self, stream=None):
         """Forgets the stored sweeps and the last stamp of `stream` (None: of all streams)."""
@@ -1067,27 +1078,14 @@ class Engine:
         points and -- `objects` -- the pass's detections or the streams' tracks into one int8 grid per frame on the GPU, in
         the layout of nav_msgs/OccupancyGrid (costmap.to_occupancy_grid makes the message's dict).  None: the stage off (the
         default); its buffers are kept.  The config key model.second.costmap selects it at construction."""
-        if cfg is None or cfg is False:
-            self._check(self._lib.pp_set_costmap(self._h, None), "pp_set_costmap")
-            return
-        c = _cm.CostmapConfig.from_any(cfg)
-        pc = _lib.PPCostmapConfig()
-        for f, v in c.to_dict().items():
-            if f == "predict_cost":
-                pc.predict_cost[:] = v
-            else:
-                setattr(pc, f, v)
-        self._check(self._lib.pp_set_costmap(self._h, ctypes.byref(pc)), "pp_set_costmap")
+        pc = None if cfg is None or cfg is False else ctypes.byref(_to_struct(_lib.PPCostmapConfig, _cm.CostmapConfig.from_any(cfg)))
+        self._check(self._lib.pp_set_costmap(self._h, pc), "pp_set_costmap")
 
     @property
     def costmap(self):
         """The CostmapConfig in force, or None while the stage is off."""
-        on, pc = ctypes.c_int32(0), _lib.PPCostmapConfig()
-        self._check(self._lib.pp_get_costmap_config(self._h, ctypes.byref(on), ctypes.byref(pc)), "pp_get_costmap_config")
-        if not on.value:
-            return None
-        return _cm.CostmapConfig(**{f.name: (tuple(pc.predict_cost) if f.name == "predict_cost" else getattr(pc, f.name))
-                                    for f in dataclasses.fields(_cm.CostmapConfig)})
+        on, pc = self._stage_config("pp_get_costmap_config", _lib.PPCostmapConfig)
+        return _from_struct(_cm.CostmapConfig, pc) if on else None
 
     def costmap_async(self):
         """Queues the stage on the resident frames behind whatever the engine's stream holds (pp_costmap_async) and returns
@@ -1113,10 +1111,7 @@ class Engine:
 
     def costmap_info(self):
         """Per frame of the last costmap run (waits for it), int32 [B] each: `points_in_grid`, `footprints`."""
-        B = getattr(self, "_costmap_batch", 0)
-        out = {k: np.zeros(max(B, 1), np.int32) for k in ("points_in_grid", "footprints")}
-        self._check(self._lib.pp_costmap_info(self._h, *(_ptr(v) for v in out.values()), B), "pp_costmap_info")
-        return {k: v[:B] for k, v in out.items()}
+        return self._stage_info("pp_costmap_info", ("points_in_grid", "footprints"), getattr(self, "_costmap_batch", 0))
 
     # ---- rolling occupancy map per stream (pp_set_occupancy, pp_occupancy_update_async, pp_get_occupancy; occupancy.py states the rule; DESIGN 7.1u) ----
     def set_occupancy(self, cfg):
@@ -1130,24 +1125,18 @@ class Engine:
             self._check(self._lib.pp_set_occupancy(self._h, None, None, 0), "pp_set_occupancy")
             return
         c = _occ.OccupancyConfig.from_any(cfg)
-        pc = _lib.PPOccupancyConfig()
-        for f, v in c.to_dict().items():
-            setattr(pc, f, v)
+        pc = _to_struct(_lib.PPOccupancyConfig, c)
         table = np.ascontiguousarray(_occ.cost_table(c), np.int8)
         self._check(self._lib.pp_set_occupancy(self._h, ctypes.byref(pc), _ptr(table), len(table)), "pp_set_occupancy")
 
     def _get_occupancy(self):
-        on, pc = ctypes.c_int32(0), _lib.PPOccupancyConfig()
-        self._check(self._lib.pp_get_occupancy_config(self._h, ctypes.byref(on), ctypes.byref(pc)), "pp_get_occupancy_config")
-        return bool(on.value), pc
+        return self._stage_config("pp_get_occupancy_config", _lib.PPOccupancyConfig)
 
     @property
     def occupancy(self):
         """The OccupancyConfig in force, or None while the stage is off."""
         on, pc = self._get_occupancy()
-        if not on:
-            return None
-        return _occ.OccupancyConfig(**{f.name: getattr(pc, f.name) for f in dataclasses.fields(_occ.OccupancyConfig)})
+        return _from_struct(_occ.OccupancyConfig, pc) if on else None
 
     def occupancy_update_async(self, poses):
         """Updates the maps of streams 0 .. B - 1 from the resident frames under poses [B, 3, 4] float64, the
@@ -1186,10 +1175,8 @@ class Engine:
     def occupancy_info(self):
         """Per frame of the last occupancy update (waits for it), int32 [B] each: rows `hits`, `ground`, `ignored`;
         `cells_hit`, `cells_free` (passed and not hit); `cleared`, the cells of the new window the old one did not hold."""
-        B = getattr(self, "_occ_batch", 0)
-        out = {k: np.zeros(max(B, 1), np.int32) for k in ("hits", "ground", "ignored", "cells_hit", "cells_free", "cleared")}
-        self._check(self._lib.pp_occupancy_info(self._h, *(_ptr(v) for v in out.values()), B), "pp_occupancy_info")
-        return {k: v[:B] for k, v in out.items()}
+        keys = ("hits", "ground", "ignored", "cells_hit", "cells_free", "cleared")
+        return self._stage_info("pp_occupancy_info", keys, getattr(self, "_occ_batch", 0))
 
     def occupancy_reset(self, stream=None):
         """Forgets the map of `stream` (None: of all streams): its next update starts from an unknown window."""
@@ -1272,10 +1259,7 @@ class Engine:
 
     def ingest_info(self):
         """Per frame of the last ingest: `finite` records and points `kept` (pp_ingest_info; waits for the ingest)."""
-        B = getattr(self, "_ing_batch", 0)
-        fin, kept = np.zeros((max(B, 1),), np.int32), np.zeros((max(B, 1),), np.int32)
-        self._check(self._lib.pp_ingest_info(self._h, _ptr(fin), _ptr(kept), B), "pp_ingest_info")
-        return {"finite": fin[:B], "kept": kept[:B]}
+        return self._stage_info("pp_ingest_info", ("finite", "kept"), getattr(self, "_ing_batch", 0))
 
     def staging_pointcloud2(self, msgs, features=None, mount=None):
         """Packs messages into a page-locked MessageStaging for ingest_pointcloud2_async (the counterpart of staging()).
@@ -1392,9 +1376,7 @@ class Engine:
         """Per camera of the last rig ingest: `finite` records (valid pixels) and points `kept`, int32 [B, cameras]
         (pp_ingest_rig_info; waits for the ingest)."""
         B, C = getattr(self, "_rig_shape", (0, 0))
-        fin, kept = np.zeros((max(B * C, 1),), np.int32), np.zeros((max(B * C, 1),), np.int32)
-        self._check(self._lib.pp_ingest_rig_info(self._h, _ptr(fin), _ptr(kept), B * C), "pp_ingest_rig_info")
-        return {"finite": fin[:B * C].reshape(B, C), "kept": kept[:B * C].reshape(B, C)}
+        return {k: v.reshape(B, C) for k, v in self._stage_info("pp_ingest_rig_info", ("finite", "kept"), B * C).items()}
 
     def staging_rig_depth(self, frames, rig):
         """Packs the depth images of B rig frames into a page-locked RigDepthStaging for ingest_rig_depth_async."""

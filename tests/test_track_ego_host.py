@@ -270,6 +270,6 @@ def test_header_exports_and_engine_name_the_new_calls(pp):
     csrc = os.path.join(os.path.dirname(pp._lib.__file__), "csrc")
     # one pose checker for the sweeps and the tracker
     assert "pose_check_orthonormal" in open(os.path.join(csrc, "pp_engine.h")).read()
-    for src in ("api_sweeps.hip", "api_track.hip"):
+    for src in ("api_sweeps.hip", "api_track.hip", "api_occupancy.hip"):    # ... reached through check_poses, stream by stream
         text = open(os.path.join(csrc, src)).read()
-        assert "pose_check_orthonormal(" in text and "is not orthonormal" not in text, src
+        assert "check_poses(" in text and "is not orthonormal" not in text and "is not finite\", who, b, i / 4" not in text, src
