@@ -245,7 +245,7 @@ static int run_pfn(pp_engine* e, int batch, bool padded, float* feat_out, bool w
         p.am_cells = e->d_cells; p.am_A = e->A; p.am_threshold = e->cfg.anchor_area_threshold; p.am_mask = e->d_mask;
         e->mask_in_pfn = true;
     }
-    ProfScope ps(e, "k_pfn_canvas:pfn+scatter");
+    ProfScope ps(e, nullptr);   // under the name of the kernel launch_pfn chooses (k_pfn_canvas or k_pfn_canvas2)
     int st = launch_pfn(p, padded, e->stream);
     if (st) return fail(e, st, "PFN: unsupported C=%d / F=%d", e->C, e->F);
     HIPCHK(e, hipGetLastError());
@@ -1371,6 +1371,8 @@ int pp_anchor_mask(pp_handle e, const int32_t* coors, int64_t num_pillars, int32
     int st = check_batch(e, batch); if (st) return st;
     if ((st = upload_coors(e, coors, num_pillars, batch, "pp_anchor_mask"))) return st;
     prof_reset(e);
+    // the cell map was built from the caller's coordinates; an occupancy bitmap is what the last pass's PFN launch left
+    e->occbits_live = false;
     if ((st = run_anchor_mask(e, batch))) return st;
     HIPCHK(e, hipMemcpyAsync(mask, e->d_mask, (size_t)batch * e->A, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));

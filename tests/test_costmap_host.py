@@ -329,3 +329,58 @@ def test_to_occupancy_grid_fields(C):
     assert C.to_occupancy_grid(grid, c)["header"] == {"stamp": None, "frame_id": ""}
     with pytest.raises(ValueError, match="grid must be"):
         C.to_occupancy_grid(grid[:3], c)
+
+
+# ---- wide grids: the compose kernel's waves inside one row (tests/test_gpu_costmap.py runs them on the GPU) ----
+@pytest.mark.parametrize("name", ["w300", "w257"])
+def test_wide_grids_put_compose_waves_inside_one_row(pp, C, name):
+    """The wave arithmetic from CM_BLOCK and the pitch rule read out of the sources, so the case cannot drift off the
+    branch `wiy0 == wiy1, wix0 > 0` of k_costmap_compose; and, on tracks of the host tracker, what the GPU test relies on:
+    every cell decided by more than the margin, every cost present, object cells in the columns past the first wave of a
+    row and in the first quad."""
+    import grid_shape_cases as gc
+    csrc = os.path.join(os.path.dirname(pp._lib.__file__), "csrc")
+    src = open(os.path.join(csrc, "costmap.hip")).read()
+    block = int(re.search(r"constexpr int CM_BLOCK = (\d+);", src).group(1))
+    assert block % 64 == 0 and "const int q = blockIdx.x * CM_BLOCK + tid;" in src and "wq0 = q - lane" in src
+    assert "wix0 = wiy0 == wiy1 ? (wq0 - wiy0 * qpr) * 4 : 0;" in src and "const int qpr = p.pitch >> 2;" in src
+    assert int(re.search(r"constexpr int CM_TILE = (\d+);", src).group(1)) == 64
+    assert "const int pitch = (c.width + 3) & ~3;" in open(os.path.join(csrc, "api_costmap.hip")).read()
+    g = gc.WIDE_COSTMAPS[name]
+    W, H = g["width"], g["height"]
+    waves = gc.compose_waves(W, H)
+    one_row = [w for w in waves if w[0] == w[1]]
+    if name == "w300":
+        assert (W + 3) // 4 == 75 and len(waves) == 11 and len(one_row) == 3
+        assert [w[2] for w in one_row] == [0, 36, 160] and one_row[0][3] == 255 and one_row[2][3] == 299
+    else:
+        assert (W + 3) // 4 == 65 and ((W + 3) & ~3) - W == 3 and len(waves) == 6
+        assert [(w[0], w[2], w[3]) for w in one_row] == [(0, 0, 255), (4, 240, 259)] and waves[1][:2] == (0, 1)
+    past0 = [w for w in one_row if w[2] > 0]
+    assert past0
+    # the tracks, on the host tracker: two updates 0.05 m apart
+    per = [gc.wide_track_rows(name, s) for s in range(gc.WIDE_STREAMS)]
+    assert all(len(rr) == 24 for rr in per) and abs(math.hypot(*gc.WIDE_MOVE) - 0.05) < 1e-12
+    t = pp.tracking.Tracker(gc.wide_track_config(), gc.WIDE_STREAMS)
+    t.step(*gc.wide_det_rows(per), [0.1] * gc.WIDE_STREAMS)
+    tr, nt, _ = t.step(*gc.wide_det_rows([gc.wide_moved(rr) for rr in per]), [0.1] * gc.WIDE_STREAMS)
+    assert nt.tolist() == [24] * gc.WIDE_STREAMS and np.abs(tr["state"][:, :24, 3]).min() > 0
+    frames = gc.wide_frames(name)
+    assert all(len(f) >= gc.WIDE_ROWS for f in frames)
+    for steps in (0, 2):
+        c = C.CostmapConfig.from_any(gc.wide_costmap_config(name, steps))
+        culled = 0
+        for b in range(gc.WIDE_STREAMS):
+            fp = C.footprints_np(c, tracks=tr[b], n_tracks=int(nt[b]))
+            assert len(fp) == 24 * (1 + steps)                               # 72: more than one LDS tile of 64
+            margin = float(C.decision_margins(c, fp).min())
+            assert margin > 1e-7, (steps, b, margin)                         # the GPU test leaves no cell out
+            grid, _ = C.costmap_np(frames[b], c, tracks=tr[b], n_tracks=int(nt[b]))
+            vals = set(np.unique(grid).tolist())
+            assert {100, 0, -1} <= vals and ({70, 60} <= vals) == (steps == 2)
+            obj = grid >= 60
+            assert obj[:, 256:].any() and obj[:, :4].any() and obj[:, 4:252].any()
+            # a wave past column 0 with object cells inside its columns and others of its row outside them: the column cull
+            # has footprints to keep and footprints to drop
+            culled += sum(1 for r0, _, c0, c1 in past0 if obj[r0, c0:c1 + 1].any() and obj[r0, :c0].any())
+        assert culled >= 1, steps

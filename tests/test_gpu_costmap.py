@@ -217,6 +217,34 @@ def test_64_live_tracks_seeded(pp, eng):
     eng.set_costmap(None)
 
 
+@pytest.mark.parametrize("name", ["w300", "w257"])
+def test_wide_grids_waves_inside_one_row(pp, eng, name):
+    """More than 64 quads a row (300 and 257 cells wide): waves of k_costmap_compose that lie inside one row and start past
+    column 0 cull a tile's records by their columns as well (tests/test_costmap_host.py restates which waves).  24 tracks
+    with velocities, 24 and 72 footprints (more than one LDS tile), 1 500 seeded rows a frame; no cell is left out."""
+    import grid_shape_cases as gc
+    eng.set_tracking(gc.wide_track_config())
+    eng.set_tracking(None)
+    eng.track_reset()
+    per = [gc.wide_track_rows(name, s) for s in range(S)]
+    frames = gc.wide_frames(name)
+    eng.upload(frames)
+    eng.track_update(*gc.wide_det_rows(per), [0.1] * S)
+    tr, nt, _ = eng.track_update(*gc.wide_det_rows([gc.wide_moved(rr) for rr in per]), [0.1] * S)
+    assert nt.tolist() == [24] * S and np.abs(tr["state"][:, :24, 3]).min() > 0
+    W = gc.WIDE_COSTMAPS[name]["width"]
+    for steps in (0, 2):
+        cfg = gc.wide_costmap_config(name, steps, (GRID["z_min"], GRID["z_max"]))
+        eng.set_costmap(cfg)
+        g = _compare(pp, eng, frames, cfg, 0, f"{name}, horizon {steps}", tracks=tr, nt=nt)
+        assert g.shape == (S, gc.WIDE_COSTMAPS[name]["height"], W)
+        assert eng.costmap_info()["footprints"].tolist() == [24 * (1 + steps)] * S
+        vals = set(np.unique(g).tolist())
+        assert 100 in vals and ({70, 60} <= vals) == (steps == 2)
+        assert (g[:, :, 256:] >= 60).any() and (g[:, :, :4] >= 60).any()
+    eng.set_costmap(None)
+
+
 # ---- 3. detections behind a pass, the stage's ordering, what it must leave alone ----
 def _weights(pp, d, seed=7):
     w = dict(pp.weights.init_weights(d, seed=seed))

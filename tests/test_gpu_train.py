@@ -61,23 +61,27 @@ def _variant(pp, name, B):
         s["num_point_features"] = 4
         cfg["eval_input_reader"]["num_point_features"] = 4
         s["voxel_feature_extractor"]["with_distance"] = True
+    elif name == "z3":                   # three z cells of the voxel height: k_tr_scatter sums a column's pillars over nz
+        r = s["voxel_generator"]["point_cloud_range"]
+        s["voxel_generator"]["point_cloud_range"] = r[:2] + [-3.0] + r[3:5] + [-3.0 + 3 * s["voxel_generator"]["voxel_size"][2]]
     return copy.deepcopy(cfg)
 
 
-@pytest.mark.parametrize("name", ["tiny", "deep", "wide", "T50-F4-dist", "two-classes", "three-classes-no-dir"])
+@pytest.mark.parametrize("name", ["tiny", "deep", "wide", "T50-F4-dist", "two-classes", "three-classes-no-dir", "z3"])
 def test_gradients_match_autograd_small_grids(pp, hip_lib, name):
     """Every trainable tensor's gradient against torch autograd over the restated network (float32), on a 20x16
     grid where float32 round-off stays small: max |diff| <= 1e-4 of the tensor's largest gradient (measured ~5e-6).
     Variants: the reference's layer counts [3,5,5]; its channel widths 64/128/256 + 128-channel upsampling and
-    PFN; 50 points per pillar with 4 point features and the distance feature."""
+    PFN; 50 points per pillar with 4 point features and the distance feature; three z cells (z from -3 to 9)."""
     B = 2
     cfg = _variant(pp, name, B)
     d = pp.config.Derived(cfg)
     rng = np.random.default_rng(4)
     F = d.num_point_features
     frames = []
+    assert d.nz == (3 if name == "z3" else 2)
     for n in (900, 400):
-        xyz = rng.uniform([0, -0.64, -3], [1.6, 0.64, 3], (n, 3))
+        xyz = rng.uniform([0, -0.64, d.pc_range[2]], [1.6, 0.64, d.pc_range[5]], (n, 3))
         frames.append(np.concatenate([xyz, rng.uniform(0, 1, (n, F - 3))], axis=1).astype(np.float32))
     d, labels, reg = _problem(pp, cfg, frames, 11)
     if d.num_class > 1:                                     # every class among the positives
@@ -350,16 +354,16 @@ def test_fused_forward_kernels_on_small_grids(hip_lib):
     """The fused training-forward launches (k_sep_u<..., TR = 1>: depthwise + product + statistics of a separable layer;
     TR = 2: the transposed convolutions' and the heads' forward products) only run from 32 768 output rows on by default,
     so the autograd tests above (640-row maps) time the separate kernels.  One child process with PP_TRAIN_FUSED_MIN=0 --
-    the switch is read once per process -- runs the same six autograd comparisons through the fused launches: ragged
+    the switch is read once per process -- runs the same seven autograd comparisons through the fused launches: ragged
     tiles (640 / 160 / 40 rows), every tile width (32 / 64 / 128 output channels), stride 1 and 2, the NaN padding header
-    on 20 x 16 maps, head bias."""
+    on 20 x 16 maps, head bias, three z cells."""
     env = dict(os.environ)
     env["PP_TRAIN_FUSED_MIN"] = "0"
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider",
                         os.path.join(ROOT, "tests", "test_gpu_train.py"), "-k", "small_grids and not fused_forward"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert "6 passed" in r.stdout, r.stdout[-1000:]
+    assert "7 passed" in r.stdout, r.stdout[-1000:]
 
 
 def test_decisions_tap_surface(pp, hip_lib):
