@@ -35,7 +35,7 @@ EXPORTS = [
     "pp_upload_points", "pp_upload_points_async", "pp_host_alloc", "pp_host_free", "pp_upload_points_device",
     "pp_current_batch", "pp_set_calib", "pp_detect_async", "pp_sync",
     "pp_get_detections", "pp_set_gemm_precision", "pp_get_gemm_precision", "pp_set_cache_budget", "pp_detect", "pp_fetch_intermediates", "pp_set_profiling", "pp_get_kernel_times",
-    "pp_timer_start", "pp_timer_stop", "pp_device_info", "pp_device_copy_bench", "pp_device_mem_free", "pp_bench_layer", "pp_layer_count", "pp_layer_tag",
+    "pp_timer_start", "pp_timer_stop", "pp_device_info", "pp_device_copy_bench", "pp_device_mem_free", "pp_bench_layer", "pp_layer_count", "pp_layer_tag", "pp_plan_layer_name",
     "pp_rotate_iou_eval", "pp_d3_box_overlap", "pp_head_loss", "pp_adamw_step_device",
     "pp_train_layout", "pp_train_layout_entry", "pp_train_step", "pp_train_step_async", "pp_train_step_wait",
     "pp_train_graph_stats", "pp_stream", "pp_train_fetch_decisions",
@@ -111,6 +111,11 @@ class PPLossConfig(ctypes.Structure):
         ("encode_rad_error_by_sin", ctypes.c_int32),
         ("use_direction_classifier", ctypes.c_int32),
     ]
+
+
+class PPLayerPlanDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("kind", "cin", "cout", "n_total", "stride", "k", "in_h", "in_w", "out_h", "out_w",
+                                              "head_mode", "has_wt16", "has_head_wt16", "sparse_input")]
 
 
 class PPTargetConfig(ctypes.Structure):
@@ -463,6 +468,7 @@ def lib():
     L.pp_layer_count.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_layer_tag.argtypes = [vp, i32]
     L.pp_layer_tag.restype = ctypes.c_char_p
+    L.pp_plan_layer_name.argtypes = [ctypes.POINTER(PPLayerPlanDesc), i32, i32, ctypes.c_char_p, i32]
     L.pp_rotate_iou_eval.argtypes = [ctypes.c_int, f32p, i64, f32p, i64, i32, f32p]
     L.pp_d3_box_overlap.argtypes = [ctypes.c_int, vp, i64, vp, i64, i32, vp]
     L.pp_head_loss.argtypes = [vp, vp, f32p, i32, ctypes.POINTER(PPLossConfig), f32p, f32p]

@@ -1183,13 +1183,13 @@ constexpr int sep_u_wpc(int nt, int s, bool prec) {
 // may this stride-1 launch share window columns between the lanes of a DPP row?  (SEP_SHARED_WINDOW: the output width
 // a multiple of 8 -- a DPP row's 8 pixels then never straddle an image row, a frame or the end of the data -- and the
 // input map the size of the output map)
-static bool sep_shared_window(const GemmArgs& a) {
-    return a.stride == 1 && a.px_w % 8 == 0 && a.in_w == a.px_w && a.in_h == a.px_h;
+static bool sep_shared_window(const LayerDesc& L) {
+    return L.stride == 1 && L.out_w % 8 == 0 && L.in_w == L.out_w && L.in_h == L.out_h;
 }
 
 // persistent launch: sep_u_wpc workgroups per CU, a multiple of 8 so that every XCD gets the same number
 template <int NT, int S>
-static void launch_u(const GemmArgs& a, int n_total, bool prec, bool occ, hipStream_t s) {
+static void launch_u(const GemmArgs& a, int n_total, bool prec, bool occ, bool sh, hipStream_t s) {
     constexpr int WPS = sep_u_wpc(NT, S, false), WPB = sep_u_wpc(NT, S, true);
     const int ntiles = (a.M + 127) / 128;
     const int ny = n_total / NT;
@@ -1205,7 +1205,7 @@ static void launch_u(const GemmArgs& a, int n_total, bool prec, bool occ, hipStr
         // window columns"): k_sep_u<64,1,3> 38.8 -> 37.5 us (block1.0 59 -> 55.5), k_sep_u<128,1,2> 26.3 -> 26.9 us -- the
         // 128-channel kernel does not get faster with three loads fewer, so it keeps the full window
         if constexpr (S == 1 && NT == 64) {
-            if (sep_shared_window(a)) {
+            if (sh) {
                 PP_LAUNCH("k_sep_u", (k_sep_u<NT, S, WPB, 1, 0, 0, 1>), grid, dim3(256), 0, s, a, ntiles);
                 return;
             }
@@ -1499,11 +1499,11 @@ __global__ __launch_bounds__(512, 1) void k_sep_p(GemmArgs a, int ntiles) {
 #undef P_TILE_OFFSETS
 }
 
-static void launch_p(const GemmArgs& a, hipStream_t s) {
+static void launch_p(const GemmArgs& a, bool sh, hipStream_t s) {
     const int ntiles = (a.M + 127) / 128;
     int gx = ntiles < g_num_cus ? ntiles : g_num_cus;
     gx = (gx + 7) & ~7;
-    if (sep_shared_window(a)) PP_LAUNCH("k_sep_p", (k_sep_p<256, 1>), dim3((unsigned)gx), dim3(512), 0, s, a, ntiles);
+    if (sh) PP_LAUNCH("k_sep_p", (k_sep_p<256, 1>), dim3((unsigned)gx), dim3(512), 0, s, a, ntiles);
     else PP_LAUNCH("k_sep_p", k_sep_p<256>, dim3((unsigned)gx), dim3(512), 0, s, a, ntiles);
 }
 
@@ -1689,19 +1689,19 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_sep_k4(GemmArgs a)
 // Measured crossover against k_sep_u (tools/k4_sweep.sh, cfg-A, B = 2..16): 1.5 workgroups per CU for
 // cin = 64, 2.5 for cin = 128, 3 for cin = 256 -- the longer the K chain, the later k_sep_u catches up.
 // PP_SEP_K4=0 turns it off, PP_SEP_K4=n sets the limit to n workgroups per CU for every layer.
-static bool sep_k4_runs(const void* wt16, int cin, int n_total, long long M) {
+static bool sep_k4_runs(const void* wt16, int cin, int n_total, long long M, int cus) {
     static int force = -2;
     if (force == -2) { const char* e = getenv("PP_SEP_K4"); force = e ? atoi(e) : -1; }
     if (force == 0 || wt16 == nullptr || !split_precision() || cin % 64 != 0 || cin > 256 || n_total % 64 != 0)
         return false;
     const int half_cus = (force > 0) ? 2 * force : (cin <= 64 ? 3 : (cin <= 128 ? 5 : 6));
-    return 2 * ((M + 31) / 32 * (n_total / 64)) <= (long long)half_cus * g_num_cus;
+    return 2 * ((M + 31) / 32 * (n_total / 64)) <= (long long)half_cus * cus;
 }
 // eight-way split: cin = 256 and at most one workgroup per CU (the latency case proper: a frame or two).  Measured
 // at B=1 (tools/latency_b1.py): block3.1-.5 8.1 -> 7.2 us; the 128-channel layers gain nothing (block2.x 5.8 -> 5.6,
 // block3.0 6.0 -> 7.0: one iteration per wave leaves nothing to pipeline) and keep four waves
-static bool sep_k8_runs(int cin, int n_total, long long M) {
-    return cin % 256 == 0 && (M + 31) / 32 * (n_total / 64) <= (long long)g_num_cus;
+static bool sep_k8_runs(int cin, int n_total, long long M, int cus) {
+    return cin % 256 == 0 && (M + 31) / 32 * (n_total / 64) <= (long long)cus;
 }
 template <int S>
 static void launch_k4(const GemmArgs& a, int n_total, bool k8, hipStream_t s) {
@@ -2450,13 +2450,13 @@ __global__ __launch_bounds__(256, 2) void k_deconv_k4(GemmArgs a) {
 // runs while the layer has at most 1.5 workgroups per CU (measured crossover against k_deconv_u on cfg-A,
 // tools/k4_sweep.sh: ahead at B = 1, 2 (160 / 320 workgroups), behind from B = 4); PP_DECONV_K4=0: never,
 // =n: up to n per CU
-static bool deconv_k4_runs(const LayerDesc& L, long long M) {
+static bool deconv_k4_runs(const LayerDesc& L, long long M, int cus) {
     static int force = -2;
     if (force == -2) { const char* e = getenv("PP_DECONV_K4"); force = e ? atoi(e) : -1; }
     if (force == 0 || L.cin % 64 != 0 || L.cin > 256) return false;
     const int nt = col_tile(L.cout);
     const int half_cus = force > 0 ? 2 * force : 3;
-    return 2 * ((M + 31) / 32 * (L.n_total / nt)) <= (long long)half_cus * g_num_cus;
+    return 2 * ((M + 31) / 32 * (L.n_total / nt)) <= (long long)half_cus * cus;
 }
 template <int NT>
 static void launch_deconv_k4(const GemmArgs& a, int n_total, hipStream_t s) {
@@ -2519,7 +2519,7 @@ static bool sep_uniform() {
 // the layer would otherwise put fewer than ~2.5 waves on a SIMD (small maps: a wave per 32 pixels x NT
 // channels is the scheduling grain; the depthwise is recomputed per channel tile, which the idle
 // vector pipe absorbs)
-static int sep_u_nt(const LayerDesc& L, long long rows) {
+static int sep_u_nt(const LayerDesc& L, long long rows, int cus) {
     if (L.cout % 64 != 0) return 32;
     if (L.cout % 128 != 0) return 64;
     const long long waves128 = (rows + 31) / 32 * (L.cout / 128);
@@ -2529,7 +2529,7 @@ static int sep_u_nt(const LayerDesc& L, long long rows) {
     // split-precision path: the depthwise (VALU) is the larger half of a chunk, so recomputing it per
     // channel tile costs more than the thinner wave supply (measured: block3 at B=64 36 vs 40 us)
     if (split_operands(L)) return 128;
-    return (waves128 * 2 < 5ll * g_num_cus * 4) ? 64 : 128;
+    return (waves128 * 2 < 5ll * cus * 4) ? 64 : 128;
 }
 
 static bool use_ws(const LayerDesc& L) {
@@ -2584,32 +2584,35 @@ struct LayerPlan {
     int prec;    // PREC, OCC (k_sep_u)
     int occ;
     int k8;      // the eight-way split (k_sep_k4)
+    int sh;      // SH, shared window columns (k_sep_p, k_sep_u<64,1,.,1,0>)
     int pxb;     // pixel tile (k_gemm_ws)
     int mode;    // MODE (k_gemm_ws / _layer): 0 separable, 1 deconv or heads
 };
 
 // rows: the output rows of this launch (what the size heuristics weigh); m_end: the end of its pixel range (frame0 > 0:
 // a sub-range of a larger batch, see launch_layer)
-static LayerPlan plan_layer(const LayerDesc& L, long long rows, long long m_end) {
+static LayerPlan plan_layer(const LayerDesc& L, long long rows, long long m_end, int cus) {
     LayerPlan p = {};
     p.nt = (L.kind == LAYER_HEAD) ? 32 : col_tile(L.cout);
     p.mode = (L.kind == LAYER_SEP) ? 0 : 1;
     p.s = (L.kind == LAYER_SEP) ? L.stride : 1;
     if (sep_uniform_runs(L, m_end)) {
-        if (sep_k4_runs(L.d_wt16, L.cin, L.n_total, rows)) {   // small map
+        if (sep_k4_runs(L.d_wt16, L.cin, L.n_total, rows, cus)) {   // small map
             p.kernel = LayerKernel::SEP_K4;
-            p.k8 = sep_k8_runs(L.cin, L.n_total, rows);
+            p.k8 = sep_k8_runs(L.cin, L.n_total, rows, cus);
         } else if (sep_p_runs(L.d_wt16, L.stride, L.cin, L.cout, L.n_total, rows, L.d_occ)) {   // depthwise once for 256 channels
             p.kernel = LayerKernel::SEP_P;
+            p.sh = sep_shared_window(L);
         } else {
             p.kernel = LayerKernel::SEP_U;
-            p.nt = sep_u_nt(L, rows);
+            p.nt = sep_u_nt(L, rows, cus);
             p.prec = split_operands(L);
             p.occ = p.prec && L.d_occ != nullptr;
             p.wpc = sep_u_wpc(p.nt, p.s, p.prec);
+            p.sh = p.prec && !p.occ && p.nt == 64 && p.s == 1 && sep_shared_window(L);   // (see launch_u)
         }
     } else if (deconv_uniform(L)) {
-        if (deconv_k4_runs(L, rows)) {   // small map: split-K
+        if (deconv_k4_runs(L, rows, cus)) {   // small map: split-K
             p.kernel = LayerKernel::DECONV_K4;
         } else if (deconv_r_runs(L)) {   // input resident in registers
             p.kernel = LayerKernel::DECONV_R;
@@ -2626,17 +2629,24 @@ static LayerPlan plan_layer(const LayerDesc& L, long long rows, long long m_end)
     return p;
 }
 
-// name of the template instantiation that runs layer L at this batch size (profiler tags)
-std::string layer_kernel_name(const LayerDesc& L, int batch) {
-    const LayerPlan p = plan_layer(L, layer_rows(L, batch), layer_rows(L, batch));
+// name of a plan's template instantiation.  full: with the SH argument of k_sep_p / k_sep_u, which the profiler tags
+// leave out
+static std::string plan_name(const LayerPlan& p, bool full) {
     char buf[64];
     switch (p.kernel) {
     case LayerKernel::SEP_K4:
         if (p.k8) snprintf(buf, sizeof(buf), "k_sep_k4<64,%d,8>", p.s);
         else snprintf(buf, sizeof(buf), "k_sep_k4<64,%d>", p.s);
         break;
-    case LayerKernel::SEP_P: snprintf(buf, sizeof(buf), "k_sep_p"); break;
-    case LayerKernel::SEP_U: snprintf(buf, sizeof(buf), "k_sep_u<%d,%d,%d,%d,%d>", p.nt, p.s, p.wpc, p.prec, p.occ); break;
+    case LayerKernel::SEP_P:
+        if (!full) snprintf(buf, sizeof(buf), "k_sep_p");
+        else if (p.sh) snprintf(buf, sizeof(buf), "k_sep_p<256,1>");
+        else snprintf(buf, sizeof(buf), "k_sep_p<256>");
+        break;
+    case LayerKernel::SEP_U:
+        if (full && p.sh) snprintf(buf, sizeof(buf), "k_sep_u<%d,%d,%d,%d,%d,0,1>", p.nt, p.s, p.wpc, p.prec, p.occ);
+        else snprintf(buf, sizeof(buf), "k_sep_u<%d,%d,%d,%d,%d>", p.nt, p.s, p.wpc, p.prec, p.occ);
+        break;
     case LayerKernel::DECONV_K4: snprintf(buf, sizeof(buf), "k_deconv_k4<%d>", p.nt); break;
     case LayerKernel::DECONV_R: snprintf(buf, sizeof(buf), "k_deconv_r<%d>", p.cin); break;
     case LayerKernel::DECONV_U: snprintf(buf, sizeof(buf), "k_deconv_u<%d,3>", p.nt); break;
@@ -2644,6 +2654,18 @@ std::string layer_kernel_name(const LayerDesc& L, int batch) {
     case LayerKernel::GEMM_LAYER: snprintf(buf, sizeof(buf), "k_gemm_layer<%d,%d>", p.nt, p.mode); break;
     }
     return std::string(buf);
+}
+
+// name of the template instantiation that runs layer L at this batch size (profiler tags)
+std::string layer_kernel_name(const LayerDesc& L, int batch) {
+    return plan_name(plan_layer(L, layer_rows(L, batch), layer_rows(L, batch), g_num_cus), false);
+}
+
+// the planner alone (pp_plan_layer_name): the full instantiation name launch_layer would run L under at this batch on a
+// part with `cus` compute units.  Only what plan_layer reads of L has to be filled in; a non-NULL d_wt16 / d_head_wt16 /
+// d_occ stands for "has float16 weight pieces / float16 head weights / a sparse input".  No device is touched.
+std::string layer_plan_name(const LayerDesc& L, int batch, int cus) {
+    return plan_name(plan_layer(L, layer_rows(L, batch), layer_rows(L, batch), cus), true);
 }
 
 // does layer L (the last fused-head deconv) leave the compact class-logit plane?  (the uniform-wave and
@@ -2658,8 +2680,8 @@ bool launch_layer_subrange_ok(const LayerDesc& L, int frame0, int batch, int tot
     if (L.kind != LAYER_SEP) return false;
     const long long hw = (long long)L.out_h * L.out_w;
     if ((frame0 * hw) % PX_TILE != 0) return false;
-    return plan_layer(L, batch * hw, batch * hw).kernel == LayerKernel::SEP_U &&
-           plan_layer(L, total_batch * hw, total_batch * hw).kernel == LayerKernel::SEP_U;
+    return plan_layer(L, batch * hw, batch * hw, g_num_cus).kernel == LayerKernel::SEP_U &&
+           plan_layer(L, total_batch * hw, total_batch * hw, g_num_cus).kernel == LayerKernel::SEP_U;
 }
 
 // f(std::integral_constant<int, V>{}) for the V of Vs that equals v (the last one when none does): a plan's value as a
@@ -2713,17 +2735,17 @@ int launch_layer(const LayerDesc& L, int batch, float* d_head, hipStream_t s, in
         a.M = batch * L.in_h * L.in_w;
         if (L.n_total != 32) return PP_ERR_UNSUPPORTED;
     }
-    const LayerPlan p = plan_layer(L, layer_rows(L, batch), a.M);
+    const LayerPlan p = plan_layer(L, layer_rows(L, batch), a.M, g_num_cus);
     const int n = L.n_total;
     switch (p.kernel) {
     case LayerKernel::SEP_K4:
         with_value<1, 2>(p.s, [&](auto S) { launch_k4<S>(a, n, p.k8, s); });
         break;
     case LayerKernel::SEP_P:
-        launch_p(a, s);
+        launch_p(a, p.sh, s);
         break;
     case LayerKernel::SEP_U:
-        with_value<1, 2>(p.s, [&](auto S) { with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_u<NT, S>(a, n, p.prec, p.occ, s); }); });
+        with_value<1, 2>(p.s, [&](auto S) { with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_u<NT, S>(a, n, p.prec, p.occ, p.sh, s); }); });
         break;
     case LayerKernel::DECONV_K4:
         with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_deconv_k4<NT>(a, n, s); });

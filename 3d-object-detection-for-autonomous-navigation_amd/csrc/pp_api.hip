@@ -1539,6 +1539,26 @@ const char* pp_layer_tag(pp_handle e, int32_t layer) {
     return e->layer_tags[layer].c_str();
 }
 
+int pp_plan_layer_name(const pp_layer_plan_desc* layer, int32_t batch, int32_t compute_units, char* name, int32_t name_capacity) {
+    if (!layer || !name || name_capacity < 1 || batch < 1 || compute_units < 1) return PP_ERR_ARG;
+    if (layer->kind != LAYER_SEP && layer->kind != LAYER_DECONV && layer->kind != LAYER_HEAD) return PP_ERR_ARG;
+    static float pieces;                 // what the planner asks of the weight pointers is only whether they are NULL
+    static int cells;
+    LayerDesc L;
+    memset(&L, 0, sizeof(L));
+    L.kind = layer->kind; L.cin = layer->cin; L.cout = layer->cout; L.n_total = layer->n_total;
+    L.stride = layer->stride; L.k = layer->k;
+    L.in_h = layer->in_h; L.in_w = layer->in_w; L.out_h = layer->out_h; L.out_w = layer->out_w;
+    L.head_mode = layer->head_mode;
+    L.d_wt16 = layer->has_wt16 ? &pieces : nullptr;
+    L.d_head_wt16 = layer->has_head_wt16 ? &pieces : nullptr;
+    L.d_occ = layer->sparse_input ? &cells : nullptr;
+    const std::string n = layer_plan_name(L, batch, compute_units);
+    if ((int)n.size() + 1 > name_capacity) return PP_ERR_ARG;
+    memcpy(name, n.c_str(), n.size() + 1);
+    return PP_OK;
+}
+
 int pp_bench_layer(pp_handle e, int32_t layer, int32_t batch, int32_t reps, int32_t ablate, float* avg_ms) {
     if (!e) return PP_ERR_ARG;
     if (!avg_ms || reps < 1 || layer < 0 || layer >= (int)e->layers.size()) return fail(e, PP_ERR_ARG, "pp_bench_layer: bad argument");

@@ -213,6 +213,8 @@ bool deconv_can_fuse_heads(const LayerDesc& L);
 bool layer_writes_cls_plane(const LayerDesc& L);   // does this layer's kernel leave the compact class-logit plane?
 bool sparse_input_supported(const LayerDesc& L, int batch);   // may L's input be a canvas with unwritten empty cells?
 std::string layer_kernel_name(const LayerDesc& L, int batch);  // template instantiation that runs L at this batch
+// the same for a part with `cus` compute units, with the SH argument the tags leave out; reads no device state
+std::string layer_plan_name(const LayerDesc& L, int batch, int cus);
 // training-mode forward of one separable layer (backbone.hip: k_sep_u<..., TR = 1>; called by train.hip)
 struct SepTrainArgs {
     const float* in;             // input map [batch][in_h][in_w][cin] with a PP_ZPAD_FLOATS header in front: NaN-filled when

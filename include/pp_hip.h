@@ -53,7 +53,8 @@ extern "C" {
  * pp_get_costmap_config, pp_costmap_async, pp_get_costmaps, pp_costmap_info (declared behind pp_get_tracks_fixed: the
  * stage reads what a pass and its tracking step leave on the device).  Then PP_OCC_MAX_CELLS, pp_occupancy_config,
  * pp_set_occupancy, pp_get_occupancy_config, pp_occupancy_update_async, pp_get_occupancy, pp_occupancy_info,
- * pp_occupancy_reset (declared behind pp_costmap_info). */
+ * pp_occupancy_reset (declared behind pp_costmap_info).  Then pp_layer_plan_desc, pp_plan_layer_name (declared behind
+ * pp_layer_tag). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -370,6 +371,27 @@ int pp_bench_layer(pp_handle h, int32_t layer, int32_t batch, int32_t reps, int3
 /* Number of RPN layer launches per forward pass and the tag ("<kernel>:<layer>") of one. */
 int pp_layer_count(pp_handle h, int32_t* count);
 const char* pp_layer_tag(pp_handle h, int32_t layer);
+/* The planner alone, for tests and tuning: which template instantiation the backbone would launch for one layer at
+ * `batch` frames on a part with `compute_units` compute units (256 on the MI355X), written to `name` as a
+ * NUL-terminated string.  It is the name of pp_layer_tag before the colon, except that k_sep_u and k_sep_p carry their
+ * shared-window argument ("k_sep_u<64,1,3,1,0,0,1>", "k_sep_p<256,1>" / "k_sep_p<256>"), which the tags leave out.
+ * Needs no handle and no device.  The process-start switches (PP_SEP_K4, PP_DECONV_K4, PP_SEP_KERNEL, PP_SEP_NT,
+ * PP_GEMM_PREC) apply as they do to a pass: read once per process.  PP_ERR_ARG: NULL, batch or compute_units < 1, an
+ * unknown kind, a name buffer that is too small (64 bytes hold every name). */
+typedef struct pp_layer_plan_desc {
+    int32_t kind;             /* 0 separable layer, 1 transposed convolution, 2 the heads as a layer of their own */
+    int32_t cin, cout;        /* channels in / out (cout of one tap of a transposed convolution) */
+    int32_t n_total;          /* cout (separable), k * k * cout (transposed convolution), 32 (heads) */
+    int32_t stride;           /* separable layers: 1 or 2 */
+    int32_t k;                /* transposed convolutions: kernel == stride */
+    int32_t in_h, in_w;       /* input map */
+    int32_t out_h, out_w;     /* output map (separable: strided; transposed convolution: in * k; heads: in) */
+    int32_t head_mode;        /* transposed convolutions: 0 heads not fused, 1 the first fused branch, 2 a later one */
+    int32_t has_wt16;         /* the layer's weights fit the float16 pieces (and the precision is PP_PREC_SPLIT_F16) */
+    int32_t has_head_wt16;    /* so does its slice of the head weights */
+    int32_t sparse_input;     /* the first layer of a sparse canvas */
+} pp_layer_plan_desc;
+int pp_plan_layer_name(const pp_layer_plan_desc* layer, int32_t batch, int32_t compute_units, char* name, int32_t name_capacity);
 
 /* ---- AP-evaluator overlaps ------------------ */
 
