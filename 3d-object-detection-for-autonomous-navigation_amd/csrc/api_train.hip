@@ -106,7 +106,9 @@ int train_buffers(pp_engine* e) {
     A1(dalloc(e, &cx.gemm_part, (size_t)cx.gemm_part_floats));
     // PP_TRAIN_ARENA_FLOATS=n: the step uses at most n floats of it (tests: the arena-exhausted branches of train.hip).
     // Where partial rows live and how many K slices a product gets change; what is computed does not.
-    if (const long cap = train_switches().arena_floats) cx.gemm_part_floats = std::min(cx.gemm_part_floats, cap);
+    cx.cus = e->plan_env.cus;
+    cx.sw = e->plan_env.sw.train;
+    if (const long cap = cx.sw.arena_floats) cx.gemm_part_floats = std::min(cx.gemm_part_floats, cap);
     if (st == PP_OK) st = ensure_loss_buffers(e);
     if (st == PP_OK) t->buffers = true;
     return st;
@@ -166,7 +168,7 @@ int train_step_launch(pp_engine* e, const float* params_dev, float* grads_dev, f
         return train_step(cx, t->shape, t->plan, params_dev, grads_dev, state_dev, batch, lp, phase);
     };
     bool launched = false;
-    if (e->prof <= 0 && t->graph_state == 0 && graphs_enabled()) {
+    if (e->prof <= 0 && t->graph_state == 0 && graphs_enabled(e)) {
         const int bucket = graph_bucket(e, e->cur_max_n);
         pp_engine::TrainState::Graph& tg = t->graph[e->in_buf & 1];
         const TrainKey key = train_key(e, batch, bucket, params_dev, grads_dev, state_dev, lc);

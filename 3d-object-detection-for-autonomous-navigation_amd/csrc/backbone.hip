@@ -29,6 +29,7 @@
 #include <string.h>
 
 #include "pp_common.h"
+#include "pp_plan.h"   // which instantiation runs a layer: plan_layer, and sep_u_wpc / col_tile for the template arguments
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 // Split-precision operands: two float16 pieces per float32 value (11 significand bits each; pp_api.hip splits the
@@ -58,21 +59,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
 
 #define PX_TILE 128
 
-int g_num_cus = 256;   // set by pp_create from the device properties (persistent launches)
-
-// GEMM arithmetic: split-precision float16 MFMA (default) or the float32 MFMA.  PP_GEMM_PREC=f32 selects the latter.
-static bool split_precision() {
-    static int dflt = -1;
-    if (dflt < 0) {
-        const char* e = getenv("PP_GEMM_PREC");
-        dflt = (e && e[0] == 'f') ? 0 : 1;
-    }
-    return dflt == 1;
-}
-// does layer L run on the split-precision MFMA?  (its weights fit the float16 pieces and the precision is not forced)
-static bool split_operands(const LayerDesc& L) { return L.d_wt16 != nullptr && split_precision(); }
-// channel tile of the GEMM kernels: the widest of 128 / 64 / 32 that divides cout
-static int col_tile(int cout) { return cout % 128 == 0 ? 128 : (cout % 64 == 0 ? 64 : 32); }
 #define KC 32
 #define LDS_STRIDE 36
 
@@ -1172,32 +1158,32 @@ __global__ __launch_bounds__(256, WPS) void k_sep_u(GemmArgs a, int ntiles) {
 #undef U_TILE_OFFSETS
 }
 
-// workgroups per CU of k_sep_u<NT, S, ., PREC> (one wave per SIMD each): the register budgets of the float32 and
-// the split-precision instantiations differ (split-precision k_sep_u<128, 1>: 256 / 168)
-constexpr int SEP128_WPB = 2, SEP64_WPB = 3;
-constexpr int sep_u_wpc(int nt, int s, bool prec) {
-    return s == 1 ? (prec ? (nt == 128 ? SEP128_WPB : (nt == 64 ? SEP64_WPB : 3)) : (nt == 128 ? 3 : 4))
-                  : (prec ? (nt == 128 ? 2 : 3) : (nt == 128 ? 2 : (nt == 64 ? 3 : 4)));
+// f(std::integral_constant<int, V>{}) for the V of Vs that equals v (the last one when none does): a plan's value as a
+// template argument
+template <int V, int... Vs, class F>
+static void with_value(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>{});
+    else if (v == V) f(std::integral_constant<int, V>{});
+    else with_value<Vs...>(v, f);
 }
 
-// may this stride-1 launch share window columns between the lanes of a DPP row?  (SEP_SHARED_WINDOW: the output width
-// a multiple of 8 -- a DPP row's 8 pixels then never straddle an image row, a frame or the end of the data -- and the
-// input map the size of the output map)
-static bool sep_shared_window(const LayerDesc& L) {
-    return L.stride == 1 && L.out_w % 8 == 0 && L.in_w == L.out_w && L.in_h == L.out_h;
+// grid.x of a persistent launch over `tiles` tiles: the chip holds cus * wpc workgroups, shared by the ny channel
+// columns (min_slots at least); one workgroup per tile at most; a multiple of 8 so that every XCD gets the same number
+static int persistent_gx(int tiles, int cus, int wpc, int ny, int min_slots = 0) {
+    int slots = (cus * wpc) / ny;
+    if (slots < min_slots) slots = min_slots;
+    const int gx = tiles < slots ? tiles : slots;
+    return (gx + 7) & ~7;
 }
 
-// persistent launch: sep_u_wpc workgroups per CU, a multiple of 8 so that every XCD gets the same number
+// persistent launch: sep_u_wpc workgroups per CU
 template <int NT, int S>
-static void launch_u(const GemmArgs& a, int n_total, bool prec, bool occ, bool sh, hipStream_t s) {
+static void launch_u(const GemmArgs& a, int n_total, bool prec, bool occ, bool sh, int cus, hipStream_t s) {
     constexpr int WPS = sep_u_wpc(NT, S, false), WPB = sep_u_wpc(NT, S, true);
     const int ntiles = (a.M + 127) / 128;
     const int ny = n_total / NT;
-    int slots = (g_num_cus * (prec ? WPB : WPS)) / ny;
-    const int mine = ntiles - a.tile_lo;               // (a.tile_lo > 0: a launch over a sub-range of the batch's frames)
-    int gx = mine < slots ? mine : slots;
-    gx = (gx + 7) & ~7;
-    dim3 grid((unsigned)gx, ny);
+    // (a.tile_lo > 0: a launch over a sub-range of the batch's frames)
+    dim3 grid((unsigned)persistent_gx(ntiles - a.tile_lo, cus, prec ? WPB : WPS, ny), ny);
     if (occ) {
         PP_LAUNCH("k_sep_u", (k_sep_u<NT, S, WPB, 1, 1>), grid, dim3(256), 0, s, a, ntiles);
     } else if (prec) {
@@ -1221,7 +1207,7 @@ static void launch_u(const GemmArgs& a, int n_total, bool prec, bool occ, bool s
 // float16 pieces -> pre-BatchNorm map + statistics partials; the depthwise output is stored for the backward pass.
 // Returns the number of statistics rows written ([rows][2][cout]), or 0 when the shape is not one the kernel takes
 // (the caller then runs the separate depthwise and product kernels).
-int launch_sep_train(const SepTrainArgs& t, hipStream_t s) {
+int launch_sep_train(const SepTrainArgs& t, int cus, hipStream_t s) {
     const long long M = (long long)t.batch * t.out_h * t.out_w;
     const long long in_bytes = (long long)t.batch * t.in_h * t.in_w * t.cin * 4;
     if (t.cin % KC != 0 || t.cout % 32 != 0 || (t.stride != 1 && t.stride != 2) || t.out_w % 2 != 0 || M >= (1 << 24) ||
@@ -1234,30 +1220,23 @@ int launch_sep_train(const SepTrainArgs& t, hipStream_t s) {
     a.stride = t.stride; a.ld_out = t.cout; a.co_off = 0; a.cout = t.cout;
     a.tr_coef = t.coef; a.tr_D = t.D; a.tr_stat = t.stat;
     const int ntiles = (a.M + 127) / 128;
-    const int nt = (t.cout % 128 == 0) ? 128 : (t.cout % 64 == 0 ? 64 : 32);
+    const int nt = col_tile(t.cout);
     const int ny = t.cout / nt;
-    const int wpb = (nt == 128) ? 2 : 3;
-    int slots = (g_num_cus * wpb) / ny;
-    int gx = ntiles < slots ? ntiles : slots;
-    gx = (gx + 7) & ~7;
+    const int gx = persistent_gx(ntiles, cus, sep_u_wpc(nt, t.stride, true), ny);   // (2, 3, 3 workgroups per CU at either stride)
     const dim3 grid((unsigned)gx, ny);
     const char* tg = t.tag ? t.tag : "k_sep_u_tr";
-    if (t.stride == 1) {
-        if (nt == 128) PP_LAUNCH(tg, (k_sep_u<128, 1, 2, 1, 0, 1>), grid, dim3(256), 0, s, a, ntiles);
-        else if (nt == 64) PP_LAUNCH(tg, (k_sep_u<64, 1, 3, 1, 0, 1>), grid, dim3(256), 0, s, a, ntiles);
-        else PP_LAUNCH(tg, (k_sep_u<32, 1, 3, 1, 0, 1>), grid, dim3(256), 0, s, a, ntiles);
-    } else {
-        if (nt == 128) PP_LAUNCH(tg, (k_sep_u<128, 2, 2, 1, 0, 1>), grid, dim3(256), 0, s, a, ntiles);
-        else if (nt == 64) PP_LAUNCH(tg, (k_sep_u<64, 2, 3, 1, 0, 1>), grid, dim3(256), 0, s, a, ntiles);
-        else PP_LAUNCH(tg, (k_sep_u<32, 2, 3, 1, 0, 1>), grid, dim3(256), 0, s, a, ntiles);
-    }
+    with_value<1, 2>(t.stride, [&](auto S) {
+        with_value<128, 64, 32>(nt, [&](auto NT) {
+            PP_LAUNCH(tg, (k_sep_u<NT, S, sep_u_wpc(NT, S, true), 1, 0, 1>), grid, dim3(256), 0, s, a, ntiles);
+        });
+    });
     return gx;          // one statistics row per workgroup of a channel column
 }
 
 // Training-mode forward of a plain product rows x K -> rows x N (a transposed convolution as a GEMM over its input
 // pixels, the heads): k_sep_u<..., TR = 2> -- no depthwise, the rest as launch_sep_train.  `in` needs no header.
 // Returns the statistics rows written (t.stat != NULL) or 1, 0 when the shape is not one the kernel takes.
-int launch_rows_train(const RowsTrainArgs& t, hipStream_t s) {
+int launch_rows_train(const RowsTrainArgs& t, int cus, hipStream_t s) {
     const long long M = t.rows;
     if (t.K % KC != 0 || t.N % 32 != 0 || M % 2 != 0 || M >= (1 << 24) || M * t.K * 4 >= (1ll << 31) - 4096 || t.ld_out % 4 != 0)
         return 0;
@@ -1268,18 +1247,15 @@ int launch_rows_train(const RowsTrainArgs& t, hipStream_t s) {
     a.stride = 1; a.ld_out = t.ld_out; a.co_off = 0; a.cout = t.N;
     a.tr_stat = t.stat;
     const int ntiles = (a.M + 127) / 128;
-    const int nt = (t.N % 128 == 0) ? 128 : (t.N % 64 == 0 ? 64 : 32);
+    const int nt = col_tile(t.N);
     const int ny = t.N / nt;
     const int wpb = 3;          // (no depthwise: 159 / 105 / 76 VGPRs -- three workgroups per CU for every tile width)
-    int slots = (g_num_cus * wpb) / ny;
-    if (slots < 8) slots = 8;
-    int gx = ntiles < slots ? ntiles : slots;
-    gx = (gx + 7) & ~7;
+    const int gx = persistent_gx(ntiles, cus, wpb, ny, 8);
     const dim3 grid((unsigned)gx, ny);
     const char* tg = t.tag ? t.tag : "k_sep_u_tr";
-    if (nt == 128) PP_LAUNCH(tg, (k_sep_u<128, 1, 3, 1, 0, 2>), grid, dim3(256), 0, s, a, ntiles);
-    else if (nt == 64) PP_LAUNCH(tg, (k_sep_u<64, 1, 3, 1, 0, 2>), grid, dim3(256), 0, s, a, ntiles);
-    else PP_LAUNCH(tg, (k_sep_u<32, 1, 3, 1, 0, 2>), grid, dim3(256), 0, s, a, ntiles);
+    with_value<128, 64, 32>(nt, [&](auto NT) {
+        PP_LAUNCH(tg, (k_sep_u<NT, 1, 3, 1, 0, 2>), grid, dim3(256), 0, s, a, ntiles);
+    });
     return gx;
 }
 
@@ -1499,20 +1475,11 @@ __global__ __launch_bounds__(512, 1) void k_sep_p(GemmArgs a, int ntiles) {
 #undef P_TILE_OFFSETS
 }
 
-static void launch_p(const GemmArgs& a, bool sh, hipStream_t s) {
+static void launch_p(const GemmArgs& a, bool sh, int cus, hipStream_t s) {
     const int ntiles = (a.M + 127) / 128;
-    int gx = ntiles < g_num_cus ? ntiles : g_num_cus;
-    gx = (gx + 7) & ~7;
+    const int gx = persistent_gx(ntiles, cus, 1, 1);   // one workgroup per CU (the LDS)
     if (sh) PP_LAUNCH("k_sep_p", (k_sep_p<256, 1>), dim3((unsigned)gx), dim3(512), 0, s, a, ntiles);
     else PP_LAUNCH("k_sep_p", k_sep_p<256>, dim3((unsigned)gx), dim3(512), 0, s, a, ntiles);
-}
-
-// does k_sep_p run this separable layer?  (256 output channels, stride 1, dense input, large enough for the persistent
-// kernels)
-static bool sep_p_runs(const void* wt16, int stride, int cin, int cout, int n_total, long long M, const int* occ) {
-    // (the 128-channel instantiation, where k_sep_u already computes the depthwise once, measured 32 us against 28.5)
-    return wt16 != nullptr && split_precision() && stride == 1 && occ == nullptr && cout == 256 &&
-           n_total == 256 && cin % 64 == 0 && cin <= 256 && M < (1 << 24);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1685,24 +1652,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_sep_k4(GemmArgs a)
     }
 }
 
-// the split-K kernel runs a layer while the map is too small to fill the chip with 32-pixel wave tiles.
-// Measured crossover against k_sep_u (tools/k4_sweep.sh, cfg-A, B = 2..16): 1.5 workgroups per CU for
-// cin = 64, 2.5 for cin = 128, 3 for cin = 256 -- the longer the K chain, the later k_sep_u catches up.
-// PP_SEP_K4=0 turns it off, PP_SEP_K4=n sets the limit to n workgroups per CU for every layer.
-static bool sep_k4_runs(const void* wt16, int cin, int n_total, long long M, int cus) {
-    static int force = -2;
-    if (force == -2) { const char* e = getenv("PP_SEP_K4"); force = e ? atoi(e) : -1; }
-    if (force == 0 || wt16 == nullptr || !split_precision() || cin % 64 != 0 || cin > 256 || n_total % 64 != 0)
-        return false;
-    const int half_cus = (force > 0) ? 2 * force : (cin <= 64 ? 3 : (cin <= 128 ? 5 : 6));
-    return 2 * ((M + 31) / 32 * (n_total / 64)) <= (long long)half_cus * cus;
-}
-// eight-way split: cin = 256 and at most one workgroup per CU (the latency case proper: a frame or two).  Measured
-// at B=1 (tools/latency_b1.py): block3.1-.5 8.1 -> 7.2 us; the 128-channel layers gain nothing (block2.x 5.8 -> 5.6,
-// block3.0 6.0 -> 7.0: one iteration per wave leaves nothing to pipeline) and keep four waves
-static bool sep_k8_runs(int cin, int n_total, long long M, int cus) {
-    return cin % 256 == 0 && (M + 31) / 32 * (n_total / 64) <= (long long)cus;
-}
+// (when the split-K kernel runs, and its eight-way split: sep_k4_runs / sep_k8_runs, pp_plan.h)
 template <int S>
 static void launch_k4(const GemmArgs& a, int n_total, bool k8, hipStream_t s) {
     dim3 grid((unsigned)((a.M + 31) / 32), n_total / 64);
@@ -2221,17 +2171,13 @@ __global__ __launch_bounds__(256, 2) void k_deconv_r(GemmArgs a, int nunits, int
 #undef R_LOAD_NEXT
 }
 
-// runs where k_deconv_u would and the shape fits (cout == 128, cin 64 / 128 / 256)
-static bool deconv_r_runs(const LayerDesc& L) {
-    // kernel == stride 1 has one tap per tile: nothing is re-read or re-split, and k_deconv_u's two-chunk register
-    // prefetch hides the tile changes better (deconv1 at B=64: 35.4 us against 37.1)
-    return L.k > 1 && L.cout == 128 && (L.cin == 64 || L.cin == 128 || L.cin == 256);
-}
+// (runs where k_deconv_u would and the shape fits: deconv_r_runs, pp_plan.h)
+// Two workgroups per CU; the (tile, tap) units are dealt evenly among as many workgroups as that takes.
 template <int CIN>
-static void launch_deconv_r(const GemmArgs& a, hipStream_t s) {
+static void launch_deconv_r(const GemmArgs& a, int cus, hipStream_t s) {
     const int ntiles = (a.M + 127) / 128;
     const long long U = (long long)ntiles * a.k * a.k;
-    const int slots = 2 * g_num_cus;
+    const int slots = 2 * cus;
     const int upw = (int)((U + slots - 1) / slots);                 // units per workgroup
     const int G = (int)((U + upw - 1) / upw);
     PP_LAUNCH("k_deconv_r", (k_deconv_r<CIN>), dim3((unsigned)G), dim3(256), 0, s, a, (int)U, upw);
@@ -2447,17 +2393,7 @@ __global__ __launch_bounds__(256, 2) void k_deconv_k4(GemmArgs a) {
     }
 }
 
-// runs while the layer has at most 1.5 workgroups per CU (measured crossover against k_deconv_u on cfg-A,
-// tools/k4_sweep.sh: ahead at B = 1, 2 (160 / 320 workgroups), behind from B = 4); PP_DECONV_K4=0: never,
-// =n: up to n per CU
-static bool deconv_k4_runs(const LayerDesc& L, long long M, int cus) {
-    static int force = -2;
-    if (force == -2) { const char* e = getenv("PP_DECONV_K4"); force = e ? atoi(e) : -1; }
-    if (force == 0 || L.cin % 64 != 0 || L.cin > 256) return false;
-    const int nt = col_tile(L.cout);
-    const int half_cus = force > 0 ? 2 * force : 3;
-    return 2 * ((M + 31) / 32 * (L.n_total / nt)) <= (long long)half_cus * cus;
-}
+// (runs while the layer has at most 1.5 workgroups per CU: deconv_k4_runs, pp_plan.h)
 template <int NT>
 static void launch_deconv_k4(const GemmArgs& a, int n_total, hipStream_t s) {
     dim3 grid((unsigned)((a.M + 31) / 32), n_total / NT);
@@ -2465,15 +2401,11 @@ static void launch_deconv_k4(const GemmArgs& a, int n_total, hipStream_t s) {
 }
 
 template <int NT>
-static void launch_deconv_u(const GemmArgs& a, int n_total, hipStream_t s) {
+static void launch_deconv_u(const GemmArgs& a, int n_total, int cus, hipStream_t s) {
     constexpr int WPS = 3;
     const int ntiles = (a.M + 127) / 128;
     const int ny = n_total / NT;
-    int slots = (g_num_cus * WPS) / ny;
-    if (slots < 8) slots = 8;
-    int gx = ntiles < slots ? ntiles : slots;
-    gx = (gx + 7) & ~7;
-    dim3 grid((unsigned)gx, ny);
+    dim3 grid((unsigned)persistent_gx(ntiles, cus, WPS, ny, 8), ny);
     PP_LAUNCH("k_deconv_u", (k_deconv_u<NT, WPS>), grid, dim3(256), 0, s, a, ntiles);
 }
 
@@ -2484,15 +2416,7 @@ static void launch_t(const GemmArgs& a, int n_total, hipStream_t s) {
     PP_LAUNCH("k_gemm_layer", (k_gemm_layer<NT, MODE>), grid, dim3(256), 0, s, a);
 }
 
-// 128-pixel tiles (8-wave workgroups: every SIMD hosts one consumer and one producer wave) are the
-// default.  64-pixel tiles (4-wave workgroups) are used only when a launch would otherwise not even
-// cover the chip's CUs once (small batches): measured at B=64 they are slower -- a 4-wave
-// workgroup's two consumer waves land on two of the four SIMDs, so the matrix pipes are unevenly fed.
-static bool ws_small_tile(long long M, int n_total, int NT) {
-    const long long tiles128 = ((M + 127) / 128) * (n_total / NT);
-    return tiles128 < 256;
-}
-
+// (pxb: 128-pixel tiles, or 64-pixel ones for a launch that would not cover the chip once: ws_small_tile, pp_plan.h)
 template <int NT, int MODE, int S>
 static void launch_ws(const GemmArgs& a, int n_total, int pxb, hipStream_t s) {
     if (pxb == 64) {
@@ -2504,63 +2428,12 @@ static void launch_ws(const GemmArgs& a, int n_total, int pxb, hipStream_t s) {
     }
 }
 
-// separable layers: uniform-wave kernel (k_sep_u) or the producer/consumer kernel (k_gemm_ws).
-// k_sep_u is the default; PP_SEP_KERNEL=ws selects the other.
-static bool sep_uniform() {
-    static int dflt = -1;
-    if (dflt < 0) {
-        const char* e = getenv("PP_SEP_KERNEL");
-        dflt = (e && e[0] == 'w') ? 0 : 1;
-    }
-    return dflt == 1;
-}
-
-// channel-tile width of the uniform-wave kernel: the widest that divides cout, narrowed to 64 when
-// the layer would otherwise put fewer than ~2.5 waves on a SIMD (small maps: a wave per 32 pixels x NT
-// channels is the scheduling grain; the depthwise is recomputed per channel tile, which the idle
-// vector pipe absorbs)
-static int sep_u_nt(const LayerDesc& L, long long rows, int cus) {
-    if (L.cout % 64 != 0) return 32;
-    if (L.cout % 128 != 0) return 64;
-    const long long waves128 = (rows + 31) / 32 * (L.cout / 128);
-    static int force = -1;
-    if (force < 0) { const char* e = getenv("PP_SEP_NT"); force = e ? atoi(e) : 0; }
-    if (force == 64 || force == 128) return force;
-    // split-precision path: the depthwise (VALU) is the larger half of a chunk, so recomputing it per
-    // channel tile costs more than the thinner wave supply (measured: block3 at B=64 36 vs 40 us)
-    if (split_operands(L)) return 128;
-    return (waves128 * 2 < 5ll * cus * 4) ? 64 : 128;
-}
-
-static bool use_ws(const LayerDesc& L) {
-    // MODE 1 producers own 4 consecutive pixels, MODE 0 producers 2 of one row: the frame's pixel
-    // count (hence every batch's) must be divisible accordingly, else the generic kernel runs
-    if (L.kind != LAYER_SEP) return (L.in_h * L.in_w) % 4 == 0;
-    return (L.stride == 1 || L.stride == 2) && (L.out_w % 2 == 0);
-}
-
-// the uniform-wave separable kernels (k_sep_u and the split-K / 256-channel ones chosen among them) run a separable
-// layer whose pixel range ends at m_end (k_sep_u's float-reciprocal index math)
-static bool sep_uniform_runs(const LayerDesc& L, long long m_end) {
-    return L.kind == LAYER_SEP && use_ws(L) && sep_uniform() && m_end < (1 << 24);
-}
-
-// one workgroup column covers the whole channel range of a deconv's tap (NT == cout): the fused head GEMM fits
-static bool one_column_tile(const LayerDesc& L) {
-    return L.cout == 32 || L.cout == 64 || L.cout == 128;
-}
-
-// the split-precision uniform-wave deconv kernel runs when its operands exist (cin % 32 == 0: an even
-// number of 16-channel chunks) and, with fused heads, when one column tile covers the tap
-static bool deconv_uniform(const LayerDesc& L) {
-    if (L.kind != LAYER_DECONV || !split_operands(L) || L.cin % 32 != 0) return false;
-    if (L.head_mode != 0 && (L.d_head_wt16 == nullptr || !one_column_tile(L))) return false;
-    return true;
-}
+// ---------------------------------------------------------------------------------------
+// What the planner (pp_plan.h) says about a layer, for the host units, and the dispatch of a plan.
 
 // can layer L (a separable layer) read a sparse canvas at this batch size?  (the kernels with the cell-map lookup)
-bool sparse_input_supported(const LayerDesc& L, int batch) {
-    return sep_uniform_runs(L, (long long)batch * L.out_h * L.out_w) && split_operands(L);
+bool sparse_input_supported(const LayerDesc& L, int batch, const PlanEnv& env) {
+    return sep_uniform_runs(L, (long long)batch * L.out_h * L.out_w, env.sw) && split_operands(L, env.sw);
 }
 
 // a deconv can carry the fused head GEMM when one workgroup column covers the tap's whole channel
@@ -2569,131 +2442,34 @@ bool deconv_can_fuse_heads(const LayerDesc& L) {
     return L.kind == LAYER_DECONV && one_column_tile(L) && use_ws(L);
 }
 
-static long long layer_rows(const LayerDesc& L, int batch) {
-    return (L.kind == LAYER_SEP) ? (long long)batch * L.out_h * L.out_w : (long long)batch * L.in_h * L.in_w;
-}
-
-// the kernel that runs one launch of a layer, with its template arguments
-enum class LayerKernel { SEP_K4, SEP_P, SEP_U, DECONV_K4, DECONV_R, DECONV_U, GEMM_WS, GEMM_LAYER };
-struct LayerPlan {
-    LayerKernel kernel;
-    int nt;      // channel tile NT (k_sep_u, k_deconv_k4 / _u, k_gemm_ws / _layer)
-    int cin;     // CIN (k_deconv_r)
-    int s;       // stride S (k_sep_k4, k_sep_u, k_gemm_ws)
-    int wpc;     // workgroups per CU (k_sep_u)
-    int prec;    // PREC, OCC (k_sep_u)
-    int occ;
-    int k8;      // the eight-way split (k_sep_k4)
-    int sh;      // SH, shared window columns (k_sep_p, k_sep_u<64,1,.,1,0>)
-    int pxb;     // pixel tile (k_gemm_ws)
-    int mode;    // MODE (k_gemm_ws / _layer): 0 separable, 1 deconv or heads
-};
-
-// rows: the output rows of this launch (what the size heuristics weigh); m_end: the end of its pixel range (frame0 > 0:
-// a sub-range of a larger batch, see launch_layer)
-static LayerPlan plan_layer(const LayerDesc& L, long long rows, long long m_end, int cus) {
-    LayerPlan p = {};
-    p.nt = (L.kind == LAYER_HEAD) ? 32 : col_tile(L.cout);
-    p.mode = (L.kind == LAYER_SEP) ? 0 : 1;
-    p.s = (L.kind == LAYER_SEP) ? L.stride : 1;
-    if (sep_uniform_runs(L, m_end)) {
-        if (sep_k4_runs(L.d_wt16, L.cin, L.n_total, rows, cus)) {   // small map
-            p.kernel = LayerKernel::SEP_K4;
-            p.k8 = sep_k8_runs(L.cin, L.n_total, rows, cus);
-        } else if (sep_p_runs(L.d_wt16, L.stride, L.cin, L.cout, L.n_total, rows, L.d_occ)) {   // depthwise once for 256 channels
-            p.kernel = LayerKernel::SEP_P;
-            p.sh = sep_shared_window(L);
-        } else {
-            p.kernel = LayerKernel::SEP_U;
-            p.nt = sep_u_nt(L, rows, cus);
-            p.prec = split_operands(L);
-            p.occ = p.prec && L.d_occ != nullptr;
-            p.wpc = sep_u_wpc(p.nt, p.s, p.prec);
-            p.sh = p.prec && !p.occ && p.nt == 64 && p.s == 1 && sep_shared_window(L);   // (see launch_u)
-        }
-    } else if (deconv_uniform(L)) {
-        if (deconv_k4_runs(L, rows, cus)) {   // small map: split-K
-            p.kernel = LayerKernel::DECONV_K4;
-        } else if (deconv_r_runs(L)) {   // input resident in registers
-            p.kernel = LayerKernel::DECONV_R;
-            p.cin = L.cin;
-        } else {
-            p.kernel = LayerKernel::DECONV_U;
-        }
-    } else if (use_ws(L)) {
-        p.kernel = LayerKernel::GEMM_WS;
-        p.pxb = ws_small_tile(rows, L.n_total, p.nt) ? 64 : 128;
-    } else {
-        p.kernel = LayerKernel::GEMM_LAYER;
-    }
-    return p;
-}
-
-// name of a plan's template instantiation.  full: with the SH argument of k_sep_p / k_sep_u, which the profiler tags
-// leave out
-static std::string plan_name(const LayerPlan& p, bool full) {
-    char buf[64];
-    switch (p.kernel) {
-    case LayerKernel::SEP_K4:
-        if (p.k8) snprintf(buf, sizeof(buf), "k_sep_k4<64,%d,8>", p.s);
-        else snprintf(buf, sizeof(buf), "k_sep_k4<64,%d>", p.s);
-        break;
-    case LayerKernel::SEP_P:
-        if (!full) snprintf(buf, sizeof(buf), "k_sep_p");
-        else if (p.sh) snprintf(buf, sizeof(buf), "k_sep_p<256,1>");
-        else snprintf(buf, sizeof(buf), "k_sep_p<256>");
-        break;
-    case LayerKernel::SEP_U:
-        if (full && p.sh) snprintf(buf, sizeof(buf), "k_sep_u<%d,%d,%d,%d,%d,0,1>", p.nt, p.s, p.wpc, p.prec, p.occ);
-        else snprintf(buf, sizeof(buf), "k_sep_u<%d,%d,%d,%d,%d>", p.nt, p.s, p.wpc, p.prec, p.occ);
-        break;
-    case LayerKernel::DECONV_K4: snprintf(buf, sizeof(buf), "k_deconv_k4<%d>", p.nt); break;
-    case LayerKernel::DECONV_R: snprintf(buf, sizeof(buf), "k_deconv_r<%d>", p.cin); break;
-    case LayerKernel::DECONV_U: snprintf(buf, sizeof(buf), "k_deconv_u<%d,3>", p.nt); break;
-    case LayerKernel::GEMM_WS: snprintf(buf, sizeof(buf), "k_gemm_ws<%d,%d,%d,%d>", p.nt, p.mode, p.s, p.pxb); break;
-    case LayerKernel::GEMM_LAYER: snprintf(buf, sizeof(buf), "k_gemm_layer<%d,%d>", p.nt, p.mode); break;
-    }
-    return std::string(buf);
-}
-
 // name of the template instantiation that runs layer L at this batch size (profiler tags)
-std::string layer_kernel_name(const LayerDesc& L, int batch) {
-    return plan_name(plan_layer(L, layer_rows(L, batch), layer_rows(L, batch), g_num_cus), false);
+std::string layer_kernel_name(const LayerDesc& L, int batch, const PlanEnv& env) {
+    return plan_name(plan_layer(L, layer_rows(L, batch), layer_rows(L, batch), env), false);
 }
 
-// the planner alone (pp_plan_layer_name): the full instantiation name launch_layer would run L under at this batch on a
-// part with `cus` compute units.  Only what plan_layer reads of L has to be filled in; a non-NULL d_wt16 / d_head_wt16 /
-// d_occ stands for "has float16 weight pieces / float16 head weights / a sparse input".  No device is touched.
-std::string layer_plan_name(const LayerDesc& L, int batch, int cus) {
-    return plan_name(plan_layer(L, layer_rows(L, batch), layer_rows(L, batch), cus), true);
+// the planner alone (pp_plan_layer_name): the full instantiation name launch_layer would run L under at this batch in
+// `env`.  Only what plan_layer reads of L has to be filled in.  No device is touched.
+std::string layer_plan_name(const LayerDesc& L, int batch, const PlanEnv& env) {
+    return plan_name(plan_layer(L, layer_rows(L, batch), layer_rows(L, batch), env), true);
 }
 
 // does layer L (the last fused-head deconv) leave the compact class-logit plane?  (the uniform-wave and
 // split-K deconv kernels do; the fallback generations do not and the post-process then scans the head rows)
-bool layer_writes_cls_plane(const LayerDesc& L) {
-    return L.kind == LAYER_DECONV && L.head_mode == 2 && L.d_cls_plane != nullptr && deconv_uniform(L);
+bool layer_writes_cls_plane(const LayerDesc& L, const PlanEnv& env) {
+    return L.kind == LAYER_DECONV && L.head_mode == 2 && L.d_cls_plane != nullptr && deconv_uniform(L, env.sw);
 }
 
 // frame0 > 0 (separable layers on k_sep_u only, launch_layer_subrange_ok): the launch covers the frames [frame0, frame0 +
 // batch) of a larger batch -- same buffers, same pixel numbering, a sub-range of the tiles
-bool launch_layer_subrange_ok(const LayerDesc& L, int frame0, int batch, int total_batch) {
+bool launch_layer_subrange_ok(const LayerDesc& L, int frame0, int batch, int total_batch, const PlanEnv& env) {
     if (L.kind != LAYER_SEP) return false;
     const long long hw = (long long)L.out_h * L.out_w;
     if ((frame0 * hw) % PX_TILE != 0) return false;
-    return plan_layer(L, batch * hw, batch * hw, g_num_cus).kernel == LayerKernel::SEP_U &&
-           plan_layer(L, total_batch * hw, total_batch * hw, g_num_cus).kernel == LayerKernel::SEP_U;
+    return plan_layer(L, batch * hw, batch * hw, env).kernel == LayerKernel::SEP_U &&
+           plan_layer(L, total_batch * hw, total_batch * hw, env).kernel == LayerKernel::SEP_U;
 }
 
-// f(std::integral_constant<int, V>{}) for the V of Vs that equals v (the last one when none does): a plan's value as a
-// template argument
-template <int V, int... Vs, class F>
-static void with_value(int v, F&& f) {
-    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>{});
-    else if (v == V) f(std::integral_constant<int, V>{});
-    else with_value<Vs...>(v, f);
-}
-
-int launch_layer(const LayerDesc& L, int batch, float* d_head, hipStream_t s, int frame0) {
+int launch_layer(const LayerDesc& L, int batch, float* d_head, hipStream_t s, const PlanEnv& env, int frame0) {
     if (batch <= 0) return 0;
     if (L.cin % KC != 0) return PP_ERR_UNSUPPORTED;
     {
@@ -2713,18 +2489,18 @@ int launch_layer(const LayerDesc& L, int batch, float* d_head, hipStream_t s, in
     a.occ = L.d_occ; a.occ_nz = L.occ_nz;
     a.occbits = L.d_occbits; a.occ_w64 = occ_words(L.in_w);
     a.tr_coef = nullptr; a.tr_D = nullptr; a.tr_stat = nullptr;
-    a.cls_plane = layer_writes_cls_plane(L) ? L.d_cls_plane : nullptr;
+    a.cls_plane = layer_writes_cls_plane(L, env) ? L.d_cls_plane : nullptr;
     a.cls_col0 = L.cls_col0; a.cls_ncol = L.cls_ncol;
     if (L.kind == LAYER_SEP) {
         a.px_h = L.out_h; a.px_w = L.out_w; a.epi = 0;
         a.M = (frame0 + batch) * L.out_h * L.out_w;
         if (frame0 > 0) {
-            if (!launch_layer_subrange_ok(L, frame0, batch, frame0 + batch)) return PP_ERR_UNSUPPORTED;
+            if (!launch_layer_subrange_ok(L, frame0, batch, frame0 + batch, env)) return PP_ERR_UNSUPPORTED;
             a.tile_lo = (int)(((long long)frame0 * L.out_h * L.out_w) / PX_TILE);
         }
         if (L.cout % 32 != 0) return PP_ERR_UNSUPPORTED;
         // a sparse input is only understood by the split-precision uniform-wave / split-K kernels
-        if (a.occ != nullptr && !sparse_input_supported(L, batch))
+        if (a.occ != nullptr && !sparse_input_supported(L, batch, env))
             return PP_ERR_UNSUPPORTED;
     } else if (L.kind == LAYER_DECONV) {
         a.px_h = L.in_h; a.px_w = L.in_w; a.epi = 1;
@@ -2735,26 +2511,26 @@ int launch_layer(const LayerDesc& L, int batch, float* d_head, hipStream_t s, in
         a.M = batch * L.in_h * L.in_w;
         if (L.n_total != 32) return PP_ERR_UNSUPPORTED;
     }
-    const LayerPlan p = plan_layer(L, layer_rows(L, batch), a.M, g_num_cus);
-    const int n = L.n_total;
+    const LayerPlan p = plan_layer(L, layer_rows(L, batch), a.M, env);
+    const int n = L.n_total, cus = env.cus;
     switch (p.kernel) {
     case LayerKernel::SEP_K4:
         with_value<1, 2>(p.s, [&](auto S) { launch_k4<S>(a, n, p.k8, s); });
         break;
     case LayerKernel::SEP_P:
-        launch_p(a, p.sh, s);
+        launch_p(a, p.sh, cus, s);
         break;
     case LayerKernel::SEP_U:
-        with_value<1, 2>(p.s, [&](auto S) { with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_u<NT, S>(a, n, p.prec, p.occ, p.sh, s); }); });
+        with_value<1, 2>(p.s, [&](auto S) { with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_u<NT, S>(a, n, p.prec, p.occ, p.sh, cus, s); }); });
         break;
     case LayerKernel::DECONV_K4:
         with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_deconv_k4<NT>(a, n, s); });
         break;
     case LayerKernel::DECONV_R:
-        with_value<256, 128, 64>(p.cin, [&](auto CIN) { launch_deconv_r<CIN>(a, s); });
+        with_value<256, 128, 64>(p.cin, [&](auto CIN) { launch_deconv_r<CIN>(a, cus, s); });
         break;
     case LayerKernel::DECONV_U:
-        with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_deconv_u<NT>(a, n, s); });
+        with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_deconv_u<NT>(a, n, cus, s); });
         break;
     case LayerKernel::GEMM_WS:   // (the deconv and head products run as MODE 1 with S = 1)
         if (p.mode == 0) with_value<1, 2>(p.s, [&](auto S) { with_value<128, 64, 32>(p.nt, [&](auto NT) { launch_ws<NT, 0, S>(a, n, p.pxb, s); }); });

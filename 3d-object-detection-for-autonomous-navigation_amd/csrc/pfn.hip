@@ -31,6 +31,7 @@
 #include <stdlib.h>
 
 #include "pp_common.h"
+#include "pp_switches.h"
 #include "anchor_mask_dev.h"
 
 template <int N>
@@ -488,31 +489,22 @@ __global__ __launch_bounds__(256) void k_pfn_canvas2(PfnParams p) {
     while (cur_cell < ncells) { write_cell(cur_cell); ++cur_cell; }
 }
 
-// PP_PFN_KERNEL=1 selects the first-generation kernel for the fused path
-static bool pfn_first_generation();
+// (PpSwitches::pfn_first_generation, PP_PFN_KERNEL=1, selects the first-generation kernel for the fused path)
 // the extra anchor-mask workgroups ride in the second-generation CSR kernel only (dense canvas, grid fits the LDS image)
-bool pfn_can_carry_anchor_mask(const PfnParams& p, bool padded_source) {
-    return !padded_source && p.feat_out == nullptr && PFN2_CW * p.nz <= 64 && !pfn_first_generation() && !p.sparse &&
+bool pfn_can_carry_anchor_mask(const PfnParams& p, bool padded_source, const PpSwitches& sw) {
+    return !padded_source && p.feat_out == nullptr && PFN2_CW * p.nz <= 64 && !sw.pfn_first_generation && !p.sparse &&
            p.ny * (p.nx | 1) <= AM_MAX_CELLS && !p.with_distance;
-}
-static bool pfn_first_generation() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("PP_PFN_KERNEL");
-        v = (e && e[0] == '1') ? 1 : 0;
-    }
-    return v == 1;
 }
 
 // does launch_pfn run the pillar-centric kernel (the one that sets the occupancy bitmap) for these parameters?
-static bool pfn_pillar_centric(const PfnParams& p, bool padded) {
+static bool pfn_pillar_centric(const PfnParams& p, bool padded, const PpSwitches& sw) {
     return !padded && !p.with_distance && p.sparse && p.pillar_cell != nullptr && p.npillars != nullptr && PFN2_CW * p.nz <= 64 &&
-           !pfn_first_generation();
+           !sw.pfn_first_generation;
 }
-bool pfn_writes_occbits(const PfnParams& p, bool padded) { return pfn_pillar_centric(p, padded); }
+bool pfn_writes_occbits(const PfnParams& p, bool padded, const PpSwitches& sw) { return pfn_pillar_centric(p, padded, sw); }
 
 template <int CPL, int F>
-static void launch_pfn_t(const PfnParams& p, bool padded, hipStream_t s) {
+static void launch_pfn_t(const PfnParams& p, bool padded, const PpSwitches& sw, hipStream_t s) {
     const int ncanvas = p.ny * p.nx;
     dim3 grid((ncanvas + 4 * PFN_CW - 1) / (4 * PFN_CW), p.batch);
     if (p.with_distance) {   // the generic kernel carries the distance feature (not a shipped configuration)
@@ -520,11 +512,11 @@ static void launch_pfn_t(const PfnParams& p, bool padded, hipStream_t s) {
         else PP_LAUNCH("k_pfn_canvas", (k_pfn_canvas<CPL, F, false, true>), grid, dim3(256), 0, s, p);
     } else if (padded) {
         PP_LAUNCH("k_pfn_canvas", (k_pfn_canvas<CPL, F, true>), grid, dim3(256), 0, s, p);
-    } else if (pfn_pillar_centric(p, padded)) {
+    } else if (pfn_pillar_centric(p, padded, sw)) {
         // sparse canvas: a wave per PFN2_CW pillars of the voxeliser's list
         dim3 gridp((p.max_voxels + 4 * PFN2_CW - 1) / (4 * PFN2_CW), p.batch);
         PP_LAUNCH("k_pfn_canvas2", (k_pfn_canvas2<CPL, F, true>), gridp, dim3(256), 0, s, p);
-    } else if (PFN2_CW * p.nz <= 64 && !pfn_first_generation()) {
+    } else if (PFN2_CW * p.nz <= 64 && !sw.pfn_first_generation) {
         dim3 grid2((ncanvas + 4 * PFN2_CW - 1) / (4 * PFN2_CW) + (p.am_mask != nullptr ? AM_PFN_BLOCKS : 0), p.batch);
         const size_t lds = (p.am_mask != nullptr) ? (size_t)p.ny * (p.nx | 1) * sizeof(int) : 0;
         PP_LAUNCH("k_pfn_canvas2", (k_pfn_canvas2<CPL, F>), grid2, dim3(256), lds, s, p);
@@ -533,7 +525,7 @@ static void launch_pfn_t(const PfnParams& p, bool padded, hipStream_t s) {
     }
 }
 
-int launch_pfn(const PfnParams& p, bool padded, hipStream_t s) {
+int launch_pfn(const PfnParams& p, bool padded, const PpSwitches& sw, hipStream_t s) {
     if (p.batch <= 0) return 0;
     const int C = p.C;
     int cpl;
@@ -544,7 +536,7 @@ int launch_pfn(const PfnParams& p, bool padded, hipStream_t s) {
     if (C % 4 != 0) return PP_ERR_UNSUPPORTED;
     if (p.F != 3 && p.F != 4) return PP_ERR_UNSUPPORTED;
 #define PFN_CASE(CPLV, FV) \
-    if (cpl == CPLV && p.F == FV) { launch_pfn_t<CPLV, FV>(p, padded, s); return 0; }
+    if (cpl == CPLV && p.F == FV) { launch_pfn_t<CPLV, FV>(p, padded, sw, s); return 0; }
     PFN_CASE(1, 3) PFN_CASE(1, 4) PFN_CASE(2, 3) PFN_CASE(2, 4) PFN_CASE(4, 3) PFN_CASE(4, 4)
 #undef PFN_CASE
     return PP_ERR_UNSUPPORTED;

@@ -7,7 +7,33 @@
 
 #include "pp_engine.h"
 
-extern int g_num_cus;   // backbone.hip: CU count for persistent launches
+// The switch table (pp_switches.h): the one place in csrc/ that reads the environment.  Each switch parses as it always
+// has (INTEGRATION.md section 5 states the values).
+PpSwitches pp_parse_switches() {
+    PpSwitches v;
+    if (const char* e = getenv("PP_GEMM_PREC")) v.gemm_f32 = e[0] == 'f';
+    if (const char* e = getenv("PP_SEP_KERNEL")) v.sep_ws = e[0] == 'w';
+    if (const char* e = getenv("PP_SEP_NT")) v.sep_nt = atoi(e);
+    if (const char* e = getenv("PP_SEP_K4")) v.sep_k4 = atoi(e);
+    if (const char* e = getenv("PP_DECONV_K4")) v.deconv_k4 = atoi(e);
+    if (const char* e = getenv("PP_PFN_KERNEL")) v.pfn_first_generation = e[0] == '1';
+    if (const char* e = getenv("PP_DENSE_CANVAS")) v.dense_canvas = e[0] == '1';
+    if (const char* e = getenv("PP_NO_GRAPH")) v.no_graph = e[0] == '1';
+    v.no_head_fusion = getenv("PP_NO_HEAD_FUSION") != nullptr;
+    TrainSwitches& t = v.train;
+    if (const char* e = getenv("PP_TRAIN_FUSED_MIN")) t.fused_min = atol(e);
+    if (const char* e = getenv("PP_TRAIN_GEMM")) t.split_gemm = e[0] != 'f';
+    if (const char* e = getenv("PP_TRAIN_FIN_THR")) {
+        long a = 0, b = 0;
+        if (sscanf(e, "%ld,%ld", &a, &b) == 2 && a > 0 && b > 0) { t.fin256 = a; t.fin64 = b; }
+    }
+    if (const char* e = getenv("PP_TRAIN_ARENA_FLOATS")) t.arena_floats = std::max(0l, atol(e));
+    return v;
+}
+const PpSwitches& pp_switches() {
+    static const PpSwitches sw = pp_parse_switches();
+    return sw;
+}
 
 static std::string g_create_error;
 
@@ -236,17 +262,18 @@ static int run_pfn(pp_engine* e, int batch, bool padded, float* feat_out, bool w
     // the bitmap is only as good as its clearing: the fused path's k_cell_first does it (run_voxelize); the stage entry
     // points build the cell map from the caller's coordinates and keep the cell-map lookups
     p.occbits = (e->sparse_canvas && !padded && e->vox[e->in_buf].occ_cleared) ? e->d_occbits : nullptr;
-    e->occbits_live = p.occbits != nullptr && pfn_writes_occbits(p, padded);
+    const PpSwitches& sw = e->plan_env.sw;
+    e->occbits_live = p.occbits != nullptr && pfn_writes_occbits(p, padded, sw);
     if (!e->occbits_live) p.occbits = nullptr;
     e->vox[e->in_buf].occ_cleared = false;
     e->mask_in_pfn = false;
-    if (with_mask && batch <= kAnchorMaskInPfnMaxBatch && pfn_can_carry_anchor_mask(p, padded)) {
+    if (with_mask && batch <= kAnchorMaskInPfnMaxBatch && pfn_can_carry_anchor_mask(p, padded, sw)) {
         // the anchor mask (needs the cell map only, read by the post-process only) rides in this launch
         p.am_cells = e->d_cells; p.am_A = e->A; p.am_threshold = e->cfg.anchor_area_threshold; p.am_mask = e->d_mask;
         e->mask_in_pfn = true;
     }
     ProfScope ps(e, nullptr);   // under the name of the kernel launch_pfn chooses (k_pfn_canvas or k_pfn_canvas2)
-    int st = launch_pfn(p, padded, e->stream);
+    int st = launch_pfn(p, padded, sw, e->stream);
     if (st) return fail(e, st, "PFN: unsupported C=%d / F=%d", e->C, e->F);
     HIPCHK(e, hipGetLastError());
     return PP_OK;
@@ -269,14 +296,14 @@ static int run_anchor_mask(pp_engine* e, int batch) {
 static void refresh_tags(pp_engine* e, int batch) {
     if (e->tag_batch == batch) return;
     for (size_t i = 0; i < e->layers.size(); ++i)
-        e->layer_tags[i] = layer_kernel_name(e->layers[i], batch) + ":" + e->layers[i].name;
+        e->layer_tags[i] = layer_kernel_name(e->layers[i], batch, e->plan_env) + ":" + e->layers[i].name;
     e->tag_batch = batch;
 }
 
 static int run_backbone(pp_engine* e, int batch) {
     refresh_tags(e, batch);
     e->cls_plane_live = false;
-    for (const LayerDesc& L : e->layers) if (layer_writes_cls_plane(L)) e->cls_plane_live = true;
+    for (const LayerDesc& L : e->layers) if (layer_writes_cls_plane(L, e->plan_env)) e->cls_plane_live = true;
     // Frame sub-ranges for the layers whose maps do not fit the last-level cache (round 4).  A run of consecutive
     // separable layers of a block is walked sub-batch by sub-batch -- L1(s0) L2(s0) L3(s0), L1(s1) ... -- so that what a
     // layer reads is what the layer before has just written for the same frames and still sits in the 256 MB cache:
@@ -322,7 +349,7 @@ static int run_backbone(pp_engine* e, int batch) {
                 ok = true;
                 for (size_t k = i; k < j && ok; ++k)
                     for (int f0 = 0; f0 < batch && ok; f0 += sub)
-                        ok = launch_layer_subrange_ok(e->layers[k], f0, std::min(sub, batch - f0), batch) &&
+                        ok = launch_layer_subrange_ok(e->layers[k], f0, std::min(sub, batch - f0), batch, e->plan_env) &&
                              (long long)sub * e->layers[k].out_h * e->layers[k].out_w >= 1024ll * 128;
                 if (!ok) sub *= 2;
             }
@@ -337,7 +364,7 @@ static int run_backbone(pp_engine* e, int batch) {
                 // sparse first layer: the occupancy bitmap when this pass's PFN launch left one, else the cell map
                 if (k == 0 && L.d_occ != nullptr) { L.d_occ = e->d_cellmap; L.d_occbits = e->occbits_live ? e->d_occbits : nullptr; }
                 ProfScope ps(e, e->layer_tags[k].c_str());
-                int st = launch_layer(L, nb, e->d_head, e->stream, f0);
+                int st = launch_layer(L, nb, e->d_head, e->stream, e->plan_env, f0);
                 if (st) return fail(e, st, "layer %s: unsupported shape (cin=%d cout=%d)", L.name, L.cin, L.cout);
             }
         }
@@ -585,9 +612,10 @@ int pp_create(const pp_config* cfg, int device, pp_handle* out) {
         return PP_ERR_HIP;
     }
     {
+        e->plan_env.sw = pp_switches();
         int ncu = 0;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0)
-            g_num_cus = ncu;
+            e->plan_env.cus = ncu;
     }
     for (int j = 0; j < 3; ++j) {
         e->geom.lo[j] = cfg->pc_range[j];
@@ -651,7 +679,7 @@ int pp_create(const pp_config* cfg, int device, pp_handle* out) {
             e->fuse_heads = true;
             for (const LayerDesc& L : e->layers)
                 if (L.kind == LAYER_DECONV && !deconv_can_fuse_heads(L)) e->fuse_heads = false;
-            if (getenv("PP_NO_HEAD_FUSION")) e->fuse_heads = false;   // A/B switch for measurements
+            if (e->plan_env.sw.no_head_fusion) e->fuse_heads = false;   // PP_NO_HEAD_FUSION: A/B switch for measurements
         }
         if (st2 == PP_OK && e->fuse_heads) {
             int nd = 0;
@@ -937,11 +965,10 @@ int pp_finalize_weights(pp_handle e) {
 // writes only the cells that hold a pillar and the first layer looks every window position up in the cell
 // map.  Needs the kernels that know the lookup (sparse_input_supported); PP_DENSE_CANVAS=1 turns it off.
 void decide_sparse_canvas(pp_engine* e) {
-    const char* env = getenv("PP_DENSE_CANVAS");
     const long long cells = (long long)e->ny * e->nx;
     LayerDesc& L0 = e->layers[0];
-    e->sparse_canvas = !(env && env[0] == '1') && cells >= 32768 && 4ll * e->cfg.max_voxels <= cells &&
-                       L0.in == e->d_canvas && sparse_input_supported(L0, e->B);
+    e->sparse_canvas = !e->plan_env.sw.dense_canvas && cells >= 32768 && 4ll * e->cfg.max_voxels <= cells &&
+                       L0.in == e->d_canvas && sparse_input_supported(L0, e->B, e->plan_env);
     L0.d_occ = e->sparse_canvas ? e->d_cellmap : nullptr;
     L0.occ_nz = e->nz;
 }
@@ -1169,15 +1196,6 @@ bool capture_exec(pp_engine* e, const std::function<int()>& enqueue, hipGraphExe
     return ok;
 }
 
-bool graphs_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char* s = getenv("PP_NO_GRAPH");
-        v = (s && s[0] == '1') ? 0 : 1;
-    }
-    return v == 1;
-}
-
 extern "C" {
 
 int pp_detect_async(pp_handle e) {
@@ -1199,7 +1217,7 @@ int pp_detect_async(pp_handle e) {
     // per-(batch, max points) constant, so the captured graph is reusable until either changes (profiling
     // needs the per-launch events and uses plain launches)
     bool launched = false;
-    if (e->prof <= 0 && e->graph_state == 0 && graphs_enabled()) {
+    if (e->prof <= 0 && e->graph_state == 0 && graphs_enabled(e)) {
         const DetectKey key = detect_key(e, B, graph_bucket(e, e->cur_max_n));
         pp_engine::GraphSlot* slot = nullptr;
         pp_engine::GraphSlot* lru = &e->graphs[0];
@@ -1553,7 +1571,10 @@ int pp_plan_layer_name(const pp_layer_plan_desc* layer, int32_t batch, int32_t c
     L.d_wt16 = layer->has_wt16 ? &pieces : nullptr;
     L.d_head_wt16 = layer->has_head_wt16 ? &pieces : nullptr;
     L.d_occ = layer->sparse_input ? &cells : nullptr;
-    const std::string n = layer_plan_name(L, batch, compute_units);
+    PlanEnv env;
+    env.cus = compute_units;
+    env.sw = pp_switches();
+    const std::string n = layer_plan_name(L, batch, env);
     if ((int)n.size() + 1 > name_capacity) return PP_ERR_ARG;
     memcpy(name, n.c_str(), n.size() + 1);
     return PP_OK;
@@ -1568,9 +1589,9 @@ int pp_bench_layer(pp_handle e, int32_t layer, int32_t batch, int32_t reps, int3
     int st = check_batch(e, batch); if (st) return st;
     const LayerDesc& L = e->layers[layer];
     for (int i = 0; i < 2; ++i)
-        if ((st = launch_layer(L, batch, e->d_head, e->stream))) return fail(e, st, "pp_bench_layer: unsupported layer");
+        if ((st = launch_layer(L, batch, e->d_head, e->stream, e->plan_env))) return fail(e, st, "pp_bench_layer: unsupported layer");
     HIPCHK(e, hipEventRecord(e->t0, e->stream));
-    for (int i = 0; i < reps; ++i) launch_layer(L, batch, e->d_head, e->stream);
+    for (int i = 0; i < reps; ++i) launch_layer(L, batch, e->d_head, e->stream, e->plan_env);
     HIPCHK(e, hipEventRecord(e->t1, e->stream));
     HIPCHK(e, hipEventSynchronize(e->t1));
     HIPCHK(e, hipGetLastError());

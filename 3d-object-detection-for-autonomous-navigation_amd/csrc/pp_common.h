@@ -196,9 +196,11 @@ struct PfnParams {
     float am_threshold;
     uint8_t* am_mask;      // [batch][A]
 };
-bool pfn_can_carry_anchor_mask(const PfnParams& p, bool padded_source);
-bool pfn_writes_occbits(const PfnParams& p, bool padded_source);           // would launch_pfn's kernel set PfnParams::occbits?   // would launch_pfn run the extra workgroups?
-int launch_pfn(const PfnParams& p, bool padded_source, hipStream_t s);  // returns 0 or PP_ERR_UNSUPPORTED
+struct PpSwitches;   // pp_switches.h: the process's PP_* switches
+struct PlanEnv;      // pp_plan.h: compute units + switches, what the choice of a kernel depends on besides the shapes
+bool pfn_can_carry_anchor_mask(const PfnParams& p, bool padded_source, const PpSwitches& sw);   // would launch_pfn run the extra workgroups?
+bool pfn_writes_occbits(const PfnParams& p, bool padded_source, const PpSwitches& sw);   // would launch_pfn's kernel set PfnParams::occbits?
+int launch_pfn(const PfnParams& p, bool padded_source, const PpSwitches& sw, hipStream_t s);  // returns 0 or PP_ERR_UNSUPPORTED
 
 void launch_anchor_mask(const int* cellmap, int batch, int nz, int ny, int nx, const int* cells, int64_t A,
                         float threshold, int* integ, uint8_t* mask, hipStream_t s);
@@ -210,11 +212,11 @@ void launch_anchor_mask_bits(const unsigned long long* occbits, int batch, int n
                              float threshold, uint8_t* mask, hipStream_t s);
 
 bool deconv_can_fuse_heads(const LayerDesc& L);
-bool layer_writes_cls_plane(const LayerDesc& L);   // does this layer's kernel leave the compact class-logit plane?
-bool sparse_input_supported(const LayerDesc& L, int batch);   // may L's input be a canvas with unwritten empty cells?
-std::string layer_kernel_name(const LayerDesc& L, int batch);  // template instantiation that runs L at this batch
-// the same for a part with `cus` compute units, with the SH argument the tags leave out; reads no device state
-std::string layer_plan_name(const LayerDesc& L, int batch, int cus);
+bool layer_writes_cls_plane(const LayerDesc& L, const PlanEnv& env);   // does this layer's kernel leave the compact class-logit plane?
+bool sparse_input_supported(const LayerDesc& L, int batch, const PlanEnv& env);   // may L's input be a canvas with unwritten empty cells?
+std::string layer_kernel_name(const LayerDesc& L, int batch, const PlanEnv& env);  // template instantiation that runs L at this batch
+// the same with the SH argument the tags leave out; reads no device state
+std::string layer_plan_name(const LayerDesc& L, int batch, const PlanEnv& env);
 // training-mode forward of one separable layer (backbone.hip: k_sep_u<..., TR = 1>; called by train.hip)
 struct SepTrainArgs {
     const float* in;             // input map [batch][in_h][in_w][cin] with a PP_ZPAD_FLOATS header in front: NaN-filled when
@@ -229,7 +231,7 @@ struct SepTrainArgs {
     int batch, in_h, in_w, cin, out_h, out_w, cout, stride;
     const char* tag;             // profiler name of the launch ("k_sep_u_tr:<layer>")
 };
-int launch_sep_train(const SepTrainArgs& t, hipStream_t s);   // rows of `stat` written, 0: shape not supported
+int launch_sep_train(const SepTrainArgs& t, int cus, hipStream_t s);   // rows of `stat` written, 0: shape not supported
 // ... and of a plain product out[rows][N] = in[rows][K] . W (+ bias): the transposed convolutions' forward GEMMs, the heads
 struct RowsTrainArgs {
     const float* in;             // [rows][K], rows contiguous (no header needed)
@@ -241,10 +243,10 @@ struct RowsTrainArgs {
     int K, N, ld_out;
     const char* tag;
 };
-int launch_rows_train(const RowsTrainArgs& t, hipStream_t s);
-int launch_layer(const LayerDesc& L, int batch, float* d_head, hipStream_t s, int frame0 = 0);
+int launch_rows_train(const RowsTrainArgs& t, int cus, hipStream_t s);
+int launch_layer(const LayerDesc& L, int batch, float* d_head, hipStream_t s, const PlanEnv& env, int frame0 = 0);  // returns 0 or PP_ERR_UNSUPPORTED
 // may L be launched over the frames [frame0, frame0 + batch) of a total_batch-frame batch (k_sep_u's tile sub-ranges)?
-bool launch_layer_subrange_ok(const LayerDesc& L, int frame0, int batch, int total_batch);  // returns 0 or PP_ERR_UNSUPPORTED
+bool launch_layer_subrange_ok(const LayerDesc& L, int frame0, int batch, int total_batch, const PlanEnv& env);
 
 struct PostParams {
     int batch;

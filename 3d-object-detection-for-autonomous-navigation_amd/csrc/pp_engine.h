@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include "pp_common.h"
+#include "pp_plan.h"
 #include "pp_ring.h"
 #include "train.h"
 
@@ -73,6 +74,8 @@ struct pp_engine {
     pp_config cfg;
     int device = 0;
     hipStream_t stream = nullptr;
+    PlanEnv plan_env;             // pp_create: the device's compute units and the process's switch table (pp_switches()).
+                                  // Every choice of a kernel, a grid or a path that depends on either reads it from here
     std::string err;
     VoxGeom geom;
     int nx = 0, ny = 0, nz = 0, ncell = 0;
@@ -560,7 +563,7 @@ inline int det_rows(const pp_engine* e) {
     return (e->rule.class_nms == PP_CLASS_NMS_PER_CLASS ? e->ncls : 1) * e->cfg.nms_post_max_size;
 }
 int graph_bucket(const pp_engine* e, int max_n);
-bool graphs_enabled();
+inline bool graphs_enabled(const pp_engine* e) { return !e->plan_env.sw.no_graph; }   // PP_NO_GRAPH=1: plain launches
 // Captures what `enqueue` queues on e->stream (thread-local capture) and instantiates it into *out.  false, with *out
 // NULL and the sticky HIP error cleared, when a step of that fails; *enqueue_status (optional) is what `enqueue` returned.
 bool capture_exec(pp_engine* e, const std::function<int()>& enqueue, hipGraphExec_t* out, int* enqueue_status);

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "pp_common.h"
+#include "pp_switches.h"
 
 struct TrainEntry {
     std::string name;    // Keras tensor name (weights.py), e.g. "rpn/block2/3/pointwise_kernel"
@@ -86,17 +87,12 @@ struct TrainLayerBuf {   // per plan layer
     float4* coef;   // [cout] (sc, sh, inv, -mean * inv): act = z * sc + sh, zhat = z * inv + nmi (k_tr_bn_finalize)
 };
 
-// The PP_TRAIN_* switches, read from the environment once per process.
-struct TrainSwitches {
-    long fused_min;           // PP_TRAIN_FUSED_MIN: fused separable forward from this many output pixels on
-    bool split_gemm;          // PP_TRAIN_GEMM=f32 clears it: every product on k_tr_gemm
-    long fin256, fin64;       // PP_TRAIN_FIN_THR=a,b: BatchNorm finalize widths
-    long arena_floats;        // PP_TRAIN_ARENA_FLOATS: cap of the split-K / deferred-reduction arena (0: none)
-};
-const TrainSwitches& train_switches();
-
 struct TrainCtx {
     hipStream_t stream;
+    // what the step's choices depend on besides the shapes, from the handle's PlanEnv: the compute units (persistent
+    // grids of the fused forward launches) and the PP_TRAIN_* switches (pp_switches.h)
+    int cus = 256;
+    TrainSwitches sw;
     // voxeliser products of the resident frames
     const float* pts_sorted;
     const int* offsets;

@@ -611,21 +611,6 @@ static void flush_deferred(TrainStepState& st) {
     st.jobs.clear();
 }
 
-const TrainSwitches& train_switches() {
-    static const TrainSwitches sw = [] {
-        TrainSwitches v{32768, true, 128, 32, 0};
-        if (const char* e = getenv("PP_TRAIN_FUSED_MIN")) v.fused_min = atol(e);
-        if (const char* e = getenv("PP_TRAIN_GEMM")) v.split_gemm = e[0] != 'f';
-        if (const char* e = getenv("PP_TRAIN_FIN_THR")) {
-            long a = 0, b = 0;
-            if (sscanf(e, "%ld,%ld", &a, &b) == 2 && a > 0 && b > 0) { v.fin256 = a; v.fin64 = b; }
-        }
-        if (const char* e = getenv("PP_TRAIN_ARENA_FLOATS")) v.arena_floats = std::max(0l, atol(e));
-        return v;
-    }();
-    return sw;
-}
-
 // 64 x 64 tiles (WM = WN = 1)
 template <int KCH>
 static void launch_gemm2(const char* tag, const TGemm2& a2, bool akc, bool bkc, dim3 grid, hipStream_t s) {
@@ -654,12 +639,12 @@ struct GemmCall {
     bool defer;
 };
 
-static bool gemm2_eligible(const GemmCall& c) {
+static bool gemm2_eligible(const TrainStepState& st, const GemmCall& c) {
     // the split-precision kernel: unit stride on one axis of each operand, 16-byte aligned rows
     const bool akc = c.sak == 1, bkc = c.sbk == 1;
     const bool a_ok = akc ? (c.sam % 4 == 0) : (c.sam == 1 && c.sak % 4 == 0 && c.M % 4 == 0);
     const bool b_ok = bkc ? (c.sbn % 4 == 0) : (c.sbn == 1 && c.sbk % 4 == 0 && c.N % 4 == 0);
-    return train_switches().split_gemm && a_ok && b_ok && c.K % 4 == 0 && ((uintptr_t)c.A % 16 == 0) && ((uintptr_t)c.B % 16 == 0);
+    return st.cx.sw.split_gemm && a_ok && b_ok && c.K % 4 == 0 && ((uintptr_t)c.A % 16 == 0) && ((uintptr_t)c.B % 16 == 0);
 }
 
 // partial tiles at arena offset `at` (the free tail, behind the regions of this step's deferred reductions)
@@ -692,7 +677,7 @@ static int tr_gemm(TrainStepState& st, const GemmCall& c) {
     TGemm g = gemm_args(st, c, st.arena_used, ksplit);
     int stat_tiles = 0;
     const int M = c.M, N = c.N, K = c.K;
-    if (gemm2_eligible(c)) {
+    if (gemm2_eligible(st, c)) {
         const bool akc = c.sak == 1, bkc = c.sbk == 1;
         int kper = ((K + ksplit - 1) / ksplit + 31) / 32 * 32;
         const long small = (long)((M + 63) / 64) * ((N + 63) / 64) * ((K + kper - 1) / kper);
@@ -725,7 +710,7 @@ static int tr_gemm(TrainStepState& st, const GemmCall& c) {
 // layer.  When both fit the split kernel's forms they go out as ONE launch (k_tr_gemm2_pair); otherwise one by one.
 static void tr_gemm_pair(TrainStepState& st, const GemmCall& w, const GemmCall& d) {
     const bool forms = w.sak != 1 && w.sbk != 1 && d.sak == 1;
-    if (forms && gemm2_eligible(w) && gemm2_eligible(d) && w.defer && w.stat_part == nullptr && d.stat_part == nullptr) {
+    if (forms && gemm2_eligible(st, w) && gemm2_eligible(st, d) && w.defer && w.stat_part == nullptr && d.stat_part == nullptr) {
         // 64-wide chunks while the launch lives on latency, the 32-wide ones (five workgroups per CU) beyond: two
         // half-filled launches of a large batch -- block3's 640 + 640 workgroups at B=32 -- fill the chip together
         int ks1, ks2, kper1, kper2, n1, n2;
@@ -2281,8 +2266,7 @@ struct StepPlan {
     bool heads_fused;
 };
 
-StepPlan plan_step(const TrainPlan& plan, const TrainShape& s, int B) {
-    const TrainSwitches& sw = train_switches();
+StepPlan plan_step(const TrainPlan& plan, const TrainShape& s, int B, const TrainSwitches& sw) {
     StepPlan sp;
     // ~128 rows of the largest map per workgroup, one per CU at least
     const long want = ((long)B * s.ny * s.nx / 128 + 255) / 256 * 256;
@@ -2323,7 +2307,7 @@ static void bn_finalize(const TrainStepState& st, const float* part, int nparts,
     // from 32 (PP_TRAIN_FIN_THR="a,b" for A/B measurements; round 4, the 20 launches of a step: thresholds 2048 / 512 ->
     // 154 us at B=32 and 102 us at B=2; 512 / 128 -> 112 / 90; 128 / 32 -> 114 / 87: the launch is a chain of dependent
     // load rounds, and more lanes per channel make it shorter even when most of them carry one pair)
-    const TrainSwitches& sw = train_switches();
+    const TrainSwitches& sw = st.cx.sw;
     const hipStream_t s = st.cx.stream;
     if ((long)nparts * ntaps >= sw.fin256)
         PP_LAUNCH("k_tr_bn_finalize:256", (k_tr_bn_finalize<256>), dim3(C), dim3(256), 0, s, part, nparts, C, n_rows,
@@ -2464,7 +2448,7 @@ int train_step(const TrainCtx& cx, const TrainShape& s, const TrainPlan& plan, c
     // stream while the forward pass runs)
     if (plan.unsupported) return PP_ERR_UNSUPPORTED;
     const int B = batch;
-    const StepPlan sp = plan_step(plan, s, B);
+    const StepPlan sp = plan_step(plan, s, B, cx.sw);
     TrainStepState st{cx, plan, params, grads, state, sp.npart, {}, 0};
     const std::vector<TrainLayer>& Ls = plan.layers;
 
@@ -2543,7 +2527,7 @@ int train_step(const TrainCtx& cx, const TrainShape& s, const TrainPlan& plan, c
                 t.Z = tb.Z; t.D = tb.D; t.stat = cx.stat_part;
                 t.batch = B; t.in_h = l.in_h; t.in_w = l.in_w; t.cin = l.cin; t.out_h = l.out_h; t.out_w = l.out_w;
                 t.cout = l.cout; t.stride = l.stride; t.tag = q.fused_tag.c_str();
-                stat_tiles = launch_sep_train(t, cx.stream);
+                stat_tiles = launch_sep_train(t, cx.cus, cx.stream);
             }
             if (stat_tiles == 0) {
                 const long nthr = rows * (l.cin / 4);
@@ -2566,7 +2550,7 @@ int train_step(const TrainCtx& cx, const TrainShape& s, const TrainPlan& plan, c
                 RowsTrainArgs t;
                 t.in = in; t.wt16 = cx.pw16 + q.pw16_off; t.bias = nullptr; t.out = tb.Z; t.stat = cx.stat_part;
                 t.rows = m; t.K = l.cin; t.N = N; t.ld_out = N; t.tag = q.fused_tag.c_str();
-                stat_tiles = launch_rows_train(t, cx.stream);
+                stat_tiles = launch_rows_train(t, cx.cus, cx.stream);
             }
             if (stat_tiles == 0)
                 stat_tiles = tr_gemm(st, GemmCall{q.fwd_tag.c_str(), in, l.cin, 1, st.p(q.pw), 1, l.cin, tb.Z, N, (int)m, N,
@@ -2589,7 +2573,7 @@ int train_step(const TrainCtx& cx, const TrainShape& s, const TrainPlan& plan, c
         RowsTrainArgs r;
         r.in = cx.cat; r.wt16 = cx.head_w16; r.bias = cx.head_b; r.out = cx.head; r.stat = nullptr;
         r.rows = px; r.K = s.CC; r.N = PP_HEAD_COLS; r.ld_out = PP_HEAD_COLS; r.tag = "k_sep_u_tr:heads";
-        heads_done = launch_rows_train(r, cx.stream);
+        heads_done = launch_rows_train(r, cx.cus, cx.stream);
     }
     if (!heads_done)
         tr_gemm(st, GemmCall{"k_tr_gemm2:fwd.heads", cx.cat, s.CC, 1, cx.head_w, PP_HEAD_COLS, 1, cx.head, PP_HEAD_COLS,

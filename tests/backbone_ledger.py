@@ -29,7 +29,7 @@ import pp_amd as pp
 
 CELL = 0.08
 Z_RANGE = (-3.0, 1.0)
-CUS = 256                         # the MI355X; g_num_cus's default
+CUS = 256                         # the MI355X; PlanEnv's default
 
 Case = collections.namedtuple(
     "Case", "name nx ny strides up0 layer_nums pfn filters ups batch max_batch max_voxels points seed env")

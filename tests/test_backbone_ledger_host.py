@@ -26,6 +26,7 @@ from conftest import ROOT
 import backbone_ledger as bl
 
 BACKBONE = os.path.join(ROOT, "3d-object-detection-for-autonomous-navigation_amd", "csrc", "backbone.hip")
+PLAN_HEADER = os.path.join(os.path.dirname(BACKBONE), "pp_plan.h")
 HEADER = os.path.join(ROOT, "include", "pp_hip.h")
 
 
@@ -82,10 +83,13 @@ def test_the_parameter_lists_are_those_of_launch_layer():
     assert src.count("(k_sep_u<NT, S, WPS, 0>)") == 1
     assert src.count("(k_gemm_ws<NT, MODE, S, 64>)") == 1 and src.count("(k_gemm_ws<NT, MODE, S, 128>)") == 1
     assert src.count("(k_deconv_u<NT, WPS>)") == 1 and "constexpr int WPS = 3;" in src
-    m = re.search(r"constexpr int sep_u_wpc\(int nt, int s, bool prec\) \{\s*return (.*?);\s*\}", src, re.S)
+    with open(PLAN_HEADER) as f:          # the workgroups per CU: the planner's header, which backbone.hip includes
+        plan_src = f.read()
+    assert '#include "pp_plan.h"' in src and "sep_u_wpc(int" not in src
+    m = re.search(r"constexpr int sep_u_wpc\(int nt, int s, bool prec\) \{\s*return (.*?);\s*\}", plan_src, re.S)
     assert " ".join(m.group(1).split()) == ("s == 1 ? (prec ? (nt == 128 ? SEP128_WPB : (nt == 64 ? SEP64_WPB : 3)) : (nt == 128 ? 3 : 4)) "
                                             ": (prec ? (nt == 128 ? 2 : 3) : (nt == 128 ? 2 : (nt == 64 ? 3 : 4)))")
-    assert "constexpr int SEP128_WPB = 2, SEP64_WPB = 3;" in src
+    assert "constexpr int SEP128_WPB = 2, SEP64_WPB = 3;" in plan_src
 
 
 def test_the_ledger_claims_exactly_the_dispatchable_set():

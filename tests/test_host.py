@@ -219,15 +219,25 @@ def test_bench_accounts_per_launch_when_a_layer_is_walked_in_sub_ranges(pp):
 
 def test_runtime_switch_table_matches_the_code():
     """INTEGRATION.md's switch table lists exactly the PP_* variables the library reads, and every name in it is read
-    by the library, the Python package or bench.py (no undocumented switch, no stale row)."""
+    by the library, the Python package or bench.py (no undocumented switch, no stale row).  The library reads them in
+    one place: the switch table's definition (pp_parse_switches, csrc/pp_api.hip; declared in csrc/pp_switches.h)."""
     pkg = os.path.join(ROOT, "3d-object-detection-for-autonomous-navigation_amd")
     csrc = os.path.join(pkg, "csrc")
     native = set()
+    readers = set()
     for f in os.listdir(csrc):
         if f.endswith((".hip", ".h")):
             with open(os.path.join(csrc, f)) as fh:
-                native |= set(re.findall(r'getenv\("(PP_[A-Z0-9_]*)"\)', fh.read()))
+                text = fh.read()
+            native |= set(re.findall(r'getenv\("(PP_[A-Z0-9_]*)"\)', text))
+            if 'getenv("PP_' in text:
+                readers.add(f)
     assert native, "no getenv(\"PP_...\") found in csrc"
+    assert readers == {"pp_api.hip"}, f"PP_* switches are read outside the switch table: {sorted(readers)}"
+    with open(os.path.join(csrc, "pp_api.hip")) as fh:
+        text = fh.read()
+    table = text[text.index("PpSwitches pp_parse_switches() {"):text.index("const PpSwitches& pp_switches() {")]
+    assert text.count('getenv("PP_') == table.count('getenv("PP_'), "a PP_* switch read outside pp_parse_switches"
     python = set()
     for path in [os.path.join(pkg, f) for f in os.listdir(pkg) if f.endswith(".py")] + [os.path.join(ROOT, "bench.py")]:
         with open(path) as fh:
