@@ -23,6 +23,7 @@ SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_
            "api_sweeps.hip", "sweeps.hip",
            "api_costmap.hip", "costmap.hip",
            "api_occupancy.hip", "occupancy.hip",
+           "api_inflate.hip", "inflate.hip",
            "api_track.hip", "track.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
@@ -57,6 +58,8 @@ EXPORTS = [
     "pp_set_costmap", "pp_get_costmap_config", "pp_costmap_async", "pp_get_costmaps", "pp_costmap_info",
     "pp_set_occupancy", "pp_get_occupancy_config", "pp_occupancy_update_async", "pp_get_occupancy", "pp_occupancy_info",
     "pp_occupancy_reset",
+    "pp_set_inflation", "pp_get_inflation_config", "pp_inflate_async", "pp_get_inflated", "pp_inflation_info",
+    "pp_inflate_grids",
     "pp_set_nms_mode", "pp_get_nms_mode", "pp_rotate_nms",
     "pp_set_projection", "pp_get_projection", "pp_get_bboxes", "pp_box3d_to_bbox",
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
@@ -232,6 +235,8 @@ PP_TRACK_MASK_ROWS = 128      # detection rows per frame the tracking step takes
 PP_COSTMAP_MAX_STEPS = 8      # predicted footprints per track (pp_set_costmap)
 PP_COSTMAP_MAX_CELLS = 262144      # width * height of a costmap
 PP_OCC_MAX_CELLS = 1048576      # width * height of an occupancy window (pp_set_occupancy)
+PP_INFLATE_MAX_RADIUS = 64      # cells: ceil(inflation_radius / resolution) at most (pp_set_inflation)
+PP_INFLATE_COSTMAP, PP_INFLATE_OCCUPANCY = 0, 1      # `source` of the pp_*inflat* calls
 PP_CLIP_NONE, PP_CLIP_VALUE, PP_CLIP_NORM, PP_CLIP_GLOBAL_NORM = 0, 1, 2, 3      # enum pp_grad_clip_mode
 
 
@@ -308,6 +313,17 @@ class PPOccupancyConfig(ctypes.Structure):
         ("l_miss", ctypes.c_int32),
         ("l_min", ctypes.c_int32),
         ("l_max", ctypes.c_int32),
+    ]
+
+
+class PPInflationConfig(ctypes.Structure):
+    _fields_ = [
+        ("resolution", ctypes.c_double),
+        ("inscribed_radius", ctypes.c_double),
+        ("inflation_radius", ctypes.c_double),
+        ("cost_scaling_factor", ctypes.c_double),
+        ("lethal_threshold", ctypes.c_int32),
+        ("unknown_min_cost", ctypes.c_int32),
     ]
 
 
@@ -562,6 +578,12 @@ def lib():
     L.pp_get_occupancy.argtypes = [vp, vp, vp, vp, i32]
     L.pp_occupancy_info.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32]
     L.pp_occupancy_reset.argtypes = [vp, i32]
+    L.pp_set_inflation.argtypes = [vp, i32, ctypes.POINTER(PPInflationConfig), vp, i32]
+    L.pp_get_inflation_config.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(PPInflationConfig)]
+    L.pp_inflate_async.argtypes = [vp, i32]
+    L.pp_get_inflated.argtypes = [vp, i32, vp, vp, i32]
+    L.pp_inflation_info.argtypes = [vp, i32, vp, vp, i32]
+    L.pp_inflate_grids.argtypes = [ctypes.c_int, vp, i32, i32, i32, ctypes.POINTER(PPInflationConfig), vp, i32, vp, vp, vp]
     L.pp_set_projection.argtypes = [vp, vp, i32]
     L.pp_get_projection.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_get_bboxes.argtypes = [vp, vp]

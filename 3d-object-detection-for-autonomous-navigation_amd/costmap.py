@@ -26,8 +26,8 @@ k = 1 .. horizon_steps, the same rectangle at (x + vx * t_k, y + vy * t_k), t_k 
 COMPOSE.  cell = max(point_cost if count >= min_points else -1, the costs of the footprints that cover it,
 0 if observed else -1), stored as int8.
 
-Out of scope: inflation (the navigation stack's inflation layer does it), a map in the fixed frame accumulated over
-time, ray-traced free space, removing the points of detected objects from the point layer, any ROS import.
+Inflation is a stage of its own behind this grid (inflation.py, Engine.set_inflation / inflated_costmaps).  Out of
+scope: a map in the fixed frame accumulated over time, ray-traced free space, removing the points of detected objects from the point layer, any ROS import.
 """
 import dataclasses
 import math

@@ -750,6 +750,24 @@ struct OccParams {
 };
 void launch_occupancy(const OccParams& p, hipStream_t s);
 
+// inflate.hip: int8 OccupancyGrids -> the grids with every obstacle grown by the robot's radius and a falling cost beyond
+// it (pp_set_inflation, pp_inflate_grids; inflation.py states the rule)
+struct InflParams {
+    int batch, width, height;
+    int R;                         // the inflation radius in cells, <= PP_INFLATE_MAX_RADIUS
+    int lethal, unknown_min;       // pp_inflation_config's lethal_threshold, unknown_min_cost
+    int in_pitch, out_pitch;       // cells of a row of `in`, and of `out` and `dist2`
+    size_t in_stride, out_stride;  // cells from one grid to the next
+    const int8_t* in[2];           // [batch][height * in_pitch]; read, never written
+    const OccCall* occ_call;       // NULL: every grid is in[0]'s.  Else [batch], the records of the occupancy update that
+                                   // wrote the grids: stream b's lies in in[1 - occ_call[b].src]
+    const int8_t* table;           // [R * R + 1] the cost by squared cell distance
+    int8_t* out;                   // [batch][height * out_pitch]
+    uint16_t* dist2;               // the same shape, or NULL: the squared distance, R * R + 1 where nothing is in reach
+    int* counts;                   // [batch][2]: obstacle cells, cells with out != in; cleared before the launch
+};
+void launch_inflate(const InflParams& p, hipStream_t s);
+
 // weight_publish.hip: the trainer's flat parameter / state buffers -> the detector's weight arrays, on the device
 enum PubKind {
     PUB_PFN_W,       // out [FA][cout] = params[src] * scale[c]

@@ -6,7 +6,7 @@
 // api_metrics.hip: the training metrics' counts; api_publish.hip: a trainer's weights into the detector, on the device;
 // api_track.hip: the per-stream track tables behind the detector's post-process; api_sweeps.hip: the per-stream sweep rings
 // in front of the pass; api_costmap.hip: the obstacle grid per frame behind it; api_occupancy.hip: the rolling occupancy
-// map per stream.  pp_ring.h: the pinned call ring and the stages' memory owner, which the handle's members are made of.
+// map per stream; api_inflate.hip: obstacle inflation behind either grid.  pp_ring.h: the pinned call ring and the stages' memory owner, which the handle's members are made of.
 #pragma once
 
 #include <cmath>
@@ -426,6 +426,23 @@ struct pp_engine {
         std::vector<int> cleared;          // pp_occupancy_info: of the stream's last update
         int batch = 0;                     // streams of the last update (pp_get_occupancy; 0: none)
     } occ;
+
+    // pp_set_inflation: the costmap's or the occupancy maps' grids with every obstacle grown by the robot's radius
+    // (api_inflate.hip).  One plain launch on the handle's stream; it reads the source's grid and writes `out` / `dist2`.
+    struct Inflation {
+        bool on = false;                   // pp_set_inflation gave a configuration and has not taken it back
+        pp_inflation_config cfg = {};      // the last configuration given
+        int R = 0;                         // ceil(inflation_radius / resolution)
+        int8_t* table = nullptr;           // [PP_INFLATE_MAX_RADIUS^2 + 1]; this and `counts` live as long as the handle (`allocs`)
+        int* counts = nullptr;             // [B][2]: lethal, raised
+        StageMem mem;                      // owns out and dist2, made by pp_inflate_async for the source's shape: not in `allocs`
+        int8_t* out = nullptr;             // [B * cells]
+        uint16_t* dist2 = nullptr;         // [B * cells]
+        size_t cells = 0;                  // height * pitch the two were allocated for (0: none yet)
+        int batch = 0;                     // grids of the last run (pp_get_inflated; 0: none)
+        int run_pitch = 0, run_w = 0, run_h = 0, run_R = 0;   // ... and their shape
+        std::vector<char> known;           // [batch] of that run; 0: the stream had been reset, its grid reads all unknown
+    } infl[2];                             // by source: PP_INFLATE_COSTMAP, PP_INFLATE_OCCUPANCY
     unsigned long long resident_gen = 0;   // counts the changes of the resident frames (set_resident, a stage call)
     unsigned long long results_gen = 0;    // resident_gen of the last pp_detect_async
 
@@ -587,6 +604,7 @@ void track_release(pp_engine* e);                       // ... what pp_destroy f
 void sweeps_release(pp_engine* e);                      // api_sweeps.hip: what pp_destroy frees of the sweep rings
 void costmap_release(pp_engine* e);                     // api_costmap.hip: what pp_destroy frees of the costmap stage
 void occupancy_release(pp_engine* e);                   // api_occupancy.hip: what pp_destroy frees of the occupancy maps
+void inflate_release(pp_engine* e);                     // api_inflate.hip: what pp_destroy frees of the inflation stage
 int ensure_metrics(pp_engine* e);                       // api_metrics.hip
 void fill_metrics_params(pp_engine* e, int batch, MetricsParams& p);   // ... on the handle's head map and loss.labels
 // ---- api_dataprep.hip: what the fused training steps (api_train.hip) queue ----

@@ -18,6 +18,7 @@ from . import tracking as _trk
 from . import sweeps as _swp
 from . import costmap as _cm
 from . import occupancy as _occ
+from . import inflation as _infl
 from .anchors import build_anchor_cells, build_anchors
 from .config import Derived
 from .weights import check_weights
@@ -421,6 +422,7 @@ class Engine:
         if d.sweeps is not None:
             self.set_sweeps(d.sweeps)
         self._costmap_queued = False                            # a costmap_async whose grids costmaps() has not fetched
+        self._infl_run = {}                                     # source index -> (batch, (H, W)) of its last inflate_async
         if d.costmap is not None:
             self.set_costmap(d.costmap)
         if weights is not None:
@@ -1153,10 +1155,10 @@ class Engine:
             raise ValueError(f"occupancy_update_async: {B} poses, the engine has {self.max_batch} streams")
         P = _swp.check_poses(poses, B)
         c = self.occupancy
-        for b in range(B):
-            _occ.window_origin(c, P[b])
+        cells = [_occ.window_origin(c, P[b]) for b in range(B)]
         self._check(self._lib.pp_occupancy_update_async(self._h, _ptr(P), B), "pp_occupancy_update_async")
         self._occ_batch = B
+        self._occ_origins = np.array(cells, np.float64).reshape(B, 2) * c.resolution      # (pp_get_occupancy's arithmetic)
         self._occ_shape = (c.height, c.width)
 
     def occupancy_maps(self, batch=None, logodds=False):
@@ -1181,6 +1183,102 @@ class Engine:
     def occupancy_reset(self, stream=None):
         """Forgets the map of `stream` (None: of all streams): its next update starts from an unknown window."""
         self._check(self._lib.pp_occupancy_reset(self._h, -1 if stream is None else int(stream)), "pp_occupancy_reset")
+        org = getattr(self, "_occ_origins", None)
+        if org is not None:
+            org[slice(None) if stream is None else slice(int(stream), int(stream) + 1)] = np.nan
+
+    # ---- obstacle inflation behind either grid (pp_set_inflation, pp_inflate_async, pp_get_inflated; inflation.py states the rule; DESIGN 7.1y) ----
+    @staticmethod
+    def _infl_source(source):
+        if source not in _infl.SOURCES:
+            raise ValueError(f"inflation: source must be one of {_infl.SOURCES}, got {source!r}")
+        return _infl.SOURCES.index(source)
+
+    def set_inflation(self, cfg, source="costmap"):
+        """An inflation.InflationConfig, a dict of its fields or True (the defaults) for the grids of `source`, "costmap"
+        or "occupancy": `inflated_costmaps()` / `inflated_occupancy_maps()` then give that stage's grids with every
+        obstacle grown by the inscribed radius and a falling cost up to the inflation radius, computed on the GPU from
+        the grid where it lies; the source's own grids stay as they are.  resolution = 0.0 takes the resolution of the
+        source's configuration in force (the source must be on); any other must equal it when the stage runs.  None: the
+        source's inflation off (the default); its buffers are kept."""
+        k = self._infl_source(source)
+        if cfg is None or cfg is False:
+            self._check(self._lib.pp_set_inflation(self._h, k, None, None, 0), "pp_set_inflation")
+            return
+        c = _infl.InflationConfig.from_any(cfg)
+        if c.resolution == 0.0:
+            src = self.costmap if k == 0 else self.occupancy
+            if src is None:
+                raise RuntimeError(f"set_inflation: resolution = 0.0 stands for the {source} stage's, and that stage is not "
+                                   f"configured (set_{source} first)")
+            c = dataclasses.replace(c, resolution=src.resolution)
+        pc = _to_struct(_lib.PPInflationConfig, c)
+        table = np.ascontiguousarray(_infl.cost_table(c), np.int8)
+        self._check(self._lib.pp_set_inflation(self._h, k, ctypes.byref(pc), _ptr(table), len(table)), "pp_set_inflation")
+
+    def inflation_config(self, source="costmap"):
+        """The InflationConfig in force for `source`, or None while its inflation is off."""
+        k = self._infl_source(source)
+        on, pc = ctypes.c_int32(0), _lib.PPInflationConfig()
+        self._check(self._lib.pp_get_inflation_config(self._h, k, ctypes.byref(on), ctypes.byref(pc)), "pp_get_inflation_config")
+        return _from_struct(_infl.InflationConfig, pc) if on.value else None
+
+    def inflate_async(self, source="costmap"):
+        """Queues the inflation of the grids of the source's last run (costmap_async / occupancy_update_async) behind
+        whatever the engine's stream holds (pp_inflate_async, one launch) and returns at once.  Raises when the source or
+        its inflation is off, the source has not run, or its resolution is not the inflation's."""
+        k = self._infl_source(source)
+        self._check(self._lib.pp_inflate_async(self._h, k), "pp_inflate_async")
+        if k == 0:
+            self._infl_run[k] = (self._costmap_batch, self._costmap_shape)
+        else:
+            self._infl_run[k] = (self._occ_batch, self._occ_shape)
+
+    @staticmethod
+    def _infl_batch(batch, run, who):
+        if batch is not None and run > 0 and int(batch) != run:
+            raise ValueError(f"{who}: the source's run has {run} grids, batch is {int(batch)}")
+
+    def _inflated(self, k, batch, clearance):
+        B0, (H, W) = self._infl_run.get(k, (0, (1, 1)))
+        B = int(batch) if batch is not None else B0
+        grid = np.zeros((max(B, 1), H, W), np.int8)
+        d2 = np.zeros((max(B, 1), H, W), np.uint16) if clearance else None
+        self._check(self._lib.pp_get_inflated(self._h, k, _ptr(grid), _ptr(d2), B), "pp_get_inflated")
+        return grid[:B], (d2[:B] if clearance else None)
+
+    def inflated_costmaps(self, batch=None, clearance=False):
+        """The inflated grids int8 [B, H, W] of the resident frames (waits for them): the costmap stage is queued first if
+        no costmap_async is pending, as `costmaps()` does, then the inflation; the pending run counts as fetched, so a
+        `costmaps()` afterwards runs the stage again on the same frames.  clearance=True: (grids, dist2 uint16 [B, H, W]), the squared cell distance to the nearest
+        obstacle (R * R + 1: none in reach).  A `batch` that is not the run's is refused before anything is queued."""
+        self._infl_batch(batch, self._costmap_batch if self._costmap_queued else self._batches()[0], "inflated_costmaps")
+        if not self._costmap_queued:
+            self.costmap_async()
+        self.inflate_async("costmap")
+        self._costmap_queued = False
+        grid, d2 = self._inflated(0, batch, clearance)
+        return (grid, d2) if clearance else grid
+
+    def inflated_occupancy_maps(self, batch=None, clearance=False):
+        """(grids int8 [B, H, W], origins float64 [B, 2]) of the streams of the last occupancy_update_async, inflated
+        (queues the inflation, waits for it); the origins are those of `occupancy_maps()`.  clearance=True: a third value,
+        dist2 uint16 [B, H, W].  A stream reset since the update reads all unknown with a NaN origin.  A `batch` that is
+        not the update's is refused before anything is queued."""
+        self._infl_batch(batch, getattr(self, "_occ_batch", 0), "inflated_occupancy_maps")
+        self.inflate_async("occupancy")
+        grid, d2 = self._inflated(1, batch, clearance)
+        org = self._occ_origins[:len(grid)].copy()
+        return (grid, org, d2) if clearance else (grid, org)
+
+    def inflation_info(self, source="costmap"):
+        """Per grid of the source's last inflation (waits for it), int32 [B] each: `lethal`, the obstacle cells, and
+        `raised`, the cells the inflation changed."""
+        k = self._infl_source(source)
+        n = self._infl_run.get(k, (0, None))[0]
+        out = {key: np.zeros(max(n, 1), np.int32) for key in ("lethal", "raised")}
+        self._check(self._lib.pp_inflation_info(self._h, k, _ptr(out["lethal"]), _ptr(out["raised"]), n), "pp_inflation_info")
+        return {key: v[:n] for key, v in out.items()}
 
     def _pose_args(self, poses, stamps, batch, who):
         """poses= of a detect*: checked before anything is queued (None: no accumulation); stamps then serve the sweeps, and

@@ -43,7 +43,8 @@ The update reads whatever rows it is given.  On the engine that is the resident 
 the carried rows of past sweeps too, which would cast rays from the CURRENT sensor position -- so the update belongs
 between the upload or ingest and the accumulation.
 
-Out of scope: decay over time, inflation, 3D voxels, removing tracked objects' points, clipping rays that leave the window
+Inflation is a stage of its own behind the published grid (inflation.py, Engine.set_inflation / inflated_occupancy_maps);
+it never feeds back into the log-odds.  Out of scope: decay over time, 3D voxels, removing tracked objects' points, clipping rays that leave the window
 (rows that end outside it are ignored, and counted), any ROS import.
 """
 import dataclasses

@@ -76,6 +76,14 @@ class VoxelNet:
         """Engine.occupancy_maps of the last occupancy_update."""
         return self.engine.occupancy_maps(batch, logodds)
 
+    def inflated_costmaps(self, batch=None, clearance=False):
+        """Engine.inflated_costmaps of the pass that has just run (engine.set_inflation(cfg, "costmap") first)."""
+        return self.engine.inflated_costmaps(batch, clearance)
+
+    def inflated_occupancy_maps(self, batch=None, clearance=False):
+        """Engine.inflated_occupancy_maps of the last occupancy_update (engine.set_inflation(cfg, "occupancy") first)."""
+        return self.engine.inflated_occupancy_maps(batch, clearance)
+
     def _need_p2(self, p2, who):
         if self.d.project_bbox and p2 is None:
             raise ValueError(f"{who}: model.second.project_bbox is on: pass p2 (the frames' camera matrices)")

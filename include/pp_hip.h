@@ -54,7 +54,9 @@ extern "C" {
  * stage reads what a pass and its tracking step leave on the device).  Then PP_OCC_MAX_CELLS, pp_occupancy_config,
  * pp_set_occupancy, pp_get_occupancy_config, pp_occupancy_update_async, pp_get_occupancy, pp_occupancy_info,
  * pp_occupancy_reset (declared behind pp_costmap_info).  Then pp_layer_plan_desc, pp_plan_layer_name (declared behind
- * pp_layer_tag). */
+ * pp_layer_tag).  Then PP_INFLATE_MAX_RADIUS, pp_inflation_config, PP_INFLATE_COSTMAP, PP_INFLATE_OCCUPANCY,
+ * pp_set_inflation, pp_get_inflation_config, pp_inflate_async, pp_get_inflated, pp_inflation_info, pp_inflate_grids
+ * (declared behind pp_occupancy_reset: the stage reads the grid either stage leaves on the device). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -1352,6 +1354,55 @@ int pp_occupancy_info(pp_handle h, int32_t* hits, int32_t* ground, int32_t* igno
 /* stream 0 .. max_batch - 1, or -1 for all: forgets the stream's map; its next update starts from an unknown window.
  * PP_ERR_STATE while a training step is in flight. */
 int pp_occupancy_reset(pp_handle h, int32_t stream);
+
+/* ---- Obstacle inflation behind either grid, and of any int8 OccupancyGrid (inflation.py states the rule): a cell with
+ * g >= lethal_threshold is an obstacle; d2 of a cell is its exact squared Euclidean distance in cells to the nearest
+ * obstacle of the grid, looked for within R = ceil(inflation_radius / resolution) cells (R * R + 1: none in reach);
+ * t = table[d2] (0 for none); a known cell (g >= 0) reads max(g, t), an unknown one t where t >= unknown_min_cost, else
+ * -1.  table[d2], with d = sqrt(d2) * resolution: 100 for d2 = 0, 99 for d <= inscribed_radius,
+ * floor(98 * exp(-cost_scaling_factor * (d - inscribed_radius)) + 0.5) for d <= inflation_radius, else 0.  The device
+ * only looks the table up: integer arithmetic throughout.  An opt-in stage: one plain launch on the handle's stream
+ * whatever the batch, not part of a captured pass. ---- */
+#define PP_INFLATE_MAX_RADIUS 64 /* R, cells */
+
+typedef struct pp_inflation_config {
+    double resolution;           /* metres per cell, > 0: the source's (the table is built for it) */
+    double inscribed_radius;     /* metres, >= 0 */
+    double inflation_radius;     /* metres, >= inscribed_radius; ceil(inflation_radius / resolution) <= PP_INFLATE_MAX_RADIUS */
+    double cost_scaling_factor;  /* 1 / m, > 0 */
+    int32_t lethal_threshold;    /* 1 .. 100 */
+    int32_t unknown_min_cost;    /* 1 .. 100 */
+} pp_inflation_config;
+
+enum { PP_INFLATE_COSTMAP = 0, PP_INFLATE_OCCUPANCY = 1 }; /* `source`: the grids of pp_costmap_async / of the occupancy maps */
+
+/* cfg == NULL: the source's inflation off (the default); its buffers are kept.  Otherwise the configuration is validated
+ * (PP_ERR_ARG naming the field).  table: n_table = R * R + 1 values 0 .. 100 (PP_ERR_ARG otherwise); NULL (n_table
+ * ignored): the table above, computed here on the host.  Waits for the stream.  PP_ERR_STATE while a training step is in
+ * flight. */
+int pp_set_inflation(pp_handle h, int32_t source, const pp_inflation_config* cfg, const int8_t* table, int32_t n_table);
+/* *on: 0 / 1; cfg_out (may be NULL): the last configuration given for the source (zeros before the first). */
+int pp_get_inflation_config(pp_handle h, int32_t source, int32_t* on, pp_inflation_config* cfg_out);
+/* Inflates the grids of the source's last run (pp_costmap_async / pp_occupancy_update_async), all of its frames / streams:
+ * queued behind whatever the handle's stream holds, one launch.  Reads the source's device grid in place (rows of
+ * (width + 3) & ~3 cells) and writes buffers of its own, made here for the source's shape: never the source's grid or
+ * log-odds.  Refused before anything is queued, PP_ERR_STATE: the source's inflation or the source stage is off, the
+ * source has not run, its resolution is not the one the table was built for, a training step is in flight. */
+int pp_inflate_async(pp_handle h, int32_t source);
+/* The grids of the source's last pp_inflate_async (waits for the stream): grid int8 [batch][height][width]; dist2 uint16
+ * of the same shape or NULL, the squared cell distance to the nearest obstacle (R * R + 1: none in reach).  A stream of
+ * the occupancy source that was reset before the call reads all unknown (its origin is pp_get_occupancy's, as every
+ * stream's).  PP_ERR_STATE when none has run, PP_ERR_ARG when batch is not that run's. */
+int pp_get_inflated(pp_handle h, int32_t source, int8_t* grid, uint16_t* dist2, int32_t batch);
+/* Per grid of that run, [batch] each (either may be NULL): obstacle cells, cells the inflation changed.  Errors as
+ * pp_get_inflated. */
+int pp_inflation_info(pp_handle h, int32_t source, int32_t* lethal, int32_t* raised, int32_t batch);
+/* Without a handle: grids int8 [batch][height][width] in host memory (height * width <= PP_OCC_MAX_CELLS, batch <= 65535)
+ * -> out of the same shape, dist2 uint16 of the same shape or NULL, counts int32 [batch][2] (lethal, raised) or NULL.
+ * cfg and table as pp_set_inflation takes them. */
+int pp_inflate_grids(int device, const int8_t* grids, int32_t batch, int32_t height, int32_t width,
+                     const pp_inflation_config* cfg, const int8_t* table, int32_t n_table, int8_t* out, uint16_t* dist2,
+                     int32_t* counts);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
