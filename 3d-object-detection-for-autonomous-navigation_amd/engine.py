@@ -1226,7 +1226,9 @@ class Engine:
     def inflate_async(self, source="costmap"):
         """Queues the inflation of the grids of the source's last run (costmap_async / occupancy_update_async) behind
         whatever the engine's stream holds (pp_inflate_async, one launch) and returns at once.  Raises when the source or
-        its inflation is off, the source has not run, or its resolution is not the inflation's."""
+        its inflation is off, the source has not run, or its resolution is not the inflation's.  It reads the source's
+        grids as they are when it runs: queue it before the next costmap_async / occupancy_update_async to inflate this
+        cycle's grids; the inflated grids then stay while the source runs again, until the next inflate_async of that source."""
         k = self._infl_source(source)
         self._check(self._lib.pp_inflate_async(self._h, k), "pp_inflate_async")
         if k == 0:
