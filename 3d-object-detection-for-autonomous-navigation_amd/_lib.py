@@ -24,6 +24,7 @@ SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_
            "api_costmap.hip", "costmap.hip",
            "api_occupancy.hip", "occupancy.hip",
            "api_inflate.hip", "inflate.hip",
+           "api_navfn.hip", "navfn.hip",
            "api_track.hip", "track.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
@@ -60,6 +61,7 @@ EXPORTS = [
     "pp_occupancy_reset",
     "pp_set_inflation", "pp_get_inflation_config", "pp_inflate_async", "pp_get_inflated", "pp_inflation_info",
     "pp_inflate_grids",
+    "pp_set_navfn", "pp_get_navfn_config", "pp_navfn_async", "pp_get_navfn", "pp_navfn_info", "pp_navfn_grids",
     "pp_set_nms_mode", "pp_get_nms_mode", "pp_rotate_nms",
     "pp_set_projection", "pp_get_projection", "pp_get_bboxes", "pp_box3d_to_bbox",
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
@@ -236,7 +238,9 @@ PP_COSTMAP_MAX_STEPS = 8      # predicted footprints per track (pp_set_costmap)
 PP_COSTMAP_MAX_CELLS = 262144      # width * height of a costmap
 PP_OCC_MAX_CELLS = 1048576      # width * height of an occupancy window (pp_set_occupancy)
 PP_INFLATE_MAX_RADIUS = 64      # cells: ceil(inflation_radius / resolution) at most (pp_set_inflation)
-PP_INFLATE_COSTMAP, PP_INFLATE_OCCUPANCY = 0, 1      # `source` of the pp_*inflat* calls
+PP_INFLATE_COSTMAP, PP_INFLATE_OCCUPANCY = 0, 1      # `source` of the pp_*inflat* calls, and of the pp_*navfn* calls behind them
+PP_NAVFN_UNREACHED = 0xFFFFFFFF # the potential of a cell no chain of moves joins to the goal (pp_get_navfn)
+PP_NAVFN_MAX_PATH = 4096        # cells: pp_navfn_config.max_path at most
 PP_CLIP_NONE, PP_CLIP_VALUE, PP_CLIP_NORM, PP_CLIP_GLOBAL_NORM = 0, 1, 2, 3      # enum pp_grad_clip_mode
 
 
@@ -324,6 +328,19 @@ class PPInflationConfig(ctypes.Structure):
         ("cost_scaling_factor", ctypes.c_double),
         ("lethal_threshold", ctypes.c_int32),
         ("unknown_min_cost", ctypes.c_int32),
+    ]
+
+
+class PPNavfnConfig(ctypes.Structure):
+    _fields_ = [
+        ("lethal_cost", ctypes.c_int32),
+        ("neutral_cost", ctypes.c_int32),
+        ("cost_factor", ctypes.c_int32),
+        ("allow_unknown", ctypes.c_int32),
+        ("unknown_cost", ctypes.c_int32),
+        ("connectivity", ctypes.c_int32),
+        ("max_path", ctypes.c_int32),
+        ("queued_rounds", ctypes.c_int32),
     ]
 
 
@@ -584,6 +601,12 @@ def lib():
     L.pp_get_inflated.argtypes = [vp, i32, vp, vp, i32]
     L.pp_inflation_info.argtypes = [vp, i32, vp, vp, i32]
     L.pp_inflate_grids.argtypes = [ctypes.c_int, vp, i32, i32, i32, ctypes.POINTER(PPInflationConfig), vp, i32, vp, vp, vp]
+    L.pp_set_navfn.argtypes = [vp, i32, ctypes.POINTER(PPNavfnConfig)]
+    L.pp_get_navfn_config.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(PPNavfnConfig)]
+    L.pp_navfn_async.argtypes = [vp, i32, vp, vp, i32]
+    L.pp_get_navfn.argtypes = [vp, i32, vp, vp, vp, i32]
+    L.pp_navfn_info.argtypes = [vp, i32, vp, vp, vp, vp, i32]
+    L.pp_navfn_grids.argtypes = [ctypes.c_int, vp, i32, i32, i32, ctypes.POINTER(PPNavfnConfig), vp, vp, vp, vp, vp, vp]
     L.pp_set_projection.argtypes = [vp, vp, i32]
     L.pp_get_projection.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_get_bboxes.argtypes = [vp, vp]

@@ -768,6 +768,33 @@ struct InflParams {
 };
 void launch_inflate(const InflParams& p, hipStream_t s);
 
+// navfn.hip: int8 OccupancyGrids and one goal cell each -> the cost-to-go field and the path from a start cell
+// (pp_set_navfn, pp_navfn_grids; navfn.py states the rule)
+struct NavCall {                   // what travels from the host per grid and call
+    int gx, gy, sx, sy;            // the goal and the start, cells
+    int flags;                     // NAV_HAS_START; NAV_KNOWN (clear: the grid reads all unknown, whatever it holds)
+};
+constexpr int NAV_HAS_START = 1, NAV_KNOWN = 2;
+// per grid, field-major int [NAV_STATE][state_stride]: the three `changed` slots rotate by round index
+enum { NAV_CHANGED = 0, NAV_ROUNDS = 3, NAV_REACHED = 4, NAV_GOAL_STATE = 5, NAV_PATH_STATE = 6, NAV_PATH_LEN = 7, NAV_STATE = 8 };
+struct NavParams {
+    int batch, width, height;
+    int pitch;                     // cells of a row of `grid`, `cost` and both `pot`
+    size_t stride;                 // cells from one grid to the next in all of them
+    int lethal, neutral, factor, allow_unknown, unknown_cost, conn, max_path;     // pp_navfn_config
+    const int8_t* grid;            // [batch][height * pitch]; read, never written
+    const NavCall* call;           // [batch]
+    uint16_t* cost;                // [batch][height * pitch], 0: blocked
+    unsigned* pot[2];              // the same shape: round r reads pot[r & 1] and writes pot[(r + 1) & 1]
+    int* state;                    // [NAV_STATE][state_stride]
+    int state_stride;
+    int* paths;                    // [batch][max_path][2]
+};
+void launch_navfn_init(const NavParams& p, hipStream_t s);
+void launch_navfn_relax(const NavParams& p, int round, hipStream_t s);       // `round` counts from 0 behind the init
+void launch_navfn_finish(const NavParams& p, int rounds, hipStream_t s);     // after `rounds` rounds; NAV_REACHED cleared before it
+int navfn_tiles(int width, int height, int* tiles_x);                        // workgroups of a round per grid
+
 // weight_publish.hip: the trainer's flat parameter / state buffers -> the detector's weight arrays, on the device
 enum PubKind {
     PUB_PFN_W,       // out [FA][cout] = params[src] * scale[c]

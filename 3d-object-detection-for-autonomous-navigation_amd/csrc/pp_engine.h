@@ -6,7 +6,7 @@
 // api_metrics.hip: the training metrics' counts; api_publish.hip: a trainer's weights into the detector, on the device;
 // api_track.hip: the per-stream track tables behind the detector's post-process; api_sweeps.hip: the per-stream sweep rings
 // in front of the pass; api_costmap.hip: the obstacle grid per frame behind it; api_occupancy.hip: the rolling occupancy
-// map per stream; api_inflate.hip: obstacle inflation behind either grid.  pp_ring.h: the pinned call ring and the stages' memory owner, which the handle's members are made of.
+// map per stream; api_inflate.hip: obstacle inflation behind either grid; api_navfn.hip: the navigation function over the inflated grid.  pp_ring.h: the pinned call ring and the stages' memory owner, which the handle's members are made of.
 #pragma once
 
 #include <cmath>
@@ -443,6 +443,29 @@ struct pp_engine {
         int run_pitch = 0, run_w = 0, run_h = 0, run_R = 0;   // ... and their shape
         std::vector<char> known;           // [batch] of that run; 0: the stream had been reset, its grid reads all unknown
     } infl[2];                             // by source: PP_INFLATE_COSTMAP, PP_INFLATE_OCCUPANCY
+
+    // pp_set_navfn: the cost-to-go field from a goal cell and the path from a start cell over infl[source].out, which it
+    // reads in place and never writes (api_navfn.hip).  Plain launches on the handle's stream: init, relaxation rounds,
+    // finish; the getters queue the rounds still missing.  Nothing of it in PostRule, DetectKey or a captured pass.
+    struct Navfn {
+        bool on = false;                   // pp_set_navfn gave a configuration and has not taken it back
+        pp_navfn_config cfg = {};          // the last configuration given
+        int* state = nullptr;              // [NAV_STATE][B]; this and d_call live as long as the handle (`allocs`)
+        NavCall* d_call = nullptr;         // [B]
+        CallRing ring;                     // the calls' goals and starts, consumed on the main stream
+        RingArray<NavCall> h_call;         // [B] per slot
+        StageMem mem;                      // owns the four buffers below, made by pp_navfn_async for the source's shape: not in `allocs`
+        uint16_t* cost = nullptr;          // [B * cells]
+        unsigned* pot[2] = {nullptr, nullptr};     // [B * cells] each
+        int* paths = nullptr;              // [B][path_cap][2]
+        size_t cells = 0;                  // height * pitch they were allocated for (0: none yet)
+        int path_cap = 0;
+        int batch = 0;                     // grids of the last run (pp_get_navfn; 0: none)
+        NavParams run = {};                // ... what it was launched with
+        int rounds = 0;                    // relaxation rounds queued behind its init so far
+        bool settled = false;              // a getter has seen every grid's field stand, and `host` holds the state words
+        std::vector<int> host;             // [NAV_STATE][B]
+    } navfn[2];                            // by source, as infl
     unsigned long long resident_gen = 0;   // counts the changes of the resident frames (set_resident, a stage call)
     unsigned long long results_gen = 0;    // resident_gen of the last pp_detect_async
 
@@ -605,6 +628,7 @@ void sweeps_release(pp_engine* e);                      // api_sweeps.hip: what 
 void costmap_release(pp_engine* e);                     // api_costmap.hip: what pp_destroy frees of the costmap stage
 void occupancy_release(pp_engine* e);                   // api_occupancy.hip: what pp_destroy frees of the occupancy maps
 void inflate_release(pp_engine* e);                     // api_inflate.hip: what pp_destroy frees of the inflation stage
+void navfn_release(pp_engine* e);                       // api_navfn.hip: what pp_destroy frees of the navigation-function stage
 int ensure_metrics(pp_engine* e);                       // api_metrics.hip
 void fill_metrics_params(pp_engine* e, int batch, MetricsParams& p);   // ... on the handle's head map and loss.labels
 // ---- api_dataprep.hip: what the fused training steps (api_train.hip) queue ----

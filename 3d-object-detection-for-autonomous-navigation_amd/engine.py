@@ -19,12 +19,13 @@ from . import sweeps as _swp
 from . import costmap as _cm
 from . import occupancy as _occ
 from . import inflation as _infl
+from . import navfn as _nav
 from .anchors import build_anchor_cells, build_anchors
 from .config import Derived
 from .weights import check_weights
 
 _STATUS = {1: "PP_ERR_ARG", 2: "PP_ERR_STATE", 3: "PP_ERR_HIP", 4: "PP_ERR_SHAPE", 5: "PP_ERR_UNSUPPORTED",
-           6: "PP_ERR_NUMERIC"}
+           6: "PP_ERR_NUMERIC", 7: "PP_ERR_INTERNAL"}
 PP_ERR_NUMERIC = 6
 _PRECISIONS = {"split_f16": 0, "f32": 1}
 _NMS_MODES = {"standup": _lib.PP_NMS_STANDUP, "rotated": _lib.PP_NMS_ROTATED, "soft": _lib.PP_NMS_SOFT}
@@ -423,6 +424,7 @@ class Engine:
             self.set_sweeps(d.sweeps)
         self._costmap_queued = False                            # a costmap_async whose grids costmaps() has not fetched
         self._infl_run = {}                                     # source index -> (batch, (H, W)) of its last inflate_async
+        self._navfn_run = {}                                    # source index -> (batch, (H, W), max_path, origins, resolution) of its last navfn_async
         if d.costmap is not None:
             self.set_costmap(d.costmap)
         if weights is not None:
@@ -1281,6 +1283,130 @@ class Engine:
         out = {key: np.zeros(max(n, 1), np.int32) for key in ("lethal", "raised")}
         self._check(self._lib.pp_inflation_info(self._h, k, _ptr(out["lethal"]), _ptr(out["raised"]), n), "pp_inflation_info")
         return {key: v[:n] for key, v in out.items()}
+
+    # ---- navigation function behind either inflation (pp_set_navfn, pp_navfn_async, pp_get_navfn; navfn.py states the rule) ----
+    def set_navfn(self, cfg, source="costmap"):
+        """A navfn.NavfnConfig, a dict of its fields or True (the defaults) for the inflated grids of `source`, "costmap" or
+        "occupancy": `navfn_async(goals)` / `plan(goals)` then compute the cost-to-go field from a goal per grid and the
+        path from the sensor's cell (or `starts`) on the GPU, from the inflated grid where it lies; the inflated grids
+        stay as they are.  None: the source's stage off (the default); its buffers are kept."""
+        k = self._infl_source(source)
+        pc = None if cfg is None or cfg is False else ctypes.byref(_to_struct(_lib.PPNavfnConfig, _nav.NavfnConfig.from_any(cfg)))
+        self._check(self._lib.pp_set_navfn(self._h, k, pc), "pp_set_navfn")
+
+    def navfn_config(self, source="costmap"):
+        """The NavfnConfig in force for `source`, or None while its stage is off."""
+        k = self._infl_source(source)
+        on, pc = ctypes.c_int32(0), _lib.PPNavfnConfig()
+        self._check(self._lib.pp_get_navfn_config(self._h, k, ctypes.byref(on), ctypes.byref(pc)), "pp_get_navfn_config")
+        return _from_struct(_nav.NavfnConfig, pc) if on.value else None
+
+    def _navfn_frame(self, k, who):
+        """(batch, (H, W), origins float64 [B, 2], resolution) of the source's last inflation: the grids' frame."""
+        if k not in self._infl_run:
+            raise RuntimeError(f"{who}: no inflation has run on the {_infl.SOURCES[k]} source (inflate_async first)")
+        B, shape = self._infl_run[k]
+        if k == 0:
+            c = self.costmap
+            if c is None:
+                raise RuntimeError(f"{who}: the costmap stage is not configured (set_costmap first)")
+            return B, shape, np.tile(np.array([[c.x_min, c.y_min]], np.float64), (B, 1)), c.resolution
+        c = self.occupancy
+        if c is None:
+            raise RuntimeError(f"{who}: the occupancy stage is not configured (set_occupancy first)")
+        return B, shape, self._occ_origins[:B].copy(), c.resolution
+
+    def _navfn_cells_async(self, k, goals, starts):
+        """pp_navfn_async on cells: goals int32 [B, 2], starts int32 [B, 2] or None (no paths)."""
+        g = np.ascontiguousarray(goals, np.int32)
+        s = None if starts is None else np.ascontiguousarray(starts, np.int32)
+        self._check(self._lib.pp_navfn_async(self._h, k, _ptr(g), _ptr(s), int(g.shape[0])), "pp_navfn_async")
+        c = self.navfn_config(_infl.SOURCES[k])
+        self._navfn_run[k] = (int(g.shape[0]), self._infl_run[k][1], c.max_path, None, None)     # (no frame in metres yet)
+
+    def navfn_async(self, goals, source="costmap", starts=None):
+        """Queues the field and the paths on the grids of the source's last inflation behind whatever the engine's stream
+        holds (pp_navfn_async) and returns at once.  goals float64 [B, 2] (or one (x, y) for every grid), metres in the
+        grids' frame: the sensor frame for the costmap, the fixed frame for the occupancy maps; they become cells through
+        navfn.goal_cells with the run's origins and the source's resolution, so a goal outside a window is no error
+        (goal_state 2).  starts=None: the sensor's own cell -- floor((0 - x_min) / resolution) and likewise in y for the
+        costmap, (W // 2, H // 2) for the occupancy maps; an array like `goals`: those points; False: no paths."""
+        k = self._infl_source(source)
+        B, shape, org, res = self._navfn_frame(k, "navfn_async")
+        G = np.asarray(goals, np.float64)
+        if G.shape not in ((2,), (B, 2)):
+            raise ValueError(f"navfn_async: goals must be metres [{B}, 2] (the inflation run's grids) or one (x, y), got {G.shape}")
+        g = _nav.goal_cells(np.broadcast_to(G, (B, 2)), org, res, shape)
+        if starts is False:
+            s = None
+        elif starts is None:
+            if k == 0:
+                s = _nav.goal_cells(np.zeros((B, 2)), org, res, shape)
+            else:
+                s = np.tile(np.array([[shape[1] // 2, shape[0] // 2]], np.int32), (B, 1))
+        else:
+            S = np.asarray(starts, np.float64)
+            if S.shape not in ((2,), (B, 2)):
+                raise ValueError(f"navfn_async: starts must be metres [{B}, 2] or one (x, y), None or False, got {S.shape}")
+            s = _nav.goal_cells(np.broadcast_to(S, (B, 2)), org, res, shape)
+        self._navfn_cells_async(k, g, s)
+        self._navfn_run[k] = self._navfn_run[k][:3] + (org, res)
+
+    def _navfn_last(self, k, who):
+        if k not in self._navfn_run:
+            raise RuntimeError(f"{who}: no navigation function has run on the {_infl.SOURCES[k]} source (navfn_async first)")
+        return self._navfn_run[k]
+
+    def navfn_fields(self, source="costmap"):
+        """The fields uint32 [B, H, W] of the source's last navfn_async (waits for it, and lets the GPU finish the rounds
+        still missing: always the exact field); navfn.UNREACHED where no chain of moves joins the cell to the goal."""
+        k = self._infl_source(source)
+        B, (H, W), _, _, _ = self._navfn_last(k, "navfn_fields")
+        pot = np.zeros((B, H, W), np.uint32)
+        self._check(self._lib.pp_get_navfn(self._h, k, _ptr(pot), None, None, B), "pp_get_navfn")
+        return pot
+
+    def navfn_paths(self, source="costmap", metres=False):
+        """(paths, path_state int32 [B]) of the source's last navfn_async (waits as navfn_fields does): a list of B arrays
+        int32 [n, 2] of cells (x, y), start and goal included; metres=True: float64 [n, 2], the cells' centres in the
+        grids' frame (navfn.path_to_metres).  path_state as navfn.py lists it."""
+        k = self._infl_source(source)
+        B, _, cap, org, res = self._navfn_last(k, "navfn_paths")
+        paths = np.zeros((B, cap, 2), np.int32)
+        n = np.zeros(B, np.int32)
+        self._check(self._lib.pp_get_navfn(self._h, k, None, _ptr(paths), _ptr(n), B), "pp_get_navfn")
+        state = self.navfn_info(source)["path_state"]
+        out = [paths[b, :n[b]].copy() for b in range(B)]
+        if metres:
+            if org is None:
+                raise RuntimeError("navfn_paths: the run was given cells, it has no frame in metres")
+            out = [_nav.path_to_metres(p, org[b], res) for b, p in enumerate(out)]
+        return out, state
+
+    def navfn_info(self, source="costmap"):
+        """Per grid of the source's last navfn_async (waits as navfn_fields does), int32 [B] each: `goal_state`,
+        `path_state`, `rounds` (relaxation rounds the GPU ran) and `reached` (cells the field reaches)."""
+        k = self._infl_source(source)
+        n = self._navfn_run.get(k, (0,))[0]
+        out = {key: np.zeros(max(n, 1), np.int32) for key in ("goal_state", "path_state", "rounds", "reached")}
+        self._check(self._lib.pp_navfn_info(self._h, k, *(_ptr(v) for v in out.values()), n), "pp_navfn_info")
+        return {key: v[:n] for key, v in out.items()}
+
+    def plan(self, goals, source="costmap", starts=None):
+        """(paths in metres, path_state int32 [B]) to `goals` (as navfn_async takes them).  "costmap": the costmap stage is
+        queued first if no costmap_async is pending, exactly as `inflated_costmaps()` does, then the inflation, then the
+        field and the paths.  "occupancy": the inflation and this stage are queued behind the caller's
+        occupancy_update_async.  Only the paths travel to the host."""
+        k = self._infl_source(source)
+        if k == 0:
+            if not self._costmap_queued:
+                self.costmap_async()
+            self.inflate_async("costmap")
+            self._costmap_queued = False
+        else:
+            self.inflate_async("occupancy")
+        self.navfn_async(goals, source, starts)
+        return self.navfn_paths(source, metres=True)
 
     def _pose_args(self, poses, stamps, batch, who):
         """poses= of a detect*: checked before anything is queued (None: no accumulation); stamps then serve the sweeps, and

@@ -84,6 +84,11 @@ class VoxelNet:
         """Engine.inflated_occupancy_maps of the last occupancy_update (engine.set_inflation(cfg, "occupancy") first)."""
         return self.engine.inflated_occupancy_maps(batch, clearance)
 
+    def plan(self, goals, source="costmap", starts=None):
+        """Engine.plan: the paths in metres to `goals` over the inflated grids of the pass that has just run, or of the
+        last occupancy_update (engine.set_inflation and engine.set_navfn for that source first)."""
+        return self.engine.plan(goals, source, starts)
+
     def _need_p2(self, p2, who):
         if self.d.project_bbox and p2 is None:
             raise ValueError(f"{who}: model.second.project_bbox is on: pass p2 (the frames' camera matrices)")

@@ -56,7 +56,10 @@ extern "C" {
  * pp_occupancy_reset (declared behind pp_costmap_info).  Then pp_layer_plan_desc, pp_plan_layer_name (declared behind
  * pp_layer_tag).  Then PP_INFLATE_MAX_RADIUS, pp_inflation_config, PP_INFLATE_COSTMAP, PP_INFLATE_OCCUPANCY,
  * pp_set_inflation, pp_get_inflation_config, pp_inflate_async, pp_get_inflated, pp_inflation_info, pp_inflate_grids
- * (declared behind pp_occupancy_reset: the stage reads the grid either stage leaves on the device). */
+ * (declared behind pp_occupancy_reset: the stage reads the grid either stage leaves on the device).  Then
+ * PP_ERR_INTERNAL, PP_NAVFN_UNREACHED, PP_NAVFN_MAX_PATH, pp_navfn_config, pp_set_navfn, pp_get_navfn_config,
+ * pp_navfn_async, pp_get_navfn, pp_navfn_info, pp_navfn_grids (declared behind pp_inflate_grids: the stage reads the
+ * inflated grid where it lies). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -66,7 +69,8 @@ enum pp_status {
     PP_ERR_HIP = 3,    /* a HIP runtime call failed (see pp_last_error) */
     PP_ERR_SHAPE = 4,  /* tensor shape does not match the configuration */
     PP_ERR_UNSUPPORTED = 5,
-    PP_ERR_NUMERIC = 6 /* non-finite head outputs: pp_get_detections / pp_detect / pp_predict never hand out NaN boxes */
+    PP_ERR_NUMERIC = 6, /* non-finite head outputs: pp_get_detections / pp_detect / pp_predict never hand out NaN boxes */
+    PP_ERR_INTERNAL = 7 /* a bound the library proves was passed all the same (pp_get_navfn: more rounds than cells) */
 };
 
 /* GEMM arithmetic of the backbone (pp_set_gemm_precision) */
@@ -1403,6 +1407,61 @@ int pp_inflation_info(pp_handle h, int32_t source, int32_t* lethal, int32_t* rai
 int pp_inflate_grids(int device, const int8_t* grids, int32_t batch, int32_t height, int32_t width,
                      const pp_inflation_config* cfg, const int8_t* table, int32_t n_table, int8_t* out, uint16_t* dist2,
                      int32_t* counts);
+
+/* ---- Navigation function behind either inflation, and of any int8 OccupancyGrid (navfn.py states the rule): the
+ * cost-to-go field from one goal cell per grid and the path that descends it from one start cell.  Cell cost c uint16, 0 =
+ * blocked: g >= lethal_cost is blocked; an unknown cell is blocked unless allow_unknown, then c = neutral_cost +
+ * cost_factor * unknown_cost; else c = neutral_cost + cost_factor * g.  Orthogonal moves weigh 5, diagonal ones
+ * (connectivity 8) 7, and a diagonal move needs both cells beside it unblocked.  pot(goal) = 0; pot(p) = min over
+ * admissible reached neighbours q of pot(q) + w * c(p); PP_NAVFN_UNREACHED elsewhere.  The ranges below bound c by
+ * 50 + 5 * 100 = 550 and a step by 7 * 550 = 3850, and 3850 * PP_OCC_MAX_CELLS < 2^32 - 1: a uint32 potential cannot
+ * overflow on any grid these calls admit.  Integer arithmetic throughout; the field is the unique fixed point of the
+ * relaxation, so the number of rounds never shows in a result.  An opt-in stage: plain launches on the handle's stream,
+ * not part of a captured pass. ---- */
+#define PP_NAVFN_UNREACHED 0xFFFFFFFFu
+#define PP_NAVFN_MAX_PATH 4096 /* cells */
+
+typedef struct pp_navfn_config {
+    int32_t lethal_cost;    /* 1 .. 100 */
+    int32_t neutral_cost;   /* 1 .. 50 */
+    int32_t cost_factor;    /* 0 .. 5 */
+    int32_t allow_unknown;  /* 0 / 1 */
+    int32_t unknown_cost;   /* 0 .. 100 */
+    int32_t connectivity;   /* 4 / 8 */
+    int32_t max_path;       /* 1 .. PP_NAVFN_MAX_PATH: cells a returned path may hold */
+    int32_t queued_rounds;  /* 0 .. 4096: relaxation rounds pp_navfn_async queues (0: a default from the grid's shape);
+                             * timing only, never a result */
+} pp_navfn_config;
+
+/* cfg == NULL: the source's stage off (the default); its buffers are kept.  Otherwise the configuration is validated
+ * (PP_ERR_ARG naming the field).  `source` is the inflation's: PP_INFLATE_COSTMAP / PP_INFLATE_OCCUPANCY.  Waits for the
+ * stream.  PP_ERR_STATE while a training step is in flight. */
+int pp_set_navfn(pp_handle h, int32_t source, const pp_navfn_config* cfg);
+/* *on: 0 / 1; cfg_out (may be NULL): the last configuration given for the source (zeros before the first). */
+int pp_get_navfn_config(pp_handle h, int32_t source, int32_t* on, pp_navfn_config* cfg_out);
+/* Queues the field and the paths on the grids of the source's last pp_inflate_async behind whatever the handle's stream
+ * holds: goals int32 [batch][2] cells (x, y); starts likewise, or NULL (no paths, path_state 4).  Reads the inflated
+ * grid in place and never writes it; a stream reset before that inflation reads all unknown.  Queues queued_rounds
+ * relaxation rounds and returns; the getters queue what is still missing.  Refused before anything is queued,
+ * PP_ERR_STATE: the stage or the source's inflation is off, that inflation has not run, a training step is in flight;
+ * PP_ERR_ARG: a batch that is not the inflation run's, goals NULL, a bad source. */
+int pp_navfn_async(pp_handle h, int32_t source, const int32_t* goals, const int32_t* starts, int32_t batch);
+/* The results of the source's last pp_navfn_async (waits for the stream, and runs further relaxation rounds until every
+ * grid's field stands: always the exact field).  pot uint32 [batch][height][width]; paths int32 [batch][max_path][2]
+ * cells (x, y) and path_len int32 [batch]; each may be NULL.  PP_ERR_STATE when none has run, PP_ERR_ARG when batch is
+ * not that run's, PP_ERR_INTERNAL should height * width rounds not suffice (they provably do). */
+int pp_get_navfn(pp_handle h, int32_t source, uint32_t* pot, int32_t* paths, int32_t* path_len, int32_t batch);
+/* Per grid of that run, [batch] each (any may be NULL): goal_state 0 ok / 1 blocked / 2 outside; path_state 0 reached /
+ * 1 start unreached or blocked / 2 start outside / 3 cut at max_path / 4 no start; relaxation rounds run; cells reached.
+ * Errors as pp_get_navfn. */
+int pp_navfn_info(pp_handle h, int32_t source, int32_t* goal_state, int32_t* path_state, int32_t* rounds,
+                  int32_t* reached, int32_t batch);
+/* Without a handle: grids int8 [batch][height][width] in host memory (height * width <= PP_OCC_MAX_CELLS, batch <= 65535),
+ * goals and starts as above -> pot, paths, path_len as pp_get_navfn gives them (each may be NULL) and info int32
+ * [4][batch] or NULL: goal_state, path_state, rounds, reached. */
+int pp_navfn_grids(int device, const int8_t* grids, int32_t batch, int32_t height, int32_t width,
+                   const pp_navfn_config* cfg, const int32_t* goals, const int32_t* starts, uint32_t* pot, int32_t* paths,
+                   int32_t* path_len, int32_t* info);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
