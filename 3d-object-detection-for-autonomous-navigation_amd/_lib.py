@@ -25,6 +25,7 @@ SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_
            "api_occupancy.hip", "occupancy.hip",
            "api_inflate.hip", "inflate.hip",
            "api_navfn.hip", "navfn.hip",
+           "api_local_plan.hip", "local_plan.hip",
            "api_track.hip", "track.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
@@ -62,6 +63,7 @@ EXPORTS = [
     "pp_set_inflation", "pp_get_inflation_config", "pp_inflate_async", "pp_get_inflated", "pp_inflation_info",
     "pp_inflate_grids",
     "pp_set_navfn", "pp_get_navfn_config", "pp_navfn_async", "pp_get_navfn", "pp_navfn_info", "pp_navfn_grids",
+    "pp_set_local_plan", "pp_get_local_plan_config", "pp_local_plan_async", "pp_get_local_plan", "pp_local_plan_grids",
     "pp_set_nms_mode", "pp_get_nms_mode", "pp_rotate_nms",
     "pp_set_projection", "pp_get_projection", "pp_get_bboxes", "pp_box3d_to_bbox",
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
@@ -241,6 +243,12 @@ PP_INFLATE_MAX_RADIUS = 64      # cells: ceil(inflation_radius / resolution) at 
 PP_INFLATE_COSTMAP, PP_INFLATE_OCCUPANCY = 0, 1      # `source` of the pp_*inflat* calls, and of the pp_*navfn* calls behind them
 PP_NAVFN_UNREACHED = 0xFFFFFFFF # the potential of a cell no chain of moves joins to the goal (pp_get_navfn)
 PP_NAVFN_MAX_PATH = 4096        # cells: pp_navfn_config.max_path at most
+PP_LOCAL_SUB = 1024             # sub-cells per cell: the unit of a pose's X and Y (pp_local_plan_async)
+PP_LOCAL_HEADINGS = 4096        # heading ticks per revolution
+PP_LOCAL_MAX_SAMPLES = 16384    # pp_local_plan_config.nv * nw at most
+PP_LOCAL_MAX_STEPS = 256        # pp_local_plan_config.steps at most
+PP_LOCAL_MAX_LOOKAHEAD = 16384  # sub-cells: pp_local_plan_config.lookahead at most
+PP_LOCAL_RESULT = 8             # int32 words per grid of pp_get_local_plan's result
 PP_CLIP_NONE, PP_CLIP_VALUE, PP_CLIP_NORM, PP_CLIP_GLOBAL_NORM = 0, 1, 2, 3      # enum pp_grad_clip_mode
 
 
@@ -341,6 +349,19 @@ class PPNavfnConfig(ctypes.Structure):
         ("connectivity", ctypes.c_int32),
         ("max_path", ctypes.c_int32),
         ("queued_rounds", ctypes.c_int32),
+    ]
+
+
+class PPLocalPlanConfig(ctypes.Structure):
+    _fields_ = [
+        ("nv", ctypes.c_int32),
+        ("nw", ctypes.c_int32),
+        ("steps", ctypes.c_int32),
+        ("lookahead", ctypes.c_int32),
+        ("pot_weight", ctypes.c_int32),
+        ("occ_weight", ctypes.c_int32),
+        ("speed_weight", ctypes.c_int32),
+        ("turn_weight", ctypes.c_int32),
     ]
 
 
@@ -607,6 +628,12 @@ def lib():
     L.pp_get_navfn.argtypes = [vp, i32, vp, vp, vp, i32]
     L.pp_navfn_info.argtypes = [vp, i32, vp, vp, vp, vp, i32]
     L.pp_navfn_grids.argtypes = [ctypes.c_int, vp, i32, i32, i32, ctypes.POINTER(PPNavfnConfig), vp, vp, vp, vp, vp, vp]
+    L.pp_set_local_plan.argtypes = [vp, i32, ctypes.POINTER(PPLocalPlanConfig), vp, i32]
+    L.pp_get_local_plan_config.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(PPLocalPlanConfig)]
+    L.pp_local_plan_async.argtypes = [vp, i32, vp, vp, i32]
+    L.pp_get_local_plan.argtypes = [vp, i32, vp, vp, vp, vp, i32]
+    L.pp_local_plan_grids.argtypes = [ctypes.c_int, vp, vp, i32, i32, i32, ctypes.POINTER(PPNavfnConfig),
+                                      ctypes.POINTER(PPLocalPlanConfig), vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.pp_set_projection.argtypes = [vp, vp, i32]
     L.pp_get_projection.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_get_bboxes.argtypes = [vp, vp]

@@ -1,0 +1,299 @@
+// C-ABI, local planner (pp_set_local_plan, pp_get_local_plan_config, pp_local_plan_async, pp_get_local_plan,
+// pp_local_plan_grids): the inflated int8 grid a source's inflation leaves on the device and the cost-to-go field its
+// navigation function leaves there -> one (v, w) command per grid from a window of rollouts (kernels: local_plan.hip; the
+// rule: local_planner.py).  A stage behind either navigation function: rollout and finish as plain launches on the
+// handle's stream.  pp_navfn_async returns before the relaxation has converged and only navfn's getters settle it, so
+// pp_local_plan_async queues its two launches behind the rounds already queued, and pp_get_local_plan first runs navfn's
+// settled_run on the source: if that queued any further round, rollout and finish are queued again.  A fetched command
+// therefore always rests on the exact field, whatever queued_rounds says.  The poses and windows travel from the host on
+// every call and are consumed on the main stream: a call ring of the stage's own (pp_ring.h).  pp_local_plan_grids needs
+// no handle: host buffers in, host buffers out, device memory for the call's duration.
+#include "pp_engine.h"
+
+static_assert(sizeof(pp_local_plan_config) == 32, "pp_local_plan_config: 8 int32 (the Python binding mirrors it)");
+static_assert(sizeof(LocalCall) == 32, "LocalCall: 8 int32, packed by the host per grid");
+static_assert(PP_LOCAL_SUB == 1024 && PP_LOCAL_HEADINGS == 4096, "sub-cells per cell, ticks per revolution");
+static_assert(PP_LOCAL_RESULT == LOC_STATE, "a grid's result words are its state fields");
+static_assert(PP_INFLATE_COSTMAP == 0 && PP_INFLATE_OCCUPANCY == 1, "pp_engine::local is indexed by source, as navfn");
+
+namespace {
+
+constexpr int LOC_MAX_SV = 1024, LOC_MAX_SW = 512, LOC_TRIG_ONE = 16384;
+
+const char* source_name(int source) { return source == PP_INFLATE_COSTMAP ? "costmap" : "occupancy"; }
+
+// Everything pp_set_local_plan and pp_local_plan_grids refuse of a configuration, by field name.  The ranges are what
+// keeps a score below 2^41 (local_plan.hip).
+int check_config(pp_engine* e, const char* who, const pp_local_plan_config& c) {
+    const struct { const char* name; int v, lo, hi; } f[] = {
+        {"nv", c.nv, 1, PP_LOCAL_MAX_SAMPLES}, {"nw", c.nw, 1, PP_LOCAL_MAX_SAMPLES}, {"steps", c.steps, 1, PP_LOCAL_MAX_STEPS},
+        {"lookahead", c.lookahead, 0, PP_LOCAL_MAX_LOOKAHEAD}, {"pot_weight", c.pot_weight, 0, 255},
+        {"occ_weight", c.occ_weight, 0, 65535}, {"speed_weight", c.speed_weight, 0, 65535}, {"turn_weight", c.turn_weight, 0, 65535}};
+    for (const auto& x : f)
+        if (x.v < x.lo || x.v > x.hi) return fail(e, PP_ERR_ARG, "%s: %s = %d outside [%d, %d]", who, x.name, x.v, x.lo, x.hi);
+    if ((long long)c.nv * c.nw > PP_LOCAL_MAX_SAMPLES)
+        return fail(e, PP_ERR_ARG, "%s: nv * nw = %lld samples, at most PP_LOCAL_MAX_SAMPLES = %d", who, (long long)c.nv * c.nw, PP_LOCAL_MAX_SAMPLES);
+    return PP_OK;
+}
+
+int check_source(pp_engine* e, const char* who, int source) {
+    if (source != PP_INFLATE_COSTMAP && source != PP_INFLATE_OCCUPANCY)
+        return fail(e, PP_ERR_ARG, "%s: source = %d (0 PP_INFLATE_COSTMAP, 1 PP_INFLATE_OCCUPANCY)", who, source);
+    return PP_OK;
+}
+
+// trig int32 [n_trig][2] = (C, S) -> a word per tick, C in the low half
+int pack_trig(pp_engine* e, const char* who, const int32_t* trig, int n_trig, std::vector<unsigned>& out) {
+    if (!trig) return fail(e, PP_ERR_ARG, "%s: trig is NULL", who);
+    if (n_trig != PP_LOCAL_HEADINGS) return fail(e, PP_ERR_ARG, "%s: the trig table has %d entries, it must have PP_LOCAL_HEADINGS = %d", who, n_trig, PP_LOCAL_HEADINGS);
+    out.resize((size_t)PP_LOCAL_HEADINGS);
+    for (int h = 0; h < PP_LOCAL_HEADINGS; ++h) {
+        const int c = trig[2 * h], s = trig[2 * h + 1];
+        if (c < -LOC_TRIG_ONE || c > LOC_TRIG_ONE || s < -LOC_TRIG_ONE || s > LOC_TRIG_ONE)
+            return fail(e, PP_ERR_ARG, "%s: trig[%d] = (%d, %d) outside [-%d, %d]", who, h, c, s, LOC_TRIG_ONE, LOC_TRIG_ONE);
+        out[(size_t)h] = ((unsigned)c & 0xFFFFu) | ((unsigned)s << 16);
+    }
+    return PP_OK;
+}
+
+// the calls' records, and what is refused of a window: every sample within |sv| <= 1024 and |sw| <= 512 (the extremes of
+// a window are its first and last sample).  `call` may be NULL: check only.
+int fill_calls(pp_engine* e, const char* who, LocalCall* call, const pp_local_plan_config& cfg, const int32_t* poses,
+               const int32_t* windows, const int32_t* goal_state, int batch) {
+    for (int b = 0; b < batch; ++b) {
+        const long long v0 = windows[4 * b], dv = windows[4 * b + 1], w0 = windows[4 * b + 2], dw = windows[4 * b + 3];
+        const long long v1 = v0 + (cfg.nv - 1) * dv, w1 = w0 + (cfg.nw - 1) * dw;
+        if (std::max(std::llabs(v0), std::llabs(v1)) > LOC_MAX_SV)
+            return fail(e, PP_ERR_ARG, "%s: windows: grid %d: sv runs from %lld to %lld, outside [-%d, %d]", who, b, v0, v1, LOC_MAX_SV, LOC_MAX_SV);
+        if (std::max(std::llabs(w0), std::llabs(w1)) > LOC_MAX_SW)
+            return fail(e, PP_ERR_ARG, "%s: windows: grid %d: sw runs from %lld to %lld, outside [-%d, %d]", who, b, w0, w1, LOC_MAX_SW, LOC_MAX_SW);
+        if (!call) continue;
+        LocalCall& c = call[b];
+        c.X = poses[3 * b]; c.Y = poses[3 * b + 1]; c.h = poses[3 * b + 2] & (PP_LOCAL_HEADINGS - 1);
+        c.v0 = (int)v0; c.dv = (int)dv; c.w0 = (int)w0; c.dw = (int)dw;
+        c.flags = goal_state && goal_state[b] != 0 ? LOC_NO_GOAL : 0;
+    }
+    return PP_OK;
+}
+
+void fill_config(LocalParams& p, const pp_local_plan_config& c) {
+    p.nv = c.nv; p.nw = c.nw; p.steps = c.steps; p.lookahead = c.lookahead;
+    p.pot_w = c.pot_weight; p.occ_w = c.occ_weight; p.speed_w = c.speed_weight; p.turn_w = c.turn_weight;
+}
+
+// the reason counts cleared, rollout, finish behind whatever `s` holds
+int queue_run(pp_engine* e, const LocalParams& p, hipStream_t s) {
+    HIPCHK(e, hipMemsetAsync(p.state + (size_t)LOC_N_OK * p.state_stride, 0, (size_t)4 * p.state_stride * sizeof(int), s));
+    launch_local_rollout(p, s);
+    launch_local_finish(p, s);
+    HIPCHK(e, hipGetLastError());
+    return PP_OK;
+}
+
+// the source's navigation function has run and the inflated grids it read still lie where they lay
+int check_navfn_run(pp_engine* e, const char* who, int source) {
+    const pp_engine::Navfn& g = e->navfn[source];
+    const pp_engine::Inflation& in = e->infl[source];
+    const NavParams& r = g.run;
+    if (in.out != r.grid || in.cells != r.stride || in.run_w != r.width || in.run_h != r.height || in.run_pitch != r.pitch || in.batch < g.batch)
+        return fail(e, PP_ERR_STATE, "%s: the inflated grids of the %s source were re-made since its navigation function ran "
+                    "(pp_navfn_async again)", who, source_name(source));
+    return PP_OK;
+}
+
+}  // namespace
+
+void local_plan_release(pp_engine* e) {
+    for (pp_engine::LocalPlan& g : e->local) {
+        g.mem.release();
+        g.ring.release();
+        g = pp_engine::LocalPlan();
+    }
+}
+
+extern "C" {
+
+int pp_set_local_plan(pp_handle e, int32_t source, const pp_local_plan_config* cfg, const int32_t* trig, int32_t n_trig) {
+    if (!e) return PP_ERR_ARG;
+    const char* who = "pp_set_local_plan";
+    if (int st = check_source(e, who, source)) return st;
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "%s: a training step is in flight", who);
+    pp_engine::LocalPlan& g = e->local[source];
+    if (!cfg) { g.on = false; return PP_OK; }
+    const pp_local_plan_config c = *cfg;
+    if (int st = check_config(e, who, c)) return st;
+    std::vector<unsigned> packed;
+    if (int st = pack_trig(e, who, trig, n_trig, packed)) return st;
+    (void)hipSetDevice(e->device);
+    HIPCHK(e, hipStreamSynchronize(e->stream));          // a run in flight reads the table to its end
+    HIPCHK(e, g.h_call.alloc(g.ring, (size_t)e->B));
+    if (!g.d_call) {
+        DevAlloc A{e};
+        A(&g.trig, (size_t)PP_LOCAL_HEADINGS); A(&g.state, (size_t)LOC_STATE * e->B); A(&g.partial, (size_t)LOC_MAX_CHUNKS * e->B);
+        A(&g.score, (size_t)e->B); A(&g.d_call, (size_t)e->B);                    // (d_call last: the ready flag)
+        if (A.st) return A.st;
+    }
+    HIPCHK(e, hipMemcpy(g.trig, packed.data(), packed.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+    g.cfg = c;
+    g.on = true;
+    return PP_OK;
+}
+
+int pp_get_local_plan_config(pp_handle e, int32_t source, int32_t* on, pp_local_plan_config* cfg_out) {
+    if (!e || !on) return PP_ERR_ARG;
+    if (int st = check_source(e, "pp_get_local_plan_config", source)) return st;
+    *on = e->local[source].on ? 1 : 0;
+    if (cfg_out) *cfg_out = e->local[source].cfg;
+    return PP_OK;
+}
+
+int pp_local_plan_async(pp_handle e, int32_t source, const int32_t* poses, const int32_t* windows, int32_t batch) {
+    if (!e) return PP_ERR_ARG;
+    const char* who = "pp_local_plan_async";
+    if (int st = check_source(e, who, source)) return st;
+    if (!poses || !windows) return fail(e, PP_ERR_ARG, "%s: poses or windows is NULL", who);
+    pp_engine::LocalPlan& g = e->local[source];
+    const pp_engine::Navfn& nav = e->navfn[source];
+    const char* name = source_name(source);
+    if (!g.on) return fail(e, PP_ERR_STATE, "%s: the local planner of the %s source is not configured (pp_set_local_plan first)", who, name);
+    if (!nav.on) return fail(e, PP_ERR_STATE, "%s: the navigation function of the %s source is not configured (pp_set_navfn first)", who, name);
+    if (int st = check_last_run(e, who, nav.pot[0] ? nav.batch : 0, batch, false, "no navigation function has run on this source (pp_navfn_async first)",
+                                "navigation function", "grids")) return st;
+    if (int st = check_navfn_run(e, who, source)) return st;
+    if (int st = fill_calls(e, who, nullptr, g.cfg, poses, windows, nullptr, batch)) return st;
+    const int samples = g.cfg.nv * g.cfg.nw;
+    (void)hipSetDevice(e->device);
+    if (samples > g.samples_cap || g.cfg.steps > g.steps_cap) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));      // a run in flight writes the old buffers to its end
+        g.mem.release();
+        g.samples_cap = 0; g.steps_cap = 0; g.batch = 0;
+        StageMem& M = g.mem;
+        M(&g.keys, (size_t)e->B * samples); M(&g.traj, (size_t)e->B * (g.cfg.steps + 1) * 3);
+        if (hipError_t st = M.failed()) {
+            (void)hipGetLastError();
+            return fail(e, PP_ERR_HIP, "%s: %d grids x %d samples and %d steps need %zu bytes of device memory and the device cannot "
+                        "hold them (%s)", who, e->B, samples, g.cfg.steps, (size_t)e->B * ((size_t)samples * 8 + (size_t)(g.cfg.steps + 1) * 12),
+                        hipGetErrorString(st));
+        }
+        g.samples_cap = samples; g.steps_cap = g.cfg.steps;
+    }
+    int slot;
+    HIPCHK(e, g.ring.take(&slot));                       // behind the last check that can refuse
+    (void)fill_calls(e, who, g.h_call.at(slot), g.cfg, poses, windows, nullptr, batch);
+    const NavParams& r = nav.run;
+    LocalParams p;
+    memset(&p, 0, sizeof(p));
+    p.batch = batch; p.width = r.width; p.height = r.height; p.pitch = r.pitch; p.stride = r.stride;
+    p.lethal = r.lethal; p.allow_unknown = r.allow_unknown; p.unknown_cost = r.unknown_cost;
+    fill_config(p, g.cfg);
+    p.grid = r.grid; p.pot = r.pot[nav.rounds & 1]; p.nav_call = r.call; p.nav_state = r.state; p.nav_state_stride = r.state_stride;
+    p.call = g.d_call; p.trig = g.trig; p.partial = g.partial;
+    p.state = g.state; p.state_stride = e->B; p.score = g.score; p.traj = g.traj;
+    p.keys = nullptr;                                    // stored when a getter asks for them
+    prof_reset(e);
+    HIPCHK(e, g.h_call.send(slot, g.d_call, (size_t)batch, e->stream));
+    HIPCHK(e, g.ring.sent(slot, e->stream));
+    {
+        ProfScope ps(e, nullptr);
+        if (int st = queue_run(e, p, e->stream)) return st;
+    }
+    g.batch = batch; g.run = p; g.nav_run = nav.run_id; g.nav_rounds = nav.rounds;
+    return PP_OK;
+}
+
+int pp_get_local_plan(pp_handle e, int32_t source, int32_t* result, uint64_t* score, int32_t* traj, uint64_t* keys, int32_t batch) {
+    if (!e) return PP_ERR_ARG;
+    const char* who = "pp_get_local_plan";
+    if (int st = check_source(e, who, source)) return st;
+    pp_engine::LocalPlan& g = e->local[source];
+    if (int st = check_last_run(e, who, g.batch, batch, false, "no local plan has run on this source (pp_local_plan_async first)",
+                                "run", "grids")) return st;
+    if (g.nav_run != e->navfn[source].run_id)
+        return fail(e, PP_ERR_STATE, "%s: a pp_navfn_async of the %s source came after the last pp_local_plan_async (pp_local_plan_async again)",
+                    who, source_name(source));
+    pp_engine::Navfn* nav = nullptr;
+    if (int st = settled_run(e, who, source, batch, &nav)) return st;
+    LocalParams& p = g.run;
+    if (nav->rounds != g.nav_rounds || (keys && !p.keys)) {      // the field moved on behind the launches, or no keys yet: again
+        if (int st = check_navfn_run(e, who, source)) return st;
+        p.pot = nav->run.pot[nav->rounds & 1];
+        if (keys) p.keys = g.keys;
+        prof_reset(e);
+        ProfScope ps(e, nullptr);
+        if (int st = queue_run(e, p, e->stream)) return st;
+        g.nav_rounds = nav->rounds;
+    }
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const size_t ss = (size_t)p.state_stride;
+    if (result) {
+        std::vector<int> host((size_t)LOC_STATE * ss);
+        HIPCHK(e, hipMemcpy(host.data(), p.state, host.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int b = 0; b < batch; ++b)
+            for (int k = 0; k < LOC_STATE; ++k) result[(size_t)b * PP_LOCAL_RESULT + k] = host[(size_t)k * ss + b];
+    }
+    if (score) HIPCHK(e, hipMemcpy(score, p.score, (size_t)batch * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (traj) HIPCHK(e, hipMemcpy(traj, p.traj, (size_t)batch * (p.steps + 1) * 3 * sizeof(int), hipMemcpyDeviceToHost));
+    if (keys) HIPCHK(e, hipMemcpy(keys, p.keys, (size_t)batch * p.nv * p.nw * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PP_OK;
+}
+
+int pp_local_plan_grids(int device, const int8_t* grids, const uint32_t* pots, int32_t batch, int32_t height, int32_t width,
+                        const pp_navfn_config* navfn_cfg, const pp_local_plan_config* cfg, const int32_t* trig, int32_t n_trig,
+                        const int32_t* poses, const int32_t* windows, const int32_t* goal_state, int32_t* result, uint64_t* score,
+                        int32_t* traj, uint64_t* keys) {
+    const char* who = "pp_local_plan_grids";
+    if (!grids || !pots || !navfn_cfg || !cfg) return fail(nullptr, PP_ERR_ARG, "%s: grids, pots, navfn_cfg or cfg is NULL", who);
+    if (!poses || !windows) return fail(nullptr, PP_ERR_ARG, "%s: poses or windows is NULL", who);
+    if (batch < 1 || batch > 65535) return fail(nullptr, PP_ERR_ARG, "%s: batch = %d outside [1, 65535]", who, batch);
+    if (int st = check_cfg_window(nullptr, who, width, height, PP_OCC_MAX_CELLS, "PP_OCC_MAX_CELLS")) return st;
+    const struct { const char* name; int v, lo, hi; } f[] = {{"lethal_cost", navfn_cfg->lethal_cost, 1, 100},
+        {"allow_unknown", navfn_cfg->allow_unknown, 0, 1}, {"unknown_cost", navfn_cfg->unknown_cost, 0, 100}};
+    for (const auto& x : f)
+        if (x.v < x.lo || x.v > x.hi) return fail(nullptr, PP_ERR_ARG, "%s: %s = %d outside [%d, %d]", who, x.name, x.v, x.lo, x.hi);
+    if (int st = check_config(nullptr, who, *cfg)) return st;
+    std::vector<unsigned> packed;
+    if (int st = pack_trig(nullptr, who, trig, n_trig, packed)) return st;
+    std::vector<LocalCall> calls((size_t)batch);
+    if (int st = fill_calls(nullptr, who, calls.data(), *cfg, poses, windows, goal_state, batch)) return st;
+    if (int st = check_device(who, device)) return st;
+    DEVCHK(hipSetDevice(device));
+    const size_t cells = (size_t)width * height, n = (size_t)batch * cells;
+    const size_t samples = (size_t)cfg->nv * cfg->nw, words = (size_t)(cfg->steps + 1) * 3;
+    DevBuf d_grid, d_pot, d_trig, d_call, d_state, d_partial, d_score, d_traj, d_keys;
+    DEVCHK(d_grid.alloc(n));
+    DEVCHK(d_pot.alloc(n * sizeof(unsigned)));
+    DEVCHK(d_trig.alloc(packed.size() * sizeof(unsigned)));
+    DEVCHK(d_call.alloc((size_t)batch * sizeof(LocalCall)));
+    DEVCHK(d_state.alloc((size_t)LOC_STATE * batch * sizeof(int)));
+    DEVCHK(d_partial.alloc((size_t)LOC_MAX_CHUNKS * batch * sizeof(unsigned long long)));
+    DEVCHK(d_score.alloc((size_t)batch * sizeof(unsigned long long)));
+    DEVCHK(d_traj.alloc((size_t)batch * words * sizeof(int)));
+    if (keys) DEVCHK(d_keys.alloc((size_t)batch * samples * sizeof(unsigned long long)));
+    DEVCHK(hipMemcpy(d_grid.p, grids, n, hipMemcpyHostToDevice));
+    DEVCHK(hipMemcpy(d_pot.p, pots, n * sizeof(unsigned), hipMemcpyHostToDevice));
+    DEVCHK(hipMemcpy(d_trig.p, packed.data(), packed.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+    DEVCHK(hipMemcpy(d_call.p, calls.data(), (size_t)batch * sizeof(LocalCall), hipMemcpyHostToDevice));
+    LocalParams p;
+    memset(&p, 0, sizeof(p));
+    p.batch = batch; p.width = width; p.height = height; p.pitch = width; p.stride = cells;
+    p.lethal = navfn_cfg->lethal_cost; p.allow_unknown = navfn_cfg->allow_unknown; p.unknown_cost = navfn_cfg->unknown_cost;
+    fill_config(p, *cfg);
+    p.grid = (const int8_t*)d_grid.p; p.pot = (const unsigned*)d_pot.p;
+    p.call = (const LocalCall*)d_call.p; p.trig = (const unsigned*)d_trig.p; p.partial = (unsigned long long*)d_partial.p;
+    p.state = (int*)d_state.p; p.state_stride = batch; p.score = (unsigned long long*)d_score.p; p.traj = (int*)d_traj.p;
+    p.keys = keys ? (unsigned long long*)d_keys.p : nullptr;
+    if (int st = queue_run(nullptr, p, nullptr)) return st;
+    DEVCHK(hipStreamSynchronize(nullptr));
+    if (result) {
+        std::vector<int> host((size_t)LOC_STATE * batch);
+        DEVCHK(hipMemcpy(host.data(), p.state, host.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int b = 0; b < batch; ++b)
+            for (int k = 0; k < LOC_STATE; ++k) result[(size_t)b * PP_LOCAL_RESULT + k] = host[(size_t)k * batch + b];
+    }
+    if (score) DEVCHK(hipMemcpy(score, p.score, (size_t)batch * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (traj) DEVCHK(hipMemcpy(traj, p.traj, (size_t)batch * words * sizeof(int), hipMemcpyDeviceToHost));
+    if (keys) DEVCHK(hipMemcpy(keys, p.keys, (size_t)batch * samples * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PP_OK;
+}
+
+}  // extern "C"

@@ -69,6 +69,8 @@ int queue_run(pp_engine* e, const NavParams& p, int rounds, hipStream_t s) {
     return PP_OK;
 }
 
+}  // namespace
+
 // Waits for `s`, then queues rounds in groups until the last round of every grid changed nothing; `host` then holds the
 // state words and `s` is idle.  *rounds: queued so far, >= 1.
 int settle(pp_engine* e, const char* who, const NavParams& p, int* rounds, hipStream_t s, std::vector<int>& host) {
@@ -108,8 +110,6 @@ int settled_run(pp_engine* e, const char* who, int source, int batch, pp_engine:
     *out = &g;
     return PP_OK;
 }
-
-}  // namespace
 
 void navfn_release(pp_engine* e) {
     for (pp_engine::Navfn& g : e->navfn) {
@@ -199,6 +199,7 @@ int pp_navfn_async(pp_handle e, int32_t source, const int32_t* goals, const int3
         if (int st = queue_run(e, p, rounds, e->stream)) return st;
     }
     g.batch = batch; g.run = p; g.rounds = rounds; g.settled = false;
+    ++g.run_id;
     return PP_OK;
 }
 

@@ -795,6 +795,43 @@ void launch_navfn_relax(const NavParams& p, int round, hipStream_t s);       // 
 void launch_navfn_finish(const NavParams& p, int rounds, hipStream_t s);     // after `rounds` rounds; NAV_REACHED cleared before it
 int navfn_tiles(int width, int height, int* tiles_x);                        // workgroups of a round per grid
 
+// local_plan.hip: the inflated grid, the field and one pose and window per grid -> the (v, w) command whose rollout scores
+// least (pp_set_local_plan, pp_local_plan_grids; local_planner.py states the rule)
+struct LocalCall {                 // what travels from the host per grid and call: 8 int32
+    int X, Y, h;                   // the pose: sub-cells and a heading tick (taken & 4095)
+    int v0, dv, w0, dw;            // the window: sample s = i * nw + j has sv = v0 + i * dv, sw = w0 + j * dw
+    int flags;                     // LOC_NO_GOAL: the field has no goal, whatever `nav_state` says (pp_local_plan_grids)
+};
+constexpr int LOC_NO_GOAL = 1;
+constexpr int LOC_BLOCK = 256;     // samples of a workgroup of the rollout
+constexpr int LOC_MAX_CHUNKS = PP_LOCAL_MAX_SAMPLES / LOC_BLOCK;
+// per grid, field-major int [LOC_STATE][state_stride]: the four reason counts are cleared before the rollout and added to by
+// it; the others are written by finish.  The first PP_LOCAL_RESULT fields are a grid's result words in their order.
+enum { LOC_CMD_STATE = 0, LOC_BEST = 1, LOC_SV = 2, LOC_SW = 3, LOC_N_OK = 4, LOC_N_OUTSIDE = 5, LOC_N_COLLISION = 6,
+       LOC_N_UNREACHED = 7, LOC_STATE = 8 };
+struct LocalParams {
+    int batch, width, height;
+    int pitch;                     // cells of a row of `grid` and `pot`
+    size_t stride;                 // cells from one grid to the next in both
+    int lethal, allow_unknown, unknown_cost;       // of the pp_navfn_config the field was made with
+    int nv, nw, steps, lookahead, pot_w, occ_w, speed_w, turn_w;     // pp_local_plan_config
+    const int8_t* grid;            // [batch][height * pitch]; read, never written
+    const unsigned* pot;           // the same shape; read, never written
+    const NavCall* nav_call;       // [batch] or NULL: NAV_KNOWN clear reads the grid all unknown
+    const int* nav_state;          // [NAV_STATE][nav_state_stride] or NULL: NAV_GOAL_STATE != 0 is "no goal"
+    int nav_state_stride;
+    const LocalCall* call;         // [batch]
+    const unsigned* trig;          // [PP_LOCAL_HEADINGS]: C[h] as int16 in the low half, S[h] in the high half
+    unsigned long long* partial;   // [batch][LOC_MAX_CHUNKS]: a workgroup's least key
+    int* state;                    // [LOC_STATE][state_stride]
+    int state_stride;
+    unsigned long long* score;     // [batch]
+    int* traj;                     // [batch][steps + 1][3]
+    unsigned long long* keys;      // [batch][nv * nw], or NULL: not stored
+};
+void launch_local_rollout(const LocalParams& p, hipStream_t s);     // the reason counts of `state` cleared before it
+void launch_local_finish(const LocalParams& p, hipStream_t s);
+
 // weight_publish.hip: the trainer's flat parameter / state buffers -> the detector's weight arrays, on the device
 enum PubKind {
     PUB_PFN_W,       // out [FA][cout] = params[src] * scale[c]

@@ -6,7 +6,7 @@
 // api_metrics.hip: the training metrics' counts; api_publish.hip: a trainer's weights into the detector, on the device;
 // api_track.hip: the per-stream track tables behind the detector's post-process; api_sweeps.hip: the per-stream sweep rings
 // in front of the pass; api_costmap.hip: the obstacle grid per frame behind it; api_occupancy.hip: the rolling occupancy
-// map per stream; api_inflate.hip: obstacle inflation behind either grid; api_navfn.hip: the navigation function over the inflated grid.  pp_ring.h: the pinned call ring and the stages' memory owner, which the handle's members are made of.
+// map per stream; api_inflate.hip: obstacle inflation behind either grid; api_navfn.hip: the navigation function over the inflated grid; api_local_plan.hip: the local planner over that grid and its field.  pp_ring.h: the pinned call ring and the stages' memory owner, which the handle's members are made of.
 #pragma once
 
 #include <cmath>
@@ -463,9 +463,33 @@ struct pp_engine {
         int batch = 0;                     // grids of the last run (pp_get_navfn; 0: none)
         NavParams run = {};                // ... what it was launched with
         int rounds = 0;                    // relaxation rounds queued behind its init so far
+        unsigned long long run_id = 0;     // counts the pp_navfn_async calls of the source (pp_get_local_plan)
         bool settled = false;              // a getter has seen every grid's field stand, and `host` holds the state words
         std::vector<int> host;             // [NAV_STATE][B]
     } navfn[2];                            // by source, as infl
+
+    // pp_set_local_plan: the (v, w) command from a window of rollouts over infl[source].out and navfn[source]'s field, both
+    // read in place and never written (api_local_plan.hip).  Plain launches on the handle's stream: rollout, finish; the
+    // getter settles the field first and queues both again if that took a further round.
+    struct LocalPlan {
+        bool on = false;                   // pp_set_local_plan gave a configuration and has not taken it back
+        pp_local_plan_config cfg = {};     // the last configuration given
+        unsigned* trig = nullptr;          // [PP_LOCAL_HEADINGS] packed; this and the next four live as long as the handle (`allocs`)
+        int* state = nullptr;              // [LOC_STATE][B]
+        unsigned long long* partial = nullptr;     // [B][LOC_MAX_CHUNKS]
+        unsigned long long* score = nullptr;       // [B]
+        LocalCall* d_call = nullptr;       // [B]
+        CallRing ring;                     // the calls' poses and windows, consumed on the main stream
+        RingArray<LocalCall> h_call;       // [B] per slot
+        StageMem mem;                      // owns keys and traj, made by pp_local_plan_async for the configuration's shape: not in `allocs`
+        unsigned long long* keys = nullptr;        // [B][samples_cap]
+        int* traj = nullptr;               // [B][steps_cap + 1][3]
+        int samples_cap = 0, steps_cap = 0;
+        int batch = 0;                     // grids of the last run (pp_get_local_plan; 0: none)
+        LocalParams run = {};              // ... what it was launched with
+        unsigned long long nav_run = 0;    // navfn[source].run_id it was queued behind
+        int nav_rounds = 0;                // navfn[source].rounds its last launches were queued behind
+    } local[2];                            // by source, as infl
     unsigned long long resident_gen = 0;   // counts the changes of the resident frames (set_resident, a stage call)
     unsigned long long results_gen = 0;    // resident_gen of the last pp_detect_async
 
@@ -629,6 +653,11 @@ void costmap_release(pp_engine* e);                     // api_costmap.hip: what
 void occupancy_release(pp_engine* e);                   // api_occupancy.hip: what pp_destroy frees of the occupancy maps
 void inflate_release(pp_engine* e);                     // api_inflate.hip: what pp_destroy frees of the inflation stage
 void navfn_release(pp_engine* e);                       // api_navfn.hip: what pp_destroy frees of the navigation-function stage
+// api_navfn.hip, for the stage behind it (api_local_plan.hip).  settle: waits for `s`, then queues rounds in groups until
+// the last round of every grid changed nothing.  settled_run: what the getters start with, the source's last run, settled.
+int settle(pp_engine* e, const char* who, const NavParams& p, int* rounds, hipStream_t s, std::vector<int>& host);
+int settled_run(pp_engine* e, const char* who, int source, int batch, pp_engine::Navfn** out);
+void local_plan_release(pp_engine* e);                  // api_local_plan.hip: what pp_destroy frees of the local planner
 int ensure_metrics(pp_engine* e);                       // api_metrics.hip
 void fill_metrics_params(pp_engine* e, int batch, MetricsParams& p);   // ... on the handle's head map and loss.labels
 // ---- api_dataprep.hip: what the fused training steps (api_train.hip) queue ----

@@ -20,6 +20,7 @@ from . import costmap as _cm
 from . import occupancy as _occ
 from . import inflation as _infl
 from . import navfn as _nav
+from . import local_planner as _loc
 from .anchors import build_anchor_cells, build_anchors
 from .config import Derived
 from .weights import check_weights
@@ -425,6 +426,7 @@ class Engine:
         self._costmap_queued = False                            # a costmap_async whose grids costmaps() has not fetched
         self._infl_run = {}                                     # source index -> (batch, (H, W)) of its last inflate_async
         self._navfn_run = {}                                    # source index -> (batch, (H, W), max_path, origins, resolution) of its last navfn_async
+        self._local_run = {}                                    # source index -> (batch, LocalPlanConfig, resolution or None, step dt or None) of its last local_plan_async
         if d.costmap is not None:
             self.set_costmap(d.costmap)
         if weights is not None:
@@ -1162,6 +1164,7 @@ class Engine:
         self._occ_batch = B
         self._occ_origins = np.array(cells, np.float64).reshape(B, 2) * c.resolution      # (pp_get_occupancy's arithmetic)
         self._occ_shape = (c.height, c.width)
+        self._occ_poses = P.copy()                              # (local_plan_async's default poses)
 
     def occupancy_maps(self, batch=None, logodds=False):
         """(grids int8 [B, H, W], origins float64 [B, 2]) of the streams of the last occupancy_update_async (waits for
@@ -1397,6 +1400,120 @@ class Engine:
         queued first if no costmap_async is pending, exactly as `inflated_costmaps()` does, then the inflation, then the
         field and the paths.  "occupancy": the inflation and this stage are queued behind the caller's
         occupancy_update_async.  Only the paths travel to the host."""
+        self._plan_async(goals, source, starts)
+        return self.navfn_paths(source, metres=True)
+
+    # ---- local planner behind either navigation function (pp_set_local_plan, pp_local_plan_async, pp_get_local_plan; local_planner.py states the rule; DESIGN 7.1aa) ----
+    def set_local_planner(self, cfg, source="costmap"):
+        """A local_planner.LocalPlanConfig, a dict of its fields or True (the defaults) for `source`, "costmap" or
+        "occupancy": `local_plan_async(poses, windows)` / `drive(goals, velocities, limits)` then roll a window of (v, w)
+        samples over the source's inflated grid and score them on its navigation function's field, on the GPU, where
+        both lie; neither is written.  None: the source's stage off (the default); its buffers are kept."""
+        k = self._infl_source(source)
+        if cfg is None or cfg is False:
+            self._check(self._lib.pp_set_local_plan(self._h, k, None, None, 0), "pp_set_local_plan")
+            return
+        pc = _to_struct(_lib.PPLocalPlanConfig, _loc.LocalPlanConfig.from_any(cfg))
+        trig = np.ascontiguousarray(_loc.trig_table(), np.int32)
+        self._check(self._lib.pp_set_local_plan(self._h, k, ctypes.byref(pc), _ptr(trig), len(trig)), "pp_set_local_plan")
+
+    def local_planner_config(self, source="costmap"):
+        """The LocalPlanConfig in force for `source`, or None while its stage is off."""
+        k = self._infl_source(source)
+        on, pc = ctypes.c_int32(0), _lib.PPLocalPlanConfig()
+        self._check(self._lib.pp_get_local_plan_config(self._h, k, ctypes.byref(on), ctypes.byref(pc)), "pp_get_local_plan_config")
+        return _from_struct(_loc.LocalPlanConfig, pc) if on.value else None
+
+    def _local_cells_async(self, k, poses, windows, resolution=None, dt=None):
+        """pp_local_plan_async on integers: poses int32 [B, 3] (X, Y, h), windows int32 [B, 4] (v0, dv, w0, dw)."""
+        P = np.ascontiguousarray(poses, np.int32)
+        Wn = np.ascontiguousarray(windows, np.int32)
+        self._check(self._lib.pp_local_plan_async(self._h, k, _ptr(P), _ptr(Wn), int(P.shape[0])), "pp_local_plan_async")
+        self._local_run[k] = (int(P.shape[0]), self.local_planner_config(_infl.SOURCES[k]), resolution, dt)
+
+    def local_plan_async(self, poses=None, windows=None, source="costmap", dt=None):
+        """Queues the rollout and the command on the grids and fields of the source's last navfn_async behind the
+        relaxation rounds that call queued (pp_local_plan_async) and returns at once.  poses float64 [B, 3] (x, y, yaw) (or
+        one for every grid), metres and radians in the grids' frame; None: the sensor at yaw 0 for the costmap, the
+        translation and atan2(R10, R00) of the last occupancy_update_async's poses for the occupancy maps.  They become
+        sub-cells and ticks through local_planner.pose_ticks with the navfn run's origins and the source's resolution, so
+        a pose outside its window is no error (cmd_state 3).  windows integers [B, 4] (v0, dv, w0, dw) (or one), as
+        local_planner.LocalLimits.window makes them; None: sv from 0 to 1024 and sw from -512 to 512.  dt: the seconds of
+        a step, which `local_commands(metric=True)` needs."""
+        k = self._infl_source(source)
+        B, _, _, org, res = self._navfn_last(k, "local_plan_async")
+        c = self.local_planner_config(source)
+        if c is None:
+            raise RuntimeError(f"local_plan_async: the local planner of the {source} source is not configured (set_local_planner first)")
+        if org is None:
+            raise RuntimeError("local_plan_async: the navigation function was given cells, it has no frame in metres")
+        if poses is None:
+            if k == 0:
+                P = np.zeros((B, 3))
+            else:
+                T = self._occ_poses[:B]
+                P = np.stack([T[:, 0, 3], T[:, 1, 3], np.arctan2(T[:, 1, 0], T[:, 0, 0])], axis=1)
+        else:
+            P = np.asarray(poses, np.float64)
+            if P.shape not in ((3,), (B, 3)):
+                raise ValueError(f"local_plan_async: poses must be (x, y, yaw) [{B}, 3] (the navigation function run's grids) or one, got {P.shape}")
+            P = np.broadcast_to(P, (B, 3))
+        ticks = _loc.pose_ticks(P[:, :2], P[:, 2], org, res)
+        if windows is None:
+            windows = (0, _loc.MAX_SV // max(c.nv - 1, 1), -_loc.MAX_SW, 2 * _loc.MAX_SW // max(c.nw - 1, 1))
+        Wn = _loc._batch_ints(windows, B, 4, "local_plan_async", "windows")
+        for b in range(B):
+            _loc.check_window(Wn[b], c, f"local_plan_async: grid {b}")
+        self._local_cells_async(k, ticks, Wn, res, None if dt is None else float(dt))
+
+    def _local_last(self, k, who):
+        if k not in self._local_run:
+            raise RuntimeError(f"{who}: no local plan has run on the {_infl.SOURCES[k]} source (local_plan_async first)")
+        return self._local_run[k]
+
+    def _local_fetch(self, k, who, traj=False, keys=False):
+        B, c, _, _ = self._local_last(k, who)
+        res = np.zeros((B, _lib.PP_LOCAL_RESULT), np.int32)
+        score = np.zeros(B, np.uint64)
+        tr = np.zeros((B, c.steps + 1, 3), np.int32) if traj else None
+        kk = np.zeros((B, c.nv * c.nw), np.uint64) if keys else None
+        self._check(self._lib.pp_get_local_plan(self._h, k, _ptr(res), _ptr(score), _ptr(tr), _ptr(kk), B), "pp_get_local_plan")
+        return _loc.unpack_results(c, B, res, score, tr, kk)
+
+    def local_commands(self, source="costmap", metric=False):
+        """(sv int32 [B], sw int32 [B], cmd_state int32 [B]) of the source's last local_plan_async, sub-cells and ticks per
+        step (waits for it; the field is settled first and the rollout queued again if that took a further round: a
+        command always rests on the exact field).  metric=True: (v float64 [B] m/s, w float64 [B] rad/s, cmd_state)
+        through local_planner.command_metric with the run's resolution and step dt.  cmd_state as local_planner.py lists
+        it; the command is (0, 0) unless it is 0."""
+        k = self._infl_source(source)
+        out = self._local_fetch(k, "local_commands")
+        if not metric:
+            return out["sv"], out["sw"], out["cmd_state"]
+        _, _, res, dt = self._local_last(k, "local_commands")
+        if res is None or dt is None:
+            raise RuntimeError("local_commands: metric=True needs the run's resolution and step dt (local_plan_async(..., dt=), or drive)")
+        v, w = _loc.command_metric(out["sv"], out["sw"], res, dt)
+        return v, w, out["cmd_state"]
+
+    def local_trajectories(self, source="costmap"):
+        """A list of B arrays int32 [steps + 1, 3], the winners' poses (X, Y, h) with the start included ([0, 3] where
+        cmd_state is not 0), of the source's last local_plan_async (waits as local_commands does)."""
+        return self._local_fetch(self._infl_source(source), "local_trajectories", traj=True)["traj"]
+
+    def local_keys(self, source="costmap"):
+        """All keys uint64 [B, nv * nw] of the source's last local_plan_async (waits as local_commands does; the rollout
+        runs once more to store them the first time): (score << 14) | sample, local_planner.INVALID for a sample that
+        did not end ok."""
+        return self._local_fetch(self._infl_source(source), "local_keys", keys=True)["keys"]
+
+    def local_plan_info(self, source="costmap"):
+        """Per grid of the source's last local_plan_async (waits as local_commands does): `cmd_state`, `best`, `sv`, `sw`,
+        `n_ok`, `n_outside`, `n_collision`, `n_unreached` int32 [B] each and `score` uint64 [B]."""
+        return self._local_fetch(self._infl_source(source), "local_plan_info")
+
+    def _plan_async(self, goals, source, starts):
+        """What `plan` queues: the source's grids, their inflation, the field and the paths."""
         k = self._infl_source(source)
         if k == 0:
             if not self._costmap_queued:
@@ -1406,7 +1523,28 @@ class Engine:
         else:
             self.inflate_async("occupancy")
         self.navfn_async(goals, source, starts)
-        return self.navfn_paths(source, metres=True)
+        return k
+
+    def drive(self, goals, velocities, limits, source="costmap", poses=None):
+        """(v float64 [B] m/s, w float64 [B] rad/s, cmd_state int32 [B]) towards `goals` (as navfn_async takes them): what
+        `plan` queues, then the local planner on the dynamic windows round the current `velocities` float64 [B, 2] (v m/s,
+        w rad/s) (or one) under `limits`, a local_planner.LocalLimits; a step lasts limits.step_dt(resolution), so a
+        rollout looks steps * step_dt ahead (LocalLimits.steps gives the steps for its sim_time).  poses as
+        local_plan_async takes them.  Only the commands travel to the host."""
+        if not isinstance(limits, _loc.LocalLimits):
+            raise ValueError(f"drive: limits must be a local_planner.LocalLimits, got {limits!r}")
+        c = self.local_planner_config(source)
+        if c is None:
+            raise RuntimeError(f"drive: the local planner of the {source} source is not configured (set_local_planner first)")
+        k = self._plan_async(goals, source, None)
+        B, _, _, _, res = self._navfn_last(k, "drive")
+        V = np.asarray(velocities, np.float64)
+        if V.shape not in ((2,), (B, 2)):
+            raise ValueError(f"drive: velocities must be (v, w) [{B}, 2] or one, got {V.shape}")
+        V = np.broadcast_to(V, (B, 2))
+        Wn = np.array([limits.window(V[b, 0], V[b, 1], c.nv, c.nw, res) for b in range(B)], np.int32)
+        self.local_plan_async(poses, Wn, source, dt=limits.step_dt(res))
+        return self.local_commands(source, metric=True)
 
     def _pose_args(self, poses, stamps, batch, who):
         """poses= of a detect*: checked before anything is queued (None: no accumulation); stamps then serve the sweeps, and

@@ -1,0 +1,473 @@
+"""Local planner over an inflated int8 grid in the layout of nav_msgs/OccupancyGrid and the cost-to-go field of navfn.py:
+a window of (v, w) samples rolled forward from the robot's pose, each scored on the field, and the best one as the velocity
+command -- the stage that reads the field.  A fifth, opt-in stage behind the navigation function of the costmap or of the
+rolling occupancy maps, and a stand-alone call for any such grid and field.
+
+The reference has no such path, so nothing here is parity with it.  This module STATES the rule: `score_np` (one sample,
+literally step by step in Python ints), `scores_np` (all samples of a window at once as numpy arrays, step-major with
+masks, an independent second statement) and `best_np` are the restatement that the GPU (csrc/local_plan.hip behind
+Engine.set_local_planner / local_plan_async / drive, and `local_plan`) equals with no tolerance.  Everything is integer
+arithmetic; metres, radians and seconds become integers here on the host (`pose_ticks`, `LocalLimits.window`).
+
+UNITS.  A position is int32 sub-cells, SUB = 1024 per cell; a heading is one of HEADINGS = 4096 ticks per revolution, tick
+0 along +x, ticks growing towards +y.  C[h], S[h] = rint(cos / sin(2 pi h / 4096) * 2^14) as int32 (`trig_table`, computed
+in float64 on the host and uploaded with the configuration; the device only looks it up).
+
+INPUT per grid: the inflated grid g[H, W], the field pot uint32 [H, W], a pose (X, Y, h) (h is taken & 4095), a window
+(v0, dv, w0, dw); the configuration fixes nv, nw and steps.  Sample s = i * nw + j has sv = v0 + i * dv sub-cells per
+step (negative: reverse) and sw = w0 + j * dw ticks per step; every sample must satisfy |sv| <= 1024 and |sw| <= 512,
+so a step never moves more than one cell along an axis.
+
+ROLLOUT.  For k = 1 .. steps: X += (sv * C[h] + 8192) >> 14, Y += (sv * S[h] + 8192) >> 14, then h = (h + sw) & 4095 --
+the move uses the old heading and the shift is arithmetic (floor).  The cell is (X >> 10, Y >> 10).  A cell outside the
+grid ends the sample as OUTSIDE (reason 1); a blocked one -- g >= lethal_cost, or unknown while allow_unknown is 0, of the
+NavfnConfig the field was made with -- as COLLISION (reason 2); otherwise occ = max(occ, g), unknown_cost standing in for
+an unknown cell.  After the last step the scored point is the end pose pushed `lookahead` sub-cells along the final
+heading, rounded like a step (0: the end cell itself); a scored cell that is outside, blocked or UNREACHED makes the
+sample UNREACHED (reason 3).
+
+SCORE.  score = pot_weight * pot(scored cell) + occ_weight * occ + speed_weight * (1024 - |sv|) + turn_weight * |sw|, below
+2^41 by the configuration's ranges; key = (score << 14) | s, 2^64 - 1 for an invalid sample.  The command is the sample
+with the least key: the lowest index wins a tie.
+
+STATES.  cmd_state, the first that applies: 4 the field has no goal (navfn goal_state != 0); 3 the pose's cell is outside
+the grid, blocked or UNREACHED; 2 arrived, pot at the pose's cell is 0; 1 no valid sample; 0 ok.  In states 1 .. 4 the
+command is (0, 0), best = -1 and the trajectory is empty; in states 2 .. 4 no sample is rolled, every key is invalid and
+the counts are 0.
+
+Results per grid: cmd_state, best, sv, sw; the counts n_ok, n_outside, n_collision, n_unreached; score; the winning
+trajectory int32 [steps + 1, 3] poses, the start included; all nv * nw keys uint64 on request.
+
+Out of scope: escaping from a blocked pose, footprints other than a point on the inflated grid, holonomic (vy) samples,
+oscillation suppression between cycles, goal-orientation alignment, a diagonal step passing between two blocked cells that
+touch only at a corner (an inscribed radius of one cell or more rules this out), a configuration key, any ROS import.
+"""
+import ctypes
+import dataclasses
+import math
+
+import numpy as np
+
+from . import _lib
+from . import navfn as _nav
+from ._lib import (PP_LOCAL_HEADINGS, PP_LOCAL_MAX_LOOKAHEAD, PP_LOCAL_MAX_SAMPLES, PP_LOCAL_MAX_STEPS, PP_LOCAL_SUB,
+                   PP_OCC_MAX_CELLS)
+
+SUB = PP_LOCAL_SUB
+HEADINGS = PP_LOCAL_HEADINGS
+ONE = 1 << 14                           # the trig table's 1.0
+MAX_SV, MAX_SW = 1024, 512              # |sv| sub-cells and |sw| ticks per step at most
+INVALID = 2 ** 64 - 1                   # the key of a sample that did not end OK
+OK, OUTSIDE, COLLISION, UNREACHED = 0, 1, 2, 3      # why a sample ended
+STATE_OK, STATE_NO_SAMPLE, STATE_ARRIVED, STATE_POSE, STATE_NO_GOAL = 0, 1, 2, 3, 4
+RESULT = ("cmd_state", "best", "sv", "sw", "n_ok", "n_outside", "n_collision", "n_unreached")      # pp_get_local_plan's words
+
+_RANGES = (("nv", 1, PP_LOCAL_MAX_SAMPLES), ("nw", 1, PP_LOCAL_MAX_SAMPLES), ("steps", 1, PP_LOCAL_MAX_STEPS),
+           ("lookahead", 0, PP_LOCAL_MAX_LOOKAHEAD), ("pot_weight", 0, 255), ("occ_weight", 0, 65535),
+           ("speed_weight", 0, 65535), ("turn_weight", 0, 65535))
+MAX_SCORE = 255 * (_nav.UNREACHED - 1) + 65535 * 100 + 65535 * 1024 + 65535 * 512
+assert SUB == 1 << 10 and HEADINGS == 1 << 12 and MAX_SV == SUB and PP_LOCAL_MAX_SAMPLES == 1 << 14
+assert MAX_SCORE < 2 ** 41                                  # so (score << 14) | s < 2^55 never reaches INVALID
+# X and Y fit int32: a rolled pose lies in the grid, a step moves at most one cell and a sample ends at its first cell
+# outside; the scored point adds the lookahead
+assert (PP_OCC_MAX_CELLS + 1) * SUB + PP_LOCAL_MAX_LOOKAHEAD < 2 ** 31
+assert MAX_SV * ONE + 8192 < 2 ** 31 and PP_LOCAL_MAX_LOOKAHEAD * ONE + 8192 < 2 ** 31       # the products do too
+
+
+@dataclasses.dataclass
+class LocalPlanConfig:
+    """nv, nw          >= 1, nv * nw <= 16384: velocity and turn-rate samples of a window
+    steps           1 .. 256: steps of a rollout
+    lookahead       0 .. 16384 sub-cells: how far beyond the end pose, along the final heading, the field is read
+    pot_weight      0 .. 255
+    occ_weight, speed_weight, turn_weight   0 .. 65535"""
+    nv: int = 9
+    nw: int = 21
+    steps: int = 32
+    lookahead: int = 0
+    pot_weight: int = 32
+    occ_weight: int = 16
+    speed_weight: int = 1
+    turn_weight: int = 1
+
+    def __post_init__(self):
+        for f, lo, hi in _RANGES:
+            v = getattr(self, f)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"LocalPlanConfig: {f} must be an integer, got {v!r}")
+            if int(v) < lo or int(v) > hi:
+                raise ValueError(f"LocalPlanConfig: {f} = {v} outside [{lo}, {hi}]")
+            setattr(self, f, int(v))
+        if self.nv * self.nw > PP_LOCAL_MAX_SAMPLES:
+            raise ValueError(f"LocalPlanConfig: nv * nw = {self.nv * self.nw} samples, at most PP_LOCAL_MAX_SAMPLES = {PP_LOCAL_MAX_SAMPLES}")
+
+    def to_dict(self):
+        return dataclasses.asdict(self)
+
+    @classmethod
+    def from_any(cls, cfg):
+        """A LocalPlanConfig, a dict of its fields (unknown keys raise, naming them) or True (the defaults)."""
+        if isinstance(cfg, cls):
+            return cfg
+        if cfg is True:
+            return cls()
+        if isinstance(cfg, dict):
+            unknown = set(cfg) - {f.name for f in dataclasses.fields(cls)}
+            if unknown:
+                raise ValueError(f"local_planner: unknown keys {sorted(unknown)}")
+            return cls(**cfg)
+        raise ValueError(f"local_planner: a LocalPlanConfig, a dict of its fields or True, got {cfg!r}")
+
+
+def trig_table():
+    """int32 [4096, 2]: (C[h], S[h]) = rint(cos / sin(2 pi h / 4096) * 2^14), in float64."""
+    a = 2.0 * np.pi * np.arange(HEADINGS, dtype=np.float64) / HEADINGS
+    return np.stack([np.rint(np.cos(a) * ONE), np.rint(np.sin(a) * ONE)], axis=1).astype(np.int32)
+
+
+_TRIG = trig_table()
+_TRIG.setflags(write=False)
+
+
+def _inputs(grid, pot, who):
+    g = np.asarray(grid)
+    p = np.asarray(pot)
+    if g.dtype != np.int8 or g.ndim != 2 or g.size == 0:
+        raise ValueError(f"{who}: a grid must be int8 [H, W] with H, W >= 1, got {g.dtype} {g.shape}")
+    if p.dtype != np.uint32 or p.shape != g.shape:
+        raise ValueError(f"{who}: pot must be uint32 of the grid's shape {g.shape}, got {p.dtype} {p.shape}")
+    return g, p
+
+
+def _ints(v, n, who, what):
+    a = np.asarray(v)
+    if a.shape != (n,) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{who}: {what} must be {n} integers, got {v!r}")
+    return tuple(int(x) for x in a)
+
+
+def check_window(window, cfg, who="local_planner"):
+    """(v0, dv, w0, dw) as ints; raises unless every sample of the window has |sv| <= 1024 and |sw| <= 512."""
+    c = LocalPlanConfig.from_any(cfg)
+    v0, dv, w0, dw = _ints(window, 4, who, "a window (v0, dv, w0, dw)")
+    v1, w1 = v0 + (c.nv - 1) * dv, w0 + (c.nw - 1) * dw
+    if max(abs(v0), abs(v1)) > MAX_SV:
+        raise ValueError(f"{who}: sv runs from {v0} to {v1}, outside [-{MAX_SV}, {MAX_SV}]")
+    if max(abs(w0), abs(w1)) > MAX_SW:
+        raise ValueError(f"{who}: sw runs from {w0} to {w1}, outside [-{MAX_SW}, {MAX_SW}]")
+    return v0, dv, w0, dw
+
+
+def sample(s, window, cfg):
+    """(sv, sw) of sample s = i * nw + j."""
+    c = LocalPlanConfig.from_any(cfg)
+    v0, dv, w0, dw = window
+    return int(v0) + (s // c.nw) * int(dv), int(w0) + (s % c.nw) * int(dw)
+
+
+def _cell_value(g, x, y, n):
+    """The rule's reading of cell (x, y): None outside the grid, -1 blocked, else the value occ takes."""
+    H, W = g.shape
+    if not (0 <= x < W and 0 <= y < H):
+        return None
+    v = int(g[y, x])
+    if v >= n.lethal_cost:
+        return -1
+    if v < 0:
+        return n.unknown_cost if n.allow_unknown else -1
+    return v
+
+
+def stream_state_np(grid, pot, pose, navfn_cfg, goal_state=0):
+    """The part of cmd_state that needs no sample: 4, 3, 2 or 0."""
+    n = _nav.NavfnConfig.from_any(navfn_cfg)
+    g, p = _inputs(grid, pot, "stream_state_np")
+    X, Y, _ = _ints(pose, 3, "stream_state_np", "a pose (X, Y, h)")
+    if int(goal_state) != 0:
+        return STATE_NO_GOAL
+    cx, cy = X >> 10, Y >> 10
+    v = _cell_value(g, cx, cy, n)
+    if v is None or v < 0 or int(p[cy, cx]) == _nav.UNREACHED:
+        return STATE_POSE
+    return STATE_ARRIVED if int(p[cy, cx]) == 0 else STATE_OK
+
+
+def score_np(grid, pot, pose, sv, sw, navfn_cfg, cfg):
+    """One sample, step by step in Python ints: (reason, score or None, poses) -- the poses [(X, Y, h)] the sample
+    reached, the start included (steps + 1 of them when reason is OK or UNREACHED)."""
+    n = _nav.NavfnConfig.from_any(navfn_cfg)
+    c = LocalPlanConfig.from_any(cfg)
+    g, p = _inputs(grid, pot, "score_np")
+    X, Y, h = _ints(pose, 3, "score_np", "a pose (X, Y, h)")
+    sv, sw = int(sv), int(sw)
+    h &= HEADINGS - 1
+    C, S = _TRIG[:, 0], _TRIG[:, 1]
+    poses = [(X, Y, h)]
+    occ = 0
+    for _ in range(c.steps):
+        X += (sv * int(C[h]) + 8192) >> 14
+        Y += (sv * int(S[h]) + 8192) >> 14
+        h = (h + sw) & (HEADINGS - 1)
+        poses.append((X, Y, h))
+        v = _cell_value(g, X >> 10, Y >> 10, n)
+        if v is None:
+            return OUTSIDE, None, poses
+        if v < 0:
+            return COLLISION, None, poses
+        occ = max(occ, v)
+    lx = X + ((c.lookahead * int(C[h]) + 8192) >> 14)
+    ly = Y + ((c.lookahead * int(S[h]) + 8192) >> 14)
+    cx, cy = lx >> 10, ly >> 10
+    v = _cell_value(g, cx, cy, n)
+    if v is None or v < 0 or int(p[cy, cx]) == _nav.UNREACHED:
+        return UNREACHED, None, poses
+    score = c.pot_weight * int(p[cy, cx]) + c.occ_weight * occ + c.speed_weight * (1024 - abs(sv)) + c.turn_weight * abs(sw)
+    return OK, score, poses
+
+
+def keys_by_sample_np(grid, pot, pose, window, navfn_cfg, cfg):
+    """(keys uint64 [nv * nw], reasons int32 [nv * nw]) of a window through `score_np`, sample by sample."""
+    c = LocalPlanConfig.from_any(cfg)
+    window = check_window(window, c, "keys_by_sample_np")
+    keys = np.full(c.nv * c.nw, INVALID, np.uint64)
+    reasons = np.zeros(c.nv * c.nw, np.int32)
+    for s in range(c.nv * c.nw):
+        sv, sw = sample(s, window, c)
+        reasons[s], score, _ = score_np(grid, pot, pose, sv, sw, navfn_cfg, c)
+        if score is not None:
+            keys[s] = (score << 14) | s
+    return keys, reasons
+
+
+def scores_np(grid, pot, pose, window, navfn_cfg, cfg):
+    """(keys uint64 [nv * nw], reasons int32 [nv * nw]) of a window, all samples at once: arrays over the samples, one
+    masked update per step."""
+    n = _nav.NavfnConfig.from_any(navfn_cfg)
+    c = LocalPlanConfig.from_any(cfg)
+    g, p = _inputs(grid, pot, "scores_np")
+    v0, dv, w0, dw = check_window(window, c, "scores_np")
+    X0, Y0, h0 = _ints(pose, 3, "scores_np", "a pose (X, Y, h)")
+    H, W = g.shape
+    # the value occ takes per cell, -1 where blocked
+    val = g.astype(np.int64)
+    val = np.where(val >= n.lethal_cost, -1, np.where(val < 0, n.unknown_cost if n.allow_unknown else -1, val))
+    N = c.nv * c.nw
+    s = np.arange(N, dtype=np.int64)
+    sv, sw = v0 + (s // c.nw) * dv, w0 + (s % c.nw) * dw
+    X, Y = np.full(N, X0, np.int64), np.full(N, Y0, np.int64)
+    h = np.full(N, h0 & (HEADINGS - 1), np.int64)
+    occ = np.zeros(N, np.int64)
+    reason = np.zeros(N, np.int32)
+    alive = np.ones(N, bool)
+    C, S = _TRIG[:, 0].astype(np.int64), _TRIG[:, 1].astype(np.int64)
+
+    def read(cx, cy, m):
+        """(inside, index): which samples of mask m lie in the grid, and an index that is (0, 0) for the others"""
+        inside = m & (cx >= 0) & (cx < W) & (cy >= 0) & (cy < H)
+        at = (np.where(inside, cy, 0), np.where(inside, cx, 0))
+        return inside, at
+
+    for _ in range(c.steps):
+        X = np.where(alive, X + ((sv * C[h] + 8192) >> 14), X)
+        Y = np.where(alive, Y + ((sv * S[h] + 8192) >> 14), Y)
+        h = np.where(alive, (h + sw) & (HEADINGS - 1), h)
+        inside, at = read(X >> 10, Y >> 10, alive)
+        v = val[at]
+        out = alive & ~inside
+        hit = inside & (v < 0)
+        reason[out] = OUTSIDE
+        reason[hit] = COLLISION
+        alive = alive & ~out & ~hit
+        occ = np.where(alive, np.maximum(occ, v), occ)
+    lx = X + ((c.lookahead * C[h] + 8192) >> 14)
+    ly = Y + ((c.lookahead * S[h] + 8192) >> 14)
+    inside, at = read(lx >> 10, ly >> 10, alive)
+    reached = inside & (val[at] >= 0) & (p[at] != _nav.UNREACHED)
+    reason[alive & ~reached] = UNREACHED
+    score = c.pot_weight * p[at].astype(np.int64) + c.occ_weight * occ + c.speed_weight * (1024 - np.abs(sv)) + c.turn_weight * np.abs(sw)
+    keys = np.where(reached, (score.astype(np.uint64) << np.uint64(14)) | s.astype(np.uint64), np.uint64(INVALID))
+    return keys.astype(np.uint64), reason
+
+
+def best_np(grid, pot, pose, window, navfn_cfg, cfg, goal_state=0, samples=None):
+    """The results of one grid as a dict: the RESULT words, `score`, `traj` int32 [steps + 1, 3] (or [0, 3]) and `keys`
+    uint64 [nv * nw].  samples: `scores_np` (the default) or `keys_by_sample_np`."""
+    c = LocalPlanConfig.from_any(cfg)
+    window = check_window(window, c, "best_np")
+    N = c.nv * c.nw
+    out = {k: 0 for k in RESULT}
+    out.update(best=-1, score=0, traj=np.zeros((0, 3), np.int32), keys=np.full(N, INVALID, np.uint64))
+    state = stream_state_np(grid, pot, pose, navfn_cfg, goal_state)
+    if state == STATE_OK:
+        keys, reasons = (samples or scores_np)(grid, pot, pose, window, navfn_cfg, c)
+        out["keys"] = keys
+        for r, name in ((OK, "n_ok"), (OUTSIDE, "n_outside"), (COLLISION, "n_collision"), (UNREACHED, "n_unreached")):
+            out[name] = int((reasons == r).sum())
+        k = int(keys.min())
+        if k == INVALID:
+            state = STATE_NO_SAMPLE
+        else:
+            s = k & (PP_LOCAL_MAX_SAMPLES - 1)
+            sv, sw = sample(s, window, c)
+            reason, score, poses = score_np(grid, pot, pose, sv, sw, navfn_cfg, c)
+            assert reason == OK and score == k >> 14
+            out.update(best=s, sv=sv, sw=sw, score=score, traj=np.array(poses, np.int32).reshape(-1, 3))
+    out["cmd_state"] = state
+    return out
+
+
+# ---- host helpers: the only place where metres, radians and seconds appear (float64) ----
+def pose_ticks(xy, yaw, origin, resolution):
+    """Metres and radians -> int32 [B, 3] (X, Y, h): X = floor((x - origin_x) / resolution * 1024) sub-cells, likewise Y,
+    h = rint(yaw / 2 pi * 4096) & 4095, for points xy [B, 2] (or [2]) and yaws [B] (or one) in the frame of grids whose
+    cell [0, 0] lies at origins [B, 2] (or [2]).  A NaN gives (-1024, -1024, 0), a pose outside its grid; a point far beyond
+    the grid is clipped to +-2^30 sub-cells, outside all the same."""
+    p = np.atleast_2d(np.asarray(xy, np.float64))
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError(f"pose_ticks: xy must be [B, 2] metres, got {np.asarray(xy).shape}")
+    o = np.broadcast_to(np.atleast_2d(np.asarray(origin, np.float64)), p.shape)
+    a = np.broadcast_to(np.asarray(yaw, np.float64).reshape(-1), (p.shape[0],))
+    if not float(resolution) > 0.0:
+        raise ValueError(f"pose_ticks: resolution = {resolution} must be > 0")
+    with np.errstate(invalid="ignore", over="ignore"):
+        f = np.floor((p - o) / float(resolution) * SUB)
+        t = np.rint(a / (2.0 * np.pi) * HEADINGS)
+    bad = ~(np.isfinite(f).all(axis=1) & np.isfinite(t))
+    f = np.clip(np.where(bad[:, None], -float(SUB), f), -float(2 ** 30), float(2 ** 30))
+    t = np.where(bad, 0.0, np.fmod(t, HEADINGS))
+    out = np.empty((p.shape[0], 3), np.int32)
+    out[:, :2] = f.astype(np.int64)
+    out[:, 2] = t.astype(np.int64) & (HEADINGS - 1)
+    return out
+
+
+def command_metric(sv, sw, resolution, dt):
+    """(v m/s, w rad/s) of a command in sub-cells and ticks per step of dt seconds."""
+    return (np.asarray(sv, np.float64) / SUB * float(resolution) / float(dt),
+            np.asarray(sw, np.float64) * (2.0 * np.pi / HEADINGS) / float(dt))
+
+
+@dataclasses.dataclass
+class LocalLimits:
+    """v_min, v_max    m/s, v_min <= v_max (v_min < 0 allows reverse); not both 0
+    w_max           rad/s, >= 0: |w| at most
+    acc_v, acc_w    m/s^2 and rad/s^2, >= 0: what a control period may change
+    sim_time        s, > 0: how far a rollout looks
+    period          s, > 0: the control period"""
+    v_min: float = 0.0
+    v_max: float = 0.5
+    w_max: float = 1.0
+    acc_v: float = 0.5
+    acc_w: float = 2.0
+    sim_time: float = 2.0
+    period: float = 0.1
+
+    def __post_init__(self):
+        for f in dataclasses.fields(self):
+            v = float(getattr(self, f.name))
+            if not math.isfinite(v):
+                raise ValueError(f"LocalLimits: {f.name} = {v} must be finite")
+            setattr(self, f.name, v)
+        if self.v_min > self.v_max or max(abs(self.v_min), abs(self.v_max)) == 0.0:
+            raise ValueError(f"LocalLimits: v_min = {self.v_min}, v_max = {self.v_max}: v_min <= v_max and not both 0")
+        for f in ("w_max", "acc_v", "acc_w"):
+            if getattr(self, f) < 0.0:
+                raise ValueError(f"LocalLimits: {f} = {getattr(self, f)} must be >= 0")
+        for f in ("sim_time", "period"):
+            if not getattr(self, f) > 0.0:
+                raise ValueError(f"LocalLimits: {f} = {getattr(self, f)} must be > 0")
+
+    def step_dt(self, resolution):
+        """Seconds per step: the fastest allowed sample moves one cell per step."""
+        return float(resolution) / max(abs(self.v_min), abs(self.v_max))
+
+    def steps(self, resolution):
+        """The steps that cover sim_time, 1 .. 256."""
+        return int(min(max(round(self.sim_time / self.step_dt(resolution)), 1), PP_LOCAL_MAX_STEPS))
+
+    def window(self, v, w, nv, nw, resolution):
+        """The dynamic window round the current velocity (v m/s, w rad/s), clipped to the limits, as integers
+        (v0, dv, w0, dw): sample i, j has v0 + i * dv sub-cells and w0 + j * dw ticks per step.  The ends are rounded
+        inwards, so no sample lies outside the limits (nor outside |sv| <= 1024, |sw| <= 512); a window narrower than
+        one unit collapses onto the nearest admissible value."""
+        dt = self.step_dt(resolution)
+        ku, kw = SUB * dt / float(resolution), HEADINGS * dt / (2.0 * np.pi)       # units per m/s, per rad/s
+
+        def axis(cur, lo, hi, acc, k, cap, n):
+            lo_u, hi_u = max(math.ceil(lo * k - 1e-9), -cap), min(math.floor(hi * k + 1e-9), cap)
+            a = max(math.ceil(max(lo, cur - acc * self.period) * k - 1e-9), lo_u)
+            b = min(math.floor(min(hi, cur + acc * self.period) * k + 1e-9), hi_u)
+            if a > b:
+                a = b = min(max(int(round(cur * k)), lo_u), hi_u)
+            d = (b - a) // (n - 1) if n > 1 else 0
+            return int(a), int(d)
+
+        v0, dv = axis(float(v), self.v_min, self.v_max, self.acc_v, ku, MAX_SV, int(nv))
+        w0, dw = axis(float(w), -self.w_max, self.w_max, self.acc_w, kw, MAX_SW, int(nw))
+        return v0, dv, w0, dw
+
+
+def _batch_ints(v, B, n, who, what):
+    a = np.asarray(v)
+    if a.shape == (n,):
+        a = np.broadcast_to(a, (B, n))
+    if a.shape != (B, n) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{who}: {what} must be integers [{B}, {n}], got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(np.clip(a, -(2 ** 31), 2 ** 31 - 1), np.int32)
+
+
+def unpack_results(c, B, res, score, traj, keys):
+    """The buffers of pp_get_local_plan / pp_local_plan_grids -> a dict: the RESULT words int32 [B] each, `score` uint64
+    [B], `traj` a list of B arrays int32 [steps + 1, 3] ([0, 3] unless cmd_state is 0), `keys` uint64 [B, nv * nw] if
+    given."""
+    out = {k: res[:, i].copy() for i, k in enumerate(RESULT)}
+    out["score"] = score
+    if traj is not None:
+        out["traj"] = [traj[b].copy() if res[b, 0] == 0 else np.zeros((0, 3), np.int32) for b in range(B)]
+    if keys is not None:
+        out["keys"] = keys
+    return out
+
+
+def local_plan(grids, pots, poses, windows, navfn_cfg, cfg, goal_state=None, keys=False, device=0):
+    """The rule on the GPU, without an engine (pp_local_plan_grids): grids int8 and pots uint32 [H, W] or [B, H, W]
+    (H * W <= PP_OCC_MAX_CELLS), poses integers [B, 3] (or one), windows integers [B, 4] (or one), goal_state integers [B]
+    or None (all 0) -> a dict: the RESULT words and `score` per grid, `traj`, and `keys` if asked (ints and arrays for one
+    grid; int32 [B], uint64 [B], a list of B arrays and uint64 [B, nv * nw] for a batch)."""
+    n = _nav.NavfnConfig.from_any(navfn_cfg)
+    c = LocalPlanConfig.from_any(cfg)
+    a, p = np.asarray(grids), np.asarray(pots)
+    one = a.ndim == 2
+    if one:
+        a, p = a[None], p[None] if p.ndim == 2 else p
+    if a.dtype != np.int8 or a.ndim != 3 or a.size == 0:
+        raise ValueError(f"local_plan: grids must be int8 [H, W] or [B, H, W] with B, H, W >= 1, got {a.dtype} {np.asarray(grids).shape}")
+    if p.dtype != np.uint32 or p.shape != a.shape:
+        raise ValueError(f"local_plan: pots must be uint32 of the grids' shape {a.shape}, got {p.dtype} {p.shape}")
+    B, H, W = a.shape
+    if H * W > PP_OCC_MAX_CELLS:
+        raise ValueError(f"local_plan: H * W = {H * W} cells, at most PP_OCC_MAX_CELLS = {PP_OCC_MAX_CELLS}")
+    a, p = np.ascontiguousarray(a), np.ascontiguousarray(p)
+    P = _batch_ints(poses, B, 3, "local_plan", "poses")
+    Wn = _batch_ints(windows, B, 4, "local_plan", "windows")
+    for b in range(B):
+        check_window(Wn[b], c, f"local_plan: grid {b}")
+    gs = None if goal_state is None else np.ascontiguousarray(np.broadcast_to(np.asarray(goal_state), (B,)), np.int32)
+    trig = np.ascontiguousarray(_TRIG)
+    res = np.zeros((B, len(RESULT)), np.int32)
+    score = np.zeros(B, np.uint64)
+    traj = np.zeros((B, c.steps + 1, 3), np.int32)
+    kk = np.zeros((B, c.nv * c.nw), np.uint64) if keys else None
+    L = _lib.lib()
+    st = L.pp_local_plan_grids(int(device), a.ctypes.data, p.ctypes.data, B, H, W, ctypes.byref(_lib.PPNavfnConfig(**n.to_dict())),
+                               ctypes.byref(_lib.PPLocalPlanConfig(**c.to_dict())), trig.ctypes.data, len(trig), P.ctypes.data,
+                               Wn.ctypes.data, None if gs is None else gs.ctypes.data, res.ctypes.data, score.ctypes.data,
+                               traj.ctypes.data, None if kk is None else kk.ctypes.data)
+    if st != 0:
+        msg = L.pp_last_error(None)
+        raise (ValueError if st == 1 else RuntimeError)(f"local_plan: {msg.decode() if msg else st}")
+    out = unpack_results(c, B, res, score, traj, kk)
+    if one:
+        out = {k: (v[0] if isinstance(v, (list, np.ndarray)) else v) for k, v in out.items()}
+        out = {k: (int(v) if np.ndim(v) == 0 else v) for k, v in out.items()}
+    return out

@@ -35,7 +35,8 @@ Counts per grid: `reached`, the cells with pot != UNREACHED; `rounds`, the relax
 (implementation-defined, at least 1 where goal_state == 0).
 
 Out of scope: several goals per grid, escaping from a blocked start, interpolated potentials and gradient paths, path
-smoothing, a local planner or velocity commands, non-circular footprints, 3D, a configuration key, any ROS import.
+smoothing, non-circular footprints, 3D, a configuration key, any ROS import.  The local planner that reads this field
+and gives velocity commands is local_planner.py.
 """
 import ctypes
 import dataclasses

@@ -89,6 +89,12 @@ class VoxelNet:
         last occupancy_update (engine.set_inflation and engine.set_navfn for that source first)."""
         return self.engine.plan(goals, source, starts)
 
+    def drive(self, goals, velocities, limits, source="costmap", poses=None):
+        """Engine.drive: the velocity commands in m/s and rad/s towards `goals` over the inflated grids of the pass that has
+        just run, or of the last occupancy_update (engine.set_inflation, engine.set_navfn and engine.set_local_planner for
+        that source first)."""
+        return self.engine.drive(goals, velocities, limits, source, poses)
+
     def _need_p2(self, p2, who):
         if self.d.project_bbox and p2 is None:
             raise ValueError(f"{who}: model.second.project_bbox is on: pass p2 (the frames' camera matrices)")

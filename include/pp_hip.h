@@ -59,7 +59,10 @@ extern "C" {
  * (declared behind pp_occupancy_reset: the stage reads the grid either stage leaves on the device).  Then
  * PP_ERR_INTERNAL, PP_NAVFN_UNREACHED, PP_NAVFN_MAX_PATH, pp_navfn_config, pp_set_navfn, pp_get_navfn_config,
  * pp_navfn_async, pp_get_navfn, pp_navfn_info, pp_navfn_grids (declared behind pp_inflate_grids: the stage reads the
- * inflated grid where it lies). */
+ * inflated grid where it lies).  Then PP_LOCAL_SUB, PP_LOCAL_HEADINGS, PP_LOCAL_MAX_SAMPLES, PP_LOCAL_MAX_STEPS,
+ * PP_LOCAL_MAX_LOOKAHEAD, PP_LOCAL_RESULT, pp_local_plan_config, pp_set_local_plan, pp_get_local_plan_config,
+ * pp_local_plan_async, pp_get_local_plan, pp_local_plan_grids (declared behind pp_navfn_grids: the stage reads the
+ * inflated grid and the field where they lie). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -1462,6 +1465,71 @@ int pp_navfn_info(pp_handle h, int32_t source, int32_t* goal_state, int32_t* pat
 int pp_navfn_grids(int device, const int8_t* grids, int32_t batch, int32_t height, int32_t width,
                    const pp_navfn_config* cfg, const int32_t* goals, const int32_t* starts, uint32_t* pot, int32_t* paths,
                    int32_t* path_len, int32_t* info);
+
+/* ---- Local planner behind either navigation function, and of any int8 OccupancyGrid with its field
+ * (local_planner.py states the rule): a window of nv * nw (v, w) samples rolled forward from one pose per grid over the
+ * inflated grid, each scored on the cost-to-go field, and the least key's sample as the command.  Integers only: a
+ * position is int32 sub-cells (PP_LOCAL_SUB per cell), a heading one of PP_LOCAL_HEADINGS ticks (tick 0 is +x, ticks
+ * grow towards +y), and cos / sin come from a table of rint(cos / sin(2 pi h / 4096) * 2^14) that travels with the
+ * configuration.  Sample s = i * nw + j: sv = v0 + i * dv sub-cells per step (negative: reverse), sw = w0 + j * dw
+ * ticks per step, |sv| <= 1024 and |sw| <= 512.  A step: X += (sv * C[h] + 8192) >> 14, Y likewise with S[h], then
+ * h = (h + sw) & 4095; the cell (X >> 10, Y >> 10) outside the grid ends the sample as OUTSIDE, a blocked one
+ * (g >= lethal_cost, or unknown while allow_unknown is 0: the source's pp_navfn_config) as COLLISION, else occ =
+ * max(occ, g) with unknown_cost for an unknown cell.  The scored cell is the end pose pushed `lookahead` sub-cells along
+ * the final heading; outside, blocked or PP_NAVFN_UNREACHED there makes the sample UNREACHED.  score = pot_weight * pot +
+ * occ_weight * occ + speed_weight * (1024 - |sv|) + turn_weight * |sw| < 2^41, key = (score << 14) | s, 2^64 - 1 for an
+ * invalid sample; the least key wins.  cmd_state: 4 the field has no goal, 3 the pose's cell is outside, blocked or
+ * unreached, 2 arrived (pot 0 at the pose's cell), 1 no valid sample, 0 ok.  An opt-in stage: plain launches on the
+ * handle's stream, not part of a captured pass. ---- */
+#define PP_LOCAL_SUB 1024           /* sub-cells per cell */
+#define PP_LOCAL_HEADINGS 4096      /* heading ticks per revolution */
+#define PP_LOCAL_MAX_SAMPLES 16384  /* nv * nw at most */
+#define PP_LOCAL_MAX_STEPS 256
+#define PP_LOCAL_MAX_LOOKAHEAD 16384 /* sub-cells */
+#define PP_LOCAL_RESULT 8           /* int32 words per grid: cmd_state, best, sv, sw, n_ok, n_outside, n_collision, n_unreached */
+
+typedef struct pp_local_plan_config {
+    int32_t nv;            /* >= 1: velocity samples; nv * nw <= PP_LOCAL_MAX_SAMPLES */
+    int32_t nw;            /* >= 1: turn-rate samples */
+    int32_t steps;         /* 1 .. PP_LOCAL_MAX_STEPS */
+    int32_t lookahead;     /* 0 .. PP_LOCAL_MAX_LOOKAHEAD sub-cells */
+    int32_t pot_weight;    /* 0 .. 255 */
+    int32_t occ_weight;    /* 0 .. 65535 */
+    int32_t speed_weight;  /* 0 .. 65535 */
+    int32_t turn_weight;   /* 0 .. 65535 */
+} pp_local_plan_config;
+
+/* cfg == NULL: the source's stage off (the default); its buffers are kept.  Otherwise the configuration is validated
+ * (PP_ERR_ARG naming the field) and trig, int32 [n_trig][2] = (C[h], S[h]), is uploaded: n_trig must be
+ * PP_LOCAL_HEADINGS and every |value| <= 16384.  `source` is the inflation's.  Waits for the stream.  PP_ERR_STATE while
+ * a training step is in flight. */
+int pp_set_local_plan(pp_handle h, int32_t source, const pp_local_plan_config* cfg, const int32_t* trig, int32_t n_trig);
+/* *on: 0 / 1; cfg_out (may be NULL): the last configuration given for the source (zeros before the first). */
+int pp_get_local_plan_config(pp_handle h, int32_t source, int32_t* on, pp_local_plan_config* cfg_out);
+/* Queues the rollout and the command on the grids and fields of the source's last pp_navfn_async behind the rounds that
+ * call queued: poses int32 [batch][3] = (X, Y, h) sub-cells and a tick (h is taken & 4095), windows int32 [batch][4] =
+ * (v0, dv, w0, dw).  Reads the inflated grid and the field in place and never writes them.  Refused before anything is
+ * queued, PP_ERR_STATE: the stage or the source's navigation function is off, that navigation function has not run, the
+ * inflated grids were re-made since it ran, a training step is in flight; PP_ERR_ARG: a batch that is not the navigation
+ * function run's, poses or windows NULL, a sample with |sv| > 1024 or |sw| > 512, a bad source. */
+int pp_local_plan_async(pp_handle h, int32_t source, const int32_t* poses, const int32_t* windows, int32_t batch);
+/* The results of the source's last pp_local_plan_async.  First settles the field as pp_get_navfn does; if that queued a
+ * further round, or keys are asked for and were not stored, the rollout and the command are queued again, so a fetched
+ * command always rests on the exact field.  result int32 [batch][PP_LOCAL_RESULT]; score uint64 [batch] (0 unless
+ * cmd_state is 0); traj int32 [batch][steps + 1][3] poses, the start included (zeros unless cmd_state is 0); keys uint64
+ * [batch][nv * nw]; each may be NULL.  PP_ERR_STATE when none has run, a pp_navfn_async of the source came after it, or
+ * the launches have to be queued again and the inflated grids were re-made meanwhile; PP_ERR_ARG when batch is not that
+ * run's. */
+int pp_get_local_plan(pp_handle h, int32_t source, int32_t* result, uint64_t* score, int32_t* traj, uint64_t* keys,
+                      int32_t batch);
+/* Without a handle: grids int8 and pots uint32 [batch][height][width] in host memory (height * width <=
+ * PP_OCC_MAX_CELLS, batch <= 65535); of navfn_cfg only lethal_cost, allow_unknown and unknown_cost are read; trig as
+ * pp_set_local_plan takes it; goal_state int32 [batch] or NULL (all 0): nonzero gives cmd_state 4; outputs as
+ * pp_get_local_plan gives them, each may be NULL. */
+int pp_local_plan_grids(int device, const int8_t* grids, const uint32_t* pots, int32_t batch, int32_t height, int32_t width,
+                        const pp_navfn_config* navfn_cfg, const pp_local_plan_config* cfg, const int32_t* trig,
+                        int32_t n_trig, const int32_t* poses, const int32_t* windows, const int32_t* goal_state,
+                        int32_t* result, uint64_t* score, int32_t* traj, uint64_t* keys);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
