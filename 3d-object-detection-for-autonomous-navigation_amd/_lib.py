@@ -25,7 +25,7 @@ SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_
            "api_occupancy.hip", "occupancy.hip",
            "api_inflate.hip", "inflate.hip",
            "api_navfn.hip", "navfn.hip",
-           "api_local_plan.hip", "local_plan.hip",
+           "api_local_plan.hip", "local_plan.hip", "local_movers.hip",
            "api_track.hip", "track.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
@@ -64,6 +64,8 @@ EXPORTS = [
     "pp_inflate_grids",
     "pp_set_navfn", "pp_get_navfn_config", "pp_navfn_async", "pp_get_navfn", "pp_navfn_info", "pp_navfn_grids",
     "pp_set_local_plan", "pp_get_local_plan_config", "pp_local_plan_async", "pp_get_local_plan", "pp_local_plan_grids",
+    "pp_set_local_movers", "pp_get_local_movers_config", "pp_local_plan_movers_async", "pp_get_local_movers",
+    "pp_local_plan_grids_movers",
     "pp_set_nms_mode", "pp_get_nms_mode", "pp_rotate_nms",
     "pp_set_projection", "pp_get_projection", "pp_get_bboxes", "pp_box3d_to_bbox",
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
@@ -249,6 +251,10 @@ PP_LOCAL_MAX_SAMPLES = 16384    # pp_local_plan_config.nv * nw at most
 PP_LOCAL_MAX_STEPS = 256        # pp_local_plan_config.steps at most
 PP_LOCAL_MAX_LOOKAHEAD = 16384  # sub-cells: pp_local_plan_config.lookahead at most
 PP_LOCAL_RESULT = 8             # int32 words per grid of pp_get_local_plan's result
+PP_LOCAL_MAX_MOVERS = 64        # movers per grid (pp_local_plan_movers_async: a track slot each)
+PP_LOCAL_MAX_MOVER_SPEED = 16384    # sub-cells per step: |mvx|, |mvy| at most
+PP_LOCAL_MAX_MOVER_RADIUS = 32767   # sub-cells: r_soft at most
+PP_LOCAL_MOVER_INFO = 4         # int32 words per grid of pp_get_local_movers' info
 PP_CLIP_NONE, PP_CLIP_VALUE, PP_CLIP_NORM, PP_CLIP_GLOBAL_NORM = 0, 1, 2, 3      # enum pp_grad_clip_mode
 
 
@@ -362,6 +368,17 @@ class PPLocalPlanConfig(ctypes.Structure):
         ("occ_weight", ctypes.c_int32),
         ("speed_weight", ctypes.c_int32),
         ("turn_weight", ctypes.c_int32),
+    ]
+
+
+class PPLocalMoverConfig(ctypes.Structure):
+    _fields_ = [
+        ("pad_hard", ctypes.c_double),
+        ("pad_soft", ctypes.c_double),
+        ("horizon", ctypes.c_int32),
+        ("mover_weight", ctypes.c_int32),
+        ("confirmed_only", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
     ]
 
 
@@ -634,6 +651,12 @@ def lib():
     L.pp_get_local_plan.argtypes = [vp, i32, vp, vp, vp, vp, i32]
     L.pp_local_plan_grids.argtypes = [ctypes.c_int, vp, vp, i32, i32, i32, ctypes.POINTER(PPNavfnConfig),
                                       ctypes.POINTER(PPLocalPlanConfig), vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.pp_set_local_movers.argtypes = [vp, i32, ctypes.POINTER(PPLocalMoverConfig)]
+    L.pp_get_local_movers_config.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(PPLocalMoverConfig)]
+    L.pp_local_plan_movers_async.argtypes = [vp, i32, vp, vp, vp, i32]
+    L.pp_get_local_movers.argtypes = [vp, i32, vp, vp, i32]
+    L.pp_local_plan_grids_movers.argtypes = [ctypes.c_int, vp, vp, i32, i32, i32, ctypes.POINTER(PPNavfnConfig),
+                                             ctypes.POINTER(PPLocalPlanConfig), vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.pp_set_projection.argtypes = [vp, vp, i32]
     L.pp_get_projection.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_get_bboxes.argtypes = [vp, vp]

@@ -13,8 +13,20 @@
 //   finish   one wave per grid: the least of the partial keys (lane = chunk), the result words, and the winner rolled
 //            once more by lane 0 to write its trajectory.
 // Keys are unique (the sample index is their low 14 bits), so the minimum does not depend on any order; the counts are
-// integer sums.  No cooperative launch, no workgroup waits on another's memory, no float.  Every loop is bounded by an
-// argument the host has checked (api_local_plan.hip).
+// integer sums.  No cooperative launch, no workgroup waits on another's memory, no float atomics.  Every loop is bounded
+// by an argument the host has checked (api_local_plan.hip).
+//
+// MOVERS (pp_local_plan_movers_async, pp_local_plan_grids_movers): rollout and finish are templates on <bool MOVERS>, and
+// the instantiation without them is the code above, unchanged.  With them the workgroup also stages the grid's table of at
+// most 64 movers in LDS (1.5 KiB) behind a cull by its first wave (lane = mover): the robot moves at most 1024 sub-cells
+// along an axis per step, so a mover farther than 1024 * k + r_soft from the start pose along either axis at every step k
+// <= min(steps, horizon) touches no sample and is dropped -- no result depends on it.  A lane that is alive behind the
+// static test of step k <= horizon walks the staged movers (every lane reads the same entry: an LDS broadcast), rejects
+// one on 32-bit |dx| > r_soft || |dy| > r_soft, behind which d2 fits 32 bits; d2 <= r_hard^2 ends it as DYNAMIC exactly as
+// a blocked cell would, d2 <= r_soft^2 raises its `near`.  Finish recomputes the winner's near on the whole table, a
+// mover per lane.  The
+// table itself comes from the host (pp_local_plan_grids_movers) or from the track slots (k_local_movers, local_movers.hip:
+// the one place of the stage that is not integer arithmetic, and so a file of its own).
 #include "pp_common.h"
 
 namespace {
@@ -22,18 +34,29 @@ namespace {
 constexpr unsigned LOC_U = PP_NAVFN_UNREACHED;
 constexpr unsigned long long LOC_INVALID = ~0ull;
 constexpr int LOC_SHIFT = 10, LOC_HMASK = PP_LOCAL_HEADINGS - 1;
-constexpr int LOC_R_OK = 0, LOC_R_OUTSIDE = 1, LOC_R_COLLISION = 2, LOC_R_UNREACHED = 3;     // why a sample ended
+constexpr int LOC_R_OK = 0, LOC_R_OUTSIDE = 1, LOC_R_COLLISION = 2, LOC_R_UNREACHED = 3, LOC_R_DYNAMIC = 4;     // why a sample ended
+constexpr int LOC_MOVER_POS = 1 << 29;                   // |mx|, |my| at most
 static_assert((1 << LOC_SHIFT) == PP_LOCAL_SUB && (PP_LOCAL_HEADINGS & LOC_HMASK) == 0, "cells and ticks by shift and mask");
 static_assert(PP_LOCAL_MAX_SAMPLES == (1 << 14), "a key's low 14 bits are the sample index");
 static_assert(LOC_MAX_CHUNKS <= 64 && LOC_BLOCK % 64 == 0, "finish reads a grid's partial keys with one wave");
-// the score: pot < 2^32 - 1 by weight <= 255, occ <= 100, 1024 - |sv| <= 1024 and |sw| <= 512 by weights <= 65535
-static_assert(255ull * 0xFFFFFFFEull + 65535ull * 100ull + 65535ull * 1024ull + 65535ull * 512ull < (1ull << 41),
+// the score: pot < 2^32 - 1 by weight <= 255, occ <= 100, 1024 - |sv| <= 1024 and |sw| <= 512 by weights <= 65535; with
+// movers, near <= horizon <= PP_LOCAL_MAX_STEPS by a weight <= 65535
+static_assert(255ull * 0xFFFFFFFEull + 65535ull * 100ull + 65535ull * 1024ull + 65535ull * 512ull + 65535ull * PP_LOCAL_MAX_STEPS < (1ull << 41),
               "a score stays below 2^41, so (score << 14) | s never reaches the invalid key");
 // X and Y: a pose that is rolled lies in the grid (< 2^20 cells on a side), a step moves at most one cell along an axis and
 // the sample ends at its first cell outside; the scored point adds the lookahead
 static_assert(((long long)PP_OCC_MAX_CELLS + 1) * PP_LOCAL_SUB + PP_LOCAL_MAX_LOOKAHEAD < (1ll << 31), "X and Y fit int32");
 static_assert(1024 * 16384 + 8192 < (1ll << 31) && (long long)PP_LOCAL_MAX_LOOKAHEAD * 16384 + 8192 < (1ll << 31),
               "a step's and the lookahead's product fit int32");
+// a mover: its position at step k <= 256 fits int32, and so does dx = X - position, because X is only compared behind the
+// static test, which left it inside the grid: 0 <= X < 2^20 cells; dx * dx + dy * dy then fits int64
+constexpr long long LOC_MAX_MPOS = (long long)LOC_MOVER_POS + (long long)PP_LOCAL_MAX_STEPS * PP_LOCAL_MAX_MOVER_SPEED;
+constexpr long long LOC_MAX_DX = (long long)PP_OCC_MAX_CELLS * PP_LOCAL_SUB + LOC_MAX_MPOS;
+static_assert(LOC_MAX_MPOS < (1ll << 31) && LOC_MAX_DX < (1ll << 31), "a mover's position and dx fit int32");
+static_assert(LOC_MAX_DX < (1ll << 31) && 2 * (LOC_MAX_DX * LOC_MAX_DX) < (1ull << 63), "d2 fits int64");
+static_assert((long long)PP_LOCAL_MAX_MOVER_RADIUS * PP_LOCAL_MAX_MOVER_RADIUS < (1ll << 31), "r * r fits int32");
+static_assert(PP_LOCAL_MAX_MOVERS == 64 && PP_WAVE == 64, "the cull: one lane per mover");
+static_assert(PP_LOCAL_MAX_STEPS * 1024 + PP_LOCAL_MAX_MOVER_RADIUS < (1 << 30), "the cull's bound fits int32");
 
 __device__ __forceinline__ int loc_round(int a) { return (a + 8192) >> 14; }         // (arithmetic shift: floor)
 __device__ __forceinline__ int loc_cos(unsigned t) { return (int)(short)(t & 0xFFFFu); }
@@ -67,9 +90,41 @@ __device__ __forceinline__ unsigned long long loc_wave_min(unsigned long long ke
     return key;
 }
 
+// One mover against a pose (X, Y) at step k: bit 0 within r_hard, bit 1 within r_soft.  A mover with |dx| > r_soft or
+// |dy| > r_soft is rejected on those 32-bit values; what passes has |dx|, |dy| <= 32767, so d2 <= 2 * 32767^2 < 2^32 and
+// needs no 64-bit product at all (for a rejected mover the unsigned products may wrap: they are not looked at).  The
+// rollout's staged table ends in entries with r_soft = -1, which nothing passes.
+static_assert(2ull * PP_LOCAL_MAX_MOVER_RADIUS * PP_LOCAL_MAX_MOVER_RADIUS < (1ull << 32), "d2 of a mover that passes the reject fits 32 bits");
+__device__ __forceinline__ unsigned loc_mover_test(int mx, int my, int mvx, int mvy, int rh, int rs, int X, int Y, int k) {
+    const int dx = X - (mx + k * mvx), dy = Y - (my + k * mvy);
+    const bool in = abs(dx) <= rs && abs(dy) <= rs;
+    const unsigned d2 = (unsigned)dx * (unsigned)dx + (unsigned)dy * (unsigned)dy;
+    return ((in & (d2 <= (unsigned)(rh * rh))) ? 1u : 0u) | ((in & (d2 <= (unsigned)(rs * rs))) ? 2u : 0u);
+}
+
+// The movers' test of a pose (X, Y) that passed the static test of step k, 1 <= k <= horizon, against the n entries of
+// the staged table, four at a time (their LDS reads issue together; the table is padded to a multiple of four): true if
+// one ends the sample, else *near raised -- by the same amount whichever mover came near, so one flag per step serves.
+__device__ __forceinline__ bool loc_movers_hit(const int* mv, int n, int X, int Y, int k, int horizon, int* near) {
+    unsigned seen = 0;
+    for (int m0 = 0; m0 < n; m0 += 4) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int* e = mv + 6 * (m0 + j);
+            seen |= loc_mover_test(e[0], e[1], e[2], e[3], e[4], e[5], X, Y, k);
+        }
+        if (seen & 1u) return true;
+    }
+    if (seen & 2u) *near = max(*near, horizon + 1 - k);
+    return false;
+}
+
+template <bool MOVERS>
 __global__ __launch_bounds__(LOC_BLOCK) void k_local_rollout(LocalParams p) {
     __shared__ unsigned s_trig[PP_LOCAL_HEADINGS];
     __shared__ unsigned long long s_min[LOC_BLOCK / 64];
+    __shared__ int s_mov[MOVERS ? PP_LOCAL_MAX_MOVERS * 6 : 1];
+    __shared__ int s_nmov;
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const LocalCall c = p.call[b];
     const int8_t* grid = p.grid + (size_t)b * p.stride;
@@ -84,10 +139,38 @@ __global__ __launch_bounds__(LOC_BLOCK) void k_local_rollout(LocalParams p) {
         return;
     }
     for (int i = tid; i < PP_LOCAL_HEADINGS; i += LOC_BLOCK) s_trig[i] = p.trig[i];
+    if (MOVERS && wave == 0) {                           // the cull: lane = mover (the whole first wave is here)
+        const int nm = min(max(p.mover_info[LOC_M_COUNT * p.state_stride + b], 0), PP_LOCAL_MAX_MOVERS);
+        const int* e = p.movers + ((size_t)b * PP_LOCAL_MAX_MOVERS + lane) * 6;
+        int m[6] = {0, 0, 0, 0, 0, 0};
+        bool keep = false;
+        if (lane < nm) {
+#pragma unroll
+            for (int q = 0; q < 6; ++q) m[q] = e[q];
+            const int kmax = min(p.steps, p.horizon);
+            for (int k = 1; k <= kmax && !keep; ++k) {
+                const int reach = 1024 * k + m[5];
+                keep = abs(c.X - (m[0] + k * m[2])) <= reach && abs(c.Y - (m[1] + k * m[3])) <= reach;
+            }
+        }
+        const unsigned long long kept = __ballot(keep);
+        const int cnt = __popcll(kept);
+        if (keep) {
+            int* d = s_mov + 6 * __popcll(kept & ((1ull << lane) - 1ull));
+#pragma unroll
+            for (int q = 0; q < 6; ++q) d[q] = m[q];
+        }
+        if (lane >= cnt) {                               // behind the kept ones: entries that nothing passes
+#pragma unroll
+            for (int q = 0; q < 6; ++q) s_mov[6 * lane + q] = q < 4 ? 0 : -1;
+        }
+        if (lane == 0) s_nmov = cnt;
+    }
     __syncthreads();
+    const int nmov = MOVERS ? s_nmov : 0;
 
     const int sv = c.v0 + (live ? s / p.nw : 0) * c.dv, sw = c.w0 + (live ? s % p.nw : 0) * c.dw;
-    int X = c.X, Y = c.Y, h = c.h & LOC_HMASK, occ = 0;
+    int X = c.X, Y = c.Y, h = c.h & LOC_HMASK, occ = 0, near = 0;
     int reason = LOC_R_OK;
     bool alive = live;                                   // an ended lane loads nothing more and stays in the wave
     for (int k = 0; k < p.steps; ++k) {
@@ -98,7 +181,13 @@ __global__ __launch_bounds__(LOC_BLOCK) void k_local_rollout(LocalParams p) {
             h = (h + sw) & LOC_HMASK;
             const int g = loc_cell(p, grid, known, X >> LOC_SHIFT, Y >> LOC_SHIFT);
             if (g < 0) { reason = g == -2 ? LOC_R_OUTSIDE : LOC_R_COLLISION; alive = false; }
-            else occ = max(occ, g);
+            else {
+                occ = max(occ, g);
+                if (MOVERS && k < p.horizon && loc_movers_hit(s_mov, nmov, X, Y, k + 1, p.horizon, &near)) {
+                    reason = LOC_R_DYNAMIC;
+                    alive = false;
+                }
+            }
         }
         if (!__any(alive)) break;                        // (the same answer in every lane of the wave)
     }
@@ -111,8 +200,9 @@ __global__ __launch_bounds__(LOC_BLOCK) void k_local_rollout(LocalParams p) {
         if (loc_cell(p, grid, known, cx, cy) >= 0) v = pot[(size_t)cy * p.pitch + cx];
         if (v == LOC_U) reason = LOC_R_UNREACHED;
         else {
-            const unsigned long long score = (unsigned long long)p.pot_w * v + (unsigned long long)(p.occ_w * occ) +
-                                             (unsigned long long)(p.speed_w * (1024 - abs(sv))) + (unsigned long long)(p.turn_w * abs(sw));
+            unsigned long long score = (unsigned long long)p.pot_w * v + (unsigned long long)(p.occ_w * occ) +
+                                       (unsigned long long)(p.speed_w * (1024 - abs(sv))) + (unsigned long long)(p.turn_w * abs(sw));
+            if (MOVERS) score += (unsigned long long)(p.mover_w * near);
             key = (score << 14) | (unsigned)s;
         }
     }
@@ -124,6 +214,10 @@ __global__ __launch_bounds__(LOC_BLOCK) void k_local_rollout(LocalParams p) {
         const int cnt = __popcll(__ballot(live && reason == r));
         if (lane == 0 && cnt) atomicAdd(st + (LOC_N_OK + r) * p.state_stride, cnt);
     }
+    if (MOVERS) {
+        const int cnt = __popcll(__ballot(live && reason == LOC_R_DYNAMIC));
+        if (lane == 0 && cnt) atomicAdd(p.mover_info + LOC_M_DYNAMIC * p.state_stride + b, cnt);
+    }
     key = loc_wave_min(key);
     if (lane == 0) s_min[wave] = key;
     __syncthreads();
@@ -134,6 +228,7 @@ __global__ __launch_bounds__(LOC_BLOCK) void k_local_rollout(LocalParams p) {
     }
 }
 
+template <bool MOVERS>
 __global__ __launch_bounds__(64) void k_local_finish(LocalParams p) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const LocalCall c = p.call[b];
@@ -156,25 +251,43 @@ __global__ __launch_bounds__(64) void k_local_finish(LocalParams p) {
             st[LOC_SV * ss] = 0;
             st[LOC_SW * ss] = 0;
             p.score[b] = 0;
+            if (MOVERS) p.mover_info[LOC_M_NEAR * ss + b] = 0;
         }
         return;
     }
-    if (lane != 0) return;
+    // Without movers lane 0 alone rolls the winner.  With them every lane rolls it, the same values in each, and lane m
+    // holds mover m of the grid's whole table against it: the winner's near is the wave's greatest.
+    if (!MOVERS && lane != 0) return;
     const int s = (int)(key & (PP_LOCAL_MAX_SAMPLES - 1));
     const int sv = c.v0 + (s / p.nw) * c.dv, sw = c.w0 + (s % p.nw) * c.dw;
-    st[LOC_CMD_STATE * ss] = 0;
-    st[LOC_BEST * ss] = s;
-    st[LOC_SV * ss] = sv;
-    st[LOC_SW * ss] = sw;
-    p.score[b] = key >> 14;
-    int X = c.X, Y = c.Y, h = c.h & LOC_HMASK;
-    traj[0] = X; traj[1] = Y; traj[2] = h;
+    if (lane == 0) {
+        st[LOC_CMD_STATE * ss] = 0;
+        st[LOC_BEST * ss] = s;
+        st[LOC_SV * ss] = sv;
+        st[LOC_SW * ss] = sw;
+        p.score[b] = key >> 14;
+    }
+    int m[6] = {0, 0, 0, 0, -1, -1};
+    if (MOVERS && lane < min(max(p.mover_info[LOC_M_COUNT * ss + b], 0), PP_LOCAL_MAX_MOVERS)) {
+        const int* e = p.movers + ((size_t)b * PP_LOCAL_MAX_MOVERS + lane) * 6;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) m[q] = e[q];
+    }
+    int X = c.X, Y = c.Y, h = c.h & LOC_HMASK, near = 0;
+    if (lane == 0) { traj[0] = X; traj[1] = Y; traj[2] = h; }
     for (int k = 1; k <= p.steps; ++k) {                 // the winner took every step inside the grid
         const unsigned t = p.trig[h];
         X += loc_round(sv * loc_cos(t));
         Y += loc_round(sv * loc_sin(t));
         h = (h + sw) & LOC_HMASK;
-        traj[3 * k] = X; traj[3 * k + 1] = Y; traj[3 * k + 2] = h;
+        if (lane == 0) { traj[3 * k] = X; traj[3 * k + 1] = Y; traj[3 * k + 2] = h; }
+        if (MOVERS && k <= p.horizon && (loc_mover_test(m[0], m[1], m[2], m[3], m[4], m[5], X, Y, k) & 2u))     // (none ended it)
+            near = max(near, p.horizon + 1 - k);
+    }
+    if (MOVERS) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) near = max(near, __shfl_xor(near, d));
+        if (lane == 0) p.mover_info[LOC_M_NEAR * ss + b] = near;
     }
 }
 
@@ -183,10 +296,12 @@ __global__ __launch_bounds__(64) void k_local_finish(LocalParams p) {
 void launch_local_rollout(const LocalParams& p, hipStream_t s) {
     if (p.batch <= 0) return;
     const int chunks = (p.nv * p.nw + LOC_BLOCK - 1) / LOC_BLOCK;
-    PP_LAUNCH("k_local_rollout", k_local_rollout, dim3(chunks, p.batch), dim3(LOC_BLOCK), 0, s, p);
+    if (p.movers) PP_LAUNCH("k_local_rollout_movers", k_local_rollout<true>, dim3(chunks, p.batch), dim3(LOC_BLOCK), 0, s, p);
+    else PP_LAUNCH("k_local_rollout", k_local_rollout<false>, dim3(chunks, p.batch), dim3(LOC_BLOCK), 0, s, p);
 }
 
 void launch_local_finish(const LocalParams& p, hipStream_t s) {
     if (p.batch <= 0) return;
-    PP_LAUNCH("k_local_finish", k_local_finish, dim3(p.batch), dim3(64), 0, s, p);
+    if (p.movers) PP_LAUNCH("k_local_finish_movers", k_local_finish<true>, dim3(p.batch), dim3(64), 0, s, p);
+    else PP_LAUNCH("k_local_finish", k_local_finish<false>, dim3(p.batch), dim3(64), 0, s, p);
 }

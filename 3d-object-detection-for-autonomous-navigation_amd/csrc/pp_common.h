@@ -828,9 +828,33 @@ struct LocalParams {
     unsigned long long* score;     // [batch]
     int* traj;                     // [batch][steps + 1][3]
     unsigned long long* keys;      // [batch][nv * nw], or NULL: not stored
+    // the movers (pp_local_plan_movers_async, pp_local_plan_grids_movers); NULL: none, and the kernels' instantiations
+    // without them run, which read nothing below
+    const int* movers;             // [batch][PP_LOCAL_MAX_MOVERS][6]: mx, my, mvx, mvy, r_hard, r_soft
+    int* mover_info;               // [PP_LOCAL_MOVER_INFO][state_stride], as LOC_M_* names the fields
+    int horizon, mover_w;          // pp_local_mover_config
 };
+// n_movers (-1: the stream has had no posed step; rolled as 0) and n_skipped are written by k_local_movers or the host,
+// n_dynamic is cleared before the rollout and added to by it, near is written by finish
+enum { LOC_M_COUNT = 0, LOC_M_SKIPPED = 1, LOC_M_DYNAMIC = 2, LOC_M_NEAR = 3 };
 void launch_local_rollout(const LocalParams& p, hipStream_t s);     // the reason counts of `state` cleared before it
 void launch_local_finish(const LocalParams& p, hipStream_t s);
+struct LocalFrame {                // what travels from the host per grid and pp_local_plan_movers_async: 4 doubles
+    double ox, oy, res, dt;        // the metres of cell [0, 0]'s corner and of a cell, the seconds of a step
+};
+struct LocalMoverParams {
+    int batch;
+    int fixed;                     // 1: the slots are carried into the fixed frame with pose_prev (the occupancy source)
+    int confirmed_only;
+    double pad_hard, pad_soft;
+    const TrkSlot* slots;          // [B][PP_TRACK_MAX]
+    const TrkPose* pose_prev;      // [B]
+    const LocalFrame* frame;       // [batch]
+    int* movers;                   // [batch][PP_LOCAL_MAX_MOVERS][6]; zeros behind a grid's movers
+    int* mover_info;               // [PP_LOCAL_MOVER_INFO][info_stride]: writes LOC_M_COUNT and LOC_M_SKIPPED
+    int info_stride;
+};
+void launch_local_movers(const LocalMoverParams& p, hipStream_t s);
 
 // weight_publish.hip: the trainer's flat parameter / state buffers -> the detector's weight arrays, on the device
 enum PubKind {

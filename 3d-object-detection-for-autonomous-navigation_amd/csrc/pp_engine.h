@@ -489,7 +489,15 @@ struct pp_engine {
         LocalParams run = {};              // ... what it was launched with
         unsigned long long nav_run = 0;    // navfn[source].run_id it was queued behind
         int nav_rounds = 0;                // navfn[source].rounds its last launches were queued behind
-    } local[2];                            // by source, as infl
+        // pp_set_local_movers: the stream's tracks as movers of pp_local_plan_movers_async (k_local_movers in front of
+        // the rollout); `run.movers` says whether the last run had them
+        bool movers_on = false;            // pp_set_local_movers gave a configuration and has not taken it back
+        pp_local_mover_config mcfg = {};   // the last configuration given
+        int* movers = nullptr;             // [B][PP_LOCAL_MAX_MOVERS][6]; this and the next two live as long as the handle (`allocs`)
+        int* mover_info = nullptr;         // [PP_LOCAL_MOVER_INFO][B]
+        LocalFrame* d_frame = nullptr;     // [B]
+        RingArray<LocalFrame> h_frame;     // [B] per slot, a rider of `ring`
+    } local[2];                           // by source, as infl
     unsigned long long resident_gen = 0;   // counts the changes of the resident frames (set_resident, a stage call)
     unsigned long long results_gen = 0;    // resident_gen of the last pp_detect_async
 

@@ -427,6 +427,7 @@ class Engine:
         self._infl_run = {}                                     # source index -> (batch, (H, W)) of its last inflate_async
         self._navfn_run = {}                                    # source index -> (batch, (H, W), max_path, origins, resolution) of its last navfn_async
         self._local_run = {}                                    # source index -> (batch, LocalPlanConfig, resolution or None, step dt or None) of its last local_plan_async
+        self._local_movers_run = {}                             # source index -> the MoverConfig that run used, or None
         if d.costmap is not None:
             self.set_costmap(d.costmap)
         if weights is not None:
@@ -1424,12 +1425,43 @@ class Engine:
         self._check(self._lib.pp_get_local_plan_config(self._h, k, ctypes.byref(on), ctypes.byref(pc)), "pp_get_local_plan_config")
         return _from_struct(_loc.LocalPlanConfig, pc) if on.value else None
 
-    def _local_cells_async(self, k, poses, windows, resolution=None, dt=None):
-        """pp_local_plan_async on integers: poses int32 [B, 3] (X, Y, h), windows int32 [B, 4] (v0, dv, w0, dw)."""
+    def set_local_movers(self, cfg, source="costmap"):
+        """A local_planner.MoverConfig, a dict of its fields or True (the defaults) for `source`: `local_plan_async(...,
+        dt=)` / `drive` then turn the live tracks of stream b into the movers of grid b on the GPU, where the track table
+        lies (set_tracking first), and test every sample, step by step, against each mover's position at that step
+        (pp_set_local_movers, pp_local_plan_movers_async; local_planner.py states both rules).  The tracks are read in the
+        sensor frame for "costmap" and carried into the fixed frame by the pose of the stream's last posed tracking step
+        for "occupancy".  None: off (the default), and every launch and result is what it was."""
+        k = self._infl_source(source)
+        if cfg is None or cfg is False:
+            self._check(self._lib.pp_set_local_movers(self._h, k, None), "pp_set_local_movers")
+            return
+        pc = _to_struct(_lib.PPLocalMoverConfig, _loc.MoverConfig.from_any(cfg))
+        self._check(self._lib.pp_set_local_movers(self._h, k, ctypes.byref(pc)), "pp_set_local_movers")
+
+    def local_movers_config(self, source="costmap"):
+        """The MoverConfig in force for `source`, or None while its movers are off."""
+        k = self._infl_source(source)
+        on, pc = ctypes.c_int32(0), _lib.PPLocalMoverConfig()
+        self._check(self._lib.pp_get_local_movers_config(self._h, k, ctypes.byref(on), ctypes.byref(pc)), "pp_get_local_movers_config")
+        return _from_struct(_loc.MoverConfig, pc) if on.value else None
+
+    def _local_cells_async(self, k, poses, windows, resolution=None, dt=None, frame=None):
+        """pp_local_plan_async on integers: poses int32 [B, 3] (X, Y, h), windows int32 [B, 4] (v0, dv, w0, dw).  frame
+        float64 [B, 4] (ox, oy, res, dt): pp_local_plan_movers_async, the source's movers in front."""
         P = np.ascontiguousarray(poses, np.int32)
         Wn = np.ascontiguousarray(windows, np.int32)
-        self._check(self._lib.pp_local_plan_async(self._h, k, _ptr(P), _ptr(Wn), int(P.shape[0])), "pp_local_plan_async")
+        mc = None
+        if frame is None:
+            self._check(self._lib.pp_local_plan_async(self._h, k, _ptr(P), _ptr(Wn), int(P.shape[0])), "pp_local_plan_async")
+        else:
+            F = np.ascontiguousarray(frame, np.float64)
+            if F.shape != (P.shape[0], 4):
+                raise ValueError(f"local_plan_async: frame must be (ox, oy, res, dt) [{P.shape[0]}, 4], got {F.shape}")
+            self._check(self._lib.pp_local_plan_movers_async(self._h, k, _ptr(P), _ptr(Wn), _ptr(F), int(P.shape[0])), "pp_local_plan_movers_async")
+            mc = self.local_movers_config(_infl.SOURCES[k])
         self._local_run[k] = (int(P.shape[0]), self.local_planner_config(_infl.SOURCES[k]), resolution, dt)
+        self._local_movers_run[k] = mc
 
     def local_plan_async(self, poses=None, windows=None, source="costmap", dt=None):
         """Queues the rollout and the command on the grids and fields of the source's last navfn_async behind the
@@ -1439,12 +1471,16 @@ class Engine:
         sub-cells and ticks through local_planner.pose_ticks with the navfn run's origins and the source's resolution, so
         a pose outside its window is no error (cmd_state 3).  windows integers [B, 4] (v0, dv, w0, dw) (or one), as
         local_planner.LocalLimits.window makes them; None: sv from 0 to 1024 and sw from -512 to 512.  dt: the seconds of
-        a step, which `local_commands(metric=True)` needs."""
+        a step, which `local_commands(metric=True)` needs -- and the source's movers, while set_local_movers has them
+        on: the call then builds their table from the streams' tracks first (pp_local_plan_movers_async)."""
         k = self._infl_source(source)
         B, _, _, org, res = self._navfn_last(k, "local_plan_async")
         c = self.local_planner_config(source)
         if c is None:
             raise RuntimeError(f"local_plan_async: the local planner of the {source} source is not configured (set_local_planner first)")
+        movers = self.local_movers_config(source) is not None
+        if movers and dt is None:
+            raise ValueError(f"local_plan_async: dt is None and the movers of the {source} source are on: they need the seconds of a step (dt=)")
         if org is None:
             raise RuntimeError("local_plan_async: the navigation function was given cells, it has no frame in metres")
         if poses is None:
@@ -1464,7 +1500,12 @@ class Engine:
         Wn = _loc._batch_ints(windows, B, 4, "local_plan_async", "windows")
         for b in range(B):
             _loc.check_window(Wn[b], c, f"local_plan_async: grid {b}")
-        self._local_cells_async(k, ticks, Wn, res, None if dt is None else float(dt))
+        frame = None
+        if movers:
+            frame = np.empty((B, 4))
+            frame[:, :2] = np.broadcast_to(np.atleast_2d(np.asarray(org, np.float64)), (B, 2))
+            frame[:, 2], frame[:, 3] = float(res), float(dt)
+        self._local_cells_async(k, ticks, Wn, res, None if dt is None else float(dt), frame)
 
     def _local_last(self, k, who):
         if k not in self._local_run:
@@ -1509,8 +1550,26 @@ class Engine:
 
     def local_plan_info(self, source="costmap"):
         """Per grid of the source's last local_plan_async (waits as local_commands does): `cmd_state`, `best`, `sv`, `sw`,
-        `n_ok`, `n_outside`, `n_collision`, `n_unreached` int32 [B] each and `score` uint64 [B]."""
-        return self._local_fetch(self._infl_source(source), "local_plan_info")
+        `n_ok`, `n_outside`, `n_collision`, `n_unreached` int32 [B] each and `score` uint64 [B]; where that run had movers
+        also `n_movers`, `n_skipped`, `n_dynamic` and `near` int32 [B]."""
+        k = self._infl_source(source)
+        out = self._local_fetch(k, "local_plan_info")
+        if self._local_movers_run.get(k) is not None:
+            out.update(self.local_movers(source)[1])
+        return out
+
+    def local_movers(self, source="costmap"):
+        """(movers int32 [B, 64, 6] -- (mx, my, mvx, mvy, r_hard, r_soft) per mover, zeros behind a grid's n_movers --, info:
+        `n_movers` (-1: an occupancy stream that has had no posed tracking step), `n_skipped`, `n_dynamic`, `near` int32 [B]
+        each) of the source's last local_plan_async with movers (waits as local_commands does; pp_get_local_movers)."""
+        k = self._infl_source(source)
+        B = self._local_last(k, "local_movers")[0]
+        if self._local_movers_run.get(k) is None:
+            raise RuntimeError(f"local_movers: the last local plan of the {source} source had no movers (set_local_movers first)")
+        M = np.zeros((B, _lib.PP_LOCAL_MAX_MOVERS, 6), np.int32)
+        info = np.zeros((B, _lib.PP_LOCAL_MOVER_INFO), np.int32)
+        self._check(self._lib.pp_get_local_movers(self._h, k, _ptr(M), _ptr(info), B), "pp_get_local_movers")
+        return M, {name: info[:, i].copy() for i, name in enumerate(_loc.MOVER_INFO)}
 
     def _plan_async(self, goals, source, starts):
         """What `plan` queues: the source's grids, their inflation, the field and the paths."""
@@ -1526,7 +1585,8 @@ class Engine:
         return k
 
     def drive(self, goals, velocities, limits, source="costmap", poses=None):
-        """(v float64 [B] m/s, w float64 [B] rad/s, cmd_state int32 [B]) towards `goals` (as navfn_async takes them): what
+        """(v float64 [B] m/s, w float64 [B] rad/s, cmd_state int32 [B]) towards `goals` (as navfn_async takes them; with
+        set_local_movers on, round the streams' moving tracks): what
         `plan` queues, then the local planner on the dynamic windows round the current `velocities` float64 [B, 2] (v m/s,
         w rad/s) (or one) under `limits`, a local_planner.LocalLimits; a step lasts limits.step_dt(resolution), so a
         rollout looks steps * step_dt ahead (LocalLimits.steps gives the steps for its sim_time).  poses as

@@ -38,9 +38,38 @@ the counts are 0.
 Results per grid: cmd_state, best, sv, sw; the counts n_ok, n_outside, n_collision, n_unreached; score; the winning
 trajectory int32 [steps + 1, 3] poses, the start included; all nv * nw keys uint64 on request.
 
-Out of scope: escaping from a blocked pose, footprints other than a point on the inflated grid, holonomic (vy) samples,
-oscillation suppression between cycles, goal-orientation alignment, a diagonal step passing between two blocked cells that
-touch only at a corner (an inscribed radius of one cell or more rules this out), a configuration key, any ROS import.
+MOVERS (opt-in: `movers=` / `mcfg=` here, Engine.set_local_movers behind an engine).  The grid has no time; a mover has.
+A mover is six int32 (mx, my, mvx, mvy, r_hard, r_soft): its position at step 0 in sub-cells of the grid's frame (it may
+lie outside the grid), its movement per rollout step, and two radii, all in sub-cells; |mx|, |my| <= 2^29, |mvx|, |mvy|
+<= PP_LOCAL_MAX_MOVER_SPEED = 16384, 0 <= r_hard <= r_soft <= PP_LOCAL_MAX_MOVER_RADIUS = 32767, at most
+PP_LOCAL_MAX_MOVERS = 64 per grid.  MoverConfig.horizon (0 .. 256) is the steps over which a prediction is trusted,
+mover_weight (0 .. 65535) what a near miss costs.  The rollout is unchanged up to and including the static test of step
+k (OUTSIDE, then COLLISION, then occ).  A sample still alive then, with k <= horizon, looks at every mover in table
+order: dx = X - (mx + k * mvx), dy = Y - (my + k * mvy), d2 = dx * dx + dy * dy, exact integers (int64 holds them); d2 <=
+r_hard^2 ends the sample as DYNAMIC (reason 4; later movers and steps are not looked at), otherwise d2 <= r_soft^2 sets
+near = max(near, horizon + 1 - k): an earlier near miss weighs more.  Neither the start pose (k = 0) nor the lookahead
+point is tested against movers.  The score gains mover_weight * near and stays below 2^41; key, tie rule and states are
+unchanged, so where every sample ends invalid cmd_state is 1 and the robot stops for a pedestrian it cannot pass.
+Further results per grid (MOVER_INFO): n_movers (-1: see below), n_skipped, n_dynamic and near, the winner's (0 unless
+cmd_state is 0); n_ok + n_outside + n_collision + n_unreached + n_dynamic = nv * nw in states 0 and 1.
+
+FROM TRACKS TO MOVERS (`movers_np`; k_local_movers on the GPU, where the track table lies).  Float64, operation by
+operation in this order, floor, rint (half to even) and ceil the only roundings, no sqrt, no trig.  A track row gives x y
+z vx vy vz w l in the grid's frame: the slot as it stands for the costmap source (`Engine.tracks()`), the slot carried into
+the fixed frame by the pose of the stream's last posed tracking step for the occupancy source (`Engine.tracks_fixed()`; a
+stream without one has n_movers = -1 and is rolled with no movers).  With the grid's origin (ox, oy) and resolution res
+in metres and dt seconds per step: MX = floor(((x - ox) / res) * 1024.0), MY likewise; MVX = rint(((vx * dt) / res) *
+1024.0), MVY likewise; RH = ceil(((fmax(w, l) * 0.5 + pad_hard) / res) * 1024.0) and RS with pad_soft, both clipped to [0,
+32767] -- the planner's robot is a point, so its radius belongs in the pads.  A live row (a confirmed one where
+confirmed_only is set) becomes a mover in ascending slot order; one with a non-finite input, |MX| or |MY| > 2^29 or |MVX|
+or |MVY| > 16384 is skipped and counted in n_skipped.
+
+Out of scope: escaping from a blocked pose, footprints other than a point on the inflated grid for the robot (against a
+mover its radius rides in pad_hard / pad_soft), holonomic (vy) samples, oscillation suppression between cycles,
+goal-orientation alignment, a diagonal step passing between two blocked cells that touch only at a corner (an inscribed
+radius of one cell or more rules this out), a configuration key, any ROS import.  Of the movers: swept collision between
+two steps (a fast mover can tunnel through a small radius), rectangular mover shapes, a lead time between the tracks' stamp
+and now, movers that react to the robot.
 """
 import ctypes
 import dataclasses
@@ -50,8 +79,9 @@ import numpy as np
 
 from . import _lib
 from . import navfn as _nav
-from ._lib import (PP_LOCAL_HEADINGS, PP_LOCAL_MAX_LOOKAHEAD, PP_LOCAL_MAX_SAMPLES, PP_LOCAL_MAX_STEPS, PP_LOCAL_SUB,
-                   PP_OCC_MAX_CELLS)
+from ._lib import (PP_LOCAL_HEADINGS, PP_LOCAL_MAX_LOOKAHEAD, PP_LOCAL_MAX_MOVER_RADIUS, PP_LOCAL_MAX_MOVER_SPEED,
+                   PP_LOCAL_MAX_MOVERS, PP_LOCAL_MAX_SAMPLES, PP_LOCAL_MAX_STEPS, PP_LOCAL_MOVER_INFO, PP_LOCAL_SUB,
+                   PP_OCC_MAX_CELLS, PP_TRACK_MAX)
 
 SUB = PP_LOCAL_SUB
 HEADINGS = PP_LOCAL_HEADINGS
@@ -59,6 +89,9 @@ ONE = 1 << 14                           # the trig table's 1.0
 MAX_SV, MAX_SW = 1024, 512              # |sv| sub-cells and |sw| ticks per step at most
 INVALID = 2 ** 64 - 1                   # the key of a sample that did not end OK
 OK, OUTSIDE, COLLISION, UNREACHED = 0, 1, 2, 3      # why a sample ended
+DYNAMIC = 4                             # ... within r_hard of a mover (only with movers)
+MAX_MOVER_POS = 1 << 29                 # |mx|, |my| at most
+MOVER_INFO = ("n_movers", "n_skipped", "n_dynamic", "near")      # pp_get_local_movers' words
 STATE_OK, STATE_NO_SAMPLE, STATE_ARRIVED, STATE_POSE, STATE_NO_GOAL = 0, 1, 2, 3, 4
 RESULT = ("cmd_state", "best", "sv", "sw", "n_ok", "n_outside", "n_collision", "n_unreached")      # pp_get_local_plan's words
 
@@ -66,12 +99,19 @@ _RANGES = (("nv", 1, PP_LOCAL_MAX_SAMPLES), ("nw", 1, PP_LOCAL_MAX_SAMPLES), ("s
            ("lookahead", 0, PP_LOCAL_MAX_LOOKAHEAD), ("pot_weight", 0, 255), ("occ_weight", 0, 65535),
            ("speed_weight", 0, 65535), ("turn_weight", 0, 65535))
 MAX_SCORE = 255 * (_nav.UNREACHED - 1) + 65535 * 100 + 65535 * 1024 + 65535 * 512
+MAX_SCORE_MOVERS = MAX_SCORE + 65535 * PP_LOCAL_MAX_STEPS   # mover_weight * near: near <= horizon + 1 - 1 <= 256
 assert SUB == 1 << 10 and HEADINGS == 1 << 12 and MAX_SV == SUB and PP_LOCAL_MAX_SAMPLES == 1 << 14
-assert MAX_SCORE < 2 ** 41                                  # so (score << 14) | s < 2^55 never reaches INVALID
+assert MAX_SCORE < MAX_SCORE_MOVERS < 2 ** 41                             # so (score << 14) | s < 2^55 never reaches INVALID
 # X and Y fit int32: a rolled pose lies in the grid, a step moves at most one cell and a sample ends at its first cell
 # outside; the scored point adds the lookahead
 assert (PP_OCC_MAX_CELLS + 1) * SUB + PP_LOCAL_MAX_LOOKAHEAD < 2 ** 31
 assert MAX_SV * ONE + 8192 < 2 ** 31 and PP_LOCAL_MAX_LOOKAHEAD * ONE + 8192 < 2 ** 31       # the products do too
+# a mover's position at step k <= 256 fits int32, and dx = X - position too: X is compared only behind the static test,
+# which left it inside the grid (0 <= X < 2^20 cells); d2 = dx * dx + dy * dy then fits int64
+_MAX_MPOS = MAX_MOVER_POS + PP_LOCAL_MAX_STEPS * PP_LOCAL_MAX_MOVER_SPEED
+_MAX_DX = PP_OCC_MAX_CELLS * SUB + _MAX_MPOS
+assert _MAX_MPOS < 2 ** 31 and _MAX_DX < 2 ** 31 and 2 * _MAX_DX * _MAX_DX < 2 ** 63
+assert PP_LOCAL_MAX_MOVER_RADIUS ** 2 < 2 ** 31 and PP_LOCAL_MAX_MOVERS == PP_TRACK_MAX and len(MOVER_INFO) == PP_LOCAL_MOVER_INFO
 
 
 @dataclasses.dataclass
@@ -117,6 +157,129 @@ class LocalPlanConfig:
                 raise ValueError(f"local_planner: unknown keys {sorted(unknown)}")
             return cls(**cfg)
         raise ValueError(f"local_planner: a LocalPlanConfig, a dict of its fields or True, got {cfg!r}")
+
+
+@dataclasses.dataclass
+class MoverConfig:
+    """horizon         0 .. 256: rollout steps over which a mover's prediction is trusted (0: movers are never tested)
+    mover_weight    0 .. 65535: what one unit of `near` adds to the score
+    pad_hard        metres, finite, >= 0: added to max(w, l) / 2 for r_hard -- the robot's radius belongs here
+    pad_soft        metres, finite, >= pad_hard: ... for r_soft
+    confirmed_only  only confirmed tracks become movers"""
+    horizon: int = 32
+    mover_weight: int = 64
+    pad_hard: float = 0.3
+    pad_soft: float = 0.8
+    confirmed_only: bool = True
+
+    def __post_init__(self):
+        for f, lo, hi in (("horizon", 0, PP_LOCAL_MAX_STEPS), ("mover_weight", 0, 65535)):
+            v = getattr(self, f)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"MoverConfig: {f} must be an integer, got {v!r}")
+            if int(v) < lo or int(v) > hi:
+                raise ValueError(f"MoverConfig: {f} = {v} outside [{lo}, {hi}]")
+            setattr(self, f, int(v))
+        for f in ("pad_hard", "pad_soft"):
+            v = getattr(self, f)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)):
+                raise ValueError(f"MoverConfig: {f} must be a finite number of metres, got {v!r}")
+            setattr(self, f, float(v))
+        if not 0.0 <= self.pad_hard <= self.pad_soft:
+            raise ValueError(f"MoverConfig: pad_hard = {self.pad_hard}, pad_soft = {self.pad_soft}: 0 <= pad_hard <= pad_soft")
+        if not isinstance(self.confirmed_only, (bool, np.bool_)) and self.confirmed_only not in (0, 1):
+            raise ValueError(f"MoverConfig: confirmed_only must be a bool, got {self.confirmed_only!r}")
+        self.confirmed_only = bool(self.confirmed_only)
+
+    def to_dict(self):
+        return dataclasses.asdict(self)
+
+    @classmethod
+    def from_any(cls, cfg):
+        """A MoverConfig, a dict of its fields (unknown keys raise, naming them) or True (the defaults)."""
+        if isinstance(cfg, cls):
+            return cfg
+        if cfg is True:
+            return cls()
+        if isinstance(cfg, dict):
+            unknown = set(cfg) - {f.name for f in dataclasses.fields(cls)}
+            if unknown:
+                raise ValueError(f"local_planner: unknown keys {sorted(unknown)}")
+            return cls(**cfg)
+        raise ValueError(f"local_planner: a MoverConfig, a dict of its fields or True, got {cfg!r}")
+
+
+def check_movers(movers, who="local_planner"):
+    """int64 [n, 6] (mx, my, mvx, mvy, r_hard, r_soft) of at most PP_LOCAL_MAX_MOVERS movers; raises, naming the mover,
+    unless each lies within the ranges the rule's integer widths rest on."""
+    a = np.asarray(movers)
+    if a.size == 0:
+        return np.zeros((0, 6), np.int64)
+    if a.ndim != 2 or a.shape[1] != 6 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{who}: movers must be integers [n, 6] (mx, my, mvx, mvy, r_hard, r_soft), got {a.dtype} {a.shape}")
+    if a.shape[0] > PP_LOCAL_MAX_MOVERS:
+        raise ValueError(f"{who}: {a.shape[0]} movers, at most PP_LOCAL_MAX_MOVERS = {PP_LOCAL_MAX_MOVERS}")
+    a = a.astype(np.int64)
+    for m, (mx, my, mvx, mvy, rh, rs) in enumerate(a.tolist()):
+        if max(abs(mx), abs(my)) > MAX_MOVER_POS:
+            raise ValueError(f"{who}: mover {m}: position ({mx}, {my}) outside [-2^29, 2^29]")
+        if max(abs(mvx), abs(mvy)) > PP_LOCAL_MAX_MOVER_SPEED:
+            raise ValueError(f"{who}: mover {m}: movement ({mvx}, {mvy}) per step outside [-{PP_LOCAL_MAX_MOVER_SPEED}, {PP_LOCAL_MAX_MOVER_SPEED}]")
+        if not 0 <= rh <= rs <= PP_LOCAL_MAX_MOVER_RADIUS:
+            raise ValueError(f"{who}: mover {m}: radii r_hard = {rh}, r_soft = {rs}, not 0 <= r_hard <= r_soft <= {PP_LOCAL_MAX_MOVER_RADIUS}")
+    return a
+
+
+def _mover_args(movers, mcfg, who):
+    """(None, None) without movers; else (int64 [n, 6], MoverConfig)."""
+    if movers is None:
+        if mcfg is not None:
+            raise ValueError(f"{who}: mcfg without movers (an empty table is movers=[])")
+        return None, None
+    if mcfg is None:
+        raise ValueError(f"{who}: movers need mcfg (a MoverConfig, a dict of its fields or True)")
+    return check_movers(movers, who), MoverConfig.from_any(mcfg)
+
+
+def movers_np(rows, n, origin, res, dt, cfg):
+    """The table of one stream from its track rows, as k_local_movers makes it: rows tracking.TRACK_DTYPE (from
+    `Engine.tracks()` for the costmap source, `Engine.tracks_fixed()` for the occupancy source), of which the first n are
+    live (n = -1: the stream has had no posed step); origin (ox, oy) and res in metres, dt seconds per step, cfg a
+    MoverConfig -> (movers int32 [PP_LOCAL_MAX_MOVERS, 6] with zeros behind them, n_movers or -1, n_skipped)."""
+    c = MoverConfig.from_any(cfg)
+    ox, oy = (float(v) for v in origin)
+    res, dt = float(res), float(dt)
+    if not (math.isfinite(ox) and math.isfinite(oy)):
+        raise ValueError(f"movers_np: origin = ({ox}, {oy}) must be finite")
+    if not (math.isfinite(res) and res > 0.0):
+        raise ValueError(f"movers_np: res = {res} must be finite and > 0")
+    if not (math.isfinite(dt) and dt > 0.0):
+        raise ValueError(f"movers_np: dt = {dt} must be finite and > 0")
+    out = np.zeros((PP_LOCAL_MAX_MOVERS, 6), np.int32)
+    n = int(n)
+    if n < 0:
+        return out, -1, 0
+    r = np.asarray(rows)[:n]
+    if n > PP_TRACK_MAX or len(r) != n:
+        raise ValueError(f"movers_np: n = {n} rows of {len(np.asarray(rows))}, at most PP_TRACK_MAX = {PP_TRACK_MAX}")
+    st = np.asarray(r["state"], np.float64).reshape(n, 6)
+    size = np.asarray(r["size"], np.float64).reshape(n, 3)
+    use = (r["confirmed"] != 0) if c.confirmed_only else np.ones(n, bool)
+    x, y, vx, vy, w, l = st[:, 0], st[:, 1], st[:, 3], st[:, 4], size[:, 0], size[:, 1]
+    finite = np.isfinite(st).all(axis=1) & np.isfinite(w) & np.isfinite(l)
+    with np.errstate(all="ignore"):
+        MX, MY = np.floor(((x - ox) / res) * 1024.0), np.floor(((y - oy) / res) * 1024.0)
+        MVX, MVY = np.rint(((vx * dt) / res) * 1024.0), np.rint(((vy * dt) / res) * 1024.0)
+        half = np.fmax(w, l) * 0.5
+        RH, RS = np.ceil(((half + c.pad_hard) / res) * 1024.0), np.ceil(((half + c.pad_soft) / res) * 1024.0)
+        ok = finite & (np.abs(MX) <= MAX_MOVER_POS) & (np.abs(MY) <= MAX_MOVER_POS)
+        ok &= (np.abs(MVX) <= PP_LOCAL_MAX_MOVER_SPEED) & (np.abs(MVY) <= PP_LOCAL_MAX_MOVER_SPEED)
+    take = use & ok
+    k = int(take.sum())
+    cols = (MX, MY, MVX, MVY, np.clip(RH, 0.0, PP_LOCAL_MAX_MOVER_RADIUS), np.clip(RS, 0.0, PP_LOCAL_MAX_MOVER_RADIUS))
+    for q, v in enumerate(cols):
+        out[:k, q] = v[take].astype(np.int64)
+    return out, k, int((use & ~ok).sum())
 
 
 def trig_table():
@@ -192,9 +355,17 @@ def stream_state_np(grid, pot, pose, navfn_cfg, goal_state=0):
     return STATE_ARRIVED if int(p[cy, cx]) == 0 else STATE_OK
 
 
-def score_np(grid, pot, pose, sv, sw, navfn_cfg, cfg):
+def score_np(grid, pot, pose, sv, sw, navfn_cfg, cfg, movers=None, mcfg=None):
     """One sample, step by step in Python ints: (reason, score or None, poses) -- the poses [(X, Y, h)] the sample
-    reached, the start included (steps + 1 of them when reason is OK or UNREACHED)."""
+    reached, the start included (steps + 1 of them when reason is OK or UNREACHED).  With movers (integers [n, 6] and a
+    MoverConfig): (reason, score or None, poses, near)."""
+    mv, mc = _mover_args(movers, mcfg, "score_np")
+    if mv is None:
+        return _score(grid, pot, pose, sv, sw, navfn_cfg, cfg, (), None)[:3]
+    return _score(grid, pot, pose, sv, sw, navfn_cfg, cfg, mv.tolist(), mc)
+
+
+def _score(grid, pot, pose, sv, sw, navfn_cfg, cfg, mv, mc):
     n = _nav.NavfnConfig.from_any(navfn_cfg)
     c = LocalPlanConfig.from_any(cfg)
     g, p = _inputs(grid, pot, "score_np")
@@ -203,29 +374,40 @@ def score_np(grid, pot, pose, sv, sw, navfn_cfg, cfg):
     h &= HEADINGS - 1
     C, S = _TRIG[:, 0], _TRIG[:, 1]
     poses = [(X, Y, h)]
-    occ = 0
-    for _ in range(c.steps):
+    occ = near = 0
+    for k in range(1, c.steps + 1):
         X += (sv * int(C[h]) + 8192) >> 14
         Y += (sv * int(S[h]) + 8192) >> 14
         h = (h + sw) & (HEADINGS - 1)
         poses.append((X, Y, h))
         v = _cell_value(g, X >> 10, Y >> 10, n)
         if v is None:
-            return OUTSIDE, None, poses
+            return OUTSIDE, None, poses, near
         if v < 0:
-            return COLLISION, None, poses
+            return COLLISION, None, poses, near
         occ = max(occ, v)
+        if mc is not None and k <= mc.horizon:
+            for mx, my, mvx, mvy, rh, rs in mv:
+                dx, dy = X - (mx + k * mvx), Y - (my + k * mvy)
+                d2 = dx * dx + dy * dy
+                assert d2 < 2 ** 63
+                if d2 <= rh * rh:
+                    return DYNAMIC, None, poses, near
+                if d2 <= rs * rs:
+                    near = max(near, mc.horizon + 1 - k)
     lx = X + ((c.lookahead * int(C[h]) + 8192) >> 14)
     ly = Y + ((c.lookahead * int(S[h]) + 8192) >> 14)
     cx, cy = lx >> 10, ly >> 10
     v = _cell_value(g, cx, cy, n)
     if v is None or v < 0 or int(p[cy, cx]) == _nav.UNREACHED:
-        return UNREACHED, None, poses
+        return UNREACHED, None, poses, near
     score = c.pot_weight * int(p[cy, cx]) + c.occ_weight * occ + c.speed_weight * (1024 - abs(sv)) + c.turn_weight * abs(sw)
-    return OK, score, poses
+    if mc is not None:
+        score += mc.mover_weight * near
+    return OK, score, poses, near
 
 
-def keys_by_sample_np(grid, pot, pose, window, navfn_cfg, cfg):
+def keys_by_sample_np(grid, pot, pose, window, navfn_cfg, cfg, movers=None, mcfg=None):
     """(keys uint64 [nv * nw], reasons int32 [nv * nw]) of a window through `score_np`, sample by sample."""
     c = LocalPlanConfig.from_any(cfg)
     window = check_window(window, c, "keys_by_sample_np")
@@ -233,15 +415,16 @@ def keys_by_sample_np(grid, pot, pose, window, navfn_cfg, cfg):
     reasons = np.zeros(c.nv * c.nw, np.int32)
     for s in range(c.nv * c.nw):
         sv, sw = sample(s, window, c)
-        reasons[s], score, _ = score_np(grid, pot, pose, sv, sw, navfn_cfg, c)
+        reasons[s], score = score_np(grid, pot, pose, sv, sw, navfn_cfg, c, movers, mcfg)[:2]
         if score is not None:
             keys[s] = (score << 14) | s
     return keys, reasons
 
 
-def scores_np(grid, pot, pose, window, navfn_cfg, cfg):
+def scores_np(grid, pot, pose, window, navfn_cfg, cfg, movers=None, mcfg=None):
     """(keys uint64 [nv * nw], reasons int32 [nv * nw]) of a window, all samples at once: arrays over the samples, one
-    masked update per step."""
+    masked update per step (and, with movers, per step and mover)."""
+    mv, mc = _mover_args(movers, mcfg, "scores_np")
     n = _nav.NavfnConfig.from_any(navfn_cfg)
     c = LocalPlanConfig.from_any(cfg)
     g, p = _inputs(grid, pot, "scores_np")
@@ -257,6 +440,7 @@ def scores_np(grid, pot, pose, window, navfn_cfg, cfg):
     X, Y = np.full(N, X0, np.int64), np.full(N, Y0, np.int64)
     h = np.full(N, h0 & (HEADINGS - 1), np.int64)
     occ = np.zeros(N, np.int64)
+    near = np.zeros(N, np.int64)
     reason = np.zeros(N, np.int32)
     alive = np.ones(N, bool)
     C, S = _TRIG[:, 0].astype(np.int64), _TRIG[:, 1].astype(np.int64)
@@ -267,7 +451,7 @@ def scores_np(grid, pot, pose, window, navfn_cfg, cfg):
         at = (np.where(inside, cy, 0), np.where(inside, cx, 0))
         return inside, at
 
-    for _ in range(c.steps):
+    for k in range(1, c.steps + 1):
         X = np.where(alive, X + ((sv * C[h] + 8192) >> 14), X)
         Y = np.where(alive, Y + ((sv * S[h] + 8192) >> 14), Y)
         h = np.where(alive, (h + sw) & (HEADINGS - 1), h)
@@ -279,28 +463,46 @@ def scores_np(grid, pot, pose, window, navfn_cfg, cfg):
         reason[hit] = COLLISION
         alive = alive & ~out & ~hit
         occ = np.where(alive, np.maximum(occ, v), occ)
+        if mc is None or k > mc.horizon:
+            continue
+        for mx, my, mvx, mvy, rh, rs in mv:                 # int64 arrays: |dx| < 2^31, so d2 < 2^63 (asserted above)
+            dx, dy = X - (mx + k * mvx), Y - (my + k * mvy)
+            d2 = dx * dx + dy * dy
+            hard = alive & (d2 <= rh * rh)
+            reason[hard] = DYNAMIC
+            alive = alive & ~hard
+            near = np.where(alive & (d2 <= rs * rs), np.maximum(near, mc.horizon + 1 - k), near)
     lx = X + ((c.lookahead * C[h] + 8192) >> 14)
     ly = Y + ((c.lookahead * S[h] + 8192) >> 14)
     inside, at = read(lx >> 10, ly >> 10, alive)
     reached = inside & (val[at] >= 0) & (p[at] != _nav.UNREACHED)
     reason[alive & ~reached] = UNREACHED
     score = c.pot_weight * p[at].astype(np.int64) + c.occ_weight * occ + c.speed_weight * (1024 - np.abs(sv)) + c.turn_weight * np.abs(sw)
+    if mc is not None:
+        score = score + mc.mover_weight * near
     keys = np.where(reached, (score.astype(np.uint64) << np.uint64(14)) | s.astype(np.uint64), np.uint64(INVALID))
     return keys.astype(np.uint64), reason
 
 
-def best_np(grid, pot, pose, window, navfn_cfg, cfg, goal_state=0, samples=None):
+def best_np(grid, pot, pose, window, navfn_cfg, cfg, goal_state=0, samples=None, movers=None, mcfg=None):
     """The results of one grid as a dict: the RESULT words, `score`, `traj` int32 [steps + 1, 3] (or [0, 3]) and `keys`
-    uint64 [nv * nw].  samples: `scores_np` (the default) or `keys_by_sample_np`."""
+    uint64 [nv * nw].  samples: `scores_np` (the default) or `keys_by_sample_np`.  With movers (integers [n, 6] and a
+    MoverConfig) also `n_movers`, `n_dynamic` and `near`."""
+    mv, mc = _mover_args(movers, mcfg, "best_np")
+    extra = () if mv is None else (mv, mc)
     c = LocalPlanConfig.from_any(cfg)
     window = check_window(window, c, "best_np")
     N = c.nv * c.nw
     out = {k: 0 for k in RESULT}
     out.update(best=-1, score=0, traj=np.zeros((0, 3), np.int32), keys=np.full(N, INVALID, np.uint64))
+    if mv is not None:
+        out.update(n_movers=len(mv), n_dynamic=0, near=0)
     state = stream_state_np(grid, pot, pose, navfn_cfg, goal_state)
     if state == STATE_OK:
-        keys, reasons = (samples or scores_np)(grid, pot, pose, window, navfn_cfg, c)
+        keys, reasons = (samples or scores_np)(grid, pot, pose, window, navfn_cfg, c, *extra)
         out["keys"] = keys
+        if mv is not None:
+            out["n_dynamic"] = int((reasons == DYNAMIC).sum())
         for r, name in ((OK, "n_ok"), (OUTSIDE, "n_outside"), (COLLISION, "n_collision"), (UNREACHED, "n_unreached")):
             out[name] = int((reasons == r).sum())
         k = int(keys.min())
@@ -309,9 +511,11 @@ def best_np(grid, pot, pose, window, navfn_cfg, cfg, goal_state=0, samples=None)
         else:
             s = k & (PP_LOCAL_MAX_SAMPLES - 1)
             sv, sw = sample(s, window, c)
-            reason, score, poses = score_np(grid, pot, pose, sv, sw, navfn_cfg, c)
+            reason, score, poses, *near = score_np(grid, pot, pose, sv, sw, navfn_cfg, c, *extra)
             assert reason == OK and score == k >> 14
             out.update(best=s, sv=sv, sw=sw, score=score, traj=np.array(poses, np.int32).reshape(-1, 3))
+            if mv is not None:
+                out["near"] = near[0]
     out["cmd_state"] = state
     return out
 
@@ -429,11 +633,15 @@ def unpack_results(c, B, res, score, traj, keys):
     return out
 
 
-def local_plan(grids, pots, poses, windows, navfn_cfg, cfg, goal_state=None, keys=False, device=0):
+def local_plan(grids, pots, poses, windows, navfn_cfg, cfg, goal_state=None, keys=False, device=0, movers=None, n_movers=None,
+               mover_cfg=None):
     """The rule on the GPU, without an engine (pp_local_plan_grids): grids int8 and pots uint32 [H, W] or [B, H, W]
     (H * W <= PP_OCC_MAX_CELLS), poses integers [B, 3] (or one), windows integers [B, 4] (or one), goal_state integers [B]
     or None (all 0) -> a dict: the RESULT words and `score` per grid, `traj`, and `keys` if asked (ints and arrays for one
-    grid; int32 [B], uint64 [B], a list of B arrays and uint64 [B, nv * nw] for a batch)."""
+    grid; int32 [B], uint64 [B], a list of B arrays and uint64 [B, nv * nw] for a batch).  With movers
+    (pp_local_plan_grids_movers): movers integers [n, 6] for one grid, [B, PP_LOCAL_MAX_MOVERS, 6] with n_movers integers
+    [B] for a batch, and mover_cfg a MoverConfig of which horizon and mover_weight are read; the dict then also holds the
+    MOVER_INFO words."""
     n = _nav.NavfnConfig.from_any(navfn_cfg)
     c = LocalPlanConfig.from_any(cfg)
     a, p = np.asarray(grids), np.asarray(pots)
@@ -453,20 +661,47 @@ def local_plan(grids, pots, poses, windows, navfn_cfg, cfg, goal_state=None, key
     for b in range(B):
         check_window(Wn[b], c, f"local_plan: grid {b}")
     gs = None if goal_state is None else np.ascontiguousarray(np.broadcast_to(np.asarray(goal_state), (B,)), np.int32)
+    if movers is None and (n_movers is not None or mover_cfg is not None):
+        raise ValueError("local_plan: n_movers or mover_cfg without movers (an empty table is movers=[])")
+    if movers is not None:
+        if mover_cfg is None:
+            raise ValueError("local_plan: movers need mover_cfg (a MoverConfig, a dict of its fields or True)")
+        mc = MoverConfig.from_any(mover_cfg)
+        M = np.zeros((B, PP_LOCAL_MAX_MOVERS, 6), np.int32)
+        m = np.asarray(movers)
+        if n_movers is None:                                # one table [n, 6], for every grid
+            t = check_movers(m, "local_plan")
+            NM = np.full(B, len(t), np.int32)
+            M[:, :len(t)] = t
+        else:
+            NM = np.ascontiguousarray(np.broadcast_to(np.asarray(n_movers), (B,)), np.int32)
+            if m.shape != (B, PP_LOCAL_MAX_MOVERS, 6) or not np.issubdtype(m.dtype, np.integer):
+                raise ValueError(f"local_plan: movers with n_movers must be integers [{B}, {PP_LOCAL_MAX_MOVERS}, 6], got {m.dtype} {m.shape}")
+            for b in range(B):
+                if not 0 <= NM[b] <= PP_LOCAL_MAX_MOVERS:
+                    raise ValueError(f"local_plan: grid {b}: n_movers = {NM[b]} outside [0, {PP_LOCAL_MAX_MOVERS}]")
+                M[b, :NM[b]] = check_movers(m[b, :NM[b]], f"local_plan: grid {b}")
+        info = np.zeros((B, PP_LOCAL_MOVER_INFO), np.int32)
     trig = np.ascontiguousarray(_TRIG)
     res = np.zeros((B, len(RESULT)), np.int32)
     score = np.zeros(B, np.uint64)
     traj = np.zeros((B, c.steps + 1, 3), np.int32)
     kk = np.zeros((B, c.nv * c.nw), np.uint64) if keys else None
     L = _lib.lib()
-    st = L.pp_local_plan_grids(int(device), a.ctypes.data, p.ctypes.data, B, H, W, ctypes.byref(_lib.PPNavfnConfig(**n.to_dict())),
-                               ctypes.byref(_lib.PPLocalPlanConfig(**c.to_dict())), trig.ctypes.data, len(trig), P.ctypes.data,
-                               Wn.ctypes.data, None if gs is None else gs.ctypes.data, res.ctypes.data, score.ctypes.data,
-                               traj.ctypes.data, None if kk is None else kk.ctypes.data)
+    head = (int(device), a.ctypes.data, p.ctypes.data, B, H, W, ctypes.byref(_lib.PPNavfnConfig(**n.to_dict())),
+            ctypes.byref(_lib.PPLocalPlanConfig(**c.to_dict())), trig.ctypes.data, len(trig), P.ctypes.data, Wn.ctypes.data,
+            None if gs is None else gs.ctypes.data)
+    outs = (res.ctypes.data, score.ctypes.data, traj.ctypes.data, None if kk is None else kk.ctypes.data)
+    if movers is None:
+        st = L.pp_local_plan_grids(*head, *outs)
+    else:
+        st = L.pp_local_plan_grids_movers(*head, mc.horizon, mc.mover_weight, M.ctypes.data, NM.ctypes.data, *outs, info.ctypes.data)
     if st != 0:
         msg = L.pp_last_error(None)
         raise (ValueError if st == 1 else RuntimeError)(f"local_plan: {msg.decode() if msg else st}")
     out = unpack_results(c, B, res, score, traj, kk)
+    if movers is not None:
+        out.update({k: info[:, i].copy() for i, k in enumerate(MOVER_INFO)})
     if one:
         out = {k: (v[0] if isinstance(v, (list, np.ndarray)) else v) for k, v in out.items()}
         out = {k: (int(v) if np.ndim(v) == 0 else v) for k, v in out.items()}

@@ -92,7 +92,7 @@ class VoxelNet:
     def drive(self, goals, velocities, limits, source="costmap", poses=None):
         """Engine.drive: the velocity commands in m/s and rad/s towards `goals` over the inflated grids of the pass that has
         just run, or of the last occupancy_update (engine.set_inflation, engine.set_navfn and engine.set_local_planner for
-        that source first)."""
+        that source first; engine.set_local_movers to avoid the streams' moving tracks too)."""
         return self.engine.drive(goals, velocities, limits, source, poses)
 
     def _need_p2(self, p2, who):

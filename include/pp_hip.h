@@ -62,7 +62,9 @@ extern "C" {
  * inflated grid where it lies).  Then PP_LOCAL_SUB, PP_LOCAL_HEADINGS, PP_LOCAL_MAX_SAMPLES, PP_LOCAL_MAX_STEPS,
  * PP_LOCAL_MAX_LOOKAHEAD, PP_LOCAL_RESULT, pp_local_plan_config, pp_set_local_plan, pp_get_local_plan_config,
  * pp_local_plan_async, pp_get_local_plan, pp_local_plan_grids (declared behind pp_navfn_grids: the stage reads the
- * inflated grid and the field where they lie). */
+ * inflated grid and the field where they lie).  Then PP_LOCAL_MAX_MOVERS, PP_LOCAL_MAX_MOVER_SPEED,
+ * PP_LOCAL_MAX_MOVER_RADIUS, PP_LOCAL_MOVER_INFO, pp_local_mover_config, pp_set_local_movers, pp_get_local_movers_config,
+ * pp_local_plan_movers_async, pp_get_local_movers, pp_local_plan_grids_movers (declared behind pp_local_plan_grids). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -1530,6 +1532,68 @@ int pp_local_plan_grids(int device, const int8_t* grids, const uint32_t* pots, i
                         const pp_navfn_config* navfn_cfg, const pp_local_plan_config* cfg, const int32_t* trig,
                         int32_t n_trig, const int32_t* poses, const int32_t* windows, const int32_t* goal_state,
                         int32_t* result, uint64_t* score, int32_t* traj, uint64_t* keys);
+
+/* ---- Movers of the local planner: time-indexed collision of every rolled sample with the stream's live tracks
+ * (local_planner.py states both rules).  A mover is six int32 (mx, my, mvx, mvy, r_hard, r_soft): its position at step
+ * 0 in sub-cells of the grid's frame (it may lie outside the grid), its movement per rollout step, and two radii, all
+ * in sub-cells; |mx|, |my| <= 2^29, |mvx|, |mvy| <= PP_LOCAL_MAX_MOVER_SPEED, 0 <= r_hard <= r_soft <=
+ * PP_LOCAL_MAX_MOVER_RADIUS, at most PP_LOCAL_MAX_MOVERS per grid.  THE ROLLOUT: a sample that is still alive after
+ * the static test of step k (OUTSIDE, then COLLISION, then occ) and has k <= horizon looks at every mover in table
+ * order: dx = X - (mx + k * mvx), dy likewise, d2 = dx * dx + dy * dy in exact integers; d2 <= r_hard^2 ends the sample
+ * as DYNAMIC (reason 4), otherwise d2 <= r_soft^2 sets near = max(near, horizon + 1 - k).  Neither the start pose nor
+ * the lookahead point is tested.  The score gains mover_weight * near (it stays below 2^41).  THE TABLE
+ * (pp_local_plan_movers_async) comes from the stream's track slots on the device, in float64 with every operation
+ * rounded on its own: a slot's x y z vx vy vz w l in the grid's frame -- as it stands for the costmap source; carried
+ * into the fixed frame by the pose of the stream's last posed tracking step for the occupancy source, with the
+ * expressions that make pp_get_tracks_fixed's rows (a stream that has had no posed step: n_movers = -1, no movers) --
+ * give MX = floor(((x - ox) / res) * 1024), MVX = rint(((vx * dt) / res) * 1024) (half to even), RH = ceil(((fmax(w, l) *
+ * 0.5 + pad_hard) / res) * 1024) clipped to [0, PP_LOCAL_MAX_MOVER_RADIUS], and MY, MVY, RS likewise.  Live slots
+ * (confirmed ones where confirmed_only is set) become movers in ascending slot order; one with a non-finite input, |MX|
+ * or |MY| > 2^29 or |MVX| or |MVY| > PP_LOCAL_MAX_MOVER_SPEED is skipped and counted. ---- */
+#define PP_LOCAL_MAX_MOVERS 64          /* per grid: PP_TRACK_MAX */
+#define PP_LOCAL_MAX_MOVER_SPEED 16384  /* sub-cells per step */
+#define PP_LOCAL_MAX_MOVER_RADIUS 32767 /* sub-cells */
+#define PP_LOCAL_MOVER_INFO 4           /* int32 words per grid: n_movers (-1: no posed step), n_skipped, n_dynamic, near */
+
+typedef struct pp_local_mover_config {
+    double pad_hard;         /* metres added to max(w, l) / 2 for r_hard: the robot's radius belongs here; finite, >= 0 */
+    double pad_soft;         /* ... for r_soft; finite, >= pad_hard */
+    int32_t horizon;         /* 0 .. PP_LOCAL_MAX_STEPS: steps over which a prediction is trusted */
+    int32_t mover_weight;    /* 0 .. 65535 */
+    int32_t confirmed_only;  /* 0 / 1: only confirmed tracks become movers */
+    int32_t reserved;        /* 0 */
+} pp_local_mover_config;
+
+/* cfg == NULL: the source's movers off (the default); the buffers are kept.  Otherwise the configuration is validated
+ * (PP_ERR_ARG naming the field).  Independent of pp_set_local_plan.  Waits for the stream.  PP_ERR_STATE while a training
+ * step is in flight. */
+int pp_set_local_movers(pp_handle h, int32_t source, const pp_local_mover_config* cfg);
+/* *on: 0 / 1; cfg_out (may be NULL): the last configuration given for the source (zeros before the first). */
+int pp_get_local_movers_config(pp_handle h, int32_t source, int32_t* on, pp_local_mover_config* cfg_out);
+/* pp_local_plan_async with the stream's tracks as movers: does and refuses everything that call does, and first builds
+ * the movers' table of every grid on the device from the track slots of stream b for grid b.  frame double [batch][4] =
+ * (ox, oy, res, dt): the metres of the grid's cell [0, 0] corner in the tracks' frame, the metres of a cell and the
+ * seconds of a rollout step.  Further refusals, all before anything is queued: PP_ERR_STATE when the source's movers are
+ * off or pp_set_tracking has never been called on the handle; PP_ERR_ARG for frame NULL, a non-finite ox or oy, and a
+ * res or dt that is not finite and > 0.  pp_local_plan_async itself never uses movers, whatever pp_set_local_movers
+ * said. */
+int pp_local_plan_movers_async(pp_handle h, int32_t source, const int32_t* poses, const int32_t* windows,
+                               const double* frame, int32_t batch);
+/* The movers of the source's last pp_local_plan_movers_async: movers int32 [batch][PP_LOCAL_MAX_MOVERS][6] (zeros behind
+ * a grid's n_movers), info int32 [batch][PP_LOCAL_MOVER_INFO]; each may be NULL.  Waits and settles as pp_get_local_plan
+ * does; where that queues the rollout again it runs on the table the call built, which is not rebuilt.  PP_ERR_STATE
+ * also when the source's last run was a pp_local_plan_async. */
+int pp_get_local_movers(pp_handle h, int32_t source, int32_t* movers, int32_t* info, int32_t batch);
+/* pp_local_plan_grids with host-given movers: movers int32 [batch][PP_LOCAL_MAX_MOVERS][6] of which grid b uses the
+ * first n_movers[b] (0 .. PP_LOCAL_MAX_MOVERS); every one of those is range-checked (PP_ERR_ARG naming the grid and the
+ * mover).  horizon and mover_weight as pp_local_mover_config has them.  info int32 [batch][PP_LOCAL_MOVER_INFO] or
+ * NULL (n_skipped is 0). */
+int pp_local_plan_grids_movers(int device, const int8_t* grids, const uint32_t* pots, int32_t batch, int32_t height,
+                               int32_t width, const pp_navfn_config* navfn_cfg, const pp_local_plan_config* cfg,
+                               const int32_t* trig, int32_t n_trig, const int32_t* poses, const int32_t* windows,
+                               const int32_t* goal_state, int32_t horizon, int32_t mover_weight, const int32_t* movers,
+                               const int32_t* n_movers, int32_t* result, uint64_t* score, int32_t* traj, uint64_t* keys,
+                               int32_t* info);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
