@@ -164,6 +164,7 @@ int pp_inflate_async(pp_handle e, int32_t source) {
     }
     HIPCHK(e, hipGetLastError());
     g.batch = batch; g.run_pitch = pitch; g.run_w = W; g.run_h = H; g.run_R = g.R;
+    ++g.run_id;                                          // (the same buffers, other grids: what navfn recorded no longer holds)
     g.known.assign((size_t)batch, 1);
     if (!cm)
         for (int b = 0; b < batch; ++b) g.known[(size_t)b] = o.has[(size_t)b];

@@ -129,12 +129,15 @@ int queue_run(pp_engine* e, const LocalParams& p, hipStream_t s) {
     return PP_OK;
 }
 
-// the source's navigation function has run and the inflated grids it read still lie where they lay
+// the source's navigation function has run and the inflated grids it read are still the ones that lie there: the same
+// buffers of the same shape (a freed one would be read otherwise), and no pp_inflate_async since (the buffers are reused
+// while the shape stands, so the pointer alone would pass the next cycle's grids under this cycle's field)
 int check_navfn_run(pp_engine* e, const char* who, int source) {
     const pp_engine::Navfn& g = e->navfn[source];
     const pp_engine::Inflation& in = e->infl[source];
     const NavParams& r = g.run;
-    if (in.out != r.grid || in.cells != r.stride || in.run_w != r.width || in.run_h != r.height || in.run_pitch != r.pitch || in.batch < g.batch)
+    if (in.out != r.grid || in.cells != r.stride || in.run_w != r.width || in.run_h != r.height || in.run_pitch != r.pitch || in.batch < g.batch ||
+        in.run_id != g.infl_run)
         return fail(e, PP_ERR_STATE, "%s: the inflated grids of the %s source were re-made since its navigation function ran "
                     "(pp_navfn_async again)", who, source_name(source));
     return PP_OK;

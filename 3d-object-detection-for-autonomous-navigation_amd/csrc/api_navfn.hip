@@ -200,6 +200,7 @@ int pp_navfn_async(pp_handle e, int32_t source, const int32_t* goals, const int3
     }
     g.batch = batch; g.run = p; g.rounds = rounds; g.settled = false;
     ++g.run_id;
+    g.infl_run = in.run_id;
     return PP_OK;
 }
 

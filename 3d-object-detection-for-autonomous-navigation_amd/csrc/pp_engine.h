@@ -442,6 +442,7 @@ struct pp_engine {
         int batch = 0;                     // grids of the last run (pp_get_inflated; 0: none)
         int run_pitch = 0, run_w = 0, run_h = 0, run_R = 0;   // ... and their shape
         std::vector<char> known;           // [batch] of that run; 0: the stream had been reset, its grid reads all unknown
+        unsigned long long run_id = 0;     // counts the pp_inflate_async calls of the source: `out` is reused, its contents are not
     } infl[2];                             // by source: PP_INFLATE_COSTMAP, PP_INFLATE_OCCUPANCY
 
     // pp_set_navfn: the cost-to-go field from a goal cell and the path from a start cell over infl[source].out, which it
@@ -464,6 +465,7 @@ struct pp_engine {
         NavParams run = {};                // ... what it was launched with
         int rounds = 0;                    // relaxation rounds queued behind its init so far
         unsigned long long run_id = 0;     // counts the pp_navfn_async calls of the source (pp_get_local_plan)
+        unsigned long long infl_run = 0;   // infl[source].run_id of the grids the last run read (check_navfn_run)
         bool settled = false;              // a getter has seen every grid's field stand, and `host` holds the state words
         std::vector<int> host;             // [NAV_STATE][B]
     } navfn[2];                            // by source, as infl

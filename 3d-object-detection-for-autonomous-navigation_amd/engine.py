@@ -424,8 +424,8 @@ class Engine:
         if d.sweeps is not None:
             self.set_sweeps(d.sweeps)
         self._costmap_queued = False                            # a costmap_async whose grids costmaps() has not fetched
-        self._infl_run = {}                                     # source index -> (batch, (H, W)) of its last inflate_async
-        self._navfn_run = {}                                    # source index -> (batch, (H, W), max_path, origins, resolution) of its last navfn_async
+        self._infl_run = {}                                     # source index -> (batch, (H, W), origins [B, 2], poses [B, 3, 4] or None) of the run its last inflate_async read
+        self._navfn_run = {}                                    # source index -> (batch, (H, W), max_path, origins, resolution, poses) of its last navfn_async
         self._local_run = {}                                    # source index -> (batch, LocalPlanConfig, resolution or None, step dt or None) of its last local_plan_async
         self._local_movers_run = {}                             # source index -> the MoverConfig that run used, or None
         if d.costmap is not None:
@@ -1234,13 +1234,22 @@ class Engine:
         whatever the engine's stream holds (pp_inflate_async, one launch) and returns at once.  Raises when the source or
         its inflation is off, the source has not run, or its resolution is not the inflation's.  It reads the source's
         grids as they are when it runs: queue it before the next costmap_async / occupancy_update_async to inflate this
-        cycle's grids; the inflated grids then stay while the source runs again, until the next inflate_async of that source."""
+        cycle's grids; the inflated grids then stay while the source runs again, until the next inflate_async of that
+        source -- and so does their frame: the call records the origins and the poses of the run it inflates, and
+        navfn_async, local_plan_async's default poses, the movers' frame and inflated_occupancy_maps read them from that
+        record, not from whatever occupancy_update_async has run since.  A navfn_async has to follow before the next
+        local_plan_async or drive: the local planner refuses a field made on the grids this call replaces
+        (PP_ERR_STATE), and so does a getter that would have to roll the samples again."""
         k = self._infl_source(source)
         self._check(self._lib.pp_inflate_async(self._h, k), "pp_inflate_async")
         if k == 0:
-            self._infl_run[k] = (self._costmap_batch, self._costmap_shape)
+            c = self.costmap
+            B = self._costmap_batch
+            org = np.tile(np.array([[c.x_min, c.y_min]], np.float64), (B, 1))      # the sensor frame: the sensor at yaw 0
+            self._infl_run[k] = (B, self._costmap_shape, org, None)
         else:
-            self._infl_run[k] = (self._occ_batch, self._occ_shape)
+            B = self._occ_batch
+            self._infl_run[k] = (B, self._occ_shape, self._occ_origins[:B].copy(), self._occ_poses[:B].copy())
 
     @staticmethod
     def _infl_batch(batch, run, who):
@@ -1248,7 +1257,7 @@ class Engine:
             raise ValueError(f"{who}: the source's run has {run} grids, batch is {int(batch)}")
 
     def _inflated(self, k, batch, clearance):
-        B0, (H, W) = self._infl_run.get(k, (0, (1, 1)))
+        B0, (H, W) = self._infl_run.get(k, (0, (1, 1)))[:2]
         B = int(batch) if batch is not None else B0
         grid = np.zeros((max(B, 1), H, W), np.int8)
         d2 = np.zeros((max(B, 1), H, W), np.uint16) if clearance else None
@@ -1276,7 +1285,7 @@ class Engine:
         self._infl_batch(batch, getattr(self, "_occ_batch", 0), "inflated_occupancy_maps")
         self.inflate_async("occupancy")
         grid, d2 = self._inflated(1, batch, clearance)
-        org = self._occ_origins[:len(grid)].copy()
+        org = self._infl_run[1][2][:len(grid)].copy()              # (of the update this inflation read)
         return (grid, org, d2) if clearance else (grid, org)
 
     def inflation_info(self, source="costmap"):
@@ -1306,19 +1315,15 @@ class Engine:
         return _from_struct(_nav.NavfnConfig, pc) if on.value else None
 
     def _navfn_frame(self, k, who):
-        """(batch, (H, W), origins float64 [B, 2], resolution) of the source's last inflation: the grids' frame."""
+        """(batch, (H, W), origins float64 [B, 2], resolution, poses [B, 3, 4] or None) of the source's last inflation:
+        the grids' frame as inflate_async recorded it, whatever the source has run since."""
         if k not in self._infl_run:
             raise RuntimeError(f"{who}: no inflation has run on the {_infl.SOURCES[k]} source (inflate_async first)")
-        B, shape = self._infl_run[k]
-        if k == 0:
-            c = self.costmap
-            if c is None:
-                raise RuntimeError(f"{who}: the costmap stage is not configured (set_costmap first)")
-            return B, shape, np.tile(np.array([[c.x_min, c.y_min]], np.float64), (B, 1)), c.resolution
-        c = self.occupancy
+        B, shape, org, poses = self._infl_run[k]
+        c = self.costmap if k == 0 else self.occupancy
         if c is None:
-            raise RuntimeError(f"{who}: the occupancy stage is not configured (set_occupancy first)")
-        return B, shape, self._occ_origins[:B].copy(), c.resolution
+            raise RuntimeError(f"{who}: the {_infl.SOURCES[k]} stage is not configured (set_{_infl.SOURCES[k]} first)")
+        return B, shape, org.copy(), c.resolution, poses
 
     def _navfn_cells_async(self, k, goals, starts):
         """pp_navfn_async on cells: goals int32 [B, 2], starts int32 [B, 2] or None (no paths)."""
@@ -1326,7 +1331,7 @@ class Engine:
         s = None if starts is None else np.ascontiguousarray(starts, np.int32)
         self._check(self._lib.pp_navfn_async(self._h, k, _ptr(g), _ptr(s), int(g.shape[0])), "pp_navfn_async")
         c = self.navfn_config(_infl.SOURCES[k])
-        self._navfn_run[k] = (int(g.shape[0]), self._infl_run[k][1], c.max_path, None, None)     # (no frame in metres yet)
+        self._navfn_run[k] = (int(g.shape[0]), self._infl_run[k][1], c.max_path, None, None, None)     # (no frame in metres yet)
 
     def navfn_async(self, goals, source="costmap", starts=None):
         """Queues the field and the paths on the grids of the source's last inflation behind whatever the engine's stream
@@ -1336,7 +1341,7 @@ class Engine:
         (goal_state 2).  starts=None: the sensor's own cell -- floor((0 - x_min) / resolution) and likewise in y for the
         costmap, (W // 2, H // 2) for the occupancy maps; an array like `goals`: those points; False: no paths."""
         k = self._infl_source(source)
-        B, shape, org, res = self._navfn_frame(k, "navfn_async")
+        B, shape, org, res, poses = self._navfn_frame(k, "navfn_async")
         G = np.asarray(goals, np.float64)
         if G.shape not in ((2,), (B, 2)):
             raise ValueError(f"navfn_async: goals must be metres [{B}, 2] (the inflation run's grids) or one (x, y), got {G.shape}")
@@ -1354,7 +1359,7 @@ class Engine:
                 raise ValueError(f"navfn_async: starts must be metres [{B}, 2] or one (x, y), None or False, got {S.shape}")
             s = _nav.goal_cells(np.broadcast_to(S, (B, 2)), org, res, shape)
         self._navfn_cells_async(k, g, s)
-        self._navfn_run[k] = self._navfn_run[k][:3] + (org, res)
+        self._navfn_run[k] = self._navfn_run[k][:3] + (org, res, poses)
 
     def _navfn_last(self, k, who):
         if k not in self._navfn_run:
@@ -1365,7 +1370,7 @@ class Engine:
         """The fields uint32 [B, H, W] of the source's last navfn_async (waits for it, and lets the GPU finish the rounds
         still missing: always the exact field); navfn.UNREACHED where no chain of moves joins the cell to the goal."""
         k = self._infl_source(source)
-        B, (H, W), _, _, _ = self._navfn_last(k, "navfn_fields")
+        B, (H, W) = self._navfn_last(k, "navfn_fields")[:2]
         pot = np.zeros((B, H, W), np.uint32)
         self._check(self._lib.pp_get_navfn(self._h, k, _ptr(pot), None, None, B), "pp_get_navfn")
         return pot
@@ -1375,7 +1380,7 @@ class Engine:
         int32 [n, 2] of cells (x, y), start and goal included; metres=True: float64 [n, 2], the cells' centres in the
         grids' frame (navfn.path_to_metres).  path_state as navfn.py lists it."""
         k = self._infl_source(source)
-        B, _, cap, org, res = self._navfn_last(k, "navfn_paths")
+        B, _, cap, org, res, _ = self._navfn_last(k, "navfn_paths")
         paths = np.zeros((B, cap, 2), np.int32)
         n = np.zeros(B, np.int32)
         self._check(self._lib.pp_get_navfn(self._h, k, None, _ptr(paths), _ptr(n), B), "pp_get_navfn")
@@ -1467,14 +1472,15 @@ class Engine:
         """Queues the rollout and the command on the grids and fields of the source's last navfn_async behind the
         relaxation rounds that call queued (pp_local_plan_async) and returns at once.  poses float64 [B, 3] (x, y, yaw) (or
         one for every grid), metres and radians in the grids' frame; None: the sensor at yaw 0 for the costmap, the
-        translation and atan2(R10, R00) of the last occupancy_update_async's poses for the occupancy maps.  They become
+        translation and atan2(R10, R00) of the poses of the occupancy_update_async whose maps the field's inflation read
+        (inflate_async records them) for the occupancy maps.  They become
         sub-cells and ticks through local_planner.pose_ticks with the navfn run's origins and the source's resolution, so
         a pose outside its window is no error (cmd_state 3).  windows integers [B, 4] (v0, dv, w0, dw) (or one), as
         local_planner.LocalLimits.window makes them; None: sv from 0 to 1024 and sw from -512 to 512.  dt: the seconds of
         a step, which `local_commands(metric=True)` needs -- and the source's movers, while set_local_movers has them
         on: the call then builds their table from the streams' tracks first (pp_local_plan_movers_async)."""
         k = self._infl_source(source)
-        B, _, _, org, res = self._navfn_last(k, "local_plan_async")
+        B, _, _, org, res, T = self._navfn_last(k, "local_plan_async")
         c = self.local_planner_config(source)
         if c is None:
             raise RuntimeError(f"local_plan_async: the local planner of the {source} source is not configured (set_local_planner first)")
@@ -1487,7 +1493,6 @@ class Engine:
             if k == 0:
                 P = np.zeros((B, 3))
             else:
-                T = self._occ_poses[:B]
                 P = np.stack([T[:, 0, 3], T[:, 1, 3], np.arctan2(T[:, 1, 0], T[:, 0, 0])], axis=1)
         else:
             P = np.asarray(poses, np.float64)
@@ -1597,7 +1602,7 @@ class Engine:
         if c is None:
             raise RuntimeError(f"drive: the local planner of the {source} source is not configured (set_local_planner first)")
         k = self._plan_async(goals, source, None)
-        B, _, _, _, res = self._navfn_last(k, "drive")
+        B, res = self._navfn_last(k, "drive")[0], self._navfn_last(k, "drive")[4]
         V = np.asarray(velocities, np.float64)
         if V.shape not in ((2,), (B, 2)):
             raise ValueError(f"drive: velocities must be (v, w) [{B}, 2] or one, got {V.shape}")

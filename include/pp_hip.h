@@ -1512,7 +1512,8 @@ int pp_get_local_plan_config(pp_handle h, int32_t source, int32_t* on, pp_local_
  * call queued: poses int32 [batch][3] = (X, Y, h) sub-cells and a tick (h is taken & 4095), windows int32 [batch][4] =
  * (v0, dv, w0, dw).  Reads the inflated grid and the field in place and never writes them.  Refused before anything is
  * queued, PP_ERR_STATE: the stage or the source's navigation function is off, that navigation function has not run, the
- * inflated grids were re-made since it ran, a training step is in flight; PP_ERR_ARG: a batch that is not the navigation
+ * inflated grids were re-made since it ran (any pp_inflate_async of the source: it reuses the buffers, so the field on
+ * the handle belongs to grids that are gone -- pp_navfn_async again), a training step is in flight; PP_ERR_ARG: a batch that is not the navigation
  * function run's, poses or windows NULL, a sample with |sv| > 1024 or |sw| > 512, a bad source. */
 int pp_local_plan_async(pp_handle h, int32_t source, const int32_t* poses, const int32_t* windows, int32_t batch);
 /* The results of the source's last pp_local_plan_async.  First settles the field as pp_get_navfn does; if that queued a
@@ -1520,8 +1521,9 @@ int pp_local_plan_async(pp_handle h, int32_t source, const int32_t* poses, const
  * command always rests on the exact field.  result int32 [batch][PP_LOCAL_RESULT]; score uint64 [batch] (0 unless
  * cmd_state is 0); traj int32 [batch][steps + 1][3] poses, the start included (zeros unless cmd_state is 0); keys uint64
  * [batch][nv * nw]; each may be NULL.  PP_ERR_STATE when none has run, a pp_navfn_async of the source came after it, or
- * the launches have to be queued again and the inflated grids were re-made meanwhile; PP_ERR_ARG when batch is not that
- * run's. */
+ * the launches have to be queued again and the inflated grids were re-made meanwhile (a pp_inflate_async of the source
+ * since its pp_navfn_async, whether or not the buffers moved; when nothing has to be queued again the results are
+ * copied as the launches left them); PP_ERR_ARG when batch is not that run's. */
 int pp_get_local_plan(pp_handle h, int32_t source, int32_t* result, uint64_t* score, int32_t* traj, uint64_t* keys,
                       int32_t batch);
 /* Without a handle: grids int8 and pots uint32 [batch][height][width] in host memory (height * width <=

@@ -27,6 +27,51 @@ COSTMAP = dict(GRID, objects="tracks", horizon_steps=2)
 OCC = dict(resolution=0.1, z_min=0.0, z_max=1.0, max_range=2.5, width=37, height=29)
 INFL_COSTMAP = dict(resolution=0.05, inscribed_radius=0.05, inflation_radius=0.2, cost_scaling_factor=8.0)          # 4 cells
 INFL_OCC = dict(resolution=0.1, inscribed_radius=0.1, inflation_radius=0.5, cost_scaling_factor=4.0, lethal_threshold=65)   # 5 cells
+# the planner behind both inflations: 5 x 13 = 65 samples (a wave and one lane).  The costmap's navigation function queues
+# ONE round: on 51 x 43 cells (2 x 2 tiles) the field is never settled at the call, so every fetch goes through the
+# getter's settle and its second rollout.  Both grids are unknown where nothing was seen and the scene is dense (the
+# sensor's own cell often lies in an inscribed band): unknown cells pass and only the obstacles themselves block.  The
+# movers' horizons are short for the same reason: the tracks of this scene are many, close and fast.
+NAV_CM = dict(lethal_cost=100, allow_unknown=1, unknown_cost=30, max_path=256, queued_rounds=1)
+NAV_OCC = dict(lethal_cost=100, allow_unknown=1, unknown_cost=20, max_path=256)
+LOC_CM = dict(nv=5, nw=13, steps=8, lookahead=1024, pot_weight=8, occ_weight=4, speed_weight=1, turn_weight=1)
+LOC_OCC = dict(nv=5, nw=13, steps=6, lookahead=512, pot_weight=16, occ_weight=8, speed_weight=2, turn_weight=1)
+MOV_CM = dict(horizon=4, mover_weight=64, pad_hard=0.0, pad_soft=0.15, confirmed_only=False)
+MOV_OCC = dict(horizon=3, mover_weight=100, pad_hard=0.0, pad_soft=0.25, confirmed_only=True)
+LIMITS = dict(v_min=-0.1, v_max=0.4, w_max=1.5, acc_v=1.0, acc_w=4.0, sim_time=1.0, period=0.2)
+PLAN_DT = 0.125      # seconds per rollout step, for both sources
+# What the costmap's planner is asked per cycle (row i % 9) and stream: a goal (x, y) and the robot's pose (x, y, yaw),
+# metres and radians in the sensor frame.  The scene is dense -- nine points in ten have y < 0, the sweeps carry old points
+# back over the sensor's own cell, eight to eleven tracks stand in it --, so the rows were chosen on the host chain
+# (tests/test_nav_cycle_host.py asserts what they reach): every goal is free, every pose lies on a free, reached cell
+# and sees collisions, cells the field does not reach and, from cycle 1 on, movers among its 65 samples.
+PLAN_CM = [
+    [(-0.3, 0.5, 0.03, 0.12, -1.1), (1.9, 0.9, 0.78, 0.12, -1.9), (1.5, 1.0, 0.78, 0.12, -1.9)],
+    [(0.6, 1.0, 0.78, 0.12, -1.9), (-0.2, 1.05, 0.03, 0.12, -1.9), (-0.3, 0.5, -0.27, 0.92, -0.4)],
+    [(-0.2, 1.05, 1.68, 1.07, -0.4), (0.2, 0.95, 0.33, 0.92, 0.5), (-0.4, 0.8, -0.12, 0.92, -1.1)],
+    [(1.9, 0.9, -0.12, 0.12, -1.1), (1.5, 1.0, 1.68, 1.07, 0.5), (1.3, 0.8, 0.03, 0.42, -1.1)],
+    [(1.95, 0.3, -0.12, 0.12, -1.1), (0.2, 0.95, 0.03, 0.92, -1.9), (1.0, 1.0, 0.33, 0.72, -1.9)],
+    [(0.2, 0.95, 0.33, 0.12, -1.9), (-0.4, 0.8, -0.12, 0.72, 0.5), (-0.4, 0.1, 1.23, 0.92, -1.9)],
+    [(1.5, 1.0, 0.03, 0.12, -1.1), (-0.2, 1.05, 0.03, 0.92, -0.4), (-0.3, 0.5, 0.33, 0.42, -0.4)],
+    [(-0.3, 0.5, 0.33, 0.12, -1.9), (1.0, 1.0, 0.78, 0.12, -1.1), (0.6, 1.0, 0.33, 0.12, -1.9)],
+    [(-0.4, 0.8, 0.33, 0.12, -1.9), (1.95, 0.3, 0.33, 0.12, -0.4), (-0.2, 1.05, 0.33, 0.12, -1.9)],
+]
+# ... and the occupancy maps' goals per cycle (row i % 9) and stream, offsets in metres from the stream's pose: two lie
+# outside every window (goal_state 2, cmd_state 4) and two at the pose itself (arrived, cmd_state 2), each between two
+# cycles of its stream that give a command
+GOALS_OCC = [
+    [(1.0, 0.5), (0.6, -0.9), (-1.1, -0.6)],
+    [(-0.8, 0.7), (1.3, -0.2), (0.0, 0.0)],
+    [(0.6, -0.9), (-1.1, -0.6), (-0.8, 0.7)],
+    [(1.3, -0.2), (1.0, 0.5), (0.6, -0.9)],
+    [(-1.1, -0.6), (-0.8, 0.7), (1.3, -0.2)],
+    [(1.0, 0.5), (0.6, -0.9), (-1.1, -0.6)],
+    [(-0.8, 0.7), (1.3, -0.2), (9.0, 0.0)],
+    [(0.0, 0.0), (-1.1, -0.6), (-0.8, 0.7)],
+    [(1.3, -0.2), (9.0, 0.0), (0.6, -0.9)],
+]
+NAV_TILE = 32        # csrc/navfn.hip: a workgroup relaxes a tile of 32 x 32 cells per round
+SRC = (("cm", "costmap"), ("occ", "occupancy"))
 IMAGE_SHAPES = [(8, 4), (6, 5), (10, 3)]      # (height, width) per stream under default_calib's identity camera matrix
 
 # rows of stream 0, 1, 2 per cycle, from {0, 1, 63, 64, 65, 257}: empty, a single row, a wave and one row either side of
@@ -34,6 +79,10 @@ IMAGE_SHAPES = [(8, 4), (6, 5), (10, 3)]      # (height, width) per stream under
 # stream 0's three 257s in a row overflow both the sweeps' capacity (200) and the frame (512)
 SIZES = [[257, 64, 65], [257, 65, 1], [257, 63, 257], [0, 257, 64], [65, 1, 257], [63, 0, 65], [257, 257, 0], [64, 257, 257],
          [1, 65, 63]]
+# metres per cycle sideways, per stream.  Stream 2's carries its window over a cell border between cycles 5 and 6, where
+# its frame is empty: an empty frame under a window that stands would leave the occupancy map, and so its inflated grid,
+# what it was, and a stale grid would pass for this cycle's
+DRIFT_Y = (-0.03, 0.0, 0.035)
 GAP_AFTER = 4        # the stamps jump by more than max_age between cycles 4 and 5
 
 OCC_INFO = ("hits", "ground", "ignored", "cells_hit", "cells_free", "cleared")
@@ -94,11 +143,26 @@ def sequence(pp, cycles=None, seed=11):
     for i in range(cycles):
         row = SIZES[i % len(SIZES)]
         frames = [_frame(rng, n) for n in row]
-        poses = np.stack([pp.sweeps.pose_from_xyyaw(0.04 * i + rng.normal() * 0.004, 0.03 * i * (b - 1) + rng.normal() * 0.004,
+        poses = np.stack([pp.sweeps.pose_from_xyyaw(0.04 * i + rng.normal() * 0.004, DRIFT_Y[b] * i + rng.normal() * 0.004,
                                                     0.03 * i * (b + 1)) for b in range(STREAMS)])
         t = 0.1 * i + (0.4 if i > GAP_AFTER else 0.0)
-        out.append(dict(frames=frames, poses=poses, stamps=np.array([t + b for b in range(STREAMS)]), planes=pl))
+        out.append(dict(frames=frames, poses=poses, stamps=np.array([t + b for b in range(STREAMS)]), planes=pl,
+                        **plan_inputs(i, poses)))
     return out
+
+
+def plan_inputs(i, poses):
+    """What the planner is asked in cycle i (no random draw: the frames above stay what they were): a goal per stream and
+    source in metres -- the sensor frame for the costmap, the fixed frame (the stream's pose plus an offset) for the
+    occupancy maps -- that moves with the cycle, the current velocity (v m/s, w rad/s) of LIMITS' window, and the robot's
+    pose (x, y, yaw) in the costmap (the default, the sensor's own cell, lies in an obstacle in most cycles: the sweeps
+    carry old points back over it; the occupancy source keeps the default, the pose of its update)."""
+    xy = poses[:, :2, 3]
+    asked = np.array(PLAN_CM[i % len(PLAN_CM)], np.float64)
+    goals_cm, pose_cm = asked[:, :2], asked[:, 2:]
+    goals_occ = xy + np.array(GOALS_OCC[i % len(GOALS_OCC)], np.float64)
+    vel = np.array([[0.05 + 0.03 * ((i + b) % 5), 0.25 * ((i + 2 * b) % 5 - 2)] for b in range(STREAMS)], np.float64)
+    return dict(goals_cm=goals_cm, goals_occ=goals_occ, velocities=vel, poses_cm=pose_cm)
 
 
 def short_at(cycles):
@@ -110,7 +174,7 @@ def short_at(cycles):
 
 def short(cycle, B):
     """The cycle for streams 0 .. B - 1 only."""
-    return dict(frames=cycle["frames"][:B], poses=cycle["poses"][:B], stamps=cycle["stamps"][:B], planes=cycle["planes"][:B])
+    return {k: v[:B] for k, v in cycle.items()}
 
 
 # ---- the host chain ----
@@ -179,6 +243,11 @@ class HostChain:
         # 7. both inflations
         out["infl_cm"] = inflate_all(pp, out["cm_grid"], self.ic)
         out["infl_occ"] = inflate_all(pp, out["occ_grid"], self.io)
+        # 8. per source: the field and the path, the movers from the tracks, the command
+        out["plan_in"] = plan_in(cycle)
+        out["plan_origin_occ"] = out["occ_origin"].copy()
+        out.update(plan_np(pp, "cm", out["infl_cm"][0], out["plan_in"], cm_origins(B), out["tracks"][0], out["tracks"][1]))
+        out.update(plan_np(pp, "occ", out["infl_occ"][0], out["plan_in"], out["occ_origin"], *out["tracks_fixed"]))
         return out
 
 
@@ -187,6 +256,86 @@ def inflate_all(pp, grids, cfg):
     res = [pp.inflation.inflate_np(g, cfg, clearance=True, info=True) for g in grids]
     return (np.stack([r[0] for r in res]), np.stack([r[1] for r in res]),
             {k: np.array([r[2][k] for r in res], np.int32) for k in ("lethal", "raised")})
+
+
+# ---- the planner's restatements on one source's inflated grids (HostChain.step on the chain's, same_plan on a run's own) ----
+PLAN_KEYS = ("field", "paths", "paths_m", "nav_info", "plan_info", "traj", "keys", "movers")
+_PLANNED = {}        # one grid's results by everything they depend on: most runs repeat the chain's grids
+
+
+def plan_in(cycle):
+    """What the planner was asked in this cycle, kept with the results: same_plan needs nothing else."""
+    return {k: np.array(cycle[k], np.float64) for k in ("goals_cm", "goals_occ", "velocities", "poses", "poses_cm")}
+
+
+def cm_origins(B):
+    return np.tile(np.array([[GRID["x_min"], GRID["y_min"]]], np.float64), (B, 1))
+
+
+def plan_configs(pp, s):
+    """(NavfnConfig, LocalPlanConfig, MoverConfig, resolution) of source s."""
+    N, L = pp.navfn, pp.local_planner
+    if s == "cm":
+        return N.NavfnConfig(**NAV_CM), L.LocalPlanConfig(**LOC_CM), L.MoverConfig(**MOV_CM), GRID["resolution"]
+    return N.NavfnConfig(**NAV_OCC), L.LocalPlanConfig(**LOC_OCC), L.MoverConfig(**MOV_OCC), OCC["resolution"]
+
+
+def plan_windows(pp, s, velocities):
+    """LIMITS' dynamic window round each stream's current velocity, int32 [B, 4]."""
+    _, lcfg, _, res = plan_configs(pp, s)
+    lim = pp.local_planner.LocalLimits(**LIMITS)
+    return np.array([lim.window(v, w, lcfg.nv, lcfg.nw, res) for v, w in np.asarray(velocities)], np.int32)
+
+
+def plan_cells(pp, s, asked, origins, shape):
+    """(goal cells [B, 2], start cells [B, 2], pose ticks [B, 3]) as navfn_async and local_plan_async make them: the paths
+    start at the sensor's cell; the robot stands at the scenario's pose in the costmap and, by default, at the update's
+    pose in the occupancy maps."""
+    N, L = pp.navfn, pp.local_planner
+    res = plan_configs(pp, s)[3]
+    B = len(origins)
+    if s == "cm":
+        goals = N.goal_cells(asked["goals_cm"][:B], origins, res, shape)
+        starts = N.goal_cells(np.zeros((B, 2)), origins, res, shape)
+        ticks = L.pose_ticks(asked["poses_cm"][:B, :2], asked["poses_cm"][:B, 2], origins, res)
+    else:
+        T = asked["poses"][:B]
+        goals = N.goal_cells(asked["goals_occ"][:B], origins, res, shape)
+        starts = np.tile(np.array([[shape[1] // 2, shape[0] // 2]], np.int32), (B, 1))
+        ticks = L.pose_ticks(T[:, :2, 3], np.arctan2(T[:, 1, 0], T[:, 0, 0]), origins, res)
+    return goals, starts, ticks
+
+
+def _plan_one(pp, s, grid, goal, start, ticks, window, origin, rows, n):
+    N, L = pp.navfn, pp.local_planner
+    ncfg, lcfg, mcfg, res = plan_configs(pp, s)
+    key = (s, grid.tobytes(), goal.tobytes(), start.tobytes(), ticks.tobytes(), window.tobytes(), np.asarray(origin, np.float64).tobytes(),
+           int(n), rows[:max(int(n), 0)].tobytes())
+    if key not in _PLANNED:
+        pot, info = N.navfn_np(grid, goal, ncfg, info=True)
+        path, pstate = N.descend_np(pot, grid, start, ncfg)
+        movers, nm, skipped = L.movers_np(rows, n, origin, res, PLAN_DT, mcfg)
+        best = L.best_np(grid, pot, ticks, window, ncfg, lcfg, info["goal_state"], movers=movers[:max(nm, 0)], mcfg=mcfg)
+        best["n_movers"], best["n_skipped"] = nm, skipped
+        _PLANNED[key] = (pot, path, N.path_to_metres(path, origin, res), dict(info, path_state=pstate), best, movers)
+    return _PLANNED[key]
+
+
+def plan_np(pp, s, grids, asked, origins, tracks, n_tracks):
+    """navfn_np, descend_np, movers_np and best_np per grid of source s ("cm" / "occ") -> the planner's keys of a cycle's dict,
+    in the shapes fetch_plan gives them."""
+    L = pp.local_planner
+    B, shape = len(grids), grids.shape[1:]
+    goals, starts, ticks = plan_cells(pp, s, asked, origins, shape)
+    wins = plan_windows(pp, s, asked["velocities"][:B])
+    res = [_plan_one(pp, s, grids[b], goals[b], starts[b], ticks[b], wins[b], origins[b], tracks[b], n_tracks[b]) for b in range(B)]
+    words = L.RESULT + ("n_movers", "n_skipped", "n_dynamic", "near")
+    info = {k: np.array([r[4][k] for r in res], np.int32) for k in words}
+    info["score"] = np.array([r[4]["score"] for r in res], np.uint64)
+    return {f"field_{s}": np.stack([r[0] for r in res]), f"paths_{s}": [r[1] for r in res], f"paths_m_{s}": [r[2] for r in res],
+            f"nav_info_{s}": {k: np.array([r[3][k] for r in res], np.int32) for k in ("goal_state", "path_state", "reached")},
+            f"plan_info_{s}": info, f"traj_{s}": [r[4]["traj"] for r in res], f"keys_{s}": np.stack([r[4]["keys"] for r in res]),
+            f"movers_{s}": np.stack([r[5] for r in res])}
 
 
 def host_chain(seq, detect, pp=None):
@@ -282,6 +431,41 @@ def same_as_chain(got, want, what, streams=None):
                 assert np.array_equal(got[key][0][b], want[key][0][b]), (what, key, b)
                 for k in ("lethal", "raised"):
                     assert got[key][2][k][b] == want[key][2][k][b], (what, key, k, b)
+    # the planner: the occupancy source always; the costmap source where the chain's grid is the run's (same_plan holds the rest)
+    if "plan_in" in got:
+        for k, v in want["plan_in"].items():
+            assert np.array_equal(got["plan_in"][k][ss], v[ss]), (what, "asked", k)
+    if "plan_origin_occ" in got:
+        assert np.array_equal(got["plan_origin_occ"][ss], want["plan_origin_occ"][ss]), (what, "the occupancy frame of the plan")
+    _same_planned(got, want, "occ", ss, what)
+    _same_planned(got, want, "cm", [b for b in ss if not und[b].any()], what)
+
+
+def _same_planned(got, want, s, ss, what):
+    """The planner's keys of source s that `got` holds against `want`'s, streams ss; exact."""
+    for name in PLAN_KEYS:
+        key = f"{name}_{s}"
+        if key not in got:
+            continue
+        g, w = got[key], want[key]
+        if isinstance(w, dict):
+            for k in w:                                 # (a run also has the rounds the GPU took: implementation-defined)
+                assert g[k].dtype == w[k].dtype and np.array_equal(g[k][ss], w[k][ss]), (what, key, k, g[k], w[k])
+        else:
+            for b in ss:
+                assert g[b].dtype == w[b].dtype and g[b].shape == w[b].shape and np.array_equal(g[b], w[b]), (what, key, b)
+
+
+def same_plan(pp, got, what):
+    """Every planner output of a run against the restatements on that run's OWN fetched inflated grids, tracks and origins
+    (whether or not the cycle's costmap has undecided cells), under what the run was asked (got["plan_in"])."""
+    for s, infl, rows in (("cm", "infl_cm", "tracks"), ("occ", "infl_occ", "tracks_fixed")):
+        if not any(f"{name}_{s}" in got for name in PLAN_KEYS):
+            continue
+        grids = got[infl][0]
+        origins = cm_origins(len(grids)) if s == "cm" else got["plan_origin_occ"]
+        want = plan_np(pp, s, grids, got["plan_in"], origins, got[rows][0], got[rows][1])
+        _same_planned(got, want, s, range(len(grids)), (what, "on the run's own grids"))
 
 
 def same_inflation(pp, got, what):
@@ -342,6 +526,10 @@ def configure(pp, eng):
     eng.set_occupancy(OCC)
     eng.set_inflation(INFL_COSTMAP, "costmap")
     eng.set_inflation(INFL_OCC, "occupancy")
+    for source, nav, loc, mov in (("costmap", NAV_CM, LOC_CM, MOV_CM), ("occupancy", NAV_OCC, LOC_OCC, MOV_OCC)):
+        eng.set_navfn(nav, source)
+        eng.set_local_planner(loc, source)
+        eng.set_local_movers(mov, source)
     rect, trv, _ = calib(pp)
     eng.set_calib(rect, trv, STREAMS)
 
@@ -398,10 +586,21 @@ class Dt:
         self.last[stream] = np.nan
 
 
-# THE CALL ORDER OF ONE CYCLE: INTEGRATION.md, "One navigation cycle", lists these nine steps, and
+# THE CALL ORDER OF ONE CYCLE: INTEGRATION.md, "One navigation cycle", lists these thirteen steps, and
 # tests/test_nav_cycle_host.py holds both that listing and run_queued's own calls to this tuple
 CYCLE_CALLS = ("upload_async", "occupancy_update_async", "crop_to_image_async", "accumulate_sweeps_async", "set_track_dt",
-               "set_track_pose", "detect_async", "costmap_async", 'inflate_async("costmap")', 'inflate_async("occupancy")')
+               "set_track_pose", "detect_async", "costmap_async", 'inflate_async("costmap")', 'inflate_async("occupancy")',
+               'navfn_async("costmap")', 'local_plan_async("costmap")', 'navfn_async("occupancy")', 'local_plan_async("occupancy")')
+SOURCE_CALLS = ("inflate_async", "navfn_async", "local_plan_async")       # ... written with the source they name
+
+
+def calls_in(text, prefix):
+    """The calls `<prefix>.<name>(...)` of a text in order, as CYCLE_CALLS writes them."""
+    out = []
+    for c in re.finditer(re.escape(prefix) + r"\.(\w+)\(([^\n]*)", text):
+        src = re.search(r'"(costmap|occupancy)"', c.group(2)) if c.group(1) in SOURCE_CALLS else None
+        out.append(c.group(1) + (f'("{src.group(1)}")' if src else ""))
+    return out
 
 
 def queue_stages(eng, cycle, dt):
@@ -419,6 +618,18 @@ def queue_behind_crop(eng, cycle, dt):
     eng.costmap_async()                                             # 7.
     eng.inflate_async("costmap")                                    # 8.
     eng.inflate_async("occupancy")                                  # 9.
+    queue_plan(eng, cycle)
+
+
+def queue_plan(eng, cycle):
+    """Steps 10 .. 13 behind both inflations: the default starts, the default pose in the occupancy maps, the window round
+    the velocity."""
+    import pp_amd as pp
+    wc, wo = (plan_windows(pp, s, cycle["velocities"]) for s, _ in SRC)
+    eng.navfn_async(cycle["goals_cm"], "costmap")                   # 10.
+    eng.local_plan_async(cycle["poses_cm"], wc, "costmap", dt=PLAN_DT)      # 11.
+    eng.navfn_async(cycle["goals_occ"], "occupancy")                # 12.
+    eng.local_plan_async(None, wo, "occupancy", dt=PLAN_DT)         # 13.
 
 
 def fetch_pass(eng, B):
@@ -452,14 +663,49 @@ def fetch_inflated(eng):
             "infl_occ": eng._inflated(1, None, True) + (eng.inflation_info("occupancy"),)}
 
 
-def fetch_all(eng, B, crop=True):
+def fetch_navfn(eng, cycle, sources=SRC):
+    """What steps 10 and 12 leave, with what they were asked and the frame the engine gave the occupancy run."""
+    out = {"plan_in": plan_in(cycle)}
+    for s, source in sources:
+        if s == "occ":
+            out["plan_origin_occ"] = eng._navfn_run[1][3].copy()
+        out[f"field_{s}"] = eng.navfn_fields(source)
+        out[f"paths_{s}"] = eng.navfn_paths(source)[0]
+        out[f"paths_m_{s}"] = eng.navfn_paths(source, metres=True)[0]
+        out[f"nav_info_{s}"] = eng.navfn_info(source)
+        assert np.array_equal(eng.navfn_paths(source)[1], out[f"nav_info_{s}"]["path_state"])
+    return out
+
+
+def fetch_local(eng, s, source, keys=True):
+    """What step 11 or 13 leaves (keys=False: nothing that makes the getter roll the samples again for their keys)."""
+    out = {f"plan_info_{s}": eng.local_plan_info(source), f"traj_{s}": eng.local_trajectories(source)}
+    if keys:
+        out[f"keys_{s}"] = eng.local_keys(source)
+    out[f"movers_{s}"], minfo = eng.local_movers(source)
+    assert all(np.array_equal(minfo[k], out[f"plan_info_{s}"][k]) for k in minfo)
+    sv, sw, state = eng.local_commands(source)
+    info = out[f"plan_info_{s}"]
+    assert np.array_equal(sv, info["sv"]) and np.array_equal(sw, info["sw"]) and np.array_equal(state, info["cmd_state"])
+    return out
+
+
+def fetch_plan(eng, cycle):
+    out = fetch_navfn(eng, cycle)
+    for s, source in SRC:
+        out.update(fetch_local(eng, s, source))
+    return out
+
+
+def fetch_all(eng, cycle, crop=True):
     out = {"sweeps_info": eng.sweeps_info()}
     if crop:
         out["kept"] = eng.crop_info()
-    out.update(fetch_pass(eng, B))
+    out.update(fetch_pass(eng, len(cycle["frames"])))
     out.update(fetch_costmap(eng))
     out.update(fetch_occupancy(eng))
     out.update(fetch_inflated(eng))
+    out.update(fetch_plan(eng, cycle))
     return out
 
 
@@ -472,7 +718,7 @@ def run_queued(pp, eng, seq):
         stagings.append(st)
         eng.upload_async(st)                                        # 1.
         queue_stages(eng, cycle, dts(cycle["stamps"]))
-        outs.append(fetch_all(eng, len(cycle["frames"])))
+        outs.append(fetch_all(eng, cycle))
     eng.sync()
     for st in stagings:
         st.close()

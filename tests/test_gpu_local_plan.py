@@ -3,7 +3,7 @@ restatement: result words, scores, trajectories and all keys must be EQUAL (np.a
 works in integers and keys are unique, so no order shows in a result.  Stand-alone on the shared cases
 (tests/local_plan_cases.py), then behind the navigation function of the costmap and of the rolling occupancy maps, whose
 own outputs must stay the bytes of an engine that never heard of the stage; the getter's second rollout behind a field
-that had not converged; the call ring; every refusal."""
+that had not converged; a second inflation or a second occupancy update behind the call; the call ring; every refusal."""
 import ctypes
 
 import numpy as np
@@ -266,6 +266,140 @@ def test_getter_rolls_again_behind_the_settled_field(pp, LP, hip_lib):
         ninfo = e.navfn_info("costmap")
         assert ninfo["rounds"][0] > 1 and np.array_equal(e.navfn_fields("costmap")[0], exact)
         _same_run(LP, e, "costmap", infl, exact[None], [0], ticks, win, nav, cfg, "settled")
+    finally:
+        e.close()
+
+
+# ---- 3b. the inflated buffers are reused while the shape stands: a second inflation behind the call is refused, never read ----
+REMADE = "the inflated grids of the costmap source were re-made since its navigation function ran"
+
+
+def _blocked_corridor_frame():
+    """The serpentine with wider gaps and two obstacle cells in the first corridor, five cells ahead of the pose (the row
+    beside them stays open): another field and other collisions than on _serpentine_frame()."""
+    pts = _serpentine_frame(gap=9)
+    for iy in (0,):
+        for ix in (7, 8):
+            pts[iy * CM["width"] + ix, 2] = 0.0
+    return pts
+
+
+def test_a_second_inflation_behind_the_call_is_refused_not_read(pp, LP, hip_lib):
+    """pp_inflate_async writes the next grids into the buffers the last ones lay in.  A getter that has to roll the samples
+    again (here: one queued round, the field is not settled at the call) would roll them over the NEW grid against the
+    OLD field; include/pp_hip.h promises PP_ERR_STATE instead, and likewise for a pp_local_plan_async without a new
+    pp_navfn_async.  The navigation function copied its costs at the call: its own getters still give the old grid's field."""
+    N = pp.navfn
+    e = pp.Engine(_tiny(pp, 1), max_batch=1, max_points_per_frame=4096)
+    try:
+        nav = dict(NAV, queued_rounds=1)
+        e.set_costmap(CM)
+        e.set_inflation(INFL, "costmap")
+        e.set_navfn(nav, "costmap")
+        e.set_local_planner(LOC, "costmap")
+        cfg = e.local_planner_config("costmap")
+        res = CM["resolution"]
+        goal = np.array([[CM["x_min"] + 1.5 * res, CM["y_min"] + 27.5 * res]])         # cell (1, 27): the far end
+        pose = np.array([[CM["x_min"] + 2.5 * res, CM["y_min"] + 0.5 * res, 0.0]])      # cell (2, 0): the near end
+        win = np.array([[100, 100, -300, 60]], np.int32)
+        ticks = LP.pose_ticks(pose[:, :2], pose[:, 2], ORG, res)
+        e.upload([_serpentine_frame()])
+        e._plan_async(goal, "costmap", None)
+        e.local_plan_async(pose, win)                      # 1. one round in front of it: a fetch has to settle and roll again
+        old = e._inflated(0, None, False)[0].copy()        # (waits for the stream; settles nothing)
+        e.upload([_blocked_corridor_frame()])              # 2. other obstacles, the same shape: the same buffers
+        e.costmap_async()
+        e.inflate_async("costmap")
+        new = e._inflated(0, None, False)[0].copy()
+        assert new.shape == old.shape and not np.array_equal(new, old)
+        exact_old = N.navfn_np(old[0], (1, 27), nav)
+        assert np.array_equal(e.navfn_fields("costmap")[0], exact_old)                 # 6. the field is the old grid's, to the last cell
+        assert e.navfn_info("costmap")["rounds"][0] > 1
+        for fetch in (e.local_commands, e.local_plan_info, e.local_trajectories, e.local_keys):
+            with pytest.raises(RuntimeError, match="PP_ERR_STATE.*pp_get_local_plan: " + REMADE):       # 3.
+                fetch("costmap")
+        with pytest.raises(RuntimeError, match="PP_ERR_STATE.*pp_local_plan_async: " + REMADE + r" \(pp_navfn_async again\)"):
+            e.local_plan_async(pose, win)                  # 4. the old field over the new grid: no
+        assert np.array_equal(e.navfn_fields("costmap")[0], exact_old)                 # (the refusals changed nothing)
+        e.navfn_async(goal, "costmap")                     # 5. again, in order: the new grid and its exact field
+        e.local_plan_async(pose, win)
+        exact = N.navfn_np(new[0], (1, 27), nav)
+        assert not np.array_equal(exact, exact_old)
+        want = LP.best_np(new[0], exact, ticks[0], win[0], nav, cfg)
+        was = LP.best_np(old[0], exact_old, ticks[0], win[0], nav, cfg)
+        stale = LP.best_np(new[0], exact_old, ticks[0], win[0], nav, cfg)              # what a getter that rolled again would have read
+        assert want["cmd_state"] == 0 and want["n_ok"] >= 8
+        assert len({(w["score"], w["n_ok"], w["n_collision"]) for w in (was, want, stale)}) == 3      # three answers that cannot pass for each other
+        sv, sw, state = e.local_commands("costmap")
+        assert (int(sv[0]), int(sw[0]), int(state[0])) == (want["sv"], want["sw"], 0)
+        assert np.array_equal(e.navfn_fields("costmap")[0], exact)
+        _same_run(LP, e, "costmap", new, exact[None], [0], ticks, win, nav, cfg, "on the new grid")
+    finally:
+        e.close()
+
+
+# ---- 3c. the occupancy frame of a plan is the one its inflation read, whatever update has run since ----
+def _sparse_frames(k):
+    """A few obstacle points behind each sensor, 1.3 to 2 m away (tests/test_gpu_local_movers.py): the way ahead stays
+    unknown, which OCC_NAV allows, so every goal and pose below is free."""
+    out = []
+    for s in range(S3):
+        rng = np.random.default_rng(40 + 10 * k + s)
+        r, a = rng.uniform(1.3, 2.0, 12 + 5 * s), rng.uniform(2.0, 4.3, 12 + 5 * s)
+        out.append(np.stack([r * np.cos(a), r * np.sin(a), np.full(len(r), 0.5)], axis=1).astype(np.float32))
+    return out
+
+
+def test_the_occupancy_frame_is_the_inflations_not_the_last_updates(pp, LP, hip_lib):
+    """update, inflate, update under a pose two and three cells on: navfn_async's goals in metres, local_plan_async's
+    default poses and navfn_paths(metres=True) belong to the grid that was inflated -- the first update's window and pose."""
+    N = pp.navfn
+    e = pp.Engine(_tiny(pp, S3), max_batch=S3, max_points_per_frame=4096)
+    try:
+        e.set_occupancy(OCC)
+        e.set_inflation(OCC_INFL, "occupancy")
+        e.set_navfn(OCC_NAV, "occupancy")
+        e.set_local_planner(OCC_LOC, "occupancy")
+        cfg, ncfg, res = e.local_planner_config("occupancy"), e.navfn_config("occupancy"), OCC["resolution"]
+        shape = (OCC["height"], OCC["width"])
+        xy0 = np.array([[0.02 + 0.1 * s, -0.03] for s in range(S3)])
+        yaw0 = np.array([0.2 + 0.5 * s for s in range(S3)])
+        xy1, yaw1 = xy0 + [0.3, -0.2], yaw0 + 0.7
+        e.upload(_sparse_frames(0))
+        e.occupancy_update_async(np.stack([pp.sweeps.pose_from_xyyaw(xy0[s, 0], xy0[s, 1], yaw0[s]) for s in range(S3)]))
+        e.inflate_async("occupancy")
+        org0 = e.occupancy_maps()[1]
+        e.upload(_sparse_frames(1))
+        e.occupancy_update_async(np.stack([pp.sweeps.pose_from_xyyaw(xy1[s, 0], xy1[s, 1], yaw1[s]) for s in range(S3)]))
+        org1 = e.occupancy_maps()[1]
+        assert np.array_equal(np.rint((org1 - org0) / res), np.tile([[3.0, -2.0]], (S3, 1)))      # the window moved by whole cells
+        G = xy0 + np.array([[1.2, 0.6], [-1.1, 0.9], [0.8, 0.3]])
+        e.navfn_async(G, "occupancy")
+        e.local_plan_async(source="occupancy")
+        infl = e._inflated(1, None, False)[0]              # the first update's maps, inflated
+        goals, moved = N.goal_cells(G, org0, res, shape), N.goal_cells(G, org1, res, shape)
+        ticks, ticks1 = LP.pose_ticks(xy0, yaw0, org0, res), LP.pose_ticks(xy1, yaw1, org1, res)
+        assert not (goals == moved).all(axis=1).any() and not (ticks == ticks1).all(axis=1).any()
+        pots, info = e.navfn_fields("occupancy"), e.navfn_info("occupancy")
+        paths, states = e.navfn_paths("occupancy")
+        mpaths, _ = e.navfn_paths("occupancy", metres=True)
+        assert (info["goal_state"] == 0).all() and (states == 0).all()
+        for s in range(S3):
+            assert np.array_equal(pots[s], N.navfn_np(infl[s], goals[s], ncfg)), s
+            assert np.argwhere(pots[s] == 0)[:, ::-1].tolist() == [goals[s].tolist()], s           # the goal cell is the first window's
+            assert paths[s][0].tolist() == [OCC["width"] // 2, OCC["height"] // 2] and paths[s][-1].tolist() == goals[s].tolist(), s
+            assert np.array_equal(mpaths[s], N.path_to_metres(paths[s], org0[s], res)), s
+        wide = np.tile(np.array([[0, LP.MAX_SV // (cfg.nv - 1), -LP.MAX_SW, 2 * LP.MAX_SW // (cfg.nw - 1)]], np.int32), (S3, 1))
+        info, traj, _ = _same_run(LP, e, "occupancy", infl, pots, [0] * S3, ticks, wide, ncfg, cfg, "the first update's frame")
+        assert (info["cmd_state"] == 0).all()
+        for s in range(S3):
+            assert traj[s][0].tolist() == ticks[s].tolist(), s                          # the pose ticks are the first update's
+        # the next inflation takes the second update's frame
+        _, org = e.inflated_occupancy_maps()
+        assert org.tobytes() == org1.tobytes()
+        e.navfn_async(G, "occupancy")
+        pots = e.navfn_fields("occupancy")
+        assert [np.argwhere(pots[s] == 0)[:, ::-1].tolist() for s in range(S3)] == [[g] for g in moved.tolist()]
     finally:
         e.close()
 

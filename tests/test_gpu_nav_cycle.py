@@ -1,13 +1,18 @@
 """The whole navigation cycle on one handle -- live feed, occupancy update, frustum crop, sweep accumulation, the tracked pass
-under ego poses with projection on, costmap, both inflations -- over 2 * OFF_RING + 1 cycles, held to the chain of the
+under ego poses with projection on, costmap, both inflations, and behind each inflation the navigation function, the movers
+from the tracks and the local planner's command -- over 2 * OFF_RING + 1 cycles, held to the chain of the
 package's numpy restatements (tests/nav_cycle_cases.py; tests/test_nav_cycle_host.py shows the chain reaches the edges).
 Every comparison is np.array_equal or bytes; the one exclusion is the costmap's undecided cells (a footprint edge within
 1e-9 m of a cell centre), at most 0.1 % of a cycle's cells, and an inflated costmap is then held to inflate_np of the run's
-own grid.  The passes of the chain come from a second engine with no stage but the projection, fed synchronously.
+own grid; every planner output of a run is held to the restatements on that run's own inflated grids, tracks and origins
+as well (K.same_plan).  The passes of the chain come from a second engine with no stage but the projection, fed
+synchronously.  The costmap's navigation function queues one round, so its field is never settled at the call and every
+fetch of its command goes through the getter's settle and second rollout.
 
 What the single-stage files cannot see is what the stages share -- the two input buffers and their events, the call rings,
 the graph key, scratch -- so the cases differ in how much the host waits: after every stage (1), once per cycle (2, 3), never
-(4), and with the next cycle's feed queued before this cycle's fetch (6).
+(4), with the next cycle's feed queued before this cycle's fetch (6), and with the next cycle queued through both
+inflations before this cycle's command is fetched (8).
 
 By design, stated here because two cases meet it:
   * pp_frustum_crop_async refuses frames whose sizes only the device knows (PP_ERR_STATE, "their sizes are device values"):
@@ -17,6 +22,11 @@ By design, stated here because two cases meet it:
   * Case 6 meets no refusal: upload_async, crop and sweeps of cycle k + 1 are accepted while cycle k's results are
     unfetched.  occupancy_update_async of cycle k + 1 stands between its feed and its crop, so cycle k's maps are fetched
     through their inflation (queued before that update), and the maps themselves at the last cycle.
+  * Case 8: the inflated buffers are reused from cycle to cycle, so once cycle k + 1's inflation is queued, a command of
+    cycle k can be fetched only if nothing has to be rolled again.  The navigation function keeps its own costs: fields,
+    paths and info stay cycle k's.  A getter that has to queue the rollout again -- the field took a further round (the
+    costmap source, always), or keys are asked for the first time -- is refused with PP_ERR_STATE; it never reads cycle
+    k + 1's grid under cycle k's field.
   * The stream-independence case (5) runs its 2-of-3 cycle two thirds through, not halfway: nav_cycle_cases.short_at
     says why (the stamp gap sits at the halfway point and would hide a reset that did nothing)."""
 import json
@@ -32,6 +42,7 @@ import nav_cycle_cases as K
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REMADE = "PP_ERR_STATE.*pp_get_local_plan: the inflated grids of the {} source were re-made since its navigation function ran"
 REFUSED = "PP_ERR_STATE.*pp_frustum_crop_async: .*ingested from camera messages, their sizes are device values"
 
 
@@ -79,6 +90,15 @@ def _run_stepwise(pp, eng, seq):
         eng.inflate_async("costmap")                                    # 8.
         eng.inflate_async("occupancy")                                  # 9.
         out.update(K.fetch_inflated(eng))
+        wc, wo = (K.plan_windows(pp, s, c["velocities"]) for s, _ in K.SRC)
+        eng.navfn_async(c["goals_cm"], "costmap")                       # 10.
+        out.update(K.fetch_navfn(eng, c, K.SRC[:1]))
+        eng.local_plan_async(c["poses_cm"], wc, "costmap", dt=K.PLAN_DT)        # 11. behind a settled field: no second rollout here
+        out.update(K.fetch_local(eng, *K.SRC[0]))
+        eng.navfn_async(c["goals_occ"], "occupancy")                    # 12.
+        out.update(K.fetch_navfn(eng, c, K.SRC[1:]))
+        eng.local_plan_async(None, wo, "occupancy", dt=K.PLAN_DT)       # 13.
+        out.update(K.fetch_local(eng, *K.SRC[1]))
         outs.append(out)
     return outs
 
@@ -102,6 +122,25 @@ def _not_empty(outs):
     assert (outs[-1]["infl_cm"][2]["raised"] > 0).all() and (outs[-1]["infl_occ"][2]["raised"] > 0).all()
     if "occ_logodds" in outs[-1]:
         assert (outs[-1]["occ_logodds"] > 0).any() and (outs[-1]["occ_logodds"] < 0).any()
+    # the planner: fields that reach cells, commands on valid samples, movers in the tables
+    for s, _ in K.SRC:
+        assert any((o[f"nav_info_{s}"]["reached"] > 100).any() for o in outs), s
+        assert any(((o[f"plan_info_{s}"]["cmd_state"] == 0) & (o[f"plan_info_{s}"]["n_ok"] >= 8)).any() for o in outs), s
+        assert any((o[f"plan_info_{s}"]["n_movers"] > 0).any() for o in outs), s
+
+
+def _planner_reached(outs):
+    """The planner's share of tests/test_nav_cycle_host.py's conditions, on a run of the whole sequence."""
+    pairs, states = len(outs) * K.STREAMS, []
+    for s, _ in K.SRC:
+        info = [o[f"plan_info_{s}"] for o in outs]
+        assert 2 * sum(int(((w["cmd_state"] == 0) & (w["n_ok"] >= 8)).sum()) for w in info) >= pairs, s
+        states += [int(v) for w in info for v in w["cmd_state"]]
+    assert sum(int((o[f"plan_info_{s}"]["n_dynamic"] > 0).sum()) for o in outs for s, _ in K.SRC) > 0
+    assert sum(int((o[f"plan_info_{s}"]["near"] > 0).sum()) for o in outs for s, _ in K.SRC) > 0
+    assert 4 in states and (1 in states or 2 in states), sorted(set(states))
+    # one queued round never settles the costmap's field: the getter finished it (and rolled the samples again)
+    assert all((o["nav_info_cm"]["rounds"] > 1).all() for o in outs), [o["nav_info_cm"]["rounds"].tolist() for o in outs]
 
 
 # ---- 1 ----
@@ -110,10 +149,12 @@ def test_step_by_step_every_cycle_equals_the_chain(pp, seq, stepwise, want):
     for i, (got, w) in enumerate(zip(stepwise, want)):
         K.same_as_chain(got, w, f"stepwise, cycle {i}")
         K.same_inflation(pp, got, f"stepwise, cycle {i}")
+        K.same_plan(pp, got, f"stepwise, cycle {i}")
         print(f"cycle {i}: kept {got['kept'].tolist()} rows {got['sweeps_info']['count'].tolist()} detections {got['n'].tolist()} "
               f"tracks {got['tracks'][1].tolist()} undecided {int(w['cm_undecided'].sum())}")
     assert sum(int(o["sweeps_info"]["truncated"].sum()) for o in stepwise) > 0
     _not_empty(stepwise)
+    _planner_reached(stepwise)
 
 
 # ---- 2 ----
@@ -121,8 +162,10 @@ def test_all_queued_equals_step_by_step_byte_for_byte(pp, queued, stepwise, want
     for i, (got, w) in enumerate(zip(queued, want)):
         K.same_as_chain(got, w, f"queued, cycle {i}")
         K.same_inflation(pp, got, f"queued, cycle {i}")
+        K.same_plan(pp, got, f"queued, cycle {i}")
         K.same_bytes(got, stepwise[i], f"queued against stepwise, cycle {i}")
     _not_empty(queued)
+    _planner_reached(queued)
 
 
 # ---- 3 ----
@@ -147,8 +190,8 @@ def test_ingested_feed_equals_the_queued_run(pp, seq, engines, queued, want):
         with pytest.raises(RuntimeError, match=REFUSED):                               # 3. refused by design (module docstring) ...
             eng.crop_to_image_async(c["planes"])
         eng.ingest_pointcloud2_async(stagings[-1], first=0, decimate=1)                # ... so the kept rows arrive as a feed
-        K.queue_behind_crop(eng, c, dts(c["stamps"]))                                  # 4. .. 9.
-        outs.append(K.fetch_all(eng, len(c["frames"]), crop=False))
+        K.queue_behind_crop(eng, c, dts(c["stamps"]))                                  # 4. .. 13.
+        outs.append(K.fetch_all(eng, c, crop=False))
         assert np.array_equal(eng.ingest_info()["kept"], queued[i]["kept"])
     eng.sync()
     for st in stagings:
@@ -169,12 +212,13 @@ def test_every_ring_full_at_once(pp, seq, engines, queued, want):
     for c, st in zip(seq, stagings):                                    # nothing fetched, no sync(): every ring turns twice
         eng.upload_async(st)
         K.queue_stages(eng, c, dts(c["stamps"]))
-    got = K.fetch_all(eng, K.STREAMS)
+    got = K.fetch_all(eng, seq[-1])
     eng.sync()
     for st in stagings:
         st.close()
     K.same_as_chain(got, want[-1], "back to back, last cycle")
     K.same_inflation(pp, got, "back to back, last cycle")
+    K.same_plan(pp, got, "back to back, last cycle")
     K.same_bytes(got, queued[-1], "back to back against queued, last cycle")
     # the stateful outputs vouch for every earlier cycle: tracks that lived through them, sweeps of the two before
     assert got["tracks"][0]["hits"].max() >= 4 and (got["sweeps_info"]["used"] == 2).all()
@@ -195,7 +239,7 @@ def test_streams_are_independent(pp, seq, engines, queued, want):
         stagings.append(eng.staging(c["frames"]))
         eng.upload_async(stagings[-1])
         K.queue_stages(eng, c, dts(c["stamps"]))
-        return K.fetch_all(eng, len(c["frames"]))
+        return K.fetch_all(eng, c)
 
     for i in range(at):
         K.same_bytes(cycle(seq[i]), queued[i], f"before the short call, cycle {i}")
@@ -204,6 +248,8 @@ def test_streams_are_independent(pp, seq, engines, queued, want):
     got = cycle(two)
     K.same_as_chain(got, chain.step(two), "the short call")
     assert got["n"].shape == (2,) and got["occ_grid"].shape[0] == 2 and got["infl_cm"][0].shape[0] == 2
+    assert got["field_cm"].shape[0] == 2 and got["keys_occ"].shape[0] == 2 and len(got["traj_occ"]) == 2
+    K.same_plan(pp, got, "the short call")
     K.reset_stream(eng, 1)
     chain.reset(1)
     dts.reset(1)
@@ -213,6 +259,7 @@ def test_streams_are_independent(pp, seq, engines, queued, want):
         # stream 2 goes on from where it was before the short call, stream 1 from nothing, stream 0 from the short call
         K.same_as_chain(got, w, f"after the short call, cycle {i}")
         K.same_inflation(pp, got, f"after the short call, cycle {i}")
+        K.same_plan(pp, got, f"after the short call, cycle {i}")
         K.same_as_chain(got, fresh.step(seq[i]), f"stream 1 against a fresh chain, cycle {i}", streams=[1])
         K.same_as_chain(got, want[i], f"stream 0 against the full run, cycle {i}", streams=[0])
         assert got["sweeps_info"]["used"][1] == i - at - 1
@@ -250,6 +297,7 @@ def test_next_feed_queued_before_this_cycles_fetch(pp, seq, engines, queued, wan
         eng.costmap_async()
         eng.inflate_async("costmap")
         eng.inflate_async("occupancy")
+        K.queue_plan(eng, c)                                            # 10. .. 13. of cycle i: queued before the next feed ...
         if not last:
             feed(i + 1)                                                 # accepted: nothing of it is refused
         else:
@@ -257,6 +305,7 @@ def test_next_feed_queued_before_this_cycles_fetch(pp, seq, engines, queued, wan
         got.update(K.fetch_pass(eng, K.STREAMS))
         got.update(K.fetch_costmap(eng))
         got.update(K.fetch_inflated(eng))
+        got.update(K.fetch_plan(eng, c))                                # ... and fetched after it, in cycle i's frame
         if not last:
             nxt = {"kept": eng.crop_info(), "sweeps_info": eng.sweeps_info()}          # (of cycle i + 1 by now)
         outs.append(got)
@@ -267,6 +316,11 @@ def test_next_feed_queued_before_this_cycles_fetch(pp, seq, engines, queued, wan
         K.same_as_chain(got, want[i], f"fed ahead, cycle {i}")
         K.same_bytes(got, queued[i], f"fed ahead against queued, cycle {i}")
         assert ("occ_grid" in got) == (i + 1 == len(seq)) and "infl_occ" in got
+        # the window has moved on under most of these fetches: the paths in metres are still those of cycle i's window
+        assert np.array_equal(got["plan_origin_occ"], want[i]["occ_origin"]), i
+        for b in range(K.STREAMS):
+            assert got["paths_m_occ"][b].dtype == np.float64 and np.array_equal(got["paths_m_occ"][b], want[i]["paths_m_occ"][b]), (i, b)
+    assert any(not np.array_equal(want[i]["occ_origin"], want[i + 1]["occ_origin"]) for i in range(len(seq) - 1))
     _not_empty(outs)
 
 
@@ -283,3 +337,72 @@ def test_plain_launches_give_the_same_digests(pp, queued):
     assert child["no_graph"] == "1"
     assert child["digests"] == [K.digest(o) for o in queued]
     assert len(set(child["digests"])) == len(queued) and child["detections"] == sum(int(o["n"].sum()) for o in queued) > 0
+
+
+# ---- 8 ----
+def test_the_command_one_cycle_behind(pp, seq, engines, queued, want):
+    """Cycle i queued whole, plan included and unfetched; cycle i + 1 queued through both inflations; then cycle i's planner
+    results are asked for (module docstring)."""
+    eng = engines[0]
+    K.reset_all(eng)
+    dts = K.Dt(pp, eng)
+    stagings = [eng.staging(c["frames"]) for c in seq]
+    queued_occ = 5                                                      # api_navfn.hip default_rounds(37, 29): 2 + 2 / 2 + 2
+    assert K.NAV_OCC.get("queued_rounds", 0) == 0 and K.NAV_CM["queued_rounds"] == 1
+    nav = [k for k in queued[0] if k.split("_")[0] in ("field", "paths", "nav")]
+    local = lambda s: [f"plan_info_{s}", f"traj_{s}", f"movers_{s}"]
+    behind = refused_occ = 0
+
+    def stages(i):                                                      # 1. .. 9. of cycle i
+        eng.upload_async(stagings[i])
+        eng.occupancy_update_async(seq[i]["poses"])
+        eng.crop_to_image_async(seq[i]["planes"])
+        eng.accumulate_sweeps_async(seq[i]["poses"], seq[i]["stamps"])
+        eng.set_track_dt(dts(seq[i]["stamps"]))
+        eng.set_track_pose(seq[i]["poses"])
+        eng.detect_async()
+        eng.costmap_async()
+        eng.inflate_async("costmap")
+        eng.inflate_async("occupancy")
+
+    stages(0)
+    for i in range(len(seq) - 1):
+        c, what = seq[i], f"one behind, cycle {i}"
+        K.queue_plan(eng, c)                                            # 10. .. 13. of cycle i, nothing of it fetched
+        stages(i + 1)                                                   # both inflated buffers now hold cycle i + 1's grids
+        # the navigation function copied its costs at the call: the fields, paths and info are cycle i's, both sources
+        got = K.fetch_navfn(eng, c)
+        got["n"] = queued[i]["n"]
+        K.same_bytes({k: got[k] for k in nav + ["n"]}, queued[i], what)
+        assert set(nav) <= set(got) and np.array_equal(got["plan_origin_occ"], want[i]["occ_origin"]), what
+        assert (got["nav_info_cm"]["rounds"] > 1).all(), what
+        # the costmap's command needs the second rollout, over a grid that is no longer there: refused
+        for fetch in (eng.local_commands, eng.local_plan_info, eng.local_trajectories, eng.local_keys):
+            with pytest.raises(RuntimeError, match=REMADE.format("costmap")):
+                fetch("costmap")
+        # the occupancy field settled within the rounds its call queued, unless a grid ran all of them and more
+        if (got["nav_info_occ"]["rounds"] <= queued_occ).all():
+            occ = K.fetch_local(eng, "occ", "occupancy", keys=False)
+            occ["n"] = queued[i]["n"]
+            K.same_bytes({k: occ[k] for k in local("occ") + ["n"]}, queued[i], what)
+            assert set(local("occ")) <= set(occ)
+            with pytest.raises(RuntimeError, match=REMADE.format("occupancy")):      # keys were not stored: a rollout again
+                eng.local_keys("occupancy")
+            assert eng.local_plan_info("occupancy")["cmd_state"].tobytes() == queued[i]["plan_info_occ"]["cmd_state"].tobytes()
+            behind += 1
+        else:
+            with pytest.raises(RuntimeError, match=REMADE.format("occupancy")):
+                eng.local_commands("occupancy")
+            refused_occ += 1
+        # the handle goes on: cycle i + 1's plan, queued and fetched in order
+        K.queue_plan(eng, seq[i + 1])
+        nxt = K.fetch_plan(eng, seq[i + 1])
+        nxt["n"] = queued[i + 1]["n"]
+        K.same_bytes(nxt, queued[i + 1], f"in order again, cycle {i + 1}")
+    got = K.fetch_all(eng, seq[-1])
+    eng.sync()
+    for st in stagings:
+        st.close()
+    K.same_bytes(got, queued[-1], "one behind, the last cycle whole")
+    print(f"one behind: occupancy commands fetched in {behind} cycles, refused in {refused_occ}")
+    assert behind >= (len(seq) - 1) // 2

@@ -99,6 +99,54 @@ def test_both_inflations_raise_cells(run):
             assert grid.dtype == np.int8 and d2.dtype == np.uint16
 
 
+def test_the_planner_reaches_what_the_gpu_comparison_is_meant_to_see(pp, run):
+    """Per source: commands on enough valid samples; movers that end samples and movers that are passed closely; a field
+    without a goal, an arrival or a stop; and nothing that stands still from one cycle to the next, or a stale grid or
+    field would pass unseen."""
+    _, outs = run
+    pairs = len(outs) * K.STREAMS
+    states = []
+    for s, _ in K.SRC:
+        info = [o[f"plan_info_{s}"] for o in outs]
+        good = sum(int(((w["cmd_state"] == 0) & (w["n_ok"] >= 8)).sum()) for w in info)
+        assert 2 * good >= pairs, (s, good, pairs)
+        states += [int(v) for w in info for v in w["cmd_state"]]
+        for w, o in zip(info, outs):
+            total = w["n_ok"] + w["n_outside"] + w["n_collision"] + w["n_unreached"] + w["n_dynamic"]
+            rolled = w["cmd_state"] <= 1
+            assert (total[rolled] == 65).all() and (total[~rolled] == 0).all(), (s, total)
+            assert np.array_equal(w["cmd_state"] == 4, o[f"nav_info_{s}"]["goal_state"] != 0), s
+    dyn = sum(int((o[f"plan_info_{s}"]["n_dynamic"] > 0).sum()) for o in outs for s, _ in K.SRC)
+    near = sum(int((o[f"plan_info_{s}"]["near"] > 0).sum()) for o in outs for s, _ in K.SRC)
+    assert dyn > 0 and near > 0, (dyn, near)
+    assert 4 in states and (1 in states or 2 in states), sorted(set(states))
+    assert pp.local_planner.MoverConfig(**K.MOV_CM).confirmed_only != pp.local_planner.MoverConfig(**K.MOV_OCC).confirmed_only
+    still = []
+    for s, infl in (("cm", "infl_cm"), ("occ", "infl_occ")):
+        for i, (a, b) in enumerate(zip(outs, outs[1:])):
+            for k in range(K.STREAMS):
+                same = (np.array_equal(a[infl][0][k], b[infl][0][k]), np.array_equal(a[f"field_{s}"][k], b[f"field_{s}"][k]),
+                        a[f"keys_{s}"][k].min() == b[f"keys_{s}"][k].min())
+                still += [(s, what, i, i + 1, k) for what, v in zip(("inflated grid", "field", "best key"), same) if v]
+    assert not still, still
+
+
+def test_the_costmap_field_is_never_settled_by_one_round(pp, run):
+    """NAV_CM queues one round.  A round relaxes each 32 x 32 tile against the halo the round before left, so a potential
+    crosses one tile edge per round at the most: with a goal in the grid and a reached cell in another tile than the
+    goal's, one round cannot give the exact field, and every fetch goes through the getter's settle and second rollout."""
+    _, outs = run
+    H, W = K.GRID["height"], K.GRID["width"]
+    assert K.NAV_CM["queued_rounds"] == 1 and W > K.NAV_TILE and H > K.NAV_TILE
+    for i, o in enumerate(outs):
+        goals = pp.navfn.goal_cells(o["plan_in"]["goals_cm"], K.cm_origins(K.STREAMS), K.GRID["resolution"], (H, W))
+        assert (o["nav_info_cm"]["goal_state"] == 0).all(), (i, o["nav_info_cm"]["goal_state"])
+        for b in range(K.STREAMS):
+            ys, xs = np.nonzero(o["field_cm"][b] != pp.navfn.UNREACHED)
+            other = (xs // K.NAV_TILE != goals[b, 0] // K.NAV_TILE) | (ys // K.NAV_TILE != goals[b, 1] // K.NAV_TILE)
+            assert other.any(), (i, b)
+
+
 def test_a_reset_stream_continues_as_a_fresh_chain_does(pp, run):
     """What the GPU test's stream-independence case relies on: no stream's outputs depend on another's, and the short call
     and the reset both show in what follows (a run that ignored either would not pass by accident)."""
@@ -132,15 +180,13 @@ def test_the_documented_call_order_is_the_one_the_gpu_test_runs():
     with open(os.path.join(root, "INTEGRATION.md")) as f:
         doc = f.read()
     listing = doc[doc.index("# One navigation cycle"):]
-    steps = [m.group(2) for m in re.finditer(r"^#\s+(\d)\. (engine\..*?)(?:\s{2,}#.*)?$", listing, re.M)][:9]
-    assert len(steps) == 9
-    documented = [c.group(1) + (c.group(2) if c.group(1) == "inflate_async" else "")
-                  for c in re.finditer(r"engine\.(\w+)(\(\"\w+\"\))?", " ".join(steps))]
+    n = len(K.CYCLE_CALLS) - 1                      # (step 5 is two calls on one line)
+    steps = [(int(m.group(1)), m.group(2)) for m in re.finditer(r"^#\s+(\d+)\. (engine\..*?)(?:\s{2,}#.*)?$", listing, re.M)][:n]
+    assert [k for k, _ in steps] == list(range(1, n + 1)) and n == 13
+    documented = K.calls_in(" \n".join(line.replace("; engine.", "\nengine.") for _, line in steps), "engine")
     assert tuple(documented) == K.CYCLE_CALLS
-    src = "".join(inspect.getsource(f) for f in (K.run_queued, K.queue_stages, K.queue_behind_crop))
-    made = [c.group(1) + (c.group(2) if c.group(1) == "inflate_async" else "")
-            for c in re.finditer(r"eng\.(\w+)(\(\"\w+\"\))?", src)]
-    made = [c for c in made if c.split("(")[0] in {x.split("(")[0] for x in K.CYCLE_CALLS}]
+    src = "".join(inspect.getsource(f) for f in (K.run_queued, K.queue_stages, K.queue_behind_crop, K.queue_plan))
+    made = [c for c in K.calls_in(src, "eng") if c.split("(")[0] in {x.split("(")[0] for x in K.CYCLE_CALLS}]
     assert tuple(made) == K.CYCLE_CALLS
 
 
