@@ -129,6 +129,7 @@ int pp_costmap_async(pp_handle e) {
     // the next upload but one writes the buffer read here: its writer waits for this event as for a pass
     HIPCHK(e, hipEventRecord(e->ev_read[e->in_buf], e->stream));
     g.batch = B; g.run_pitch = g.pitch; g.run_w = c.width; g.run_h = c.height; g.run_objects = c.objects;
+    g.run_res = c.resolution;
     return PP_OK;
 }
 

@@ -120,11 +120,13 @@ int pp_inflate_async(pp_handle e, int32_t source) {
     const pp_engine::Occupancy& o = e->occ;
     if (!(cm ? c.on : o.on))
         return fail(e, PP_ERR_STATE, "%s: the %s stage is not configured (%s first)", who, name, cm ? "pp_set_costmap" : "pp_set_occupancy");
-    const double res = cm ? c.cfg.resolution : o.cfg.resolution;
+    const int batch = cm ? (c.grid ? c.batch : 0) : (o.marks ? o.batch : 0);
+    // the resolution of the grids that lie there: of the costmap's last run, whatever pp_set_costmap has given since (its
+    // buffers and that run stay while the shape stands); an occupancy configuration of another resolution forgets the maps
+    const double res = cm ? (batch > 0 ? c.run_res : c.cfg.resolution) : o.cfg.resolution;
     if (res != g.cfg.resolution)
         return fail(e, PP_ERR_STATE, "%s: the %s stage has resolution = %g, the inflation table was built for %g (pp_set_inflation again)",
                     who, name, res, g.cfg.resolution);
-    const int batch = cm ? (c.grid ? c.batch : 0) : (o.marks ? o.batch : 0);
     if (int st = check_last_run(e, who, batch, batch, false, cm ? "no costmap stage has run (pp_costmap_async first)"
                                 : "no update has run (pp_occupancy_update_async first)", "run", "grids")) return st;
     const int W = cm ? c.run_w : o.cfg.width, H = cm ? c.run_h : o.cfg.height, pitch = cm ? c.run_pitch : o.pitch;

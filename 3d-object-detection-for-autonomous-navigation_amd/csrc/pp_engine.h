@@ -398,6 +398,7 @@ struct pp_engine {
         int* info = nullptr;               // [2][B]: footprints, flagged
         int batch = 0;                     // frames of the last run (pp_get_costmaps; 0: none)
         int run_pitch = 0, run_w = 0, run_h = 0, run_objects = 0;   // ... and its grid
+        double run_res = 0.0;              // ... and the resolution its cells were counted at (pp_inflate_async compares its table's)
     } cmap;
 
     // pp_set_occupancy: one rolling log-odds window per stream in the fixed frame, updated from the resident frames under

@@ -424,7 +424,7 @@ class Engine:
         if d.sweeps is not None:
             self.set_sweeps(d.sweeps)
         self._costmap_queued = False                            # a costmap_async whose grids costmaps() has not fetched
-        self._infl_run = {}                                     # source index -> (batch, (H, W), origins [B, 2], poses [B, 3, 4] or None) of the run its last inflate_async read
+        self._infl_run = {}                                     # source index -> (batch, (H, W), origins [B, 2], poses [B, 3, 4] or None, resolution) of the run its last inflate_async read
         self._navfn_run = {}                                    # source index -> (batch, (H, W), max_path, origins, resolution, poses) of its last navfn_async
         self._local_run = {}                                    # source index -> (batch, LocalPlanConfig, resolution or None, step dt or None) of its last local_plan_async
         self._local_movers_run = {}                             # source index -> the MoverConfig that run used, or None
@@ -1100,7 +1100,9 @@ class Engine:
         self._check(self._lib.pp_costmap_async(self._h), "pp_costmap_async")
         self._costmap_queued = True
         self._costmap_batch = self._batches()[0]
-        self._costmap_shape = (self.costmap.height, self.costmap.width)
+        c = self.costmap
+        self._costmap_shape = (c.height, c.width)
+        self._costmap_frame = (c.x_min, c.y_min, c.resolution)  # (of this run: set_costmap may give another before inflate_async)
 
     def costmaps(self, batch=None, counts=False):
         """The grids int8 [B, H, W] of the resident frames (waits for them): of the costmap_async still unfetched, else the
@@ -1165,6 +1167,7 @@ class Engine:
         self._occ_batch = B
         self._occ_origins = np.array(cells, np.float64).reshape(B, 2) * c.resolution      # (pp_get_occupancy's arithmetic)
         self._occ_shape = (c.height, c.width)
+        self._occ_res = c.resolution
         self._occ_poses = P.copy()                              # (local_plan_async's default poses)
 
     def occupancy_maps(self, batch=None, logodds=False):
@@ -1235,21 +1238,23 @@ class Engine:
         its inflation is off, the source has not run, or its resolution is not the inflation's.  It reads the source's
         grids as they are when it runs: queue it before the next costmap_async / occupancy_update_async to inflate this
         cycle's grids; the inflated grids then stay while the source runs again, until the next inflate_async of that
-        source -- and so does their frame: the call records the origins and the poses of the run it inflates, and
-        navfn_async, local_plan_async's default poses, the movers' frame and inflated_occupancy_maps read them from that
-        record, not from whatever occupancy_update_async has run since.  A navfn_async has to follow before the next
+        source -- and so does their frame: the call records the batch, the shape, the origins, the resolution and the
+        poses of the run it inflates (for the costmap as costmap_async found them, whatever set_costmap has given
+        since), and navfn_async, local_plan_async's default poses, the movers' frame and inflated_occupancy_maps read them
+        from that record, not from whatever occupancy_update_async has run or set_costmap / set_occupancy has given since:
+        the source may even be off by then.  The table's resolution is held to the run's as well.  A navfn_async has to follow before the next
         local_plan_async or drive: the local planner refuses a field made on the grids this call replaces
         (PP_ERR_STATE), and so does a getter that would have to roll the samples again."""
         k = self._infl_source(source)
         self._check(self._lib.pp_inflate_async(self._h, k), "pp_inflate_async")
         if k == 0:
-            c = self.costmap
             B = self._costmap_batch
-            org = np.tile(np.array([[c.x_min, c.y_min]], np.float64), (B, 1))      # the sensor frame: the sensor at yaw 0
-            self._infl_run[k] = (B, self._costmap_shape, org, None)
+            x_min, y_min, res = self._costmap_frame                # (of the costmap_async it read, not of the configuration in force)
+            org = np.tile(np.array([[x_min, y_min]], np.float64), (B, 1))          # the sensor frame: the sensor at yaw 0
+            self._infl_run[k] = (B, self._costmap_shape, org, None, res)
         else:
             B = self._occ_batch
-            self._infl_run[k] = (B, self._occ_shape, self._occ_origins[:B].copy(), self._occ_poses[:B].copy())
+            self._infl_run[k] = (B, self._occ_shape, self._occ_origins[:B].copy(), self._occ_poses[:B].copy(), self._occ_res)
 
     @staticmethod
     def _infl_batch(batch, run, who):
@@ -1319,11 +1324,8 @@ class Engine:
         the grids' frame as inflate_async recorded it, whatever the source has run since."""
         if k not in self._infl_run:
             raise RuntimeError(f"{who}: no inflation has run on the {_infl.SOURCES[k]} source (inflate_async first)")
-        B, shape, org, poses = self._infl_run[k]
-        c = self.costmap if k == 0 else self.occupancy
-        if c is None:
-            raise RuntimeError(f"{who}: the {_infl.SOURCES[k]} stage is not configured (set_{_infl.SOURCES[k]} first)")
-        return B, shape, org.copy(), c.resolution, poses
+        B, shape, org, poses, res = self._infl_run[k]
+        return B, shape, org.copy(), res, poses
 
     def _navfn_cells_async(self, k, goals, starts):
         """pp_navfn_async on cells: goals int32 [B, 2], starts int32 [B, 2] or None (no paths)."""
@@ -1337,8 +1339,10 @@ class Engine:
         """Queues the field and the paths on the grids of the source's last inflation behind whatever the engine's stream
         holds (pp_navfn_async) and returns at once.  goals float64 [B, 2] (or one (x, y) for every grid), metres in the
         grids' frame: the sensor frame for the costmap, the fixed frame for the occupancy maps; they become cells through
-        navfn.goal_cells with the run's origins and the source's resolution, so a goal outside a window is no error
-        (goal_state 2).  starts=None: the sensor's own cell -- floor((0 - x_min) / resolution) and likewise in y for the
+        navfn.goal_cells with the origins and the resolution inflate_async recorded for those grids, so a goal outside a
+        window is no error (goal_state 2) and a set_costmap / set_occupancy since, None included, changes nothing.  The
+        run's own record holds (batch, shape, max_path, origins, resolution, poses): the getters and local_plan_async
+        read it, not the configurations in force.  starts=None: the sensor's own cell -- floor((0 - x_min) / resolution) and likewise in y for the
         costmap, (W // 2, H // 2) for the occupancy maps; an array like `goals`: those points; False: no paths."""
         k = self._infl_source(source)
         B, shape, org, res, poses = self._navfn_frame(k, "navfn_async")
@@ -1474,8 +1478,11 @@ class Engine:
         one for every grid), metres and radians in the grids' frame; None: the sensor at yaw 0 for the costmap, the
         translation and atan2(R10, R00) of the poses of the occupancy_update_async whose maps the field's inflation read
         (inflate_async records them) for the occupancy maps.  They become
-        sub-cells and ticks through local_planner.pose_ticks with the navfn run's origins and the source's resolution, so
-        a pose outside its window is no error (cmd_state 3).  windows integers [B, 4] (v0, dv, w0, dw) (or one), as
+        sub-cells and ticks through local_planner.pose_ticks with the navfn run's origins and resolution (its record), so
+        a pose outside its window is no error (cmd_state 3).  The run's own record holds (batch, LocalPlanConfig,
+        resolution, step dt) and the MoverConfig it used: the getters size and unpack by them and
+        local_commands(metric=True) converts by them, whatever set_local_planner, set_local_movers or set_costmap give
+        afterwards.  windows integers [B, 4] (v0, dv, w0, dw) (or one), as
         local_planner.LocalLimits.window makes them; None: sv from 0 to 1024 and sw from -512 to 512.  dt: the seconds of
         a step, which `local_commands(metric=True)` needs -- and the source's movers, while set_local_movers has them
         on: the call then builds their table from the streams' tracks first (pp_local_plan_movers_async)."""

@@ -1396,7 +1396,8 @@ int pp_get_inflation_config(pp_handle h, int32_t source, int32_t* on, pp_inflati
  * queued behind whatever the handle's stream holds, one launch.  Reads the source's device grid in place (rows of
  * (width + 3) & ~3 cells) and writes buffers of its own, made here for the source's shape: never the source's grid or
  * log-odds.  Refused before anything is queued, PP_ERR_STATE: the source's inflation or the source stage is off, the
- * source has not run, its resolution is not the one the table was built for, a training step is in flight. */
+ * source has not run, its resolution is not the one the table was built for, a training step is in flight.  The
+ * costmap's resolution is that of its last run, the cells that lie there, whatever pp_set_costmap has given since. */
 int pp_inflate_async(pp_handle h, int32_t source);
 /* The grids of the source's last pp_inflate_async (waits for the stream): grid int8 [batch][height][width]; dist2 uint16
  * of the same shape or NULL, the squared cell distance to the nearest obstacle (R * R + 1: none in reach).  A stream of
