@@ -28,7 +28,7 @@ static_assert(PP_INFLATE_COSTMAP == 0 && PP_INFLATE_OCCUPANCY == 1, "pp_engine::
 
 namespace {
 
-constexpr int LOC_MAX_SV = 1024, LOC_MAX_SW = 512, LOC_TRIG_ONE = 16384;
+constexpr int LOC_MAX_SV = 1024, LOC_MAX_SW = 512;
 
 const char* source_name(int source) { return source == PP_INFLATE_COSTMAP ? "costmap" : "occupancy"; }
 
@@ -49,20 +49,6 @@ int check_config(pp_engine* e, const char* who, const pp_local_plan_config& c) {
 int check_source(pp_engine* e, const char* who, int source) {
     if (source != PP_INFLATE_COSTMAP && source != PP_INFLATE_OCCUPANCY)
         return fail(e, PP_ERR_ARG, "%s: source = %d (0 PP_INFLATE_COSTMAP, 1 PP_INFLATE_OCCUPANCY)", who, source);
-    return PP_OK;
-}
-
-// trig int32 [n_trig][2] = (C, S) -> a word per tick, C in the low half
-int pack_trig(pp_engine* e, const char* who, const int32_t* trig, int n_trig, std::vector<unsigned>& out) {
-    if (!trig) return fail(e, PP_ERR_ARG, "%s: trig is NULL", who);
-    if (n_trig != PP_LOCAL_HEADINGS) return fail(e, PP_ERR_ARG, "%s: the trig table has %d entries, it must have PP_LOCAL_HEADINGS = %d", who, n_trig, PP_LOCAL_HEADINGS);
-    out.resize((size_t)PP_LOCAL_HEADINGS);
-    for (int h = 0; h < PP_LOCAL_HEADINGS; ++h) {
-        const int c = trig[2 * h], s = trig[2 * h + 1];
-        if (c < -LOC_TRIG_ONE || c > LOC_TRIG_ONE || s < -LOC_TRIG_ONE || s > LOC_TRIG_ONE)
-            return fail(e, PP_ERR_ARG, "%s: trig[%d] = (%d, %d) outside [-%d, %d]", who, h, c, s, LOC_TRIG_ONE, LOC_TRIG_ONE);
-        out[(size_t)h] = ((unsigned)c & 0xFFFFu) | ((unsigned)s << 16);
-    }
     return PP_OK;
 }
 

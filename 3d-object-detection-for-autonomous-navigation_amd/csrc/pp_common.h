@@ -856,6 +856,40 @@ struct LocalMoverParams {
 };
 void launch_local_movers(const LocalMoverParams& p, hipStream_t s);
 
+// scan_match.hip: the resident points under a prior pose per stream, matched against the stream's log-odds window
+// (pp_set_scan_match, pp_scan_match_grids; scan_match.py states the rule)
+struct ScanCall {                  // what travels from the host per stream and call: 6 doubles, 4 int32
+    double r0[3], r1[3];           // rows 0 and 1 of the prior's rotation
+    int sx, sy;                    // the sensor in sub-cells of the stream's window (0 where flags are set)
+    int flags;                     // PP_SCAN_NO_MAP | PP_SCAN_OUTSIDE: nothing is scored
+    int src;                       // which of the two log-odds copies holds the stream's map
+};
+constexpr int SCAN_TILE = 64;      // translation candidates of a workgroup of k_scan_scores: one per lane of a wave
+constexpr int SCAN_INFO = 4;       // int32 per stream in front of the marks: rows used, rows ignored, scan cells, spare
+struct ScanParams {
+    pp_occupancy_config occ;       // resolution, z_min, z_max, max_range, width, height
+    pp_scan_match_config cfg;
+    int batch, F;
+    int pitch;                     // cells of a row of the log-odds
+    size_t map_stride;             // cells from one stream's log-odds to the next
+    int max_n;                     // the host's bound on the rows of a frame
+    int list_cap;                  // entries of a stream's list
+    int mark_words;                // 32-bit words of a stream's marks: a bit per cell of width * height
+    int n_trans, tiles;            // (2 nx + 1)(2 ny + 1), and the workgroups of a heading that cover them
+    const float* points;           // the resident rows [.][F]
+    const int* offsets;            // [batch + 1] device values
+    const ScanCall* call;          // [batch]
+    const unsigned* trig;          // [PP_LOCAL_HEADINGS]: C[h] as int16 in the low half, S[h] in the high half
+    const int16_t* logodds[2];     // [.][map_stride] each; stream b's lies in logodds[call[b].src]; 0 where not known
+    int* info;                     // [batch][SCAN_INFO], cleared with the marks before the launches
+    unsigned* marks;               // [batch][mark_words], cleared before the launches
+    int2* list;                    // [batch][list_cap]: (ux, uy) of every scan cell, each once, in no fixed order
+    int* scores;                   // [batch][candidates]
+    unsigned long long* partial;   // [batch][(2 nt + 1) * tiles]: a workgroup's least key
+    int* words;                    // [batch][PP_SCAN_RESULT]
+};
+void launch_scan_match(const ScanParams& p, hipStream_t s);         // info and marks cleared before it
+
 // weight_publish.hip: the trainer's flat parameter / state buffers -> the detector's weight arrays, on the device
 enum PubKind {
     PUB_PFN_W,       // out [FA][cout] = params[src] * scale[c]

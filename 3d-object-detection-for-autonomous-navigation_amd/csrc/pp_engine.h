@@ -501,6 +501,30 @@ struct pp_engine {
         LocalFrame* d_frame = nullptr;     // [B]
         RingArray<LocalFrame> h_frame;     // [B] per slot, a rider of `ring`
     } local[2];                           // by source, as infl
+
+    // pp_set_scan_match: the resident frames under a prior pose per stream, matched against occ.logodds, which it reads in
+    // place and never writes (api_scan_match.hip).  Plain launches on the handle's stream: cells, scores, finish.  Nothing
+    // of it in PostRule, DetectKey or a captured pass, and api_occupancy.hip knows nothing of it: the stage compares the
+    // occupancy window's shape with its own buffers' at every call.
+    struct ScanMatch {
+        bool on = false;                   // pp_set_scan_match gave a configuration and has not taken it back
+        pp_scan_match_config cfg = {};     // the last configuration given
+        unsigned* trig = nullptr;          // [PP_LOCAL_HEADINGS] packed; this and the next two live as long as the handle (`allocs`)
+        int* words = nullptr;              // [B][PP_SCAN_RESULT]
+        ScanCall* d_call = nullptr;        // [B]
+        CallRing ring;                     // the calls' priors, consumed on the main stream
+        RingArray<ScanCall> h_call;        // [B] per slot
+        StageMem mem_cfg;                  // owns scores and partial, made by pp_set_scan_match for the configuration: not in `allocs`
+        int* scores = nullptr;             // [B][cand_cap]
+        unsigned long long* partial = nullptr;     // [B][part_cap]
+        int cand_cap = 0, part_cap = 0;
+        StageMem mem_win;                  // owns clear and list, made by pp_scan_match_async for the occupancy window's shape: not in `allocs`
+        unsigned* clear = nullptr;         // [B][SCAN_INFO] the tallies, then [B][mark_words] the marks: one clear per call
+        int2* list = nullptr;              // [B][list_cap]
+        int win_w = 0, win_h = 0, list_cap = 0, mark_words = 0;     // what the two were made for (0: none yet)
+        int batch = 0;                     // streams of the last match (pp_get_scan_match; 0: none)
+        int run_cands = 0;                 // ... and its candidates per stream
+    } scan;
     unsigned long long resident_gen = 0;   // counts the changes of the resident frames (set_resident, a stage call)
     unsigned long long results_gen = 0;    // resident_gen of the last pp_detect_async
 
@@ -669,6 +693,7 @@ void navfn_release(pp_engine* e);                       // api_navfn.hip: what p
 int settle(pp_engine* e, const char* who, const NavParams& p, int* rounds, hipStream_t s, std::vector<int>& host);
 int settled_run(pp_engine* e, const char* who, int source, int batch, pp_engine::Navfn** out);
 void local_plan_release(pp_engine* e);                  // api_local_plan.hip: what pp_destroy frees of the local planner
+void scan_match_release(pp_engine* e);                  // api_scan_match.hip: what pp_destroy frees of the scan match
 int ensure_metrics(pp_engine* e);                       // api_metrics.hip
 void fill_metrics_params(pp_engine* e, int batch, MetricsParams& p);   // ... on the handle's head map and loss.labels
 // ---- api_dataprep.hip: what the fused training steps (api_train.hip) queue ----
@@ -728,6 +753,22 @@ inline int check_cfg_window(pp_engine* e, const char* who, int width, int height
     if (height < 1) return fail(e, PP_ERR_ARG, "%s: height = %d must be >= 1", who, height);
     if ((long long)width * height > max_cells)
         return fail(e, PP_ERR_ARG, "%s: width * height = %lld cells, at most %s = %d", who, (long long)width * height, max_name, max_cells);
+    return PP_OK;
+}
+
+// What pp_set_local_plan, pp_set_scan_match and their stand-alone calls take as the trig table: int32 [n_trig][2] = (C, S)
+// -> a word per tick, C as int16 in the low half, S in the high half
+constexpr int PP_TRIG_ONE = 16384;
+inline int pack_trig(pp_engine* e, const char* who, const int32_t* trig, int n_trig, std::vector<unsigned>& out) {
+    if (!trig) return fail(e, PP_ERR_ARG, "%s: trig is NULL", who);
+    if (n_trig != PP_LOCAL_HEADINGS) return fail(e, PP_ERR_ARG, "%s: the trig table has %d entries, it must have PP_LOCAL_HEADINGS = %d", who, n_trig, PP_LOCAL_HEADINGS);
+    out.resize((size_t)PP_LOCAL_HEADINGS);
+    for (int h = 0; h < PP_LOCAL_HEADINGS; ++h) {
+        const int c = trig[2 * h], s = trig[2 * h + 1];
+        if (c < -PP_TRIG_ONE || c > PP_TRIG_ONE || s < -PP_TRIG_ONE || s > PP_TRIG_ONE)
+            return fail(e, PP_ERR_ARG, "%s: trig[%d] = (%d, %d) outside [-%d, %d]", who, h, c, s, PP_TRIG_ONE, PP_TRIG_ONE);
+        out[(size_t)h] = ((unsigned)c & 0xFFFFu) | ((unsigned)s << 16);
+    }
     return PP_OK;
 }
 

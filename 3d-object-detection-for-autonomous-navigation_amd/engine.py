@@ -21,6 +21,7 @@ from . import occupancy as _occ
 from . import inflation as _infl
 from . import navfn as _nav
 from . import local_planner as _loc
+from . import scan_match as _scan
 from .anchors import build_anchor_cells, build_anchors
 from .config import Derived
 from .weights import check_weights
@@ -1195,6 +1196,74 @@ class Engine:
         org = getattr(self, "_occ_origins", None)
         if org is not None:
             org[slice(None) if stream is None else slice(int(stream), int(stream) + 1)] = np.nan
+
+    # ---- scan match in front of the occupancy update (pp_set_scan_match, pp_scan_match_async, pp_get_scan_match; scan_match.py states the rule) ----
+    def set_scan_match(self, cfg):
+        """A scan_match.ScanMatchConfig, a dict of its fields or True (the defaults): `scan_match_async(poses)` then matches
+        the resident frames under PRIOR poses against the streams' occupancy maps as they stand (set_occupancy first), a
+        brute-force search over a window of translations and headings scored on the maps' log-odds, and `localize(poses)`
+        corrects the priors by it before it fuses the frames.  None: off (the default), and every launch, buffer and
+        result of the other stages is what it was."""
+        if cfg is None or cfg is False:
+            self._check(self._lib.pp_set_scan_match(self._h, None, None, 0), "pp_set_scan_match")
+            return
+        c = _scan.ScanMatchConfig.from_any(cfg)
+        pc = _to_struct(_lib.PPScanMatchConfig, c)
+        trig = np.ascontiguousarray(_loc.trig_table(), np.int32)
+        self._check(self._lib.pp_set_scan_match(self._h, ctypes.byref(pc), _ptr(trig), len(trig)), "pp_set_scan_match")
+
+    @property
+    def scan_match(self):
+        """The ScanMatchConfig in force, or None while the stage is off."""
+        on, pc = self._stage_config("pp_get_scan_match_config", _lib.PPScanMatchConfig)
+        return _from_struct(_scan.ScanMatchConfig, pc) if on else None
+
+    def scan_match_async(self, poses):
+        """Matches the resident frames of streams 0 .. B - 1 under the priors poses [B, 3, 4] float64 against the streams'
+        maps, exactly as scan_match.match_np does on the host (pp_scan_match_async): queued behind whatever the engine's
+        stream holds, returns at once.  B must be the resident batch.  Neither the maps nor their windows change; a stream
+        without a map gives NO_MAP."""
+        c = self.scan_match
+        if c is None:
+            raise RuntimeError("scan_match_async: the scan match is not configured (set_scan_match first)")
+        oc = self.occupancy
+        if oc is None:
+            raise RuntimeError("scan_match_async: the occupancy stage is not configured (set_occupancy first)")
+        P = np.asarray(poses)
+        B = P.shape[0] if P.ndim == 3 else -1
+        if B > self.max_batch:
+            raise ValueError(f"scan_match_async: {B} poses, the engine has {self.max_batch} streams")
+        P = _swp.check_poses(poses, B)
+        self._check(self._lib.pp_scan_match_async(self._h, _ptr(P), B), "pp_scan_match_async")
+        self._scan_run = (B, c, oc, P.copy())                   # (what scan_match_poses corrects, and by what)
+
+    def scan_match_results(self, scores=False):
+        """words int32 [B, 8] (scan_match.WORDS: status, dx, dy, dt in steps, best, prior, n_scan, ignored) of the last
+        scan_match_async (waits for it); scores=True: (words, scores int32 [B, candidates])."""
+        B, c = (self._scan_run[0], self._scan_run[1]) if getattr(self, "_scan_run", None) else (0, None)
+        words = np.zeros((max(B, 1), _lib.PP_SCAN_RESULT), np.int32)
+        sc = np.zeros((max(B, 1), c.candidates if c else 1), np.int32) if scores else None
+        self._check(self._lib.pp_get_scan_match(self._h, _ptr(words), _ptr(sc), B), "pp_get_scan_match")
+        return (words[:B], sc[:B]) if scores else words[:B]
+
+    def scan_match_poses(self):
+        """The corrected poses float64 [B, 3, 4] of the last scan_match_async (waits for it): scan_match.corrected_pose of
+        its words and its priors, by the configurations that call ran with."""
+        return self._scan_correct(self.scan_match_results())
+
+    def _scan_correct(self, words):
+        B, c, oc, P = self._scan_run
+        return np.stack([_scan.corrected_pose(P[b], words[b], oc, c) for b in range(B)])
+
+    def localize(self, poses):
+        """One frame of scan-matched mapping: scan_match_async(poses), the wait, the correction, then
+        occupancy_update_async(corrected).  Returns (corrected float64 [B, 3, 4], words int32 [B, 8]).  On a stream's first
+        frame there is no map yet: the prior comes back with NO_MAP and starts the map."""
+        self.scan_match_async(poses)
+        words = self.scan_match_results()
+        corrected = self._scan_correct(words)
+        self.occupancy_update_async(corrected)
+        return corrected, words
 
     # ---- obstacle inflation behind either grid (pp_set_inflation, pp_inflate_async, pp_get_inflated; inflation.py states the rule; DESIGN 7.1y) ----
     @staticmethod

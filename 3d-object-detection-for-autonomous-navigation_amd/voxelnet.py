@@ -72,6 +72,12 @@ class VoxelNet:
         or ingest and a sweep accumulation."""
         return self.engine.occupancy_update_async(poses)
 
+    def localize(self, poses):
+        """Engine.localize on the resident frames (engine.set_occupancy and engine.set_scan_match first): the priors
+        corrected by a scan match against the streams' maps, then the frames fused under the corrected poses.  Returns
+        (corrected poses [B, 3, 4], words [B, 8])."""
+        return self.engine.localize(poses)
+
     def occupancy_maps(self, batch=None, logodds=False):
         """Engine.occupancy_maps of the last occupancy_update."""
         return self.engine.occupancy_maps(batch, logodds)

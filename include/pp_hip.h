@@ -64,7 +64,10 @@ extern "C" {
  * pp_local_plan_async, pp_get_local_plan, pp_local_plan_grids (declared behind pp_navfn_grids: the stage reads the
  * inflated grid and the field where they lie).  Then PP_LOCAL_MAX_MOVERS, PP_LOCAL_MAX_MOVER_SPEED,
  * PP_LOCAL_MAX_MOVER_RADIUS, PP_LOCAL_MOVER_INFO, pp_local_mover_config, pp_set_local_movers, pp_get_local_movers_config,
- * pp_local_plan_movers_async, pp_get_local_movers, pp_local_plan_grids_movers (declared behind pp_local_plan_grids). */
+ * pp_local_plan_movers_async, pp_get_local_movers, pp_local_plan_grids_movers (declared behind pp_local_plan_grids).  Then
+ * PP_SCAN_MAX_CANDIDATES, PP_SCAN_RESULT, pp_scan_status, pp_scan_match_config, pp_set_scan_match,
+ * pp_get_scan_match_config, pp_scan_match_async, pp_get_scan_match, pp_scan_match_grids (declared behind
+ * pp_local_plan_grids_movers: the stage reads the occupancy maps' log-odds where they lie). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -1597,6 +1600,59 @@ int pp_local_plan_grids_movers(int device, const int8_t* grids, const uint32_t* 
                                const int32_t* goal_state, int32_t horizon, int32_t mover_weight, const int32_t* movers,
                                const int32_t* n_movers, int32_t* result, uint64_t* score, int32_t* traj, uint64_t* keys,
                                int32_t* info);
+
+/* ---- scan match: the resident points of frame b under stream b's PRIOR sensor-to-fixed pose, matched against the
+ * stream's occupancy map as it stands BEFORE the frame is fused into it (scan_match.py states the rule).  Opt-in, off by
+ * default.  SCAN CELLS: per row, float64, dx = ((R00 x + R01 y) + R02 z), dy with row 1 (no translation); gx = floor(dx /
+ * resolution) + width / 2, gy likewise; the row is used iff it passes pp_occupancy_update_async's tests and z >= z_min;
+ * every distinct cell is one scan cell, its centre in sub-cells from the sensor ux = (gx - width / 2) * 1024 + 512.
+ * SENSOR: sx = floor((t_x / resolution - ox) * 1024) with the window's current origin cell, on the host.  CANDIDATES:
+ * c = (it * (2 ny + 1) + iy) * (2 nx + 1) + ix; dh = (it - nt) * theta_step, (C, S) = trig[dh & 4095]; rx = (C ux - S uy +
+ * 8192) >> 14, ry = (S ux + C uy + 8192) >> 14 in int64; the cell cx = (sx + (ix - nx) * xy_step + rx) >> 10, cy likewise;
+ * score[c] = the sum of the log-odds of those cells that lie in the window (unknown cells hold 0).  BEST: the least key
+ * ((2^30 - score) << 32) | ((|it - nt| + |iy - ny| + |ix - nx|) << 16) | c. ---- */
+#define PP_SCAN_MAX_CANDIDATES 65536 /* (2 nx + 1)(2 ny + 1)(2 nt + 1) at most */
+#define PP_SCAN_RESULT 8             /* int32 words per stream: status, ix - nx, iy - ny, it - nt, best score, the prior's score,
+                                        scan cells, rows ignored */
+enum pp_scan_status {                /* bits of word 0 */
+    PP_SCAN_NO_MAP = 1,              /* the stream has no map: nothing scored, every score 0 */
+    PP_SCAN_OUTSIDE = 2,             /* the prior's cell lies outside the stream's window: likewise */
+    PP_SCAN_FEW_CELLS = 4,           /* scan cells < min_cells */
+    PP_SCAN_LOW_SCORE = 8,           /* best * 100 < min_mean * scan cells */
+    PP_SCAN_EDGE = 16                /* the best lies on a face of a search axis whose half-width is > 0 */
+};
+
+typedef struct pp_scan_match_config {
+    int32_t nx;            /* 0 .. 127: half-width of the search window in x, steps */
+    int32_t ny;            /* 0 .. 127 */
+    int32_t nt;            /* 0 .. 127: in heading; (2 nx + 1)(2 ny + 1)(2 nt + 1) <= PP_SCAN_MAX_CANDIDATES */
+    int32_t xy_step;       /* 1 .. 4096 sub-cells (PP_LOCAL_SUB per cell) per translation step */
+    int32_t theta_step;    /* 1 .. 512 ticks (PP_LOCAL_HEADINGS per revolution) per rotation step */
+    int32_t min_cells;     /* 0 .. PP_OCC_MAX_CELLS */
+    int32_t min_mean;      /* -100000 .. 100000: a best score below min_mean * scan cells / 100 is PP_SCAN_LOW_SCORE */
+    int32_t reserved;      /* 0 */
+} pp_scan_match_config;
+
+/* cfg == NULL: the stage off (the default); the buffers are kept.  Otherwise the configuration is validated (PP_ERR_ARG
+ * naming the field); trig as pp_set_local_plan takes it.  PP_ERR_STATE while the occupancy stage is not configured or a
+ * training step is in flight.  Waits for the stream. */
+int pp_set_scan_match(pp_handle h, const pp_scan_match_config* cfg, const int32_t* trig, int32_t n_trig);
+/* *on: 0 / 1; cfg_out (may be NULL): the last configuration given (zeros before the first). */
+int pp_get_scan_match_config(pp_handle h, int32_t* on, pp_scan_match_config* cfg_out);
+/* Matches the resident frames against the maps of streams 0 .. batch - 1 under the priors poses double [batch][3][4],
+ * checked as pp_occupancy_update_async checks its poses.  Queued behind whatever the stream holds (an update queued before
+ * it has been applied, one queued after it has not); returns at once.  Neither the maps nor their windows change. */
+int pp_scan_match_async(pp_handle h, const double* poses, int32_t batch);
+/* The last match: words int32 [batch][PP_SCAN_RESULT], scores int32 [batch][candidates] (may be NULL).  Waits for it. */
+int pp_get_scan_match(pp_handle h, int32_t* words, int32_t* scores, int32_t batch);
+/* Without a handle: logodds int16 and known uint8 (0 / 1) [batch][height][width] in host memory, the rows float32
+ * [offsets[batch]][num_features] with offsets int32 [batch + 1], the priors, origin_cells int32 [batch][2] and has_map
+ * int32 [batch] (0: PP_SCAN_NO_MAP); of occ_cfg resolution, z_min, z_max and max_range are read (its width and height must
+ * be the grids').  words and scores as pp_get_scan_match gives them. */
+int pp_scan_match_grids(int device, const int16_t* logodds, const uint8_t* known, int32_t batch, int32_t height, int32_t width,
+                        const float* points, const int32_t* offsets, int32_t num_features, const double* poses,
+                        const int32_t* origin_cells, const int32_t* has_map, const pp_occupancy_config* occ_cfg,
+                        const pp_scan_match_config* cfg, const int32_t* trig, int32_t n_trig, int32_t* words, int32_t* scores);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
