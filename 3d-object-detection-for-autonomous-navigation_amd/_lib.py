@@ -27,6 +27,7 @@ SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_
            "api_navfn.hip", "navfn.hip",
            "api_local_plan.hip", "local_plan.hip", "local_movers.hip",
            "api_scan_match.hip", "scan_match.hip",
+           "api_frontier.hip", "frontier.hip",
            "api_track.hip", "track.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
@@ -68,6 +69,7 @@ EXPORTS = [
     "pp_set_local_movers", "pp_get_local_movers_config", "pp_local_plan_movers_async", "pp_get_local_movers",
     "pp_local_plan_grids_movers",
     "pp_set_scan_match", "pp_get_scan_match_config", "pp_scan_match_async", "pp_get_scan_match", "pp_scan_match_grids",
+    "pp_set_frontier", "pp_get_frontier_config", "pp_frontier_async", "pp_get_frontiers", "pp_frontier_grids",
     "pp_set_nms_mode", "pp_get_nms_mode", "pp_rotate_nms",
     "pp_set_projection", "pp_get_projection", "pp_get_bboxes", "pp_box3d_to_bbox",
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
@@ -260,6 +262,9 @@ PP_LOCAL_MOVER_INFO = 4         # int32 words per grid of pp_get_local_movers' i
 PP_SCAN_MAX_CANDIDATES = 65536  # pp_scan_match_config: (2 nx + 1)(2 ny + 1)(2 nt + 1) at most
 PP_SCAN_RESULT = 8              # int32 words per stream of pp_get_scan_match's result
 PP_SCAN_NO_MAP, PP_SCAN_OUTSIDE, PP_SCAN_FEW_CELLS, PP_SCAN_LOW_SCORE, PP_SCAN_EDGE = 1, 2, 4, 8, 16      # its status bits
+PP_FRONTIER_MAX = 64            # frontiers pp_get_frontiers returns per grid at most
+PP_FRONTIER_INFO = 6            # int32 words per grid of its info: frontier_cells, clusters, small, unreached, kept, returned
+PP_FRONTIER_NONE = 0xFFFFFFFF   # the label of a cell that is no frontier cell
 PP_CLIP_NONE, PP_CLIP_VALUE, PP_CLIP_NORM, PP_CLIP_GLOBAL_NORM = 0, 1, 2, 3      # enum pp_grad_clip_mode
 
 
@@ -397,6 +402,18 @@ class PPScanMatchConfig(ctypes.Structure):
         ("min_cells", ctypes.c_int32),
         ("min_mean", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
+    ]
+
+
+class PPFrontierConfig(ctypes.Structure):
+    _fields_ = [
+        ("free_max", ctypes.c_int32),
+        ("connectivity", ctypes.c_int32),
+        ("min_size", ctypes.c_int32),
+        ("max_frontiers", ctypes.c_int32),
+        ("rank", ctypes.c_int32),
+        ("use_field", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 2),
     ]
 
 
@@ -681,6 +698,11 @@ def lib():
     L.pp_get_scan_match.argtypes = [vp, vp, vp, i32]
     L.pp_scan_match_grids.argtypes = [ctypes.c_int, vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp,
                                       ctypes.POINTER(PPOccupancyConfig), ctypes.POINTER(PPScanMatchConfig), vp, i32, vp, vp]
+    L.pp_set_frontier.argtypes = [vp, i32, ctypes.POINTER(PPFrontierConfig)]
+    L.pp_get_frontier_config.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(PPFrontierConfig)]
+    L.pp_frontier_async.argtypes = [vp, i32, vp, i32]
+    L.pp_get_frontiers.argtypes = [vp, i32, vp, vp, vp, i32]
+    L.pp_frontier_grids.argtypes = [ctypes.c_int, vp, vp, i32, i32, i32, ctypes.POINTER(PPFrontierConfig), vp, vp, vp, vp]
     L.pp_set_projection.argtypes = [vp, vp, i32]
     L.pp_get_projection.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_get_bboxes.argtypes = [vp, vp]

@@ -115,6 +115,8 @@ int queue_run(pp_engine* e, const LocalParams& p, hipStream_t s) {
     return PP_OK;
 }
 
+}  // namespace
+
 // the source's navigation function has run and the inflated grids it read are still the ones that lie there: the same
 // buffers of the same shape (a freed one would be read otherwise), and no pp_inflate_async since (the buffers are reused
 // while the shape stands, so the pointer alone would pass the next cycle's grids under this cycle's field)
@@ -128,8 +130,6 @@ int check_navfn_run(pp_engine* e, const char* who, int source) {
                     "(pp_navfn_async again)", who, source_name(source));
     return PP_OK;
 }
-
-}  // namespace
 
 void local_plan_release(pp_engine* e) {
     for (pp_engine::LocalPlan& g : e->local) {

@@ -890,6 +890,39 @@ struct ScanParams {
 };
 void launch_scan_match(const ScanParams& p, hipStream_t s);         // info and marks cleared before it
 
+// frontier.hip: int8 OccupancyGrids -> the clusters of their frontier cells, ranked (pp_set_frontier, pp_frontier_grids;
+// frontier.py states the rule)
+struct FrontierCall {              // what travels from the host per grid and call: 4 int32
+    int rx, ry;                    // the reference cell (read while use_field is 0)
+    int flags;                     // FRONTIER_KNOWN (clear: the grid reads all unknown, whatever it holds)
+    int pad;
+};
+constexpr int FRONTIER_KNOWN = 1;
+// per grid int [FR_INFO_WORDS]: the first PP_FRONTIER_INFO are a grid's info words in their order; FR_CELLS, FR_CLUSTERS
+// and FR_OVERRUN are cleared before the launches and added to by them, the others are written by select
+enum { FR_CELLS = 0, FR_CLUSTERS = 1, FR_SMALL = 2, FR_UNREACHED = 3, FR_KEPT = 4, FR_RETURNED = 5, FR_OVERRUN = 6, FR_INFO_WORDS = 8 };
+struct FrontierParams {
+    int batch, width, height;
+    int pitch;                     // cells of a row of `grid`
+    size_t stride;                 // cells from one grid to the next in `grid`
+    int free_max, conn, min_size, max_frontiers, rank, use_field;     // pp_frontier_config
+    const int8_t* grid;            // [batch][height * pitch]; read, never written
+    const FrontierCall* call;      // [batch]
+    const unsigned* pot;           // use_field: [batch][height * pot_pitch], read by select only; else NULL
+    int pot_pitch;
+    size_t pot_stride;
+    // rows of `width` cells, width * height cells from one grid to the next, in everything below
+    unsigned* labels;              // [batch][height * width]: the parent of a frontier cell (its root behind stats), NONE elsewhere
+    unsigned* count;               // the same shape: n at a root
+    unsigned long long* sums;      // [batch][height * width][2]: sx, sy at a root
+    unsigned long long* rep;       // [batch][height * width]: the least representative key at a root
+    unsigned* roots;               // [batch][height * width]: the roots, each once, in no fixed order (FR_CLUSTERS of them)
+    int* info;                     // [batch][FR_INFO_WORDS]
+    int* words;                    // [batch][PP_FRONTIER_MAX][8]
+};
+void launch_frontier(const FrontierParams& p, hipStream_t s);           // mark, label, stats, rep, select; info cleared before it
+void launch_frontier_select(const FrontierParams& p, hipStream_t s);    // the ranking alone, on another field
+
 // weight_publish.hip: the trainer's flat parameter / state buffers -> the detector's weight arrays, on the device
 enum PubKind {
     PUB_PFN_W,       // out [FA][cout] = params[src] * scale[c]

@@ -525,6 +525,31 @@ struct pp_engine {
         int batch = 0;                     // streams of the last match (pp_get_scan_match; 0: none)
         int run_cands = 0;                 // ... and its candidates per stream
     } scan;
+
+    // pp_set_frontier: the clusters of the frontier cells of infl[source].out, ranked as exploration goals; with use_field
+    // the ranking reads navfn[source]'s field.  Both are read in place and never written (api_frontier.hip).  Plain
+    // launches on the handle's stream: mark, label, stats, rep, select; the getter settles the field first and queues
+    // select again if that took a further round.  Nothing of it in PostRule, DetectKey or a captured pass.
+    struct Frontier {
+        bool on = false;                   // pp_set_frontier gave a configuration and has not taken it back
+        pp_frontier_config cfg = {};       // the last configuration given
+        int* info = nullptr;               // [B][FR_INFO_WORDS]; this and the next two live as long as the handle (`allocs`)
+        int* words = nullptr;              // [B][PP_FRONTIER_MAX][8]
+        FrontierCall* d_call = nullptr;    // [B]
+        CallRing ring;                     // the calls' reference cells, consumed on the main stream
+        RingArray<FrontierCall> h_call;    // [B] per slot
+        StageMem mem;                      // owns the five buffers below, made by pp_frontier_async for the inflation run's shape: not in `allocs`
+        unsigned* labels = nullptr;        // [B][h * w]
+        unsigned* count = nullptr;         // [B][h * w]
+        unsigned* roots = nullptr;         // [B][h * w]
+        unsigned long long* sums = nullptr;        // [B][h * w][2]
+        unsigned long long* rep = nullptr;         // [B][h * w]
+        int w = 0, h = 0;                  // the shape they were made for (0: none yet)
+        int batch = 0;                     // grids of the last run (pp_get_frontiers; 0: none)
+        FrontierParams run = {};           // ... what it was launched with
+        unsigned long long nav_run = 0;    // navfn[source].run_id it was queued behind (use_field)
+        int nav_rounds = 0;                // navfn[source].rounds its last select was queued behind
+    } frontier[2];                         // by source, as infl
     unsigned long long resident_gen = 0;   // counts the changes of the resident frames (set_resident, a stage call)
     unsigned long long results_gen = 0;    // resident_gen of the last pp_detect_async
 
@@ -693,6 +718,10 @@ void navfn_release(pp_engine* e);                       // api_navfn.hip: what p
 int settle(pp_engine* e, const char* who, const NavParams& p, int* rounds, hipStream_t s, std::vector<int>& host);
 int settled_run(pp_engine* e, const char* who, int source, int batch, pp_engine::Navfn** out);
 void local_plan_release(pp_engine* e);                  // api_local_plan.hip: what pp_destroy frees of the local planner
+// api_local_plan.hip, for every stage that reads the field in place: the source's navigation function has run on the
+// inflated grids that still lie there
+int check_navfn_run(pp_engine* e, const char* who, int source);
+void frontier_release(pp_engine* e);                    // api_frontier.hip: what pp_destroy frees of the frontier stage
 void scan_match_release(pp_engine* e);                  // api_scan_match.hip: what pp_destroy frees of the scan match
 int ensure_metrics(pp_engine* e);                       // api_metrics.hip
 void fill_metrics_params(pp_engine* e, int batch, MetricsParams& p);   // ... on the handle's head map and loss.labels

@@ -22,6 +22,7 @@ from . import inflation as _infl
 from . import navfn as _nav
 from . import local_planner as _loc
 from . import scan_match as _scan
+from . import frontier as _fr
 from .anchors import build_anchor_cells, build_anchors
 from .config import Derived
 from .weights import check_weights
@@ -426,6 +427,7 @@ class Engine:
             self.set_sweeps(d.sweeps)
         self._costmap_queued = False                            # a costmap_async whose grids costmaps() has not fetched
         self._infl_run = {}                                     # source index -> (batch, (H, W), origins [B, 2], poses [B, 3, 4] or None, resolution) of the run its last inflate_async read
+        self._frontier_run = {}                                 # source index -> (batch, (H, W), origins [B, 2], resolution) of its last frontier_async
         self._navfn_run = {}                                    # source index -> (batch, (H, W), max_path, origins, resolution, poses) of its last navfn_async
         self._local_run = {}                                    # source index -> (batch, LocalPlanConfig, resolution or None, step dt or None) of its last local_plan_async
         self._local_movers_run = {}                             # source index -> the MoverConfig that run used, or None
@@ -1404,6 +1406,13 @@ class Engine:
         c = self.navfn_config(_infl.SOURCES[k])
         self._navfn_run[k] = (int(g.shape[0]), self._infl_run[k][1], c.max_path, None, None, None)     # (no frame in metres yet)
 
+    def _sensor_cells(self, k, B, org, res, shape):
+        """The sensor's own cell per grid, int32 [B, 2]: floor((0 - x_min) / resolution) and likewise in y for the costmap,
+        (W // 2, H // 2) for the occupancy maps."""
+        if k == 0:
+            return _nav.goal_cells(np.zeros((B, 2)), org, res, shape)
+        return np.tile(np.array([[shape[1] // 2, shape[0] // 2]], np.int32), (B, 1))
+
     def navfn_async(self, goals, source="costmap", starts=None):
         """Queues the field and the paths on the grids of the source's last inflation behind whatever the engine's stream
         holds (pp_navfn_async) and returns at once.  goals float64 [B, 2] (or one (x, y) for every grid), metres in the
@@ -1422,10 +1431,7 @@ class Engine:
         if starts is False:
             s = None
         elif starts is None:
-            if k == 0:
-                s = _nav.goal_cells(np.zeros((B, 2)), org, res, shape)
-            else:
-                s = np.tile(np.array([[shape[1] // 2, shape[0] // 2]], np.int32), (B, 1))
+            s = self._sensor_cells(k, B, org, res, shape)
         else:
             S = np.asarray(starts, np.float64)
             if S.shape not in ((2,), (B, 2)):
@@ -1481,6 +1487,96 @@ class Engine:
         occupancy_update_async.  Only the paths travel to the host."""
         self._plan_async(goals, source, starts)
         return self.navfn_paths(source, metres=True)
+
+    # ---- frontier clusters behind either inflation (pp_set_frontier, pp_frontier_async, pp_get_frontiers; frontier.py states the rule; DESIGN 7.1ad) ----
+    def set_frontier(self, cfg, source="costmap"):
+        """A frontier.FrontierConfig, a dict of its fields or True (the defaults) for the inflated grids of `source`,
+        "costmap" or "occupancy": `frontier_async()` / `explore()` then find the clusters of the frontier cells -- free
+        cells that touch unknown space -- and rank them as goals on the GPU, from the inflated grid where it lies; the
+        inflated grids stay as they are.  None: the source's stage off (the default); its buffers are kept."""
+        k = self._infl_source(source)
+        pc = None if cfg is None or cfg is False else ctypes.byref(_lib.PPFrontierConfig(**_fr.FrontierConfig.from_any(cfg).to_dict()))
+        self._check(self._lib.pp_set_frontier(self._h, k, pc), "pp_set_frontier")
+
+    def frontier_config(self, source="costmap"):
+        """The FrontierConfig in force for `source`, or None while its stage is off."""
+        k = self._infl_source(source)
+        on, pc = ctypes.c_int32(0), _lib.PPFrontierConfig()
+        self._check(self._lib.pp_get_frontier_config(self._h, k, ctypes.byref(on), ctypes.byref(pc)), "pp_get_frontier_config")
+        return _fr.FrontierConfig(**{f.name: getattr(pc, f.name) for f in dataclasses.fields(_fr.FrontierConfig)}) if on.value else None
+
+    def frontier_async(self, source="costmap", refs=None):
+        """Queues the frontier stage on the grids of the source's last inflation behind whatever the engine's stream holds
+        (pp_frontier_async, five launches) and returns at once.  refs integer cells [B, 2] (or one (x, y)): the reference
+        cell the distance D is taken from while use_field is 0; None: the sensor's own cell, as navfn_async(starts=None)
+        defines it.  With use_field the field of the source's last navfn_async is read (its goal should be the robot's own
+        cell).  The call records the batch, the shape, the origins and the resolution inflate_async recorded for those
+        grids: `frontiers` reads that record, not the configurations in force."""
+        k = self._infl_source(source)
+        B, shape, org, res, _ = self._navfn_frame(k, "frontier_async")
+        if refs is None:
+            r = self._sensor_cells(k, B, org, res, shape)
+        else:
+            r = np.asarray(refs)
+            if r.shape == (2,):
+                r = np.broadcast_to(r, (B, 2))
+            if r.shape != (B, 2) or not np.issubdtype(r.dtype, np.integer):
+                raise ValueError(f"frontier_async: refs must be integer cells [{B}, 2] (the inflation run's grids) or one (x, y), got {r.dtype} {r.shape}")
+        r = np.ascontiguousarray(np.clip(r, -(2 ** 31), 2 ** 31 - 1), np.int32)
+        self._check(self._lib.pp_frontier_async(self._h, k, _ptr(r), B), "pp_frontier_async")
+        self._frontier_run[k] = (B, shape, org, res)
+
+    def frontiers(self, source="costmap", metres=False, labels=False):
+        """(frontiers, info) of the source's last frontier_async (waits for it; under use_field the GPU first finishes the
+        field's missing rounds and ranks again on the exact field).  frontiers: a list of B structured arrays, one row per
+        returned frontier in rank order, with the fields x, y (the representative cell), cx, cy (the centroid cell), n,
+        label and cost (D, uint64); metres=True: x, y, cx, cy are float64, the cells' centres in the grids' frame through
+        the origins and the resolution of the run's own record.  info: frontier.INFO -> int32 [B].  labels=True adds the
+        label arrays uint32 [B, H, W] as a third value."""
+        k = self._infl_source(source)
+        if k not in self._frontier_run:
+            raise RuntimeError(f"frontiers: no frontier stage has run on the {_infl.SOURCES[k]} source (frontier_async first)")
+        B, (H, W), org, res = self._frontier_run[k]
+        words = np.zeros((B, _lib.PP_FRONTIER_MAX, 8), np.int32)
+        info = np.zeros((B, _lib.PP_FRONTIER_INFO), np.int32)
+        lab = np.zeros((B, H, W), np.uint32) if labels else None
+        self._check(self._lib.pp_get_frontiers(self._h, k, _ptr(words), _ptr(info), _ptr(lab), B), "pp_get_frontiers")
+        xy = np.float64 if metres else np.int32
+        dt = np.dtype([("x", xy), ("y", xy), ("cx", xy), ("cy", xy), ("n", np.int32), ("label", np.uint32), ("cost", np.uint64)])
+        out = []
+        for b in range(B):
+            w = words[b, :info[b, 5]]
+            f = np.zeros(len(w), dt)
+            rep, cen = w[:, 0:2], w[:, 2:4]
+            if metres:
+                rep, cen = _fr.cells_to_metres(rep, org[b], res), _fr.cells_to_metres(cen, org[b], res)
+            f["x"], f["y"], f["cx"], f["cy"] = rep[:, 0], rep[:, 1], cen[:, 0], cen[:, 1]
+            f["n"], f["label"] = w[:, 4], w[:, 5].view(np.uint32)
+            f["cost"] = np.array(_fr.cost_of(w), np.uint64)
+            out.append(f)
+        d = {name: info[:, i].copy() for i, name in enumerate(_fr.INFO)}
+        return (out, d, lab) if labels else (out, d)
+
+    def explore(self, source="occupancy"):
+        """The ranked exploration goals of every stream: a list of B entries, float64 [k, 2] metres (x, y) in the grids'
+        frame -- the representative cells' centres, best first -- or None for a stream with no frontier.  Queues what
+        `plan` queues in front of the field (the costmap stage if none is pending and the inflation, or the inflation
+        behind the caller's occupancy_update_async), then, when the source's FrontierConfig has use_field set,
+        navfn_async with the sensor's own cells as goals and no starts, then the frontier stage; only the goals travel to
+        the host.  With use_field this USES THE SOURCE'S NAVFN SLOT: the field then holds the cost from the robot, so a
+        `plan(goal)` afterwards replaces that field with the one towards `goal` (and a `frontiers()` after such a plan is
+        refused until the next frontier_async)."""
+        c = self.frontier_config(source)
+        if c is None:
+            raise RuntimeError(f"explore: the frontier stage of the {source} source is not configured (set_frontier first)")
+        k = self._inflated_async(source)
+        B, shape, org, res, poses = self._navfn_frame(k, "explore")
+        if c.use_field:
+            self._navfn_cells_async(k, self._sensor_cells(k, B, org, res, shape), None)
+            self._navfn_run[k] = self._navfn_run[k][:3] + (org, res, poses)
+        self.frontier_async(source)
+        fr, _ = self.frontiers(source, metres=True)
+        return [np.stack([f["x"], f["y"]], axis=1) if len(f) else None for f in fr]
 
     # ---- local planner behind either navigation function (pp_set_local_plan, pp_local_plan_async, pp_get_local_plan; local_planner.py states the rule; DESIGN 7.1aa) ----
     def set_local_planner(self, cfg, source="costmap"):
@@ -1652,8 +1748,8 @@ class Engine:
         self._check(self._lib.pp_get_local_movers(self._h, k, _ptr(M), _ptr(info), B), "pp_get_local_movers")
         return M, {name: info[:, i].copy() for i, name in enumerate(_loc.MOVER_INFO)}
 
-    def _plan_async(self, goals, source, starts):
-        """What `plan` queues: the source's grids, their inflation, the field and the paths."""
+    def _inflated_async(self, source):
+        """What `plan` and `explore` queue first: the costmap stage if no costmap_async is pending, and the source's inflation."""
         k = self._infl_source(source)
         if k == 0:
             if not self._costmap_queued:
@@ -1662,6 +1758,11 @@ class Engine:
             self._costmap_queued = False
         else:
             self.inflate_async("occupancy")
+        return k
+
+    def _plan_async(self, goals, source, starts):
+        """What `plan` queues: the source's grids, their inflation, the field and the paths."""
+        k = self._inflated_async(source)
         self.navfn_async(goals, source, starts)
         return k
 

@@ -101,6 +101,12 @@ class VoxelNet:
         that source first; engine.set_local_movers to avoid the streams' moving tracks too)."""
         return self.engine.drive(goals, velocities, limits, source, poses)
 
+    def explore(self, source="occupancy"):
+        """Engine.explore: the ranked exploration goals in metres per stream (None where a stream has no frontier) over the
+        inflated grids of the pass that has just run, or of the last occupancy_update (engine.set_inflation and
+        engine.set_frontier for that source first, and engine.set_navfn when its FrontierConfig has use_field set)."""
+        return self.engine.explore(source)
+
     def _need_p2(self, p2, who):
         if self.d.project_bbox and p2 is None:
             raise ValueError(f"{who}: model.second.project_bbox is on: pass p2 (the frames' camera matrices)")

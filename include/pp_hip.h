@@ -67,7 +67,10 @@ extern "C" {
  * pp_local_plan_movers_async, pp_get_local_movers, pp_local_plan_grids_movers (declared behind pp_local_plan_grids).  Then
  * PP_SCAN_MAX_CANDIDATES, PP_SCAN_RESULT, pp_scan_status, pp_scan_match_config, pp_set_scan_match,
  * pp_get_scan_match_config, pp_scan_match_async, pp_get_scan_match, pp_scan_match_grids (declared behind
- * pp_local_plan_grids_movers: the stage reads the occupancy maps' log-odds where they lie). */
+ * pp_local_plan_grids_movers: the stage reads the occupancy maps' log-odds where they lie).  Then PP_FRONTIER_MAX,
+ * PP_FRONTIER_INFO, PP_FRONTIER_NONE, pp_frontier_config, pp_set_frontier, pp_get_frontier_config, pp_frontier_async,
+ * pp_get_frontiers, pp_frontier_grids (declared behind pp_scan_match_grids: the stage reads the inflated grid, and under
+ * use_field the navigation function's field, where they lie). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -1653,6 +1656,60 @@ int pp_scan_match_grids(int device, const int16_t* logodds, const uint8_t* known
                         const float* points, const int32_t* offsets, int32_t num_features, const double* poses,
                         const int32_t* origin_cells, const int32_t* has_map, const pp_occupancy_config* occ_cfg,
                         const pp_scan_match_config* cfg, const int32_t* trig, int32_t n_trig, int32_t* words, int32_t* scores);
+
+/* ---- Frontier clusters behind either inflation, and of any int8 OccupancyGrid (frontier.py states the rule): where to
+ * explore next.  FRONTIER CELL: 0 <= g <= free_max and at least one of the four edge neighbours inside the grid is -1.
+ * CLUSTERS: the connected components of the frontier cells under `connectivity`; a cluster's label is the least linear
+ * index y * width + x of its cells (labels uint32 [height][width], PP_FRONTIER_NONE elsewhere).  Per cluster n = cells,
+ * sx = sum of x, sy = sum of y, the centroid cell cx = (2 sx + n) / (2 n) (cy likewise), the REPRESENTATIVE the member
+ * with the least key (((x - cx)^2 + (y - cy)^2) << 20) | (y * width + x).  Clusters with n < min_size are dropped (counted
+ * in `small`).  COST D: use_field 0, the squared cell distance from the grid's reference cell to the representative
+ * (< 2^43); use_field 1, the uint32 potential of a navigation-function field at the representative, and a cluster whose D
+ * is PP_NAVFN_UNREACHED is dropped (counted in `unreached`).  ORDER: ascending (D << 20) | label (rank 0) or
+ * ((2^20 - n) << 20) | label (rank 1); the first max_frontiers are returned, eight int32 words each: x, y, cx, cy, n,
+ * label, D low, D high.  Integers only, a unique answer whatever the schedule.  An opt-in stage: plain launches on the
+ * handle's stream, not part of a captured pass. ---- */
+#define PP_FRONTIER_MAX 64   /* frontiers returned per grid at most */
+#define PP_FRONTIER_INFO 6   /* int32 per grid: frontier_cells, clusters, small, unreached, kept, returned */
+#define PP_FRONTIER_NONE 0xFFFFFFFFu
+
+typedef struct pp_frontier_config {
+    int32_t free_max;       /* 0 .. 99: a known cell with g <= free_max is free */
+    int32_t connectivity;   /* 4 / 8: of the clusters (the frontier test always looks at four neighbours) */
+    int32_t min_size;       /* 1 .. PP_OCC_MAX_CELLS cells */
+    int32_t max_frontiers;  /* 1 .. PP_FRONTIER_MAX */
+    int32_t rank;           /* 0 nearest (least D), 1 largest (most cells) */
+    int32_t use_field;      /* 0: D from the reference cell; 1: D from the source's navigation-function field */
+    int32_t reserved[2];    /* 0 */
+} pp_frontier_config;
+
+/* cfg == NULL: the source's stage off (the default); its buffers are kept.  Otherwise the configuration is validated
+ * (PP_ERR_ARG naming the field).  `source` is the inflation's.  Waits for the stream.  PP_ERR_STATE while a training step
+ * is in flight. */
+int pp_set_frontier(pp_handle h, int32_t source, const pp_frontier_config* cfg);
+/* *on: 0 / 1; cfg_out (may be NULL): the last configuration given for the source (zeros before the first). */
+int pp_get_frontier_config(pp_handle h, int32_t source, int32_t* on, pp_frontier_config* cfg_out);
+/* Queues the five launches on the grids of the source's last pp_inflate_async behind whatever the handle's stream holds:
+ * refs int32 [batch][2], the reference cell (x, y) of every grid, each coordinate within +-2^20 (it need not lie in the
+ * grid; read only while use_field is 0).  Reads the inflated grid in place and never writes it; a stream reset before that
+ * inflation reads all unknown and has no frontier.  With use_field 1 the field of the source's last pp_navfn_async is read
+ * in place, as pp_local_plan_async reads it.  Refused before anything is queued, PP_ERR_STATE: the stage or the source's
+ * inflation is off, that inflation has not run, a training step is in flight, and under use_field no navigation function
+ * has run or its field belongs to grids a later pp_inflate_async replaced; PP_ERR_ARG: a bad source, refs NULL, a batch
+ * that is not the inflation run's, a reference cell out of range. */
+int pp_frontier_async(pp_handle h, int32_t source, const int32_t* refs, int32_t batch);
+/* The results of the source's last pp_frontier_async (waits for it; under use_field it first settles the field as
+ * pp_get_navfn does and ranks again if that took a further round): words int32 [batch][PP_FRONTIER_MAX][8] (zeros behind
+ * a grid's `returned` frontiers), info int32 [batch][PP_FRONTIER_INFO], labels uint32 [batch][height][width]; each may be
+ * NULL.  PP_ERR_STATE when none has run (or, under use_field, a pp_navfn_async or pp_inflate_async came after it and the
+ * ranking would have to run again), PP_ERR_ARG when batch is not that run's, PP_ERR_INTERNAL should a loop bound derived
+ * from the cell count not suffice (they provably do). */
+int pp_get_frontiers(pp_handle h, int32_t source, int32_t* words, int32_t* info, uint32_t* labels, int32_t batch);
+/* Without a handle: grids int8 [batch][height][width] in host memory (height * width <= PP_OCC_MAX_CELLS, batch <= 65535),
+ * pot uint32 of the same shape (required iff cfg->use_field, else it may be NULL), refs as above -> words, info, labels as
+ * pp_get_frontiers gives them (each may be NULL). */
+int pp_frontier_grids(int device, const int8_t* grids, const uint32_t* pot, int32_t batch, int32_t height, int32_t width,
+                      const pp_frontier_config* cfg, const int32_t* refs, int32_t* words, int32_t* info, uint32_t* labels);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
