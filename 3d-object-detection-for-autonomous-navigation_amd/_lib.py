@@ -70,6 +70,7 @@ EXPORTS = [
     "pp_local_plan_grids_movers",
     "pp_set_scan_match", "pp_get_scan_match_config", "pp_scan_match_async", "pp_get_scan_match", "pp_scan_match_grids",
     "pp_set_frontier", "pp_get_frontier_config", "pp_frontier_async", "pp_get_frontiers", "pp_frontier_grids",
+    "pp_set_local_footprint", "pp_get_local_footprint_config", "pp_get_local_footprint", "pp_local_plan_grids_footprint",
     "pp_set_nms_mode", "pp_get_nms_mode", "pp_rotate_nms",
     "pp_set_projection", "pp_get_projection", "pp_get_bboxes", "pp_box3d_to_bbox",
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
@@ -259,6 +260,9 @@ PP_LOCAL_MAX_MOVERS = 64        # movers per grid (pp_local_plan_movers_async: a
 PP_LOCAL_MAX_MOVER_SPEED = 16384    # sub-cells per step: |mvx|, |mvy| at most
 PP_LOCAL_MAX_MOVER_RADIUS = 32767   # sub-cells: r_soft at most
 PP_LOCAL_MOVER_INFO = 4         # int32 words per grid of pp_get_local_movers' info
+PP_LOCAL_MAX_PROBES = 256       # probes of a footprint (pp_set_local_footprint)
+PP_LOCAL_MAX_PROBE = 32767      # sub-cells: |fx|, |fy| of a probe at most
+PP_LOCAL_FOOT_INFO = 4          # int32 words per grid of pp_get_local_footprint's info
 PP_SCAN_MAX_CANDIDATES = 65536  # pp_scan_match_config: (2 nx + 1)(2 ny + 1)(2 nt + 1) at most
 PP_SCAN_RESULT = 8              # int32 words per stream of pp_get_scan_match's result
 PP_SCAN_NO_MAP, PP_SCAN_OUTSIDE, PP_SCAN_FEW_CELLS, PP_SCAN_LOW_SCORE, PP_SCAN_EDGE = 1, 2, 4, 8, 16      # its status bits
@@ -389,6 +393,13 @@ class PPLocalMoverConfig(ctypes.Structure):
         ("mover_weight", ctypes.c_int32),
         ("confirmed_only", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
+    ]
+
+
+class PPLocalFootprintConfig(ctypes.Structure):
+    _fields_ = [
+        ("foot_lethal", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 3),
     ]
 
 
@@ -641,6 +652,12 @@ def lib():
     L.pp_sweeps_accumulate_async.argtypes = [vp, vp, vp, i32]
     L.pp_sweeps_info.argtypes = [vp, vp, vp, vp, vp, i32]
     L.pp_sweeps_reset.argtypes = [vp, i32]
+    L.pp_set_local_footprint.argtypes = [vp, i32, ctypes.POINTER(PPLocalFootprintConfig), vp, i32]
+    L.pp_get_local_footprint_config.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(PPLocalFootprintConfig), vp, ctypes.POINTER(i32)]
+    L.pp_get_local_footprint.argtypes = [vp, i32, vp, i32]
+    L.pp_local_plan_grids_footprint.argtypes = [ctypes.c_int, vp, vp, i32, i32, i32, ctypes.POINTER(PPNavfnConfig),
+                                                ctypes.POINTER(PPLocalPlanConfig), vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32,
+                                                vp, vp, vp, vp, vp, vp]
     L.pp_set_nms_mode.argtypes = [vp, i32]
     L.pp_get_nms_mode.argtypes = [vp, ctypes.POINTER(i32)]
     L.pp_rotate_nms.argtypes = [ctypes.c_int, f32p, i64, ctypes.c_float, i32, i32, vp, ctypes.POINTER(i64)]

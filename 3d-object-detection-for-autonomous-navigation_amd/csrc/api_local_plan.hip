@@ -14,6 +14,11 @@
 // step seconds) ride the stage's call ring next to the poses and windows.  The rollout and the finish then run in their
 // instantiations with movers.  The getter's re-queue runs those two again on the table that call built: the tracks may
 // have moved on since, the table has not.
+// FOOTPRINT.  pp_set_local_footprint (and pp_get_local_footprint_config, pp_get_local_footprint,
+// pp_local_plan_grids_footprint) gives the source a table of probes, checked and packed here into a word of two int16
+// halves per probe; while it is on, both async calls launch the rollout and the finish in their instantiations with a
+// footprint, in front of which the chunks' slots of `partial` are set to all ones (the rollout lowers them) and n_footprint
+// is cleared.  No third async entry: the footprint is a property of the robot, not of a call.
 #include "pp_engine.h"
 
 static_assert(sizeof(pp_local_plan_config) == 32, "pp_local_plan_config: 8 int32 (the Python binding mirrors it)");
@@ -22,6 +27,9 @@ static_assert(sizeof(pp_local_mover_config) == 32, "pp_local_mover_config: 2 dou
 static_assert(sizeof(LocalFrame) == 32, "LocalFrame: 4 doubles, as pp_local_plan_movers_async's frame rows");
 static_assert(PP_LOCAL_MAX_MOVERS == PP_TRACK_MAX && PP_TRACK_MAX == PP_WAVE, "k_local_movers: one lane per track slot, a mover per slot at most");
 static_assert(PP_LOCAL_MOVER_INFO == 4 && LOC_M_NEAR == 3, "a grid's info words are the mover_info fields");
+static_assert(sizeof(pp_local_footprint_config) == 16, "pp_local_footprint_config: 4 int32 (the Python binding mirrors it)");
+static_assert(PP_LOCAL_FOOT_INFO == 4 && LOC_F_RESERVED == 3, "a grid's footprint words are the foot_info fields");
+static_assert(PP_LOCAL_MAX_PROBE == 32767, "a probe's coordinates are int16 halves of one word");
 static_assert(PP_LOCAL_SUB == 1024 && PP_LOCAL_HEADINGS == 4096, "sub-cells per cell, ticks per revolution");
 static_assert(PP_LOCAL_RESULT == LOC_STATE, "a grid's result words are its state fields");
 static_assert(PP_INFLATE_COSTMAP == 0 && PP_INFLATE_OCCUPANCY == 1, "pp_engine::local is indexed by source, as navfn");
@@ -105,10 +113,30 @@ int check_movers(const char* who, const int32_t* movers, const int32_t* n_movers
     return PP_OK;
 }
 
+// what pp_set_local_footprint and pp_local_plan_grids_footprint refuse of a footprint, naming the field or the probe; the
+// table packed into `out` (fx in the low half, fy in the high half of a word)
+int check_footprint(pp_engine* e, const char* who, int foot_lethal, const int32_t* probes, int n, std::vector<unsigned>& out) {
+    if (foot_lethal < 1 || foot_lethal > 100) return fail(e, PP_ERR_ARG, "%s: foot_lethal = %d outside [1, 100]", who, foot_lethal);
+    if (n < 1 || n > PP_LOCAL_MAX_PROBES) return fail(e, PP_ERR_ARG, "%s: n_probes = %d outside [1, PP_LOCAL_MAX_PROBES = %d]", who, n, PP_LOCAL_MAX_PROBES);
+    if (!probes) return fail(e, PP_ERR_ARG, "%s: probes is NULL", who);
+    out.resize((size_t)n);
+    for (int q = 0; q < n; ++q) {
+        const int32_t fx = probes[2 * q], fy = probes[2 * q + 1];
+        if (fx < -PP_LOCAL_MAX_PROBE || fx > PP_LOCAL_MAX_PROBE || fy < -PP_LOCAL_MAX_PROBE || fy > PP_LOCAL_MAX_PROBE)
+            return fail(e, PP_ERR_ARG, "%s: probe %d: (%d, %d) outside [-%d, %d]", who, q, fx, fy, PP_LOCAL_MAX_PROBE, PP_LOCAL_MAX_PROBE);
+        out[(size_t)q] = ((unsigned)fx & 0xFFFFu) | ((unsigned)fy << 16);
+    }
+    return PP_OK;
+}
+
 // the reason counts cleared, rollout, finish behind whatever `s` holds
 int queue_run(pp_engine* e, const LocalParams& p, hipStream_t s) {
     HIPCHK(e, hipMemsetAsync(p.state + (size_t)LOC_N_OK * p.state_stride, 0, (size_t)4 * p.state_stride * sizeof(int), s));
     if (p.movers) HIPCHK(e, hipMemsetAsync(p.mover_info + (size_t)LOC_M_DYNAMIC * p.state_stride, 0, (size_t)p.state_stride * sizeof(int), s));
+    if (p.probes) {                                      // n_footprint cleared; the chunks' least keys all ones: the rollout lowers them
+        HIPCHK(e, hipMemsetAsync(p.foot_info + (size_t)LOC_F_FOOTPRINT * p.state_stride, 0, (size_t)p.state_stride * sizeof(int), s));
+        HIPCHK(e, hipMemsetAsync(p.partial, 0xFF, (size_t)p.batch * LOC_MAX_CHUNKS * sizeof(unsigned long long), s));
+    }
     launch_local_rollout(p, s);
     launch_local_finish(p, s);
     HIPCHK(e, hipGetLastError());
@@ -210,6 +238,46 @@ int pp_get_local_movers_config(pp_handle e, int32_t source, int32_t* on, pp_loca
     return PP_OK;
 }
 
+int pp_set_local_footprint(pp_handle e, int32_t source, const pp_local_footprint_config* cfg, const int32_t* probes, int32_t n) {
+    if (!e) return PP_ERR_ARG;
+    const char* who = "pp_set_local_footprint";
+    if (int st = check_source(e, who, source)) return st;
+    if (e->train_pending) return fail(e, PP_ERR_STATE, "%s: a training step is in flight", who);
+    pp_engine::LocalPlan& g = e->local[source];
+    if (n == 0 && !probes) { g.foot_on = false; return PP_OK; }
+    if (!cfg) return fail(e, PP_ERR_ARG, "%s: cfg is NULL (n = 0 with probes NULL turns the footprint off)", who);
+    const pp_local_footprint_config c = *cfg;
+    for (int i = 0; i < 3; ++i)
+        if (c.reserved[i] != 0) return fail(e, PP_ERR_ARG, "%s: reserved[%d] = %d must be 0", who, i, c.reserved[i]);
+    std::vector<unsigned> packed;
+    if (int st = check_footprint(e, who, c.foot_lethal, probes, n, packed)) return st;
+    (void)hipSetDevice(e->device);
+    HIPCHK(e, hipStreamSynchronize(e->stream));          // a run in flight reads the table to its end
+    if (!g.foot_info) {
+        DevAlloc A{e};
+        A(&g.d_probes, (size_t)PP_LOCAL_MAX_PROBES); A(&g.foot_info, (size_t)PP_LOCAL_FOOT_INFO * e->B);      // (foot_info last: the ready flag)
+        if (A.st) return A.st;
+    }
+    HIPCHK(e, hipMemcpy(g.d_probes, packed.data(), packed.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+    if (g.run.probes) g.batch = 0;                       // a getter could queue the last run again, on a table that is gone
+    g.probes.assign(probes, probes + (size_t)2 * n);
+    g.fcfg = c;
+    g.foot_on = true;
+    return PP_OK;
+}
+
+int pp_get_local_footprint_config(pp_handle e, int32_t source, int32_t* on, pp_local_footprint_config* cfg_out, int32_t* probes_out,
+                                  int32_t* n_out) {
+    if (!e || !on) return PP_ERR_ARG;
+    if (int st = check_source(e, "pp_get_local_footprint_config", source)) return st;
+    const pp_engine::LocalPlan& g = e->local[source];
+    *on = g.foot_on ? 1 : 0;
+    if (cfg_out) *cfg_out = g.fcfg;
+    if (probes_out && !g.probes.empty()) memcpy(probes_out, g.probes.data(), g.probes.size() * sizeof(int32_t));
+    if (n_out) *n_out = (int32_t)(g.probes.size() / 2);
+    return PP_OK;
+}
+
 // pp_local_plan_async (frame == NULL) and pp_local_plan_movers_async
 static int plan_async(pp_engine* e, const char* who, int32_t source, const int32_t* poses, const int32_t* windows,
                       const double* frame, bool with_movers, int32_t batch) {
@@ -271,6 +339,9 @@ static int plan_async(pp_engine* e, const char* who, int32_t source, const int32
         memcpy(g.h_frame.at(slot), frame, (size_t)batch * sizeof(LocalFrame));
         HIPCHK(e, g.h_frame.send(slot, g.d_frame, (size_t)batch, e->stream));
         p.movers = g.movers; p.mover_info = g.mover_info; p.horizon = g.mcfg.horizon; p.mover_w = g.mcfg.mover_weight;
+    }
+    if (g.foot_on) {
+        p.probes = g.d_probes; p.n_probes = (int)(g.probes.size() / 2); p.foot_lethal = g.fcfg.foot_lethal; p.foot_info = g.foot_info;
     }
     HIPCHK(e, g.ring.sent(slot, e->stream));
     {
@@ -364,12 +435,33 @@ int pp_get_local_movers(pp_handle e, int32_t source, int32_t* movers, int32_t* i
     return PP_OK;
 }
 
-// pp_local_plan_grids (movers == NULL) and pp_local_plan_grids_movers
+int pp_get_local_footprint(pp_handle e, int32_t source, int32_t* info, int32_t batch) {
+    if (!e) return PP_ERR_ARG;
+    const char* who = "pp_get_local_footprint";
+    if (int st = check_source(e, who, source)) return st;
+    const pp_engine::LocalPlan& g = e->local[source];
+    if (g.batch >= 1 && !g.run.probes)
+        return fail(e, PP_ERR_STATE, "%s: the last run of the %s source had no footprint (pp_set_local_footprint, then pp_local_plan_async)",
+                    who, source_name(source));
+    if (int st = settle_local(e, who, source, false, batch)) return st;
+    const LocalParams& p = g.run;
+    const size_t ss = (size_t)p.state_stride;
+    if (info) {
+        std::vector<int> host((size_t)PP_LOCAL_FOOT_INFO * ss);
+        HIPCHK(e, hipMemcpy(host.data(), p.foot_info, host.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int b = 0; b < batch; ++b)
+            for (int k = 0; k < PP_LOCAL_FOOT_INFO; ++k) info[(size_t)b * PP_LOCAL_FOOT_INFO + k] = host[(size_t)k * ss + b];
+    }
+    return PP_OK;
+}
+
+// pp_local_plan_grids (movers == NULL, probes == NULL), pp_local_plan_grids_movers and pp_local_plan_grids_footprint
 static int plan_grids(const char* who, int device, const int8_t* grids, const uint32_t* pots, int32_t batch, int32_t height, int32_t width,
                       const pp_navfn_config* navfn_cfg, const pp_local_plan_config* cfg, const int32_t* trig, int32_t n_trig,
                       const int32_t* poses, const int32_t* windows, const int32_t* goal_state, bool with_movers, int32_t horizon,
                       int32_t mover_weight, const int32_t* movers, const int32_t* n_movers, int32_t* result, uint64_t* score,
-                      int32_t* traj, uint64_t* keys, int32_t* info) {
+                      int32_t* traj, uint64_t* keys, int32_t* info, bool with_foot = false, const int32_t* probes = nullptr,
+                      int32_t n_probes = 0, int32_t foot_lethal = 0, int32_t* foot_info = nullptr) {
     if (!grids || !pots || !navfn_cfg || !cfg) return fail(nullptr, PP_ERR_ARG, "%s: grids, pots, navfn_cfg or cfg is NULL", who);
     if (!poses || !windows) return fail(nullptr, PP_ERR_ARG, "%s: poses or windows is NULL", who);
     if (batch < 1 || batch > 65535) return fail(nullptr, PP_ERR_ARG, "%s: batch = %d outside [1, 65535]", who, batch);
@@ -391,6 +483,9 @@ static int plan_grids(const char* who, int device, const int8_t* grids, const ui
         minfo.assign((size_t)PP_LOCAL_MOVER_INFO * batch, 0);
         for (int b = 0; b < batch; ++b) minfo[(size_t)LOC_M_COUNT * batch + b] = n_movers[b];
     }
+    std::vector<unsigned> probe_words;
+    if (with_foot)
+        if (int st = check_footprint(nullptr, who, foot_lethal, probes, n_probes, probe_words)) return st;
     if (int st = check_device(who, device)) return st;
     DEVCHK(hipSetDevice(device));
     const size_t cells = (size_t)width * height, n = (size_t)batch * cells;
@@ -426,8 +521,21 @@ static int plan_grids(const char* who, int device, const int8_t* grids, const ui
         DEVCHK(hipMemcpy(d_minfo.p, minfo.data(), minfo.size() * sizeof(int), hipMemcpyHostToDevice));
         p.movers = (const int*)d_movers.p; p.mover_info = (int*)d_minfo.p; p.horizon = horizon; p.mover_w = mover_weight;
     }
+    DevBuf d_probes, d_finfo;
+    if (with_foot) {
+        DEVCHK(d_probes.alloc(probe_words.size() * sizeof(unsigned)));
+        DEVCHK(d_finfo.alloc((size_t)PP_LOCAL_FOOT_INFO * batch * sizeof(int)));
+        DEVCHK(hipMemcpy(d_probes.p, probe_words.data(), probe_words.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+        p.probes = (const unsigned*)d_probes.p; p.n_probes = n_probes; p.foot_lethal = foot_lethal; p.foot_info = (int*)d_finfo.p;
+    }
     if (int st = queue_run(nullptr, p, nullptr)) return st;
     DEVCHK(hipStreamSynchronize(nullptr));
+    if (with_foot && foot_info) {
+        std::vector<int> host((size_t)PP_LOCAL_FOOT_INFO * batch);
+        DEVCHK(hipMemcpy(host.data(), p.foot_info, host.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int b = 0; b < batch; ++b)
+            for (int k = 0; k < PP_LOCAL_FOOT_INFO; ++k) foot_info[(size_t)b * PP_LOCAL_FOOT_INFO + k] = host[(size_t)k * batch + b];
+    }
     if (with_movers && info) {
         DEVCHK(hipMemcpy(minfo.data(), p.mover_info, minfo.size() * sizeof(int), hipMemcpyDeviceToHost));
         for (int b = 0; b < batch; ++b)
@@ -461,6 +569,18 @@ int pp_local_plan_grids_movers(int device, const int8_t* grids, const uint32_t* 
                                int32_t* info) {
     return plan_grids("pp_local_plan_grids_movers", device, grids, pots, batch, height, width, navfn_cfg, cfg, trig, n_trig, poses,
                       windows, goal_state, true, horizon, mover_weight, movers, n_movers, result, score, traj, keys, info);
+}
+
+int pp_local_plan_grids_footprint(int device, const int8_t* grids, const uint32_t* pots, int32_t batch, int32_t height,
+                                  int32_t width, const pp_navfn_config* navfn_cfg, const pp_local_plan_config* cfg,
+                                  const int32_t* trig, int32_t n_trig, const int32_t* poses, const int32_t* windows,
+                                  const int32_t* goal_state, int32_t horizon, int32_t mover_weight, const int32_t* movers,
+                                  const int32_t* n_movers, const int32_t* probes, int32_t n_probes, int32_t foot_lethal,
+                                  int32_t* result, uint64_t* score, int32_t* traj, uint64_t* keys, int32_t* info,
+                                  int32_t* foot_info) {
+    return plan_grids("pp_local_plan_grids_footprint", device, grids, pots, batch, height, width, navfn_cfg, cfg, trig, n_trig, poses,
+                      windows, goal_state, movers != nullptr, horizon, mover_weight, movers, n_movers, result, score, traj, keys, info,
+                      true, probes, n_probes, foot_lethal, foot_info);
 }
 
 }  // extern "C"

@@ -27,6 +27,21 @@
 // mover per lane.  The
 // table itself comes from the host (pp_local_plan_grids_movers) or from the track slots (k_local_movers, local_movers.hip:
 // the one place of the stage that is not integer arithmetic, and so a file of its own).
+//
+// FOOTPRINT (pp_set_local_footprint, pp_local_plan_grids_footprint): the bodies of rollout and finish carry a second flag,
+// <bool MOVERS, bool FOOT>, four instantiations; the two without a footprint are the code above, unchanged, under their
+// old launch names.  With one, the workgroup also stages the probe table in LDS (256 words of two int16 halves: 1 KiB) and
+// a sample is rolled by a GROUP of LOC_FOOT_GROUP neighbouring lanes of one wave instead of one lane: X, Y, h, occ and
+// near are replicated in the group (every lane of it takes the same step and reads the same centre cell), and behind the
+// centre's static test lane j of the group walks the probes q = j, j + G, ... under the heading after the step's turn,
+// stopping at its first probe that is not free.  The group's verdict is the minimum of (q << 1) | blocked over its lanes
+// by lane shuffles (all ones: every probe free), taken by every lane of the wave at once, so the FIRST failing probe of
+// the table decides OUTSIDE against FOOTPRINT as the rule's table order does.  A workgroup rolls LOC_BLOCK / G samples;
+// the workgroups of one chunk of LOC_BLOCK samples lower the chunk's slot of `partial` (all ones before the launch) with
+// one 64-bit integer atomic min each -- keys are unique, so the order does not matter -- and finish reads the slots as
+// before.  The group's first lane alone stores the key and counts.  State 5 and start_probe come from loc_foot_start in
+// both kernels: a lane takes a probe, a ballot, the lowest set bit, 64 probes a trip; each wave of the rollout runs it on
+// its own and gets the same answer.  The winner's re-roll in finish tests no probe: the winner passed them all.
 #include "pp_common.h"
 
 namespace {
@@ -35,6 +50,8 @@ constexpr unsigned LOC_U = PP_NAVFN_UNREACHED;
 constexpr unsigned long long LOC_INVALID = ~0ull;
 constexpr int LOC_SHIFT = 10, LOC_HMASK = PP_LOCAL_HEADINGS - 1;
 constexpr int LOC_R_OK = 0, LOC_R_OUTSIDE = 1, LOC_R_COLLISION = 2, LOC_R_UNREACHED = 3, LOC_R_DYNAMIC = 4;     // why a sample ended
+constexpr int LOC_R_FOOTPRINT = 5;                       // ... on a blocked probe of the footprint
+constexpr int LOC_FOOT_FREE = 0x7FFFFFFF;                // a verdict: no probe failed (above every (q << 1) | blocked)
 constexpr int LOC_MOVER_POS = 1 << 29;                   // |mx|, |my| at most
 static_assert((1 << LOC_SHIFT) == PP_LOCAL_SUB && (PP_LOCAL_HEADINGS & LOC_HMASK) == 0, "cells and ticks by shift and mask");
 static_assert(PP_LOCAL_MAX_SAMPLES == (1 << 14), "a key's low 14 bits are the sample index");
@@ -57,6 +74,15 @@ static_assert(LOC_MAX_DX < (1ll << 31) && 2 * (LOC_MAX_DX * LOC_MAX_DX) < (1ull 
 static_assert((long long)PP_LOCAL_MAX_MOVER_RADIUS * PP_LOCAL_MAX_MOVER_RADIUS < (1ll << 31), "r * r fits int32");
 static_assert(PP_LOCAL_MAX_MOVERS == 64 && PP_WAVE == 64, "the cull: one lane per mover");
 static_assert(PP_LOCAL_MAX_STEPS * 1024 + PP_LOCAL_MAX_MOVER_RADIUS < (1 << 30), "the cull's bound fits int32");
+// a probe: |fx|, |fy| <= 32767 are int16 halves of one word; its rotation fx * C - fy * S (and fx * S + fy * C) with |C|,
+// |S| <= 16384 fits int32, and so does X + rx: a pose whose probes are looked at lies in the grid
+static_assert(PP_LOCAL_MAX_PROBE == 32767 && PP_LOCAL_MAX_PROBES == 256, "a probe is two int16; 256 of them are 1 KiB of LDS");
+static_assert(32767ll * 16384 * 2 + 8192 < (1ll << 31), "a probe's rotation fits int32");
+static_assert(((long long)PP_OCC_MAX_CELLS + 1) * PP_LOCAL_SUB + 2ll * PP_LOCAL_MAX_PROBE + 1 < (1ll << 31), "X + rx and Y + ry fit int32");
+static_assert(((PP_LOCAL_MAX_PROBES - 1) << 1 | 1) < LOC_FOOT_FREE, "every failing verdict lies below the free one");
+static_assert(LOC_FOOT_GROUP >= 1 && LOC_FOOT_GROUP <= PP_WAVE && (LOC_FOOT_GROUP & (LOC_FOOT_GROUP - 1)) == 0 && LOC_BLOCK % LOC_FOOT_GROUP == 0,
+              "a group is a power of two of neighbouring lanes of one wave, and the groups of a workgroup lie in one chunk");
+static_assert(PP_LOCAL_FOOT_INFO == 4 && LOC_F_RESERVED == 3, "a grid's footprint words are the foot_info fields");
 
 __device__ __forceinline__ int loc_round(int a) { return (a + 8192) >> 14; }         // (arithmetic shift: floor)
 __device__ __forceinline__ int loc_cos(unsigned t) { return (int)(short)(t & 0xFFFFu); }
@@ -119,26 +145,60 @@ __device__ __forceinline__ bool loc_movers_hit(const int* mv, int n, int X, int 
     return false;
 }
 
-template <bool MOVERS>
-__global__ __launch_bounds__(LOC_BLOCK) void k_local_rollout(LocalParams p) {
+// What the rule reads of the cell of probe word w at the pose (X, Y) under the heading whose table word is t: -1 free, 0
+// outside the grid, 1 blocked -- so (q << 1) | answer is probe q's verdict where it is not free.
+__device__ __forceinline__ int loc_probe(const LocalParams& p, const int8_t* grid, bool known, unsigned w, unsigned t, int X, int Y) {
+    const int fx = (int)(short)(w & 0xFFFFu), fy = (int)w >> 16, C = loc_cos(t), S = loc_sin(t);
+    const int cx = (X + loc_round(fx * C - fy * S)) >> LOC_SHIFT, cy = (Y + loc_round(fx * S + fy * C)) >> LOC_SHIFT;
+    if (cx < 0 || cx >= p.width || cy < 0 || cy >= p.height) return 0;
+    const int g = known ? (int)grid[(size_t)cy * p.pitch + cx] : -1;
+    return (g >= p.foot_lethal || (g < 0 && !p.allow_unknown)) ? 1 : -1;
+}
+
+// The first probe that is not free at the start pose (which lies in the grid: the stream's state is 0), -1 if none: a
+// lane takes a probe, 64 a trip.  The whole wave is here, and every lane returns the same answer.
+__device__ __forceinline__ int loc_foot_start(const LocalParams& p, const LocalCall& c, const int8_t* grid, bool known, int lane) {
+    const unsigned t = p.trig[c.h & LOC_HMASK];
+    for (int q0 = 0; q0 < p.n_probes; q0 += 64) {
+        const int q = q0 + lane;
+        const bool bad = q < p.n_probes && loc_probe(p, grid, known, p.probes[q], t, c.X, c.Y) >= 0;
+        const unsigned long long m = __ballot(bad);
+        if (m) return q0 + __ffsll((long long)m) - 1;
+    }
+    return -1;
+}
+
+template <bool MOVERS, bool FOOT>
+__device__ __forceinline__ void loc_rollout(const LocalParams& p) {
+    constexpr int G = FOOT ? LOC_FOOT_GROUP : 1, PER = LOC_BLOCK / G;       // lanes of a sample, samples of a workgroup
     __shared__ unsigned s_trig[PP_LOCAL_HEADINGS];
     __shared__ unsigned long long s_min[LOC_BLOCK / 64];
     __shared__ int s_mov[MOVERS ? PP_LOCAL_MAX_MOVERS * 6 : 1];
     __shared__ int s_nmov;
+    __shared__ unsigned s_probe[FOOT ? PP_LOCAL_MAX_PROBES : 1];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int sub = tid & (G - 1);                       // the lane's place in its sample's group (0: it stores and counts)
     const LocalCall c = p.call[b];
     const int8_t* grid = p.grid + (size_t)b * p.stride;
     const unsigned* pot = p.pot + (size_t)b * p.stride;
     const bool known = !p.nav_call || (p.nav_call[b].flags & NAV_KNOWN) != 0;
-    const int n = p.nv * p.nw, s = (int)blockIdx.x * LOC_BLOCK + tid;
-    const bool live = s < n;
-    unsigned long long* partial = p.partial + (size_t)b * LOC_MAX_CHUNKS + blockIdx.x;
-    if (loc_stream_state(p, b, c, grid, pot, known) >= 2) {      // no sample is rolled (the whole workgroup returns)
+    const int n = p.nv * p.nw, s = (int)blockIdx.x * PER + tid / G;
+    const bool live = s < n, lead = live && sub == 0;
+    unsigned long long* partial = p.partial + (size_t)b * LOC_MAX_CHUNKS + blockIdx.x / G;
+    if constexpr (FOOT) {                                // states 4, 3, 2, then 5: no sample is rolled (the whole workgroup returns)
+        const int state = loc_stream_state(p, b, c, grid, pot, known);
+        if (state >= 2 || loc_foot_start(p, c, grid, known, lane) >= 0) {
+            if (p.keys && lead) p.keys[(size_t)b * n + s] = LOC_INVALID;
+            return;                                      // (the chunk's slot of `partial` holds all ones already)
+        }
+    } else if (loc_stream_state(p, b, c, grid, pot, known) >= 2) {      // no sample is rolled (the whole workgroup returns)
         if (p.keys && live) p.keys[(size_t)b * n + s] = LOC_INVALID;
         if (tid == 0) *partial = LOC_INVALID;
         return;
     }
     for (int i = tid; i < PP_LOCAL_HEADINGS; i += LOC_BLOCK) s_trig[i] = p.trig[i];
+    if (FOOT)
+        for (int i = tid; i < p.n_probes; i += LOC_BLOCK) s_probe[i] = p.probes[i];
     if (MOVERS && wave == 0) {                           // the cull: lane = mover (the whole first wave is here)
         const int nm = min(max(p.mover_info[LOC_M_COUNT * p.state_stride + b], 0), PP_LOCAL_MAX_MOVERS);
         const int* e = p.movers + ((size_t)b * PP_LOCAL_MAX_MOVERS + lane) * 6;
@@ -174,6 +234,7 @@ __global__ __launch_bounds__(LOC_BLOCK) void k_local_rollout(LocalParams p) {
     int reason = LOC_R_OK;
     bool alive = live;                                   // an ended lane loads nothing more and stays in the wave
     for (int k = 0; k < p.steps; ++k) {
+        int bad = LOC_FOOT_FREE;                         // with a footprint: this lane's first probe that is not free
         if (alive) {
             const unsigned t = s_trig[h];
             X += loc_round(sv * loc_cos(t));
@@ -183,10 +244,26 @@ __global__ __launch_bounds__(LOC_BLOCK) void k_local_rollout(LocalParams p) {
             if (g < 0) { reason = g == -2 ? LOC_R_OUTSIDE : LOC_R_COLLISION; alive = false; }
             else {
                 occ = max(occ, g);
-                if (MOVERS && k < p.horizon && loc_movers_hit(s_mov, nmov, X, Y, k + 1, p.horizon, &near)) {
+                if (!FOOT && MOVERS && k < p.horizon && loc_movers_hit(s_mov, nmov, X, Y, k + 1, p.horizon, &near)) {
                     reason = LOC_R_DYNAMIC;
                     alive = false;
                 }
+                if (FOOT) {                              // the lane's share of the probes, under the heading after the turn
+                    const unsigned th = s_trig[h];
+                    for (int q = sub; q < p.n_probes && bad == LOC_FOOT_FREE; q += G) {
+                        const int r = loc_probe(p, grid, known, s_probe[q], th, X, Y);
+                        if (r >= 0) bad = (q << 1) | r;
+                    }
+                }
+            }
+        }
+        if (FOOT) {                                      // the group's verdict: every lane of the wave is here
+#pragma unroll
+            for (int m = G / 2; m >= 1; m >>= 1) bad = min(bad, __shfl_xor(bad, m));
+            if (bad != LOC_FOOT_FREE) { reason = (bad & 1) ? LOC_R_FOOTPRINT : LOC_R_OUTSIDE; alive = false; }
+            else if (MOVERS && alive && k < p.horizon && loc_movers_hit(s_mov, nmov, X, Y, k + 1, p.horizon, &near)) {
+                reason = LOC_R_DYNAMIC;
+                alive = false;
             }
         }
         if (!__any(alive)) break;                        // (the same answer in every lane of the wave)
@@ -206,17 +283,21 @@ __global__ __launch_bounds__(LOC_BLOCK) void k_local_rollout(LocalParams p) {
             key = (score << 14) | (unsigned)s;
         }
     }
-    if (p.keys && live) p.keys[(size_t)b * n + s] = key;
+    if (p.keys && lead) p.keys[(size_t)b * n + s] = key;
 
     int* st = p.state + b;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int cnt = __popcll(__ballot(live && reason == r));
+        const int cnt = __popcll(__ballot(lead && reason == r));
         if (lane == 0 && cnt) atomicAdd(st + (LOC_N_OK + r) * p.state_stride, cnt);
     }
     if (MOVERS) {
-        const int cnt = __popcll(__ballot(live && reason == LOC_R_DYNAMIC));
+        const int cnt = __popcll(__ballot(lead && reason == LOC_R_DYNAMIC));
         if (lane == 0 && cnt) atomicAdd(p.mover_info + LOC_M_DYNAMIC * p.state_stride + b, cnt);
+    }
+    if (FOOT) {
+        const int cnt = __popcll(__ballot(lead && reason == LOC_R_FOOTPRINT));
+        if (lane == 0 && cnt) atomicAdd(p.foot_info + LOC_F_FOOTPRINT * p.state_stride + b, cnt);
     }
     key = loc_wave_min(key);
     if (lane == 0) s_min[wave] = key;
@@ -224,12 +305,18 @@ __global__ __launch_bounds__(LOC_BLOCK) void k_local_rollout(LocalParams p) {
     if (tid == 0) {
 #pragma unroll
         for (int w = 1; w < LOC_BLOCK / 64; ++w) key = s_min[w] < key ? s_min[w] : key;
-        *partial = key;
+        if (FOOT) atomicMin(partial, key);               // (one of the chunk's G workgroups)
+        else *partial = key;
     }
 }
 
 template <bool MOVERS>
-__global__ __launch_bounds__(64) void k_local_finish(LocalParams p) {
+__global__ __launch_bounds__(LOC_BLOCK) void k_local_rollout(LocalParams p) { loc_rollout<MOVERS, false>(p); }
+template <bool MOVERS>
+__global__ __launch_bounds__(LOC_BLOCK) void k_local_rollout_foot(LocalParams p) { loc_rollout<MOVERS, true>(p); }
+
+template <bool MOVERS, bool FOOT>
+__device__ __forceinline__ void loc_finish(const LocalParams& p) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const LocalCall c = p.call[b];
     const int8_t* grid = p.grid + (size_t)b * p.stride;
@@ -237,6 +324,15 @@ __global__ __launch_bounds__(64) void k_local_finish(LocalParams p) {
     const bool known = !p.nav_call || (p.nav_call[b].flags & NAV_KNOWN) != 0;
     const int n = p.nv * p.nw, chunks = (n + LOC_BLOCK - 1) / LOC_BLOCK, ss = p.state_stride;
     int state = loc_stream_state(p, b, c, grid, pot, known);
+    if (FOOT) {                                          // state 5 and start_probe, as the rollout's workgroups found them
+        const int start = state == 0 ? loc_foot_start(p, c, grid, known, lane) : -1;
+        if (start >= 0) state = 5;
+        if (lane == 0) {
+            p.foot_info[LOC_F_COUNT * ss + b] = p.n_probes;
+            p.foot_info[LOC_F_START * ss + b] = start;
+            p.foot_info[LOC_F_RESERVED * ss + b] = 0;
+        }
+    }
     unsigned long long key = state == 0 && lane < chunks ? p.partial[(size_t)b * LOC_MAX_CHUNKS + lane] : LOC_INVALID;
     key = loc_wave_min(key);
     if (state == 0 && key == LOC_INVALID) state = 1;
@@ -291,17 +387,29 @@ __global__ __launch_bounds__(64) void k_local_finish(LocalParams p) {
     }
 }
 
+template <bool MOVERS>
+__global__ __launch_bounds__(64) void k_local_finish(LocalParams p) { loc_finish<MOVERS, false>(p); }
+template <bool MOVERS>
+__global__ __launch_bounds__(64) void k_local_finish_foot(LocalParams p) { loc_finish<MOVERS, true>(p); }
+
 }  // namespace
 
 void launch_local_rollout(const LocalParams& p, hipStream_t s) {
     if (p.batch <= 0) return;
     const int chunks = (p.nv * p.nw + LOC_BLOCK - 1) / LOC_BLOCK;
-    if (p.movers) PP_LAUNCH("k_local_rollout_movers", k_local_rollout<true>, dim3(chunks, p.batch), dim3(LOC_BLOCK), 0, s, p);
+    if (p.probes) {                                      // a workgroup rolls LOC_BLOCK / LOC_FOOT_GROUP samples
+        const int groups = (p.nv * p.nw + LOC_BLOCK / LOC_FOOT_GROUP - 1) / (LOC_BLOCK / LOC_FOOT_GROUP);
+        if (p.movers) PP_LAUNCH("k_local_rollout_movers_foot", k_local_rollout_foot<true>, dim3(groups, p.batch), dim3(LOC_BLOCK), 0, s, p);
+        else PP_LAUNCH("k_local_rollout_foot", k_local_rollout_foot<false>, dim3(groups, p.batch), dim3(LOC_BLOCK), 0, s, p);
+    } else if (p.movers) PP_LAUNCH("k_local_rollout_movers", k_local_rollout<true>, dim3(chunks, p.batch), dim3(LOC_BLOCK), 0, s, p);
     else PP_LAUNCH("k_local_rollout", k_local_rollout<false>, dim3(chunks, p.batch), dim3(LOC_BLOCK), 0, s, p);
 }
 
 void launch_local_finish(const LocalParams& p, hipStream_t s) {
     if (p.batch <= 0) return;
-    if (p.movers) PP_LAUNCH("k_local_finish_movers", k_local_finish<true>, dim3(p.batch), dim3(64), 0, s, p);
+    if (p.probes) {
+        if (p.movers) PP_LAUNCH("k_local_finish_movers_foot", k_local_finish_foot<true>, dim3(p.batch), dim3(64), 0, s, p);
+        else PP_LAUNCH("k_local_finish_foot", k_local_finish_foot<false>, dim3(p.batch), dim3(64), 0, s, p);
+    } else if (p.movers) PP_LAUNCH("k_local_finish_movers", k_local_finish<true>, dim3(p.batch), dim3(64), 0, s, p);
     else PP_LAUNCH("k_local_finish", k_local_finish<false>, dim3(p.batch), dim3(64), 0, s, p);
 }

@@ -822,7 +822,8 @@ struct LocalParams {
     int nav_state_stride;
     const LocalCall* call;         // [batch]
     const unsigned* trig;          // [PP_LOCAL_HEADINGS]: C[h] as int16 in the low half, S[h] in the high half
-    unsigned long long* partial;   // [batch][LOC_MAX_CHUNKS]: a workgroup's least key
+    unsigned long long* partial;   // [batch][LOC_MAX_CHUNKS]: a workgroup's least key (with a footprint: the least key of a
+                                   // chunk of LOC_BLOCK samples, all ones before the rollout, whose workgroups lower it)
     int* state;                    // [LOC_STATE][state_stride]
     int state_stride;
     unsigned long long* score;     // [batch]
@@ -833,10 +834,21 @@ struct LocalParams {
     const int* movers;             // [batch][PP_LOCAL_MAX_MOVERS][6]: mx, my, mvx, mvy, r_hard, r_soft
     int* mover_info;               // [PP_LOCAL_MOVER_INFO][state_stride], as LOC_M_* names the fields
     int horizon, mover_w;          // pp_local_mover_config
+    // the footprint (pp_set_local_footprint, pp_local_plan_grids_footprint); NULL: a point, and the kernels'
+    // instantiations without it run, which read nothing below
+    const unsigned* probes;        // [n_probes]: fx as int16 in the low half, fy in the high half; one table for every grid
+    int n_probes, foot_lethal;     // 1 .. PP_LOCAL_MAX_PROBES; pp_local_footprint_config
+    int* foot_info;                // [PP_LOCAL_FOOT_INFO][state_stride], as LOC_F_* names the fields
 };
 // n_movers (-1: the stream has had no posed step; rolled as 0) and n_skipped are written by k_local_movers or the host,
 // n_dynamic is cleared before the rollout and added to by it, near is written by finish
 enum { LOC_M_COUNT = 0, LOC_M_SKIPPED = 1, LOC_M_DYNAMIC = 2, LOC_M_NEAR = 3 };
+// n_footprint is cleared before the rollout and added to by it; the others are written by finish
+enum { LOC_F_COUNT = 0, LOC_F_FOOTPRINT = 1, LOC_F_START = 2, LOC_F_RESERVED = 3 };
+// The footprint rollout gives every sample a group of LOC_FOOT_GROUP lanes of one wave, lane j of which takes the probes
+// q = j (mod LOC_FOOT_GROUP); a workgroup then rolls LOC_BLOCK / LOC_FOOT_GROUP samples.  Chosen by measurement among 1,
+// 8, 16 and 64.
+constexpr int LOC_FOOT_GROUP = 64;
 void launch_local_rollout(const LocalParams& p, hipStream_t s);     // the reason counts of `state` cleared before it
 void launch_local_finish(const LocalParams& p, hipStream_t s);
 struct LocalFrame {                // what travels from the host per grid and pp_local_plan_movers_async: 4 doubles

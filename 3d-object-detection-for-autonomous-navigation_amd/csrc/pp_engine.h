@@ -500,6 +500,13 @@ struct pp_engine {
         int* mover_info = nullptr;         // [PP_LOCAL_MOVER_INFO][B]
         LocalFrame* d_frame = nullptr;     // [B]
         RingArray<LocalFrame> h_frame;     // [B] per slot, a rider of `ring`
+        // pp_set_local_footprint: the robot as a table of probes, used by both async calls while it is on; `run.probes`
+        // says whether the last run had it
+        bool foot_on = false;              // pp_set_local_footprint gave a table and has not taken it back
+        pp_local_footprint_config fcfg = {};       // the last configuration given
+        std::vector<int32_t> probes;       // [n][2], the last table given (pp_get_local_footprint_config)
+        unsigned* d_probes = nullptr;      // [PP_LOCAL_MAX_PROBES] packed; this and the next live as long as the handle (`allocs`)
+        int* foot_info = nullptr;          // [PP_LOCAL_FOOT_INFO][B]
     } local[2];                           // by source, as infl
 
     // pp_set_scan_match: the resident frames under a prior pose per stream, matched against occ.logodds, which it reads in

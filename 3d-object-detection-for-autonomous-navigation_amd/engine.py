@@ -431,6 +431,7 @@ class Engine:
         self._navfn_run = {}                                    # source index -> (batch, (H, W), max_path, origins, resolution, poses) of its last navfn_async
         self._local_run = {}                                    # source index -> (batch, LocalPlanConfig, resolution or None, step dt or None) of its last local_plan_async
         self._local_movers_run = {}                             # source index -> the MoverConfig that run used, or None
+        self._local_foot_run = {}                               # source index -> (Footprint, FootprintConfig) that run used, or None
         if d.costmap is not None:
             self.set_costmap(d.costmap)
         if weights is not None:
@@ -1620,6 +1621,47 @@ class Engine:
         self._check(self._lib.pp_get_local_movers_config(self._h, k, ctypes.byref(on), ctypes.byref(pc)), "pp_get_local_movers_config")
         return _from_struct(_loc.MoverConfig, pc) if on.value else None
 
+    def set_local_footprint(self, footprint, cfg=True, source="costmap"):
+        """A local_planner.Footprint (or its probes, integers [P, 2]) for `source`, with cfg a local_planner.FootprintConfig,
+        a dict of its fields or True (the defaults): `local_plan_async` / `drive` then roll the robot as that oriented
+        polygon instead of a point -- every sample's probes are tested on the inflated grid at every step, in the rollout
+        kernel, with or without movers (pp_set_local_footprint; local_planner.py states the rule).  Inflate by
+        `footprint.inscribed_radius()`.  None: off (the default), and every launch and result is what it was.  A new
+        footprint replaces the table a last run with a footprint read: fetch that run's results first."""
+        k = self._infl_source(source)
+        if footprint is None or footprint is False:
+            self._check(self._lib.pp_set_local_footprint(self._h, k, None, None, 0), "pp_set_local_footprint")
+            return
+        fp, fc = _loc._foot_args(footprint, cfg, "set_local_footprint")
+        pc = _to_struct(_lib.PPLocalFootprintConfig, fc)
+        P = np.ascontiguousarray(fp, np.int32)
+        self._check(self._lib.pp_set_local_footprint(self._h, k, ctypes.byref(pc), _ptr(P), len(P)), "pp_set_local_footprint")
+        if self._local_foot_run.get(k) is not None:
+            self._local_run.pop(k, None)
+
+    def local_footprint_config(self, source="costmap"):
+        """(Footprint, FootprintConfig) in force for `source`, or None while its footprint is off."""
+        k = self._infl_source(source)
+        on, n, pc = ctypes.c_int32(0), ctypes.c_int32(0), _lib.PPLocalFootprintConfig()
+        P = np.zeros((_lib.PP_LOCAL_MAX_PROBES, 2), np.int32)
+        self._check(self._lib.pp_get_local_footprint_config(self._h, k, ctypes.byref(on), ctypes.byref(pc), _ptr(P), ctypes.byref(n)),
+                    "pp_get_local_footprint_config")
+        if not on.value:
+            return None
+        return _loc.Footprint(P[:n.value]), _loc.FootprintConfig(foot_lethal=int(pc.foot_lethal))
+
+    def local_footprint(self, source="costmap"):
+        """`n_probes`, `n_footprint` (samples ended on a blocked probe) and `start_probe` (the first probe that is not free
+        at the start pose, -1: none) int32 [B] each, of the source's last local_plan_async with a footprint (waits as
+        local_commands does; pp_get_local_footprint)."""
+        k = self._infl_source(source)
+        B = self._local_last(k, "local_footprint")[0]
+        if self._local_foot_run.get(k) is None:
+            raise RuntimeError(f"local_footprint: the last local plan of the {source} source had no footprint (set_local_footprint first)")
+        info = np.zeros((B, _lib.PP_LOCAL_FOOT_INFO), np.int32)
+        self._check(self._lib.pp_get_local_footprint(self._h, k, _ptr(info), B), "pp_get_local_footprint")
+        return {name: info[:, i].copy() for i, name in enumerate(_loc.FOOT_INFO)}
+
     def _local_cells_async(self, k, poses, windows, resolution=None, dt=None, frame=None):
         """pp_local_plan_async on integers: poses int32 [B, 3] (X, Y, h), windows int32 [B, 4] (v0, dv, w0, dw).  frame
         float64 [B, 4] (ox, oy, res, dt): pp_local_plan_movers_async, the source's movers in front."""
@@ -1636,6 +1678,7 @@ class Engine:
             mc = self.local_movers_config(_infl.SOURCES[k])
         self._local_run[k] = (int(P.shape[0]), self.local_planner_config(_infl.SOURCES[k]), resolution, dt)
         self._local_movers_run[k] = mc
+        self._local_foot_run[k] = self.local_footprint_config(_infl.SOURCES[k])
 
     def local_plan_async(self, poses=None, windows=None, source="costmap", dt=None):
         """Queues the rollout and the command on the grids and fields of the source's last navfn_async behind the
@@ -1703,7 +1746,7 @@ class Engine:
         step (waits for it; the field is settled first and the rollout queued again if that took a further round: a
         command always rests on the exact field).  metric=True: (v float64 [B] m/s, w float64 [B] rad/s, cmd_state)
         through local_planner.command_metric with the run's resolution and step dt.  cmd_state as local_planner.py lists
-        it; the command is (0, 0) unless it is 0."""
+        it (5: the footprint is not free at the start pose); the command is (0, 0) unless it is 0."""
         k = self._infl_source(source)
         out = self._local_fetch(k, "local_commands")
         if not metric:
@@ -1728,11 +1771,14 @@ class Engine:
     def local_plan_info(self, source="costmap"):
         """Per grid of the source's last local_plan_async (waits as local_commands does): `cmd_state`, `best`, `sv`, `sw`,
         `n_ok`, `n_outside`, `n_collision`, `n_unreached` int32 [B] each and `score` uint64 [B]; where that run had movers
-        also `n_movers`, `n_skipped`, `n_dynamic` and `near` int32 [B]."""
+        also `n_movers`, `n_skipped`, `n_dynamic` and `near` int32 [B]; where it had a footprint also `n_probes`,
+        `n_footprint` and `start_probe` int32 [B]."""
         k = self._infl_source(source)
         out = self._local_fetch(k, "local_plan_info")
         if self._local_movers_run.get(k) is not None:
             out.update(self.local_movers(source)[1])
+        if self._local_foot_run.get(k) is not None:
+            out.update(self.local_footprint(source))
         return out
 
     def local_movers(self, source="costmap"):

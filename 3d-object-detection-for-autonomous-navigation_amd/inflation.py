@@ -28,7 +28,8 @@ t >= unknown_min_cost, else -1.  Obstacle cells therefore read 100.  unknown_min
 Outputs: the grid int8 [H, W]; optionally the clearance map dist2 uint16 [H, W] (NONE where nothing is in reach); per
 grid the counts `lethal` (obstacle cells) and `raised` (cells with out != g).
 
-Out of scope: treating unknown cells as obstacles, non-circular footprints, feeding inflated costs back into the
+Out of scope: treating unknown cells as obstacles, non-circular footprints (the local planner's footprint, local_planner.py,
+rolls the robot's outline itself and wants this stage at the footprint's inscribed radius), feeding inflated costs back into the
 occupancy maps' log-odds, 3D, any ROS import.
 """
 import ctypes

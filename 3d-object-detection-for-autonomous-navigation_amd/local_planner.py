@@ -64,12 +64,46 @@ in metres and dt seconds per step: MX = floor(((x - ox) / res) * 1024.0), MY lik
 confirmed_only is set) becomes a mover in ascending slot order; one with a non-finite input, |MX| or |MY| > 2^29 or |MVX|
 or |MVY| > 16384 is skipped and counted in n_skipped.
 
-Out of scope: escaping from a blocked pose, footprints other than a point on the inflated grid for the robot (against a
+FOOTPRINT (opt-in: `footprint=` / `fcfg=` here, Engine.set_local_footprint behind an engine).  Without one the robot is a
+point on the inflated grid: its CENTRE keeps an inscribed radius from obstacles, which is exact only for a disc.  A
+footprint is a table of P probe points (fx, fy) in the robot's frame, int32 sub-cells, x forward along heading tick h, y to
+the left; 1 <= P <= PP_LOCAL_MAX_PROBES = 256, |fx|, |fy| <= PP_LOCAL_MAX_PROBE = 32767, so 32767 * 16384 * 2 + 8192 <
+2^31 and the rotation fits int32.  PROBES: at a pose (X, Y, h) probe q lies at (X + ((fx * C[h] - fy * S[h] + 8192) >> 14),
+Y + ((fx * S[h] + fy * C[h] + 8192) >> 14)); its cell is that >> 10, the shift arithmetic, so a negative coordinate is a
+cell outside the grid.  TEST: a probe's cell is OUTSIDE the grid; BLOCKED if g >= foot_lethal (FootprintConfig, 1 .. 100,
+default 100) or if it is unknown while the NavfnConfig's allow_unknown is 0; free otherwise.  Inflation leaves exactly 100
+on obstacle cells and 99 on the inscribed ring, so with the default the corners may enter the ring -- which is the point:
+inflate by `Footprint.inscribed_radius()` and let the probes keep the corners off the obstacles.  Probes never contribute
+to occ, which stays the centre's alone (every close pass would cost 99 otherwise).  ROLLOUT: step k is unchanged up to
+and including the centre's static test (OUTSIDE, COLLISION, occ); a sample still alive then looks at the probes in table
+order under the heading AFTER the step's turn (the pose stored in the trajectory), and the first probe that is not free
+ends it: as OUTSIDE (reason 1) if its cell is outside, as FOOTPRINT (reason 5) if blocked.  Then the movers' test runs,
+unchanged, if movers are on.  The lookahead point is the centre's only.  STATE 5: the footprint at the start pose has a
+probe that is not free; the order of the states is 4, 3, 2, 5, 1, 0, and in state 5 no sample is rolled, the command is
+(0, 0), best = -1, the trajectory is empty, every key is invalid and the counts are 0.  Further results per grid
+(FOOT_INFO): n_probes, n_footprint (samples ended with reason 5; a probe that is outside counts in n_outside) and
+start_probe, the index of the first probe that is not free at the start pose, -1 if none or if the state is 2 .. 4; n_ok +
+n_outside + n_collision + n_unreached + n_dynamic + n_footprint = nv * nw in states 0 and 1.  With footprint=None every
+function returns exactly what it returned before.
+
+FROM METRES TO PROBES (`Footprint`, host only, float64).  `Footprint.polygon(vertices_m, resolution, spacing=0.5)` takes the
+vertices in order, closed implicitly; an edge of length L gives n = max(1, ceil(L / (spacing * resolution))) points at
+the fractions i / n, i = 0 .. n - 1, each rint((p / resolution) * 1024.0); duplicates are dropped, the first kept.  It is
+the OUTLINE only, no interior: a step moves the centre at most one cell and the outline is sampled every half cell, so
+the outline cannot jump an obstacle cell that the start pose did not already contain -- as long as a step's turn moves
+no probe by more than about a cell either (|sw| * circumscribed radius <= about 650 cells * ticks; a long robot that spins
+fast can sweep a corner across a thin wall between two steps).
+
+Out of scope: escaping from a blocked pose, footprints other than a point on the inflated grid for the robot unless a
+footprint is set (against a
 mover its radius rides in pad_hard / pad_soft), holonomic (vy) samples, oscillation suppression between cycles,
 goal-orientation alignment, a diagonal step passing between two blocked cells that touch only at a corner (an inscribed
 radius of one cell or more rules this out), a configuration key, any ROS import.  Of the movers: swept collision between
 two steps (a fast mover can tunnel through a small radius), rectangular mover shapes, a lead time between the tracks' stamp
-and now, movers that react to the robot.
+and now, movers that react to the robot.  Of the footprint: filled footprints (interior cells), the area swept between two
+steps, a footprint-aware inflation or navigation function (both keep the inscribed radius), a skip of the probe test where
+the centre's cost proves the circumscribed circle free (a natural follow-up), rectangular movers, escaping from state 5,
+holonomic samples.
 """
 import ctypes
 import dataclasses
@@ -79,9 +113,9 @@ import numpy as np
 
 from . import _lib
 from . import navfn as _nav
-from ._lib import (PP_LOCAL_HEADINGS, PP_LOCAL_MAX_LOOKAHEAD, PP_LOCAL_MAX_MOVER_RADIUS, PP_LOCAL_MAX_MOVER_SPEED,
-                   PP_LOCAL_MAX_MOVERS, PP_LOCAL_MAX_SAMPLES, PP_LOCAL_MAX_STEPS, PP_LOCAL_MOVER_INFO, PP_LOCAL_SUB,
-                   PP_OCC_MAX_CELLS, PP_TRACK_MAX)
+from ._lib import (PP_LOCAL_FOOT_INFO, PP_LOCAL_HEADINGS, PP_LOCAL_MAX_LOOKAHEAD, PP_LOCAL_MAX_MOVER_RADIUS,
+                   PP_LOCAL_MAX_MOVER_SPEED, PP_LOCAL_MAX_MOVERS, PP_LOCAL_MAX_PROBE, PP_LOCAL_MAX_PROBES, PP_LOCAL_MAX_SAMPLES,
+                   PP_LOCAL_MAX_STEPS, PP_LOCAL_MOVER_INFO, PP_LOCAL_SUB, PP_OCC_MAX_CELLS, PP_TRACK_MAX)
 
 SUB = PP_LOCAL_SUB
 HEADINGS = PP_LOCAL_HEADINGS
@@ -90,9 +124,12 @@ MAX_SV, MAX_SW = 1024, 512              # |sv| sub-cells and |sw| ticks per step
 INVALID = 2 ** 64 - 1                   # the key of a sample that did not end OK
 OK, OUTSIDE, COLLISION, UNREACHED = 0, 1, 2, 3      # why a sample ended
 DYNAMIC = 4                             # ... within r_hard of a mover (only with movers)
+FOOTPRINT = 5                           # ... on a blocked probe of the footprint (only with a footprint)
 MAX_MOVER_POS = 1 << 29                 # |mx|, |my| at most
 MOVER_INFO = ("n_movers", "n_skipped", "n_dynamic", "near")      # pp_get_local_movers' words
 STATE_OK, STATE_NO_SAMPLE, STATE_ARRIVED, STATE_POSE, STATE_NO_GOAL = 0, 1, 2, 3, 4
+STATE_FOOTPRINT = 5                     # a probe of the footprint is not free at the start pose (behind 4, 3, 2; before 1, 0)
+FOOT_INFO = ("n_probes", "n_footprint", "start_probe")      # pp_get_local_footprint's words (a fourth is reserved, 0)
 RESULT = ("cmd_state", "best", "sv", "sw", "n_ok", "n_outside", "n_collision", "n_unreached")      # pp_get_local_plan's words
 
 _RANGES = (("nv", 1, PP_LOCAL_MAX_SAMPLES), ("nw", 1, PP_LOCAL_MAX_SAMPLES), ("steps", 1, PP_LOCAL_MAX_STEPS),
@@ -112,6 +149,10 @@ _MAX_MPOS = MAX_MOVER_POS + PP_LOCAL_MAX_STEPS * PP_LOCAL_MAX_MOVER_SPEED
 _MAX_DX = PP_OCC_MAX_CELLS * SUB + _MAX_MPOS
 assert _MAX_MPOS < 2 ** 31 and _MAX_DX < 2 ** 31 and 2 * _MAX_DX * _MAX_DX < 2 ** 63
 assert PP_LOCAL_MAX_MOVER_RADIUS ** 2 < 2 ** 31 and PP_LOCAL_MAX_MOVERS == PP_TRACK_MAX and len(MOVER_INFO) == PP_LOCAL_MOVER_INFO
+# a probe: two int16; its rotation fits int32, and so does X + rx, because a pose whose probes are looked at lies in the grid
+assert PP_LOCAL_MAX_PROBE == 32767 and PP_LOCAL_MAX_PROBES == 256 and len(FOOT_INFO) + 1 == PP_LOCAL_FOOT_INFO
+assert PP_LOCAL_MAX_PROBE * ONE * 2 + 8192 < 2 ** 31
+assert (PP_OCC_MAX_CELLS + 1) * SUB + 2 * PP_LOCAL_MAX_PROBE + 1 < 2 ** 31
 
 
 @dataclasses.dataclass
@@ -241,6 +282,189 @@ def _mover_args(movers, mcfg, who):
     return check_movers(movers, who), MoverConfig.from_any(mcfg)
 
 
+@dataclasses.dataclass
+class FootprintConfig:
+    """foot_lethal     1 .. 100: a probe's cell with g >= foot_lethal is blocked (100: obstacle cells only, so the corners may
+                    enter the inscribed ring that inflation marks 99)"""
+    foot_lethal: int = 100
+
+    def __post_init__(self):
+        v = self.foot_lethal
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"FootprintConfig: foot_lethal must be an integer, got {v!r}")
+        if int(v) < 1 or int(v) > 100:
+            raise ValueError(f"FootprintConfig: foot_lethal = {v} outside [1, 100]")
+        self.foot_lethal = int(v)
+
+    def to_dict(self):
+        return dataclasses.asdict(self)
+
+    @classmethod
+    def from_any(cls, cfg):
+        """A FootprintConfig, a dict of its fields (unknown keys raise, naming them) or True (the defaults)."""
+        if isinstance(cfg, cls):
+            return cfg
+        if cfg is True:
+            return cls()
+        if isinstance(cfg, dict):
+            unknown = set(cfg) - {f.name for f in dataclasses.fields(cls)}
+            if unknown:
+                raise ValueError(f"local_planner: unknown keys {sorted(unknown)}")
+            return cls(**cfg)
+        raise ValueError(f"local_planner: a FootprintConfig, a dict of its fields or True, got {cfg!r}")
+
+
+def check_probes(probes, who="local_planner"):
+    """int64 [P, 2] (fx, fy) of 1 .. PP_LOCAL_MAX_PROBES probes; raises, naming the probe, unless |fx|, |fy| <=
+    PP_LOCAL_MAX_PROBE."""
+    a = np.asarray(probes)
+    if a.ndim != 2 or a.shape[1] != 2 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{who}: probes must be integers [P, 2] (fx, fy), got {a.dtype} {a.shape}")
+    if not 1 <= a.shape[0] <= PP_LOCAL_MAX_PROBES:
+        raise ValueError(f"{who}: {a.shape[0]} probes, 1 to PP_LOCAL_MAX_PROBES = {PP_LOCAL_MAX_PROBES}")
+    a = a.astype(np.int64)
+    for q, (fx, fy) in enumerate(a.tolist()):
+        if max(abs(fx), abs(fy)) > PP_LOCAL_MAX_PROBE:
+            raise ValueError(f"{who}: probe {q}: ({fx}, {fy}) outside [-{PP_LOCAL_MAX_PROBE}, {PP_LOCAL_MAX_PROBE}]")
+    return a
+
+
+class Footprint:
+    """The robot as a table of probes int64 [P, 2] (fx, fy) in sub-cells of its own frame, x forward, y to the left
+    (`probes`), as the rule takes it.  `Footprint(probes)` takes the table itself; `Footprint.polygon` and
+    `Footprint.rectangle` make it from metres (host only, float64) and remember the outline for the two radii."""
+
+    def __init__(self, probes, vertices=None):
+        self.probes = check_probes(probes, "Footprint")
+        self.probes.setflags(write=False)
+        self.vertices = None if vertices is None else np.array(vertices, np.float64)
+
+    def __len__(self):
+        return len(self.probes)
+
+    def __eq__(self, other):
+        return isinstance(other, Footprint) and np.array_equal(self.probes, other.probes)
+
+    def __repr__(self):
+        return f"Footprint({len(self.probes)} probes)"
+
+    @classmethod
+    def polygon(cls, vertices_m, resolution, spacing=0.5):
+        """The outline of the polygon with the vertices float [n, 2] metres in the robot's frame, in order, closed
+        implicitly, sampled every `spacing` cells of `resolution` metres: an edge of length L gives n = max(1, ceil(L /
+        (spacing * resolution))) points at the fractions i / n, i = 0 .. n - 1, each rint((p / resolution) * 1024.0);
+        duplicates are dropped, the first kept.  Refused, with the reason named: fewer than 3 vertices, the origin (the
+        point the planner rolls) not strictly inside, a probe out of range, more than PP_LOCAL_MAX_PROBES probes."""
+        v = np.asarray(vertices_m, np.float64)
+        res, spacing = float(resolution), float(spacing)
+        if v.ndim != 2 or v.shape[1] != 2 or not np.isfinite(v).all():
+            raise ValueError(f"Footprint.polygon: vertices must be finite metres [n, 2], got {np.asarray(vertices_m).shape}")
+        if len(v) < 3:
+            raise ValueError(f"Footprint.polygon: {len(v)} vertices, fewer than 3")
+        if not (math.isfinite(res) and res > 0.0):
+            raise ValueError(f"Footprint.polygon: resolution = {res} must be finite and > 0")
+        if not (math.isfinite(spacing) and spacing > 0.0):
+            raise ValueError(f"Footprint.polygon: spacing = {spacing} must be finite and > 0")
+        if not _origin_strictly_inside(v):
+            raise ValueError("Footprint.polygon: the origin is not strictly inside the polygon")
+        probes, seen = [], set()
+        for a, b in zip(v, np.roll(v, -1, axis=0)):
+            n = max(1, math.ceil(math.hypot(b[0] - a[0], b[1] - a[1]) / (spacing * res)))
+            for i in range(n):
+                pt = a + (b - a) * (i / n)
+                q = (int(np.rint((pt[0] / res) * 1024.0)), int(np.rint((pt[1] / res) * 1024.0)))
+                if max(abs(q[0]), abs(q[1])) > PP_LOCAL_MAX_PROBE:
+                    raise ValueError(f"Footprint.polygon: the probe ({q[0]}, {q[1]}) at ({pt[0]:g}, {pt[1]:g}) m is out of range "
+                                     f"[-{PP_LOCAL_MAX_PROBE}, {PP_LOCAL_MAX_PROBE}] sub-cells")
+                if q not in seen:
+                    seen.add(q)
+                    probes.append(q)
+        if len(probes) > PP_LOCAL_MAX_PROBES:
+            raise ValueError(f"Footprint.polygon: {len(probes)} probes, more than PP_LOCAL_MAX_PROBES = {PP_LOCAL_MAX_PROBES} (a larger spacing)")
+        return cls(np.array(probes, np.int64), v)
+
+    @classmethod
+    def rectangle(cls, length, width, offset_x=0.0, *, resolution, spacing=0.5):
+        """The rectangle `length` metres along x and `width` metres along y whose centre lies offset_x metres in front of
+        the origin, counter-clockwise from the rear right corner."""
+        l, w, o = float(length), float(width), float(offset_x)
+        if not (math.isfinite(l) and math.isfinite(w) and l > 0.0 and w > 0.0 and math.isfinite(o)):
+            raise ValueError(f"Footprint.rectangle: length = {l}, width = {w}, offset_x = {o}: finite, length and width > 0")
+        return cls.polygon([(o - l / 2, -w / 2), (o + l / 2, -w / 2), (o + l / 2, w / 2), (o - l / 2, w / 2)], resolution, spacing)
+
+    def _outline(self, who):
+        if self.vertices is None:
+            raise ValueError(f"Footprint.{who}: a footprint given as probes has no outline in metres")
+        return self.vertices
+
+    def inscribed_radius(self):
+        """Metres from the origin to the nearest point of the outline: what belongs in InflationConfig.inscribed_radius
+        (the centre then keeps that far from obstacles, and the probes look after the rest of the robot)."""
+        v = self._outline("inscribed_radius")
+        return min(_segment_distance(a, b) for a, b in zip(v, np.roll(v, -1, axis=0)))
+
+    def circumscribed_radius(self):
+        """Metres from the origin to the farthest vertex: beyond it nothing can touch the robot."""
+        return float(np.hypot(*self._outline("circumscribed_radius").T).max())
+
+
+def _segment_distance(a, b):
+    """Metres from the origin to the segment a - b."""
+    d = b - a
+    t = min(max(float(-(a @ d) / (d @ d)), 0.0), 1.0) if float(d @ d) > 0.0 else 0.0
+    return float(np.hypot(*(a + t * d)))
+
+
+def _origin_strictly_inside(v):
+    """The crossing number of the ray from the origin along +x is odd, and the origin lies on no edge."""
+    inside = False
+    for a, b in zip(v, np.roll(v, -1, axis=0)):
+        if _segment_distance(a, b) == 0.0:
+            return False
+        if (a[1] > 0.0) != (b[1] > 0.0) and a[0] + (0.0 - a[1]) * (b[0] - a[0]) / (b[1] - a[1]) > 0.0:
+            inside = not inside
+    return inside
+
+
+def _foot_args(footprint, fcfg, who):
+    """(None, None) without a footprint; else (probes int64 [P, 2], FootprintConfig): a Footprint or a table of probes, and
+    fcfg a FootprintConfig, a dict of its fields, True or None (the defaults)."""
+    if footprint is None:
+        if fcfg is not None:
+            raise ValueError(f"{who}: fcfg without a footprint")
+        return None, None
+    probes = footprint.probes if isinstance(footprint, Footprint) else check_probes(footprint, who)
+    return probes, FootprintConfig.from_any(True if fcfg is None else fcfg)
+
+
+def _probe_cell(X, Y, h, fx, fy):
+    """The cell of probe (fx, fy) at the pose (X, Y, h), in Python ints."""
+    C, S = int(_TRIG[h, 0]), int(_TRIG[h, 1])
+    assert abs(fx * C - fy * S) + 8192 < 2 ** 31 and abs(fx * S + fy * C) + 8192 < 2 ** 31
+    return (X + ((fx * C - fy * S + 8192) >> 14)) >> 10, (Y + ((fx * S + fy * C + 8192) >> 14)) >> 10
+
+
+def _probe_value(g, n, fc, cx, cy):
+    """The rule's reading of a probe's cell: None outside the grid, True blocked, False free."""
+    H, W = g.shape
+    if not (0 <= cx < W and 0 <= cy < H):
+        return None
+    v = int(g[cy, cx])
+    return v >= fc.foot_lethal or (v < 0 and not n.allow_unknown)
+
+
+def start_probe_np(grid, pose, navfn_cfg, footprint, fcfg=None):
+    """The index of the first probe that is not free at the pose, -1 if none."""
+    n = _nav.NavfnConfig.from_any(navfn_cfg)
+    fp, fc = _foot_args(footprint, fcfg, "start_probe_np")
+    g = np.asarray(grid)
+    X, Y, h = _ints(pose, 3, "start_probe_np", "a pose (X, Y, h)")
+    for q, (fx, fy) in enumerate(fp.tolist()):
+        if _probe_value(g, n, fc, *_probe_cell(X, Y, h & (HEADINGS - 1), fx, fy)) is not False:
+            return q
+    return -1
+
+
 def movers_np(rows, n, origin, res, dt, cfg):
     """The table of one stream from its track rows, as k_local_movers makes it: rows tracking.TRACK_DTYPE (from
     `Engine.tracks()` for the costmap source, `Engine.tracks_fixed()` for the occupancy source), of which the first n are
@@ -355,17 +579,21 @@ def stream_state_np(grid, pot, pose, navfn_cfg, goal_state=0):
     return STATE_ARRIVED if int(p[cy, cx]) == 0 else STATE_OK
 
 
-def score_np(grid, pot, pose, sv, sw, navfn_cfg, cfg, movers=None, mcfg=None):
+def score_np(grid, pot, pose, sv, sw, navfn_cfg, cfg, movers=None, mcfg=None, footprint=None, fcfg=None):
     """One sample, step by step in Python ints: (reason, score or None, poses) -- the poses [(X, Y, h)] the sample
     reached, the start included (steps + 1 of them when reason is OK or UNREACHED).  With movers (integers [n, 6] and a
-    MoverConfig): (reason, score or None, poses, near)."""
+    MoverConfig): (reason, score or None, poses, near).  With a footprint (a Footprint or probes [P, 2], and a
+    FootprintConfig or None for the defaults) the tuple is the same; the start pose's own probes are not looked at (that
+    is state 5, `start_probe_np`)."""
     mv, mc = _mover_args(movers, mcfg, "score_np")
+    fp, fc = _foot_args(footprint, fcfg, "score_np")
+    foot = None if fp is None else (fp.tolist(), fc)
     if mv is None:
-        return _score(grid, pot, pose, sv, sw, navfn_cfg, cfg, (), None)[:3]
-    return _score(grid, pot, pose, sv, sw, navfn_cfg, cfg, mv.tolist(), mc)
+        return _score(grid, pot, pose, sv, sw, navfn_cfg, cfg, (), None, foot)[:3]
+    return _score(grid, pot, pose, sv, sw, navfn_cfg, cfg, mv.tolist(), mc, foot)
 
 
-def _score(grid, pot, pose, sv, sw, navfn_cfg, cfg, mv, mc):
+def _score(grid, pot, pose, sv, sw, navfn_cfg, cfg, mv, mc, foot=None):
     n = _nav.NavfnConfig.from_any(navfn_cfg)
     c = LocalPlanConfig.from_any(cfg)
     g, p = _inputs(grid, pot, "score_np")
@@ -386,6 +614,13 @@ def _score(grid, pot, pose, sv, sw, navfn_cfg, cfg, mv, mc):
         if v < 0:
             return COLLISION, None, poses, near
         occ = max(occ, v)
+        if foot is not None:                                # the probes in table order, under the heading after the turn
+            for fx, fy in foot[0]:
+                blocked = _probe_value(g, n, foot[1], *_probe_cell(X, Y, h, fx, fy))
+                if blocked is None:
+                    return OUTSIDE, None, poses, near
+                if blocked:
+                    return FOOTPRINT, None, poses, near
         if mc is not None and k <= mc.horizon:
             for mx, my, mvx, mvy, rh, rs in mv:
                 dx, dy = X - (mx + k * mvx), Y - (my + k * mvy)
@@ -407,7 +642,7 @@ def _score(grid, pot, pose, sv, sw, navfn_cfg, cfg, mv, mc):
     return OK, score, poses, near
 
 
-def keys_by_sample_np(grid, pot, pose, window, navfn_cfg, cfg, movers=None, mcfg=None):
+def keys_by_sample_np(grid, pot, pose, window, navfn_cfg, cfg, movers=None, mcfg=None, footprint=None, fcfg=None):
     """(keys uint64 [nv * nw], reasons int32 [nv * nw]) of a window through `score_np`, sample by sample."""
     c = LocalPlanConfig.from_any(cfg)
     window = check_window(window, c, "keys_by_sample_np")
@@ -415,16 +650,17 @@ def keys_by_sample_np(grid, pot, pose, window, navfn_cfg, cfg, movers=None, mcfg
     reasons = np.zeros(c.nv * c.nw, np.int32)
     for s in range(c.nv * c.nw):
         sv, sw = sample(s, window, c)
-        reasons[s], score = score_np(grid, pot, pose, sv, sw, navfn_cfg, c, movers, mcfg)[:2]
+        reasons[s], score = score_np(grid, pot, pose, sv, sw, navfn_cfg, c, movers, mcfg, footprint, fcfg)[:2]
         if score is not None:
             keys[s] = (score << 14) | s
     return keys, reasons
 
 
-def scores_np(grid, pot, pose, window, navfn_cfg, cfg, movers=None, mcfg=None):
+def scores_np(grid, pot, pose, window, navfn_cfg, cfg, movers=None, mcfg=None, footprint=None, fcfg=None):
     """(keys uint64 [nv * nw], reasons int32 [nv * nw]) of a window, all samples at once: arrays over the samples, one
-    masked update per step (and, with movers, per step and mover)."""
+    masked update per step (and, with movers, per step and mover; with a footprint, one over samples x probes per step)."""
     mv, mc = _mover_args(movers, mcfg, "scores_np")
+    fp, fc = _foot_args(footprint, fcfg, "scores_np")
     n = _nav.NavfnConfig.from_any(navfn_cfg)
     c = LocalPlanConfig.from_any(cfg)
     g, p = _inputs(grid, pot, "scores_np")
@@ -444,6 +680,10 @@ def scores_np(grid, pot, pose, window, navfn_cfg, cfg, movers=None, mcfg=None):
     reason = np.zeros(N, np.int32)
     alive = np.ones(N, bool)
     C, S = _TRIG[:, 0].astype(np.int64), _TRIG[:, 1].astype(np.int64)
+    if fp is not None:                                      # a probe's reading by the cell's value + 1 (0: unknown)
+        foot_raw = np.maximum(g.astype(np.int64), -1)
+        foot_blocked = np.arange(-1, 128) >= fc.foot_lethal
+        foot_blocked[0] = not n.allow_unknown
 
     def read(cx, cy, m):
         """(inside, index): which samples of mask m lie in the grid, and an index that is (0, 0) for the others"""
@@ -463,6 +703,18 @@ def scores_np(grid, pot, pose, window, navfn_cfg, cfg, movers=None, mcfg=None):
         reason[hit] = COLLISION
         alive = alive & ~out & ~hit
         occ = np.where(alive, np.maximum(occ, v), occ)
+        if fp is not None:                                  # [N, P]: 0 free, 1 outside, 2 blocked; the first that is not free
+            Ch, Sh = C[h][:, None], S[h][:, None]
+            px = (X[:, None] + ((fp[None, :, 0] * Ch - fp[None, :, 1] * Sh + 8192) >> 14)) >> 10
+            py = (Y[:, None] + ((fp[None, :, 0] * Sh + fp[None, :, 1] * Ch + 8192) >> 14)) >> 10
+            inside = (px >= 0) & (px < W) & (py >= 0) & (py < H)
+            gq = foot_raw[np.where(inside, py, 0), np.where(inside, px, 0)]
+            status = np.where(inside, np.where(foot_blocked[gq + 1], 2, 0), 1)
+            first = np.argmax(status != 0, axis=1)
+            verdict = status[np.arange(N), first]
+            reason[alive & (verdict == 1)] = OUTSIDE
+            reason[alive & (verdict == 2)] = FOOTPRINT
+            alive = alive & (verdict == 0)
         if mc is None or k > mc.horizon:
             continue
         for mx, my, mvx, mvy, rh, rs in mv:                 # int64 arrays: |dx| < 2^31, so d2 < 2^63 (asserted above)
@@ -484,12 +736,16 @@ def scores_np(grid, pot, pose, window, navfn_cfg, cfg, movers=None, mcfg=None):
     return keys.astype(np.uint64), reason
 
 
-def best_np(grid, pot, pose, window, navfn_cfg, cfg, goal_state=0, samples=None, movers=None, mcfg=None):
+def best_np(grid, pot, pose, window, navfn_cfg, cfg, goal_state=0, samples=None, movers=None, mcfg=None, footprint=None, fcfg=None):
     """The results of one grid as a dict: the RESULT words, `score`, `traj` int32 [steps + 1, 3] (or [0, 3]) and `keys`
     uint64 [nv * nw].  samples: `scores_np` (the default) or `keys_by_sample_np`.  With movers (integers [n, 6] and a
-    MoverConfig) also `n_movers`, `n_dynamic` and `near`."""
+    MoverConfig) also `n_movers`, `n_dynamic` and `near`.  With a footprint (a Footprint or probes [P, 2], and a
+    FootprintConfig or None for the defaults) also the FOOT_INFO words `n_probes`, `n_footprint` and `start_probe`."""
     mv, mc = _mover_args(movers, mcfg, "best_np")
+    fp, fc = _foot_args(footprint, fcfg, "best_np")
     extra = () if mv is None else (mv, mc)
+    if fp is not None:
+        extra = (mv, mc, fp, fc)
     c = LocalPlanConfig.from_any(cfg)
     window = check_window(window, c, "best_np")
     N = c.nv * c.nw
@@ -497,12 +753,20 @@ def best_np(grid, pot, pose, window, navfn_cfg, cfg, goal_state=0, samples=None,
     out.update(best=-1, score=0, traj=np.zeros((0, 3), np.int32), keys=np.full(N, INVALID, np.uint64))
     if mv is not None:
         out.update(n_movers=len(mv), n_dynamic=0, near=0)
+    if fp is not None:
+        out.update(n_probes=len(fp), n_footprint=0, start_probe=-1)
     state = stream_state_np(grid, pot, pose, navfn_cfg, goal_state)
+    if state == STATE_OK and fp is not None:
+        out["start_probe"] = start_probe_np(grid, pose, navfn_cfg, fp, fc)
+        if out["start_probe"] >= 0:
+            state = STATE_FOOTPRINT
     if state == STATE_OK:
         keys, reasons = (samples or scores_np)(grid, pot, pose, window, navfn_cfg, c, *extra)
         out["keys"] = keys
         if mv is not None:
             out["n_dynamic"] = int((reasons == DYNAMIC).sum())
+        if fp is not None:
+            out["n_footprint"] = int((reasons == FOOTPRINT).sum())
         for r, name in ((OK, "n_ok"), (OUTSIDE, "n_outside"), (COLLISION, "n_collision"), (UNREACHED, "n_unreached")):
             out[name] = int((reasons == r).sum())
         k = int(keys.min())
@@ -634,14 +898,16 @@ def unpack_results(c, B, res, score, traj, keys):
 
 
 def local_plan(grids, pots, poses, windows, navfn_cfg, cfg, goal_state=None, keys=False, device=0, movers=None, n_movers=None,
-               mover_cfg=None):
+               mover_cfg=None, footprint=None, fcfg=None):
     """The rule on the GPU, without an engine (pp_local_plan_grids): grids int8 and pots uint32 [H, W] or [B, H, W]
     (H * W <= PP_OCC_MAX_CELLS), poses integers [B, 3] (or one), windows integers [B, 4] (or one), goal_state integers [B]
     or None (all 0) -> a dict: the RESULT words and `score` per grid, `traj`, and `keys` if asked (ints and arrays for one
     grid; int32 [B], uint64 [B], a list of B arrays and uint64 [B, nv * nw] for a batch).  With movers
     (pp_local_plan_grids_movers): movers integers [n, 6] for one grid, [B, PP_LOCAL_MAX_MOVERS, 6] with n_movers integers
     [B] for a batch, and mover_cfg a MoverConfig of which horizon and mover_weight are read; the dict then also holds the
-    MOVER_INFO words."""
+    MOVER_INFO words.  With a footprint (pp_local_plan_grids_footprint, with or without movers): a Footprint or probes
+    integers [P, 2], one table for every grid, and fcfg a FootprintConfig, a dict of its fields, True or None (the
+    defaults); the dict then also holds the FOOT_INFO words."""
     n = _nav.NavfnConfig.from_any(navfn_cfg)
     c = LocalPlanConfig.from_any(cfg)
     a, p = np.asarray(grids), np.asarray(pots)
@@ -661,6 +927,7 @@ def local_plan(grids, pots, poses, windows, navfn_cfg, cfg, goal_state=None, key
     for b in range(B):
         check_window(Wn[b], c, f"local_plan: grid {b}")
     gs = None if goal_state is None else np.ascontiguousarray(np.broadcast_to(np.asarray(goal_state), (B,)), np.int32)
+    fp, fc = _foot_args(footprint, fcfg, "local_plan")
     if movers is None and (n_movers is not None or mover_cfg is not None):
         raise ValueError("local_plan: n_movers or mover_cfg without movers (an empty table is movers=[])")
     if movers is not None:
@@ -692,7 +959,12 @@ def local_plan(grids, pots, poses, windows, navfn_cfg, cfg, goal_state=None, key
             ctypes.byref(_lib.PPLocalPlanConfig(**c.to_dict())), trig.ctypes.data, len(trig), P.ctypes.data, Wn.ctypes.data,
             None if gs is None else gs.ctypes.data)
     outs = (res.ctypes.data, score.ctypes.data, traj.ctypes.data, None if kk is None else kk.ctypes.data)
-    if movers is None:
+    if fp is not None:
+        F = np.ascontiguousarray(fp, np.int32)
+        finfo = np.zeros((B, PP_LOCAL_FOOT_INFO), np.int32)
+        mover_args = (0, 0, None, None, None) if movers is None else (mc.horizon, mc.mover_weight, M.ctypes.data, NM.ctypes.data, info.ctypes.data)
+        st = L.pp_local_plan_grids_footprint(*head, *mover_args[:4], F.ctypes.data, len(F), fc.foot_lethal, *outs, mover_args[4], finfo.ctypes.data)
+    elif movers is None:
         st = L.pp_local_plan_grids(*head, *outs)
     else:
         st = L.pp_local_plan_grids_movers(*head, mc.horizon, mc.mover_weight, M.ctypes.data, NM.ctypes.data, *outs, info.ctypes.data)
@@ -702,6 +974,8 @@ def local_plan(grids, pots, poses, windows, navfn_cfg, cfg, goal_state=None, key
     out = unpack_results(c, B, res, score, traj, kk)
     if movers is not None:
         out.update({k: info[:, i].copy() for i, k in enumerate(MOVER_INFO)})
+    if fp is not None:
+        out.update({k: finfo[:, i].copy() for i, k in enumerate(FOOT_INFO)})
     if one:
         out = {k: (v[0] if isinstance(v, (list, np.ndarray)) else v) for k, v in out.items()}
         out = {k: (int(v) if np.ndim(v) == 0 else v) for k, v in out.items()}

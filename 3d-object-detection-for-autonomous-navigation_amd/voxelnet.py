@@ -98,7 +98,8 @@ class VoxelNet:
     def drive(self, goals, velocities, limits, source="costmap", poses=None):
         """Engine.drive: the velocity commands in m/s and rad/s towards `goals` over the inflated grids of the pass that has
         just run, or of the last occupancy_update (engine.set_inflation, engine.set_navfn and engine.set_local_planner for
-        that source first; engine.set_local_movers to avoid the streams' moving tracks too)."""
+        that source first; engine.set_local_movers to avoid the streams' moving tracks too, engine.set_local_footprint to roll
+        the robot as an oriented polygon instead of a point)."""
         return self.engine.drive(goals, velocities, limits, source, poses)
 
     def explore(self, source="occupancy"):

@@ -70,7 +70,10 @@ extern "C" {
  * pp_local_plan_grids_movers: the stage reads the occupancy maps' log-odds where they lie).  Then PP_FRONTIER_MAX,
  * PP_FRONTIER_INFO, PP_FRONTIER_NONE, pp_frontier_config, pp_set_frontier, pp_get_frontier_config, pp_frontier_async,
  * pp_get_frontiers, pp_frontier_grids (declared behind pp_scan_match_grids: the stage reads the inflated grid, and under
- * use_field the navigation function's field, where they lie). */
+ * use_field the navigation function's field, where they lie).  Then PP_LOCAL_MAX_PROBES, PP_LOCAL_MAX_PROBE,
+ * PP_LOCAL_FOOT_INFO, pp_local_footprint_config, pp_set_local_footprint, pp_get_local_footprint_config,
+ * pp_get_local_footprint, pp_local_plan_grids_footprint (declared behind pp_local_plan_grids_movers: the footprint rides
+ * in the local planner's rollout). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -1603,6 +1606,51 @@ int pp_local_plan_grids_movers(int device, const int8_t* grids, const uint32_t* 
                                const int32_t* goal_state, int32_t horizon, int32_t mover_weight, const int32_t* movers,
                                const int32_t* n_movers, int32_t* result, uint64_t* score, int32_t* traj, uint64_t* keys,
                                int32_t* info);
+
+/* ---- Footprint of the local planner: an oriented polygon instead of a point (local_planner.py states the rule).  A
+ * footprint is a table of n probe points (fx, fy) in the robot's frame, int32 sub-cells, x forward along the heading
+ * tick, y to the left; 1 <= n <= PP_LOCAL_MAX_PROBES, |fx|, |fy| <= PP_LOCAL_MAX_PROBE.  At a pose (X, Y, h) probe q lies
+ * at (X + ((fx C[h] - fy S[h] + 8192) >> 14), Y + ((fx S[h] + fy C[h] + 8192) >> 14)), its cell is that >> 10; the cell is
+ * OUTSIDE the grid, BLOCKED (g >= foot_lethal, or unknown while the navfn configuration's allow_unknown is 0) or free.
+ * THE ROLLOUT: a sample still alive behind the centre's static test of a step looks at the probes in table order under
+ * the heading after the step's turn; the first probe that is not free ends it, as OUTSIDE (reason 1) if its cell is
+ * outside, as FOOTPRINT (reason 5) if blocked.  Probes never raise occ.  The movers' test, where they are on, follows.
+ * cmd_state 5 (behind 4, 3, 2, before 1 and 0): a probe is not free at the start pose; no sample is rolled.  Once set, the
+ * footprint is used by pp_local_plan_async and pp_local_plan_movers_async alike. ---- */
+#define PP_LOCAL_MAX_PROBES 256         /* probes of a footprint at most */
+#define PP_LOCAL_MAX_PROBE 32767        /* sub-cells: |fx|, |fy| at most */
+#define PP_LOCAL_FOOT_INFO 4            /* int32 words per grid: n_probes, n_footprint, start_probe (-1: none), 0 */
+
+typedef struct pp_local_footprint_config {
+    int32_t foot_lethal;     /* 1 .. 100: a probe's cell with g >= foot_lethal is blocked */
+    int32_t reserved[3];     /* 0 */
+} pp_local_footprint_config;
+
+/* n == 0 with probes == NULL (cfg may be NULL then): the source's footprint off (the default); its buffers are kept and
+ * every launch and result is what it was.  Otherwise probes int32 [n][2] and the configuration are validated (PP_ERR_ARG
+ * naming the probe or the field).  Independent of pp_set_local_plan and pp_set_local_movers.  Waits for the stream.  A
+ * new table replaces the one a last run with a footprint read, so that run's results can no longer be fetched (its
+ * getters answer PP_ERR_STATE until the next pp_local_plan_async).  PP_ERR_STATE while a training step is in flight. */
+int pp_set_local_footprint(pp_handle h, int32_t source, const pp_local_footprint_config* cfg, const int32_t* probes, int32_t n);
+/* *on: 0 / 1; cfg_out (may be NULL): the last configuration given (zeros before the first); probes_out (may be NULL):
+ * int32 [PP_LOCAL_MAX_PROBES][2] of which the first *n_out (may be NULL) are the last table given. */
+int pp_get_local_footprint_config(pp_handle h, int32_t source, int32_t* on, pp_local_footprint_config* cfg_out,
+                                  int32_t* probes_out, int32_t* n_out);
+/* The footprint words of the source's last pp_local_plan_async or pp_local_plan_movers_async: info int32
+ * [batch][PP_LOCAL_FOOT_INFO] (may be NULL).  Waits and settles as pp_get_local_plan does.  PP_ERR_STATE also when that
+ * run had no footprint. */
+int pp_get_local_footprint(pp_handle h, int32_t source, int32_t* info, int32_t batch);
+/* pp_local_plan_grids_movers with a footprint: probes int32 [n_probes][2] (1 .. PP_LOCAL_MAX_PROBES, every one
+ * range-checked, PP_ERR_ARG naming the probe), one table for every grid, and foot_lethal as pp_local_footprint_config
+ * has it.  movers may be NULL: no movers (n_movers, horizon, mover_weight and info are then not read).  foot_info int32
+ * [batch][PP_LOCAL_FOOT_INFO] or NULL. */
+int pp_local_plan_grids_footprint(int device, const int8_t* grids, const uint32_t* pots, int32_t batch, int32_t height,
+                                  int32_t width, const pp_navfn_config* navfn_cfg, const pp_local_plan_config* cfg,
+                                  const int32_t* trig, int32_t n_trig, const int32_t* poses, const int32_t* windows,
+                                  const int32_t* goal_state, int32_t horizon, int32_t mover_weight, const int32_t* movers,
+                                  const int32_t* n_movers, const int32_t* probes, int32_t n_probes, int32_t foot_lethal,
+                                  int32_t* result, uint64_t* score, int32_t* traj, uint64_t* keys, int32_t* info,
+                                  int32_t* foot_info);
 
 /* ---- scan match: the resident points of frame b under stream b's PRIOR sensor-to-fixed pose, matched against the
  * stream's occupancy map as it stands BEFORE the frame is fused into it (scan_match.py states the rule).  Opt-in, off by
