@@ -28,6 +28,7 @@ SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_
            "api_local_plan.hip", "local_plan.hip", "local_movers.hip",
            "api_scan_match.hip", "scan_match.hip",
            "api_frontier.hip", "frontier.hip",
+           "api_object_mask.hip", "object_mask.hip",
            "api_track.hip", "track.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
@@ -71,6 +72,8 @@ EXPORTS = [
     "pp_set_scan_match", "pp_get_scan_match_config", "pp_scan_match_async", "pp_get_scan_match", "pp_scan_match_grids",
     "pp_set_frontier", "pp_get_frontier_config", "pp_frontier_async", "pp_get_frontiers", "pp_frontier_grids",
     "pp_set_local_footprint", "pp_get_local_footprint_config", "pp_get_local_footprint", "pp_local_plan_grids_footprint",
+    "pp_set_object_mask", "pp_get_object_mask_config", "pp_object_mask_async", "pp_object_mask_shape", "pp_get_object_mask",
+    "pp_occupancy_masked", "pp_object_mask_points",
     "pp_set_nms_mode", "pp_get_nms_mode", "pp_rotate_nms",
     "pp_set_projection", "pp_get_projection", "pp_get_bboxes", "pp_box3d_to_bbox",
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
@@ -265,6 +268,9 @@ PP_LOCAL_MAX_PROBE = 32767      # sub-cells: |fx|, |fy| of a probe at most
 PP_LOCAL_FOOT_INFO = 4          # int32 words per grid of pp_get_local_footprint's info
 PP_SCAN_MAX_CANDIDATES = 65536  # pp_scan_match_config: (2 nx + 1)(2 ny + 1)(2 nt + 1) at most
 PP_SCAN_RESULT = 8              # int32 words per stream of pp_get_scan_match's result
+PP_OBJMASK_MAX_FOOTPRINTS = 128  # footprints of a frame's object mask (pp_set_object_mask)
+PP_OBJMASK_INFO = 4              # int32 words per frame of pp_get_object_mask's info
+PP_OBJMASK_OCCUPANCY, PP_OBJMASK_SCAN_MATCH, PP_OBJMASK_COSTMAP = 1, 2, 4     # bits of pp_object_mask_config.consumers
 PP_SCAN_NO_MAP, PP_SCAN_OUTSIDE, PP_SCAN_FEW_CELLS, PP_SCAN_LOW_SCORE, PP_SCAN_EDGE = 1, 2, 4, 8, 16      # its status bits
 PP_FRONTIER_MAX = 64            # frontiers pp_get_frontiers returns per grid at most
 PP_FRONTIER_INFO = 6            # int32 words per grid of its info: frontier_cells, clusters, small, unreached, kept, returned
@@ -412,6 +418,18 @@ class PPScanMatchConfig(ctypes.Structure):
         ("theta_step", ctypes.c_int32),
         ("min_cells", ctypes.c_int32),
         ("min_mean", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class PPObjectMaskConfig(ctypes.Structure):
+    _fields_ = [
+        ("min_score", ctypes.c_double),
+        ("min_speed", ctypes.c_double),
+        ("pad", ctypes.c_double),
+        ("objects", ctypes.c_int32),
+        ("confirmed_only", ctypes.c_int32),
+        ("consumers", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
     ]
 
@@ -733,6 +751,13 @@ def lib():
     L.pp_get_train_metrics.argtypes = [vp, vp]
     L.pp_grad_clip_workspace_bytes.argtypes = [i64, i32, i32, ctypes.POINTER(i64)]
     L.pp_grad_norm_device.argtypes = [ctypes.c_int, vp, vp, i64, vp, i32, vp, i32, vp]
+    L.pp_set_object_mask.argtypes = [vp, ctypes.POINTER(PPObjectMaskConfig)]
+    L.pp_get_object_mask_config.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(PPObjectMaskConfig)]
+    L.pp_object_mask_async.argtypes = [vp, vp, vp, i32]
+    L.pp_object_mask_shape.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.pp_get_object_mask.argtypes = [vp, vp, vp, i32]
+    L.pp_occupancy_masked.argtypes = [vp, vp, i32]
+    L.pp_object_mask_points.argtypes = [ctypes.c_int, vp, vp, i32, i32, vp, vp, ctypes.c_double, vp, i32, vp]
     L.pp_adamw_step_clipped_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, i64, vp, i32, vp, i32,
                                                ctypes.POINTER(PPGradClipConfig), vp, ctypes.c_float, ctypes.c_float,
                                                ctypes.c_float, ctypes.c_float, ctypes.c_float]

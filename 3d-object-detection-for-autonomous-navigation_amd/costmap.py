@@ -27,7 +27,11 @@ COMPOSE.  cell = max(point_cost if count >= min_points else -1, the costs of the
 0 if observed else -1), stored as int8.
 
 Inflation is a stage of its own behind this grid (inflation.py, Engine.set_inflation / inflated_costmaps).  Out of
-scope: a map in the fixed frame accumulated over time, ray-traced free space, removing the points of detected objects from the point layer, any ROS import.
+scope: a map in the fixed frame accumulated over time (occupancy.py), ray-traced free space, any ROS import.
+
+OBJECT MASK (object_mask.py; point_layer_np / costmap_np(..., mask=)): an in-grid row whose mask bit is set marks its cell
+OBSERVED and adds no count, as a row outside the z band does -- an object is then painted once, as its footprint, and not
+a second time as raw points.  Without a mask the rule is what it was.
 """
 import dataclasses
 import math
@@ -202,8 +206,9 @@ def _uv(c, f):
     return (dx * f[2]) - (dy * f[3]), (dx * f[3]) + (dy * f[2])
 
 
-def point_layer_np(points, cfg):
-    """(counts int32 [H, W], observed bool [H, W]) of one frame's rows [n, F >= 3] float32."""
+def point_layer_np(points, cfg, mask=None):
+    """(counts int32 [H, W], observed bool [H, W]) of one frame's rows [n, F >= 3] float32; mask: bool [n], the rows'
+    object mask, or None."""
     c = CostmapConfig.from_any(cfg)
     p = np.asarray(points)
     if p.dtype != np.float32 or p.ndim != 2 or p.shape[1] < 3:
@@ -215,6 +220,11 @@ def point_layer_np(points, cfg):
         iny = (fy >= 0) & (np.floor(fy) < c.height)
         ing = inx & iny
         zin = ing & (c.z_min <= z) & (z <= c.z_max)
+    if mask is not None:
+        m = np.asarray(mask, bool).reshape(-1)
+        if m.shape != (len(p),):
+            raise ValueError(f"costmap: mask must be bool [{len(p)}], got {m.shape}")
+        zin = zin & ~m
     cell = np.floor(fy[ing]).astype(np.int64) * c.width + np.floor(fx[ing]).astype(np.int64)
     n = c.width * c.height
     observed = np.bincount(cell, minlength=n) > 0
@@ -223,10 +233,10 @@ def point_layer_np(points, cfg):
     return counts.reshape(c.height, c.width), observed.reshape(c.height, c.width)
 
 
-def costmap_np(points, cfg, dets=None, n_dets=None, tracks=None, n_tracks=None):
-    """One frame: (grid int8 [H, W], counts int32 [H, W])."""
+def costmap_np(points, cfg, dets=None, n_dets=None, tracks=None, n_tracks=None, mask=None):
+    """One frame: (grid int8 [H, W], counts int32 [H, W]).  mask as point_layer_np takes it."""
     c = CostmapConfig.from_any(cfg)
-    counts, observed = point_layer_np(points, c)
+    counts, observed = point_layer_np(points, c, mask)
     grid = np.where(observed, 0, -1).astype(np.int32)
     grid = np.maximum(grid, np.where(counts >= c.min_points, c.point_cost, -1))
     if c.objects:

@@ -146,6 +146,9 @@ int pp_occupancy_update_async(pp_handle e, const double* poses, int32_t batch) {
                         who, b, P[3], P[7], c.resolution);
         return (int)PP_OK;
     })) return st;
+    const unsigned long long* mask = nullptr;
+    int mask_stride = 0;
+    if (int st = object_mask_for(e, who, PP_OBJMASK_OCCUPANCY, batch, &mask, &mask_stride)) return st;
     (void)hipSetDevice(e->device);
     int slot;
     HIPCHK(e, g.ring.take(&slot));
@@ -179,6 +182,7 @@ int pp_occupancy_update_async(pp_handle e, const double* poses, int32_t batch) {
     p.logodds[0] = g.logodds[0]; p.logodds[1] = g.logodds[1];
     p.grid[0] = g.grid[0]; p.grid[1] = g.grid[1];
     p.table = g.table;
+    p.mask = mask; p.mask_stride = mask_stride;
     prof_reset(e);
     HIPCHK(e, g.h_call.send(slot, g.d_call, (size_t)batch, e->stream));
     HIPCHK(e, g.ring.sent(slot, e->stream));
@@ -248,6 +252,18 @@ int pp_occupancy_info(pp_handle e, int32_t* hits, int32_t* ground, int32_t* igno
             if (outs[k]) outs[k][b] = info[(size_t)b * PP_OCC_INFO + k];
         if (cleared) cleared[b] = g.cleared[(size_t)b];
     }
+    return PP_OK;
+}
+
+int pp_occupancy_masked(pp_handle e, int32_t* masked, int32_t batch) {
+    if (!e) return PP_ERR_ARG;
+    if (!masked) return fail(e, PP_ERR_ARG, "pp_occupancy_masked: masked is NULL");
+    pp_engine::Occupancy& g = e->occ;
+    if (int st = check_last_run(e, "pp_occupancy_masked", g.marks ? g.batch : 0, batch, true,
+                                "no update has run (pp_occupancy_update_async first)", "update", "streams")) return st;
+    (void)hipSetDevice(e->device);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    HIPCHK(e, hipMemcpy2D(masked, sizeof(int), g.info + 6, PP_OCC_INFO * sizeof(int), sizeof(int), (size_t)batch, hipMemcpyDeviceToHost));
     return PP_OK;
 }
 

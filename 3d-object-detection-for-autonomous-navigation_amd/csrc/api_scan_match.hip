@@ -139,6 +139,9 @@ int pp_scan_match_async(pp_handle e, const double* poses, int32_t batch) {
     const pp_occupancy_config& c = o.cfg;
     if (int st = check_poses(e, who, poses, nullptr, batch, [&](int b, const double* P) { return check_translation(e, who, b, P, c.resolution); }))
         return st;
+    const unsigned long long* mask = nullptr;
+    int mask_stride = 0;
+    if (int st = object_mask_for(e, who, PP_OBJMASK_SCAN_MATCH, batch, &mask, &mask_stride)) return st;
     (void)hipSetDevice(e->device);
     // the buffers shaped by the occupancy window: re-made where pp_set_occupancy changed it since they were made
     const int list_cap = (int)std::min<long long>((long long)c.width * c.height, (long long)e->NMAX);
@@ -173,6 +176,7 @@ int pp_scan_match_async(pp_handle e, const double* poses, int32_t batch) {
     p.logodds[0] = o.logodds[0]; p.logodds[1] = o.logodds[1];
     p.info = (int*)g.clear; p.marks = g.clear + (size_t)e->B * SCAN_INFO; p.list = g.list;
     p.scores = g.scores; p.partial = g.partial; p.words = g.words;
+    p.mask = mask; p.mask_stride = mask_stride;
     prof_reset(e);
     HIPCHK(e, g.h_call.send(slot, g.d_call, (size_t)batch, e->stream));
     HIPCHK(e, g.ring.sent(slot, e->stream));

@@ -5,6 +5,8 @@
 //   k_costmap_compose   a lane per four cells of a row: point layer, footprints (through LDS, box test first), one store
 // All cell arithmetic is float64 with + - * / and comparisons (-ffp-contract=off keeps the products and sums apart); the
 // only transcendental calls are the cos and sin of a footprint's yaw.
+// OBJECT MASK (CostmapParams::mask, NULL while no mask is in force): an in-grid row whose bit is set in the wave's word
+// marks its cell observed and adds no count, as a row outside the z band does.
 #include "pp_common.h"
 
 namespace {
@@ -110,15 +112,16 @@ __global__ __launch_bounds__(CM_BLOCK) void k_costmap_points(CostmapParams p) {
     if ((int)blockIdx.x * CM_BLOCK >= n) return;           // (the whole workgroup)
     const int i = blockIdx.x * CM_BLOCK + tid;
     int key = -1;
-    bool zin = false;
+    bool zin = false, masked = false;
     if (i < n) {
+        if (p.mask) masked = ((p.mask[(size_t)b * p.mask_stride + (i >> 6)] >> lane) & 1ull) != 0ull;   // one word per wave: rows 64 k .. 64 k + 63 of the frame
         const float* r = p.points + (size_t)(o0 + i) * p.F;
         const double x = (double)r[0], y = (double)r[1], z = (double)r[2];
         const double fx = (x - c.x_min) / c.resolution, fy = (y - c.y_min) / c.resolution;
         // fx >= 0 and floor(fx) < width, the latter as fx < width (the same set, and no integer conversion of a huge value)
         if (fx >= 0.0 && fx < (double)c.width && fy >= 0.0 && fy < (double)c.height) {
             key = (int)fy * p.pitch + (int)fx;
-            zin = c.z_min <= z && z <= c.z_max;
+            zin = c.z_min <= z && z <= c.z_max && !masked;  // a masked row marks its cell observed and adds no count
         }
     }
     // lanes of a run of equal cells (depth-camera rows land in neighbouring cells in runs) add once, through the run's

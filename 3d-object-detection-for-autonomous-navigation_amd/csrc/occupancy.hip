@@ -11,11 +11,15 @@
 // it), the walks' marks plain stores of one and the same byte -- a walk then waits for no memory round trip (the same
 // walks through test-then-atomicOr on the words took 5 - 10 times as long).  The only floating-point work is the endpoint transform (float64, + * / and floor;
 // -ffp-contract=off keeps products and sums apart); there is no floating-point atomic and no transcendental call.
+// OBJECT MASK (OccParams::mask, NULL while no mask is in force): a row of the hit band whose bit is set in the wave's word
+// is a MASKED end -- a third mark bit, so its cell is listed and gets its ray like any end cell, while k_occ_apply, which
+// reads HIT and GROUND alone, neither hits nor frees it.  A wave covers rows 64 k .. 64 k + 63 of a frame: one word.
 #include "pp_common.h"
 
 namespace {
 
 constexpr int OCC_BLOCK = 256;
+static_assert(PP_OCC_HIT == 1u && PP_OCC_GROUND == 2u && PP_OCC_MASKED == 4u, "k_occ_endpoints: the mark bit of kind k is 1 << k");
 static_assert(sizeof(OccCall) == 96, "OccCall: 8 doubles, 8 int32 (api_occupancy.hip fills a pinned ring of them)");
 
 __global__ __launch_bounds__(OCC_BLOCK) void k_occ_endpoints(OccParams p) {
@@ -25,8 +29,10 @@ __global__ __launch_bounds__(OCC_BLOCK) void k_occ_endpoints(OccParams p) {
     if ((int)blockIdx.x * OCC_BLOCK >= n) return;          // (the whole workgroup)
     const int i = blockIdx.x * OCC_BLOCK + tid;
     const bool row = i < n;
-    int code = -1;                                         // cell * 2 + (ground ? 1 : 0) of a used row
+    int code = -1;                                         // cell * 4 + kind of a used row: 0 hit, 1 ground, 2 masked end
+    bool masked = false;
     if (row) {
+        if (p.mask) masked = ((p.mask[(size_t)b * p.mask_stride + (i >> 6)] >> lane) & 1ull) != 0ull;   // one word per wave: rows 64 k .. 64 k + 63 of the frame
         const OccCall& q = p.call[b];
         const float* r = p.points + (size_t)(o0 + i) * p.F;
         const double x = (double)r[0], y = (double)r[1], z = (double)r[2];
@@ -36,21 +42,21 @@ __global__ __launch_bounds__(OCC_BLOCK) void k_occ_endpoints(OccParams p) {
         const double gx = floor(px / c.resolution) - (double)q.ox, gy = floor(py / c.resolution) - (double)q.oy;
         const bool used = gx >= 0.0 && gx < (double)c.width && gy >= 0.0 && gy < (double)c.height &&
                           (x * x + y * y) <= c.max_range * c.max_range && z <= c.z_max;
-        if (used) code = ((int)gy * p.pitch + (int)gx) * 2 + (z >= c.z_min ? 0 : 1);
+        if (used) code = ((int)gy * p.pitch + (int)gx) * 4 + (z >= c.z_min ? (masked ? 2 : 0) : 1);
     }
     // lanes of a run of equal codes (depth-camera rows end in neighbouring cells in runs) mark once, through the run's
     // first lane; every lane of the wave takes part in the shuffle and the ballots
     const int prev = __shfl_up(code, 1);
     const bool head = lane == 0 || code != prev;
-    const unsigned long long hit = __ballot(code >= 0 && !(code & 1)), gnd = __ballot(code >= 0 && (code & 1)),
-                             ign = __ballot(row && code < 0);
+    const unsigned long long hit = __ballot(code >= 0 && (code & 3) == 0), gnd = __ballot(code >= 0 && (code & 3) == 1),
+                             msk = __ballot(code >= 0 && (code & 3) == 2), ign = __ballot(row && code < 0);
     if (head && code >= 0) {
-        const int cell = code >> 1;
-        const unsigned bits = (code & 1) ? PP_OCC_GROUND : PP_OCC_HIT;
+        const int cell = code >> 2;
+        const unsigned bits = 1u << (code & 3);            // PP_OCC_HIT, PP_OCC_GROUND, PP_OCC_MASKED
         unsigned* w = p.marks + (size_t)b * c.height * p.pitch + cell;
         if ((*w & bits) != bits) {
             const unsigned old = atomicOr(w, bits);
-            if (!(old & (PP_OCC_HIT | PP_OCC_GROUND))) {   // the first endpoint of this cell: its one ray
+            if (!(old & (PP_OCC_HIT | PP_OCC_GROUND | PP_OCC_MASKED))) {   // the first endpoint of this cell: its one ray
                 const int k = atomicAdd(p.info + (size_t)b * PP_OCC_INFO + 5, 1);
                 if (k < p.list_cap) p.list[(size_t)b * p.list_cap + k] = cell;
             }
@@ -61,6 +67,7 @@ __global__ __launch_bounds__(OCC_BLOCK) void k_occ_endpoints(OccParams p) {
         if (hit) atomicAdd(info + 0, __popcll(hit));
         if (gnd) atomicAdd(info + 1, __popcll(gnd));
         if (ign) atomicAdd(info + 2, __popcll(ign));
+        if (msk) atomicAdd(info + 6, __popcll(msk));
     }
 }
 

@@ -714,6 +714,8 @@ struct CostmapParams {
     unsigned* words;               // [batch][height * pitch]: bits 0..30 the count, bit 31 observed without a count
     int8_t* grid;                  // [batch][height * pitch]
     int* tap;                      // [batch][height * pitch] the counts
+    const unsigned long long* mask;    // the object mask's words [batch][mask_stride], or NULL: no row is masked
+    int mask_stride;
 };
 void launch_costmap(const CostmapParams& p, hipStream_t s);
 
@@ -730,7 +732,8 @@ struct OccCall {
 };
 #define PP_OCC_HIT 1u              // mark bits of an end cell of a frame
 #define PP_OCC_GROUND 2u
-#define PP_OCC_INFO 8              // int32 per stream: hits, ground, ignored, cells_hit, cells_free, listed cells, 2 spare
+#define PP_OCC_MASKED 4u           // ... of a row in the hit band that the object mask names: the cell's ray, and no hit
+#define PP_OCC_INFO 8              // int32 per stream: hits, ground, ignored, cells_hit, cells_free, listed cells, masked rows, 1 spare
 struct OccParams {
     pp_occupancy_config cfg;
     int batch, F;
@@ -747,6 +750,8 @@ struct OccParams {
     int16_t* logodds[2];           // [B][height * pitch] each: the two state copies
     int8_t* grid[2];               // [B][height * pitch] each; -1 is also the state's "not known"
     const int8_t* table;           // [l_max - l_min + 1]
+    const unsigned long long* mask;    // the object mask's words [batch][mask_stride], or NULL: no row is masked
+    int mask_stride;
 };
 void launch_occupancy(const OccParams& p, hipStream_t s);
 
@@ -899,8 +904,46 @@ struct ScanParams {
     int* scores;                   // [batch][candidates]
     unsigned long long* partial;   // [batch][(2 nt + 1) * tiles]: a workgroup's least key
     int* words;                    // [batch][PP_SCAN_RESULT]
+    const unsigned long long* mask;    // the object mask's words [batch][mask_stride], or NULL: no row is masked
+    int mask_stride;
 };
 void launch_scan_match(const ScanParams& p, hipStream_t s);         // info and marks cleared before it
+
+// object_mask.hip: per resident row, "this return lies in the BEV rectangle of an object" (pp_set_object_mask,
+// pp_object_mask_points; object_mask.py states the rule).  One footprint of a frame's table, with a conservative float32
+// box for the rows' pretest: 64 bytes, read by every lane of a wave at one LDS address (a broadcast)
+struct OmFootprint {
+    double ox, oy, c, s, hx, hy;
+    float xlo, xhi, ylo, yhi;      // no row outside the box lies in the rectangle (an empty box: xlo > xhi)
+};
+struct OmCall {                    // what travels from the host per stream and call: 14 doubles, 2 int32
+    double m[12];                  // the pose [R | t] the slots' copies are carried into
+    double psi;                    // atan2(R10, R00), from the host
+    double dt;                     // seconds the copies are predicted by
+    int has_pose, has_dt;
+};
+enum { OM_DETECTIONS = 1, OM_TRACKS = 2, OM_GIVEN = 3 };      // OmParams::objects (1, 2: pp_object_mask_config's)
+struct OmParams {
+    pp_object_mask_config cfg;     // (OM_GIVEN reads pad alone)
+    int objects;
+    int batch, F;
+    int max_n;                     // the host's bound on the rows of a frame
+    const float* points;           // the resident rows [.][F]
+    const int* offsets;            // [batch + 1] device values
+    const pp_detection* dets;      // OM_DETECTIONS: [batch][det_rows]
+    const int* n_dets;             // [batch], PP_NDETS_NONFINITE: the frame takes no objects
+    int det_rows;
+    const TrkSlot* slots;          // OM_TRACKS: [B][PP_TRACK_MAX], read and never written
+    const TrkPose* pose_prev;      // [B] the tracker's record of the stream's last posed step
+    const OmCall* call;            // [batch], or NULL: the slots as they stand
+    const double* given;           // OM_GIVEN: [.][5] x y w l yaw, frame b's rows from given_off[b]
+    const int* given_off;          // [batch + 1]
+    OmFootprint* table;            // [batch][PP_OBJMASK_MAX_FOOTPRINTS], compacted in source order
+    int* info;                     // [batch][PP_OBJMASK_INFO]
+    unsigned long long* words;     // [batch][stride]; every run writes words 0 .. 4 * ceil(max_n / 256) - 1 of a frame
+    int stride;
+};
+void launch_object_mask(const OmParams& p, hipStream_t s);
 
 // frontier.hip: int8 OccupancyGrids -> the clusters of their frontier cells, ranked (pp_set_frontier, pp_frontier_grids;
 // frontier.py states the rule)

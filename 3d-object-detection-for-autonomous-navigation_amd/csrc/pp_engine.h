@@ -6,7 +6,7 @@
 // api_metrics.hip: the training metrics' counts; api_publish.hip: a trainer's weights into the detector, on the device;
 // api_track.hip: the per-stream track tables behind the detector's post-process; api_sweeps.hip: the per-stream sweep rings
 // in front of the pass; api_costmap.hip: the obstacle grid per frame behind it; api_occupancy.hip: the rolling occupancy
-// map per stream; api_inflate.hip: obstacle inflation behind either grid; api_navfn.hip: the navigation function over the inflated grid; api_local_plan.hip: the local planner over that grid and its field.  pp_ring.h: the pinned call ring and the stages' memory owner, which the handle's members are made of.
+// map per stream; api_inflate.hip: obstacle inflation behind either grid; api_navfn.hip: the navigation function over the inflated grid; api_local_plan.hip: the local planner over that grid and its field; api_object_mask.hip: the per-point object mask in front of the three readers of the resident rows.  pp_ring.h: the pinned call ring and the stages' memory owner, which the handle's members are made of.
 #pragma once
 
 #include <cmath>
@@ -557,6 +557,25 @@ struct pp_engine {
         unsigned long long nav_run = 0;    // navfn[source].run_id it was queued behind (use_field)
         int nav_rounds = 0;                // navfn[source].rounds its last select was queued behind
     } frontier[2];                         // by source, as infl
+
+    // pp_set_object_mask: a bit per resident row, "this return lies in the BEV rectangle of a detection / a track"
+    // (api_object_mask.hip).  Two plain launches on the handle's stream; the three readers of the rows (occupancy update,
+    // scan match, costmap points) take its words through object_mask_for while they are named in cfg.consumers.  Nothing
+    // of it in PostRule, DetectKey or a captured pass.
+    struct ObjMask {
+        bool on = false;                   // pp_set_object_mask gave a configuration and has not taken it back
+        pp_object_mask_config cfg = {};    // the last configuration given
+        OmFootprint* table = nullptr;      // [B][PP_OBJMASK_MAX_FOOTPRINTS]; this and the next three live as long as the handle (`allocs`)
+        int* info = nullptr;               // [B][PP_OBJMASK_INFO]
+        unsigned long long* words = nullptr;       // [B][stride]
+        OmCall* d_call = nullptr;          // [B]
+        int stride = 0;                    // 4 * ceil(NMAX / 256): a word per wave of k_objmask_rows' largest grid
+        CallRing ring;                     // the calls' poses and dt values, consumed on the main stream
+        RingArray<OmCall> h_call;          // [B] per slot
+        int batch = 0;                     // frames of the last run (pp_get_object_mask; 0: none, or made stale by a new configuration)
+        int run_words = 0;                 // ... ceil(max_n / 64) of it
+        unsigned long long gen = 0;        // ... and the resident_gen it belongs to
+    } omask;
     unsigned long long resident_gen = 0;   // counts the changes of the resident frames (set_resident, a stage call)
     unsigned long long results_gen = 0;    // resident_gen of the last pp_detect_async
 
@@ -730,6 +749,7 @@ void local_plan_release(pp_engine* e);                  // api_local_plan.hip: w
 int check_navfn_run(pp_engine* e, const char* who, int source);
 void frontier_release(pp_engine* e);                    // api_frontier.hip: what pp_destroy frees of the frontier stage
 void scan_match_release(pp_engine* e);                  // api_scan_match.hip: what pp_destroy frees of the scan match
+void object_mask_release(pp_engine* e);                 // api_object_mask.hip: what pp_destroy frees of the object mask
 int ensure_metrics(pp_engine* e);                       // api_metrics.hip
 void fill_metrics_params(pp_engine* e, int batch, MetricsParams& p);   // ... on the handle's head map and loss.labels
 // ---- api_dataprep.hip: what the fused training steps (api_train.hip) queue ----
@@ -767,6 +787,18 @@ inline int check_last_run(pp_engine* e, const char* who, int last_batch, int bat
     if (!while_training && e->train_pending) return fail(e, PP_ERR_STATE, "%s: a training step is in flight", who);
     if (last_batch < 1) return fail(e, PP_ERR_STATE, "%s: %s", who, none);
     if (batch != last_batch) return fail(e, PP_ERR_ARG, "%s: the last %s had %d %s, batch is %d", who, run, last_batch, unit, batch);
+    return PP_OK;
+}
+// What a reader of the resident rows (`bit`: its PP_OBJMASK_* name) asks before it takes a ring slot or queues anything:
+// *words stays NULL while the object mask is off or does not name the reader; a named reader without a mask of the
+// resident frames is refused -- it never runs unmasked silently
+inline int object_mask_for(pp_engine* e, const char* who, int bit, int batch, const unsigned long long** words, int* stride) {
+    const pp_engine::ObjMask& g = e->omask;
+    *words = nullptr; *stride = 0;
+    if (!g.on || !(g.cfg.consumers & bit)) return PP_OK;
+    if (g.batch != batch || g.gen != e->resident_gen)
+        return fail(e, PP_ERR_STATE, "%s: the object mask names this stage and holds no mask of the resident frames (pp_object_mask_async first)", who);
+    *words = g.words; *stride = g.stride;
     return PP_OK;
 }
 // both streams idle: nothing queued reads a stage's tables any more

@@ -19,6 +19,8 @@
 // WIDTHS.  ux, uy, sx, the shifts and the rotated cell stay inside int32 (scan_match.py asserts the bound from width *
 // height <= 2^20); the rotation's products C * ux reach 2^14 * 2^30 and are formed in int64; |score| <= 2^20 cells * 1000
 // < 2^30 fits int32.  The log-odds are read with no `known` test: the occupancy state holds 0 wherever a cell is not known.
+// OBJECT MASK (ScanParams::mask, NULL while no mask is in force): a row whose bit is set in the wave's word takes no part
+// and is counted with the ignored rows.
 // BOUNDS.  A lookup outside the window reads cell 0 of the stream and adds 0, so every load lies in the stream's map; the
 // list is written below list_cap only and read below min(count, list_cap); a mark word lies below mark_words because the
 // cell passed the window test.
@@ -53,7 +55,9 @@ __global__ __launch_bounds__(SCAN_ROWS) void k_scan_cells(ScanParams p) {
     const int i = blockIdx.x * SCAN_ROWS + tid;
     const bool row = i < n;
     int cell = -1;                                         // gy * width + gx of a used row
+    bool masked = false;
     if (row) {
+        if (p.mask) masked = ((p.mask[(size_t)b * p.mask_stride + (i >> 6)] >> lane) & 1ull) != 0ull;   // one word per wave: rows 64 k .. 64 k + 63 of the frame
         const ScanCall& q = p.call[b];
         const float* r = p.points + (size_t)(o0 + i) * p.F;
         const double x = (double)r[0], y = (double)r[1], z = (double)r[2];
@@ -63,7 +67,7 @@ __global__ __launch_bounds__(SCAN_ROWS) void k_scan_cells(ScanParams p) {
         const double gx = floor(dx / c.resolution) + (double)(c.width / 2), gy = floor(dy / c.resolution) + (double)(c.height / 2);
         const bool used = gx >= 0.0 && gx < (double)c.width && gy >= 0.0 && gy < (double)c.height &&
                           (x * x + y * y) <= c.max_range * c.max_range && z <= c.z_max && z >= c.z_min;
-        if (used) cell = (int)gy * c.width + (int)gx;
+        if (used && !masked) cell = (int)gy * c.width + (int)gx;          // a masked row takes no part: ignored
     }
     // lanes of a run of equal cells mark once, through the run's first lane; every lane of the wave takes part in the
     // shuffle and the ballots

@@ -23,6 +23,7 @@ from . import navfn as _nav
 from . import local_planner as _loc
 from . import scan_match as _scan
 from . import frontier as _fr
+from . import object_mask as _om
 from .anchors import build_anchor_cells, build_anchors
 from .config import Derived
 from .weights import check_weights
@@ -1187,11 +1188,15 @@ class Engine:
         self._check(self._lib.pp_get_occupancy(self._h, _ptr(grid), _ptr(lo), _ptr(org), B), "pp_get_occupancy")
         return (grid[:B], org[:B], lo[:B]) if logodds else (grid[:B], org[:B])
 
-    def occupancy_info(self):
+    def occupancy_info(self, masked=False):
         """Per frame of the last occupancy update (waits for it), int32 [B] each: rows `hits`, `ground`, `ignored`;
-        `cells_hit`, `cells_free` (passed and not hit); `cleared`, the cells of the new window the old one did not hold."""
+        `cells_hit`, `cells_free` (passed and not hit); `cleared`, the cells of the new window the old one did not hold.
+        masked=True: a seventh key, `masked`, the rows the object mask turned from hits into masked ends."""
         keys = ("hits", "ground", "ignored", "cells_hit", "cells_free", "cleared")
-        return self._stage_info("pp_occupancy_info", keys, getattr(self, "_occ_batch", 0))
+        info = self._stage_info("pp_occupancy_info", keys, getattr(self, "_occ_batch", 0))
+        if masked:
+            info.update(self._stage_info("pp_occupancy_masked", ("masked",), getattr(self, "_occ_batch", 0)))
+        return info
 
     def occupancy_reset(self, stream=None):
         """Forgets the map of `stream` (None: of all streams): its next update starts from an unknown window."""
@@ -1267,6 +1272,54 @@ class Engine:
         corrected = self._scan_correct(words)
         self.occupancy_update_async(corrected)
         return corrected, words
+
+    # ---- per-point object mask in front of the three readers of the rows (pp_set_object_mask, pp_object_mask_async, pp_get_object_mask; object_mask.py states the rule) ----
+    def set_object_mask(self, cfg):
+        """An object_mask.ObjectMaskConfig, a dict of its fields or True (the defaults): `object_mask_async()` then marks
+        every resident row that lies in the BEV rectangle of a detection of the last pass or of a live track, on the GPU,
+        and the stages named in `consumers` -- occupancy_update_async, scan_match_async (so localize), costmap_async --
+        leave those rows out as object_mask.py states.  A named stage refuses to run without a mask of the resident
+        frames.  None: off (the default), and every launch, buffer and result of the other stages is what it was."""
+        pc = None if cfg is None or cfg is False else ctypes.byref(_to_struct(_lib.PPObjectMaskConfig, _om.ObjectMaskConfig.from_any(cfg)))
+        self._check(self._lib.pp_set_object_mask(self._h, pc), "pp_set_object_mask")
+
+    @property
+    def object_mask_config(self):
+        """The ObjectMaskConfig in force, or None while the stage is off."""
+        on, pc = self._stage_config("pp_get_object_mask_config", _lib.PPObjectMaskConfig)
+        return _from_struct(_om.ObjectMaskConfig, pc) if on else None
+
+    def object_mask_async(self, poses=None, dt=None):
+        """Queues the mask of the resident frames behind whatever the engine's stream holds (pp_object_mask_async) and
+        returns at once.  objects = "tracks" reads the streams' tracks as the last step left them; poses [B, 3, 4] float64
+        (the sensor-to-fixed transforms of the resident frames) and dt [B] seconds bring a copy of them to now -- carried
+        as the tracker's next posed step would carry them, then predicted -- which is what lets the mask run in front of
+        localize, before the pass of the current frame.  The tracker itself is not touched."""
+        B = self._batches()[0]
+        P = None
+        if poses is not None:
+            P = np.ascontiguousarray(poses, np.float64)
+            if P.ndim != 3 or P.shape != (B, 3, 4):
+                raise ValueError(f"object_mask_async: poses must be [{B}, 3, 4] (one per resident frame), got {P.shape}")
+        t = None
+        if dt is not None:
+            t = np.ascontiguousarray(dt, np.float64).reshape(-1)
+            if t.shape[0] != B:
+                raise ValueError(f"object_mask_async: {t.shape[0]} dt values for {B} resident frames")
+        self._check(self._lib.pp_object_mask_async(self._h, _ptr(P), _ptr(t), B), "pp_object_mask_async")
+
+    def object_mask(self, batch=None):
+        """(masks, info) of the last object_mask_async (waits for it): masks a list of B bool arrays, one flag per row of
+        the frame; info a dict of int32 [B] each: `footprints`, `masked` rows, `rows`, `flagged`.  Raises when none has
+        run, or when the frames it belongs to have been replaced since."""
+        nb, wpf = ctypes.c_int32(0), ctypes.c_int32(0)
+        self._check(self._lib.pp_object_mask_shape(self._h, ctypes.byref(nb), ctypes.byref(wpf)), "pp_object_mask_shape")
+        B = int(batch) if batch is not None else int(nb.value)
+        words = np.zeros((max(B, 1), max(int(wpf.value), 1)), np.uint64)
+        info = np.zeros((max(B, 1), _lib.PP_OBJMASK_INFO), np.int32)
+        self._check(self._lib.pp_get_object_mask(self._h, _ptr(words), _ptr(info), B), "pp_get_object_mask")
+        masks = [_om.unpack_words(words[b], info[b, 2]) for b in range(B)]
+        return masks, {k: info[:B, i].copy() for i, k in enumerate(_om.INFO)}
 
     # ---- obstacle inflation behind either grid (pp_set_inflation, pp_inflate_async, pp_get_inflated; inflation.py states the rule; DESIGN 7.1y) ----
     @staticmethod

@@ -44,7 +44,13 @@ the carried rows of past sweeps too, which would cast rays from the CURRENT sens
 between the upload or ingest and the accumulation.
 
 Inflation is a stage of its own behind the published grid (inflation.py, Engine.set_inflation / inflated_occupancy_maps);
-it never feeds back into the log-odds.  Out of scope: decay over time, 3D voxels, removing tracked objects' points, clipping rays that leave the window
+it never feeds back into the log-odds.  OBJECT MASK (object_mask.py; update(..., mask=)): a used row with z >= z_min whose mask bit is set is a MASKED end on
+its cell, not a hit.  Every cell with a hit, ground or masked end still gets its one ray; a cell whose only ends are
+masked is neither hit nor passed by its own ray (another ray may pass it), and a hit from an unmasked row in the same
+cell still wins.  The free space in front of an object is kept, the object itself leaves nothing.  Without a mask the
+rule is what it was.
+
+Out of scope: decay over time, 3D voxels, clipping rays that leave the window
 (rows that end outside it are ignored, and counted), any ROS import.
 """
 import dataclasses
@@ -178,9 +184,11 @@ def window_origin(cfg, pose):
     return tuple(out)
 
 
-def end_cells(cfg, points, pose, origin_cell):
+def end_cells(cfg, points, pose, origin_cell, mask=None):
     """Step 2 for one frame: (hit bool [H, W], ground bool [H, W], (rows that hit, ground rows, ignored rows)) of rows
-    float32 [n, F >= 3] under pose [3, 4] in the window whose origin cell is `origin_cell`."""
+    float32 [n, F >= 3] under pose [3, 4] in the window whose origin cell is `origin_cell`.  With mask bool [n] (the
+    object mask of the rows): (hit, ground, masked-end bool [H, W], (rows that hit, ground rows, ignored rows, masked
+    rows)) -- a masked row of the hit band is a masked end and no hit."""
     c = OccupancyConfig.from_any(cfg)
     p, P = np.asarray(points), np.asarray(pose, np.float64)
     W, H = c.width, c.height
@@ -195,10 +203,20 @@ def end_cells(cfg, points, pose, origin_cell):
                 & (z <= c.z_max))
         is_hit = used & (z >= c.z_min)
     is_ground = used & ~is_hit
+    if mask is not None:
+        m = np.asarray(mask, bool).reshape(-1)
+        if m.shape != (len(p),):
+            raise ValueError(f"occupancy: mask must be bool [{len(p)}], got {m.shape}")
+        is_masked = is_hit & m
+        is_hit = is_hit & ~m
+        masked = np.zeros((H, W), bool)
+        masked[gy[is_masked].astype(np.int64), gx[is_masked].astype(np.int64)] = True
     hit = np.zeros((H, W), bool)
     ground = np.zeros((H, W), bool)
     hit[gy[is_hit].astype(np.int64), gx[is_hit].astype(np.int64)] = True
     ground[gy[is_ground].astype(np.int64), gx[is_ground].astype(np.int64)] = True
+    if mask is not None:
+        return hit, ground, masked, (int(is_hit.sum()), int(is_ground.sum()), int(len(p) - used.sum()), int(is_masked.sum()))
     return hit, ground, (int(is_hit.sum()), int(is_ground.sum()), int(len(p) - used.sum()))
 
 
@@ -272,9 +290,10 @@ class OccupancyMap:
         self._L, self._known, self.origin_cell = L, known, new
         return W * H - kept
 
-    def update(self, points, pose):
+    def update(self, points, pose, mask=None):
         """One frame.  Returns the info dict: rows `hits`, `ground`, `ignored`; `cells_hit`, `cells_free` (passed and not
-        hit); `cleared`, the cells of the new window the old one did not hold (all of them at the first update)."""
+        hit); `cleared`, the cells of the new window the old one did not hold (all of them at the first update).  mask:
+        bool [n], the rows' object mask (object_mask.py) -- the dict then also counts the `masked` rows."""
         c = self.cfg
         p = np.asarray(points)
         if p.dtype != np.float32 or p.ndim != 2 or p.shape[1] < 3:
@@ -282,14 +301,22 @@ class OccupancyMap:
         P = _swp.check_poses(np.asarray(pose, np.float64)[None], 1)[0]
         W, H = c.width, c.height
         cleared = self._move_window(window_origin(c, P))
-        hit, ground, rows = end_cells(c, p, P, self.origin_cell)
-        ey, ex = np.nonzero(hit | ground)
+        if mask is None:
+            hit, ground, rows = end_cells(c, p, P, self.origin_cell)
+            ends = hit | ground
+        else:
+            hit, ground, masked, rows = end_cells(c, p, P, self.origin_cell, mask)
+            ends = hit | ground | masked
+        ey, ex = np.nonzero(ends)
         passed = _passed_by_rays(ex, ey, W // 2, H // 2, (H, W)) | ground
         delta = np.where(hit, c.l_hit, np.where(passed, -c.l_miss, 0)).astype(np.int32)
         self._L = np.clip(self._L.astype(np.int32) + delta, c.l_min, c.l_max).astype(np.int16)
         self._known |= hit | passed
-        return {"hits": rows[0], "ground": rows[1], "ignored": rows[2],
+        info = {"hits": rows[0], "ground": rows[1], "ignored": rows[2],
                 "cells_hit": int(hit.sum()), "cells_free": int((passed & ~hit).sum()), "cleared": int(cleared)}
+        if mask is not None:
+            info["masked"] = rows[3]
+        return info
 
 
 def to_occupancy_grid(grid, origin, cfg, stamp=None, frame_id=""):

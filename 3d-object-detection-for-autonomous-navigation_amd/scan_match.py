@@ -48,8 +48,13 @@ The stage relies on one property of the occupancy state: L = 0 wherever a cell i
 cell starts as L = 0, unknown, and only a hit or a pass, which make it known, change L), so the device adds L alone.  The
 restatement writes the `known` test out; `scan_match_grids` zeroes L where not known before it uploads.
 
+OBJECT MASK (object_mask.py; scan_cells_np / match_np(..., mask=)): a row whose mask bit is set takes no part in step 1
+and is counted with the ignored rows, so a person close to the sensor contributes no scan cell.  Without a mask the rule
+is what it was.
+
 Out of scope: multi-resolution branch and bound, sub-cell refinement, a covariance from the score volume, loop closure,
-removing tracked objects' points from the scan, any correction of roll, pitch or z.
+any correction of roll, pitch or z.  (No longer in that list: removing tracked objects' points from the scan, which is
+the object mask above, a stage of its own in front of this one.)
 """
 import ctypes
 import dataclasses
@@ -131,9 +136,10 @@ class ScanMatchConfig:
         raise ValueError(f"scan_match: a ScanMatchConfig, a dict of its fields or True, got {cfg!r}")
 
 
-def scan_cells_np(occ_cfg, points, pose):
+def scan_cells_np(occ_cfg, points, pose, mask=None):
     """Step 1 for one frame: (cells int64 [n_scan, 2] = (ux, uy) in ascending (gy, gx), (rows used, rows ignored,
-    n_scan)) of rows float32 [n, F >= 3] under the rotation of pose [3, 4]."""
+    n_scan)) of rows float32 [n, F >= 3] under the rotation of pose [3, 4].  mask: bool [n], the rows' object mask
+    (object_mask.py) -- a masked row takes no part and is counted with the ignored rows."""
     c = _occ.OccupancyConfig.from_any(occ_cfg)
     p, P = np.asarray(points), np.asarray(pose, np.float64)
     if p.dtype != np.float32 or p.ndim != 2 or p.shape[1] < 3:
@@ -147,6 +153,11 @@ def scan_cells_np(occ_cfg, points, pose):
         gy = np.floor(dy / c.resolution) + float(H // 2)
         used = ((gx >= 0) & (gx < W) & (gy >= 0) & (gy < H) & ((x * x + y * y) <= c.max_range * c.max_range)
                 & (z <= c.z_max) & (z >= c.z_min))
+    if mask is not None:
+        m = np.asarray(mask, bool).reshape(-1)
+        if m.shape != (len(p),):
+            raise ValueError(f"scan_match: mask must be bool [{len(p)}], got {m.shape}")
+        used = used & ~m
     flat = np.unique(gy[used].astype(np.int64) * W + gx[used].astype(np.int64))
     cells = np.stack([(flat % W - W // 2) * SUB + SUB // 2, (flat // W - H // 2) * SUB + SUB // 2], axis=1)
     return cells.astype(np.int64), (int(used.sum()), int(len(p) - used.sum()), int(len(flat)))
@@ -232,16 +243,16 @@ def best_np(scores, cfg, n_scan, ignored, status=0):
     return np.array([status, ddx, ddy, ddt, best, int(s[centre]), int(n_scan), int(ignored)], np.int32)
 
 
-def match_grid_np(occ_cfg, logodds, known, origin_cell, points, pose, cfg):
+def match_grid_np(occ_cfg, logodds, known, origin_cell, points, pose, cfg, mask=None):
     """Steps 1 .. 4 on a map given as arrays: logodds int16 [H, W], known bool [H, W], origin_cell (ox, oy) or None (no
-    map) -> (words int32 [8], scores int64 [candidates])."""
+    map) -> (words int32 [8], scores int64 [candidates]).  mask as scan_cells_np takes it."""
     oc = _occ.OccupancyConfig.from_any(occ_cfg)
     cfg = ScanMatchConfig.from_any(cfg)
     L, K = np.asarray(logodds), np.asarray(known, bool)
     if L.shape != (oc.height, oc.width) or K.shape != L.shape:
         raise ValueError(f"scan_match: logodds and known must be [{oc.height}, {oc.width}], got {L.shape} and {K.shape}")
     P = _swp.check_poses(np.asarray(pose, np.float64)[None], 1)[0]
-    cells, (_, ignored, n_scan) = scan_cells_np(oc, points, P)
+    cells, (_, ignored, n_scan) = scan_cells_np(oc, points, P, mask)
     status, sensor = 0, (0, 0)
     if origin_cell is None:
         status = NO_MAP
@@ -253,10 +264,10 @@ def match_grid_np(occ_cfg, logodds, known, origin_cell, points, pose, cfg):
     return best_np(scores, cfg, n_scan, ignored, status), scores
 
 
-def match_np(occupancy_map, points, pose, cfg):
+def match_np(occupancy_map, points, pose, cfg, mask=None):
     """Steps 1 .. 4 against an occupancy.OccupancyMap as it stands -> (words int32 [8], scores int64 [candidates])."""
     m = occupancy_map
-    return match_grid_np(m.cfg, m._L, m._known, m.origin_cell, points, pose, cfg)
+    return match_grid_np(m.cfg, m._L, m._known, m.origin_cell, points, pose, cfg, mask)
 
 
 def corrected_pose(pose, words, occ_cfg, cfg):

@@ -78,6 +78,11 @@ class VoxelNet:
         (corrected poses [B, 3, 4], words [B, 8])."""
         return self.engine.localize(poses)
 
+    def object_mask(self, poses=None, dt=None):
+        """Engine.object_mask_async on the resident frames (engine.set_object_mask first): in front of localize with the
+        frames' poses and dt, or behind the pass without either.  Returns nothing; engine.object_mask() fetches the bits."""
+        return self.engine.object_mask_async(poses, dt)
+
     def occupancy_maps(self, batch=None, logodds=False):
         """Engine.occupancy_maps of the last occupancy_update."""
         return self.engine.occupancy_maps(batch, logodds)

@@ -73,7 +73,11 @@ extern "C" {
  * use_field the navigation function's field, where they lie).  Then PP_LOCAL_MAX_PROBES, PP_LOCAL_MAX_PROBE,
  * PP_LOCAL_FOOT_INFO, pp_local_footprint_config, pp_set_local_footprint, pp_get_local_footprint_config,
  * pp_get_local_footprint, pp_local_plan_grids_footprint (declared behind pp_local_plan_grids_movers: the footprint rides
- * in the local planner's rollout). */
+ * in the local planner's rollout).  Then PP_OBJMASK_MAX_FOOTPRINTS, PP_OBJMASK_INFO, PP_OBJMASK_OCCUPANCY,
+ * PP_OBJMASK_SCAN_MATCH, PP_OBJMASK_COSTMAP, pp_object_mask_config, pp_set_object_mask, pp_get_object_mask_config,
+ * pp_object_mask_async, pp_object_mask_shape, pp_get_object_mask, pp_occupancy_masked, pp_object_mask_points (declared
+ * behind pp_frontier_grids: the stage reads what a pass and its tracking step leave, and the three readers of the
+ * resident rows read its bits). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -1758,6 +1762,64 @@ int pp_get_frontiers(pp_handle h, int32_t source, int32_t* words, int32_t* info,
  * pp_get_frontiers gives them (each may be NULL). */
 int pp_frontier_grids(int device, const int8_t* grids, const uint32_t* pot, int32_t batch, int32_t height, int32_t width,
                       const pp_frontier_config* cfg, const int32_t* refs, int32_t* words, int32_t* info, uint32_t* labels);
+
+/* ---- Per-point object mask (object_mask.py states the rule): per resident row, one bit "this return belongs to an
+ * object" -- the row's (x, y) lies in the BEV rectangle of a detection of the last pass or of a live track, exactly the
+ * costmap's footprint test (u = (dx * c) - (dy * s), v = (dx * s) + (dy * c), |u| <= hx and |v| <= hy, float64; a NaN
+ * fails) with the row in the place of a cell's centre.  The three readers of the rows use the bit while they are named in
+ * `consumers`: the occupancy update takes a masked row in the hit band as a MASKED end (its cell still gets its one ray,
+ * and is itself neither hit nor passed by that ray), the scan match ignores it, the costmap's point layer marks its cell
+ * observed and counts nothing.  An opt-in stage: two plain launches on the handle's stream, nothing of it in a captured
+ * pass; with the stage off every launch, buffer and result of every other stage is what it was.  A mask belongs to the
+ * resident frames it was computed for: any change of them (upload, ingest, crop, sweeps) makes it stale, and a reader
+ * named in `consumers` then answers PP_ERR_STATE until pp_object_mask_async has run again. ---- */
+#define PP_OBJMASK_MAX_FOOTPRINTS 128 /* footprints of a frame: PP_TRACK_MAX slots, or the 128 detection rows the tracker admits */
+#define PP_OBJMASK_INFO 4             /* int32 per frame: footprints, masked rows, rows, flagged */
+enum { PP_OBJMASK_OCCUPANCY = 1, PP_OBJMASK_SCAN_MATCH = 2, PP_OBJMASK_COSTMAP = 4 };   /* bits of `consumers` */
+
+typedef struct pp_object_mask_config {
+    double min_score;      /* detections under it leave no footprint */
+    double min_speed;      /* m/s, >= 0: a track masks only if (vx * vx + vy * vy) >= min_speed * min_speed */
+    double pad;            /* metres added to a footprint's half extents, >= 0 */
+    int32_t objects;       /* 1 the last pass's detections, 2 the streams' tracks */
+    int32_t confirmed_only;/* tracks: only the confirmed ones */
+    int32_t consumers;     /* PP_OBJMASK_* bits: the stages that read the mask */
+    int32_t reserved;      /* 0 */
+} pp_object_mask_config;
+
+/* cfg == NULL: the stage off (the default); its buffers are kept.  Otherwise the configuration is validated (PP_ERR_ARG
+ * naming the field); a configuration other than the last makes the last mask stale.  PP_ERR_STATE while a training step
+ * is in flight. */
+int pp_set_object_mask(pp_handle h, const pp_object_mask_config* cfg);
+/* *on: 0 / 1; cfg_out (may be NULL): the last configuration given (zeros before the first). */
+int pp_get_object_mask_config(pp_handle h, int32_t* on, pp_object_mask_config* cfg_out);
+/* Queues the stage on the resident frames behind whatever the handle's stream holds: the footprint tables (one workgroup
+ * per frame), then a lane per resident row.  objects = tracks reads the streams' slots as the last step left them; poses
+ * [batch][3][4] (may be NULL) carries a COPY of every slot from the stream's last posed tracking step into the frame of
+ * the pose, exactly as that step's stage 0 would (skipped for a stream without such a step), and dt [batch] seconds
+ * (may be NULL; each finite and >= 0) then predicts the copy, x + vx * dt.  The tracker's tables are not written.
+ * Refused before anything is queued, the last mask staying as it is: PP_ERR_STATE when the stage is off, no frames are
+ * resident, a training step is in flight, objects = detections and no pass has run on the resident frames, objects =
+ * tracks before the first pp_set_tracking; PP_ERR_ARG for poses or dt under objects = detections, a batch that is not the
+ * resident one, a dt that is not finite or negative, a pose that is not finite or not orthonormal; PP_ERR_UNSUPPORTED for
+ * objects = detections with more than PP_OBJMASK_MAX_FOOTPRINTS result rows per frame. */
+int pp_object_mask_async(pp_handle h, const double* poses /* [batch][3][4] or NULL */, const double* dt /* [batch] or NULL */,
+                         int32_t batch);
+/* The shape of the last run: *words_per_frame = ceil(max_n / 64) for the longest frame's bound max_n.  Waits for nothing. */
+int pp_object_mask_shape(pp_handle h, int32_t* batch, int32_t* words_per_frame);
+/* The mask of the last pp_object_mask_async (waits for the stream): words uint64 [batch][words_per_frame], bit (i & 63)
+ * of word i >> 6 for row i of the frame, zero past the frame's rows; info int32 [batch][PP_OBJMASK_INFO].  Either may be
+ * NULL.  PP_ERR_STATE when none has run or the frames it belongs to are gone, PP_ERR_ARG when batch is not that run's. */
+int pp_get_object_mask(pp_handle h, uint64_t* words, int32_t* info, int32_t batch);
+/* The rows of the last occupancy update that were masked ends, [batch].  Errors as pp_occupancy_info. */
+int pp_occupancy_masked(pp_handle h, int32_t* masked, int32_t batch);
+/* Without a handle: points [offsets[batch]][num_features >= 3] float32 and offsets [batch + 1] in host memory; footprints
+ * [sum counts][5] float64 = x y w l yaw, the frames' back to back, counts [batch] each 0 .. PP_OBJMASK_MAX_FOOTPRINTS;
+ * pad >= 0 -> words uint64 [batch][words_per_frame] (words_per_frame >= ceil(longest frame / 64)) and info as above
+ * (either may be NULL).  A footprint with a non-finite field covers nothing. */
+int pp_object_mask_points(int device, const float* points, const int32_t* offsets, int32_t num_features, int32_t batch,
+                          const double* footprints, const int32_t* counts, double pad, uint64_t* words,
+                          int32_t words_per_frame, int32_t* info);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
