@@ -29,6 +29,7 @@ SOURCES = ["pp_api.hip", "api_ingest.hip", "api_crop.hip", "api_eval.hip", "api_
            "api_scan_match.hip", "scan_match.hip",
            "api_frontier.hip", "frontier.hip",
            "api_object_mask.hip", "object_mask.hip",
+           "api_ground.hip", "ground.hip",
            "api_track.hip", "track.hip"]
 # -fno-slp-vectorize: keeps f32 FMAs as v_fma_f32; the SLP vectoriser's v_pk_fma_f32 is slow on a SIMD
 # that is also issuing MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
@@ -74,6 +75,7 @@ EXPORTS = [
     "pp_set_local_footprint", "pp_get_local_footprint_config", "pp_get_local_footprint", "pp_local_plan_grids_footprint",
     "pp_set_object_mask", "pp_get_object_mask_config", "pp_object_mask_async", "pp_object_mask_shape", "pp_get_object_mask",
     "pp_occupancy_masked", "pp_object_mask_points",
+    "pp_set_ground", "pp_get_ground_config", "pp_ground_async", "pp_ground_used", "pp_ground_shape", "pp_get_ground", "pp_ground_points",
     "pp_set_nms_mode", "pp_get_nms_mode", "pp_rotate_nms",
     "pp_set_projection", "pp_get_projection", "pp_get_bboxes", "pp_box3d_to_bbox",
     "pp_set_class_nms", "pp_get_class_nms", "pp_get_detection_rows",
@@ -271,6 +273,10 @@ PP_SCAN_RESULT = 8              # int32 words per stream of pp_get_scan_match's 
 PP_OBJMASK_MAX_FOOTPRINTS = 128  # footprints of a frame's object mask (pp_set_object_mask)
 PP_OBJMASK_INFO = 4              # int32 words per frame of pp_get_object_mask's info
 PP_OBJMASK_OCCUPANCY, PP_OBJMASK_SCAN_MATCH, PP_OBJMASK_COSTMAP = 1, 2, 4     # bits of pp_object_mask_config.consumers
+PP_GROUND_MAX_HYP = 512         # hypotheses of a frame's ground fit at most (pp_set_ground)
+PP_GROUND_INFO = 12             # int32 words per frame of pp_get_ground's info
+PP_GROUND_SUMS = 9              # int64 sums per frame of its refit
+PP_GROUND_OCCUPANCY, PP_GROUND_SCAN_MATCH, PP_GROUND_COSTMAP = 1, 2, 4        # bits of pp_ground_config.consumers
 PP_SCAN_NO_MAP, PP_SCAN_OUTSIDE, PP_SCAN_FEW_CELLS, PP_SCAN_LOW_SCORE, PP_SCAN_EDGE = 1, 2, 4, 8, 16      # its status bits
 PP_FRONTIER_MAX = 64            # frontiers pp_get_frontiers returns per grid at most
 PP_FRONTIER_INFO = 6            # int32 words per grid of its info: frontier_cells, clusters, small, unreached, kept, returned
@@ -431,6 +437,17 @@ class PPObjectMaskConfig(ctypes.Structure):
         ("confirmed_only", ctypes.c_int32),
         ("consumers", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
+    ]
+
+
+class PPGroundConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ("max_range", "cand_z_max", "max_slope", "h_min", "h_max", "inlier_dist", "ground_dist",
+                                               "overhead_max", "fallback_c")] + [
+        ("seed", ctypes.c_uint64),
+        ("hypotheses", ctypes.c_int32),
+        ("min_inliers", ctypes.c_int32),
+        ("refine", ctypes.c_int32),
+        ("consumers", ctypes.c_int32),
     ]
 
 
@@ -758,6 +775,13 @@ def lib():
     L.pp_get_object_mask.argtypes = [vp, vp, vp, i32]
     L.pp_occupancy_masked.argtypes = [vp, vp, i32]
     L.pp_object_mask_points.argtypes = [ctypes.c_int, vp, vp, i32, i32, vp, vp, ctypes.c_double, vp, i32, vp]
+    L.pp_set_ground.argtypes = [vp, ctypes.POINTER(PPGroundConfig)]
+    L.pp_get_ground_config.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(PPGroundConfig)]
+    L.pp_ground_async.argtypes = [vp, vp, i32]
+    L.pp_ground_used.argtypes = [vp, ctypes.POINTER(i32)]
+    L.pp_ground_shape.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.pp_get_ground.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32]
+    L.pp_ground_points.argtypes = [ctypes.c_int, vp, vp, i32, i32, ctypes.POINTER(PPGroundConfig), vp, vp, vp, vp, vp, i32, vp, vp]
     L.pp_adamw_step_clipped_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, i64, vp, i32, vp, i32,
                                                ctypes.POINTER(PPGradClipConfig), vp, ctypes.c_float, ctypes.c_float,
                                                ctypes.c_float, ctypes.c_float, ctypes.c_float]

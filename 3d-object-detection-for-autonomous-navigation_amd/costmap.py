@@ -32,6 +32,9 @@ scope: a map in the fixed frame accumulated over time (occupancy.py), ray-traced
 OBJECT MASK (object_mask.py; point_layer_np / costmap_np(..., mask=)): an in-grid row whose mask bit is set marks its cell
 OBSERVED and adds no count, as a row outside the z band does -- an object is then painted once, as its footprint, and not
 a second time as raw points.  Without a mask the rule is what it was.
+
+GROUND CLASSES (ground.py; point_layer_np / costmap_np(..., ground=)): an in-grid row marks its cell observed, as now, and
+adds to the count iff its class is OBSTACLE (and it is not object-masked), in the place of the z band.
 """
 import dataclasses
 import math
@@ -206,9 +209,9 @@ def _uv(c, f):
     return (dx * f[2]) - (dy * f[3]), (dx * f[3]) + (dy * f[2])
 
 
-def point_layer_np(points, cfg, mask=None):
+def point_layer_np(points, cfg, mask=None, ground=None):
     """(counts int32 [H, W], observed bool [H, W]) of one frame's rows [n, F >= 3] float32; mask: bool [n], the rows'
-    object mask, or None."""
+    object mask, or None; ground: the pair (ground bool [n], obstacle bool [n]) of the rows' classes (ground.py), or None."""
     c = CostmapConfig.from_any(cfg)
     p = np.asarray(points)
     if p.dtype != np.float32 or p.ndim != 2 or p.shape[1] < 3:
@@ -219,7 +222,11 @@ def point_layer_np(points, cfg, mask=None):
         inx = (fx >= 0) & (np.floor(fx) < c.width)
         iny = (fy >= 0) & (np.floor(fy) < c.height)
         ing = inx & iny
-        zin = ing & (c.z_min <= z) & (z <= c.z_max)
+        if ground is None:
+            zin = ing & (c.z_min <= z) & (z <= c.z_max)
+        else:
+            from . import ground as _gr
+            zin = ing & _gr.check_classes(ground, len(p), "costmap")[1]
     if mask is not None:
         m = np.asarray(mask, bool).reshape(-1)
         if m.shape != (len(p),):
@@ -233,10 +240,10 @@ def point_layer_np(points, cfg, mask=None):
     return counts.reshape(c.height, c.width), observed.reshape(c.height, c.width)
 
 
-def costmap_np(points, cfg, dets=None, n_dets=None, tracks=None, n_tracks=None, mask=None):
-    """One frame: (grid int8 [H, W], counts int32 [H, W]).  mask as point_layer_np takes it."""
+def costmap_np(points, cfg, dets=None, n_dets=None, tracks=None, n_tracks=None, mask=None, ground=None):
+    """One frame: (grid int8 [H, W], counts int32 [H, W]).  mask and ground as point_layer_np takes them."""
     c = CostmapConfig.from_any(cfg)
-    counts, observed = point_layer_np(points, c, mask)
+    counts, observed = point_layer_np(points, c, mask, ground)
     grid = np.where(observed, 0, -1).astype(np.int32)
     grid = np.maximum(grid, np.where(counts >= c.min_points, c.point_cost, -1))
     if c.objects:

@@ -108,6 +108,7 @@ int pp_costmap_async(pp_handle e) {
     CostmapParams p;
     memset(&p, 0, sizeof(p));
     if (int st = object_mask_for(e, "pp_costmap_async", PP_OBJMASK_COSTMAP, B, &p.mask, &p.mask_stride)) return st;
+    if (int st = ground_for(e, "pp_costmap_async", PP_GROUND_COSTMAP, B, &p.gnd, &p.obs, &p.cls_stride)) return st;
     if (int st = resident_points(e, B, e->stream, false, &p.points)) return st;
     p.cfg = c;
     p.batch = B; p.F = e->F; p.pitch = g.pitch; p.max_n = std::min(e->cur_max_n, e->NMAX);

@@ -149,6 +149,9 @@ int pp_occupancy_update_async(pp_handle e, const double* poses, int32_t batch) {
     const unsigned long long* mask = nullptr;
     int mask_stride = 0;
     if (int st = object_mask_for(e, who, PP_OBJMASK_OCCUPANCY, batch, &mask, &mask_stride)) return st;
+    const unsigned long long *cls_gnd = nullptr, *cls_obs = nullptr;
+    int cls_stride = 0;
+    if (int st = ground_for(e, who, PP_GROUND_OCCUPANCY, batch, &cls_gnd, &cls_obs, &cls_stride)) return st;
     (void)hipSetDevice(e->device);
     int slot;
     HIPCHK(e, g.ring.take(&slot));
@@ -183,6 +186,7 @@ int pp_occupancy_update_async(pp_handle e, const double* poses, int32_t batch) {
     p.grid[0] = g.grid[0]; p.grid[1] = g.grid[1];
     p.table = g.table;
     p.mask = mask; p.mask_stride = mask_stride;
+    p.gnd = cls_gnd; p.obs = cls_obs; p.cls_stride = cls_stride;
     prof_reset(e);
     HIPCHK(e, g.h_call.send(slot, g.d_call, (size_t)batch, e->stream));
     HIPCHK(e, g.ring.sent(slot, e->stream));

@@ -142,6 +142,9 @@ int pp_scan_match_async(pp_handle e, const double* poses, int32_t batch) {
     const unsigned long long* mask = nullptr;
     int mask_stride = 0;
     if (int st = object_mask_for(e, who, PP_OBJMASK_SCAN_MATCH, batch, &mask, &mask_stride)) return st;
+    const unsigned long long *cls_gnd = nullptr, *cls_obs = nullptr;
+    int cls_stride = 0;
+    if (int st = ground_for(e, who, PP_GROUND_SCAN_MATCH, batch, &cls_gnd, &cls_obs, &cls_stride)) return st;
     (void)hipSetDevice(e->device);
     // the buffers shaped by the occupancy window: re-made where pp_set_occupancy changed it since they were made
     const int list_cap = (int)std::min<long long>((long long)c.width * c.height, (long long)e->NMAX);
@@ -177,6 +180,7 @@ int pp_scan_match_async(pp_handle e, const double* poses, int32_t batch) {
     p.info = (int*)g.clear; p.marks = g.clear + (size_t)e->B * SCAN_INFO; p.list = g.list;
     p.scores = g.scores; p.partial = g.partial; p.words = g.words;
     p.mask = mask; p.mask_stride = mask_stride;
+    p.gnd = cls_gnd; p.obs = cls_obs; p.cls_stride = cls_stride;
     prof_reset(e);
     HIPCHK(e, g.h_call.send(slot, g.d_call, (size_t)batch, e->stream));
     HIPCHK(e, g.ring.sent(slot, e->stream));

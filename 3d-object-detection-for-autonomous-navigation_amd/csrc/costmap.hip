@@ -7,6 +7,8 @@
 // only transcendental calls are the cos and sin of a footprint's yaw.
 // OBJECT MASK (CostmapParams::mask, NULL while no mask is in force): an in-grid row whose bit is set in the wave's word
 // marks its cell observed and adds no count, as a row outside the z band does.
+// GROUND CLASSES (CostmapParams::obs, NULL while the ground stage does not name this reader): an in-grid row adds to the
+// count iff its OBSTACLE bit is set, in the place of the z band.
 #include "pp_common.h"
 
 namespace {
@@ -121,7 +123,10 @@ __global__ __launch_bounds__(CM_BLOCK) void k_costmap_points(CostmapParams p) {
         // fx >= 0 and floor(fx) < width, the latter as fx < width (the same set, and no integer conversion of a huge value)
         if (fx >= 0.0 && fx < (double)c.width && fy >= 0.0 && fy < (double)c.height) {
             key = (int)fy * p.pitch + (int)fx;
-            zin = c.z_min <= z && z <= c.z_max && !masked;  // a masked row marks its cell observed and adds no count
+            // a masked row marks its cell observed and adds no count; the ground stage's OBSTACLE bit stands in the place
+            // of the z band while it names this reader
+            const bool band = p.obs ? ((p.obs[(size_t)b * p.cls_stride + (i >> 6)] >> lane) & 1ull) != 0ull : (c.z_min <= z && z <= c.z_max);
+            zin = band && !masked;
         }
     }
     // lanes of a run of equal cells (depth-camera rows land in neighbouring cells in runs) add once, through the run's

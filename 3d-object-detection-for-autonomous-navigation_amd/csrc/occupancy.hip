@@ -14,6 +14,9 @@
 // OBJECT MASK (OccParams::mask, NULL while no mask is in force): a row of the hit band whose bit is set in the wave's word
 // is a MASKED end -- a third mark bit, so its cell is listed and gets its ray like any end cell, while k_occ_apply, which
 // reads HIT and GROUND alone, neither hits nor frees it.  A wave covers rows 64 k .. 64 k + 63 of a frame: one word.
+// GROUND CLASSES (OccParams::gnd / obs, NULL while the ground stage does not name this reader): the z <= z_max test and the
+// z >= z_min split are dropped; an in-window, in-range row is a hit iff its OBSTACLE bit is set, a ground return iff its
+// GROUND bit is set, and ignored otherwise.  Two more words per wave.
 #include "pp_common.h"
 
 namespace {
@@ -40,9 +43,18 @@ __global__ __launch_bounds__(OCC_BLOCK) void k_occ_endpoints(OccParams p) {
         const double py = ((q.r1[0] * x + q.r1[1] * y) + q.r1[2] * z) + q.ty;
         // the window index stays a double until it is known to lie in the window (a huge or non-finite value fails here)
         const double gx = floor(px / c.resolution) - (double)q.ox, gy = floor(py / c.resolution) - (double)q.oy;
-        const bool used = gx >= 0.0 && gx < (double)c.width && gy >= 0.0 && gy < (double)c.height &&
-                          (x * x + y * y) <= c.max_range * c.max_range && z <= c.z_max;
-        if (used) code = ((int)gy * p.pitch + (int)gx) * 4 + (z >= c.z_min ? (masked ? 2 : 0) : 1);
+        const bool inwin = gx >= 0.0 && gx < (double)c.width && gy >= 0.0 && gy < (double)c.height &&
+                           (x * x + y * y) <= c.max_range * c.max_range;
+        bool used, hitband;
+        if (p.obs) {                                       // the ground stage's classes in the place of the z band
+            const size_t w = (size_t)b * p.cls_stride + (i >> 6);
+            hitband = ((p.obs[w] >> lane) & 1ull) != 0ull;
+            used = inwin && (hitband || ((p.gnd[w] >> lane) & 1ull) != 0ull);
+        } else {
+            used = inwin && z <= c.z_max;
+            hitband = z >= c.z_min;
+        }
+        if (used) code = ((int)gy * p.pitch + (int)gx) * 4 + (hitband ? (masked ? 2 : 0) : 1);
     }
     // lanes of a run of equal codes (depth-camera rows end in neighbouring cells in runs) mark once, through the run's
     // first lane; every lane of the wave takes part in the shuffle and the ballots

@@ -832,6 +832,7 @@ int pp_destroy(pp_handle e) {
     local_plan_release(e);
     scan_match_release(e);
     object_mask_release(e);
+    ground_release(e);
     frontier_release(e);
     navfn_release(e);
     for (void* p : {(void*)e->h_feed[0], (void*)e->h_feed[1], (void*)e->h_train_losses, (void*)e->h_dets, (void*)e->h_ndets, (void*)e->proj.h_bbox, (void*)e->metrics.h_counts})

@@ -716,6 +716,9 @@ struct CostmapParams {
     int* tap;                      // [batch][height * pitch] the counts
     const unsigned long long* mask;    // the object mask's words [batch][mask_stride], or NULL: no row is masked
     int mask_stride;
+    const unsigned long long* gnd;     // the ground stage's GROUND and OBSTACLE words [batch][cls_stride] each, or both NULL:
+    const unsigned long long* obs;     // the fixed z band decides
+    int cls_stride;
 };
 void launch_costmap(const CostmapParams& p, hipStream_t s);
 
@@ -752,6 +755,9 @@ struct OccParams {
     const int8_t* table;           // [l_max - l_min + 1]
     const unsigned long long* mask;    // the object mask's words [batch][mask_stride], or NULL: no row is masked
     int mask_stride;
+    const unsigned long long* gnd;     // the ground stage's GROUND and OBSTACLE words [batch][cls_stride] each, or both NULL:
+    const unsigned long long* obs;     // the fixed z band decides
+    int cls_stride;
 };
 void launch_occupancy(const OccParams& p, hipStream_t s);
 
@@ -906,6 +912,9 @@ struct ScanParams {
     int* words;                    // [batch][PP_SCAN_RESULT]
     const unsigned long long* mask;    // the object mask's words [batch][mask_stride], or NULL: no row is masked
     int mask_stride;
+    const unsigned long long* gnd;     // the ground stage's GROUND and OBSTACLE words [batch][cls_stride] each, or both NULL:
+    const unsigned long long* obs;     // the fixed z band decides
+    int cls_stride;
 };
 void launch_scan_match(const ScanParams& p, hipStream_t s);         // info and marks cleared before it
 
@@ -944,6 +953,34 @@ struct OmParams {
     int stride;
 };
 void launch_object_mask(const OmParams& p, hipStream_t s);
+
+// ground.hip: per resident frame one plane z = a x + b y + c by RANSAC, per row a class from its vertical residual
+// (pp_set_ground, pp_ground_points; ground.py states the rule and the order of every operation).  One hypothesis of a
+// frame's table: 32 bytes, read by every lane of a wave at one LDS address (a broadcast)
+struct GrHyp {
+    double a, b, c;
+    int valid, pad;                // pad: the record's k
+};
+struct GrParams {
+    pp_ground_config cfg;
+    int batch, F;
+    int max_n;                     // the host's bound on the rows of a frame
+    int K;                         // cfg.hypotheses
+    const float* points;           // the resident rows [.][F]
+    const int* offsets;            // [batch + 1] device values
+    const unsigned* triples;       // [batch][K][3]
+    GrHyp* hyp;                    // [batch][K]
+    GrHyp* chyp;                   // [batch][K]: the valid records of a frame in order of k, back to back, k in `pad`; info[4] of them
+    int* counts;                   // [batch][K]
+    long long* sums;               // [batch][PP_GROUND_SUMS]
+    double* plane;                 // [batch][3]: the winner's (or the fallback) plane after the pick, the final one after the refit
+    int* info;                     // [batch][PP_GROUND_INFO]
+    unsigned long long* gnd;       // [batch][stride]; every run writes words 0 .. 4 * ceil(max_n / 256) - 1 of a frame
+    unsigned long long* obs;       // [batch][stride]
+    int stride;
+};
+void launch_ground(const GrParams& p, hipStream_t s);
+int ground_launches(const GrParams& p);      // the launches launch_ground queues
 
 // frontier.hip: int8 OccupancyGrids -> the clusters of their frontier cells, ranked (pp_set_frontier, pp_frontier_grids;
 // frontier.py states the rule)

@@ -6,7 +6,7 @@
 // api_metrics.hip: the training metrics' counts; api_publish.hip: a trainer's weights into the detector, on the device;
 // api_track.hip: the per-stream track tables behind the detector's post-process; api_sweeps.hip: the per-stream sweep rings
 // in front of the pass; api_costmap.hip: the obstacle grid per frame behind it; api_occupancy.hip: the rolling occupancy
-// map per stream; api_inflate.hip: obstacle inflation behind either grid; api_navfn.hip: the navigation function over the inflated grid; api_local_plan.hip: the local planner over that grid and its field; api_object_mask.hip: the per-point object mask in front of the three readers of the resident rows.  pp_ring.h: the pinned call ring and the stages' memory owner, which the handle's members are made of.
+// map per stream; api_inflate.hip: obstacle inflation behind either grid; api_navfn.hip: the navigation function over the inflated grid; api_local_plan.hip: the local planner over that grid and its field; api_object_mask.hip: the per-point object mask in front of the three readers of the resident rows; api_ground.hip: the ground plane and the rows' classes in front of the same readers.  pp_ring.h: the pinned call ring and the stages' memory owner, which the handle's members are made of.
 #pragma once
 
 #include <cmath>
@@ -576,6 +576,31 @@ struct pp_engine {
         int run_words = 0;                 // ... ceil(max_n / 64) of it
         unsigned long long gen = 0;        // ... and the resident_gen it belongs to
     } omask;
+
+    // pp_set_ground: one plane per resident frame and two bits per row, GROUND and OBSTACLE (api_ground.hip).  Plain
+    // launches on the handle's stream; the three readers of the rows take its words through ground_for while they are
+    // named in cfg.consumers.  Nothing of it in PostRule, DetectKey or a captured pass.
+    struct Ground {
+        bool on = false;                   // pp_set_ground gave a configuration and has not taken it back
+        pp_ground_config cfg = {};         // the last configuration given
+        GrHyp* hyp = nullptr;              // [B][PP_GROUND_MAX_HYP]; this and the next eight live as long as the handle (`allocs`)
+        GrHyp* chyp = nullptr;             // [B][PP_GROUND_MAX_HYP]: the valid ones, compacted
+        int* counts = nullptr;             // [B][PP_GROUND_MAX_HYP]
+        long long* sums = nullptr;         // [B][PP_GROUND_SUMS]
+        double* plane = nullptr;           // [B][3]
+        int* info = nullptr;               // [B][PP_GROUND_INFO]
+        unsigned long long* gnd = nullptr; // [B][stride]
+        unsigned long long* obs = nullptr; // [B][stride]
+        unsigned* d_tri = nullptr;         // [B][PP_GROUND_MAX_HYP][3]
+        int stride = 0;                    // 4 * ceil(NMAX / 256): a word per wave of k_ground_class' largest grid
+        CallRing ring;                     // the calls' triples, consumed on the main stream
+        RingArray<unsigned> h_tri;         // [B][PP_GROUND_MAX_HYP][3] per slot
+        int batch = 0;                     // frames of the last run (pp_get_ground; 0: none, or made stale by a new configuration)
+        int run_words = 0;                 // ... ceil(max_n / 64) of it
+        int run_k = 0;                     // ... and its hypotheses
+        unsigned long long gen = 0;        // ... and the resident_gen it belongs to
+        int used = 0;                      // PP_GROUND_* bits: the readers whose last queued run took the classes (ground_for)
+    } ground;
     unsigned long long resident_gen = 0;   // counts the changes of the resident frames (set_resident, a stage call)
     unsigned long long results_gen = 0;    // resident_gen of the last pp_detect_async
 
@@ -750,6 +775,7 @@ int check_navfn_run(pp_engine* e, const char* who, int source);
 void frontier_release(pp_engine* e);                    // api_frontier.hip: what pp_destroy frees of the frontier stage
 void scan_match_release(pp_engine* e);                  // api_scan_match.hip: what pp_destroy frees of the scan match
 void object_mask_release(pp_engine* e);                 // api_object_mask.hip: what pp_destroy frees of the object mask
+void ground_release(pp_engine* e);                      // api_ground.hip: what pp_destroy frees of the ground stage
 int ensure_metrics(pp_engine* e);                       // api_metrics.hip
 void fill_metrics_params(pp_engine* e, int batch, MetricsParams& p);   // ... on the handle's head map and loss.labels
 // ---- api_dataprep.hip: what the fused training steps (api_train.hip) queue ----
@@ -799,6 +825,19 @@ inline int object_mask_for(pp_engine* e, const char* who, int bit, int batch, co
     if (g.batch != batch || g.gen != e->resident_gen)
         return fail(e, PP_ERR_STATE, "%s: the object mask names this stage and holds no mask of the resident frames (pp_object_mask_async first)", who);
     *words = g.words; *stride = g.stride;
+    return PP_OK;
+}
+// The same question for the ground stage's classes (`bit`: the reader's PP_GROUND_* name): *gnd and *obs stay NULL while the
+// stage is off or does not name the reader; a named reader without classes of the resident frames is refused
+inline int ground_for(pp_engine* e, const char* who, int bit, int batch, const unsigned long long** gnd, const unsigned long long** obs,
+                      int* stride) {
+    pp_engine::Ground& g = e->ground;
+    *gnd = nullptr; *obs = nullptr; *stride = 0;
+    if (!g.on || !(g.cfg.consumers & bit)) { g.used &= ~bit; return PP_OK; }
+    if (g.batch != batch || g.gen != e->resident_gen)
+        return fail(e, PP_ERR_STATE, "%s: the ground stage names this stage and holds no classes of the resident frames (pp_ground_async first)", who);
+    *gnd = g.gnd; *obs = g.obs; *stride = g.stride;
+    g.used |= bit;                                         // (pp_ground_used; a later refusal of the same call leaves the run before it, which took them or not)
     return PP_OK;
 }
 // both streams idle: nothing queued reads a stage's tables any more

@@ -21,6 +21,8 @@
 // < 2^30 fits int32.  The log-odds are read with no `known` test: the occupancy state holds 0 wherever a cell is not known.
 // OBJECT MASK (ScanParams::mask, NULL while no mask is in force): a row whose bit is set in the wave's word takes no part
 // and is counted with the ignored rows.
+// GROUND CLASSES (ScanParams::obs, NULL while the ground stage does not name this reader): a row takes part iff its OBSTACLE
+// bit is set, in the place of the z band.
 // BOUNDS.  A lookup outside the window reads cell 0 of the stream and adds 0, so every load lies in the stream's map; the
 // list is written below list_cap only and read below min(count, list_cap); a mark word lies below mark_words because the
 // cell passed the window test.
@@ -65,8 +67,10 @@ __global__ __launch_bounds__(SCAN_ROWS) void k_scan_cells(ScanParams p) {
         const double dy = (q.r1[0] * x + q.r1[1] * y) + q.r1[2] * z;
         // the index stays a double until it is known to lie in the window (a huge or non-finite value fails here)
         const double gx = floor(dx / c.resolution) + (double)(c.width / 2), gy = floor(dy / c.resolution) + (double)(c.height / 2);
+        // the ground stage's OBSTACLE bit in the place of the z band, while it names this reader
+        const bool band = p.obs ? ((p.obs[(size_t)b * p.cls_stride + (i >> 6)] >> lane) & 1ull) != 0ull : (z <= c.z_max && z >= c.z_min);
         const bool used = gx >= 0.0 && gx < (double)c.width && gy >= 0.0 && gy < (double)c.height &&
-                          (x * x + y * y) <= c.max_range * c.max_range && z <= c.z_max && z >= c.z_min;
+                          (x * x + y * y) <= c.max_range * c.max_range && band;
         if (used && !masked) cell = (int)gy * c.width + (int)gx;          // a masked row takes no part: ignored
     }
     // lanes of a run of equal cells mark once, through the run's first lane; every lane of the wave takes part in the

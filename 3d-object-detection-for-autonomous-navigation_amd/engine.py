@@ -24,6 +24,7 @@ from . import local_planner as _loc
 from . import scan_match as _scan
 from . import frontier as _fr
 from . import object_mask as _om
+from . import ground as _gr
 from .anchors import build_anchor_cells, build_anchors
 from .config import Derived
 from .weights import check_weights
@@ -1123,9 +1124,13 @@ class Engine:
         self._check(self._lib.pp_get_costmaps(self._h, _ptr(grid), _ptr(cnt), B), "pp_get_costmaps")
         return (grid[:B], cnt[:B]) if counts else grid[:B]
 
-    def costmap_info(self):
-        """Per frame of the last costmap run (waits for it), int32 [B] each: `points_in_grid`, `footprints`."""
-        return self._stage_info("pp_costmap_info", ("points_in_grid", "footprints"), getattr(self, "_costmap_batch", 0))
+    def costmap_info(self, classes=False):
+        """Per frame of the last costmap run (waits for it), int32 [B] each: `points_in_grid`, `footprints`.  classes=True:
+        a third key, `classes`, True when the ground stage's classes stood in the place of the z band in that run."""
+        info = self._stage_info("pp_costmap_info", ("points_in_grid", "footprints"), getattr(self, "_costmap_batch", 0))
+        if classes:
+            info["classes"] = self._ground_used("costmap")
+        return info
 
     # ---- rolling occupancy map per stream (pp_set_occupancy, pp_occupancy_update_async, pp_get_occupancy; occupancy.py states the rule; DESIGN 7.1u) ----
     def set_occupancy(self, cfg):
@@ -1188,14 +1193,17 @@ class Engine:
         self._check(self._lib.pp_get_occupancy(self._h, _ptr(grid), _ptr(lo), _ptr(org), B), "pp_get_occupancy")
         return (grid[:B], org[:B], lo[:B]) if logodds else (grid[:B], org[:B])
 
-    def occupancy_info(self, masked=False):
+    def occupancy_info(self, masked=False, classes=False):
         """Per frame of the last occupancy update (waits for it), int32 [B] each: rows `hits`, `ground`, `ignored`;
         `cells_hit`, `cells_free` (passed and not hit); `cleared`, the cells of the new window the old one did not hold.
-        masked=True: a seventh key, `masked`, the rows the object mask turned from hits into masked ends."""
+        masked=True: a seventh key, `masked`, the rows the object mask turned from hits into masked ends.  classes=True:
+        the key `classes`, True when the ground stage's classes stood in the place of the z band in that update."""
         keys = ("hits", "ground", "ignored", "cells_hit", "cells_free", "cleared")
         info = self._stage_info("pp_occupancy_info", keys, getattr(self, "_occ_batch", 0))
         if masked:
             info.update(self._stage_info("pp_occupancy_masked", ("masked",), getattr(self, "_occ_batch", 0)))
+        if classes:
+            info["classes"] = self._ground_used("occupancy")
         return info
 
     def occupancy_reset(self, stream=None):
@@ -1245,14 +1253,18 @@ class Engine:
         self._check(self._lib.pp_scan_match_async(self._h, _ptr(P), B), "pp_scan_match_async")
         self._scan_run = (B, c, oc, P.copy())                   # (what scan_match_poses corrects, and by what)
 
-    def scan_match_results(self, scores=False):
+    def scan_match_results(self, scores=False, classes=False):
         """words int32 [B, 8] (scan_match.WORDS: status, dx, dy, dt in steps, best, prior, n_scan, ignored) of the last
-        scan_match_async (waits for it); scores=True: (words, scores int32 [B, candidates])."""
+        scan_match_async (waits for it); scores=True: (words, scores int32 [B, candidates]); classes=True: one more value
+        at the end, True when the ground stage's classes stood in the place of the z band in that match."""
         B, c = (self._scan_run[0], self._scan_run[1]) if getattr(self, "_scan_run", None) else (0, None)
         words = np.zeros((max(B, 1), _lib.PP_SCAN_RESULT), np.int32)
         sc = np.zeros((max(B, 1), c.candidates if c else 1), np.int32) if scores else None
         self._check(self._lib.pp_get_scan_match(self._h, _ptr(words), _ptr(sc), B), "pp_get_scan_match")
-        return (words[:B], sc[:B]) if scores else words[:B]
+        out = (words[:B], sc[:B]) if scores else (words[:B],)
+        if classes:
+            out = out + (self._ground_used("scan_match"),)
+        return out if len(out) > 1 else out[0]
 
     def scan_match_poses(self):
         """The corrected poses float64 [B, 3, 4] of the last scan_match_async (waits for it): scan_match.corrected_pose of
@@ -1320,6 +1332,76 @@ class Engine:
         self._check(self._lib.pp_get_object_mask(self._h, _ptr(words), _ptr(info), B), "pp_get_object_mask")
         masks = [_om.unpack_words(words[b], info[b, 2]) for b in range(B)]
         return masks, {k: info[:B, i].copy() for i, k in enumerate(_om.INFO)}
+
+    # ---- ground plane per frame and the rows' classes in front of the same three readers (pp_set_ground, pp_ground_async, pp_get_ground; ground.py states the rule) ----
+    def set_ground(self, cfg):
+        """A ground.GroundConfig, a dict of its fields or True (the defaults): `ground_async()` then fits one plane
+        z = a x + b y + c per resident frame by RANSAC on the GPU and classifies every row by its vertical residual, and
+        the stages named in `consumers` -- occupancy_update_async, scan_match_async (so localize), costmap_async -- use
+        the classes in the place of their fixed z band, as ground.py states.  A named stage refuses to run without
+        classes of the resident frames.  None: off (the default), and every launch, buffer and result of the other stages
+        is what it was."""
+        if cfg is None or cfg is False:
+            self._check(self._lib.pp_set_ground(self._h, None), "pp_set_ground")
+            return
+        c = _gr.GroundConfig.from_any(cfg)
+        _gr.check_refine(c, self.max_points_per_frame)
+        if getattr(self, "_ground_drawn", None) != (c.seed, c.hypotheses):
+            self._ground_drawn, self._ground_call = (c.seed, c.hypotheses), 0      # another stream of triples: its call index starts at 0
+        self._check(self._lib.pp_set_ground(self._h, ctypes.byref(_to_struct(_lib.PPGroundConfig, c))), "pp_set_ground")
+
+    @property
+    def ground_config(self):
+        """The GroundConfig in force, or None while the stage is off."""
+        on, pc = self._stage_config("pp_get_ground_config", _lib.PPGroundConfig)
+        return _from_struct(_gr.GroundConfig, pc) if on else None
+
+    def _ground_used(self, reader):
+        """Whether the reader's last queued run took the classes in the place of its z band (pp_ground_used)."""
+        bits = ctypes.c_int32(0)
+        self._check(self._lib.pp_ground_used(self._h, ctypes.byref(bits)), "pp_ground_used")
+        return bool(bits.value & _gr.CONSUMERS[reader])
+
+    def ground_async(self, triples=None):
+        """Queues the fit and the classes of the resident frames behind whatever the engine's stream holds
+        (pp_ground_async) and returns at once.  triples: uint32 [B, K, 3], or None: ground.draw_triples(seed, call_index,
+        B, K), call_index counting this engine's drawn calls under this seed and K (a set_ground that gives the same seed and K
+        again does not start it over, so a caller that re-sends its configuration every cycle still draws new triples)."""
+        c = self.ground_config
+        if c is None:
+            raise RuntimeError("ground_async: the ground stage is not configured (set_ground first)")
+        B = self._batches()[0]
+        if triples is None:
+            t = _gr.draw_triples(c.seed, getattr(self, "_ground_call", 0), max(B, 1), c.hypotheses)
+        else:
+            t = np.ascontiguousarray(triples)
+            if t.dtype != np.uint32 or t.shape != (B, c.hypotheses, 3):
+                raise ValueError(f"ground_async: triples must be uint32 [{B}, {c.hypotheses}, 3], got {t.dtype} {t.shape}")
+        self._check(self._lib.pp_ground_async(self._h, _ptr(t), B), "pp_ground_async")
+        if triples is None:
+            self._ground_call = getattr(self, "_ground_call", 0) + 1
+        self._ground_k = c.hypotheses
+
+    def ground(self, batch=None, bits=False, debug=False):
+        """(planes float64 [B, 3] = a b c, info) of the last ground_async (waits for it); info a dict of int32 [B] each
+        (ground.INFO).  bits=True: two more values, the GROUND and the OBSTACLE flags, each a list of B bool arrays, one
+        flag per row.  debug=True: two more at the end, the refit's sums int64 [B, 9] (ground.SUMS) and the hypotheses'
+        counts int32 [B, K].  Raises when none has run, or when the frames it belongs to have been replaced since."""
+        nb, wpf = ctypes.c_int32(0), ctypes.c_int32(0)
+        self._check(self._lib.pp_ground_shape(self._h, ctypes.byref(nb), ctypes.byref(wpf)), "pp_ground_shape")
+        B = int(batch) if batch is not None else int(nb.value)
+        n1, w1 = max(B, 1), max(int(wpf.value), 1)
+        planes, info = np.zeros((n1, 3), np.float64), np.zeros((n1, _lib.PP_GROUND_INFO), np.int32)
+        gw, ow = (np.zeros((n1, w1), np.uint64), np.zeros((n1, w1), np.uint64)) if bits else (None, None)
+        sums = np.zeros((n1, _lib.PP_GROUND_SUMS), np.int64) if debug else None
+        counts = np.zeros((n1, getattr(self, "_ground_k", 1)), np.int32) if debug else None
+        self._check(self._lib.pp_get_ground(self._h, _ptr(planes), _ptr(info), _ptr(gw), _ptr(ow), _ptr(sums), _ptr(counts), B), "pp_get_ground")
+        out = (planes[:B], {k: info[:B, i].copy() for i, k in enumerate(_gr.INFO)})
+        if bits:
+            out += ([_gr.unpack_words(gw[b], info[b, 11]) for b in range(B)], [_gr.unpack_words(ow[b], info[b, 11]) for b in range(B)])
+        if debug:
+            out += (sums[:B], counts[:B])
+        return out
 
     # ---- obstacle inflation behind either grid (pp_set_inflation, pp_inflate_async, pp_get_inflated; inflation.py states the rule; DESIGN 7.1y) ----
     @staticmethod

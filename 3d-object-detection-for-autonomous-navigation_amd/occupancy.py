@@ -48,7 +48,9 @@ it never feeds back into the log-odds.  OBJECT MASK (object_mask.py; update(...,
 its cell, not a hit.  Every cell with a hit, ground or masked end still gets its one ray; a cell whose only ends are
 masked is neither hit nor passed by its own ray (another ray may pass it), and a hit from an unmasked row in the same
 cell still wins.  The free space in front of an object is kept, the object itself leaves nothing.  Without a mask the
-rule is what it was.
+rule is what it was.  GROUND CLASSES (ground.py; update(..., ground=)): the z <= z_max test and the z >= z_min split are
+dropped; an in-window, in-range row is a HIT iff OBSTACLE, a GROUND return iff GROUND and ignored otherwise, and an
+object-mask bit still turns a hit into a masked end.  Without them the rule is what it was.
 
 Out of scope: decay over time, 3D voxels, clipping rays that leave the window
 (rows that end outside it are ignored, and counted), any ROS import.
@@ -184,11 +186,13 @@ def window_origin(cfg, pose):
     return tuple(out)
 
 
-def end_cells(cfg, points, pose, origin_cell, mask=None):
+def end_cells(cfg, points, pose, origin_cell, mask=None, ground=None):
     """Step 2 for one frame: (hit bool [H, W], ground bool [H, W], (rows that hit, ground rows, ignored rows)) of rows
     float32 [n, F >= 3] under pose [3, 4] in the window whose origin cell is `origin_cell`.  With mask bool [n] (the
     object mask of the rows): (hit, ground, masked-end bool [H, W], (rows that hit, ground rows, ignored rows, masked
-    rows)) -- a masked row of the hit band is a masked end and no hit."""
+    rows)) -- a masked row of the hit band is a masked end and no hit.  With ground = (ground bool [n], obstacle bool [n])
+    (the rows' classes, ground.py) the z tests are dropped: an in-window, in-range row is used iff it has one of the two
+    bits, and lies in the hit band iff OBSTACLE."""
     c = OccupancyConfig.from_any(cfg)
     p, P = np.asarray(points), np.asarray(pose, np.float64)
     W, H = c.width, c.height
@@ -199,9 +203,15 @@ def end_cells(cfg, points, pose, origin_cell, mask=None):
         py = ((P[1, 0] * x + P[1, 1] * y) + P[1, 2] * z) + P[1, 3]
         gx = np.floor(px / c.resolution) - float(ox)
         gy = np.floor(py / c.resolution) - float(oy)
-        used = ((gx >= 0) & (gx < W) & (gy >= 0) & (gy < H) & ((x * x + y * y) <= c.max_range * c.max_range)
-                & (z <= c.z_max))
-        is_hit = used & (z >= c.z_min)
+        inwin = (gx >= 0) & (gx < W) & (gy >= 0) & (gy < H) & ((x * x + y * y) <= c.max_range * c.max_range)
+        if ground is None:
+            used = inwin & (z <= c.z_max)
+            is_hit = used & (z >= c.z_min)
+        else:
+            from . import ground as _gr
+            g_bit, o_bit = _gr.check_classes(ground, len(p), "occupancy")
+            used = inwin & (g_bit | o_bit)
+            is_hit = used & o_bit
     is_ground = used & ~is_hit
     if mask is not None:
         m = np.asarray(mask, bool).reshape(-1)
@@ -290,10 +300,11 @@ class OccupancyMap:
         self._L, self._known, self.origin_cell = L, known, new
         return W * H - kept
 
-    def update(self, points, pose, mask=None):
+    def update(self, points, pose, mask=None, ground=None):
         """One frame.  Returns the info dict: rows `hits`, `ground`, `ignored`; `cells_hit`, `cells_free` (passed and not
         hit); `cleared`, the cells of the new window the old one did not hold (all of them at the first update).  mask:
-        bool [n], the rows' object mask (object_mask.py) -- the dict then also counts the `masked` rows."""
+        bool [n], the rows' object mask (object_mask.py) -- the dict then also counts the `masked` rows.  ground: the pair
+        (ground bool [n], obstacle bool [n]) of the rows' classes (ground.py), in the place of the z band."""
         c = self.cfg
         p = np.asarray(points)
         if p.dtype != np.float32 or p.ndim != 2 or p.shape[1] < 3:
@@ -302,13 +313,13 @@ class OccupancyMap:
         W, H = c.width, c.height
         cleared = self._move_window(window_origin(c, P))
         if mask is None:
-            hit, ground, rows = end_cells(c, p, P, self.origin_cell)
-            ends = hit | ground
+            hit, gnd, rows = end_cells(c, p, P, self.origin_cell, None, ground)
+            ends = hit | gnd
         else:
-            hit, ground, masked, rows = end_cells(c, p, P, self.origin_cell, mask)
-            ends = hit | ground | masked
+            hit, gnd, masked, rows = end_cells(c, p, P, self.origin_cell, mask, ground)
+            ends = hit | gnd | masked
         ey, ex = np.nonzero(ends)
-        passed = _passed_by_rays(ex, ey, W // 2, H // 2, (H, W)) | ground
+        passed = _passed_by_rays(ex, ey, W // 2, H // 2, (H, W)) | gnd
         delta = np.where(hit, c.l_hit, np.where(passed, -c.l_miss, 0)).astype(np.int32)
         self._L = np.clip(self._L.astype(np.int32) + delta, c.l_min, c.l_max).astype(np.int16)
         self._known |= hit | passed

@@ -50,7 +50,8 @@ restatement writes the `known` test out; `scan_match_grids` zeroes L where not k
 
 OBJECT MASK (object_mask.py; scan_cells_np / match_np(..., mask=)): a row whose mask bit is set takes no part in step 1
 and is counted with the ignored rows, so a person close to the sensor contributes no scan cell.  Without a mask the rule
-is what it was.
+is what it was.  GROUND CLASSES (ground.py; scan_cells_np / match_np(..., ground=)): a row takes part iff its class is
+OBSTACLE (and it is not object-masked), in the place of the z band.
 
 Out of scope: multi-resolution branch and bound, sub-cell refinement, a covariance from the score volume, loop closure,
 any correction of roll, pitch or z.  (No longer in that list: removing tracked objects' points from the scan, which is
@@ -136,10 +137,11 @@ class ScanMatchConfig:
         raise ValueError(f"scan_match: a ScanMatchConfig, a dict of its fields or True, got {cfg!r}")
 
 
-def scan_cells_np(occ_cfg, points, pose, mask=None):
+def scan_cells_np(occ_cfg, points, pose, mask=None, ground=None):
     """Step 1 for one frame: (cells int64 [n_scan, 2] = (ux, uy) in ascending (gy, gx), (rows used, rows ignored,
     n_scan)) of rows float32 [n, F >= 3] under the rotation of pose [3, 4].  mask: bool [n], the rows' object mask
-    (object_mask.py) -- a masked row takes no part and is counted with the ignored rows."""
+    (object_mask.py) -- a masked row takes no part and is counted with the ignored rows.  ground: the pair (ground bool [n],
+    obstacle bool [n]) of the rows' classes (ground.py) -- OBSTACLE stands in the place of the z band."""
     c = _occ.OccupancyConfig.from_any(occ_cfg)
     p, P = np.asarray(points), np.asarray(pose, np.float64)
     if p.dtype != np.float32 or p.ndim != 2 or p.shape[1] < 3:
@@ -151,8 +153,12 @@ def scan_cells_np(occ_cfg, points, pose, mask=None):
         dy = (P[1, 0] * x + P[1, 1] * y) + P[1, 2] * z
         gx = np.floor(dx / c.resolution) + float(W // 2)
         gy = np.floor(dy / c.resolution) + float(H // 2)
-        used = ((gx >= 0) & (gx < W) & (gy >= 0) & (gy < H) & ((x * x + y * y) <= c.max_range * c.max_range)
-                & (z <= c.z_max) & (z >= c.z_min))
+        if ground is None:
+            band = (z <= c.z_max) & (z >= c.z_min)
+        else:
+            from . import ground as _gr
+            band = _gr.check_classes(ground, len(p), "scan_match")[1]
+        used = (gx >= 0) & (gx < W) & (gy >= 0) & (gy < H) & ((x * x + y * y) <= c.max_range * c.max_range) & band
     if mask is not None:
         m = np.asarray(mask, bool).reshape(-1)
         if m.shape != (len(p),):
@@ -243,7 +249,7 @@ def best_np(scores, cfg, n_scan, ignored, status=0):
     return np.array([status, ddx, ddy, ddt, best, int(s[centre]), int(n_scan), int(ignored)], np.int32)
 
 
-def match_grid_np(occ_cfg, logodds, known, origin_cell, points, pose, cfg, mask=None):
+def match_grid_np(occ_cfg, logodds, known, origin_cell, points, pose, cfg, mask=None, ground=None):
     """Steps 1 .. 4 on a map given as arrays: logodds int16 [H, W], known bool [H, W], origin_cell (ox, oy) or None (no
     map) -> (words int32 [8], scores int64 [candidates]).  mask as scan_cells_np takes it."""
     oc = _occ.OccupancyConfig.from_any(occ_cfg)
@@ -252,7 +258,7 @@ def match_grid_np(occ_cfg, logodds, known, origin_cell, points, pose, cfg, mask=
     if L.shape != (oc.height, oc.width) or K.shape != L.shape:
         raise ValueError(f"scan_match: logodds and known must be [{oc.height}, {oc.width}], got {L.shape} and {K.shape}")
     P = _swp.check_poses(np.asarray(pose, np.float64)[None], 1)[0]
-    cells, (_, ignored, n_scan) = scan_cells_np(oc, points, P, mask)
+    cells, (_, ignored, n_scan) = scan_cells_np(oc, points, P, mask, ground)
     status, sensor = 0, (0, 0)
     if origin_cell is None:
         status = NO_MAP
@@ -264,10 +270,10 @@ def match_grid_np(occ_cfg, logodds, known, origin_cell, points, pose, cfg, mask=
     return best_np(scores, cfg, n_scan, ignored, status), scores
 
 
-def match_np(occupancy_map, points, pose, cfg, mask=None):
+def match_np(occupancy_map, points, pose, cfg, mask=None, ground=None):
     """Steps 1 .. 4 against an occupancy.OccupancyMap as it stands -> (words int32 [8], scores int64 [candidates])."""
     m = occupancy_map
-    return match_grid_np(m.cfg, m._L, m._known, m.origin_cell, points, pose, cfg, mask)
+    return match_grid_np(m.cfg, m._L, m._known, m.origin_cell, points, pose, cfg, mask, ground)
 
 
 def corrected_pose(pose, words, occ_cfg, cfg):

@@ -83,6 +83,12 @@ class VoxelNet:
         frames' poses and dt, or behind the pass without either.  Returns nothing; engine.object_mask() fetches the bits."""
         return self.engine.object_mask_async(poses, dt)
 
+    def ground(self, triples=None):
+        """Engine.ground_async on the resident frames (engine.set_ground first): behind the upload or ingest and in front of
+        object_mask and localize, and again behind a crop or the sweeps.  Returns nothing; engine.ground() fetches the
+        planes, the info words and the bits."""
+        return self.engine.ground_async(triples)
+
     def occupancy_maps(self, batch=None, logodds=False):
         """Engine.occupancy_maps of the last occupancy_update."""
         return self.engine.occupancy_maps(batch, logodds)

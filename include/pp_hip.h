@@ -77,7 +77,9 @@ extern "C" {
  * PP_OBJMASK_SCAN_MATCH, PP_OBJMASK_COSTMAP, pp_object_mask_config, pp_set_object_mask, pp_get_object_mask_config,
  * pp_object_mask_async, pp_object_mask_shape, pp_get_object_mask, pp_occupancy_masked, pp_object_mask_points (declared
  * behind pp_frontier_grids: the stage reads what a pass and its tracking step leave, and the three readers of the
- * resident rows read its bits). */
+ * resident rows read its bits).  Then PP_GROUND_MAX_HYP, PP_GROUND_INFO, PP_GROUND_OCCUPANCY, PP_GROUND_SCAN_MATCH,
+ * PP_GROUND_COSTMAP, pp_ground_config, pp_set_ground, pp_get_ground_config, pp_ground_async, pp_ground_used, pp_ground_shape,
+ * pp_get_ground, pp_ground_points (declared behind pp_object_mask_points: the same three readers read its two bit planes). */
 #define PP_ABI_VERSION 4
 
 enum pp_status {
@@ -1820,6 +1822,74 @@ int pp_occupancy_masked(pp_handle h, int32_t* masked, int32_t batch);
 int pp_object_mask_points(int device, const float* points, const int32_t* offsets, int32_t num_features, int32_t batch,
                           const double* footprints, const int32_t* counts, double pad, uint64_t* words,
                           int32_t words_per_frame, int32_t* info);
+
+/* ---- Ground plane per frame (ground.py states the rule and every operation's order): one plane z = a x + b y + c fitted
+ * by RANSAC over K hypotheses, an optional integer least-squares refit over the winner's inliers, and per resident row a
+ * class from its vertical residual r = z - (((a * x) + (b * y)) + c): GROUND |r| <= ground_dist, OBSTACLE ground_dist < r
+ * <= overhead_max, OVERHEAD above, BELOW under -ground_dist, IGNORED for a NaN.  All float64 with + - * / and comparisons,
+ * integer atomics only: two runs give the same bytes, and they are the restatement's.  The three readers of the rows use
+ * the classes in place of their fixed z band while they are named in `consumers`: the occupancy update takes an in-window,
+ * in-range row as a hit iff OBSTACLE and as a ground return iff GROUND, the scan match and the costmap's point layer count
+ * a row iff OBSTACLE (an object-mask bit applies on top, as before).  An opt-in stage of plain launches on the handle's
+ * stream, nothing of it in a captured pass; with the stage off every launch, buffer and result of every other stage is
+ * what it was.  The classes belong to the resident frames they were computed for: any change of them (upload, ingest,
+ * crop, sweeps) makes them stale, and a reader named in `consumers` then answers PP_ERR_STATE until pp_ground_async has
+ * run again. ---- */
+#define PP_GROUND_MAX_HYP 512         /* hypotheses of a frame at most */
+#define PP_GROUND_INFO 12             /* int32 per frame: status (0 ok, 1 fallback), winner (-1: no valid hypothesis), inliers,
+                                       * candidates, valid hypotheses, rows GROUND, OBSTACLE, OVERHEAD, BELOW, IGNORED, refit
+                                       * (1: the refit's plane stands), rows */
+#define PP_GROUND_SUMS 9              /* int64 per frame: N Sx Sy Sz Sxx Sxy Syy Sxz Syz of the refit (zeros when it did not run) */
+enum { PP_GROUND_OCCUPANCY = 1, PP_GROUND_SCAN_MATCH = 2, PP_GROUND_COSTMAP = 4 };   /* bits of `consumers` */
+
+typedef struct pp_ground_config {
+    double max_range;      /* metres, > 0: a candidate row has (x * x + y * y) <= max_range * max_range */
+    double cand_z_max;     /* ... and z <= cand_z_max */
+    double max_slope;      /* >= 0: a plane stands only if (a * a + b * b) <= max_slope * max_slope */
+    double h_min, h_max;   /* ... and h_min <= -c <= h_max */
+    double inlier_dist;    /* >= 0 */
+    double ground_dist;    /* >= 0 */
+    double overhead_max;   /* >= ground_dist */
+    double fallback_c;     /* the plane (0, 0, fallback_c) of a frame without a fit */
+    uint64_t seed;         /* of the caller's generator of triples; kept and returned, never read here */
+    int32_t hypotheses;    /* K, 1 .. PP_GROUND_MAX_HYP */
+    int32_t min_inliers;   /* >= 1 */
+    int32_t refine;        /* 0 / 1; 1 needs max_range <= 64, |cand_z_max| <= 64, max_slope * max_range + max(|h_min|, |h_max|)
+                            * + inlier_dist <= 63 and rows per frame * 2^28 < 2^53: the refit's sums are then exact */
+    int32_t consumers;     /* PP_GROUND_* bits: the stages that read the classes */
+} pp_ground_config;
+
+/* cfg == NULL: the stage off (the default); its buffers are kept.  Otherwise the configuration is validated (PP_ERR_ARG
+ * naming the field); a configuration other than the last makes the last classes stale.  PP_ERR_STATE while a training
+ * step is in flight. */
+int pp_set_ground(pp_handle h, const pp_ground_config* cfg);
+/* *on: 0 / 1; cfg_out (may be NULL): the last configuration given (zeros before the first). */
+int pp_get_ground_config(pp_handle h, int32_t* on, pp_ground_config* cfg_out);
+/* Queues the stage on the resident frames behind whatever the handle's stream holds.  triples uint32 [batch][K][3], K the
+ * configured hypotheses: entry u names row (u * n) >> 32 of its frame of n rows.  Refused before anything is queued, the
+ * last classes staying as they are: PP_ERR_STATE when the stage is off, no frames are resident or a training step is in
+ * flight; PP_ERR_ARG for a NULL triples or a batch that is not the resident one. */
+int pp_ground_async(pp_handle h, const uint32_t* triples, int32_t batch);
+/* *readers: the PP_GROUND_* bits of the readers whose LAST queued run took the classes in the place of its z band
+ * (pp_occupancy_update_async, pp_scan_match_async, pp_costmap_async), as pp_occupancy_masked tells of the object mask: a
+ * bit is set when that call found the stage on, itself named and classes of the resident frames, and cleared when it ran
+ * on its band.  Waits for nothing. */
+int pp_ground_used(pp_handle h, int32_t* readers);
+/* The shape of the last run: *words_per_frame = ceil(max_n / 64) for the longest frame's bound max_n.  Waits for nothing. */
+int pp_ground_shape(pp_handle h, int32_t* batch, int32_t* words_per_frame);
+/* The results of the last pp_ground_async (waits for the stream): planes float64 [batch][3] = a b c; info int32
+ * [batch][PP_GROUND_INFO]; ground_words and obstacle_words uint64 [batch][words_per_frame], bit (i & 63) of word i >> 6
+ * for row i of the frame, zero past the frame's rows; sums int64 [batch][PP_GROUND_SUMS]; counts int32 [batch][K], the
+ * hypotheses' inliers (0 where invalid).  Each may be NULL.  PP_ERR_STATE when none has run or the frames it belongs to
+ * are gone, PP_ERR_ARG when batch is not that run's. */
+int pp_get_ground(pp_handle h, double* planes, int32_t* info, uint64_t* ground_words, uint64_t* obstacle_words, int64_t* sums,
+                  int32_t* counts, int32_t batch);
+/* Without a handle: points [offsets[batch]][num_features >= 3] float32 and offsets [batch + 1] in host memory, triples
+ * [batch][cfg->hypotheses][3] -> the outputs of pp_get_ground (words_per_frame >= ceil(longest frame / 64); each may be
+ * NULL).  `consumers` is not read. */
+int pp_ground_points(int device, const float* points, const int32_t* offsets, int32_t num_features, int32_t batch,
+                     const pp_ground_config* cfg, const uint32_t* triples, double* planes, int32_t* info, uint64_t* ground_words,
+                     uint64_t* obstacle_words, int32_t words_per_frame, int64_t* sums, int32_t* counts);
 
 /* Measurement helper: `reps` device-to-device copies of `bytes` on the handle's stream, timed with HIP events;
  * *gbytes_per_s = read + written bytes per second (what an HBM-bound kernel can reach on this part, next to the
